@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- candidate trajectories / second of the MI355X Frenet planner.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (obstacle preparation -> Frenet state ->
 lattice -> Frenet->Cartesian + checks -> collision -> argmin -> selected paths)
@@ -24,18 +24,21 @@ Workload
 (child `torch.distributed.run`, before this process touches the GPU); under
 `torch.distributed.run` it is a plain rank.
 
-Two timed legs of exactly K steps each (barrier + synchronize on both sides):
-the SERIAL leg (one plan call in flight) yields `serial`, `kernel_ms` and the
-`roofline` of the dominant kernel -- a launch has the GPU to itself there, so
-kernel_ms[dominant] <= serial.ms_per_step -- and the HEADLINE leg (`--overlap`
-plan calls in flight, default 4: how a server keeps batches in flight) yields
-`value` / `ms_per_step`.  `--overlap 1` runs the serial leg only.
+A plain run times the HEADLINE leg only: W warm-up steps, then exactly K timed
+steps (barrier + synchronize on both sides) with `--overlap` plan calls in
+flight (default 4: how a server keeps batches in flight), which yield `value` /
+`ms_per_step`, and prints ONE JSON line on rank 0.  `--dump-outputs DIR` writes
+the records of the last timed step as .npy arrays (see dump_outputs).
 
-Prints ONE JSON line on rank 0 with the extra objects "roofline" (dominant
-kernel, HIP events on its stream inside the timed serial leg), "roofline_issue"
-(VALU issue bound from the committed PMC profile), "roofline_valu" (SURVEY
-8(d)'s nominal brute-force flop count against the fp32 vector peak) and
-"cpu_baseline" (the CPU oracle on this host).
+`--full` adds, in the same line: the SERIAL leg of K steps (one plan call in
+flight) with `serial`, `kernel_ms` and the `roofline` of the dominant kernel --
+a launch has the GPU to itself there, so kernel_ms[dominant] <=
+serial.ms_per_step; `--overlap 1` then runs the serial leg only -- the headline
+leg `--repeats` times (median reported), "roofline_issue" (VALU issue bound
+from the committed PMC profile), "roofline_valu" (SURVEY 8(d)'s nominal
+brute-force flop count against the fp32 vector peak), the parity spot check
+against the oracle, "cpu_baseline" (the CPU oracle on this host), the latency
+rows and the time-major layout's serial leg.
 """
 import argparse
 import hashlib
@@ -149,15 +152,55 @@ def parse_args():
     ap.add_argument("--dyn-layout", choices=("spt", "tsp"), default="spt",
                     help="layout of the obstacle tensors: spt = the reference's [S][P][T][2] (default), tsp = time-major "
                          "[T][S][P][2] as libfot's own resampler can write it (FOT_DYN_LAYOUT_TSP)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: serial leg with per-kernel times and rooflines, repeats of "
+                         "the headline leg, parity against the oracle, CPU baseline, latency rows, the other layout")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="the timed K-step headline leg is run this many times; the line reports the median repeat")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true")
+                    help="--full: the timed K-step headline leg is run this many times; the line reports the median "
+                         "repeat (a plain run times it once)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-latency", action="store_true", help="--full without the latency rows")
     ap.add_argument("--no-parity", action="store_true",
-                    help="timing diagnostics only (FOT_EVAL_ABLATE / FOT_CULL_ABLATE builds give wrong results)")
+                    help="--full without the parity check: timing diagnostics only (FOT_EVAL_ABLATE / FOT_CULL_ABLATE "
+                         "builds give wrong results)")
     ap.add_argument("--cpu-instances", type=int, default=256,
                     help="instances of the same workload timed on the single-thread CPU oracle (~53 ms each)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the last timed step (rank 0's shard) to DIR/<field>.npy")
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, raw, n, n_total, cap=8192):
+    """The fot_result records one plan call handed back, as the arrays a caller reads off them (BatchResult): one
+    float64 array per header field, and the selected path's arrays [instance][sample] over the n_total samples a
+    record can hold, zero past n_keep and for instances without a path.  The record's markers of values that do not
+    exist (cost = inf without a path, frenet0 / ref0 = NaN without a Frenet state: include/fot.h) are zero likewise,
+    so every array is finite; any other non-finite value is an error.  At most `cap` instances (a fixed sample beyond
+    that, about 53 MB at the cap); `instance` holds their indices in the batch."""
+    from integrated_path_planning_amd import _abi
+    rec = np.frombuffer(raw, dtype=np.dtype(_abi.Result), count=n)
+    idx = np.arange(n) if n <= cap else np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+    rec = rec[idx]
+    ok = rec["status"] == _abi.PLAN_OK
+    has_state = (rec["status"] != _abi.PLAN_C2F_FAILED)[:, None]
+    out = {"instance": idx}
+    for f in ("status", "best_index", "n_cand", "n_keep", "stats_valid", "new_last_kappa", "new_prev_s"):
+        out[f] = rec[f]
+    out["cost"] = np.where(ok, rec["cost"], 0.0)                                # (FrenetPath.cost: no path, no cost)
+    out["frenet0"] = np.where(has_state, rec["frenet0"], 0.0)
+    out["ref0"] = np.where(has_state, rec["ref0"], 0.0)
+    out["stats"] = np.where(rec["stats_valid"][:, None] != 0, rec["stats"], 0)   # (None for the caller otherwise)
+    has_path = ok[:, None] & (np.arange(n_total)[None, :] < rec["n_keep"][:, None])
+    for f in _abi.PATH_FIELDS:
+        out["path_" + f] = np.where(has_path, rec[f][:, :n_total], 0.0)
+    for k, v in out.items():
+        if not np.isfinite(v).all():
+            bad = np.flatnonzero(~np.isfinite(v).reshape(len(idx), -1).any(axis=1))
+            raise ValueError(f"--dump-outputs: {k} is not finite for instance(s) {idx[bad][:8].tolist()} "
+                             f"(status {rec['status'][bad][:8].tolist()})")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def self_launch(args):
@@ -314,23 +357,24 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    # ---- serial leg: one plan call in flight; per-kernel HIP events -> kernel_ms, roofline
     n_ov = max(1, min(args.overlap, 4))
-    pg1 = make_pg(2)
-    leg1 = Leg(1, make_planner, dev, bstructs, out_bytes, pg1, rehearse, n_inst, wire_bytes)
-    el1, prof, first1 = leg1.run(args.warmup, args.steps, profile=True)
-    el1 = reduce_max(el1)
-    # the same leg once more without the event pairs around every launch (they cost a few microseconds per kernel)
-    el1_plain, _, _ = leg1.run(2, args.steps, profile=False)
-    el1_plain = reduce_max(el1_plain)
+    if args.full:
+        # ---- serial leg: one plan call in flight; per-kernel HIP events -> kernel_ms, roofline
+        pg1 = make_pg(2)
+        leg1 = Leg(1, make_planner, dev, bstructs, out_bytes, pg1, rehearse, n_inst, wire_bytes)
+        el1, prof, first1 = leg1.run(args.warmup, args.steps, profile=True)
+        el1 = reduce_max(el1)
+        # the same leg once more without the event pairs around every launch (they cost a few microseconds per kernel)
+        el1_plain, _, _ = leg1.run(2, args.steps, profile=False)
+        el1_plain = reduce_max(el1_plain)
     # ---- headline leg
-    if n_ov > 1:
+    if n_ov > 1 or not args.full:
         pg = make_pg(max(2, n_ov))
         leg = Leg(n_ov, make_planner, dev, bstructs, out_bytes, pg, rehearse, n_inst, wire_bytes)
-        # the K-step leg `--repeats` times (W warm-up steps before the first, each repeat bracketed by the barrier +
-        # synchronise of Leg.fence and reduced with MAX over the ranks): the line carries the MEDIAN repeat, min / max beside
+        # the K-step leg once (W warm-up steps before it, bracketed by the barrier + synchronise of Leg.fence and reduced
+        # with MAX over the ranks); --full: `--repeats` times, the line carries the MEDIAN repeat, min / max beside
         runs = []
-        for r_ in range(max(1, args.repeats)):
+        for r_ in range(max(1, args.repeats) if args.full else 1):
             el_, _, first_ = leg.run(args.warmup if r_ == 0 else 0, args.steps, profile=False)
             runs.append((reduce_max(el_), first_))
         elapsed, first = sorted(runs)[(len(runs) - 1) // 2]
@@ -338,10 +382,14 @@ def main():
     else:
         pg, leg, elapsed, first = pg1, leg1, el1, first1
         repeats_ms = [el1 / args.steps * 1e3]
+    if args.dump_outputs and rank == 0:
+        last = leg.count - 1                                    # Leg.fence has synchronised the device
+        dump_outputs(args.dump_outputs, leg.outs[last % leg.n_ov].cpu().numpy(), n_inst,
+                     leg.planners[0].n_total_samples)
 
     # ---- candidates actually generated: one untimed pass per rotation batch, counted from its result records
-    bp = leg1.planners[0]
-    stream = leg1.streams[0]
+    bp = (leg1 if args.full else leg).planners[0]
+    stream = (leg1 if args.full else leg).streams[0]
     torch.cuda.set_stream(stream)                               # everything below (copies, collectives) follows it
     chk = torch.zeros(out_bytes, dtype=torch.uint8, device=dev)
     cand_batch, recs0 = [], None
@@ -362,11 +410,11 @@ def main():
         return int(tot.item())
 
     cand_total = cand_of_leg(first)
-    cand_serial = cand_of_leg(first1)
+    cand_serial = cand_of_leg(first1) if args.full else None
     value = cand_total / elapsed
 
     gathered_ok = None
-    if world > 1:
+    if world > 1 and args.full:
         # one more gathered step on batch 0: every rank's slice of the gathered tensor must hold that rank's records
         assert bp.n_total_samples * 60 + 176 <= wire_bytes
         j, send, recv = pg.slot()
@@ -394,6 +442,35 @@ def main():
         dist.destroy_process_group()
         return
 
+    cfg_name = "config4" if (world == 1 and n_inst == 256) else "config5" if n_inst == 512 else "config4-like"
+    line = {
+        "metric": "candidate trajectories/sec", "value": value, "unit": "candidates/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic" if not rehearse else "synthetic (REHEARSAL of the N>1 control flow on one GPU: not a measurement)",
+        "config": {"workload": "%s: %d ego instances/GPU x 2240-candidate lattice (5 s, dt 0.1 s), "
+                               "20-sample x 30-pedestrian x 51-step fp32 prediction distribution (layout %s), eps=0; "
+                               "%d distinct batches rotated (%.0f MB of obstacle tensors per GPU)"
+                               % (cfg_name, n_inst, "[S][P][T][2]" if args.dyn_layout == "spt" else "[T][S][P][2]", n_rot,
+                                  obstacle_mb),
+                   "instances_per_gpu": n_inst, "instances_total": n_inst * world, "rotation_batches": n_rot,
+                   "plan_calls_in_flight": n_ov, "candidates_per_step": cand_total // args.steps,
+                   "parallelism": "instances sharded over %d GPU(s), RCCL all-gather of %d-byte wire records (fot_result: "
+                                  "%d bytes)" % (world, wire_bytes, _abi.RESULT_BYTES)},
+    }
+
+    def emit(line):
+        print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        emit(line)
+        return
+
+    # ==== --full: everything below measures or checks beside the headline
     # ---- roofline of the dominant kernel (HIP events on its stream, inside the timed serial leg)
     dom = max(prof, key=lambda k: prof[k]["total_ms"])
     dom_ms = prof[dom]["total_ms"] / max(prof[dom]["launches"], 1)
@@ -713,25 +790,10 @@ def main():
         legt.close()
         del dt_, pbt
 
-    cfg_name = "config4" if (world == 1 and n_inst == 256) else "config5" if n_inst == 512 else "config4-like"
-    line = {
-        "metric": "candidate trajectories/sec", "value": value, "unit": "candidates/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+    line.update({
         "repeats": {"n": len(repeats_ms), "ms_per_step": [round(v, 5) for v in repeats_ms], "min": min(repeats_ms),
                     "max": max(repeats_ms), "reported": "median repeat (value, ms_per_step): each repeat is exactly "
                     "`steps` timed steps between a barrier + synchronise on both sides, MAX over the ranks"},
-        "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic" if not rehearse else "synthetic (REHEARSAL of the N>1 control flow on one GPU: not a measurement)",
-        "config": {"workload": "%s: %d ego instances/GPU x 2240-candidate lattice (5 s, dt 0.1 s), "
-                               "20-sample x 30-pedestrian x 51-step fp32 prediction distribution (layout %s), eps=0; "
-                               "%d distinct batches rotated (%.0f MB of obstacle tensors per GPU)"
-                               % (cfg_name, n_inst, "[S][P][T][2]" if args.dyn_layout == "spt" else "[T][S][P][2]", n_rot,
-                                  obstacle_mb),
-                   "instances_per_gpu": n_inst, "instances_total": n_inst * world, "rotation_batches": n_rot,
-                   "plan_calls_in_flight": n_ov, "candidates_per_step": cand_total // args.steps,
-                   "parallelism": "instances sharded over %d GPU(s), RCCL all-gather of %d-byte wire records (fot_result: "
-                                  "%d bytes)" % (world, wire_bytes, _abi.RESULT_BYTES)},
         "layout_tsp_serial": layout_tsp,
         "serial": {"ms_per_step": el1 / args.steps * 1e3, "value": cand_serial / el1, "plan_calls_in_flight": 1,
                    "steps": args.steps, "kernel_ms": kernels,
@@ -740,11 +802,8 @@ def main():
         "kernel_source_hash": src_hash,
         "cpu_baseline": cpu, "latency": latency, "host_api": host_api,
         "parity": {"instances_checked_against_oracle": n_check, "ok": n_check > 0, "all_gather_ok": gathered_ok},
-    }
-    print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    })
+    emit(line)
 
 
 if __name__ == "__main__":

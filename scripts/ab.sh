@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 PK=integrated_path_planning_amd
 cp $PK/libfot.so $PK/libfot_new.so
 run() {
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-latency --no-parity --steps 100 --warmup 10 "$@" | python3 -c "
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-latency --no-parity --steps 100 --warmup 10 "$@" | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$TAG', 'headline %.4f' % d['ms_per_step'], 'serial %.4f' % d['serial']['ms_per_step'], d['serial']['kernel_ms'])"
 }
 for i in 1 2; do

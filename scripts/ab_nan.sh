@@ -10,7 +10,7 @@ if [ -n "$FLAGS" ]; then
   make -C integrated_path_planning_amd/csrc EXTRA="$FLAGS" | grep -v hipcc
 fi
 one() {
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-latency --no-parity --steps 100 --warmup 10 --repeats 3 | python3 -c "
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-latency --no-parity --steps 100 --warmup 10 --repeats 3 | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1 $FLAGS', 'headline', round(d['ms_per_step'],4), 'serial', round(d['serial']['ms_per_step'],4), d['serial']['kernel_ms'])"
 }
 for r in 1 2; do

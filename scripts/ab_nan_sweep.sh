@@ -3,7 +3,7 @@
 set -e
 cd "$(dirname "$0")/.."
 one() {
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-latency --no-parity --steps 100 --warmup 10 --repeats 3 | python3 -c "
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-latency --no-parity --steps 100 --warmup 10 --repeats 3 | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', 'headline', round(d['ms_per_step'],4), 'serial', round(d['serial']['ms_per_step'],4), d['serial']['kernel_ms'])"
 }
 for v in "4 4" "6 4" "10 4" "4 8" "4 2" "4 4"; do

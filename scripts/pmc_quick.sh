@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_quick
 mkdir -p "$OUT"
-timeout -k 10 300 rocprofv3 --pmc ${FOT_PMC:-SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_VMEM_RD SQ_INSTS_LDS} --output-format csv -d "$OUT/sq" -o run -- python3 bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-latency --no-parity --overlap 1 > "$OUT/sq.log" 2>&1
+timeout -k 10 300 rocprofv3 --pmc ${FOT_PMC:-SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_VMEM_RD SQ_INSTS_LDS} --output-format csv -d "$OUT/sq" -o run -- python3 bench.py --full --steps 12 --warmup 3 --no-cpu-baseline --no-latency --no-parity --overlap 1 > "$OUT/sq.log" 2>&1
 python3 - <<PY
 import csv, glob, collections
 acc = collections.defaultdict(lambda: collections.defaultdict(lambda: [0.0, 0]))

@@ -11,7 +11,7 @@ shift || true
 EXTRA="${*:---overlap 1}"
 OUT=gpurun_out/prof_$TAG
 mkdir -p "$OUT"
-ARGS="bench.py --steps 24 --warmup 4 --no-cpu-baseline --no-latency --no-parity $EXTRA"
+ARGS="bench.py --full --steps 24 --warmup 4 --no-cpu-baseline --no-latency --no-parity $EXTRA"
 export FOT_PROFILE_ARGS="$ARGS"
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
