@@ -1,0 +1,572 @@
+"""Obstacles placed at the collision radius, through plan(): the float32 broad phase at its edge.
+
+Every collision decision of plan() first passes k_cull's float32 box, the strips of its entry lists and the two float32
+thresholds of k_evaluate's sink; only the band between the thresholds reaches the reference's float64 test.  Random
+placement (tests/test_gpu_fuzz.py) almost never puts an obstacle in the sliver of the radius where one of these bounds
+could be wrong, so here every obstacle is put there on purpose: at R (1 + delta) from a chosen (candidate, step, circle)
+point, delta in +-{1e-2 .. 1e-7}, which straddles cull_margin's 1 mm slack and both float32 thresholds at every
+coordinate size the scenes reach (a map frame 1.5e4 m from the origin; a lattice of 76 steps reaching 200 m).
+
+Judges, per instance and under every evaluation kernel (EVAL_PATHS):
+  A. the oracle's per-candidate status / keep / n_t tables and record (independent float64 reference);
+  C. fot_debug_margins: every target obstacle with |delta| <= 1e-3 was listed by k_cull for its step (its collision
+     margin on its candidate is |(1 + delta)^2 - 1|, about 2|delta|), independently of the outcome;
+  D. time-major float64 tensors give byte-identical records; float32 tensors match the oracle on the rounded inputs.
+Targets are placed relative to the ORACLE's candidate points, and only at |delta| >= 10 |p_lib - p_oracle| / R (asserted
+per target), so a legitimate float64 re-association between the two cannot flip a decision.
+
+The bounds themselves are properties on the host: tests/test_broadphase_bounds.py.  Each assertion message names scene,
+kind, instance (with its targets), delta, evaluation path and candidate.
+"""
+import numpy as np
+import pytest
+
+import eps_band
+from helpers import EVAL_PATHS, assert_record_matches_oracle, oracle_plan_for_request, set_eval_path
+from integrated_path_planning_amd import _abi
+from integrated_path_planning_amd.batch import PackedBatch, PlanRequest
+from integrated_path_planning_amd.footprint import EgoFootprint
+from integrated_path_planning_amd.planner import BatchPlanner
+from oracle import oracle as orc
+
+pytestmark = pytest.mark.gpu
+
+DELTAS = [s * d for d in (1e-2, 1e-3, 1e-4, 3e-5, 1e-5, 1e-6, 1e-7) for s in (-1.0, 1.0)]
+MG_COLLISION = list(_abi.MARGIN_NAMES).index("collision")
+FAR = 5.0e3                                         # where the rows of a track away from its target step are put
+
+LENIENT = dict(max_accel=30.0, max_curvature=10.0, max_lat_accel=80.0, d_road_w=1.0, max_road_width=3.0,
+               robot_radius=1.0, obstacle_radius=0.3, d_t_s=2.0, k_j=0.1, k_t=0.1, k_d=1.0, k_s_dot=1.0, k_lat=1.0,
+               k_lon=1.0)
+
+
+def straight(th, length, origin=(3.0, -2.0)):
+    t = np.linspace(0.0, length, 12)
+    return origin[0] + t * np.cos(th), origin[1] + t * np.sin(th)
+
+
+def arc(radius=30.0, span=2.4):
+    th = np.linspace(0.0, span, 40)
+    return radius * np.sin(th) + 1.0, radius * (1.0 - np.cos(th)) - 1.0
+
+
+# name -> (waypoints, planner kwargs, ego (s, lateral offset, yaw offset, v, a), target speed)
+SCENES = {
+    "straight": (straight(0.7, 250.0), dict(dt=0.2, min_t=3.0, max_t=4.0, max_speed=25.0), (10.0, 0.3, 0.02, 8.0, 0.0), 10.0),
+    "arc30": (arc(), dict(dt=0.2, min_t=3.0, max_t=4.0, max_speed=25.0), (5.0, -0.2, -0.03, 6.0, 0.3), 7.0),
+    "far": (straight(-2.2, 250.0, origin=(1.5e4, -1.2e4)), dict(dt=0.2, min_t=3.0, max_t=4.0, max_speed=25.0),
+            (10.0, 0.3, 0.02, 8.0, 0.0), 10.0),
+    "long": (straight(0.4, 600.0), dict(dt=0.1, min_t=7.2, max_t=7.5, max_speed=45.0), (5.0, 0.1, 0.0, 28.0, 0.0), 28.0),
+}
+
+
+class Scene:
+    """One reference path and ego, the planner kwargs of one obstacle kind, the obstacle-free lattice of both sides."""
+
+    def __init__(self, name, extra):
+        (wx, wy), skw, (s0, off, dyaw, v, a), self.target = SCENES[name]
+        self.name = name
+        self.kw = dict(LENIENT, **skw, **extra)
+        okw = dict(self.kw)
+        fp = okw.pop("footprint", None)
+        self.offsets = np.zeros(1) if fp is None else np.asarray(fp.offsets, float)
+        if fp is not None:
+            okw["footprint_offsets"], okw["footprint_radius"] = list(fp.offsets), fp.radius
+            self.r = fp.radius + self.kw["obstacle_radius"]
+        else:
+            self.r = self.kw["robot_radius"] + self.kw["obstacle_radius"]
+        self.r_dyn = self.r * self.kw.get("collision_margin_inflation", 1.0)
+        self.params, self.sp = orc.make_params(**okw), orc.Spline(wx, wy)
+        x, y, yaw = (c[0] for c in self.sp.eval([s0])[:3])
+        self.ego = PlanRequest(float(x - np.sin(yaw) * off), float(y + np.cos(yaw) * off), float(yaw + dyaw), v, a,
+                               target_speed=self.target)
+        self.bp = BatchPlanner(waypoints=(wx, wy), **self.kw)
+        self.n_t = int(round(self.kw["max_t"] / self.kw["dt"])) + 1
+        free = oracle_plan_for_request(orc, self.params, self.sp, self.request(), table=True)
+        self.free = free
+        self.frenet0 = free.frenet0
+        # the lattice as the library generates it (all instances share the ego, so instance 0 of any call stands for all)
+        self.bp.plan_batch([self.request()])
+        _, self.lib_status, _, self.lib_nt = self.bp.candidates(0)
+        np.testing.assert_array_equal(self.lib_status, free.cand_status, err_msg=f"{name}: obstacle-free lattice")
+        self._orc_paths, self._lib_paths = {}, {}
+
+    def request(self, **obs):
+        e = self.ego
+        return PlanRequest(e.x, e.y, e.yaw, e.v, e.a, target_speed=e.target_speed, **obs)
+
+    def orc_path(self, c):
+        if c not in self._orc_paths:
+            keep, arr, _ = orc.candidate_path(self.params, self.sp, self.frenet0, self.target, c)
+            self._orc_paths[c] = arr
+        return self._orc_paths[c]
+
+    def lib_path(self, c):
+        if c not in self._lib_paths:
+            fp = self.bp.candidate_path(c, 0)
+            self._lib_paths[c] = np.array([fp.x, fp.y, fp.yaw])
+        return self._lib_paths[c]
+
+    def point(self, c, k, circle):
+        """(oracle point, library point, yaw, lateral offset) of circle `circle` of candidate c at step k."""
+        o, lp = self.orc_path(c), self.lib_path(c)
+        off = self.offsets[circle]
+        po = np.array([o[9, k] + off * np.cos(o[11, k]), o[10, k] + off * np.sin(o[11, k])])
+        pl = np.array([lp[0, k] + off * np.cos(lp[2, k]), lp[1, k] + off * np.sin(lp[2, k])])
+        return po, pl, o[11, k], o[5, k]
+
+    def candidates(self):
+        """The target candidates: the two extreme lateral offsets of the shortest and the longest horizon, the slowest
+        and the fastest terminal speed, two brake-ladder entries -- among those that reach the collision check."""
+        ok = np.flatnonzero(self.free.cand_status == _abi.ST_OK)
+        nt = self.free.cand_nt
+        n_min_t = int(round(self.kw["min_t"] / self.kw["dt"])) + 1
+        grid = ok[nt[ok] >= n_min_t]
+        brake = ok[nt[ok] < n_min_t]
+        out = []
+        for hz in (nt[grid].min(), nt[grid].max()):
+            g = grid[nt[grid] == hz]
+            d_end = np.array([self.orc_path(c)[5, nt[c] - 1] for c in g])
+            out += [int(g[np.argmin(d_end)]), int(g[np.argmax(d_end)])]
+        v_end = np.array([self.orc_path(c)[12, nt[c] - 1] for c in grid])
+        out += [int(grid[np.argmin(v_end)]), int(grid[np.argmax(v_end)])]
+        if len(brake):
+            out += [int(brake[0]), int(brake[-1])]
+        return list(dict.fromkeys(out))
+
+    def steps(self, c):
+        nt = int(self.free.cand_nt[c])
+        ks = [0, 1, 3, 4, 7, 8] + ([63, 64, 65] if self.n_t > 64 else []) + [nt - 1]
+        return sorted({k for k in ks if k < nt})
+
+
+class Target:
+    """One obstacle position: R (1 + delta) from (candidate, step, circle) in direction `u`."""
+
+    def __init__(self, sc, c, k, circle, u_kind, delta, radius):
+        self.c, self.k, self.circle, self.u_kind, self.delta, self.radius = c, k, circle, u_kind, delta, radius
+        self.own_radius = True               # placed at the radius of its own kind (judge C applies)
+        po, pl, yaw, d = sc.point(c, k, circle)
+        dev = float(np.hypot(*(po - pl)))
+        self.floor = max(1e-7, 10.0 * dev / radius)
+        normal = np.array([-np.sin(yaw), np.cos(yaw)]) * (1.0 if d >= 0 else -1.0)
+        u = {"normal": normal, "tangent": np.array([np.cos(yaw), np.sin(yaw)]),
+             "rand0": np.array([np.cos(2.1), np.sin(2.1)]), "rand1": np.array([np.cos(-0.7), np.sin(-0.7)])}[u_kind]
+        self.pos = po + radius * (1.0 + delta) * u
+        # the collision margin fot_debug_margins reports for this obstacle on its candidate: |d^2 - R^2| / R^2, d from
+        # the library's point and the map-frame coordinates rounded to float64
+        self.margin_bound = abs((1.0 + delta) ** 2 - 1.0) + 4.0 * (dev + np.spacing(np.abs(self.pos).max())) / radius \
+            + 1e-12
+
+    def label(self):
+        return f"cand {self.c} step {self.k} circle {self.circle} dir {self.u_kind} delta {self.delta:+.0e}"
+
+
+def targets(sc, radius, circle=0):
+    """Targets over the candidates x steps of the scene, each at every delta of DELTAS above its floor; directions
+    cycling over the (candidate, step) points: outward normal, forward tangent (at a candidate's last step), two fixed
+    random directions."""
+    out = []
+    dirs = ("normal", "rand0", "normal", "rand1")
+    j = 0
+    for c in sc.candidates():
+        for k in sc.steps(c):
+            u = "tangent" if k == sc.free.cand_nt[c] - 1 and j % 2 == 0 else dirs[j % 4]
+            j += 1
+            probe = Target(sc, c, k, circle, u, 0.0, radius)
+            assert probe.floor <= 1e-6, f"{sc.name}: library and oracle points differ by {probe.floor * radius / 10:.3e} m " \
+                                        f"at {probe.label()}"
+            out += [Target(sc, c, k, circle, u, d, radius) for d in DELTAS if abs(d) >= probe.floor]
+    return out
+
+
+def far_point(t):
+    return t.pos + np.array([FAR, -FAR])
+
+
+def track(sc, t, T, row_of=None):
+    """[T, 2] track: the target position at the row step t.k reads (min(k, T-1)), FAR elsewhere."""
+    tr = np.repeat(far_point(t)[None], T, 0) + np.arange(T)[:, None] * 0.01
+    tr[min(t.k, T - 1)] = t.pos
+    return tr
+
+
+# ---- kinds: each returns (requests, per-instance list of its Targets) ------------------------------------------------
+
+def kind_static(sc):
+    ts = targets(sc, sc.r)
+    return [sc.request(static=t.pos[None].copy()) for t in ts], [[t] for t in ts]
+
+
+def kind_dyn(sc, T):
+    """Single tracks of length T; with T < n_t the targets past T - 1 read the held last row."""
+    ts = targets(sc, sc.r_dyn)
+    reqs, meta = [], []
+    for t in ts:
+        if T < sc.n_t and t.k < T - 1 and t.k not in (0, 1):
+            continue                                 # (short tracks: the held last row and the first steps only)
+        reqs.append(sc.request(dyn=track(sc, t, T)[None]))
+        meta.append([t])
+    return reqs, meta
+
+
+def kind_mixed(sc):
+    """A static obstacle at the DYNAMIC radius (between the two radii: a miss only the smaller radius decides) and a
+    dynamic one at its own radius, in one instance."""
+    ts_d = targets(sc, sc.r_dyn)
+    ts_s = targets(sc, sc.r_dyn)
+    reqs, meta = [], []
+    for td, ts_ in zip(ts_d, ts_s[len(ts_s) // 2:] + ts_s[:len(ts_s) // 2]):
+        ts_.own_radius = False
+        reqs.append(sc.request(static=ts_.pos[None].copy(), dyn=track(sc, td, sc.n_t)[None]))
+        meta.append([td, ts_])
+    return reqs, meta
+
+
+def kind_dist(sc, S=20):
+    """S samples of one tensor, two tracks each: the target hit in max_viol and max_viol + 1 distinct samples (at least
+    one), and in one of them twice (both tracks), which counts once."""
+    eps = sc.kw["chance_epsilon"]
+    max_viol = int(np.floor(eps * S))
+    ts = targets(sc, sc.r)
+    reqs, meta = [], []
+    for i, t in enumerate(ts):
+        n_hit = max(1, max_viol) + (i % 2)
+        far = np.repeat(track(sc, t, sc.n_t)[None], 2, 0)
+        far[:, t.k] = far_point(t)
+        dist = np.repeat(far[None], S, 0)
+        dist[:, 1] += np.array([7.0, 3.0])
+        for s in range(n_hit):
+            dist[(3 * s + i) % S, 0, t.k] = t.pos
+        dist[i % S, 1, t.k] = t.pos                  # a second hit in a sample (it may be one of the above)
+        reqs.append(sc.request(dist=dist))
+        meta.append([t])
+    return reqs, meta
+
+
+def kind_footprint(sc):
+    """Static obstacles at the radius from the outermost circle centre."""
+    outer = int(np.argmax(np.abs(sc.offsets)))
+    ts = targets(sc, sc.r, circle=outer)
+    return [sc.request(static=t.pos[None].copy()) for t in ts], [[t] for t in ts]
+
+
+def kind_crowded(sc, one_step=False, n_inst=6):
+    """300-600 near misses each, R (1 + delta) from some candidate point, delta in [floor, 1e-2]: bins, chunk pairs and
+    the float64 re-check fill up.  one_step: all of them at step 3 (a kept list beyond k_cull's 256)."""
+    rng = np.random.default_rng(77 + 1000 * one_step + sorted(SCENES).index(sc.name))
+    cands = sc.candidates()
+    reqs, meta = [], []
+    for i in range(n_inst):
+        n = int(rng.integers(300, 601))
+        pts, ts = [], []
+        for _ in range(n):
+            c = int(rng.choice(cands))
+            k = 3 if one_step else int(rng.integers(0, sc.free.cand_nt[c]))
+            u = ("normal", "rand0", "rand1")[int(rng.integers(0, 3))]
+            probe = Target(sc, c, k, 0, u, 0.0, sc.r)
+            d = float(np.exp(rng.uniform(np.log(max(1e-7, probe.floor)), np.log(1e-2))))
+            t = Target(sc, c, k, 0, u, d, sc.r)
+            pts.append(t.pos)
+            ts.append(t)
+        # probes: near misses 1e-7 .. 1e-6 outside the radius on each target candidate, closer to it than the crowd
+        # comes (judge C applies to those that stay isolated)
+        for c in cands:
+            k = 3 if one_step else int(rng.integers(0, sc.free.cand_nt[c]))
+            probe = Target(sc, c, k, 0, "normal", 0.0, sc.r)
+            t = Target(sc, c, k, 0, "normal", max(probe.floor, float(rng.choice([1e-7, 3e-7, 1e-6]))), sc.r)
+            pts.append(t.pos)
+            ts.append(t)
+        reqs.append(sc.request(static=np.array(pts)))
+        meta.append(ts)
+    return reqs, meta
+
+
+CASES = [
+    ("straight", "static", {}), ("arc30", "static", {}), ("far", "static", {}), ("long", "static", {}),
+    ("straight", "dyn_full", dict(collision_margin_inflation=1.2)),
+    ("long", "dyn_short", dict(collision_margin_inflation=1.2)),
+    ("far", "mixed", dict(collision_margin_inflation=1.2)),
+    ("long", "mixed", dict(collision_margin_inflation=1.2)),
+    ("straight", "dist_eps0", dict(chance_epsilon=0.0)),
+    ("arc30", "dist_eps0.1", dict(chance_epsilon=0.1)),
+    ("arc30", "footprint3", dict(footprint=EgoFootprint.multi_circle(4.6, 1.9, 3))),
+    ("far", "footprint8", dict(footprint=EgoFootprint.multi_circle(4.6, 1.9, 8))),
+    ("straight", "crowded", {}), ("long", "crowded", {}), ("straight", "crowded_one_step", {}),
+]
+
+
+def build(sc, kind):
+    if kind == "static":
+        return kind_static(sc)
+    if kind == "dyn_full":
+        return kind_dyn(sc, sc.n_t + 3)
+    if kind == "dyn_short":
+        return kind_dyn(sc, sc.n_t // 2)
+    if kind == "mixed":
+        return kind_mixed(sc)
+    if kind.startswith("dist"):
+        return kind_dist(sc)
+    if kind.startswith("footprint"):
+        return kind_footprint(sc)
+    return kind_crowded(sc, one_step=kind == "crowded_one_step")
+
+
+def rounded32(rq):
+    """The request with its obstacle tensors rounded to float32 (what a float32 plan call sees)."""
+    r32 = lambda a: None if a is None else np.asarray(a, np.float32).astype(np.float64)
+    return PlanRequest(rq.x, rq.y, rq.yaw, rq.v, rq.a, target_speed=rq.target_speed, static=r32(rq.static),
+                       dyn=r32(rq.dyn), dist=r32(rq.dist))
+
+
+def obstacle_points(rq):
+    """Every obstacle coordinate of a request (static points, every row of every track), [n, 2]."""
+    pts = [np.asarray(a, float).reshape(-1, 2) for a in (rq.static, rq.dyn, rq.dist) if a is not None]
+    return np.concatenate(pts) if pts else np.zeros((0, 2))
+
+
+def isolated(sc, rq, t):
+    """Judge C applies to target t when no OTHER obstacle of the instance comes within t's margin bound of either
+    radius at any point of t's candidate: then a collision margin <= the bound can only come from t itself, so
+    it proves that k_cull listed t (the margin is a minimum over the candidate's listed obstacles)."""
+    if not t.own_radius or abs(t.delta) > 1e-3:
+        return False
+    pts = obstacle_points(rq)
+    pts = pts[~np.all(pts == t.pos, axis=1)]
+    if not len(pts):
+        return True
+    x, y, yaw = sc.lib_path(t.c)
+    cx = (x[:, None] + sc.offsets[None] * np.cos(yaw)[:, None]).ravel()
+    cy = (y[:, None] + sc.offsets[None] * np.sin(yaw)[:, None]).ravel()
+    d2 = (cx[:, None] - pts[None, :, 0]) ** 2 + (cy[:, None] - pts[None, :, 1]) ** 2
+    m = min(np.abs(d2 / (r * r) - 1.0).min() for r in (sc.r, sc.r_dyn))
+    return t.margin_bound < m
+
+
+class Replay:
+    """Re-raises an assertion of one instance with the full list of its targets appended (crowded instances hold
+    hundreds; the short label names the first three)."""
+
+    def __init__(self, ts):
+        self.ts = ts
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, typ, exc, tb):
+        if typ is not None and issubclass(typ, AssertionError) and len(self.ts) > 3:
+            raise AssertionError(f"{exc}\nall {len(self.ts)} targets of the instance: "
+                                 + "; ".join(f"{t.label()} at ({t.pos[0]!r}, {t.pos[1]!r})" for t in self.ts)) from None
+        return False
+
+
+@pytest.mark.parametrize("scene,kind,extra", CASES, ids=[f"{s}-{k}" for s, k, _ in CASES])
+def test_boundary_obstacles_match_the_oracle(scene, kind, extra):
+    sc = Scene(scene, extra)
+    reqs, meta = build(sc, kind)
+    assert len(reqs) >= 6
+    wants = [oracle_plan_for_request(orc, sc.params, sc.sp, rq, table=True) for rq in reqs]
+    wants32 = [oracle_plan_for_request(orc, sc.params, sc.sp, rounded32(rq), table=True) for rq in reqs]
+    # the scene decides something at the boundary: instances with an obstacle inside collide where the obstacle-free
+    # plan did not (crowded scenes hold near misses only)
+    changed = sum(int((w.cand_status != sc.free.cand_status).any()) for w in wants)
+    if not kind.startswith("crowded"):
+        assert changed >= len(reqs) // 5, f"{scene}/{kind}: only {changed} of {len(reqs)} instances change a status"
+    judge_c = [[t for t in ts if isolated(sc, rq, t)] for rq, ts in zip(reqs, meta)]
+    eligible = sum(t.own_radius and abs(t.delta) <= 1e-3 for ts in meta for t in ts)
+    n_c = sum(len(v) for v in judge_c)
+    assert n_c >= (2 * len(reqs) if kind.startswith("crowded") else eligible // 2), \
+        f"{scene}/{kind}: judge C applies to {n_c} of {eligible} near targets only"
+    dyn_any = any(rq.dyn is not None or rq.dist is not None for rq in reqs)
+
+    def label(i, path):
+        return f"{scene}/{kind} inst {i} [{path}] " + "; ".join(t.label() for t in meta[i][:3])
+
+    for path in EVAL_PATHS:
+        set_eval_path(sc.bp, path)
+        res = sc.bp.plan_batch(reqs)
+        for i, want in enumerate(wants):
+            lab = label(i, path)
+            with Replay(meta[i]):
+                _, status, keep, nt = sc.bp.candidates(i)
+                assert len(status) == want.n_cand, lab
+                np.testing.assert_array_equal(nt, want.cand_nt, err_msg=lab)
+                np.testing.assert_array_equal(keep, want.cand_keep, err_msg=lab)
+                eps_band.check_status_table(sc.bp, i, status, want.cand_status, lab)
+                assert_record_matches_oracle(res.records[i], want, label=lab)
+                # C: k_cull listed every isolated near target for its step (margins of the entry lists of this call)
+                m = sc.bp.margins(i)[:, MG_COLLISION]
+                for t in judge_c[i]:
+                    assert m[t.c] <= t.margin_bound, \
+                        f"{lab}: target not listed by k_cull ({t.label()}): collision margin {m[t.c]:.3e}"
+        # D: time-major float64 tensors give the very same records; float32 tensors the oracle's on rounded inputs
+        rec = bytes(res.records)
+        if dyn_any:
+            tsp = sc.bp.plan_packed(PackedBatch(reqs, np.float64, dyn_layout_tsp=True))
+            assert bytes(tsp.records) == rec, f"{scene}/{kind} [{path}]: time-major layout changes the records"
+        f32 = sc.bp.plan_batch(reqs, obstacle_dtype=np.float32)
+        for i, want32 in enumerate(wants32):
+            lab = label(i, f"{path}, float32 tensors")
+            with Replay(meta[i]):
+                _, status, keep, _ = sc.bp.candidates(i)
+                np.testing.assert_array_equal(status, want32.cand_status, err_msg=lab)
+                np.testing.assert_array_equal(keep, want32.cand_keep, err_msg=lab)
+                assert_record_matches_oracle(f32.records[i], want32, label=lab)
+    set_eval_path(sc.bp, "auto")
+    sc.bp.close()
+
+
+# ---- B: the rounding level, the library against its own float64 predicate ---------------------------------------------
+
+# Tier B's floor, in ulps of sq.  The debug path (candidate_path) and the best candidate's record agree bit for bit
+# (asserted), but on hardware the collision points k_evaluate tests are NOT bit-identical to the debug path at every
+# step: with obstacles 0..4 ulps of sq from the debug points, candidate 0 at step 3 of the straight and long scenes was
+# decided against the float64 predicate on those points (0 ulps: no collision where the predicate says hit).  The two
+# computations of a point differ by a few ulps of its coordinates (< 1e-13 m here), i.e. some hundreds of ulps of sq;
+# placements at B_FLOOR_ULPS .. B_FLOOR_ULPS + B_WINDOW ulps on either side leave a margin of several times that.
+B_FLOOR_ULPS = 8192
+B_WINDOW = 64
+
+
+def ulp_placements(p, u, sq, n_side=4, reach=150, floor=B_FLOOR_ULPS, window=B_WINDOW):
+    """Obstacles whose float64 squared distance (dx*dx)+(dy*dy) from p lies floor .. floor + window ulps of sq inside
+    and outside: a 2-D grid of float64 steps around p + sqrt(sq) u, up to n_side distinct values per side, the nearest
+    first.  Returns [(obstacle, ulps)] (fewer where the coordinates' spacing does not allow them)."""
+    j = np.arange(-reach, reach + 1, dtype=float)
+    out = []
+    for sign, lo, hi in ((-1.0, -floor - window, -floor), (1.0, floor, floor + window)):
+        o0 = p + np.sqrt(sq + sign * (floor + window / 2) * np.spacing(sq)) * u
+        ox = (o0[0] + j * np.spacing(o0[0]))[:, None] * np.ones(len(j))[None]
+        oy = np.ones(len(j))[:, None] * (o0[1] + j * np.spacing(o0[1]))[None]
+        dx, dy = p[0] - ox, p[1] - oy
+        ul = ((dx * dx + dy * dy - sq) / np.spacing(sq)).ravel()
+        sel = np.flatnonzero((ul >= lo) & (ul <= hi))
+        seen = set()
+        for f in sel[np.argsort(np.abs(ul[sel]), kind="stable")]:
+            v = int(round(ul[f]))
+            if v not in seen and len(seen) < n_side:
+                seen.add(v)
+                out.append((np.array([ox.ravel()[f], oy.ravel()[f]]), v))
+    return sorted(out, key=lambda a: abs(a[1]))
+
+
+def lib_points(sc):
+    """[n_cand, n_t] x, y of every candidate as the library's debug path gives them (NaN past a candidate's end)."""
+    n = len(sc.lib_status)
+    X = np.full((n, sc.n_t), np.nan)
+    Y = np.full((n, sc.n_t), np.nan)
+    for c in range(n):
+        x, y, _ = sc.lib_path(c)
+        X[c, :len(x)], Y[c, :len(y)] = x, y
+    return X, Y
+
+
+def expected_status(sc, X, Y, keep, static=None, dist=None, max_viol=0):
+    """The obstacle-free status, except that a pending candidate (status OK before the collision check) becomes
+    COLLISION exactly when numpy's (dx*dx)+(dy*dy) <= sq on the library's own points says so -- the static obstacles
+    as hard constraints, the samples of a distribution counted once each against max_viol (oracle/fot_oracle.c)."""
+    st = sc.lib_status.copy()
+    pend = np.flatnonzero(st == _abi.ST_OK)
+    ks = np.arange(sc.n_t)
+    live = ks[None, :] < keep[pend][:, None]
+    sq = sc.r * sc.r
+    hit = np.zeros(len(pend), bool)
+    for o in (np.zeros((0, 2)) if static is None else static):
+        dx, dy = X[pend] - o[0], Y[pend] - o[1]
+        hit |= ((dx * dx + dy * dy <= sq) & live).any(1)
+    if dist is not None:
+        S, P, T = dist.shape[:3]
+        rows = np.minimum(ks, T - 1)
+        viol = np.zeros(len(pend), int)
+        for s_ in range(S):
+            hs = np.zeros(len(pend), bool)
+            for p_ in range(P):
+                o = dist[s_, p_, rows]
+                dx, dy = X[pend] - o[None, :, 0], Y[pend] - o[None, :, 1]
+                hs |= ((dx * dx + dy * dy <= sq) & live).any(1)
+            viol += hs
+        hit |= viol > max_viol
+    st[pend[hit]] = _abi.ST_COLLISION
+    return st
+
+
+B_CASES = [("straight", "static", {}), ("long", "static", {}), ("straight", "dist_eps0.1", dict(chance_epsilon=0.1))]
+
+
+@pytest.mark.parametrize("scene,kind,extra", B_CASES, ids=[f"{s}-{k}" for s, k, _ in B_CASES])
+def test_rounding_level_hits_match_the_library_predicate(scene, kind, extra):
+    """Obstacles B_FLOOR_ULPS .. + B_WINDOW ulps of sq (about 1e-12 relative) inside and outside the library's own
+    candidate points: far below the reach of any float32 bound, so every such pair is decided by the float64 re-check of
+    k_evaluate's sink (exact_chunk_f32first).
+    Each candidate's status must be what the float64 predicate of collide_candidate says on the same points, under every
+    evaluation kernel; the exact path without a broad phase (paths_collision_free) must agree."""
+    sc = Scene(scene, extra)
+    # precondition: the debug path is the evaluation's path, bit for bit (the best candidate against its record)
+    res = sc.bp.plan_batch([sc.request()])
+    rec = res.records[0]
+    assert rec.status == 0, f"{scene}/{kind}: the obstacle-free plan fails"
+    x, y, _ = sc.lib_path(rec.best_index)
+    n = rec.n_keep
+    for f, v in (("x", x), ("y", y)):
+        got = np.ctypeslib.as_array(getattr(rec, f))[:n]
+        assert np.array_equal(got, v[:n]), \
+            f"{scene}/{kind}: candidate_path({rec.best_index}).{f} differs from the record's " \
+            f"(max {np.abs(got - v[:n]).max():.3e}): the debug path is not the evaluated one"
+    _, _, keep, _ = sc.bp.candidates(0)
+    X, Y = lib_points(sc)
+    S, max_viol = 20, int(np.floor(sc.kw.get("chance_epsilon", 0.0) * 20))
+    dirs = {"normal": None, "rand0": np.array([np.cos(2.1), np.sin(2.1)])}
+    reqs, labels, close = [], [], []
+    for c in sc.candidates():
+        for k in sc.steps(c):
+            p = np.array([X[c, k], Y[c, k]])
+            for dname, u in dirs.items():
+                if u is None:
+                    yaw = sc.lib_path(c)[2][k]
+                    u = np.array([-np.sin(yaw), np.cos(yaw)])
+                pl = ulp_placements(p, u, sc.r * sc.r)
+                close.append(any(v < 0 for _, v in pl) and any(v > 0 for _, v in pl))
+                for o, v in pl:
+                    lab = f"cand {c} step {k} dir {dname} ulps {v:+d} obstacle ({o[0]!r}, {o[1]!r})"
+                    if kind == "static":
+                        reqs.append(sc.request(static=o[None].copy()))
+                    else:                           # the placement in max_viol or max_viol + 1 samples, twice in one
+                        n_in = max_viol + (len(reqs) % 2)
+                        dist = np.zeros((S, 2, sc.n_t, 2)) + np.array([FAR, -FAR]) + p
+                        dist[:, 1] += np.array([7.0, 3.0])
+                        for s_ in range(n_in):
+                            dist[(5 * s_ + len(reqs)) % S, 0, k] = o
+                        dist[len(reqs) % S, 1, k] = o
+                        reqs.append(sc.request(dist=dist))
+                        lab += f" in {n_in} samples (max_viol {max_viol})"
+                    labels.append(lab)
+    assert np.mean(close) >= 0.5, f"{scene}/{kind}: placements on both sides found for {np.mean(close):.0%} of the points"
+    want = [expected_status(sc, X, Y, keep, rq.static, None if rq.dist is None else np.asarray(rq.dist), max_viol)
+            for rq in reqs]
+    assert sum((w != sc.lib_status).any() for w in want) >= len(reqs) // 4
+    # the same expectation through the exact path (fot_check_collision_paths: no broad phase, no float32)
+    pend = np.flatnonzero(sc.lib_status == _abi.ST_OK)
+    paths = []
+    for c in pend:
+        xx, yy, yw = sc.lib_path(c)
+        kk = keep[c]
+        paths.append(FrenetPathLike(xx[:kk], yy[:kk], yw[:kk], np.arange(kk) * sc.kw["dt"]))
+    for i, rq in enumerate(reqs):
+        free = sc.bp.paths_collision_free(paths, static=rq.static, dist=rq.dist)
+        np.testing.assert_array_equal(want[i][pend] == _abi.ST_COLLISION, ~free,
+                                      err_msg=f"{scene}/{kind} inst {i} {labels[i]}: exact path")
+    for path in EVAL_PATHS:
+        set_eval_path(sc.bp, path)
+        sc.bp.plan_batch(reqs)
+        for i, w in enumerate(want):
+            _, status, _, _ = sc.bp.candidates(i)
+            bad = np.flatnonzero(status != w)
+            assert not len(bad), f"{scene}/{kind} inst {i} [{path}] {labels[i]}: {len(bad)} candidate(s) differ from " \
+                                 f"the float64 predicate, e.g. cand {bad[0]}: got {status[bad[0]]} want {w[bad[0]]}"
+    set_eval_path(sc.bp, "auto")
+    sc.bp.close()
+
+
+class FrenetPathLike:
+    def __init__(self, x, y, yaw, t):
+        self.x, self.y, self.yaw, self.t = x, y, yaw, t
