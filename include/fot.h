@@ -209,6 +209,30 @@ int fot_plan_batch_device(fot_handle *h, const fot_batch *batch, fot_result *out
 /* block until everything the handle enqueued on its own stream has finished */
 int fot_synchronize(fot_handle *h);
 
+/* ---- scenarios: several planner configurations and reference paths in one handle --------------------------------
+ * A scenario is what one reference FrenetPlanner object is (integrated_simulator.py:289, 342-366): one fot_params and
+ * one reference path.  Scenario 0 is the handle's own (fot_create's params, fot_set_path_*); fot_add_scenario adds
+ * scenarios 1, 2, ... up to FOT_MAX_SCENARIOS in all, and fot_plan_batch_scenarios[_device] plans every instance i of a
+ * batch on scenario scenario[i] (a host array of n_inst ids; NULL = scenario 0 for all) in ONE launch sequence.
+ * fot_plan_batch / fot_plan_batch_device are these calls with scenario = NULL.
+ *   - every scenario of a handle has the handle's dt and max_t (one time grid: n_total, the records, the wire form);
+ *     params with another dt or max_t are FOT_ERR_INVALID, any other limit fails as fot_create would fail
+ *   - a 65th scenario is FOT_ERR_UNSUPPORTED, an unknown id FOT_ERR_INVALID, an instance whose scenario has no path
+ *     FOT_ERR_NO_PATH_SET, a FOT_PREV_S_CHAINED instance on another scenario than its predecessor FOT_ERR_INVALID
+ *     (a chain is one planner object); a refused call changes nothing
+ *   - fot_debug_candidates / fot_debug_candidate_path / fot_debug_margins answer for instance i on its own scenario
+ *   - every other entry point works on scenario 0: fot_loop_*, fot_check_paths, fot_check_collision_paths,
+ *     fot_spline_eval, fot_get_path_coeffs, fot_frenet_state_batch, fot_safety_metrics_batch, fot_debug_time_info */
+#define FOT_MAX_SCENARIOS 64
+int fot_add_scenario(fot_handle *h, const fot_params *params, int32_t *id_out);
+int fot_set_scenario_path_waypoints(fot_handle *h, int32_t id, int32_t n, const double *wx, const double *wy);
+int fot_set_scenario_path_coeffs(fot_handle *h, int32_t id, int32_t n, const double *s,
+                                 const double *ax, const double *bx, const double *cx, const double *dx,
+                                 const double *ay, const double *by, const double *cy, const double *dy);
+int fot_plan_batch_scenarios(fot_handle *h, const fot_batch *batch, const int32_t *scenario, fot_result *out);
+int fot_plan_batch_scenarios_device(fot_handle *h, const fot_batch *batch, const int32_t *scenario,
+                                    fot_result *out_dev, void *stream);
+
 /* FrenetPlanner._cartesian_to_frenet_state (frenet_planner.py:334-374) for n egos.
  * frenet[n][6], ref[n][6], new_prev_s[n], ok[n] (1 = converted) -- host arrays */
 int fot_frenet_state_batch(fot_handle *h, int32_t n, const fot_ego *ego,

@@ -129,12 +129,15 @@ SYMBOLS = ["fot_version", "fot_abi_info", "fot_create", "fot_destroy", "fot_live
            "fot_plan_batch_device", "fot_synchronize", "fot_frenet_state_batch", "fot_debug_candidates",
            "fot_debug_candidate_path", "fot_debug_margins", "fot_debug_set_eval_segments", "fot_debug_set_tile_cut", "fot_debug_time_info", "fot_check_collision_paths", "fot_check_paths", "fot_resample_n_dense", "fot_resample_predictions",
            "fot_predict_cv", "fot_safety_metrics_batch", "fot_loop_set_static", "fot_loop_plan", "fot_loop_observe", "fot_loop_observe_begin", "fot_loop_observe_end", "fot_loop_begin", "fot_loop_step", "fot_gather_paths", "fot_wire_n_total", "fot_wire_record_bytes",
-           "fot_pack_records_device", "fot_pack_records_host", "fot_unpack_records", "fot_profile_enable", "fot_profile_read", "fot_profile_kernel_name"]
+           "fot_pack_records_device", "fot_pack_records_host", "fot_unpack_records", "fot_profile_enable", "fot_profile_read", "fot_profile_kernel_name",
+           "fot_add_scenario", "fot_set_scenario_path_waypoints", "fot_set_scenario_path_coeffs",
+           "fot_plan_batch_scenarios", "fot_plan_batch_scenarios_device"]
 PROFILE_KERNELS = 3                      # FOT_PROFILE_KERNELS (include/fot.h)
 ABI_VERSION = 4                          # FOT_ABI_VERSION
 MAX_TI, MAX_TV, MAX_BRAKE, MAX_PRED_LEN = 64, 32, 32, 32
 EGO_IS_FRENET = 3                        # FOT_EGO_IS_FRENET (fot_ego.has_prev_s)
 MARGIN_GROUPS = 8                        # FOT_MARGIN_GROUPS
+MAX_SCENARIOS = 64                       # FOT_MAX_SCENARIOS
 MARGIN_NAMES = ["speed", "accel", "curvature", "lat_accel", "road", "collision", "stop_filter", "structural"]
 
 _lib = None
@@ -314,6 +317,15 @@ def lib():
     L.fot_spline_eval.argtypes = [vp, C.c_int32] + [dp] * 6
     L.fot_plan_batch.argtypes = [vp, C.POINTER(Batch), C.POINTER(Result)]
     L.fot_plan_batch_device.argtypes = [vp, C.POINTER(Batch), vp, vp]
+    # (a library that predates scenarios still loads -- the A side of an A/B against an older build; build() checks that
+    #  every symbol of SYMBOLS is there)
+    for name, args in (("fot_add_scenario", [vp, C.POINTER(Params), ip]),
+                       ("fot_set_scenario_path_waypoints", [vp, C.c_int32, C.c_int32, dp, dp]),
+                       ("fot_set_scenario_path_coeffs", [vp, C.c_int32, C.c_int32] + [dp] * 9),
+                       ("fot_plan_batch_scenarios", [vp, C.POINTER(Batch), ip, C.POINTER(Result)]),
+                       ("fot_plan_batch_scenarios_device", [vp, C.POINTER(Batch), ip, vp, vp])):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = args
     L.fot_synchronize.argtypes = [vp]
     L.fot_frenet_state_batch.argtypes = [vp, C.c_int32, C.POINTER(Ego), dp, dp, dp, ip]
     L.fot_debug_candidates.argtypes = [vp, C.c_int32, C.c_int32, dp, ip, ip, ip]

@@ -33,6 +33,7 @@ class PlanRequest:
     static: Optional[np.ndarray] = None          # [Ns, 2]
     dyn: Optional[np.ndarray] = None             # [P, T, 2]
     dist: Optional[np.ndarray] = None            # [S, P, T, 2]
+    scenario: int = 0                            # planner configuration + reference path (BatchPlanner.add_scenario)
 
 
 def _dyn_of(req: PlanRequest):
@@ -71,6 +72,7 @@ class PackedBatch:
         self.static_off = np.zeros(n + 1, dtype=np.int32)
         self.dyn_off = np.zeros(max(n, 1), dtype=np.int64)
         self.dyn_dims = np.zeros((max(n, 1), 4), dtype=np.int32)
+        self.scenario = np.zeros(max(n, 1), dtype=np.int32)     # fot_plan_batch_scenarios' scenario[n_inst]
         statics: List[np.ndarray] = []
         dyns: List[np.ndarray] = []
         dyn_cursor = 0
@@ -91,6 +93,7 @@ class PackedBatch:
                 e.has_prev_s = 0 if r.prev_s is None else 1
                 e.prev_s = 0.0 if r.prev_s is None else float(r.prev_s)
             self.target[i] = float(r.target_speed)
+            self.scenario[i] = int(r.scenario)
             ov = r.overrides or {}
             o = self.overrides[i]
             o.max_speed = float(ov.get("max_speed", nan))
@@ -120,6 +123,7 @@ class PackedBatch:
         self.static_xy = (np.concatenate(statics, axis=0) if statics else np.empty((0, 2))).astype(self.np_dtype)
         self.static_xy = np.ascontiguousarray(self.static_xy)
         self.dyn_xy = np.ascontiguousarray(np.concatenate(dyns, axis=0) if dyns else np.empty((0, 2), self.np_dtype))
+        self.mixed = bool(n and np.any(self.scenario[:n] != 0))   # some instance is not on scenario 0
         self.n_candidates_hint = None
         self.c = self._make_struct(self.static_xy.ctypes.data if self.static_xy.size else None,
                                    self.dyn_xy.ctypes.data if self.dyn_xy.size else None)
@@ -138,6 +142,10 @@ class PackedBatch:
         b.dyn_off = self.dyn_off.ctypes.data_as(C.POINTER(C.c_int64)) if dyn_ptr else None
         b.dyn_dims = self.dyn_dims.ctypes.data_as(C.POINTER(C.c_int32)) if dyn_ptr else None
         return b
+
+    def scenario_ptr(self):
+        """The ``scenario`` argument of ``fot_plan_batch_scenarios[_device]``: NULL when every instance is on scenario 0."""
+        return self.scenario.ctypes.data_as(C.POINTER(C.c_int32)) if self.mixed else None
 
     def with_device_obstacles(self, static_dev_ptr: Optional[int], dyn_dev_ptr: Optional[int]) -> _abi.Batch:
         """Same batch with the obstacle coordinates already resident in HBM."""

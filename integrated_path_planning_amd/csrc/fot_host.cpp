@@ -147,6 +147,17 @@ struct LoopState {
     }
 };
 
+// One planner configuration + reference path of a handle (a reference FrenetPlanner object); scenario 0 is the handle's own.
+struct Scenario {
+    fot_params params = fot_params();
+    DevParams P;                             // (element `id` of the handle's DevParams table in HBM)
+    HostSpline spline;
+    DevBuf dSpline;                          // its 9 coefficient arrays (element `id` of the SplineView table)
+    bool has_path = false;
+    TileShapes shapes;                       // its run of the handle's tile table ...
+    int32_t shape_base = 0;                  // ... starting at this entry
+};
+
 constexpr int FOT_LANES = 4;                  // lanes available; lanes_cfg of them are used (FOT_LANES env, default 1)
 constexpr int FOT_SPLIT_MIN_INSTANCES = 32;  // smaller batches run as one piece on the caller's stream
 
@@ -169,14 +180,12 @@ struct fot_handle {
     int32_t done_seq = 0;
     bool done_seq_armed = false;             // the call being enqueued wants the flags
     int tile_cut = 0;                    // fot_debug_set_tile_cut (TILE_CUT_*)
-    fot_params params;
-    DevParams P;
-    DevBuf dP;
-    HostSpline spline;
-    DevBuf dSpline;
-    TileShapes shapes;                       // tile table (host copy) ...
-    DevBuf dShapes;                          // ... and in HBM: cand0[] | n[] | span[]
-    bool has_path = false;
+    std::vector<Scenario> sc;                // scenarios; sc[0]: fot_create's params + fot_set_path_*
+    std::vector<ScenarioRef> refs;           // what build_batch_layout needs of each (rebuilt with the tile table)
+    DevBuf dP;                               // DevParams[sc.size()]
+    DevBuf dSplineTab;                       // SplineView[sc.size()]
+    int32_t n_shape_entries = 0;             // entries of the concatenated tile table ...
+    DevBuf dShapes;                          // ... in HBM: cand0[] | n[] | span[]
     Workspace ws[FOT_LANES];
     int lanes_cfg = 1;                       // sub-batches a large batch is split into
     int lanes_used = 0;                      // lanes of the most recent plan call
@@ -262,50 +271,130 @@ int order_end(fot_handle *h, hipStream_t st)
     return FOT_OK;
 }
 
-SplineView spline_view(const fot_handle *h)
+SplineView spline_view(const fot_handle *h, int scen = 0)
 {
     SplineView v;
-    const double *b = h->dSpline.as<double>();
-    const int n = h->spline.n;
+    const double *b = h->sc[(size_t)scen].dSpline.as<double>();
+    const int n = h->sc[(size_t)scen].spline.n;
     v.s = b; v.ax = b + n; v.bx = b + 2 * n; v.cx = b + 3 * n; v.dx = b + 4 * n;
     v.ay = b + 5 * n; v.by = b + 6 * n; v.cy = b + 7 * n; v.dy = b + 8 * n;
     v.n = n; v._pad = 0;
     return v;
 }
 
-int upload_spline(fot_handle *h)
+// the SplineView of every scenario, in HBM (a scenario without a path yet: an empty view no batch can reach)
+int upload_spline_table(fot_handle *h)
 {
-    const int n = h->spline.n;
+    std::vector<SplineView> tab(h->sc.size());
+    for (size_t s = 0; s < h->sc.size(); ++s) tab[s] = spline_view(h, (int)s);
+    HIP_TRY(h, h->dSplineTab.ensure(sizeof(SplineView) * tab.size()));
+    HIP_TRY(h, hipMemcpy(h->dSplineTab.p, tab.data(), sizeof(SplineView) * tab.size(), hipMemcpyHostToDevice));
+    return FOT_OK;
+}
+
+// scenario `scen`'s spline into HBM (its coefficient arrays and its entry of the SplineView table)
+int upload_spline(fot_handle *h, int scen = 0)
+{
+    Scenario &S = h->sc[(size_t)scen];
+    const int n = S.spline.n;
     std::vector<double> flat((size_t)9 * n, 0.0);
-    const std::vector<double> *src[9] = { &h->spline.s, &h->spline.ax, &h->spline.bx, &h->spline.cx, &h->spline.dx,
-                                          &h->spline.ay, &h->spline.by, &h->spline.cy, &h->spline.dy };
+    const std::vector<double> *src[9] = { &S.spline.s, &S.spline.ax, &S.spline.bx, &S.spline.cx, &S.spline.dx,
+                                          &S.spline.ay, &S.spline.by, &S.spline.cy, &S.spline.dy };
     for (int f = 0; f < 9; ++f)
         std::memcpy(flat.data() + (size_t)f * n, src[f]->data(), sizeof(double) * std::min((size_t)n, src[f]->size()));
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipDeviceSynchronize());                          // nothing may still be reading the old spline
-    HIP_TRY(h, h->dSpline.ensure(flat.size() * sizeof(double)));
-    HIP_TRY(h, hipMemcpy(h->dSpline.p, flat.data(), flat.size() * sizeof(double), hipMemcpyHostToDevice));
-    h->has_path = true;
+    HIP_TRY(h, S.dSpline.ensure(flat.size() * sizeof(double)));
+    HIP_TRY(h, hipMemcpy(S.dSpline.p, flat.data(), flat.size() * sizeof(double), hipMemcpyHostToDevice));
+    { int r = upload_spline_table(h); if (r != FOT_OK) return r; }
+    S.has_path = true;
     h->last_valid = false;
     return FOT_OK;
 }
 
-// (re)builds the handle's tile table for the given cut and puts it into HBM: cand0[] | n[] | span[]
+// the DevParams of every scenario, element s = scenario s, into HBM
+int upload_params(fot_handle *h)
+{
+    std::vector<DevParams> tab(h->sc.size());
+    for (size_t s = 0; s < h->sc.size(); ++s) tab[s] = h->sc[s].P;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipDeviceSynchronize());                          // nothing may still be reading the old table
+    HIP_TRY(h, h->dP.ensure(sizeof(DevParams) * tab.size()));
+    HIP_TRY(h, hipMemcpy(h->dP.p, tab.data(), sizeof(DevParams) * tab.size(), hipMemcpyHostToDevice));
+    h->last_valid = false;
+    return FOT_OK;
+}
+
+// (re)builds the tile tables of all scenarios for the given cut (one cut per handle) and puts their concatenation into
+// HBM: cand0[] | n[] | span[]
 int upload_tile_shapes(fot_handle *h, int cut)
 {
-    build_tile_shapes(h->P, h->shapes, cut);
+    const size_t n_sc = h->sc.size();
+    std::vector<const DevParams *> ps(n_sc);
+    std::vector<TileShapes> shapes(n_sc);
+    for (size_t s = 0; s < n_sc; ++s) ps[s] = &h->sc[s].P;
+    build_tile_shapes(ps.data(), (int)n_sc, shapes.data(), cut);
+    std::vector<int32_t> cand0, nn, span;
+    for (size_t s = 0; s < n_sc; ++s) {
+        h->sc[s].shape_base = (int32_t)cand0.size();
+        cand0.insert(cand0.end(), shapes[s].cand0.begin(), shapes[s].cand0.end());
+        nn.insert(nn.end(), shapes[s].n.begin(), shapes[s].n.end());
+        span.insert(span.end(), shapes[s].span.begin(), shapes[s].span.end());
+        h->sc[s].shapes = std::move(shapes[s]);
+    }
+    h->refs.assign(n_sc, ScenarioRef());
+    for (size_t s = 0; s < n_sc; ++s) {
+        h->refs[s].hp = &h->sc[s].params; h->refs[s].P = &h->sc[s].P;
+        h->refs[s].shapes = &h->sc[s].shapes; h->refs[s].shape_base = h->sc[s].shape_base;
+    }
     h->tile_cut = cut;
-    const size_t nt = h->shapes.cand0.size();
+    const size_t nt = cand0.size();
+    h->n_shape_entries = (int32_t)nt;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipDeviceSynchronize());                          // nothing may still be reading the old table
     HIP_TRY(h, h->dShapes.ensure(sizeof(int32_t) * 3 * std::max<size_t>(nt, 1)));
     if (nt) {
-        HIP_TRY(h, hipMemcpy(h->dShapes.p, h->shapes.cand0.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(h->dShapes.as<int32_t>() + nt, h->shapes.n.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(h->dShapes.as<int32_t>() + 2 * nt, h->shapes.span.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->dShapes.p, cand0.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->dShapes.as<int32_t>() + nt, nn.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->dShapes.as<int32_t>() + 2 * nt, span.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice));
     }
     h->last_valid = false;
     return FOT_OK;
+}
+
+// The scenarios a batch's instances name: known ids with a path, chains on one scenario (scen NULL: scenario 0)
+int check_scenarios(fot_handle *h, const fot_batch &b, const int32_t *scen)
+{
+    const int n_inst = b.n_inst;
+    if (!scen) return h->sc[0].has_path ? FOT_OK : fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
+    for (int i = 0; i < n_inst; ++i) {
+        if (scen[i] < 0 || scen[i] >= (int)h->sc.size()) return fail(h, FOT_ERR_INVALID, "unknown scenario id");
+        if (!h->sc[(size_t)scen[i]].has_path)
+            return fail(h, FOT_ERR_NO_PATH_SET, "an instance's scenario has no path (fot_set_scenario_path_*)");
+    }
+    // (build_batch_layout refuses this too, lane by lane; checked here so that a refused call enqueues nothing)
+    for (int i = 1; i < n_inst && b.ego; ++i)
+        if (b.ego[i].has_prev_s == FOT_PREV_S_CHAINED && scen[i] != scen[i - 1])
+            return fail(h, FOT_ERR_INVALID, "a chained instance must be on its predecessor's scenario (a chain is one planner)");
+    return FOT_OK;
+    return FOT_OK;
+}
+
+// the paths of a batch laid out by L: its one scenario's in the kernel arguments, or the table of a mixed batch
+PathSet path_set(const fot_handle *h, const BatchLayout &L, const DevParams **P_launch)
+{
+    const DevParams *dP = h->dP.as<DevParams>();
+    if (L.scens.size() <= 1) {
+        const int s = L.scens.empty() ? 0 : L.scens[0];
+        *P_launch = dP + s;
+        return PathSet::single(spline_view(h, s));
+    }
+    PathSet ps;
+    ps.table = h->dSplineTab.as<SplineView>();
+    ps.mixed = 1;
+    for (int s : L.scens) ps.knots[ps.n_knots++] = h->sc[(size_t)s].spline.n;
+    *P_launch = dP;
+    return ps;
 }
 
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -359,12 +448,12 @@ struct ProfScope {
 // sync_caller: see enqueue_plan.
 // d_dyn_stage: HBM block the NaN-scan blocks copy the dynamic tensors into as they read them (a small call's tensors
 // lie in pinned host memory: the later kernels then read the copy instead of crossing PCIe again), or nullptr.
-int enqueue_lane(fot_handle *h, Workspace &w, const fot_batch &b, const void *d_static, const void *d_dyn,
-                 fot_result *d_out, hipStream_t st, bool sync_caller = false, void *d_dyn_stage = nullptr)
+int enqueue_lane(fot_handle *h, Workspace &w, const fot_batch &b, const int32_t *scen, const void *d_static,
+                 const void *d_dyn, fot_result *d_out, hipStream_t st, bool sync_caller = false, void *d_dyn_stage = nullptr)
 {
     BatchLayout &L = w.last;
     std::string err;
-    int rc = build_batch_layout(h->params, h->P, h->shapes, b, L, err);
+    int rc = build_batch_layout(h->refs.data(), (int)h->refs.size(), scen, b, L, err);
     if (rc != FOT_OK) return fail(h, rc, err);
     if (L.n_inst == 0) return FOT_OK;
 
@@ -378,7 +467,7 @@ int enqueue_lane(fot_handle *h, Workspace &w, const fot_batch &b, const void *d_
     std::memcpy(stg, L.desc.data(), sizeof(InstDesc) * (size_t)L.n_inst);
 
     // --- workspace (grow-only; a growing hipFree/hipMalloc synchronises, steady state does not)
-    const DevParams &P = h->P;
+    const DevParams &P = h->sc[0].P;                             // (n_total: the same in every scenario)
     HIP_TRY(h, w.dMeta.ensure(meta_bytes));
     HIP_TRY(h, w.dState.ensure(sizeof(InstState) * (size_t)L.n_inst));
     const size_t slots = (size_t)std::max<int64_t>(L.n_slots, 1);
@@ -401,13 +490,13 @@ int enqueue_lane(fot_handle *h, Workspace &w, const fot_batch &b, const void *d_
     const InstDesc *d_desc = (const InstDesc *)w.dMeta.p;
     TileTable tt;
     tt.cand0 = h->dShapes.as<int32_t>();
-    tt.n = h->dShapes.as<int32_t>() + h->shapes.cand0.size();
-    tt.span = h->dShapes.as<int32_t>() + 2 * h->shapes.cand0.size();
+    tt.n = h->dShapes.as<int32_t>() + h->n_shape_entries;
+    tt.span = h->dShapes.as<int32_t>() + 2 * (size_t)h->n_shape_entries;
     tt.n_tiles = L.n_tiles; tt.max_tiles = L.max_tiles; tt.row_budget = L.row_budget;
     tt.eval_segments = h->eval_segments;
     tt.grouped = L.grouped;
-    const DevParams *dP = h->dP.as<DevParams>();
-    const SplineView sv = spline_view(h);
+    const DevParams *dP = nullptr;
+    const PathSet sv = path_set(h, L, &dP);
     CandArrays ca;
     ca.cost = w.dCost.as<double>(); ca.parts = w.dParts.as<TilePart>();
     ca.status = w.dStatus.as<uint8_t>(); ca.keep = w.dKeep.as<uint16_t>();
@@ -448,7 +537,7 @@ int enqueue_lane(fot_handle *h, Workspace &w, const fot_batch &b, const void *d_
     }
     if (L.any_obstacles) {
         ProfScope ps(h, 1, st);
-        LAUNCH_TRY(h, launch_cull(dP, d_desc, w.dState.as<InstState>(), L.n_inst, P.n_total, P.n_ti + P.n_brake, sv,
+        LAUNCH_TRY(h, launch_cull(dP, d_desc, w.dState.as<InstState>(), L.n_inst, P.n_total, L.n_ext, sv,
                                   d_static, d_dyn, b.obstacle_dtype, ea, tt, st));
     }
     {
@@ -479,12 +568,12 @@ fot_batch sub_batch(const fot_batch &b, int i0, int n)
 // fork into the lanes' streams and join `user` again.
 // sync_caller: the caller waits for the records right behind this call (the synchronous entry points): the selecting
 // waves then raise a flag per record in pinned memory (wait_records).
-int enqueue_plan(fot_handle *h, const fot_batch &b, const void *d_static, const void *d_dyn, fot_result *d_out,
-                 hipStream_t user, bool sync_caller = false, void *d_dyn_stage = nullptr)
+int enqueue_plan(fot_handle *h, const fot_batch &b, const int32_t *scen, const void *d_static, const void *d_dyn,
+                 fot_result *d_out, hipStream_t user, bool sync_caller = false, void *d_dyn_stage = nullptr)
 {
-    if (!h->has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
-    h->last_valid = false;
     if (b.n_inst < 0) return fail(h, FOT_ERR_INVALID, "n_inst < 0");
+    { int r = check_scenarios(h, b, scen); if (r != FOT_OK) return r; }
+    h->last_valid = false;
     if (b.n_inst == 0) { h->lanes_used = 0; h->last_valid = true; return FOT_OK; }
     if (!d_out) return fail(h, FOT_ERR_INVALID, "out is NULL");
     if (!b.ego || !b.target_speed) return fail(h, FOT_ERR_INVALID, "ego / target_speed missing");
@@ -494,7 +583,7 @@ int enqueue_plan(fot_handle *h, const fot_batch &b, const void *d_static, const 
 
     if (b.n_inst < FOT_SPLIT_MIN_INSTANCES * h->lanes_cfg / 2 || h->lanes_cfg <= 1) {
         h->ws[0].first_inst = 0;
-        int rc = enqueue_lane(h, h->ws[0], b, d_static, d_dyn, d_out, user, sync_caller, d_dyn_stage);
+        int rc = enqueue_lane(h, h->ws[0], b, scen, d_static, d_dyn, d_out, user, sync_caller, d_dyn_stage);
         if (rc != FOT_OK) return rc;
         h->lanes_used = 1;
         h->last_valid = true;
@@ -512,7 +601,7 @@ int enqueue_plan(fot_handle *h, const fot_batch &b, const void *d_static, const 
         if (n <= 0) { w.last = BatchLayout(); w.first_inst = i0; continue; }
         HIP_TRY(h, hipStreamWaitEvent(w.stream, h->fork, 0));
         w.first_inst = i0;
-        int rc = enqueue_lane(h, w, sub_batch(b, i0, n), d_static, d_dyn, d_out + i0, w.stream);
+        int rc = enqueue_lane(h, w, sub_batch(b, i0, n), scen ? scen + i0 : nullptr, d_static, d_dyn, d_out + i0, w.stream);
         if (rc != FOT_OK) return rc;
         HIP_TRY(h, hipEventRecord(w.done, w.stream));
         HIP_TRY(h, hipStreamWaitEvent(user, w.done, 0));
@@ -622,8 +711,10 @@ int fot_create(const fot_params *params, int device, fot_handle **out)
         const int v = std::atoi(ev);
         if (v >= 1 && v <= FOT_LANES) h->lanes_cfg = v;
     }
-    h->params = *params;
-    h->P = P;
+    h->sc.reserve(FOT_MAX_SCENARIOS);
+    h->sc.emplace_back();
+    h->sc[0].params = *params;
+    h->sc[0].P = P;
     auto bail = [&](hipError_t ee, const char *what) {
         int r = hip_fail(nullptr, ee, what);
         destroy_handle(h);
@@ -644,7 +735,8 @@ int fot_create(const fot_params *params, int device, fot_handle **out)
         if ((e = hipEventCreateWithFlags(&w.done, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
     }
     if ((e = h->dP.ensure(sizeof(DevParams))) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMemcpy(h->dP.p, &h->P, sizeof(DevParams), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
+    if ((e = hipMemcpy(h->dP.p, &h->sc[0].P, sizeof(DevParams), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
+    if (upload_spline_table(h) != FOT_OK) { std::string m = h->err; destroy_handle(h); return fail(nullptr, FOT_ERR_HIP, m); }
     {
         int cut = TILE_CUT_AUTO;                                 // FOT_TILE_CUT=wave|group: diagnostics scripts
         if (const char *ev = std::getenv("FOT_TILE_CUT")) cut = ev[0] == 'g' ? TILE_CUT_GROUP : ev[0] == 'w' ? TILE_CUT_WAVE : TILE_CUT_AUTO;
@@ -694,7 +786,8 @@ void destroy_handle(fot_handle *h)
         delete h;
         return;
     }
-    DevBuf *bufs[] = { &h->dP, &h->dSpline, &h->dShapes, &h->dUserStatic, &h->dUserDyn, &h->dOut, &h->dTmpA, &h->dTmpB, &h->dTmpC, &h->dTmpD
+    for (Scenario &S : h->sc) S.dSpline.release();
+    DevBuf *bufs[] = { &h->dP, &h->dSplineTab, &h->dShapes, &h->dUserStatic, &h->dUserDyn, &h->dOut, &h->dTmpA, &h->dTmpB, &h->dTmpC, &h->dTmpD
                      };
     for (DevBuf *b : bufs) b->release();
     for (Workspace &w : h->ws) w.release();
@@ -711,39 +804,81 @@ void destroy_handle(fot_handle *h)
 
 extern "C" {
 
-int fot_set_path_waypoints(fot_handle *h, int32_t n, const double *wx, const double *wy)
+int fot_set_scenario_path_waypoints(fot_handle *h, int32_t id, int32_t n, const double *wx, const double *wy)
 {
     if (!h) return FOT_ERR_INVALID;
+    if (id < 0 || id >= (int)h->sc.size()) return fail(h, FOT_ERR_INVALID, "unknown scenario id");
     std::string err;
     HostSpline sp;
     int rc = build_spline(n, wx, wy, sp, err);
     if (rc != FOT_OK) return fail(h, rc, err);
-    h->spline = sp;
-    return upload_spline(h);
+    h->sc[(size_t)id].spline = sp;
+    return upload_spline(h, id);
+}
+
+int fot_set_path_waypoints(fot_handle *h, int32_t n, const double *wx, const double *wy)
+{
+    return fot_set_scenario_path_waypoints(h, 0, n, wx, wy);
+}
+
+int fot_set_scenario_path_coeffs(fot_handle *h, int32_t id, int32_t n, const double *s,
+                                 const double *ax, const double *bx, const double *cx, const double *dx,
+                                 const double *ay, const double *by, const double *cy, const double *dy)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (id < 0 || id >= (int)h->sc.size()) return fail(h, FOT_ERR_INVALID, "unknown scenario id");
+    if (n < 2 || !s || !ax || !bx || !cx || !dx || !ay || !by || !cy || !dy)
+        return fail(h, FOT_ERR_INVALID, "spline needs >= 2 knots and all nine coefficient arrays");
+    HostSpline &sp = h->sc[(size_t)id].spline;
+    sp.n = n;
+    sp.s.assign(s, s + n);
+    sp.ax.assign(ax, ax + n); sp.bx.assign(bx, bx + n - 1); sp.cx.assign(cx, cx + n); sp.dx.assign(dx, dx + n - 1);
+    sp.ay.assign(ay, ay + n); sp.by.assign(by, by + n - 1); sp.cy.assign(cy, cy + n); sp.dy.assign(dy, dy + n - 1);
+    sp.bx.resize(n, 0.0); sp.dx.resize(n, 0.0); sp.by.resize(n, 0.0); sp.dy.resize(n, 0.0);
+    return upload_spline(h, id);
 }
 
 int fot_set_path_coeffs(fot_handle *h, int32_t n, const double *s,
                         const double *ax, const double *bx, const double *cx, const double *dx,
                         const double *ay, const double *by, const double *cy, const double *dy)
 {
+    return fot_set_scenario_path_coeffs(h, 0, n, s, ax, bx, cx, dx, ay, by, cy, dy);
+}
+
+int fot_add_scenario(fot_handle *h, const fot_params *params, int32_t *id_out)
+{
     if (!h) return FOT_ERR_INVALID;
-    if (n < 2 || !s || !ax || !bx || !cx || !dx || !ay || !by || !cy || !dy)
-        return fail(h, FOT_ERR_INVALID, "spline needs >= 2 knots and all nine coefficient arrays");
-    HostSpline &sp = h->spline;
-    sp.n = n;
-    sp.s.assign(s, s + n);
-    sp.ax.assign(ax, ax + n); sp.bx.assign(bx, bx + n - 1); sp.cx.assign(cx, cx + n); sp.dx.assign(dx, dx + n - 1);
-    sp.ay.assign(ay, ay + n); sp.by.assign(by, by + n - 1); sp.cy.assign(cy, cy + n); sp.dy.assign(dy, dy + n - 1);
-    sp.bx.resize(n, 0.0); sp.dx.resize(n, 0.0); sp.by.resize(n, 0.0); sp.dy.resize(n, 0.0);
-    return upload_spline(h);
+    if (!params || !id_out) return fail(h, FOT_ERR_INVALID, "params / id_out is NULL");
+    const fot_params &p0 = h->sc[0].params;
+    if (!(params->dt == p0.dt) || !(params->max_t == p0.max_t))
+        return fail(h, FOT_ERR_INVALID, "a scenario has the handle's dt and max_t (one time grid per handle)");
+    DevParams P;
+    std::string err;
+    int rc = build_dev_params(*params, P, err);
+    if (rc != FOT_OK) return fail(h, rc, err);
+    if ((int)h->sc.size() >= FOT_MAX_SCENARIOS) return fail(h, FOT_ERR_UNSUPPORTED, "more than FOT_MAX_SCENARIOS scenarios");
+    h->sc.emplace_back();
+    Scenario &S = h->sc.back();
+    S.params = *params;
+    S.P = P;
+    rc = upload_params(h);
+    if (rc == FOT_OK) rc = upload_spline_table(h);
+    if (rc == FOT_OK) rc = upload_tile_shapes(h, h->tile_cut);
+    if (rc != FOT_OK) {                                          // (a HIP failure: back to the scenarios before the call)
+        h->sc.pop_back();
+        (void)upload_params(h); (void)upload_spline_table(h); (void)upload_tile_shapes(h, h->tile_cut);
+        return rc;
+    }
+    *id_out = (int32_t)h->sc.size() - 1;
+    return FOT_OK;
 }
 
 int fot_get_path_coeffs(const fot_handle *h, int32_t *n_out, double *s,
                         double *ax, double *bx, double *cx, double *dx,
                         double *ay, double *by, double *cy, double *dy)
 {
-    if (!h || !h->has_path) return FOT_ERR_NO_PATH_SET;
-    const HostSpline &sp = h->spline;
+    if (!h || !h->sc[0].has_path) return FOT_ERR_NO_PATH_SET;
+    const HostSpline &sp = h->sc[0].spline;
     const int n = sp.n;
     if (n_out) *n_out = n;
     auto cp = [](double *dst, const std::vector<double> &src, int cnt) {
@@ -759,7 +894,7 @@ int fot_spline_eval(fot_handle *h, int32_t n, const double *s, double *x, double
                     double *yaw, double *kappa, double *dkappa)
 {
     if (!h) return FOT_ERR_INVALID;
-    if (!h->has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
+    if (!h->sc[0].has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
     if (n <= 0) return FOT_OK;
     if (!s) return fail(h, FOT_ERR_INVALID, "s is NULL");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -767,7 +902,7 @@ int fot_spline_eval(fot_handle *h, int32_t n, const double *s, double *x, double
     HIP_TRY(h, h->dTmpA.ensure(sizeof(double) * (size_t)n));
     HIP_TRY(h, h->dTmpB.ensure(sizeof(double) * 5 * (size_t)n));
     HIP_TRY(h, hipMemcpyAsync(h->dTmpA.p, s, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    LAUNCH_TRY(h, launch_spline_eval(spline_view(h), n, h->dTmpA.as<double>(), h->dTmpB.as<double>(), h->stream));
+    LAUNCH_TRY(h, launch_spline_eval(spline_view(h, 0), n, h->dTmpA.as<double>(), h->dTmpB.as<double>(), h->stream));
     std::vector<double> outv((size_t)5 * n);
     HIP_TRY(h, hipMemcpyAsync(outv.data(), h->dTmpB.p, sizeof(double) * 5 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -777,12 +912,18 @@ int fot_spline_eval(fot_handle *h, int32_t n, const double *s, double *x, double
     return FOT_OK;
 }
 
-int fot_plan_batch_device(fot_handle *h, const fot_batch *batch, fot_result *out_dev, void *stream)
+int fot_plan_batch_scenarios_device(fot_handle *h, const fot_batch *batch, const int32_t *scenario, fot_result *out_dev,
+                                    void *stream)
 {
     if (!h) return FOT_ERR_INVALID;
     if (!batch) return fail(h, FOT_ERR_INVALID, "batch is NULL");
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    return enqueue_plan(h, *batch, batch->static_xy, batch->dyn_xy, out_dev, st);
+    return enqueue_plan(h, *batch, scenario, batch->static_xy, batch->dyn_xy, out_dev, st);
+}
+
+int fot_plan_batch_device(fot_handle *h, const fot_batch *batch, fot_result *out_dev, void *stream)
+{
+    return fot_plan_batch_scenarios_device(h, batch, nullptr, out_dev, stream);
 }
 
 int fot_resample_n_dense(const fot_resample_params *rp, int32_t pred_len)
@@ -937,7 +1078,7 @@ int fot_safety_metrics_batch(fot_handle *h, int32_t n, const double *ego, const 
         std::memcpy(p_off, ped_off, sizeof(int32_t) * ((size_t)n + 1));
         if (n_ped) { std::memcpy(p_pos, ped_pos, sizeof(double) * 2 * n_ped); std::memcpy(p_vel, ped_vel, sizeof(double) * 2 * n_ped); }
         LAUNCH_TRY(h, launch_safety(h->dP.as<DevParams>(), n, (const double *)p, (const int32_t *)p_off, (const double *)p_pos,
-                                    (const double *)p_vel, ego_radius, ped_radius, h->params.footprint_radius,
+                                    (const double *)p_vel, ego_radius, ped_radius, h->sc[0].params.footprint_radius,
                                     use_footprint, (fot_safety *)h->hSmallOut.p, st));
         HIP_TRY(h, hipStreamSynchronize(st));
         std::memcpy(out, h->hSmallOut.p, sizeof(fot_safety) * (size_t)n);
@@ -955,7 +1096,7 @@ int fot_safety_metrics_batch(fot_handle *h, int32_t n, const double *ego, const 
     }
     LAUNCH_TRY(h, launch_safety(h->dP.as<DevParams>(), n, (const double *)a, (const int32_t *)(a + align256(ego_b)),
                                 (const double *)b, (const double *)(b + align256(ped_b)), ego_radius, ped_radius,
-                                h->params.footprint_radius, use_footprint, h->dTmpC.as<fot_safety>(), st));
+                                h->sc[0].params.footprint_radius, use_footprint, h->dTmpC.as<fot_safety>(), st));
     HIP_TRY(h, hipMemcpyAsync(out, h->dTmpC.p, sizeof(fot_safety) * (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     return FOT_OK;
@@ -982,7 +1123,7 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
                    fot_safety *safety_out, const fot_result **records, int32_t rec_first)
 {
     if (!h) return FOT_ERR_INVALID;
-    if (!h->has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
+    if (!h->sc[0].has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
     if (n_req < 0 || (n_req > 0 && (!req || !records))) return fail(h, FOT_ERR_INVALID, "requests");
     LoopState &L = h->loop;
     if (!frame && !L.have_frame) return fail(h, FOT_ERR_INVALID, "no frame: the first fot_loop_plan of a step carries one");
@@ -1073,7 +1214,7 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
         if (frame->ego && safety_out && n > 0) {
             HIP_TRY(h, L.hOut.ensure(sizeof(fot_safety) * (size_t)n));
             LAUNCH_TRY(h, launch_safety(h->dP.as<DevParams>(), n, p_ego, p_off, p_pos, p_vel, L.ego_radius, L.ped_radius,
-                                        h->params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st));
+                                        h->sc[0].params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st));
             metrics = true;
         }
         L.have_frame = true;
@@ -1122,7 +1263,7 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
             // the records' flags instead of the stream (wait_records): the metrics' kernel ran ahead of the plan kernels on
             // this stream and wrote host memory directly, so its results are there once a record behind it is
             arm_records(h, n_req);
-            int rc = enqueue_plan(h, b, b.static_xy, b.dyn_xy, rec_out, st, true);
+            int rc = enqueue_plan(h, b, nullptr, b.static_xy, b.dyn_xy, rec_out, st, true);
             if (rc != FOT_OK) { h->done_seq_armed = false; return rc; }
             rc = wait_records(h, n_req, st);
             if (rc != FOT_OK) return rc;
@@ -1149,7 +1290,7 @@ int fot_loop_plan(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, con
 int fot_loop_observe_begin(fot_handle *h, int32_t n, const double *ego5, const double *prev_s)
 {
     if (!h) return FOT_ERR_INVALID;
-    if (!h->has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
+    if (!h->sc[0].has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
     LoopState &L = h->loop;
     L.observe_n = -1;
     if (!L.have_frame) return fail(h, FOT_ERR_INVALID, "no frame: fot_loop_plan of this step comes first");
@@ -1176,9 +1317,9 @@ int fot_loop_observe_begin(fot_handle *h, int32_t n, const double *ego5, const d
         p_desc[i] = d;
     }
     LAUNCH_TRY(h, launch_safety(h->dP.as<DevParams>(), n, p_ego, L.p_off, L.p_pos, L.p_vel, L.ego_radius, L.ped_radius,
-                                h->params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st));
+                                h->sc[0].params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st));
     InstState *p_state = (InstState *)((char *)L.hOut.p + saf_b);
-    LAUNCH_TRY(h, launch_frenet_state(h->dP.as<DevParams>(), spline_view(h), p_desc, p_state, n, MetaImport(), NanScan(),
+    LAUNCH_TRY(h, launch_frenet_state(h->dP.as<DevParams>(), PathSet::single(spline_view(h, 0)), p_desc, p_state, n, MetaImport(), NanScan(),
                                       nullptr, st));
     { int r = order_end(h, st); if (r != FOT_OK) return r; }
     L.observe_n = n;
@@ -1489,15 +1630,20 @@ int fot_synchronize(fot_handle *h)
 
 int fot_plan_batch(fot_handle *h, const fot_batch *batch, fot_result *out)
 {
+    return fot_plan_batch_scenarios(h, batch, nullptr, out);
+}
+
+int fot_plan_batch_scenarios(fot_handle *h, const fot_batch *batch, const int32_t *scenario, fot_result *out)
+{
     if (!h) return FOT_ERR_INVALID;
     if (!batch) return fail(h, FOT_ERR_INVALID, "batch is NULL");
     if (batch->n_inst > 0 && !out) return fail(h, FOT_ERR_INVALID, "out is NULL");
     if (batch->n_inst <= 0) return batch->n_inst == 0 ? FOT_OK : fail(h, FOT_ERR_INVALID, "n_inst < 0");
-    if (!h->has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
+    { int r = check_scenarios(h, *batch, scenario); if (r != FOT_OK) return r; }
     // extents of the caller's obstacle arrays
     BatchLayout probe;
     std::string err;
-    int rc = build_batch_layout(h->params, h->P, h->shapes, *batch, probe, err);
+    int rc = build_batch_layout(h->refs.data(), (int)h->refs.size(), scenario, *batch, probe, err);
     if (rc != FOT_OK) return fail(h, rc, err);
     const size_t elem = batch->obstacle_dtype == FOT_F32 ? sizeof(float) : sizeof(double);
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1521,14 +1667,14 @@ int fot_plan_batch(fot_handle *h, const fot_batch *batch, fot_result *out)
         void *stage = nullptr;
         if (dy_bytes && !no_stage) { HIP_TRY(h, h->dUserDyn.ensure(dy_bytes + 256)); stage = h->dUserDyn.p; }
         arm_records(h, batch->n_inst);
-        rc = enqueue_plan(h, *batch, in, in + dy_off, (fot_result *)h->hRecOut.p, h->stream, true, stage);
+        rc = enqueue_plan(h, *batch, scenario, in, in + dy_off, (fot_result *)h->hRecOut.p, h->stream, true, stage);
         if (rc != FOT_OK) { h->done_seq_armed = false; return rc; }
         rc = wait_records(h, batch->n_inst, h->stream);
         if (rc != FOT_OK) return rc;
         // what the device wrote of each record: the header and the first n_total entries of the 15 path arrays (a fifth of
         // the record at 51 samples -- the whole-record copy cost a one-ego call 2 us); the caller's entries past n_total stay
         // as they are
-        const size_t head = offsetof(fot_result, t), used = sizeof(double) * (size_t)h->P.n_total;
+        const size_t head = offsetof(fot_result, t), used = sizeof(double) * (size_t)h->sc[0].P.n_total;
         for (int i = 0; i < batch->n_inst; ++i) {
             const fot_result *src = (const fot_result *)h->hRecOut.p + i;
             std::memcpy(&out[i], src, head);
@@ -1541,7 +1687,7 @@ int fot_plan_batch(fot_handle *h, const fot_batch *batch, fot_result *out)
     HIP_TRY(h, h->dOut.ensure_zeroed(sizeof(fot_result) * (size_t)batch->n_inst));
     if (st_bytes) HIP_TRY(h, hipMemcpyAsync(h->dUserStatic.p, batch->static_xy, st_bytes, hipMemcpyHostToDevice, h->stream));
     if (dy_bytes) HIP_TRY(h, hipMemcpyAsync(h->dUserDyn.p, batch->dyn_xy, dy_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = enqueue_plan(h, *batch, h->dUserStatic.p, h->dUserDyn.p, h->dOut.as<fot_result>(), h->stream);
+    rc = enqueue_plan(h, *batch, scenario, h->dUserStatic.p, h->dUserDyn.p, h->dOut.as<fot_result>(), h->stream);
     if (rc != FOT_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(out, h->dOut.p, sizeof(fot_result) * (size_t)batch->n_inst, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1552,7 +1698,7 @@ int fot_frenet_state_batch(fot_handle *h, int32_t n, const fot_ego *ego,
                            double *frenet, double *ref, double *new_prev_s, int32_t *ok)
 {
     if (!h) return FOT_ERR_INVALID;
-    if (!h->has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
+    if (!h->sc[0].has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
     if (n <= 0) return FOT_OK;
     if (!ego) return fail(h, FOT_ERR_INVALID, "ego is NULL");
     std::vector<InstDesc> desc((size_t)n);
@@ -1567,7 +1713,7 @@ int fot_frenet_state_batch(fot_handle *h, int32_t n, const fot_ego *ego,
         HIP_TRY(h, h->hSmallIn.ensure(sizeof(InstDesc) * (size_t)n));
         HIP_TRY(h, h->hSmallOut.ensure(sizeof(InstState) * (size_t)n));
         std::memcpy(h->hSmallIn.p, desc.data(), sizeof(InstDesc) * (size_t)n);
-        LAUNCH_TRY(h, launch_frenet_state(h->dP.as<DevParams>(), spline_view(h), (const InstDesc *)h->hSmallIn.p,
+        LAUNCH_TRY(h, launch_frenet_state(h->dP.as<DevParams>(), PathSet::single(spline_view(h, 0)), (const InstDesc *)h->hSmallIn.p,
                                           (InstState *)h->hSmallOut.p, n, MetaImport(), NanScan(), nullptr, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         const InstState *stp = (const InstState *)h->hSmallOut.p;
@@ -1582,7 +1728,7 @@ int fot_frenet_state_batch(fot_handle *h, int32_t n, const fot_ego *ego,
     HIP_TRY(h, h->dTmpA.ensure(sizeof(InstDesc) * (size_t)n));
     HIP_TRY(h, h->dTmpB.ensure(sizeof(InstState) * (size_t)n));
     HIP_TRY(h, hipMemcpyAsync(h->dTmpA.p, desc.data(), sizeof(InstDesc) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    LAUNCH_TRY(h, launch_frenet_state(h->dP.as<DevParams>(), spline_view(h), h->dTmpA.as<InstDesc>(),
+    LAUNCH_TRY(h, launch_frenet_state(h->dP.as<DevParams>(), PathSet::single(spline_view(h, 0)), h->dTmpA.as<InstDesc>(),
                                       h->dTmpB.as<InstState>(), n, MetaImport(), NanScan(), nullptr, h->stream));
     std::vector<InstState> st((size_t)n);
     HIP_TRY(h, hipMemcpyAsync(st.data(), h->dTmpB.p, sizeof(InstState) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
@@ -1620,9 +1766,10 @@ int fot_debug_candidates(fot_handle *h, int32_t inst, int32_t cap, double *cost,
     for (int i = 0; i < m; ++i) {
         if (status) status[i] = st8[i];
         if (keep) keep[i] = kp16[i];
-        if (n_t) {
-            if (i < D.n_grid) n_t[i] = h->P.ti[i / (D.n_tv * h->P.n_di)].n_t;
-            else n_t[i] = h->P.n_total;
+        if (n_t) {                                               // (on the instance's own scenario)
+            const DevParams &P = h->sc[(size_t)D.scen].P;
+            if (i < D.n_grid) n_t[i] = P.ti[i / (D.n_tv * P.n_di)].n_t;
+            else n_t[i] = P.n_total;
         }
     }
     return n;
@@ -1641,8 +1788,9 @@ int fot_debug_candidate_path(fot_handle *h, int32_t inst, int32_t index, double 
     HIP_TRY(h, h->dTmpA.ensure(sizeof(double) * 15 * FOT_MAX_NT));
     HIP_TRY(h, h->dTmpD.ensure(sizeof(int32_t) * 2));
     HIP_TRY(h, hipMemsetAsync(h->dTmpA.p, 0, sizeof(double) * 15 * FOT_MAX_NT, h->stream));
-    LAUNCH_TRY(h, launch_debug_path(h->dP.as<DevParams>(), (const InstDesc *)w->dMeta.p, w->dState.as<InstState>(),
-                                    spline_view(h), local, index,
+    const int scen = w->last.desc[(size_t)local].scen;          // the instance's own scenario
+    LAUNCH_TRY(h, launch_debug_path(h->dP.as<DevParams>() + scen, (const InstDesc *)w->dMeta.p, w->dState.as<InstState>(),
+                                    spline_view(h, scen), local, index,
                                     h->dTmpA.as<double>(), h->dTmpD.as<int32_t>(), h->stream));
     int32_t meta[2] = { 0, 0 };
     HIP_TRY(h, hipMemcpyAsync(arrays, h->dTmpA.p, sizeof(double) * 15 * FOT_MAX_NT, hipMemcpyDeviceToHost, h->stream));
@@ -1653,7 +1801,7 @@ int fot_debug_candidate_path(fot_handle *h, int32_t inst, int32_t index, double 
     return FOT_OK;
 }
 
-int32_t fot_wire_n_total(const fot_handle *h) { return h ? h->P.n_total : FOT_ERR_INVALID; }
+int32_t fot_wire_n_total(const fot_handle *h) { return h ? h->sc[0].P.n_total : FOT_ERR_INVALID; }
 
 int32_t fot_wire_record_bytes(int32_t n_total)
 {
@@ -1671,7 +1819,7 @@ int fot_pack_records_device(fot_handle *h, int32_t n, const fot_result *records_
     // ordered behind the handle's previous enqueue whatever stream that ran on: the records are usually the output of
     // the plan call just made, and NULL (= the handle's own stream) is also torch's default-stream handle
     { int r = order_begin(h, st); if (r != FOT_OK) return r; }
-    LAUNCH_TRY(h, launch_pack_wire(n, h->P.n_total, fot_wire_record_bytes(h->P.n_total), records_dev,
+    LAUNCH_TRY(h, launch_pack_wire(n, h->sc[0].P.n_total, fot_wire_record_bytes(h->sc[0].P.n_total), records_dev,
                                    (unsigned char *)wire_dev, st));
     return order_end(h, st);
 }
@@ -1759,7 +1907,7 @@ int fot_debug_time_info(const fot_handle *h, double time, int32_t *n_t, double *
 {
     if (!h || !(time > 0.0)) return FOT_ERR_INVALID;
     TimeInfo ti;
-    if (!time_info(time, h->params.dt, ti)) return FOT_ERR_UNSUPPORTED;      // more than FOT_MAX_NT samples
+    if (!time_info(time, h->sc[0].params.dt, ti)) return FOT_ERR_UNSUPPORTED;      // more than FOT_MAX_NT samples
     if (n_t) *n_t = ti.n_t;
     if (quartic_inv4) std::memcpy(quartic_inv4, ti.qa, sizeof(ti.qa));
     if (quintic_inv9) std::memcpy(quintic_inv9, ti.qi, sizeof(ti.qi));
@@ -1785,8 +1933,9 @@ int fot_debug_margins(fot_handle *h, int32_t inst, int32_t cap, double *margins)
     EntryArrays ea;
     ea.cnt = w->dEntCnt.as<int32_t>(); ea.e32 = w->dEnt32.as<f2>(); ea.e64 = w->dEnt64.as<d2>();
     ea.sid = w->dEntSid.as<uint8_t>(); ea.rng = w->dWaveRng.as<TileStep>();
-    LAUNCH_TRY(h, launch_debug_margins(h->dP.as<DevParams>(), (const InstDesc *)w->dMeta.p, w->dState.as<InstState>(),
-                                       spline_view(h), local, ea, m, h->dTmpB.as<double>(), h->stream));
+    const int scen = w->last.desc[(size_t)local].scen;          // the instance's own scenario
+    LAUNCH_TRY(h, launch_debug_margins(h->dP.as<DevParams>() + scen, (const InstDesc *)w->dMeta.p, w->dState.as<InstState>(),
+                                       spline_view(h, scen), local, ea, m, h->dTmpB.as<double>(), h->stream));
     HIP_TRY(h, hipMemcpyAsync(margins, h->dTmpB.p, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return n;
@@ -1805,7 +1954,7 @@ int check_ext(fot_handle *h, int mode, int32_t n_paths, const int32_t *len, cons
     if (!h) return FOT_ERR_INVALID;
     if (n_paths <= 0) return FOT_OK;
     if (!len || !status_out) return fail(h, FOT_ERR_INVALID, "NULL path array");
-    const DevParams &P = h->P;
+    const DevParams &P = h->sc[0].P;
     // one single-instance batch carries limits + obstacle set
     fot_ego ego = {};
     double target = 0.0;
@@ -1818,7 +1967,7 @@ int check_ext(fot_handle *h, int mode, int32_t n_paths, const int32_t *len, cons
     b.static_xy = static_xy; b.static_off = soff; b.dyn_xy = dyn; b.dyn_off = doff; b.dyn_dims = dims;
     BatchLayout L;
     std::string err;
-    int rc = build_batch_layout(h->params, P, h->shapes, b, L, err);
+    int rc = build_batch_layout(h->sc[0].params, P, h->sc[0].shapes, b, L, err);
     if (rc != FOT_OK) return fail(h, rc, err);
     h->last_valid = false;
 
@@ -1882,7 +2031,7 @@ int fot_check_collision_paths(fot_handle *h, int32_t n_paths, const int32_t *len
 {
     if (!h) return FOT_ERR_INVALID;
     if (n_paths > 0 && (!x || !y || !t)) return fail(h, FOT_ERR_INVALID, "NULL path array");
-    if (n_paths > 0 && h->P.has_footprint && !yaw)
+    if (n_paths > 0 && h->sc[0].P.has_footprint && !yaw)
         return fail(h, FOT_ERR_INVALID, "yaw is required with a multi-circle footprint");
     const double *arr[9] = { x, y, yaw, nullptr, nullptr, nullptr, nullptr, nullptr, t };
     return check_ext(h, 0, n_paths, len, nullptr, arr, nullptr, NAN, n_static, static_xy, mode, S, Pn, T, dyn, free_out);

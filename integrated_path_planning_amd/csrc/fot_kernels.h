@@ -76,15 +76,40 @@ struct TileTable {
     int eval_segments = 0;              // time segments per tile in k_evaluate: 0 = by batch size, 1..4 forced (tests)
 };
 
+// The scenarios (planner constants + reference path) of a plan launch.  A batch on ONE scenario passes that scenario's
+// path in the kernel arguments (`one`) and its constants as the launcher's P, as a single-planner handle always did.  A
+// mixed batch passes the handle's tables: P = DevParams[scenarios] and `table` = SplineView[scenarios] in HBM, and every
+// workgroup resolves P + desc[inst].scen and table[desc[inst].scen] once it knows its instance.
+struct PathSet {
+    SplineView one = SplineView();
+    const SplineView *table = nullptr;
+    int mixed = 0;
+    int n_knots = 0;                    // knot counts of the batch's paths (what the LDS for a staged path is sized by)
+    int knots[FOT_MAX_SCENARIOS] = { 0 };
+    // most knots of a path of the batch that still fits `cap` (0: none does; longer paths are read from HBM)
+    int fit_knots(int cap) const
+    {
+        int m = 0;
+        for (int i = 0; i < n_knots; ++i) if (knots[i] <= cap && knots[i] > m) m = knots[i];
+        return m;
+    }
+    static PathSet single(const SplineView &sp)
+    {
+        PathSet ps;
+        ps.one = sp; ps.n_knots = 1; ps.knots[0] = sp.n;
+        return ps;
+    }
+};
+
 // every launcher returns 0 or the hipError_t of the launch
-int launch_frenet_state(const DevParams *P, SplineView sp, const InstDesc *desc, InstState *state, int n_inst,
+int launch_frenet_state(const DevParams *P, const PathSet &ps, const InstDesc *desc, InstState *state, int n_inst,
                         MetaImport imp, NanScan scan, int32_t *inst_done, hipStream_t st);
-// n_ext: horizons + brake-ladder entries of the planner (sizes k_cull's per-horizon tables in LDS)
+// n_ext: most horizons + brake-ladder entries of a scenario of the batch (sizes k_cull's per-horizon tables in LDS)
 int launch_cull(const DevParams *P, const InstDesc *desc, const InstState *state, int n_inst, int n_total, int n_ext,
-                SplineView sp, const void *static_xy, const void *dyn_xy, int dtype, EntryArrays e, TileTable tiles,
+                const PathSet &ps, const void *static_xy, const void *dyn_xy, int dtype, EntryArrays e, TileTable tiles,
                 hipStream_t st);
 // evaluation + selection: the records land in `out`; inst_done: one counter per instance (zeroed by k_frenet_state)
-int launch_evaluate(const DevParams *P, SplineView sp, const InstDesc *desc, const InstState *state, int n_total,
+int launch_evaluate(const DevParams *P, const PathSet &ps, const InstDesc *desc, const InstState *state, int n_total,
                     int n_inst, TileTable tiles, EntryArrays e, CandArrays c, fot_result *out, int32_t *inst_done,
                     hipStream_t st);
 int launch_debug_path(const DevParams *P, const InstDesc *desc, const InstState *state,

@@ -66,6 +66,25 @@ __device__ __forceinline__ ScanBest wave_argmin(ScanBest b)
     return b;
 }
 
+// Entry i of a read-only table in HBM (the scenarios' SplineView table) read through the constant address space: a
+// scalar load even where the kernel also stores to global memory, instead of vector loads that hold the entry's 80
+// bytes in VGPRs until they are read back to scalars.
+template <typename T>
+__device__ __forceinline__ T load_const(const T *table, int i)
+{
+    static_assert(sizeof(T) % sizeof(uint64_t) == 0, "copied in 8-byte words");
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) uint64_t const_u64;
+    const_u64 *src = (const_u64 *)(table + i);
+    T v;
+#pragma unroll
+    for (int k = 0; k < (int)(sizeof(T) / sizeof(uint64_t)); ++k) ((uint64_t *)&v)[k] = src[k];
+    return v;
+#else
+    return table[i];
+#endif
+}
+
 // The reference spline (9 coefficient arrays of n knots) copied into LDS: the nearest-point search and the segment
 // lookups are chains of dependent reads of these arrays, each an L2 round trip otherwise.  Paths with more knots than
 // the launch reserved LDS for (lds_knots) stay in HBM.  Dynamic LDS: 9 * lds_knots doubles.
@@ -339,11 +358,19 @@ __device__ __forceinline__ void frenet_state_block(const DevParams *__restrict__
 }
 
 __global__ void __launch_bounds__(FRENET_WG)
-k_frenet_state(const DevParams *__restrict__ Pp, SplineView sp_hbm, int lds_knots, const InstDesc *desc,
-               InstState *__restrict__ state, int n_inst, MetaImport imp, NanScan scan, int32_t *__restrict__ inst_done)
+k_frenet_state(const DevParams *__restrict__ Pp, SplineView sp_hbm, const SplineView *__restrict__ sp_table, int mixed,
+               int lds_knots, const InstDesc *desc, InstState *__restrict__ state, int n_inst, MetaImport imp,
+               NanScan scan, int32_t *__restrict__ inst_done)
 {
     SplineView sp = sp_hbm;
-    if ((int)blockIdx.x < n_inst) sp = stage_spline(sp_hbm, lds_knots);       // (the scan blocks never look at the path)
+    if ((int)blockIdx.x < n_inst) {                              // (the scan blocks never look at the path)
+        if (mixed) {                                             // the instance's scenario (a chain shares its head's)
+            const int scen = (imp.h_desc ? imp.h_desc : desc)[blockIdx.x].scen;
+            Pp += scen;
+            sp_hbm = load_const(sp_table, scen);
+        }
+        sp = stage_spline(sp_hbm, lds_knots);
+    }
     frenet_state_block(Pp, sp, desc, state, n_inst, imp, scan, inst_done, (int)blockIdx.x);
 }
 
@@ -424,6 +451,7 @@ __device__ __forceinline__ T ld_agent(const T *p) { return __hip_atomic_load(p, 
 struct EvalKernArgs {
     const DevParams *Pp; SplineView sp; const InstDesc *desc; const InstState *state;
     int row_budget, lds_knots, ablate, n_inst, max_tiles;
+    const SplineView *sp_table; int mixed;           // a mixed batch: Pp + desc[inst].scen, sp_table[desc[inst].scen] (PathSet)
     const int32_t *tile_cand0, *tile_n;
     const TileStep *wave_rng; const f2 *ent32; const d2 *ent64; const uint8_t *ent_sid;
     double *cand_cost; uint8_t *cand_status; uint16_t *cand_keep;   // per candidate: for fot_debug_candidates only
@@ -929,8 +957,8 @@ __device__ __forceinline__ TilePart tile_part_empty()
 __device__ __forceinline__ void select_instance_wave(int inst, int lane)
 {
     const EvalKernArgs &KA = eval_kernargs();
-    const DevParams &P = *KA.Pp;
     const InstDesc &D = KA.desc[inst];
+    const DevParams &P = KA.Pp[KA.mixed ? D.scen : 0];
     const InstState &S = KA.state[inst];
     fot_result &R = KA.out[inst];
     // The record's header starts out all zero, and so do the first n_total entries of its 15 path arrays wherever no
@@ -999,7 +1027,7 @@ __device__ __forceinline__ void select_instance_wave(int inst, int lane)
     const CandDecode cd = decode_candidate(P, D, S.frenet0, best.idx);
     const LonInfo L = profile_info(P, D, S.frenet0, cd.lon_slot, false);
     ComputeTab tab;
-    tab.sp = KA.sp; tab.L = L; tab.dt = P.dt;
+    tab.sp = KA.mixed ? load_const(KA.sp_table, D.scen) : KA.sp; tab.L = L; tab.dt = P.dt;
     double q[6];
     lat_coeffs(S.frenet0, cd.di, cd.brake ? P.brake[cd.ti] : P.ti[cd.ti], q);
 #ifndef FOT_SEL_NO_PATH
@@ -1091,22 +1119,46 @@ k_evaluate(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, 
 #ifdef FOT_TIMELINE
     if (threadIdx.x == 0) s_tl_entry[0] = __builtin_amdgcn_s_memrealtime();
 #endif
-    // LDS: per wave [rows | summaries | row offsets], then the spline (shared by the workgroup's waves)
-    const SplineView sp_lds = stage_spline(a.sp, a.lds_knots, s_lon + waves_per_wg * wave_doubles);
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+    const int lane = threadIdx.x & (WAVE - 1);
+    double *my_rows = s_lon + wv * wave_doubles;
+    const int x = (int)blockIdx.x & (N_XCD - 1);
+    const int m_x = (a.n_inst - x + N_XCD - 1) / N_XCD;            // instances x, x + 8, ...
+    // the tile of wave w of this workgroup: instance (-1: none) and position
+    const auto wave_inst = [&](int w, int &pos_w) {
+        const int q = ((int)blockIdx.x >> 3) * waves_per_wg + w;
+        if (m_x <= 0 || q >= m_x * a.max_tiles) return -1;
+        pos_w = q / m_x;
+        const int i = x + N_XCD * (q - pos_w * m_x);
+        return pos_w < desc[i].n_tiles ? i : -1;                  // (a shorter lattice than the batch's longest: none)
+    };
+    int pos = 0;
+    const int inst = wave_inst(wv, pos);
+    // LDS: per wave [rows | summaries | row offsets], then the spline (shared by the workgroup's waves).  The waves of a
+    // workgroup serve different instances: in a mixed batch the spline is staged when all of them are on one scenario,
+    // otherwise every wave reads its own scenario's spline from HBM (no LDS taken from the row tables).
+    SplineView sp_stage = a.sp;
+    if (a.mixed) {
+        int common = -1;                                         // -1: none yet, -2: the waves disagree
+        for (int w = 0; w < waves_per_wg; ++w) {                 // (uniform: every wave walks the same workgroup)
+            int pw;
+            const int iw = wave_inst(w, pw);
+            if (iw < 0) continue;
+            const int sw = desc[iw].scen;
+            common = common == -1 || common == sw ? sw : -2;
+        }
+        if (common >= 0) sp_stage = load_const(a.sp_table, common);
+        else sp_stage.n = a.lds_knots + 1;                       // nothing staged: no wave reads sp_stage
+        if (inst >= 0) Pp += desc[inst].scen;
+    }
+    SplineView sp_lds = stage_spline(sp_stage, a.lds_knots, s_lon + waves_per_wg * wave_doubles);
+    if (a.mixed && inst >= 0 && sp_stage.n > a.lds_knots) sp_lds = load_const(a.sp_table, desc[inst].scen);
 #ifdef FOT_TIMELINE
     if (threadIdx.x == 0) s_tl_entry[1] = __builtin_amdgcn_s_memrealtime();
     __syncthreads();
 #endif
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
-    const int lane = threadIdx.x & (WAVE - 1);
-    double *my_rows = s_lon + wv * wave_doubles;
-    const int x = (int)blockIdx.x & (N_XCD - 1), q = ((int)blockIdx.x >> 3) * waves_per_wg + wv;
-    const int m_x = (a.n_inst - x + N_XCD - 1) / N_XCD;            // instances x, x + 8, ...
-    if (m_x <= 0 || q >= m_x * a.max_tiles) return;
-    const int pos = q / m_x, j = q - pos * m_x;
-    const int inst = x + N_XCD * j;
+    if (inst < 0) return;
     const int n_tiles = desc[inst].n_tiles;
-    if (pos >= n_tiles) return;                                  // a shorter lattice than the batch's longest
     TilePart tp = tile_part_empty();
     evaluate_tile<TILE_WAVE>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, my_rows, inst,
                          n_tiles - 1 - pos, lane, x, tp);
@@ -1126,17 +1178,19 @@ k_evaluate_split(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ 
     const int wave_doubles = eval_wave_doubles(a.row_budget);
     // LDS: [rows | summaries | row offsets] of the tile, the segments' hand-over, then the spline
     double *s_part = s_lon + wave_doubles;
-    const SplineView sp_lds = stage_spline(a.sp, a.lds_knots, s_part + (SEG_MAX - 1) * SEG_DOUBLES);
     const int seg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
     const int lane = threadIdx.x & (WAVE - 1);
     const int x = (int)blockIdx.x & (N_XCD - 1), q = (int)blockIdx.x >> 3;
     const int m_x = (a.n_inst - x + N_XCD - 1) / N_XCD;
-    if (m_x <= 0) return;
+    if (m_x <= 0) return;                                        // (the whole workgroup: one tile, one instance)
     if (q >= m_x * a.max_tiles) return;
     const int pos = q / m_x, j = q - pos * m_x;
     const int inst = x + N_XCD * j;
     const int n_tiles = desc[inst].n_tiles;
     if (pos >= n_tiles) return;
+    SplineView sp_hbm = a.sp;
+    if (a.mixed) { Pp += desc[inst].scen; sp_hbm = load_const(a.sp_table, desc[inst].scen); }
+    const SplineView sp_lds = stage_spline(sp_hbm, a.lds_knots, s_part + (SEG_MAX - 1) * SEG_DOUBLES);
     const int tile = n_tiles - 1 - pos;
     TilePart tp = tile_part_empty();
     evaluate_tile<TILE_SPLIT>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, s_lon, inst, tile, lane, x,
@@ -1156,18 +1210,20 @@ k_evaluate_group(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ 
                  const int32_t *__restrict__ tile_n, const TileStep *__restrict__ wave_rng,
                  const f2 *__restrict__ ent32, const EvalKernArgs a)
 {
-    // LDS: [rows | summaries | row offsets] of the group, then the spline
-    const SplineView sp_lds = stage_spline(a.sp, a.lds_knots, s_lon + eval_group_doubles());
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
     const int lane = threadIdx.x & (WAVE - 1);
     const int x = (int)blockIdx.x & (N_XCD - 1), q = (int)blockIdx.x >> 3;
     const int m_x = (a.n_inst - x + N_XCD - 1) / N_XCD;
     const int n_entries = m_x * (a.max_tiles / GROUP_TILES);      // groups in this queue
-    if (m_x <= 0 || q >= n_entries) return;
+    if (m_x <= 0 || q >= n_entries) return;                      // (the whole workgroup: one group, one instance)
     const int pos = q / m_x, j = q - pos * m_x;
     const int inst = x + N_XCD * j;
     const int n_groups = desc[inst].n_tiles / GROUP_TILES;
     if (pos >= n_groups) return;                                 // a shorter lattice than the batch's longest
+    // LDS: [rows | summaries | row offsets] of the group, then the spline
+    SplineView sp_hbm = a.sp;
+    if (a.mixed) { Pp += desc[inst].scen; sp_hbm = load_const(a.sp_table, desc[inst].scen); }
+    const SplineView sp_lds = stage_spline(sp_hbm, a.lds_knots, s_lon + eval_group_doubles());
     const int tile0 = (n_groups - 1 - pos) * GROUP_TILES;
     TilePart tp = tile_part_empty();
     evaluate_tile<TILE_GROUP>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, s_lon, inst, tile0 + wv,
@@ -1564,20 +1620,22 @@ cull_group(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, 
 template <typename T>
 __global__ void __launch_bounds__(CULL_KG * WAVE)
 k_cull(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, const InstState *__restrict__ state,
-       int n_inst, SplineView sp_hbm, int lds_knots, const T *__restrict__ static_xy, const T *__restrict__ dyn_xy,
+       int n_inst, SplineView sp_hbm, const SplineView *__restrict__ sp_table, int mixed, int lds_knots,
+       const T *__restrict__ static_xy, const T *__restrict__ dyn_xy,
        int32_t *__restrict__ ent_cnt, f2 *__restrict__ ent32, d2 *__restrict__ ent64, uint8_t *__restrict__ ent_sid,
        TileStep *__restrict__ wave_rng, const int32_t *__restrict__ tile_cand0, const int32_t *__restrict__ tile_n,
        const int32_t *__restrict__ tile_span, const uint8_t *__restrict__ nan_flag,
        int ablate)
 {
     if (ablate & 32) return;                                     // (timing diagnostics: the launch alone)
-    const SplineView sp = stage_spline(sp_hbm, lds_knots);      // every wave, before any of them leaves
-    const int groups = (Pp->n_total + CULL_KG - 1) / CULL_KG;
+    const int groups = (Pp->n_total + CULL_KG - 1) / CULL_KG;   // (n_total: one time grid for every scenario)
     // workgroups go round-robin over the 8 XCDs: all groups of instance i run back to back on XCD i mod 8, so the
     // runs that neighbouring groups cut out of the same cache lines of the prediction tensor meet in one L2
     const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
     const int inst = xcd + 8 * (seq / groups), k0 = (seq % groups) * CULL_KG;
-    if (inst >= n_inst) return;
+    if (inst >= n_inst) return;                                  // (the whole workgroup)
+    if (mixed) { Pp += desc[inst].scen; sp_hbm = load_const(sp_table, desc[inst].scen); }
+    const SplineView sp = stage_spline(sp_hbm, lds_knots);      // every wave, before any of them leaves
     cull_group<T, CULL_KG>(Pp, desc, state, sp, s_spl + 9 * lds_knots, static_xy, dyn_xy, ent_cnt, ent32, ent64, ent_sid,
                            wave_rng, tile_cand0, tile_n, tile_span, nan_flag, ablate, inst, k0);
 }
@@ -1902,49 +1960,51 @@ k_safety(const DevParams *__restrict__ Pp, int n, const double *__restrict__ ego
 
 #define FOT_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
-int launch_frenet_state(const DevParams *P, SplineView sp, const InstDesc *desc, InstState *state, int n_inst,
+int launch_frenet_state(const DevParams *P, const PathSet &ps, const InstDesc *desc, InstState *state, int n_inst,
                         MetaImport imp, NanScan scan, int32_t *inst_done, hipStream_t st)
 {
     if (n_inst <= 0) return 0;
-    const int lds_knots = sp.n <= SPLINE_LDS_KNOTS ? sp.n : 0;
+    const int lds_knots = ps.fit_knots(SPLINE_LDS_KNOTS);
     const int64_t grid = (int64_t)n_inst * (1 + (scan.flag ? scan.blocks_per_inst : 0));
     if (grid > 0x7fffffffLL) return (int)hipErrorInvalidConfiguration;
-    k_frenet_state<<<(unsigned)grid, FRENET_WG, sizeof(double) * 9 * (size_t)lds_knots, st>>>(P, sp, lds_knots, desc, state,
-                                                                                         n_inst, imp, scan, inst_done);
+    k_frenet_state<<<(unsigned)grid, FRENET_WG, sizeof(double) * 9 * (size_t)lds_knots, st>>>(
+        P, ps.one, ps.table, ps.mixed, lds_knots, desc, state, n_inst, imp, scan, inst_done);
     FOT_LAUNCH_CHECK();
     return 0;
 }
 
 int launch_cull(const DevParams *P, const InstDesc *desc, const InstState *state, int n_inst, int n_total, int n_ext,
-                SplineView sp, const void *static_xy, const void *dyn_xy, int dtype, EntryArrays e, TileTable tiles,
+                const PathSet &ps, const void *static_xy, const void *dyn_xy, int dtype, EntryArrays e, TileTable tiles,
                 hipStream_t st)
 {
     if (n_inst <= 0 || n_total <= 0) return 0;
     const unsigned grid = (unsigned)((int64_t)((n_inst + 7) / 8 * 8) * ((n_total + CULL_KG - 1) / CULL_KG));
     static const int ablate_env = getenv("FOT_CULL_ABLATE") ? atoi(getenv("FOT_CULL_ABLATE")) : 0;   // timing diagnostics
     const int ablate = (ablate_env & ~128) | (e.eager_nan ? 128 : 0);
-    const int lds_knots = sp.n <= 64 ? sp.n : 0;                           // a short spline rides along in LDS
+    const int lds_knots = ps.fit_knots(64);                                 // a short spline rides along in LDS
     // + per horizon / brake-ladder entry: lateral extents of the group's steps, the two extreme lateral quintics
     const size_t lds = sizeof(double) * (9 * (size_t)lds_knots + (size_t)n_ext * (CULL_KG * 2 + 9));
     if (dtype == FOT_F32)
-        k_cull<float><<<grid, CULL_KG * WAVE, lds, st>>>(P, desc, state, n_inst, sp, lds_knots, (const float *)static_xy,
+        k_cull<float><<<grid, CULL_KG * WAVE, lds, st>>>(P, desc, state, n_inst, ps.one, ps.table, ps.mixed, lds_knots,
+                                             (const float *)static_xy,
                                              (const float *)dyn_xy, e.cnt, e.e32, e.e64, e.sid, e.rng, tiles.cand0, tiles.n, tiles.span,
                                              e.nan_flag, ablate);
     else
-        k_cull<double><<<grid, CULL_KG * WAVE, lds, st>>>(P, desc, state, n_inst, sp, lds_knots, (const double *)static_xy,
+        k_cull<double><<<grid, CULL_KG * WAVE, lds, st>>>(P, desc, state, n_inst, ps.one, ps.table, ps.mixed, lds_knots,
+                                              (const double *)static_xy,
                                               (const double *)dyn_xy, e.cnt, e.e32, e.e64, e.sid, e.rng, tiles.cand0,
                                               tiles.n, tiles.span, e.nan_flag, ablate);
     FOT_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_evaluate(const DevParams *P, SplineView sp, const InstDesc *desc, const InstState *state, int n_total,
+int launch_evaluate(const DevParams *P, const PathSet &ps, const InstDesc *desc, const InstState *state, int n_total,
                     int n_inst, TileTable tiles, EntryArrays e, CandArrays c, fot_result *out, int32_t *inst_done,
                     hipStream_t st)
 {
     if (n_inst <= 0) return 0;
     static const int ablate = getenv("FOT_EVAL_ABLATE") ? atoi(getenv("FOT_EVAL_ABLATE")) : 0;
-    const int lds_knots = sp.n <= 28 ? sp.n : 0;                           // a short spline rides along (2 KB at most)
+    const int lds_knots = ps.fit_knots(28);                                 // a short spline rides along (2 KB at most)
     // Three launch shapes, 8 queues each (workgroup b serves the instances b mod 8):
     //  * a handful of egos: every tile one workgroup, cut into time segments (k_evaluate_split);
     //  * the grouped cut: one workgroup per group of four tiles (k_evaluate_group, four waves per SIMD);
@@ -1960,7 +2020,8 @@ int launch_evaluate(const DevParams *P, SplineView sp, const InstDesc *desc, con
     const size_t lds = sizeof(double) * ((size_t)eval_wave_doubles(tiles.row_budget) * wpw + 9 * (size_t)lds_knots
                                          + (n_seg > 1 ? (size_t)(SEG_MAX - 1) * SEG_DOUBLES : 0));
     EvalKernArgs a;
-    a.Pp = P; a.sp = sp; a.desc = desc; a.state = state;
+    a.Pp = P; a.sp = ps.one; a.desc = desc; a.state = state;
+    a.sp_table = ps.table; a.mixed = ps.mixed;
     a.row_budget = tiles.row_budget; a.lds_knots = lds_knots; a.ablate = ablate;
     a.n_inst = n_inst; a.max_tiles = tiles.max_tiles;
     a.tile_cand0 = tiles.cand0; a.tile_n = tiles.n;

@@ -265,16 +265,30 @@ inline void fill_tile_spans(const DevParams &P, TileShapes &T)
 // group's sixteen profiles may then hold fewer candidates than four per-wave tiles.  `cut` forces one
 // (fot_debug_set_tile_cut: the GPU tests run every golden under both).
 enum { TILE_CUT_AUTO = 0, TILE_CUT_WAVE = 1, TILE_CUT_GROUP = 2 };
-inline void build_tile_shapes(const DevParams &P, TileShapes &T, int cut = TILE_CUT_AUTO)
+// The tile tables of a handle's n scenarios (P[s]: scenario s), cut ONE way: the automatic choice weighs the tiles of
+// all scenarios together.  T[s] is scenario s's table; the handle concatenates them in HBM.
+inline void build_tile_shapes(const DevParams *const *P, int n, TileShapes *T, int cut = TILE_CUT_AUTO)
 {
-    TileShapes wave, grouped;
-    build_tile_shapes_wave(P, wave);
-    build_tile_shapes_grouped(P, grouped);
-    bool use_groups = (double)grouped.n_real <= 1.15 * (double)wave.n_real;
+    std::vector<TileShapes> wave((size_t)n), grouped((size_t)n);
+    int64_t n_wave = 0, n_grouped = 0;
+    for (int s = 0; s < n; ++s) {
+        build_tile_shapes_wave(*P[s], wave[(size_t)s]);
+        build_tile_shapes_grouped(*P[s], grouped[(size_t)s]);
+        n_wave += wave[(size_t)s].n_real;
+        n_grouped += grouped[(size_t)s].n_real;
+    }
+    bool use_groups = (double)n_grouped <= 1.15 * (double)n_wave;
     if (cut == TILE_CUT_WAVE) use_groups = false;
     if (cut == TILE_CUT_GROUP) use_groups = true;
-    T = use_groups ? grouped : wave;
-    fill_tile_spans(P, T);
+    for (int s = 0; s < n; ++s) {
+        T[s] = use_groups ? grouped[(size_t)s] : wave[(size_t)s];
+        fill_tile_spans(*P[s], T[s]);
+    }
+}
+inline void build_tile_shapes(const DevParams &P, TileShapes &T, int cut = TILE_CUT_AUTO)
+{
+    const DevParams *one = &P;
+    build_tile_shapes(&one, 1, &T, cut);
 }
 
 struct BatchLayout {
@@ -294,25 +308,52 @@ struct BatchLayout {
     int64_t max_dyn_bytes = 0;    // largest dynamic tensor of one instance (sizes the NaN scan)
     bool any_obstacles = false;
     bool any_tmajor = false;      // some instance's tensor is time-major (its NaN flags come from k_frenet_state's scan blocks)
+    int n_ext = 0;                // most horizons + brake-ladder entries of a scenario of the batch (k_cull's LDS tables)
+    std::vector<int32_t> scens;   // the scenarios the batch uses, ascending
 };
 
-inline int build_batch_layout(const fot_params &hp, const DevParams &P, const TileShapes &shapes, const fot_batch &b,
+// One scenario of a handle as a batch layout sees it: its planner constants, its tile table and where that table's run
+// starts in the handle's concatenated table in HBM.
+struct ScenarioRef {
+    const fot_params *hp = nullptr;
+    const DevParams *P = nullptr;
+    const TileShapes *shapes = nullptr;
+    int32_t shape_base = 0;
+};
+
+// scen: [n_inst] scenario of each instance (indices into sc[0, n_scen)), or nullptr = scenario 0 for every instance.
+// Each instance takes its limits, dt, lattice and tile run from its own scenario; the cut and the per-wave row budget
+// are the handle's (the largest over its scenarios).
+inline int build_batch_layout(const ScenarioRef *sc, int n_scen, const int32_t *scen, const fot_batch &b,
                               BatchLayout &L, std::string &err)
 {
     L = BatchLayout();
+    if (n_scen < 1 || !sc) { err = "no scenario"; return FOT_ERR_INVALID; }
     if (b.n_inst < 0) { err = "n_inst < 0"; return FOT_ERR_INVALID; }
     if (b.n_inst > 0 && (!b.ego || !b.target_speed)) { err = "ego / target_speed missing"; return FOT_ERR_INVALID; }
     if (b.obstacle_dtype != FOT_F32 && b.obstacle_dtype != FOT_F64) { err = "obstacle_dtype"; return FOT_ERR_INVALID; }
     L.n_inst = b.n_inst;
     L.desc.resize(b.n_inst);
-    L.row_budget = shapes.row_budget;
-    L.grouped = shapes.grouped;
+    L.grouped = sc[0].shapes->grouped;
+    for (int s = 0; s < n_scen; ++s)
+        if (sc[s].shapes->row_budget > L.row_budget) L.row_budget = sc[s].shapes->row_budget;
+    std::vector<uint8_t> used((size_t)n_scen, 0);
     for (int i = 0; i < b.n_inst; ++i) {
         InstDesc &D = L.desc[i];
         D = InstDesc();
         D.ego = b.ego[i];
+        const int si = scen ? scen[i] : 0;
+        if (si < 0 || si >= n_scen) { err = "unknown scenario id"; return FOT_ERR_INVALID; }
+        const fot_params &hp = *sc[si].hp;
+        const DevParams &P = *sc[si].P;
+        const TileShapes &shapes = *sc[si].shapes;
+        D.scen = si;
+        used[(size_t)si] = 1;
         if (D.ego.has_prev_s < 0 || D.ego.has_prev_s > FOT_EGO_IS_FRENET) { err = "has_prev_s must be 0 .. 3"; return FOT_ERR_INVALID; }
         if (i == 0 && D.ego.has_prev_s == FOT_PREV_S_CHAINED) { err = "the first instance cannot be chained"; return FOT_ERR_INVALID; }
+        if (i > 0 && D.ego.has_prev_s == FOT_PREV_S_CHAINED && si != L.desc[i - 1].scen) {
+            err = "a chained instance must be on its predecessor's scenario (a chain is one planner)"; return FOT_ERR_INVALID;
+        }
         const double target = b.target_speed[i];
         D.target_speed = target;
         D.max_stop = b.max_stop_distance ? b.max_stop_distance[i] : NAN;
@@ -339,7 +380,7 @@ inline int build_batch_layout(const fot_params &hp, const DevParams &P, const Ti
 
         // tiles of this instance: its lattice shape's run of the handle's tile table
         const int n_tiles_i = shapes.tiles_of(D.n_tv);
-        D.shape_off = shapes.off[D.n_tv];
+        D.shape_off = sc[si].shape_base + shapes.off[D.n_tv];
         const int64_t slots_i = ((int64_t)D.n_cand_max + WAVE - 1) / WAVE * WAVE;
         if (L.n_slots + slots_i > 0x7fffffffLL || (int64_t)L.n_tiles + n_tiles_i > 0x7fffffffLL) {
             err = "batch too large"; return FOT_ERR_UNSUPPORTED;
@@ -405,7 +446,22 @@ inline int build_batch_layout(const fot_params &hp, const DevParams &P, const Ti
         err = "obstacle offsets given without coordinates";
         return FOT_ERR_INVALID;
     }
+    for (int s = 0; s < n_scen; ++s)
+        if (used[(size_t)s]) {
+            L.scens.push_back(s);
+            const int e = sc[s].P->n_ti + sc[s].P->n_brake;
+            if (e > L.n_ext) L.n_ext = e;
+        }
     return FOT_OK;
+}
+
+// the single-scenario form: every instance on the one planner
+inline int build_batch_layout(const fot_params &hp, const DevParams &P, const TileShapes &shapes, const fot_batch &b,
+                              BatchLayout &L, std::string &err)
+{
+    ScenarioRef one;
+    one.hp = &hp; one.P = &P; one.shapes = &shapes; one.shape_base = 0;
+    return build_batch_layout(&one, 1, nullptr, b, L, err);
 }
 
 }  // namespace fot

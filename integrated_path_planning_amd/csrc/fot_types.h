@@ -84,7 +84,7 @@ struct InstDesc {
     int32_t dyn_tmajor;                  // 1: the dynamic tensor is [T][S][P][2] (FOT_DYN_LAYOUT_TSP), 0: [S][P][T][2]
     int32_t max_viol;                    // floor(eps*S)
     int32_t n_chained;                   // instances right behind this one that continue its nearest-point cache
-    int32_t _pad;
+    int32_t scen;                        // its scenario: DevParams element and SplineView table entry of the handle
     int64_t nan_off;                     // first of this instance's S * P track flags (fot_kernels.hip scan_nan_tracks)
 };
 

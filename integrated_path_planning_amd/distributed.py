@@ -156,6 +156,9 @@ class ShardedPlanner:
 
         torch = self.torch
         n_total = len(requests)
+        # one planner configuration per rank: a request on another scenario is refused, not planned on scenario 0
+        if any(getattr(r, "scenario", 0) != 0 for r in requests):
+            raise ValueError("ShardedPlanner plans on scenario 0 only; requests with scenario != 0 are not supported")
         lo, hi = shard_bounds(n_total, self.world)[self.rank]
         pb = PackedBatch(requests[lo:hi], obstacle_dtype)
         dyn = torch.from_numpy(pb.dyn_xy).to(self.device) if pb.dyn_xy.size else None

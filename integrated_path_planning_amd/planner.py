@@ -143,16 +143,24 @@ class BatchResult:
         return fp
 
 
+def _params_from_kwargs(planner_kwargs: dict) -> "_abi.Params":
+    """``fot_params`` of a FrenetPlanner's keyword arguments (``footprint=`` an EgoFootprint, the rest make_params')."""
+    kw = dict(planner_kwargs)
+    fp = kw.pop("footprint", None)
+    if fp is not None:
+        kw["footprint_offsets"] = np.asarray(fp.offsets, dtype=float).tolist()
+        kw["footprint_radius"] = float(fp.radius)
+    return make_params(**kw)
+
+
 class BatchPlanner:
-    """One libfot handle: planner parameters + reference path on one GPU."""
+    """One libfot handle: planner parameters + reference path on one GPU (scenario 0), and any further scenarios
+    (``add_scenario``) that one plan call may mix."""
 
     def __init__(self, reference_path=None, waypoints=None, device: int = -1, **planner_kwargs):
         self._lib = _abi.lib()
-        fp = planner_kwargs.pop("footprint", None)
-        if fp is not None:
-            planner_kwargs["footprint_offsets"] = np.asarray(fp.offsets, dtype=float).tolist()
-            planner_kwargs["footprint_radius"] = float(fp.radius)
-        self.params = make_params(**planner_kwargs)
+        self.params = _params_from_kwargs(planner_kwargs)
+        self.scenario_params = [self.params]     # [id]: fot_params of scenario id (0: the handle's own)
         h = C.c_void_p()
         _abi.check(None, self._lib.fot_create(C.byref(self.params), int(device), C.byref(h)))
         self._h = h
@@ -189,16 +197,38 @@ class BatchPlanner:
         self.close()
 
     # -- reference path ---------------------------------------------------
-    def set_path(self, path):
+    def set_path(self, path, scenario: int = 0):
         arrs = spline_arrays(path)
-        _abi.check(self._h, self._lib.fot_set_path_coeffs(self._h, len(arrs[0]), *[_as_dp(a) for a in arrs]))
+        if scenario == 0:
+            _abi.check(self._h, self._lib.fot_set_path_coeffs(self._h, len(arrs[0]), *[_as_dp(a) for a in arrs]))
+        else:
+            _abi.check(self._h, self._lib.fot_set_scenario_path_coeffs(self._h, int(scenario), len(arrs[0]),
+                                                                       *[_as_dp(a) for a in arrs]))
 
-    def set_waypoints(self, wx, wy):
+    def set_waypoints(self, wx, wy, scenario: int = 0):
         wx = np.ascontiguousarray(wx, dtype=np.float64)
         wy = np.ascontiguousarray(wy, dtype=np.float64)
         if wx.shape != wy.shape or wx.ndim != 1:
             raise ValueError("waypoints must be two 1-D arrays of equal length")
-        _abi.check(self._h, self._lib.fot_set_path_waypoints(self._h, len(wx), _as_dp(wx), _as_dp(wy)))
+        if scenario == 0:
+            _abi.check(self._h, self._lib.fot_set_path_waypoints(self._h, len(wx), _as_dp(wx), _as_dp(wy)))
+        else:
+            _abi.check(self._h, self._lib.fot_set_scenario_path_waypoints(self._h, int(scenario), len(wx), _as_dp(wx),
+                                                                          _as_dp(wy)))
+
+    def add_scenario(self, reference_path=None, waypoints=None, **planner_kwargs) -> int:
+        """A further planner configuration + reference path (what one more reference ``FrenetPlanner`` object is) on this
+        handle; same keyword arguments as the constructor.  Returns the id a ``PlanRequest.scenario`` names.  dt and
+        max_t must be the handle's (one time grid per handle)."""
+        params = _params_from_kwargs(planner_kwargs)
+        sid = C.c_int32(-1)
+        _abi.check(self._h, self._lib.fot_add_scenario(self._h, C.byref(params), C.byref(sid)))
+        self.scenario_params.append(params)
+        if reference_path is not None:
+            self.set_path(reference_path, scenario=sid.value)
+        elif waypoints is not None:
+            self.set_waypoints(*waypoints, scenario=sid.value)
+        return sid.value
 
     def path_coeffs(self) -> List[np.ndarray]:
         n = C.c_int32(0)
@@ -218,18 +248,36 @@ class BatchPlanner:
     # -- planning ---------------------------------------------------------
     def plan_packed(self, pb: PackedBatch) -> BatchResult:
         out = (_abi.Result * max(pb.n, 1))()
-        _abi.check(self._h, self._lib.fot_plan_batch(self._h, C.byref(pb.c), out))
+        if pb.mixed:
+            _abi.check(self._h, self._lib.fot_plan_batch_scenarios(self._h, C.byref(pb.c), pb.scenario_ptr(), out))
+        else:                                    # (= fot_plan_batch_scenarios with no scenario ids)
+            _abi.check(self._h, self._lib.fot_plan_batch(self._h, C.byref(pb.c), out))
         return BatchResult(out, pb.n, [not np.isnan(v) for v in pb.max_stop[: pb.n]])
 
     def plan_batch(self, requests: Sequence[PlanRequest], obstacle_dtype=np.float64) -> BatchResult:
         return self.plan_packed(PackedBatch(requests, obstacle_dtype))
 
-    def plan_packed_device(self, batch_struct: _abi.Batch, out_dev_ptr: int, stream: Optional[int] = None):
+    def plan_packed_device(self, batch_struct: _abi.Batch, out_dev_ptr: int, stream: Optional[int] = None,
+                           scenario=None):
         """Obstacles and results resident in HBM; enqueues on ``stream`` (a hipStream_t handle) and returns immediately.
         ``None`` / 0 = the handle's own stream, which no other stream waits for (torch's default stream has handle 0:
-        pass an explicit ``torch.cuda.Stream`` and follow up on that stream, or call ``synchronize()``)."""
-        _abi.check(self._h, self._lib.fot_plan_batch_device(self._h, C.byref(batch_struct), C.c_void_p(out_dev_ptr),
-                                                            C.c_void_p(stream) if stream else None))
+        pass an explicit ``torch.cuda.Stream`` and follow up on that stream, or call ``synchronize()``).
+        ``scenario``: the instances' scenario ids (a ``PackedBatch`` -- its ``scenario`` array --, an int32 array of
+        n_inst, or None = scenario 0 for all)."""
+        if scenario is None:
+            _abi.check(self._h, self._lib.fot_plan_batch_device(self._h, C.byref(batch_struct), C.c_void_p(out_dev_ptr),
+                                                                C.c_void_p(stream) if stream else None))
+            return
+        if isinstance(scenario, PackedBatch):
+            scen_ptr = scenario.scenario_ptr()
+        else:
+            scen = np.ascontiguousarray(scenario, dtype=np.int32)          # (read while the call enqueues)
+            if scen.shape != (batch_struct.n_inst,):
+                raise ValueError("scenario must hold one id per instance")
+            scen_ptr = scen.ctypes.data_as(C.POINTER(C.c_int32))
+        _abi.check(self._h, self._lib.fot_plan_batch_scenarios_device(self._h, C.byref(batch_struct), scen_ptr,
+                                                                      C.c_void_p(out_dev_ptr),
+                                                                      C.c_void_p(stream) if stream else None))
 
     @property
     def n_total_samples(self) -> int:

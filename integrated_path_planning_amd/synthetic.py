@@ -23,6 +23,18 @@ TARGET_SPEED = 30.0 / 3.6
 CONFIG2_PLANNER = dict(dt=0.1)                                       # module defaults otherwise
 CONFIG3_PLANNER = dict(dt=0.1, robot_radius=1.0, obstacle_radius=0.2, chance_epsilon=0.0)
 
+# The planner settings of the reference's three scenario files (scenario_01/02/03: waypoints, road width and lateral
+# step, speed and acceleration limits; dt 0.1 s, default horizon), as three scenarios of one handle:
+# (waypoints, planner keyword arguments) each.
+SCENARIO_PLANNERS = [
+    ((np.arange(0.0, 61.0, 10.0), np.zeros(7)),
+     dict(CONFIG3_PLANNER, max_road_width=2.7, d_road_w=0.3, max_speed=10.0, max_accel=2.0)),
+    ((np.arange(0.0, 51.0, 10.0), np.zeros(6)),
+     dict(CONFIG3_PLANNER, max_road_width=3.4, d_road_w=0.2, max_speed=6.0, max_accel=1.5)),
+    ((CURVED_WX, CURVED_WY),
+     dict(CONFIG3_PLANNER, max_road_width=1.2, d_road_w=0.3, max_speed=8.0, max_accel=2.0)),
+]
+
 
 @dataclass
 class Instance:

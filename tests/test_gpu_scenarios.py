@@ -1,0 +1,312 @@
+"""Scenarios on the GPU: instances of different planner configurations and reference paths in ONE plan call
+(fot_plan_batch_scenarios[_device]) give, byte for byte, the records a handle of each instance's own planner gives."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import eps_band
+from conftest import Golden, golden_names
+from helpers import EVAL_PATHS, TIGHT, request_from_golden, set_eval_path
+from integrated_path_planning_amd import _abi, synthetic as syn
+from integrated_path_planning_amd.batch import PackedBatch, request_from_instance
+from integrated_path_planning_amd.params import DT, MAX_T, make_params
+from integrated_path_planning_amd.planner import BatchPlanner
+
+pytestmark = pytest.mark.gpu
+
+
+def _grid_goldens():
+    """Every golden whose resolved planner has dt 0.1 s and max_t 5 s (one time grid: one handle can hold them all)."""
+    out = []
+    for name in golden_names():
+        g = Golden(name)
+        if "planner" not in g.meta or "wx" not in g.z:
+            continue
+        kw = g.planner_kwargs()
+        if abs(kw.get("dt", DT) - 0.1) < 1e-12 and abs(kw.get("max_t", MAX_T) - 5.0) < 1e-12:
+            out.append(g)
+    return out
+
+
+def _single(g, **kw):
+    return BatchPlanner(waypoints=(g["wx"], g["wy"]), **g.planner_kwargs(), **kw)
+
+
+def _mixed_handle(goldens):
+    """One handle: scenario 0 from goldens[0], scenario k from goldens[k]."""
+    bp = _single(goldens[0])
+    for k, g in enumerate(goldens[1:], start=1):
+        assert bp.add_scenario(waypoints=(g["wx"], g["wy"]), **g.planner_kwargs()) == k
+    return bp
+
+
+def _rec_bytes(rec):
+    return bytes(memoryview(rec).cast("B"))
+
+
+@pytest.fixture(scope="module")
+def grid_goldens():
+    gs = _grid_goldens()
+    assert 30 <= len(gs) <= _abi.MAX_SCENARIOS, len(gs)
+    return gs
+
+
+@pytest.fixture(scope="module")
+def single_records(grid_goldens):
+    """What a single-scenario handle gives for each golden: record bytes and candidate table."""
+    out = []
+    for g in grid_goldens:
+        bp = _single(g)
+        res = bp.plan_batch([request_from_golden(g)])
+        out.append((_rec_bytes(res.records[0]), bp.candidates(0)))
+        bp.close()
+    return out
+
+
+def _check_table(bp, inst, g, label):
+    cost, status, keep, nt = bp.candidates(inst)
+    assert len(cost) == len(g["cand_cost"]), label
+    np.testing.assert_array_equal(nt, g["cand_nt"], err_msg=label)
+    np.testing.assert_array_equal(keep, g["cand_keep"], err_msg=label)
+    np.testing.assert_allclose(cost, g["cand_cost"], rtol=TIGHT, atol=TIGHT, err_msg=label)
+    eps_band.check_status_table(bp, inst, status, g["cand_status"], label)
+
+
+@pytest.mark.parametrize("eval_path", EVAL_PATHS)
+def test_every_golden_in_one_call(grid_goldens, single_records, eval_path):
+    bp = _mixed_handle(grid_goldens)
+    set_eval_path(bp, eval_path)
+    order = np.random.default_rng(2024).permutation(len(grid_goldens))
+    reqs = []
+    for k in order:
+        r = request_from_golden(grid_goldens[k])
+        r.scenario = int(k)
+        reqs.append(r)
+    res = bp.plan_batch(reqs)
+    for i, k in enumerate(order):
+        g = grid_goldens[k]
+        assert _rec_bytes(res.records[i]) == single_records[k][0], f"{g.name} [{eval_path}]"
+        _check_table(bp, i, g, f"{g.name} mixed [{eval_path}]")
+    bp.close()
+
+
+def test_device_entry_at_size():
+    """The three scenario settings of the reference's scenario files, 256 instances spread over them, float32
+    obstacles in HBM, one call on a torch stream; against three single-scenario handles on the three subsets."""
+    import torch
+    dev = torch.device("cuda", 0)
+    (w0, kw0), *rest = syn.SCENARIO_PLANNERS
+    bp = BatchPlanner(waypoints=w0, device=0, **kw0)
+    for k, (w, kw) in enumerate(rest, start=1):
+        assert bp.add_scenario(waypoints=w, **kw) == k
+    n = 256
+    reqs = []
+    for i in range(n):
+        r = request_from_instance(syn.config3_instance(i, S=8, P=12))
+        r.scenario = (i * 7 // 5) % 3
+        reqs.append(r)
+
+    def run(planner, rq, scenario):
+        pb = PackedBatch(rq, np.float32)
+        dyn = torch.from_numpy(pb.dyn_xy).to(dev)
+        out = torch.zeros(len(rq) * _abi.RESULT_BYTES, dtype=torch.uint8, device=dev)
+        st = torch.cuda.Stream(device=dev)
+        planner.plan_packed_device(pb.with_device_obstacles(None, dyn.data_ptr()), out.data_ptr(), st.cuda_stream,
+                                   scenario=pb if scenario else None)
+        st.synchronize()
+        raw = out.cpu().numpy().tobytes()
+        return [raw[j * _abi.RESULT_BYTES:(j + 1) * _abi.RESULT_BYTES] for j in range(len(rq))]
+
+    mixed = run(bp, reqs, True)
+    n_ok = 0
+    for k, (w, kw) in enumerate(syn.SCENARIO_PLANNERS):
+        idx = [i for i in range(n) if reqs[i].scenario == k]
+        one = BatchPlanner(waypoints=w, device=0, **kw)
+        sub = []
+        for i in idx:
+            r = request_from_instance(syn.config3_instance(i, S=8, P=12))
+            sub.append(r)
+        want = run(one, sub, False)
+        for j, i in enumerate(idx):
+            assert mixed[i] == want[j], f"instance {i} (scenario {k})"
+            n_ok += _abi.Result.from_buffer_copy(want[j]).status == _abi.PLAN_OK
+        one.close()
+    assert n_ok > 0
+    bp.close()
+
+
+def _chain(g, n=3):
+    """An escalation-style chain on one planner: the same ego planned again with tighter settings, nearest-point cache
+    chained (integrated_simulator.py:602-644)."""
+    reqs = []
+    for j in range(n):
+        r = request_from_golden(g)
+        r.target_speed = max(0.5, r.target_speed * (1.0 - 0.3 * j))
+        if j > 0:
+            r.chain_prev_s = True
+            r.prev_s = None
+            r.overrides = {"max_accel": 1.0 + 0.5 * j}
+        reqs.append(r)
+    return reqs
+
+
+def test_chains(grid_goldens):
+    gs = grid_goldens[:6]
+    bp = _mixed_handle(gs)
+    k = 3
+    chain = _chain(gs[k])
+    want = _single(gs[k]).plan_batch(_chain(gs[k]))
+    reqs = []
+    for s in (1, 0, 5):
+        r = request_from_golden(gs[s]); r.scenario = s; reqs.append(r)
+    for r in chain:
+        r.scenario = k
+    reqs[2:2] = chain                                             # the chain in the middle of the mixed batch
+    res = bp.plan_batch(reqs)
+    for j in range(len(chain)):
+        assert _rec_bytes(res.records[2 + j]) == _rec_bytes(want.records[j]), j
+    # a chain across scenarios is one planner continuing on another's path: refused
+    bad = [request_from_golden(gs[0])] + _chain(gs[1])[1:]
+    bad[0].scenario = 0
+    for r in bad[1:]:
+        r.scenario = 1
+    with pytest.raises(_abi.FotError) as e:
+        bp.plan_batch(bad)
+    assert e.value.code == _abi.ERR_INVALID
+    bp.close()
+
+
+def _assert_plans_golden(bp, g, scenario=0):
+    r = request_from_golden(g)
+    r.scenario = scenario
+    res = bp.plan_batch([r])
+    assert res.records[0].best_index == int(g["best_index"])
+    cost, status, _, _ = bp.candidates(0)
+    np.testing.assert_array_equal(status, g["cand_status"].astype(np.int32))
+
+
+def test_errors_leave_the_handle_usable(grid_goldens):
+    g0, g1 = grid_goldens[0], grid_goldens[1]
+    bp = _single(g0)
+    lib, h = bp._lib, bp._h
+    sid = C.c_int32(-1)
+
+    def add(**over):
+        kw = dict(g1.planner_kwargs()); kw.update(over)
+        return lib.fot_add_scenario(h, C.byref(make_params(**kw)), C.byref(sid))
+
+    assert add(dt=0.2) == _abi.ERR_INVALID                        # another time grid
+    _assert_plans_golden(bp, g0)
+    assert add(max_t=4.5) == _abi.ERR_INVALID
+    _assert_plans_golden(bp, g0)
+    assert add(d_road_w=-1.0) == _abi.ERR_INVALID                 # what fot_create refuses, refused alike
+    p = make_params(**g1.planner_kwargs())
+    p.n_circles = _abi.MAX_CIRCLES + 1
+    assert lib.fot_add_scenario(h, C.byref(p), C.byref(sid)) == _abi.ERR_UNSUPPORTED
+    _assert_plans_golden(bp, g0)
+    # scenario 1 without a path yet
+    assert add() == _abi.OK and sid.value == 1
+    r = request_from_golden(g1); r.scenario = 1
+    with pytest.raises(_abi.FotError) as e:
+        bp.plan_batch([request_from_golden(g0), r])
+    assert e.value.code == _abi.ERR_NO_PATH_SET
+    _assert_plans_golden(bp, g0)
+    bp.set_waypoints(g1["wx"], g1["wy"], scenario=1)
+    _assert_plans_golden(bp, g1, scenario=1)
+    # unknown ids
+    r.scenario = 7
+    with pytest.raises(_abi.FotError) as e:
+        bp.plan_batch([r])
+    assert e.value.code == _abi.ERR_INVALID
+    assert lib.fot_set_scenario_path_waypoints(h, 9, len(g1["wx"]), g1["wx"].ctypes.data_as(C.POINTER(C.c_double)),
+                                               g1["wy"].ctypes.data_as(C.POINTER(C.c_double))) == _abi.ERR_INVALID
+    _assert_plans_golden(bp, g0)
+    # up to FOT_MAX_SCENARIOS, then refused
+    for k in range(2, _abi.MAX_SCENARIOS):
+        assert bp.add_scenario(waypoints=(g1["wx"], g1["wy"]), **g1.planner_kwargs()) == k
+    assert add() == _abi.ERR_UNSUPPORTED
+    _assert_plans_golden(bp, g0)
+    _assert_plans_golden(bp, g1, scenario=_abi.MAX_SCENARIOS - 1)
+    bp.close()
+
+
+@pytest.mark.parametrize("cut", [1, 2], ids=["wave", "group"])
+def test_scenario_zero_unchanged(grid_goldens, cut):
+    """After scenarios are added, the calls without scenario ids are scenario 0's: records and candidate tables
+    byte-identical to a fresh handle's, host and device entry points."""
+    import torch
+    gs = grid_goldens[:8]
+    fresh = _single(gs[0])
+    bp = _mixed_handle(gs)
+    for p in (fresh, bp):
+        p.set_tile_cut(cut)
+    reqs = [request_from_golden(g) for g in gs]                   # every ego, on scenario 0's path and planner
+    a, b = fresh.plan_batch(reqs), bp.plan_batch(reqs)
+    for i in range(len(reqs)):
+        assert _rec_bytes(a.records[i]) == _rec_bytes(b.records[i]), i
+        for x, y in zip(fresh.candidates(i), bp.candidates(i)):
+            np.testing.assert_array_equal(x, y)
+    dev = torch.device("cuda", 0)
+    pb = PackedBatch(reqs)
+    dyn = torch.from_numpy(pb.dyn_xy).to(dev) if pb.dyn_xy.size else None
+    stat = torch.from_numpy(pb.static_xy).to(dev) if pb.static_xy.size else None
+    outs = []
+    for p in (fresh, bp):
+        out = torch.zeros(len(reqs) * _abi.RESULT_BYTES, dtype=torch.uint8, device=dev)
+        st = torch.cuda.Stream(device=dev)
+        p.plan_packed_device(pb.with_device_obstacles(stat.data_ptr() if stat is not None else None,
+                                                      dyn.data_ptr() if dyn is not None else None),
+                             out.data_ptr(), st.cuda_stream)
+        st.synchronize()
+        outs.append(out.cpu().numpy().tobytes())
+        outs.append([p.candidates(i) for i in range(len(reqs))])
+    assert outs[0] == outs[2]
+    for x, y in zip(outs[1], outs[3]):
+        for u, v in zip(x, y):
+            np.testing.assert_array_equal(u, v)
+    fresh.close(); bp.close()
+
+
+def test_debug_accessors_on_the_instances_scenario(grid_goldens):
+    gs = grid_goldens[:5]
+    bp = _mixed_handle(gs)
+    reqs = []
+    for k in (2, 0, 4, 1, 3):
+        r = request_from_golden(gs[k]); r.scenario = k; reqs.append(r)
+    bp.plan_batch(reqs)
+    for i, k in enumerate((2, 0, 4, 1, 3)):
+        one = _single(gs[k])
+        one.plan_batch([request_from_golden(gs[k])])
+        m1, m2 = bp.margins(i), one.margins(0)
+        np.testing.assert_array_equal(m1, m2)
+        n_cand = len(one.candidates(0)[0])
+        for idx in sorted({0, n_cand // 2, n_cand - 1}):
+            p1, p2 = bp.candidate_path(idx, inst=i), one.candidate_path(idx, inst=0)
+            for f in _abi.PATH_FIELDS:
+                np.testing.assert_array_equal(np.array(getattr(p1, f)), np.array(getattr(p2, f)), err_msg=f"{k} {idx} {f}")
+        one.close()
+    bp.close()
+
+
+def test_lane_split_keeps_records(grid_goldens, monkeypatch):
+    """A mixed batch large enough for the lanes (FOT_LANES=4: four sub-batches on four streams) gives the records of
+    the unsplit call."""
+    gs = grid_goldens[:10]
+    rng = np.random.default_rng(11)
+    reqs = []
+    for i in range(160):
+        k = int(rng.integers(0, len(gs)))
+        r = request_from_golden(gs[k]); r.scenario = k; reqs.append(r)
+    whole = _mixed_handle(gs)
+    a = whole.plan_batch(reqs)
+    monkeypatch.setenv("FOT_LANES", "4")
+    split = _mixed_handle(gs)
+    monkeypatch.delenv("FOT_LANES")
+    b = split.plan_batch(reqs)
+    for i in range(len(reqs)):
+        assert _rec_bytes(a.records[i]) == _rec_bytes(b.records[i]), i
+    for i in (0, 57, 159):
+        for x, y in zip(whole.candidates(i), split.candidates(i)):
+            np.testing.assert_array_equal(x, y)
+    whole.close(); split.close()
