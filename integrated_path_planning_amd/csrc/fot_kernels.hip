@@ -430,6 +430,27 @@ __device__ __forceinline__ float min_sqdist32_f16(const f16 &c, float fx, float 
     return fminf(m, t[3].y);
 }
 
+// smallest float32 squared distance from (fx, fy) to the entries of chunks [0, n) behind cp: the double-buffered
+// walk of FusedSink::put32 (same hand-issued loads, same prefetch of one chunk past the list) with one running
+// minimum per lane instead of a near bit per chunk
+__device__ __forceinline__ float min_sqdist32_walk(const f2x8 *cp, int n, float &fx, float fy)
+{
+    float m = INFINITY;
+    f16 ca, cb;
+    sload_chunk<0>(ca, cp);
+    swait_chunk(ca);
+    for (int c = 0; c < n; c += 2) {
+        sload_chunk_ahead<64>(cb, cp, fx);
+        m = fminf(m, min_sqdist32_f16(ca, fx, fy));
+        swait_chunk(cb);
+        sload_chunk_ahead<128>(ca, cp, fx);
+        if (c + 1 < n) m = fminf(m, min_sqdist32_f16(cb, fx, fy));  // wave-uniform
+        swait_chunk(ca);
+        cp += 2;
+    }
+    return m;
+}
+
 // EntryCollider (fot_math.hpp) with the chunk walk on the scalar unit.  Everything that addresses the entry lists is
 // wave-uniform (instance, time step), so one chunk (8 obstacles, 64 B) is one s_load_dwordx16 shared by the 64
 // candidates of the wave; each lane keeps the float32 minimum squared distance of the chunk and only chunks that
@@ -545,8 +566,18 @@ struct FusedSink {
         if (n_chunks == 0) return;                                // wave-uniform
         if (!alive || hit) return;                                // lanes whose collision outcome is already settled
         float fx = fx_in;                                         // (tied into the hand-issued loads below)
-        bool sure = false;                                        // some obstacle is certainly within its radius
         const f2x8 *row = chunks + (int64_t)k * chunks_per_k + c_lo;
+        if (thr_fatal >= 0.0f) {                                  // wave-uniform: a certain hit settles the candidate
+            // Min-only walk: one running minimum over every chunk of the step, no per-chunk compare, bit or exec-mask
+            // work.  A minimum at or below thr_fatal is a certain hit (some chunk's minimum is); a minimum above thr
+            // means that no chunk of the step is near, so the classic walk below would neither set a near bit nor
+            // re-check anything.  Only the lanes in between -- a float32 distance in the thin band (thr_sure, thr] --
+            // walk the step again below, and there decide exactly as every lane did before.
+            const float m = min_sqdist32_walk(row, n_chunks, fx, fy);
+            if (m <= thr_fatal) { hit = true; return; }
+            if (!(m <= thr)) return;
+        }
+        bool sure = false;                                        // some obstacle is certainly within its radius
         for (int c0 = 0; c0 < n_chunks; c0 += 32) {               // 32 chunks per pass: one bit per chunk and lane
             const int nb = n_chunks - c0 < 32 ? n_chunks - c0 : 32;   // (may be odd: the last pair then tests one chunk)
             const f2x8 *cp = row + c0;
