@@ -168,10 +168,10 @@ const char *fot_version(void);
  * corruption").  out[i], i < cap: FOT_ABI_VERSION, sizeof of fot_params, fot_ego, fot_overrides, fot_result, fot_batch,
  * fot_resample_params, fot_safety, fot_loop_frame, fot_loop_request, fot_wire_header, then FOT_MAX_NT, FOT_MAX_CIRCLES,
  * FOT_MAX_TI, FOT_MAX_TV, FOT_MAX_BRAKE, FOT_MAX_SAMPLES, FOT_MAX_PRED_LEN, FOT_PROFILE_KERNELS, FOT_MARGIN_GROUPS,
- * sizeof of fot_loop_config, fot_loop_step_out.
+ * sizeof of fot_loop_config, fot_loop_step_out, fot_loop_replay, fot_loop_run_out.
  * Returns the number of words the library knows (FOT_ABI_INFO_WORDS of ITS header). */
-#define FOT_ABI_VERSION 4
-#define FOT_ABI_INFO_WORDS 22
+#define FOT_ABI_VERSION 5
+#define FOT_ABI_INFO_WORDS 24
 int32_t fot_abi_info(int32_t cap, int32_t *out);
 
 /* FrenetPlanner.__init__ (frenet_planner.py:149-225).  device < 0: current device. */
@@ -439,6 +439,71 @@ typedef struct fot_loop_step_out {
 } fot_loop_step_out;
 int fot_loop_begin(fot_handle *h, int32_t n_episodes, const fot_loop_config *cfg, const double *ego5);
 int fot_loop_step(fot_handle *h, const fot_loop_frame *frame, const int32_t *episode, fot_loop_step_out *out);
+
+/* ---- whole replayed episodes behind one call ------------------------------------------------------------------------
+ * With replayed pedestrians nothing in an episode depends on the caller between two lock steps, so the caller hands the
+ * recording over once and the library runs the steps itself: a C caller's episode is three calls,
+ *   fot_loop_begin (slots, fail-safe constants, initial egos) -> fot_loop_set_replay (recording, observer and predictor
+ *   constants, goal) -> fot_loop_run (up to max_steps lock steps; again until it returns 0).
+ * fot_loop_set_replay copies the recording of every episode slot into HBM, where it stays, and runs the warm-up
+ * (warmup_frames frames that only fill the observer, integrated_simulator.py:406-422; int(obs_len * sgan_dt / dt) in the
+ * reference).  It needs a fot_loop_begin with the same number of slots before it.  Refusals -- the codes fot_loop_plan has
+ * for the same faults; a refused call changes nothing: no fot_loop_begin / n_slots differs from its count / ped_off not
+ * starting at 0 or decreasing / a slot with n_frames < 1 or > n_frames_max / obs_len < 2 / bad predictor parameters
+ * (FOT_ERR_INVALID), pred_len > FOT_MAX_PRED_LEN or n_dense + 1 > FOT_MAX_NT (FOT_ERR_UNSUPPORTED).
+ * Constant-velocity predictor only: a frame with dist_raw samples needs a producer every step and stays with
+ * fot_loop_step.  Scenario 0, like every fot_loop_*.
+ *
+ * fot_loop_run: one lock step is what the closed loop around fot_loop_step does, in this order: the replay frame and the
+ * observer's clock advance (observer.py:28-102, its 1e-9 sampling tolerance, samples rounded through float32), the frame
+ * of the running episodes is built ON THE DEVICE from the resident recording, the prepend decision per episode
+ * (integrated_simulator.py:503-511), the body of fot_loop_step, then termination: `collision` of the new state's metrics
+ * ends the episode with code 1, else s_end - s_now < goal_distance with code 2.  The step's records stay in HBM; the host
+ * reads a digest of each (status, counts, cost, state updates, sample 1).  Returns the number of lock steps executed
+ * (0: no episode runs any more) or a negative error.
+ * Per-step outputs, entry [k][slot] of arrays sized max_steps x n_slots (any pointer may be NULL): entries of a slot that
+ * does not run at step k are not written, except followed = -1.  frame / obs_*_frame: replay frame counters (row
+ * min(frame, n_frames[slot] - 1) of a slot's recording); obs_last_frame / obs_prev_frame are the frames of the observer's
+ * last two samples, -1 while it fills: with the staleness all a caller needs to rebuild the step's pedestrian frame and
+ * prediction (fot_predict_cv) from its own copy of the recording.
+ * paths non-NULL: the first n_keep samples of the 15 path arrays of the record every running slot followed, as one dense
+ * block [k][15][n_slots][n_total] (fot_result array order t .. c, n_total = fot_wire_n_total), zero beyond n_keep and for
+ * slots without a path; it is kept in HBM during the run and copied out once at the end of the call.
+ * While a replay is set fot_loop_step on the same handle is refused (FOT_ERR_INVALID): the handle owns the clock.  The
+ * next fot_loop_begin drops the replay. */
+typedef struct fot_loop_replay {
+    int32_t n_slots;                /* == n_episodes of fot_loop_begin */
+    int32_t n_frames_max;           /* frames (rows) of pos / vel */
+    int32_t obs_len, pred_len;      /* observer window; predictor (trajectory_predictor.py:188) */
+    int32_t warmup_frames;
+    int32_t use_footprint;          /* as fot_safety_metrics_batch */
+    const int32_t *ped_off;         /* [n_slots + 1]: pedestrians of slot e = columns [ped_off[e], ped_off[e+1]) */
+    const int32_t *n_frames;        /* [n_slots] recorded frames of each slot (>= 1); its last frame is held afterwards */
+    const double *pos, *vel;        /* [n_frames_max][ped_off[n_slots]][2] host memory, frame 0 = time 0 before warm-up */
+    fot_resample_params rp;
+    double ego_radius, ped_radius;
+    double s_end;                   /* arc length of the reference path's end */
+    double goal_distance;           /* the goal test's distance (2.0 m in the reference, integrated_simulator.py:873-883) */
+} fot_loop_replay;
+typedef struct fot_loop_run_out {
+    double *ego;                    /* [max_steps][n_slots][5] the new ego states */
+    double *jerk;                   /* [max_steps][n_slots] */
+    int32_t *state;                 /* machine state after the step */
+    int32_t *stats;                 /* [max_steps][n_slots][8], a row of -1: None */
+    int32_t *followed;              /* 1: a path was followed, 0: emergency stop, -1: the slot does not run at this step */
+    int32_t *keep;                  /* samples of the followed path (0: none) */
+    double *cost;
+    fot_safety *after;              /* metrics of the new ego states */
+    double *s_now;                  /* arc length of the new state's nearest path point */
+    int32_t *frame;                 /* [max_steps] replay frame of the step */
+    int32_t *obs_last_frame, *obs_prev_frame;   /* [max_steps] */
+    double *staleness;              /* [max_steps] */
+    int32_t *steps;                 /* [n_slots] lock steps the slot has taken since fot_loop_set_replay */
+    int32_t *termination;           /* [n_slots] 0: runs, 1: collision, 2: goal */
+    double *paths;                  /* [max_steps][15][n_slots][n_total], or NULL */
+} fot_loop_run_out;
+int fot_loop_set_replay(fot_handle *h, const fot_loop_replay *replay);
+int fot_loop_run(fot_handle *h, int32_t max_steps, fot_loop_run_out *out);
 
 /* Host utility (no GPU): the first kmax samples of the 15 path arrays of records[index[i]], i < n, as one dense block
  * out[15][n][kmax] in fot_result array order (t .. c) -- what a history keeps of a step's records. */

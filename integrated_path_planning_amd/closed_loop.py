@@ -231,6 +231,60 @@ class EpisodeHistory:
 _TERMINATION = (None, "collision", "goal", "timeout")
 
 
+class _ResidentStep(dict):
+    """Lock step k of one fot_loop_run call as the dictionary ``_step_native`` writes (same keys and dtypes), filled
+    when somebody first reads it: the pedestrian frame and the observer's samples are looked up in the recording by the
+    frame indices the library reported."""
+
+    def __init__(self, loop: "BatchedClosedLoop", out: dict, k: int, t: float, keep_paths: bool):
+        super().__init__()
+        self._src = (loop, out, k, t, keep_paths)
+
+    def _fill(self) -> None:
+        if self._src is None:
+            return
+        loop, o, k, t, keep_paths = self._src
+        self._src = None
+        sel = np.flatnonzero(o["followed"][k] >= 0)
+        n = len(sel)
+        counts = (loop.ped_off[sel + 1] - loop.ped_off[sel]).astype(np.int64)
+        off = np.concatenate([[0], np.cumsum(counts)])
+        slot = np.full(len(loop.episodes), -1, np.int64)
+        slot[sel] = np.arange(n)
+        rows = None if n == len(loop.episodes) else loop._rows_of(sel)
+
+        def frame(which, f):
+            a = loop._ped_all[which]
+            a = a[min(int(f), len(a) - 1)]
+            return a if rows is None else a[rows]
+
+        pred_src = None
+        if o["obs_last_frame"][k] >= 0:
+            o32 = np.stack([frame("trajectories", o["obs_prev_frame"][k]), frame("trajectories", o["obs_last_frame"][k])],
+                           axis=0).astype(np.float32)
+            pred_src = (o32, float(o["staleness"][k]))
+        if keep_paths:
+            paths = {f: o["paths"][k, j][sel] for j, f in enumerate(_abi.PATH_FIELDS)}
+        else:
+            paths = {f: np.zeros((n, int(o["keep"][k].max()) if n else 0)) for f in _abi.PATH_FIELDS}
+        self.update(time=t, slot=slot, off=off, ego=o["ego"][k][sel], jerk=o["jerk"][k][sel],
+                    state=o["state"][k][sel].astype(np.int64), pos=frame("trajectories", o["frame"][k]),
+                    vel=frame("velocities", o["frame"][k]), pred=None, pred_src=pred_src, after=o["after"][k][sel],
+                    stats=o["stats"][k][sel].astype(np.int64), has_path=o["followed"][k][sel] > 0,
+                    keep=o["keep"][k][sel].astype(np.int64), cost=o["cost"][k][sel], paths=paths, t_pred=0.0,
+                    t_plan=o["t_plan"], sel=sel)
+
+    def __missing__(self, key):
+        if self._src is None:
+            raise KeyError(key)
+        self._fill()
+        return self[key]
+
+    def get(self, key, default=None):
+        self._fill()
+        return super().get(key, default)
+
+
 class Episode:
     """View of one episode of the loop: its history, how many steps it ran and why it ended (None while it runs)."""
 
@@ -327,10 +381,11 @@ class BatchedClosedLoop:
     """
 
     MAX_REPLAN = 3                                               # integrated_simulator.py:383
+    GOAL_DISTANCE = 2.0                                          # integrated_simulator.py:873-883
 
     def __init__(self, config, ped_tracks: Sequence[np.ndarray], ego_initial_states: Optional[Sequence] = None,
                  device: int = -1, engine=None, resampler=None, sample_source=None, fused: Optional[bool] = None,
-                 device_samples: bool = False):
+                 device_samples: bool = False, resident: bool = False):
         """sample_source: the multi-sample predictor in front of the planner -- a callable
         ``(obs_last [P, 2], obs_prev [P, 2]) -> raw samples [S, pred_len, P, 2]`` at the predictor's own time step
         (what S forward passes of Social-GAN on PyTorch-ROCm return for the pedestrians of all running episodes; the
@@ -339,7 +394,16 @@ class BatchedClosedLoop:
         to the mean (``predict_single_best``, trajectory_predictor.py:340-352).  None: the constant-velocity predictor.
         device_samples: the sample source returns a ``torch`` tensor in DEVICE memory ([S, pred_len, sum P, 2], float32 or
         float64) -- Social-GAN's own output on PyTorch-ROCm.  With ``distribution_aware_planning`` the samples then never
-        leave the GPU: they are resampled into the planner's tensor inside the lock step's one call (fot_loop_step)."""
+        leave the GPU: they are resampled into the planner's tensor inside the lock step's one call (fot_loop_step).
+        resident: the whole episode inside the library (fot_loop_set_replay / fot_loop_run): the recording is uploaded to
+        HBM once, and ``run(n)`` is a few calls that execute n lock steps each without coming back to Python in between;
+        ``step()`` is ``run(1)``.  Constant-velocity predictor on the library's own engine only.  The loop's arrays
+        (``ego``, ``sm.state``, ``alive``, ...) are brought up to date after every call; the Python ``observer`` is not
+        advanced (the handle owns the clock)."""
+        self._resident = bool(resident)
+        if self._resident and (sample_source is not None or engine is not None or resampler is not None or fused not in (None, True)):
+            raise ValueError("resident=True needs the constant-velocity predictor on the library's own engine "
+                             "(no sample_source, engine or resampler; the one-call step)")
         self.config = config if not isinstance(config, dict) else _Cfg(config)
         c = self.config
         self.dt = float(c.dt)
@@ -449,6 +513,12 @@ class BatchedClosedLoop:
             lc.emergency_accel, lc.emergency_lat_accel = float(sm_.e_accel), float(sm_.e_lat)
             lc.max_replan = self.MAX_REPLAN
             self.engine.loop_begin(lc, self.ego)
+        if self._resident:
+            self.engine.loop_set_replay(
+                self.ped_off, self.n_frames, self._ped_all["trajectories"], self._ped_all["velocities"],
+                obs_len=c.obs_len, pred_len=self.resampler.pred_len, rp=self.resampler.params,
+                warmup_frames=int(c.obs_len * self.sgan_dt / c.dt), ego_radius=self.ego_radius, ped_radius=self.ped_radius,
+                use_footprint=self.footprint is not None, s_end=self.s_end, goal_distance=self.GOAL_DISTANCE)
 
     def close(self) -> None:
         """Release the libfot handle (streams, workspace) now rather than at garbage collection."""
@@ -559,6 +629,8 @@ class BatchedClosedLoop:
     # ------------------------------------------------------------------------------------------------------
     def step(self) -> int:
         """One lock step of every running episode (integrated_simulator.py:678-747); returns how many ran."""
+        if self._resident:
+            return self._run_resident(1)
         sel = np.flatnonzero(self.alive)
         n = len(sel)
         if n == 0:
@@ -909,9 +981,56 @@ class BatchedClosedLoop:
                           None if s["pred"] is None else s["pred"][lo:hi], path, m,
                           {"prediction": s["t_pred"], "planning": s["t_plan"]})
 
-    def run(self, n_steps: Optional[int] = None) -> List[EpisodeHistory]:
+    def _run_resident(self, n_steps: int, keep_paths: bool = True) -> int:
+        """n_steps lock steps inside the library (fot_loop_run), in calls whose history block fits the arena's current
+        chunk; the loop's arrays follow the handle after every call.  Returns how many episodes ran the first step."""
+        first, left = None, int(n_steps)
+        while left > 0 and self.alive.any():
+            pos, paths_out = len(self._steps), None
+            while keep_paths and pos >= self._arena_steps:
+                self._grow_arena(64)
+            for chunk in self._arena if keep_paths else ():
+                if pos < len(chunk):
+                    paths_out = chunk[pos: pos + left]
+                    break
+                pos -= len(chunk)
+            ask = len(paths_out) if keep_paths else left
+            t0 = time.perf_counter()
+            o = self.engine.loop_run(ask, keep_paths=keep_paths, paths_out=paths_out)
+            wall = time.perf_counter() - t0
+            done = o["n_steps"]
+            if done == 0:
+                break
+            ran = o["followed"] >= 0                                   # [done, slots]
+            o["t_plan"] = wall / max(int(ran.sum()), 1)
+            if first is None:
+                first = int(ran[0].sum())
+            for k in range(done):
+                self._steps.append(_ResidentStep(self, o, k, self.time, keep_paths))
+                self.time += self.dt
+                self.ped_time += self.dt
+            self.frame += done
+            took = np.flatnonzero(ran.any(axis=0))
+            last = done - 1 - np.argmax(ran[::-1, took], axis=0)      # the last step of the call each slot ran
+            self.ego[took], self.jerk[took] = o["ego"][last, took], o["jerk"][last, took]
+            self.sm.state[took], self.last_stats[took] = o["state"][last, took], o["stats"][last, took]
+            self.step_counts += ran.sum(axis=0)
+            code = o["termination"]
+            self.termination[code != 0] = code[code != 0]
+            self.alive[:] = code == 0
+            left -= done
+        return first or 0
+
+    def run(self, n_steps: Optional[int] = None, keep_paths: bool = True) -> List[EpisodeHistory]:
+        """keep_paths=False (resident loops only): the followed paths are not brought back from the device; a step's
+        record then shows zeros in their place."""
         if n_steps is None:
             n_steps = int(self.config.total_time / self.config.dt)
+        if self._resident:
+            self._run_resident(n_steps, keep_paths)
+            n_steps = 0
+        elif not keep_paths:
+            raise ValueError("keep_paths=False needs resident=True")
         for _ in range(n_steps):
             if self.step() == 0:
                 break

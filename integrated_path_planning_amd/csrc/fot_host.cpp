@@ -18,6 +18,7 @@
 
 #include "fot_kernels.h"
 #include "fot_math.hpp"
+#include "fot_replay.hpp"
 #include "fot_setup.hpp"
 
 using namespace fot;
@@ -122,9 +123,33 @@ struct LoopEpisodes {
     std::vector<int32_t> stats;              // [n][8] last_check_stats, a row of -1: None
 };
 
+// fot_loop_set_replay / fot_loop_run: the recording (host copy for the prepend test, HBM copy for the frame kernel), the
+// replay clock and what a resident step keeps on the device
+struct LoopReplay {
+    bool set = false;
+    fot_loop_replay cfg = fot_loop_replay();     // the constants (its pointers are cleared)
+    int n_cols = 0, n_dense = 0, max_lvl = 1;
+    std::vector<int32_t> ped_off, n_frames;      // per slot
+    std::vector<double> pos, vel;                // [n_frames_max][n_cols][2]
+    ReplayClock clock;
+    std::vector<uint8_t> alive;
+    std::vector<int32_t> steps, termination;
+    DevBuf dPos, dVel, dTab;                     // the recording; slot_ped0 | slot_frames
+    DevBuf dFrame;                               // the step's compacted frame (FrameDev)
+    DevBuf dRec, dHist;                          // the step's records; followed paths of the call's steps
+    PinnedBuf hStage, hDigest, hHistTab, hWord;  // FrameStage | LoopDigest[] | followed record + slot | completion words
+    int32_t seq = 0;                             // value the completion words are raised to next
+    void release()
+    {
+        dPos.release(); dVel.release(); dTab.release(); dFrame.release(); dRec.release(); dHist.release();
+        hStage.release(); hDigest.release(); hHistTab.release(); hWord.release();
+    }
+};
+
 // fot_loop_*: what one closed-loop step leaves behind for the step's later calls
 struct LoopState {
     LoopEpisodes ep;
+    LoopReplay replay;
     PinnedBuf hFrame, hObserve, hOut, hRec;  // frame inputs | fot_loop_observe's inputs | small outputs | records
     DevBuf dDyn, dStatic;                    // the prediction tensor; the static points, one copy per request
     std::vector<double> static_xy;           // host copy of the static points
@@ -135,7 +160,7 @@ struct LoopState {
     int dist_S = 0;                          // > 0: the blocks are [dist_S][P_e][t_len][2] distributions
     bool have_frame = false;
     const void *dyn_ptr = nullptr;           // the tensor: dDyn, or the pinned current positions (predictor not ready)
-    const int32_t *p_off = nullptr;          // the frame's pedestrians in hFrame
+    const int32_t *p_off = nullptr;          // the frame's pedestrians in hFrame (a resident step: in HBM, LoopReplay::dFrame)
     const double *p_pos = nullptr, *p_vel = nullptr;
     double ego_radius = 0.0, ped_radius = 0.0;
     int use_footprint = 0;
@@ -143,7 +168,7 @@ struct LoopState {
     void release()
     {
         hFrame.release(); hObserve.release(); hOut.release(); hRec.release();
-        dDyn.release(); dStatic.release();
+        dDyn.release(); dStatic.release(); replay.release();
     }
 };
 
@@ -683,6 +708,7 @@ int32_t fot_abi_info(int32_t cap, int32_t *out)
         FOT_MAX_NT, FOT_MAX_CIRCLES, FOT_MAX_TI, FOT_MAX_TV, FOT_MAX_BRAKE, FOT_MAX_SAMPLES, FOT_MAX_PRED_LEN,
         FOT_PROFILE_KERNELS, FOT_MARGIN_GROUPS,
         (int32_t)sizeof(fot_loop_config), (int32_t)sizeof(fot_loop_step_out),
+        (int32_t)sizeof(fot_loop_replay), (int32_t)sizeof(fot_loop_run_out),
     };
     for (int i = 0; i < FOT_ABI_INFO_WORDS && i < cap && out; ++i) out[i] = v[i];
     return FOT_ABI_INFO_WORDS;
@@ -1117,6 +1143,50 @@ int fot_loop_set_static(fot_handle *h, int32_t n_points, const double *xy)
 
 namespace {
 
+// The requests of a loop step as one plan call against the step's tensor (LoopState: pedestrian counts, block offsets and
+// lengths of the frame's episodes), records to rec_out: enqueued on st, not waited for.
+int loop_enqueue_requests(fot_handle *h, int32_t n_req, const fot_loop_request *req, fot_result *rec_out, hipStream_t st,
+                          bool sync_caller)
+{
+    LoopState &L = h->loop;
+    const int n_ep = (int)L.ped_off.size() - 1;
+    const int n_static = (int)(L.static_xy.size() / 2);
+    if (n_static > 0 && L.static_tiles < n_req) {              // (grows a few times in the life of a loop)
+        const int tiles = std::max(n_req, 2 * L.static_tiles);
+        std::vector<double> rep((size_t)tiles * L.static_xy.size());
+        for (int t = 0; t < tiles; ++t)
+            std::memcpy(rep.data() + (size_t)t * L.static_xy.size(), L.static_xy.data(), sizeof(double) * L.static_xy.size());
+        HIP_TRY(h, hipStreamSynchronize(st));
+        HIP_TRY(h, L.dStatic.ensure(sizeof(double) * rep.size()));
+        HIP_TRY(h, hipMemcpy(L.dStatic.p, rep.data(), sizeof(double) * rep.size(), hipMemcpyHostToDevice));
+        L.static_tiles = tiles;
+    }
+    std::vector<fot_ego> ego((size_t)n_req);
+    std::vector<fot_overrides> ov((size_t)n_req);
+    std::vector<double> tgt((size_t)n_req), stop((size_t)n_req);
+    std::vector<int32_t> s_off((size_t)n_req + 1), dims(4 * (size_t)n_req);
+    std::vector<int64_t> d_off((size_t)n_req);
+    bool any_dyn = false;
+    for (int j = 0; j < n_req; ++j) {
+        const int e = req[j].episode;
+        if (e < 0 || e >= n_ep) return fail(h, FOT_ERR_INVALID, "request: episode out of range");
+        ego[j] = req[j].ego; ov[j] = req[j].overrides; tgt[j] = req[j].target_speed; stop[j] = req[j].max_stop_distance;
+        s_off[j] = j * n_static;
+        const int P_e = L.ped_off[e + 1] - L.ped_off[e];
+        d_off[j] = L.blk_off[e];
+        dims[4 * j] = P_e > 0 ? (L.dist_S > 0 ? FOT_DYN_DISTRIBUTION : FOT_DYN_SINGLE) : FOT_DYN_NONE;
+        dims[4 * j + 1] = L.dist_S > 0 ? L.dist_S : 1; dims[4 * j + 2] = P_e; dims[4 * j + 3] = L.t_len[e];
+        any_dyn = any_dyn || P_e > 0;
+    }
+    s_off[n_req] = n_req * n_static;
+    fot_batch b = fot_batch();
+    b.n_inst = n_req; b.obstacle_dtype = FOT_F64;
+    b.ego = ego.data(); b.target_speed = tgt.data(); b.overrides = ov.data(); b.max_stop_distance = stop.data();
+    if (n_static > 0) { b.static_xy = L.dStatic.p; b.static_off = s_off.data(); }
+    if (any_dyn) { b.dyn_xy = L.dyn_ptr; b.dyn_off = d_off.data(); b.dyn_dims = dims.data(); }
+    return enqueue_plan(h, b, nullptr, b.static_xy, b.dyn_xy, rec_out, st, sync_caller);
+}
+
 // fot_loop_plan; rec_first: the request's records start at record rec_first of the handle's pinned block (the escalation
 // levels of a step land behind its level-0 records, which stay where they are)
 int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, const fot_loop_request *req,
@@ -1221,40 +1291,6 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
     }
     const int n_ep = (int)L.ped_off.size() - 1;
     if (n_req > 0) {
-        const int n_static = (int)(L.static_xy.size() / 2);
-        if (n_static > 0 && L.static_tiles < n_req) {              // (grows a few times in the life of a loop)
-            const int tiles = std::max(n_req, 2 * L.static_tiles);
-            std::vector<double> rep((size_t)tiles * L.static_xy.size());
-            for (int t = 0; t < tiles; ++t)
-                std::memcpy(rep.data() + (size_t)t * L.static_xy.size(), L.static_xy.data(), sizeof(double) * L.static_xy.size());
-            HIP_TRY(h, hipStreamSynchronize(st));
-            HIP_TRY(h, L.dStatic.ensure(sizeof(double) * rep.size()));
-            HIP_TRY(h, hipMemcpy(L.dStatic.p, rep.data(), sizeof(double) * rep.size(), hipMemcpyHostToDevice));
-            L.static_tiles = tiles;
-        }
-        std::vector<fot_ego> ego((size_t)n_req);
-        std::vector<fot_overrides> ov((size_t)n_req);
-        std::vector<double> tgt((size_t)n_req), stop((size_t)n_req);
-        std::vector<int32_t> s_off((size_t)n_req + 1), dims(4 * (size_t)n_req);
-        std::vector<int64_t> d_off((size_t)n_req);
-        bool any_dyn = false;
-        for (int j = 0; j < n_req; ++j) {
-            const int e = req[j].episode;
-            if (e < 0 || e >= n_ep) return fail(h, FOT_ERR_INVALID, "request: episode out of range");
-            ego[j] = req[j].ego; ov[j] = req[j].overrides; tgt[j] = req[j].target_speed; stop[j] = req[j].max_stop_distance;
-            s_off[j] = j * n_static;
-            const int P_e = L.ped_off[e + 1] - L.ped_off[e];
-            d_off[j] = L.blk_off[e];
-            dims[4 * j] = P_e > 0 ? (L.dist_S > 0 ? FOT_DYN_DISTRIBUTION : FOT_DYN_SINGLE) : FOT_DYN_NONE;
-            dims[4 * j + 1] = L.dist_S > 0 ? L.dist_S : 1; dims[4 * j + 2] = P_e; dims[4 * j + 3] = L.t_len[e];
-            any_dyn = any_dyn || P_e > 0;
-        }
-        s_off[n_req] = n_req * n_static;
-        fot_batch b = fot_batch();
-        b.n_inst = n_req; b.obstacle_dtype = FOT_F64;
-        b.ego = ego.data(); b.target_speed = tgt.data(); b.overrides = ov.data(); b.max_stop_distance = stop.data();
-        if (n_static > 0) { b.static_xy = L.dStatic.p; b.static_off = s_off.data(); }
-        if (any_dyn) { b.dyn_xy = L.dyn_ptr; b.dyn_off = d_off.data(); b.dyn_dims = dims.data(); }
         if (rec_first > 0 && sizeof(fot_result) * ((size_t)rec_first + (size_t)n_req) > L.hRec.cap)
             return fail(h, FOT_ERR_INVALID, "internal: record block too small for the escalation levels");
         HIP_TRY(h, L.hRec.ensure(sizeof(fot_result) * ((size_t)rec_first + (size_t)n_req)));
@@ -1263,7 +1299,7 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
             // the records' flags instead of the stream (wait_records): the metrics' kernel ran ahead of the plan kernels on
             // this stream and wrote host memory directly, so its results are there once a record behind it is
             arm_records(h, n_req);
-            int rc = enqueue_plan(h, b, nullptr, b.static_xy, b.dyn_xy, rec_out, st, true);
+            int rc = loop_enqueue_requests(h, n_req, req, rec_out, st, true);
             if (rc != FOT_OK) { h->done_seq_armed = false; return rc; }
             rc = wait_records(h, n_req, st);
             if (rc != FOT_OK) return rc;
@@ -1398,6 +1434,133 @@ void sm_update(LoopEpisodes &E, int e, bool found, double clearance, double clea
     }
 }
 
+
+// ---- the host side of one lock step, shared by fot_loop_step (records in pinned memory) and fot_loop_run (digests of
+//      records that stay in HBM): Rec is fot_result or LoopDigest, which name the fields read here alike
+void rec_sample1(const fot_result &r, double *g) { g[0] = r.x[1]; g[1] = r.y[1]; g[2] = r.yaw[1]; g[3] = r.v[1]; g[4] = r.a[1]; }
+void rec_sample1(const LoopDigest &r, double *g) { g[0] = r.x1; g[1] = r.y1; g[2] = r.yaw1; g[3] = r.v1; g[4] = r.a1; }
+
+int loop_max_levels(const fot_loop_config &c) { return 1 + c.max_replan < 3 ? 1 + c.max_replan : 3; }   // NORMAL -> CAUTION -> EMERGENCY, then no change
+
+struct StepWork {
+    std::vector<int> st0, n_lvl, next_rec, path_rec, keep;
+    std::vector<double> speed, ego4, ego5n, jerk, cost;
+    std::vector<fot_loop_request> req, more;
+    std::vector<fot_safety> m;               // metrics of the current ego states
+};
+
+// level 0 of every episode: the configuration of its current state (issued on LAST step's clearance); request i plans
+// against episode i of the frame
+void step_level0(const LoopEpisodes &E, const int32_t *episode, int n, StepWork &W)
+{
+    const fot_loop_config &c = E.cfg;
+    const int max_lvl = loop_max_levels(c);
+    W.st0.assign((size_t)n, 0); W.n_lvl.assign((size_t)n, 0);
+    W.speed.assign((size_t)n, 0.0); W.ego4.assign(4 * (size_t)n, 0.0);
+    W.req.assign((size_t)n, fot_loop_request());
+    W.m.assign((size_t)n, fot_safety());
+    for (int i = 0; i < n; ++i) {
+        const int e = episode[i];
+        W.st0[i] = E.state[e];
+        W.n_lvl[i] = std::min(3 - W.st0[i], max_lvl);
+        const double *g = &E.ego[5 * (size_t)e];
+        W.speed[i] = g[3];
+        for (int k = 0; k < 4; ++k) W.ego4[4 * (size_t)i + k] = g[k];
+        fot_loop_request &r = W.req[i];
+        r = fot_loop_request();
+        r.ego.x = g[0]; r.ego.y = g[1]; r.ego.yaw = g[2]; r.ego.v = g[3]; r.ego.a = g[4];
+        r.ego.last_kappa = E.last_kappa[e];
+        r.ego.has_prev_s = std::isnan(E.prev_s[e]) ? 0 : 1;
+        r.ego.prev_s = std::isnan(E.prev_s[e]) ? 0.0 : E.prev_s[e];
+        sm_config(c, W.st0[i], E.clear_ahead[e], &r.target_speed, &r.overrides, &r.max_stop_distance);
+        r.episode = i;
+    }
+}
+
+// episodes whose first attempt failed: every further escalation level they can reach, for ONE more launch (the
+// configurations update(False, ...) would issue on THIS step's metrics, nearest-point cache chained); their records
+// follow the n level-0 records
+template <class Rec>
+void step_escalations(const LoopEpisodes &E, const int32_t *episode, int n, const Rec *rec, StepWork &W)
+{
+    const fot_loop_config &c = E.cfg;
+    W.next_rec.assign((size_t)n, -1);
+    W.more.clear();
+    for (int i = 0; i < n; ++i) {
+        if (rec[i].status == FOT_PLAN_OK || W.n_lvl[i] <= 1) continue;
+        const int e = episode[i];
+        W.next_rec[i] = n + (int)W.more.size();
+        const double nps0 = rec[i].new_prev_s, p = std::isnan(nps0) ? E.prev_s[e] : nps0;
+        for (int lvl = 1; lvl < W.n_lvl[i]; ++lvl) {
+            fot_loop_request r = W.req[i];
+            const bool chain = lvl > 1;
+            r.ego.has_prev_s = chain ? FOT_PREV_S_CHAINED : (std::isnan(p) ? 0 : 1);
+            r.ego.prev_s = (chain || std::isnan(p)) ? 0.0 : p;
+            sm_config(c, W.st0[i] + lvl, W.m[i].clearance_ahead, &r.target_speed, &r.overrides, &r.max_stop_distance);
+            W.more.push_back(r);
+        }
+    }
+}
+
+// replay of the retry loop (integrated_simulator.py:576-653) episode by episode, then the ego update (:655-676) or the
+// emergency stop (:749-802): E moves on, W gets the followed record, its kept samples and cost, the jerk and the new egos
+template <class Rec>
+void step_resolve(LoopEpisodes &E, const int32_t *episode, int n, const Rec *rec, StepWork &W)
+{
+    const fot_loop_config &c = E.cfg;
+    W.path_rec.assign((size_t)n, -1); W.keep.assign((size_t)n, 0);
+    W.jerk.assign((size_t)n, 0.0); W.cost.assign((size_t)n, 0.0); W.ego5n.assign(5 * (size_t)n, 0.0);
+    auto adopt = [&](int i, int r) {                             // planner state after a plan() call
+        const int e = episode[i];
+        if (!std::isnan(rec[r].new_prev_s)) E.prev_s[e] = rec[r].new_prev_s;
+        for (int k = 0; k < 8; ++k) E.stats[8 * (size_t)e + k] = rec[r].stats_valid ? rec[r].stats[k] : -1;
+        if (rec[r].status == FOT_PLAN_OK) { E.last_kappa[e] = rec[r].new_last_kappa; W.path_rec[i] = r; }
+    };
+    for (int i = 0; i < n; ++i) {
+        const int e = episode[i];
+        int cur = i, retries = 0;
+        adopt(i, cur);
+        bool found = rec[cur].status == FOT_PLAN_OK;
+        int issued = W.st0[i];                                    // state of the configuration the attempt ran under
+        sm_update(E, e, found, W.m[i].clearance, W.m[i].clearance_ahead, W.speed[i]);
+        while (!found && E.state[e] != issued && retries < c.max_replan && retries + 1 < W.n_lvl[i]) {
+            cur = retries == 0 ? W.next_rec[i] : cur + 1;
+            ++retries;
+            adopt(i, cur);
+            const bool ok = rec[cur].status == FOT_PLAN_OK;
+            found = found || ok;
+            issued = E.state[e];
+            if (!ok) sm_update(E, e, false, W.m[i].clearance, W.m[i].clearance_ahead, W.speed[i]);
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        const int e = episode[i];
+        double *g = &E.ego[5 * (size_t)e];
+        const double old_a = g[4];
+        const int r = W.path_rec[i];
+        const int keep = r >= 0 ? rec[r].n_keep : 0;
+        double jerk;
+        if (keep >= 2) {
+            rec_sample1(rec[r], g);
+            jerk = (g[4] - old_a) / c.dt;
+        } else {
+            // the position integrates along the heading at the OLD speed; the deceleration is what stopping 0.2 m short
+            // of the nearest pedestrian ahead needs, bounded to [max_accel, emergency_decel]
+            const double v = g[3], clr = E.last_clearance[e];
+            const double cap = std::isnan(c.emergency_decel) ? c.max_accel * 2.0 : c.emergency_decel;
+            const double required = std::isfinite(clr) ? v * v / (2.0 * std::fmax(clr - 0.2, 0.05)) : cap;
+            const double max_dec = std::fmin(std::fmax(required, c.max_accel), cap);
+            const double nv = std::fmax(0.0, v - max_dec * c.dt), na = nv > 0.0 ? -max_dec : 0.0;
+            g[0] = g[0] + v * std::cos(g[2]) * c.dt; g[1] = g[1] + v * std::sin(g[2]) * c.dt;
+            g[3] = nv; g[4] = na;
+            jerk = (na - old_a) / c.dt;
+            E.last_kappa[e] = 0.0;                                // planner.reset_ego_curvature()
+        }
+        for (int k = 0; k < 5; ++k) W.ego5n[5 * (size_t)i + k] = g[k];
+        W.jerk[i] = jerk; W.keep[i] = keep; W.cost[i] = rec[r >= 0 ? r : 0].cost;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1414,6 +1577,7 @@ int fot_loop_begin(fot_handle *h, int32_t n_episodes, const fot_loop_config *cfg
     E.prev_s.assign(n, NAN); E.last_kappa.assign(n, 0.0); E.goal_prev_s.assign(n, NAN);
     E.last_clearance.assign(n, INFINITY); E.clear.assign(n, INFINITY); E.clear_ahead.assign(n, INFINITY);
     E.state.assign(n, 0); E.fails.assign(n, 0); E.stats.assign(8 * n, -1);
+    h->loop.replay.set = false;                                  // (a new loop: the handle's clock, if it had one, is gone)
     return FOT_OK;
 }
 
@@ -1423,7 +1587,7 @@ int fot_loop_step(fot_handle *h, const fot_loop_frame *frame, const int32_t *epi
     if (!frame || !out) return fail(h, FOT_ERR_INVALID, "fot_loop_step: frame / out");
     LoopState &L = h->loop;
     LoopEpisodes &E = L.ep;
-    const fot_loop_config &c = E.cfg;
+    if (L.replay.set) return fail(h, FOT_ERR_INVALID, "fot_loop_step: a replay is set (fot_loop_run steps this handle; fot_loop_begin drops the replay)");
     const int n = frame->n_episodes;
     if (n < 0 || (n > 0 && !episode)) return fail(h, FOT_ERR_INVALID, "fot_loop_step: episode");
     out->records = nullptr; out->n_records = 0;
@@ -1433,132 +1597,45 @@ int fot_loop_step(fot_handle *h, const fot_loop_frame *frame, const int32_t *epi
         if (episode[i] < 0 || episode[i] >= E.n || seen[(size_t)episode[i]]) return fail(h, FOT_ERR_INVALID, "fot_loop_step: episode slots must be distinct and below fot_loop_begin's count");
         seen[(size_t)episode[i]] = 1;
     }
-    const int max_lvl = 1 + c.max_replan < 3 ? 1 + c.max_replan : 3;     // NORMAL -> CAUTION -> EMERGENCY, then no change
-    // --- level 0 of every episode: the configuration of its current state (issued on LAST step's clearance), with the
-    //     frame's prediction and the metrics of the current ego states
-    std::vector<int> st0((size_t)n), n_lvl((size_t)n);
-    std::vector<double> speed((size_t)n), ego4(4 * (size_t)n);
-    std::vector<fot_loop_request> req((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        const int e = episode[i];
-        st0[i] = E.state[e];
-        n_lvl[i] = std::min(3 - st0[i], max_lvl);
-        const double *g = &E.ego[5 * (size_t)e];
-        speed[i] = g[3];
-        for (int k = 0; k < 4; ++k) ego4[4 * (size_t)i + k] = g[k];
-        fot_loop_request &r = req[i];
-        r = fot_loop_request();
-        r.ego.x = g[0]; r.ego.y = g[1]; r.ego.yaw = g[2]; r.ego.v = g[3]; r.ego.a = g[4];
-        r.ego.last_kappa = E.last_kappa[e];
-        r.ego.has_prev_s = std::isnan(E.prev_s[e]) ? 0 : 1;
-        r.ego.prev_s = std::isnan(E.prev_s[e]) ? 0.0 : E.prev_s[e];
-        sm_config(c, st0[i], E.clear_ahead[e], &r.target_speed, &r.overrides, &r.max_stop_distance);
-        r.episode = i;
-    }
+    StepWork W;
+    step_level0(E, episode, n, W);
     HIP_TRY(h, hipSetDevice(h->device));
     if (L.observe_n > 0) { HIP_TRY(h, hipStreamSynchronize(h->stream)); L.observe_n = -1; }
     // (all records of the step in one pinned block that must not move between the two plan calls)
-    HIP_TRY(h, L.hRec.ensure(sizeof(fot_result) * (size_t)n * (size_t)max_lvl));
+    HIP_TRY(h, L.hRec.ensure(sizeof(fot_result) * (size_t)n * (size_t)loop_max_levels(E.cfg)));
     fot_loop_frame fr = *frame;
-    fr.ego = ego4.data();
-    std::vector<fot_safety> m((size_t)n);
+    fr.ego = W.ego4.data();
     const fot_result *rec = nullptr;
-    { int rc = loop_plan_impl(h, &fr, n, req.data(), m.data(), &rec, 0); if (rc != FOT_OK) return rc; }
+    { int rc = loop_plan_impl(h, &fr, n, W.req.data(), W.m.data(), &rec, 0); if (rc != FOT_OK) return rc; }
     rec = (const fot_result *)L.hRec.p;
-    for (int i = 0; i < n; ++i) E.last_clearance[episode[i]] = m[i].clearance_ahead;
-    // --- episodes whose first attempt failed: every further escalation level they can reach in ONE more launch (the
-    //     configurations update(False, ...) would issue on THIS step's metrics, nearest-point cache chained)
-    std::vector<int> next_rec((size_t)n, -1);
-    std::vector<fot_loop_request> more;
-    for (int i = 0; i < n; ++i) {
-        if (rec[i].status == FOT_PLAN_OK || n_lvl[i] <= 1) continue;
-        const int e = episode[i];
-        next_rec[i] = n + (int)more.size();
-        const double nps0 = rec[i].new_prev_s, p = std::isnan(nps0) ? E.prev_s[e] : nps0;
-        for (int lvl = 1; lvl < n_lvl[i]; ++lvl) {
-            fot_loop_request r = req[i];
-            const bool chain = lvl > 1;
-            r.ego.has_prev_s = chain ? FOT_PREV_S_CHAINED : (std::isnan(p) ? 0 : 1);
-            r.ego.prev_s = (chain || std::isnan(p)) ? 0.0 : p;
-            sm_config(c, st0[i] + lvl, m[i].clearance_ahead, &r.target_speed, &r.overrides, &r.max_stop_distance);
-            more.push_back(r);
-        }
-    }
+    for (int i = 0; i < n; ++i) E.last_clearance[episode[i]] = W.m[i].clearance_ahead;
+    step_escalations(E, episode, n, rec, W);
     int n_rec = n;
-    if (!more.empty()) {
+    if (!W.more.empty()) {
         const fot_result *unused = nullptr;
-        int rc = loop_plan_impl(h, nullptr, (int)more.size(), more.data(), nullptr, &unused, n);
+        int rc = loop_plan_impl(h, nullptr, (int)W.more.size(), W.more.data(), nullptr, &unused, n);
         if (rc != FOT_OK) return rc;
         rec = (const fot_result *)L.hRec.p;
-        n_rec += (int)more.size();
+        n_rec += (int)W.more.size();
     }
-    // --- replay of the retry loop (integrated_simulator.py:576-653), episode by episode
-    std::vector<int> path_rec((size_t)n, -1);
-    auto adopt = [&](int i, int r) {                             // planner state after a plan() call
-        const int e = episode[i];
-        if (!std::isnan(rec[r].new_prev_s)) E.prev_s[e] = rec[r].new_prev_s;
-        for (int k = 0; k < 8; ++k) E.stats[8 * (size_t)e + k] = rec[r].stats_valid ? rec[r].stats[k] : -1;
-        if (rec[r].status == FOT_PLAN_OK) { E.last_kappa[e] = rec[r].new_last_kappa; path_rec[i] = r; }
-    };
+    step_resolve(E, episode, n, rec, W);
     for (int i = 0; i < n; ++i) {
-        const int e = episode[i];
-        int cur = i, retries = 0;
-        adopt(i, cur);
-        bool found = rec[cur].status == FOT_PLAN_OK;
-        int issued = st0[i];                                      // state of the configuration the attempt ran under
-        sm_update(E, e, found, m[i].clearance, m[i].clearance_ahead, speed[i]);
-        while (!found && E.state[e] != issued && retries < c.max_replan && retries + 1 < n_lvl[i]) {
-            cur = retries == 0 ? next_rec[i] : cur + 1;
-            ++retries;
-            adopt(i, cur);
-            const bool ok = rec[cur].status == FOT_PLAN_OK;
-            found = found || ok;
-            issued = E.state[e];
-            if (!ok) sm_update(E, e, false, m[i].clearance, m[i].clearance_ahead, speed[i]);
-        }
-    }
-    // --- ego update (:655-676) or emergency stop (:749-802)
-    std::vector<double> ego5n(5 * (size_t)n);
-    for (int i = 0; i < n; ++i) {
-        const int e = episode[i];
-        double *g = &E.ego[5 * (size_t)e];
-        const double old_a = g[4];
-        const int r = path_rec[i];
-        const int keep = r >= 0 ? rec[r].n_keep : 0;
-        double jerk;
-        if (keep >= 2) {
-            g[0] = rec[r].x[1]; g[1] = rec[r].y[1]; g[2] = rec[r].yaw[1]; g[3] = rec[r].v[1]; g[4] = rec[r].a[1];
-            jerk = (g[4] - old_a) / c.dt;
-        } else {
-            // the position integrates along the heading at the OLD speed; the deceleration is what stopping 0.2 m short
-            // of the nearest pedestrian ahead needs, bounded to [max_accel, emergency_decel]
-            const double v = g[3], clr = E.last_clearance[e];
-            const double cap = std::isnan(c.emergency_decel) ? c.max_accel * 2.0 : c.emergency_decel;
-            const double required = std::isfinite(clr) ? v * v / (2.0 * std::fmax(clr - 0.2, 0.05)) : cap;
-            const double max_dec = std::fmin(std::fmax(required, c.max_accel), cap);
-            const double nv = std::fmax(0.0, v - max_dec * c.dt), na = nv > 0.0 ? -max_dec : 0.0;
-            g[0] = g[0] + v * std::cos(g[2]) * c.dt; g[1] = g[1] + v * std::sin(g[2]) * c.dt;
-            g[3] = nv; g[4] = na;
-            jerk = (na - old_a) / c.dt;
-            E.last_kappa[e] = 0.0;                                // planner.reset_ego_curvature()
-        }
-        for (int k = 0; k < 5; ++k) ego5n[5 * (size_t)i + k] = g[k];
-        if (out->ego) for (int k = 0; k < 5; ++k) out->ego[5 * (size_t)i + k] = g[k];
-        if (out->jerk) out->jerk[i] = jerk;
-        if (out->record) out->record[i] = r;
-        if (out->keep) out->keep[i] = keep;
-        if (out->cost) out->cost[i] = rec[r >= 0 ? r : 0].cost;
+        if (out->ego) for (int k = 0; k < 5; ++k) out->ego[5 * (size_t)i + k] = W.ego5n[5 * (size_t)i + k];
+        if (out->jerk) out->jerk[i] = W.jerk[i];
+        if (out->record) out->record[i] = W.path_rec[i];
+        if (out->keep) out->keep[i] = W.keep[i];
+        if (out->cost) out->cost[i] = W.cost[i];
     }
     // --- result metrics on the new ego states and the goal test's nearest point (:864-883): enqueued, the rest of the
     //     outputs filled while they run
     std::vector<double> gps((size_t)n);
     for (int i = 0; i < n; ++i) gps[i] = E.goal_prev_s[episode[i]];
-    { int rc = fot_loop_observe_begin(h, n, ego5n.data(), gps.data()); if (rc != FOT_OK) return rc; }
+    { int rc = fot_loop_observe_begin(h, n, W.ego5n.data(), gps.data()); if (rc != FOT_OK) return rc; }
     for (int i = 0; i < n; ++i) {
         const int e = episode[i];
         if (out->state) out->state[i] = E.state[e];
         if (out->stats) for (int k = 0; k < 8; ++k) out->stats[8 * (size_t)i + k] = E.stats[8 * (size_t)e + k];
-        if (out->before) out->before[i] = m[i];
+        if (out->before) out->before[i] = W.m[i];
     }
     std::vector<fot_safety> after((size_t)n);
     { int rc = fot_loop_observe_end(h, after.data(), gps.data()); if (rc != FOT_OK) return rc; }
@@ -1570,6 +1647,292 @@ int fot_loop_step(fot_handle *h, const fot_loop_frame *frame, const int32_t *epi
     out->records = rec;
     out->n_records = n_rec;
     return FOT_OK;
+}
+
+}  // extern "C"
+
+// ---- whole replayed episodes: the recording resident in HBM, the lock steps run by the library ------------------------
+namespace {
+
+// Waits until the device has raised *word to seq (k_loop_digest / k_loop_history, in pinned memory); after 20 ms without
+// it the stream is synchronised instead, as wait_records does.
+int wait_word(fot_handle *h, const int32_t *word, int32_t seq, hipStream_t st)
+{
+    volatile const int32_t *w = (volatile const int32_t *)word;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int spins = 0; *w != seq;) {
+        __builtin_ia32_pause();
+        if ((++spins & 1023) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 0.02) {
+            HIP_TRY(h, hipStreamSynchronize(st));
+            return FOT_OK;
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return FOT_OK;
+}
+
+int32_t next_seq(LoopReplay &R)
+{
+    if (++R.seq == 0) R.seq = 1;                                  // (0 is what a fresh word holds)
+    return R.seq;
+}
+
+// the regions of LoopReplay::dFrame / hStage for up to n episodes and `rows` pedestrians
+struct FrameLayout {
+    size_t ped_b, ep_b, off_b, blk_b, pre_b, ego_b;
+    FrameLayout(size_t n, size_t rows)
+        : ped_b(align256(16 * std::max<size_t>(rows, 1))), ep_b(align256(4 * std::max<size_t>(rows, 1))),
+          off_b(align256(4 * (n + 1))), blk_b(align256(8 * (n + 1))), pre_b(align256(4 * std::max<size_t>(n, 1))),
+          ego_b(align256(32 * std::max<size_t>(n, 1))) {}
+    size_t dev_bytes() const { return 4 * ped_b + ep_b + off_b + blk_b + pre_b + ego_b; }
+    size_t stage_bytes() const { return pre_b + off_b + blk_b + pre_b + ego_b; }
+    FrameDev dev(void *base) const
+    {
+        char *p = (char *)base;
+        FrameDev f;
+        f.pos = (double *)p; f.vel = (double *)(p + ped_b); f.last = (double *)(p + 2 * ped_b); f.prev = (double *)(p + 3 * ped_b);
+        p += 4 * ped_b;
+        f.ped_ep = (int32_t *)p; p += ep_b;
+        f.ped0 = (int32_t *)p; p += off_b;
+        f.blk = (int64_t *)p; p += blk_b;
+        f.prepend = (int32_t *)p; p += pre_b;
+        f.ego = (double *)p;
+        return f;
+    }
+};
+
+// one lock step of the running slots `sel`; step k of the call (outputs row k)
+int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loop_run_out *out, double *d_hist_step)
+{
+    LoopState &L = h->loop;
+    LoopReplay &R = L.replay;
+    LoopEpisodes &E = L.ep;
+    const fot_loop_replay &C = R.cfg;
+    hipStream_t st = h->stream;
+    const int n = (int)sel.size(), n_slots = C.n_slots;
+    { int r = order_begin(h, st); if (r != FOT_OK) return r; }
+    // --- 1. pedestrians + observer
+    R.clock.advance();
+    const bool ready = R.clock.ready();
+    const int f_cur = R.clock.frame, f_last = R.clock.last_frame(), f_prev = R.clock.prev_frame();
+    const double stale = R.clock.staleness();
+    if (out->frame) out->frame[k] = f_cur;
+    if (out->obs_last_frame) out->obs_last_frame[k] = f_last;
+    if (out->obs_prev_frame) out->obs_prev_frame[k] = f_prev;
+    if (out->staleness) out->staleness[k] = stale;
+    // --- 2. the frame of the running episodes: tables on the host, pedestrians on the device
+    const FrameLayout FL((size_t)n_slots, (size_t)R.n_cols);
+    char *stg = (char *)R.hStage.p;
+    int32_t *s_slot = (int32_t *)stg, *s_ped0 = (int32_t *)(stg + FL.pre_b);
+    int64_t *s_blk = (int64_t *)(stg + FL.pre_b + FL.off_b);
+    int32_t *s_pre = (int32_t *)(stg + FL.pre_b + FL.off_b + FL.blk_b);
+    double *s_ego = (double *)(stg + 2 * FL.pre_b + FL.off_b + FL.blk_b);
+    StepWork W;
+    step_level0(E, sel.data(), n, W);
+    L.ped_off.assign((size_t)n + 1, 0); L.blk_off.assign((size_t)n + 1, 0); L.t_len.assign((size_t)n, 1);
+    L.dist_S = 0;
+    const size_t row_doubles = 2 * (size_t)R.n_cols;
+    for (int i = 0; i < n; ++i) {
+        const int e = sel[i], c0 = R.ped_off[e], P_e = R.ped_off[e + 1] - c0, nf = R.n_frames[e];
+        int pre = 0;
+        if (ready && f_prev >= 0 && P_e > 0) {
+            const double *cur = R.pos.data() + (size_t)replay_row(f_cur, nf) * row_doubles + 2 * (size_t)c0;
+            const double *last = R.pos.data() + (size_t)replay_row(f_last, nf) * row_doubles + 2 * (size_t)c0;
+            const double *prev = R.pos.data() + (size_t)replay_row(f_prev, nf) * row_doubles + 2 * (size_t)c0;
+            pre = replay_prepend(P_e, last, prev, cur, C.rp.sgan_dt, C.rp.sim_dt, stale) ? 1 : 0;
+        }
+        L.t_len[i] = ready ? R.n_dense + pre : 1;
+        L.ped_off[i + 1] = L.ped_off[i] + P_e;
+        L.blk_off[i + 1] = L.blk_off[i] + (int64_t)P_e * L.t_len[i];
+        s_slot[i] = e; s_ped0[i] = L.ped_off[i]; s_blk[i] = L.blk_off[i]; s_pre[i] = pre;
+        for (int q = 0; q < 4; ++q) s_ego[4 * (size_t)i + q] = W.ego4[4 * (size_t)i + q];
+    }
+    s_ped0[n] = L.ped_off[n]; s_blk[n] = L.blk_off[n];
+    const int rows = L.ped_off[n];
+    ReplayView rv;
+    rv.pos = R.dPos.as<double>(); rv.vel = R.dVel.as<double>();
+    rv.slot_ped0 = R.dTab.as<int32_t>(); rv.slot_frames = R.dTab.as<int32_t>() + (n_slots + 1);
+    rv.n_cols = R.n_cols;
+    FrameStage fs;
+    fs.slot = s_slot; fs.ped0 = s_ped0; fs.blk = s_blk; fs.prepend = s_pre; fs.ego = s_ego;
+    const FrameDev fd = FL.dev(R.dFrame.p);
+    LAUNCH_TRY(h, launch_loop_frame(rv, fs, fd, n, f_cur, ready ? f_last : -1, ready ? f_prev : -1, st));
+    L.p_off = fd.ped0; L.p_pos = fd.pos; L.p_vel = fd.vel;
+    L.ego_radius = C.ego_radius; L.ped_radius = C.ped_radius; L.use_footprint = C.use_footprint;
+    L.dyn_ptr = fd.pos;                                          // not ready: the current positions, T = 1
+    if (ready && rows > 0) {
+        L.dyn_ptr = L.dDyn.p;
+        LAUNCH_TRY(h, launch_predict_cv_frame(C.rp.sgan_dt, C.rp.sim_dt, stale, rows, R.n_dense, fd, L.dDyn.as<double>(), st));
+    }
+    LAUNCH_TRY(h, launch_safety(h->dP.as<DevParams>(), n, fd.ego, fd.ped0, fd.pos, fd.vel, L.ego_radius, L.ped_radius,
+                                h->sc[0].params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st));
+    L.have_frame = true; L.observe_n = -1;
+    // --- 3. level 0 of every episode; the records stay in HBM, the host reads their digests
+    fot_result *d_rec = R.dRec.as<fot_result>();
+    LoopDigest *dig = (LoopDigest *)R.hDigest.p;
+    int32_t *word = (int32_t *)R.hWord.p;
+    { int rc = loop_enqueue_requests(h, n, W.req.data(), d_rec, st, false); if (rc != FOT_OK) return rc; }
+    int32_t seq = next_seq(R);
+    LAUNCH_TRY(h, launch_loop_digest(d_rec, n, dig, word, seq, st));
+    { int rc = wait_word(h, word, seq, st); if (rc != FOT_OK) return rc; }
+    std::memcpy(W.m.data(), L.hOut.p, sizeof(fot_safety) * (size_t)n);   // (k_safety ran ahead of the plan on this stream)
+    for (int i = 0; i < n; ++i) E.last_clearance[sel[i]] = W.m[i].clearance_ahead;
+    step_escalations(E, sel.data(), n, dig, W);
+    if (!W.more.empty()) {
+        const int n_more = (int)W.more.size();
+        int rc = loop_enqueue_requests(h, n_more, W.more.data(), d_rec + n, st, false);
+        if (rc != FOT_OK) return rc;
+        seq = next_seq(R);
+        LAUNCH_TRY(h, launch_loop_digest(d_rec + n, n_more, dig + n, word, seq, st));
+        rc = wait_word(h, word, seq, st);
+        if (rc != FOT_OK) return rc;
+    }
+    // --- 4. retry loop, ego update; 5. metrics of the new states + the goal test's nearest point
+    step_resolve(E, sel.data(), n, dig, W);
+    std::vector<double> gps((size_t)n);
+    for (int i = 0; i < n; ++i) gps[i] = E.goal_prev_s[sel[i]];
+    { int rc = fot_loop_observe_begin(h, n, W.ego5n.data(), gps.data()); if (rc != FOT_OK) return rc; }
+    // the followed paths into the history block, and the word that tells the host the step's results are there
+    int32_t *t_src = (int32_t *)R.hHistTab.p, *t_slot = t_src + n_slots;
+    for (int i = 0; i < n; ++i) { t_src[i] = W.path_rec[i]; t_slot[i] = sel[i]; }
+    seq = next_seq(R);
+    LAUNCH_TRY(h, launch_loop_history(d_rec, n, t_src, t_slot, d_hist_step, n_slots, h->sc[0].P.n_total, word + 16, seq, st));
+    { int rc = wait_word(h, word + 16, seq, st); if (rc != FOT_OK) return rc; }
+    L.observe_n = -1;
+    const fot_safety *after = (const fot_safety *)L.hOut.p;
+    const InstState *p_state = (const InstState *)((const char *)L.hOut.p + align256(sizeof(fot_safety) * (size_t)n));
+    const size_t row = (size_t)k * (size_t)n_slots;
+    if (out->followed) for (int e = 0; e < n_slots; ++e) out->followed[row + e] = -1;
+    for (int i = 0; i < n; ++i) {
+        const int e = sel[i];
+        const size_t o = row + (size_t)e;
+        const double s_now = p_state[i].new_prev_s;
+        E.goal_prev_s[e] = s_now;
+        if (out->ego) for (int q = 0; q < 5; ++q) out->ego[5 * o + q] = W.ego5n[5 * (size_t)i + q];
+        if (out->jerk) out->jerk[o] = W.jerk[i];
+        if (out->state) out->state[o] = E.state[e];
+        if (out->stats) for (int q = 0; q < 8; ++q) out->stats[8 * o + q] = E.stats[8 * (size_t)e + q];
+        if (out->followed) out->followed[o] = W.path_rec[i] >= 0 ? 1 : 0;
+        if (out->keep) out->keep[o] = W.keep[i];
+        if (out->cost) out->cost[o] = W.cost[i];
+        if (out->after) out->after[o] = after[i];
+        if (out->s_now) out->s_now[o] = s_now;
+        R.steps[e] += 1;
+        R.termination[e] = replay_termination(after[i].collision, C.s_end, s_now, C.goal_distance);
+        if (R.termination[e] != 0) R.alive[e] = 0;
+    }
+    return FOT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fot_loop_set_replay(fot_handle *h, const fot_loop_replay *rp)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (!h->sc[0].has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
+    if (!rp) return fail(h, FOT_ERR_INVALID, "fot_loop_set_replay: replay is NULL");
+    LoopState &L = h->loop;
+    const LoopEpisodes &E = L.ep;
+    if (!(E.cfg.dt > 0.0)) return fail(h, FOT_ERR_INVALID, "fot_loop_set_replay: fot_loop_begin comes first");
+    const int n = rp->n_slots;
+    if (n != E.n) return fail(h, FOT_ERR_INVALID, "fot_loop_set_replay: n_slots differs from fot_loop_begin's episode count");
+    if (!rp->ped_off || (n > 0 && !rp->n_frames) || rp->n_frames_max < 1 || rp->warmup_frames < 0)
+        return fail(h, FOT_ERR_INVALID, "fot_loop_set_replay: ped_off / n_frames / n_frames_max / warmup_frames");
+    for (int i = 0; i < n; ++i)
+        if (rp->ped_off[i + 1] < rp->ped_off[i] || rp->ped_off[0] != 0)
+            return fail(h, FOT_ERR_INVALID, "ped_off must start at 0 and be non-decreasing");
+    for (int i = 0; i < n; ++i)
+        if (rp->n_frames[i] < 1 || rp->n_frames[i] > rp->n_frames_max)
+            return fail(h, FOT_ERR_INVALID, "fot_loop_set_replay: every slot needs 1 .. n_frames_max recorded frames");
+    const size_t cols = n > 0 ? (size_t)rp->ped_off[n] : 0;
+    if (cols > 0 && (!rp->pos || !rp->vel)) return fail(h, FOT_ERR_INVALID, "fot_loop_set_replay: NULL recording");
+    if (rp->obs_len < 2) return fail(h, FOT_ERR_INVALID, "fot_loop_set_replay: obs_len < 2 (the predictor needs two samples)");
+    if (!(rp->rp.sim_dt > 0.0) || !(rp->rp.sgan_dt > 0.0) || rp->pred_len < 1)
+        return fail(h, FOT_ERR_INVALID, "fot_loop_set_replay: predictor parameters");
+    if (rp->pred_len > FOT_MAX_PRED_LEN) return fail(h, FOT_ERR_UNSUPPORTED, "pred_len > FOT_MAX_PRED_LEN");
+    const int n_dense = resample_n_dense(rp->rp.sgan_dt, rp->rp.sim_dt, rp->rp.plan_horizon, rp->pred_len);
+    if (n_dense + 1 > FOT_MAX_NT) return fail(h, FOT_ERR_UNSUPPORTED, "more than FOT_MAX_NT time steps");
+    // --- accepted: everything the steps need is allocated here, so that no block grows (and moves) inside a run
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                 // nothing may still read what is replaced below
+    LoopReplay &R = L.replay;
+    R.set = false;
+    const size_t rec_doubles = (size_t)rp->n_frames_max * cols * 2;
+    const int max_lvl = loop_max_levels(E.cfg);
+    const size_t n_rec = (size_t)std::max(n, 1) * (size_t)max_lvl;
+    const FrameLayout FL((size_t)n, cols);
+    HIP_TRY(h, R.dPos.ensure(sizeof(double) * std::max<size_t>(rec_doubles, 2)));
+    HIP_TRY(h, R.dVel.ensure(sizeof(double) * std::max<size_t>(rec_doubles, 2)));
+    HIP_TRY(h, R.dTab.ensure(sizeof(int32_t) * (2 * (size_t)n + 1)));
+    HIP_TRY(h, R.dFrame.ensure(FL.dev_bytes()));
+    HIP_TRY(h, R.dRec.ensure_zeroed(sizeof(fot_result) * n_rec));
+    HIP_TRY(h, L.dDyn.ensure(sizeof(double) * 2 * std::max<size_t>(cols, 1) * (size_t)(n_dense + 1)));
+    HIP_TRY(h, R.hStage.ensure(FL.stage_bytes()));
+    HIP_TRY(h, R.hDigest.ensure(sizeof(LoopDigest) * n_rec));
+    HIP_TRY(h, R.hHistTab.ensure(sizeof(int32_t) * 2 * (size_t)std::max(n, 1)));
+    HIP_TRY(h, R.hWord.ensure(sizeof(int32_t) * 32));
+    HIP_TRY(h, L.hOut.ensure(align256(sizeof(fot_safety) * (size_t)std::max(n, 1)) + sizeof(InstState) * (size_t)std::max(n, 1)));
+    HIP_TRY(h, L.hObserve.ensure(align256(sizeof(double) * 4 * (size_t)std::max(n, 1)) + align256(sizeof(InstDesc) * (size_t)std::max(n, 1))));
+    if (rec_doubles) {
+        HIP_TRY(h, hipMemcpy(R.dPos.p, rp->pos, sizeof(double) * rec_doubles, hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(R.dVel.p, rp->vel, sizeof(double) * rec_doubles, hipMemcpyHostToDevice));
+    }
+    std::vector<int32_t> tab(2 * (size_t)n + 1);
+    for (int i = 0; i <= n; ++i) tab[(size_t)i] = rp->ped_off[i];
+    for (int i = 0; i < n; ++i) tab[(size_t)n + 1 + (size_t)i] = rp->n_frames[i];
+    HIP_TRY(h, hipMemcpy(R.dTab.p, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice));
+    R.cfg = *rp;
+    R.cfg.ped_off = nullptr; R.cfg.n_frames = nullptr; R.cfg.pos = nullptr; R.cfg.vel = nullptr;
+    R.n_cols = (int)cols; R.n_dense = n_dense; R.max_lvl = max_lvl;
+    R.ped_off.assign(rp->ped_off, rp->ped_off + n + 1);
+    R.n_frames.assign(rp->n_frames, rp->n_frames + n);
+    R.pos.assign(rp->pos, rp->pos + rec_doubles);
+    R.vel.clear();                                               // (the host needs the positions only: the prepend test)
+    R.alive.assign((size_t)n, 1); R.steps.assign((size_t)n, 0); R.termination.assign((size_t)n, 0);
+    R.clock.reset(rp->obs_len, rp->rp.sim_dt, rp->rp.sgan_dt);
+    for (int i = 0; i < rp->warmup_frames; ++i) R.clock.advance();   // fills the observer (integrated_simulator.py:406-422)
+    L.have_frame = false; L.observe_n = -1;
+    R.set = true;
+    return FOT_OK;
+}
+
+int fot_loop_run(fot_handle *h, int32_t max_steps, fot_loop_run_out *out)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopState &L = h->loop;
+    LoopReplay &R = L.replay;
+    if (!R.set) return fail(h, FOT_ERR_INVALID, "fot_loop_run: fot_loop_set_replay comes first");
+    if (max_steps < 0 || !out) return fail(h, FOT_ERR_INVALID, "fot_loop_run: max_steps / out");
+    const int n_slots = R.cfg.n_slots;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    const size_t step_doubles = 15 * (size_t)n_slots * (size_t)h->sc[0].P.n_total;
+    const bool keep_paths = out->paths != nullptr && step_doubles > 0 && max_steps > 0;
+    if (keep_paths) {
+        HIP_TRY(h, R.dHist.ensure(sizeof(double) * step_doubles * (size_t)max_steps));
+        HIP_TRY(h, hipMemsetAsync(R.dHist.p, 0, sizeof(double) * step_doubles * (size_t)max_steps, st));
+    }
+    int done = 0;
+    std::vector<int32_t> sel;
+    for (; done < max_steps; ++done) {
+        sel.clear();
+        for (int e = 0; e < n_slots; ++e) if (R.alive[(size_t)e]) sel.push_back(e);
+        if (sel.empty()) break;
+        int rc = loop_run_step(h, sel, done, out, keep_paths ? R.dHist.as<double>() + step_doubles * (size_t)done : nullptr);
+        if (rc != FOT_OK) return rc;
+    }
+    if (done > 0) { int r = order_end(h, st); if (r != FOT_OK) return r; }
+    if (keep_paths && done > 0) {                                // the call's history block, in one copy
+        HIP_TRY(h, hipMemcpyAsync(out->paths, R.dHist.p, sizeof(double) * step_doubles * (size_t)done, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+    }
+    for (int e = 0; e < n_slots; ++e) {
+        if (out->steps) out->steps[e] = R.steps[(size_t)e];
+        if (out->termination) out->termination[e] = R.termination[(size_t)e];
+    }
+    return done;
 }
 
 }  // extern "C"

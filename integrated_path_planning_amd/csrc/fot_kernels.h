@@ -1,6 +1,7 @@
 // fot_kernels.h -- host-callable launchers of the gfx950 kernels (fot_kernels.hip).
 #pragma once
 
+#include <cstddef>
 #include <hip/hip_runtime.h>
 #include "fot_types.h"
 
@@ -127,6 +128,66 @@ int launch_sample_dist(int S, int P, int T, int skip, const void *out, int out_d
 int launch_safety(const DevParams *P, int n, const double *ego, const int32_t *ped_off, const double *ped_pos,
                   const double *ped_vel, double ego_radius, double ped_radius, double footprint_radius, int use_fp,
                   fot_safety *out, hipStream_t st);
+// ---- fot_loop_run: the frame of a lock step built from the HBM-resident recording, and what the host reads of a step
+
+// The recording fot_loop_set_replay left in HBM and the per-slot tables beside it.
+struct ReplayView {
+    const double *pos = nullptr, *vel = nullptr;     // [n_frames_max][n_cols][2]
+    const int32_t *slot_ped0 = nullptr;              // [n_slots + 1] first column of each slot
+    const int32_t *slot_frames = nullptr;            // [n_slots] recorded frames (the last one is held afterwards)
+    int n_cols = 0;
+};
+
+// What the host stages for a step's frame in pinned memory (one entry per RUNNING episode, slot order): k_loop_frame
+// moves it into HBM with the pedestrians, so that the step's other kernels read HBM only.
+struct FrameStage {
+    const int32_t *slot = nullptr;                   // [n_run] slot of running episode i
+    const int32_t *ped0 = nullptr;                   // [n_run + 1] first row of episode i in the compacted frame
+    const int64_t *blk = nullptr;                    // [n_run + 1] first point of episode i's block of the prediction tensor
+    const int32_t *prepend = nullptr;                // [n_run] 1: the current positions lead episode i's tracks
+    const double *ego = nullptr;                     // [n_run][4] x, y, yaw, v
+};
+
+// The compacted frame in HBM: rows [ped0[i], ped0[i + 1]) belong to running episode i.
+struct FrameDev {
+    double *pos = nullptr, *vel = nullptr;           // [rows][2] current positions / velocities
+    double *last = nullptr, *prev = nullptr;         // [rows][2] the observer's last two samples, rounded through float32
+    int32_t *ped_ep = nullptr;                       // [rows] running episode of each row
+    int32_t *ped0 = nullptr;                         // [n_run + 1]
+    int64_t *blk = nullptr;                          // [n_run + 1]
+    int32_t *prepend = nullptr;                      // [n_run]
+    double *ego = nullptr;                           // [n_run][4]
+};
+
+// What the host needs of a record to replay the retry loop and move the ego: the record's first 80 bytes as they are
+// (fot_result up to new_prev_s) and sample 1 of x, y, yaw, v, a.  128 bytes = eight 16-byte stores per record.
+struct LoopDigest {
+    int32_t status, best_index, n_cand, n_keep;
+    double cost;
+    int32_t stats[8];
+    int32_t stats_valid, _pad;
+    double new_last_kappa, new_prev_s;
+    double x1, y1, yaw1, v1, a1, _zero;
+};
+static_assert(sizeof(LoopDigest) == 128 && offsetof(LoopDigest, x1) == offsetof(fot_result, frenet0) &&
+              offsetof(LoopDigest, new_prev_s) == offsetof(fot_result, new_prev_s) && sizeof(fot_result) % 16 == 0,
+              "LoopDigest starts with fot_result's header");
+
+// f_cur / f_last / f_prev: replay frames of the current positions and of the observer's last two samples (f_last < 0:
+// the observer still fills, last / prev are not written)
+int launch_loop_frame(ReplayView rv, FrameStage in, FrameDev out, int n_run, int f_cur, int f_last, int f_prev,
+                      hipStream_t st);
+// constant-velocity tracks of every row of the frame in ONE launch, episode i's [P_i][n_dense + prepend[i]][2] block at
+// point blk[i] of `out`: k_resample's float32-observation path (cv = 2) with the prepend decided per episode
+int launch_predict_cv_frame(double sgan_dt, double sim_dt, double staleness, int n_rows, int n_dense, FrameDev f,
+                            double *out, hipStream_t st);
+// digests of rec[0 .. n) into pinned memory, then `*done = seq` behind a system-scope release
+int launch_loop_digest(const fot_result *rec, int n, LoopDigest *out, int32_t *done, int32_t seq, hipStream_t st);
+// end of a step: raises `*done = seq` (everything in front of it on the stream is then in host memory) and, with hist,
+// copies the first n_total samples of the 15 path arrays of rec[src[i]] (src[i] < 0: none) into
+// hist[15][n_slots][n_total] at slot[i]; src / slot are pinned host memory
+int launch_loop_history(const fot_result *rec, int n_run, const int32_t *src, const int32_t *slot, double *hist,
+                        int n_slots, int n_total, int32_t *done, int32_t seq, hipStream_t st);
 int launch_check_ext(const DevParams *P, const InstDesc *desc, int n_paths, int mode, const int32_t *len,
                      const int32_t *flags, const double *arrays, const double *static_xy, const double *dyn_xy,
                      int32_t *status_out, hipStream_t st);

@@ -1986,6 +1986,107 @@ k_safety(const DevParams *__restrict__ Pp, int n, const double *__restrict__ ego
 }
 
 // ---------------------------------------------------------------------------
+// fot_loop_run: the step's frame from the resident recording, the records' digests, the history of followed paths
+// ---------------------------------------------------------------------------
+
+// One workgroup per running episode.  Its rows of the recording -- current positions and velocities at frame f_cur, the
+// observer's last two samples at f_last / f_prev, each clamped to the slot's own recording -- go into the compacted
+// frame as 16-byte rows; thread 0 moves the episode's entries of the host's tables into HBM.
+__global__ void __launch_bounds__(WAVE)
+k_loop_frame(ReplayView rv, FrameStage in, FrameDev out, int n_run, int f_cur, int f_last, int f_prev)
+{
+    const int i = blockIdx.x;
+    if (i >= n_run) return;
+    const int slot = in.slot[i], q0 = in.ped0[i], q1 = in.ped0[i + 1];
+    const int c0 = rv.slot_ped0[slot], last_row = rv.slot_frames[slot] - 1;
+    const int64_t cols = rv.n_cols;
+    const double2 *pos = (const double2 *)rv.pos, *vel = (const double2 *)rv.vel;
+    const int64_t r_cur = (int64_t)min(f_cur, last_row) * cols + c0;
+    const int64_t r_last = (int64_t)min(max(f_last, 0), last_row) * cols + c0;
+    const int64_t r_prev = (int64_t)min(max(f_prev, 0), last_row) * cols + c0;
+    for (int p = threadIdx.x; p < q1 - q0; p += WAVE) {
+        const int q = q0 + p;
+        ((double2 *)out.pos)[q] = pos[r_cur + p];
+        ((double2 *)out.vel)[q] = vel[r_cur + p];
+        out.ped_ep[q] = i;
+        if (f_last >= 0) {
+            const double2 l = pos[r_last + p];
+            double2 w; w.x = (double)(float)l.x; w.y = (double)(float)l.y;     // the observer hands over float32 (observer.py:134)
+            ((double2 *)out.last)[q] = w;
+            double2 u = w;                                               // (no second sample: zero velocity)
+            if (f_prev >= 0) { const double2 v = pos[r_prev + p]; u.x = (double)(float)v.x; u.y = (double)(float)v.y; }
+            ((double2 *)out.prev)[q] = u;
+        }
+    }
+    if (threadIdx.x == 0) {
+        out.ped0[i] = q0; out.blk[i] = in.blk[i]; out.prepend[i] = in.prepend[i];
+        if (i == n_run - 1) { out.ped0[n_run] = q1; out.blk[n_run] = in.blk[n_run]; }
+    }
+    if (threadIdx.x < 4) out.ego[4 * i + threadIdx.x] = in.ego[4 * i + threadIdx.x];
+}
+
+// one thread per (row, axis) of the frame; the arithmetic of k_resample's cv = 2 path, operation for operation
+__global__ void k_predict_cv_frame(double sgan_dt, double sim_dt, double staleness, int n_rows, int n_dense, FrameDev f,
+                                   double *__restrict__ out)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n_rows * 2) return;
+    const int ax = idx & 1, p = idx >> 1;
+    const int e = f.ped_ep[p], p0 = f.ped0[e], pre = f.prepend[e] ? 1 : 0;
+    const int T = n_dense + pre;
+    double *dst = out + 2 * (f.blk[e] + (int64_t)(p - p0) * T) + ax;
+    if (pre) dst[0] = f.pos[2 * p + ax];
+    dst += 2 * pre;
+    const double cur = f.last[2 * p + ax];                          // obs_last
+    const double vel = (double)(((float)cur - (float)f.prev[2 * p + ax]) / (float)sgan_dt);
+    for (int i = 0; i < n_dense; ++i) {
+        const double t = (sim_dt + (double)i * sim_dt) + staleness;
+        dst[2 * i] = (double)(cur + vel * t);
+    }
+}
+
+// One workgroup: eight lanes per record, one 16-byte store each into the pinned digest; every wave releases its stores
+// at system scope before the barrier behind which thread 0 raises the completion word the host polls (the ordering of
+// record_written, for any number of records).
+__global__ void __launch_bounds__(256)
+k_loop_digest(const fot_result *__restrict__ rec, int n, LoopDigest *out, int32_t *done, int32_t seq)
+{
+    for (int c = threadIdx.x; c < 8 * n; c += 256) {
+        const int r = c >> 3, j = c & 7;
+        double2 v;
+        if (j < 5) v = ((const double2 *)(rec + r))[j];                   // the header up to new_prev_s, as it is
+        else if (j == 5) { v.x = rec[r].x[1]; v.y = rec[r].y[1]; }
+        else if (j == 6) { v.x = rec[r].yaw[1]; v.y = rec[r].v[1]; }
+        else { v.x = rec[r].a[1]; v.y = 0.0; }
+        ((double2 *)(out + r))[j] = v;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Workgroup i copies the followed record of running episode i into the step's history block; workgroup 0 first raises
+// the step's completion word: this launch runs behind the step's last kernels on its stream, whose results in pinned
+// memory are complete when it starts.
+__global__ void __launch_bounds__(256)
+k_loop_history(const fot_result *__restrict__ rec, int n_run, const int32_t *__restrict__ src,
+               const int32_t *__restrict__ slot, double *__restrict__ hist, int n_slots, int n_total, int32_t *done,
+               int32_t seq)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    const int i = blockIdx.x;
+    if (!hist || i >= n_run) return;
+    const int r = src[i];
+    if (r < 0) return;
+    const double *from = rec[r].t;                                   // the 15 arrays lie back to back, FOT_MAX_NT apart
+    double *to = hist + (int64_t)slot[i] * n_total;
+    for (int c = threadIdx.x; c < 15 * n_total; c += 256) {
+        const int f = c / n_total, k = c - f * n_total;
+        to[(int64_t)f * n_slots * n_total + k] = from[f * FOT_MAX_NT + k];
+    }
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
 
@@ -2151,6 +2252,41 @@ int launch_safety(const DevParams *P, int n, const double *ego, const int32_t *p
 {
     if (n <= 0) return 0;
     k_safety<<<n, WAVE, 0, st>>>(P, n, ego, ped_off, ped_pos, ped_vel, ego_radius, ped_radius, footprint_radius, use_fp, out);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_frame(ReplayView rv, FrameStage in, FrameDev out, int n_run, int f_cur, int f_last, int f_prev,
+                      hipStream_t st)
+{
+    if (n_run <= 0) return 0;
+    k_loop_frame<<<n_run, WAVE, 0, st>>>(rv, in, out, n_run, f_cur, f_last, f_prev);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_predict_cv_frame(double sgan_dt, double sim_dt, double staleness, int n_rows, int n_dense, FrameDev f,
+                            double *out, hipStream_t st)
+{
+    if (n_rows <= 0) return 0;
+    const int bs = 128, grid = (2 * n_rows + bs - 1) / bs;
+    k_predict_cv_frame<<<grid, bs, 0, st>>>(sgan_dt, sim_dt, staleness, n_rows, n_dense, f, out);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_digest(const fot_result *rec, int n, LoopDigest *out, int32_t *done, int32_t seq, hipStream_t st)
+{
+    k_loop_digest<<<1, 256, 0, st>>>(rec, n > 0 ? n : 0, out, done, seq);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_history(const fot_result *rec, int n_run, const int32_t *src, const int32_t *slot, double *hist,
+                        int n_slots, int n_total, int32_t *done, int32_t seq, hipStream_t st)
+{
+    const int grid = hist && n_run > 0 ? n_run : 1;
+    k_loop_history<<<grid, 256, 0, st>>>(rec, n_run, src, slot, hist, n_slots, n_total, done, seq);
     FOT_LAUNCH_CHECK();
     return 0;
 }

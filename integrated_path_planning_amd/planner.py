@@ -458,6 +458,67 @@ class BatchPlanner:
         o["before"], o["after"] = o["before"][:n], o["after"][:n]
         return o
 
+    def loop_set_replay(self, ped_off, n_frames, positions, velocities, *, obs_len: int, pred_len: int, rp,
+                        warmup_frames: int, ego_radius: float, ped_radius: float, use_footprint: bool, s_end: float,
+                        goal_distance: float = 2.0) -> None:
+        """``fot_loop_set_replay``: hands the recording of every episode slot of ``loop_begin`` to the library, which
+        keeps it in HBM and runs the warm-up.  positions / velocities [n_frames_max, sum P, 2] (slot e owns columns
+        ``ped_off[e]:ped_off[e + 1]`` and ``n_frames[e]`` recorded frames, its last one held afterwards); rp: the
+        predictor's ``ResampleParams``.  Constant-velocity predictor only."""
+        off = np.ascontiguousarray(ped_off, dtype=np.int32)
+        nf = np.ascontiguousarray(n_frames, dtype=np.int32)
+        pos = np.ascontiguousarray(positions, dtype=np.float64)
+        vel = np.ascontiguousarray(velocities, dtype=np.float64)
+        n = len(off) - 1
+        if len(nf) != n or pos.shape != vel.shape or pos.ndim != 3 or pos.shape[1:] != (int(off[-1]), 2):
+            raise ValueError("loop_set_replay: positions / velocities [n_frames_max, ped_off[-1], 2], one n_frames per slot")
+        r = _abi.LoopReplay()
+        r.n_slots, r.n_frames_max, r.obs_len, r.pred_len = n, int(pos.shape[0]), int(obs_len), int(pred_len)
+        r.warmup_frames, r.use_footprint = int(warmup_frames), int(bool(use_footprint))
+        r.ped_off, r.n_frames = _addr(off), _addr(nf) if n else None
+        r.pos, r.vel = (_addr(pos), _addr(vel)) if pos.size else (None, None)
+        r.rp = rp
+        r.ego_radius, r.ped_radius, r.s_end, r.goal_distance = float(ego_radius), float(ped_radius), float(s_end), float(goal_distance)
+        _abi.check(self._h, self._lib.fot_loop_set_replay(self._h, C.addressof(r)))
+        self._replay_slots = n
+
+    def loop_run(self, max_steps: int, keep_paths: bool = True, paths_out: Optional[np.ndarray] = None) -> dict:
+        """``fot_loop_run``: up to ``max_steps`` lock steps of every running episode inside the library.  Returns the
+        arrays of ``fot_loop_run_out`` cut to the ``n_steps`` executed: per step and slot ``ego`` [k, n, 5], ``jerk``,
+        ``state``, ``stats`` [k, n, 8], ``followed`` (1 path, 0 emergency stop, -1 the slot did not run), ``keep``,
+        ``cost``, ``after`` (``SAFETY_DT``), ``s_now``; per step ``frame``, ``obs_last_frame``, ``obs_prev_frame``,
+        ``staleness``; per slot ``steps``, ``termination`` (0 runs, 1 collision, 2 goal); with ``keep_paths`` ``paths``
+        [k, 15, n, n_total], zero beyond ``keep`` and for slots without a path (written into ``paths_out``, a
+        C-contiguous float64 array of max_steps * 15 * n * n_total elements, if given)."""
+        n, k = int(self._replay_slots), int(max_steps)
+        i32, m = np.int32, max(n, 1)
+        o = dict(ego=np.zeros((k, n, 5)), jerk=np.zeros((k, n)), state=np.zeros((k, n), i32), stats=np.zeros((k, n, 8), i32),
+                 followed=np.full((k, n), -1, i32), keep=np.zeros((k, n), i32), cost=np.zeros((k, n)),
+                 after=np.zeros((k, m), dtype=self.SAFETY_DT), s_now=np.zeros((k, n)), frame=np.zeros(k, i32),
+                 obs_last_frame=np.zeros(k, i32), obs_prev_frame=np.zeros(k, i32), staleness=np.zeros(k),
+                 steps=np.zeros(m, i32), termination=np.zeros(m, i32))
+        if keep_paths:
+            shape = (k, len(_abi.PATH_FIELDS), n, self.n_total_samples)
+            if paths_out is None:
+                paths_out = np.empty(shape)
+            elif paths_out.size != int(np.prod(shape)) or paths_out.dtype != np.float64 or not paths_out.flags.c_contiguous:
+                raise ValueError(f"paths_out must be a C-contiguous float64 array of {int(np.prod(shape))} elements")
+            o["paths"] = paths_out.reshape(shape)
+        ro = _abi.LoopRunOut()
+        for name, arr in o.items():
+            setattr(ro, name, _addr(arr) if arr.size else None)
+        fn = _fast(self._lib, "fot_loop_run", _vp, C.c_int32, _vp)
+        done = fn(self._h, k, C.addressof(ro))
+        if done < 0:
+            _abi.check(self._h, done)
+        for name in _abi.LOOP_RUN_OUT_FIELDS:
+            if name in o and name not in ("steps", "termination"):
+                o[name] = o[name][:done]
+        o["after"] = o["after"][:, :n]
+        o["steps"], o["termination"] = o["steps"][:n], o["termination"][:n]
+        o["n_steps"] = int(done)
+        return o
+
     def _loop_frame(self, frame: dict):
         """fot_loop_frame from the dictionary ``loop_plan`` / ``loop_step`` take (+ the arrays it points into)."""
         f, keep = _abi.LoopFrame(), []

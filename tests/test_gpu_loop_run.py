@@ -1,0 +1,302 @@
+"""Whole replayed closed-loop episodes inside the library (fot_loop_set_replay / fot_loop_run, BatchedClosedLoop with
+resident=True) on the GPU: against the reference episodes, byte for byte against the one-call-per-step form
+(fot_loop_step), in chunks, and through the C ABI alone."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from closed_loop_common import assert_episode_matches, assert_npz_layout, load_episodes, scenario_config
+from integrated_path_planning_amd import _abi
+from integrated_path_planning_amd.closed_loop import BatchedClosedLoop, _VectorStateMachine, _Cfg, footprint_from_config
+from integrated_path_planning_amd.planner import BatchPlanner
+from integrated_path_planning_amd.prediction import PredictionResampler
+
+pytestmark = pytest.mark.gpu
+
+VARIANTS = ["base", "fast", "shift", "walls", "turn", "footprint", "inflate", "rnd0", "rnd1", "rnd2", "rnd3", "rnd4", "rnd5"]
+STEP_KEYS = ("sel", "ego", "jerk", "state", "stats", "keep", "cost", "after", "has_path")
+
+
+@pytest.fixture(scope="module")
+def episodes():
+    return load_episodes()
+
+
+def _spy_s_now(sim):
+    """Collects the s_now of every step from the library call the loop makes (the step dictionaries do not keep it)."""
+    got = []
+    if sim._resident:
+        orig = sim.engine.loop_run
+
+        def loop_run(*a, **kw):
+            o = orig(*a, **kw)
+            for k in range(o["n_steps"]):
+                got.append(o["s_now"][k][o["followed"][k] >= 0].copy())
+            return o
+        sim.engine.loop_run = loop_run
+    else:
+        orig = sim.engine.loop_step
+
+        def loop_step(frame, episode):
+            o = orig(frame, episode)
+            got.append(o["s_now"].copy())
+            return o
+        sim.engine.loop_step = loop_step
+    return got
+
+
+def _assert_same_bytes(a, b, s_a, s_b, paths=True, label=""):
+    """Two loops step by step: equal BYTES of everything a step leaves, of termination and of the step counts."""
+    assert len(a._steps) == len(b._steps), f"{label}: {len(a._steps)} lock steps against {len(b._steps)}"
+    assert len(s_a) == len(s_b) == len(a._steps)
+    for k, (x, y) in enumerate(zip(a._steps, b._steps)):
+        for key in STEP_KEYS:
+            u, v = np.ascontiguousarray(x[key]), np.ascontiguousarray(y[key])
+            assert u.dtype == v.dtype and u.shape == v.shape, f"{label} step {k} {key}: {u.dtype}{u.shape} / {v.dtype}{v.shape}"
+            assert u.tobytes() == v.tobytes(), f"{label} step {k}: {key} differs"
+        assert x["time"] == y["time"] and x["off"].tobytes() == np.asarray(y["off"]).tobytes()
+        assert s_a[k].tobytes() == s_b[k].tobytes(), f"{label} step {k}: s_now differs"
+        assert x["pos"].tobytes() == y["pos"].tobytes() and x["vel"].tobytes() == y["vel"].tobytes(), f"{label} step {k}: frame"
+        if paths:
+            for i in np.flatnonzero(x["has_path"]):
+                kn = int(x["keep"][i])
+                for f in _abi.PATH_FIELDS:
+                    assert x["paths"][f][i, :kn].tobytes() == y["paths"][f][i, :kn].tobytes(), f"{label} step {k} ep {i}: path {f}"
+    assert a.termination.tobytes() == b.termination.tobytes(), label
+    assert a.step_counts.tobytes() == b.step_counts.tobytes(), label
+    assert a.alive.tobytes() == b.alive.tobytes() and a.ego.tobytes() == b.ego.tobytes(), label
+    assert a.sm.state.tobytes() == b.sm.state.tobytes() and a.last_stats.tobytes() == b.last_stats.tobytes(), label
+    assert a.time == b.time and a.frame == b.frame
+
+
+def _assert_same_predictions(a, b):
+    """the predicted trajectories of the first, a middle and the last step of every episode"""
+    for ea, eb in zip(a.episodes, b.episodes):
+        n = len(ea.history)
+        for i in sorted({0, n // 2, n - 1}) if n else ():
+            pa, pb = ea.history[i].predicted_trajectories, eb.history[i].predicted_trajectories
+            assert (pa is None) == (pb is None)
+            if pa is not None:
+                assert pa.tobytes() == pb.tobytes()
+
+
+@pytest.mark.parametrize("name", VARIANTS)
+def test_reference_episode_resident_and_equal_to_stepwise(episodes, name, tmp_path):
+    """Every reference episode with the whole run inside the library: the reference's steps, termination and
+    trajectory.npz layout; and byte for byte what the one-call-per-step form leaves (the arithmetic is the same, only
+    where the bytes live differs)."""
+    cfg = scenario_config(episodes["meta"], name)
+    tracks = [episodes[name + "_ped_traj"]]
+    with BatchedClosedLoop(cfg, tracks, resident=True) as res, BatchedClosedLoop(cfg, tracks) as stp:
+        assert res._resident and not stp._resident and stp._native
+        s_res, s_stp = _spy_s_now(res), _spy_s_now(stp)
+        hists = res.run()
+        assert_episode_matches(hists[0], res.episodes[0].termination_reason, episodes, name)
+        files = res.save_results(str(tmp_path))
+        z = np.load(files[0], allow_pickle=True)
+        var = episodes["meta"]["variants"][name]
+        assert_npz_layout({k: z[k] for k in z.files}, var["npz_keys"], var["steps"])
+        stp.run()
+        _assert_same_bytes(res, stp, s_res, s_stp, label=name)
+        _assert_same_predictions(res, stp)
+
+
+def _crowds(episodes):
+    """52 episodes on the base scenario: six recorded crowds, each as it is, shifted sideways and along the road,
+    cut short (the last frame is then held), thinned out; one episode without pedestrians; standing crowds."""
+    tracks = []
+    for name in ("base", "fast", "shift", "rnd0", "rnd1", "rnd5"):
+        tr = episodes[name + "_ped_traj"]
+        tracks += [tr, tr + np.array([0.0, 0.4]), tr - np.array([0.0, 0.4]), tr[:120], tr[:70], tr[:, ::2],
+                   tr + np.array([2.0, 0.0]), tr[:200, 1::3]]
+    walk = episodes["base_ped_traj"]
+    tracks += [np.zeros((len(walk), 0, 2)), np.repeat(walk[60:61], 90, axis=0), np.repeat(walk[60:61, :3], 30, axis=0),
+               walk[:1]]
+    return tracks
+
+
+def test_lock_step_group_equals_stepwise(episodes):
+    """One lock-step group whose episodes end at different steps by collision, at the goal and by timeout (200 of the
+    base episode's 274 steps), with an episode without pedestrians and recordings of different lengths."""
+    cfg = scenario_config(episodes["meta"])
+    tracks = _crowds(episodes)
+    assert len(tracks) >= 48
+    with BatchedClosedLoop(cfg, tracks, resident=True) as res, BatchedClosedLoop(cfg, tracks) as stp:
+        s_res, s_stp = _spy_s_now(res), _spy_s_now(stp)
+        res.run(200)
+        stp.run(200)
+        reasons = [e.termination_reason for e in stp.episodes]
+        assert {"collision", "goal", "timeout"} <= set(reasons), reasons
+        assert len(set(stp.step_counts.tolist())) > 4                # they end at different steps
+        _assert_same_bytes(res, stp, s_res, s_stp, label="group")
+        assert [e.termination_reason for e in res.episodes] == reasons
+        _assert_same_predictions(res, stp)
+
+
+def test_chunked_runs_equal_one_run(episodes):
+    """run(7), run(1), step(), run() in sequence leave what one run() leaves; without the paths the other outputs are
+    the same; fot_loop_step on the handle is refused while the replay is set."""
+    cfg = scenario_config(episodes["meta"])
+    tracks = [episodes[n + "_ped_traj"] for n in ("base", "fast", "shift")]
+    with BatchedClosedLoop(cfg, tracks, resident=True) as one, BatchedClosedLoop(cfg, tracks, resident=True) as many, \
+            BatchedClosedLoop(cfg, tracks, resident=True) as bare:
+        s_one, s_many, s_bare = _spy_s_now(one), _spy_s_now(many), _spy_s_now(bare)
+        one.run()
+        many.run(7)
+        assert len(many._steps) == 7 and many.frame == one.frame - len(one._steps) + 7
+        many.run(1)
+        assert many.step() == 3 and len(many._steps) == 9
+        many.run()
+        _assert_same_bytes(one, many, s_one, s_many, label="chunks")
+        bare.run(keep_paths=False)
+        _assert_same_bytes(one, bare, s_one, s_bare, paths=False, label="no paths")
+        for n, ep in zip(("base", "fast", "shift"), many.episodes):
+            assert_episode_matches(ep.history, ep.termination_reason, episodes, n)
+        frame = dict(ped_off=np.zeros(2, np.int32), ped_pos=np.zeros((0, 2)), ped_vel=np.zeros((0, 2)), ego_radius=1.0,
+                     ped_radius=0.2)
+        with pytest.raises(_abi.FotError) as err:
+            many.engine.loop_step(frame, np.zeros(1, np.int32))
+        assert err.value.code == _abi.ERR_INVALID and "replay" in str(err.value)
+
+
+def test_standing_and_walking_crowds_in_one_frame(episodes):
+    """Episodes that disagree on the prepend rule in one frame (a standing crowd beside a walking one, one without
+    pedestrians): the resident step predicts them in ONE launch and equals the stepwise form, which launches per run of
+    equal flags."""
+    cfg = scenario_config(episodes["meta"])
+    walk = episodes["base_ped_traj"][:140]
+    stand = np.repeat(walk[60:61], len(walk), axis=0)
+    none = np.zeros((len(walk), 0, 2))
+    tracks = [stand, walk, none, stand[:, :3], walk[:, ::2]]
+    with BatchedClosedLoop(cfg, tracks, resident=True) as res, BatchedClosedLoop(cfg, tracks) as stp:
+        s_res, s_stp = _spy_s_now(res), _spy_s_now(stp)
+        res.run(60)
+        stp.run(60)
+        _assert_same_bytes(res, stp, s_res, s_stp, label="mixed prepend")
+        for ea, eb in zip(res.episodes, stp.episodes):
+            for ra, rb in zip(ea.history, eb.history):
+                pa, pb = ra.predicted_trajectories, rb.predicted_trajectories
+                assert (pa is None) == (pb is None) and (pa is None or pa.tobytes() == pb.tobytes())
+
+
+# ---- the C ABI alone -----------------------------------------------------------------------------------------------
+def _planner_for(cfg):
+    c = _Cfg(cfg)
+    return BatchPlanner(
+        waypoints=(np.asarray(c.reference_waypoints_x, float), np.asarray(c.reference_waypoints_y, float)), device=-1,
+        max_speed=c.ego_max_speed, max_accel=c.ego_max_accel, max_curvature=c.ego_max_curvature,
+        max_lat_accel=c.ego_max_lat_accel, dt=c.dt, d_road_w=c.d_road_w, max_road_width=c.max_road_width,
+        robot_radius=c.ego_radius, obstacle_radius=c.obstacle_radius, min_t=c.min_t, max_t=c.max_t, d_t_s=c.d_t_s,
+        n_s_sample=c.n_s_sample, k_j=c.k_j, k_t=c.k_t, k_d=c.k_d, k_s_dot=c.k_s_dot, k_lat=c.k_lat, k_lon=c.k_lon,
+        chance_epsilon=c.chance_epsilon, collision_margin_inflation=c.collision_margin_inflation,
+        footprint=footprint_from_config(c))
+
+
+def _loop_config(cfg):
+    c = _Cfg(cfg)
+    sm, lc = _VectorStateMachine(c, 1), _abi.LoopConfig()
+    lc.dt, lc.target_speed, lc.max_accel, lc.emergency_decel = c.dt, sm.target, c.ego_max_accel, c.ego_emergency_decel
+    lc.clearance_caution, lc.clearance_emergency = sm.clr_caution, sm.clr_emergency
+    lc.trigger_clearance_caution, lc.trigger_time_headway = sm.trig_c, sm.trig_h
+    lc.envelope_decel, lc.envelope_standoff = sm.env_decel, sm.env_standoff
+    lc.caution_accel, lc.caution_speed, lc.caution_speed_mult = sm.c_accel, sm.c_speed, sm.c_speed_mult
+    lc.emergency_accel, lc.emergency_lat_accel, lc.max_replan = sm.e_accel, sm.e_lat, 3
+    return lc
+
+
+def test_c_abi_episode_in_three_calls_and_refusals(episodes):
+    """fot_loop_begin -> fot_loop_set_replay -> fot_loop_run through ctypes, no BatchedClosedLoop: the base episode
+    (274 steps, goal).  Every refusal returns its code and leaves the handle as it was: a valid episode after the refused
+    calls equals the undisturbed one byte for byte."""
+    cfg = scenario_config(episodes["meta"])
+    lib = _abi.lib()
+    pos = np.ascontiguousarray(episodes["base_ped_traj"], np.float64)
+    vel = np.zeros_like(pos)
+    vel[:-1] = (pos[1:] - pos[:-1]) / cfg["dt"]
+    vel[-1] = vel[-2]
+    off, nfr = np.array([0, pos.shape[1]], np.int32), np.array([len(pos)], np.int32)
+    ego5 = np.array([cfg["ego_initial_state"][:5]], np.float64)
+    lc = _loop_config(cfg)
+
+    def replay(bp, **change):
+        r = _abi.LoopReplay()
+        r.n_slots, r.n_frames_max, r.obs_len, r.pred_len = 1, len(pos), cfg["obs_len"], cfg["pred_len"]
+        r.warmup_frames, r.use_footprint = int(cfg["obs_len"] * 0.4 / cfg["dt"]), 0
+        r.ped_off, r.n_frames, r.pos, r.vel = off.ctypes.data, nfr.ctypes.data, pos.ctypes.data, vel.ctypes.data
+        r.rp = PredictionResampler(bp, pred_len=cfg["pred_len"], sgan_dt=0.4, sim_dt=cfg["dt"], plan_horizon=cfg["max_t"]).params
+        r.ego_radius, r.ped_radius = cfg["ego_radius"], cfg["ped_radius"]
+        r.s_end, r.goal_distance = float(bp.path_coeffs()[0][-1]), 2.0
+        keep = []
+        for k, v in change.items():
+            if isinstance(v, np.ndarray):
+                keep.append(v)
+                v = v.ctypes.data
+            if k in ("plan_horizon",):
+                r.rp = _abi.ResampleParams(0.4, cfg["dt"], float(v))
+            else:
+                setattr(r, k, v)
+        r._keep = keep
+        return r
+
+    def set_replay(bp, **change):
+        r = replay(bp, **change)                                     # (alive across the call)
+        return lib.fot_loop_set_replay(bp._h, C.addressof(r))
+
+    def episode(bp):
+        h, chunk, n_total = bp._h, 64, bp.n_total_samples
+        out = {k: [] for k in ("ego", "jerk", "state", "after", "s_now", "keep", "paths", "frame", "staleness")}
+        steps, term = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        while True:
+            a = dict(ego=np.zeros((chunk, 1, 5)), jerk=np.zeros((chunk, 1)), state=np.zeros((chunk, 1), np.int32),
+                     after=np.zeros((chunk, 1), dtype=bp.SAFETY_DT), s_now=np.zeros((chunk, 1)),
+                     keep=np.zeros((chunk, 1), np.int32), paths=np.zeros((chunk, 15, 1, n_total)),
+                     frame=np.zeros(chunk, np.int32), staleness=np.zeros(chunk))
+            ro = _abi.LoopRunOut()
+            for k, v in a.items():
+                setattr(ro, k, v.ctypes.data)
+            ro.steps, ro.termination = steps.ctypes.data, term.ctypes.data
+            done = lib.fot_loop_run(h, chunk, C.addressof(ro))
+            assert done >= 0, lib.fot_last_error(h)
+            if done == 0:
+                break
+            for k, v in a.items():
+                out[k].append(v[:done].copy())
+        return {k: np.concatenate(v) for k, v in out.items()}, int(steps[0]), int(term[0])
+
+    empty_out = _abi.LoopRunOut()
+    with _planner_for(cfg) as bp:
+        h = bp._h
+        # refused: no fot_loop_begin yet
+        assert set_replay(bp) == _abi.ERR_INVALID
+        assert lib.fot_loop_run(h, 4, C.addressof(empty_out)) == _abi.ERR_INVALID
+        _abi.check(h, lib.fot_loop_begin(h, 1, C.addressof(lc), ego5.ctypes.data))
+        _abi.check(h, set_replay(bp))
+        first, steps, term = episode(bp)
+        meta = episodes["meta"]["variants"]["base"]
+        assert (steps, term) == (meta["steps"], 2) and meta["termination"] == "goal"
+        want = episodes["base_ego"]
+        np.testing.assert_allclose(first["ego"][:, 0, :], want[:, :5], rtol=1e-6, atol=1e-6)
+        np.testing.assert_allclose(first["jerk"][:, 0], want[:, 5], rtol=1e-6, atol=1e-4)
+        np.testing.assert_array_equal(first["state"][:, 0], episodes["base_state"])
+        np.testing.assert_array_equal(first["keep"][:, 0], episodes["base_planned_len"])
+        for i, kn in enumerate(episodes["base_planned_len"]):
+            np.testing.assert_allclose(first["paths"][i, 9, 0, :kn], episodes["base_planned_x"][i, :kn], atol=1e-6)
+            assert not first["paths"][i, :, 0, kn:].any()
+        # a second, valid episode on the same handle with every refusal in between
+        _abi.check(h, lib.fot_loop_begin(h, 1, C.addressof(lc), ego5.ctypes.data))
+        assert lib.fot_loop_run(h, 4, C.addressof(empty_out)) == _abi.ERR_INVALID     # fot_loop_begin dropped the replay
+        _abi.check(h, set_replay(bp))
+        refusals = [(dict(n_slots=2), _abi.ERR_INVALID), (dict(ped_off=np.array([0, -1], np.int32)), _abi.ERR_INVALID),
+                    (dict(ped_off=np.array([1, 14], np.int32)), _abi.ERR_INVALID),
+                    (dict(n_frames=np.array([0], np.int32)), _abi.ERR_INVALID),
+                    (dict(n_frames=np.array([len(pos) + 1], np.int32)), _abi.ERR_INVALID),
+                    (dict(obs_len=1), _abi.ERR_INVALID), (dict(pred_len=_abi.MAX_PRED_LEN + 1), _abi.ERR_UNSUPPORTED),
+                    (dict(plan_horizon=25.6), _abi.ERR_UNSUPPORTED)]
+        for change, code in refusals:
+            assert set_replay(bp, **change) == code, change
+            assert lib.fot_last_error(h)
+        again, steps2, term2 = episode(bp)
+        assert (steps2, term2) == (steps, term)
+        for k in first:
+            assert first[k].tobytes() == again[k].tobytes(), k
