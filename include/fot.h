@@ -221,14 +221,20 @@ int fot_synchronize(fot_handle *h);
  *     FOT_ERR_NO_PATH_SET, a FOT_PREV_S_CHAINED instance on another scenario than its predecessor FOT_ERR_INVALID
  *     (a chain is one planner object); a refused call changes nothing
  *   - fot_debug_candidates / fot_debug_candidate_path / fot_debug_margins answer for instance i on its own scenario
- *   - every other entry point works on scenario 0: fot_loop_*, fot_check_paths, fot_check_collision_paths,
- *     fot_spline_eval, fot_get_path_coeffs, fot_frenet_state_batch, fot_safety_metrics_batch, fot_debug_time_info */
+ *   - a closed loop begun with fot_loop_begin_scenarios runs every episode slot on a scenario of its own (below); a loop
+ *     begun with fot_loop_begin, and the two-call form fot_loop_plan / fot_loop_observe*, work on scenario 0
+ *   - every other entry point works on scenario 0: fot_check_paths, fot_check_collision_paths,
+ *     fot_spline_eval, fot_get_path_coeffs (fot_get_scenario_path_coeffs reads any), fot_frenet_state_batch, fot_safety_metrics_batch, fot_debug_time_info */
 #define FOT_MAX_SCENARIOS 64
 int fot_add_scenario(fot_handle *h, const fot_params *params, int32_t *id_out);
 int fot_set_scenario_path_waypoints(fot_handle *h, int32_t id, int32_t n, const double *wx, const double *wy);
 int fot_set_scenario_path_coeffs(fot_handle *h, int32_t id, int32_t n, const double *s,
                                  const double *ax, const double *bx, const double *cx, const double *dx,
                                  const double *ay, const double *by, const double *cy, const double *dy);
+/* fot_get_path_coeffs for scenario id (0: the same call) */
+int fot_get_scenario_path_coeffs(const fot_handle *h, int32_t id, int32_t *n_out, double *s,
+                                 double *ax, double *bx, double *cx, double *dx,
+                                 double *ay, double *by, double *cy, double *dy);
 int fot_plan_batch_scenarios(fot_handle *h, const fot_batch *batch, const int32_t *scenario, fot_result *out);
 int fot_plan_batch_scenarios_device(fot_handle *h, const fot_batch *batch, const int32_t *scenario,
                                     fot_result *out_dev, void *stream);
@@ -359,7 +365,9 @@ int fot_safety_metrics_batch(fot_handle *h, int32_t n, const double *ego, const 
  * ego5 [n][5] = x, y, yaw, v, a; prev_s [n], NaN = no cached arc length.  _begin enqueues the two launches and returns,
  * _end waits and hands the results over (any may be NULL); no other call on the handle in between.
  *
- * fot_loop_set_static: the static obstacle points every request of the loop sees (kept in HBM, one copy per request). */
+ * fot_loop_set_static: the static obstacle points every request of the loop sees (kept in HBM, one copy per request);
+ * it is fot_loop_set_scenario_static for scenario 0.  These two calls and fot_loop_observe* are the two-call form: they
+ * work on scenario 0 whatever loop the handle has begun. */
 typedef struct fot_loop_frame {
     int32_t n_episodes;
     int32_t pred_len;               /* of the predictor (trajectory_predictor.py:188) */
@@ -438,6 +446,27 @@ typedef struct fot_loop_step_out {
     int32_t _pad;
 } fot_loop_step_out;
 int fot_loop_begin(fot_handle *h, int32_t n_episodes, const fot_loop_config *cfg, const double *ego5);
+/* ---- episodes of different scenarios in one lock step ---------------------------------------------------------------
+ * fot_loop_begin_scenarios is fot_loop_begin with a scenario per episode slot: slot e runs on scenario slot_scenario[e]
+ * (fot_add_scenario; 0 = the handle's own), with the fail-safe and simulator constants cfg[slot_scenario[e]] and, when
+ * use_footprint[slot_scenario[e]] != 0 (use_footprint NULL = all 0), the scenario's multi-circle footprint in the safety
+ * metrics.  cfg / use_footprint: n_cfg entries indexed by scenario id; entries of scenarios no slot names are not read.
+ * fot_loop_begin is this call with every slot on scenario 0.  Per slot from then on: the reference path and planner
+ * constants of its plan() calls (escalation retries included), the path of the goal test's nearest point, the metrics'
+ * footprint, the state machine's and the emergency stop's constants, the static obstacle points
+ * (fot_loop_set_scenario_static: scenario id's point set, kept once in HBM; a step's per-request blocks are gathered from
+ * the sets on the device) and, in fot_loop_run, the goal: s_end is the last knot of the slot's own path, and
+ * fot_loop_replay.s_end is ignored.  fot_loop_frame.use_footprint / fot_loop_replay.use_footprint are ignored too.
+ * fot_loop_step and fot_loop_run take no new argument: the slot knows its scenario.
+ * Common to the scenarios of a loop: dt (and max_t: fot_add_scenario), and what the frame / the replay carries once:
+ * ego_radius, ped_radius, pred_len, obs_len, sgan_dt, goal_distance.
+ * Refusals; a refused call changes nothing, a run in progress goes on: slot_scenario[e] not a scenario of the handle, or
+ * n_cfg <= slot_scenario[e], or configurations in use with different dt (FOT_ERR_INVALID); a slot's scenario without a
+ * path (FOT_ERR_NO_PATH_SET); fot_loop_set_scenario_static with an unknown id (FOT_ERR_INVALID); fot_loop_step of a
+ * scenario loop with dist_raw samples (FOT_ERR_UNSUPPORTED: constant-velocity predictor only). */
+int fot_loop_begin_scenarios(fot_handle *h, int32_t n_episodes, int32_t n_cfg, const fot_loop_config *cfg,
+                             const int32_t *use_footprint, const int32_t *slot_scenario, const double *ego5);
+int fot_loop_set_scenario_static(fot_handle *h, int32_t id, int32_t n_points, const double *xy);
 int fot_loop_step(fot_handle *h, const fot_loop_frame *frame, const int32_t *episode, fot_loop_step_out *out);
 
 /* ---- whole replayed episodes behind one call ------------------------------------------------------------------------
@@ -452,7 +481,8 @@ int fot_loop_step(fot_handle *h, const fot_loop_frame *frame, const int32_t *epi
  * starting at 0 or decreasing / a slot with n_frames < 1 or > n_frames_max / obs_len < 2 / bad predictor parameters
  * (FOT_ERR_INVALID), pred_len > FOT_MAX_PRED_LEN or n_dense + 1 > FOT_MAX_NT (FOT_ERR_UNSUPPORTED).
  * Constant-velocity predictor only: a frame with dist_raw samples needs a producer every step and stays with
- * fot_loop_step.  Scenario 0, like every fot_loop_*.
+ * fot_loop_step.  The slots run on scenario 0 after fot_loop_begin, each on its own scenario after
+ * fot_loop_begin_scenarios.
  *
  * fot_loop_run: one lock step is what the closed loop around fot_loop_step does, in this order: the replay frame and the
  * observer's clock advance (observer.py:28-102, its 1e-9 sampling tolerance, samples rounded through float32), the frame
@@ -482,7 +512,7 @@ typedef struct fot_loop_replay {
     const double *pos, *vel;        /* [n_frames_max][ped_off[n_slots]][2] host memory, frame 0 = time 0 before warm-up */
     fot_resample_params rp;
     double ego_radius, ped_radius;
-    double s_end;                   /* arc length of the reference path's end */
+    double s_end;                   /* arc length of the reference path's end (a scenario loop: ignored, each slot's own path's end) */
     double goal_distance;           /* the goal test's distance (2.0 m in the reference, integrated_simulator.py:873-883) */
 } fot_loop_replay;
 typedef struct fot_loop_run_out {

@@ -145,7 +145,8 @@ SYMBOLS = ["fot_version", "fot_abi_info", "fot_create", "fot_destroy", "fot_live
            "fot_predict_cv", "fot_safety_metrics_batch", "fot_loop_set_static", "fot_loop_plan", "fot_loop_observe", "fot_loop_observe_begin", "fot_loop_observe_end", "fot_loop_begin", "fot_loop_step", "fot_loop_set_replay", "fot_loop_run", "fot_gather_paths", "fot_wire_n_total", "fot_wire_record_bytes",
            "fot_pack_records_device", "fot_pack_records_host", "fot_unpack_records", "fot_profile_enable", "fot_profile_read", "fot_profile_kernel_name",
            "fot_add_scenario", "fot_set_scenario_path_waypoints", "fot_set_scenario_path_coeffs",
-           "fot_plan_batch_scenarios", "fot_plan_batch_scenarios_device"]
+           "fot_plan_batch_scenarios", "fot_plan_batch_scenarios_device", "fot_get_scenario_path_coeffs",
+           "fot_loop_begin_scenarios", "fot_loop_set_scenario_static"]
 PROFILE_KERNELS = 3                      # FOT_PROFILE_KERNELS (include/fot.h)
 ABI_VERSION = 5                          # FOT_ABI_VERSION
 MAX_TI, MAX_TV, MAX_BRAKE, MAX_PRED_LEN = 64, 32, 32, 32
@@ -338,7 +339,10 @@ def lib():
                        ("fot_set_scenario_path_waypoints", [vp, C.c_int32, C.c_int32, dp, dp]),
                        ("fot_set_scenario_path_coeffs", [vp, C.c_int32, C.c_int32] + [dp] * 9),
                        ("fot_plan_batch_scenarios", [vp, C.POINTER(Batch), ip, C.POINTER(Result)]),
-                       ("fot_plan_batch_scenarios_device", [vp, C.POINTER(Batch), ip, vp, vp])):
+                       ("fot_plan_batch_scenarios_device", [vp, C.POINTER(Batch), ip, vp, vp]),
+                       ("fot_get_scenario_path_coeffs", [vp, C.c_int32, ip] + [dp] * 9),
+                       ("fot_loop_begin_scenarios", [vp, C.c_int32, C.c_int32, vp, vp, vp, vp]),
+                       ("fot_loop_set_scenario_static", [vp, C.c_int32, C.c_int32, vp])):
         if hasattr(L, name):
             getattr(L, name).argtypes = args
     L.fot_synchronize.argtypes = [vp]

@@ -144,43 +144,75 @@ class _VectorStateMachine:
     episodes at once: the same transitions and planner configurations, as masked array updates.  Codes 0 / 1 / 2 =
     NORMAL / CAUTION / EMERGENCY."""
 
-    def __init__(self, config, n: int):
+    CONSTANTS = ("clr_caution", "clr_emergency", "trig_c", "trig_h", "env_decel", "env_standoff", "target", "c_accel",
+                 "c_speed_mult", "c_speed", "e_accel", "e_lat")
+
+    @staticmethod
+    def constants_of(config) -> Dict[str, float]:
+        """The machine's constants as the scalar class resolves them from one configuration."""
         one = FailSafeStateMachine(config)                       # the scalar class resolves the configuration keys
         c = config
-        self.clr_caution, self.clr_emergency = one.clearance_caution, one.clearance_emergency
-        self.trig_c, self.trig_h = one.trigger_clearance_caution, one.trigger_time_headway
-        self.env_decel, self.env_standoff = one.envelope_decel, one.envelope_standoff
-        self.target = float(c.ego_target_speed)
-        self.c_accel = c.ego_max_accel * getattr(c, "state_machine_caution_accel_multiplier", 1.5)
-        self.c_speed_mult = getattr(c, "state_machine_caution_speed_multiplier", 0.8)
-        self.c_speed = c.ego_max_speed * self.c_speed_mult
-        self.e_accel = c.ego_max_accel * getattr(c, "state_machine_emergency_accel_multiplier", 3.0)
-        self.e_lat = getattr(c, "ego_max_lat_accel", 3.0) * getattr(c, "state_machine_emergency_lat_accel_multiplier", 2.0)
+        k = dict(clr_caution=one.clearance_caution, clr_emergency=one.clearance_emergency,
+                 trig_c=one.trigger_clearance_caution, trig_h=one.trigger_time_headway,
+                 env_decel=one.envelope_decel, env_standoff=one.envelope_standoff, target=float(c.ego_target_speed))
+        k["c_accel"] = c.ego_max_accel * getattr(c, "state_machine_caution_accel_multiplier", 1.5)
+        k["c_speed_mult"] = getattr(c, "state_machine_caution_speed_multiplier", 0.8)
+        k["c_speed"] = c.ego_max_speed * k["c_speed_mult"]
+        k["e_accel"] = c.ego_max_accel * getattr(c, "state_machine_emergency_accel_multiplier", 3.0)
+        k["e_lat"] = getattr(c, "ego_max_lat_accel", 3.0) * getattr(c, "state_machine_emergency_lat_accel_multiplier", 2.0)
+        return k
+
+    def __init__(self, config, n: int, slot_scenario=None):
+        """config: one configuration (every constant a scalar, as before), or a sequence of configurations with
+        ``slot_scenario[e]`` = the configuration of episode e (every constant an array of n, one entry per episode)."""
+        if slot_scenario is None:
+            for name, v in self.constants_of(config).items():
+                setattr(self, name, v)
+        else:
+            per = [self.constants_of(c) for c in config]
+            scen = np.asarray(slot_scenario, np.int64)
+            if scen.shape != (n,):
+                raise ValueError("slot_scenario: one configuration index per episode")
+            for name in self.CONSTANTS:
+                setattr(self, name, np.array([per[k][name] for k in scen], dtype=float))
+        self.per_episode = slot_scenario is not None
         self.state = np.zeros(n, np.int64)
         self.fails = np.zeros(n, np.int64)
         self.clear = np.full(n, np.inf)                          # _last_clearance
         self.clear_ahead = np.full(n, np.inf)                    # _last_clearance_ahead
 
-    def config(self, state: np.ndarray, clear_ahead: np.ndarray):
-        """_get_planner_config (:181-247) -> target speed, overrides [n, 4] (NaN = absent), max_stop (NaN = None)."""
+    def _k(self, name: str, who):
+        """constant ``name`` for the episodes ``who`` (the scalar itself when there is one configuration)"""
+        v = getattr(self, name)
+        if not self.per_episode:
+            return v
+        if who is None:
+            raise ValueError("per-episode constants: say which episodes (who=)")
+        return v[who]
+
+    def config(self, state: np.ndarray, clear_ahead: np.ndarray, who=None):
+        """_get_planner_config (:181-247) -> target speed, overrides [n, 4] (NaN = absent), max_stop (NaN = None).
+        who: the episode of every entry (needed when the constants are per episode)."""
         n = len(state)
+        env_decel, env_standoff, tgt0 = self._k("env_decel", who), self._k("env_standoff", who), self._k("target", who)
+        c_speed_mult = self._k("c_speed_mult", who)
         fin = np.isfinite(clear_ahead)
-        has_env = fin & (self.env_decel > 0.0)
-        v_env = np.sqrt(2.0 * self.env_decel * np.maximum(np.where(fin, clear_ahead, 0.0) - self.env_standoff, 0.0))
+        has_env = fin & (env_decel > 0.0)
+        v_env = np.sqrt(2.0 * env_decel * np.maximum(np.where(fin, clear_ahead, 0.0) - env_standoff, 0.0))
         stop_room = np.where(fin, np.maximum(np.where(fin, clear_ahead, 0.0) - 0.2, 0.05), np.nan)
-        target = np.full(n, self.target)
+        target = np.full(n, tgt0)
         ov = np.full((n, 4), np.nan)
         stop = np.full(n, np.nan)
         nm, ca, em = state == 0, state == 1, state == 2
-        target = np.where(nm & has_env & (v_env < self.target), v_env, target)
-        t_ca = np.where(has_env, np.minimum(self.target * self.c_speed_mult, v_env), self.target * self.c_speed_mult)
+        target = np.where(nm & has_env & (v_env < tgt0), v_env, target)
+        t_ca = np.where(has_env, np.minimum(tgt0 * c_speed_mult, v_env), tgt0 * c_speed_mult)
         target = np.where(ca, t_ca, target)
         stop = np.where(ca & has_env & (v_env <= 0.0), stop_room, stop)
-        ov[ca, 1], ov[ca, 0] = self.c_accel, self.c_speed
+        per = (lambda name, m: self._k(name, who)[m]) if self.per_episode else (lambda name, m: getattr(self, name))
+        ov[ca, 1], ov[ca, 0] = per("c_accel", ca), per("c_speed", ca)
         target = np.where(em, 0.0, target)
-        ov[em, 1], ov[em, 3] = self.e_accel, self.e_lat
-        if self.env_decel > 0.0:
-            stop = np.where(em, stop_room, stop)
+        ov[em, 1], ov[em, 3] = per("e_accel", em), per("e_lat", em)
+        stop = np.where(em & (env_decel > 0.0), stop_room, stop)
         return target, ov, stop
 
     def update(self, sel: np.ndarray, found: np.ndarray, clearance: np.ndarray, clearance_ahead: np.ndarray,
@@ -188,7 +220,7 @@ class _VectorStateMachine:
         """update() (:116-179) for the episodes ``sel`` (index array): observe the metrics, then the transitions."""
         self.clear[sel], self.clear_ahead[sel] = clearance, clearance_ahead
         st, fl = self.state[sel], self.fails[sel]
-        trigger = self.trig_c + self.trig_h * np.maximum(speed, 0.0)
+        trigger = self._k("trig_c", sel) + self._k("trig_h", sel) * np.maximum(speed, 0.0)
         nm, ca, em = st == 0, st == 1, st == 2
         new_st, new_fl = st.copy(), fl.copy()
         a = nm & ~found
@@ -197,11 +229,11 @@ class _VectorStateMachine:
         new_st[b] = 1; new_fl[b] = 0
         new_fl[nm & found & ~b] = 0
         c1 = ca & found & (fl == 0)
-        new_st[c1 & (clearance > np.maximum(self.clr_caution, trigger))] = 0
+        new_st[c1 & (clearance > np.maximum(self._k("clr_caution", sel), trigger))] = 0
         c2 = ca & ~c1 & ~found
         new_st[c2] = 2; new_fl[c2] = fl[c2] + 1
         new_fl[ca & ~c1 & found] = 0
-        new_st[em & found & (clearance > self.clr_emergency)] = 1
+        new_st[em & found & (clearance > self._k("clr_emergency", sel))] = 1
         self.state[sel], self.fails[sel] = new_st, new_fl
 
 
@@ -368,11 +400,86 @@ def emergency_stop(x, y, yaw, v, clearance_ahead, dt, max_accel, emergency_decel
     return x + v * cy * dt, y + v * sy * dt, nv, na
 
 
+def planner_kwargs_from_config(c, footprint=None) -> dict:
+    """The FrenetPlanner arguments a scenario configuration stands for (integrated_simulator.py:342-366)."""
+    return dict(
+        max_speed=c.ego_max_speed, max_accel=c.ego_max_accel, max_curvature=c.ego_max_curvature,
+        max_lat_accel=getattr(c, "ego_max_lat_accel", 3.0), dt=c.dt, d_road_w=c.d_road_w,
+        max_road_width=c.max_road_width, robot_radius=getattr(c, "ego_radius", 1.0), obstacle_radius=c.obstacle_radius,
+        min_t=getattr(c, "min_t", 4.0), max_t=getattr(c, "max_t", 5.0), d_t_s=getattr(c, "d_t_s", 5.0 / 3.6),
+        n_s_sample=getattr(c, "n_s_sample", 1), k_j=c.k_j, k_t=c.k_t, k_d=c.k_d, k_s_dot=c.k_s_dot, k_lat=c.k_lat,
+        k_lon=c.k_lon, chance_epsilon=getattr(c, "chance_epsilon", 0.0),
+        collision_margin_inflation=getattr(c, "collision_margin_inflation", 1.0), footprint=footprint)
+
+
+def loop_config_from(c, k: Dict[str, float], max_replan: int) -> "_abi.LoopConfig":
+    """fot_loop_config of one configuration; k: ``_VectorStateMachine.constants_of(c)``."""
+    lc = _abi.LoopConfig()
+    lc.dt, lc.target_speed, lc.max_accel = float(c.dt), float(k["target"]), float(c.ego_max_accel)
+    dec = getattr(c, "ego_emergency_decel", None)
+    lc.emergency_decel = float("nan") if dec is None else float(dec)
+    lc.clearance_caution, lc.clearance_emergency = float(k["clr_caution"]), float(k["clr_emergency"])
+    lc.trigger_clearance_caution, lc.trigger_time_headway = float(k["trig_c"]), float(k["trig_h"])
+    lc.envelope_decel, lc.envelope_standoff = float(k["env_decel"]), float(k["env_standoff"])
+    lc.caution_accel, lc.caution_speed, lc.caution_speed_mult = float(k["c_accel"]), float(k["c_speed"]), float(k["c_speed_mult"])
+    lc.emergency_accel, lc.emergency_lat_accel = float(k["e_accel"]), float(k["e_lat"])
+    lc.max_replan = int(max_replan)
+    return lc
+
+
+# what the episodes of one loop must agree on: one time grid per handle (dt, max_t), and what the frame / the replay
+# carries once per loop (observer and predictor lengths, the metrics' radii), the run length and the predictor
+COMMON_FIELDS = (("dt", None), ("max_t", 5.0), ("obs_len", None), ("pred_len", None), ("ego_radius", 1.0),
+                 ("ped_radius", 0.3), ("total_time", 0.0), ("prediction_method", "sgan"),
+                 ("distribution_aware_planning", False))
+
+
+def scenario_key(c) -> tuple:
+    """What makes two configurations the same scenario of a loop: the planner and loop fields actually used -- the
+    planner's arguments, the reference path, the footprint, the static obstacle points and the fail-safe / simulator
+    constants.  Fields nothing reads (output_path, visualisation, ...) and the per-episode ones (ego_initial_state) do
+    not count."""
+    fp = footprint_from_config(c)
+    kw = planner_kwargs_from_config(c)
+    kw.pop("footprint")
+    k = _VectorStateMachine.constants_of(c)
+    dec = getattr(c, "ego_emergency_decel", None)
+    return (tuple(sorted((n, float(v)) for n, v in kw.items())),
+            tuple(float(v) for v in c.reference_waypoints_x), tuple(float(v) for v in c.reference_waypoints_y),
+            None if fp is None else (tuple(float(o) for o in fp.offsets), float(fp.radius)),
+            expand_static_obstacles(getattr(c, "static_obstacles", None), step=0.5).tobytes(),
+            tuple(float(k[n]) for n in _VectorStateMachine.CONSTANTS), None if dec is None else float(dec))
+
+
+def merge_configs(configs: Sequence) -> tuple:
+    """Per-episode configurations -> (the distinct scenarios in order of first appearance, scenario index per episode).
+    Equal configurations (``scenario_key``) share a scenario; a difference in a field the episodes of one loop must
+    agree on (``COMMON_FIELDS``) raises ValueError naming the field."""
+    cfgs = [c if not isinstance(c, dict) else _Cfg(c) for c in configs]
+    if not cfgs:
+        raise ValueError("no configuration")
+    for name, default in COMMON_FIELDS:
+        v0 = getattr(cfgs[0], name, default)
+        for i, c in enumerate(cfgs[1:], 1):
+            if getattr(c, name, default) != v0:
+                raise ValueError(f"the episodes of one loop must agree on {name}: episode 0 has {v0!r}, episode {i} "
+                                 f"has {getattr(c, name, default)!r}")
+    keys, distinct, slot = {}, [], np.zeros(len(cfgs), np.int32)
+    for i, c in enumerate(cfgs):
+        key = scenario_key(c)
+        if key not in keys:
+            keys[key] = len(distinct)
+            distinct.append(c)
+        slot[i] = keys[key]
+    return distinct, slot, cfgs
+
+
 class BatchedClosedLoop:
     """N episodes of the reference's closed loop in lock-step.
 
     config: the scenario dictionary (or an object with the same attributes) the reference's SimulationConfig is
-    built from; ped_tracks: one [T, N_i, 2] array of replayed pedestrian positions per episode (frame spacing
+    built from -- or a list of them, one per episode: equal ones share a scenario of the one handle, and episodes of
+    different scenarios advance in the same lock step (one-call step or ``resident=True``); ped_tracks: one [T, N_i, 2] array of replayed pedestrian positions per episode (frame spacing
     config.dt, frame 0 = time 0 before warm-up); ego_initial_states: optional per-episode [x, y, yaw, v, a].
 
     The state of all episodes lives in arrays (ego, state machine, planner caches, pedestrian frames); a lock step is a
@@ -404,6 +511,20 @@ class BatchedClosedLoop:
         if self._resident and (sample_source is not None or engine is not None or resampler is not None or fused not in (None, True)):
             raise ValueError("resident=True needs the constant-velocity predictor on the library's own engine "
                              "(no sample_source, engine or resampler; the one-call step)")
+        # a sequence of configurations, one per episode: equal ones share a scenario of the ONE handle; more than one
+        # distinct scenario runs through the one-call step or resident=True only
+        self.scenarios, self.slot_scenario, per_episode = None, None, None
+        if isinstance(config, (list, tuple)):
+            if len(config) != len(ped_tracks):
+                raise ValueError(f"{len(config)} configurations for {len(ped_tracks)} episodes: one configuration per episode")
+            distinct, slot, per_episode = merge_configs(config)
+            config = distinct[0]
+            if len(distinct) > 1:
+                if engine is not None or resampler is not None or sample_source is not None or fused not in (None, True):
+                    raise ValueError("the five-call and two-call steps, stand-in engines and sample sources take one "
+                                     "configuration: episodes of different configurations run through the one-call step "
+                                     "(fused=None / True) or resident=True")
+                self.scenarios, self.slot_scenario = distinct, slot
         self.config = config if not isinstance(config, dict) else _Cfg(config)
         c = self.config
         self.dt = float(c.dt)
@@ -424,14 +545,20 @@ class BatchedClosedLoop:
         self._owns_engine = engine is None
         self.engine = engine if engine is not None else BatchPlanner(
             waypoints=(np.asarray(c.reference_waypoints_x, float), np.asarray(c.reference_waypoints_y, float)),
-            device=device, max_speed=c.ego_max_speed, max_accel=c.ego_max_accel, max_curvature=c.ego_max_curvature,
-            max_lat_accel=getattr(c, "ego_max_lat_accel", 3.0), dt=c.dt, d_road_w=c.d_road_w,
-            max_road_width=c.max_road_width, robot_radius=self.ego_radius, obstacle_radius=c.obstacle_radius,
-            min_t=getattr(c, "min_t", 4.0), max_t=getattr(c, "max_t", 5.0), d_t_s=getattr(c, "d_t_s", 5.0 / 3.6),
-            n_s_sample=getattr(c, "n_s_sample", 1), k_j=c.k_j, k_t=c.k_t, k_d=c.k_d, k_s_dot=c.k_s_dot, k_lat=c.k_lat,
-            k_lon=c.k_lon, chance_epsilon=getattr(c, "chance_epsilon", 0.0),
-            collision_margin_inflation=getattr(c, "collision_margin_inflation", 1.0), footprint=self.footprint)
+            device=device, **planner_kwargs_from_config(c, self.footprint))
         self.s_end = float(self.engine.path_coeffs()[0][-1])
+        if self.scenarios is not None:
+            # scenario 0 is the first configuration; the other distinct ones join the same handle.  Per episode from here
+            # on: the goal (its own path's end), the footprint flag, the static points, the state machine's constants
+            self.scenario_footprints = [self.footprint] + [footprint_from_config(k) for k in self.scenarios[1:]]
+            for k, fp_k in zip(self.scenarios[1:], self.scenario_footprints[1:]):
+                self.engine.add_scenario(
+                    waypoints=(np.asarray(k.reference_waypoints_x, float), np.asarray(k.reference_waypoints_y, float)),
+                    **planner_kwargs_from_config(k, fp_k))
+            s_end = np.array([float(self.engine.path_coeffs(i)[0][-1]) for i in range(len(self.scenarios))])
+            self.s_end = s_end[self.slot_scenario]
+            self.scenario_static_points = [expand_static_obstacles(getattr(k, "static_obstacles", None), step=0.5)
+                                           for k in self.scenarios]
         # the step's device work in two calls, prediction resident in HBM (fot_loop_*): the constant-velocity predictor
         # on the library's own engine; a sample source hands its samples over on the host, stand-in engines have no device
         self._device_samples = bool(device_samples)
@@ -449,14 +576,20 @@ class BatchedClosedLoop:
         self._native = self._fused and fused != "two-call" and hasattr(self.engine, "loop_step")
         if self._device_samples and not self._native:
             raise ValueError("device_samples runs through the one-call step only")
-        if self._fused:
+        if self.scenarios is not None and not self._native:
+            raise ValueError("episodes of different configurations need the one-call step: more than one configuration "
+                             "is not supported by this engine")
+        if self.scenarios is not None:
+            for i, pts in enumerate(self.scenario_static_points):
+                self.engine.loop_set_scenario_static(i, pts)
+        elif self._fused:
             self.engine.loop_set_static(self.static_obstacle_points)
         self.sgan_dt = 0.4                                            # integrated_simulator.py:323-327
         self.resampler = resampler if resampler is not None else PredictionResampler(
             self.engine, pred_len=c.pred_len, sgan_dt=self.sgan_dt, sim_dt=c.dt, plan_horizon=getattr(c, "max_t", 5.0))
         n = len(ped_tracks)
         if ego_initial_states is None:
-            ego_initial_states = [c.ego_initial_state] * n
+            ego_initial_states = [c.ego_initial_state] * n if per_episode is None else [k.ego_initial_state for k in per_episode]
         # ---- pedestrians: replayed tracks, every episode on the same clock (replay_source.py:31-118)
         self.peds = [ReplayPedestrians(tr, c.dt) for tr in ped_tracks]
         self.n_frames = np.array([p.n_frames for p in self.peds])
@@ -480,7 +613,7 @@ class BatchedClosedLoop:
         e0 = np.array([np.asarray(v, float)[:5] for v in ego_initial_states], dtype=float).reshape(n, 5)
         self.ego = e0.copy()                                         # x, y, yaw, v, a
         self.jerk = np.array([float(np.asarray(v, float)[5]) if len(v) > 5 else 0.0 for v in ego_initial_states])
-        self.sm = _VectorStateMachine(c, n)
+        self.sm = _VectorStateMachine(c, n) if self.scenarios is None else _VectorStateMachine(self.scenarios, n, self.slot_scenario)
         self.prev_s = np.full(n, np.nan)                             # planner.converter._prev_s (NaN: not set yet)
         self.last_kappa = np.zeros(n)                                # planner._last_kappa
         self.goal_prev_s = np.full(n, np.nan)                        # the simulator's own converter (:873)
@@ -501,24 +634,19 @@ class BatchedClosedLoop:
         self.termination = np.zeros(n, np.int8)                      # index into _TERMINATION
         self.episodes: List[Episode] = [Episode(self, e) for e in range(n)]
         self._warmup()
-        if self._native:
-            sm_, lc = self.sm, _abi.LoopConfig()
-            lc.dt, lc.target_speed, lc.max_accel = float(c.dt), float(sm_.target), float(c.ego_max_accel)
-            dec = getattr(c, "ego_emergency_decel", None)
-            lc.emergency_decel = float("nan") if dec is None else float(dec)
-            lc.clearance_caution, lc.clearance_emergency = float(sm_.clr_caution), float(sm_.clr_emergency)
-            lc.trigger_clearance_caution, lc.trigger_time_headway = float(sm_.trig_c), float(sm_.trig_h)
-            lc.envelope_decel, lc.envelope_standoff = float(sm_.env_decel), float(sm_.env_standoff)
-            lc.caution_accel, lc.caution_speed, lc.caution_speed_mult = float(sm_.c_accel), float(sm_.c_speed), float(sm_.c_speed_mult)
-            lc.emergency_accel, lc.emergency_lat_accel = float(sm_.e_accel), float(sm_.e_lat)
-            lc.max_replan = self.MAX_REPLAN
-            self.engine.loop_begin(lc, self.ego)
+        if self._native and self.scenarios is not None:
+            self.engine.loop_begin_scenarios(
+                [loop_config_from(k, _VectorStateMachine.constants_of(k), self.MAX_REPLAN) for k in self.scenarios],
+                [fp_k is not None for fp_k in self.scenario_footprints], self.slot_scenario, self.ego)
+        elif self._native:
+            self.engine.loop_begin(loop_config_from(c, _VectorStateMachine.constants_of(c), self.MAX_REPLAN), self.ego)
         if self._resident:
             self.engine.loop_set_replay(
                 self.ped_off, self.n_frames, self._ped_all["trajectories"], self._ped_all["velocities"],
                 obs_len=c.obs_len, pred_len=self.resampler.pred_len, rp=self.resampler.params,
                 warmup_frames=int(c.obs_len * self.sgan_dt / c.dt), ego_radius=self.ego_radius, ped_radius=self.ped_radius,
-                use_footprint=self.footprint is not None, s_end=self.s_end, goal_distance=self.GOAL_DISTANCE)
+                use_footprint=self.footprint is not None, s_end=float(np.ravel(self.s_end)[0]),
+                goal_distance=self.GOAL_DISTANCE)      # (a scenario loop: the library takes each slot's own path's end)
 
     def close(self) -> None:
         """Release the libfot handle (streams, workspace) now rather than at garbage collection."""
@@ -841,7 +969,7 @@ class BatchedClosedLoop:
             pred=None, pred_src=pred_src, after=after, stats=self.last_stats[sel].copy(), has_path=path_rec >= 0, keep=keep,
             cost=o["cost"], paths=paths, t_pred=0.0, t_plan=t_plan, sel=sel))
         collided = after["collision"] != 0
-        at_goal = self.s_end - s_now < 2.0
+        at_goal = (self.s_end if self.scenarios is None else self.s_end[sel]) - s_now < 2.0
         self.step_counts[sel] += 1
         self.termination[sel[at_goal & ~collided]] = 2
         self.termination[sel[collided]] = 1

@@ -113,7 +113,15 @@ struct Workspace {
 // FailSafeStateMachine carry from step to step), one slot per episode
 struct LoopEpisodes {
     int n = 0;
-    fot_loop_config cfg = fot_loop_config();
+    fot_loop_config cfg = fot_loop_config();  // of fot_loop_begin; of a scenario loop: the first scenario in use (dt)
+    // fot_loop_begin_scenarios: every slot on a scenario of its own.  cfgs[s] / use_fp[s]: the fail-safe and simulator
+    // constants and the metrics' footprint flag of scenario s (entries of scenarios no slot names are never read).
+    bool scenarios = false;
+    std::vector<fot_loop_config> cfgs;
+    std::vector<int32_t> use_fp;
+    std::vector<int32_t> scen;               // [n] scenario of each slot
+    int max_lvl = 1;                         // most escalation levels of a configuration in use (sizes the record blocks)
+    const fot_loop_config &cfg_of(int e) const { return scenarios ? cfgs[(size_t)scen[(size_t)e]] : cfg; }
     std::vector<double> ego;                 // [n][5] x, y, yaw, v, a
     std::vector<double> prev_s, last_kappa;  // planner.converter._prev_s (NaN: none yet), planner._last_kappa
     std::vector<double> goal_prev_s;         // the simulator's own converter (integrated_simulator.py:873)
@@ -154,6 +162,15 @@ struct LoopState {
     DevBuf dDyn, dStatic;                    // the prediction tensor; the static points, one copy per request
     std::vector<double> static_xy;           // host copy of the static points
     int static_tiles = 0;                    // copies resident in dStatic
+    // a scenario loop: every scenario's points once in HBM (dScenStatic, scenario s at point scen_static_off[s]); a
+    // step's per-request blocks are gathered from them on the device (k_static_gather) into dGather
+    std::vector<std::vector<double>> scen_static;    // [scenario] host copies (fot_loop_set_scenario_static)
+    std::vector<int32_t> scen_static_off;    // [scenarios + 1] as resident in dScenStatic
+    bool scen_static_dirty = true;
+    DevBuf dScenStatic, dGather, dSafScen;   // ... ; SafetyScen[scenarios]
+    PinnedBuf hGather;                       // StaticGather[requests] of the plan call being enqueued
+    std::vector<int32_t> frame_scen;         // scenario of each episode of the frame (empty: all on scenario 0)
+    const int32_t *p_scen = nullptr;         // the same where k_safety reads it (beside p_off), or nullptr
     std::vector<int32_t> ped_off;            // of the frame
     std::vector<int64_t> blk_off;            // first point of each episode's block in the tensor
     std::vector<int32_t> t_len;              // samples per track of each episode's block
@@ -169,6 +186,7 @@ struct LoopState {
     {
         hFrame.release(); hObserve.release(); hOut.release(); hRec.release();
         dDyn.release(); dStatic.release(); replay.release();
+        dScenStatic.release(); dGather.release(); dSafScen.release(); hGather.release();
     }
 };
 
@@ -903,8 +921,17 @@ int fot_get_path_coeffs(const fot_handle *h, int32_t *n_out, double *s,
                         double *ax, double *bx, double *cx, double *dx,
                         double *ay, double *by, double *cy, double *dy)
 {
-    if (!h || !h->sc[0].has_path) return FOT_ERR_NO_PATH_SET;
-    const HostSpline &sp = h->sc[0].spline;
+    return fot_get_scenario_path_coeffs(h, 0, n_out, s, ax, bx, cx, dx, ay, by, cy, dy);
+}
+
+int fot_get_scenario_path_coeffs(const fot_handle *h, int32_t id, int32_t *n_out, double *s,
+                                 double *ax, double *bx, double *cx, double *dx,
+                                 double *ay, double *by, double *cy, double *dy)
+{
+    if (!h) return FOT_ERR_NO_PATH_SET;
+    if (id < 0 || id >= (int)h->sc.size()) return FOT_ERR_INVALID;
+    if (!h->sc[(size_t)id].has_path) return FOT_ERR_NO_PATH_SET;
+    const HostSpline &sp = h->sc[(size_t)id].spline;
     const int n = sp.n;
     if (n_out) *n_out = n;
     auto cp = [](double *dst, const std::vector<double> &src, int cnt) {
@@ -1128,20 +1155,62 @@ int fot_safety_metrics_batch(fot_handle *h, int32_t n, const double *ego, const 
     return FOT_OK;
 }
 
-int fot_loop_set_static(fot_handle *h, int32_t n_points, const double *xy)
+int fot_loop_set_scenario_static(fot_handle *h, int32_t id, int32_t n_points, const double *xy)
 {
     if (!h) return FOT_ERR_INVALID;
+    if (id < 0 || id >= (int)h->sc.size()) return fail(h, FOT_ERR_INVALID, "unknown scenario id");
     if (n_points < 0 || (n_points > 0 && !xy)) return fail(h, FOT_ERR_INVALID, "static points");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));                 // nothing may still be reading the old copies
-    h->loop.static_xy.assign(xy, xy + 2 * (size_t)n_points);
-    h->loop.static_tiles = 0;
+    LoopState &L = h->loop;
+    if (L.scen_static.size() < h->sc.size()) L.scen_static.resize(h->sc.size());
+    L.scen_static[(size_t)id].assign(xy, xy + 2 * (size_t)n_points);
+    L.scen_static_dirty = true;                                  // (uploaded by the next scenario loop's step / replay)
+    if (id == 0) {                                               // scenario 0 is what a fot_loop_begin loop sees
+        L.static_xy = L.scen_static[0];
+        L.static_tiles = 0;
+    }
     return FOT_OK;
+}
+
+int fot_loop_set_static(fot_handle *h, int32_t n_points, const double *xy)
+{
+    return fot_loop_set_scenario_static(h, 0, n_points, xy);
 }
 
 }  // extern "C"
 
 namespace {
+
+// A scenario loop's static points: every scenario's set once in HBM (rebuilt after fot_loop_set_scenario_static), and
+// room for the per-request blocks of n_req requests.  Synchronises only when something has to be uploaded or to grow.
+int ensure_scen_static(fot_handle *h, int n_req, hipStream_t st)
+{
+    LoopState &L = h->loop;
+    const size_t n_sc = h->sc.size();
+    if (L.scen_static_dirty || L.scen_static_off.size() != n_sc + 1) {
+        L.scen_static.resize(n_sc);
+        std::vector<int32_t> off(n_sc + 1, 0);
+        for (size_t s = 0; s < n_sc; ++s) off[s + 1] = off[s] + (int32_t)(L.scen_static[s].size() / 2);
+        std::vector<double> all;
+        all.reserve(2 * (size_t)off[n_sc]);
+        for (size_t s = 0; s < n_sc; ++s) all.insert(all.end(), L.scen_static[s].begin(), L.scen_static[s].end());
+        HIP_TRY(h, hipStreamSynchronize(st));
+        HIP_TRY(h, L.dScenStatic.ensure(sizeof(double) * std::max<size_t>(all.size(), 2)));
+        if (!all.empty()) HIP_TRY(h, hipMemcpy(L.dScenStatic.p, all.data(), sizeof(double) * all.size(), hipMemcpyHostToDevice));
+        L.scen_static_off = off;
+        L.scen_static_dirty = false;
+    }
+    int32_t most = 0;
+    for (size_t s = 0; s + 1 < L.scen_static_off.size(); ++s) most = std::max(most, L.scen_static_off[s + 1] - L.scen_static_off[s]);
+    const size_t need = sizeof(double) * 2 * (size_t)most * (size_t)std::max(n_req, 1);
+    if (need > L.dGather.cap || sizeof(StaticGather) * (size_t)std::max(n_req, 1) > L.hGather.cap) {
+        HIP_TRY(h, hipStreamSynchronize(st));                    // (a block that grows moves)
+        HIP_TRY(h, L.dGather.ensure(std::max<size_t>(need, 16)));
+        HIP_TRY(h, L.hGather.ensure(sizeof(StaticGather) * (size_t)std::max(n_req, 1)));
+    }
+    return FOT_OK;
+}
 
 // The requests of a loop step as one plan call against the step's tensor (LoopState: pedestrian counts, block offsets and
 // lengths of the frame's episodes), records to rec_out: enqueued on st, not waited for.
@@ -1150,7 +1219,18 @@ int loop_enqueue_requests(fot_handle *h, int32_t n_req, const fot_loop_request *
 {
     LoopState &L = h->loop;
     const int n_ep = (int)L.ped_off.size() - 1;
-    const int n_static = (int)(L.static_xy.size() / 2);
+    const bool by_scen = !L.frame_scen.empty();                  // a scenario loop: request j is on its episode's scenario
+    const int n_static = by_scen ? 0 : (int)(L.static_xy.size() / 2);
+    std::vector<int32_t> scen;
+    if (by_scen) {
+        scen.resize((size_t)n_req);
+        for (int j = 0; j < n_req; ++j) {
+            const int e = req[j].episode;
+            if (e < 0 || e >= n_ep || e >= (int)L.frame_scen.size()) return fail(h, FOT_ERR_INVALID, "request: episode out of range");
+            scen[(size_t)j] = L.frame_scen[(size_t)e];
+        }
+        int r = ensure_scen_static(h, n_req, st); if (r != FOT_OK) return r;
+    }
     if (n_static > 0 && L.static_tiles < n_req) {              // (grows a few times in the life of a loop)
         const int tiles = std::max(n_req, 2 * L.static_tiles);
         std::vector<double> rep((size_t)tiles * L.static_xy.size());
@@ -1171,29 +1251,46 @@ int loop_enqueue_requests(fot_handle *h, int32_t n_req, const fot_loop_request *
         const int e = req[j].episode;
         if (e < 0 || e >= n_ep) return fail(h, FOT_ERR_INVALID, "request: episode out of range");
         ego[j] = req[j].ego; ov[j] = req[j].overrides; tgt[j] = req[j].target_speed; stop[j] = req[j].max_stop_distance;
-        s_off[j] = j * n_static;
+        if (!by_scen) s_off[j] = j * n_static;
+        if (by_scen) {
+            // its scenario's points: gathered on the device into [s_off[j], s_off[j + 1]) of dGather, the layout k_cull reads
+            const int32_t sc = scen[(size_t)j], src = L.scen_static_off[(size_t)sc], cnt = L.scen_static_off[(size_t)sc + 1] - src;
+            StaticGather &g = ((StaticGather *)L.hGather.p)[j];
+            g.src = src; g.dst = s_off[j]; g.n = cnt; g._pad = 0;
+            s_off[j + 1] = s_off[j] + cnt;
+        }
         const int P_e = L.ped_off[e + 1] - L.ped_off[e];
         d_off[j] = L.blk_off[e];
         dims[4 * j] = P_e > 0 ? (L.dist_S > 0 ? FOT_DYN_DISTRIBUTION : FOT_DYN_SINGLE) : FOT_DYN_NONE;
         dims[4 * j + 1] = L.dist_S > 0 ? L.dist_S : 1; dims[4 * j + 2] = P_e; dims[4 * j + 3] = L.t_len[e];
         any_dyn = any_dyn || P_e > 0;
     }
-    s_off[n_req] = n_req * n_static;
+    if (!by_scen) s_off[n_req] = n_req * n_static;
     fot_batch b = fot_batch();
     b.n_inst = n_req; b.obstacle_dtype = FOT_F64;
     b.ego = ego.data(); b.target_speed = tgt.data(); b.overrides = ov.data(); b.max_stop_distance = stop.data();
     if (n_static > 0) { b.static_xy = L.dStatic.p; b.static_off = s_off.data(); }
+    if (by_scen && s_off[n_req] > 0) {
+        if (sizeof(double) * 2 * (size_t)s_off[n_req] > L.dGather.cap) return fail(h, FOT_ERR_INVALID, "internal: static block too small");
+        { int r = check_scenarios(h, b, scen.data()); if (r != FOT_OK) return r; }   // (a refused call enqueues nothing)
+        { int r = order_begin(h, st); if (r != FOT_OK) return r; }
+        LAUNCH_TRY(h, launch_static_gather((const StaticGather *)L.hGather.p, n_req, L.dScenStatic.as<double>(),
+                                           L.dGather.as<double>(), st));
+        b.static_xy = L.dGather.p; b.static_off = s_off.data();
+    }
     if (any_dyn) { b.dyn_xy = L.dyn_ptr; b.dyn_off = d_off.data(); b.dyn_dims = dims.data(); }
-    return enqueue_plan(h, b, nullptr, b.static_xy, b.dyn_xy, rec_out, st, sync_caller);
+    return enqueue_plan(h, b, by_scen ? scen.data() : nullptr, b.static_xy, b.dyn_xy, rec_out, st, sync_caller);
 }
 
 // fot_loop_plan; rec_first: the request's records start at record rec_first of the handle's pinned block (the escalation
 // levels of a step land behind its level-0 records, which stay where they are)
+// ep_scen: the scenario of each episode of the frame (a scenario loop's step), or nullptr: all on scenario 0
 int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, const fot_loop_request *req,
-                   fot_safety *safety_out, const fot_result **records, int32_t rec_first)
+                   fot_safety *safety_out, const fot_result **records, int32_t rec_first, const int32_t *ep_scen = nullptr)
 {
     if (!h) return FOT_ERR_INVALID;
-    if (!h->sc[0].has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
+    if (!ep_scen && (frame || h->loop.frame_scen.empty()) && !h->sc[0].has_path)
+        return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
     if (n_req < 0 || (n_req > 0 && (!req || !records))) return fail(h, FOT_ERR_INVALID, "requests");
     LoopState &L = h->loop;
     if (!frame && !L.have_frame) return fail(h, FOT_ERR_INVALID, "no frame: the first fot_loop_plan of a step carries one");
@@ -1229,7 +1326,7 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
         const size_t off_b = align256(sizeof(int32_t) * ((size_t)n + 1));
         const size_t ped_b = align256(sizeof(double) * 2 * std::max<size_t>(n_ped, 1));
         const size_t blk_b = align256(sizeof(int64_t) * ((size_t)n + 1)), pe_b = align256(sizeof(int32_t) * std::max<size_t>(n_ped, 1));
-        HIP_TRY(h, L.hFrame.ensure(ego_b + off_b + 4 * ped_b + blk_b + pe_b));
+        HIP_TRY(h, L.hFrame.ensure(ego_b + off_b + 4 * ped_b + blk_b + pe_b + (ep_scen ? off_b : 0)));
         char *p = (char *)L.hFrame.p;
         double *p_ego = (double *)p;
         int32_t *p_off = (int32_t *)(p + ego_b);
@@ -1252,6 +1349,12 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
             L.blk_off[e + 1] = L.blk_off[e] + (int64_t)(dist ? frame->dist_S : 1) * (L.ped_off[e + 1] - L.ped_off[e]) * L.t_len[e];
         }
         L.p_off = p_off; L.p_pos = p_pos; L.p_vel = p_vel;
+        L.p_scen = nullptr; L.frame_scen.clear();
+        if (ep_scen && n > 0) {                                    // the episodes' scenarios, behind the other tables
+            int32_t *p_sc = (int32_t *)(p + ego_b + off_b + 4 * ped_b + blk_b + pe_b);
+            std::memcpy(p_sc, ep_scen, sizeof(int32_t) * (size_t)n);
+            L.p_scen = p_sc; L.frame_scen.assign(ep_scen, ep_scen + n);
+        }
         L.ego_radius = frame->ego_radius; L.ped_radius = frame->ped_radius; L.use_footprint = frame->use_footprint;
         L.dyn_ptr = p_pos;                                         // not ready: the current positions, read in place
         if (dist && n_ped > 0) {
@@ -1284,7 +1387,8 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
         if (frame->ego && safety_out && n > 0) {
             HIP_TRY(h, L.hOut.ensure(sizeof(fot_safety) * (size_t)n));
             LAUNCH_TRY(h, launch_safety(h->dP.as<DevParams>(), n, p_ego, p_off, p_pos, p_vel, L.ego_radius, L.ped_radius,
-                                        h->sc[0].params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st));
+                                        h->sc[0].params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st,
+                                        L.p_scen, L.dSafScen.as<SafetyScen>()));
             metrics = true;
         }
         L.have_frame = true;
@@ -1323,11 +1427,18 @@ int fot_loop_plan(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, con
     return loop_plan_impl(h, frame, n_req, req, safety_out, records, 0);
 }
 
-int fot_loop_observe_begin(fot_handle *h, int32_t n, const double *ego5, const double *prev_s)
+}  // extern "C"
+
+namespace {
+
+// fot_loop_observe_begin; a scenario loop's frame (LoopState::frame_scen): ego i is measured with, and projected on the
+// path of, the scenario of episode i
+int observe_begin_impl(fot_handle *h, int32_t n, const double *ego5, const double *prev_s)
 {
     if (!h) return FOT_ERR_INVALID;
-    if (!h->sc[0].has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
     LoopState &L = h->loop;
+    const bool by_scen = !L.frame_scen.empty();
+    if (!by_scen && !h->sc[0].has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
     L.observe_n = -1;
     if (!L.have_frame) return fail(h, FOT_ERR_INVALID, "no frame: fot_loop_plan of this step comes first");
     if (n != (int)L.ped_off.size() - 1) return fail(h, FOT_ERR_INVALID, "one ego per episode of the frame");
@@ -1350,16 +1461,36 @@ int fot_loop_observe_begin(fot_handle *h, int32_t n, const double *ego5, const d
         const bool cached = prev_s && !std::isnan(prev_s[i]);
         d.ego.has_prev_s = cached ? 1 : 0;
         d.ego.prev_s = cached ? prev_s[i] : 0.0;
+        d.scen = by_scen ? L.frame_scen[(size_t)i] : 0;
         p_desc[i] = d;
     }
     LAUNCH_TRY(h, launch_safety(h->dP.as<DevParams>(), n, p_ego, L.p_off, L.p_pos, L.p_vel, L.ego_radius, L.ped_radius,
-                                h->sc[0].params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st));
+                                h->sc[0].params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st,
+                                L.p_scen, L.dSafScen.as<SafetyScen>()));
     InstState *p_state = (InstState *)((char *)L.hOut.p + saf_b);
-    LAUNCH_TRY(h, launch_frenet_state(h->dP.as<DevParams>(), PathSet::single(spline_view(h, 0)), p_desc, p_state, n, MetaImport(), NanScan(),
-                                      nullptr, st));
+    PathSet ps = PathSet::single(spline_view(h, 0));
+    if (by_scen) {                                               // the handle's path table, as a mixed plan batch passes it
+        ps = PathSet();
+        ps.table = h->dSplineTab.as<SplineView>();
+        ps.mixed = 1;
+        std::vector<uint8_t> used(h->sc.size(), 0);
+        for (int i = 0; i < n; ++i) used[(size_t)L.frame_scen[(size_t)i]] = 1;
+        for (size_t sc = 0; sc < used.size(); ++sc) if (used[sc]) ps.knots[ps.n_knots++] = h->sc[sc].spline.n;
+    }
+    LAUNCH_TRY(h, launch_frenet_state(h->dP.as<DevParams>(), ps, p_desc, p_state, n, MetaImport(), NanScan(), nullptr, st));
     { int r = order_end(h, st); if (r != FOT_OK) return r; }
     L.observe_n = n;
     return FOT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fot_loop_observe_begin(fot_handle *h, int32_t n, const double *ego5, const double *prev_s)
+{
+    // (the two-call form stays on scenario 0: what fot_loop_plan's frame leaves behind)
+    return observe_begin_impl(h, n, ego5, prev_s);
 }
 
 int fot_loop_observe_end(fot_handle *h, fot_safety *safety_out, double *new_prev_s)
@@ -1417,7 +1548,7 @@ void sm_config(const fot_loop_config &c, int state, double clear_ahead, double *
 // FailSafeStateMachine.update (state_machine.py:116-179) of episode e: observe the metrics, then the transition
 void sm_update(LoopEpisodes &E, int e, bool found, double clearance, double clearance_ahead, double speed)
 {
-    const fot_loop_config &c = E.cfg;
+    const fot_loop_config &c = E.cfg_of(e);
     E.clear[e] = clearance; E.clear_ahead[e] = clearance_ahead;
     const int st = E.state[e], fl = E.fails[e];
     const double trigger = c.trigger_clearance_caution + c.trigger_time_headway * std::fmax(speed, 0.0);
@@ -1453,16 +1584,15 @@ struct StepWork {
 // against episode i of the frame
 void step_level0(const LoopEpisodes &E, const int32_t *episode, int n, StepWork &W)
 {
-    const fot_loop_config &c = E.cfg;
-    const int max_lvl = loop_max_levels(c);
     W.st0.assign((size_t)n, 0); W.n_lvl.assign((size_t)n, 0);
     W.speed.assign((size_t)n, 0.0); W.ego4.assign(4 * (size_t)n, 0.0);
     W.req.assign((size_t)n, fot_loop_request());
     W.m.assign((size_t)n, fot_safety());
     for (int i = 0; i < n; ++i) {
         const int e = episode[i];
+        const fot_loop_config &c = E.cfg_of(e);                   // (the episode's own scenario's constants)
         W.st0[i] = E.state[e];
-        W.n_lvl[i] = std::min(3 - W.st0[i], max_lvl);
+        W.n_lvl[i] = std::min(3 - W.st0[i], loop_max_levels(c));
         const double *g = &E.ego[5 * (size_t)e];
         W.speed[i] = g[3];
         for (int k = 0; k < 4; ++k) W.ego4[4 * (size_t)i + k] = g[k];
@@ -1483,12 +1613,12 @@ void step_level0(const LoopEpisodes &E, const int32_t *episode, int n, StepWork 
 template <class Rec>
 void step_escalations(const LoopEpisodes &E, const int32_t *episode, int n, const Rec *rec, StepWork &W)
 {
-    const fot_loop_config &c = E.cfg;
     W.next_rec.assign((size_t)n, -1);
     W.more.clear();
     for (int i = 0; i < n; ++i) {
         if (rec[i].status == FOT_PLAN_OK || W.n_lvl[i] <= 1) continue;
         const int e = episode[i];
+        const fot_loop_config &c = E.cfg_of(e);
         W.next_rec[i] = n + (int)W.more.size();
         const double nps0 = rec[i].new_prev_s, p = std::isnan(nps0) ? E.prev_s[e] : nps0;
         for (int lvl = 1; lvl < W.n_lvl[i]; ++lvl) {
@@ -1507,7 +1637,6 @@ void step_escalations(const LoopEpisodes &E, const int32_t *episode, int n, cons
 template <class Rec>
 void step_resolve(LoopEpisodes &E, const int32_t *episode, int n, const Rec *rec, StepWork &W)
 {
-    const fot_loop_config &c = E.cfg;
     W.path_rec.assign((size_t)n, -1); W.keep.assign((size_t)n, 0);
     W.jerk.assign((size_t)n, 0.0); W.cost.assign((size_t)n, 0.0); W.ego5n.assign(5 * (size_t)n, 0.0);
     auto adopt = [&](int i, int r) {                             // planner state after a plan() call
@@ -1518,6 +1647,7 @@ void step_resolve(LoopEpisodes &E, const int32_t *episode, int n, const Rec *rec
     };
     for (int i = 0; i < n; ++i) {
         const int e = episode[i];
+        const fot_loop_config &c = E.cfg_of(e);
         int cur = i, retries = 0;
         adopt(i, cur);
         bool found = rec[cur].status == FOT_PLAN_OK;
@@ -1535,6 +1665,7 @@ void step_resolve(LoopEpisodes &E, const int32_t *episode, int n, const Rec *rec
     }
     for (int i = 0; i < n; ++i) {
         const int e = episode[i];
+        const fot_loop_config &c = E.cfg_of(e);
         double *g = &E.ego[5 * (size_t)e];
         const double old_a = g[4];
         const int r = W.path_rec[i];
@@ -1573,11 +1704,69 @@ int fot_loop_begin(fot_handle *h, int32_t n_episodes, const fot_loop_config *cfg
     LoopEpisodes &E = h->loop.ep;
     const size_t n = (size_t)n_episodes;
     E.n = n_episodes; E.cfg = *cfg;
+    E.scenarios = false; E.cfgs.clear(); E.use_fp.clear(); E.scen.clear();
+    E.max_lvl = loop_max_levels(*cfg);
+    h->loop.frame_scen.clear(); h->loop.p_scen = nullptr;
     E.ego.assign(ego5, ego5 + 5 * n);
     E.prev_s.assign(n, NAN); E.last_kappa.assign(n, 0.0); E.goal_prev_s.assign(n, NAN);
     E.last_clearance.assign(n, INFINITY); E.clear.assign(n, INFINITY); E.clear_ahead.assign(n, INFINITY);
     E.state.assign(n, 0); E.fails.assign(n, 0); E.stats.assign(8 * n, -1);
     h->loop.replay.set = false;                                  // (a new loop: the handle's clock, if it had one, is gone)
+    return FOT_OK;
+}
+
+int fot_loop_begin_scenarios(fot_handle *h, int32_t n_episodes, int32_t n_cfg, const fot_loop_config *cfg,
+                             const int32_t *use_footprint, const int32_t *slot_scenario, const double *ego5)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (n_episodes < 0 || n_cfg < 1 || !cfg || (n_episodes > 0 && (!ego5 || !slot_scenario)))
+        return fail(h, FOT_ERR_INVALID, "fot_loop_begin_scenarios: arguments");
+    // --- everything is checked before anything changes
+    int first = -1;
+    for (int e = 0; e < n_episodes; ++e) {
+        const int sc = slot_scenario[e];
+        if (sc < 0 || sc >= (int)h->sc.size()) return fail(h, FOT_ERR_INVALID, "fot_loop_begin_scenarios: unknown scenario id");
+        if (sc >= n_cfg) return fail(h, FOT_ERR_INVALID, "fot_loop_begin_scenarios: n_cfg is smaller than a slot's scenario id");
+        if (!h->sc[(size_t)sc].has_path)
+            return fail(h, FOT_ERR_NO_PATH_SET, "fot_loop_begin_scenarios: a slot's scenario has no path (fot_set_scenario_path_*)");
+        const fot_loop_config &c = cfg[sc];
+        if (!(c.dt > 0.0) || c.max_replan < 0 || c.max_replan > 8) return fail(h, FOT_ERR_INVALID, "fot_loop_begin_scenarios: dt / max_replan");
+        if (first < 0) first = sc;
+        if (c.dt != cfg[first].dt) return fail(h, FOT_ERR_INVALID, "fot_loop_begin_scenarios: the scenarios of a loop share dt");
+    }
+    if (first < 0) {                                             // no slot: nothing is in use but the first configuration
+        first = 0;
+        if (!(cfg[0].dt > 0.0) || cfg[0].max_replan < 0 || cfg[0].max_replan > 8) return fail(h, FOT_ERR_INVALID, "fot_loop_begin_scenarios: dt / max_replan");
+    }
+    const size_t n_sc = h->sc.size();
+    std::vector<SafetyScen> tab(n_sc);
+    for (size_t s = 0; s < n_sc; ++s) {
+        tab[s].footprint_radius = h->sc[s].params.footprint_radius;
+        tab[s].use_fp = ((int)s < n_cfg && use_footprint && use_footprint[s]) ? 1 : 0;
+        tab[s]._pad = 0;
+    }
+    LoopState &L = h->loop;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                 // nothing may still be reading the old table
+    HIP_TRY(h, L.dSafScen.ensure(sizeof(SafetyScen) * n_sc));
+    HIP_TRY(h, hipMemcpy(L.dSafScen.p, tab.data(), sizeof(SafetyScen) * n_sc, hipMemcpyHostToDevice));
+    // --- accepted
+    LoopEpisodes &E = L.ep;
+    const size_t n = (size_t)n_episodes;
+    E.n = n_episodes; E.cfg = cfg[first];
+    E.scenarios = true;
+    E.cfgs.assign(cfg, cfg + n_cfg);
+    E.use_fp.assign((size_t)n_cfg, 0);
+    for (int s = 0; s < n_cfg; ++s) E.use_fp[(size_t)s] = use_footprint && use_footprint[s] ? 1 : 0;
+    E.scen.assign(slot_scenario, slot_scenario + n);
+    E.max_lvl = loop_max_levels(cfg[first]);
+    for (size_t e = 0; e < n; ++e) E.max_lvl = std::max(E.max_lvl, loop_max_levels(cfg[E.scen[e]]));
+    L.frame_scen.clear(); L.p_scen = nullptr; L.have_frame = false;
+    E.ego.assign(ego5, ego5 + 5 * n);
+    E.prev_s.assign(n, NAN); E.last_kappa.assign(n, 0.0); E.goal_prev_s.assign(n, NAN);
+    E.last_clearance.assign(n, INFINITY); E.clear.assign(n, INFINITY); E.clear_ahead.assign(n, INFINITY);
+    E.state.assign(n, 0); E.fails.assign(n, 0); E.stats.assign(8 * n, -1);
+    L.replay.set = false;
     return FOT_OK;
 }
 
@@ -1597,16 +1786,26 @@ int fot_loop_step(fot_handle *h, const fot_loop_frame *frame, const int32_t *epi
         if (episode[i] < 0 || episode[i] >= E.n || seen[(size_t)episode[i]]) return fail(h, FOT_ERR_INVALID, "fot_loop_step: episode slots must be distinct and below fot_loop_begin's count");
         seen[(size_t)episode[i]] = 1;
     }
+    std::vector<int32_t> ep_scen;
+    if (E.scenarios) {
+        if (frame->dist_raw) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_step: a scenario loop takes the constant-velocity predictor only (no dist_raw)");
+        ep_scen.resize((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            ep_scen[(size_t)i] = E.scen[(size_t)episode[i]];
+            if (ep_scen[(size_t)i] >= (int)h->sc.size() || !h->sc[(size_t)ep_scen[(size_t)i]].has_path)
+                return fail(h, FOT_ERR_NO_PATH_SET, "fot_loop_step: a slot's scenario has no path");
+        }
+    }
     StepWork W;
     step_level0(E, episode, n, W);
     HIP_TRY(h, hipSetDevice(h->device));
     if (L.observe_n > 0) { HIP_TRY(h, hipStreamSynchronize(h->stream)); L.observe_n = -1; }
     // (all records of the step in one pinned block that must not move between the two plan calls)
-    HIP_TRY(h, L.hRec.ensure(sizeof(fot_result) * (size_t)n * (size_t)loop_max_levels(E.cfg)));
+    HIP_TRY(h, L.hRec.ensure(sizeof(fot_result) * (size_t)n * (size_t)E.max_lvl));
     fot_loop_frame fr = *frame;
     fr.ego = W.ego4.data();
     const fot_result *rec = nullptr;
-    { int rc = loop_plan_impl(h, &fr, n, W.req.data(), W.m.data(), &rec, 0); if (rc != FOT_OK) return rc; }
+    { int rc = loop_plan_impl(h, &fr, n, W.req.data(), W.m.data(), &rec, 0, E.scenarios ? ep_scen.data() : nullptr); if (rc != FOT_OK) return rc; }
     rec = (const fot_result *)L.hRec.p;
     for (int i = 0; i < n; ++i) E.last_clearance[episode[i]] = W.m[i].clearance_ahead;
     step_escalations(E, episode, n, rec, W);
@@ -1684,8 +1883,8 @@ struct FrameLayout {
         : ped_b(align256(16 * std::max<size_t>(rows, 1))), ep_b(align256(4 * std::max<size_t>(rows, 1))),
           off_b(align256(4 * (n + 1))), blk_b(align256(8 * (n + 1))), pre_b(align256(4 * std::max<size_t>(n, 1))),
           ego_b(align256(32 * std::max<size_t>(n, 1))) {}
-    size_t dev_bytes() const { return 4 * ped_b + ep_b + off_b + blk_b + pre_b + ego_b; }
-    size_t stage_bytes() const { return pre_b + off_b + blk_b + pre_b + ego_b; }
+    size_t dev_bytes() const { return 4 * ped_b + ep_b + off_b + blk_b + pre_b + ego_b + pre_b; }
+    size_t stage_bytes() const { return pre_b + off_b + blk_b + pre_b + ego_b + pre_b; }
     FrameDev dev(void *base) const
     {
         char *p = (char *)base;
@@ -1696,7 +1895,8 @@ struct FrameLayout {
         f.ped0 = (int32_t *)p; p += off_b;
         f.blk = (int64_t *)p; p += blk_b;
         f.prepend = (int32_t *)p; p += pre_b;
-        f.ego = (double *)p;
+        f.ego = (double *)p; p += ego_b;
+        f.scen = (int32_t *)p;
         return f;
     }
 };
@@ -1727,8 +1927,11 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     int64_t *s_blk = (int64_t *)(stg + FL.pre_b + FL.off_b);
     int32_t *s_pre = (int32_t *)(stg + FL.pre_b + FL.off_b + FL.blk_b);
     double *s_ego = (double *)(stg + 2 * FL.pre_b + FL.off_b + FL.blk_b);
+    int32_t *s_scen = (int32_t *)(stg + 2 * FL.pre_b + FL.off_b + FL.blk_b + FL.ego_b);
     StepWork W;
     step_level0(E, sel.data(), n, W);
+    L.frame_scen.clear();
+    if (E.scenarios) L.frame_scen.resize((size_t)n);
     L.ped_off.assign((size_t)n + 1, 0); L.blk_off.assign((size_t)n + 1, 0); L.t_len.assign((size_t)n, 1);
     L.dist_S = 0;
     const size_t row_doubles = 2 * (size_t)R.n_cols;
@@ -1745,6 +1948,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         L.ped_off[i + 1] = L.ped_off[i] + P_e;
         L.blk_off[i + 1] = L.blk_off[i] + (int64_t)P_e * L.t_len[i];
         s_slot[i] = e; s_ped0[i] = L.ped_off[i]; s_blk[i] = L.blk_off[i]; s_pre[i] = pre;
+        if (E.scenarios) s_scen[i] = L.frame_scen[(size_t)i] = E.scen[(size_t)e];
         for (int q = 0; q < 4; ++q) s_ego[4 * (size_t)i + q] = W.ego4[4 * (size_t)i + q];
     }
     s_ped0[n] = L.ped_off[n]; s_blk[n] = L.blk_off[n];
@@ -1755,9 +1959,11 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     rv.n_cols = R.n_cols;
     FrameStage fs;
     fs.slot = s_slot; fs.ped0 = s_ped0; fs.blk = s_blk; fs.prepend = s_pre; fs.ego = s_ego;
+    fs.scen = E.scenarios ? s_scen : nullptr;
     const FrameDev fd = FL.dev(R.dFrame.p);
     LAUNCH_TRY(h, launch_loop_frame(rv, fs, fd, n, f_cur, ready ? f_last : -1, ready ? f_prev : -1, st));
     L.p_off = fd.ped0; L.p_pos = fd.pos; L.p_vel = fd.vel;
+    L.p_scen = E.scenarios ? fd.scen : nullptr;
     L.ego_radius = C.ego_radius; L.ped_radius = C.ped_radius; L.use_footprint = C.use_footprint;
     L.dyn_ptr = fd.pos;                                          // not ready: the current positions, T = 1
     if (ready && rows > 0) {
@@ -1765,7 +1971,8 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         LAUNCH_TRY(h, launch_predict_cv_frame(C.rp.sgan_dt, C.rp.sim_dt, stale, rows, R.n_dense, fd, L.dDyn.as<double>(), st));
     }
     LAUNCH_TRY(h, launch_safety(h->dP.as<DevParams>(), n, fd.ego, fd.ped0, fd.pos, fd.vel, L.ego_radius, L.ped_radius,
-                                h->sc[0].params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st));
+                                h->sc[0].params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st,
+                                L.p_scen, L.dSafScen.as<SafetyScen>()));
     L.have_frame = true; L.observe_n = -1;
     // --- 3. level 0 of every episode; the records stay in HBM, the host reads their digests
     fot_result *d_rec = R.dRec.as<fot_result>();
@@ -1818,7 +2025,9 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         if (out->after) out->after[o] = after[i];
         if (out->s_now) out->s_now[o] = s_now;
         R.steps[e] += 1;
-        R.termination[e] = replay_termination(after[i].collision, C.s_end, s_now, C.goal_distance);
+        // the goal of a scenario loop's slot: the end of its own scenario's path (its spline's last knot)
+        const double s_end = E.scenarios ? h->sc[(size_t)E.scen[(size_t)e]].spline.s.back() : C.s_end;
+        R.termination[e] = replay_termination(after[i].collision, s_end, s_now, C.goal_distance);
         if (R.termination[e] != 0) R.alive[e] = 0;
     }
     return FOT_OK;
@@ -1831,10 +2040,13 @@ extern "C" {
 int fot_loop_set_replay(fot_handle *h, const fot_loop_replay *rp)
 {
     if (!h) return FOT_ERR_INVALID;
-    if (!h->sc[0].has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
     if (!rp) return fail(h, FOT_ERR_INVALID, "fot_loop_set_replay: replay is NULL");
     LoopState &L = h->loop;
     const LoopEpisodes &E = L.ep;
+    if (!E.scenarios && !h->sc[0].has_path) return fail(h, FOT_ERR_NO_PATH_SET, "fot_set_path_* has not been called");
+    for (int e = 0; E.scenarios && e < E.n; ++e)
+        if (E.scen[(size_t)e] >= (int)h->sc.size() || !h->sc[(size_t)E.scen[(size_t)e]].has_path)
+            return fail(h, FOT_ERR_NO_PATH_SET, "fot_loop_set_replay: a slot's scenario has no path");
     if (!(E.cfg.dt > 0.0)) return fail(h, FOT_ERR_INVALID, "fot_loop_set_replay: fot_loop_begin comes first");
     const int n = rp->n_slots;
     if (n != E.n) return fail(h, FOT_ERR_INVALID, "fot_loop_set_replay: n_slots differs from fot_loop_begin's episode count");
@@ -1860,7 +2072,7 @@ int fot_loop_set_replay(fot_handle *h, const fot_loop_replay *rp)
     LoopReplay &R = L.replay;
     R.set = false;
     const size_t rec_doubles = (size_t)rp->n_frames_max * cols * 2;
-    const int max_lvl = loop_max_levels(E.cfg);
+    const int max_lvl = E.max_lvl;
     const size_t n_rec = (size_t)std::max(n, 1) * (size_t)max_lvl;
     const FrameLayout FL((size_t)n, cols);
     HIP_TRY(h, R.dPos.ensure(sizeof(double) * std::max<size_t>(rec_doubles, 2)));
@@ -1875,6 +2087,7 @@ int fot_loop_set_replay(fot_handle *h, const fot_loop_replay *rp)
     HIP_TRY(h, R.hWord.ensure(sizeof(int32_t) * 32));
     HIP_TRY(h, L.hOut.ensure(align256(sizeof(fot_safety) * (size_t)std::max(n, 1)) + sizeof(InstState) * (size_t)std::max(n, 1)));
     HIP_TRY(h, L.hObserve.ensure(align256(sizeof(double) * 4 * (size_t)std::max(n, 1)) + align256(sizeof(InstDesc) * (size_t)std::max(n, 1))));
+    if (E.scenarios) { int r = ensure_scen_static(h, (int)n_rec, h->stream); if (r != FOT_OK) return r; }
     if (rec_doubles) {
         HIP_TRY(h, hipMemcpy(R.dPos.p, rp->pos, sizeof(double) * rec_doubles, hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(R.dVel.p, rp->vel, sizeof(double) * rec_doubles, hipMemcpyHostToDevice));

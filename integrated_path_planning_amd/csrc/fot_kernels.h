@@ -125,9 +125,25 @@ int launch_resample(double sgan_dt, double sim_dt, double staleness, int S, int 
                     const int32_t *ped_ep = nullptr, const int32_t *ep_ped0 = nullptr, const int64_t *ep_blk = nullptr);
 int launch_sample_dist(int S, int P, int T, int skip, const void *out, int out_dtype, int tmajor, double *dist,
                        hipStream_t st);
+// What the safety metrics need of a scenario beyond its DevParams: element s of a table in HBM belongs to scenario s.
+struct SafetyScen {
+    double footprint_radius;
+    int32_t use_fp;                                  // the loop's metrics use this scenario's multi-circle footprint
+    int32_t _pad;
+};
+// ep_scen == nullptr: every ego on scenario P[0] with footprint_radius / use_fp as given.  Otherwise ego e is on scenario
+// ep_scen[e]: its constants are P[ep_scen[e]], its footprint radius and flag scen_tab[ep_scen[e]] (the two arguments are
+// then ignored).
 int launch_safety(const DevParams *P, int n, const double *ego, const int32_t *ped_off, const double *ped_pos,
                   const double *ped_vel, double ego_radius, double ped_radius, double footprint_radius, int use_fp,
-                  fot_safety *out, hipStream_t st);
+                  fot_safety *out, hipStream_t st, const int32_t *ep_scen = nullptr, const SafetyScen *scen_tab = nullptr);
+// The static obstacle points of a scenario loop's requests: request j's points are n points from point src of `points`
+// (the scenarios' point sets, each once in HBM), copied to point dst of `out` -- the static_off layout k_cull reads.
+// The table lies in pinned host memory or HBM; the host has checked every range.
+struct StaticGather {
+    int32_t src, dst, n, _pad;
+};
+int launch_static_gather(const StaticGather *tab, int n_req, const double *points, double *out, hipStream_t st);
 // ---- fot_loop_run: the frame of a lock step built from the HBM-resident recording, and what the host reads of a step
 
 // The recording fot_loop_set_replay left in HBM and the per-slot tables beside it.
@@ -146,6 +162,7 @@ struct FrameStage {
     const int64_t *blk = nullptr;                    // [n_run + 1] first point of episode i's block of the prediction tensor
     const int32_t *prepend = nullptr;                // [n_run] 1: the current positions lead episode i's tracks
     const double *ego = nullptr;                     // [n_run][4] x, y, yaw, v
+    const int32_t *scen = nullptr;                   // [n_run] scenario of running episode i, or nullptr (all on scenario 0)
 };
 
 // The compacted frame in HBM: rows [ped0[i], ped0[i + 1]) belong to running episode i.
@@ -157,6 +174,7 @@ struct FrameDev {
     int64_t *blk = nullptr;                          // [n_run + 1]
     int32_t *prepend = nullptr;                      // [n_run]
     double *ego = nullptr;                           // [n_run][4]
+    int32_t *scen = nullptr;                         // [n_run], written when FrameStage::scen is given
 };
 
 // What the host needs of a record to replay the retry loop and move the ego: the record's first 80 bytes as they are

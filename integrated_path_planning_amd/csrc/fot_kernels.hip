@@ -1947,10 +1947,19 @@ __device__ __forceinline__ double wave_min_f64(double v)
 __global__ void __launch_bounds__(WAVE)
 k_safety(const DevParams *__restrict__ Pp, int n, const double *__restrict__ ego, const int32_t *__restrict__ ped_off,
          const double *__restrict__ ped_pos, const double *__restrict__ ped_vel, double ego_radius, double ped_radius,
-         double footprint_radius, int use_fp, fot_safety *__restrict__ out)
+         double footprint_radius, int use_fp, fot_safety *__restrict__ out, const int32_t *__restrict__ ep_scen,
+         const SafetyScen *__restrict__ scen_tab)
 {
     const int e = blockIdx.x;
     if (e >= n) return;
+    // a scenario loop: the episode's scenario picks the constants, the footprint radius and the flag.  One episode = one
+    // workgroup of one wave, so the id and everything read through it are wave-uniform (scalar loads).
+    if (ep_scen) {
+        const int scen = ep_scen[e];
+        Pp += scen;
+        footprint_radius = scen_tab[scen].footprint_radius;
+        use_fp = scen_tab[scen].use_fp;
+    }
     const DevParams &P = *Pp;
     const double x = ego[4 * e], y = ego[4 * e + 1], yaw = ego[4 * e + 2], v = ego[4 * e + 3];
     const double hx = cos(yaw), hy = sin(yaw);
@@ -2023,6 +2032,18 @@ k_loop_frame(ReplayView rv, FrameStage in, FrameDev out, int n_run, int f_cur, i
         if (i == n_run - 1) { out.ped0[n_run] = q1; out.blk[n_run] = in.blk[n_run]; }
     }
     if (threadIdx.x < 4) out.ego[4 * i + threadIdx.x] = in.ego[4 * i + threadIdx.x];
+    if (in.scen && threadIdx.x == 0) out.scen[i] = in.scen[i];
+}
+
+// One workgroup per request of a scenario loop: its scenario's static points, resident once in HBM, into the request's
+// own run of the block k_cull reads (fot_batch::static_off layout).  16-byte rows, coalesced both ways.
+__global__ void __launch_bounds__(256)
+k_static_gather(const StaticGather *__restrict__ tab, int n_req, const double2 *__restrict__ points, double2 *__restrict__ out)
+{
+    const int j = blockIdx.x;
+    if (j >= n_req) return;
+    const int src = tab[j].src, dst = tab[j].dst, n = tab[j].n;
+    for (int p = threadIdx.x; p < n; p += 256) out[dst + p] = points[src + p];
 }
 
 // one thread per (row, axis) of the frame; the arithmetic of k_resample's cv = 2 path, operation for operation
@@ -2248,10 +2269,20 @@ int launch_sample_dist(int S, int P, int T, int skip, const void *out, int out_d
 
 int launch_safety(const DevParams *P, int n, const double *ego, const int32_t *ped_off, const double *ped_pos,
                   const double *ped_vel, double ego_radius, double ped_radius, double footprint_radius, int use_fp,
-                  fot_safety *out, hipStream_t st)
+                  fot_safety *out, hipStream_t st, const int32_t *ep_scen, const SafetyScen *scen_tab)
 {
     if (n <= 0) return 0;
-    k_safety<<<n, WAVE, 0, st>>>(P, n, ego, ped_off, ped_pos, ped_vel, ego_radius, ped_radius, footprint_radius, use_fp, out);
+    if (!scen_tab) ep_scen = nullptr;
+    k_safety<<<n, WAVE, 0, st>>>(P, n, ego, ped_off, ped_pos, ped_vel, ego_radius, ped_radius, footprint_radius, use_fp, out,
+                                 ep_scen, scen_tab);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_static_gather(const StaticGather *tab, int n_req, const double *points, double *out, hipStream_t st)
+{
+    if (n_req <= 0) return 0;
+    k_static_gather<<<n_req, 256, 0, st>>>(tab, n_req, (const double2 *)points, (double2 *)out);
     FOT_LAUNCH_CHECK();
     return 0;
 }

@@ -230,14 +230,23 @@ class BatchPlanner:
             self.set_waypoints(*waypoints, scenario=sid.value)
         return sid.value
 
-    def path_coeffs(self) -> List[np.ndarray]:
+    def path_coeffs(self, scenario: int = 0) -> List[np.ndarray]:
         n = C.c_int32(0)
-        _abi.check(self._h, self._lib.fot_get_path_coeffs(self._h, C.byref(n), *([None] * 9)))
+        if scenario == 0:
+            get = lambda *a: self._lib.fot_get_path_coeffs(self._h, *a)
+        else:
+            get = lambda *a: self._lib.fot_get_scenario_path_coeffs(self._h, int(scenario), *a)
+        _abi.check(self._h, get(C.byref(n), *([None] * 9)))
         k = n.value
         out = [np.zeros(k), np.zeros(k), np.zeros(k - 1), np.zeros(k), np.zeros(k - 1),
                np.zeros(k), np.zeros(k - 1), np.zeros(k), np.zeros(k - 1)]
-        _abi.check(self._h, self._lib.fot_get_path_coeffs(self._h, C.byref(n), *[_as_dp(a) for a in out]))
+        _abi.check(self._h, get(C.byref(n), *[_as_dp(a) for a in out]))
         return out
+
+    @property
+    def n_scenarios(self) -> int:
+        """Scenarios of this handle (scenario 0 and every ``add_scenario``)."""
+        return len(self.scenario_params)
 
     def spline_eval(self, s):
         s = np.ascontiguousarray(np.atleast_1d(s), dtype=np.float64)
@@ -431,6 +440,28 @@ class BatchPlanner:
         ego = np.ascontiguousarray(ego5, dtype=np.float64).reshape(-1, 5)
         self._loop_n = len(ego)
         _abi.check(self._h, self._lib.fot_loop_begin(self._h, len(ego), C.addressof(config), _addr(ego) if len(ego) else None))
+
+    def loop_begin_scenarios(self, configs: Sequence["_abi.LoopConfig"], use_footprint: Sequence[bool],
+                             slot_scenario: np.ndarray, ego5: np.ndarray) -> None:
+        """``fot_loop_begin_scenarios``: ``loop_begin`` with a scenario per episode slot.  ``configs[s]`` /
+        ``use_footprint[s]``: the fail-safe constants and the metrics' footprint flag of scenario ``s``;
+        ``slot_scenario[e]``: the scenario of slot e."""
+        ego = np.ascontiguousarray(ego5, dtype=np.float64).reshape(-1, 5)
+        scen = np.ascontiguousarray(slot_scenario, dtype=np.int32)
+        if scen.shape != (len(ego),) or len(configs) != len(use_footprint) or not len(configs):
+            raise ValueError("loop_begin_scenarios: one scenario id per slot, one footprint flag per configuration")
+        cfgs = (_abi.LoopConfig * len(configs))(*configs)
+        ufp = np.ascontiguousarray([bool(u) for u in use_footprint], dtype=np.int32)
+        self._loop_n = len(ego)
+        _abi.check(self._h, self._lib.fot_loop_begin_scenarios(
+            self._h, len(ego), len(configs), C.addressof(cfgs), _addr(ufp), _addr(scen) if len(ego) else None,
+            _addr(ego) if len(ego) else None))
+
+    def loop_set_scenario_static(self, scenario: int, points: Optional[np.ndarray]) -> None:
+        """The static obstacle points the loop's requests on ``scenario`` see (``fot_loop_set_scenario_static``)."""
+        pts = np.ascontiguousarray(np.empty((0, 2)) if points is None else points, dtype=np.float64).reshape(-1, 2)
+        _abi.check(self._h, self._lib.fot_loop_set_scenario_static(self._h, int(scenario), len(pts),
+                                                                   _addr(pts) if len(pts) else None))
 
     def loop_step(self, frame: dict, episode: np.ndarray) -> dict:
         """``fot_loop_step``: the whole lock step of the frame's episodes (``episode[i]`` = slot of episode i) in one

@@ -1,0 +1,363 @@
+"""Closed-loop episodes of DIFFERENT scenarios in one lock step: the 13 reference episodes of
+tests/golden/closed_loop/reference_cv_episodes.npz cover five planner / loop configurations (scenario_01, scenario_02 with
+static walls, scenario_03 with a curved path, scenario_01 with the three-circle footprint, scenario_01 with the inflated
+margin).  One BatchedClosedLoop over a list of configurations runs them on ONE handle (fot_loop_begin_scenarios); every
+episode must reproduce its reference, and equal -- exactly -- what it does in a loop of its own scenario alone."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from closed_loop_common import assert_episode_matches, load_episodes, scenario_config
+from integrated_path_planning_amd import _abi
+from integrated_path_planning_amd.batch import PlanRequest
+from integrated_path_planning_amd.closed_loop import (BatchedClosedLoop, _Cfg, _VectorStateMachine, expand_static_obstacles,
+                                                      footprint_from_config, loop_config_from, merge_configs,
+                                                      planner_kwargs_from_config)
+from integrated_path_planning_amd.planner import BatchPlanner
+from integrated_path_planning_amd.prediction import PredictionResampler
+
+pytestmark = pytest.mark.gpu
+
+# interleaved: neighbouring slots are on different scenarios
+NAMES = ("base", "walls", "turn", "footprint", "inflate", "fast", "rnd3", "rnd2", "shift", "rnd4", "rnd0", "rnd1", "rnd5")
+
+
+@pytest.fixture(scope="module")
+def episodes():
+    return load_episodes()
+
+
+def _build(episodes, names, **kw):
+    return BatchedClosedLoop([scenario_config(episodes["meta"], n) for n in names],
+                             [episodes[n + "_ped_traj"] for n in names], **kw)
+
+
+def _per_episode(sim):
+    """What every episode did at each of its steps, from the loop's per-step arrays."""
+    out = [[] for _ in sim.episodes]
+    for s in sim._steps:
+        for e in range(len(sim.episodes)):
+            i = int(s["slot"][e])
+            if i < 0:
+                continue
+            kn, has = int(s["keep"][i]), bool(s["has_path"][i])
+            out[e].append(dict(ego=np.array(s["ego"][i]), jerk=float(s["jerk"][i]), state=int(s["state"][i]),
+                               stats=np.array(s["stats"][i]), has_path=has, keep=kn,
+                               cost=float(s["cost"][i]) if has else 0.0,       # (no path: the field is not the episode's)
+                               after=np.array(s["after"][i]).tobytes(),
+                               paths=np.stack([np.array(s["paths"][f][i, :kn]) for f in _abi.PATH_FIELDS])))
+    return out
+
+
+def _assert_same_episode(a, b, label):
+    assert len(a) == len(b), f"{label}: {len(a)} steps against {len(b)}"
+    for k, (x, y) in enumerate(zip(a, b)):
+        for f in ("ego", "stats", "paths"):
+            assert np.array_equal(x[f], y[f]), f"{label} step {k}: {f}"
+        for f in ("jerk", "state", "has_path", "keep", "cost", "after"):
+            assert x[f] == y[f], f"{label} step {k}: {f}"
+
+
+@pytest.fixture(scope="module")
+def mixed_runs(episodes):
+    """The 13 episodes in one mixed loop: stepwise (one call per lock step) and resident (whole runs in the library)."""
+    lib = _abi.lib()
+    runs = {}
+    for form, kw in (("step", {}), ("resident", dict(resident=True))):
+        before = lib.fot_live_handles()
+        sim = _build(episodes, NAMES, **kw)
+        runs[form + "_handles"] = lib.fot_live_handles() - before
+        runs[form + "_scenarios"] = sim.engine.n_scenarios
+        hists = sim.run()
+        runs[form] = dict(hists=[list(h) for h in hists], term=[ep.termination_reason for ep in sim.episodes],
+                          steps=[ep.step_count for ep in sim.episodes], per=_per_episode(sim))
+        sim.close()
+    return runs
+
+
+@pytest.mark.parametrize("form", ["step", "resident"])
+def test_thirteen_reference_episodes_five_scenarios_one_handle(episodes, mixed_runs, form):
+    """Every episode of the mixed loop passes the comparison of the per-scenario tests (same tolerances) and ends with the
+    reference's termination reason and step count; the loop created exactly one handle, which holds five scenarios."""
+    assert mixed_runs[form + "_handles"] == 1
+    assert mixed_runs[form + "_scenarios"] == 5
+    r = mixed_runs[form]
+    for h, term, steps, name in zip(r["hists"], r["term"], r["steps"], NAMES):
+        assert_episode_matches(h, term, episodes, name)
+        assert steps == episodes["meta"]["variants"][name]["steps"]
+    assert len(set(r["steps"])) > 5                                # (the episodes end at different lock steps)
+
+
+def test_mixed_equals_separate_exactly(episodes, mixed_runs):
+    """No arithmetic of an episode depends on its neighbours: per step ego, state, stats, the followed record's cost /
+    keep and its 15 path arrays equal, under np.array_equal, what five single-configuration loops on handles of their own
+    produce -- for the stepwise and for the resident mixed loop."""
+    _, slot, _ = merge_configs([scenario_config(episodes["meta"], n) for n in NAMES])
+    for k in range(int(slot.max()) + 1):
+        members = [i for i in range(len(NAMES)) if slot[i] == k]
+        names = [NAMES[i] for i in members]
+        cfg = scenario_config(episodes["meta"], names[0])
+        with BatchedClosedLoop(cfg, [episodes[n + "_ped_traj"] for n in names]) as alone:
+            assert alone.scenarios is None and alone._native
+            alone.run()
+            per = _per_episode(alone)
+        for j, i in enumerate(members):
+            for form in ("step", "resident"):
+                _assert_same_episode(mixed_runs[form]["per"][i], per[j], f"{NAMES[i]} ({form} mixed against alone)")
+
+
+def test_resident_chunks_equal_stepping_under_scenarios(episodes, mixed_runs):
+    """run(n) in chunks gives the histories of stepping; episodes of different scenarios end at different steps (the
+    reference's counts differ per variant) and the remaining ones continue unaffected."""
+    with _build(episodes, NAMES, resident=True) as sim:
+        sim.run(7)
+        sim.run(1)
+        assert sim.step() == len(NAMES)
+        while sim.alive.any():
+            sim.run(50)
+        per = _per_episode(sim)
+        term = [ep.termination_reason for ep in sim.episodes]
+    assert term == mixed_runs["step"]["term"]
+    for i, name in enumerate(NAMES):
+        _assert_same_episode(per[i], mixed_runs["step"]["per"][i], f"{name} (chunked resident against stepping)")
+        assert len(per[i]) == episodes["meta"]["variants"][name]["steps"]
+
+
+@pytest.mark.parametrize("kw", [{}, dict(resident=True)], ids=["step", "resident"])
+def test_reversed_slot_order_gives_the_same_episodes(episodes, mixed_runs, kw):
+    """The same episodes in reversed slot order (so scenario 0 is scenario_01 in one loop and not in the other, and every
+    scenario id changes): the same per-episode histories."""
+    names = NAMES[::-1][3:] + NAMES[::-1][:3]                      # (reversed, begun at a scenario_03 episode)
+    with _build(episodes, names, **kw) as sim:
+        assert names[0] == "rnd4" and sorted(names) == sorted(NAMES)
+        assert list(sim.scenarios[0].reference_waypoints_y) != list(scenario_config(episodes["meta"])["reference_waypoints_y"])
+        sim.run()
+        per = _per_episode(sim)
+        term = [ep.termination_reason for ep in sim.episodes]
+    for j, name in enumerate(names):
+        i = NAMES.index(name)
+        assert term[j] == mixed_runs["step"]["term"][i]
+        _assert_same_episode(per[j], mixed_runs["step"]["per"][i], f"{name} (reversed order)")
+
+
+def test_forms_that_take_one_configuration_refuse_a_mixed_list(episodes):
+    cfgs = [scenario_config(episodes["meta"], n) for n in ("base", "turn")]
+    tracks = [episodes[n + "_ped_traj"] for n in ("base", "turn")]
+    for fused in (False, "two-call"):
+        with pytest.raises(ValueError, match="one configuration"):
+            BatchedClosedLoop(cfgs, tracks, fused=fused)
+    with pytest.raises(ValueError, match="one configuration per episode"):
+        BatchedClosedLoop(cfgs, tracks[:1])
+    # equal configurations in a list are one scenario: today's loop, any form
+    with BatchedClosedLoop([cfgs[0], dict(cfgs[0])], [tracks[0]] * 2, fused="two-call") as sim:
+        assert sim.scenarios is None and sim.engine.n_scenarios == 1
+
+
+# ---- the C ABI in plain calls -----------------------------------------------------------------------------------------
+def _cfg_parts(cfg):
+    c = _Cfg(cfg)
+    return c, planner_kwargs_from_config(c, footprint_from_config(c)), \
+        (np.asarray(c.reference_waypoints_x, float), np.asarray(c.reference_waypoints_y, float))
+
+
+def test_c_abi_scenario_episodes_and_refusals(episodes):
+    """fot_add_scenario x2 -> paths -> fot_loop_begin_scenarios -> per-scenario static -> fot_loop_set_replay ->
+    fot_loop_run until it returns 0, through ctypes: one episode each of base, walls and turn reproduces the reference.
+    Then every refusal: its code, and a run in progress continues and still matches."""
+    lib = _abi.lib()
+    names = ("base", "walls", "turn")
+    cfgs = [scenario_config(episodes["meta"], n) for n in names]
+    parts = [_cfg_parts(c) for c in cfgs]
+    c0 = parts[0][0]
+    tr = [np.asarray(episodes[n + "_ped_traj"], np.float64) for n in names]
+    off = np.concatenate([[0], np.cumsum([t.shape[1] for t in tr])]).astype(np.int32)
+    nfr = np.array([len(t) for t in tr], np.int32)
+    pos = np.zeros((int(nfr.max()), int(off[-1]), 2))
+    for e, t in enumerate(tr):
+        pos[: len(t), off[e]:off[e + 1]] = t
+        pos[len(t):, off[e]:off[e + 1]] = t[-1]
+    vel = np.zeros_like(pos)
+    vel[:-1] = (pos[1:] - pos[:-1]) / c0.dt
+    vel[-1] = vel[-2]
+    ego5 = np.array([c["ego_initial_state"][:5] for c in cfgs], np.float64)
+    lcs = (_abi.LoopConfig * 3)(*[loop_config_from(p[0], _VectorStateMachine.constants_of(p[0]), 3) for p in parts])
+    ufp = np.zeros(3, np.int32)
+    slot_scen = np.array([0, 1, 2], np.int32)
+
+    def begin(h, n_cfg=3, scen=slot_scen):
+        return lib.fot_loop_begin_scenarios(h, 3, n_cfg, C.addressof(lcs), ufp.ctypes.data, scen.ctypes.data, ego5.ctypes.data)
+
+    def set_replay(bp):
+        r = _abi.LoopReplay()
+        r.n_slots, r.n_frames_max, r.obs_len, r.pred_len = 3, len(pos), c0.obs_len, c0.pred_len
+        r.warmup_frames, r.use_footprint = int(c0.obs_len * 0.4 / c0.dt), 0
+        r.ped_off, r.n_frames, r.pos, r.vel = off.ctypes.data, nfr.ctypes.data, pos.ctypes.data, vel.ctypes.data
+        r.rp = PredictionResampler(bp, pred_len=c0.pred_len, sgan_dt=0.4, sim_dt=c0.dt, plan_horizon=c0.max_t).params
+        r.ego_radius, r.ped_radius = c0.ego_radius, c0.ped_radius
+        r.s_end, r.goal_distance = -1.0, 2.0                       # (s_end: ignored by a scenario loop)
+        return lib.fot_loop_set_replay(bp._h, C.addressof(r))
+
+    def run(bp, chunk, max_calls=None):
+        n_total = bp.n_total_samples
+        out = {k: [] for k in ("ego", "jerk", "state", "followed", "keep", "paths")}
+        steps, term = np.zeros(3, np.int32), np.zeros(3, np.int32)
+        calls = 0
+        while max_calls is None or calls < max_calls:
+            a = dict(ego=np.zeros((chunk, 3, 5)), jerk=np.zeros((chunk, 3)), state=np.zeros((chunk, 3), np.int32),
+                     followed=np.full((chunk, 3), -1, np.int32), keep=np.zeros((chunk, 3), np.int32),
+                     paths=np.zeros((chunk, 15, 3, n_total)))
+            ro = _abi.LoopRunOut()
+            for k, v in a.items():
+                setattr(ro, k, v.ctypes.data)
+            ro.steps, ro.termination = steps.ctypes.data, term.ctypes.data
+            done = lib.fot_loop_run(bp._h, chunk, C.addressof(ro))
+            assert done >= 0, lib.fot_last_error(bp._h)
+            calls += 1
+            if done == 0:
+                break
+            for k, v in a.items():
+                out[k].append(v[:done].copy())
+        return {k: np.concatenate(v) for k, v in out.items()}, steps.copy(), term.copy()
+
+    def check(o, steps, term):
+        for e, n in enumerate(names):
+            meta = episodes["meta"]["variants"][n]
+            assert (int(steps[e]), int(term[e])) == (meta["steps"], {"collision": 1, "goal": 2}[meta["termination"]]), n
+            k = meta["steps"]
+            assert (o["followed"][:k, e] >= 0).all() and (o["followed"][k:, e] == -1).all()
+            want = episodes[n + "_ego"]
+            np.testing.assert_allclose(o["ego"][:k, e], want[:, :5], rtol=1e-6, atol=1e-6, err_msg=n)
+            np.testing.assert_allclose(o["jerk"][:k, e], want[:, 5], rtol=1e-6, atol=1e-4, err_msg=n)
+            np.testing.assert_array_equal(o["state"][:k, e], episodes[n + "_state"], err_msg=n)
+            np.testing.assert_array_equal(o["keep"][:k, e], episodes[n + "_planned_len"], err_msg=n)
+            for i, kn in enumerate(episodes[n + "_planned_len"]):
+                np.testing.assert_allclose(o["paths"][i, 9, e, :kn], episodes[n + "_planned_x"][i, :kn], atol=1e-6)
+
+    with BatchPlanner(waypoints=parts[0][2], device=-1, **parts[0][1]) as bp:
+        h = bp._h
+        ids = []
+        for _, kw, _ in parts[1:]:
+            sid = C.c_int32(-1)
+            from integrated_path_planning_amd.planner import _params_from_kwargs
+            prm = _params_from_kwargs(kw)
+            _abi.check(h, lib.fot_add_scenario(h, C.byref(prm), C.byref(sid)))
+            ids.append(sid.value)
+        assert ids == [1, 2]
+        # refused: scenario 2 has no path yet
+        wx, wy = parts[1][2]
+        _abi.check(h, lib.fot_set_scenario_path_waypoints(h, 1, len(wx), wx.ctypes.data_as(C.POINTER(C.c_double)),
+                                                          wy.ctypes.data_as(C.POINTER(C.c_double))))
+        assert begin(h) == _abi.ERR_NO_PATH_SET
+        wx, wy = parts[2][2]
+        _abi.check(h, lib.fot_set_scenario_path_waypoints(h, 2, len(wx), wx.ctypes.data_as(C.POINTER(C.c_double)),
+                                                          wy.ctypes.data_as(C.POINTER(C.c_double))))
+        _abi.check(h, begin(h))
+        for sid, (c, _, _) in enumerate(parts):
+            pts = np.ascontiguousarray(expand_static_obstacles(getattr(c, "static_obstacles", None), step=0.5))
+            _abi.check(h, lib.fot_loop_set_scenario_static(h, sid, len(pts), pts.ctypes.data if len(pts) else None))
+        _abi.check(h, set_replay(bp))
+        first, steps, term = run(bp, 64)
+        check(first, steps, term)
+        # a second run of the same episodes with every refusal tried while it is in progress
+        _abi.check(h, begin(h))
+        _abi.check(h, set_replay(bp))
+        head, _, _ = run(bp, 20, max_calls=2)
+        assert begin(h, scen=np.array([0, 1, 3], np.int32)) == _abi.ERR_INVALID          # unknown scenario id
+        assert begin(h, scen=np.array([0, -1, 2], np.int32)) == _abi.ERR_INVALID
+        assert begin(h, n_cfg=2) == _abi.ERR_INVALID                                     # n_cfg below the largest id in use
+        pts = np.zeros((2, 2))
+        assert lib.fot_loop_set_scenario_static(h, 3, 2, pts.ctypes.data) == _abi.ERR_INVALID
+        assert lib.fot_loop_set_scenario_static(h, 1, -1, pts.ctypes.data) == _abi.ERR_INVALID
+        assert lib.fot_last_error(h)
+        fr = _abi.LoopFrame()
+        so = _abi.LoopStepOut()
+        assert lib.fot_loop_step(h, C.addressof(fr), None, C.addressof(so)) == _abi.ERR_INVALID   # the replay owns the clock
+        tail, steps2, term2 = run(bp, 64)
+        again = {k: np.concatenate([head[k], tail[k]]) for k in first}
+        assert (steps2 == steps).all() and (term2 == term).all()
+        for k in first:
+            assert first[k].tobytes() == again[k].tobytes(), k
+        # a scenario loop takes the constant-velocity predictor only
+        _abi.check(h, begin(h))
+        fr = _abi.LoopFrame()
+        fr.n_episodes, fr.pred_len, fr.dist_raw, fr.dist_S = 1, c0.pred_len, 1 << 20, 2
+        one_off = np.zeros(2, np.int32)
+        fr.ped_off = one_off.ctypes.data
+        slot = np.zeros(1, np.int32)
+        assert lib.fot_loop_step(h, C.addressof(fr), slot.ctypes.data, C.addressof(so)) == _abi.ERR_UNSUPPORTED
+
+
+# ---- the static points gathered on the device -------------------------------------------------------------------------
+def _static_scene(episodes, slots, blocker):
+    """One lock step, no pedestrians, of slots on three scenarios with different static point sets: scenario_01 has none,
+    scenario_02 its walls, scenario_03 three points (with ``blocker`` right in front of its ego: level 0 fails and the
+    escalation retries are planned).  Returns the candidate tables of the step's LAST plan call and those of the same
+    requests planned through fot_plan_batch_scenarios with the static points passed from the host."""
+    cfgs = [scenario_config(episodes["meta"], n) for n in ("base", "walls", "turn")]
+    parts = [_cfg_parts(c) for c in cfgs]
+    x0, y0 = cfgs[2]["ego_initial_state"][:2]
+    near = np.array([[x0 + 6.0, y0], [x0 + 6.5, y0 + 0.4], [x0 + 6.5, y0 - 0.4]]) if blocker else \
+        np.array([[x0 + 6.0, y0 + 30.0], [x0 + 6.5, y0 + 30.4], [x0 + 6.5, y0 + 29.6]])
+    points = [np.empty((0, 2)), expand_static_obstacles(cfgs[1]["static_obstacles"], step=0.5), near]
+    assert len({len(p) for p in points}) == 3 and len(points[0]) == 0
+    consts = [_VectorStateMachine.constants_of(p[0]) for p in parts]
+    slots = np.asarray(slots, np.int32)
+    n = len(slots)
+    ego5 = np.array([cfgs[k]["ego_initial_state"][:5] for k in slots], np.float64)
+    with BatchPlanner(waypoints=parts[0][2], device=-1, **parts[0][1]) as bp:
+        for _, kw, wp in parts[1:]:
+            bp.add_scenario(waypoints=wp, **kw)
+        for k, p in enumerate(points):
+            bp.loop_set_scenario_static(k, p)
+        bp.loop_begin_scenarios([loop_config_from(p[0], k, 3) for p, k in zip(parts, consts)], [False] * 3, slots, ego5)
+        frame = dict(ped_off=np.zeros(n + 1, np.int32), ped_pos=np.zeros((0, 2)), ped_vel=np.zeros((0, 2)),
+                     ego_radius=1.0, ped_radius=0.2)
+        o = bp.loop_step(frame, np.arange(n, dtype=np.int32))
+        rec = o["records"].copy()
+        n_rec = len(rec)
+        failed = [i for i in range(n) if rec["status"][i] != 0]
+        loop_tabs = [bp.candidates(j) for j in range(n_rec - n if n_rec > n else n)]
+
+        def request(i, state, prev_s, chain):
+            k = int(slots[i])
+            sm = _VectorStateMachine(parts[k][0], 1)
+            tgt, ov, stop = sm.config(np.array([state]), np.array([np.inf]))
+            keys = ("max_speed", "max_accel", "max_curvature", "max_lat_accel")
+            return PlanRequest(*ego5[i], target_speed=float(tgt[0]), prev_s=prev_s, chain_prev_s=chain,
+                               overrides={q: float(ov[0, j]) for j, q in enumerate(keys) if not np.isnan(ov[0, j])} or None,
+                               max_stop_distance=None if np.isnan(stop[0]) else float(stop[0]),
+                               static=points[k] if len(points[k]) else None, scenario=k)
+
+        level0 = [request(i, 0, None, False) for i in range(n)]
+        if n_rec > n:                                              # the last call planned the escalation levels
+            reqs = []
+            for i in failed:
+                nps = float(rec["new_prev_s"][i])
+                reqs += [request(i, 1, None if np.isnan(nps) else nps, False), request(i, 2, None, True)]
+            assert len(reqs) == n_rec - n
+        else:
+            reqs = level0
+        res0 = bp.plan_batch(level0)
+        head = [(res0.records[i].status, res0.records[i].best_index, res0.records[i].cost, list(res0.records[i].stats))
+                for i in range(n)]
+        bp.plan_batch(reqs)
+        host_tabs = [bp.candidates(j) for j in range(len(reqs))]
+    loop_head = [(int(rec["status"][i]), int(rec["best_index"][i]), float(rec["cost"][i]), list(rec["stats"][i])) for i in range(n)]
+    return loop_tabs, host_tabs, loop_head, head, len(failed), [int(slots[i]) for i in failed]
+
+
+@pytest.mark.parametrize("blocker", [False, True], ids=["level0", "escalations"])
+def test_static_points_gathered_on_the_device(episodes, blocker):
+    """Two scenarios with different numbers of static points and one with none, requests interleaved: the per-candidate
+    status tables (fot_debug_candidates) of the step's requests -- the level-0 launch, and the launch of the escalation
+    retries -- equal those of the same requests planned with the static points passed from the host."""
+    slots = [0, 1, 2, 1, 2, 0, 2, 1, 0]
+    loop_tabs, host_tabs, loop_head, head, n_failed, failed_scen = _static_scene(episodes, slots, blocker)
+    assert loop_head == head                                       # the level-0 records: status, selection, cost, stats
+    if blocker:
+        assert n_failed >= 3 and 2 in failed_scen                  # (the blocked scenario_03 slots escalate)
+    assert len(loop_tabs) == len(host_tabs) > 0
+    for j, (a, b) in enumerate(zip(loop_tabs, host_tabs)):
+        for name, x, y in zip(("cost", "status", "keep", "n_t"), a, b):
+            assert np.array_equal(x, y, equal_nan=True), f"request {j}: {name}"
