@@ -168,10 +168,10 @@ const char *fot_version(void);
  * corruption").  out[i], i < cap: FOT_ABI_VERSION, sizeof of fot_params, fot_ego, fot_overrides, fot_result, fot_batch,
  * fot_resample_params, fot_safety, fot_loop_frame, fot_loop_request, fot_wire_header, then FOT_MAX_NT, FOT_MAX_CIRCLES,
  * FOT_MAX_TI, FOT_MAX_TV, FOT_MAX_BRAKE, FOT_MAX_SAMPLES, FOT_MAX_PRED_LEN, FOT_PROFILE_KERNELS, FOT_MARGIN_GROUPS,
- * sizeof of fot_loop_config, fot_loop_step_out, fot_loop_replay, fot_loop_run_out.
+ * sizeof of fot_loop_config, fot_loop_step_out, fot_loop_replay, fot_loop_run_out, fot_loop_summary.
  * Returns the number of words the library knows (FOT_ABI_INFO_WORDS of ITS header). */
-#define FOT_ABI_VERSION 5
-#define FOT_ABI_INFO_WORDS 24
+#define FOT_ABI_VERSION 6
+#define FOT_ABI_INFO_WORDS 25
 int32_t fot_abi_info(int32_t cap, int32_t *out);
 
 /* FrenetPlanner.__init__ (frenet_planner.py:149-225).  device < 0: current device. */
@@ -534,6 +534,48 @@ typedef struct fot_loop_run_out {
 } fot_loop_run_out;
 int fot_loop_set_replay(fot_handle *h, const fot_loop_replay *replay);
 int fot_loop_run(fot_handle *h, int32_t max_steps, fot_loop_run_out *out);
+
+/* ---- per-episode summary metrics, accumulated while the resident loop runs --------------------------------------------
+ * What the reference computes of an episode's whole history when it ends (calculate_aggregate_metrics,
+ * src/core/metrics.py:272-320; one row of metrics_summary.csv), restricted to what a replayed loop with the
+ * constant-velocity predictor produces.  Per slot, over its L = steps lock steps so far:
+ *   - from every step's NEW ego state and the metrics of that state (fot_loop_run_out.after): min_dist, collision_count,
+ *     min_ttc (over steps with 0 < ttc < inf, else inf), max / mean / rms of |jerk|, max / mean of |a|; L = 0 gives the
+ *     reference's values of an empty history (0, 0, inf, 0 ...);
+ *   - prediction error against the recording.  Step i's prediction is the dense track [P][n_dense][2] without the
+ *     prepended current position; d_i[p][k] = Euclidean distance of dense sample k to the pedestrian's position at step
+ *     i + 1 + k, recording row min(frame_i + 1 + k, n_frames[slot] - 1).
+ *       planning_ade / planning_fde / planning_eval_count (metrics.py:225-269): E = min(n_dense, L - (i + 1)), origins
+ *       with E == 0 skipped; sum_p mean_{k<E} d_i[p][k] and sum_p d_i[p][E-1] over the origins, divided by the count (+= P).
+ *       ade / fde / ade_eval_count (metrics.py:31-114): stride = round(sgan_dt / sim_dt), samples k = stride j - 1,
+ *       j = 1 .. pred_len; an origin counts if n_dense > stride pred_len - 1 and i + stride pred_len < L.
+ *       ade_per_agent / fde_per_agent: equal to ade / fde (the constant-velocity predictor's samples are identical, so
+ *       best-of-N picks nothing); pred_samples: num_samples of fot_loop_summary_enable if an origin counted, else 0.
+ *       nll = NaN, nll_eval_count = 0 (identical samples are skipped, metrics.py:155-158).
+ *     Steps without a prediction (observer not ready) and slots without pedestrians contribute nothing; with no counted
+ *     origin the means are NaN and the counts 0.
+ *   - steps, termination (0: runs, 1: collision, 2: goal), total_time = steps * dt.
+ * fot_loop_summary_enable: between fot_loop_set_replay and the first step of a run (on = 0 switches it off again).  A
+ * loop that never enables it launches and allocates nothing for it.  With it, every lock step launches one more kernel
+ * behind the prediction (no host synchronisation): per running slot the row c_i[k] = sum_p d_i[p][k] goes into a ring of
+ * n_dense rows in HBM, and the row it replaces -- its horizon is complete by then -- is folded into running totals.
+ * fot_loop_summaries folds the ring's remaining rows with their truncated horizons into a COPY of the totals, so it may
+ * be called between two fot_loop_run calls and the run goes on.  A slot's numbers do not depend on the other slots.
+ * Refusals (FOT_ERR_INVALID, a refused call changes nothing): no replay set; sgan_dt / sim_dt not an integer; num_samples
+ * < 1; enabling or disabling after the first step; n_slots differing from the loop's; summaries not enabled; out NULL.
+ * fot_loop_begin* drops the accumulators with the replay. */
+typedef struct fot_loop_summary {
+    double min_dist, min_ttc;
+    double max_jerk, mean_jerk, rms_jerk, max_accel, mean_accel;
+    double ade, fde, ade_per_agent, fde_per_agent;
+    double planning_ade, planning_fde;
+    double nll;
+    double total_time;
+    int32_t collision_count, pred_samples, ade_eval_count, planning_eval_count, nll_eval_count;
+    int32_t steps, termination, _pad;
+} fot_loop_summary;
+int fot_loop_summary_enable(fot_handle *h, int32_t on, int32_t num_samples);
+int fot_loop_summaries(fot_handle *h, int32_t n_slots, fot_loop_summary *out);
 
 /* Host utility (no GPU): the first kmax samples of the 15 path arrays of records[index[i]], i < n, as one dense block
  * out[15][n][kmax] in fot_result array order (t .. c) -- what a history keeps of a step's records. */

@@ -492,7 +492,7 @@ class BatchedClosedLoop:
 
     def __init__(self, config, ped_tracks: Sequence[np.ndarray], ego_initial_states: Optional[Sequence] = None,
                  device: int = -1, engine=None, resampler=None, sample_source=None, fused: Optional[bool] = None,
-                 device_samples: bool = False, resident: bool = False):
+                 device_samples: bool = False, resident: bool = False, summaries: bool = False):
         """sample_source: the multi-sample predictor in front of the planner -- a callable
         ``(obs_last [P, 2], obs_prev [P, 2]) -> raw samples [S, pred_len, P, 2]`` at the predictor's own time step
         (what S forward passes of Social-GAN on PyTorch-ROCm return for the pedestrians of all running episodes; the
@@ -506,8 +506,16 @@ class BatchedClosedLoop:
         HBM once, and ``run(n)`` is a few calls that execute n lock steps each without coming back to Python in between;
         ``step()`` is ``run(1)``.  Constant-velocity predictor on the library's own engine only.  The loop's arrays
         (``ego``, ``sm.state``, ``alive``, ...) are brought up to date after every call; the Python ``observer`` is not
-        advanced (the handle owns the clock)."""
+        advanced (the handle owns the clock).
+        summaries (resident loops only): the library accumulates every episode's summary metrics on the device while the
+        loop runs -- the reference's ``calculate_aggregate_metrics``; ``aggregate_metrics()`` / ``save_summaries()`` read
+        them, a few hundred bytes per episode whatever its length.  ``pred_samples`` reports the configuration's
+        ``num_samples`` (trajectory_predictor's sample count, integrated_simulator.py:333: the constant-velocity
+        predictor hands the metrics that many identical samples)."""
         self._resident = bool(resident)
+        self._summaries = bool(summaries)
+        if self._summaries and not self._resident:
+            raise ValueError("summaries=True needs resident=True (the summary is accumulated by the resident loop)")
         if self._resident and (sample_source is not None or engine is not None or resampler is not None or fused not in (None, True)):
             raise ValueError("resident=True needs the constant-velocity predictor on the library's own engine "
                              "(no sample_source, engine or resampler; the one-call step)")
@@ -647,6 +655,8 @@ class BatchedClosedLoop:
                 warmup_frames=int(c.obs_len * self.sgan_dt / c.dt), ego_radius=self.ego_radius, ped_radius=self.ped_radius,
                 use_footprint=self.footprint is not None, s_end=float(np.ravel(self.s_end)[0]),
                 goal_distance=self.GOAL_DISTANCE)      # (a scenario loop: the library takes each slot's own path's end)
+            if self._summaries:
+                self.engine.loop_summary_enable(True, int(getattr(c, "num_samples", 1)))
 
     def close(self) -> None:
         """Release the libfot handle (streams, workspace) now rather than at garbage collection."""
@@ -1195,6 +1205,49 @@ class BatchedClosedLoop:
             planned_yaw=planned("yaw"),
             planned_cost=np.array([r.planned_path.cost if r.planned_path is not None else float("inf")
                                    for r in history]))
+
+    # the reference's keys in the reference's order (calculate_aggregate_metrics, src/core/metrics.py:300-320)
+    SUMMARY_KEYS = ("min_dist", "collision_count", "min_ttc", "max_jerk", "mean_jerk", "rms_jerk", "max_accel", "mean_accel",
+                    "ade", "fde", "ade_per_agent", "fde_per_agent", "pred_samples", "ade_eval_count", "planning_ade",
+                    "planning_fde", "planning_eval_count", "nll", "nll_eval_count")
+    SUMMARY_INT_KEYS = ("collision_count", "pred_samples", "ade_eval_count", "planning_eval_count", "nll_eval_count")
+
+    def aggregate_metrics(self) -> List[Dict[str, Any]]:
+        """One dictionary per episode: the keys and value types of the reference's ``calculate_aggregate_metrics`` over the
+        steps run so far (ints for the counts, ``inf`` / NaN where the reference has them) plus ``termination_reason``,
+        ``steps``, ``total_time`` and ``collision``.  Accumulated on the device by the resident loop (``summaries=True``):
+        no step record is read and no prediction recomputed.  May be called between two ``run()`` calls."""
+        if not self._resident or not self._summaries:
+            raise ValueError("aggregate_metrics() needs BatchedClosedLoop(..., resident=True, summaries=True)")
+        rec = self.engine.loop_summaries()
+        out = []
+        for e in range(len(self.episodes)):
+            r = rec[e]
+            d = {k: (int(r[k]) if k in self.SUMMARY_INT_KEYS else float(r[k])) for k in self.SUMMARY_KEYS}
+            reason = _TERMINATION[int(r["termination"])] or _TERMINATION[int(self.termination[e])]
+            d.update(termination_reason=reason, steps=int(r["steps"]), total_time=float(r["total_time"]),
+                     collision=bool(r["collision_count"] > 0))
+            out.append(d)
+        return out
+
+    def save_summaries(self, output_path: str) -> str:
+        """``metrics_summary.csv`` under output_path: one header, one row per episode, the reference's column names (its
+        wall-clock columns avg_/max_*_time are left out)."""
+        import csv
+        rows = self.aggregate_metrics()
+        os.makedirs(output_path, exist_ok=True)
+        f = os.path.join(output_path, "metrics_summary.csv")
+        # the reference's row (integrated_simulator.py:1008-1028): context, the metrics, then the collision flag
+        cols = (["episode", "prediction_method", "ego_target_speed", "termination_reason", "total_time", "steps"]
+                + list(self.SUMMARY_KEYS) + ["collision"])
+        with open(f, "w", newline="") as fh:
+            w = csv.DictWriter(fh, fieldnames=cols)
+            w.writeheader()
+            for i, d in enumerate(rows):
+                c = self.config if self.scenarios is None else self.scenarios[int(self.slot_scenario[i])]
+                w.writerow(dict(d, episode=i, prediction_method=getattr(c, "prediction_method", "unknown"),
+                                ego_target_speed=getattr(c, "ego_target_speed", 0.0)))
+        return f
 
     def save_results(self, output_path: str) -> List[str]:
         """One directory per episode (episode_000, ...), each with the reference's trajectory.npz."""

@@ -19,6 +19,7 @@
 #include "fot_kernels.h"
 #include "fot_math.hpp"
 #include "fot_replay.hpp"
+#include "fot_summary.hpp"
 #include "fot_setup.hpp"
 
 using namespace fot;
@@ -131,6 +132,19 @@ struct LoopEpisodes {
     std::vector<int32_t> stats;              // [n][8] last_check_stats, a row of -1: None
 };
 
+// fot_loop_summary_enable / fot_loop_summaries: the prediction-error ring and totals in HBM (fot_summary.hpp) and, per slot,
+// what the host accumulates of every step's new ego state and metrics in step order
+struct LoopSummaryAcc {
+    bool on = false;
+    int num_samples = 1;
+    SummaryShape shape = SummaryShape();
+    DevBuf dRing, dRingP, dTotals;               // [slots][n_dense][n_dense] rows | [slots][n_dense] counts | SummaryTotals[slots]
+    PinnedBuf hOut, hSteps;                      // fot_loop_summary[slots] the kernel fills | steps of each slot
+    std::vector<double> min_dist, min_ttc, max_jerk, sum_jerk, sum_jerk2, max_accel, sum_accel;
+    std::vector<int32_t> collisions;
+    void release() { dRing.release(); dRingP.release(); dTotals.release(); hOut.release(); hSteps.release(); }
+};
+
 // fot_loop_set_replay / fot_loop_run: the recording (host copy for the prepend test, HBM copy for the frame kernel), the
 // replay clock and what a resident step keeps on the device
 struct LoopReplay {
@@ -147,8 +161,10 @@ struct LoopReplay {
     DevBuf dRec, dHist;                          // the step's records; followed paths of the call's steps
     PinnedBuf hStage, hDigest, hHistTab, hWord;  // FrameStage | LoopDigest[] | followed record + slot | completion words
     int32_t seq = 0;                             // value the completion words are raised to next
+    LoopSummaryAcc sum;
     void release()
     {
+        sum.release();
         dPos.release(); dVel.release(); dTab.release(); dFrame.release(); dRec.release(); dHist.release();
         hStage.release(); hDigest.release(); hHistTab.release(); hWord.release();
     }
@@ -726,7 +742,7 @@ int32_t fot_abi_info(int32_t cap, int32_t *out)
         FOT_MAX_NT, FOT_MAX_CIRCLES, FOT_MAX_TI, FOT_MAX_TV, FOT_MAX_BRAKE, FOT_MAX_SAMPLES, FOT_MAX_PRED_LEN,
         FOT_PROFILE_KERNELS, FOT_MARGIN_GROUPS,
         (int32_t)sizeof(fot_loop_config), (int32_t)sizeof(fot_loop_step_out),
-        (int32_t)sizeof(fot_loop_replay), (int32_t)sizeof(fot_loop_run_out),
+        (int32_t)sizeof(fot_loop_replay), (int32_t)sizeof(fot_loop_run_out), (int32_t)sizeof(fot_loop_summary),
     };
     for (int i = 0; i < FOT_ABI_INFO_WORDS && i < cap && out; ++i) out[i] = v[i];
     return FOT_ABI_INFO_WORDS;
@@ -1712,6 +1728,7 @@ int fot_loop_begin(fot_handle *h, int32_t n_episodes, const fot_loop_config *cfg
     E.last_clearance.assign(n, INFINITY); E.clear.assign(n, INFINITY); E.clear_ahead.assign(n, INFINITY);
     E.state.assign(n, 0); E.fails.assign(n, 0); E.stats.assign(8 * n, -1);
     h->loop.replay.set = false;                                  // (a new loop: the handle's clock, if it had one, is gone)
+    h->loop.replay.sum.on = false;                               // ... and the summaries' accumulators with it
     return FOT_OK;
 }
 
@@ -1767,6 +1784,7 @@ int fot_loop_begin_scenarios(fot_handle *h, int32_t n_episodes, int32_t n_cfg, c
     E.last_clearance.assign(n, INFINITY); E.clear.assign(n, INFINITY); E.clear_ahead.assign(n, INFINITY);
     E.state.assign(n, 0); E.fails.assign(n, 0); E.stats.assign(8 * n, -1);
     L.replay.set = false;
+    L.replay.sum.on = false;
     return FOT_OK;
 }
 
@@ -1970,6 +1988,10 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         L.dyn_ptr = L.dDyn.p;
         LAUNCH_TRY(h, launch_predict_cv_frame(C.rp.sgan_dt, C.rp.sim_dt, stale, rows, R.n_dense, fd, L.dDyn.as<double>(), st));
     }
+    if (R.sum.on)                                                // this step's row of every running slot's ring
+        LAUNCH_TRY(h, launch_loop_pred_error(rv, s_slot, fd, L.dDyn.as<double>(), n, ready && rows > 0 ? 1 : 0, f_cur,
+                                             R.steps[(size_t)sel[0]], R.sum.shape, R.sum.dRing.as<double>(),
+                                             R.sum.dRingP.as<int32_t>(), R.sum.dTotals.as<SummaryTotals>(), st));
     LAUNCH_TRY(h, launch_safety(h->dP.as<DevParams>(), n, fd.ego, fd.ped0, fd.pos, fd.vel, L.ego_radius, L.ped_radius,
                                 h->sc[0].params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st,
                                 L.p_scen, L.dSafScen.as<SafetyScen>()));
@@ -2025,6 +2047,15 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         if (out->after) out->after[o] = after[i];
         if (out->s_now) out->s_now[o] = s_now;
         R.steps[e] += 1;
+        if (R.sum.on) {                                          // (calculate_aggregate_metrics, metrics.py:279-308)
+            LoopSummaryAcc &A = R.sum;
+            const double aj = std::fabs(W.jerk[i]), aa = std::fabs(W.ego5n[5 * (size_t)i + 4]), ttc = after[i].ttc;
+            A.min_dist[e] = std::fmin(A.min_dist[e], after[i].min_distance);
+            if (after[i].collision != 0) A.collisions[e] += 1;
+            if (ttc > 0.0 && ttc != INFINITY && ttc < A.min_ttc[e]) A.min_ttc[e] = ttc;
+            A.max_jerk[e] = std::fmax(A.max_jerk[e], aj); A.sum_jerk[e] += aj; A.sum_jerk2[e] += aj * aj;
+            A.max_accel[e] = std::fmax(A.max_accel[e], aa); A.sum_accel[e] += aa;
+        }
         // the goal of a scenario loop's slot: the end of its own scenario's path (its spline's last knot)
         const double s_end = E.scenarios ? h->sc[(size_t)E.scen[(size_t)e]].spline.s.back() : C.s_end;
         R.termination[e] = replay_termination(after[i].collision, s_end, s_now, C.goal_distance);
@@ -2071,6 +2102,7 @@ int fot_loop_set_replay(fot_handle *h, const fot_loop_replay *rp)
     HIP_TRY(h, hipStreamSynchronize(h->stream));                 // nothing may still read what is replaced below
     LoopReplay &R = L.replay;
     R.set = false;
+    R.sum.on = false;                                            // (a new recording: summaries are enabled again, if wanted)
     const size_t rec_doubles = (size_t)rp->n_frames_max * cols * 2;
     const int max_lvl = E.max_lvl;
     const size_t n_rec = (size_t)std::max(n, 1) * (size_t)max_lvl;
@@ -2108,6 +2140,79 @@ int fot_loop_set_replay(fot_handle *h, const fot_loop_replay *rp)
     for (int i = 0; i < rp->warmup_frames; ++i) R.clock.advance();   // fills the observer (integrated_simulator.py:406-422)
     L.have_frame = false; L.observe_n = -1;
     R.set = true;
+    return FOT_OK;
+}
+
+int fot_loop_summary_enable(fot_handle *h, int32_t on, int32_t num_samples)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopReplay &R = h->loop.replay;
+    if (!R.set) return fail(h, FOT_ERR_INVALID, "fot_loop_summary_enable: fot_loop_set_replay comes first");
+    const int n = R.cfg.n_slots;
+    for (int e = 0; e < n; ++e)
+        if (R.steps[(size_t)e] != 0) return fail(h, FOT_ERR_INVALID, "fot_loop_summary_enable: the run has begun (enable between fot_loop_set_replay and the first step)");
+    if (R.clock.frame != R.cfg.warmup_frames) return fail(h, FOT_ERR_INVALID, "fot_loop_summary_enable: the run has begun (enable between fot_loop_set_replay and the first step)");
+    LoopSummaryAcc &A = R.sum;
+    if (!on) { A.on = false; return FOT_OK; }
+    if (num_samples < 1) return fail(h, FOT_ERR_INVALID, "fot_loop_summary_enable: num_samples < 1");
+    const int stride = summary_stride(R.cfg.rp.sgan_dt, R.cfg.rp.sim_dt);
+    if (stride < 1) return fail(h, FOT_ERR_INVALID, "fot_loop_summary_enable: sgan_dt must be a multiple of sim_dt");
+    // --- accepted: the ring and the totals start out zero (a row with count 0 contributes nothing)
+    const size_t ns = (size_t)std::max(n, 1), nd = (size_t)R.n_dense;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, A.dRing.ensure(sizeof(double) * ns * nd * nd));
+    HIP_TRY(h, A.dRingP.ensure(sizeof(int32_t) * ns * nd));
+    HIP_TRY(h, A.dTotals.ensure(sizeof(SummaryTotals) * ns));
+    HIP_TRY(h, A.hOut.ensure(sizeof(fot_loop_summary) * ns));
+    HIP_TRY(h, A.hSteps.ensure(sizeof(int32_t) * ns));
+    HIP_TRY(h, hipMemsetAsync(A.dRing.p, 0, sizeof(double) * ns * nd * nd, h->stream));
+    HIP_TRY(h, hipMemsetAsync(A.dRingP.p, 0, sizeof(int32_t) * ns * nd, h->stream));
+    HIP_TRY(h, hipMemsetAsync(A.dTotals.p, 0, sizeof(SummaryTotals) * ns, h->stream));
+    A.shape = summary_shape(R.n_dense, stride, R.cfg.pred_len);
+    A.num_samples = num_samples;
+    A.min_dist.assign(ns, INFINITY); A.min_ttc.assign(ns, INFINITY);
+    A.max_jerk.assign(ns, 0.0); A.sum_jerk.assign(ns, 0.0); A.sum_jerk2.assign(ns, 0.0);
+    A.max_accel.assign(ns, 0.0); A.sum_accel.assign(ns, 0.0); A.collisions.assign(ns, 0);
+    A.on = true;
+    return FOT_OK;
+}
+
+int fot_loop_summaries(fot_handle *h, int32_t n_slots, fot_loop_summary *out)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopReplay &R = h->loop.replay;
+    if (!R.set) return fail(h, FOT_ERR_INVALID, "fot_loop_summaries: fot_loop_set_replay comes first");
+    LoopSummaryAcc &A = R.sum;
+    if (!A.on) return fail(h, FOT_ERR_INVALID, "fot_loop_summaries: summaries are not enabled (fot_loop_summary_enable)");
+    if (n_slots != R.cfg.n_slots) return fail(h, FOT_ERR_INVALID, "fot_loop_summaries: n_slots differs from the loop's");
+    if (n_slots > 0 && !out) return fail(h, FOT_ERR_INVALID, "fot_loop_summaries: out is NULL");
+    if (n_slots == 0) return FOT_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    int32_t *steps = (int32_t *)A.hSteps.p;
+    fot_loop_summary *rec = (fot_loop_summary *)A.hOut.p;
+    for (int e = 0; e < n_slots; ++e) steps[e] = R.steps[(size_t)e];
+    // totals + the ring's rows with their truncated horizons -> the prediction-error keys; nothing in HBM changes
+    LAUNCH_TRY(h, launch_loop_summary(A.shape, A.dRing.as<double>(), A.dRingP.as<int32_t>(), A.dTotals.as<SummaryTotals>(),
+                                      steps, n_slots, A.num_samples, rec, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const double dt = R.cfg.rp.sim_dt;
+    for (int e = 0; e < n_slots; ++e) {
+        fot_loop_summary s = rec[e];
+        const int L = R.steps[(size_t)e];
+        // an empty history: the reference's values (metrics.py:301-308)
+        s.min_dist = L > 0 ? A.min_dist[e] : 0.0;
+        s.min_ttc = A.min_ttc[e];
+        s.collision_count = A.collisions[e];
+        s.max_jerk = A.max_jerk[e]; s.max_accel = A.max_accel[e];
+        s.mean_jerk = L > 0 ? A.sum_jerk[e] / (double)L : 0.0;
+        s.rms_jerk = L > 0 ? std::sqrt(A.sum_jerk2[e] / (double)L) : 0.0;
+        s.mean_accel = L > 0 ? A.sum_accel[e] / (double)L : 0.0;
+        s.steps = L; s.termination = R.termination[(size_t)e]; s._pad = 0;
+        s.total_time = (double)L * dt;
+        out[e] = s;
+    }
     return FOT_OK;
 }
 

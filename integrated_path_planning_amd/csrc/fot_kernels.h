@@ -4,6 +4,7 @@
 #include <cstddef>
 #include <hip/hip_runtime.h>
 #include "fot_types.h"
+#include "fot_summary.hpp"
 
 namespace fot {
 
@@ -206,6 +207,18 @@ int launch_loop_digest(const fot_result *rec, int n, LoopDigest *out, int32_t *d
 // hist[15][n_slots][n_total] at slot[i]; src / slot are pinned host memory
 int launch_loop_history(const fot_result *rec, int n_run, const int32_t *src, const int32_t *slot, double *hist,
                         int n_slots, int n_total, int32_t *done, int32_t seq, hipStream_t st);
+// ---- fot_loop_summaries (fot_summary.hpp): the prediction error of a resident loop
+// Behind the step's prediction: running episode i (slot slot_of[i], pinned host memory) writes the row of lock step
+// `step` -- sum over its pedestrians of the distance between dense sample k of its block of `dyn` (the prepended column
+// skipped) and recording row min(f_cur + 1 + k, frames - 1) -- into place step % n_dense of its ring and folds the row it
+// replaces into totals[slot].  have_pred == 0 (observer not ready) or no pedestrians: an empty row.
+int launch_loop_pred_error(ReplayView rv, const int32_t *slot_of, FrameDev f, const double *dyn, int n_run, int have_pred,
+                           int f_cur, int step, SummaryShape S, double *ring, int32_t *ring_P, SummaryTotals *totals,
+                           hipStream_t st);
+// totals + the ring's rows under steps[slot] (pinned) -> the prediction-error keys and counts of out[slot] (pinned); the
+// other fields of the record are the host's.  Changes nothing in HBM.
+int launch_loop_summary(SummaryShape S, const double *ring, const int32_t *ring_P, const SummaryTotals *totals,
+                        const int32_t *steps, int n_slots, int num_samples, fot_loop_summary *out, hipStream_t st);
 int launch_check_ext(const DevParams *P, const InstDesc *desc, int n_paths, int mode, const int32_t *len,
                      const int32_t *flags, const double *arrays, const double *static_xy, const double *dyn_xy,
                      int32_t *status_out, hipStream_t st);

@@ -21,6 +21,7 @@
 
 #include "fot_math.hpp"
 #include "fot_kernels.h"
+#include "fot_summary.hpp"
 
 namespace fot {
 
@@ -2108,6 +2109,98 @@ k_loop_history(const fot_result *__restrict__ rec, int n_run, const int32_t *__r
 }
 
 // ---------------------------------------------------------------------------
+// fot_loop_summaries: the prediction error of a resident loop, accumulated while it runs (fot_summary.hpp)
+// ---------------------------------------------------------------------------
+
+// One workgroup per running episode, behind the step's prediction.  Row c[k] = sum_p |pred[p][k] - recording[f_cur + 1 +
+// k][p]| of this step goes into place step % n_dense of the slot's ring; the row it replaces -- the one of step - n_dense,
+// whose horizon is complete now -- is folded into the slot's totals first, by thread 0 from a copy in LDS.
+// Lanes: G = the power of two >= P (at most 64) lanes side by side take the pedestrians of one dense sample, so a
+// recording row's [P][2] run is read as adjacent 16-byte loads; 256 / G samples are in flight per pass.  The sum over the
+// pedestrians is a butterfly over the G lanes: its order depends on P alone, never on the other slots or on timing.
+__global__ void __launch_bounds__(256)
+k_loop_pred_error(ReplayView rv, const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn, int n_run,
+                  int have_pred, int f_cur, int step, SummaryShape S, double *__restrict__ ring,
+                  int32_t *__restrict__ ring_P, SummaryTotals *__restrict__ totals)
+{
+    __shared__ double old_row[FOT_MAX_NT];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    if (i >= n_run) return;
+    const int slot = slot_of[i], nd = S.n_dense, r = step % nd;
+    double *row = ring + ((int64_t)slot * nd + r) * nd;
+    int32_t *row_P = ring_P + (int64_t)slot * nd + r;
+    for (int k = tid; k < nd; k += 256) old_row[k] = row[k];
+    __syncthreads();
+    const int p0 = f.ped0[i], P = have_pred ? f.ped0[i + 1] - p0 : 0;
+    if (tid == 0) {
+        const int old_P = *row_P;
+        if (step >= nd && old_P > 0) {
+            SummaryTotals T = totals[slot];
+            summary_fold_row(T, S, old_row, old_P, step - nd, step + 1);
+            totals[slot] = T;
+        }
+        *row_P = P > 0 ? P : 0;
+    }
+    if (P <= 0) {
+        for (int k = tid; k < nd; k += 256) row[k] = 0.0;
+        return;
+    }
+    const int pre = f.prepend[i] ? 1 : 0, T_blk = nd + pre;
+    const double2 *pred = (const double2 *)dyn + f.blk[i];            // [P][T_blk], the prepended column skipped below
+    const double2 *rec = (const double2 *)rv.pos + rv.slot_ped0[slot];
+    const int last_row = rv.slot_frames[slot] - 1;
+    const int64_t cols = rv.n_cols;
+    int G = 1;
+    while (G < P && G < WAVE) G <<= 1;
+    const int per_pass = 256 / G, g = tid / G, lane = tid & (G - 1);
+    for (int base = 0; base < nd; base += per_pass) {               // (uniform trip count: every lane takes part in the butterfly)
+        const int k = base + g;
+        double acc = 0.0;
+        if (k < nd) {
+            const int64_t gt_row = (int64_t)min(f_cur + 1 + k, last_row) * cols;
+            for (int p = lane; p < P; p += G) {
+                const double2 q = pred[(int64_t)p * T_blk + pre + k], w = rec[gt_row + p];
+                acc += sqrt(sum_sq_unfused(q.x - w.x, q.y - w.y));
+            }
+        }
+        for (int m = G >> 1; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, WAVE);
+        if (k < nd && lane == 0) row[k] = acc;
+    }
+}
+
+// One workgroup per slot, on request: thread t forms the terms of the ring's t-th oldest row under the slot's current
+// length L (its truncated horizon), thread 0 adds them to a COPY of the totals in step order and writes the
+// prediction-error keys of the slot's record in pinned memory.  Ring and totals are left as they are.
+__global__ void __launch_bounds__(256)
+k_loop_summary(SummaryShape S, const double *__restrict__ ring, const int32_t *__restrict__ ring_P,
+               const SummaryTotals *__restrict__ totals, const int32_t *__restrict__ steps, int n_slots, int num_samples,
+               fot_loop_summary *out)
+{
+    __shared__ SummaryTerms terms[FOT_MAX_NT];
+    const int slot = blockIdx.x, tid = threadIdx.x;
+    if (slot >= n_slots) return;
+    const int L = steps[slot], nd = S.n_dense;
+    const int first = L > nd ? L - nd : 0, n_tail = L - first;
+    for (int t = tid; t < n_tail; t += 256) {
+        const int i = first + t, r = i % nd;
+        terms[t] = summary_row_terms(S, ring + ((int64_t)slot * nd + r) * nd, ring_P[(int64_t)slot * nd + r], i, L);
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    SummaryTotals T = totals[slot];
+    for (int t = 0; t < n_tail; ++t) summary_add_terms(T, terms[t]);
+    double m[4];
+    summary_means(T, m);
+    fot_loop_summary *o = out + slot;
+    o->ade = m[0]; o->fde = m[1]; o->ade_per_agent = m[0]; o->fde_per_agent = m[1];
+    o->planning_ade = m[2]; o->planning_fde = m[3];
+    o->nll = __builtin_nan("");
+    o->pred_samples = T.std_count > 0 ? num_samples : 0;
+    o->ade_eval_count = (int32_t)T.std_count; o->planning_eval_count = (int32_t)T.plan_count;
+    o->nll_eval_count = 0;
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
 
@@ -2318,6 +2411,27 @@ int launch_loop_history(const fot_result *rec, int n_run, const int32_t *src, co
 {
     const int grid = hist && n_run > 0 ? n_run : 1;
     k_loop_history<<<grid, 256, 0, st>>>(rec, n_run, src, slot, hist, n_slots, n_total, done, seq);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_pred_error(ReplayView rv, const int32_t *slot_of, FrameDev f, const double *dyn, int n_run, int have_pred,
+                           int f_cur, int step, SummaryShape S, double *ring, int32_t *ring_P, SummaryTotals *totals,
+                           hipStream_t st)
+{
+    if (n_run <= 0) return 0;
+    if (S.n_dense < 1 || S.n_dense > FOT_MAX_NT || step < 0) return (int)hipErrorInvalidValue;
+    k_loop_pred_error<<<n_run, 256, 0, st>>>(rv, slot_of, f, dyn, n_run, have_pred, f_cur, step, S, ring, ring_P, totals);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_summary(SummaryShape S, const double *ring, const int32_t *ring_P, const SummaryTotals *totals,
+                        const int32_t *steps, int n_slots, int num_samples, fot_loop_summary *out, hipStream_t st)
+{
+    if (n_slots <= 0) return 0;
+    if (S.n_dense < 1 || S.n_dense > FOT_MAX_NT) return (int)hipErrorInvalidValue;
+    k_loop_summary<<<n_slots, 256, 0, st>>>(S, ring, ring_P, totals, steps, n_slots, num_samples, out);
     FOT_LAUNCH_CHECK();
     return 0;
 }

@@ -550,6 +550,22 @@ class BatchPlanner:
         o["n_steps"] = int(done)
         return o
 
+    LOOP_SUMMARY_DT = np.dtype(_abi.LoopSummary)
+
+    def loop_summary_enable(self, on: bool = True, num_samples: int = 1) -> None:
+        """``fot_loop_summary_enable``: the resident loop accumulates every slot's episode summary while it runs (between
+        ``loop_set_replay`` and the first ``loop_run``).  num_samples: what ``pred_samples`` reports (the reference's
+        constant-velocity predictor hands its metrics ``num_samples`` identical samples)."""
+        _abi.check(self._h, self._lib.fot_loop_summary_enable(self._h, int(bool(on)), int(num_samples)))
+
+    def loop_summaries(self) -> np.ndarray:
+        """``fot_loop_summaries``: one ``fot_loop_summary`` record per slot (``LOOP_SUMMARY_DT``) of the steps run so far;
+        the run may go on afterwards."""
+        n = int(self._replay_slots)
+        out = np.zeros(max(n, 1), dtype=self.LOOP_SUMMARY_DT)
+        _abi.check(self._h, self._lib.fot_loop_summaries(self._h, n, _addr(out)))
+        return out[:n]
+
     def _loop_frame(self, frame: dict):
         """fot_loop_frame from the dictionary ``loop_plan`` / ``loop_step`` take (+ the arrays it points into)."""
         f, keep = _abi.LoopFrame(), []
