@@ -6,6 +6,7 @@ from integrated_path_planning_amd.data_structures import EgoVehicleState
 from integrated_path_planning_amd.footprint import EgoFootprint
 from integrated_path_planning_amd.safety import SafetyMonitor, compute_safety_metrics_static
 from oracle import oracle as orc
+import prediction_common as pc
 from test_safety_oracle import load_cases, oracle_params
 
 pytestmark = pytest.mark.gpu
@@ -74,3 +75,176 @@ def test_empty_batch_and_bad_arguments():
     assert len(mon.metrics_batch(np.empty((0, 4)), [], [], 1.0, 0.2)) == 0
     with pytest.raises(ValueError):
         mon.metrics_batch([[0, 0, 0, 1]], [np.zeros((2, 2))], [np.zeros((3, 2))], 1.0, 0.2)
+
+
+# ---- k_safety at its decisions, against the NumPy restatement (tests/prediction_common.py) -----------------------------
+# Ties are exact in float64 on both sides: yaw = 0 (cos, sin = 1, 0), integer / 3-4-5 coordinates (exact sqrt), radii that
+# are sums of small dyadic fractions.  ER + PR = 1.25.
+ER, PR = 1.0, 0.25
+INF = float("inf")
+KEYS = ("min_distance", "ttc", "clearance", "clearance_ahead")
+
+
+def _dyadic_footprint(n):
+    """n circles half a metre apart, radius 1 (+ PR = 1.25): every centre exact at yaw 0."""
+    return EgoFootprint(offsets=(np.arange(n) - (n - 1) / 2.0) * 0.5, radius=1.0)
+
+
+def _restated(ego, pos, vel, foot=None, er=ER, pr=PR):
+    kw = {} if foot is None else dict(offsets=foot.offsets, footprint_radius=foot.radius)
+    return pc.safety_metrics(ego, pos, vel, er, pr, **kw)
+
+
+def _check_rows(got, egos, pos, vel, foot, label, er=ER, pr=PR):
+    assert len(got) == len(egos)
+    for i in range(len(egos)):
+        want = _restated(egos[i], pos[i], vel[i], foot, er, pr)
+        assert bool(got[i]["collision"]) == want["collision"], f"{label} ego {i} collision"
+        for k in KEYS:
+            np.testing.assert_allclose(float(got[i][k]), want[k], err_msg=f"{label} ego {i} {k}", **TOL)
+        assert not any(np.isnan(float(got[i][k])) for k in KEYS), f"{label} ego {i}"
+
+
+def _one(mon, ego, pos, vel, foot=None):
+    pos, vel = np.asarray(pos, dtype=np.float64).reshape(-1, 2), np.asarray(vel, dtype=np.float64).reshape(-1, 2)
+    got = mon.metrics_batch([ego], [pos], [vel], ER, PR)
+    _check_rows(got, [ego], [pos], [vel], foot, "scene")
+    want = _restated(ego, pos, vel, foot)
+    return got[0], want
+
+
+def test_pedestrian_exactly_at_the_combined_radius_and_one_ulp_inside():
+    mon = SafetyMonitor()
+    # 3-4-5 scaled by 1/4: distance exactly 1.25; the ego closes at 2 m/s
+    got, want = _one(mon, [0.0, 0.0, 0.0, 2.0], [[0.75, 1.0]], [[0.0, 0.0]])
+    for r in (got, want):
+        assert not bool(r["collision"]) and float(r["min_distance"]) == 1.25
+        assert float(r["clearance"]) == 0.0 and float(r["clearance_ahead"]) == 0.0 and float(r["ttc"]) == 0.0
+    # touching, moving apart: not closing, no time to collision
+    got, want = _one(mon, [0.0, 0.0, 0.0, 0.0], [[0.75, 1.0]], [[1.0, 1.0]])
+    for r in (got, want):
+        assert not bool(r["collision"]) and float(r["ttc"]) == INF and float(r["clearance"]) == 0.0
+    # on the axis at the radius, and one ulp inside it: a collision, and no time to collision from a pair already inside
+    inside = float(np.nextafter(1.25, 0.0))
+    for x, hit in ((1.25, False), (inside, True), (float(np.nextafter(1.25, 2.0)), False)):
+        got, want = _one(mon, [0.0, 0.0, 0.0, 2.0], [[x, 0.0]], [[0.0, 0.0]])
+        for r in (got, want):
+            assert bool(r["collision"]) == hit and float(r["min_distance"]) == x
+            assert float(r["clearance"]) == x - 1.25
+            assert (float(r["ttc"]) == INF) == hit
+    # the pair inside gives none, the pair outside still does
+    got, want = _one(mon, [0.0, 0.0, 0.0, 2.0], [[inside, 0.0], [5.0, 0.0]], [[0.0, 0.0], [0.0, 0.0]])
+    for r in (got, want):
+        assert bool(r["collision"]) and float(r["ttc"]) == (5.0 - 1.25) / (10.0 / (5.0 + 1e-8))
+
+
+def test_pedestrian_exactly_abeam_is_not_ahead():
+    mon = SafetyMonitor()
+    for side in (3.0, -3.0):
+        got, want = _one(mon, [2.0, 1.0, 0.0, 1.0], [[2.0, 1.0 + side]], [[0.0, 0.0]])
+        for r in (got, want):
+            assert float(r["clearance_ahead"]) == INF and float(r["clearance"]) == 1.75 and not bool(r["collision"])
+    # the smallest step forward is ahead, the smallest step back is not
+    for x, ahead in ((float(np.nextafter(2.0, 3.0)), True), (float(np.nextafter(2.0, 1.0)), False)):
+        got, want = _one(mon, [2.0, 1.0, 0.0, 1.0], [[x, 4.0]], [[0.0, 0.0]])
+        for r in (got, want):
+            assert (float(r["clearance_ahead"]) != INF) == ahead
+    # abeam and nearest, with one farther ahead: the forward clearance is the farther one's
+    got, want = _one(mon, [0.0, 0.0, 0.0, 1.0], [[0.0, 2.0], [3.0, 4.0]], [[0.0, 0.0], [0.0, 0.0]])
+    for r in (got, want):
+        assert float(r["clearance"]) == 0.75 and float(r["clearance_ahead"]) == 3.75
+    # with a footprint the test is still on the vehicle centre, not on a circle's
+    foot = _dyadic_footprint(8)
+    got, want = _one(SafetyMonitor(foot), [0.0, 0.0, 0.0, 1.0], [[0.0, 3.0]], [[0.0, 0.0]], foot)
+    for r in (got, want):
+        assert float(r["clearance_ahead"]) == INF and float(r["min_distance"]) == float(np.hypot(0.25, 3.0))
+
+
+def test_closing_speed_around_its_threshold():
+    mon = SafetyMonitor()
+    # a standing ego, a pedestrian 5 m ahead walking towards it at s: closing speed 5 s / (5 + 1e-8)
+    for s, closing in ((1e-5 * (1 + 1e-6), True), (1e-5 * (1 - 1e-6), False), (1e-5, False), (1e-5 * (1 + 1e-8), True)):
+        got, want = _one(mon, [0.0, 0.0, 0.0, 0.0], [[5.0, 0.0]], [[-s, 0.0]])
+        assert (5.0 * s / (5.0 + 1e-8) > 1e-5) == closing
+        for r in (got, want):
+            assert (float(r["ttc"]) != INF) == closing, s
+        if closing:
+            np.testing.assert_allclose(float(got["ttc"]), 3.75 / (5.0 * s / (5.0 + 1e-8)), rtol=1e-12)
+
+
+def test_pedestrian_on_a_circle_centre():
+    got, want = _one(SafetyMonitor(), [1.0, 2.0, 0.0, 3.0], [[1.0, 2.0]], [[0.5, 0.5]])
+    for r in (got, want):
+        assert float(r["min_distance"]) == 0.0 and bool(r["collision"]) and float(r["clearance"]) == -1.25
+        assert float(r["ttc"]) == INF and float(r["clearance_ahead"]) == INF
+    foot = _dyadic_footprint(4)
+    got, want = _one(SafetyMonitor(foot), [1.0, 2.0, 0.0, 3.0], [[1.75, 2.0], [9.0, 2.0]], [[0.0, 0.0], [0.0, 0.0]], foot)
+    for r in (got, want):
+        assert float(r["min_distance"]) == 0.0 and bool(r["collision"]) and float(r["clearance_ahead"]) == -1.25
+        assert np.isfinite(float(r["ttc"]))
+
+
+@pytest.mark.parametrize("n_circ", [1, 8])
+def test_pedestrian_counts_around_the_wave_stride(n_circ):
+    """63 / 64 / 65 / 1000 pedestrians per ego (n_circ x count pairs cross the 64-lane stride), an ego without any in
+    between, and the deciding pedestrian in the LAST slot: exactly at the combined radius of the last circle."""
+    rng = np.random.default_rng(40 + n_circ)
+    foot = None if n_circ == 1 else _dyadic_footprint(n_circ)
+    mon = SafetyMonitor(foot)
+    counts = [63, 0, 64, 65, 0, 1000, 1]
+    egos, pos, vel = [], [], []
+    for c in counts:
+        ego = np.array([float(rng.integers(-20, 20)), float(rng.integers(-20, 20)), 0.0, 2.0])
+        p = ego[:2] + np.column_stack([rng.uniform(-30, 30, c), rng.choice([-1.0, 1.0], c) * rng.uniform(4, 30, c)])
+        v = rng.normal(0, 1.2, (c, 2))
+        if c:
+            front = 0.0 if foot is None else float(foot.offsets[-1])
+            p[-1] = ego[:2] + [front + 0.75, 1.0]                     # 3-4-5 from the front circle: exactly 1.25
+            v[-1] = 0.0
+        egos.append(ego); pos.append(p); vel.append(v)
+    got = mon.metrics_batch(np.array(egos), pos, vel, ER, PR)
+    _check_rows(got, egos, pos, vel, foot, f"{n_circ} circles")
+    for i, c in enumerate(counts):
+        if c == 0:
+            assert not bool(got[i]["collision"])
+            assert all(float(got[i][k]) == INF for k in KEYS), i
+        else:
+            assert float(got[i]["min_distance"]) == 1.25 and float(got[i]["clearance"]) == 0.0, (i, c)
+            assert not bool(got[i]["collision"]) and float(got[i]["ttc"]) == 0.0, (i, c)
+    # the same egos one at a time
+    for i in range(len(counts)):
+        one = mon.metrics_batch([egos[i]], [pos[i]], [vel[i]], ER, PR)
+        assert one[0].tobytes() == got[i].tobytes(), i
+
+
+def test_use_footprint_on_a_handle_without_one():
+    rng = np.random.default_rng(9)
+    mon = SafetyMonitor()
+    egos = np.column_stack([rng.normal(0, 10, 5), rng.normal(0, 10, 5), rng.uniform(-3, 3, 5), rng.uniform(0, 8, 5)])
+    pos = [egos[i, :2] + rng.normal(0, 6, (40, 2)) for i in range(5)]
+    vel = [rng.normal(0, 1.2, (40, 2)) for _ in range(5)]
+    with_flag = mon.engine.safety_metrics(egos, pos, vel, ER, PR, use_footprint=True)
+    without = mon.engine.safety_metrics(egos, pos, vel, ER, PR, use_footprint=False)
+    assert with_flag.tobytes() == without.tobytes()
+    _check_rows(with_flag, egos, pos, vel, None, "flag without footprint")       # the centre circle of ego_radius
+
+
+def test_staged_batch_equals_small_batches_row_for_row():
+    """More pedestrians than the pinned small-call path holds (2 x 16 bytes x 48 000 > 1 MiB): the same rows as the same
+    egos sent fifty at a time, and the restatement on every tenth ego."""
+    rng = np.random.default_rng(17)
+    foot = _dyadic_footprint(4)
+    mon = SafetyMonitor(foot)
+    n, per = 600, 80
+    egos = np.column_stack([rng.normal(0, 30, n), rng.normal(0, 30, n), rng.uniform(-np.pi, np.pi, n), rng.uniform(0, 10, n)])
+    counts = rng.integers(per - 10, per + 11, n)
+    counts[[7, 300, 599]] = 0
+    pos = [egos[i, :2] + rng.normal(0, 8, (c, 2)) for i, c in enumerate(counts)]
+    vel = [rng.normal(0, 1.2, (c, 2)) for c in counts]
+    assert 2 * 16 * int(counts.sum()) > (1 << 20)
+    big = mon.metrics_batch(egos, pos, vel, ER, PR)
+    for a in range(0, n, 50):
+        part = mon.metrics_batch(egos[a:a + 50], pos[a:a + 50], vel[a:a + 50], ER, PR)
+        assert part.tobytes() == big[a:a + 50].tobytes(), a
+    idx = list(range(0, n, 10)) + [7, 300, 599]
+    _check_rows(big[idx], egos[idx], [pos[i] for i in idx], [vel[i] for i in idx], foot, "staged")
