@@ -11,8 +11,12 @@ N episodes that share planner parameters and reference path advance together, an
   fails, ONE more with every further escalation level of the failed episodes (row f2),
 * ONE nearest-point launch for the goal test,
 
-instead of N x (1 + up to 3 retries) sequential ``plan()`` calls.  All per-episode state (ego, state machine, planner
-caches, pedestrian frame) lives in arrays; the reference's scalar control flow is restated as masked array updates, and
+instead of N x (1 + up to 3 retries) sequential ``plan()`` calls -- behind ONE library call per lock step
+(``fot_loop_step``) on the library's own engine, as five separate calls where the prediction comes through the host (a
+sample source, a stand-in engine, ``fused=False``), or with the whole run inside the library (``resident=True``).  The
+forms end in one step record and one termination test.  All per-episode state (ego, state machine, planner
+caches, pedestrian frame) lives in arrays; the reference's scalar control flow is restated as masked array updates (the
+fail-safe transitions themselves once, in state_machine.py), and
 the histories are recorded as per-step arrays that turn into ``StepRecord`` objects only when read.  Pedestrians are
 replayed tracks -- the contract of the reference's ``ReplayPedestrianSource`` (src/simulation/replay_source.py:31-118);
 the Social-Force simulator and the Social-GAN network are outside SURVEY 8.  ``save_results`` writes
@@ -38,7 +42,7 @@ from .footprint import EgoFootprint
 from .planner import BatchPlanner
 from .prediction import PredictionResampler
 from . import _abi
-from .state_machine import FailSafeStateMachine, VehicleState
+from .state_machine import CONSTANTS, STATES, constants_of, sm_config, sm_update
 
 
 class ReplayPedestrians:
@@ -136,44 +140,26 @@ class StepRecord:
     processing_times: Dict[str, float]
 
 
-_STATES = (VehicleState.NORMAL, VehicleState.CAUTION, VehicleState.EMERGENCY)      # array code 0, 1, 2
-
-
 class _VectorStateMachine:
     """``FailSafeStateMachine`` (state_machine.py here, src/core/state_machine.py:29-278 in the reference) for all
-    episodes at once: the same transitions and planner configurations, as masked array updates.  Codes 0 / 1 / 2 =
+    episodes at once: the state of every episode in arrays, moved by ``sm_update`` / ``sm_config``.  Codes 0 / 1 / 2 =
     NORMAL / CAUTION / EMERGENCY."""
 
-    CONSTANTS = ("clr_caution", "clr_emergency", "trig_c", "trig_h", "env_decel", "env_standoff", "target", "c_accel",
-                 "c_speed_mult", "c_speed", "e_accel", "e_lat")
-
-    @staticmethod
-    def constants_of(config) -> Dict[str, float]:
-        """The machine's constants as the scalar class resolves them from one configuration."""
-        one = FailSafeStateMachine(config)                       # the scalar class resolves the configuration keys
-        c = config
-        k = dict(clr_caution=one.clearance_caution, clr_emergency=one.clearance_emergency,
-                 trig_c=one.trigger_clearance_caution, trig_h=one.trigger_time_headway,
-                 env_decel=one.envelope_decel, env_standoff=one.envelope_standoff, target=float(c.ego_target_speed))
-        k["c_accel"] = c.ego_max_accel * getattr(c, "state_machine_caution_accel_multiplier", 1.5)
-        k["c_speed_mult"] = getattr(c, "state_machine_caution_speed_multiplier", 0.8)
-        k["c_speed"] = c.ego_max_speed * k["c_speed_mult"]
-        k["e_accel"] = c.ego_max_accel * getattr(c, "state_machine_emergency_accel_multiplier", 3.0)
-        k["e_lat"] = getattr(c, "ego_max_lat_accel", 3.0) * getattr(c, "state_machine_emergency_lat_accel_multiplier", 2.0)
-        return k
+    CONSTANTS = CONSTANTS
+    constants_of = staticmethod(constants_of)
 
     def __init__(self, config, n: int, slot_scenario=None):
-        """config: one configuration (every constant a scalar, as before), or a sequence of configurations with
+        """config: one configuration (every constant a scalar), or a sequence of configurations with
         ``slot_scenario[e]`` = the configuration of episode e (every constant an array of n, one entry per episode)."""
         if slot_scenario is None:
-            for name, v in self.constants_of(config).items():
+            for name, v in constants_of(config).items():
                 setattr(self, name, v)
         else:
-            per = [self.constants_of(c) for c in config]
+            per = [constants_of(c) for c in config]
             scen = np.asarray(slot_scenario, np.int64)
             if scen.shape != (n,):
                 raise ValueError("slot_scenario: one configuration index per episode")
-            for name in self.CONSTANTS:
+            for name in CONSTANTS:
                 setattr(self, name, np.array([per[k][name] for k in scen], dtype=float))
         self.per_episode = slot_scenario is not None
         self.state = np.zeros(n, np.int64)
@@ -181,60 +167,25 @@ class _VectorStateMachine:
         self.clear = np.full(n, np.inf)                          # _last_clearance
         self.clear_ahead = np.full(n, np.inf)                    # _last_clearance_ahead
 
-    def _k(self, name: str, who):
-        """constant ``name`` for the episodes ``who`` (the scalar itself when there is one configuration)"""
-        v = getattr(self, name)
+    def _constants(self, who) -> Dict[str, Any]:
+        """the constants of the episodes ``who`` (the scalars themselves when there is one configuration)"""
         if not self.per_episode:
-            return v
+            return {name: getattr(self, name) for name in CONSTANTS}
         if who is None:
             raise ValueError("per-episode constants: say which episodes (who=)")
-        return v[who]
+        return {name: getattr(self, name)[who] for name in CONSTANTS}
 
     def config(self, state: np.ndarray, clear_ahead: np.ndarray, who=None):
         """_get_planner_config (:181-247) -> target speed, overrides [n, 4] (NaN = absent), max_stop (NaN = None).
         who: the episode of every entry (needed when the constants are per episode)."""
-        n = len(state)
-        env_decel, env_standoff, tgt0 = self._k("env_decel", who), self._k("env_standoff", who), self._k("target", who)
-        c_speed_mult = self._k("c_speed_mult", who)
-        fin = np.isfinite(clear_ahead)
-        has_env = fin & (env_decel > 0.0)
-        v_env = np.sqrt(2.0 * env_decel * np.maximum(np.where(fin, clear_ahead, 0.0) - env_standoff, 0.0))
-        stop_room = np.where(fin, np.maximum(np.where(fin, clear_ahead, 0.0) - 0.2, 0.05), np.nan)
-        target = np.full(n, tgt0)
-        ov = np.full((n, 4), np.nan)
-        stop = np.full(n, np.nan)
-        nm, ca, em = state == 0, state == 1, state == 2
-        target = np.where(nm & has_env & (v_env < tgt0), v_env, target)
-        t_ca = np.where(has_env, np.minimum(tgt0 * c_speed_mult, v_env), tgt0 * c_speed_mult)
-        target = np.where(ca, t_ca, target)
-        stop = np.where(ca & has_env & (v_env <= 0.0), stop_room, stop)
-        per = (lambda name, m: self._k(name, who)[m]) if self.per_episode else (lambda name, m: getattr(self, name))
-        ov[ca, 1], ov[ca, 0] = per("c_accel", ca), per("c_speed", ca)
-        target = np.where(em, 0.0, target)
-        ov[em, 1], ov[em, 3] = per("e_accel", em), per("e_lat", em)
-        stop = np.where(em & (env_decel > 0.0), stop_room, stop)
-        return target, ov, stop
+        return sm_config(state, clear_ahead, self._constants(who))[:3]
 
     def update(self, sel: np.ndarray, found: np.ndarray, clearance: np.ndarray, clearance_ahead: np.ndarray,
                speed: np.ndarray) -> None:
         """update() (:116-179) for the episodes ``sel`` (index array): observe the metrics, then the transitions."""
         self.clear[sel], self.clear_ahead[sel] = clearance, clearance_ahead
-        st, fl = self.state[sel], self.fails[sel]
-        trigger = self._k("trig_c", sel) + self._k("trig_h", sel) * np.maximum(speed, 0.0)
-        nm, ca, em = st == 0, st == 1, st == 2
-        new_st, new_fl = st.copy(), fl.copy()
-        a = nm & ~found
-        new_st[a] = 1; new_fl[a] = fl[a] + 1
-        b = nm & found & (trigger > 0.0) & (clearance < trigger)
-        new_st[b] = 1; new_fl[b] = 0
-        new_fl[nm & found & ~b] = 0
-        c1 = ca & found & (fl == 0)
-        new_st[c1 & (clearance > np.maximum(self._k("clr_caution", sel), trigger))] = 0
-        c2 = ca & ~c1 & ~found
-        new_st[c2] = 2; new_fl[c2] = fl[c2] + 1
-        new_fl[ca & ~c1 & found] = 0
-        new_st[em & found & (clearance > self._k("clr_emergency", sel))] = 1
-        self.state[sel], self.fails[sel] = new_st, new_fl
+        self.state[sel], self.fails[sel] = sm_update(self.state[sel], self.fails[sel], found, clearance, speed,
+                                                     self._constants(sel))
 
 
 class EpisodeHistory:
@@ -281,8 +232,6 @@ class _ResidentStep(dict):
         n = len(sel)
         counts = (loop.ped_off[sel + 1] - loop.ped_off[sel]).astype(np.int64)
         off = np.concatenate([[0], np.cumsum(counts)])
-        slot = np.full(len(loop.episodes), -1, np.int64)
-        slot[sel] = np.arange(n)
         rows = None if n == len(loop.episodes) else loop._rows_of(sel)
 
         def frame(which, f):
@@ -299,12 +248,13 @@ class _ResidentStep(dict):
             paths = {f: o["paths"][k, j][sel] for j, f in enumerate(_abi.PATH_FIELDS)}
         else:
             paths = {f: np.zeros((n, int(o["keep"][k].max()) if n else 0)) for f in _abi.PATH_FIELDS}
-        self.update(time=t, slot=slot, off=off, ego=o["ego"][k][sel], jerk=o["jerk"][k][sel],
-                    state=o["state"][k][sel].astype(np.int64), pos=frame("trajectories", o["frame"][k]),
-                    vel=frame("velocities", o["frame"][k]), pred=None, pred_src=pred_src, after=o["after"][k][sel],
-                    stats=o["stats"][k][sel].astype(np.int64), has_path=o["followed"][k][sel] > 0,
-                    keep=o["keep"][k][sel].astype(np.int64), cost=o["cost"][k][sel], paths=paths, t_pred=0.0,
-                    t_plan=o["t_plan"], sel=sel)
+        self.update(loop._step_record(
+            time=t, sel=sel, off=off, ego=o["ego"][k][sel], jerk=o["jerk"][k][sel],
+            state=o["state"][k][sel].astype(np.int64), pos=frame("trajectories", o["frame"][k]),
+            vel=frame("velocities", o["frame"][k]), pred=None, pred_src=pred_src, after=o["after"][k][sel],
+            stats=o["stats"][k][sel].astype(np.int64), has_path=o["followed"][k][sel] > 0,
+            keep=o["keep"][k][sel].astype(np.int64), cost=o["cost"][k][sel], paths=paths, t_pred=0.0,
+            t_plan=o["t_plan"]))
 
     def __missing__(self, key):
         if self._src is None:
@@ -413,7 +363,7 @@ def planner_kwargs_from_config(c, footprint=None) -> dict:
 
 
 def loop_config_from(c, k: Dict[str, float], max_replan: int) -> "_abi.LoopConfig":
-    """fot_loop_config of one configuration; k: ``_VectorStateMachine.constants_of(c)``."""
+    """fot_loop_config of one configuration; k: ``constants_of(c)``."""
     lc = _abi.LoopConfig()
     lc.dt, lc.target_speed, lc.max_accel = float(c.dt), float(k["target"]), float(c.ego_max_accel)
     dec = getattr(c, "ego_emergency_decel", None)
@@ -442,13 +392,13 @@ def scenario_key(c) -> tuple:
     fp = footprint_from_config(c)
     kw = planner_kwargs_from_config(c)
     kw.pop("footprint")
-    k = _VectorStateMachine.constants_of(c)
+    k = constants_of(c)
     dec = getattr(c, "ego_emergency_decel", None)
     return (tuple(sorted((n, float(v)) for n, v in kw.items())),
             tuple(float(v) for v in c.reference_waypoints_x), tuple(float(v) for v in c.reference_waypoints_y),
             None if fp is None else (tuple(float(o) for o in fp.offsets), float(fp.radius)),
             expand_static_obstacles(getattr(c, "static_obstacles", None), step=0.5).tobytes(),
-            tuple(float(k[n]) for n in _VectorStateMachine.CONSTANTS), None if dec is None else float(dec))
+            tuple(float(k[n]) for n in CONSTANTS), None if dec is None else float(dec))
 
 
 def merge_configs(configs: Sequence) -> tuple:
@@ -483,7 +433,8 @@ class BatchedClosedLoop:
     config.dt, frame 0 = time 0 before warm-up); ego_initial_states: optional per-episode [x, y, yaw, v, a].
 
     The state of all episodes lives in arrays (ego, state machine, planner caches, pedestrian frames); a lock step is a
-    fixed sequence of array operations and five libfot calls, whatever the number of episodes.  Histories are recorded
+    fixed sequence of array operations and one libfot call (five where the prediction comes through the host), whatever
+    the number of episodes.  Histories are recorded
     as per-step arrays and turned into ``StepRecord`` objects only when somebody reads them.
     """
 
@@ -511,7 +462,11 @@ class BatchedClosedLoop:
         loop runs -- the reference's ``calculate_aggregate_metrics``; ``aggregate_metrics()`` / ``save_summaries()`` read
         them, a few hundred bytes per episode whatever its length.  ``pred_samples`` reports the configuration's
         ``num_samples`` (trajectory_predictor's sample count, integrated_simulator.py:333: the constant-velocity
-        predictor hands the metrics that many identical samples)."""
+        predictor hands the metrics that many identical samples).
+        fused: True = the lock step behind one library call (fot_loop_step), False = five separate calls with the
+        prediction through the host, None = one call where the engine and the predictor allow it."""
+        if fused not in (None, False, True):
+            raise ValueError("fused: None (automatic), False (five calls per step) or True (one call per step)")
         self._resident = bool(resident)
         self._summaries = bool(summaries)
         if self._summaries and not self._resident:
@@ -529,8 +484,8 @@ class BatchedClosedLoop:
             config = distinct[0]
             if len(distinct) > 1:
                 if engine is not None or resampler is not None or sample_source is not None or fused not in (None, True):
-                    raise ValueError("the five-call and two-call steps, stand-in engines and sample sources take one "
-                                     "configuration: episodes of different configurations run through the one-call step "
+                    raise ValueError("the five-call step, stand-in engines and sample sources take one configuration: "
+                                     "episodes of different configurations run through the one-call step "
                                      "(fused=None / True) or resident=True")
                 self.scenarios, self.slot_scenario = distinct, slot
         self.config = config if not isinstance(config, dict) else _Cfg(config)
@@ -567,21 +522,17 @@ class BatchedClosedLoop:
             self.s_end = s_end[self.slot_scenario]
             self.scenario_static_points = [expand_static_obstacles(getattr(k, "static_obstacles", None), step=0.5)
                                            for k in self.scenarios]
-        # the step's device work in two calls, prediction resident in HBM (fot_loop_*): the constant-velocity predictor
-        # on the library's own engine; a sample source hands its samples over on the host, stand-in engines have no device
         self._device_samples = bool(device_samples)
         if self._device_samples and not (sample_source is not None and self.distribution_aware and engine is None and resampler is None):
             raise ValueError("device_samples needs a sample_source, distribution_aware_planning and the library's own engine")
-        can_fuse = (sample_source is None or self._device_samples) and resampler is None and hasattr(self.engine, "loop_plan")
-        if fused not in (None, False, True, "two-call"):
-            raise ValueError("fused: None (automatic), False, True or 'two-call'")
+        # the whole step behind ONE call (fot_loop_step: the episodes' state, the fail-safe machine and the retry loop live
+        # in the handle, the prediction stays in HBM): the constant-velocity predictor -- or samples in device memory -- on
+        # the library's own engine.  A sample source hands its samples over on the host and stand-in engines have no
+        # device: those run the step of five separate calls, which the tests also hold the one-call step against
+        can_fuse = (sample_source is None or self._device_samples) and resampler is None and hasattr(self.engine, "loop_step")
         if fused and not can_fuse:
             raise ValueError("fused=True needs the constant-velocity predictor on the library's own engine")
-        self._fused = can_fuse if fused is None else bool(fused)
-        # ... and, on the library's own engine, the whole step behind ONE call (fot_loop_step: the episodes' state, the
-        # fail-safe machine and the retry loop live in the handle); fused="two-call" keeps the round-3 form (two calls,
-        # the retry loop replayed here on arrays) -- the tests run both against each other and against the five-call step
-        self._native = self._fused and fused != "two-call" and hasattr(self.engine, "loop_step")
+        self._native = can_fuse if fused is None else bool(fused)
         if self._device_samples and not self._native:
             raise ValueError("device_samples runs through the one-call step only")
         if self.scenarios is not None and not self._native:
@@ -590,7 +541,7 @@ class BatchedClosedLoop:
         if self.scenarios is not None:
             for i, pts in enumerate(self.scenario_static_points):
                 self.engine.loop_set_scenario_static(i, pts)
-        elif self._fused:
+        elif self._native:
             self.engine.loop_set_static(self.static_obstacle_points)
         self.sgan_dt = 0.4                                            # integrated_simulator.py:323-327
         self.resampler = resampler if resampler is not None else PredictionResampler(
@@ -644,10 +595,10 @@ class BatchedClosedLoop:
         self._warmup()
         if self._native and self.scenarios is not None:
             self.engine.loop_begin_scenarios(
-                [loop_config_from(k, _VectorStateMachine.constants_of(k), self.MAX_REPLAN) for k in self.scenarios],
+                [loop_config_from(k, constants_of(k), self.MAX_REPLAN) for k in self.scenarios],
                 [fp_k is not None for fp_k in self.scenario_footprints], self.slot_scenario, self.ego)
         elif self._native:
-            self.engine.loop_begin(loop_config_from(c, _VectorStateMachine.constants_of(c), self.MAX_REPLAN), self.ego)
+            self.engine.loop_begin(loop_config_from(c, constants_of(c), self.MAX_REPLAN), self.ego)
         if self._resident:
             self.engine.loop_set_replay(
                 self.ped_off, self.n_frames, self._ped_all["trajectories"], self._ped_all["velocities"],
@@ -661,7 +612,7 @@ class BatchedClosedLoop:
     def close(self) -> None:
         """Release the libfot handle (streams, workspace) now rather than at garbage collection."""
         if self.engine is not None:
-            for s in self._steps:                                     # predictions of fused steps nobody has read yet
+            for s in self._steps:                                     # predictions of one-call steps nobody has read yet
                 if s["pred"] is None and s.get("pred_src") is not None and not isinstance(s["pred_src"][0], str):
                     s["pred"] = self._materialise_prediction(s["pred_src"], s["off"])
                     s["pred_src"] = None                              # (a distribution's samples: only while somebody asks)
@@ -685,15 +636,18 @@ class BatchedClosedLoop:
         self._arena.append(chunk)
         self._arena_steps += steps
 
-    def _history_block(self, k: int, n: int, kmax: int) -> np.ndarray:
-        """[15, n, kmax] block of lock step k in the arena."""
+    def _arena_rows(self, k: int, count: int) -> np.ndarray:
+        """The arena's rows of lock steps [k, k + count): as many of them as the chunk that holds step k has left."""
         while k >= self._arena_steps:
             self._grow_arena(64)
         for chunk in self._arena:
             if k < len(chunk):
-                return chunk[k, : len(_abi.PATH_FIELDS) * n * kmax].reshape(len(_abi.PATH_FIELDS), n, kmax)
+                return chunk[k: k + count]
             k -= len(chunk)
-        raise IndexError(k)
+
+    def _history_block(self, k: int, n: int, kmax: int) -> np.ndarray:
+        """[15, n, kmax] block of lock step k in the arena."""
+        return self._arena_rows(k, 1)[0, : len(_abi.PATH_FIELDS) * n * kmax].reshape(len(_abi.PATH_FIELDS), n, kmax)
 
     def _ped_frame(self, which: str, sel: np.ndarray) -> np.ndarray:
         """positions / velocities of the episodes ``sel`` at the current frame, concatenated [sum P, 2]."""
@@ -770,31 +724,24 @@ class BatchedClosedLoop:
         if self._resident:
             return self._run_resident(1)
         sel = np.flatnonzero(self.alive)
-        n = len(sel)
-        if n == 0:
+        if len(sel) == 0:
             return 0
-        c, sm = self.config, self.sm
         self._advance_pedestrians()                                   # 1. pedestrians + observer
-        counts = (self.ped_off[sel + 1] - self.ped_off[sel]).astype(np.int64)
-        off = np.concatenate([[0], np.cumsum(counts)])
+        off = np.concatenate([[0], np.cumsum(self.ped_off[sel + 1] - self.ped_off[sel])])
         pos = self._ped_frame("trajectories", sel)
         vel = self._ped_frame("velocities", sel)
-        st0 = sm.state[sel]
-        n_lvl = np.minimum(3 - st0, 1 + self.MAX_REPLAN)             # NORMAL -> CAUTION -> EMERGENCY, then no change
-        everyone = np.arange(n)
-        speed = self.ego[sel, 3].copy()
-        if self._native:
-            return self._step_native(sel, off, pos, vel)
-        if self._fused:
-            return self._step_fused(sel, off, counts, pos, vel, st0, n_lvl, everyone, speed)
+        form = self._step_native if self._native else self._step_five_calls
+        return form(sel, off, pos, vel)
+
+    def _step_five_calls(self, sel, off, pos, vel):
+        """Steps 2-5 in five separate libfot calls, the prediction and the retry loop on the host: what a sample source
+        or a stand-in engine runs, and what the tests hold the one-call step against."""
+        n = len(sel)
+        counts = np.diff(off)
         pred, prepend, t_pred, dist = self._predict(sel, off, pos)    # 2. prediction
         m = self._metrics(sel, off, pos, vel)                         # 3. planning cycle (:529-653)
         t0 = time.perf_counter()
-        clearance, clearance_ahead = m["clearance"].copy(), m["clearance_ahead"].copy()
-        self.last_clearance[sel] = clearance_ahead
-        # --- level 0 of every episode = the current state's configuration (issued from LAST step's clearance)
         # --- obstacles: the same static points for every request; one dynamic tensor per episode, shared by its levels
-        pts = self.static_obstacle_points
         if pred is None:                                              # not ready: current positions only (:495-498)
             dyn, t_len = pos[:, None, :], np.ones(n, np.int64)
         elif prepend.all():
@@ -828,64 +775,128 @@ class BatchedClosedLoop:
         else:
             d_xy = np.ascontiguousarray(dyn).reshape(-1, 2)
             d_off_ep = off[:-1] * T_alloc
+        dynamic = (d_xy, d_off_ep, np.stack([mode, n_smp, counts, t_len], axis=1))
+        return self._finish_step(sel, off, pos, vel, pred, t_pred, t0, dynamic, m["clearance"].copy(),
+                                 m["clearance_ahead"].copy())
 
-        def plan(who, state, clear_ahead, prev_s, chain):
-            """one plan() per entry: episode who[i] under the configuration of `state[i]`; chain[i]: nearest-point
-            cache handed over from the entry before (the next escalation level of the same episode)"""
-            tgt, ov, stop = sm.config(state, clear_ahead)
-            r = len(who)
-            ego = np.zeros(r, dtype=self.engine.EGO_DT)
-            for col, f in enumerate(("x", "y", "yaw", "v", "a")):
-                ego[f] = self.ego[sel, col][who]
-            ego["last_kappa"] = self.last_kappa[sel][who]
-            ego["has_prev_s"] = np.where(chain, 2, ~np.isnan(prev_s))
-            ego["prev_s"] = np.where(chain | np.isnan(prev_s), 0.0, prev_s)
-            s_xy = np.tile(pts, (r, 1)) if len(pts) else None
-            s_off = np.arange(r + 1, dtype=np.int64) * len(pts) if len(pts) else None
-            d_dims = np.stack([mode[who], n_smp[who], counts[who], t_len[who]], axis=1)
-            return self.engine.plan_arrays(ego, tgt, ov, stop, s_xy, s_off, d_xy, d_off_ep[who], d_dims)
+    def _plan_entries(self, sel, who, state, clear_ahead, prev_s, chain, dynamic):
+        """One plan() per entry: episode sel[who[i]] under the configuration of ``state[i]``; chain[i]: nearest-point
+        cache handed over from the entry before (the next escalation level of the same episode).  dynamic: the step's
+        obstacle tensor, every episode's offset into it and its dimensions."""
+        tgt, ov, stop = self.sm.config(state, clear_ahead)
+        r = len(who)
+        ego = np.zeros(r, dtype=self.engine.EGO_DT)
+        for col, f in enumerate(("x", "y", "yaw", "v", "a")):
+            ego[f] = self.ego[sel, col][who]
+        ego["last_kappa"] = self.last_kappa[sel][who]
+        ego["has_prev_s"] = np.where(chain, 2, ~np.isnan(prev_s))
+        ego["prev_s"] = np.where(chain | np.isnan(prev_s), 0.0, prev_s)
+        pts = self.static_obstacle_points
+        s_xy = np.tile(pts, (r, 1)) if len(pts) else None
+        s_off = np.arange(r + 1, dtype=np.int64) * len(pts) if len(pts) else None
+        d_xy, d_off_ep, d_dims = dynamic
+        return self.engine.plan_arrays(ego, tgt, ov, stop, s_xy, s_off, d_xy, d_off_ep[who], d_dims[who])
 
-        return self._finish_step(sel, off, pos, vel, pred, None, t_pred, t0, plan, st0, n_lvl, everyone, speed, clearance,
-                                 clearance_ahead, lambda new_ego: (lambda r=(self._metrics(sel, off, pos, vel), self.engine.nearest_s_arrays(
-                                     new_ego[:, 0], new_ego[:, 1], new_ego[:, 2], new_ego[:, 3], new_ego[:, 4],
-                                     self.goal_prev_s[sel])): r))
-
-    def _step_fused(self, sel, off, counts, pos, vel, st0, n_lvl, everyone, speed):
-        """Steps 2-5 with the device work in two libfot calls (fot_loop_plan / fot_loop_observe): prediction, current
-        metrics and the level-0 plans in one enqueue -- the prediction tensor is written and read in HBM --, the new
-        state's metrics and the goal test's nearest point in another.  The step record keeps the observer's two samples
-        instead of the prediction, which is computed again (same kernel, same numbers) if somebody reads it."""
-        sm = self.sm
+    def _finish_step(self, sel, off, pos, vel, pred, t_pred, t0, dynamic, clearance, clearance_ahead):
+        """The rest of the five-call step: the level-0 plans, replay of the retry loop, ego update, result metrics and
+        goal test.  dynamic: the obstacles as ``_plan_entries`` takes them; clearance, clearance_ahead: the current
+        metrics the fail-safe machine observes."""
+        c, sm = self.config, self.sm
         n = len(sel)
-        t0 = time.perf_counter()
-        frame, pred_src = self._loop_frame(sel, off, pos, vel)
-
-        def requests(who, state, clear_ahead, prev_s, chain):
-            # fot_loop_request is 15 eight-byte slots: x y yaw v a last_kappa prev_s | has_prev_s, pad | 4 overrides |
-            # target_speed max_stop_distance | episode, pad -- filled column-wise through a float64 / int32 view
-            tgt, ov, stop = sm.config(state, clear_ahead)
-            req = np.zeros(len(who), dtype=self.engine.LOOP_REQUEST_DT)
-            f64 = req.view(np.float64).reshape(len(who), 15)
-            i32 = req.view(np.int32).reshape(len(who), 30)
-            f64[:, 0:5] = self.ego[sel[who]]
-            f64[:, 5] = self.last_kappa[sel[who]]
-            f64[:, 6] = np.where(chain | np.isnan(prev_s), 0.0, prev_s)
-            i32[:, 14] = np.where(chain, 2, ~np.isnan(prev_s))
-            f64[:, 8:12] = ov
-            f64[:, 12], f64[:, 13] = tgt, stop
-            i32[:, 28] = who
-            return req
-
-        # (view=True: the records are read -- the selected paths copied into the history arena -- before the next call)
-        rec0, m = self.engine.loop_plan(requests(everyone, st0, sm.clear_ahead[sel], self.prev_s[sel], np.zeros(n, bool)),
-                                        frame, view=True)
-        t_pred = 0.0                                                  # (inside the one call: not separable)
-        clearance, clearance_ahead = m["clearance"].copy(), m["clearance_ahead"].copy()
+        everyone = np.arange(n)
         self.last_clearance[sel] = clearance_ahead
-        plan = lambda *a: self.engine.loop_plan(requests(*a), view=True)[0]
-        return self._finish_step(sel, off, pos, vel, None, pred_src, t_pred, t0, plan, st0, n_lvl, everyone, speed,
-                                 clearance, clearance_ahead, lambda new_ego: self.engine.loop_observe_begin(new_ego, self.goal_prev_s[sel]),
-                                 first=rec0)
+        st0 = sm.state[sel]
+        n_lvl = np.minimum(3 - st0, 1 + self.MAX_REPLAN)             # NORMAL -> CAUTION -> EMERGENCY, then no change
+        speed = self.ego[sel, 3].copy()
+        # --- level 0 of every episode = the current state's configuration (issued from LAST step's clearance)
+        rec = self._plan_entries(sel, everyone, st0, sm.clear_ahead[sel], self.prev_s[sel], np.zeros(n, bool), dynamic)
+        # --- replay of the retry loop (:576-653).  Episodes whose first attempt failed get every further escalation
+        #     level they can reach planned in ONE more launch (the configurations update(False, ...) would issue on THIS
+        #     step's metrics, nearest-point cache chained from attempt to attempt); the control flow is then replayed.
+        found_all = rec["status"] == 0
+        cur = everyone.copy()                                         # record of each episode's current attempt
+        path_rec = np.full(n, -1, np.int64)
+        failed = np.flatnonzero(~found_all[:n] & (n_lvl > 1))
+        if len(failed):
+            extra = n_lvl[failed] - 1
+            who = np.repeat(failed, extra)
+            base1 = np.concatenate([[0], np.cumsum(extra)])[:-1]
+            lvl = 1 + np.arange(len(who)) - np.repeat(base1, extra)
+            nps0 = rec["new_prev_s"][who]
+            rec = np.concatenate([rec, self._plan_entries(sel, who, st0[who] + lvl, clearance_ahead[who],
+                                                          np.where(np.isnan(nps0), self.prev_s[sel][who], nps0), lvl > 1,
+                                                          dynamic)])
+            found_all = rec["status"] == 0
+            next_rec = np.full(n, -1, np.int64)                       # record of level 1 of each failed episode
+            next_rec[failed] = n + base1
+        t_plan = (time.perf_counter() - t0) / n
+
+        def adopt(which, r):                                          # planner state after a plan() call
+            nps = rec["new_prev_s"][r]
+            e = sel[which]
+            self.prev_s[e] = np.where(np.isnan(nps), self.prev_s[e], nps)
+            self.last_stats[e] = np.where(rec["stats_valid"][r][:, None] != 0, rec["stats"][r], -1)
+            ok = found_all[r]
+            self.last_kappa[e[ok]] = rec["new_last_kappa"][r[ok]]
+            path_rec[which[ok]] = r[ok]
+
+        adopt(everyone, cur)
+        found = found_all[cur]
+        issued = st0.copy()                                           # state of the configuration the attempt ran under
+        sm.update(sel, found, clearance, clearance_ahead, speed)
+        retries = np.zeros(n, np.int64)
+        active = ~found & (sm.state[sel] != issued) & (retries < self.MAX_REPLAN) & (retries + 1 < n_lvl)
+        while active.any():
+            w = np.flatnonzero(active)
+            cur[w] = np.where(retries[w] == 0, next_rec[w], cur[w] + 1)
+            retries[w] += 1
+            adopt(w, cur[w])
+            ok = found_all[cur[w]]
+            found[w[ok]] = True
+            issued[w] = sm.state[sel[w]]
+            again = w[~ok]
+            if len(again):
+                sm.update(sel[again], np.zeros(len(again), bool), clearance[again], clearance_ahead[again], speed[again])
+            active = np.zeros(n, bool)
+            active[again] = (sm.state[sel[again]] != issued[again]) & (retries[again] < self.MAX_REPLAN) & \
+                            (retries[again] + 1 < n_lvl[again])
+        # --- 4. ego update (:655-676) or emergency stop (:749-802)
+        old_a = self.ego[sel, 4].copy()
+        keep = np.where(path_rec >= 0, rec["n_keep"][np.maximum(path_rec, 0)], 0)
+        follow = keep >= 2
+        new_ego = self.ego[sel].copy()
+        jerk = np.zeros(n)
+        if follow.any():
+            r = path_rec[follow]
+            for col, f in enumerate(("x", "y", "yaw", "v", "a")):
+                new_ego[follow, col] = rec[f][r, 1]
+            jerk[follow] = (new_ego[follow, 4] - old_a[follow]) / self.dt
+        brake = ~follow
+        if brake.any():
+            x, y, yaw, v = (self.ego[sel, k][brake] for k in range(4))
+            nx, ny, nv, na = emergency_stop(x, y, yaw, v, self.last_clearance[sel][brake], c.dt, c.ego_max_accel,
+                                            getattr(c, "ego_emergency_decel", None))
+            new_ego[brake, 0], new_ego[brake, 1] = nx, ny
+            new_ego[brake, 3], new_ego[brake, 4] = nv, na
+            jerk[brake] = (na - old_a[brake]) / c.dt
+            self.last_kappa[sel[brake]] = 0.0                         # planner.reset_ego_curvature()
+        self.ego[sel], self.jerk[sel] = new_ego, jerk
+        # --- 5. result metrics on the new ego state, goal test (:864-883)
+        after = self._metrics(sel, off, pos, vel)
+        s_now = self.engine.nearest_s_arrays(new_ego[:, 0], new_ego[:, 1], new_ego[:, 2], new_ego[:, 3], new_ego[:, 4],
+                                             self.goal_prev_s[sel])
+        self.goal_prev_s[sel] = s_now
+        chosen = np.maximum(path_rec, 0)
+        kmax = int(keep.max()) if n else 0
+        if hasattr(self.engine, "gather_paths"):                      # one dense block, copied by the library
+            block = self.engine.gather_paths(rec, chosen, kmax, out=self._history_block(len(self._steps), n, kmax))
+            paths = {f: block[j] for j, f in enumerate(_abi.PATH_FIELDS)}
+        else:
+            paths = {f: rec[f][chosen, :kmax].copy() for f in _abi.PATH_FIELDS}
+        return self._close_step(
+            s_now, sel=sel, off=off, ego=new_ego, jerk=jerk, state=sm.state[sel].copy(), pos=pos, vel=vel, pred=pred,
+            pred_src=None, after=after, stats=self.last_stats[sel].copy(), has_path=path_rec >= 0, keep=keep,
+            cost=rec["cost"][chosen], paths=paths, t_pred=t_pred, t_plan=t_plan)
 
     def _best_sample(self, dist: np.ndarray, off: np.ndarray) -> np.ndarray:
         """predict_single_best (trajectory_predictor.py:340-352) per episode: the sample closest to the sample mean over
@@ -898,7 +909,7 @@ class BatchedClosedLoop:
         return dist[np.repeat(best, off[1:] - off[:-1]), np.arange(dist.shape[1])]
 
     def _materialise_prediction(self, pred_src, off):
-        """The prediction a fused step left in HBM, computed again for whoever reads the step's record (same kernels,
+        """The prediction a one-call step left in HBM, computed again for whoever reads the step's record (same kernels,
         same numbers): the constant-velocity tracks, or the best sample of the distribution's raw samples."""
         if isinstance(pred_src[0], str):                              # ("dist", raw samples in HBM, observations, staleness)
             _, raw, o32, stale = pred_src
@@ -909,7 +920,7 @@ class BatchedClosedLoop:
         return self.resampler.predict_cv(o32, staleness=stale, float32_observations=True)
 
     def _loop_frame(self, sel, off, pos, vel):
-        """The frame of fot_loop_plan / fot_loop_step for the running episodes: pedestrians, the observer's last two
+        """The frame of fot_loop_step for the running episodes: pedestrians, the observer's last two
         samples, per episode whether the current positions lead the prediction (:503-511), staleness."""
         frame = dict(ped_off=off, ped_pos=pos, ped_vel=vel, ego=self.ego[sel, :4], ego_radius=self.ego_radius,
                      ped_radius=self.ped_radius, use_footprint=self.footprint is not None)
@@ -969,130 +980,36 @@ class BatchedClosedLoop:
         self.last_stats[sel] = o["stats"]
         chosen = np.maximum(path_rec, 0)
         kmax = int(keep.max()) if n else 0
-        slot = np.full(len(self.episodes), -1, np.int64)
-        slot[sel] = np.arange(n)
         block = self.engine.gather_paths(rec, chosen, kmax, out=self._history_block(len(self._steps), n, kmax))
         paths = {f: block[j] for j, f in enumerate(_abi.PATH_FIELDS)}
-        after, s_now = o["after"], o["s_now"]
-        self._steps.append(dict(
-            time=self.time, slot=slot, off=off, ego=new_ego, jerk=o["jerk"], state=self.sm.state[sel].copy(), pos=pos, vel=vel,
-            pred=None, pred_src=pred_src, after=after, stats=self.last_stats[sel].copy(), has_path=path_rec >= 0, keep=keep,
-            cost=o["cost"], paths=paths, t_pred=0.0, t_plan=t_plan, sel=sel))
-        collided = after["collision"] != 0
-        at_goal = (self.s_end if self.scenarios is None else self.s_end[sel]) - s_now < 2.0
-        self.step_counts[sel] += 1
-        self.termination[sel[at_goal & ~collided]] = 2
-        self.termination[sel[collided]] = 1
-        self.alive[sel[collided | at_goal]] = False
-        self.time += self.dt
-        return n
+        return self._close_step(
+            o["s_now"], sel=sel, off=off, ego=new_ego, jerk=o["jerk"], state=self.sm.state[sel].copy(), pos=pos, vel=vel,
+            pred=None, pred_src=pred_src, after=o["after"], stats=self.last_stats[sel].copy(), has_path=path_rec >= 0,
+            keep=keep, cost=o["cost"], paths=paths, t_pred=0.0, t_plan=t_plan)
 
-    def _finish_step(self, sel, off, pos, vel, pred, pred_src, t_pred, t0, plan, st0, n_lvl, everyone, speed, clearance,
-                     clearance_ahead, observe, first=None):
-        """The rest of a lock step, whoever planned: replay of the retry loop, ego update, result metrics, history.
-        ``plan(who, state, clear_ahead, prev_s, chain)`` -> records; ``observe(new_ego)`` -> a callable that returns
-        (metrics, nearest s) -- the fused step enqueues the two launches and collects them behind the bookkeeping;
-        ``first``: the records of level 0 when they were planned already (with the frame's prediction and metrics)."""
-        c, sm = self.config, self.sm
-        n = len(sel)
-        rec = first if first is not None else plan(everyone, st0, sm.clear_ahead[sel], self.prev_s[sel], np.zeros(n, bool))
-        # --- replay of the retry loop (:576-653).  Episodes whose first attempt failed get every further escalation
-        #     level they can reach planned in ONE more launch (the configurations update(False, ...) would issue on THIS
-        #     step's metrics, nearest-point cache chained from attempt to attempt); the control flow is then replayed.
-        found_all = rec["status"] == 0
-        cur = everyone.copy()                                         # record of each episode's current attempt
-        path_rec = np.full(n, -1, np.int64)
-        failed = np.flatnonzero(~found_all[:n] & (n_lvl > 1))
-        if len(failed):
-            extra = n_lvl[failed] - 1
-            who = np.repeat(failed, extra)
-            base1 = np.concatenate([[0], np.cumsum(extra)])[:-1]
-            lvl = 1 + np.arange(len(who)) - np.repeat(base1, extra)
-            nps0 = rec["new_prev_s"][who]
-            head = rec.copy()                                         # (a view of the handle's block when fused)
-            rec = np.concatenate([head, plan(who, st0[who] + lvl, clearance_ahead[who],
-                                             np.where(np.isnan(nps0), self.prev_s[sel][who], nps0), lvl > 1)])
-            found_all = rec["status"] == 0
-            next_rec = np.full(n, -1, np.int64)                       # record of level 1 of each failed episode
-            next_rec[failed] = n + base1
-        t_plan = (time.perf_counter() - t0) / n
-
-        def adopt(which, r):                                          # planner state after a plan() call
-            nps = rec["new_prev_s"][r]
-            e = sel[which]
-            self.prev_s[e] = np.where(np.isnan(nps), self.prev_s[e], nps)
-            self.last_stats[e] = np.where(rec["stats_valid"][r][:, None] != 0, rec["stats"][r], -1)
-            ok = found_all[r]
-            self.last_kappa[e[ok]] = rec["new_last_kappa"][r[ok]]
-            path_rec[which[ok]] = r[ok]
-
-        adopt(everyone, cur)
-        found = found_all[cur]
-        issued = st0.copy()                                           # state of the configuration the attempt ran under
-        sm.update(sel, found, clearance, clearance_ahead, speed)
-        retries = np.zeros(n, np.int64)
-        active = ~found & (sm.state[sel] != issued) & (retries < self.MAX_REPLAN) & (retries + 1 < n_lvl)
-        while active.any():
-            w = np.flatnonzero(active)
-            cur[w] = np.where(retries[w] == 0, next_rec[w], cur[w] + 1)
-            retries[w] += 1
-            adopt(w, cur[w])
-            ok = found_all[cur[w]]
-            found[w[ok]] = True
-            issued[w] = sm.state[sel[w]]
-            again = w[~ok]
-            if len(again):
-                sm.update(sel[again], np.zeros(len(again), bool), clearance[again], clearance_ahead[again], speed[again])
-            active = np.zeros(n, bool)
-            active[again] = (sm.state[sel[again]] != issued[again]) & (retries[again] < self.MAX_REPLAN) & \
-                            (retries[again] + 1 < n_lvl[again])
-        # --- 4. ego update (:655-676) or emergency stop (:749-802)
-        old_a = self.ego[sel, 4].copy()
-        keep = np.where(path_rec >= 0, rec["n_keep"][np.maximum(path_rec, 0)], 0)
-        follow = keep >= 2
-        new_ego = self.ego[sel].copy()
-        jerk = np.zeros(n)
-        if follow.any():
-            r = path_rec[follow]
-            for col, f in enumerate(("x", "y", "yaw", "v", "a")):
-                new_ego[follow, col] = rec[f][r, 1]
-            jerk[follow] = (new_ego[follow, 4] - old_a[follow]) / self.dt
-        brake = ~follow
-        if brake.any():
-            x, y, yaw, v = (self.ego[sel, k][brake] for k in range(4))
-            nx, ny, nv, na = emergency_stop(x, y, yaw, v, self.last_clearance[sel][brake], c.dt, c.ego_max_accel,
-                                            getattr(c, "ego_emergency_decel", None))
-            new_ego[brake, 0], new_ego[brake, 1] = nx, ny
-            new_ego[brake, 3], new_ego[brake, 4] = nv, na
-            jerk[brake] = (na - old_a[brake]) / c.dt
-            self.last_kappa[sel[brake]] = 0.0                         # planner.reset_ego_curvature()
-        self.ego[sel], self.jerk[sel] = new_ego, jerk
-        # --- 5. result metrics on the new ego state, goal test (:864-883)
-        pending = observe(new_ego)                                    # enqueued; collected below, behind the bookkeeping
-        chosen = np.maximum(path_rec, 0)
-        kmax = int(keep.max()) if n else 0
+    def _step_record(self, *, time, sel, off, ego, jerk, state, pos, vel, pred, pred_src, after, stats, has_path, keep,
+                     cost, paths, t_pred, t_plan) -> dict:
+        """What the history keeps of one lock step, one row per episode of ``sel`` (``slot``: episode -> row, -1 = it
+        did not run); pos / vel / pred: the pedestrians of those episodes one after the other, episode i at
+        off[i]:off[i + 1].  pred_src: what a prediction that stayed in HBM is computed again from when somebody reads it."""
         slot = np.full(len(self.episodes), -1, np.int64)
-        slot[sel] = everyone
-        if hasattr(self.engine, "gather_paths"):                      # one dense block, copied by the library
-            block = self.engine.gather_paths(rec, chosen, kmax, out=self._history_block(len(self._steps), n, kmax))
-            paths = {f: block[j] for j, f in enumerate(_abi.PATH_FIELDS)}
-        else:
-            paths = {f: rec[f][chosen, :kmax].copy() for f in _abi.PATH_FIELDS}
-        after, s_now = pending()
-        self.goal_prev_s[sel] = s_now
-        self._steps.append(dict(
-            time=self.time, slot=slot, off=off, ego=new_ego, jerk=jerk, state=sm.state[sel].copy(), pos=pos, vel=vel,
-            pred=pred, pred_src=pred_src, after=after, stats=self.last_stats[sel].copy(), has_path=path_rec >= 0, keep=keep,
-            cost=rec["cost"][chosen], paths=paths,
-            t_pred=t_pred, t_plan=t_plan, sel=sel))
-        collided = after["collision"] != 0
-        at_goal = self.s_end - s_now < 2.0
+        slot[sel] = np.arange(len(sel))
+        return dict(time=time, slot=slot, off=off, ego=ego, jerk=jerk, state=state, pos=pos, vel=vel, pred=pred,
+                    pred_src=pred_src, after=after, stats=stats, has_path=has_path, keep=keep, cost=cost, paths=paths,
+                    t_pred=t_pred, t_plan=t_plan, sel=sel)
+
+    def _close_step(self, s_now, *, sel, **arrays) -> int:
+        """The end of a lock step, whichever form ran it: its record into the history, then termination
+        (integrated_simulator.py:864-883) -- collision first, then the goal within GOAL_DISTANCE of the path's end."""
+        self._steps.append(self._step_record(time=self.time, sel=sel, **arrays))
+        collided = arrays["after"]["collision"] != 0
+        at_goal = (self.s_end if self.scenarios is None else self.s_end[sel]) - s_now < self.GOAL_DISTANCE
         self.step_counts[sel] += 1
         self.termination[sel[at_goal & ~collided]] = 2
         self.termination[sel[collided]] = 1
         self.alive[sel[collided | at_goal]] = False
         self.time += self.dt
-        return n
+        return len(sel)
 
     def _record(self, k: int, e: int) -> StepRecord:
         """StepRecord of episode e at lock step k, from the step's arrays."""
@@ -1100,7 +1017,7 @@ class BatchedClosedLoop:
         i = int(s["slot"][e])
         lo, hi = int(s["off"][i]), int(s["off"][i + 1])
         ego = EgoVehicleState(*(float(v) for v in s["ego"][i]), jerk=float(s["jerk"][i]), timestamp=s["time"] + self.dt)
-        ego.state = _STATES[int(s["state"][i])]
+        ego.state = STATES[int(s["state"][i])]
         path = None
         if s["has_path"][i]:
             kn = int(s["keep"][i])
@@ -1112,7 +1029,7 @@ class BatchedClosedLoop:
         if s["stats"][i, 0] >= 0:
             m["n_collision_rejected"] = int(s["stats"][i, _abi.ST_COLLISION])
         p = self.peds[e]
-        if s["pred"] is None and s.get("pred_src") is not None:       # fused step: the prediction stayed in HBM
+        if s["pred"] is None and s.get("pred_src") is not None:       # one-call step: the prediction stayed in HBM
             s["pred"] = self._materialise_prediction(s["pred_src"], s["off"])
             s["pred_src"] = None
         return StepRecord(s["time"], ego, s["pos"][lo:hi].copy(), s["vel"][lo:hi].copy(), p.goals.copy(),
@@ -1124,14 +1041,7 @@ class BatchedClosedLoop:
         chunk; the loop's arrays follow the handle after every call.  Returns how many episodes ran the first step."""
         first, left = None, int(n_steps)
         while left > 0 and self.alive.any():
-            pos, paths_out = len(self._steps), None
-            while keep_paths and pos >= self._arena_steps:
-                self._grow_arena(64)
-            for chunk in self._arena if keep_paths else ():
-                if pos < len(chunk):
-                    paths_out = chunk[pos: pos + left]
-                    break
-                pos -= len(chunk)
+            paths_out = self._arena_rows(len(self._steps), left) if keep_paths else None
             ask = len(paths_out) if keep_paths else left
             t0 = time.perf_counter()
             o = self.engine.loop_run(ask, keep_paths=keep_paths, paths_out=paths_out)

@@ -1,9 +1,10 @@
 """Fail-safe state machine and the escalate-and-retry planning cycle.
 
-``FailSafeStateMachine`` restates the reference's scalar control logic (src/core/state_machine.py:29-278):
-NORMAL / CAUTION / EMERGENCY, the planner configuration each state issues, the transitions on plan success,
-failure and clearance.  ``SpeculativePlanningCycle`` restates ``IntegratedSimulator._execute_planning_cycle``
-(integrated_simulator.py:529-653) the MI355X way: the configurations of every escalation level that the loop
+``sm_update`` / ``sm_config`` restate the reference's control logic (src/core/state_machine.py:29-278) over arrays of
+episodes: NORMAL / CAUTION / EMERGENCY, the transitions on plan success, failure and clearance, the planner
+configuration each state issues.  ``FailSafeStateMachine`` is the reference's class as a view of one episode of them;
+the closed-loop driver's vector machine calls them for all episodes at once.  ``SpeculativePlanningCycle`` restates
+``IntegratedSimulator._execute_planning_cycle`` (integrated_simulator.py:529-653) the MI355X way: the configurations of every escalation level that the loop
 could reach are known before planning (they depend only on the state and on the current safety metrics), so
 all of them are planned in ONE launch -- same ego, same obstacles, chained nearest-point cache -- and the
 reference's control flow is then replayed on the results.  A failing step costs one launch instead of up to four
@@ -12,7 +13,6 @@ sequential ``plan()`` calls.
 from __future__ import annotations
 
 import copy
-import math
 from dataclasses import dataclass
 from enum import Enum, auto
 from typing import Any, Dict, List, Optional, Tuple
@@ -37,101 +37,121 @@ class StateMachineOutput:
     max_stop_distance: Optional[float] = None
 
 
+STATES = tuple(VehicleState)                                   # array code 0, 1, 2 = NORMAL, CAUTION, EMERGENCY
+OVERRIDES = ("max_speed", "max_accel", "max_curvature", "max_lat_accel")      # the columns of sm_config's overrides
+
+# the machine's constants, under the names of fot_loop_config's fields in short
+CONSTANTS = ("clr_caution", "clr_emergency", "trig_c", "trig_h", "env_decel", "env_standoff", "target", "c_accel",
+             "c_speed_mult", "c_speed", "e_accel", "e_lat")
+
+
+def constants_of(config) -> Dict[str, float]:
+    """The machine's constants as the reference resolves them from one configuration read with getattr
+    (state_machine.py:32-98, :181-247)."""
+    c = config
+    fp_mode = getattr(c, "ego_footprint", None)
+    if fp_mode is not None and fp_mode != "circle":
+        seg = c.vehicle_length / c.ego_footprint_n_circles                          # footprint.py:37-39
+        ego_radius = float(np.hypot(seg / 2, c.vehicle_width / 2))
+    else:
+        ego_radius = getattr(c, "ego_radius", 1.0)
+    combined = ego_radius + getattr(c, "ped_radius", 0.2)
+    rc = getattr(c, "state_machine_recover_clearance_caution", None)
+    re = getattr(c, "state_machine_recover_clearance_emergency", None)
+    k = dict(clr_caution=rc if rc is not None else getattr(c, "state_machine_safe_distance_caution", 2.0) - combined,
+             clr_emergency=re if re is not None else getattr(c, "state_machine_safe_distance_emergency", 3.0) - combined,
+             trig_c=getattr(c, "state_machine_trigger_clearance_caution", 0.0),
+             trig_h=getattr(c, "state_machine_trigger_time_headway", 0.0),
+             env_decel=getattr(c, "state_machine_envelope_decel", 0.0),
+             env_standoff=getattr(c, "state_machine_envelope_standoff", 0.5), target=float(c.ego_target_speed))
+    k["c_accel"] = c.ego_max_accel * getattr(c, "state_machine_caution_accel_multiplier", 1.5)
+    k["c_speed_mult"] = getattr(c, "state_machine_caution_speed_multiplier", 0.8)
+    k["c_speed"] = c.ego_max_speed * k["c_speed_mult"]
+    k["e_accel"] = c.ego_max_accel * getattr(c, "state_machine_emergency_accel_multiplier", 3.0)
+    k["e_lat"] = getattr(c, "ego_max_lat_accel", 3.0) * getattr(c, "state_machine_emergency_lat_accel_multiplier", 2.0)
+    return k
+
+
+# The transitions and the planner configurations, once: over arrays with one entry per episode (state codes as in
+# STATES; every constant of ``k`` a scalar or an array of the same shape).  They read side by side with sm_update /
+# sm_config of csrc/fot_host.cpp, which fot_loop_step and fot_loop_run run.
+
+def sm_update(state, fails, found, clearance, speed, k):
+    """The transition of update() (state_machine.py:116-179) -> new state, new count of consecutive failures."""
+    trigger = k["trig_c"] + k["trig_h"] * np.maximum(speed, 0.0)
+    nm, ca, em = state == 0, state == 1, state == 2
+    preventive = found & (trigger > 0.0) & (clearance < trigger)
+    recovered = found & (fails == 0) & (clearance > np.maximum(k["clr_caution"], trigger))
+    new_state = np.where(nm & (~found | preventive), 1, state)
+    new_state = np.where(ca & ~found, 2, np.where(ca & recovered, 0, new_state))
+    new_state = np.where(em & found & (clearance > k["clr_emergency"]), 1, new_state)
+    return new_state, np.where(em, fails, np.where(found, 0, fails + 1))
+
+
+def sm_config(state, clear_ahead, k):
+    """_get_planner_config (:181-247) on the clearance ahead the machine last observed -> target speed, the overrides
+    [..., 4] in the order of OVERRIDES (NaN = absent), the stop room (NaN = None), and whether the target speed is an
+    override (False: the configuration's own, which the reference issues as None)."""
+    fin = np.isfinite(clear_ahead)
+    has_env = fin & (k["env_decel"] > 0.0)
+    ahead = np.where(fin, clear_ahead, 0.0)
+    v_env = np.sqrt(2.0 * k["env_decel"] * np.maximum(ahead - k["env_standoff"], 0.0))      # _envelope_speed (:249-264)
+    stop_room = np.where(fin, np.maximum(ahead - 0.2, 0.05), np.nan)             # _stop_room_to_pedestrian (:266-278)
+    nm, ca, em = state == 0, state == 1, state == 2
+    slowed = nm & has_env & (v_env < k["target"])
+    t_ca = k["target"] * k["c_speed_mult"]
+    target = np.where(slowed, v_env, k["target"])
+    target = np.where(ca, np.where(has_env, np.minimum(t_ca, v_env), t_ca), target)
+    target = np.where(em, 0.0, target)
+    stop = np.where(ca & has_env & (v_env <= 0.0), stop_room, np.nan)
+    stop = np.where(em & (k["env_decel"] > 0.0), stop_room, stop)
+    absent = np.full(np.shape(state), np.nan)
+    ov = np.stack([np.where(ca, k["c_speed"], absent), np.where(ca, k["c_accel"], np.where(em, k["e_accel"], absent)),
+                   absent, np.where(em, k["e_lat"], absent)], axis=-1)
+    return target, ov, stop, slowed | ~nm
+
+
 class FailSafeStateMachine:
-    """Same constructor contract as the reference: a config object read with getattr (state_machine.py:32-98)."""
+    """Same constructor contract as the reference: a config object read with getattr (state_machine.py:32-98).  One
+    episode's view of sm_update / sm_config; its state is plain Python values (``SpeculativePlanningCycle`` runs its dry
+    run on a shallow copy)."""
+
+    THRESHOLDS = dict(clearance_caution="clr_caution", clearance_emergency="clr_emergency",
+                      trigger_clearance_caution="trig_c", trigger_time_headway="trig_h", envelope_decel="env_decel",
+                      envelope_standoff="env_standoff")
 
     def __init__(self, config) -> None:
         self.config = config
         self.current_state = VehicleState.NORMAL
         self.consecutive_failures = 0
-        fp_mode = getattr(config, "ego_footprint", None)
-        if fp_mode is not None and fp_mode != "circle":
-            seg = config.vehicle_length / config.ego_footprint_n_circles          # footprint.py:37-39
-            ego_radius = float(np.hypot(seg / 2, config.vehicle_width / 2))
-        else:
-            ego_radius = getattr(config, "ego_radius", 1.0)
-        combined = ego_radius + getattr(config, "ped_radius", 0.2)
-        rc = getattr(config, "state_machine_recover_clearance_caution", None)
-        re = getattr(config, "state_machine_recover_clearance_emergency", None)
-        self.clearance_caution = rc if rc is not None else getattr(config, "state_machine_safe_distance_caution", 2.0) - combined
-        self.clearance_emergency = re if re is not None else getattr(config, "state_machine_safe_distance_emergency", 3.0) - combined
-        self.trigger_clearance_caution = getattr(config, "state_machine_trigger_clearance_caution", 0.0)
-        self.trigger_time_headway = getattr(config, "state_machine_trigger_time_headway", 0.0)
-        self.envelope_decel = getattr(config, "state_machine_envelope_decel", 0.0)
-        self.envelope_standoff = getattr(config, "state_machine_envelope_standoff", 0.5)
+        self._k = constants_of(config)
+        for name, key in self.THRESHOLDS.items():
+            setattr(self, name, self._k[key])
         self._last_clearance = float("inf")
         self._last_clearance_ahead = float("inf")
+
+    def _constants(self) -> Dict[str, float]:
+        """(the thresholds as the attributes hold them now)"""
+        return dict(self._k, **{key: getattr(self, name) for name, key in self.THRESHOLDS.items()})
 
     def observe_metrics(self, safety_metrics: Dict[str, Any]) -> None:                # :99-113
         self._last_clearance = safety_metrics.get("clearance", float("inf"))
         self._last_clearance_ahead = safety_metrics.get("clearance_ahead", self._last_clearance)
 
     def update(self, plan_found: bool, safety_metrics: Dict[str, Any], ego_speed: float = 0.0) -> StateMachineOutput:
-        """Transitions of state_machine.py:116-179."""
         self.observe_metrics(safety_metrics)
-        trigger = self.trigger_clearance_caution + self.trigger_time_headway * max(ego_speed, 0.0)
-        clearance = safety_metrics.get("clearance", float("inf"))
-        if self.current_state == VehicleState.NORMAL:
-            if not plan_found:
-                self.current_state = VehicleState.CAUTION
-                self.consecutive_failures += 1
-            elif trigger > 0.0 and clearance < trigger:
-                self.current_state = VehicleState.CAUTION                             # preventive escalation
-                self.consecutive_failures = 0
-            else:
-                self.consecutive_failures = 0
-        elif self.current_state == VehicleState.CAUTION:
-            if plan_found and self.consecutive_failures == 0:
-                if clearance > max(self.clearance_caution, trigger):
-                    self.current_state = VehicleState.NORMAL
-            elif not plan_found:
-                self.current_state = VehicleState.EMERGENCY
-                self.consecutive_failures += 1
-            else:
-                self.consecutive_failures = 0
-        elif self.current_state == VehicleState.EMERGENCY:
-            if plan_found and clearance > self.clearance_emergency:
-                self.current_state = VehicleState.CAUTION
+        state, fails = sm_update(np.int64(STATES.index(self.current_state)), np.int64(self.consecutive_failures),
+                                 np.bool_(plan_found), np.float64(self._last_clearance), np.float64(ego_speed),
+                                 self._constants())
+        self.current_state, self.consecutive_failures = STATES[int(state)], int(fails)
         return self._get_planner_config()
 
-    def _envelope_speed(self) -> Optional[float]:                                     # :249-264
-        if self.envelope_decel <= 0.0 or not math.isfinite(self._last_clearance_ahead):
-            return None
-        room = max(self._last_clearance_ahead - self.envelope_standoff, 0.0)
-        return math.sqrt(2.0 * self.envelope_decel * room)
-
-    def _stop_room_to_pedestrian(self) -> Optional[float]:                            # :266-278
-        if not math.isfinite(self._last_clearance_ahead):
-            return None
-        return max(self._last_clearance_ahead - 0.2, 0.05)
-
-    def _get_planner_config(self) -> StateMachineOutput:                              # :181-247
-        cfg = self.config
-        if self.current_state == VehicleState.NORMAL:
-            override = None
-            v_env = self._envelope_speed()
-            if v_env is not None and v_env < cfg.ego_target_speed:
-                override = v_env
-            return StateMachineOutput(VehicleState.NORMAL, override, None)
-        if self.current_state == VehicleState.CAUTION:
-            accel_mult = getattr(cfg, "state_machine_caution_accel_multiplier", 1.5)
-            speed_mult = getattr(cfg, "state_machine_caution_speed_multiplier", 0.8)
-            target = cfg.ego_target_speed * speed_mult
-            stop = None
-            v_env = self._envelope_speed()
-            if v_env is not None:
-                target = min(target, v_env)
-                if v_env <= 0.0:
-                    stop = self._stop_room_to_pedestrian()
-            return StateMachineOutput(VehicleState.CAUTION, target,
-                                      {"max_accel": cfg.ego_max_accel * accel_mult,
-                                       "max_speed": cfg.ego_max_speed * speed_mult}, stop)
-        accel_mult = getattr(cfg, "state_machine_emergency_accel_multiplier", 3.0)
-        lat_mult = getattr(cfg, "state_machine_emergency_lat_accel_multiplier", 2.0)
-        return StateMachineOutput(VehicleState.EMERGENCY, 0.0,
-                                  {"max_accel": cfg.ego_max_accel * accel_mult,
-                                   "max_lat_accel": getattr(cfg, "ego_max_lat_accel", 3.0) * lat_mult},
-                                  self._stop_room_to_pedestrian() if self.envelope_decel > 0.0 else None)
+    def _get_planner_config(self) -> StateMachineOutput:
+        target, ov, stop, overridden = sm_config(np.int64(STATES.index(self.current_state)),
+                                                 np.float64(self._last_clearance_ahead), self._constants())
+        overrides = {name: float(v) for name, v in zip(OVERRIDES, ov) if not np.isnan(v)}
+        return StateMachineOutput(self.current_state, float(target) if overridden else None, overrides or None,
+                                  None if np.isnan(stop) else float(stop))
 
 
 @dataclass

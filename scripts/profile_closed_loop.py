@@ -1,5 +1,5 @@
-"""Host-side time split of the batched closed-loop driver: lock steps of 64 scenario_01 episodes, fused (two libfot
-calls per step) and unfused (five).  First the plain wall time per step, then the libfot calls timed by wrapping the
+"""Host-side time split of the batched closed-loop driver: lock steps of 64 scenario_01 episodes, fused (one libfot
+call per step) and unfused (five).  First the plain wall time per step, then the libfot calls timed by wrapping the
 engine's methods (perf_counter around each; cProfile's own overhead distorts a sub-millisecond step -- see
 cprofile_closed_loop.py for where Python spends its share); what is left of the step is NumPy / Python."""
 import json
@@ -37,7 +37,7 @@ def run(fused, wrapped):
         setattr(obj, name, g)
 
     if wrapped:
-        for nm in ("plan_arrays", "safety_metrics_cat", "nearest_s_arrays", "loop_plan", "loop_observe"):
+        for nm in ("plan_arrays", "safety_metrics_cat", "nearest_s_arrays", "loop_step", "gather_paths"):
             wrap(loop.engine, nm)
         wrap(loop.resampler, "predict_cv")
     for _ in range(20):

@@ -121,25 +121,21 @@ def _same_histories(ha, hb):
                 np.testing.assert_array_equal(ra.predicted_trajectories, rb.predicted_trajectories)
 
 
-def test_two_calls_per_step_equal_five_calls_per_step(episodes):
-    """The fused step (fot_loop_plan + fot_loop_observe, prediction resident in HBM) and the step of five separate calls
-    (prediction through the host) are the same computation: the three reference episodes again, unfused, against the
-    reference AND record by record against the fused run -- ego states, metrics, selected paths, and the predictions the
-    fused run computes again when its history is read."""
+def test_one_call_per_step_equals_five_calls_per_step(episodes):
+    """The one-call step (fot_loop_step, prediction resident in HBM) and the step of five separate calls (prediction
+    through the host) are the same computation: the three reference episodes again, unfused, against the reference AND
+    record by record against the one-call run -- ego states, metrics, selected paths, and the predictions the one-call
+    run computes again when its history is read."""
     cfg = scenario_config(episodes["meta"])
     names = ("base", "fast", "shift")
     tracks = [episodes[n + "_ped_traj"] for n in names]
     with BatchedClosedLoop(cfg, tracks, fused=False) as plain:
-        assert not plain._fused
+        assert not plain._native
         h_plain = plain.run()
         for h, ep, n in zip(h_plain, plain.episodes, names):
             assert_episode_matches(h, ep.termination_reason, episodes, n)
         h_plain = [list(h) for h in h_plain]
-    with BatchedClosedLoop(cfg, tracks, fused="two-call") as fused:
-        assert fused._fused and not fused._native
-        h_fused = [list(h) for h in fused.run()]
-    _same_histories(h_plain, h_fused)
-    # ... and the whole step behind ONE call (fot_loop_step: episode state, fail-safe machine and retry loop in the library)
+    # the whole step behind ONE call (fot_loop_step: episode state, fail-safe machine and retry loop in the library)
     with BatchedClosedLoop(cfg, tracks) as native:
         assert native._native
         h_native = [list(h) for h in native.run()]
@@ -158,9 +154,8 @@ def test_fused_step_with_standing_and_walking_crowds(episodes):
     none = np.zeros((len(walk), 0, 2))
     tracks = [stand, walk, none, stand[:, :3], walk[:, ::2]]
     runs = []
-    for fused in (False, "two-call", True):
+    for fused in (False, True):
         with BatchedClosedLoop(cfg, tracks, fused=fused) as sim:
             hists = sim.run(60)
         runs.append([list(h) for h in hists])
     _same_histories(runs[0], runs[1])
-    _same_histories(runs[0], runs[2])

@@ -144,13 +144,13 @@ def test_reversed_slot_order_gives_the_same_episodes(episodes, mixed_runs, kw):
 def test_forms_that_take_one_configuration_refuse_a_mixed_list(episodes):
     cfgs = [scenario_config(episodes["meta"], n) for n in ("base", "turn")]
     tracks = [episodes[n + "_ped_traj"] for n in ("base", "turn")]
-    for fused in (False, "two-call"):
+    for fused in (False,):
         with pytest.raises(ValueError, match="one configuration"):
             BatchedClosedLoop(cfgs, tracks, fused=fused)
     with pytest.raises(ValueError, match="one configuration per episode"):
         BatchedClosedLoop(cfgs, tracks[:1])
     # equal configurations in a list are one scenario: today's loop, any form
-    with BatchedClosedLoop([cfgs[0], dict(cfgs[0])], [tracks[0]] * 2, fused="two-call") as sim:
+    with BatchedClosedLoop([cfgs[0], dict(cfgs[0])], [tracks[0]] * 2, fused=False) as sim:
         assert sim.scenarios is None and sim.engine.n_scenarios == 1
 
 

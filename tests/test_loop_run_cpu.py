@@ -220,4 +220,6 @@ def test_resident_needs_the_librarys_own_engine_and_the_cv_predictor():
     with pytest.raises(ValueError, match="resident"):
         BatchedClosedLoop(cfg, tracks, sample_source=lambda last, prev: None, resident=True)
     with pytest.raises(ValueError, match="resident"):
-        BatchedClosedLoop(cfg, tracks, fused="two-call", resident=True)
+        BatchedClosedLoop(cfg, tracks, fused=False, resident=True)
+    with pytest.raises(ValueError):
+        BatchedClosedLoop(cfg, tracks, fused="two-call")
