@@ -170,7 +170,7 @@ const char *fot_version(void);
  * FOT_MAX_TI, FOT_MAX_TV, FOT_MAX_BRAKE, FOT_MAX_SAMPLES, FOT_MAX_PRED_LEN, FOT_PROFILE_KERNELS, FOT_MARGIN_GROUPS,
  * sizeof of fot_loop_config, fot_loop_step_out, fot_loop_replay, fot_loop_run_out, fot_loop_summary.
  * Returns the number of words the library knows (FOT_ABI_INFO_WORDS of ITS header). */
-#define FOT_ABI_VERSION 6
+#define FOT_ABI_VERSION 7
 #define FOT_ABI_INFO_WORDS 25
 int32_t fot_abi_info(int32_t cap, int32_t *out);
 
@@ -295,11 +295,21 @@ int fot_check_collision_paths(fot_handle *h, int32_t n_paths, const int32_t *len
 
 /* FrenetPlanner._check_paths (frenet_planner.py:891-993) followed by _apply_stop_distance_filter (:307-324)
  * for n_paths externally supplied paths: arrays [n_paths][FOT_MAX_NT] host (yaw, d, s may be NULL = zeros),
- * len[n_paths], flags[n_paths] (bit0: x/y/yaw/s/d all present -> low-speed curvature rules apply, :1017-1022;
- * bit1: d present -> road-corridor test applies; NULL = both), overrides may be NULL, max_stop_distance NaN = None,
- * obstacle set as in fot_check_collision_paths.  status_out[n_paths]: FOT_ST_* (FOT_ST_OK = 'ok', FOT_ST_DROPPED =
- * silently skipped). */
-int fot_check_paths(fot_handle *h, int32_t n_paths, const int32_t *len, const int32_t *flags,
+ * len[n_paths] = samples of x, y and t (0: the path is skipped, as the reference skips an empty path and one whose x
+ * and t differ in length).  The reference applies every rule over the arrays that rule reads, which an externally
+ * constructed path may hold in different lengths; rule_len[n_paths][FOT_CHECK_RULE_LENS] carries them, each
+ * 0..FOT_MAX_NT and possibly larger than len[i]:
+ *   [0] n_geo = min(len x, y, yaw, s, d): the low-speed curvature rules apply while k < n_geo (:1017-1022)
+ *   [1] len d: the road-corridor test runs over all of d (:982)
+ *   [2] [3] [4] len v, a, c: finiteness (:944) and the limits (:964, :966) run over all of each; the curvature rules
+ *       (:1013) and the lateral acceleration (:975) over min(len v, len c)
+ *   [5] len s: the stop filter reads s[len s - 1] - s[0] and v[len v - 1] (:317-318; no v: never at rest, no s: no travel)
+ * NULL = every array holds len[i] samples.  Nothing beyond an array's own length is read into a decision.  yaw is read
+ * up to len[i] by the collision test with a footprint (a shorter yaw is held by the caller, :1158-1161).
+ * overrides may be NULL, max_stop_distance NaN = None, obstacle set as in fot_check_collision_paths.
+ * status_out[n_paths]: FOT_ST_* (FOT_ST_OK = 'ok', FOT_ST_DROPPED = silently skipped). */
+#define FOT_CHECK_RULE_LENS 6
+int fot_check_paths(fot_handle *h, int32_t n_paths, const int32_t *len, const int32_t *rule_len,
                     const double *x, const double *y, const double *yaw, const double *v, const double *a,
                     const double *c, const double *d, const double *s, const double *t,
                     const fot_overrides *overrides, double max_stop_distance,

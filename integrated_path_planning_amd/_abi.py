@@ -12,6 +12,7 @@ import weakref
 
 MAX_NT = 256
 MAX_CIRCLES = 8
+CHECK_RULE_LENS = 6                      # FOT_CHECK_RULE_LENS: n_geo, len d, v, a, c, s per path of fot_check_paths
 MAX_SAMPLES = 64
 
 OK = 0
@@ -158,7 +159,7 @@ SYMBOLS = ["fot_version", "fot_abi_info", "fot_create", "fot_destroy", "fot_live
            "fot_plan_batch_scenarios", "fot_plan_batch_scenarios_device", "fot_get_scenario_path_coeffs",
            "fot_loop_begin_scenarios", "fot_loop_set_scenario_static"]
 PROFILE_KERNELS = 3                      # FOT_PROFILE_KERNELS (include/fot.h)
-ABI_VERSION = 6                          # FOT_ABI_VERSION
+ABI_VERSION = 7                          # FOT_ABI_VERSION
 MAX_TI, MAX_TV, MAX_BRAKE, MAX_PRED_LEN = 64, 32, 32, 32
 EGO_IS_FRENET = 3                        # FOT_EGO_IS_FRENET (fot_ego.has_prev_s)
 MARGIN_GROUPS = 8                        # FOT_MARGIN_GROUPS

@@ -2627,7 +2627,7 @@ int fot_debug_margins(fot_handle *h, int32_t inst, int32_t cap, double *margins)
 namespace {
 
 // shared body of fot_check_collision_paths (mode 0) and fot_check_paths (mode 1)
-int check_ext(fot_handle *h, int mode, int32_t n_paths, const int32_t *len, const int32_t *flags,
+int check_ext(fot_handle *h, int mode, int32_t n_paths, const int32_t *len, const int32_t *rule_len,
               const double *const arr[9], const fot_overrides *ov, double max_stop,
               int32_t n_static, const double *static_xy, int32_t dmode, int32_t S, int32_t Pn, int32_t T,
               const double *dyn, int32_t *status_out)
@@ -2658,9 +2658,14 @@ int check_ext(fot_handle *h, int mode, int32_t n_paths, const int32_t *len, cons
         if (len[i] < 0 || len[i] > FOT_MAX_NT) return fail(h, FOT_ERR_INVALID, "path length out of range");
     for (int f = 0; f < 9; ++f)
         if (arr[f]) std::memcpy(flat.data() + f * plane, arr[f], sizeof(double) * plane);
-    std::vector<int32_t> meta(2 * np, 3);
+    // meta: len[np], then rule_len[np][FOT_CHECK_RULE_LENS] (NULL: every array holds len[i] samples)
+    std::vector<int32_t> meta((1 + FOT_CHECK_RULE_LENS) * np);
     std::memcpy(meta.data(), len, sizeof(int32_t) * np);
-    if (flags) std::memcpy(meta.data() + np, flags, sizeof(int32_t) * np);
+    for (size_t j = 0; j < FOT_CHECK_RULE_LENS * np; ++j) {
+        const int32_t v = rule_len ? rule_len[j] : len[j / FOT_CHECK_RULE_LENS];
+        if (v < 0 || v > FOT_MAX_NT) return fail(h, FOT_ERR_INVALID, "rule length out of range");
+        meta[np + j] = v;
+    }
 
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = h->stream;
@@ -2718,7 +2723,7 @@ int fot_check_collision_paths(fot_handle *h, int32_t n_paths, const int32_t *len
     return check_ext(h, 0, n_paths, len, nullptr, arr, nullptr, NAN, n_static, static_xy, mode, S, Pn, T, dyn, free_out);
 }
 
-int fot_check_paths(fot_handle *h, int32_t n_paths, const int32_t *len, const int32_t *flags,
+int fot_check_paths(fot_handle *h, int32_t n_paths, const int32_t *len, const int32_t *rule_len,
                     const double *x, const double *y, const double *yaw, const double *v, const double *a,
                     const double *c, const double *d, const double *s, const double *t,
                     const fot_overrides *overrides, double max_stop_distance,
@@ -2728,7 +2733,7 @@ int fot_check_paths(fot_handle *h, int32_t n_paths, const int32_t *len, const in
     if (!h) return FOT_ERR_INVALID;
     if (n_paths > 0 && (!x || !y || !v || !a || !c || !t)) return fail(h, FOT_ERR_INVALID, "NULL path array");
     const double *arr[9] = { x, y, yaw, v, a, c, d, s, t };
-    return check_ext(h, 1, n_paths, len, flags, arr, overrides, max_stop_distance, n_static, static_xy, mode, S, Pn, T,
+    return check_ext(h, 1, n_paths, len, rule_len, arr, overrides, max_stop_distance, n_static, static_xy, mode, S, Pn, T,
                      dyn, status_out);
 }
 

@@ -220,7 +220,7 @@ int launch_loop_pred_error(ReplayView rv, const int32_t *slot_of, FrameDev f, co
 int launch_loop_summary(SummaryShape S, const double *ring, const int32_t *ring_P, const SummaryTotals *totals,
                         const int32_t *steps, int n_slots, int num_samples, fot_loop_summary *out, hipStream_t st);
 int launch_check_ext(const DevParams *P, const InstDesc *desc, int n_paths, int mode, const int32_t *len,
-                     const int32_t *flags, const double *arrays, const double *static_xy, const double *dyn_xy,
+                     const int32_t *rule_len, const double *arrays, const double *static_xy, const double *dyn_xy,
                      int32_t *status_out, hipStream_t st);
 
 }  // namespace fot

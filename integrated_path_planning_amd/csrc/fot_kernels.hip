@@ -1798,9 +1798,10 @@ struct PathArraySource {
     }
 };
 
-// mode 0: collision only (status_out = 1 free / 0 hit); mode 1: _check_paths categories (FOT_ST_*)
+// mode 0: collision only (status_out = 1 free / 0 hit); mode 1: _check_paths categories (FOT_ST_*).
+// rule_len[n_paths][FOT_CHECK_RULE_LENS]: n_geo and the lengths of d, v, a, c, s (mode 1), each 0..FOT_MAX_NT.
 __global__ void k_check_ext(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, int n_paths, int mode,
-                            const int32_t *__restrict__ len, const int32_t *__restrict__ flags,
+                            const int32_t *__restrict__ len, const int32_t *__restrict__ rule_len,
                             const double *__restrict__ arrays /* [9][n_paths][FOT_MAX_NT]: x y yaw v a c d s t */,
                             const double *__restrict__ static_xy, const double *__restrict__ dyn_xy,
                             int32_t *__restrict__ status_out)
@@ -1819,24 +1820,41 @@ __global__ void k_check_ext(const DevParams *__restrict__ Pp, const InstDesc *__
     src.circ_off = P.circ_off; src.has_footprint = P.has_footprint;
     ObstacleView obs;
     obs.stat = static_xy; obs.dyn = dyn_xy; obs.dtype = FOT_F64;
+    // a NaN in any collision point makes the reference's path box NaN, which no obstacle is inside (np.min / np.max
+    // propagate it, frenet_planner.py:1177-1178): such a path collides with nothing, at any of its samples
+    bool nan_point = false;
+    const int n_circ = P.has_footprint ? P.n_circ : 1;
+    for (int k = 0; k < n; ++k)
+        for (int ci = 0; ci < n_circ; ++ci) {
+            double px, py;
+            src.get(k, ci, px, py);
+            nan_point |= isnan(px) || isnan(py);
+        }
     if (mode == 0) {
-        const bool hit = n > 0 && collide_candidate(P, D, obs, n, src);
+        const bool hit = n > 0 && !nan_point && collide_candidate(P, D, obs, n, src);
         status_out[i] = hit ? 0 : 1;
         return;
     }
-    const bool has_geo = flags[i] & 1, has_d = flags[i] & 2;
+    const int32_t *rl = rule_len + (int64_t)i * FOT_CHECK_RULE_LENS;
+    const int n_geo = rl[0] < n ? rl[0] : n, n_d = rl[1], n_v = rl[2], n_a = rl[3], n_c = rl[4], n_s = rl[5];
+    int n_loop = n;
+    n_loop = n_d > n_loop ? n_d : n_loop; n_loop = n_v > n_loop ? n_v : n_loop;
+    n_loop = n_a > n_loop ? n_a : n_loop; n_loop = n_c > n_loop ? n_c : n_loop;
     CheckAcc acc;
     check_init(acc);
     const LoopConst lc = loop_const(P, D);
-    for (int k = 0; k < n; ++k) {
+    for (int k = 0; k < n_loop && n > 0; ++k) {
+        const uint32_t has = (k < n ? RL_XY : 0u) | (k < n_v ? RL_V : 0u) | (k < n_a ? RL_A : 0u) | (k < n_c ? RL_C : 0u) |
+                             (k < n_d ? RL_D : 0u) | (k < n_geo ? RL_GEO : 0u);
         PathSample ps;
         ps.x = ax[k]; ps.y = ay[k]; ps.cos_t = cos(ayaw[k]); ps.sin_t = sin(ayaw[k]);
         ps.kappa = ac[k]; ps.v = av[k]; ps.a = aa[k]; ps.d = ad[k];
-        check_sample(lc, acc, k, ps, has_geo, has_d, [&] { return fabs(as[k] - as[k - 1]); });
+        check_sample_ext(lc, acc, k, ps, has, [&] { return fabs(as[k] - as[k - 1]); });
     }
     int st = check_status(D, acc, n);
-    if (st == ST_PENDING && n > 0 && collide_candidate(P, D, obs, n, src)) st = FOT_ST_COLLISION;
-    if (n > 0) st = final_status(st, av[n - 1], as[n - 1] - as[0], D.max_stop);
+    if (st == ST_PENDING && n > 0 && !nan_point && collide_candidate(P, D, obs, n, src)) st = FOT_ST_COLLISION;
+    // the stop filter reads the last entries of v and s as the caller gave them (:317-318): no v never stops, no s is no travel
+    if (n > 0) st = final_status(st, n_v > 0 ? av[n_v - 1] : NAN, n_s > 0 ? as[n_s - 1] - as[0] : 0.0, D.max_stop);
     status_out[i] = st;
 }
 
@@ -2437,11 +2455,11 @@ int launch_loop_summary(SummaryShape S, const double *ring, const int32_t *ring_
 }
 
 int launch_check_ext(const DevParams *P, const InstDesc *desc, int n_paths, int mode, const int32_t *len,
-                     const int32_t *flags, const double *arrays, const double *static_xy, const double *dyn_xy,
+                     const int32_t *rule_len, const double *arrays, const double *static_xy, const double *dyn_xy,
                      int32_t *status_out, hipStream_t st)
 {
     if (n_paths <= 0) return 0;
-    k_check_ext<<<(n_paths + 63) / 64, 64, 0, st>>>(P, desc, n_paths, mode, len, flags, arrays, static_xy, dyn_xy,
+    k_check_ext<<<(n_paths + 63) / 64, 64, 0, st>>>(P, desc, n_paths, mode, len, rule_len, arrays, static_xy, dyn_xy,
                                                     status_out);
     FOT_LAUNCH_CHECK();
     return 0;

@@ -671,6 +671,43 @@ FOT_HD void check_sample(const LoopConst &C, CheckAcc &c, int k, const PathSampl
     c.prev = p;
 }
 
+// check_sample for an externally constructed path (fot_check_paths), whose arrays may differ in length: the reference
+// applies every rule over the arrays that rule reads (finiteness and the limits over all of v / a / c, the curvature and
+// lateral-acceleration rules over min(len v, len c), the low-speed rules while k < n_geo, the road test over all of d,
+// the step length over x / y).  `has`: which arrays hold sample k.  With every bit set this is check_sample(.., true, true).
+enum : uint32_t { RL_XY = 1u, RL_V = 2u, RL_A = 4u, RL_C = 8u, RL_D = 16u, RL_GEO = 32u };
+
+template <class ArcStep>
+FOT_HD void check_sample_ext(const LoopConst &C, CheckAcc &c, int k, const PathSample &p, uint32_t has,
+                             const ArcStep &arc_step)
+{
+    check_flag(c, ((has & RL_V) && !isfinite(p.v)) || ((has & RL_A) && !isfinite(p.a)) ||
+                  ((has & RL_C) && !isfinite(p.kappa)), CK_NONFINITE);                        // :944-946
+    if (k > 0) {
+        double step2 = 0.0;
+        if (has & RL_XY) {                                                                    // :953-956
+            step2 = sum_sq_unfused(p.x - c.prev.x, p.y - c.prev.y);
+            check_flag(c, isnan(step2), CK_NANSTEP);
+            if (step2 > c.max_step2) c.max_step2 = step2;
+        }
+        check_flag(c, (has & RL_V) && p.v > C.lim_speed, CK_SPEED);                           // :964
+        check_flag(c, (has & RL_A) && fabs(p.a) > C.lim_accel, CK_ACCEL);                     // :966
+        if ((has & RL_V) && (has & RL_C)) {
+            if (p.v > 0.5) {                                                                   // LOW_SPEED_CURVATURE_GATE
+                check_flag(c, fabs(p.kappa) > C.lim_curv, CK_CURV);
+            } else if (has & RL_GEO) {                                                         // (implies RL_XY)
+                check_flag(c, fabs(p.d - c.prev.d) > fmax(1.5 * arc_step(), 0.02), CK_CURV);
+                const double sn = p.sin_t * c.prev.cos_t - p.cos_t * c.prev.sin_t;
+                const double cs = p.cos_t * c.prev.cos_t + p.sin_t * c.prev.sin_t;
+                if (!(cs > 0.0 && fabs(sn) <= 0.09 * cs)) check_flag(c, yaw_step_over_cap(sn, cs, C.lim_curv, step2), CK_CURV);
+            }
+            check_flag(c, p.v * p.v * fabs(p.kappa) > C.lim_lat, CK_LAT);                     // :975
+        }
+        check_flag(c, (has & RL_D) && fabs(p.d) > C.road_lim, CK_ROAD);                       // :982
+    }
+    c.prev = p;
+}
+
 // first failing category in the reference's order; ST_PENDING = collision check outstanding
 FOT_HD int check_status(const InstDesc &D, const CheckAcc &c, int keep)
 {

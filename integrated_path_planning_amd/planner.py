@@ -754,28 +754,29 @@ class BatchPlanner:
 
     @staticmethod
     def _pack_paths(paths: Sequence, fields: Sequence[str]):
-        """FrenetPath-like objects -> {field: [n, MAX_NT]} arrays, lengths, presence flags."""
+        """FrenetPath-like objects -> {field: [n, MAX_NT]} arrays, lengths of x / t, and the per-rule lengths of
+        ``fot_check_paths`` [n, CHECK_RULE_LENS]: every array keeps its own length (the reference applies each rule over
+        the arrays that rule reads, frenet_planner.py:944-984, :1013-1022, :317-318), zeros behind it."""
         n = len(paths)
         arrs = {f: np.zeros((max(n, 1), _abi.MAX_NT)) for f in fields}
         ln = np.zeros(max(n, 1), np.int32)
-        flags = np.zeros(max(n, 1), np.int32)
+        rule_len = np.zeros((max(n, 1), _abi.CHECK_RULE_LENS), np.int32)
         for i, fp in enumerate(paths):
             m = min(len(fp.x), len(fp.t))                        # frenet_planner.py:1146
-            if m > _abi.MAX_NT:
-                raise ValueError(f"path longer than {_abi.MAX_NT} samples")
-            ln[i] = m
-            present = {}
+            own = {}
             for f in fields:
                 v = getattr(fp, f, None)
                 v = np.zeros(0) if v is None else np.asarray(v, dtype=float)
-                present[f] = len(v) >= m and m > 0
+                if len(v) > _abi.MAX_NT:
+                    raise ValueError(f"path {i}: {f} is longer than {_abi.MAX_NT} samples")
+                own[f] = len(v)
+                arrs[f][i, :len(v)] = v
                 if f == "yaw" and 0 < len(v) < m:                # :1158-1161 hold the last value
-                    v = np.concatenate([v, np.full(m - len(v), v[-1])])
-                k = min(len(v), m)
-                arrs[f][i, :k] = v[:k]
-            geo = all(present.get(f, False) for f in ("x", "y", "yaw", "s", "d") if f in fields)
-            flags[i] = (1 if geo else 0) | (2 if present.get("d", False) else 0)
-        return arrs, ln, flags
+                    arrs[f][i, len(v):m] = v[-1]
+            ln[i] = m
+            geo = min(own.get(f, 0) for f in ("x", "y", "yaw", "s", "d"))
+            rule_len[i] = [geo] + [own.get(f, 0) for f in ("d", "v", "a", "c", "s")]
+        return arrs, ln, rule_len
 
     def _obstacle_args(self, static, dyn, dist):
         req = PlanRequest(0, 0, 0, 0, 0, static=static, dyn=dyn, dist=dist)
@@ -801,7 +802,7 @@ class BatchPlanner:
         """_check_paths (+ stop-distance filter) categories of FrenetPath-like objects: FOT_ST_* per path."""
         n = len(paths)
         fields = ("x", "y", "yaw", "v", "a", "c", "d", "s", "t")
-        arrs, ln, flags = self._pack_paths(paths, fields)
+        arrs, ln, rule_len = self._pack_paths(paths, fields)
         for i, fp in enumerate(paths):                           # :933-940 silently skipped
             if len(fp.x) == 0 or len(fp.x) != len(fp.t):
                 ln[i] = 0
@@ -813,7 +814,7 @@ class BatchPlanner:
         ov.max_curvature, ov.max_lat_accel = float(o.get("max_curvature", nan)), float(o.get("max_lat_accel", nan))
         status = np.zeros(max(n, 1), np.int32)
         _abi.check(self._h, self._lib.fot_check_paths(
-            self._h, n, ln.ctypes.data_as(_ip), flags.ctypes.data_as(_ip), *[_as_dp(arrs[f]) for f in fields],
+            self._h, n, ln.ctypes.data_as(_ip), rule_len.ctypes.data_as(_ip), *[_as_dp(arrs[f]) for f in fields],
             C.byref(ov), nan if max_stop_distance is None else float(max_stop_distance), *oargs,
             status.ctypes.data_as(_ip)))
         status = status[:n]

@@ -698,11 +698,14 @@ static int collision_geometry(const orc_params *p, int n, const double *x, const
     double aabb_r = fmax(r, r_dyn);
     double mnx = g->px[0], mxx = g->px[0], mny = g->py[0], mxy = g->py[0];
     for (int i = 1; i < m; ++i) {
-        /* np.min/np.max propagate NaN; internal paths are finite here */
         if (g->px[i] < mnx) mnx = g->px[i];
         if (g->px[i] > mxx) mxx = g->px[i];
         if (g->py[i] < mny) mny = g->py[i];
         if (g->py[i] > mxy) mxy = g->py[i];
+        /* np.min / np.max propagate a NaN point (:1177-1178): an external path that holds one has a NaN box, which no
+         * obstacle is inside (internal paths are finite here) */
+        if (isnan(g->px[i])) mnx = mxx = NAN;
+        if (isnan(g->py[i])) mny = mxy = NAN;
     }
     g->minx = mnx - aabb_r; g->miny = mny - aabb_r;
     g->maxx = mxx + aabb_r; g->maxy = mxy + aabb_r;

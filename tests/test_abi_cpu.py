@@ -158,6 +158,7 @@ def test_header_constants_match_the_python_mirror():
     defs = {k: int(v) for k, v in re.findall(r"#define (FOT_[A-Z_]+) (\d+)\b", text)}
     assert defs["FOT_PROFILE_KERNELS"] == _abi.PROFILE_KERNELS
     assert defs["FOT_MAX_NT"] == _abi.MAX_NT
+    assert defs["FOT_CHECK_RULE_LENS"] == _abi.CHECK_RULE_LENS
 
 
 def test_abi_info_matches_the_binding_and_the_header():
