@@ -168,10 +168,11 @@ const char *fot_version(void);
  * corruption").  out[i], i < cap: FOT_ABI_VERSION, sizeof of fot_params, fot_ego, fot_overrides, fot_result, fot_batch,
  * fot_resample_params, fot_safety, fot_loop_frame, fot_loop_request, fot_wire_header, then FOT_MAX_NT, FOT_MAX_CIRCLES,
  * FOT_MAX_TI, FOT_MAX_TV, FOT_MAX_BRAKE, FOT_MAX_SAMPLES, FOT_MAX_PRED_LEN, FOT_PROFILE_KERNELS, FOT_MARGIN_GROUPS,
- * sizeof of fot_loop_config, fot_loop_step_out, fot_loop_replay, fot_loop_run_out, fot_loop_summary.
+ * sizeof of fot_loop_config, fot_loop_step_out, fot_loop_replay, fot_loop_run_out, fot_loop_summary, fot_pred_origin,
+ * fot_pred_score.
  * Returns the number of words the library knows (FOT_ABI_INFO_WORDS of ITS header). */
-#define FOT_ABI_VERSION 7
-#define FOT_ABI_INFO_WORDS 25
+#define FOT_ABI_VERSION 8
+#define FOT_ABI_INFO_WORDS 27
 int32_t fot_abi_info(int32_t cap, int32_t *out);
 
 /* FrenetPlanner.__init__ (frenet_planner.py:149-225).  device < 0: current device. */
@@ -560,7 +561,8 @@ int fot_loop_run(fot_handle *h, int32_t max_steps, fot_loop_run_out *out);
  *       ade / fde / ade_eval_count (metrics.py:31-114): stride = round(sgan_dt / sim_dt), samples k = stride j - 1,
  *       j = 1 .. pred_len; an origin counts if n_dense > stride pred_len - 1 and i + stride pred_len < L.
  *       ade_per_agent / fde_per_agent: equal to ade / fde (the constant-velocity predictor's samples are identical, so
- *       best-of-N picks nothing); pred_samples: num_samples of fot_loop_summary_enable if an origin counted, else 0.
+ *       best-of-N picks nothing; a multi-sample predictor's loop gets them from fot_loop_prediction_scores);
+ *       pred_samples: num_samples of fot_loop_summary_enable if an origin counted, else 0.
  *       nll = NaN, nll_eval_count = 0 (identical samples are skipped, metrics.py:155-158).
  *     Steps without a prediction (observer not ready) and slots without pedestrians contribute nothing; with no counted
  *     origin the means are NaN and the counts 0.
@@ -586,6 +588,59 @@ typedef struct fot_loop_summary {
 } fot_loop_summary;
 int fot_loop_summary_enable(fot_handle *h, int32_t on, int32_t num_samples);
 int fot_loop_summaries(fot_handle *h, int32_t n_slots, fot_loop_summary *out);
+
+/* ---- prediction scores: best-of-N ADE / FDE and the KDE log-likelihood of a sample distribution, on the device --------
+ * The six keys of the reference's summary that compare predictors (calculate_aggregate_metrics, src/core/metrics.py:
+ * 272-320: ade, fde, ade_per_agent, fde_per_agent, nll, nll_eval_count) are functions of the whole [S][P][T][2] sample
+ * distribution of every step.  One record per prediction origin holds what that origin contributes
+ * (_standard_ade_fde_details :31-114, _kde_nll_details :117-176), computed by one workgroup from the tensor where it lies.
+ * With q[s][p][k] dense sample k of the origin's block (the prepended current position skipped: `skip`), evaluation
+ * indices k_j = stride j - 1, j = 1 .. E, truth g[p][j] and d[s][p][j] = |q[s][p][k_j] - g[p][j]|:
+ *   ade_scene = min_s mean_{p, j} d                      fde_scene = min_s mean_p d[s][p][E]      (one sample per scene)
+ *   ade_agent_sum = sum_p min_s mean_j d[s][p][j]        fde_agent_sum = sum_p min_s d[s][p][E]   (minADE / minFDE)
+ *   log_lik_sum, nll_count: evaluated only if S >= 2 and the samples differ somewhere ((p, j, axis) with max_s != min_s;
+ *   otherwise 0 / 0 and FOT_PRED_NLL not set, :155-158).  Per (p, j) and axis the bandwidth b = max(std_s(q, ddof = 1)
+ *   S^(-1/6), 0.05) with a two-pass standard deviation; l_s = -1/2 sum_axis ((q - g) / b)^2 - log(2 pi b_x b_y);
+ *   log p = max(max_s l + log(mean_s exp(l_s - max l)), -20); log_lik_sum = sum_{p, j} log p, nll_count = P E.
+ * All of it in float64 whatever the tensor's element type (a float32 tensor gives the scores of the rounded samples), every
+ * reduction in an order fixed by (S, P, E) alone, no floating-point atomics: an origin's record is byte-identical alone
+ * and inside any batch.  flags: FOT_PRED_NLL; FOT_PRED_NONFINITE: a sample at an evaluation index or a truth coordinate
+ * was not finite -- the terms it enters are NaN, as NumPy's min / maximum give.  An episode folds the records of its
+ * origins with a complete horizon in step order as the reference does: total_ade += ade_scene n_peds, total_fde +=
+ * fde_scene n_peds, the agent sums and log_lik_sum as they are, counts += n_peds / nll_count; ade = total_ade / count ...,
+ * nll = -log_lik / nll_eval_count.
+ *
+ * fot_prediction_scores (stateless, synchronous): origin i's block starts at POINT desc[i].offset of `tensor` (host memory,
+ * or device memory with on_device != 0; dtype FOT_F32 | FOT_F64), laid out [S][P][T][2] (layout 0) or [T][S][P][2]
+ * (FOT_DYN_LAYOUT_TSP); skip 1: sample 0 of every track is the prepended current position.  truth: host [sum P][E][2]
+ * float64, the origins' pedestrians one after the other; out: host, n_origins records.  stream NULL = the handle's.
+ * P = 0 gives a zero record (n_peds 0).  Refusals, a refused call changes nothing: stride < 1, E < 1, S < 1, P < 0,
+ * stride E - 1 >= T - skip, skip not 0 / 1, a negative offset, an unknown layout or dtype (FOT_ERR_INVALID); S >
+ * FOT_MAX_SAMPLES or E > FOT_MAX_PRED_LEN -- the kernel keeps E truth points per pedestrian of a tile in LDS
+ * (FOT_ERR_UNSUPPORTED).
+ * fot_loop_prediction_scores: the same for the distribution blocks the most recent fot_loop_step / fot_loop_plan frame
+ * with dist_raw left in the handle's own tensor (float64, [dist_S][P_e][n_dense + 1][2], skip 1): n_episodes == the
+ * frame's, truth [sum P][E][2] in the frame's pedestrian order.  The samples stay in HBM; the call is enqueued on the
+ * loop's stream and synchronises once.  FOT_ERR_INVALID when the last frame carried no distribution, n_episodes differs,
+ * or a replay is set (fot_loop_run owns the handle's tensor then). */
+#define FOT_PRED_NLL 1
+#define FOT_PRED_NONFINITE 2
+typedef struct fot_pred_origin {
+    int64_t offset;                 /* first point (2-vector) of the block in the tensor */
+    int32_t S, P, T;                /* samples, pedestrians, entries per track (the prepended one included) */
+    int32_t layout;                 /* 0 | FOT_DYN_LAYOUT_TSP */
+    int32_t skip;                   /* 0 | 1 */
+    int32_t _pad;
+} fot_pred_origin;
+typedef struct fot_pred_score {
+    double ade_scene, fde_scene, ade_agent_sum, fde_agent_sum, log_lik_sum;
+    int32_t n_peds, n_samples, nll_count, flags;
+} fot_pred_score;
+int fot_prediction_scores(fot_handle *h, int32_t n_origins, const fot_pred_origin *desc, const void *tensor, int32_t dtype,
+                          int32_t on_device, int32_t stride, int32_t E, const double *truth, fot_pred_score *out,
+                          void *stream);
+int fot_loop_prediction_scores(fot_handle *h, int32_t n_episodes, int32_t stride, int32_t E, const double *truth,
+                               fot_pred_score *out);
 
 /* Host utility (no GPU): the first kmax samples of the 15 path arrays of records[index[i]], i < n, as one dense block
  * out[15][n][kmax] in fot_result array order (t .. c) -- what a history keeps of a step's records. */

@@ -135,6 +135,20 @@ class LoopSummary(C.Structure):                                    # fot_loop_su
     _fields_ = [(n, C.c_double) for n in LOOP_SUMMARY_F64] + [(n, C.c_int32) for n in LOOP_SUMMARY_I32]
 
 
+class PredOrigin(C.Structure):                                     # fot_pred_origin
+    _fields_ = [("offset", C.c_int64), ("S", C.c_int32), ("P", C.c_int32), ("T", C.c_int32), ("layout", C.c_int32),
+                ("skip", C.c_int32), ("_pad", C.c_int32)]
+
+
+PRED_SCORE_F64 = ("ade_scene", "fde_scene", "ade_agent_sum", "fde_agent_sum", "log_lik_sum")
+PRED_SCORE_I32 = ("n_peds", "n_samples", "nll_count", "flags")
+PRED_NLL, PRED_NONFINITE = 1, 2          # FOT_PRED_NLL, FOT_PRED_NONFINITE (fot_pred_score.flags)
+
+
+class PredScore(C.Structure):                                      # fot_pred_score
+    _fields_ = [(n, C.c_double) for n in PRED_SCORE_F64] + [(n, C.c_int32) for n in PRED_SCORE_I32]
+
+
 class Batch(C.Structure):
     _fields_ = [("n_inst", C.c_int32), ("obstacle_dtype", C.c_int32),
                 ("ego", C.POINTER(Ego)), ("target_speed", C.POINTER(C.c_double)),
@@ -153,13 +167,13 @@ SYMBOLS = ["fot_version", "fot_abi_info", "fot_create", "fot_destroy", "fot_live
            "fot_set_path_coeffs", "fot_get_path_coeffs", "fot_spline_eval", "fot_plan_batch",
            "fot_plan_batch_device", "fot_synchronize", "fot_frenet_state_batch", "fot_debug_candidates",
            "fot_debug_candidate_path", "fot_debug_margins", "fot_debug_set_eval_segments", "fot_debug_set_tile_cut", "fot_debug_time_info", "fot_check_collision_paths", "fot_check_paths", "fot_resample_n_dense", "fot_resample_predictions",
-           "fot_predict_cv", "fot_safety_metrics_batch", "fot_loop_set_static", "fot_loop_plan", "fot_loop_observe", "fot_loop_observe_begin", "fot_loop_observe_end", "fot_loop_begin", "fot_loop_step", "fot_loop_set_replay", "fot_loop_run", "fot_loop_summary_enable", "fot_loop_summaries", "fot_gather_paths", "fot_wire_n_total", "fot_wire_record_bytes",
+           "fot_predict_cv", "fot_safety_metrics_batch", "fot_loop_set_static", "fot_loop_plan", "fot_loop_observe", "fot_loop_observe_begin", "fot_loop_observe_end", "fot_loop_begin", "fot_loop_step", "fot_loop_set_replay", "fot_loop_run", "fot_loop_summary_enable", "fot_loop_summaries", "fot_prediction_scores", "fot_loop_prediction_scores", "fot_gather_paths", "fot_wire_n_total", "fot_wire_record_bytes",
            "fot_pack_records_device", "fot_pack_records_host", "fot_unpack_records", "fot_profile_enable", "fot_profile_read", "fot_profile_kernel_name",
            "fot_add_scenario", "fot_set_scenario_path_waypoints", "fot_set_scenario_path_coeffs",
            "fot_plan_batch_scenarios", "fot_plan_batch_scenarios_device", "fot_get_scenario_path_coeffs",
            "fot_loop_begin_scenarios", "fot_loop_set_scenario_static"]
 PROFILE_KERNELS = 3                      # FOT_PROFILE_KERNELS (include/fot.h)
-ABI_VERSION = 7                          # FOT_ABI_VERSION
+ABI_VERSION = 8                          # FOT_ABI_VERSION
 MAX_TI, MAX_TV, MAX_BRAKE, MAX_PRED_LEN = 64, 32, 32, 32
 EGO_IS_FRENET = 3                        # FOT_EGO_IS_FRENET (fot_ego.has_prev_s)
 MARGIN_GROUPS = 8                        # FOT_MARGIN_GROUPS
@@ -174,7 +188,8 @@ def abi_expectation():
     return [ABI_VERSION, C.sizeof(Params), C.sizeof(Ego), C.sizeof(Overrides), C.sizeof(Result), C.sizeof(Batch),
             C.sizeof(ResampleParams), C.sizeof(Safety), C.sizeof(LoopFrame), C.sizeof(LoopRequest), C.sizeof(WireHeader),
             MAX_NT, MAX_CIRCLES, MAX_TI, MAX_TV, MAX_BRAKE, MAX_SAMPLES, MAX_PRED_LEN, PROFILE_KERNELS, MARGIN_GROUPS,
-            C.sizeof(LoopConfig), C.sizeof(LoopStepOut), C.sizeof(LoopReplay), C.sizeof(LoopRunOut), C.sizeof(LoopSummary)]
+            C.sizeof(LoopConfig), C.sizeof(LoopStepOut), C.sizeof(LoopReplay), C.sizeof(LoopRunOut), C.sizeof(LoopSummary),
+            C.sizeof(PredOrigin), C.sizeof(PredScore)]
 
 
 ABI_WORD_NAMES = ["FOT_ABI_VERSION", "sizeof(fot_params)", "sizeof(fot_ego)", "sizeof(fot_overrides)", "sizeof(fot_result)",
@@ -182,7 +197,7 @@ ABI_WORD_NAMES = ["FOT_ABI_VERSION", "sizeof(fot_params)", "sizeof(fot_ego)", "s
                   "sizeof(fot_loop_request)", "sizeof(fot_wire_header)", "FOT_MAX_NT", "FOT_MAX_CIRCLES", "FOT_MAX_TI",
                   "FOT_MAX_TV", "FOT_MAX_BRAKE", "FOT_MAX_SAMPLES", "FOT_MAX_PRED_LEN", "FOT_PROFILE_KERNELS",
                   "FOT_MARGIN_GROUPS", "sizeof(fot_loop_config)", "sizeof(fot_loop_step_out)", "sizeof(fot_loop_replay)",
-                  "sizeof(fot_loop_run_out)", "sizeof(fot_loop_summary)"]
+                  "sizeof(fot_loop_run_out)", "sizeof(fot_loop_summary)", "sizeof(fot_pred_origin)", "sizeof(fot_pred_score)"]
 
 
 def _check_abi(L, path):
@@ -385,6 +400,8 @@ def lib():
     L.fot_loop_run.argtypes = [vp, C.c_int32, vp]
     L.fot_loop_summary_enable.argtypes = [vp, C.c_int32, C.c_int32]
     L.fot_loop_summaries.argtypes = [vp, C.c_int32, vp]
+    L.fot_prediction_scores.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
+    L.fot_loop_prediction_scores.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
     L.fot_gather_paths.argtypes = [vp, C.c_int32, vp, C.c_int32, vp]
     L.fot_wire_n_total.argtypes = [vp]
     L.fot_wire_record_bytes.argtypes = [C.c_int32]

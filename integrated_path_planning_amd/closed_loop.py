@@ -443,7 +443,8 @@ class BatchedClosedLoop:
 
     def __init__(self, config, ped_tracks: Sequence[np.ndarray], ego_initial_states: Optional[Sequence] = None,
                  device: int = -1, engine=None, resampler=None, sample_source=None, fused: Optional[bool] = None,
-                 device_samples: bool = False, resident: bool = False, summaries: bool = False):
+                 device_samples: bool = False, resident: bool = False, summaries: bool = False,
+                 prediction_scores: bool = False):
         """sample_source: the multi-sample predictor in front of the planner -- a callable
         ``(obs_last [P, 2], obs_prev [P, 2]) -> raw samples [S, pred_len, P, 2]`` at the predictor's own time step
         (what S forward passes of Social-GAN on PyTorch-ROCm return for the pedestrians of all running episodes; the
@@ -463,6 +464,13 @@ class BatchedClosedLoop:
         them, a few hundred bytes per episode whatever its length.  ``pred_samples`` reports the configuration's
         ``num_samples`` (trajectory_predictor's sample count, integrated_simulator.py:333: the constant-velocity
         predictor hands the metrics that many identical samples).
+        prediction_scores (stepwise loops with a sample_source): every lock step the library scores the step's sample
+        distribution of every running episode against the replayed tracks -- best-of-N ADE / FDE, scene level and per
+        agent, and the KDE log-likelihood (``fot_loop_prediction_scores`` on the tensor in HBM with ``device_samples``,
+        ``fot_prediction_scores`` on the host distribution otherwise, the "planned on the best sample" mode included);
+        ``prediction_metrics()`` folds the records as the reference's ``calculate_aggregate_metrics`` does.  The element
+        type of the planner's tensor is the one scored (float64 here; a float32 tensor would give the metrics of the
+        rounded samples).
         fused: True = the lock step behind one library call (fot_loop_step), False = five separate calls with the
         prediction through the host, None = one call where the engine and the predictor allow it."""
         if fused not in (None, False, True):
@@ -471,6 +479,13 @@ class BatchedClosedLoop:
         self._summaries = bool(summaries)
         if self._summaries and not self._resident:
             raise ValueError("summaries=True needs resident=True (the summary is accumulated by the resident loop)")
+        self._pred_scores = bool(prediction_scores)
+        if self._pred_scores and self._resident:
+            raise ValueError("prediction_scores=True scores the stepwise loop's distributions (resident=False)")
+        if self._pred_scores and sample_source is None:
+            raise ValueError("prediction_scores=True needs a multi-sample predictor (sample_source)")
+        if self._pred_scores and engine is not None and not hasattr(engine, "prediction_scores"):
+            raise ValueError("prediction_scores=True needs the library's own engine (fot_prediction_scores)")
         if self._resident and (sample_source is not None or engine is not None or resampler is not None or fused not in (None, True)):
             raise ValueError("resident=True needs the constant-velocity predictor on the library's own engine "
                              "(no sample_source, engine or resampler; the one-call step)")
@@ -592,6 +607,12 @@ class BatchedClosedLoop:
         self.step_counts = np.zeros(n, np.int64)                     # lock steps each episode took part in
         self.termination = np.zeros(n, np.int8)                      # index into _TERMINATION
         self.episodes: List[Episode] = [Episode(self, e) for e in range(n)]
+        self._score_dist, self._score_steps = None, []
+        if self._pred_scores:
+            ratio = self.sgan_dt / self.dt                            # _steps_for_interval (metrics.py:22-28)
+            self._score_stride = int(round(ratio))
+            if self._score_stride < 1 or not np.isclose(ratio, self._score_stride):
+                raise ValueError(f"prediction_scores: the predictor's step {self.sgan_dt} must be a multiple of dt = {self.dt}")
         self._warmup()
         if self._native and self.scenarios is not None:
             self.engine.loop_begin_scenarios(
@@ -704,6 +725,7 @@ class BatchedClosedLoop:
                 o32 = obs.astype(np.float32).astype(np.float64)
                 raw = np.asarray(self.sample_source(o32[1], o32[0]), dtype=np.float64)       # [S, pred_len, sum P, 2]
                 dist = self.resampler.process_prediction(raw, anchor_pos=o32[1], staleness=stale)
+                self._score_dist = dist                               # (what the reference records of the step, :447)
                 if raw.shape[0] == 1:
                     pred, dist = dist[0], None
                 else:
@@ -731,7 +753,68 @@ class BatchedClosedLoop:
         pos = self._ped_frame("trajectories", sel)
         vel = self._ped_frame("velocities", sel)
         form = self._step_native if self._native else self._step_five_calls
-        return form(sel, off, pos, vel)
+        self._score_dist = None
+        n = form(sel, off, pos, vel)
+        if self._pred_scores:
+            self._score_step(sel, off)
+        return n
+
+    def _score_step(self, sel, off) -> None:
+        """The step's distribution of every episode of ``sel`` scored against the replayed tracks: the truth of origin
+        frame f is row min(f + stride j, frames - 1), j = 1 .. pred_len (a shorter recording holds its last frame); the
+        records wait in ``_score_steps`` for ``prediction_metrics()``."""
+        stride, E = self._score_stride, int(self.resampler.pred_len)
+        host = self._score_dist
+        ready = host is not None or (self._device_samples and self._steps[-1]["pred_src"] is not None)
+        if not ready or stride * E - 1 >= self.resampler.n_dense:     # no prediction yet / no complete horizon (:78)
+            return
+        tracks = self._ped_all["trajectories"]
+        rows = np.minimum(self.frame + stride * np.arange(1, E + 1), len(tracks) - 1)
+        truth = np.ascontiguousarray(tracks[rows][:, self._rows_of(sel)].transpose(1, 0, 2))      # [sum P, E, 2]
+        if host is None:
+            rec = self.engine.loop_prediction_scores(len(sel), stride, E, truth)
+        else:
+            S_, T = host.shape[0], host.shape[2]
+            blocks = [np.ascontiguousarray(host[:, off[i]:off[i + 1]]).reshape(-1, 2) for i in range(len(sel))]
+            origins = [(S_ * int(off[i]) * T, S_, int(off[i + 1] - off[i]), T, False, 0) for i in range(len(sel))]
+            rec = self.engine.prediction_scores(np.concatenate(blocks) if blocks else np.zeros((0, 2)), origins, truth,
+                                                stride, E)
+        self._score_steps.append((sel, self.step_counts[sel] - 1, rec))
+
+    def prediction_metrics(self) -> List[Dict[str, Any]]:
+        """Per episode the prediction keys of the reference's ``calculate_aggregate_metrics`` over the steps run so far:
+        ``ade``, ``fde`` (scene-level best-of-N), ``ade_per_agent``, ``fde_per_agent`` (minADE / minFDE), ``pred_samples``,
+        ``ade_eval_count``, ``nll``, ``nll_eval_count`` -- NaN / 0 where nothing counted.  An origin counts once its
+        episode has stride * pred_len further steps (metrics.py:78); the records are folded in step order as the
+        reference folds them.  Needs ``prediction_scores=True``; may be called between two steps."""
+        if not self._pred_scores:
+            raise ValueError("prediction_metrics() needs BatchedClosedLoop(..., prediction_scores=True)")
+        n = len(self.episodes)
+        horizon = self._score_stride * int(self.resampler.pred_len)
+        tot = np.zeros((n, 5))
+        count, nll_count, samples = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int64)
+        for sel, index, rec in self._score_steps:
+            for e, i, r in zip(sel, index, rec):
+                if r["n_peds"] <= 0 or i + horizon >= self.step_counts[e]:
+                    continue
+                tot[e, 0] += float(r["ade_scene"]) * int(r["n_peds"])
+                tot[e, 1] += float(r["fde_scene"]) * int(r["n_peds"])
+                tot[e, 2] += float(r["ade_agent_sum"])
+                tot[e, 3] += float(r["fde_agent_sum"])
+                count[e] += int(r["n_peds"])
+                samples[e] = max(samples[e], int(r["n_samples"]))
+                if r["flags"] & _abi.PRED_NLL:
+                    tot[e, 4] += float(r["log_lik_sum"])
+                    nll_count[e] += int(r["nll_count"])
+        nan = float("nan")
+        out = []
+        for e in range(n):
+            c = int(count[e])
+            m = [float(v) / c for v in tot[e, :4]] if c else [nan] * 4
+            out.append(dict(ade=m[0], fde=m[1], ade_per_agent=m[2], fde_per_agent=m[3], pred_samples=int(samples[e]) if c else 0,
+                            ade_eval_count=c, nll=-float(tot[e, 4]) / int(nll_count[e]) if nll_count[e] else nan,
+                            nll_eval_count=int(nll_count[e])))
+        return out
 
     def _step_five_calls(self, sel, off, pos, vel):
         """Steps 2-5 in five separate libfot calls, the prediction and the retry loop on the host: what a sample source

@@ -251,6 +251,8 @@ struct fot_handle {
     DevBuf dUserStatic, dUserDyn, dOut;      // device copies for the host-pointer entry point
     PinnedBuf hSmallIn, hSmallOut;           // ... and, for small calls, pinned host blocks the kernels use directly
     PinnedBuf hRecOut;                       // ... the records of a small plan call (a block of its own: zero past n_total)
+    PinnedBuf hScoreIn, hScoreOut;           // fot_prediction_scores: PredOriginDev[] | truth; the records the kernel writes
+    DevBuf dScoreT;                          // ... the device copy of a host tensor
     DevBuf dTmpA, dTmpB, dTmpC, dTmpD;
     LoopState loop;
     bool last_valid = false;
@@ -743,6 +745,7 @@ int32_t fot_abi_info(int32_t cap, int32_t *out)
         FOT_PROFILE_KERNELS, FOT_MARGIN_GROUPS,
         (int32_t)sizeof(fot_loop_config), (int32_t)sizeof(fot_loop_step_out),
         (int32_t)sizeof(fot_loop_replay), (int32_t)sizeof(fot_loop_run_out), (int32_t)sizeof(fot_loop_summary),
+        (int32_t)sizeof(fot_pred_origin), (int32_t)sizeof(fot_pred_score),
     };
     for (int i = 0; i < FOT_ABI_INFO_WORDS && i < cap && out; ++i) out[i] = v[i];
     return FOT_ABI_INFO_WORDS;
@@ -852,6 +855,7 @@ void destroy_handle(fot_handle *h)
     for (DevBuf *b : bufs) b->release();
     for (Workspace &w : h->ws) w.release();
     h->hSmallIn.release(); h->hSmallOut.release(); h->hRecOut.release(); h->hDone.release();
+    h->hScoreIn.release(); h->hScoreOut.release(); h->dScoreT.release();
     h->loop.release();
     for (hipEvent_t e : h->prof_pool) (void)hipEventDestroy(e);
     if (h->fork) (void)hipEventDestroy(h->fork);
@@ -2214,6 +2218,103 @@ int fot_loop_summaries(fot_handle *h, int32_t n_slots, fot_loop_summary *out)
         out[e] = s;
     }
     return FOT_OK;
+}
+
+// Shared body of fot_prediction_scores and fot_loop_prediction_scores: `tensor` is device memory, or host memory of
+// tensor_bytes bytes to be copied first (tensor_bytes > 0).  Checks every origin before anything is enqueued or written.
+static int prediction_scores_impl(fot_handle *h, const char *who, int32_t n, const fot_pred_origin *desc, const void *tensor,
+                                  size_t tensor_bytes, int32_t dtype, int32_t stride, int32_t E, const double *truth,
+                                  fot_pred_score *out, hipStream_t st)
+{
+    const std::string w(who);
+    if (stride < 1 || E < 1) return fail(h, FOT_ERR_INVALID, w + ": stride and E must be positive");
+    if (E > FOT_MAX_PRED_LEN) return fail(h, FOT_ERR_UNSUPPORTED, w + ": E > FOT_MAX_PRED_LEN");
+    size_t rows = 0;
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        const fot_pred_origin &d = desc[i];
+        if (d.S < 1 || d.P < 0 || d.T < 1 || d.offset < 0 || (d.skip != 0 && d.skip != 1) ||
+            (d.layout != 0 && d.layout != FOT_DYN_LAYOUT_TSP))
+            return fail(h, FOT_ERR_INVALID, w + ": an origin's S / P / T / offset / skip / layout");
+        if (!ps_horizon_fits(stride, E, d.T, d.skip))
+            return fail(h, FOT_ERR_INVALID, w + ": stride E - 1 reaches past an origin's dense track (T - skip)");
+        if (d.S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, w + ": S > FOT_MAX_SAMPLES");
+        rows += (size_t)d.P;
+        any |= d.P > 0;
+    }
+    if (!out || (any && (!truth || !tensor))) return fail(h, FOT_ERR_INVALID, w + ": NULL tensor / truth / out");
+    if (!any) {                                                    // nothing for the device to do
+        for (int i = 0; i < n; ++i) {
+            const PredScoreTerms z = ps_zero(desc[i].S);
+            out[i] = fot_pred_score{ 0.0, 0.0, 0.0, 0.0, 0.0, z.n_peds, z.n_samples, z.nll_count, z.flags };
+        }
+        return FOT_OK;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    { int r = order_begin(h, st); if (r != FOT_OK) return r; }
+    const size_t desc_b = align256(sizeof(PredOriginDev) * (size_t)n), truth_b = sizeof(double) * 2 * rows * (size_t)E;
+    HIP_TRY(h, h->hScoreIn.ensure(desc_b + truth_b));
+    HIP_TRY(h, h->hScoreOut.ensure(sizeof(fot_pred_score) * (size_t)n));
+    PredOriginDev *pd = (PredOriginDev *)h->hScoreIn.p;
+    double *pt = (double *)((char *)h->hScoreIn.p + desc_b);
+    size_t row = 0;
+    for (int i = 0; i < n; ++i) {
+        const fot_pred_origin &d = desc[i];
+        pd[i] = PredOriginDev{ d.offset, (int64_t)row, ps_scott(d.S), d.S, d.P, d.T, d.layout == FOT_DYN_LAYOUT_TSP ? 1 : 0,
+                               d.skip, 0 };
+        row += (size_t)d.P;
+    }
+    std::memcpy(pt, truth, truth_b);
+    const void *d_tensor = tensor;
+    if (tensor_bytes > 0) {
+        HIP_TRY(h, h->dScoreT.ensure(tensor_bytes));
+        HIP_TRY(h, hipMemcpyAsync(h->dScoreT.p, tensor, tensor_bytes, hipMemcpyHostToDevice, st));
+        d_tensor = h->dScoreT.p;
+    }
+    LAUNCH_TRY(h, launch_pred_scores(pd, n, d_tensor, dtype, stride, E, pt, (fot_pred_score *)h->hScoreOut.p, st));
+    { int r = order_end(h, st); if (r != FOT_OK) return r; }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    std::memcpy(out, h->hScoreOut.p, sizeof(fot_pred_score) * (size_t)n);
+    return FOT_OK;
+}
+
+int fot_prediction_scores(fot_handle *h, int32_t n_origins, const fot_pred_origin *desc, const void *tensor, int32_t dtype,
+                          int32_t on_device, int32_t stride, int32_t E, const double *truth, fot_pred_score *out,
+                          void *stream)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (n_origins < 0 || (n_origins > 0 && !desc)) return fail(h, FOT_ERR_INVALID, "fot_prediction_scores: n_origins / desc");
+    if (dtype != FOT_F32 && dtype != FOT_F64) return fail(h, FOT_ERR_INVALID, "fot_prediction_scores: dtype");
+    if (n_origins == 0) return FOT_OK;
+    size_t bytes = 0;
+    if (!on_device) {                                              // the host tensor up to the end of the last block
+        int64_t end = 0;
+        for (int i = 0; i < n_origins; ++i)
+            if (desc[i].offset >= 0 && desc[i].S > 0 && desc[i].P > 0 && desc[i].T > 0)
+                end = std::max(end, desc[i].offset + (int64_t)desc[i].S * desc[i].P * desc[i].T);
+        bytes = (dtype == FOT_F32 ? 4 : 8) * 2 * (size_t)end;
+    }
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    return prediction_scores_impl(h, "fot_prediction_scores", n_origins, desc, tensor, bytes, dtype, stride, E, truth, out, st);
+}
+
+int fot_loop_prediction_scores(fot_handle *h, int32_t n_episodes, int32_t stride, int32_t E, const double *truth,
+                               fot_pred_score *out)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopState &L = h->loop;
+    if (L.replay.set) return fail(h, FOT_ERR_INVALID, "fot_loop_prediction_scores: a replay is set (fot_loop_run owns the handle's tensor)");
+    if (!L.have_frame || L.dist_S < 1)
+        return fail(h, FOT_ERR_INVALID, "fot_loop_prediction_scores: the last frame carried no distribution (fot_loop_frame.dist_raw)");
+    if (n_episodes != (int)L.ped_off.size() - 1) return fail(h, FOT_ERR_INVALID, "fot_loop_prediction_scores: n_episodes differs from the frame's");
+    if (n_episodes == 0) return FOT_OK;
+    std::vector<fot_pred_origin> desc((size_t)n_episodes);
+    for (int e = 0; e < n_episodes; ++e)
+        desc[(size_t)e] = fot_pred_origin{ L.blk_off[(size_t)e], L.dist_S, L.ped_off[(size_t)e + 1] - L.ped_off[(size_t)e],
+                                           L.t_len[(size_t)e], 0, 1, 0 };
+    // (a frame without pedestrians left no tensor: every P is 0 and none is read)
+    return prediction_scores_impl(h, "fot_loop_prediction_scores", n_episodes, desc.data(), L.dDyn.p, 0, FOT_F64, stride, E,
+                                  truth, out, h->stream);
 }
 
 int fot_loop_run(fot_handle *h, int32_t max_steps, fot_loop_run_out *out)

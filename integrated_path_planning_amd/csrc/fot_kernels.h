@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include "fot_types.h"
 #include "fot_summary.hpp"
+#include "fot_predscore.hpp"
 
 namespace fot {
 
@@ -126,6 +127,18 @@ int launch_resample(double sgan_dt, double sim_dt, double staleness, int S, int 
                     const int32_t *ped_ep = nullptr, const int32_t *ep_ped0 = nullptr, const int64_t *ep_blk = nullptr);
 int launch_sample_dist(int S, int P, int T, int skip, const void *out, int out_dtype, int tmajor, double *dist,
                        hipStream_t st);
+// ---- fot_prediction_scores (fot_predscore.hpp): one workgroup per prediction origin
+// What the kernel needs of an origin: its block (first point in the tensor), the first row of its pedestrians in `truth`
+// ([rows][E][2]) and Scott's factor S^(-1/6), which the host forms.
+struct PredOriginDev {
+    int64_t offset, truth_row;
+    double scott;
+    int32_t S, P, T, tmajor, skip, _pad;
+};
+// desc / truth / out: HBM or pinned host memory.  The host has checked every origin (1 <= S <= FOT_MAX_SAMPLES, 1 <= E <=
+// FOT_MAX_PRED_LEN, stride E - 1 < T - skip).
+int launch_pred_scores(const PredOriginDev *desc, int n, const void *tensor, int dtype, int stride, int E,
+                       const double *truth, fot_pred_score *out, hipStream_t st);
 // What the safety metrics need of a scenario beyond its DevParams: element s of a table in HBM belongs to scenario s.
 struct SafetyScen {
     double footprint_radius;

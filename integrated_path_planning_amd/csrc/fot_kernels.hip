@@ -22,6 +22,7 @@
 #include "fot_math.hpp"
 #include "fot_kernels.h"
 #include "fot_summary.hpp"
+#include "fot_predscore.hpp"
 
 namespace fot {
 
@@ -1953,6 +1954,127 @@ k_sample_dist(int S, int P, int T, int skip, int tmajor, const TO *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------
+// fot_prediction_scores (fot_predscore.hpp): one workgroup per prediction origin
+// ---------------------------------------------------------------------------
+// Pedestrians are taken in tiles of PS_TILE_PAIRS / E whose truth points lie in LDS.  Per tile, lanes first run over the
+// pedestrians (sequential over s and j: the row sums d[s][p][.] feed the per-agent minima in registers and, through a
+// butterfly over the wave, the per-sample scene sums in LDS, one slot per (s, wave)), then over the (p, j) pairs (the
+// bandwidths and log p of a pair stay in the lane that owns it).  Lanes past the tile add 0.0.  The partial sums of the
+// lanes meet in a butterfly and the waves' in index order: the order of every sum follows from (S, P, E) alone.
+constexpr int PS_THREADS = 256;
+constexpr int PS_WAVES = PS_THREADS / WAVE;
+constexpr int PS_TILE_PAIRS = 1024;              // truth points of a tile in LDS (16 KB); >= FOT_MAX_PRED_LEN
+static_assert(PS_TILE_PAIRS >= FOT_MAX_PRED_LEN, "a tile holds one pedestrian's evaluation points at least");
+
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, WAVE);
+    return v;
+}
+
+template <typename TO>
+__global__ void __launch_bounds__(PS_THREADS)
+k_pred_scores(const PredOriginDev *__restrict__ desc, const TO *__restrict__ tensor, int stride, int E,
+              const double *__restrict__ truth, fot_pred_score *__restrict__ out)
+{
+    __shared__ double s_g[PS_TILE_PAIRS * 2];
+    __shared__ double s_scene[2][FOT_MAX_SAMPLES][PS_WAVES];
+    __shared__ double s_part[3][PS_WAVES];
+    const PredOriginDev D = desc[blockIdx.x];
+    const int S = D.S, P = D.P, T = D.T, skip = D.skip, tmajor = D.tmajor;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    if (P <= 0) {                                                    // (uniform)
+        if (tid == 0) {
+            fot_pred_score r;
+            r.ade_scene = r.fde_scene = r.ade_agent_sum = r.fde_agent_sum = r.log_lik_sum = 0.0;
+            r.n_peds = 0; r.n_samples = S; r.nll_count = 0; r.flags = 0;
+            out[blockIdx.x] = r;
+        }
+        return;
+    }
+    const TO *base = tensor + 2 * D.offset;
+    auto at = [&](int s, int p, int k) {                             // dense sample k: the prepended entry skipped
+        const int kk = k + skip;
+        return base + (tmajor ? ((int64_t)kk * S + s) * P + p : ((int64_t)s * P + p) * T + kk) * 2;
+    };
+    for (int i = tid; i < 2 * FOT_MAX_SAMPLES * PS_WAVES; i += PS_THREADS) (&s_scene[0][0][0])[i] = 0.0;
+    const int tile_peds = P < PS_TILE_PAIRS / E ? P : PS_TILE_PAIRS / E;
+    double agent_a = 0.0, agent_f = 0.0, ll = 0.0;
+    int varies = 0, nonfinite = 0;
+    for (int p0 = 0; p0 < P; p0 += tile_peds) {
+        const int np = P - p0 < tile_peds ? P - p0 : tile_peds;
+        __syncthreads();                                             // the tile before is done with s_g (first: the zeros)
+        const double *g_src = truth + ((int64_t)D.truth_row + p0) * E * 2;
+        for (int i = tid; i < np * E * 2; i += PS_THREADS) {
+            const double v = g_src[i];
+            nonfinite |= !ps_finite(v);
+            s_g[i] = v;
+        }
+        __syncthreads();
+        // ---- displacement terms: lanes over the tile's pedestrians
+        for (int c = 0; c < np; c += PS_THREADS) {                   // (every lane takes every turn: the butterflies)
+            const int pl = c + tid, p = p0 + pl;
+            const bool active = pl < np;
+            double best_a = 0.0, best_f = 0.0;
+            for (int s = 0; s < S; ++s) {
+                double row = 0.0, last = 0.0;
+                if (active)
+                    for (int j = 0; j < E; ++j) {
+                        const TO *e = at(s, p, stride * (j + 1) - 1);
+                        const double qx = (double)e[0], qy = (double)e[1];
+                        nonfinite |= !ps_finite(qx) || !ps_finite(qy);
+                        last = ps_dist(qx, qy, s_g[(pl * E + j) * 2], s_g[(pl * E + j) * 2 + 1]);
+                        row += last;
+                    }
+                const double a = row / (double)E;
+                best_a = s == 0 ? a : ps_min(best_a, a);
+                best_f = s == 0 ? last : ps_min(best_f, last);
+                const double w_row = wave_sum_f64(row), w_last = wave_sum_f64(last);
+                if (lane == 0) { s_scene[0][s][wave] += w_row; s_scene[1][s][wave] += w_last; }
+            }
+            agent_a += best_a; agent_f += best_f;                    // (a lane past the tile: 0.0)
+        }
+        // ---- KDE terms: lanes over the tile's (p, j) pairs
+        if (S >= 2)
+            for (int i = tid; i < np * E; i += PS_THREADS) {
+                const int pl = i / E, j = i - pl * E, p = p0 + pl, k = stride * (j + 1) - 1;
+                auto qx = [&](int s) { return (double)at(s, p, k)[0]; };
+                auto qy = [&](int s) { return (double)at(s, p, k)[1]; };
+                bool vx, vy;
+                const double bx = ps_bandwidth(S, D.scott, qx, &vx), by = ps_bandwidth(S, D.scott, qy, &vy);
+                varies |= vx || vy;
+                ll += ps_log_p(S, qx, qy, s_g[i * 2], s_g[i * 2 + 1], bx, by);
+            }
+    }
+    const double w_a = wave_sum_f64(agent_a), w_f = wave_sum_f64(agent_f), w_l = wave_sum_f64(ll);
+    if (lane == 0) { s_part[0][wave] = w_a; s_part[1][wave] = w_f; s_part[2][wave] = w_l; }
+    varies = __syncthreads_or(varies);                               // (also orders s_part and s_scene for thread 0)
+    nonfinite = __syncthreads_or(nonfinite);
+    if (tid != 0) return;
+    double tot[3];
+    for (int q = 0; q < 3; ++q) {
+        tot[q] = s_part[q][0];
+        for (int w = 1; w < PS_WAVES; ++w) tot[q] += s_part[q][w];
+    }
+    fot_pred_score r;
+    r.ade_scene = r.fde_scene = 0.0;
+    for (int s = 0; s < S; ++s) {
+        double a = s_scene[0][s][0], f = s_scene[1][s][0];
+        for (int w = 1; w < PS_WAVES; ++w) { a += s_scene[0][s][w]; f += s_scene[1][s][w]; }
+        a /= (double)P * (double)E; f /= (double)P;
+        r.ade_scene = s == 0 ? a : ps_min(r.ade_scene, a);
+        r.fde_scene = s == 0 ? f : ps_min(r.fde_scene, f);
+    }
+    r.ade_agent_sum = tot[0]; r.fde_agent_sum = tot[1];
+    r.log_lik_sum = varies ? tot[2] : 0.0;
+    r.n_peds = P; r.n_samples = S;
+    r.nll_count = varies ? P * E : 0;
+    r.flags = (varies ? PS_FLAG_NLL : 0) | (nonfinite ? PS_FLAG_NONFINITE : 0);
+    out[blockIdx.x] = r;
+}
+
+// ---------------------------------------------------------------------------
 // safety metrics, one wave per ego, lanes over (footprint circle, pedestrian) pairs
 // ---------------------------------------------------------------------------
 
@@ -2374,6 +2496,16 @@ int launch_sample_dist(int S, int P, int T, int skip, const void *out, int out_d
     if (S <= 0) return 0;
     if (out_dtype == FOT_F32) k_sample_dist<float><<<S, 256, 0, st>>>(S, P, T, skip, tmajor, (const float *)out, dist);
     else k_sample_dist<double><<<S, 256, 0, st>>>(S, P, T, skip, tmajor, (const double *)out, dist);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_pred_scores(const PredOriginDev *desc, int n, const void *tensor, int dtype, int stride, int E,
+                       const double *truth, fot_pred_score *out, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    if (dtype == FOT_F32) k_pred_scores<float><<<n, PS_THREADS, 0, st>>>(desc, (const float *)tensor, stride, E, truth, out);
+    else k_pred_scores<double><<<n, PS_THREADS, 0, st>>>(desc, (const double *)tensor, stride, E, truth, out);
     FOT_LAUNCH_CHECK();
     return 0;
 }

@@ -566,6 +566,55 @@ class BatchPlanner:
         _abi.check(self._h, self._lib.fot_loop_summaries(self._h, n, _addr(out)))
         return out[:n]
 
+    PRED_SCORE_DT = np.dtype(_abi.PredScore)
+    PRED_ORIGIN_DT = np.dtype(_abi.PredOrigin)
+
+    def prediction_scores(self, tensor, origins, truth, stride: int, E: int, stream: Optional[int] = None) -> np.ndarray:
+        """``fot_prediction_scores``: one ``fot_pred_score`` record (``PRED_SCORE_DT``) per prediction origin -- best-of-N
+        ADE / FDE terms, scene level and per agent, and the KDE log-likelihood of the truth under the samples.
+
+        tensor: the samples, a NumPy array or a contiguous ``torch`` CUDA tensor (float32 or float64; any shape, read as a
+        flat run of points); origins: ``(offset, S, P, T, t_major, skip)`` per origin -- its block starts at point
+        ``offset``, laid out [S, P, T, 2] or, with ``t_major``, [T, S, P, 2]; ``skip`` 1: entry 0 of every track is the
+        prepended current position; truth: [sum P, E, 2], the origins' pedestrians one after the other; evaluation indices
+        ``stride * j - 1``, j = 1 .. E, of the dense track.  A float32 tensor gives the scores of the rounded samples."""
+        on_device = hasattr(tensor, "data_ptr")
+        if on_device:
+            import torch
+            if not (tensor.is_cuda and tensor.is_contiguous() and tensor.dtype in (torch.float32, torch.float64)):
+                raise TypeError("prediction_scores: a contiguous CUDA tensor of float32 or float64")
+            code, n_points, ptr = (_abi.F32 if tensor.dtype == torch.float32 else _abi.F64), tensor.numel() // 2, tensor.data_ptr()
+            if stream is None:
+                torch.cuda.current_stream(tensor.device).synchronize()   # (the library reads it on its own stream)
+        else:
+            tensor = np.ascontiguousarray(tensor, dtype=np.float32 if np.asarray(tensor).dtype == np.float32 else np.float64)
+            code, n_points, ptr = (_abi.F32 if tensor.dtype == np.float32 else _abi.F64), tensor.size // 2, tensor.ctypes.data
+        desc = np.zeros(len(origins), dtype=self.PRED_ORIGIN_DT)
+        for i, (offset, S, P, T, t_major, skip) in enumerate(origins):
+            desc[i] = (int(offset), int(S), int(P), int(T), _abi.DYN_LAYOUT_TSP if t_major else 0, int(skip), 0)
+            if offset >= 0 and min(S, P, T) > 0 and int(offset) + int(S) * int(P) * int(T) > n_points:
+                raise ValueError(f"prediction_scores: origin {i} reaches past the tensor ({n_points} points)")
+        truth = np.ascontiguousarray(truth, dtype=np.float64)
+        rows = int(desc["P"].clip(min=0).sum())
+        if truth.size != rows * max(int(E), 0) * 2:
+            raise ValueError(f"prediction_scores: truth must be [sum P = {rows}, E = {E}, 2]")
+        out = np.zeros(max(len(desc), 1), dtype=self.PRED_SCORE_DT)
+        _abi.check(self._h, self._lib.fot_prediction_scores(
+            self._h, len(desc), _addr(desc) if len(desc) else None, C.c_void_p(ptr) if n_points else None, code,
+            int(on_device), int(stride), int(E), _addr(truth) if truth.size else None, _addr(out),
+            C.c_void_p(stream) if stream else None))
+        return out[:len(desc)]
+
+    def loop_prediction_scores(self, n_episodes: int, stride: int, E: int, truth: np.ndarray) -> np.ndarray:
+        """``fot_loop_prediction_scores``: the records of the distribution blocks the last ``loop_step`` / ``loop_plan``
+        frame with ``dist_raw`` left in the handle's tensor (the samples stay in HBM); truth [sum P, E, 2] in the frame's
+        pedestrian order."""
+        truth = np.ascontiguousarray(truth, dtype=np.float64)
+        out = np.zeros(max(int(n_episodes), 1), dtype=self.PRED_SCORE_DT)
+        _abi.check(self._h, self._lib.fot_loop_prediction_scores(self._h, int(n_episodes), int(stride), int(E),
+                                                                 _addr(truth) if truth.size else None, _addr(out)))
+        return out[:int(n_episodes)]
+
     def _loop_frame(self, frame: dict):
         """fot_loop_frame from the dictionary ``loop_plan`` / ``loop_step`` take (+ the arrays it points into)."""
         f, keep = _abi.LoopFrame(), []

@@ -106,3 +106,43 @@ class PredictionResampler:
             _abi.OUT_DEVICE | (_abi.OUT_TMAJOR if t_major else 0), C.byref(t_out),
             None if dist is None else dist.ctypes.data_as(_dp), C.c_void_p(stream) if stream else None))
         return t_out.value, dist
+
+
+def prediction_scores(engine: BatchPlanner, samples, truth, stride: int, t_major: bool = False, skip: int = 0,
+                      stream: Optional[int] = None) -> np.ndarray:
+    """Score sample predictions on the device: per origin what the reference's ``_standard_ade_fde_details`` and
+    ``_kde_nll_details`` (src/core/metrics.py:31-176) add to their totals for it (``fot_prediction_scores``).
+
+    samples: one origin's distribution [S, P, T, 2] ([T, S, P, 2] with ``t_major``) or a sequence of them, NumPy arrays or
+    ``torch`` CUDA tensors of one element type (float32 / float64; a float32 tensor gives the scores of the rounded
+    samples, the arithmetic is float64 either way); a sequence of device tensors is scored origin by origin where it lies,
+    a sequence of arrays in one launch.  truth: per origin [P, E, 2] -- the pedestrians' positions ``stride * j`` steps
+    after the origin, j = 1 .. E, compared with dense samples ``stride * j - 1 + skip``.  Returns one record per origin
+    (``BatchPlanner.PRED_SCORE_DT``: ade_scene, fde_scene, ade_agent_sum, fde_agent_sum, log_lik_sum, n_peds, n_samples,
+    nll_count, flags)."""
+    single = hasattr(samples, "shape") and len(samples.shape) == 4
+    blocks = [samples] if single else list(samples)
+    truths = [np.asarray(truth, dtype=np.float64)] if single else [np.asarray(t, dtype=np.float64) for t in truth]
+    if len(blocks) != len(truths):
+        raise ValueError("prediction_scores: one truth block per origin")
+    E = {t.shape[1] for t in truths}
+    if len(E) > 1:
+        raise ValueError("prediction_scores: the origins of one call share E")
+    E = E.pop() if E else 1
+
+    def dims(b):
+        if len(b.shape) != 4 or b.shape[-1] != 2:
+            raise ValueError(f"prediction_scores: a distribution is [S, P, T, 2], got {tuple(b.shape)}")
+        return (b.shape[1], b.shape[2], b.shape[0]) if t_major else (b.shape[0], b.shape[1], b.shape[2])
+
+    if blocks and hasattr(blocks[0], "data_ptr"):                   # device tensors: each where it lies
+        out = [engine.prediction_scores(b, [(0,) + dims(b) + (t_major, skip)], t, stride, E, stream)
+               for b, t in zip(blocks, truths)]
+        return np.concatenate(out) if out else np.zeros(0, dtype=engine.PRED_SCORE_DT)
+    dt = np.float32 if blocks and all(np.asarray(b).dtype == np.float32 for b in blocks) else np.float64
+    flat = [np.ascontiguousarray(b, dtype=dt).reshape(-1, 2) for b in blocks]
+    off = np.concatenate([[0], np.cumsum([len(f) for f in flat])])
+    origins = [(int(off[i]),) + dims(b) + (t_major, skip) for i, b in enumerate(blocks)]
+    tensor = np.concatenate(flat) if flat else np.zeros((0, 2), dt)
+    tr = np.concatenate([t.reshape(-1, E, 2) for t in truths]) if truths else np.zeros((0, E, 2))
+    return engine.prediction_scores(tensor, origins, tr, stride, E, stream)
