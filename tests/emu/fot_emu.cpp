@@ -443,3 +443,18 @@ extern "C" void emu_spline_xy(int n_knots, const double *coef9n, int n, const do
     v.n = n_knots; v._pad = 0;
     for (int i = 0; i < n; ++i) spline_xy(v, s[i], x[i], y[i]);
 }
+
+// spline_index / global_search_count (fot_math.hpp) on a knot array alone, for the long-path test
+extern "C" void emu_spline_index(int n_knots, const double *knots, int n, const double *s, int32_t *out)
+{
+    SplineView v = SplineView();
+    v.s = knots; v.n = n_knots;
+    for (int i = 0; i < n; ++i) out[i] = spline_index(v, s[i]);
+}
+
+extern "C" int emu_global_search_count(int n_knots, const double *knots)
+{
+    SplineView v = SplineView();
+    v.s = knots; v.n = n_knots;
+    return global_search_count(v);
+}

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate golden vectors by running the REFERENCE planner (build container only).
 
-Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py [--ref /root/reference]
+Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py [--ref /root/reference] [--only NAME | rnd | crawl | long]
 
 The reference (mnhrk15/integrated_path_planning) is imported read-only from
 ``--ref``; its only missing dependency on the planner path, ``loguru`` (logging),
@@ -304,6 +304,76 @@ def build_fuzz_cases(seed_inst):
     return cases
 
 
+# (t0, shift): the pedestrians of scenario_01 at time t0, their frame's origin `shift` away from the ego -- chosen so that
+# every case has colliding candidates beside passing ones (check_long_case)
+LONG_PEDS = {"long_65_mid": (4.0, (15.0, 0.0)), "long_513_mid": (6.0, (0.0, 0.0)), "long_513_stale": (7.0, (10.0, 3.0)),
+             "long_2000_global": (7.0, (10.0, 3.0)), "long_2000_multi": (6.0, (20.0, -3.0))}
+LONG_END_STATIC = [[1.9, 1.2], [1.0, -1.6], [4.0, 0.2]]      # long_2000_end: in the ego's frame, about the end of the road
+
+
+def build_long_cases():
+    """Reference paths of 65, 513 and 2000 knots (tests/long_paths_common.py: one road, a path of n knots is its first n
+    waypoints): either side of what the plan kernels stage in LDS (28 / 64 / 512 knots), a global nearest-point scan of
+    tens of thousands of samples, a binary search eleven levels deep, a cached window at its edge, horizons that run off
+    the end of a long spline.  Planner constants of scenario_01."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import long_paths_common as lp
+    from oracle import oracle as orc                                       # (samples points along the path, nothing else)
+    assert lp.PLANNER == SCEN01                                            # (what the GPU tests on the same road plan with)
+    cases = []
+
+    def add(name, n_knots, frac, planner=SCEN01, d=0.0, dyaw=0.0, v=5.0, a=0.0, back=None, **kw):
+        wx, wy = lp.road(n_knots)
+        sp = orc.Spline(wx, wy)
+        s_end = float(sp.coeffs()[0][-1])
+        s = frac * s_end if back is None else s_end - back
+        x, y, yaw = lp.pose_at(sp, s, d)
+        pose = lp.pose_at(sp, s)                                            # obstacles are placed about the path itself
+        obstacles = kw.pop("obstacles")(pose)
+        prev_s = kw.pop("prev_s", None)
+        c = dict(name=name, path=dict(wx=[float(q) for q in wx], wy=[float(q) for q in wy]), planner=planner,
+                 ego=[float(x), float(y), float(yaw + dyaw), float(v), float(a)],
+                 target_speed=kw.pop("target_speed", 6.0), overrides=kw.pop("overrides", None),
+                 max_stop=kw.pop("max_stop", None), prev_s=None if prev_s is None else float(s + prev_s),
+                 last_kappa=kw.pop("last_kappa", 0.0), footprint=kw.pop("footprint", None),
+                 static=obstacles.get("static", np.empty((0, 2))), dyn=obstacles.get("dyn"), dist=obstacles.get("dist"))
+        assert not kw, kw
+        cases.append(c)
+
+    def peds(t0, shift, static=None):
+        """the 14 scripted pedestrians of scenario_01 at time t0, moved beside the ego (+ static points in its frame)"""
+        def place(pose):
+            o = dict(dyn=lp.to_pose(scen01_peds(t0), pose, shift))
+            if static is not None:
+                o["static"] = lp.to_pose(static, pose)
+            return o
+        return place
+
+    add("long_65_mid", 65, 0.5, obstacles=peds(*LONG_PEDS["long_65_mid"], static=[[14.0, 2.2], [22.0, -1.9], [30.0, 0.4], [-6.0, 0.0]]))
+    add("long_513_mid", 513, 0.6, planner=dict(SCEN01, chance_epsilon=0.2), prev_s=-0.45, v=4.5, a=0.2, last_kappa=0.003,
+        obstacles=lambda pose: dict(dist=lp.to_pose(np.stack([scen01_peds(LONG_PEDS["long_513_mid"][0] + 0.2 * k) + 0.03 * k for k in range(8)]),
+                                                    pose, LONG_PEDS["long_513_mid"][1])))
+    add("long_513_stale", 513, 0.6, prev_s=-40.0, obstacles=peds(*LONG_PEDS["long_513_stale"]))
+    add("long_2000_global", 2000, 0.8, d=0.4, dyaw=0.1, v=4.0, a=0.3,
+        obstacles=peds(*LONG_PEDS["long_2000_global"], static=[[16.0, -2.0], [25.0, 1.5], [33.0, 0.0]]))
+    add("long_2000_end", 2000, None, back=2.0, v=3.0, a=-0.5, target_speed=2.0,
+        obstacles=lambda pose: dict(static=lp.to_pose(LONG_END_STATIC, pose)))
+    add("long_2000_multi", 2000, 0.3, v=3.0, a=-0.5, target_speed=0.0, max_stop=6.0,
+        overrides=dict(max_accel=6.0, max_lat_accel=6.0), footprint=dict(length=4.5, width=1.8, n=3),
+        obstacles=peds(*LONG_PEDS["long_2000_multi"]))
+    return cases
+
+
+def check_long_case(name, z):
+    """What a long case must exercise (decided when it is generated): a selected path (except at the very end of the
+    road), three distinct candidate statuses, and candidates that collide beside candidates that pass."""
+    status = set(int(v) for v in z["cand_status"])
+    ok, hit = STATUS_NAMES.index("ok"), STATUS_NAMES.index("collision_error")
+    assert name == "long_2000_end" or int(z["best_index"]) >= 0, f"{name}: no selected path"
+    assert len(status) >= 3, f"{name}: candidate statuses {sorted(status)}"
+    assert ok in status and hit in status, f"{name}: candidate statuses {sorted(status)} (move its obstacles)"
+
+
 # what the 36 000-seed sweep of round 4 flagged (profiles/r04_fuzz36000.log, gpurun_out/r04_crawl.txt)
 CRAWL_CASES = [(17857, 3), (19368, 3)]
 
@@ -409,6 +479,7 @@ def run_case(ref, case, out_dir):
     ok = int((out["cand_status"] == 6).sum())
     print(f"{case['name']:22s} n_cand={n:5d} ok={ok:5d} best={int(out['best_index']):5d} "
           f"cost={float(out['best_cost']):.6f} stats={out['stats'].tolist()}")
+    return out
 
 
 def run_time_cache(ref, out_dir):
@@ -452,6 +523,10 @@ def main():
     if args.only == "crawl":                         # the fuzz instances a sweep flagged
         for case in build_fuzz_cases(CRAWL_CASES):
             run_case(ref, case, HERE)
+        return
+    if args.only == "long":                          # reference paths of 65 / 513 / 2000 knots
+        for case in build_long_cases():
+            check_long_case(case["name"], run_case(ref, case, HERE))
         return
     if args.only == "rnd":                           # the random block alone (--random N of them)
         for case in build_random_cases(args.random):

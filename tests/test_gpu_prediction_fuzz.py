@@ -45,7 +45,11 @@ def _torch_dtype(dt):
 def _device_out(n, dt):
     """A device tensor of n values plus as many guard values behind them, all SENTINEL."""
     import torch
-    return torch.full((2 * n,), SENTINEL, dtype=_torch_dtype(dt), device=torch.device("cuda", 0))
+    buf = torch.full((2 * n,), SENTINEL, dtype=_torch_dtype(dt), device=torch.device("cuda", 0))
+    # The fill runs on torch's default stream; the library is handed stream 0 = its OWN stream, which is non-blocking and
+    # waits for no other.  Without this the fill can land AFTER the library's kernel and leave the tensor all SENTINEL.
+    torch.cuda.synchronize()
+    return buf
 
 
 def _finish_device(buf, n):

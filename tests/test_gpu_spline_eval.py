@@ -28,11 +28,14 @@ def _waypoints(kind):
     if kind == "arc":
         a = np.linspace(0.0, 1.5 * np.pi, 19)
         return 5.0 * np.cos(a), 5.0 * np.sin(a)
+    if kind == "road1500":                                                  # eleven levels of spline_index's binary search,
+        import long_paths_common as lp                                      # read from HBM by every kernel that plans on it
+        return lp.road(1500)
     rng = np.random.default_rng(25)
     return np.cumsum(rng.uniform(1.0, 6.0, 25)), np.cumsum(rng.normal(0.0, 2.0, 25))
 
 
-@pytest.fixture(scope="module", params=["straight", "arc", "random25"])
+@pytest.fixture(scope="module", params=["straight", "arc", "random25", "road1500"])
 def pair(request):
     wx, wy = _waypoints(request.param)
     return BatchPlanner(waypoints=(wx, wy)), orc.Spline(wx, wy), wx, wy
