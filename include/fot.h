@@ -169,10 +169,11 @@ const char *fot_version(void);
  * fot_resample_params, fot_safety, fot_loop_frame, fot_loop_request, fot_wire_header, then FOT_MAX_NT, FOT_MAX_CIRCLES,
  * FOT_MAX_TI, FOT_MAX_TV, FOT_MAX_BRAKE, FOT_MAX_SAMPLES, FOT_MAX_PRED_LEN, FOT_PROFILE_KERNELS, FOT_MARGIN_GROUPS,
  * sizeof of fot_loop_config, fot_loop_step_out, fot_loop_replay, fot_loop_run_out, fot_loop_summary, fot_pred_origin,
- * fot_pred_score.
+ * fot_pred_score, fot_sgan_desc, then FOT_SGAN_MAX_EMBEDDING, FOT_SGAN_MAX_HIDDEN, FOT_SGAN_MAX_MLP,
+ * FOT_SGAN_MAX_BOTTLENECK, FOT_SGAN_MAX_OBS_LEN, FOT_SGAN_MAX_PEDS, FOT_SGAN_POOL_HIDDEN.
  * Returns the number of words the library knows (FOT_ABI_INFO_WORDS of ITS header). */
 #define FOT_ABI_VERSION 8
-#define FOT_ABI_INFO_WORDS 27
+#define FOT_ABI_INFO_WORDS 35
 int32_t fot_abi_info(int32_t cap, int32_t *out);
 
 /* FrenetPlanner.__init__ (frenet_planner.py:149-225).  device < 0: current device. */
@@ -641,6 +642,73 @@ int fot_prediction_scores(fot_handle *h, int32_t n_origins, const fot_pred_origi
                           void *stream);
 int fot_loop_prediction_scores(fot_handle *h, int32_t n_episodes, int32_t stride, int32_t E, const double *truth,
                                fot_pred_score *out);
+
+/* ---- Social-GAN sample generation on the device -------------------------------------------------------------------------
+ * float32 inference of the reference's default predictor (src/prediction/sgan_vendor/models.py, TrajectoryGenerator.forward
+ * in eval mode, then relative_to_abs) for many scenes at once; a scene is one episode's pedestrians.  What the reference
+ * runs as num_samples forward passes (trajectory_predictor.py:340-346) is one call: the encoder runs once per pedestrian,
+ * the first pooling and the context MLP once per scene, and only the part behind the noise once per sample.  The output
+ * [S][pred_len][sum P][2] float32 is what fot_loop_frame.dist_raw and fot_resample_predictions read.
+ *
+ * Supported: num_layers 1; pooling none ('lstm') or the pool net ('sgan'), also at every decoder step; noise mixed per
+ * pedestrian or per scene; a noise_dim of one entry, 0 included (without noise and pooling and with encoder_h_dim ==
+ * decoder_h_dim the context MLP is absent, as in the reference).  BatchNorm is an eval-mode affine map: the caller folds
+ * it into the Linear in front of it, the library never sees it.  FOT_ERR_UNSUPPORTED: social pooling (FOT_SGAN_SPOOL),
+ * dropout > 0, num_layers > 1, a dimension above its FOT_SGAN_MAX_*, pred_len > FOT_MAX_PRED_LEN, S > FOT_MAX_SAMPLES,
+ * a scene of more than FOT_SGAN_MAX_PEDS pedestrians.
+ *
+ * Weights: ONE packed float32 blob, every matrix row-major [out][in] as torch stores it, LSTM gates in torch's order
+ * i, f, g, o, with E = embedding_dim, He / Hd = encoder / decoder_h_dim, M = mlp_dim, B = bottleneck_dim, nd = noise_dim:
+ *   encoder      spatial_embedding W [E][2], b [E]; LSTM W_ih [4 He][E], W_hh [4 He][He], b_ih [4 He], b_hh [4 He]
+ *   pool net     (pooling) spatial_embedding W [E][2], b [E]; W [512][E + He], b [512]; W [B][512], b [B]
+ *   context MLP  (noise, pooling or He != Hd) W [M][He + B], b [M]; W [Hd - nd][M], b [Hd - nd]   (B = 0 without pooling)
+ *   decoder      spatial_embedding W [E][2], b [E]; LSTM W_ih [4 Hd][E], W_hh [4 Hd][Hd], b_ih [4 Hd], b_hh [4 Hd];
+ *                hidden2pos W [2][Hd], b [2]
+ *   per step     (pooling and pool_every_timestep) pool net as above with Hd for He; MLP W [M][Hd + B], b [M]; W [Hd][M], b [Hd]
+ * fot_sgan_weight_count gives the blob's length for a descriptor (no handle, no device: it also answers the refusals
+ * above).  fot_sgan_load replaces the handle's model; fot_sgan_unload drops it.
+ *
+ * fot_sgan_sample (synchronous: `out` is written when it returns; enqueued on `stream`, NULL = the handle's):
+ *   ped_off [n_scenes + 1] host, non-decreasing from 0; empty scenes are allowed
+ *   obs     [obs_len][sum P][2] float32 absolute positions (the observer's window); the displacements the model reads are
+ *           formed here: row 0 zero, row t = obs[t] - obs[t - 1] in float32 (observer.py:126-135)
+ *   noise   [S][rows][nd] float32, rows = sum P (FOT_SGAN_NOISE_PED) or n_scenes (FOT_SGAN_NOISE_GLOBAL); may be NULL when
+ *           nd == 0.  The caller draws it (the reference takes the same through user_noise)
+ *   flags   FOT_OUT_DEVICE: out is device memory; FOT_SGAN_OBS_DEVICE / FOT_SGAN_NOISE_DEVICE: so is obs / noise
+ *   out     [S][pred_len][sum P][2] float32 absolute positions
+ * Every output element is one thread's sum in index order and the pool's max is exact in any order: a scene's numbers are
+ * the same bits alone and inside any launch, whatever the placement of the tensors.
+ * FOT_ERR_INVALID, nothing changed: no model loaded, n_scenes < 0, offsets not starting at 0 or decreasing, S < 1, a NULL
+ * tensor that is needed; fot_sgan_load with n other than fot_sgan_weight_count's. */
+#define FOT_SGAN_MAX_EMBEDDING 64
+#define FOT_SGAN_MAX_HIDDEN 128      /* encoder_h_dim, decoder_h_dim */
+#define FOT_SGAN_MAX_MLP 1024
+#define FOT_SGAN_MAX_BOTTLENECK 1024
+#define FOT_SGAN_MAX_OBS_LEN 32
+#define FOT_SGAN_MAX_PEDS 256        /* pedestrians of one scene */
+#define FOT_SGAN_POOL_HIDDEN 512     /* first layer of the pool net: fixed by the reference (models.py:159) */
+#define FOT_SGAN_POOL_NONE 0
+#define FOT_SGAN_POOL_NET 1
+#define FOT_SGAN_SPOOL 2
+#define FOT_SGAN_NOISE_PED 0
+#define FOT_SGAN_NOISE_GLOBAL 1
+#define FOT_SGAN_OBS_DEVICE 4
+#define FOT_SGAN_NOISE_DEVICE 8
+typedef struct fot_sgan_desc {
+    int32_t obs_len, pred_len;
+    int32_t embedding_dim, encoder_h_dim, decoder_h_dim, mlp_dim, bottleneck_dim, noise_dim;
+    int32_t num_layers;
+    int32_t pooling_type;           /* FOT_SGAN_POOL_NONE | FOT_SGAN_POOL_NET | FOT_SGAN_SPOOL (refused) */
+    int32_t pool_every_timestep;    /* counts only with pooling (models.py:81) */
+    int32_t noise_mix_type;         /* FOT_SGAN_NOISE_PED | FOT_SGAN_NOISE_GLOBAL */
+    float dropout;                  /* > 0 is refused */
+    int32_t _pad;
+} fot_sgan_desc;
+int fot_sgan_weight_count(const fot_sgan_desc *desc, int64_t *n);
+int fot_sgan_load(fot_handle *h, const fot_sgan_desc *desc, int64_t n, const float *weights);
+int fot_sgan_unload(fot_handle *h);
+int fot_sgan_sample(fot_handle *h, int32_t n_scenes, const int32_t *ped_off, const void *obs, int32_t S, const void *noise,
+                    int32_t flags, void *out, void *stream);
 
 /* Host utility (no GPU): the first kmax samples of the 15 path arrays of records[index[i]], i < n, as one dense block
  * out[15][n][kmax] in fot_result array order (t .. c) -- what a history keeps of a step's records. */

@@ -149,6 +149,12 @@ class PredScore(C.Structure):                                      # fot_pred_sc
     _fields_ = [(n, C.c_double) for n in PRED_SCORE_F64] + [(n, C.c_int32) for n in PRED_SCORE_I32]
 
 
+class SganDesc(C.Structure):                                      # fot_sgan_desc
+    _fields_ = [(n, C.c_int32) for n in ("obs_len", "pred_len", "embedding_dim", "encoder_h_dim", "decoder_h_dim", "mlp_dim",
+                                         "bottleneck_dim", "noise_dim", "num_layers", "pooling_type", "pool_every_timestep",
+                                         "noise_mix_type")] + [("dropout", C.c_float), ("_pad", C.c_int32)]
+
+
 class Batch(C.Structure):
     _fields_ = [("n_inst", C.c_int32), ("obstacle_dtype", C.c_int32),
                 ("ego", C.POINTER(Ego)), ("target_speed", C.POINTER(C.c_double)),
@@ -171,13 +177,20 @@ SYMBOLS = ["fot_version", "fot_abi_info", "fot_create", "fot_destroy", "fot_live
            "fot_pack_records_device", "fot_pack_records_host", "fot_unpack_records", "fot_profile_enable", "fot_profile_read", "fot_profile_kernel_name",
            "fot_add_scenario", "fot_set_scenario_path_waypoints", "fot_set_scenario_path_coeffs",
            "fot_plan_batch_scenarios", "fot_plan_batch_scenarios_device", "fot_get_scenario_path_coeffs",
-           "fot_loop_begin_scenarios", "fot_loop_set_scenario_static"]
+           "fot_loop_begin_scenarios", "fot_loop_set_scenario_static",
+           "fot_sgan_weight_count", "fot_sgan_load", "fot_sgan_unload", "fot_sgan_sample"]
 PROFILE_KERNELS = 3                      # FOT_PROFILE_KERNELS (include/fot.h)
 ABI_VERSION = 8                          # FOT_ABI_VERSION
 MAX_TI, MAX_TV, MAX_BRAKE, MAX_PRED_LEN = 64, 32, 32, 32
 EGO_IS_FRENET = 3                        # FOT_EGO_IS_FRENET (fot_ego.has_prev_s)
 MARGIN_GROUPS = 8                        # FOT_MARGIN_GROUPS
 MAX_SCENARIOS = 64                       # FOT_MAX_SCENARIOS
+# Social-GAN sample generation (fot_sgan_*): capacities, descriptor codes, placement flags of fot_sgan_sample
+SGAN_MAX_EMBEDDING, SGAN_MAX_HIDDEN, SGAN_MAX_MLP, SGAN_MAX_BOTTLENECK, SGAN_MAX_OBS_LEN, SGAN_MAX_PEDS = 64, 128, 1024, 1024, 32, 256
+SGAN_POOL_HIDDEN = 512
+SGAN_POOL_NONE, SGAN_POOL_NET, SGAN_SPOOL = 0, 1, 2
+SGAN_NOISE_PED, SGAN_NOISE_GLOBAL = 0, 1
+SGAN_OBS_DEVICE, SGAN_NOISE_DEVICE = 4, 8
 MARGIN_NAMES = ["speed", "accel", "curvature", "lat_accel", "road", "collision", "stop_filter", "structural"]
 
 _lib = None
@@ -189,7 +202,9 @@ def abi_expectation():
             C.sizeof(ResampleParams), C.sizeof(Safety), C.sizeof(LoopFrame), C.sizeof(LoopRequest), C.sizeof(WireHeader),
             MAX_NT, MAX_CIRCLES, MAX_TI, MAX_TV, MAX_BRAKE, MAX_SAMPLES, MAX_PRED_LEN, PROFILE_KERNELS, MARGIN_GROUPS,
             C.sizeof(LoopConfig), C.sizeof(LoopStepOut), C.sizeof(LoopReplay), C.sizeof(LoopRunOut), C.sizeof(LoopSummary),
-            C.sizeof(PredOrigin), C.sizeof(PredScore)]
+            C.sizeof(PredOrigin), C.sizeof(PredScore),
+            C.sizeof(SganDesc), SGAN_MAX_EMBEDDING, SGAN_MAX_HIDDEN, SGAN_MAX_MLP, SGAN_MAX_BOTTLENECK, SGAN_MAX_OBS_LEN,
+            SGAN_MAX_PEDS, SGAN_POOL_HIDDEN]
 
 
 ABI_WORD_NAMES = ["FOT_ABI_VERSION", "sizeof(fot_params)", "sizeof(fot_ego)", "sizeof(fot_overrides)", "sizeof(fot_result)",
@@ -197,7 +212,9 @@ ABI_WORD_NAMES = ["FOT_ABI_VERSION", "sizeof(fot_params)", "sizeof(fot_ego)", "s
                   "sizeof(fot_loop_request)", "sizeof(fot_wire_header)", "FOT_MAX_NT", "FOT_MAX_CIRCLES", "FOT_MAX_TI",
                   "FOT_MAX_TV", "FOT_MAX_BRAKE", "FOT_MAX_SAMPLES", "FOT_MAX_PRED_LEN", "FOT_PROFILE_KERNELS",
                   "FOT_MARGIN_GROUPS", "sizeof(fot_loop_config)", "sizeof(fot_loop_step_out)", "sizeof(fot_loop_replay)",
-                  "sizeof(fot_loop_run_out)", "sizeof(fot_loop_summary)", "sizeof(fot_pred_origin)", "sizeof(fot_pred_score)"]
+                  "sizeof(fot_loop_run_out)", "sizeof(fot_loop_summary)", "sizeof(fot_pred_origin)", "sizeof(fot_pred_score)",
+                  "sizeof(fot_sgan_desc)", "FOT_SGAN_MAX_EMBEDDING", "FOT_SGAN_MAX_HIDDEN", "FOT_SGAN_MAX_MLP",
+                  "FOT_SGAN_MAX_BOTTLENECK", "FOT_SGAN_MAX_OBS_LEN", "FOT_SGAN_MAX_PEDS", "FOT_SGAN_POOL_HIDDEN"]
 
 
 def _check_abi(L, path):
@@ -402,6 +419,10 @@ def lib():
     L.fot_loop_summaries.argtypes = [vp, C.c_int32, vp]
     L.fot_prediction_scores.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
     L.fot_loop_prediction_scores.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
+    L.fot_sgan_weight_count.argtypes = [C.POINTER(SganDesc), C.POINTER(C.c_int64)]
+    L.fot_sgan_load.argtypes = [vp, C.POINTER(SganDesc), C.c_int64, vp]
+    L.fot_sgan_unload.argtypes = [vp]
+    L.fot_sgan_sample.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp]
     L.fot_gather_paths.argtypes = [vp, C.c_int32, vp, C.c_int32, vp]
     L.fot_wire_n_total.argtypes = [vp]
     L.fot_wire_record_bytes.argtypes = [C.c_int32]

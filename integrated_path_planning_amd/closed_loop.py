@@ -447,6 +447,8 @@ class BatchedClosedLoop:
                  prediction_scores: bool = False):
         """sample_source: the multi-sample predictor in front of the planner -- a callable
         ``(obs_last [P, 2], obs_prev [P, 2]) -> raw samples [S, pred_len, P, 2]`` at the predictor's own time step
+        (a source with the attribute ``needs_history = True``, such as ``prediction.SganSampler``, is called with the
+        observer's whole window ``[obs_len, P, 2]`` float32 and the running episodes' pedestrian offsets instead)
         (what S forward passes of Social-GAN on PyTorch-ROCm return for the pedestrians of all running episodes; the
         tests script one).  With it the episodes plan against the whole distribution when the configuration says
         ``distribution_aware_planning`` (integrated_simulator.py:459-460, 514-525), otherwise against the sample closest
@@ -705,6 +707,15 @@ class BatchedClosedLoop:
         return self.engine.safety_metrics_cat(egos, off, pos, vel, self.ego_radius, self.ped_radius,
                                               use_footprint=self.footprint is not None)
 
+    def _draw_samples(self, obs_last, obs_prev, rows, off):
+        """One call of the sample source.  A source with ``needs_history = True`` (``prediction.SganSampler``) is handed the
+        observer's whole window for the running episodes' rows, [obs_len, n, 2] float32 as the observer hands it over
+        (observer.py:126-135), and their pedestrian offsets; any other source the last two samples, as before."""
+        if not getattr(self.sample_source, "needs_history", False):
+            return self.sample_source(obs_last, obs_prev)
+        window = np.stack([h[rows] for h in self.observer.history], axis=0).astype(np.float32)
+        return self.sample_source(window, np.asarray(off, dtype=np.int32))
+
     def _predict(self, sel, off, pos):
         """_update_prediction (:424-527): one launch over the pedestrians of all running episodes.  Returns the
         prediction [sum P, T, 2] (None while the observer fills), per episode whether the current positions are
@@ -723,7 +734,8 @@ class BatchedClosedLoop:
                 # the observer hands over float32 tensors (observer.py:134); the samples are resampled to the
                 # simulation step on the device (process_prediction, :233-313), all pedestrians in one launch
                 o32 = obs.astype(np.float32).astype(np.float64)
-                raw = np.asarray(self.sample_source(o32[1], o32[0]), dtype=np.float64)       # [S, pred_len, sum P, 2]
+                raw = self._draw_samples(o32[1], o32[0], rows, off)
+                raw = np.asarray(raw.detach().cpu().numpy() if hasattr(raw, "detach") else raw, dtype=np.float64)   # [S, pred_len, sum P, 2]
                 dist = self.resampler.process_prediction(raw, anchor_pos=o32[1], staleness=stale)
                 self._score_dist = dist                               # (what the reference records of the step, :447)
                 if raw.shape[0] == 1:
@@ -1033,7 +1045,7 @@ class BatchedClosedLoop:
             pred_src = (o32, stale)
             if self._device_samples:
                 # the multi-sample predictor's raw output stays in HBM: handed to the step as a device pointer
-                raw = self.sample_source(o32[1].astype(np.float64), o32[0].astype(np.float64))
+                raw = self._draw_samples(o32[1].astype(np.float64), o32[0].astype(np.float64), self._rows_of(sel), off)
                 if not (hasattr(raw, "data_ptr") and raw.is_cuda and raw.is_contiguous() and raw.dim() == 4):
                     raise TypeError("device_samples: the sample source must return a contiguous CUDA tensor [S, pred_len, sum P, 2]")
                 import torch

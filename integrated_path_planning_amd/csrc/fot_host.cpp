@@ -21,6 +21,7 @@
 #include "fot_replay.hpp"
 #include "fot_summary.hpp"
 #include "fot_setup.hpp"
+#include "fot_sgan.h"
 
 using namespace fot;
 
@@ -255,6 +256,14 @@ struct fot_handle {
     DevBuf dScoreT;                          // ... the device copy of a host tensor
     DevBuf dTmpA, dTmpB, dTmpC, dTmpD;
     LoopState loop;
+    // fot_sgan_*: the loaded model (descriptor, device image of the weights) and the work arrays of a sample call
+    struct Sgan {
+        bool loaded = false;
+        fot_sgan_desc desc{};
+        SgDev dev{};
+        DevBuf dImg, dOff, dScene, dObs, dNoise, dOut, dHenc, dPool, dCtx, dH, dC, dXY;
+        void release() { for (DevBuf *b : { &dImg, &dOff, &dScene, &dObs, &dNoise, &dOut, &dHenc, &dPool, &dCtx, &dH, &dC, &dXY }) b->release(); }
+    } sgan;
     bool last_valid = false;
     // profiling: event pairs around kernel launches
     bool prof_on = false;
@@ -746,6 +755,8 @@ int32_t fot_abi_info(int32_t cap, int32_t *out)
         (int32_t)sizeof(fot_loop_config), (int32_t)sizeof(fot_loop_step_out),
         (int32_t)sizeof(fot_loop_replay), (int32_t)sizeof(fot_loop_run_out), (int32_t)sizeof(fot_loop_summary),
         (int32_t)sizeof(fot_pred_origin), (int32_t)sizeof(fot_pred_score),
+        (int32_t)sizeof(fot_sgan_desc), FOT_SGAN_MAX_EMBEDDING, FOT_SGAN_MAX_HIDDEN, FOT_SGAN_MAX_MLP, FOT_SGAN_MAX_BOTTLENECK,
+        FOT_SGAN_MAX_OBS_LEN, FOT_SGAN_MAX_PEDS, FOT_SGAN_POOL_HIDDEN,
     };
     for (int i = 0; i < FOT_ABI_INFO_WORDS && i < cap && out; ++i) out[i] = v[i];
     return FOT_ABI_INFO_WORDS;
@@ -856,6 +867,7 @@ void destroy_handle(fot_handle *h)
     for (Workspace &w : h->ws) w.release();
     h->hSmallIn.release(); h->hSmallOut.release(); h->hRecOut.release(); h->hDone.release();
     h->hScoreIn.release(); h->hScoreOut.release(); h->dScoreT.release();
+    h->sgan.release();
     h->loop.release();
     for (hipEvent_t e : h->prof_pool) (void)hipEventDestroy(e);
     if (h->fork) (void)hipEventDestroy(h->fork);
@@ -2315,6 +2327,153 @@ int fot_loop_prediction_scores(fot_handle *h, int32_t n_episodes, int32_t stride
     // (a frame without pedestrians left no tensor: every P is 0 and none is read)
     return prediction_scores_impl(h, "fot_loop_prediction_scores", n_episodes, desc.data(), L.dDyn.p, 0, FOT_F64, stride, E,
                                   truth, out, h->stream);
+}
+
+// ---- Social-GAN sample generation (include/fot.h; kernels: fot_sgan.hip, arithmetic: fot_sgan.hpp) ------------------------
+int fot_sgan_weight_count(const fot_sgan_desc *desc, int64_t *n)
+{
+    if (!desc || !n) return fail(nullptr, FOT_ERR_INVALID, "fot_sgan_weight_count: desc / n is NULL");
+    std::string why;
+    const int rc = sg_check_desc(*desc, why);
+    if (rc != FOT_OK) return fail(nullptr, rc, why);
+    *n = sg_blob_layout(*desc).total;
+    return FOT_OK;
+}
+
+int fot_sgan_load(fot_handle *h, const fot_sgan_desc *desc, int64_t n, const float *weights)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (!desc || !weights) return fail(h, FOT_ERR_INVALID, "fot_sgan_load: desc / weights is NULL");
+    std::string why;
+    const int rc = sg_check_desc(*desc, why);
+    if (rc != FOT_OK) return fail(h, rc, why);
+    if (n != sg_blob_layout(*desc).total) return fail(h, FOT_ERR_INVALID, "fot_sgan_load: n is not fot_sgan_weight_count of the descriptor");
+    std::vector<float> img;
+    const SgDev dev = sg_dev_image(*desc, weights, img);
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                   // (a sample call of the model before this one is synchronous anyway)
+    fot_handle::Sgan &G = h->sgan;
+    G.loaded = false;
+    HIP_TRY(h, G.dImg.ensure(sizeof(float) * img.size()));
+    HIP_TRY(h, hipMemcpy(G.dImg.p, img.data(), sizeof(float) * img.size(), hipMemcpyHostToDevice));
+    G.desc = *desc;
+    G.dev = dev;
+    G.loaded = true;
+    return FOT_OK;
+}
+
+int fot_sgan_unload(fot_handle *h)
+{
+    if (!h) return FOT_ERR_INVALID;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->sgan.loaded = false;
+    h->sgan.release();
+    return FOT_OK;
+}
+
+int fot_sgan_sample(fot_handle *h, int32_t n_scenes, const int32_t *ped_off, const void *obs, int32_t S, const void *noise,
+                    int32_t flags, void *out, void *stream)
+{
+    if (!h) return FOT_ERR_INVALID;
+    fot_handle::Sgan &G = h->sgan;
+    if (!G.loaded) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: no model loaded (fot_sgan_load)");
+    if (n_scenes < 0 || !ped_off) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: n_scenes / ped_off (one offset even for no scene)");
+    if (S < 1) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: S < 1");
+    if (flags & ~(FOT_OUT_DEVICE | FOT_SGAN_OBS_DEVICE | FOT_SGAN_NOISE_DEVICE)) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: flags");
+    if (ped_off[0] != 0) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: ped_off must start at 0 and be non-decreasing");
+    int widest = 0;
+    for (int i = 0; i < n_scenes; ++i) {
+        if (ped_off[i + 1] < ped_off[i]) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: ped_off must start at 0 and be non-decreasing");
+        widest = std::max(widest, ped_off[i + 1] - ped_off[i]);
+    }
+    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, "fot_sgan_sample: S > FOT_MAX_SAMPLES");
+    if (widest > FOT_SGAN_MAX_PEDS) return fail(h, FOT_ERR_UNSUPPORTED, "fot_sgan_sample: a scene of more than FOT_SGAN_MAX_PEDS pedestrians");
+    const fot_sgan_desc &d = G.desc;
+    const int N = ped_off[n_scenes];
+    const bool global_noise = d.noise_mix_type == FOT_SGAN_NOISE_GLOBAL;
+    const int nd = d.noise_dim, noise_rows = global_noise ? n_scenes : N;
+    if (N == 0) return FOT_OK;
+    if (!obs || !out || (nd > 0 && !noise)) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: NULL tensor");
+    const int E = d.embedding_dim, He = d.encoder_h_dim, Hd = d.decoder_h_dim, T = d.obs_len, L = d.pred_len;
+    const bool pooled = sg_pooled(d), steps = sg_pool_steps(d), context = sg_has_context(d);
+    const int nc = context ? Hd - nd : He;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    { int r = order_begin(h, st); if (r != FOT_OK) return r; }
+    const size_t obs_bytes = sizeof(float) * 2 * (size_t)T * N, noise_bytes = sizeof(float) * (size_t)S * noise_rows * nd;
+    const size_t out_bytes = sizeof(float) * 2 * (size_t)S * L * N, rows = (size_t)S * N;
+    // the offsets and, for noise per scene, every pedestrian's scene
+    std::vector<int32_t> scene_of;
+    HIP_TRY(h, G.dOff.ensure(sizeof(int32_t) * ((size_t)n_scenes + 1)));
+    HIP_TRY(h, hipMemcpyAsync(G.dOff.p, ped_off, sizeof(int32_t) * ((size_t)n_scenes + 1), hipMemcpyHostToDevice, st));
+    if (global_noise && nd > 0) {
+        scene_of.resize((size_t)N);
+        for (int i = 0; i < n_scenes; ++i) std::fill(scene_of.begin() + ped_off[i], scene_of.begin() + ped_off[i + 1], i);
+        HIP_TRY(h, G.dScene.ensure(sizeof(int32_t) * (size_t)N));
+        HIP_TRY(h, hipMemcpyAsync(G.dScene.p, scene_of.data(), sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, st));
+    }
+    const float *d_obs = (const float *)obs, *d_noise = (const float *)noise;
+    if (!(flags & FOT_SGAN_OBS_DEVICE)) {
+        HIP_TRY(h, G.dObs.ensure(obs_bytes));
+        HIP_TRY(h, hipMemcpyAsync(G.dObs.p, obs, obs_bytes, hipMemcpyHostToDevice, st));
+        d_obs = G.dObs.as<float>();
+    }
+    if (nd > 0 && !(flags & FOT_SGAN_NOISE_DEVICE)) {
+        HIP_TRY(h, G.dNoise.ensure(noise_bytes));
+        HIP_TRY(h, hipMemcpyAsync(G.dNoise.p, noise, noise_bytes, hipMemcpyHostToDevice, st));
+        d_noise = G.dNoise.as<float>();
+    }
+    float *d_out = (float *)out;
+    if (!(flags & FOT_OUT_DEVICE)) { HIP_TRY(h, G.dOut.ensure(out_bytes)); d_out = G.dOut.as<float>(); }
+    const float *img = G.dImg.as<float>();
+    const int32_t *d_off = G.dOff.as<int32_t>();
+    // once per pedestrian / scene: encoder, first pooling, context MLP
+    HIP_TRY(h, G.dHenc.ensure(sizeof(float) * (size_t)N * He));
+    LAUNCH_TRY(h, launch_sgan_encode(img, G.dev.enc, E, He, T, N, d_obs, G.dHenc.as<float>(), st));
+    const int bp = pooled ? G.dev.pool.b_pad : 0;
+    if (pooled) {
+        HIP_TRY(h, G.dPool.ensure(sizeof(float) * (steps ? rows : (size_t)N) * bp));
+        HIP_TRY(h, hipMemsetAsync(G.dPool.p, 0, sizeof(float) * (size_t)N * bp, st));
+        LAUNCH_TRY(h, launch_sgan_pool(img, G.dev.pool, n_scenes, 1, N, d_off, G.dHenc.as<float>(),
+                                       d_obs + 2 * (size_t)(T - 1) * N, G.dPool.as<float>(), st));
+    }
+    const float *d_ctx = G.dHenc.as<float>();
+    if (context) {
+        HIP_TRY(h, G.dCtx.ensure(sizeof(float) * (size_t)N * nc));
+        LAUNCH_TRY(h, launch_sgan_mlp(img, G.dev.ctx, G.dHenc.as<float>(), He, G.dPool.as<float>(), pooled ? d.bottleneck_dim : 0, bp,
+                                      N, G.dCtx.as<float>(), nc, st));
+        d_ctx = G.dCtx.as<float>();
+    }
+    // once per sample: the decoder
+    SgDecode a{};
+    a.img = img; a.l = G.dev.dec; a.pos_w = G.dev.pos_w; a.pos_b = G.dev.pos_b;
+    a.E = E; a.H = Hd; a.N = N; a.S = S; a.obs_len = T; a.pred_len = L;
+    a.obs = d_obs; a.ctx = d_ctx; a.noise = d_noise; a.row_scene = global_noise && nd > 0 ? G.dScene.as<int32_t>() : nullptr;
+    a.nc = nc; a.nd = nd; a.noise_rows = noise_rows; a.out = d_out;
+    if (!steps) {
+        a.t0 = 0; a.n_steps = L; a.init = 1; a.save = 0;
+        LAUNCH_TRY(h, launch_sgan_decode(a, st));
+    } else {
+        HIP_TRY(h, G.dH.ensure(sizeof(float) * rows * Hd));
+        HIP_TRY(h, G.dC.ensure(sizeof(float) * rows * Hd));
+        HIP_TRY(h, G.dXY.ensure(sizeof(float) * rows * 6));
+        a.h = G.dH.as<float>(); a.c = G.dC.as<float>();
+        a.pos = G.dXY.as<float>(); a.rel = a.pos + rows * 2; a.cum = a.pos + rows * 4;
+        a.n_steps = 1; a.save = 1;
+        for (int t = 0; t < L; ++t) {
+            a.t0 = t; a.init = t == 0;
+            LAUNCH_TRY(h, launch_sgan_decode(a, st));
+            if (t == L - 1) break;                                   // (the last step's pooled state is never read)
+            HIP_TRY(h, hipMemsetAsync(G.dPool.p, 0, sizeof(float) * rows * bp, st));
+            LAUNCH_TRY(h, launch_sgan_pool(img, G.dev.dpool, n_scenes, S, N, d_off, a.h, a.pos, G.dPool.as<float>(), st));
+            LAUNCH_TRY(h, launch_sgan_mlp(img, G.dev.dmlp, a.h, Hd, G.dPool.as<float>(), d.bottleneck_dim, bp, (int64_t)rows, a.h, Hd, st));
+        }
+    }
+    if (!(flags & FOT_OUT_DEVICE)) HIP_TRY(h, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    { int r = order_end(h, st); if (r != FOT_OK) return r; }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return FOT_OK;
 }
 
 int fot_loop_run(fot_handle *h, int32_t max_steps, fot_loop_run_out *out)

@@ -2,9 +2,12 @@
 
 Mirrors ``TrajectoryPredictor.process_prediction`` / ``predict_cv`` / the closest-to-mean pick of
 ``predict_single_best`` (reference src/prediction/trajectory_predictor.py:188-353) and the current-position
-prepend of ``IntegratedSimulator._update_prediction`` (integrated_simulator.py:503-525).  The Social-GAN
-forward passes themselves stay in PyTorch-ROCm; this turns their raw output into the planner's
-``[S, P, T, 2]`` tensor without leaving the GPU.
+prepend of ``IntegratedSimulator._update_prediction`` (integrated_simulator.py:503-525): the samples' raw output is
+turned into the planner's ``[S, P, T, 2]`` tensor without leaving the GPU.
+
+The Social-GAN forward passes themselves run in the library as well (``SganWeights`` / ``SganSampler`` over
+``fot_sgan_sample``): all samples of all scenes in one call, in float32, from weights under the reference's state-dict
+names; PyTorch-ROCm only draws the noise.
 """
 from __future__ import annotations
 
@@ -146,3 +149,184 @@ def prediction_scores(engine: BatchPlanner, samples, truth, stride: int, t_major
     tensor = np.concatenate(flat) if flat else np.zeros((0, 2), dt)
     tr = np.concatenate([t.reshape(-1, E, 2) for t in truths]) if truths else np.zeros((0, E, 2))
     return engine.prediction_scores(tensor, origins, tr, stride, E, stream)
+
+
+# ---- Social-GAN sample generation (fot_sgan_*) ---------------------------------------------------------------------------
+_POOLING = {None: _abi.SGAN_POOL_NONE, "none": _abi.SGAN_POOL_NONE, "pool_net": _abi.SGAN_POOL_NET, "spool": _abi.SGAN_SPOOL}
+_NOISE_MIX = {"ped": _abi.SGAN_NOISE_PED, "global": _abi.SGAN_NOISE_GLOBAL}
+_BN_EPS = 1e-5                                                      # nn.BatchNorm1d's default; make_mlp passes no other
+
+
+def _np64(v):
+    return np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float64)
+
+
+def fold_batch_norm(weight, bias, bn_weight, bn_bias, running_mean, running_var, eps: float = _BN_EPS):
+    """Linear followed by an eval-mode BatchNorm1d as ONE Linear: y = g (W x + b - mean) / sqrt(var + eps) + beta, in
+    float64.  Returns (W', b')."""
+    scale = _np64(bn_weight) / np.sqrt(_np64(running_var) + eps)
+    return _np64(weight) * scale[:, None], (_np64(bias) - _np64(running_mean)) * scale + _np64(bn_bias)
+
+
+class SganWeights:
+    """A Social-GAN generator as ``fot_sgan_load`` takes it: the descriptor and ONE packed float32 blob in the order
+    include/fot.h documents, BatchNorm folded into the Linear in front of it."""
+
+    def __init__(self, desc: _abi.SganDesc, blob: np.ndarray, noise_type: str = "gaussian"):
+        self.desc, self.blob, self.noise_type = desc, np.ascontiguousarray(blob, dtype=np.float32), noise_type
+        n = C.c_int64(0)
+        rc = _abi.lib().fot_sgan_weight_count(C.byref(desc), C.byref(n))
+        if rc != _abi.OK:
+            raise _abi.FotError(rc, (_abi.lib().fot_last_error(None) or b"").decode())
+        if n.value != self.blob.size:
+            raise ValueError(f"SganWeights: the blob holds {self.blob.size} floats, the descriptor needs {n.value}")
+
+    @staticmethod
+    def descriptor(args) -> _abi.SganDesc:
+        """The generator's constructor arguments (a checkpoint's ``args``; the reference's names and defaults,
+        trajectory_predictor.py:87-104) as a ``fot_sgan_desc``."""
+        get = lambda k, default: args[k] if k in args else args.get(k + "_g", default) if hasattr(args, "get") else default
+        noise_dim = get("noise_dim", (8,))
+        noise_dim = tuple(noise_dim) if hasattr(noise_dim, "__len__") else (int(noise_dim),)
+        if len(noise_dim) != 1:
+            raise ValueError(f"SganWeights: a noise_dim of one entry, got {noise_dim}")
+        pooling = get("pooling_type", "pool_net")
+        pooling = pooling.lower() if isinstance(pooling, str) else pooling
+        if pooling not in _POOLING:
+            raise ValueError(f"SganWeights: unknown pooling_type {pooling!r}")
+        mix = get("noise_mix_type", "ped")
+        if mix not in _NOISE_MIX:
+            raise ValueError(f"SganWeights: unknown noise_mix_type {mix!r}")
+        return _abi.SganDesc(int(get("obs_len", 8)), int(get("pred_len", 12)), int(get("embedding_dim", 64)),
+                             int(get("encoder_h_dim", 64)), int(get("decoder_h_dim", 128)), int(get("mlp_dim", 1024)),
+                             int(get("bottleneck_dim", 1024)), int(noise_dim[0]), int(get("num_layers", 1)), _POOLING[pooling],
+                             int(bool(get("pool_every_timestep", True))), _NOISE_MIX[mix], float(get("dropout", 0.0)), 0)
+
+    @classmethod
+    def from_state_dict(cls, args, state) -> "SganWeights":
+        """args: the generator's constructor arguments (mapping); state: arrays (NumPy or torch) under the reference's
+        state-dict names (``encoder.encoder.weight_ih_l0`` ...).  An MLP layer followed by BatchNorm (``<seq>.<i + 1>.
+        running_mean`` present) is folded; everything is packed in float64 and rounded to float32 once."""
+        d = cls.descriptor(args)
+        pooled = d.pooling_type == _abi.SGAN_POOL_NET
+        parts = []
+
+        def linear(prefix):
+            parts.extend([_np64(state[prefix + ".weight"]), _np64(state[prefix + ".bias"])])
+
+        def lstm(prefix):
+            for k in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
+                parts.append(_np64(state[f"{prefix}.{k}"]))
+
+        def mlp(prefix):                                            # make_mlp: Linear [, BatchNorm1d], ReLU, twice
+            idx = sorted(int(k[len(prefix) + 1:].split(".")[0]) for k in state
+                         if k.startswith(prefix + ".") and k.endswith(".weight") and np.ndim(state[k]) == 2)
+            if len(idx) != 2:
+                raise KeyError(f"SganWeights: {prefix} is not a two-layer MLP")
+            for i in idx:
+                w, b = _np64(state[f"{prefix}.{i}.weight"]), _np64(state[f"{prefix}.{i}.bias"])
+                bn = f"{prefix}.{i + 1}"
+                if bn + ".running_mean" in state:
+                    w, b = fold_batch_norm(w, b, state[bn + ".weight"], state[bn + ".bias"], state[bn + ".running_mean"],
+                                           state[bn + ".running_var"])
+                parts.extend([w, b])
+
+        def pool(prefix):
+            linear(prefix + ".spatial_embedding")
+            mlp(prefix + ".mlp_pre_pool")
+
+        linear("encoder.spatial_embedding"); lstm("encoder.encoder")
+        if pooled:
+            pool("pool_net")
+        if d.noise_dim > 0 or pooled or d.encoder_h_dim != d.decoder_h_dim:
+            mlp("mlp_decoder_context")
+        linear("decoder.spatial_embedding"); lstm("decoder.decoder"); linear("decoder.hidden2pos")
+        if pooled and d.pool_every_timestep:
+            pool("decoder.pool_net"); mlp("decoder.mlp")
+        blob = np.concatenate([p.reshape(-1) for p in parts]).astype(np.float32)
+        return cls(d, blob, noise_type=args.get("noise_type", "gaussian") if hasattr(args, "get") else "gaussian")
+
+    @classmethod
+    def from_checkpoint(cls, path) -> "SganWeights":
+        """A released checkpoint file: ``torch.load`` and ``from_state_dict(ckpt['args'], ckpt['g_state'])`` (``g_best_state``
+        when there is no ``g_state``), as the reference's loader reads it (trajectory_predictor.py:74, 124-128).
+
+        NEVER EXERCISED: no checkpoint file was available where this was written and tested; only ``from_state_dict`` on
+        seeded weights is."""
+        import torch
+        ckpt = torch.load(path, map_location="cpu", weights_only=False)
+        args = ckpt["args"]
+        args = args if hasattr(args, "get") else vars(args)
+        return cls.from_state_dict(args, ckpt["g_state"] if "g_state" in ckpt else ckpt["g_best_state"])
+
+
+class SganSampler:
+    """The multi-sample predictor in front of the planner, in the library: ``sample(obs, ped_off)`` gives the raw samples
+    [S, pred_len, sum P, 2] of every scene as a float32 ``torch`` device tensor -- what ``fot_loop_frame.dist_raw`` and
+    ``resample_device`` read.  A ``sample_source`` of ``BatchedClosedLoop`` (``needs_history``: it is handed the observer's
+    whole window).  The noise is drawn on the device from the sampler's own ``torch.Generator`` (``noise_type`` 'gaussian':
+    ``randn``; 'uniform': ``rand`` mapped to [-1, 1), models.py:27-32) or supplied; ``last_noise`` / ``last_obs`` /
+    ``last_ped_off`` keep what the most recent call used."""
+    needs_history = True
+
+    def __init__(self, engine: BatchPlanner, weights: SganWeights, num_samples: int, seed: Optional[int] = None,
+                 noise_type: str = "gaussian"):
+        import torch
+        if noise_type not in ("gaussian", "uniform"):
+            raise ValueError(f'Unrecognized noise type "{noise_type}"')
+        if not 1 <= int(num_samples) <= _abi.MAX_SAMPLES:
+            raise ValueError(f"SganSampler: 1 <= num_samples <= {_abi.MAX_SAMPLES}")
+        self.engine, self.weights, self.num_samples, self.noise_type = engine, weights, int(num_samples), noise_type
+        self._lib = _abi.lib()
+        self.load(weights)
+        dev = int(getattr(engine, "device", -1))                    # (fot_create's device < 0: the current one)
+        self.device = torch.device("cuda", torch.cuda.current_device() if dev < 0 else dev)
+        self.generator = torch.Generator(device=self.device)
+        if seed is not None:
+            self.generator.manual_seed(int(seed))
+        self.last_noise = self.last_obs = self.last_ped_off = None
+
+    def load(self, weights: SganWeights) -> None:
+        """Replace the handle's model."""
+        _abi.check(self.engine._h, self._lib.fot_sgan_load(self.engine._h, C.byref(weights.desc), weights.blob.size,
+                                                           weights.blob.ctypes.data))
+        self.weights = weights
+
+    def draw_noise(self, n_rows: int, n_scenes: int):
+        import torch
+        d = self.weights.desc
+        rows = n_scenes if d.noise_mix_type == _abi.SGAN_NOISE_GLOBAL else n_rows
+        shape = (self.num_samples, rows, d.noise_dim)
+        if self.noise_type == "gaussian":
+            return torch.randn(shape, device=self.device, dtype=torch.float32, generator=self.generator)
+        return torch.rand(shape, device=self.device, dtype=torch.float32, generator=self.generator).sub_(0.5).mul_(2.0)
+
+    def sample(self, obs, ped_off, noise=None):
+        """obs [obs_len, sum P, 2] absolute positions (NumPy, or a float32 torch device tensor); ped_off [n_scenes + 1]."""
+        import torch
+        d = self.weights.desc
+        off = np.ascontiguousarray(ped_off, dtype=np.int32)
+        n_scenes, n = len(off) - 1, int(off[-1])
+        if hasattr(obs, "data_ptr"):
+            obs_t = obs.to(device=self.device, dtype=torch.float32).contiguous()
+        else:
+            obs_t = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32)).to(self.device)
+        if tuple(obs_t.shape) != (d.obs_len, n, 2):
+            raise ValueError(f"SganSampler: obs is [obs_len = {d.obs_len}, sum P = {n}, 2], got {tuple(obs_t.shape)}")
+        if noise is None:
+            noise_t = self.draw_noise(n, n_scenes)
+        else:
+            noise_t = torch.as_tensor(noise, dtype=torch.float32).to(self.device).contiguous()
+            rows = n_scenes if d.noise_mix_type == _abi.SGAN_NOISE_GLOBAL else n
+            if tuple(noise_t.shape) != (self.num_samples, rows, d.noise_dim):
+                raise ValueError(f"SganSampler: noise is [S, rows, noise_dim] = {(self.num_samples, rows, d.noise_dim)}")
+        out = torch.empty((self.num_samples, d.pred_len, n, 2), device=self.device, dtype=torch.float32)
+        torch.cuda.current_stream(self.device).synchronize()        # (the library reads the tensors on its own stream)
+        _abi.check(self.engine._h, self._lib.fot_sgan_sample(
+            self.engine._h, n_scenes, off.ctypes.data, C.c_void_p(obs_t.data_ptr()), self.num_samples,
+            C.c_void_p(noise_t.data_ptr()) if noise_t.numel() else None,
+            _abi.OUT_DEVICE | _abi.SGAN_OBS_DEVICE | _abi.SGAN_NOISE_DEVICE, C.c_void_p(out.data_ptr()), None))
+        self.last_noise, self.last_obs, self.last_ped_off = noise_t, obs_t, off
+        return out
+
+    __call__ = sample
