@@ -168,6 +168,9 @@ def fold_batch_norm(weight, bias, bn_weight, bn_bias, running_mean, running_var,
     return _np64(weight) * scale[:, None], (_np64(bias) - _np64(running_mean)) * scale + _np64(bn_bias)
 
 
+_NOISE_TYPES = ("gaussian", "uniform")
+
+
 class SganWeights:
     """A Social-GAN generator as ``fot_sgan_load`` takes it: the descriptor and ONE packed float32 blob in the order
     include/fot.h documents, BatchNorm folded into the Linear in front of it."""
@@ -251,8 +254,9 @@ class SganWeights:
         """A released checkpoint file: ``torch.load`` and ``from_state_dict(ckpt['args'], ckpt['g_state'])`` (``g_best_state``
         when there is no ``g_state``), as the reference's loader reads it (trajectory_predictor.py:74, 124-128).
 
-        NEVER EXERCISED: no checkpoint file was available where this was written and tested; only ``from_state_dict`` on
-        seeded weights is."""
+        Tested on files the suite writes itself (``args`` as a mapping and as an object, ``g_state`` and ``g_best_state``,
+        the ``_g``-suffixed dimension names); NEVER run on a released checkpoint file: none was available where this was
+        written and tested."""
         import torch
         ckpt = torch.load(path, map_location="cpu", weights_only=False)
         args = ckpt["args"]
@@ -265,18 +269,19 @@ class SganSampler:
     [S, pred_len, sum P, 2] of every scene as a float32 ``torch`` device tensor -- what ``fot_loop_frame.dist_raw`` and
     ``resample_device`` read.  A ``sample_source`` of ``BatchedClosedLoop`` (``needs_history``: it is handed the observer's
     whole window).  The noise is drawn on the device from the sampler's own ``torch.Generator`` (``noise_type`` 'gaussian':
-    ``randn``; 'uniform': ``rand`` mapped to [-1, 1), models.py:27-32) or supplied; ``last_noise`` / ``last_obs`` /
-    ``last_ped_off`` keep what the most recent call used."""
+    ``randn``; 'uniform': ``rand`` mapped to [-1, 1), models.py:27-32) or supplied.  ``noise_type`` is the loaded weights' own
+    (the checkpoint's, as the reference draws: models.py:393) unless the constructor is given one; ``last_noise`` /
+    ``last_obs`` / ``last_ped_off`` keep what the most recent call used."""
     needs_history = True
 
     def __init__(self, engine: BatchPlanner, weights: SganWeights, num_samples: int, seed: Optional[int] = None,
-                 noise_type: str = "gaussian"):
+                 noise_type: Optional[str] = None):
         import torch
-        if noise_type not in ("gaussian", "uniform"):
+        if noise_type is not None and noise_type not in _NOISE_TYPES:
             raise ValueError(f'Unrecognized noise type "{noise_type}"')
         if not 1 <= int(num_samples) <= _abi.MAX_SAMPLES:
             raise ValueError(f"SganSampler: 1 <= num_samples <= {_abi.MAX_SAMPLES}")
-        self.engine, self.weights, self.num_samples, self.noise_type = engine, weights, int(num_samples), noise_type
+        self.engine, self.weights, self.num_samples, self._noise_type = engine, weights, int(num_samples), noise_type
         self._lib = _abi.lib()
         self.load(weights)
         dev = int(getattr(engine, "device", -1))                    # (fot_create's device < 0: the current one)
@@ -286,8 +291,14 @@ class SganSampler:
             self.generator.manual_seed(int(seed))
         self.last_noise = self.last_obs = self.last_ped_off = None
 
+    @property
+    def noise_type(self) -> str:
+        return self._noise_type if self._noise_type is not None else self.weights.noise_type
+
     def load(self, weights: SganWeights) -> None:
         """Replace the handle's model."""
+        if self._noise_type is None and weights.noise_type not in _NOISE_TYPES:
+            raise ValueError(f'Unrecognized noise type "{weights.noise_type}"')
         _abi.check(self.engine._h, self._lib.fot_sgan_load(self.engine._h, C.byref(weights.desc), weights.blob.size,
                                                            weights.blob.ctypes.data))
         self.weights = weights

@@ -6,6 +6,10 @@ tests rebuild the weights from the seed, the fixture carries none), and runs for
 per sample in float32 and again in float64 (torch.set_default_dtype: the model creates its zero states with the default
 dtype).  Writes tests/golden/sgan/cases.npz -- per case the descriptor and seed (meta), obs, ped_off, the noise and the
 absolute outputs of both runs; no reference code.
+
+    make_golden_sgan.py [--only cases]   sgan_common.CASES      -> tests/golden/sgan/cases.npz (the default)
+    make_golden_sgan.py --only edges     sgan_common.EDGE_CASES -> tests/golden/sgan/edges.npz
+    make_golden_sgan.py --only edges --probe    nothing is written: per edge case, the largest step at each weight scale
 """
 import argparse
 import json
@@ -48,9 +52,43 @@ def run_reference(TrajectoryGenerator, relative_to_abs, torch, a, state, obs, of
         torch.set_default_dtype(torch.float32)
 
 
+SCALES = (1.5, 2.0, 2.5, 3.0)
+
+
+def run_case(ref, name, scale):
+    """(arrays of the case, its meta entry) at a weight scale; the reference alone is held to the conditions."""
+    TrajectoryGenerator, relative_to_abs, torch = ref
+    c = sc.case(name)
+    a = sc.case_args(name)
+    seed = sc.case_seed(name)
+    state = sc.seeded_state(a, seed, scale)
+    obs, off, noise = sc.case_inputs(name)
+    r32 = run_reference(TrajectoryGenerator, relative_to_abs, torch, a, state, obs, off, noise, torch.float32)
+    r64 = run_reference(TrajectoryGenerator, relative_to_abs, torch, a, state, obs, off, noise, torch.float64)
+    assert r32.dtype == np.float32 and r64.dtype == np.float64 and r32.shape == (c["S"], a["pred_len"], int(off[-1]), 2)
+    steps = np.diff(np.concatenate([np.broadcast_to(obs[-1].astype(np.float64), (c["S"], 1) + obs[-1].shape), r64], axis=1), axis=1)
+    move = float(np.max(np.linalg.norm(steps, axis=-1)))
+    e_ref = float(np.max(np.abs(r32 - r64)))
+    print(f"{name:26s} scale {scale:3.1f} largest step {move:6.3f} m   e_ref {e_ref:.3e}   bound {sc.accuracy_bound(r32, r64):.3e}",
+          flush=True)
+    meta = dict(args={**a, "noise_dim": list(a["noise_dim"])}, seed=seed, scale=scale, scenes=c["scenes"], S=c["S"],
+                largest_step=move, e_ref=e_ref)
+    arrays = {f"{name}/{k}": v for k, v in (("obs", obs), ("ped_off", off), ("noise", noise), ("out32", r32), ("out64", r64))}
+    why = []
+    if not np.isfinite(r64).all():
+        why.append("the float64 output is not finite")
+    if not e_ref > 0.0:
+        why.append(f"e_ref must be positive, got {e_ref}")
+    if not 0.3 <= move <= 2.0:
+        why.append(f"the trajectories must move 0.3 .. 2 m per step, got {move}")
+    return arrays, meta, why
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
+    ap.add_argument("--only", choices=("cases", "edges"), default="cases")
+    ap.add_argument("--probe", action="store_true")
     args = ap.parse_args()
     sys.path.insert(0, args.ref)
     import torch
@@ -58,30 +96,22 @@ def main():
     from src.prediction.sgan_vendor.utils import relative_to_abs
 
     torch.set_num_threads(1)
+    ref = (TrajectoryGenerator, relative_to_abs, torch)
+    table, path = (sc.CASES, sc.FIXTURE) if args.only == "cases" else (sc.EDGE_CASES, sc.EDGE_FIXTURE)
+    if args.probe:
+        for name in table:
+            print(name, "->", [s for s in SCALES if not run_case(ref, name, s)[2]], flush=True)
+        return
     out, meta = {}, {}
-    for name, (dims, pooling, every, mix, bn, scenes, S, scale) in sc.CASES.items():
-        a = sc.case_args(name)
-        seed = sc.case_seed(name)
-        state = sc.seeded_state(a, seed, scale)
-        obs, off, noise = sc.case_inputs(name)
-        r32 = run_reference(TrajectoryGenerator, relative_to_abs, torch, a, state, obs, off, noise, torch.float32)
-        r64 = run_reference(TrajectoryGenerator, relative_to_abs, torch, a, state, obs, off, noise, torch.float64)
-        assert r32.dtype == np.float32 and r64.dtype == np.float64 and r32.shape == (S, sc.PRED_LEN, int(off[-1]), 2)
-        steps = np.diff(np.concatenate([np.broadcast_to(obs[-1].astype(np.float64), (S, 1) + obs[-1].shape), r64], axis=1), axis=1)
-        move = float(np.max(np.linalg.norm(steps, axis=-1)))
-        e_ref = float(np.max(np.abs(r32 - r64)))
-        print(f"{name:26s} largest step {move:6.3f} m   e_ref {e_ref:.3e}   bound {sc.accuracy_bound(r32, r64):.3e}")
-        assert 0.3 <= move <= 2.0, f"{name}: the trajectories must move 0.3 .. 2 m per step, got {move}"
-        assert np.isfinite(r64).all() and e_ref > 0.0
-        meta[name] = dict(args={**a, "noise_dim": list(a["noise_dim"])}, seed=seed, scale=scale, scenes=scenes, S=S,
-                          largest_step=move, e_ref=e_ref)
-        for k, v in (("obs", obs), ("ped_off", off), ("noise", noise), ("out32", r32), ("out64", r64)):
-            out[f"{name}/{k}"] = v
+    for name in table:
+        arrays, meta[name], why = run_case(ref, name, sc.case_scale(name))
+        assert not why, f"{name}: " + "; ".join(why)
+        out.update(arrays)
     out["meta"] = np.asarray(json.dumps(meta))
-    os.makedirs(os.path.dirname(sc.FIXTURE), exist_ok=True)
-    np.savez_compressed(sc.FIXTURE, **out)
-    print("wrote", sc.FIXTURE, os.path.getsize(sc.FIXTURE), "bytes")
-    assert os.path.getsize(sc.FIXTURE) < 1_000_000
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes")
+    assert os.path.getsize(path) < 1_000_000
 
 
 if __name__ == "__main__":

@@ -9,6 +9,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FIXTURE = os.path.join(HERE, "golden", "sgan", "cases.npz")
+EDGE_FIXTURE = os.path.join(HERE, "golden", "sgan", "edges.npz")
 OBS_LEN, PRED_LEN = 8, 12
 POOL_HIDDEN = 512                                  # PoolHiddenNet's first layer (models.py:159)
 BN_EPS = 1e-5
@@ -43,12 +44,75 @@ CASES = {
 }
 
 
+def _edge(dims, scenes, S=1, pooling="pool_net", every=True, mix="ped", bn=False, obs_len=OBS_LEN, pred_len=PRED_LEN, scale=2.0,
+          inputs=None):
+    """dims: a key of DIMS or the six numbers; inputs: None, 'stationary', 'coincident' or 'far' (case_inputs)."""
+    return dict(dims=DIMS[dims] if isinstance(dims, str) else tuple(dims), dims_name=dims if isinstance(dims, str) else None,
+                pooling=pooling, every=every, mix=mix, bn=bn, scenes=list(scenes), S=S, scale=scale, obs_len=obs_len,
+                pred_len=pred_len, inputs=inputs)
+
+
+B_DIMS = DIMS["b"]
+# The edges of fot_sgan_sample: the lengths, the dimensions and the scene sizes at which a tile loop of csrc/fot_sgan.hip ends,
+# one short of it and one over it (LSTM tile: 16 rows, 4 per thread; pool: 16 neighbours, blocks of 8 outputs; MLP: 4 rows;
+# loops strided by 256 threads over 4 H, M and O), and inputs with exact zeros.  Shapes as small as the loop in question allows.
+# Weight scale 2: of 1.5 / 2 / 2.5 / 3 the one at which the reference moves 0.3 .. 2 m per step in every case (make_golden_sgan.py --probe).
+EDGE_CASES = {
+    # lengths (the library accepts 1 .. 32 of both)
+    "len_obs1":          _edge("a", [3, 2], S=2, obs_len=1),                    # k_sgan_decode: rel = 0 without a step before
+    "len_obs2":          _edge("b", [4], S=2, every=False, mix="global", obs_len=2),
+    "len_obs32":         _edge("a", [5], pooling=None, every=False, bn=True, obs_len=32),
+    "len_pred1":         _edge("a", [3], S=2, pred_len=1),                      # pooling at every step, never pooled
+    "len_pred32_step":   _edge("a", [4, 1], S=2, pred_len=32),                  # 32 launches, the state in HBM
+    "len_pred32_once":   _edge("a", [5], S=2, every=False, pred_len=32),        # one launch
+    # dimensions
+    "dim_all_min":       _edge((1, 1, 2, 1, 1, 1), [3, 1], S=2),
+    "dim_b8_scene16":    _edge(B_DIMS[:4] + (8, 4), [16]),
+    "dim_b9_scene16":    _edge(B_DIMS[:4] + (9, 4), [16], bn=True),             # padded to 16: seven phantom outputs
+    "dim_b1":            _edge(B_DIMS[:4] + (1, 4), [5], S=2, every=False),
+    "dim_hd64":          _edge((16, 32, 64, 64, 8, 8), [17]),                   # 4 H = the 256 threads
+    "dim_hd65_scene17":  _edge((16, 32, 65, 64, 8, 8), [17]),
+    "dim_hd128_he1":     _edge((16, 1, 128, 64, 8, 8), [17], every=False, mix="global"),
+    "dim_m256":          _edge((16, 32, 32, 256, 8, 8), [5], pooling=None, every=False),
+    "dim_m257_scene15":  _edge((16, 32, 32, 257, 8, 8), [15], S=2),
+    "dim_ctx_of_one":    _edge((16, 32, 32, 64, 8, 31), [5], S=2, every=False),  # nd = Hd - 1
+    "dim_nd0_he_ne_hd":  _edge((16, 24, 32, 64, 8, 0), [5], S=2, pooling=None, every=False),
+    "cap_c_scene17":     _edge("c", [17], bn=True, pred_len=3),
+    # scene sizes and rows
+    "scn_tiles_step":    _edge("b", [15, 16, 17, 31, 32, 33], pred_len=4),
+    "scn_tiles_once":    _edge("b", [15, 16, 17, 31, 32, 33], every=False, mix="global", pred_len=4),
+    "scn_256_and_1":     _edge("a", [256, 1], obs_len=2, pred_len=3),           # FOT_SGAN_MAX_PEDS
+    "rows_16":           _edge("b", [8], S=2, pred_len=4),                      # S N = one LSTM tile, four MLP tiles
+    "rows_17":           _edge("b", [8, 9], pred_len=4),
+    "rows_4":            _edge("b", [2], S=2, pred_len=4),
+    "rows_5":            _edge("b", [1], S=5, pred_len=4),
+    "scn_40_small":      _edge("b", [i * 7 % 3 for i in range(40)], S=3, mix="global", pred_len=4),
+    "s64_step_scene17":  _edge("a", [17], S=64, pred_len=3),
+    # inputs
+    "in_stationary":     _edge("a", [3], S=2, inputs="stationary"),             # every displacement exactly 0
+    "in_coincident":     _edge("a", [3], S=2, inputs="coincident"),             # dx = dy = 0 in the pool
+    "in_far":            _edge("a", [3, 2], S=2, inputs="far"),                 # 2e4 m from the origin
+}
+
+
+def case(name):
+    """A case of either table in the form of _edge()."""
+    if name in EDGE_CASES:
+        return EDGE_CASES[name]
+    dims, pooling, every, mix, bn, scenes, S, scale = CASES[name]
+    return _edge(dims, scenes, S=S, pooling=pooling, every=every, mix=mix, bn=bn, scale=scale)
+
+
+def case_scale(name):
+    return case(name)["scale"]
+
+
 def case_args(name):
-    dims, pooling, every, mix, bn, _, _, _ = CASES[name]
-    e, he, hd, m, b, nd = DIMS[dims]
-    return dict(obs_len=OBS_LEN, pred_len=PRED_LEN, embedding_dim=e, encoder_h_dim=he, decoder_h_dim=hd, mlp_dim=m,
-                bottleneck_dim=b, noise_dim=(nd,), num_layers=1, pooling_type=pooling, pool_every_timestep=every,
-                noise_mix_type=mix, batch_norm=bn, dropout=0.0, noise_type="gaussian")
+    c = case(name)
+    e, he, hd, m, b, nd = c["dims"]
+    return dict(obs_len=c["obs_len"], pred_len=c["pred_len"], embedding_dim=e, encoder_h_dim=he, decoder_h_dim=hd, mlp_dim=m,
+                bottleneck_dim=b, noise_dim=(nd,), num_layers=1, pooling_type=c["pooling"], pool_every_timestep=c["every"],
+                noise_mix_type=c["mix"], batch_norm=c["bn"], dropout=0.0, noise_type="gaussian")
 
 
 def case_seed(name):
@@ -114,16 +178,26 @@ def seeded_state(a, seed, scale=3.0):
 
 
 def case_inputs(name):
-    """obs [obs_len, N, 2] float32 (walking pedestrians), ped_off, noise [S, rows, nd] float32 -- from the case's seed."""
-    _, _, _, mix, _, scenes, S, _ = CASES[name]
+    """obs [obs_len, N, 2] float32 (walking pedestrians), ped_off, noise [S, rows, nd] float32 -- from the case's seed.  An edge
+    case's ``inputs``: 'stationary' -- the first pedestrian stands still; 'coincident' -- the second walks in the first one's
+    steps; 'far' -- everything 2e4 m from the origin."""
+    c = case(name)
+    mix, scenes, S = c["mix"], c["scenes"], c["S"]
     a = case_args(name)
     rng = np.random.default_rng(case_seed(name) + 50_000)
     off = np.concatenate([[0], np.cumsum(scenes)]).astype(np.int32)
     n = int(off[-1])
     start = rng.uniform(-6.0, 6.0, size=(n, 2))
     vel = rng.uniform(-0.6, 0.6, size=(n, 2))
-    steps = vel[None] + rng.normal(0.0, 0.05, size=(OBS_LEN, n, 2))
-    obs = (start[None] + np.cumsum(steps, axis=0)).astype(np.float32)
+    steps = vel[None] + rng.normal(0.0, 0.05, size=(a["obs_len"], n, 2))
+    track = start[None] + np.cumsum(steps, axis=0)
+    if c["inputs"] == "stationary":
+        track[:, 0] = track[0, 0]
+    elif c["inputs"] == "coincident":
+        track[:, 1] = track[:, 0]
+    elif c["inputs"] == "far":
+        track = track + np.array([2.0e4, -2.0e4])
+    obs = track.astype(np.float32)
     rows = len(scenes) if mix == "global" else n
     noise = rng.standard_normal(size=(S, rows, a["noise_dim"][0])).astype(np.float32)
     return obs, off, noise
@@ -223,8 +297,8 @@ def accuracy_bound(ref32, ref64):
     return max(8.0 * e_ref, 16.0 * float(np.spacing(np.float32(top))))
 
 
-def load_fixture():
-    z = np.load(FIXTURE, allow_pickle=False)
+def load_fixture(path=FIXTURE):
+    z = np.load(path, allow_pickle=False)
     return {k: z[k] for k in z.files}
 
 

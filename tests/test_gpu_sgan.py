@@ -33,7 +33,7 @@ _weights = {}
 def case_weights(name):
     if name not in _weights:
         a = sc.case_args(name)
-        _weights[name] = SganWeights.from_state_dict(a, sc.seeded_state(a, sc.case_seed(name), sc.CASES[name][7]))
+        _weights[name] = SganWeights.from_state_dict(a, sc.seeded_state(a, sc.case_seed(name), sc.case_scale(name)))
     return _weights[name]
 
 
@@ -209,7 +209,7 @@ def test_distribution_aware_closed_loop_with_the_sampler(engine):
     tracks = [sc.charging_wall_tracks(), fx["weave_s4_ped_traj"][:, :0], fx["weave_s4_ped_traj"]]
     name = "a_pool_step_ped_bn"
     a = sc.case_args(name)
-    state = sc.seeded_state(a, sc.case_seed(name), sc.CASES[name][7])
+    state = sc.seeded_state(a, sc.case_seed(name), sc.case_scale(name))
     S = 4
     src = _RecordingSampler(engine, case_weights(name), S, seed=5)
     with BatchedClosedLoop(cfg, tracks, sample_source=src, device_samples=True, prediction_scores=True) as sim:
