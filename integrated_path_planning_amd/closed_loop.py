@@ -749,8 +749,14 @@ class BatchedClosedLoop:
             return None, np.zeros(len(sel), bool), t_pred, None
         # np.allclose(pred[:, 0], current) of the reference (rtol 1e-5, atol 1e-8; finite inputs), per episode
         close = np.all(np.abs(pred[:, 0, :] - pos) <= 1e-8 + 1e-5 * np.abs(pos), axis=1)
-        same = np.logical_and.reduceat(close, off[:-1]) if len(close) else np.zeros(len(sel), bool)
-        return pred, ~same, t_pred, dist if self.distribution_aware else None
+        # (counted through a running sum: np.logical_and.reduceat has no empty segment, and an episode without pedestrians
+        #  at the END of the frame is an index past the array)
+        n_far = np.concatenate([[0], np.cumsum(~close)])
+        prepend = n_far[off[1:]] != n_far[off[:-1]]
+        empty = off[1:] == off[:-1]
+        if empty.any() and not empty.all():                          # no pedestrians: no block either way; agree with the rest
+            prepend[empty] = prepend[~empty].all()
+        return pred, prepend, t_pred, dist if self.distribution_aware else None
 
     # ------------------------------------------------------------------------------------------------------
     def step(self) -> int:

@@ -386,7 +386,8 @@ class BatchPlanner:
         synchronisation.  ``requests``: structured [r] of ``LOOP_REQUEST_DT``.  ``frame`` (None = the tensor of the
         previous call): ped_off [n+1], ped_pos / ped_vel [sum P, 2], obs_last / obs_prev [sum P, 2] float32 or None
         (predictor not ready), prepend [n] bool, ego [n, 4] (x, y, yaw, v) or None, staleness, pred_len, rp
-        (``_abi.ResampleParams``), ego_radius, ped_radius, use_footprint.
+        (``_abi.ResampleParams``), ego_radius, ped_radius, use_footprint; optionally dist_raw (device pointer to raw
+        samples [dist_S][pred_len][sum P][2]), dist_S, dist_dtype: the requests then plan against the distribution.
         Returns (records, metrics): the records as a structured array of ``RESULT_DT`` -- a COPY by default; with
         ``view=True`` a view of the handle's pinned block, valid only until the next ``loop_plan`` or ``close()`` on this
         planner (the lock-step driver reads it at once and keeps nothing) -- and the metrics [n] of ``SAFETY_DT`` (None
@@ -414,6 +415,8 @@ class BatchPlanner:
                     f.obs_prev = _addr(prev)
                     keep.append(prev)
                 f.rp = frame["rp"]
+            if frame.get("dist_raw") is not None:                      # raw samples of a multi-sample predictor, in HBM
+                f.dist_raw, f.dist_S, f.dist_dtype = int(frame["dist_raw"]), int(frame["dist_S"]), int(frame["dist_dtype"])
             if frame.get("ego") is not None:
                 ego = np.ascontiguousarray(frame["ego"], dtype=np.float64).reshape(n, 4)
                 f.ego = _addr(ego)

@@ -289,11 +289,24 @@ def test_c_abi_scenario_episodes_and_refusals(episodes):
 
 
 # ---- the static points gathered on the device -------------------------------------------------------------------------
-def _static_scene(episodes, slots, blocker):
+def _sized_static_set(cfg, size, blocker, seed):
+    """``size`` static points of a scenario: decoys far from every ego (60 - 90 m to the side) and, as the LAST three of a
+    set of three or more, a row across the road 6 m ahead of the scenario's ego -- the two outer points leave a gap on
+    the centre line that only the very last point closes -- or, without ``blocker``, the same row 30 m to the side."""
+    rng = np.random.default_rng(seed)
+    n_last = 3 if size >= 3 else 0
+    decoys = np.column_stack([rng.uniform(-40.0, 80.0, size - n_last), 60.0 + rng.uniform(0.0, 30.0, size - n_last)])
+    x0, y0 = cfg["ego_initial_state"][:2]
+    row = np.array([[x0 + 6.5, y0 + 1.6], [x0 + 6.5, y0 - 1.6], [x0 + 6.0, y0]]) + (0.0 if blocker else np.array([0.0, 30.0]))
+    return np.concatenate([decoys, row[:n_last]])
+
+
+def _static_scene(episodes, slots, blocker, sizes=None):
     """One lock step, no pedestrians, of slots on three scenarios with different static point sets: scenario_01 has none,
     scenario_02 its walls, scenario_03 three points (with ``blocker`` right in front of its ego: level 0 fails and the
     escalation retries are planned).  Returns the candidate tables of the step's LAST plan call and those of the same
-    requests planned through fot_plan_batch_scenarios with the static points passed from the host."""
+    requests planned through fot_plan_batch_scenarios with the static points passed from the host.  sizes: the three
+    scenarios' sets have these many points instead (``_sized_static_set``: the blocking points are the last of their set)."""
     cfgs = [scenario_config(episodes["meta"], n) for n in ("base", "walls", "turn")]
     parts = [_cfg_parts(c) for c in cfgs]
     x0, y0 = cfgs[2]["ego_initial_state"][:2]
@@ -301,6 +314,9 @@ def _static_scene(episodes, slots, blocker):
         np.array([[x0 + 6.0, y0 + 30.0], [x0 + 6.5, y0 + 30.4], [x0 + 6.5, y0 + 29.6]])
     points = [np.empty((0, 2)), expand_static_obstacles(cfgs[1]["static_obstacles"], step=0.5), near]
     assert len({len(p) for p in points}) == 3 and len(points[0]) == 0
+    if sizes is not None:                                          # sets of given sizes (_sized_static_set) instead
+        points = [_sized_static_set(cfgs[k], int(sizes[k]), blocker, 40 + k) for k in range(3)]
+        assert [len(p) for p in points] == list(sizes)
     consts = [_VectorStateMachine.constants_of(p[0]) for p in parts]
     slots = np.asarray(slots, np.int32)
     n = len(slots)
@@ -357,6 +373,29 @@ def test_static_points_gathered_on_the_device(episodes, blocker):
     assert loop_head == head                                       # the level-0 records: status, selection, cost, stats
     if blocker:
         assert n_failed >= 3 and 2 in failed_scen                  # (the blocked scenario_03 slots escalate)
+    assert len(loop_tabs) == len(host_tabs) > 0
+    for j, (a, b) in enumerate(zip(loop_tabs, host_tabs)):
+        for name, x, y in zip(("cost", "status", "keep", "n_t"), a, b):
+            assert np.array_equal(x, y, equal_nan=True), f"request {j}: {name}"
+
+
+@pytest.mark.parametrize("blocker", [False, True], ids=["level0", "escalations"])
+@pytest.mark.parametrize("sizes", [(0, 255, 257), (1, 256, 600)], ids=["0_255_257", "1_256_600"])
+def test_static_sets_across_the_gather_s_block_width(episodes, sizes, blocker):
+    """k_static_gather copies a request's set 256 points per pass: sets of 255, 256, 257 and 600 points (and of none and
+    one) whose blocking points are the LAST three, the decisive one the very last -- a gather that stopped after its first
+    pass would leave the centre line of the 257- and 600-point scenarios open.  Same comparison as above: level-0 records
+    and candidate tables against the same requests with host-passed points; blocked, every slot of a scenario whose set
+    has a blocking row fails level 0 and escalates."""
+    slots = [0, 1, 2, 1, 2, 0, 2, 1, 0]
+    loop_tabs, host_tabs, loop_head, head, n_failed, failed_scen = _static_scene(episodes, slots, blocker, sizes)
+    assert loop_head == head
+    blocked = sorted(k for k in range(3) if sizes[k] >= 3)
+    assert blocked == [1, 2]
+    if blocker:
+        assert sorted(failed_scen) == sorted(k for k in slots if k in blocked), failed_scen
+    else:
+        assert n_failed == 0
     assert len(loop_tabs) == len(host_tabs) > 0
     for j, (a, b) in enumerate(zip(loop_tabs, host_tabs)):
         for name, x, y in zip(("cost", "status", "keep", "n_t"), a, b):
