@@ -492,8 +492,8 @@ int fot_loop_step(fot_handle *h, const fot_loop_frame *frame, const int32_t *epi
  * for the same faults; a refused call changes nothing: no fot_loop_begin / n_slots differs from its count / ped_off not
  * starting at 0 or decreasing / a slot with n_frames < 1 or > n_frames_max / obs_len < 2 / bad predictor parameters
  * (FOT_ERR_INVALID), pred_len > FOT_MAX_PRED_LEN or n_dense + 1 > FOT_MAX_NT (FOT_ERR_UNSUPPORTED).
- * Constant-velocity predictor only: a frame with dist_raw samples needs a producer every step and stays with
- * fot_loop_step.  The slots run on scenario 0 after fot_loop_begin, each on its own scenario after
+ * The predictor is constant velocity, or -- after fot_loop_set_sampler, below -- the model of fot_sgan_load with the
+ * library's own noise; a frame with dist_raw samples of any other producer stays with fot_loop_step.  The slots run on scenario 0 after fot_loop_begin, each on its own scenario after
  * fot_loop_begin_scenarios.
  *
  * fot_loop_run: one lock step is what the closed loop around fot_loop_step does, in this order: the replay frame and the
@@ -709,6 +709,53 @@ int fot_sgan_load(fot_handle *h, const fot_sgan_desc *desc, int64_t n, const flo
 int fot_sgan_unload(fot_handle *h);
 int fot_sgan_sample(fot_handle *h, int32_t n_scenes, const int32_t *ped_off, const void *obs, int32_t S, const void *noise,
                     int32_t flags, void *out, void *stream);
+
+/* ---- counter-based noise for the sampler, and the resident loop's Social-GAN predictor -------------------------------------
+ * fot_sgan_noise writes the tensor [S][rows][noise_dim] that fot_sgan_sample takes as `noise`, drawn by the library itself:
+ * Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; 10 rounds) with
+ *   key     = the 64-bit seed, low word first
+ *   counter = { b = d / 4, p | (s << 16), step, slot }
+ * for dimension d of sample s of the row that is pedestrian p of slot `row_slot[r]` (row_index[r]: its index WITHIN the
+ * slot; 0 for a model with noise per scene, FOT_SGAN_NOISE_GLOBAL, whose rows are scenes) at that slot's own step count
+ * row_step[r] (fot_loop_run_out.steps before the step).  One block x0 .. x3 yields dimensions 4 b .. 4 b + 3:
+ *   FOT_NOISE_RAW          the uint32 words themselves (what bit-for-bit tests read)
+ *   FOT_NOISE_UNIFORM      (x >> 8) 2^-24, torch.rand's [0, 1)
+ *   FOT_NOISE_UNIFORM_SYM  (uniform - 0.5) 2: the reference's noise_type 'uniform' (sgan_vendor/models.py get_noise), [-1, 1)
+ *   FOT_NOISE_GAUSSIAN     Box-Muller on (x0, x1) and (x2, x3): u1 = ((x >> 8) + 1) 2^-24 in (0, 1], u2 = (x' >> 8) 2^-24,
+ *                          r = sqrt(-2 ln u1), outputs r cos(2 pi u2), r sin(2 pi u2), in float64, rounded once to float32
+ * A number is a function of (seed, slot, step, p, s, d) alone -- no atomics, nothing of the launch shape or of the other
+ * rows -- so a stepwise caller can ask for exactly the noise a resident loop used for any subset of slots at any step.  It
+ * is NOT torch.randn's stream: seeds are not comparable with the reference's runs.
+ * row_slot / row_step / row_index: host [rows]; flags FOT_OUT_DEVICE: out is device memory.  Synchronous, enqueued on
+ * `stream` (NULL = the handle's).  No model needs to be loaded.  FOT_ERR_INVALID, nothing changed: an unknown kind or
+ * flag, S < 1, rows < 0, noise_dim < 0, a NULL table or `out` that is needed, a negative table entry, row_index > 65535;
+ * FOT_ERR_UNSUPPORTED: S > FOT_MAX_SAMPLES.
+ *
+ * fot_loop_set_sampler(h, S, seed, kind): between fot_loop_set_replay and the first step.  The resident loop then predicts
+ * with the model of fot_sgan_load instead of constant velocity: once the observer is ready, a step gathers the window
+ * [obs_len][rows][2] float32 from the recording in HBM (the observer's sample frames, clamped to each slot's recording),
+ * draws the noise above (kind: FOT_NOISE_GAUSSIAN | FOT_NOISE_UNIFORM_SYM) for the running slots at their step counts,
+ * runs the sampler and resamples the S samples into each episode's [S][P_e][n_dense + 1][2] block, the current positions
+ * leading every sample -- what fot_loop_step makes of a frame with dist_raw.  Nothing is synchronised and nothing crosses
+ * the bus in between; level 0, the escalation levels, the resolve and the history run as without a sampler.  seed, slot
+ * and fot_loop_run_out.steps reproduce any step's noise through fot_sgan_noise.
+ * Refusals, a refused call changes nothing.  FOT_ERR_INVALID: no replay set; no model loaded; after the first step; S < 1;
+ * an unknown kind; the model's obs_len / pred_len differ from the replay's.  FOT_ERR_UNSUPPORTED: S > FOT_MAX_SAMPLES; a
+ * slot of more than FOT_SGAN_MAX_PEDS pedestrians; a loop begun with fot_loop_begin_scenarios; summaries enabled
+ * (fot_loop_summary_enable is refused in turn while a sampler is set: its prediction-error ring reads the
+ * constant-velocity tensor's layout).  fot_sgan_load / fot_sgan_unload are refused (FOT_ERR_INVALID) while a sampler is
+ * set; fot_loop_begin* and fot_loop_set_replay drop the sampler.
+ * Both entries are additions: no structure, capacity or existing entry changes, so FOT_ABI_VERSION and the words of
+ * fot_abi_info stay as they are; a binding that needs the entries looks the symbols up. */
+#define FOT_NOISE_RAW 0
+#define FOT_NOISE_UNIFORM 1
+#define FOT_NOISE_GAUSSIAN 2
+#define FOT_NOISE_UNIFORM_SYM 3
+#define FOT_NOISE_KINDS 4
+int fot_sgan_noise(fot_handle *h, uint64_t seed, int32_t kind, int32_t S, int32_t rows, int32_t noise_dim,
+                   const int32_t *row_slot, const int32_t *row_step, const int32_t *row_index, int32_t flags, void *out,
+                   void *stream);
+int fot_loop_set_sampler(fot_handle *h, int32_t S, uint64_t seed, int32_t kind);
 
 /* Host utility (no GPU): the first kmax samples of the 15 path arrays of records[index[i]], i < n, as one dense block
  * out[15][n][kmax] in fot_result array order (t .. c) -- what a history keeps of a step's records. */

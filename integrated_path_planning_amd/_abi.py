@@ -178,7 +178,7 @@ SYMBOLS = ["fot_version", "fot_abi_info", "fot_create", "fot_destroy", "fot_live
            "fot_add_scenario", "fot_set_scenario_path_waypoints", "fot_set_scenario_path_coeffs",
            "fot_plan_batch_scenarios", "fot_plan_batch_scenarios_device", "fot_get_scenario_path_coeffs",
            "fot_loop_begin_scenarios", "fot_loop_set_scenario_static",
-           "fot_sgan_weight_count", "fot_sgan_load", "fot_sgan_unload", "fot_sgan_sample"]
+           "fot_sgan_weight_count", "fot_sgan_load", "fot_sgan_unload", "fot_sgan_sample", "fot_sgan_noise", "fot_loop_set_sampler"]
 PROFILE_KERNELS = 3                      # FOT_PROFILE_KERNELS (include/fot.h)
 ABI_VERSION = 8                          # FOT_ABI_VERSION
 MAX_TI, MAX_TV, MAX_BRAKE, MAX_PRED_LEN = 64, 32, 32, 32
@@ -191,6 +191,8 @@ SGAN_POOL_HIDDEN = 512
 SGAN_POOL_NONE, SGAN_POOL_NET, SGAN_SPOOL = 0, 1, 2
 SGAN_NOISE_PED, SGAN_NOISE_GLOBAL = 0, 1
 SGAN_OBS_DEVICE, SGAN_NOISE_DEVICE = 4, 8
+# kinds of fot_sgan_noise (FOT_NOISE_*)
+NOISE_RAW, NOISE_UNIFORM, NOISE_GAUSSIAN, NOISE_UNIFORM_SYM, NOISE_KINDS = 0, 1, 2, 3, 4
 MARGIN_NAMES = ["speed", "accel", "curvature", "lat_accel", "road", "collision", "stop_filter", "structural"]
 
 _lib = None
@@ -423,6 +425,8 @@ def lib():
     L.fot_sgan_load.argtypes = [vp, C.POINTER(SganDesc), C.c_int64, vp]
     L.fot_sgan_unload.argtypes = [vp]
     L.fot_sgan_sample.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp]
+    L.fot_sgan_noise.argtypes = [vp, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, vp]
+    L.fot_loop_set_sampler.argtypes = [vp, C.c_int32, C.c_uint64, C.c_int32]
     L.fot_gather_paths.argtypes = [vp, C.c_int32, vp, C.c_int32, vp]
     L.fot_wire_n_total.argtypes = [vp]
     L.fot_wire_record_bytes.argtypes = [C.c_int32]

@@ -222,6 +222,7 @@ class _ResidentStep(dict):
     def __init__(self, loop: "BatchedClosedLoop", out: dict, k: int, t: float, keep_paths: bool):
         super().__init__()
         self._src = (loop, out, k, t, keep_paths)
+        self.window_frames, self.lock_step = None, -1                # set by a loop whose sampler predicted at this step
 
     def _fill(self) -> None:
         if self._src is None:
@@ -244,6 +245,10 @@ class _ResidentStep(dict):
             o32 = np.stack([frame("trajectories", o["obs_prev_frame"][k]), frame("trajectories", o["obs_last_frame"][k])],
                            axis=0).astype(np.float32)
             pred_src = (o32, float(o["staleness"][k]))
+            if self.window_frames is not None:                        # the loop's sampler predicted (every slot's step
+                assert self.window_frames[-1] == int(o["obs_last_frame"][k])    # count is the lock step's index)
+                window = np.stack([frame("trajectories", f) for f in self.window_frames], axis=0).astype(np.float32)
+                pred_src = ("sgan", window, sel, np.full(n, self.lock_step, np.int64), o32, float(o["staleness"][k]))
         if keep_paths:
             paths = {f: o["paths"][k, j][sel] for j, f in enumerate(_abi.PATH_FIELDS)}
         else:
@@ -458,7 +463,11 @@ class BatchedClosedLoop:
         leave the GPU: they are resampled into the planner's tensor inside the lock step's one call (fot_loop_step).
         resident: the whole episode inside the library (fot_loop_set_replay / fot_loop_run): the recording is uploaded to
         HBM once, and ``run(n)`` is a few calls that execute n lock steps each without coming back to Python in between;
-        ``step()`` is ``run(1)``.  Constant-velocity predictor on the library's own engine only.  The loop's arrays
+        ``step()`` is ``run(1)``.  On the library's own engine, with the constant-velocity predictor -- or with a
+        ``prediction.SganSampler`` in counter mode built without an engine (``SganSampler(None, weights, S,
+        counter_seed=...)``, ``device_samples=True``, ``distribution_aware_planning``): window, noise, samples and the
+        planner's tensor are then formed inside the library every step (fot_loop_set_sampler), nothing crosses the
+        bus.  The loop's arrays
         (``ego``, ``sm.state``, ``alive``, ...) are brought up to date after every call; the Python ``observer`` is not
         advanced (the handle owns the clock).
         summaries (resident loops only): the library accumulates every episode's summary metrics on the device while the
@@ -488,9 +497,19 @@ class BatchedClosedLoop:
             raise ValueError("prediction_scores=True needs a multi-sample predictor (sample_source)")
         if self._pred_scores and engine is not None and not hasattr(engine, "prediction_scores"):
             raise ValueError("prediction_scores=True needs the library's own engine (fot_prediction_scores)")
-        if self._resident and (sample_source is not None or engine is not None or resampler is not None or fused not in (None, True)):
+        # a resident loop's sample source: prediction.SganSampler in counter mode, run inside the library
+        # (fot_loop_set_sampler) on the loop's own engine, planning against the whole distribution
+        self._resident_sampler = bool(self._resident and sample_source is not None and device_samples
+                                      and getattr(sample_source, "counter_seed", None) is not None
+                                      and hasattr(sample_source, "bind") and engine is None
+                                      and getattr(sample_source, "engine", None) is None)
+        if self._resident and ((sample_source is not None and not self._resident_sampler) or engine is not None
+                               or resampler is not None or fused not in (None, True)):
             raise ValueError("resident=True needs the constant-velocity predictor on the library's own engine "
                              "(no sample_source, engine or resampler; the one-call step)")
+        if self._resident_sampler and self._summaries:
+            raise ValueError("summaries=True with a sampler: the resident loop's summaries read the constant-velocity "
+                             "prediction (not supported yet)")
         # a sequence of configurations, one per episode: equal ones share a scenario of the ONE handle; more than one
         # distinct scenario runs through the one-call step or resident=True only
         self.scenarios, self.slot_scenario, per_episode = None, None, None
@@ -539,6 +558,12 @@ class BatchedClosedLoop:
             self.s_end = s_end[self.slot_scenario]
             self.scenario_static_points = [expand_static_obstacles(getattr(k, "static_obstacles", None), step=0.5)
                                            for k in self.scenarios]
+        if sample_source is not None and engine is None and hasattr(sample_source, "bind") and \
+                getattr(sample_source, "engine", self.engine) is None:
+            sample_source.bind(self.engine)                           # (a sampler built without an engine joins this one)
+        if self._resident_sampler and (isinstance(config, (list, tuple)) or self.scenarios is not None):
+            raise ValueError("resident=True with a sampler takes one configuration (a scenario loop plans against no "
+                             "distribution)")
         self._device_samples = bool(device_samples)
         if self._device_samples and not (sample_source is not None and self.distribution_aware and engine is None and resampler is None):
             raise ValueError("device_samples needs a sample_source, distribution_aware_planning and the library's own engine")
@@ -585,6 +610,7 @@ class BatchedClosedLoop:
         self._rows_key, self._rows = None, None
         self.frame, self.ped_time = 0, 0.0
         self.observer = Observer(c.obs_len, c.dt, self.sgan_dt)      # one sampling clock; samples = all episodes' peds
+        self._frame_clock = Observer(c.obs_len, c.dt, self.sgan_dt)  # the same clock on frame numbers (a resident loop's window)
         # ---- ego, state machine and planner caches as arrays
         e0 = np.array([np.asarray(v, float)[:5] for v in ego_initial_states], dtype=float).reshape(n, 5)
         self.ego = e0.copy()                                         # x, y, yaw, v, a
@@ -631,6 +657,8 @@ class BatchedClosedLoop:
                 goal_distance=self.GOAL_DISTANCE)      # (a scenario loop: the library takes each slot's own path's end)
             if self._summaries:
                 self.engine.loop_summary_enable(True, int(getattr(c, "num_samples", 1)))
+            if self._resident_sampler:
+                self.engine.loop_set_sampler(sample_source.num_samples, sample_source.counter_seed, sample_source.noise_kind)
 
     def close(self) -> None:
         """Release the libfot handle (streams, workspace) now rather than at garbage collection."""
@@ -691,6 +719,7 @@ class BatchedClosedLoop:
         self.ped_time += self.dt
         every = np.arange(len(self.peds))
         self.observer.update(self._ped_frame("trajectories", every), self.ped_time)
+        self._frame_clock.update(np.array([self.frame]), self.ped_time)
 
     def _warmup(self) -> None:
         """integrated_simulator.py:406-422: fill the observers before time 0."""
@@ -714,6 +743,10 @@ class BatchedClosedLoop:
         if not getattr(self.sample_source, "needs_history", False):
             return self.sample_source(obs_last, obs_prev)
         window = np.stack([h[rows] for h in self.observer.history], axis=0).astype(np.float32)
+        if getattr(self.sample_source, "counter_seed", None) is not None:
+            # the counter mode: the noise is keyed by every running episode's slot and its own step count
+            sel = np.flatnonzero(self.alive)
+            return self.sample_source(window, np.asarray(off, dtype=np.int32), slots=sel, steps=self.step_counts[sel])
         return self.sample_source(window, np.asarray(off, dtype=np.int32))
 
     def _predict(self, sel, off, pos):
@@ -1004,7 +1037,11 @@ class BatchedClosedLoop:
         the episode's own pedestrians -> [sum P, T, 2]."""
         n = len(off) - 1
         dev = np.linalg.norm(dist - dist.mean(axis=0)[None], axis=-1).sum(axis=2)      # [S, sum P]
-        per_ep = np.add.reduceat(dev, off[:-1], axis=1) if dev.shape[1] else np.zeros((len(dist), n))
+        # (np.add.reduceat takes no index past the array: episodes without pedestrians at the END of the frame are left out)
+        m = int(np.count_nonzero(off[:-1] < dev.shape[1]))
+        per_ep = np.zeros((len(dist), n))
+        if m:
+            per_ep[:, :m] = np.add.reduceat(dev, off[:m], axis=1)
         per_ep[:, off[:-1] == off[1:]] = 0.0                                      # (episodes without pedestrians)
         best = np.argmin(per_ep, axis=0)                                         # [episodes]
         return dist[np.repeat(best, off[1:] - off[:-1]), np.arange(dist.shape[1])]
@@ -1012,6 +1049,12 @@ class BatchedClosedLoop:
     def _materialise_prediction(self, pred_src, off):
         """The prediction a one-call step left in HBM, computed again for whoever reads the step's record (same kernels,
         same numbers): the constant-velocity tracks, or the best sample of the distribution's raw samples."""
+        if isinstance(pred_src[0], str) and pred_src[0] == "sgan":
+            # a resident sampler step: the window, the running slots and their step counts -- the library's noise and
+            # samples once more, then as a stepwise step's
+            _, window, sel, steps, o32, stale = pred_src
+            raw = self.sample_source.sample(window, np.asarray(off, dtype=np.int32), slots=sel, steps=steps)
+            pred_src = ("dist", raw, o32, stale)
         if isinstance(pred_src[0], str):                              # ("dist", raw samples in HBM, observations, staleness)
             _, raw, o32, stale = pred_src
             raw_h = raw.detach().cpu().numpy().astype(np.float64)
@@ -1158,6 +1201,10 @@ class BatchedClosedLoop:
                 self._steps.append(_ResidentStep(self, o, k, self.time, keep_paths))
                 self.time += self.dt
                 self.ped_time += self.dt
+                self._frame_clock.update(np.array([self.frame + k + 1]), self.ped_time)
+                if self._resident_sampler and self._frame_clock.is_ready:
+                    self._steps[-1].window_frames = [int(f[0]) for f in self._frame_clock.history]
+                    self._steps[-1].lock_step = len(self._steps) - 1
             self.frame += done
             took = np.flatnonzero(ran.any(axis=0))
             last = done - 1 - np.argmax(ran[::-1, took], axis=0)      # the last step of the call each slot ran

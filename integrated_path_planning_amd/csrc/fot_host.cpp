@@ -146,6 +146,17 @@ struct LoopSummaryAcc {
     void release() { dRing.release(); dRingP.release(); dTotals.release(); hOut.release(); hSteps.release(); }
 };
 
+// fot_loop_set_sampler: the resident loop's Social-GAN predictor -- the window, the noise and the raw samples of a step in
+// HBM, the noise kernel's row tables in pinned memory
+struct LoopSampler {
+    bool on = false;
+    int S = 0, kind = 0;
+    uint64_t seed = 0;
+    DevBuf dWin, dNoise, dRaw;                   // [obs_len][rows][2] | [S][noise rows][nd] | [S][pred_len][rows][2], float32
+    PinnedBuf hTab;                              // slot | step | index, n_cols + n_slots entries each
+    void release() { dWin.release(); dNoise.release(); dRaw.release(); hTab.release(); }
+};
+
 // fot_loop_set_replay / fot_loop_run: the recording (host copy for the prepend test, HBM copy for the frame kernel), the
 // replay clock and what a resident step keeps on the device
 struct LoopReplay {
@@ -163,9 +174,10 @@ struct LoopReplay {
     PinnedBuf hStage, hDigest, hHistTab, hWord;  // FrameStage | LoopDigest[] | followed record + slot | completion words
     int32_t seq = 0;                             // value the completion words are raised to next
     LoopSummaryAcc sum;
+    LoopSampler smp;
     void release()
     {
-        sum.release();
+        sum.release(); smp.release();
         dPos.release(); dVel.release(); dTab.release(); dFrame.release(); dRec.release(); dHist.release();
         hStage.release(); hDigest.release(); hHistTab.release(); hWord.release();
     }
@@ -262,7 +274,12 @@ struct fot_handle {
         fot_sgan_desc desc{};
         SgDev dev{};
         DevBuf dImg, dOff, dScene, dObs, dNoise, dOut, dHenc, dPool, dCtx, dH, dC, dXY;
-        void release() { for (DevBuf *b : { &dImg, &dOff, &dScene, &dObs, &dNoise, &dOut, &dHenc, &dPool, &dCtx, &dH, &dC, &dXY }) b->release(); }
+        PinnedBuf hTab;                          // fot_sgan_noise: the row tables the kernel reads
+        void release()
+        {
+            for (DevBuf *b : { &dImg, &dOff, &dScene, &dObs, &dNoise, &dOut, &dHenc, &dPool, &dCtx, &dH, &dC, &dXY }) b->release();
+            hTab.release();
+        }
     } sgan;
     bool last_valid = false;
     // profiling: event pairs around kernel launches
@@ -1745,6 +1762,7 @@ int fot_loop_begin(fot_handle *h, int32_t n_episodes, const fot_loop_config *cfg
     E.state.assign(n, 0); E.fails.assign(n, 0); E.stats.assign(8 * n, -1);
     h->loop.replay.set = false;                                  // (a new loop: the handle's clock, if it had one, is gone)
     h->loop.replay.sum.on = false;                               // ... and the summaries' accumulators with it
+    h->loop.replay.smp.on = false;                               // ... and the sampler
     return FOT_OK;
 }
 
@@ -1801,6 +1819,7 @@ int fot_loop_begin_scenarios(fot_handle *h, int32_t n_episodes, int32_t n_cfg, c
     E.state.assign(n, 0); E.fails.assign(n, 0); E.stats.assign(8 * n, -1);
     L.replay.set = false;
     L.replay.sum.on = false;
+    L.replay.smp.on = false;
     return FOT_OK;
 }
 
@@ -1935,6 +1954,65 @@ struct FrameLayout {
     }
 };
 
+// The launches of fot_sgan_sample behind its inputs, enqueue only (no copy from host memory, no synchronisation): all S
+// samples of the N > 0 pedestrians of n_scenes scenes.  d_off [n_scenes + 1] and d_scene [N] (the scene of every pedestrian;
+// nullptr unless the noise is per scene) are device memory, as are the tensors.
+int sgan_enqueue(fot_handle *h, int n_scenes, int N, int S, const int32_t *d_off, const int32_t *d_scene, const float *d_obs,
+                 const float *d_noise, float *d_out, hipStream_t st)
+{
+    fot_handle::Sgan &G = h->sgan;
+    const fot_sgan_desc &d = G.desc;
+    const int nd = d.noise_dim, noise_rows = d.noise_mix_type == FOT_SGAN_NOISE_GLOBAL ? n_scenes : N;
+    const int E = d.embedding_dim, He = d.encoder_h_dim, Hd = d.decoder_h_dim, T = d.obs_len, L = d.pred_len;
+    const bool pooled = sg_pooled(d), steps = sg_pool_steps(d), context = sg_has_context(d);
+    const int nc = context ? Hd - nd : He;
+    const size_t rows = (size_t)S * N;
+    const float *img = G.dImg.as<float>();
+    // once per pedestrian / scene: encoder, first pooling, context MLP
+    HIP_TRY(h, G.dHenc.ensure(sizeof(float) * (size_t)N * He));
+    LAUNCH_TRY(h, launch_sgan_encode(img, G.dev.enc, E, He, T, N, d_obs, G.dHenc.as<float>(), st));
+    const int bp = pooled ? G.dev.pool.b_pad : 0;
+    if (pooled) {
+        HIP_TRY(h, G.dPool.ensure(sizeof(float) * (steps ? rows : (size_t)N) * bp));
+        HIP_TRY(h, hipMemsetAsync(G.dPool.p, 0, sizeof(float) * (size_t)N * bp, st));
+        LAUNCH_TRY(h, launch_sgan_pool(img, G.dev.pool, n_scenes, 1, N, d_off, G.dHenc.as<float>(),
+                                       d_obs + 2 * (size_t)(T - 1) * N, G.dPool.as<float>(), st));
+    }
+    const float *d_ctx = G.dHenc.as<float>();
+    if (context) {
+        HIP_TRY(h, G.dCtx.ensure(sizeof(float) * (size_t)N * nc));
+        LAUNCH_TRY(h, launch_sgan_mlp(img, G.dev.ctx, G.dHenc.as<float>(), He, G.dPool.as<float>(), pooled ? d.bottleneck_dim : 0, bp,
+                                      N, G.dCtx.as<float>(), nc, st));
+        d_ctx = G.dCtx.as<float>();
+    }
+    // once per sample: the decoder
+    SgDecode a{};
+    a.img = img; a.l = G.dev.dec; a.pos_w = G.dev.pos_w; a.pos_b = G.dev.pos_b;
+    a.E = E; a.H = Hd; a.N = N; a.S = S; a.obs_len = T; a.pred_len = L;
+    a.obs = d_obs; a.ctx = d_ctx; a.noise = d_noise; a.row_scene = d_scene;
+    a.nc = nc; a.nd = nd; a.noise_rows = noise_rows; a.out = d_out;
+    if (!steps) {
+        a.t0 = 0; a.n_steps = L; a.init = 1; a.save = 0;
+        LAUNCH_TRY(h, launch_sgan_decode(a, st));
+    } else {
+        HIP_TRY(h, G.dH.ensure(sizeof(float) * rows * Hd));
+        HIP_TRY(h, G.dC.ensure(sizeof(float) * rows * Hd));
+        HIP_TRY(h, G.dXY.ensure(sizeof(float) * rows * 6));
+        a.h = G.dH.as<float>(); a.c = G.dC.as<float>();
+        a.pos = G.dXY.as<float>(); a.rel = a.pos + rows * 2; a.cum = a.pos + rows * 4;
+        a.n_steps = 1; a.save = 1;
+        for (int t = 0; t < L; ++t) {
+            a.t0 = t; a.init = t == 0;
+            LAUNCH_TRY(h, launch_sgan_decode(a, st));
+            if (t == L - 1) break;                                   // (the last step's pooled state is never read)
+            HIP_TRY(h, hipMemsetAsync(G.dPool.p, 0, sizeof(float) * rows * bp, st));
+            LAUNCH_TRY(h, launch_sgan_pool(img, G.dev.dpool, n_scenes, S, N, d_off, a.h, a.pos, G.dPool.as<float>(), st));
+            LAUNCH_TRY(h, launch_sgan_mlp(img, G.dev.dmlp, a.h, Hd, G.dPool.as<float>(), d.bottleneck_dim, bp, (int64_t)rows, a.h, Hd, st));
+        }
+    }
+    return FOT_OK;
+}
+
 // one lock step of the running slots `sel`; step k of the call (outputs row k)
 int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loop_run_out *out, double *d_hist_step)
 {
@@ -1969,18 +2047,22 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     L.ped_off.assign((size_t)n + 1, 0); L.blk_off.assign((size_t)n + 1, 0); L.t_len.assign((size_t)n, 1);
     L.dist_S = 0;
     const size_t row_doubles = 2 * (size_t)R.n_cols;
+    int rows_run = 0;
+    for (int i = 0; i < n; ++i) rows_run += R.ped_off[sel[i] + 1] - R.ped_off[sel[i]];
+    const bool sampled = R.smp.on && ready && rows_run > 0;      // this step predicts with the sampler
     for (int i = 0; i < n; ++i) {
         const int e = sel[i], c0 = R.ped_off[e], P_e = R.ped_off[e + 1] - c0, nf = R.n_frames[e];
         int pre = 0;
-        if (ready && f_prev >= 0 && P_e > 0) {
+        if (!sampled && ready && f_prev >= 0 && P_e > 0) {
             const double *cur = R.pos.data() + (size_t)replay_row(f_cur, nf) * row_doubles + 2 * (size_t)c0;
             const double *last = R.pos.data() + (size_t)replay_row(f_last, nf) * row_doubles + 2 * (size_t)c0;
             const double *prev = R.pos.data() + (size_t)replay_row(f_prev, nf) * row_doubles + 2 * (size_t)c0;
             pre = replay_prepend(P_e, last, prev, cur, C.rp.sgan_dt, C.rp.sim_dt, stale) ? 1 : 0;
         }
+        if (sampled) pre = 1;                                    // (the current positions lead EVERY sample, :514-525)
         L.t_len[i] = ready ? R.n_dense + pre : 1;
         L.ped_off[i + 1] = L.ped_off[i] + P_e;
-        L.blk_off[i + 1] = L.blk_off[i] + (int64_t)P_e * L.t_len[i];
+        L.blk_off[i + 1] = L.blk_off[i] + (int64_t)(sampled ? R.smp.S : 1) * P_e * L.t_len[i];
         s_slot[i] = e; s_ped0[i] = L.ped_off[i]; s_blk[i] = L.blk_off[i]; s_pre[i] = pre;
         if (E.scenarios) s_scen[i] = L.frame_scen[(size_t)i] = E.scen[(size_t)e];
         for (int q = 0; q < 4; ++q) s_ego[4 * (size_t)i + q] = W.ego4[4 * (size_t)i + q];
@@ -2000,7 +2082,39 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     L.p_scen = E.scenarios ? fd.scen : nullptr;
     L.ego_radius = C.ego_radius; L.ped_radius = C.ped_radius; L.use_footprint = C.use_footprint;
     L.dyn_ptr = fd.pos;                                          // not ready: the current positions, T = 1
-    if (ready && rows > 0) {
+    if (sampled) {
+        // window -> noise -> samples -> every episode's [S][P_e][n_dense + 1][2] block, all in HBM behind k_loop_frame
+        LoopSampler &M = R.smp;
+        const fot_sgan_desc &d = h->sgan.desc;
+        const bool global_noise = d.noise_mix_type == FOT_SGAN_NOISE_GLOBAL;
+        const int nd = d.noise_dim, noise_rows = global_noise ? n : rows;
+        SgWindow w{};
+        w.pos = rv.pos; w.slot_ped0 = rv.slot_ped0; w.slot_frames = rv.slot_frames;
+        w.ped_ep = fd.ped_ep; w.ep_ped0 = fd.ped0; w.ep_slot = s_slot;
+        w.n_cols = R.n_cols; w.rows = rows; w.obs_len = d.obs_len;
+        for (int j = 0; j < d.obs_len; ++j) w.frames.f[j] = R.clock.sample_frame[(size_t)j];
+        w.out = M.dWin.as<float>();
+        LAUNCH_TRY(h, launch_sgan_window(w, st));
+        if (nd > 0) {
+            const size_t cap = (size_t)R.n_cols + (size_t)n_slots;
+            int32_t *t_slot = (int32_t *)M.hTab.p, *t_step = t_slot + cap, *t_idx = t_step + cap;
+            int r = 0;
+            for (int i = 0; i < n; ++i) {
+                const int e = sel[i], P_e = R.ped_off[e + 1] - R.ped_off[e];
+                for (int p = 0; p < (global_noise ? 1 : P_e); ++p, ++r) { t_slot[r] = e; t_step[r] = R.steps[(size_t)e]; t_idx[r] = p; }
+            }
+            SgNoise a{};
+            a.seed = M.seed; a.kind = M.kind; a.S = M.S; a.rows = noise_rows; a.nd = nd; a.n_blk = (nd + 3) / 4;
+            a.slot = t_slot; a.step = t_step; a.index = t_idx; a.out = (uint32_t *)M.dNoise.p;
+            LAUNCH_TRY(h, launch_sgan_noise(a, st));
+        }
+        { int r = sgan_enqueue(h, n, rows, M.S, fd.ped0, global_noise && nd > 0 ? fd.ped_ep : nullptr, M.dWin.as<float>(),
+                               M.dNoise.as<float>(), M.dRaw.as<float>(), st); if (r != FOT_OK) return r; }
+        L.dyn_ptr = L.dDyn.p;
+        L.dist_S = M.S;
+        LAUNCH_TRY(h, launch_resample(C.rp.sgan_dt, C.rp.sim_dt, stale, M.S, C.pred_len, rows, R.n_dense, 1, 1, 0, M.dRaw.p,
+                                      FOT_F32, fd.last, fd.pos, L.dDyn.p, FOT_F64, 0, st, fd.ped_ep, fd.ped0, fd.blk));
+    } else if (ready && rows > 0) {
         L.dyn_ptr = L.dDyn.p;
         LAUNCH_TRY(h, launch_predict_cv_frame(C.rp.sgan_dt, C.rp.sim_dt, stale, rows, R.n_dense, fd, L.dDyn.as<double>(), st));
     }
@@ -2119,6 +2233,7 @@ int fot_loop_set_replay(fot_handle *h, const fot_loop_replay *rp)
     LoopReplay &R = L.replay;
     R.set = false;
     R.sum.on = false;                                            // (a new recording: summaries are enabled again, if wanted)
+    R.smp.on = false;                                            // ... and so is a sampler
     const size_t rec_doubles = (size_t)rp->n_frames_max * cols * 2;
     const int max_lvl = E.max_lvl;
     const size_t n_rec = (size_t)std::max(n, 1) * (size_t)max_lvl;
@@ -2170,6 +2285,7 @@ int fot_loop_summary_enable(fot_handle *h, int32_t on, int32_t num_samples)
     if (R.clock.frame != R.cfg.warmup_frames) return fail(h, FOT_ERR_INVALID, "fot_loop_summary_enable: the run has begun (enable between fot_loop_set_replay and the first step)");
     LoopSummaryAcc &A = R.sum;
     if (!on) { A.on = false; return FOT_OK; }
+    if (R.smp.on) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_summary_enable: a sampler is set (fot_loop_set_sampler): the prediction-error ring reads the constant-velocity tensor");
     if (num_samples < 1) return fail(h, FOT_ERR_INVALID, "fot_loop_summary_enable: num_samples < 1");
     const int stride = summary_stride(R.cfg.rp.sgan_dt, R.cfg.rp.sim_dt);
     if (stride < 1) return fail(h, FOT_ERR_INVALID, "fot_loop_summary_enable: sgan_dt must be a multiple of sim_dt");
@@ -2344,6 +2460,7 @@ int fot_sgan_load(fot_handle *h, const fot_sgan_desc *desc, int64_t n, const flo
 {
     if (!h) return FOT_ERR_INVALID;
     if (!desc || !weights) return fail(h, FOT_ERR_INVALID, "fot_sgan_load: desc / weights is NULL");
+    if (h->loop.replay.set && h->loop.replay.smp.on) return fail(h, FOT_ERR_INVALID, "fot_sgan_load: the resident loop's sampler uses the model (fot_loop_set_sampler)");
     std::string why;
     const int rc = sg_check_desc(*desc, why);
     if (rc != FOT_OK) return fail(h, rc, why);
@@ -2365,6 +2482,7 @@ int fot_sgan_load(fot_handle *h, const fot_sgan_desc *desc, int64_t n, const flo
 int fot_sgan_unload(fot_handle *h)
 {
     if (!h) return FOT_ERR_INVALID;
+    if (h->loop.replay.set && h->loop.replay.smp.on) return fail(h, FOT_ERR_INVALID, "fot_sgan_unload: the resident loop's sampler uses the model (fot_loop_set_sampler)");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->sgan.loaded = false;
@@ -2395,14 +2513,12 @@ int fot_sgan_sample(fot_handle *h, int32_t n_scenes, const int32_t *ped_off, con
     const int nd = d.noise_dim, noise_rows = global_noise ? n_scenes : N;
     if (N == 0) return FOT_OK;
     if (!obs || !out || (nd > 0 && !noise)) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: NULL tensor");
-    const int E = d.embedding_dim, He = d.encoder_h_dim, Hd = d.decoder_h_dim, T = d.obs_len, L = d.pred_len;
-    const bool pooled = sg_pooled(d), steps = sg_pool_steps(d), context = sg_has_context(d);
-    const int nc = context ? Hd - nd : He;
+    const int T = d.obs_len, L = d.pred_len;
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     { int r = order_begin(h, st); if (r != FOT_OK) return r; }
     const size_t obs_bytes = sizeof(float) * 2 * (size_t)T * N, noise_bytes = sizeof(float) * (size_t)S * noise_rows * nd;
-    const size_t out_bytes = sizeof(float) * 2 * (size_t)S * L * N, rows = (size_t)S * N;
+    const size_t out_bytes = sizeof(float) * 2 * (size_t)S * L * N;
     // the offsets and, for noise per scene, every pedestrian's scene
     std::vector<int32_t> scene_of;
     HIP_TRY(h, G.dOff.ensure(sizeof(int32_t) * ((size_t)n_scenes + 1)));
@@ -2426,53 +2542,97 @@ int fot_sgan_sample(fot_handle *h, int32_t n_scenes, const int32_t *ped_off, con
     }
     float *d_out = (float *)out;
     if (!(flags & FOT_OUT_DEVICE)) { HIP_TRY(h, G.dOut.ensure(out_bytes)); d_out = G.dOut.as<float>(); }
-    const float *img = G.dImg.as<float>();
-    const int32_t *d_off = G.dOff.as<int32_t>();
-    // once per pedestrian / scene: encoder, first pooling, context MLP
-    HIP_TRY(h, G.dHenc.ensure(sizeof(float) * (size_t)N * He));
-    LAUNCH_TRY(h, launch_sgan_encode(img, G.dev.enc, E, He, T, N, d_obs, G.dHenc.as<float>(), st));
-    const int bp = pooled ? G.dev.pool.b_pad : 0;
-    if (pooled) {
-        HIP_TRY(h, G.dPool.ensure(sizeof(float) * (steps ? rows : (size_t)N) * bp));
-        HIP_TRY(h, hipMemsetAsync(G.dPool.p, 0, sizeof(float) * (size_t)N * bp, st));
-        LAUNCH_TRY(h, launch_sgan_pool(img, G.dev.pool, n_scenes, 1, N, d_off, G.dHenc.as<float>(),
-                                       d_obs + 2 * (size_t)(T - 1) * N, G.dPool.as<float>(), st));
-    }
-    const float *d_ctx = G.dHenc.as<float>();
-    if (context) {
-        HIP_TRY(h, G.dCtx.ensure(sizeof(float) * (size_t)N * nc));
-        LAUNCH_TRY(h, launch_sgan_mlp(img, G.dev.ctx, G.dHenc.as<float>(), He, G.dPool.as<float>(), pooled ? d.bottleneck_dim : 0, bp,
-                                      N, G.dCtx.as<float>(), nc, st));
-        d_ctx = G.dCtx.as<float>();
-    }
-    // once per sample: the decoder
-    SgDecode a{};
-    a.img = img; a.l = G.dev.dec; a.pos_w = G.dev.pos_w; a.pos_b = G.dev.pos_b;
-    a.E = E; a.H = Hd; a.N = N; a.S = S; a.obs_len = T; a.pred_len = L;
-    a.obs = d_obs; a.ctx = d_ctx; a.noise = d_noise; a.row_scene = global_noise && nd > 0 ? G.dScene.as<int32_t>() : nullptr;
-    a.nc = nc; a.nd = nd; a.noise_rows = noise_rows; a.out = d_out;
-    if (!steps) {
-        a.t0 = 0; a.n_steps = L; a.init = 1; a.save = 0;
-        LAUNCH_TRY(h, launch_sgan_decode(a, st));
-    } else {
-        HIP_TRY(h, G.dH.ensure(sizeof(float) * rows * Hd));
-        HIP_TRY(h, G.dC.ensure(sizeof(float) * rows * Hd));
-        HIP_TRY(h, G.dXY.ensure(sizeof(float) * rows * 6));
-        a.h = G.dH.as<float>(); a.c = G.dC.as<float>();
-        a.pos = G.dXY.as<float>(); a.rel = a.pos + rows * 2; a.cum = a.pos + rows * 4;
-        a.n_steps = 1; a.save = 1;
-        for (int t = 0; t < L; ++t) {
-            a.t0 = t; a.init = t == 0;
-            LAUNCH_TRY(h, launch_sgan_decode(a, st));
-            if (t == L - 1) break;                                   // (the last step's pooled state is never read)
-            HIP_TRY(h, hipMemsetAsync(G.dPool.p, 0, sizeof(float) * rows * bp, st));
-            LAUNCH_TRY(h, launch_sgan_pool(img, G.dev.dpool, n_scenes, S, N, d_off, a.h, a.pos, G.dPool.as<float>(), st));
-            LAUNCH_TRY(h, launch_sgan_mlp(img, G.dev.dmlp, a.h, Hd, G.dPool.as<float>(), d.bottleneck_dim, bp, (int64_t)rows, a.h, Hd, st));
-        }
-    }
+    { int r = sgan_enqueue(h, n_scenes, N, S, G.dOff.as<int32_t>(), global_noise && nd > 0 ? G.dScene.as<int32_t>() : nullptr, d_obs,
+                           d_noise, d_out, st); if (r != FOT_OK) return r; }
     if (!(flags & FOT_OUT_DEVICE)) HIP_TRY(h, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     { int r = order_end(h, st); if (r != FOT_OK) return r; }
     HIP_TRY(h, hipStreamSynchronize(st));
+    return FOT_OK;
+}
+
+int fot_sgan_noise(fot_handle *h, uint64_t seed, int32_t kind, int32_t S, int32_t rows, int32_t noise_dim,
+                   const int32_t *row_slot, const int32_t *row_step, const int32_t *row_index, int32_t flags, void *out,
+                   void *stream)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (kind < 0 || kind >= FOT_NOISE_KINDS) return fail(h, FOT_ERR_INVALID, "fot_sgan_noise: kind");
+    if (flags & ~FOT_OUT_DEVICE) return fail(h, FOT_ERR_INVALID, "fot_sgan_noise: flags");
+    if (S < 1 || rows < 0 || noise_dim < 0) return fail(h, FOT_ERR_INVALID, "fot_sgan_noise: S < 1 / rows < 0 / noise_dim < 0");
+    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, "fot_sgan_noise: S > FOT_MAX_SAMPLES");
+    if (rows == 0 || noise_dim == 0) return FOT_OK;
+    if (!row_slot || !row_step || !row_index || !out) return fail(h, FOT_ERR_INVALID, "fot_sgan_noise: NULL table / out");
+    for (int r = 0; r < rows; ++r)
+        if (row_slot[r] < 0 || row_step[r] < 0 || row_index[r] < 0 || row_index[r] > 0xFFFF)
+            return fail(h, FOT_ERR_INVALID, "fot_sgan_noise: a negative table entry, or a row_index above 65535");
+    fot_handle::Sgan &G = h->sgan;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const size_t n_out = (size_t)S * (size_t)rows * (size_t)noise_dim;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                  // (the tables' block: nothing of an earlier call reads it)
+    HIP_TRY(h, G.hTab.ensure(sizeof(int32_t) * 3 * (size_t)rows));
+    uint32_t *d_out = (uint32_t *)out;
+    if (!(flags & FOT_OUT_DEVICE)) { HIP_TRY(h, G.dNoise.ensure(sizeof(uint32_t) * n_out)); d_out = (uint32_t *)G.dNoise.p; }
+    { int r = order_begin(h, st); if (r != FOT_OK) return r; }
+    int32_t *t = (int32_t *)G.hTab.p;
+    std::memcpy(t, row_slot, sizeof(int32_t) * (size_t)rows);
+    std::memcpy(t + rows, row_step, sizeof(int32_t) * (size_t)rows);
+    std::memcpy(t + 2 * (size_t)rows, row_index, sizeof(int32_t) * (size_t)rows);
+    SgNoise a{};
+    a.seed = seed; a.kind = kind; a.S = S; a.rows = rows; a.nd = noise_dim; a.n_blk = (noise_dim + 3) / 4;
+    a.slot = t; a.step = t + rows; a.index = t + 2 * (size_t)rows; a.out = d_out;
+    LAUNCH_TRY(h, launch_sgan_noise(a, st));
+    if (!(flags & FOT_OUT_DEVICE)) HIP_TRY(h, hipMemcpyAsync(out, d_out, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, st));
+    { int r = order_end(h, st); if (r != FOT_OK) return r; }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return FOT_OK;
+}
+
+int fot_loop_set_sampler(fot_handle *h, int32_t S, uint64_t seed, int32_t kind)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopState &L = h->loop;
+    LoopReplay &R = L.replay;
+    fot_handle::Sgan &G = h->sgan;
+    if (!R.set) return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: fot_loop_set_replay comes first");
+    if (!G.loaded) return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: no model loaded (fot_sgan_load)");
+    const int n = R.cfg.n_slots;
+    bool begun = R.clock.frame != R.cfg.warmup_frames;
+    for (int e = 0; e < n; ++e) begun = begun || R.steps[(size_t)e] != 0;
+    if (begun) return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: the run has begun (set it between fot_loop_set_replay and the first step)");
+    if (S < 1) return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: S < 1");
+    if (kind != FOT_NOISE_GAUSSIAN && kind != FOT_NOISE_UNIFORM_SYM)
+        return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: kind is FOT_NOISE_GAUSSIAN or FOT_NOISE_UNIFORM_SYM");
+    const fot_sgan_desc &d = G.desc;
+    if (d.obs_len != R.cfg.obs_len || d.pred_len != R.cfg.pred_len)
+        return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: the model's obs_len / pred_len differ from the replay's");
+    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_sampler: S > FOT_MAX_SAMPLES");
+    for (int e = 0; e < n; ++e)
+        if (R.ped_off[(size_t)e + 1] - R.ped_off[(size_t)e] > FOT_SGAN_MAX_PEDS)
+            return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_sampler: a slot of more than FOT_SGAN_MAX_PEDS pedestrians");
+    if (L.ep.scenarios) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_sampler: a scenario loop plans against no distribution");
+    if (R.sum.on) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_sampler: summaries are enabled (their prediction-error ring reads the constant-velocity tensor)");
+    // --- accepted: everything a step needs is allocated here, so that no block grows (and moves) inside a run
+    LoopSampler &M = R.smp;
+    const size_t N = std::max<size_t>((size_t)R.n_cols, 1), rows = (size_t)S * N, ns = (size_t)std::max(n, 1);
+    const int bp = sg_pooled(d) ? G.dev.pool.b_pad : 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    M.on = false;
+    HIP_TRY(h, M.dWin.ensure(sizeof(float) * 2 * (size_t)d.obs_len * N));
+    HIP_TRY(h, M.dNoise.ensure(sizeof(float) * (size_t)S * std::max(N, ns) * (size_t)std::max(d.noise_dim, 1)));
+    HIP_TRY(h, M.dRaw.ensure(sizeof(float) * 2 * (size_t)S * (size_t)d.pred_len * N));
+    HIP_TRY(h, M.hTab.ensure(sizeof(int32_t) * 3 * (N + ns)));
+    HIP_TRY(h, L.dDyn.ensure(sizeof(double) * 2 * rows * (size_t)(R.n_dense + 1)));
+    HIP_TRY(h, G.dHenc.ensure(sizeof(float) * N * (size_t)d.encoder_h_dim));
+    if (bp > 0) HIP_TRY(h, G.dPool.ensure(sizeof(float) * (sg_pool_steps(d) ? rows : N) * (size_t)bp));
+    if (sg_has_context(d)) HIP_TRY(h, G.dCtx.ensure(sizeof(float) * N * (size_t)std::max(d.decoder_h_dim - d.noise_dim, 1)));
+    if (sg_pool_steps(d)) {
+        HIP_TRY(h, G.dH.ensure(sizeof(float) * rows * (size_t)d.decoder_h_dim));
+        HIP_TRY(h, G.dC.ensure(sizeof(float) * rows * (size_t)d.decoder_h_dim));
+        HIP_TRY(h, G.dXY.ensure(sizeof(float) * rows * 6));
+    }
+    M.S = S; M.seed = seed; M.kind = kind;
+    M.on = true;
     return FOT_OK;
 }
 

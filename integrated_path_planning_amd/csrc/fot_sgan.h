@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "fot_noise.hpp"
 #include "fot_sgan.hpp"
 
 namespace fot {
@@ -23,6 +24,32 @@ struct SgDecode {
     float *out;                              // [S][pred_len][N][2]
 };
 
+// fot_sgan_noise: out[s][r][d] (32-bit words: float32, or the raw uint32 of NOISE_RAW), n_blk = ceil(nd / 4) blocks per row;
+// row r is index[r] of slot[r] at that slot's step[r] (tables: pinned host memory or HBM)
+struct SgNoise {
+    uint64_t seed;
+    int32_t kind, S, rows, nd, n_blk, _pad;
+    const int32_t *slot, *step, *index;      // [rows]
+    uint32_t *out;                           // [S][rows][nd]
+};
+
+// The observer's window of a resident step: sample j is replay frame frames.f[j]; row q of the compacted frame belongs
+// to running episode ped_ep[q], which is slot ep_slot[.] with its first row at ep_ped0[.].
+struct SgWindowFrames {
+    int32_t f[FOT_SGAN_MAX_OBS_LEN];
+};
+struct SgWindow {
+    const double *pos;                       // the recording [n_frames_max][n_cols][2]
+    const int32_t *slot_ped0, *slot_frames;  // per slot: first column, recorded frames
+    const int32_t *ped_ep, *ep_ped0;         // HBM (FrameDev)
+    const int32_t *ep_slot;                  // pinned host memory (FrameStage)
+    int32_t n_cols, rows, obs_len, _pad;
+    SgWindowFrames frames;
+    float *out;                              // [obs_len][rows][2]
+};
+
+int launch_sgan_noise(const SgNoise &a, hipStream_t st);
+int launch_sgan_window(const SgWindow &a, hipStream_t st);
 int launch_sgan_encode(const float *img, const SgDevLstm &l, int E, int H, int obs_len, int N, const float *obs, float *henc,
                        hipStream_t st);
 // h [S][N][p.h_dim], pos [S][N][2] -> out [S][N][p.b_pad], which the caller has zeroed

@@ -6,6 +6,8 @@
 //   k_sgan_mlp      4 rows per workgroup through a two-layer MLP, input and middle layer in LDS
 //   k_sgan_decode   16 (sample, pedestrian) rows per workgroup: all pred_len steps in one launch, or -- with pooling at
 //                   every step -- one step per launch, the state in HBM between the launches
+//   k_sgan_noise    fot_sgan_noise: one thread per (sample, row, block of four noise dimensions), fot_noise.hpp's Philox
+//   k_sgan_window   the resident loop's observer window [obs_len][rows][2] float32 out of the recording in HBM
 // A thread owns an output element and adds its terms in index order; several rows share one read of a weight.  Plain
 // float32 VALU: the f32-input MFMA forms of gfx950 run at the vector rate.
 #include <hip/hip_runtime.h>
@@ -310,6 +312,37 @@ __global__ __launch_bounds__(SG_THREADS) void k_sgan_mlp(const float *__restrict
     }
 }
 
+// One thread per (sample s, row r, block b): the numbers of dimensions 4 b .. 4 b + 3 of row r of sample s, a function of
+// (seed, slot[r], step[r], index[r], s, b) alone -- no atomics, nothing of the launch shape.  The tables lie in pinned
+// host memory or HBM.
+__global__ __launch_bounds__(SG_THREADS) void k_sgan_noise(SgNoise a)
+{
+    const int64_t t = (int64_t)blockIdx.x * SG_THREADS + threadIdx.x;
+    const int64_t per_s = (int64_t)a.rows * a.n_blk;
+    if (t >= per_s * a.S) return;
+    const int s = (int)(t / per_s), r = (int)((t - s * per_s) / a.n_blk), b = (int)(t % a.n_blk);
+    uint32_t v[4];
+    noise_values(noise_block(a.seed, a.slot[r], a.step[r], a.index[r], s, b), a.kind, v);
+    uint32_t *dst = a.out + ((int64_t)s * a.rows + r) * a.nd + 4 * b;
+    for (int j = 0; j < 4; ++j)
+        if (4 * b + j < a.nd) dst[j] = v[j];
+}
+
+// One thread per (window sample j, frame row q): the position of the row's pedestrian at replay frame frames[j], clamped
+// to its slot's own recording and rounded to float32 as the observer hands it over (observer.py:134).
+__global__ __launch_bounds__(SG_THREADS) void k_sgan_window(SgWindow a)
+{
+    const int64_t t = (int64_t)blockIdx.x * SG_THREADS + threadIdx.x;
+    if (t >= (int64_t)a.obs_len * a.rows) return;
+    const int j = (int)(t / a.rows), q = (int)(t % a.rows);
+    const int i = a.ped_ep[q], slot = a.ep_slot[i], p = q - a.ep_ped0[i];
+    const int last_row = a.slot_frames[slot] - 1;
+    const int row = min(max(a.frames.f[j], 0), last_row);
+    const double2 v = ((const double2 *)a.pos)[(int64_t)row * a.n_cols + a.slot_ped0[slot] + p];
+    float2 w; w.x = (float)v.x; w.y = (float)v.y;
+    ((float2 *)a.out)[t] = w;
+}
+
 }  // namespace
 
 #define FOT_SG_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
@@ -346,6 +379,24 @@ int launch_sgan_decode(const SgDecode &a, hipStream_t st)
     const int64_t total = (int64_t)a.S * a.N;
     if (total <= 0 || a.n_steps <= 0) return 0;
     k_sgan_decode<<<(unsigned)((total + SG_RT - 1) / SG_RT), SG_THREADS, 0, st>>>(a);
+    FOT_SG_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_sgan_noise(const SgNoise &a, hipStream_t st)
+{
+    const int64_t total = (int64_t)a.S * a.rows * a.n_blk;
+    if (total <= 0) return 0;
+    k_sgan_noise<<<(unsigned)((total + SG_THREADS - 1) / SG_THREADS), SG_THREADS, 0, st>>>(a);
+    FOT_SG_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_sgan_window(const SgWindow &a, hipStream_t st)
+{
+    const int64_t total = (int64_t)a.obs_len * a.rows;
+    if (total <= 0) return 0;
+    k_sgan_window<<<(unsigned)((total + SG_THREADS - 1) / SG_THREADS), SG_THREADS, 0, st>>>(a);
     FOT_SG_LAUNCH_CHECK();
     return 0;
 }

@@ -498,7 +498,7 @@ class BatchPlanner:
         """``fot_loop_set_replay``: hands the recording of every episode slot of ``loop_begin`` to the library, which
         keeps it in HBM and runs the warm-up.  positions / velocities [n_frames_max, sum P, 2] (slot e owns columns
         ``ped_off[e]:ped_off[e + 1]`` and ``n_frames[e]`` recorded frames, its last one held afterwards); rp: the
-        predictor's ``ResampleParams``.  Constant-velocity predictor only."""
+        predictor's ``ResampleParams``.  Constant-velocity predictor unless ``loop_set_sampler`` follows."""
         off = np.ascontiguousarray(ped_off, dtype=np.int32)
         nf = np.ascontiguousarray(n_frames, dtype=np.int32)
         pos = np.ascontiguousarray(positions, dtype=np.float64)
@@ -554,6 +554,35 @@ class BatchPlanner:
         return o
 
     LOOP_SUMMARY_DT = np.dtype(_abi.LoopSummary)
+
+    def loop_set_sampler(self, num_samples: int, seed: int, kind: int = _abi.NOISE_GAUSSIAN) -> None:
+        """``fot_loop_set_sampler``: the resident loop predicts with the model of ``fot_sgan_load`` and the library's own
+        counter-based noise (between ``loop_set_replay`` and the first ``loop_run``)."""
+        _abi.check(self._h, self._lib.fot_loop_set_sampler(self._h, int(num_samples), int(seed) & 0xFFFFFFFFFFFFFFFF, int(kind)))
+
+    def sgan_noise(self, seed: int, kind: int, num_samples: int, noise_dim: int, row_slot, row_step, row_index, out=None,
+                   stream: Optional[int] = None):
+        """``fot_sgan_noise``: the counter-based noise [S, rows, noise_dim] of the rows (slot, that slot's step count, index
+        within the slot).  out: None -- a new NumPy array (uint32 for ``NOISE_RAW``, float32 otherwise); a NumPy array
+        of that shape; or a ``torch`` device tensor, written where it lies on ``stream``."""
+        slot, step, idx = (np.ascontiguousarray(v, dtype=np.int32) for v in (row_slot, row_step, row_index))
+        rows = len(slot)
+        if len(step) != rows or len(idx) != rows:
+            raise ValueError("sgan_noise: one slot, step and index per row")
+        shape = (int(num_samples), rows, int(noise_dim))
+        if out is None:
+            out = np.zeros(shape, dtype=np.uint32 if kind == _abi.NOISE_RAW else np.float32)
+        on_device = hasattr(out, "data_ptr")
+        if tuple(out.shape) != shape or (on_device and not out.is_contiguous()) or (not on_device and not out.flags.c_contiguous):
+            raise ValueError(f"sgan_noise: out is a contiguous [S, rows, noise_dim] = {shape}")
+        if out.element_size() != 4 if on_device else out.dtype.itemsize != 4:
+            raise ValueError("sgan_noise: 32-bit elements")
+        ptr = out.data_ptr() if on_device else out.ctypes.data
+        _abi.check(self._h, self._lib.fot_sgan_noise(
+            self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(kind), shape[0], rows, shape[2], slot.ctypes.data, step.ctypes.data,
+            idx.ctypes.data, _abi.OUT_DEVICE if on_device else 0, C.c_void_p(ptr) if ptr else None,
+            C.c_void_p(stream) if stream else None))
+        return out
 
     def loop_summary_enable(self, on: bool = True, num_samples: int = 1) -> None:
         """``fot_loop_summary_enable``: the resident loop accumulates every slot's episode summary while it runs (between

@@ -271,25 +271,47 @@ class SganSampler:
     whole window).  The noise is drawn on the device from the sampler's own ``torch.Generator`` (``noise_type`` 'gaussian':
     ``randn``; 'uniform': ``rand`` mapped to [-1, 1), models.py:27-32) or supplied.  ``noise_type`` is the loaded weights' own
     (the checkpoint's, as the reference draws: models.py:393) unless the constructor is given one; ``last_noise`` /
-    ``last_obs`` / ``last_ped_off`` keep what the most recent call used."""
+    ``last_obs`` / ``last_ped_off`` keep what the most recent call used.
+
+    counter_seed: the counter mode.  The noise is then the library's own (``fot_sgan_noise``: Philox4x32-10 keyed by the
+    seed, counted by slot, that slot's step, pedestrian, sample and dimension), not torch's stream -- a row's numbers do
+    not depend on which other episodes still run, and ``BatchedClosedLoop(..., resident=True)`` draws the same inside
+    the library.  ``sample`` then needs the rows' ``slots`` and ``steps`` (a loop passes them).  The numbers differ from
+    ``torch.randn``'s: seeds are not comparable with the reference's runs.
+    engine None: the sampler joins the engine of the loop it is handed to (``bind``)."""
     needs_history = True
 
-    def __init__(self, engine: BatchPlanner, weights: SganWeights, num_samples: int, seed: Optional[int] = None,
-                 noise_type: Optional[str] = None):
-        import torch
+    def __init__(self, engine: Optional[BatchPlanner], weights: SganWeights, num_samples: int, seed: Optional[int] = None,
+                 noise_type: Optional[str] = None, counter_seed: Optional[int] = None):
         if noise_type is not None and noise_type not in _NOISE_TYPES:
             raise ValueError(f'Unrecognized noise type "{noise_type}"')
         if not 1 <= int(num_samples) <= _abi.MAX_SAMPLES:
             raise ValueError(f"SganSampler: 1 <= num_samples <= {_abi.MAX_SAMPLES}")
-        self.engine, self.weights, self.num_samples, self._noise_type = engine, weights, int(num_samples), noise_type
+        self.engine, self.weights, self.num_samples, self._noise_type = None, weights, int(num_samples), noise_type
+        self.counter_seed = None if counter_seed is None else int(counter_seed) & 0xFFFFFFFFFFFFFFFF
+        self._seed = seed
         self._lib = _abi.lib()
-        self.load(weights)
+        self.device = self.generator = None
+        self.last_noise = self.last_obs = self.last_ped_off = None
+        if self._noise_type is None and weights.noise_type not in _NOISE_TYPES:
+            raise ValueError(f'Unrecognized noise type "{weights.noise_type}"')
+        if engine is not None:
+            self.bind(engine)
+
+    def bind(self, engine: BatchPlanner) -> None:
+        """Join ``engine``: its handle gets the model, its device the generator."""
+        import torch
+        if self.engine is not None and self.engine is not engine:
+            raise ValueError("SganSampler: the sampler already belongs to another engine")
+        if self.engine is engine:
+            return
+        self.engine = engine
+        self.load(self.weights)
         dev = int(getattr(engine, "device", -1))                    # (fot_create's device < 0: the current one)
         self.device = torch.device("cuda", torch.cuda.current_device() if dev < 0 else dev)
         self.generator = torch.Generator(device=self.device)
-        if seed is not None:
-            self.generator.manual_seed(int(seed))
-        self.last_noise = self.last_obs = self.last_ped_off = None
+        if self._seed is not None:
+            self.generator.manual_seed(int(self._seed))
 
     @property
     def noise_type(self) -> str:
@@ -312,8 +334,36 @@ class SganSampler:
             return torch.randn(shape, device=self.device, dtype=torch.float32, generator=self.generator)
         return torch.rand(shape, device=self.device, dtype=torch.float32, generator=self.generator).sub_(0.5).mul_(2.0)
 
-    def sample(self, obs, ped_off, noise=None):
-        """obs [obs_len, sum P, 2] absolute positions (NumPy, or a float32 torch device tensor); ped_off [n_scenes + 1]."""
+    @property
+    def noise_kind(self) -> int:
+        """The ``fot_sgan_noise`` kind that stands for ``noise_type``."""
+        return _abi.NOISE_GAUSSIAN if self.noise_type == "gaussian" else _abi.NOISE_UNIFORM_SYM
+
+    def counter_noise(self, slots, steps, counts, kind: Optional[int] = None):
+        """The counter mode's noise of the scenes ``slots`` (pedestrian counts ``counts``) at their step counts ``steps``,
+        from ``fot_sgan_noise`` as a device tensor [S, rows, noise_dim] -- exactly what a resident loop with this seed
+        uses for those slots at those steps, whatever else runs beside them."""
+        import torch
+        if self.counter_seed is None:
+            raise ValueError("SganSampler: counter_noise needs counter_seed")
+        d = self.weights.desc
+        slots, steps, counts = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (slots, steps, counts))
+        if not len(slots) == len(steps) == len(counts):
+            raise ValueError("SganSampler: one step and one pedestrian count per slot")
+        if d.noise_mix_type == _abi.SGAN_NOISE_GLOBAL:
+            row_slot, row_step, row_idx = slots, steps, np.zeros(len(slots), np.int64)
+        else:
+            row_slot, row_step = np.repeat(slots, counts), np.repeat(steps, counts)
+            row_idx = np.concatenate([np.arange(c) for c in counts]) if len(counts) else np.zeros(0, np.int64)
+        dtype = torch.int32 if kind == _abi.NOISE_RAW else torch.float32    # (raw words: their bits, as int32)
+        out = torch.empty((self.num_samples, len(row_slot), d.noise_dim), device=self.device, dtype=dtype)
+        torch.cuda.current_stream(self.device).synchronize()        # (the library writes it on its own stream)
+        return self.engine.sgan_noise(self.counter_seed, self.noise_kind if kind is None else kind, self.num_samples,
+                                      d.noise_dim, row_slot, row_step, row_idx, out=out)
+
+    def sample(self, obs, ped_off, noise=None, slots=None, steps=None):
+        """obs [obs_len, sum P, 2] absolute positions (NumPy, or a float32 torch device tensor); ped_off [n_scenes + 1];
+        slots / steps (counter mode, without ``noise``): the slot and step count of every scene."""
         import torch
         d = self.weights.desc
         off = np.ascontiguousarray(ped_off, dtype=np.int32)
@@ -324,7 +374,11 @@ class SganSampler:
             obs_t = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32)).to(self.device)
         if tuple(obs_t.shape) != (d.obs_len, n, 2):
             raise ValueError(f"SganSampler: obs is [obs_len = {d.obs_len}, sum P = {n}, 2], got {tuple(obs_t.shape)}")
-        if noise is None:
+        if noise is None and self.counter_seed is not None:
+            if slots is None or steps is None:
+                raise ValueError("SganSampler: the counter mode needs every scene's slot and step count (slots, steps)")
+            noise_t = self.counter_noise(slots, steps, np.diff(off))
+        elif noise is None:
             noise_t = self.draw_noise(n, n_scenes)
         else:
             noise_t = torch.as_tensor(noise, dtype=torch.float32).to(self.device).contiguous()
