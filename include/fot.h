@@ -757,6 +757,44 @@ int fot_sgan_noise(fot_handle *h, uint64_t seed, int32_t kind, int32_t S, int32_
                    void *stream);
 int fot_loop_set_sampler(fot_handle *h, int32_t S, uint64_t seed, int32_t kind);
 
+/* ---- prediction scores and episode summaries of a resident sampler loop ------------------------------------------------
+ * fot_loop_scores_enable(h, on): between fot_loop_set_sampler and the first step (on = 0 switches it off again).  Every
+ * sampled lock step then, on the loop's stream behind the resample and ahead of the safety and plan launches and without
+ * a synchronisation of its own,
+ *   - chooses every running episode's representative sample (predict_single_best, trajectory_predictor.py:346-351): over
+ *     the episode's own pedestrians and the n_dense dense samples (the prepended current position is not part of it)
+ *     dev[s] = sum_{p,k} |q[s][p][k] - mean_s q[.][p][k]|, the first minimum (S = 1: sample 0);
+ *   - writes that sample's error row into the prediction-error ring of fot_loop_summary_enable (planning_ade,
+ *     planning_fde, planning_eval_count: the reference evaluates them on predicted_trajectories, the representative sample);
+ *   - scores the whole distribution where it lies in HBM, one fot_pred_score record per running episode as
+ *     fot_loop_prediction_scores gives it (skip = 1, float64), against the resident recording: the truth of origin frame f
+ *     is row min(f + stride j, n_frames[slot] - 1), j = 1 .. pred_len, stride = round(sgan_dt / sim_dt).  The records land
+ *     in pinned memory and are folded per slot on the host once their horizon is complete: the record of a slot's step i
+ *     counts when the slot takes step i + stride pred_len (metrics.py:78), ade_scene n_peds, fde_scene n_peds, the agent
+ *     sums and log_lik_sum added in step order, the counts n_peds and nll_count beside them.
+ * Everything the mode needs is allocated here.  With stride pred_len - 1 >= n_dense no origin ever has a complete horizon
+ * and ade .. nll stay NaN / 0 (accepted, as the reference does).  A loop that does not enable the mode launches and
+ * allocates nothing of this, and its steps' outputs are the same bytes with the mode on and off.
+ * Refusals (FOT_ERR_INVALID, nothing changed): no replay set; no sampler set; after the first step; sgan_dt / sim_dt not
+ * an integer.  fot_loop_begin*, fot_loop_set_replay and fot_loop_set_sampler drop the mode, as they drop the sampler.
+ *
+ * fot_loop_score_summaries(h, n_slots, out): one fot_loop_summary per slot of the steps run so far; may be called between
+ * two fot_loop_run calls, the run goes on.  min_dist .. mean_accel, steps, termination, total_time: as fot_loop_summaries.
+ * ade, fde (scene-level best-of-N), ade_per_agent, fde_per_agent, ade_eval_count, nll, nll_eval_count, pred_samples (S if
+ * an origin counted, else 0): the fold above; records whose horizon is not complete yet do not count.  planning_ade,
+ * planning_fde, planning_eval_count: the ring, with the truncated horizon E = min(n_dense, L - (i + 1)).
+ * FOT_ERR_INVALID: scores not enabled; n_slots differs from the loop's; out is NULL.
+ *
+ * fot_loop_last_best_sample(h, n_slots, out): out[slot] = the representative sample the most recent lock step chose for
+ * the slot; -1: the slot did not run, the step did not predict (observer not ready), or the slot has no pedestrians.
+ * Together with seed, slot and step it rebuilds a step's predicted_trajectories without redoing the selection.
+ * FOT_ERR_INVALID as above.
+ * The three entries are additions: no structure, capacity or existing entry changes, FOT_ABI_VERSION and the words of
+ * fot_abi_info stay as they are; a binding that needs them looks the symbols up. */
+int fot_loop_scores_enable(fot_handle *h, int32_t on);
+int fot_loop_score_summaries(fot_handle *h, int32_t n_slots, fot_loop_summary *out);
+int fot_loop_last_best_sample(fot_handle *h, int32_t n_slots, int32_t *out);
+
 /* Host utility (no GPU): the first kmax samples of the 15 path arrays of records[index[i]], i < n, as one dense block
  * out[15][n][kmax] in fot_result array order (t .. c) -- what a history keeps of a step's records. */
 int fot_gather_paths(const fot_result *records, int32_t n, const int32_t *index, int32_t kmax, double *out);

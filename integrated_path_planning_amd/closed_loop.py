@@ -475,7 +475,9 @@ class BatchedClosedLoop:
         them, a few hundred bytes per episode whatever its length.  ``pred_samples`` reports the configuration's
         ``num_samples`` (trajectory_predictor's sample count, integrated_simulator.py:333: the constant-velocity
         predictor hands the metrics that many identical samples).
-        prediction_scores (stepwise loops with a sample_source): every lock step the library scores the step's sample
+        prediction_scores (stepwise loops with a sample_source, and resident loops with their own sampler -- there the
+        records are formed and folded inside the library, fot_loop_scores_enable, and ``aggregate_metrics()`` /
+        ``save_summaries()`` give the whole summary row): every lock step the library scores the step's sample
         distribution of every running episode against the replayed tracks -- best-of-N ADE / FDE, scene level and per
         agent, and the KDE log-likelihood (``fot_loop_prediction_scores`` on the tensor in HBM with ``device_samples``,
         ``fot_prediction_scores`` on the host distribution otherwise, the "planned on the best sample" mode included);
@@ -491,18 +493,21 @@ class BatchedClosedLoop:
         if self._summaries and not self._resident:
             raise ValueError("summaries=True needs resident=True (the summary is accumulated by the resident loop)")
         self._pred_scores = bool(prediction_scores)
-        if self._pred_scores and self._resident:
-            raise ValueError("prediction_scores=True scores the stepwise loop's distributions (resident=False)")
-        if self._pred_scores and sample_source is None:
-            raise ValueError("prediction_scores=True needs a multi-sample predictor (sample_source)")
-        if self._pred_scores and engine is not None and not hasattr(engine, "prediction_scores"):
-            raise ValueError("prediction_scores=True needs the library's own engine (fot_prediction_scores)")
         # a resident loop's sample source: prediction.SganSampler in counter mode, run inside the library
         # (fot_loop_set_sampler) on the loop's own engine, planning against the whole distribution
         self._resident_sampler = bool(self._resident and sample_source is not None and device_samples
                                       and getattr(sample_source, "counter_seed", None) is not None
                                       and hasattr(sample_source, "bind") and engine is None
                                       and getattr(sample_source, "engine", None) is None)
+        if self._pred_scores and self._resident and not self._resident_sampler:
+            raise ValueError("prediction_scores=True scores the stepwise loop's distributions (resident=False), or those "
+                             "of a resident loop's own sampler (a counter-seeded sample_source with device_samples=True)")
+        # a resident sampler loop scored inside the library (fot_loop_scores_enable): the summary with it
+        self._resident_scores = bool(self._pred_scores and self._resident_sampler)
+        if self._pred_scores and sample_source is None:
+            raise ValueError("prediction_scores=True needs a multi-sample predictor (sample_source)")
+        if self._pred_scores and engine is not None and not hasattr(engine, "prediction_scores"):
+            raise ValueError("prediction_scores=True needs the library's own engine (fot_prediction_scores)")
         if self._resident and ((sample_source is not None and not self._resident_sampler) or engine is not None
                                or resampler is not None or fused not in (None, True)):
             raise ValueError("resident=True needs the constant-velocity predictor on the library's own engine "
@@ -659,6 +664,8 @@ class BatchedClosedLoop:
                 self.engine.loop_summary_enable(True, int(getattr(c, "num_samples", 1)))
             if self._resident_sampler:
                 self.engine.loop_set_sampler(sample_source.num_samples, sample_source.counter_seed, sample_source.noise_kind)
+            if self._resident_scores:
+                self.engine.loop_scores_enable(True)
 
     def close(self) -> None:
         """Release the libfot handle (streams, workspace) now rather than at garbage collection."""
@@ -840,6 +847,10 @@ class BatchedClosedLoop:
         reference folds them.  Needs ``prediction_scores=True``; may be called between two steps."""
         if not self._pred_scores:
             raise ValueError("prediction_metrics() needs BatchedClosedLoop(..., prediction_scores=True)")
+        if self._resident_scores:                                     # folded inside the library, record by record
+            keys = ("ade", "fde", "ade_per_agent", "fde_per_agent", "pred_samples", "ade_eval_count", "nll", "nll_eval_count")
+            return [{k: (int(r[k]) if k in self.SUMMARY_INT_KEYS else float(r[k])) for k in keys}
+                    for r in self.engine.loop_score_summaries()]
         n = len(self.episodes)
         horizon = self._score_stride * int(self.resampler.pred_len)
         tot = np.zeros((n, 5))
@@ -1273,11 +1284,13 @@ class BatchedClosedLoop:
     def aggregate_metrics(self) -> List[Dict[str, Any]]:
         """One dictionary per episode: the keys and value types of the reference's ``calculate_aggregate_metrics`` over the
         steps run so far (ints for the counts, ``inf`` / NaN where the reference has them) plus ``termination_reason``,
-        ``steps``, ``total_time`` and ``collision``.  Accumulated on the device by the resident loop (``summaries=True``):
+        ``steps``, ``total_time`` and ``collision``.  Accumulated on the device by the resident loop (``summaries=True``; a
+        resident sampler loop: ``prediction_scores=True``, best-of-N and KDE keys over the whole distributions):
         no step record is read and no prediction recomputed.  May be called between two ``run()`` calls."""
-        if not self._resident or not self._summaries:
-            raise ValueError("aggregate_metrics() needs BatchedClosedLoop(..., resident=True, summaries=True)")
-        rec = self.engine.loop_summaries()
+        if not self._resident or not (self._summaries or self._resident_scores):
+            raise ValueError("aggregate_metrics() needs BatchedClosedLoop(..., resident=True, summaries=True), or a resident "
+                             "sampler loop with prediction_scores=True")
+        rec = self.engine.loop_score_summaries() if self._resident_scores else self.engine.loop_summaries()
         out = []
         for e in range(len(self.episodes)):
             r = rec[e]

@@ -20,6 +20,7 @@
 #include "fot_math.hpp"
 #include "fot_replay.hpp"
 #include "fot_summary.hpp"
+#include "fot_loopscore.hpp"
 #include "fot_setup.hpp"
 #include "fot_sgan.h"
 
@@ -157,6 +158,21 @@ struct LoopSampler {
     void release() { dWin.release(); dNoise.release(); dRaw.release(); hTab.release(); }
 };
 
+// fot_loop_scores_enable: a resident sampler loop scores its predictor (fot_loopscore.hpp).  The representative sample's
+// error rows go through LoopSummaryAcc's ring (armed, but not `on`: fot_loop_summaries stays refused); the per-origin
+// records of a step land in hRec and wait in each slot's ring of H = stride * pred_len records for their horizon.
+struct LoopScores {
+    bool on = false;
+    int stride = 0, H = 0;
+    bool std_ok = false;                         // stride * pred_len - 1 < n_dense: the standard metrics apply at all
+    DevBuf dBest, dDev, dTruth;                  // int32[slots] | [slots][FOT_MAX_SAMPLES] deviation sums | [cols][pred_len][2]
+    PinnedBuf hBest, hDesc, hRec;                // int32[slots] | PredOriginDev[slots] | fot_pred_score[slots] of the step
+    std::vector<PredScoreTerms> ring;            // [slots][H]
+    std::vector<ScoreFold> fold;                 // [slots]
+    std::vector<int32_t> last_best;              // [slots] of the most recent lock step
+    void release() { dBest.release(); dDev.release(); dTruth.release(); hBest.release(); hDesc.release(); hRec.release(); }
+};
+
 // fot_loop_set_replay / fot_loop_run: the recording (host copy for the prepend test, HBM copy for the frame kernel), the
 // replay clock and what a resident step keeps on the device
 struct LoopReplay {
@@ -175,9 +191,10 @@ struct LoopReplay {
     int32_t seq = 0;                             // value the completion words are raised to next
     LoopSummaryAcc sum;
     LoopSampler smp;
+    LoopScores sc;
     void release()
     {
-        sum.release(); smp.release();
+        sum.release(); smp.release(); sc.release();
         dPos.release(); dVel.release(); dTab.release(); dFrame.release(); dRec.release(); dHist.release();
         hStage.release(); hDigest.release(); hHistTab.release(); hWord.release();
     }
@@ -1763,6 +1780,7 @@ int fot_loop_begin(fot_handle *h, int32_t n_episodes, const fot_loop_config *cfg
     h->loop.replay.set = false;                                  // (a new loop: the handle's clock, if it had one, is gone)
     h->loop.replay.sum.on = false;                               // ... and the summaries' accumulators with it
     h->loop.replay.smp.on = false;                               // ... and the sampler
+    h->loop.replay.sc.on = false;                                // ... and its scores
     return FOT_OK;
 }
 
@@ -1820,6 +1838,7 @@ int fot_loop_begin_scenarios(fot_handle *h, int32_t n_episodes, int32_t n_cfg, c
     L.replay.set = false;
     L.replay.sum.on = false;
     L.replay.smp.on = false;
+    L.replay.sc.on = false;
     return FOT_OK;
 }
 
@@ -2118,10 +2137,25 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         L.dyn_ptr = L.dDyn.p;
         LAUNCH_TRY(h, launch_predict_cv_frame(C.rp.sgan_dt, C.rp.sim_dt, stale, rows, R.n_dense, fd, L.dDyn.as<double>(), st));
     }
-    if (R.sum.on)                                                // this step's row of every running slot's ring
+    const bool scored = R.sc.on && sampled;                      // the step's distributions are scored where they lie
+    if (scored)                                                  // every episode's representative sample
+        LAUNCH_TRY(h, launch_loop_best_sample(s_slot, fd, L.dDyn.as<double>(), n, R.smp.S, R.n_dense, R.sc.dDev.as<double>(),
+                                              R.sc.dBest.as<int32_t>(), (int32_t *)R.sc.hBest.p, st));
+    if (R.sum.on || R.sc.on)                                     // this step's row of every running slot's ring
         LAUNCH_TRY(h, launch_loop_pred_error(rv, s_slot, fd, L.dDyn.as<double>(), n, ready && rows > 0 ? 1 : 0, f_cur,
                                              R.steps[(size_t)sel[0]], R.sum.shape, R.sum.dRing.as<double>(),
-                                             R.sum.dRingP.as<int32_t>(), R.sum.dTotals.as<SummaryTotals>(), st));
+                                             R.sum.dRingP.as<int32_t>(), R.sum.dTotals.as<SummaryTotals>(), st,
+                                             scored ? R.sc.dBest.as<int32_t>() : nullptr));
+    if (scored && R.sc.std_ok) {                                 // one origin per running episode, the truth from the recording
+        PredOriginDev *pd = (PredOriginDev *)R.sc.hDesc.p;
+        const double scott = ps_scott(R.smp.S);
+        for (int i = 0; i < n; ++i)
+            pd[i] = PredOriginDev{ L.blk_off[(size_t)i], (int64_t)L.ped_off[(size_t)i], scott, R.smp.S,
+                                   L.ped_off[(size_t)i + 1] - L.ped_off[(size_t)i], R.n_dense + 1, 0, 1, 0 };
+        LAUNCH_TRY(h, launch_loop_score_truth(rv, s_slot, fd, rows, f_cur, R.sc.stride, C.pred_len, R.sc.dTruth.as<double>(), st));
+        LAUNCH_TRY(h, launch_pred_scores(pd, n, L.dDyn.p, FOT_F64, R.sc.stride, C.pred_len, R.sc.dTruth.as<double>(),
+                                         (fot_pred_score *)R.sc.hRec.p, st));
+    }
     LAUNCH_TRY(h, launch_safety(h->dP.as<DevParams>(), n, fd.ego, fd.ped0, fd.pos, fd.vel, L.ego_radius, L.ped_radius,
                                 h->sc[0].params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st,
                                 L.p_scen, L.dSafScen.as<SafetyScen>()));
@@ -2135,6 +2169,24 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     LAUNCH_TRY(h, launch_loop_digest(d_rec, n, dig, word, seq, st));
     { int rc = wait_word(h, word, seq, st); if (rc != FOT_OK) return rc; }
     std::memcpy(W.m.data(), L.hOut.p, sizeof(fot_safety) * (size_t)n);   // (k_safety ran ahead of the plan on this stream)
+    if (R.sc.on) {                                               // ... and so did the step's scores: into the slots' rings
+        LoopScores &Q = R.sc;
+        const fot_pred_score *rec = (const fot_pred_score *)Q.hRec.p;
+        const int32_t *best = (const int32_t *)Q.hBest.p;
+        std::fill(Q.last_best.begin(), Q.last_best.end(), -1);
+        for (int i = 0; i < n; ++i) {
+            const int e = sel[i];
+            PredScoreTerms t = ps_zero(R.smp.S);                 // (no prediction, or no horizon that could ever complete)
+            if (scored && Q.std_ok) {
+                const fot_pred_score &r = rec[i];
+                t.ade_scene = r.ade_scene; t.fde_scene = r.fde_scene; t.ade_agent_sum = r.ade_agent_sum;
+                t.fde_agent_sum = r.fde_agent_sum; t.log_lik_sum = r.log_lik_sum;
+                t.n_peds = r.n_peds; t.n_samples = r.n_samples; t.nll_count = r.nll_count; t.flags = r.flags;
+            }
+            score_ring_push(Q.fold[(size_t)e], Q.ring.data() + (size_t)e * (size_t)Q.H, Q.H, R.steps[(size_t)e], t);
+            if (scored && L.ped_off[(size_t)i + 1] > L.ped_off[(size_t)i]) Q.last_best[(size_t)e] = best[e];
+        }
+    }
     for (int i = 0; i < n; ++i) E.last_clearance[sel[i]] = W.m[i].clearance_ahead;
     step_escalations(E, sel.data(), n, dig, W);
     if (!W.more.empty()) {
@@ -2177,7 +2229,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         if (out->after) out->after[o] = after[i];
         if (out->s_now) out->s_now[o] = s_now;
         R.steps[e] += 1;
-        if (R.sum.on) {                                          // (calculate_aggregate_metrics, metrics.py:279-308)
+        if (R.sum.on || R.sc.on) {                               // (calculate_aggregate_metrics, metrics.py:279-308)
             LoopSummaryAcc &A = R.sum;
             const double aj = std::fabs(W.jerk[i]), aa = std::fabs(W.ego5n[5 * (size_t)i + 4]), ttc = after[i].ttc;
             A.min_dist[e] = std::fmin(A.min_dist[e], after[i].min_distance);
@@ -2193,6 +2245,8 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     }
     return FOT_OK;
 }
+
+int summary_arm(fot_handle *h, int num_samples, int stride);     // (below fot_loop_summary_enable)
 
 }  // namespace
 
@@ -2234,6 +2288,7 @@ int fot_loop_set_replay(fot_handle *h, const fot_loop_replay *rp)
     R.set = false;
     R.sum.on = false;                                            // (a new recording: summaries are enabled again, if wanted)
     R.smp.on = false;                                            // ... and so is a sampler
+    R.sc.on = false;                                             // ... and its scores
     const size_t rec_doubles = (size_t)rp->n_frames_max * cols * 2;
     const int max_lvl = E.max_lvl;
     const size_t n_rec = (size_t)std::max(n, 1) * (size_t)max_lvl;
@@ -2289,8 +2344,22 @@ int fot_loop_summary_enable(fot_handle *h, int32_t on, int32_t num_samples)
     if (num_samples < 1) return fail(h, FOT_ERR_INVALID, "fot_loop_summary_enable: num_samples < 1");
     const int stride = summary_stride(R.cfg.rp.sgan_dt, R.cfg.rp.sim_dt);
     if (stride < 1) return fail(h, FOT_ERR_INVALID, "fot_loop_summary_enable: sgan_dt must be a multiple of sim_dt");
-    // --- accepted: the ring and the totals start out zero (a row with count 0 contributes nothing)
-    const size_t ns = (size_t)std::max(n, 1), nd = (size_t)R.n_dense;
+    { int r = summary_arm(h, num_samples, stride); if (r != FOT_OK) return r; }
+    A.on = true;
+    return FOT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The prediction-error ring, its totals and the host's accumulators of a run that has not begun: allocated and zeroed
+// (a row with count 0 contributes nothing).  Leaves LoopSummaryAcc::on as it is.
+int summary_arm(fot_handle *h, int num_samples, int stride)
+{
+    LoopReplay &R = h->loop.replay;
+    LoopSummaryAcc &A = R.sum;
+    const size_t ns = (size_t)std::max(R.cfg.n_slots, 1), nd = (size_t)R.n_dense;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     HIP_TRY(h, A.dRing.ensure(sizeof(double) * ns * nd * nd));
@@ -2306,20 +2375,14 @@ int fot_loop_summary_enable(fot_handle *h, int32_t on, int32_t num_samples)
     A.min_dist.assign(ns, INFINITY); A.min_ttc.assign(ns, INFINITY);
     A.max_jerk.assign(ns, 0.0); A.sum_jerk.assign(ns, 0.0); A.sum_jerk2.assign(ns, 0.0);
     A.max_accel.assign(ns, 0.0); A.sum_accel.assign(ns, 0.0); A.collisions.assign(ns, 0);
-    A.on = true;
     return FOT_OK;
 }
 
-int fot_loop_summaries(fot_handle *h, int32_t n_slots, fot_loop_summary *out)
+// one record per slot from the ring, its totals and the host's accumulators (n_slots > 0, checked by the caller)
+int summaries_fill(fot_handle *h, int32_t n_slots, fot_loop_summary *out)
 {
-    if (!h) return FOT_ERR_INVALID;
     LoopReplay &R = h->loop.replay;
-    if (!R.set) return fail(h, FOT_ERR_INVALID, "fot_loop_summaries: fot_loop_set_replay comes first");
     LoopSummaryAcc &A = R.sum;
-    if (!A.on) return fail(h, FOT_ERR_INVALID, "fot_loop_summaries: summaries are not enabled (fot_loop_summary_enable)");
-    if (n_slots != R.cfg.n_slots) return fail(h, FOT_ERR_INVALID, "fot_loop_summaries: n_slots differs from the loop's");
-    if (n_slots > 0 && !out) return fail(h, FOT_ERR_INVALID, "fot_loop_summaries: out is NULL");
-    if (n_slots == 0) return FOT_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = h->stream;
     int32_t *steps = (int32_t *)A.hSteps.p;
@@ -2345,6 +2408,93 @@ int fot_loop_summaries(fot_handle *h, int32_t n_slots, fot_loop_summary *out)
         s.total_time = (double)L * dt;
         out[e] = s;
     }
+    return FOT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fot_loop_summaries(fot_handle *h, int32_t n_slots, fot_loop_summary *out)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopReplay &R = h->loop.replay;
+    if (!R.set) return fail(h, FOT_ERR_INVALID, "fot_loop_summaries: fot_loop_set_replay comes first");
+    if (!R.sum.on) return fail(h, FOT_ERR_INVALID, "fot_loop_summaries: summaries are not enabled (fot_loop_summary_enable)");
+    if (n_slots != R.cfg.n_slots) return fail(h, FOT_ERR_INVALID, "fot_loop_summaries: n_slots differs from the loop's");
+    if (n_slots > 0 && !out) return fail(h, FOT_ERR_INVALID, "fot_loop_summaries: out is NULL");
+    if (n_slots == 0) return FOT_OK;
+    return summaries_fill(h, n_slots, out);
+}
+
+int fot_loop_scores_enable(fot_handle *h, int32_t on)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopReplay &R = h->loop.replay;
+    if (!R.set) return fail(h, FOT_ERR_INVALID, "fot_loop_scores_enable: fot_loop_set_replay comes first");
+    if (!R.smp.on) return fail(h, FOT_ERR_INVALID, "fot_loop_scores_enable: no sampler is set (fot_loop_set_sampler comes first)");
+    const int n = R.cfg.n_slots;
+    bool begun = R.clock.frame != R.cfg.warmup_frames;
+    for (int e = 0; e < n; ++e) begun = begun || R.steps[(size_t)e] != 0;
+    if (begun) return fail(h, FOT_ERR_INVALID, "fot_loop_scores_enable: the run has begun (enable between fot_loop_set_sampler and the first step)");
+    LoopScores &Q = R.sc;
+    if (!on) { Q.on = false; return FOT_OK; }
+    const int stride = summary_stride(R.cfg.rp.sgan_dt, R.cfg.rp.sim_dt);
+    if (stride < 1) return fail(h, FOT_ERR_INVALID, "fot_loop_scores_enable: sgan_dt must be a multiple of sim_dt");
+    // --- accepted: everything the mode needs is allocated here
+    Q.on = false;
+    { int r = summary_arm(h, R.smp.S, stride); if (r != FOT_OK) return r; }
+    const size_t ns = (size_t)std::max(n, 1), cols = (size_t)std::max(R.n_cols, 1), E = (size_t)R.cfg.pred_len;
+    HIP_TRY(h, Q.dBest.ensure(sizeof(int32_t) * ns));
+    HIP_TRY(h, Q.dDev.ensure(sizeof(double) * ns * FOT_MAX_SAMPLES));
+    HIP_TRY(h, Q.dTruth.ensure(sizeof(double) * 2 * cols * E));
+    HIP_TRY(h, Q.hBest.ensure(sizeof(int32_t) * ns));
+    HIP_TRY(h, Q.hDesc.ensure(sizeof(PredOriginDev) * ns));
+    HIP_TRY(h, Q.hRec.ensure(sizeof(fot_pred_score) * ns));
+    HIP_TRY(h, hipMemsetAsync(Q.dBest.p, 0xFF, sizeof(int32_t) * ns, h->stream));
+    HIP_TRY(h, hipMemsetAsync(Q.dDev.p, 0, sizeof(double) * ns * FOT_MAX_SAMPLES, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    std::memset(Q.hBest.p, 0xFF, sizeof(int32_t) * ns);
+    std::memset(Q.hRec.p, 0, sizeof(fot_pred_score) * ns);
+    Q.stride = stride; Q.H = stride * R.cfg.pred_len;
+    Q.std_ok = ps_horizon_fits(stride, R.cfg.pred_len, R.n_dense + 1, 1);
+    Q.ring.assign(ns * (size_t)Q.H, ps_zero(R.smp.S));
+    Q.fold.assign(ns, score_fold_zero());
+    Q.last_best.assign(ns, -1);
+    Q.on = true;
+    return FOT_OK;
+}
+
+int fot_loop_score_summaries(fot_handle *h, int32_t n_slots, fot_loop_summary *out)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopReplay &R = h->loop.replay;
+    if (!R.set || !R.sc.on) return fail(h, FOT_ERR_INVALID, "fot_loop_score_summaries: scores are not enabled (fot_loop_scores_enable)");
+    if (n_slots != R.cfg.n_slots) return fail(h, FOT_ERR_INVALID, "fot_loop_score_summaries: n_slots differs from the loop's");
+    if (n_slots > 0 && !out) return fail(h, FOT_ERR_INVALID, "fot_loop_score_summaries: out is NULL");
+    if (n_slots == 0) return FOT_OK;
+    { int r = summaries_fill(h, n_slots, out); if (r != FOT_OK) return r; }
+    // the ring's standard-cadence totals are the representative sample's: the best-of-N and KDE keys are the fold's
+    for (int e = 0; e < n_slots; ++e) {
+        double m[5];
+        int32_t samples = 0;
+        const ScoreFold &F = R.sc.fold[(size_t)e];
+        score_fold_means(F, m, &samples);
+        fot_loop_summary &s = out[e];
+        s.ade = m[0]; s.fde = m[1]; s.ade_per_agent = m[2]; s.fde_per_agent = m[3]; s.nll = m[4];
+        s.ade_eval_count = (int32_t)F.count; s.nll_eval_count = (int32_t)F.nll_count; s.pred_samples = samples;
+    }
+    return FOT_OK;
+}
+
+int fot_loop_last_best_sample(fot_handle *h, int32_t n_slots, int32_t *out)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopReplay &R = h->loop.replay;
+    if (!R.set || !R.sc.on) return fail(h, FOT_ERR_INVALID, "fot_loop_last_best_sample: scores are not enabled (fot_loop_scores_enable)");
+    if (n_slots != R.cfg.n_slots) return fail(h, FOT_ERR_INVALID, "fot_loop_last_best_sample: n_slots differs from the loop's");
+    if (n_slots > 0 && !out) return fail(h, FOT_ERR_INVALID, "fot_loop_last_best_sample: out is NULL");
+    for (int e = 0; e < n_slots; ++e) out[e] = R.sc.last_best[(size_t)e];
     return FOT_OK;
 }
 
@@ -2633,6 +2783,7 @@ int fot_loop_set_sampler(fot_handle *h, int32_t S, uint64_t seed, int32_t kind)
     }
     M.S = S; M.seed = seed; M.kind = kind;
     M.on = true;
+    R.sc.on = false;                                             // (a new sampler: its scores are enabled again, if wanted)
     return FOT_OK;
 }
 

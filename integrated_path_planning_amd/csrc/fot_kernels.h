@@ -6,6 +6,7 @@
 #include "fot_types.h"
 #include "fot_summary.hpp"
 #include "fot_predscore.hpp"
+#include "fot_loopscore.hpp"
 
 namespace fot {
 
@@ -224,10 +225,21 @@ int launch_loop_history(const fot_result *rec, int n_run, const int32_t *src, co
 // Behind the step's prediction: running episode i (slot slot_of[i], pinned host memory) writes the row of lock step
 // `step` -- sum over its pedestrians of the distance between dense sample k of its block of `dyn` (the prepended column
 // skipped) and recording row min(f_cur + 1 + k, frames - 1) -- into place step % n_dense of its ring and folds the row it
-// replaces into totals[slot].  have_pred == 0 (observer not ready) or no pedestrians: an empty row.
+// replaces into totals[slot].  have_pred == 0 (observer not ready) or no pedestrians: an empty row.  best (HBM, per slot;
+// nullptr: none): episode i's block is a distribution [S][P][T][2] and its row is that of sample best[slot].
 int launch_loop_pred_error(ReplayView rv, const int32_t *slot_of, FrameDev f, const double *dyn, int n_run, int have_pred,
                            int f_cur, int step, SummaryShape S, double *ring, int32_t *ring_P, SummaryTotals *totals,
-                           hipStream_t st);
+                           hipStream_t st, const int32_t *best = nullptr);
+// ---- fot_loop_scores_enable (fot_loopscore.hpp): a resident sampler loop scores its predictor
+// The representative sample of running episode i's [S][P_i][n_dense + 1][2] block at point f.blk[i] of `dyn`:
+// dev_tab[slot][FOT_MAX_SAMPLES] (HBM) receives the S deviation sums, best_tab[slot] (HBM) and best_host[slot] (pinned) the
+// first minimum, -1 for an episode without pedestrians.  slot_of: pinned host memory.
+int launch_loop_best_sample(const int32_t *slot_of, FrameDev f, const double *dyn, int n_run, int S, int n_dense,
+                            double *dev_tab, int32_t *best_tab, int32_t *best_host, hipStream_t st);
+// The truth k_pred_scores reads for the step's origins, out[n_rows][E][2] (HBM): recording row min(f_cur + stride j,
+// frames - 1), j = 1 .. E, of every row of the frame.
+int launch_loop_score_truth(ReplayView rv, const int32_t *slot_of, FrameDev f, int n_rows, int f_cur, int stride, int E,
+                            double *out, hipStream_t st);
 // totals + the ring's rows under steps[slot] (pinned) -> the prediction-error keys and counts of out[slot] (pinned); the
 // other fields of the record are the host's.  Changes nothing in HBM.
 int launch_loop_summary(SummaryShape S, const double *ring, const int32_t *ring_P, const SummaryTotals *totals,

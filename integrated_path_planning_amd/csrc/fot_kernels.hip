@@ -23,6 +23,7 @@
 #include "fot_kernels.h"
 #include "fot_summary.hpp"
 #include "fot_predscore.hpp"
+#include "fot_loopscore.hpp"
 
 namespace fot {
 
@@ -2261,7 +2262,7 @@ k_loop_history(const fot_result *__restrict__ rec, int n_run, const int32_t *__r
 __global__ void __launch_bounds__(256)
 k_loop_pred_error(ReplayView rv, const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn, int n_run,
                   int have_pred, int f_cur, int step, SummaryShape S, double *__restrict__ ring,
-                  int32_t *__restrict__ ring_P, SummaryTotals *__restrict__ totals)
+                  int32_t *__restrict__ ring_P, SummaryTotals *__restrict__ totals, const int32_t *__restrict__ best)
 {
     __shared__ double old_row[FOT_MAX_NT];
     const int i = blockIdx.x, tid = threadIdx.x;
@@ -2286,7 +2287,8 @@ k_loop_pred_error(ReplayView rv, const int32_t *__restrict__ slot_of, FrameDev f
         return;
     }
     const int pre = f.prepend[i] ? 1 : 0, T_blk = nd + pre;
-    const double2 *pred = (const double2 *)dyn + f.blk[i];            // [P][T_blk], the prepended column skipped below
+    // [P][T_blk], the prepended column skipped below; of a distribution [S][P][T_blk]: the slot's representative sample
+    const double2 *pred = (const double2 *)dyn + f.blk[i] + (best ? (int64_t)max(best[slot], 0) * P * T_blk : 0);
     const double2 *rec = (const double2 *)rv.pos + rv.slot_ped0[slot];
     const int last_row = rv.slot_frames[slot] - 1;
     const int64_t cols = rv.n_cols;
@@ -2338,6 +2340,88 @@ k_loop_summary(SummaryShape S, const double *__restrict__ ring, const int32_t *_
     o->pred_samples = T.std_count > 0 ? num_samples : 0;
     o->ade_eval_count = (int32_t)T.std_count; o->planning_eval_count = (int32_t)T.plan_count;
     o->nll_eval_count = 0;
+}
+
+// ---------------------------------------------------------------------------
+// fot_loop_scores_enable (fot_loopscore.hpp): a resident sampler loop scores its predictor while it runs
+// ---------------------------------------------------------------------------
+
+// One workgroup per running episode, behind the ragged resample: the representative sample of the episode's
+// [S][P][n_dense + 1][2] block (predict_single_best).  Lanes run over the (p, k) points of the dense tracks, 256 a pass
+// (adjacent lanes: adjacent samples k of a track); a lane forms its point's mean over the samples in index order, then
+// its deviation from every sample; the lanes of a wave meet in a butterfly per sample and pass, the passes add up in a
+// slot of LDS per (sample, wave), the waves in index order: the order of every sum follows from (S, P, n_dense) alone,
+// so an episode chooses the same sample alone and in any batch.  An episode without pedestrians has no distribution: -1.
+constexpr int BS_THREADS = 256;
+constexpr int BS_WAVES = BS_THREADS / WAVE;
+
+__global__ void __launch_bounds__(BS_THREADS)
+k_loop_best_sample(const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn, int n_run, int S,
+                   int n_dense, double *__restrict__ dev_tab, int32_t *__restrict__ best_tab, int32_t *best_host)
+{
+    __shared__ double s_part[FOT_MAX_SAMPLES][BS_WAVES];
+    __shared__ double s_dev[FOT_MAX_SAMPLES];
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    if (i >= n_run) return;
+    const int slot = slot_of[i], p0 = f.ped0[i], P = f.ped0[i + 1] - p0;
+    if (P <= 0) {                                                    // (uniform)
+        if (tid == 0) { best_tab[slot] = -1; best_host[slot] = -1; }
+        return;
+    }
+    const int T = n_dense + 1, n = P * n_dense;
+    const int64_t sample_pts = (int64_t)P * T;
+    const double2 *blk = (const double2 *)dyn + f.blk[i];
+    for (int c = tid; c < FOT_MAX_SAMPLES * BS_WAVES; c += BS_THREADS) (&s_part[0][0])[c] = 0.0;
+    __syncthreads();
+    for (int base = 0; base < n; base += BS_THREADS) {               // (uniform trip count: the butterflies)
+        const int idx = base + tid;
+        const bool active = idx < n;
+        const int p = idx / n_dense, k = idx - p * n_dense;
+        const double2 *e = blk + (int64_t)p * T + 1 + k;             // sample s: e[s * sample_pts]; the prepended entry skipped
+        double mx = 0.0, my = 0.0;
+        if (active) {
+            for (int s = 0; s < S; ++s) {
+                const double2 v = e[s * sample_pts];
+                mx += v.x; my += v.y;
+            }
+            mx /= (double)S; my /= (double)S;
+        }
+        for (int s = 0; s < S; ++s) {
+            double d = 0.0;
+            if (active) {
+                const double2 v = e[s * sample_pts];
+                d = bs_dev(v.x, v.y, mx, my);
+            }
+            d = wave_sum_f64(d);
+            if (lane == 0) s_part[s][wave] += d;                     // (this wave's own column)
+        }
+    }
+    __syncthreads();
+    if (tid < S) {
+        double t = s_part[tid][0];
+        for (int w = 1; w < BS_WAVES; ++w) t += s_part[tid][w];
+        s_dev[tid] = t;
+        dev_tab[(int64_t)slot * FOT_MAX_SAMPLES + tid] = t;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int best = bs_first_min(S, s_dev);
+        best_tab[slot] = best; best_host[slot] = best;
+    }
+}
+
+// One thread per (row of the frame, evaluation step j): the truth of the step's origins, [rows][E][2], from the resident
+// recording -- row min(f_cur + stride (j + 1), frames - 1) of the pedestrian's slot (a shorter recording holds its last frame).
+__global__ void __launch_bounds__(256)
+k_loop_score_truth(ReplayView rv, const int32_t *__restrict__ slot_of, FrameDev f, int n_rows, int f_cur, int stride, int E,
+                   double2 *__restrict__ out)
+{
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n_rows * E) return;
+    const int p = idx / E, j = idx - p * E;
+    const int e = f.ped_ep[p], slot = slot_of[e];
+    const int row = min(f_cur + stride * (j + 1), rv.slot_frames[slot] - 1);
+    out[idx] = ((const double2 *)rv.pos)[(int64_t)row * rv.n_cols + rv.slot_ped0[slot] + (p - f.ped0[e])];
 }
 
 // ---------------------------------------------------------------------------
@@ -2567,11 +2651,32 @@ int launch_loop_history(const fot_result *rec, int n_run, const int32_t *src, co
 
 int launch_loop_pred_error(ReplayView rv, const int32_t *slot_of, FrameDev f, const double *dyn, int n_run, int have_pred,
                            int f_cur, int step, SummaryShape S, double *ring, int32_t *ring_P, SummaryTotals *totals,
-                           hipStream_t st)
+                           hipStream_t st, const int32_t *best)
 {
     if (n_run <= 0) return 0;
     if (S.n_dense < 1 || S.n_dense > FOT_MAX_NT || step < 0) return (int)hipErrorInvalidValue;
-    k_loop_pred_error<<<n_run, 256, 0, st>>>(rv, slot_of, f, dyn, n_run, have_pred, f_cur, step, S, ring, ring_P, totals);
+    k_loop_pred_error<<<n_run, 256, 0, st>>>(rv, slot_of, f, dyn, n_run, have_pred, f_cur, step, S, ring, ring_P, totals, best);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_best_sample(const int32_t *slot_of, FrameDev f, const double *dyn, int n_run, int S, int n_dense,
+                            double *dev_tab, int32_t *best_tab, int32_t *best_host, hipStream_t st)
+{
+    if (n_run <= 0) return 0;
+    if (S < 1 || S > FOT_MAX_SAMPLES || n_dense < 1) return (int)hipErrorInvalidValue;
+    k_loop_best_sample<<<n_run, BS_THREADS, 0, st>>>(slot_of, f, dyn, n_run, S, n_dense, dev_tab, best_tab, best_host);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_score_truth(ReplayView rv, const int32_t *slot_of, FrameDev f, int n_rows, int f_cur, int stride, int E,
+                            double *out, hipStream_t st)
+{
+    if (n_rows <= 0) return 0;
+    if (stride < 1 || E < 1 || E > FOT_MAX_PRED_LEN) return (int)hipErrorInvalidValue;
+    const int n = n_rows * E;
+    k_loop_score_truth<<<(n + 255) / 256, 256, 0, st>>>(rv, slot_of, f, n_rows, f_cur, stride, E, (double2 *)out);
     FOT_LAUNCH_CHECK();
     return 0;
 }

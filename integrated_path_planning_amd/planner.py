@@ -598,6 +598,28 @@ class BatchPlanner:
         _abi.check(self._h, self._lib.fot_loop_summaries(self._h, n, _addr(out)))
         return out[:n]
 
+    def loop_scores_enable(self, on: bool = True) -> None:
+        """``fot_loop_scores_enable``: a resident sampler loop scores every step's distribution where it lies in HBM and
+        accumulates the episode summaries while it runs (between ``loop_set_sampler`` and the first ``loop_run``)."""
+        _abi.check(self._h, self._lib.fot_loop_scores_enable(self._h, int(bool(on))))
+
+    def loop_score_summaries(self) -> np.ndarray:
+        """``fot_loop_score_summaries``: one ``fot_loop_summary`` record per slot (``LOOP_SUMMARY_DT``) of the steps run so
+        far -- best-of-N ADE / FDE and KDE-NLL over the origins with a complete horizon, the planning keys of the
+        representative samples, the safety and comfort keys; the run may go on afterwards."""
+        n = int(self._replay_slots)
+        out = np.zeros(max(n, 1), dtype=self.LOOP_SUMMARY_DT)
+        _abi.check(self._h, self._lib.fot_loop_score_summaries(self._h, n, _addr(out)))
+        return out[:n]
+
+    def loop_last_best_sample(self) -> np.ndarray:
+        """``fot_loop_last_best_sample``: per slot the representative sample the most recent lock step chose (-1: the slot
+        did not run, did not predict or has no pedestrians)."""
+        n = int(self._replay_slots)
+        out = np.full(max(n, 1), -1, np.int32)
+        _abi.check(self._h, self._lib.fot_loop_last_best_sample(self._h, n, _addr(out)))
+        return out[:n]
+
     PRED_SCORE_DT = np.dtype(_abi.PredScore)
     PRED_ORIGIN_DT = np.dtype(_abi.PredOrigin)
 
