@@ -280,6 +280,15 @@ int fot_debug_set_eval_segments(fot_handle *h, int32_t n_seg);
  * (synchronises the device); applies to the handle's later plan calls. */
 int fot_debug_set_tile_cut(fot_handle *h, int32_t cut);
 
+/* Test hook.  The evaluation kernels have a lean form for launches that cannot use the chance budget or a second block
+ * of time steps: every scenario of the handle has at most 64 samples per candidate and the single centre circle (no
+ * footprint circles), and every instance of the launch has max_viol == 0 (epsilon = 0).  The library picks it per launch;
+ * same decisions, byte-identical records.  form = 1 makes the handle's later plan calls run the general form whatever
+ * they are eligible for, 0 restores the choice by eligibility, -1 changes nothing.  Returns (>= 0) the forms the launches
+ * of the handle's most recent plan call took -- 0: none yet, 1: general, 2: lean, 3: both (a batch split into lanes) --
+ * or a negative FOT_ERR_*. */
+int fot_debug_set_eval_form(fot_handle *h, int32_t form);
+
 /* FrenetPlanner._build_time_cache (frenet_planner.py:586-617) as the library holds it for a horizon of `time`
  * seconds: the sample count n_t = round(time / dt) + 1 and the closed-form inverses of the quartic / quintic
  * boundary-value matrices (row-major 2x2 and 3x3) that every lattice polynomial is solved with.  Host only. */

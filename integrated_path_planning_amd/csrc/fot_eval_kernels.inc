@@ -1,0 +1,134 @@
+// The three evaluation kernels, included twice by fot_kernels.hip: as k_evaluate / k_evaluate_split / k_evaluate_group
+// (FOT_EVAL_LEAN false: the general form) and as k_evaluate_lean / k_evaluate_split_lean / k_evaluate_group_lean
+// (FOT_EVAL_LEAN true: FusedSink<true>).  Two inclusions rather than a template body behind two wrappers: each kernel
+// then reads its argument struct in place, exactly as the single form did (through a wrapper the struct is copied and
+// every field loaded at entry -- three more lane-spilled SGPRs in the grouped kernel).
+
+// One wave per tile.  The grid deals the tiles out position-major and XCD-aligned: workgroup b serves the instances
+// x, x + 8, ... with x = b mod 8 -- the XCD that, under round-robin placement, also ran k_cull's workgroups for them,
+// so their lists sit in its L2 (speed only) -- and an instance's LAST tile comes first (late horizons and the brake
+// ladder run longest), so the long tiles start early and the short ones fill the end of the launch.  The waves of a
+// workgroup share nothing but the staged spline: each has its own slice of LDS.
+__global__ void __launch_bounds__(EVAL_WG) __attribute__((amdgpu_waves_per_eu(3, 3)))
+FOT_EVAL_KERNEL(k_evaluate)(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, const InstState *__restrict__ state,
+           const int32_t *__restrict__ tile_cand0, const int32_t *__restrict__ tile_n,
+           const TileStep *__restrict__ wave_rng, const f2 *__restrict__ ent32, const EvalKernArgs a)
+{
+    // (eval_kernargs() addresses the struct's fields in the argument segment, behind the EVAL_LEAD_PTRS pointers)
+    const int waves_per_wg = (int)blockDim.x / WAVE;
+    const int wave_doubles = eval_wave_doubles(a.row_budget);
+#ifdef FOT_TIMELINE
+    if (threadIdx.x == 0) s_tl_entry[0] = __builtin_amdgcn_s_memrealtime();
+#endif
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+    const int lane = threadIdx.x & (WAVE - 1);
+    double *my_rows = s_lon + wv * wave_doubles;
+    const int x = (int)blockIdx.x & (N_XCD - 1);
+    const int m_x = (a.n_inst - x + N_XCD - 1) / N_XCD;            // instances x, x + 8, ...
+    // the tile of wave w of this workgroup: instance (-1: none) and position
+    const auto wave_inst = [&](int w, int &pos_w) {
+        const int q = ((int)blockIdx.x >> 3) * waves_per_wg + w;
+        if (m_x <= 0 || q >= m_x * a.max_tiles) return -1;
+        pos_w = q / m_x;
+        const int i = x + N_XCD * (q - pos_w * m_x);
+        return pos_w < desc[i].n_tiles ? i : -1;                  // (a shorter lattice than the batch's longest: none)
+    };
+    int pos = 0;
+    const int inst = wave_inst(wv, pos);
+    // LDS: per wave [rows | summaries | row offsets], then the spline (shared by the workgroup's waves).  The waves of a
+    // workgroup serve different instances: in a mixed batch the spline is staged when all of them are on one scenario,
+    // otherwise every wave reads its own scenario's spline from HBM (no LDS taken from the row tables).
+    SplineView sp_stage = a.sp;
+    if (a.mixed) {
+        int common = -1;                                         // -1: none yet, -2: the waves disagree
+        for (int w = 0; w < waves_per_wg; ++w) {                 // (uniform: every wave walks the same workgroup)
+            int pw;
+            const int iw = wave_inst(w, pw);
+            if (iw < 0) continue;
+            const int sw = desc[iw].scen;
+            common = common == -1 || common == sw ? sw : -2;
+        }
+        if (common >= 0) sp_stage = load_const(a.sp_table, common);
+        else sp_stage.n = a.lds_knots + 1;                       // nothing staged: no wave reads sp_stage
+        if (inst >= 0) Pp += desc[inst].scen;
+    }
+    SplineView sp_lds = stage_spline(sp_stage, a.lds_knots, s_lon + waves_per_wg * wave_doubles);
+    if (a.mixed && inst >= 0 && sp_stage.n > a.lds_knots) sp_lds = load_const(a.sp_table, desc[inst].scen);
+#ifdef FOT_TIMELINE
+    if (threadIdx.x == 0) s_tl_entry[1] = __builtin_amdgcn_s_memrealtime();
+    __syncthreads();
+#endif
+    if (inst < 0) return;
+    const int n_tiles = desc[inst].n_tiles;
+    TilePart tp = tile_part_empty();
+    evaluate_tile<TILE_WAVE, FOT_EVAL_LEAN>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, my_rows, inst,
+                         n_tiles - 1 - pos, lane, x, tp);
+    tile_done(inst, n_tiles - 1 - pos, lane, tp);
+}
+
+// The same for a handful of egos (fewer tiles than the GPU has SIMDs): a tile alone on its SIMD is a chain of
+// ~50 dependent time steps of ~1.1 us, so the workgroup's waves (blockDim.x / 64 <= SEG_MAX) take a time segment
+// each of ONE tile and its first wave merges them.  One workgroup per tile, same tile order.
+__global__ void __launch_bounds__(SEG_MAX * WAVE)
+FOT_EVAL_KERNEL(k_evaluate_split)(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc,
+                 const InstState *__restrict__ state, const int32_t *__restrict__ tile_cand0,
+                 const int32_t *__restrict__ tile_n, const TileStep *__restrict__ wave_rng,
+                 const f2 *__restrict__ ent32, const EvalKernArgs a)
+{
+    const int n_seg = (int)blockDim.x / WAVE;
+    const int wave_doubles = eval_wave_doubles(a.row_budget);
+    // LDS: [rows | summaries | row offsets] of the tile, the segments' hand-over, then the spline
+    double *s_part = s_lon + wave_doubles;
+    const int seg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int x = (int)blockIdx.x & (N_XCD - 1), q = (int)blockIdx.x >> 3;
+    const int m_x = (a.n_inst - x + N_XCD - 1) / N_XCD;
+    if (m_x <= 0) return;                                        // (the whole workgroup: one tile, one instance)
+    if (q >= m_x * a.max_tiles) return;
+    const int pos = q / m_x, j = q - pos * m_x;
+    const int inst = x + N_XCD * j;
+    const int n_tiles = desc[inst].n_tiles;
+    if (pos >= n_tiles) return;
+    SplineView sp_hbm = a.sp;
+    if (a.mixed) { Pp += desc[inst].scen; sp_hbm = load_const(a.sp_table, desc[inst].scen); }
+    const SplineView sp_lds = stage_spline(sp_hbm, a.lds_knots, s_part + (SEG_MAX - 1) * SEG_DOUBLES);
+    const int tile = n_tiles - 1 - pos;
+    TilePart tp = tile_part_empty();
+    evaluate_tile<TILE_SPLIT, FOT_EVAL_LEAN>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, s_lon, inst, tile, lane, x,
+                              tp, seg, n_seg, s_part);
+    if (seg == 0) tile_done(inst, tile, lane, tp);               // (the wave that merged the segments and holds the results)
+}
+
+// The grouped cut (fot_math.hpp): one workgroup per group of GROUP_TILES tiles, one shared row table, four such
+// workgroups per CU -- four waves per SIMD.  Same order as above with groups in the place of tiles: queue x holds the
+// groups of the instances x, x + 8, ... position-major, an instance's last group first.
+#ifndef FOT_GROUP_WAVES
+#define FOT_GROUP_WAVES 4
+#endif
+__global__ void __launch_bounds__(GROUP_TILES * WAVE) __attribute__((amdgpu_waves_per_eu(FOT_GROUP_WAVES, FOT_GROUP_WAVES)))
+FOT_EVAL_KERNEL(k_evaluate_group)(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc,
+                 const InstState *__restrict__ state, const int32_t *__restrict__ tile_cand0,
+                 const int32_t *__restrict__ tile_n, const TileStep *__restrict__ wave_rng,
+                 const f2 *__restrict__ ent32, const EvalKernArgs a)
+{
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int x = (int)blockIdx.x & (N_XCD - 1), q = (int)blockIdx.x >> 3;
+    const int m_x = (a.n_inst - x + N_XCD - 1) / N_XCD;
+    const int n_entries = m_x * (a.max_tiles / GROUP_TILES);      // groups in this queue
+    if (m_x <= 0 || q >= n_entries) return;                      // (the whole workgroup: one group, one instance)
+    const int pos = q / m_x, j = q - pos * m_x;
+    const int inst = x + N_XCD * j;
+    const int n_groups = desc[inst].n_tiles / GROUP_TILES;
+    if (pos >= n_groups) return;                                 // a shorter lattice than the batch's longest
+    // LDS: [rows | summaries | row offsets] of the group, then the spline
+    SplineView sp_hbm = a.sp;
+    if (a.mixed) { Pp += desc[inst].scen; sp_hbm = load_const(a.sp_table, desc[inst].scen); }
+    const SplineView sp_lds = stage_spline(sp_hbm, a.lds_knots, s_lon + eval_group_doubles());
+    const int tile0 = (n_groups - 1 - pos) * GROUP_TILES;
+    TilePart tp = tile_part_empty();
+    evaluate_tile<TILE_GROUP, FOT_EVAL_LEAN>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, s_lon, inst, tile0 + wv,
+                              lane, x, tp, wv, GROUP_TILES, nullptr, tile0);
+    tile_done(inst, tile0 + wv, lane, tp);
+}
+

@@ -269,6 +269,8 @@ struct fot_handle {
     int32_t done_seq = 0;
     bool done_seq_armed = false;             // the call being enqueued wants the flags
     int tile_cut = 0;                    // fot_debug_set_tile_cut (TILE_CUT_*)
+    int eval_form = 0;                   // fot_debug_set_eval_form: 0 = by eligibility, 1 = the general form always
+    int last_eval_forms = 0;             // forms the launches of the most recent plan call took: 1 general | 2 lean
     std::vector<Scenario> sc;                // scenarios; sc[0]: fot_create's params + fot_set_path_*
     std::vector<ScenarioRef> refs;           // what build_batch_layout needs of each (rebuilt with the tile table)
     DevBuf dP;                               // DevParams[sc.size()]
@@ -599,6 +601,12 @@ int enqueue_lane(fot_handle *h, Workspace &w, const fot_batch &b, const int32_t 
     tt.n_tiles = L.n_tiles; tt.max_tiles = L.max_tiles; tt.row_budget = L.row_budget;
     tt.eval_segments = h->eval_segments;
     tt.grouped = L.grouped;
+    // The lean evaluation kernels (FusedSink<true>): at most 64 samples per candidate and the single centre circle in
+    // every scenario of the handle, no chance budget on any instance of this launch.  Anything else: the general form.
+    tt.lean = h->eval_form == 0 ? 1 : 0;
+    for (const Scenario &S : h->sc) if (S.P.n_total > WAVE || S.P.has_footprint) tt.lean = 0;
+    for (int i = 0; i < L.n_inst && tt.lean; ++i) if (L.desc[(size_t)i].max_viol != 0) tt.lean = 0;
+    h->last_eval_forms |= tt.lean ? 2 : 1;
     const DevParams *dP = nullptr;
     const PathSet sv = path_set(h, L, &dP);
     CandArrays ca;
@@ -678,6 +686,7 @@ int enqueue_plan(fot_handle *h, const fot_batch &b, const int32_t *scen, const v
     if (b.n_inst < 0) return fail(h, FOT_ERR_INVALID, "n_inst < 0");
     { int r = check_scenarios(h, b, scen); if (r != FOT_OK) return r; }
     h->last_valid = false;
+    h->last_eval_forms = 0;
     if (b.n_inst == 0) { h->lanes_used = 0; h->last_valid = true; return FOT_OK; }
     if (!d_out) return fail(h, FOT_ERR_INVALID, "out is NULL");
     if (!b.ego || !b.target_speed) return fail(h, FOT_ERR_INVALID, "ego / target_speed missing");
@@ -3153,6 +3162,15 @@ int fot_debug_set_tile_cut(fot_handle *h, int32_t cut)
         return fail(h, FOT_ERR_INVALID, "fot_debug_set_tile_cut: 0 (automatic), 1 (per-wave rows), 2 (groups)");
     if (cut == h->tile_cut) return FOT_OK;
     return upload_tile_shapes(h, cut);
+}
+
+int fot_debug_set_eval_form(fot_handle *h, int32_t form)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (form < -1 || form > 1)
+        return fail(h, FOT_ERR_INVALID, "fot_debug_set_eval_form: 0 (by eligibility), 1 (general form), -1 (query only)");
+    if (form >= 0) h->eval_form = form;
+    return h->last_eval_forms;
 }
 
 int fot_debug_time_info(const fot_handle *h, double time, int32_t *n_t, double *quartic_inv4, double *quintic_inv9)

@@ -78,6 +78,8 @@ struct TileTable {
     int n_tiles = 0, max_tiles = 0, row_budget = 0;
     int grouped = 0;                    // groups of GROUP_TILES tiles share a row table (TileShapes::grouped)
     int eval_segments = 0;              // time segments per tile in k_evaluate: 0 = by batch size, 1..4 forced (tests)
+    int lean = 0;                       // the launch may take the lean evaluation kernels: at most 64 samples per candidate,
+                                        // the single centre circle, no chance budget on any instance (enqueue_lane)
 };
 
 // The scenarios (planner constants + reference path) of a plan launch.  A batch on ONE scenario passes that scenario's

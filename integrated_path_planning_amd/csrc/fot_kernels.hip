@@ -491,6 +491,12 @@ __device__ __forceinline__ const EvalKernArgs &eval_kernargs()
     return *(const EvalKernArgs *)((const char *)__builtin_amdgcn_kernarg_segment_ptr() + EVAL_LEAD_PTRS * sizeof(void *));
 }
 
+// LEAN: the form for launches whose every instance has no chance budget (max_viol == 0) on handles of at most 64 samples
+// per candidate (launch_evaluate): a certain hit always settles the candidate, so thr_fatal is thr_sure -- no lane
+// register, lane read or branch for it --, hit_mask / viol are never touched (the exact re-check counts on locals: its
+// first violation is a hit), and the per-step values never need a second block of 64 steps.  Same thresholds, same
+// min-only walk, same per-chunk walk of the band lanes, same exact re-check: the decisions are the general form's.
+template <bool LEAN>
 struct FusedSink {
     const DevParams *Pp;
     const InstDesc *Dp;
@@ -533,13 +539,14 @@ struct FusedSink {
 
     __device__ __forceinline__ void row_begin(int k)
     {
-        if ((k & ~(WAVE - 1)) != step_base) steps_load(k & ~(WAVE - 1));      // wave-uniform; never taken up to 64 samples
-        const int kl = k & (WAVE - 1);
+        if constexpr (!LEAN)
+            if ((k & ~(WAVE - 1)) != step_base) steps_load(k & ~(WAVE - 1));  // wave-uniform; never taken up to 64 samples
+        const int kl = LEAN ? k : k & (WAVE - 1);
         const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)my_rng, kl);
         c_lo = (int)(r >> 16);
         n_chunks = (int)(r & 0xffffu) - c_lo;
         thr = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_thr), kl));
-        thr_fatal = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_thr_fatal), kl));
+        thr_fatal = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, LEAN ? my_thr_sure : my_thr_fatal), kl));
         if (n_chunks > 0 && !no_warm) {
             const f2x8 *row = chunks + (int64_t)k * chunks_per_k + c_lo;
             asm volatile("s_load_dword %0, %1, 0x0\n\t"
@@ -570,7 +577,7 @@ struct FusedSink {
         if (!alive || hit) return;                                // lanes whose collision outcome is already settled
         float fx = fx_in;                                         // (tied into the hand-issued loads below)
         const f2x8 *row = chunks + (int64_t)k * chunks_per_k + c_lo;
-        if (thr_fatal >= 0.0f) {                                  // wave-uniform: a certain hit settles the candidate
+        if (LEAN || thr_fatal >= 0.0f) {                          // wave-uniform: a certain hit settles the candidate
             // Min-only walk: one running minimum over every chunk of the step, no per-chunk compare, bit or exec-mask
             // work.  A minimum at or below thr_fatal is a certain hit (some chunk's minimum is); a minimum above thr
             // means that no chunk of the step is near, so the classic walk below would neither set a near bit nor
@@ -627,16 +634,23 @@ struct FusedSink {
         px += D.ego.x; py += D.ego.y;                             // the exact entries are in the caller's frame
         const double sq_dyn = D.dyn_mode == FOT_DYN_SINGLE ? P.sq_r_dyn : P.sq_r;
         const EvalKernArgs &KA = eval_kernargs();
-        const float thr_sure = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_thr_sure), k & (WAVE - 1)));
+        const float thr_sure = LEAN ? thr_fatal :
+            __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_thr_sure), k & (WAVE - 1)));
         const d2 *e64 = KA.ent64 + D.ent_off;
         const uint8_t *sid = KA.ent_sid + D.ent_off;
         const int64_t base = ((int64_t)k * chunks_per_k + c_lo) * ENT_CHUNK;
+        uint64_t mask_l = 0;                                      // (LEAN: no budget, nothing outlives the first violation)
+        int viol_l = 0;
         while (near_bits != 0 && !hit) {
             const int hb = 31 - __clz((int)near_bits);             // highest bit = earliest chunk
             near_bits &= ~(1u << hb);
             const int64_t e = base + (int64_t)(c0 + nb - 1 - hb) * ENT_CHUNK;
-            exact_chunk_f32first(chunks[e / ENT_CHUNK], e64 + e, sid + e, fx, fy, thr, thr_sure, px, py, P.sq_r, sq_dyn,
-                                 D.max_viol, hit_mask, viol, hit);
+            if constexpr (LEAN)
+                exact_chunk_f32first(chunks[e / ENT_CHUNK], e64 + e, sid + e, fx, fy, thr, thr_sure, px, py, P.sq_r, sq_dyn,
+                                     0, mask_l, viol_l, hit);
+            else
+                exact_chunk_f32first(chunks[e / ENT_CHUNK], e64 + e, sid + e, fx, fy, thr, thr_sure, px, py, P.sq_r, sq_dyn,
+                                     D.max_viol, hit_mask, viol, hit);
         }
     }
 
@@ -746,7 +760,7 @@ __device__ __forceinline__ void wave_lds_fence()
 //   TILE_GROUP  the workgroup's GROUP_TILES waves take the tiles grp_tile0 + sub of one group (fot_math.hpp): they
 //               build the rows of ALL the group's profiles together, each walks its own tile.
 enum { TILE_WAVE = 0, TILE_SPLIT = 1, TILE_GROUP = 2 };
-template <int MODE>
+template <int MODE, bool LEAN>
 __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc,
                                               const InstState *__restrict__ state,
                                               const int32_t *__restrict__ tile_cand0, const int32_t *__restrict__ tile_n,
@@ -833,7 +847,7 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
         my_step = wave_rng[(int64_t)(D.tile0 + tile) * n_total + step_base0 + lane];
     const uint32_t my_rng = my_step.rng;
     // (while every lane is active: the time-step loop reads lane k of these, candidate or not)
-    const float my_thr_fatal = D.max_viol == 0 ? my_step.thr_sure : -1.0f;
+    const float my_thr_fatal = LEAN ? 0.0f : D.max_viol == 0 ? my_step.thr_sure : -1.0f;   // (LEAN: not read)
 #ifdef FOT_TIMELINE
     const uint64_t t_wave = __builtin_amdgcn_s_memrealtime();
     const uint64_t c_wave = __builtin_amdgcn_s_memtime();
@@ -871,7 +885,7 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
         // come back through v_readlane in every time step -- three vector registers are cheaper
         asm volatile("" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]));
 
-        FusedSink sink;
+        FusedSink<LEAN> sink;
         sink.Pp = Pp; sink.Dp = &D;
         sink.my_rng = my_rng;
         sink.my_thr = my_step.thr; sink.my_thr_sure = my_step.thr_sure; sink.thr = 0.0f; sink.thr_fatal = -1.0f;
@@ -889,9 +903,11 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
         // kernel that is bound by exactly those (r02: 0.257 -> 0.242 ms).  12 VGPRs; the kernel still fits 168.
         asm volatile("" : "+v"(lc.dt), "+v"(lc.lim_speed), "+v"(lc.lim_accel), "+v"(lc.lim_curv), "+v"(lc.lim_lat),
                           "+v"(lc.road_lim));
-        lc.n_circ_fp = __builtin_amdgcn_readfirstlane(lc.n_circ_fp);
-        asm volatile("" : "+s"(lc.n_circ_fp));
-        evaluate_segment(P, lc, L, tab, q, k0, k1, sink, g);   // (SPLIT: a quarter of the steps -- latency, not issue, bound)
+        if constexpr (!LEAN) {                                   // (LEAN: the single centre circle, never read)
+            lc.n_circ_fp = __builtin_amdgcn_readfirstlane(lc.n_circ_fp);
+            asm volatile("" : "+s"(lc.n_circ_fp));
+        }
+        evaluate_segment<LEAN>(P, lc, L, tab, q, k0, k1, sink, g);   // (SPLIT: a quarter of the steps -- latency, not issue, bound)
         hit_mask = sink.hit_mask; hit = sink.hit;
 #ifdef FOT_TIMELINE
         tl_rows = tab.t_rows;
@@ -1137,133 +1153,16 @@ k_select_only(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ des
     }
 }
 
-// One wave per tile.  The grid deals the tiles out position-major and XCD-aligned: workgroup b serves the instances
-// x, x + 8, ... with x = b mod 8 -- the XCD that, under round-robin placement, also ran k_cull's workgroups for them,
-// so their lists sit in its L2 (speed only) -- and an instance's LAST tile comes first (late horizons and the brake
-// ladder run longest), so the long tiles start early and the short ones fill the end of the launch.  The waves of a
-// workgroup share nothing but the staged spline: each has its own slice of LDS.
-__global__ void __launch_bounds__(EVAL_WG) __attribute__((amdgpu_waves_per_eu(3, 3)))
-k_evaluate(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, const InstState *__restrict__ state,
-           const int32_t *__restrict__ tile_cand0, const int32_t *__restrict__ tile_n,
-           const TileStep *__restrict__ wave_rng, const f2 *__restrict__ ent32, const EvalKernArgs a)
-{
-    // (eval_kernargs() addresses the struct's fields in the argument segment, behind the EVAL_LEAD_PTRS pointers)
-    const int waves_per_wg = (int)blockDim.x / WAVE;
-    const int wave_doubles = eval_wave_doubles(a.row_budget);
-#ifdef FOT_TIMELINE
-    if (threadIdx.x == 0) s_tl_entry[0] = __builtin_amdgcn_s_memrealtime();
-#endif
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
-    const int lane = threadIdx.x & (WAVE - 1);
-    double *my_rows = s_lon + wv * wave_doubles;
-    const int x = (int)blockIdx.x & (N_XCD - 1);
-    const int m_x = (a.n_inst - x + N_XCD - 1) / N_XCD;            // instances x, x + 8, ...
-    // the tile of wave w of this workgroup: instance (-1: none) and position
-    const auto wave_inst = [&](int w, int &pos_w) {
-        const int q = ((int)blockIdx.x >> 3) * waves_per_wg + w;
-        if (m_x <= 0 || q >= m_x * a.max_tiles) return -1;
-        pos_w = q / m_x;
-        const int i = x + N_XCD * (q - pos_w * m_x);
-        return pos_w < desc[i].n_tiles ? i : -1;                  // (a shorter lattice than the batch's longest: none)
-    };
-    int pos = 0;
-    const int inst = wave_inst(wv, pos);
-    // LDS: per wave [rows | summaries | row offsets], then the spline (shared by the workgroup's waves).  The waves of a
-    // workgroup serve different instances: in a mixed batch the spline is staged when all of them are on one scenario,
-    // otherwise every wave reads its own scenario's spline from HBM (no LDS taken from the row tables).
-    SplineView sp_stage = a.sp;
-    if (a.mixed) {
-        int common = -1;                                         // -1: none yet, -2: the waves disagree
-        for (int w = 0; w < waves_per_wg; ++w) {                 // (uniform: every wave walks the same workgroup)
-            int pw;
-            const int iw = wave_inst(w, pw);
-            if (iw < 0) continue;
-            const int sw = desc[iw].scen;
-            common = common == -1 || common == sw ? sw : -2;
-        }
-        if (common >= 0) sp_stage = load_const(a.sp_table, common);
-        else sp_stage.n = a.lds_knots + 1;                       // nothing staged: no wave reads sp_stage
-        if (inst >= 0) Pp += desc[inst].scen;
-    }
-    SplineView sp_lds = stage_spline(sp_stage, a.lds_knots, s_lon + waves_per_wg * wave_doubles);
-    if (a.mixed && inst >= 0 && sp_stage.n > a.lds_knots) sp_lds = load_const(a.sp_table, desc[inst].scen);
-#ifdef FOT_TIMELINE
-    if (threadIdx.x == 0) s_tl_entry[1] = __builtin_amdgcn_s_memrealtime();
-    __syncthreads();
-#endif
-    if (inst < 0) return;
-    const int n_tiles = desc[inst].n_tiles;
-    TilePart tp = tile_part_empty();
-    evaluate_tile<TILE_WAVE>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, my_rows, inst,
-                         n_tiles - 1 - pos, lane, x, tp);
-    tile_done(inst, n_tiles - 1 - pos, lane, tp);
-}
-
-// The same for a handful of egos (fewer tiles than the GPU has SIMDs): a tile alone on its SIMD is a chain of
-// ~50 dependent time steps of ~1.1 us, so the workgroup's waves (blockDim.x / 64 <= SEG_MAX) take a time segment
-// each of ONE tile and its first wave merges them.  One workgroup per tile, same tile order.
-__global__ void __launch_bounds__(SEG_MAX * WAVE)
-k_evaluate_split(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc,
-                 const InstState *__restrict__ state, const int32_t *__restrict__ tile_cand0,
-                 const int32_t *__restrict__ tile_n, const TileStep *__restrict__ wave_rng,
-                 const f2 *__restrict__ ent32, const EvalKernArgs a)
-{
-    const int n_seg = (int)blockDim.x / WAVE;
-    const int wave_doubles = eval_wave_doubles(a.row_budget);
-    // LDS: [rows | summaries | row offsets] of the tile, the segments' hand-over, then the spline
-    double *s_part = s_lon + wave_doubles;
-    const int seg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int x = (int)blockIdx.x & (N_XCD - 1), q = (int)blockIdx.x >> 3;
-    const int m_x = (a.n_inst - x + N_XCD - 1) / N_XCD;
-    if (m_x <= 0) return;                                        // (the whole workgroup: one tile, one instance)
-    if (q >= m_x * a.max_tiles) return;
-    const int pos = q / m_x, j = q - pos * m_x;
-    const int inst = x + N_XCD * j;
-    const int n_tiles = desc[inst].n_tiles;
-    if (pos >= n_tiles) return;
-    SplineView sp_hbm = a.sp;
-    if (a.mixed) { Pp += desc[inst].scen; sp_hbm = load_const(a.sp_table, desc[inst].scen); }
-    const SplineView sp_lds = stage_spline(sp_hbm, a.lds_knots, s_part + (SEG_MAX - 1) * SEG_DOUBLES);
-    const int tile = n_tiles - 1 - pos;
-    TilePart tp = tile_part_empty();
-    evaluate_tile<TILE_SPLIT>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, s_lon, inst, tile, lane, x,
-                              tp, seg, n_seg, s_part);
-    if (seg == 0) tile_done(inst, tile, lane, tp);               // (the wave that merged the segments and holds the results)
-}
-
-// The grouped cut (fot_math.hpp): one workgroup per group of GROUP_TILES tiles, one shared row table, four such
-// workgroups per CU -- four waves per SIMD.  Same order as above with groups in the place of tiles: queue x holds the
-// groups of the instances x, x + 8, ... position-major, an instance's last group first.
-#ifndef FOT_GROUP_WAVES
-#define FOT_GROUP_WAVES 4
-#endif
-__global__ void __launch_bounds__(GROUP_TILES * WAVE) __attribute__((amdgpu_waves_per_eu(FOT_GROUP_WAVES, FOT_GROUP_WAVES)))
-k_evaluate_group(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc,
-                 const InstState *__restrict__ state, const int32_t *__restrict__ tile_cand0,
-                 const int32_t *__restrict__ tile_n, const TileStep *__restrict__ wave_rng,
-                 const f2 *__restrict__ ent32, const EvalKernArgs a)
-{
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int x = (int)blockIdx.x & (N_XCD - 1), q = (int)blockIdx.x >> 3;
-    const int m_x = (a.n_inst - x + N_XCD - 1) / N_XCD;
-    const int n_entries = m_x * (a.max_tiles / GROUP_TILES);      // groups in this queue
-    if (m_x <= 0 || q >= n_entries) return;                      // (the whole workgroup: one group, one instance)
-    const int pos = q / m_x, j = q - pos * m_x;
-    const int inst = x + N_XCD * j;
-    const int n_groups = desc[inst].n_tiles / GROUP_TILES;
-    if (pos >= n_groups) return;                                 // a shorter lattice than the batch's longest
-    // LDS: [rows | summaries | row offsets] of the group, then the spline
-    SplineView sp_hbm = a.sp;
-    if (a.mixed) { Pp += desc[inst].scen; sp_hbm = load_const(a.sp_table, desc[inst].scen); }
-    const SplineView sp_lds = stage_spline(sp_hbm, a.lds_knots, s_lon + eval_group_doubles());
-    const int tile0 = (n_groups - 1 - pos) * GROUP_TILES;
-    TilePart tp = tile_part_empty();
-    evaluate_tile<TILE_GROUP>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, s_lon, inst, tile0 + wv,
-                              lane, x, tp, wv, GROUP_TILES, nullptr, tile0);
-    tile_done(inst, tile0 + wv, lane, tp);
-}
+#define FOT_EVAL_LEAN false
+#define FOT_EVAL_KERNEL(name) name
+#include "fot_eval_kernels.inc"
+#undef FOT_EVAL_LEAN
+#undef FOT_EVAL_KERNEL
+#define FOT_EVAL_LEAN true
+#define FOT_EVAL_KERNEL(name) name##_lean
+#include "fot_eval_kernels.inc"
+#undef FOT_EVAL_LEAN
+#undef FOT_EVAL_KERNEL
 
 // ---------------------------------------------------------------------------
 // collision broad phase: entry lists
@@ -2479,6 +2378,7 @@ int launch_evaluate(const DevParams *P, const PathSet &ps, const InstDesc *desc,
     //  * a handful of egos: every tile one workgroup, cut into time segments (k_evaluate_split);
     //  * the grouped cut: one workgroup per group of four tiles (k_evaluate_group, four waves per SIMD);
     //  * the per-wave cut: four independent tiles per workgroup (k_evaluate, three waves per SIMD).
+    // Each in its lean form (FusedSink) when the host found the launch eligible (tiles.lean: enqueue_lane).
     int n_seg = tiles.n_tiles <= 2304 ? SEG_MAX : 1;       // (scripts/segment_sweep.py: four segments win up to ~64 egos)
     if (tiles.eval_segments >= 1 && tiles.eval_segments <= SEG_MAX) n_seg = tiles.eval_segments;
     static const int force_wpw = getenv("FOT_EVAL_WPW") ? atoi(getenv("FOT_EVAL_WPW")) : 0;      // diagnostics
@@ -2501,15 +2401,16 @@ int launch_evaluate(const DevParams *P, const PathSet &ps, const InstDesc *desc,
     if (tiles.n_tiles <= 0) {
         k_select_only<<<(unsigned)n_inst, WAVE, 0, st>>>(P, desc, state, tiles.cand0, tiles.n, e.rng, e.e32, a);
     } else if (n_seg > 1) {
-        k_evaluate_split<<<(unsigned)n_blocks, n_seg * WAVE, lds, st>>>(P, desc, state, tiles.cand0, tiles.n, e.rng,
-                                                                        e.e32, a);
+        (tiles.lean ? k_evaluate_split_lean : k_evaluate_split)<<<(unsigned)n_blocks, n_seg * WAVE, lds, st>>>(
+            P, desc, state, tiles.cand0, tiles.n, e.rng, e.e32, a);
     } else if (tiles.grouped) {                                            // one workgroup per group of tiles
         const int per_q = (n_inst + N_XCD - 1) / N_XCD * (tiles.max_tiles / GROUP_TILES);
         const size_t g_lds = sizeof(double) * ((size_t)eval_group_doubles() + 9 * (size_t)lds_knots);
-        k_evaluate_group<<<(unsigned)(per_q * N_XCD), GROUP_TILES * WAVE, g_lds, st>>>(P, desc, state, tiles.cand0,
-                                                                                      tiles.n, e.rng, e.e32, a);
+        (tiles.lean ? k_evaluate_group_lean : k_evaluate_group)<<<(unsigned)(per_q * N_XCD), GROUP_TILES * WAVE, g_lds, st>>>(
+            P, desc, state, tiles.cand0, tiles.n, e.rng, e.e32, a);
     } else {
-        k_evaluate<<<(unsigned)n_blocks, wpw * WAVE, lds, st>>>(P, desc, state, tiles.cand0, tiles.n, e.rng, e.e32, a);
+        (tiles.lean ? k_evaluate_lean : k_evaluate)<<<(unsigned)n_blocks, wpw * WAVE, lds, st>>>(
+            P, desc, state, tiles.cand0, tiles.n, e.rng, e.e32, a);
     }
     FOT_LAUNCH_CHECK();
     return 0;

@@ -801,8 +801,9 @@ FOT_HD void seg_init(SegState &g)
     g.first_nan = -1; g.k_last = -1;
 }
 
-// time steps [k0, k1) of one candidate
-template <class Tab, class Sink>
+// time steps [k0, k1) of one candidate.  LEAN: the caller vouches for the single centre circle (C.n_circ_fp == 0), so the
+// footprint-circle loop is not instantiated; everything else is the same walk (the sink has a lean form of its own).
+template <bool LEAN = false, class Tab, class Sink>
 FOT_HD void evaluate_segment(const DevParams &P, const LoopConst &C, const LonInfo &L, const Tab &lon_tab,
                              const double *q, int k0, int k1, Sink &sink, SegState &g)
 {
@@ -841,7 +842,9 @@ FOT_HD void evaluate_segment(const DevParams &P, const LoopConst &C, const LonIn
             ps.v = c.v; ps.a = c.a; ps.d = d;
             check_sample(C, acc, k, ps, true, true, [&] { return fabs(lon_tab.s_at(k) - lon_tab.s_at(k - 1)); });
             const bool alive = (acc.fl & CK_FAILED) == 0;
-            if (C.n_circ_fp > 0) {
+            if constexpr (LEAN) {
+                sink.put(k, 0, c.x, c.y, alive);
+            } else if (C.n_circ_fp > 0) {
                 for (int ci = 0; ci < C.n_circ_fp; ++ci)
                     sink.put(k, ci, c.x + P.circ_off[ci] * c.cos_t, c.y + P.circ_off[ci] * c.sin_t, alive);
             } else {
@@ -895,13 +898,13 @@ FOT_HD void finish_candidate(const DevParams &P, const InstDesc &D, const LonInf
     out.travel = g.k_last >= 0 ? lon_tab.s_at(g.k_last) - lon_tab.s_at(0) : 0.0;   // NaN is sticky: sample 0 was valid
 }
 
-template <class Tab, class Sink>
+template <bool LEAN = false, class Tab, class Sink>
 FOT_HD void evaluate_candidate(const DevParams &P, const InstDesc &D, const LoopConst &C, const LonInfo &L,
                                const Tab &lon_tab, const double *q, int n_loop, Sink &sink, CandResult &out)
 {
     SegState g;
     seg_init(g);
-    evaluate_segment(P, C, L, lon_tab, q, 0, n_loop, sink, g);
+    evaluate_segment<LEAN>(P, C, L, lon_tab, q, 0, n_loop, sink, g);
     finish_candidate(P, D, L, lon_tab, q, g, sink.collided(), out);
 }
 
@@ -1316,7 +1319,10 @@ FOT_HD void exact_chunk_f32first(const f2x8 &c32, const d2 *e64, const uint8_t *
 // entry lists of its instance (same decision as collide_candidate).  cnt[k]: entries of time step k (multiple of 8);
 // the entry arrays hold ent_cap slots per k.  This is the portable form; k_evaluate's sink is the same logic with
 // the chunk walk on scalar loads.
-struct EntryCollider {
+// LEAN (launches without a chance budget, max_viol == 0): no sample mask and no violation count are carried -- the exact
+// re-check works on locals, because its first violation is a hit.
+template <bool LEAN>
+struct EntryColliderT {
     const uint32_t *rng;                 // [n_total] strip ranges of this candidate's wave, nullptr: no obstacles
     const float *thr_k = nullptr, *thr_sure_k = nullptr;   // [n_total] the tile's thresholds per step (box_thresholds),
                                                            // nullptr: derived from the point itself
@@ -1354,16 +1360,23 @@ struct EntryCollider {
         for (int c = c_lo * ENT_CHUNK; c < c_hi * ENT_CHUNK && !hit; c += ENT_CHUNK) {
             const float m = min_sqdist32_8(*(const f2x8 *)(e32 + base + c), fx, fy);
             if (m > thr) continue;
-            if (max_viol == 0 && m <= thr_sure) { hit = true; break; }      // certain hit: one violation is fatal
+            if ((LEAN || max_viol == 0) && m <= thr_sure) { hit = true; break; }   // certain hit: one violation is fatal
             double px, py;
             get_exact(px, py);
-            exact_chunk_f32first(*(const f2x8 *)(e32 + base + c), e64 + base + c, sid + base + c, fx, fy, thr, thr_sure,
-                                 px, py, sq_static, sq_dyn, max_viol, hit_mask, viol, hit);
+            if constexpr (LEAN) {
+                uint64_t mask_l = 0; int viol_l = 0;
+                exact_chunk_f32first(*(const f2x8 *)(e32 + base + c), e64 + base + c, sid + base + c, fx, fy, thr, thr_sure,
+                                     px, py, sq_static, sq_dyn, 0, mask_l, viol_l, hit);
+            } else {
+                exact_chunk_f32first(*(const f2x8 *)(e32 + base + c), e64 + base + c, sid + base + c, fx, fy, thr, thr_sure,
+                                     px, py, sq_static, sq_dyn, max_viol, hit_mask, viol, hit);
+            }
         }
     }
     FOT_HD void restart() { hit_mask = 0; viol = 0; hit = false; }
     FOT_HD bool collided() const { return hit; }
 };
+using EntryCollider = EntryColliderT<false>;
 
 // ---------------------------------------------------------------------------
 // selection (reference: frenet_planner.py:307-324, 1235-1259)

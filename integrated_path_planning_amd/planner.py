@@ -794,6 +794,21 @@ class BatchPlanner:
         cut = {"auto": 0, "wave": 1, "group": 2}.get(cut, cut)
         _abi.check(self._h, self._lib.fot_debug_set_tile_cut(self._h, int(cut)))
 
+    def set_eval_form(self, form) -> int:
+        """Test hook (``fot_debug_set_eval_form``): 0 / "auto" (the lean evaluation kernels where a launch is eligible:
+        at most 64 samples, the single centre circle, epsilon = 0 on every instance), 1 / "general" (the general form
+        always), -1 / "query".  Returns the forms the most recent plan call's launches took: 0 none yet, 1 general,
+        2 lean, 3 both."""
+        form = {"auto": 0, "general": 1, "query": -1}.get(form, form)
+        rc = self._lib.fot_debug_set_eval_form(self._h, int(form))
+        if rc < 0:
+            _abi.check(self._h, rc)
+        return rc
+
+    def last_eval_form(self) -> str:
+        """Which evaluation kernels the most recent plan call ran: "none", "general", "lean" or "both"."""
+        return ("none", "general", "lean", "both")[self.set_eval_form(-1)]
+
     def time_info(self, time: float):
         """(n_t, quartic inverse [2, 2], quintic inverse [3, 3]) the library solves a horizon of ``time`` seconds with
         (``fot_debug_time_info``)."""
