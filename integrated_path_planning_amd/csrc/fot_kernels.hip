@@ -879,7 +879,6 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
         tab.lds_row0 = (int)(my_rows - s_lon) + s_row0[p] * ROW_FIELDS;
         tab.k_max = profile_rows(P, D, cd.lon_slot) - 1;
         tab.info = s_info + p;
-        tab.dt = P.dt;
         lat_coeffs(S.frenet0, cd.di, cd.brake ? P.brake[cd.ti] : P.ti[cd.ti], q);
         // q[0..2] are the instance's lateral state (wave-uniform): as scalar values they end up in spilled SGPRs and
         // come back through v_readlane in every time step -- three vector registers are cheaper
@@ -903,6 +902,9 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
         // kernel that is bound by exactly those (r02: 0.257 -> 0.242 ms).  12 VGPRs; the kernel still fits 168.
         asm volatile("" : "+v"(lc.dt), "+v"(lc.lim_speed), "+v"(lc.lim_accel), "+v"(lc.lim_curv), "+v"(lc.lim_lat),
                           "+v"(lc.road_lim));
+        // (the arc step of the low-speed rule reads the table's dt: the same vector register, not a scalar copy of
+        //  P.dt that is lane-spilled before the loop and read back by two v_readlane in that branch)
+        tab.dt = lc.dt;
         if constexpr (!LEAN) {                                   // (LEAN: the single centre circle, never read)
             lc.n_circ_fp = __builtin_amdgcn_readfirstlane(lc.n_circ_fp);
             asm volatile("" : "+s"(lc.n_circ_fp));

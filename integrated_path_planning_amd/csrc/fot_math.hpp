@@ -54,8 +54,9 @@ FOT_HD double sum_sq_unfused(double a, double b);
 
 // a * b + c as ONE rounding on the device (v_fma_f64), spelled out where two kernels must produce the same bits from
 // the same expression whatever the compiler's contraction heuristics make of the code around it; two roundings on the
-// host (the CPU logic test compares with tolerances, and builds with -ffp-contract=off)
-#if defined(__HIP_DEVICE_COMPILE__)
+// host (the CPU logic test compares with tolerances, and builds with -ffp-contract=off).  FOT_HOST_FMA: a host test
+// that measures the device's own roundings (tests/emu/fot_lat_emu.cpp) asks for the fused form there too.
+#if defined(__HIP_DEVICE_COMPILE__) || defined(FOT_HOST_FMA)
 #define FOT_FMA(a, b, c) __builtin_fma((a), (b), (c))
 #else
 #define FOT_FMA(a, b, c) ((a) * (b) + (c))
@@ -363,10 +364,23 @@ FOT_HD void lon_eval(const LonInfo &L, double t, double &s, double &sd, double &
 
 FOT_HD void lat_eval(const double *q, double t, double &d, double &dd, double &ddd, double &dddd)
 {
-    // Horner form of the quintic and its three derivatives (:688-691)
-    d = quintic_value(q, t);
-    dd = q[1] + t * (2.0 * q[2] + t * (3.0 * q[3] + t * (4.0 * q[4] + t * (5.0 * q[5]))));
-    ddd = 2.0 * q[2] + t * (6.0 * q[3] + t * (12.0 * q[4] + t * (20.0 * q[5])));
+    // The quintic and its derivatives (:688-691).  Value, first derivative and half the second by repeated synthetic
+    // division from the plain coefficients: dividing by (x - t) three times leaves p(t), p'(t) and p''(t) / 2 as the
+    // remainders, 12 fused multiply-adds and one exact doubling -- none of the products 2 q2 ... 20 q5 of the
+    // derivatives' own Horner forms, which the compiler formed again in every time step.  The first row IS
+    // quintic_value (d_last enters the cost: its bits must not move); the third derivative keeps its Horner form.
+    const double b4 = FOT_FMA(t, q[5], q[4]);
+    const double b3 = FOT_FMA(t, b4, q[3]);
+    const double b2 = FOT_FMA(t, b3, q[2]);
+    const double b1 = FOT_FMA(t, b2, q[1]);
+    d = FOT_FMA(t, b1, q[0]);
+    const double c4 = FOT_FMA(t, q[5], b4);
+    const double c3 = FOT_FMA(t, c4, b3);
+    const double c2 = FOT_FMA(t, c3, b2);
+    dd = FOT_FMA(t, c2, b1);
+    const double e4 = FOT_FMA(t, q[5], c4);
+    const double e3 = FOT_FMA(t, e4, c3);
+    ddd = 2.0 * FOT_FMA(t, e3, c2);
     dddd = 6.0 * q[3] + t * (24.0 * q[4] + t * (60.0 * q[5]));
 }
 

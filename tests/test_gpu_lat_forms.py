@@ -1,0 +1,122 @@
+"""The lateral quintic by synthetic division (csrc/fot_math.hpp lat_eval) through every kernel that evaluates it.
+
+lat_eval is one definition: the evaluation walk of every kernel form, the selection's path rebuild, k_debug_path and
+k_cull's lateral extents all call it, so records stay byte-identical between the grouped, per-wave and segmented kernels
+and between the lean and the general form.  One batch of three instances on one handle (three scenarios, one time grid):
+
+  * a config-3 seed (prediction distribution, moving ego);
+  * an ego at 0.2 m/s whose lattice is the brake ladder alone.  The reference generates the ladder only for an ego
+    faster than 0.1 m/s (frenet_planner.py:453-503: a standing ego has no ladder, and with no grid no candidate at
+    all), so this is the slowest ego that has one; min_t = 5.5 s above max_t = 5 s leaves no horizon for the grid and
+    ten ladder entries 0.5 ... 5.0 s, each held (lat_sample past n_eval) to the end of the time grid except the last.
+    Every sample of it is below the low-speed gate;
+  * a config-2 seed (static obstacles, module defaults).
+
+planned under every path of helpers.EVAL_PATHS in the lean form (what the call takes by itself) and with the general
+form forced: the records are byte-identical across all eight, the candidate tables equal the oracle's (status, kept
+length; cost at the suite's 1e-8), the selected path is within the suite's 1e-8 of the oracle's, and k_debug_path's
+lateral columns d, d', d'', d''' of five candidates per instance are within 1e-12 of the oracle's -- relative to the
+column's largest magnitude: both sides carry a few ulp of the sum of the polynomial's terms (tests/test_lat_eval_cpu.py),
+which near a zero crossing of a derivative is not small against the value itself.  Measured: the worst
+difference is 1.4e-14 of the column's largest magnitude.
+"""
+import numpy as np
+import pytest
+
+import eps_band
+from helpers import (EVAL_PATHS, TIGHT, PlanRequest, assert_record_matches_oracle, oracle_plan_for_request,
+                     request_from_instance, set_eval_path)
+from integrated_path_planning_amd import _abi, synthetic as syn
+from integrated_path_planning_amd.planner import BatchPlanner
+from oracle import oracle as orc
+
+pytestmark = pytest.mark.gpu
+
+WP = (syn.STRAIGHT_WX, syn.STRAIGHT_WY)
+LADDER_PLANNER = dict(syn.CONFIG3_PLANNER, min_t=5.5, max_t=5.0)
+PLANNERS = [syn.CONFIG3_PLANNER, LADDER_PLANNER, syn.CONFIG2_PLANNER]
+LAT_ROWS = {"d": 5, "d_d": 6, "d_dd": 7, "d_ddd": 8}              # rows of a [15, MAX_NT] path array (_abi.PATH_FIELDS)
+
+
+def requests():
+    c3 = request_from_instance(syn.config3_instance(3, S=8, P=12))
+    for f in ("static", "dyn", "dist"):                        # float64 inputs: the oracle sees the values the device sees
+        v = getattr(c3, f)
+        if v is not None:
+            setattr(c3, f, np.asarray(v, np.float64))
+    ladder = PlanRequest(12.0, 0.3, 0.02, 0.2, 0.0, target_speed=syn.TARGET_SPEED)
+    c2 = request_from_instance(syn.config2_instance(5))
+    reqs = [c3, ladder, c2]
+    for k, r in enumerate(reqs):
+        r.scenario = k
+    return reqs
+
+
+@pytest.fixture(scope="module")
+def wants():
+    """the oracle's plan of each instance with its candidate table, computed once"""
+    sp = orc.Spline(*WP)
+    out = []
+    for rq, kw in zip(requests(), PLANNERS):
+        params = orc.make_params(**kw)
+        out.append((params, sp, oracle_plan_for_request(orc, params, sp, rq, table=True)))
+    return out
+
+
+def rec_bytes(rec):
+    return bytes(memoryview(rec).cast("B"))
+
+
+def test_the_ladder_instance_is_the_brake_ladder_alone(wants):
+    want = wants[1][2]
+    assert want.n_cand == 10 and want.status == _abi.PLAN_OK
+    np.testing.assert_array_equal(want.cand_nt, 51)                                  # padded to the end of the time grid
+    assert wants[0][2].status == _abi.PLAN_OK and wants[2][2].status == _abi.PLAN_OK
+
+
+def test_records_tables_and_lateral_columns_under_every_path_and_form(wants):
+    reqs = requests()
+    bp = BatchPlanner(waypoints=WP, **PLANNERS[0])
+    for k, kw in enumerate(PLANNERS[1:], start=1):
+        assert bp.add_scenario(waypoints=WP, **kw) == k
+    first = None
+    for path in EVAL_PATHS:
+        set_eval_path(bp, path)
+        for form in ("lean", "general"):
+            bp.set_eval_form("auto" if form == "lean" else "general")
+            res = bp.plan_batch(reqs)
+            label = f"[{path}, {form}]"
+            assert bp.last_eval_form() == form, f"{label}: ran the {bp.last_eval_form()} form"
+            got = [rec_bytes(res.records[i]) for i in range(len(reqs))]
+            if first is None:
+                first = got
+            for i in range(len(reqs)):
+                assert got[i] == first[i], f"{label} inst {i}: record differs from [{EVAL_PATHS[0]}, lean]"
+            for i, (params, sp, want) in enumerate(wants):
+                lab = f"{label} inst {i}"
+                assert_record_matches_oracle(res.records[i], want, label=lab)
+                cost, status, keep, nt = bp.candidates(i)
+                assert len(cost) == want.n_cand, lab
+                np.testing.assert_array_equal(nt, want.cand_nt, err_msg=lab)
+                np.testing.assert_array_equal(keep, want.cand_keep, err_msg=lab)
+                np.testing.assert_allclose(cost, want.cand_cost, rtol=TIGHT, atol=TIGHT, err_msg=lab)
+                eps_band.check_status_table(bp, i, status, want.cand_status, lab)
+    # k_debug_path of the last call: the lateral columns of five candidates per instance (the first, the last -- a
+    # brake-ladder entry with held samples -- and three in between)
+    worst = 0.0
+    for i, (params, sp, want) in enumerate(wants):
+        n = want.n_cand
+        for c in sorted({0, n // 4, n // 2, (3 * n) // 4, n - 1}):
+            fp = bp.candidate_path(c, i)
+            _, arr, _ = orc.candidate_path(params, sp, want.frenet0, reqs[i].target_speed, c)
+            n_t = int(want.cand_nt[c])
+            assert len(fp.d) == n_t, f"inst {i} cand {c}"
+            for f, row in LAT_ROWS.items():
+                g, w = np.asarray(getattr(fp, f)), arr[row, :n_t]
+                scale = float(np.max(np.abs(w)))
+                if scale > 0.0:
+                    worst = max(worst, float(np.max(np.abs(g - w))) / scale)
+                np.testing.assert_allclose(g, w, rtol=0.0, atol=1e-12 * scale, err_msg=f"inst {i} cand {c} {f}")
+    print(f"lateral columns: worst difference {worst:.2e} of the column's largest magnitude")
+    bp.set_eval_form("auto")
+    bp.close()
