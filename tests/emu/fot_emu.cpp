@@ -27,11 +27,53 @@ struct VecSink {
     void put(int k, int ci, double x, double y, bool) { d2 v; v.x = x; v.y = y; (*pts)[(size_t)ci * n_total + k] = v; }
     bool collided() const { return false; }
 };
+// Which walk of a candidate the tables and the selection of emu_plan_batch report: 1 -- the walk in one piece (the
+// segmented walks must then agree with it: -110 .. -112); 2 .. 4 -- the walk in that many time segments, merged
+// (k_evaluate_split), reported as it comes out so that a test can hold IT to an independent reference.
+int g_table_segments = 1;
+
 struct VecSource {
     const d2 *pts; int n_total;
     void get(int k, int ci, double &x, double &y) const { const d2 &v = pts[(size_t)ci * n_total + k]; x = v.x; y = v.y; }
     int tindex(int k) const { return k; }
 };
+// k_frenet_state of one instance (nlanes = 1): nearest point, Frenet state, brake-ladder gate.  prev_s_in: the cached arc
+// length the search starts from (a chained instance: its predecessor's result).
+bool emu_frenet_state(const DevParams &P, const InstDesc &D, const SplineView &sp, double prev_s_in, InstState &S)
+{
+    const double x = D.ego.x, y = D.ego.y, s_end = sp.s[sp.n - 1];
+    double best_s = 0.0;
+    bool need_global = true;
+    const bool given = D.ego.has_prev_s == FOT_EGO_IS_FRENET;
+    if (given) need_global = false;
+    if (D.ego.has_prev_s && !given) {
+        const double s_min = fmax(0.0, prev_s_in - 10.0), s_max = fmin(s_end, prev_s_in + 10.0);
+        ScanBest bb = scan_samples(sp, x, y, s_min, s_max, 100, 0, 1, false);
+        best_s = bb.idx >= 0 ? linspace_at(s_min, s_max, 100, bb.idx) : 0.0;
+        need_global = (fabs(best_s - s_min) < 1e-3 && s_min > 0.0) || (fabs(best_s - s_max) < 1e-3 && s_max < s_end);
+    }
+    const int n_glob = global_search_count(sp);
+    if (need_global) {
+        ScanBest bb = scan_samples(sp, x, y, 0.0, s_end, n_glob, 0, 1, true);
+        best_s = linspace_at(0.0, s_end, n_glob, bb.idx >= 0 ? bb.idx : 0);
+    }
+    if (!given) best_s = refine_nearest(sp, x, y, best_s);
+    S.new_prev_s = given ? NAN : best_s;
+    const bool ok = given ? frenet_state_given(sp, D.ego, S.frenet0, S.ref0) : frenet_state_at(sp, D.ego, best_s, S.frenet0, S.ref0);
+    S.c2f_ok = ok;
+    S.n_brake = (ok && S.frenet0[1] > 0.1) ? P.n_brake : 0;
+    S.n_cand = ok ? D.n_grid + S.n_brake : 0;
+    return ok;
+}
+
+SplineView spline_view(const HostSpline &hs)
+{
+    SplineView sp;
+    sp.n = hs.n; sp.s = hs.s.data();
+    sp.ax = hs.ax.data(); sp.bx = hs.bx.data(); sp.cx = hs.cx.data(); sp.dx = hs.dx.data();
+    sp.ay = hs.ay.data(); sp.by = hs.by.data(); sp.cy = hs.cy.data(); sp.dy = hs.dy.data();
+    return sp;
+}
 }  // namespace
 
 extern "C" int emu_plan_batch(const fot_params *params, int n_knots, const double *wx, const double *wy,
@@ -48,10 +90,7 @@ extern "C" int emu_plan_batch(const fot_params *params, int n_knots, const doubl
     if (rc == FOT_OK) build_tile_shapes(P, shapes);
     if (rc == FOT_OK) rc = build_batch_layout(*params, P, shapes, *b, L, err);
     if (rc != FOT_OK) { if (errbuf) std::strncpy(errbuf, err.c_str(), 255); return rc; }
-    SplineView sp;
-    sp.n = hs.n; sp.s = hs.s.data();
-    sp.ax = hs.ax.data(); sp.bx = hs.bx.data(); sp.cx = hs.cx.data(); sp.dx = hs.dx.data();
-    sp.ay = hs.ay.data(); sp.by = hs.by.data(); sp.cy = hs.cy.data(); sp.dy = hs.dy.data();
+    const SplineView sp = spline_view(hs);
 
     std::memset(out, 0, sizeof(fot_result) * (size_t)L.n_inst);
     std::vector<LonInfo> lon_info((size_t)L.n_lon + 1);
@@ -61,30 +100,8 @@ extern "C" int emu_plan_batch(const fot_params *params, int n_knots, const doubl
         fot_result &R = out[inst];
         // --- k_frenet_state (nlanes = 1)
         InstState S;
-        const double x = D.ego.x, y = D.ego.y, s_end = sp.s[sp.n - 1];
-        double best_s = 0.0;
-        bool need_global = true;
         const bool chained = D.ego.has_prev_s == FOT_PREV_S_CHAINED;
-        const double prev_s_in = chained ? out[inst - 1].new_prev_s : D.ego.prev_s;
-        const bool given = D.ego.has_prev_s == FOT_EGO_IS_FRENET;
-        if (given) need_global = false;
-        if (D.ego.has_prev_s && !given) {
-            const double s_min = fmax(0.0, prev_s_in - 10.0), s_max = fmin(s_end, prev_s_in + 10.0);
-            ScanBest bb = scan_samples(sp, x, y, s_min, s_max, 100, 0, 1, false);
-            best_s = bb.idx >= 0 ? linspace_at(s_min, s_max, 100, bb.idx) : 0.0;
-            need_global = (fabs(best_s - s_min) < 1e-3 && s_min > 0.0) || (fabs(best_s - s_max) < 1e-3 && s_max < s_end);
-        }
-        const int n_glob = global_search_count(sp);
-        if (need_global) {
-            ScanBest bb = scan_samples(sp, x, y, 0.0, s_end, n_glob, 0, 1, true);
-            best_s = linspace_at(0.0, s_end, n_glob, bb.idx >= 0 ? bb.idx : 0);
-        }
-        if (!given) best_s = refine_nearest(sp, x, y, best_s);
-        S.new_prev_s = given ? NAN : best_s;
-        bool ok = given ? frenet_state_given(sp, D.ego, S.frenet0, S.ref0) : frenet_state_at(sp, D.ego, best_s, S.frenet0, S.ref0);
-        S.c2f_ok = ok;
-        S.n_brake = (ok && S.frenet0[1] > 0.1) ? P.n_brake : 0;
-        S.n_cand = ok ? D.n_grid + S.n_brake : 0;
+        const bool ok = emu_frenet_state(P, D, sp, chained ? out[inst - 1].new_prev_s : D.ego.prev_s, S);
         if (!ok) {
             R.status = FOT_PLAN_C2F_FAILED; R.best_index = -1; R.cost = INFINITY;
             R.new_last_kappa = D.ego.last_kappa; R.new_prev_s = S.new_prev_s;
@@ -296,6 +313,7 @@ extern "C" int emu_plan_batch(const fot_params *params, int n_knots, const doubl
                 }
             }
             for (int n_seg = 2; n_seg <= 4; ++n_seg) {   // k_evaluate_split: time segments merged == the single walk
+                if (g_table_segments > 1 && n_seg != g_table_segments) continue;
                 const int n_loop = P.n_total, seg_len = (n_loop + n_seg - 1) / n_seg;
                 const LoopConst lc = loop_const(P, D);
                 SegState g;
@@ -319,6 +337,7 @@ extern "C" int emu_plan_batch(const fot_params *params, int n_knots, const doubl
                 hit |= pc > D.max_viol;
                 CandResult rs;
                 finish_candidate(P, D, Li, GlobalTab{ tab }, q, g, hit, rs);
+                if (n_seg == g_table_segments) { r = rs; break; }   // tabled instead of compared (emu_table_segments)
                 if (rs.status != r.status || rs.keep != r.keep) return -110;
                 if (std::memcmp(&rs.v_last, &r.v_last, sizeof(double)) || std::memcmp(&rs.travel, &r.travel, sizeof(double)))
                     return -111;
@@ -358,6 +377,77 @@ extern "C" int emu_plan_batch(const fot_params *params, int n_knots, const doubl
     }
     return FOT_OK;
 }
+
+// The candidates of instance 0 of a one-instance batch as the library's debug path gives them (k_debug_path: the rows
+// computed on the spot, final_sample per sample): n_t per candidate and the 15 FrenetPath arrays,
+// paths [cand_cap][15][FOT_MAX_NT], untruncated (nullptr: not wanted); margins [cand_cap][FOT_MARGIN_GROUPS]: what
+// fot_debug_margins reports without obstacles (nullptr: not wanted).  Returns the number of candidates, or a negative
+// error.
+extern "C" int emu_candidate_paths(const fot_params *params, int n_knots, const double *wx, const double *wy,
+                                   const fot_batch *b, int cand_cap, int32_t *cand_nt, double *paths, double *margins,
+                                   char *errbuf)
+{
+    std::string err;
+    DevParams P;
+    int rc = build_dev_params(*params, P, err);
+    HostSpline hs;
+    if (rc == FOT_OK) rc = build_spline(n_knots, wx, wy, hs, err);
+    BatchLayout L;
+    TileShapes shapes;
+    if (rc == FOT_OK) build_tile_shapes(P, shapes);
+    if (rc == FOT_OK) rc = build_batch_layout(*params, P, shapes, *b, L, err);
+    if (rc == FOT_OK && L.n_inst != 1) { rc = FOT_ERR_INVALID; err = "one instance"; }
+    if (rc != FOT_OK) { if (errbuf) std::strncpy(errbuf, err.c_str(), 255); return rc < 0 ? rc : -rc; }
+    const SplineView sp = spline_view(hs);
+    const InstDesc &D = L.desc[0];
+    InstState S;
+    if (!emu_frenet_state(P, D, sp, D.ego.prev_s, S)) return 0;
+    for (int idx = 0; idx < S.n_cand && idx < cand_cap; ++idx) {
+        const CandDecode cd = decode_candidate(P, D, S.frenet0, idx);
+        const LonInfo Li = profile_info(P, D, S.frenet0, cd.lon_slot, false);
+        ComputeTab tab;
+        tab.sp = sp; tab.L = Li; tab.dt = P.dt;
+        double q[6];
+        lat_coeffs(S.frenet0, cd.di, cd.brake ? P.brake[cd.ti] : P.ti[cd.ti], q);
+        cand_nt[idx] = Li.n_t;
+        if (margins) {
+            MarginEntries none = { nullptr, nullptr, nullptr, 0 };
+            candidate_margins(P, D, Li, tab, q, none, margins + (size_t)idx * MARGIN_CATS);
+        }
+        if (paths) {
+            double *dst = paths + (size_t)idx * 15 * FOT_MAX_NT;
+            for (int k = 0; k < Li.n_t; ++k) {
+                double o[15];
+                final_sample(P, Li, tab, q, k, o);
+                for (int f = 0; f < 15; ++f) dst[f * FOT_MAX_NT + k] = o[f];
+            }
+        }
+    }
+    return S.n_cand;
+}
+
+// Length of a time segment of k_evaluate_split for every candidate of a lattice shape: each tile walks
+// n_loop = the longest of its own profiles in n_seg pieces of ceil(n_loop / n_seg) steps (csrc/fot_kernels.hip), under
+// the per-wave cut (grouped 0) or the grouped one.  n_cand: the candidates the instance has (a standing ego: no ladder).
+extern "C" int emu_segment_lengths(const fot_params *params, int n_tv, int n_cand, int grouped, int n_seg, int32_t *seg_len)
+{
+    std::string err;
+    DevParams P;
+    if (build_dev_params(*params, P, err) != FOT_OK || n_tv < 1 || n_tv > FOT_MAX_TV || n_seg < 1) return -1;
+    TileShapes T;
+    if (grouped) build_tile_shapes_grouped(P, T); else build_tile_shapes_wave(P, T);
+    const InstDesc D = shape_desc(P, n_tv);
+    if (n_cand > D.n_cand_max) return -2;
+    for (int t = T.off[n_tv]; t < T.off[n_tv + 1]; ++t) {
+        const int c0 = T.cand0[(size_t)t], c1 = std::min(c0 + T.n[(size_t)t], n_cand);
+        int n_loop = 0;
+        for (int c = c0; c < c1; ++c) n_loop = std::max(n_loop, c < D.n_grid ? P.ti[c / (n_tv * P.n_di)].n_t : P.n_total);
+        for (int c = c0; c < c1; ++c) seg_len[c] = (n_loop + n_seg - 1) / n_seg;
+    }
+    return 0;
+}
+
+extern "C" void emu_table_segments(int n_seg) { g_table_segments = n_seg >= 2 && n_seg <= 4 ? n_seg : 1; }
 
 extern "C" int emu_spline(int n, const double *wx, const double *wy, double *out9n)
 {
