@@ -111,24 +111,47 @@ FOT_EVAL_KERNEL(k_evaluate_group)(const DevParams *__restrict__ Pp, const InstDe
                  const int32_t *__restrict__ tile_n, const TileStep *__restrict__ wave_rng,
                  const f2 *__restrict__ ent32, const EvalKernArgs a)
 {
+#ifdef FOT_TIMELINE
+    if (threadIdx.x == 0) s_tl_entry[0] = __builtin_amdgcn_s_memrealtime();
+#endif
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
     const int lane = threadIdx.x & (WAVE - 1);
     const int x = (int)blockIdx.x & (N_XCD - 1), q = (int)blockIdx.x >> 3;
     const int m_x = (a.n_inst - x + N_XCD - 1) / N_XCD;
-    const int n_entries = m_x * (a.max_tiles / GROUP_TILES);      // groups in this queue
+    const int n_pos = a.max_tiles / GROUP_TILES;                  // group positions of an instance
+    const int n_entries = m_x * n_pos;                            // groups in this queue
     if (m_x <= 0 || q >= n_entries) return;                      // (the whole workgroup: one group, one instance)
     const int pos = q / m_x, j = q - pos * m_x;
-    const int inst = x + N_XCD * j;
-    const int n_groups = desc[inst].n_tiles / GROUP_TILES;
-    if (pos >= n_groups) return;                                 // a shorter lattice than the batch's longest
-    // LDS: [rows | summaries | row offsets] of the group, then the spline
+    int inst = x + N_XCD * j;
+    // (the general form: one register across the loop, not the two it is made of -- two lane-spilled SGPRs less; the
+    //  lean form has room for both and its time step comes out two vector instructions shorter without this)
+    if (!FOT_EVAL_LEAN) asm volatile("" : "+s"(inst));
+    // LDS: the rows of the group, its header (GroupHead: k_frenet_state has built it), then the spline.  The header's
+    // address follows from the arguments alone: one coalesced load, issued with the spline's, both behind ONE barrier.
+    GroupHead *s_head = (GroupHead *)(s_lon + GROUP_ROWS * ROW_FIELDS);
+    constexpr int HEAD_WORDS = (int)(sizeof(GroupHead) / sizeof(unsigned long long));
+    static_assert(HEAD_WORDS <= GROUP_TILES * WAVE, "one 8-byte word per thread");
+    const unsigned long long *head_src = (const unsigned long long *)(eval_kernargs().heads + ((int64_t)inst * n_pos + pos));
+    unsigned long long head_word = 0ull;
+    if ((int)threadIdx.x < HEAD_WORDS) head_word = head_src[threadIdx.x];
     SplineView sp_hbm = a.sp;
     if (a.mixed) { Pp += desc[inst].scen; sp_hbm = load_const(a.sp_table, desc[inst].scen); }
-    const SplineView sp_lds = stage_spline(sp_hbm, a.lds_knots, s_lon + eval_group_doubles());
-    const int tile0 = (n_groups - 1 - pos) * GROUP_TILES;
+    double *s_knots = s_lon + eval_group_doubles();
+    const bool staged = sp_hbm.n <= a.lds_knots;
+    if (staged) stage_spline_copy(sp_hbm, s_knots);
+    if ((int)threadIdx.x < HEAD_WORDS) ((unsigned long long *)s_head)[threadIdx.x] = head_word;
+    __syncthreads();
+#ifdef FOT_TIMELINE
+    if (threadIdx.x == 0) s_tl_entry[1] = __builtin_amdgcn_s_memrealtime();   // header and spline in LDS
+#endif
+    const SplineView sp_lds = staged ? staged_spline_view(sp_hbm, s_knots) : sp_hbm;
+    const int present = __builtin_amdgcn_readfirstlane(s_head->present);
+    if (present == GROUP_HEAD_ABSENT) return;                    // a shorter lattice than the batch's longest: all waves
+    const int tile0 = __builtin_amdgcn_readfirstlane(s_head->grp_tile0);
     TilePart tp = tile_part_empty();
-    evaluate_tile<TILE_GROUP, FOT_EVAL_LEAN>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, s_lon, inst, tile0 + wv,
-                              lane, x, tp, wv, GROUP_TILES, nullptr, tile0);
+    // (GROUP_HEAD_EMPTY -- no Frenet state, or the brake ladder of a standing ego: the tiles count as done, nothing found)
+    evaluate_group_tile<FOT_EVAL_LEAN>(Pp, desc, wave_rng, ent32, a, sp_lds, s_lon, inst, tile0 + wv, wv, lane, x, tp,
+                                       present == GROUP_HEAD_FULL);
     tile_done(inst, tile0 + wv, lane, tp);
 }
 

@@ -96,12 +96,13 @@ struct Workspace {
     DevBuf dEntCnt, dEnt32, dEnt64, dEntSid, dWaveRng;   // broad phase: culled entry lists + per-wave chunk ranges
     DevBuf dNanFlag;                         // one flag per pedestrian track (NanScan)
     DevBuf dDone;                            // tiles evaluated so far, per instance (tile_done)
+    DevBuf dHeads;                           // GroupHead[n_inst][max_tiles / GROUP_TILES] of a grouped evaluation
     BatchLayout last;                        // layout of this lane's part of the most recent plan call
     int first_inst = 0;                      // global index of this lane's first instance
     void release()
     {
         DevBuf *bufs[] = { &dMeta, &dState, &dCost, &dParts, &dStatus, &dKeep,
-                           &dWaveRng, &dEntCnt, &dEnt32, &dEnt64, &dEntSid, &dNanFlag, &dDone };
+                           &dWaveRng, &dEntCnt, &dEnt32, &dEnt64, &dEntSid, &dNanFlag, &dDone, &dHeads };
         for (DevBuf *b : bufs) b->release();
         for (int i = 0; i < 2; ++i) {
             staging[i].release();
@@ -607,6 +608,13 @@ int enqueue_lane(fot_handle *h, Workspace &w, const fot_batch &b, const int32_t 
     for (const Scenario &S : h->sc) if (S.P.n_total > WAVE || S.P.has_footprint) tt.lean = 0;
     for (int i = 0; i < L.n_inst && tt.lean; ++i) if (L.desc[(size_t)i].max_viol != 0) tt.lean = 0;
     h->last_eval_forms |= tt.lean ? 2 : 1;
+    GroupHeadOut gh;                                             // the grouped kernels' headers: k_frenet_state builds them
+    if (evaluate_in_groups(tt)) {
+        gh.n_pos = L.max_tiles / GROUP_TILES;
+        HIP_TRY(h, w.dHeads.ensure(sizeof(GroupHead) * (size_t)L.n_inst * (size_t)gh.n_pos));
+        gh.heads = tt.heads = w.dHeads.as<GroupHead>();
+        gh.tile_cand0 = tt.cand0; gh.tile_n = tt.n;
+    }
     const DevParams *dP = nullptr;
     const PathSet sv = path_set(h, L, &dP);
     CandArrays ca;
@@ -645,7 +653,7 @@ int enqueue_lane(fot_handle *h, Workspace &w, const fot_batch &b, const int32_t 
     }
     {
         ProfScope ps(h, 0, st);
-        LAUNCH_TRY(h, launch_frenet_state(dP, sv, d_desc, w.dState.as<InstState>(), L.n_inst, imp, scan, w.dDone.as<int32_t>(), st));
+        LAUNCH_TRY(h, launch_frenet_state(dP, sv, d_desc, w.dState.as<InstState>(), L.n_inst, imp, scan, w.dDone.as<int32_t>(), st, gh));
     }
     if (L.any_obstacles) {
         ProfScope ps(h, 1, st);

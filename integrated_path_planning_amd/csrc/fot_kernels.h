@@ -80,6 +80,16 @@ struct TileTable {
     int eval_segments = 0;              // time segments per tile in k_evaluate: 0 = by batch size, 1..4 forced (tests)
     int lean = 0;                       // the launch may take the lean evaluation kernels: at most 64 samples per candidate,
                                         // the single centre circle, no chance budget on any instance (enqueue_lane)
+    GroupHead *heads = nullptr;         // [n_inst][max_tiles / GROUP_TILES] group headers, where evaluate_in_groups()
+};
+// the evaluation of this batch goes to the grouped kernels (launch_evaluate): k_frenet_state then builds their headers
+bool evaluate_in_groups(const TileTable &tiles);
+
+// The group-header table k_frenet_state fills for the grouped evaluation kernels (heads == nullptr: none wanted)
+struct GroupHeadOut {
+    GroupHead *heads = nullptr;         // [n_inst][n_pos]
+    const int32_t *tile_cand0 = nullptr, *tile_n = nullptr;   // the handle's tile table
+    int n_pos = 0;                      // group positions per instance: max_tiles / GROUP_TILES of the batch
 };
 
 // The scenarios (planner constants + reference path) of a plan launch.  A batch on ONE scenario passes that scenario's
@@ -109,7 +119,8 @@ struct PathSet {
 
 // every launcher returns 0 or the hipError_t of the launch
 int launch_frenet_state(const DevParams *P, const PathSet &ps, const InstDesc *desc, InstState *state, int n_inst,
-                        MetaImport imp, NanScan scan, int32_t *inst_done, hipStream_t st);
+                        MetaImport imp, NanScan scan, int32_t *inst_done, hipStream_t st,
+                        GroupHeadOut gh = GroupHeadOut());
 // n_ext: most horizons + brake-ladder entries of a scenario of the batch (sizes k_cull's per-horizon tables in LDS)
 int launch_cull(const DevParams *P, const InstDesc *desc, const InstState *state, int n_inst, int n_total, int n_ext,
                 const PathSet &ps, const void *static_xy, const void *dyn_xy, int dtype, EntryArrays e, TileTable tiles,

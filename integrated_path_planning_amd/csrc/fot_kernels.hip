@@ -94,19 +94,30 @@ __device__ __forceinline__ T load_const(const T *table, int i)
 extern __shared__ double s_spl[];
 constexpr int SPLINE_LDS_KNOTS = 512;
 
-__device__ __forceinline__ SplineView stage_spline(const SplineView &g, int lds_knots, double *s_spl = fot::s_spl)
+// (in two steps, for a caller that has more to put behind the same barrier: the copy, and the view of the copied path)
+__device__ __forceinline__ void stage_spline_copy(const SplineView &g, double *s_spl)
 {
-    if (g.n > lds_knots) return g;
     const double *src[9] = { g.s, g.ax, g.bx, g.cx, g.dx, g.ay, g.by, g.cy, g.dy };
     for (int i = threadIdx.x; i < 9 * g.n; i += blockDim.x) {
         const int a = i / g.n, j = i - a * g.n;
         s_spl[i] = src[a][j];
     }
-    __syncthreads();
+}
+
+__device__ __forceinline__ SplineView staged_spline_view(const SplineView &g, double *s_spl)
+{
     SplineView l = g;
     l.s = s_spl; l.ax = s_spl + g.n; l.bx = s_spl + 2 * g.n; l.cx = s_spl + 3 * g.n; l.dx = s_spl + 4 * g.n;
     l.ay = s_spl + 5 * g.n; l.by = s_spl + 6 * g.n; l.cy = s_spl + 7 * g.n; l.dy = s_spl + 8 * g.n;
     return l;
+}
+
+__device__ __forceinline__ SplineView stage_spline(const SplineView &g, int lds_knots, double *s_spl = fot::s_spl)
+{
+    if (g.n > lds_knots) return g;
+    stage_spline_copy(g, s_spl);
+    __syncthreads();
+    return staged_spline_view(g, s_spl);
 }
 
 // refine_nearest (fot_math.hpp), three rounds per evaluation.  A round compares the distances at s - ds, s, s + ds and
@@ -257,7 +268,8 @@ __device__ __forceinline__ ScanBest block_argmin(ScanBest b, ScanBest *s_best)
 // instances) one part of the NaN scan of an instance's tensor.  `sp`: the reference path, staged by the caller.
 __device__ __forceinline__ void frenet_state_block(const DevParams *__restrict__ Pp, const SplineView &sp, const InstDesc *desc,
                                                    InstState *__restrict__ state, int n_inst, const MetaImport &imp,
-                                                   const NanScan &scan, int32_t *__restrict__ inst_done, int block)
+                                                   const NanScan &scan, int32_t *__restrict__ inst_done, int block,
+                                                   const GroupHeadOut &gh)
 {
     __shared__ ScanBest s_best[FRENET_WG / WAVE];
     __shared__ InstDesc s_desc;                                   // the descriptor being worked on, read once
@@ -345,15 +357,34 @@ __device__ __forceinline__ void frenet_state_block(const DevParams *__restrict__
                 ok = frenet_state_at(sp, D.ego, best_s, fr, ref);
             }
         }
+        const int nb = (ok && fr[1] > 0.1) ? P.n_brake : 0;       // BRAKE_MIN_SPEED gate
+        const int n_cand = ok ? D.n_grid + nb : 0;
         if (tid == 0) {
             if (inst_done) inst_done[inst] = 0;                   // tiles of this instance evaluated so far (tile_done)
             InstState &S = state[inst];
             for (int i = 0; i < 6; ++i) { S.frenet0[i] = ok ? fr[i] : NAN; S.ref0[i] = ok ? ref[i] : NAN; }
             S.new_prev_s = new_prev_s;
             S.c2f_ok = ok ? 1 : 0;
-            const int nb = (ok && fr[1] > 0.1) ? P.n_brake : 0;   // BRAKE_MIN_SPEED gate
             S.n_brake = nb;
-            S.n_cand = ok ? D.n_grid + nb : 0;
+            S.n_cand = n_cand;
+        }
+        // The group headers of the instance (GroupHead): one lane per (position, profile) -- the first lane of a
+        // position also takes what is one value per group, the first GROUP_TILES lanes a tile each.  Every position of
+        // the batch gets at least its `present` word: the table outlives the call.
+        if (gh.heads) {
+            for (int t = tid; t < gh.n_pos * GROUP_MAX_PROFILES; t += FRENET_WG) {
+                const int pos = t / GROUP_MAX_PROFILES, p = t - pos * GROUP_MAX_PROFILES;
+                GroupHead &H = gh.heads[(int64_t)inst * gh.n_pos + pos];
+                GroupStage G;
+                const int32_t kind = group_head_stage(P, D, fr, ok ? 1 : 0, n_cand, gh.tile_cand0, gh.tile_n, pos, G);
+                if (kind != GROUP_HEAD_FULL) {
+                    if (p == 0) group_head_none(kind, G, H);
+                    continue;
+                }
+                if (p == 0) group_head_common(P, D, fr, G, H);
+                if (p < GROUP_TILES) group_head_tile(P, D, fr, n_cand, gh.tile_cand0, gh.tile_n, G, p, H);
+                group_head_profile(P, D, fr, G, p, H);
+            }
         }
         carry_prev_s = new_prev_s;
         chained = true;
@@ -363,7 +394,7 @@ __device__ __forceinline__ void frenet_state_block(const DevParams *__restrict__
 __global__ void __launch_bounds__(FRENET_WG)
 k_frenet_state(const DevParams *__restrict__ Pp, SplineView sp_hbm, const SplineView *__restrict__ sp_table, int mixed,
                int lds_knots, const InstDesc *desc, InstState *__restrict__ state, int n_inst, MetaImport imp,
-               NanScan scan, int32_t *__restrict__ inst_done)
+               NanScan scan, int32_t *__restrict__ inst_done, GroupHeadOut gh)
 {
     SplineView sp = sp_hbm;
     if ((int)blockIdx.x < n_inst) {                              // (the scan blocks never look at the path)
@@ -374,7 +405,7 @@ k_frenet_state(const DevParams *__restrict__ Pp, SplineView sp_hbm, const Spline
         }
         sp = stage_spline(sp_hbm, lds_knots);
     }
-    frenet_state_block(Pp, sp, desc, state, n_inst, imp, scan, inst_done, (int)blockIdx.x);
+    frenet_state_block(Pp, sp, desc, state, n_inst, imp, scan, inst_done, (int)blockIdx.x, gh);
 }
 
 // ---------------------------------------------------------------------------
@@ -476,7 +507,8 @@ struct EvalKernArgs {
     const DevParams *Pp; SplineView sp; const InstDesc *desc; const InstState *state;
     int row_budget, lds_knots, ablate, n_inst, max_tiles;
     const SplineView *sp_table; int mixed;           // a mixed batch: Pp + desc[inst].scen, sp_table[desc[inst].scen] (PathSet)
-    const int32_t *tile_cand0, *tile_n;
+    const int32_t *tile_cand0;
+    const GroupHead *heads;                          // the grouped kernels' headers (TileTable::heads)
     const TileStep *wave_rng; const f2 *ent32; const d2 *ent64; const uint8_t *ent_sid;
     double *cand_cost; uint8_t *cand_status; uint16_t *cand_keep;   // per candidate: for fot_debug_candidates only
     TilePart *parts;                                 // per tile: what its wave found (tile_done)
@@ -676,7 +708,7 @@ __host__ __device__ constexpr int eval_wave_doubles(int row_budget)
 // doubles of LDS of a group's shared table (k_evaluate_group)
 __host__ __device__ constexpr int eval_group_doubles()
 {
-    return GROUP_ROWS * ROW_FIELDS + GROUP_MAX_PROFILES * LONINFO_DOUBLES + GROUP_MAX_PROFILES / 2;
+    return GROUP_ROWS * ROW_FIELDS + (int)(sizeof(GroupHead) / sizeof(double));   // rows | the group's header
 }
 // A tile cut into time segments (k_evaluate_split): what a later segment hands to the wave of segment 0, per lane
 constexpr int SEG_MAX = 4;
@@ -752,14 +784,47 @@ __device__ __forceinline__ void wave_lds_fence()
     __builtin_amdgcn_wave_barrier();
 }
 
+// What a tile's wave leaves behind, every lane of it: the candidates' final statuses (stop-distance filter included,
+// frenet_planner.py:307-324) in the candidate arrays and, in tp, what the selection needs of the tile: the histogram of
+// the statuses and the cheapest 'ok' candidate (lowest index among equals)
+__device__ __forceinline__ void tile_results(const DevParams &P, const InstDesc &D, const StagedTab &tab, const LonInfo &L,
+                                             const double *q, SegState &g, bool hit, bool has_cand, int64_t slot, int cand0,
+                                             int lane, TilePart &tp)
+{
+    int st_final = FOT_ST_DROPPED;
+    ScanBest mine = { INFINITY, -1 };
+    int my_keep = 0;
+    if (has_cand) {
+        CandResult r;
+        {
+            LonInfo Lf = *tab.info;                              // (read again here: not carried through the walk)
+            Lf.n_t = L.n_t;
+            finish_candidate(P, D, Lf, tab, q, g, hit, r);
+        }
+        st_final = final_status(r.status, r.v_last, r.travel, D.max_stop);
+        const EvalKernArgs &KA = eval_kernargs();
+        KA.cand_cost[slot] = r.cost;
+        KA.cand_status[slot] = (uint8_t)st_final;
+        KA.cand_keep[slot] = (uint16_t)r.keep;
+        my_keep = r.keep;
+        if (st_final == FOT_ST_OK) { mine.dist = r.cost; mine.idx = cand0 + lane; }
+    }
+    {
+        const ScanBest best = wave_argmin(mine);                 // every lane of the wave is here
+        tp.cost = best.dist; tp.idx = best.idx;
+        tp.keep = __builtin_amdgcn_readfirstlane(__shfl(my_keep, best.idx >= 0 ? best.idx - cand0 : 0, WAVE));
+#pragma unroll
+        for (int c = 0; c < 8; ++c) tp.cnt[c] = __popcll(__ballot(st_final == c));
+    }
+}
+
 // One tile: rows of its profiles into LDS, then one candidate per lane.
 //   TILE_WAVE   the wave owns the tile and its slice of LDS (rows_base).
 //   TILE_SPLIT  the workgroup's n_sub waves share the tile -- they build the rows together, wave `sub` walks the time
 //               steps [sub, sub + 1) * ceil(n_loop / n_sub) of every candidate, and wave 0 merges the segments
 //               (seg_merge) through `s_part`.
-//   TILE_GROUP  the workgroup's GROUP_TILES waves take the tiles grp_tile0 + sub of one group (fot_math.hpp): they
-//               build the rows of ALL the group's profiles together, each walks its own tile.
-enum { TILE_WAVE = 0, TILE_SPLIT = 1, TILE_GROUP = 2 };
+// (The grouped cut has its own form, evaluate_group_tile below.)
+enum { TILE_WAVE = 0, TILE_SPLIT = 1 };
 template <int MODE, bool LEAN>
 __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc,
                                               const InstState *__restrict__ state,
@@ -767,9 +832,9 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
                                               const TileStep *__restrict__ wave_rng, const f2 *__restrict__ ent32,
                                               const EvalKernArgs &a, const SplineView &sp_lds,
                                               double *my_rows, int inst, int tile, int lane, int tl_tag, TilePart &tp,
-                                              int sub = 0, int n_sub = 1, double *s_part = nullptr, int grp_tile0 = 0)
+                                              int sub = 0, int n_sub = 1, double *s_part = nullptr)
 {
-    constexpr bool SPLIT = MODE == TILE_SPLIT, GROUP = MODE == TILE_GROUP;
+    constexpr bool SPLIT = MODE == TILE_SPLIT;
     const int seg = SPLIT ? sub : 0, n_seg = SPLIT ? n_sub : 1;
     const DevParams &P = *Pp;
     const InstDesc &D = desc[inst];
@@ -777,22 +842,17 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
     const int n_total = P.n_total;
     const int cand0 = tile_cand0[D.shape_off + tile];
     int n = tile_n[D.shape_off + tile];
-    // candidates whose profiles are staged in this slice: the tile's own, or the whole group's
+    // candidates whose profiles are staged in this slice: the tile's own
     int stage_c0 = cand0, stage_c1 = cand0 + n;                  // [first, one past the last)
-    if constexpr (GROUP) {
-        stage_c0 = tile_cand0[D.shape_off + grp_tile0];
-        stage_c1 = tile_cand0[D.shape_off + grp_tile0 + GROUP_TILES - 1] + tile_n[D.shape_off + grp_tile0 + GROUP_TILES - 1];
-    }
-    if constexpr (!GROUP) { if (n <= 0) return; }               // (a padding tile of the grouped cut)
+    if (n <= 0) return;                                          // (a padding tile of the grouped cut)
     if (!S.c2f_ok || stage_c0 >= S.n_cand) return;              // (the brake ladder of a standing ego) -- the whole workgroup
     if (stage_c1 > S.n_cand) stage_c1 = S.n_cand;
     if (cand0 + n > S.n_cand) n = S.n_cand - cand0 > 0 ? S.n_cand - cand0 : 0;
 #ifdef FOT_TIMELINE
     const uint64_t t_blk = __builtin_amdgcn_s_memrealtime();
 #endif
-    constexpr int PROF_CAP = GROUP ? GROUP_MAX_PROFILES : TILE_MAX_PROFILES;
-    LonInfo *s_info = (LonInfo *)(my_rows + (GROUP ? GROUP_ROWS : a.row_budget) * ROW_FIELDS);
-    int *s_row0 = (int *)(s_info + PROF_CAP);
+    LonInfo *s_info = (LonInfo *)(my_rows + a.row_budget * ROW_FIELDS);
+    int *s_row0 = (int *)(s_info + TILE_MAX_PROFILES);
     // staged profiles: of the first .. last staged candidate (slots grow with the candidate index)
     const int slot_lo = decode_candidate(P, D, S.frenet0, stage_c0).lon_slot;
     const int n_stage = decode_candidate(P, D, S.frenet0, stage_c1 - 1).lon_slot - slot_lo + 1;
@@ -826,7 +886,6 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
         r[4] = ls.cos_r; r[5] = ls.sin_r; r[6] = ls.kr; r[7] = ls.dkr; r[8] = ls.inv_sd;
     }
     lds_fence();
-    if constexpr (GROUP) { if (n <= 0) return; }                // (a padding tile, or one past a standing ego's lattice)
     // the time steps this tile needs: the longest of its OWN profiles
     {
         const int own_lo = decode_candidate(P, D, S.frenet0, cand0).lon_slot - slot_lo;
@@ -975,6 +1034,137 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
 #pragma unroll
         for (int c = 0; c < 8; ++c) tp.cnt[c] = __popcll(__ballot(st_final == c));
     }
+#ifdef FOT_TIMELINE
+    tl_rows = (uint64_t)__shfl((unsigned long long)tl_rows, 0);
+    if (tl_wave < 16384 && lane == 0) {
+        g_timeline[tl_wave * 4 + 0] = t_blk; g_timeline[tl_wave * 4 + 1] = t_wave;
+        g_timeline[tl_wave * 4 + 2] = __builtin_amdgcn_s_memrealtime();
+        g_timeline[tl_wave * 4 + 3] = (uint64_t)(uint32_t)tl_chunks | ((uint64_t)(uint32_t)tl_tag << 32);
+        g_shader_clock[tl_wave * 2 + 0] = c_wave; g_shader_clock[tl_wave * 2 + 1] = __builtin_amdgcn_s_memtime();
+        g_row_wait[tl_wave] = tl_rows;
+        g_phase[tl_wave * 4 + 0] = s_tl_entry[0]; g_phase[tl_wave * 4 + 1] = s_tl_entry[1];
+        g_phase[tl_wave * 4 + 2] = t_info; g_phase[tl_wave * 4 + 3] = t_loop_end;
+    }
+#endif
+}
+
+// The same for the grouped cut (fot_math.hpp): the workgroup's GROUP_TILES waves take the tiles of one group, wave `sub`
+// the tile `tile`; they build the rows of ALL the group's profiles together, each walks its own tile.  Nothing is derived here
+// that no lane decides: it comes out of the group's header (GroupHead, built by k_frenet_state), which the caller has put
+// into LDS behind the rows, all waves behind a barrier.  The per-lane set-up is issued BEFORE the rows are built -- it
+// reads none -- so that its loads (the step ranges, the horizon's matrices) and integer divisions run under the build.
+template <bool LEAN>
+__device__ __forceinline__ void evaluate_group_tile(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc,
+                                                    const TileStep *__restrict__ wave_rng, const f2 *__restrict__ ent32,
+                                                    const EvalKernArgs &a, const SplineView &sp_lds, double *my_rows,
+                                                    int inst, int tile, int sub, int lane, int tl_tag, TilePart &tp, bool full)
+{
+    if (!full) return;                                           // (GROUP_HEAD_EMPTY: the whole workgroup)
+    const DevParams &P = *Pp;
+    const InstDesc &D = desc[inst];                             // (an address: read by the rare branches and behind the loop)
+    const GroupHead *head = (const GroupHead *)(my_rows + GROUP_ROWS * ROW_FIELDS);
+    const auto uni = [](const int32_t &v) { return __builtin_amdgcn_readfirstlane(v); };   // wave-uniform: a scalar register
+    const LonInfo *info_tab = head->info;
+    const int *row0_tab = head->row0;
+    const int n_total = uni(head->n_total), total_rows = uni(head->total_rows), slot_lo = uni(head->slot_lo);
+    const int cand0 = uni(head->t_cand0[sub]), n = uni(head->t_n[sub]), n_loop = uni(head->t_n_loop[sub]);
+    const int inst_tile0 = uni(head->tile0), ent_cap = uni(head->ent_cap);
+#ifdef FOT_TIMELINE
+    const uint64_t t_blk = __builtin_amdgcn_s_memrealtime(), t_info = t_blk;
+#endif
+    // lane l holds the strip range of time step l (read back with v_readlane): loaded while every lane of the wave is
+    // still active, lanes without a candidate included
+    TileStep my_step = { 0u, 0.0f, 0.0f, 0u };
+    if (n > 0 && ent_cap != 0 && lane < n_total && !(a.ablate & 1))
+        my_step = wave_rng[(int64_t)(inst_tile0 + tile) * n_total + lane];
+    const uint32_t my_rng = my_step.rng;
+    const float my_thr_fatal = LEAN ? 0.0f : uni(head->max_viol) == 0 ? my_step.thr_sure : -1.0f;   // (LEAN: not read)
+    SegState g;
+    seg_init(g);
+    LonInfo L;
+    StagedTab tab;
+    LoopConst lc;
+    int64_t slot = 0;
+    double q[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };              // lateral quintic of the lane's candidate
+    // (lanes 0 .. n_total-1 enter both regions below, candidate or not: see evaluate_tile)
+    const bool has_cand = lane < n;
+    const bool walks = has_cand || lane < n_total;
+    if (n > 0 && walks) {
+        const int idx = cand0 + (has_cand ? lane : 0);           // candidate index inside the instance
+        slot = (int64_t)uni(head->cand_off) + idx;
+        const CandDecode cd = decode_candidate(*head, *head, head->frenet0, idx);
+        const int p = cd.lon_slot - slot_lo;
+        L = info_tab[p];
+        if (!has_cand) L.n_t = 0;
+        tab.lds_row0 = (int)(my_rows - s_lon) + row0_tab[p] * ROW_FIELDS;
+        tab.k_max = row0_tab[p + 1] - row0_tab[p] - 1;           // (profile_rows() of the slot, less one)
+        tab.info = info_tab + p;
+        lat_coeffs(head->frenet0, cd.di, cd.brake ? P.brake[cd.ti] : P.ti[cd.ti], q);
+        asm volatile("" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]));   // (vector registers: see evaluate_tile)
+        lc.dt = head->dt; lc.road_lim = head->road_lim;
+        lc.lim_speed = head->lim_speed; lc.lim_accel = head->lim_accel; lc.lim_curv = head->lim_curv; lc.lim_lat = head->lim_lat;
+        asm volatile("" : "+v"(lc.dt), "+v"(lc.lim_speed), "+v"(lc.lim_accel), "+v"(lc.lim_curv), "+v"(lc.lim_lat),
+                          "+v"(lc.road_lim));
+        tab.dt = lc.dt;
+    }
+#ifdef FOT_TIMELINE
+    uint64_t tl_rows = 0;
+    int tl_chunks = (int)(my_rng & 0xffffu) - (int)(my_rng >> 16);
+    for (int o = 32; o > 0; o >>= 1) tl_chunks += __shfl_xor(tl_chunks, o);
+#endif
+    // the rows of the group's profiles, all waves together
+    {
+        const double dt = head->dt, ego_x = head->ego_x, ego_y = head->ego_y;
+        for (int i = sub * WAVE + lane; i < total_rows; i += GROUP_TILES * WAVE) {
+            int p = 0;                                           // (row0 is total_rows from n_stage on; no read waits for another)
+#pragma unroll
+            for (int pp = 1; pp < GROUP_MAX_PROFILES; ++pp) p += i >= row0_tab[pp] ? 1 : 0;
+            const int k = i - row0_tab[p];
+            const LonInfo Lp = info_tab[p];
+            LonSample ls;
+            double sddd;
+            make_lon_sample(sp_lds, Lp, k, dt, ls, sddd);        // (k == n_eval of a brake profile: its hold state)
+            double *r = my_rows + (int64_t)i * ROW_FIELDS;
+            r[0] = ls.sd; r[1] = ls.sdd; r[2] = ls.rx - ego_x; r[3] = ls.ry - ego_y;   // (instance-local: see evaluate_tile)
+            r[4] = ls.cos_r; r[5] = ls.sin_r; r[6] = ls.kr; r[7] = ls.dkr; r[8] = ls.inv_sd;
+        }
+    }
+    __syncthreads();
+    if (n <= 0) return;                                          // (a padding tile, or one past a standing ego's lattice)
+#ifdef FOT_TIMELINE
+    const uint64_t t_wave = __builtin_amdgcn_s_memrealtime();
+    const uint64_t c_wave = __builtin_amdgcn_s_memtime();
+    const int tl_wave = inst_tile0 + tile;
+#endif
+    bool hit = false;
+    if (walks) {
+        // the walk's wave-uniform state is set up HERE: scalar values do not survive the join of the region above
+        FusedSink<LEAN> sink;
+        sink.Pp = Pp; sink.Dp = &D;
+        sink.my_rng = my_rng;
+        sink.my_thr = my_step.thr; sink.my_thr_sure = my_step.thr_sure; sink.thr = 0.0f; sink.thr_fatal = -1.0f;
+        sink.my_thr_fatal = my_thr_fatal;
+        sink.step_base = 0; sink.step_row = inst_tile0 + tile; sink.lane_id = lane;
+        const int64_t ent_off = ((int64_t)uni(((const int32_t *)&head->ent_off)[1]) << 32) | (uint32_t)uni(((const int32_t *)&head->ent_off)[0]);
+        sink.chunks = (const f2x8 *)(ent32 + ent_off);
+        sink.chunks_per_k = ent_cap / ENT_CHUNK;
+        sink.hit_mask = 0; sink.viol = 0; sink.hit = false; sink.n_chunks = 0; sink.c_lo = 0; sink.pf = 0;
+        sink.no_warm = (a.ablate & 2) != 0;
+        lc.n_circ_fp = 0;
+        if constexpr (!LEAN) {                                   // (LEAN: the single centre circle, never read)
+            lc.n_circ_fp = uni(head->n_circ_fp);
+            asm volatile("" : "+s"(lc.n_circ_fp));
+        }
+        evaluate_segment<LEAN>(P, lc, L, tab, q, 0, n_loop, sink, g);
+        hit = sink.hit;
+#ifdef FOT_TIMELINE
+        tl_rows = tab.t_rows;
+#endif
+    }
+#ifdef FOT_TIMELINE
+    const uint64_t t_loop_end = __builtin_amdgcn_s_memrealtime();
+#endif
+    tile_results(P, D, tab, L, q, g, hit, has_cand, slot, cand0, lane, tp);
 #ifdef FOT_TIMELINE
     tl_rows = (uint64_t)__shfl((unsigned long long)tl_rows, 0);
     if (tl_wave < 16384 && lane == 0) {
@@ -2332,14 +2522,14 @@ k_loop_score_truth(ReplayView rv, const int32_t *__restrict__ slot_of, FrameDev 
 #define FOT_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 int launch_frenet_state(const DevParams *P, const PathSet &ps, const InstDesc *desc, InstState *state, int n_inst,
-                        MetaImport imp, NanScan scan, int32_t *inst_done, hipStream_t st)
+                        MetaImport imp, NanScan scan, int32_t *inst_done, hipStream_t st, GroupHeadOut gh)
 {
     if (n_inst <= 0) return 0;
     const int lds_knots = ps.fit_knots(SPLINE_LDS_KNOTS);
     const int64_t grid = (int64_t)n_inst * (1 + (scan.flag ? scan.blocks_per_inst : 0));
     if (grid > 0x7fffffffLL) return (int)hipErrorInvalidConfiguration;
     k_frenet_state<<<(unsigned)grid, FRENET_WG, sizeof(double) * 9 * (size_t)lds_knots, st>>>(
-        P, ps.one, ps.table, ps.mixed, lds_knots, desc, state, n_inst, imp, scan, inst_done);
+        P, ps.one, ps.table, ps.mixed, lds_knots, desc, state, n_inst, imp, scan, inst_done, gh);
     FOT_LAUNCH_CHECK();
     return 0;
 }
@@ -2369,6 +2559,19 @@ int launch_cull(const DevParams *P, const InstDesc *desc, const InstState *state
     return 0;
 }
 
+// time segments per tile of a batch's evaluation (1: whole tiles)
+static int eval_segments_of(const TileTable &tiles)
+{
+    int n_seg = tiles.n_tiles <= 2304 ? SEG_MAX : 1;       // (scripts/segment_sweep.py: four segments win up to ~64 egos)
+    if (tiles.eval_segments >= 1 && tiles.eval_segments <= SEG_MAX) n_seg = tiles.eval_segments;
+    return n_seg;
+}
+
+bool evaluate_in_groups(const TileTable &tiles)
+{
+    return tiles.n_tiles > 0 && eval_segments_of(tiles) == 1 && tiles.grouped;
+}
+
 int launch_evaluate(const DevParams *P, const PathSet &ps, const InstDesc *desc, const InstState *state, int n_total,
                     int n_inst, TileTable tiles, EntryArrays e, CandArrays c, fot_result *out, int32_t *inst_done,
                     hipStream_t st)
@@ -2381,8 +2584,7 @@ int launch_evaluate(const DevParams *P, const PathSet &ps, const InstDesc *desc,
     //  * the grouped cut: one workgroup per group of four tiles (k_evaluate_group, four waves per SIMD);
     //  * the per-wave cut: four independent tiles per workgroup (k_evaluate, three waves per SIMD).
     // Each in its lean form (FusedSink) when the host found the launch eligible (tiles.lean: enqueue_lane).
-    int n_seg = tiles.n_tiles <= 2304 ? SEG_MAX : 1;       // (scripts/segment_sweep.py: four segments win up to ~64 egos)
-    if (tiles.eval_segments >= 1 && tiles.eval_segments <= SEG_MAX) n_seg = tiles.eval_segments;
+    const int n_seg = eval_segments_of(tiles);
     static const int force_wpw = getenv("FOT_EVAL_WPW") ? atoi(getenv("FOT_EVAL_WPW")) : 0;      // diagnostics
     int wpw = n_seg > 1 ? 1 : tiles.n_tiles >= 1024 ? EVAL_WG / WAVE : 1;
     if (n_seg == 1 && force_wpw >= 1 && force_wpw <= EVAL_WG / WAVE) wpw = force_wpw;
@@ -2396,16 +2598,18 @@ int launch_evaluate(const DevParams *P, const PathSet &ps, const InstDesc *desc,
     a.sp_table = ps.table; a.mixed = ps.mixed;
     a.row_budget = tiles.row_budget; a.lds_knots = lds_knots; a.ablate = ablate;
     a.n_inst = n_inst; a.max_tiles = tiles.max_tiles;
-    a.tile_cand0 = tiles.cand0; a.tile_n = tiles.n;
+    a.tile_cand0 = tiles.cand0;
     a.wave_rng = e.rng; a.ent32 = e.e32; a.ent64 = e.e64; a.ent_sid = e.sid;
     a.cand_cost = c.cost; a.cand_status = c.status; a.cand_keep = c.keep; a.parts = c.parts;
     a.out = out; a.inst_done = inst_done; a.done_flag = c.done_flag; a.done_seq = c.done_seq;
+    a.heads = tiles.heads;
     if (tiles.n_tiles <= 0) {
         k_select_only<<<(unsigned)n_inst, WAVE, 0, st>>>(P, desc, state, tiles.cand0, tiles.n, e.rng, e.e32, a);
     } else if (n_seg > 1) {
         (tiles.lean ? k_evaluate_split_lean : k_evaluate_split)<<<(unsigned)n_blocks, n_seg * WAVE, lds, st>>>(
             P, desc, state, tiles.cand0, tiles.n, e.rng, e.e32, a);
     } else if (tiles.grouped) {                                            // one workgroup per group of tiles
+        if (!tiles.heads) return (int)hipErrorInvalidValue;                // (evaluate_in_groups(): the caller builds them)
         const int per_q = (n_inst + N_XCD - 1) / N_XCD * (tiles.max_tiles / GROUP_TILES);
         const size_t g_lds = sizeof(double) * ((size_t)eval_group_doubles() + 9 * (size_t)lds_knots);
         (tiles.lean ? k_evaluate_group_lean : k_evaluate_group)<<<(unsigned)(per_q * N_XCD), GROUP_TILES * WAVE, g_lds, st>>>(

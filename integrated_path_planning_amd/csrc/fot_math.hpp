@@ -1413,7 +1413,9 @@ struct CandDecode {
     double di;             // lateral target offset
 };
 
-FOT_HD CandDecode decode_candidate(const DevParams &P, const InstDesc &D, const double *fr, int idx)
+// (P, D: anything that holds the lattice's counts under these names -- the parameter blocks, or a GroupHead for both)
+template <class PP, class DD>
+FOT_HD CandDecode decode_candidate(const PP &P, const DD &D, const double *fr, int idx)
 {
     CandDecode c;
     if (idx < D.n_grid) {
@@ -1430,6 +1432,108 @@ FOT_HD CandDecode decode_candidate(const DevParams &P, const InstDesc &D, const 
         c.di = fr[3];
     }
     return c;
+}
+
+// ---------------------------------------------------------------------------
+// group headers (GroupHead, fot_types.h): what the grouped evaluation kernels need before their first time step and
+// that no lane decides, derived once per instance.  In parts, so that k_frenet_state can hand them to different lanes;
+// build_group_head is all of them.  tile_cand0 / tile_n: the handle's tile table (TileTable).
+// ---------------------------------------------------------------------------
+static_assert(GROUP_HEAD_TILES == GROUP_TILES && GROUP_HEAD_PROFILES == GROUP_MAX_PROFILES, "GroupHead's array sizes");
+
+struct GroupStage {
+    int grp_tile0, slot_lo, n_stage;
+};
+
+// the group at position `pos` of the instance and the profiles it stages -> GROUP_HEAD_ABSENT / _EMPTY / _FULL
+FOT_HD int32_t group_head_stage(const DevParams &P, const InstDesc &D, const double *fr, int c2f_ok, int n_cand,
+                             const int32_t *tile_cand0, const int32_t *tile_n, int pos, GroupStage &G)
+{
+    const int n_groups = D.n_tiles / GROUP_TILES;
+    if (pos >= n_groups) return GROUP_HEAD_ABSENT;              // a shorter lattice than the batch's longest
+    G.grp_tile0 = (n_groups - 1 - pos) * GROUP_TILES;
+    // candidates whose profiles are staged: the whole group's, [first, one past the last)
+    const int stage_c0 = tile_cand0[D.shape_off + G.grp_tile0];
+    int stage_c1 = tile_cand0[D.shape_off + G.grp_tile0 + GROUP_TILES - 1] + tile_n[D.shape_off + G.grp_tile0 + GROUP_TILES - 1];
+    if (!c2f_ok || stage_c0 >= n_cand) return GROUP_HEAD_EMPTY; // (the brake ladder of a standing ego)
+    if (stage_c1 > n_cand) stage_c1 = n_cand;
+    // staged profiles: of the first .. last staged candidate (slots grow with the candidate index)
+    G.slot_lo = decode_candidate(P, D, fr, stage_c0).lon_slot;
+    G.n_stage = decode_candidate(P, D, fr, stage_c1 - 1).lon_slot - G.slot_lo + 1;
+    return GROUP_HEAD_FULL;
+}
+
+// a header without content: ABSENT, or EMPTY with the group's first tile
+FOT_HD void group_head_none(int32_t kind, const GroupStage &G, GroupHead &H)
+{
+    H.present = kind;
+    if (kind == GROUP_HEAD_EMPTY) H.grp_tile0 = G.grp_tile0;
+}
+
+// everything that is one value per group, and the row offsets
+FOT_HD void group_head_common(const DevParams &P, const InstDesc &D, const double *fr, const GroupStage &G, GroupHead &H)
+{
+    H.present = GROUP_HEAD_FULL;
+    H.slot_lo = G.slot_lo; H.n_stage = G.n_stage; H.grp_tile0 = G.grp_tile0;
+    int total_rows = 0;
+    for (int p = 0; p <= GROUP_MAX_PROFILES; ++p) {
+        H.row0[p] = total_rows;
+        if (p < G.n_stage) total_rows += profile_rows(P, D, G.slot_lo + p);
+    }
+    H.total_rows = total_rows;
+    const LoopConst lc = loop_const(P, D);
+    H.n_total = P.n_total; H.n_circ_fp = lc.n_circ_fp;
+    H.cand_off = D.cand_off; H.tile0 = D.tile0; H.ent_cap = D.ent_cap; H.max_viol = D.max_viol;
+    H.n_grid = D.n_grid; H.n_tv = D.n_tv; H.n_di = P.n_di; H.n_side = P.n_side; H.n_ti = P.n_ti;
+    H.ent_off = D.ent_off;
+    H.d_road_w = P.d_road_w; H.dt = lc.dt; H.road_lim = lc.road_lim;
+    H.lim_speed = lc.lim_speed; H.lim_accel = lc.lim_accel; H.lim_curv = lc.lim_curv; H.lim_lat = lc.lim_lat;
+    H.ego_x = D.ego.x; H.ego_y = D.ego.y;
+    for (int i = 0; i < 6; ++i) H.frenet0[i] = fr[i];
+}
+
+// tile t of the group: its candidates below n_cand, its own profiles and the time steps the longest of them needs
+FOT_HD void group_head_tile(const DevParams &P, const InstDesc &D, const double *fr, int n_cand,
+                            const int32_t *tile_cand0, const int32_t *tile_n, const GroupStage &G, int t, GroupHead &H)
+{
+    const int cand0 = tile_cand0[D.shape_off + G.grp_tile0 + t];
+    int n = tile_n[D.shape_off + G.grp_tile0 + t];
+    if (cand0 + n > n_cand) n = n_cand - cand0 > 0 ? n_cand - cand0 : 0;
+    int own_lo = 0, own_hi = -1, n_loop = 0;
+    if (n > 0) {                                                // (else: a padding tile, or one past a standing ego's lattice)
+        own_lo = decode_candidate(P, D, fr, cand0).lon_slot - G.slot_lo;
+        own_hi = decode_candidate(P, D, fr, cand0 + n - 1).lon_slot - G.slot_lo;
+        for (int p = own_lo; p <= own_hi; ++p) {
+            const int nt = profile_info(P, D, fr, G.slot_lo + p, false).n_t;
+            n_loop = nt > n_loop ? nt : n_loop;
+        }
+    }
+    H.t_cand0[t] = cand0; H.t_n[t] = n; H.t_n_loop[t] = n_loop; H.t_own_lo[t] = own_lo; H.t_own_hi[t] = own_hi;
+}
+
+// staged profile p of the group (zero behind the last one)
+FOT_HD void group_head_profile(const DevParams &P, const InstDesc &D, const double *fr, const GroupStage &G, int p,
+                               GroupHead &H)
+{
+    LonInfo L;
+    if (p < G.n_stage) {
+        L = profile_info(P, D, fr, G.slot_lo + p, true);
+    } else {
+        L.a0 = L.a1 = L.a2 = L.a3 = L.a4 = L.Js = L.sd_last = L.T = 0.0;
+        L.n_t = 0; L.n_eval = 0;
+    }
+    H.info[p] = L;
+}
+
+FOT_HD void build_group_head(const DevParams &P, const InstDesc &D, const double *fr, int c2f_ok, int n_cand,
+                             const int32_t *tile_cand0, const int32_t *tile_n, int pos, GroupHead &H)
+{
+    GroupStage G;
+    const int32_t kind = group_head_stage(P, D, fr, c2f_ok, n_cand, tile_cand0, tile_n, pos, G);
+    if (kind != GROUP_HEAD_FULL) { group_head_none(kind, G, H); return; }
+    group_head_common(P, D, fr, G, H);
+    for (int t = 0; t < GROUP_TILES; ++t) group_head_tile(P, D, fr, n_cand, tile_cand0, tile_n, G, t, H);
+    for (int p = 0; p < GROUP_MAX_PROFILES; ++p) group_head_profile(P, D, fr, G, p, H);
 }
 
 // yaw of the selected path's samples.  A real function on the device, like yaw_step_over_cap and for the same reason:

@@ -109,4 +109,36 @@ struct LonInfo {
     int32_t n_eval;                      // samples on the polynomial (== n_t unless brake)
 };
 
+// What a workgroup of the grouped evaluation kernels needs before its first time step and that no lane of it decides:
+// one record per (instance, position of the group in the evaluation's launch order), built by k_frenet_state once the
+// instance's Frenet state is known (fot_math.hpp build_group_head), fetched by the workgroup with one coalesced load.
+// Position `pos` holds the instance's group n_groups - 1 - pos (the last group is evaluated first).
+constexpr int GROUP_HEAD_TILES = 4, GROUP_HEAD_PROFILES = 16;   // == GROUP_TILES, GROUP_MAX_PROFILES (fot_math.hpp)
+enum : int32_t {
+    GROUP_HEAD_ABSENT = 0,               // no such group in this instance's lattice: no workgroup's business
+    GROUP_HEAD_EMPTY = 2,                // its tiles exist but hold nothing to evaluate (no Frenet state, or the group
+                                         // lies past n_cand: the brake ladder of a standing ego): they only count as done
+    GROUP_HEAD_FULL = 1
+};
+struct alignas(128) GroupHead {
+    int32_t present;                     // GROUP_HEAD_ABSENT / _EMPTY / _FULL; ABSENT: the only word that is written
+    int32_t grp_tile0;                   // first tile of the group, inside the instance; EMPTY: nothing else is written
+    int32_t slot_lo, n_stage;            // staged profiles: slots [slot_lo, slot_lo + n_stage)
+    int32_t total_rows;                  // rows of all staged profiles
+    int32_t n_total, n_circ_fp;          // P.n_total, loop_const().n_circ_fp
+    int32_t cand_off, tile0, ent_cap, max_viol;         // of the InstDesc
+    int32_t n_grid, n_tv, n_di, n_side, n_ti;           // what decode_candidate reads
+    int32_t row0[GROUP_HEAD_PROFILES + 1];              // first row of profile p; total_rows from n_stage on
+    int32_t t_cand0[GROUP_HEAD_TILES], t_n[GROUP_HEAD_TILES];   // per tile: first candidate, candidates below n_cand
+    int32_t t_n_loop[GROUP_HEAD_TILES];                 // time steps: the longest of the tile's own profiles
+    int32_t t_own_lo[GROUP_HEAD_TILES], t_own_hi[GROUP_HEAD_TILES];   // own profiles, relative to slot_lo (t_n > 0)
+    int64_t ent_off;
+    double d_road_w, dt, road_lim;       // of the DevParams
+    double lim_speed, lim_accel, lim_curv, lim_lat;     // of the InstDesc
+    double ego_x, ego_y;
+    double frenet0[6];
+    LonInfo info[GROUP_HEAD_PROFILES];   // profile_info(.., slot_lo + p, true); zero from n_stage on
+};
+static_assert(sizeof(GroupHead) % 128 == 0 && sizeof(GroupHead) == 1536, "whole 128-byte lines");
+
 }  // namespace fot
