@@ -804,6 +804,49 @@ int fot_loop_scores_enable(fot_handle *h, int32_t on);
 int fot_loop_score_summaries(fot_handle *h, int32_t n_slots, fot_loop_summary *out);
 int fot_loop_last_best_sample(fot_handle *h, int32_t n_slots, int32_t *out);
 
+/* ---- planning on the representative prediction sample (the reference's default: distribution_aware_planning = False,
+ *      integrated_simulator.py:447-455, 503-513), the samples never leaving HBM ----
+ * fot_loop_plan_sample(h, mode): what the requests of a lock step plan against when its frame carries a distribution
+ * (fot_loop_frame.dist_raw; the sampled step of a fot_loop_run with a sampler):
+ *   FOT_LOOP_PLAN_DISTRIBUTION    the whole distribution under the chance constraint (the default)
+ *   FOT_LOOP_PLAN_REPRESENTATIVE  every episode's representative sample (predict_single_best: the sample closest to the
+ *                                 sample mean over the episode's own pedestrians, the selection of fot_loop_scores_enable),
+ *                                 as FOT_DYN_SINGLE with S = 1; chance_epsilon plays no part, collision_margin_inflation
+ *                                 applies as in any single-sample plan.  The escalation levels plan against the same block.
+ * The frame is resampled into the distribution blocks as before (fot_loop_prediction_scores and the scores of a resident
+ * loop read them unchanged); the selection and one more kernel follow on the same stream and leave, per episode, ONE block
+ * [P_e][n_dense + 1][2] whatever the reference's conditional prepend decides:
+ *   prepended      [current, dense[0], ..., dense[n_dense - 1]]
+ *   not prepended  [dense[0], ..., dense[n_dense - 1], dense[n_dense - 1]]     (the last entry once more)
+ * The episode prepends unless |dense[0] - current| <= 1e-8 + 1e-5 |current| holds for all its pedestrians on both axes
+ * (np.allclose; a NaN makes it false).  The second form is the same obstacle as the reference's [P_e][n_dense][2]: the
+ * collision check clips its time index to the last entry (frenet_planner.py:1226-1227), and a track's min / max box and
+ * the NaN-track rule do not see a repeated entry.  dist_S = 1 selects sample 0 and goes through the same rule.  A frame
+ * without dist_raw (observer not ready, constant velocity) behaves as in mode 0.
+ * Allowed after fot_loop_begin; with a replay set only before the run's first step.  fot_loop_begin* resets the mode to
+ * FOT_LOOP_PLAN_DISTRIBUTION.  With the mode on fot_loop_last_best_sample answers for stepwise loops too (the slots of
+ * fot_loop_begin; fot_loop_plan's episode i is slot i).  What the mode needs is allocated when it is switched on or grows
+ * with the frames; a loop that never switches it on launches and allocates nothing new.
+ * FOT_ERR_INVALID (nothing changed): unknown mode; no loop begun; after a resident run's first step.
+ * FOT_ERR_UNSUPPORTED (nothing changed): a loop begun with fot_loop_begin_scenarios.
+ *
+ * fot_loop_run_best_samples(h, n_steps, n_slots, out): fot_loop_last_best_sample for every lock step of the most recent
+ * fot_loop_run call, out[k][slot], k < n_steps = that call's return value -- a run of many steps per call keeps what each
+ * step planned on.  FOT_ERR_INVALID: no replay set, the mode is off, n_steps or n_slots differ from the call's.
+ *
+ * fot_debug_loop_block (tests): the block the most recent frame's `episode` (index in the frame) plans against, copied
+ * to xy[cap_points][2], with its pedestrians *P and time entries *T.  Mode 1 with a distribution: the [P][n_dense + 1][2]
+ * block above and *prepended = 1 / 0 (-1 without pedestrians); otherwise the episode's block of the handle's tensor
+ * ([dist_S][P][T][2] of a distribution) and *prepended = -1.  Synchronous.  FOT_ERR_INVALID: no frame, episode out of
+ * range, a block of more than cap_points points (*P and *T are set).
+ * Additions only: FOT_ABI_VERSION and the words of fot_abi_info stay as they are. */
+#define FOT_LOOP_PLAN_DISTRIBUTION 0
+#define FOT_LOOP_PLAN_REPRESENTATIVE 1
+int fot_loop_plan_sample(fot_handle *h, int32_t mode);
+int fot_loop_run_best_samples(fot_handle *h, int32_t n_steps, int32_t n_slots, int32_t *out);
+int fot_debug_loop_block(fot_handle *h, int32_t episode, int32_t cap_points, double *xy, int32_t *P, int32_t *T,
+                         int32_t *prepended);
+
 /* Host utility (no GPU): the first kmax samples of the 15 path arrays of records[index[i]], i < n, as one dense block
  * out[15][n][kmax] in fot_result array order (t .. c) -- what a history keeps of a step's records. */
 int fot_gather_paths(const fot_result *records, int32_t n, const int32_t *index, int32_t kmax, double *out);

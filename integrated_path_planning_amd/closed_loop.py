@@ -223,6 +223,7 @@ class _ResidentStep(dict):
         super().__init__()
         self._src = (loop, out, k, t, keep_paths)
         self.window_frames, self.lock_step = None, -1                # set by a loop whose sampler predicted at this step
+        self.best = None                                             # ... and planned on the representative sample
 
     def _fill(self) -> None:
         if self._src is None:
@@ -249,6 +250,8 @@ class _ResidentStep(dict):
                 assert self.window_frames[-1] == int(o["obs_last_frame"][k])    # count is the lock step's index)
                 window = np.stack([frame("trajectories", f) for f in self.window_frames], axis=0).astype(np.float32)
                 pred_src = ("sgan", window, sel, np.full(n, self.lock_step, np.int64), o32, float(o["staleness"][k]))
+                if self.best is not None:                             # the sample the device chose and planned on
+                    pred_src = pred_src + (self.best[sel].astype(np.int64),)
         if keep_paths:
             paths = {f: o["paths"][k, j][sel] for j, f in enumerate(_abi.PATH_FIELDS)}
         else:
@@ -449,7 +452,7 @@ class BatchedClosedLoop:
     def __init__(self, config, ped_tracks: Sequence[np.ndarray], ego_initial_states: Optional[Sequence] = None,
                  device: int = -1, engine=None, resampler=None, sample_source=None, fused: Optional[bool] = None,
                  device_samples: bool = False, resident: bool = False, summaries: bool = False,
-                 prediction_scores: bool = False):
+                 prediction_scores: bool = False, plan_on_representative_sample: bool = False):
         """sample_source: the multi-sample predictor in front of the planner -- a callable
         ``(obs_last [P, 2], obs_prev [P, 2]) -> raw samples [S, pred_len, P, 2]`` at the predictor's own time step
         (a source with the attribute ``needs_history = True``, such as ``prediction.SganSampler``, is called with the
@@ -484,6 +487,12 @@ class BatchedClosedLoop:
         ``prediction_metrics()`` folds the records as the reference's ``calculate_aggregate_metrics`` does.  The element
         type of the planner's tensor is the one scored (float64 here; a float32 tensor would give the metrics of the
         rounded samples).
+        plan_on_representative_sample: the reference's default (``distribution_aware_planning`` unset) with the samples
+        staying in HBM: ``device_samples=True`` is then accepted without ``distribution_aware_planning`` -- the one-call
+        step, or ``resident=True`` with a counter-seeded ``SganSampler``.  The library chooses every episode's
+        representative sample on the device, lays it out as one fixed-shape [P, n_dense + 1, 2] block (the conditional
+        prepend decided there, ``fot_loop_plan_sample``) and plans against it; a step's ``pred`` in the history is the
+        sample the device chose.  Not together with ``distribution_aware_planning``.
         fused: True = the lock step behind one library call (fot_loop_step), False = five separate calls with the
         prediction through the host, None = one call where the engine and the predictor allow it."""
         if fused not in (None, False, True):
@@ -540,6 +549,13 @@ class BatchedClosedLoop:
             raise NotImplementedError("the Social-GAN / LSTM networks are not part of this build (SURVEY 8 f1): hand "
                                       "their samples in through sample_source, or use prediction_method='cv'")
         self.distribution_aware = bool(getattr(c, "distribution_aware_planning", False))
+        self._plan_rep = bool(plan_on_representative_sample)
+        if self._plan_rep and self.distribution_aware:
+            raise ValueError("plan_on_representative_sample plans against ONE sample of the distribution: not together "
+                             "with distribution_aware_planning (choose one of the two)")
+        if self._plan_rep and not device_samples:
+            raise ValueError("plan_on_representative_sample needs device_samples=True (a sample source handing its "
+                             "samples over on the host plans on the representative sample already)")
         if self.distribution_aware and sample_source is None:
             raise ValueError("distribution_aware_planning needs a multi-sample predictor (sample_source): the "
                              "constant-velocity predictor yields one sample")
@@ -570,7 +586,8 @@ class BatchedClosedLoop:
             raise ValueError("resident=True with a sampler takes one configuration (a scenario loop plans against no "
                              "distribution)")
         self._device_samples = bool(device_samples)
-        if self._device_samples and not (sample_source is not None and self.distribution_aware and engine is None and resampler is None):
+        if self._device_samples and not (sample_source is not None and (self.distribution_aware or self._plan_rep)
+                                         and engine is None and resampler is None):
             raise ValueError("device_samples needs a sample_source, distribution_aware_planning and the library's own engine")
         # the whole step behind ONE call (fot_loop_step: the episodes' state, the fail-safe machine and the retry loop live
         # in the handle, the prediction stays in HBM): the constant-velocity predictor -- or samples in device memory -- on
@@ -666,6 +683,8 @@ class BatchedClosedLoop:
                 self.engine.loop_set_sampler(sample_source.num_samples, sample_source.counter_seed, sample_source.noise_kind)
             if self._resident_scores:
                 self.engine.loop_scores_enable(True)
+        if self._plan_rep:
+            self.engine.loop_plan_sample(_abi.LOOP_PLAN_REPRESENTATIVE)
 
     def close(self) -> None:
         """Release the libfot handle (streams, workspace) now rather than at garbage collection."""
@@ -1063,13 +1082,16 @@ class BatchedClosedLoop:
         if isinstance(pred_src[0], str) and pred_src[0] == "sgan":
             # a resident sampler step: the window, the running slots and their step counts -- the library's noise and
             # samples once more, then as a stepwise step's
-            _, window, sel, steps, o32, stale = pred_src
+            _, window, sel, steps, o32, stale = pred_src[:6]
             raw = self.sample_source.sample(window, np.asarray(off, dtype=np.int32), slots=sel, steps=steps)
-            pred_src = ("dist", raw, o32, stale)
+            pred_src = ("dist", raw, o32, stale) + tuple(pred_src[6:])
         if isinstance(pred_src[0], str):                              # ("dist", raw samples in HBM, observations, staleness)
-            _, raw, o32, stale = pred_src
+            _, raw, o32, stale = pred_src[:4]
             raw_h = raw.detach().cpu().numpy().astype(np.float64)
             dist = self.resampler.process_prediction(raw_h, anchor_pos=o32[1].astype(np.float64), staleness=stale)
+            if len(pred_src) > 4:                                     # the sample the device chose and planned on, per episode
+                off = np.asarray(off)
+                return dist[np.repeat(np.maximum(pred_src[4], 0), off[1:] - off[:-1]), np.arange(dist.shape[1])]
             return dist[0] if raw_h.shape[0] == 1 else self._best_sample(dist, np.asarray(off))
         o32, stale = pred_src
         return self.resampler.predict_cv(o32, staleness=stale, float32_observations=True)
@@ -1128,6 +1150,8 @@ class BatchedClosedLoop:
         frame.pop("ego")
         o = self.engine.loop_step(frame, sel)
         t_plan = (time.perf_counter() - t0) / n
+        if self._plan_rep and pred_src is not None and isinstance(pred_src[0], str):
+            pred_src = pred_src + (self.engine.loop_last_best_sample()[sel].astype(np.int64),)   # what the step planned on
         rec, path_rec, keep = o["records"], o["record"].astype(np.int64), o["keep"].astype(np.int64)
         new_ego = o["ego"]
         self.ego[sel], self.jerk[sel] = new_ego, o["jerk"]
@@ -1208,6 +1232,8 @@ class BatchedClosedLoop:
             o["t_plan"] = wall / max(int(ran.sum()), 1)
             if first is None:
                 first = int(ran[0].sum())
+            # (planning on the representative sample: what every step of the call chose, for the history)
+            best = self.engine.loop_run_best_samples(done) if self._plan_rep else None
             for k in range(done):
                 self._steps.append(_ResidentStep(self, o, k, self.time, keep_paths))
                 self.time += self.dt
@@ -1216,6 +1242,8 @@ class BatchedClosedLoop:
                 if self._resident_sampler and self._frame_clock.is_ready:
                     self._steps[-1].window_frames = [int(f[0]) for f in self._frame_clock.history]
                     self._steps[-1].lock_step = len(self._steps) - 1
+                    if best is not None:
+                        self._steps[-1].best = best[k]
             self.frame += done
             took = np.flatnonzero(ran.any(axis=0))
             last = done - 1 - np.argmax(ran[::-1, took], axis=0)      # the last step of the call each slot ran

@@ -201,10 +201,24 @@ struct LoopReplay {
     }
 };
 
+// fot_loop_plan_sample: the requests plan against every episode's representative sample (fot_repsample.hpp).  Nothing
+// here is allocated before the mode is switched on; the tables grow with the loop's frames as dDyn does.
+struct LoopRep {
+    int mode = 0;                                // FOT_LOOP_PLAN_*
+    bool frame = false;                          // the most recent frame left planning blocks in dBlk (it carried a distribution)
+    int T = 0;                                   // their time entries: n_dense + 1
+    DevBuf dBlk, dBest, dDev, dPre;              // [rows][T][2] | int32[slots] | [slots][FOT_MAX_SAMPLES] | int32[episodes]
+    PinnedBuf hBest, hPre;                       // int32[slots] | int32[episodes of the frame]
+    std::vector<int32_t> last_best;              // [slots of fot_loop_begin] of the most recent lock step
+    std::vector<int32_t> run_best;               // [steps][slots] of the most recent fot_loop_run call (fot_loop_run_best_samples)
+    void release() { dBlk.release(); dBest.release(); dDev.release(); dPre.release(); hBest.release(); hPre.release(); }
+};
+
 // fot_loop_*: what one closed-loop step leaves behind for the step's later calls
 struct LoopState {
     LoopEpisodes ep;
     LoopReplay replay;
+    LoopRep rep;
     PinnedBuf hFrame, hObserve, hOut, hRec;  // frame inputs | fot_loop_observe's inputs | small outputs | records
     DevBuf dDyn, dStatic;                    // the prediction tensor; the static points, one copy per request
     std::vector<double> static_xy;           // host copy of the static points
@@ -232,7 +246,7 @@ struct LoopState {
     void release()
     {
         hFrame.release(); hObserve.release(); hOut.release(); hRec.release();
-        dDyn.release(); dStatic.release(); replay.release();
+        dDyn.release(); dStatic.release(); replay.release(); rep.release();
         dScenStatic.release(); dGather.release(); dSafScen.release(); hGather.release();
     }
 };
@@ -1295,6 +1309,35 @@ int ensure_scen_static(fot_handle *h, int n_req, hipStream_t st)
     return FOT_OK;
 }
 
+// FOT_LOOP_PLAN_REPRESENTATIVE: room for a frame of n_ep episodes on slots below n_slots with `rows` pedestrians and T time
+// entries per track.  (A block that grows is freed first, which waits for the device: nothing still reads the old one.)
+int rep_ensure(fot_handle *h, int n_slots, int n_ep, size_t rows, int T)
+{
+    LoopRep &Q = h->loop.rep;
+    const size_t ns = (size_t)std::max(n_slots, 1), ne = (size_t)std::max(n_ep, 1);
+    HIP_TRY(h, Q.dBlk.ensure(sizeof(double) * 2 * std::max<size_t>(rows, 1) * (size_t)T));
+    HIP_TRY(h, Q.dBest.ensure(sizeof(int32_t) * ns));
+    HIP_TRY(h, Q.dDev.ensure(sizeof(double) * ns * FOT_MAX_SAMPLES));
+    HIP_TRY(h, Q.dPre.ensure(sizeof(int32_t) * ne));
+    HIP_TRY(h, Q.hBest.ensure(sizeof(int32_t) * ns));
+    HIP_TRY(h, Q.hPre.ensure(sizeof(int32_t) * ne));
+    return FOT_OK;
+}
+
+// The planning blocks of the frame's n episodes behind their distribution blocks in dDyn (f: pos, ped0, blk): the
+// selection into the given tables (the mode's own, or the scores' where a resident loop scores too), then
+// k_loop_rep_block.  Enqueue only.
+int rep_enqueue(fot_handle *h, const int32_t *slot_of, const FrameDev &f, int n, int S, int n_dense, double *dev_tab,
+                int32_t *best_tab, int32_t *best_host, hipStream_t st)
+{
+    LoopState &L = h->loop;
+    LoopRep &Q = L.rep;
+    LAUNCH_TRY(h, launch_loop_best_sample(slot_of, f, L.dDyn.as<double>(), n, S, n_dense, dev_tab, best_tab, best_host, st));
+    LAUNCH_TRY(h, launch_loop_rep_block(slot_of, f, L.dDyn.as<double>(), best_tab, n, S, n_dense, Q.dBlk.as<double>(),
+                                        Q.dPre.as<int32_t>(), (int32_t *)Q.hPre.p, st));
+    return FOT_OK;
+}
+
 // The requests of a loop step as one plan call against the step's tensor (LoopState: pedestrian counts, block offsets and
 // lengths of the frame's episodes), records to rec_out: enqueued on st, not waited for.
 int loop_enqueue_requests(fot_handle *h, int32_t n_req, const fot_loop_request *req, fot_result *rec_out, hipStream_t st,
@@ -1343,9 +1386,16 @@ int loop_enqueue_requests(fot_handle *h, int32_t n_req, const fot_loop_request *
             s_off[j + 1] = s_off[j] + cnt;
         }
         const int P_e = L.ped_off[e + 1] - L.ped_off[e];
-        d_off[j] = L.blk_off[e];
-        dims[4 * j] = P_e > 0 ? (L.dist_S > 0 ? FOT_DYN_DISTRIBUTION : FOT_DYN_SINGLE) : FOT_DYN_NONE;
-        dims[4 * j + 1] = L.dist_S > 0 ? L.dist_S : 1; dims[4 * j + 2] = P_e; dims[4 * j + 3] = L.t_len[e];
+        if (L.rep.frame) {
+            // its episode's representative sample: one [P_e][T][2] block per episode, in the frame's pedestrian order
+            d_off[j] = (int64_t)L.ped_off[e] * L.rep.T;
+            dims[4 * j] = P_e > 0 ? FOT_DYN_SINGLE : FOT_DYN_NONE;
+            dims[4 * j + 1] = 1; dims[4 * j + 2] = P_e; dims[4 * j + 3] = L.rep.T;
+        } else {
+            d_off[j] = L.blk_off[e];
+            dims[4 * j] = P_e > 0 ? (L.dist_S > 0 ? FOT_DYN_DISTRIBUTION : FOT_DYN_SINGLE) : FOT_DYN_NONE;
+            dims[4 * j + 1] = L.dist_S > 0 ? L.dist_S : 1; dims[4 * j + 2] = P_e; dims[4 * j + 3] = L.t_len[e];
+        }
         any_dyn = any_dyn || P_e > 0;
     }
     if (!by_scen) s_off[n_req] = n_req * n_static;
@@ -1361,15 +1411,18 @@ int loop_enqueue_requests(fot_handle *h, int32_t n_req, const fot_loop_request *
                                            L.dGather.as<double>(), st));
         b.static_xy = L.dGather.p; b.static_off = s_off.data();
     }
-    if (any_dyn) { b.dyn_xy = L.dyn_ptr; b.dyn_off = d_off.data(); b.dyn_dims = dims.data(); }
+    if (any_dyn) { b.dyn_xy = L.rep.frame ? L.rep.dBlk.p : L.dyn_ptr; b.dyn_off = d_off.data(); b.dyn_dims = dims.data(); }
     return enqueue_plan(h, b, by_scen ? scen.data() : nullptr, b.static_xy, b.dyn_xy, rec_out, st, sync_caller);
 }
 
 // fot_loop_plan; rec_first: the request's records start at record rec_first of the handle's pinned block (the escalation
 // levels of a step land behind its level-0 records, which stay where they are)
 // ep_scen: the scenario of each episode of the frame (a scenario loop's step), or nullptr: all on scenario 0
+// ep_slot: the slot of each episode of the frame (fot_loop_step), or nullptr: episode i is slot i (what the representative
+// sample's tables are indexed by)
 int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, const fot_loop_request *req,
-                   fot_safety *safety_out, const fot_result **records, int32_t rec_first, const int32_t *ep_scen = nullptr)
+                   fot_safety *safety_out, const fot_result **records, int32_t rec_first, const int32_t *ep_scen = nullptr,
+                   const int32_t *ep_slot = nullptr)
 {
     if (!h) return FOT_ERR_INVALID;
     if (!ep_scen && (frame || h->loop.frame_scen.empty()) && !h->sc[0].has_path)
@@ -1384,7 +1437,8 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
         L.observe_n = -1;
     }
     { int r = order_begin(h, st); if (r != FOT_OK) return r; }
-    bool metrics = false;
+    bool metrics = false, rep_pending = false;
+    std::vector<int32_t> rep_slots;                              // the frame's slots, where it left representative samples
     if (frame) {
         const int n = frame->n_episodes;
         if (n < 0 || !frame->ped_off) return fail(h, FOT_ERR_INVALID, "frame: n_episodes / ped_off (one offset even for no episode)");
@@ -1409,7 +1463,8 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
         const size_t off_b = align256(sizeof(int32_t) * ((size_t)n + 1));
         const size_t ped_b = align256(sizeof(double) * 2 * std::max<size_t>(n_ped, 1));
         const size_t blk_b = align256(sizeof(int64_t) * ((size_t)n + 1)), pe_b = align256(sizeof(int32_t) * std::max<size_t>(n_ped, 1));
-        HIP_TRY(h, L.hFrame.ensure(ego_b + off_b + 4 * ped_b + blk_b + pe_b + (ep_scen ? off_b : 0)));
+        const bool rep_on = L.rep.mode == FOT_LOOP_PLAN_REPRESENTATIVE && dist;   // (never a scenario loop: the tail is free)
+        HIP_TRY(h, L.hFrame.ensure(ego_b + off_b + 4 * ped_b + blk_b + pe_b + (ep_scen || rep_on ? off_b : 0)));
         char *p = (char *)L.hFrame.p;
         double *p_ego = (double *)p;
         int32_t *p_off = (int32_t *)(p + ego_b);
@@ -1427,6 +1482,7 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
         L.blk_off.assign((size_t)n + 1, 0);
         L.t_len.assign((size_t)std::max(n, 1), 1);
         L.dist_S = dist ? frame->dist_S : 0;
+        L.rep.frame = false;
         for (int e = 0; e < n; ++e) {
             L.t_len[e] = dist ? n_dense + 1 : ready ? n_dense + (frame->prepend[e] ? 1 : 0) : 1;
             L.blk_off[e + 1] = L.blk_off[e] + (int64_t)(dist ? frame->dist_S : 1) * (L.ped_off[e + 1] - L.ped_off[e]) * L.t_len[e];
@@ -1451,6 +1507,17 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
             LAUNCH_TRY(h, launch_resample(frame->rp.sgan_dt, frame->rp.sim_dt, frame->staleness, frame->dist_S, frame->pred_len,
                                           (int)n_ped, n_dense, 1, 1, 0, frame->dist_raw, frame->dist_dtype, p_last, p_pos,
                                           L.dDyn.p, FOT_F64, 0, st, p_pe, p_off, p_blk));
+            if (rep_on) {
+                // the selection and every episode's single-sample block behind the resample, on the same stream
+                int32_t *p_slot = (int32_t *)(p + ego_b + off_b + 4 * ped_b + blk_b + pe_b);
+                int n_tab = std::max(L.ep.n, n);
+                for (int e = 0; e < n; ++e) p_slot[e] = ep_slot ? ep_slot[e] : e;
+                { int r = rep_ensure(h, n_tab, n, n_ped, n_dense + 1); if (r != FOT_OK) return r; }
+                FrameDev fd;
+                fd.pos = p_pos; fd.ped0 = p_off; fd.blk = p_blk;
+                { int r = rep_enqueue(h, p_slot, fd, n, frame->dist_S, n_dense, L.rep.dDev.as<double>(), L.rep.dBest.as<int32_t>(),
+                                      (int32_t *)L.rep.hBest.p, st); if (r != FOT_OK) return r; }
+            }
         } else if (ready && n_ped > 0) {
             HIP_TRY(h, L.dDyn.ensure(sizeof(double) * 2 * (size_t)L.blk_off[n]));
             L.dyn_ptr = L.dDyn.p;
@@ -1474,6 +1541,12 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
                                         L.p_scen, L.dSafScen.as<SafetyScen>()));
             metrics = true;
         }
+        if (rep_on) {
+            L.rep.frame = true; L.rep.T = n_dense + 1;
+            rep_pending = n_ped > 0;
+            rep_slots.assign((size_t)n, 0);
+            for (int e = 0; e < n; ++e) rep_slots[(size_t)e] = ep_slot ? ep_slot[e] : e;
+        }
         L.have_frame = true;
     }
     const int n_ep = (int)L.ped_off.size() - 1;
@@ -1496,6 +1569,15 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
         HIP_TRY(h, hipStreamSynchronize(st));
     }
     if (metrics) std::memcpy(safety_out, L.hOut.p, sizeof(fot_safety) * (size_t)n_ep);
+    if (frame && L.rep.mode == FOT_LOOP_PLAN_REPRESENTATIVE)     // (a frame without a distribution chose nothing)
+        std::fill(L.rep.last_best.begin(), L.rep.last_best.end(), -1);
+    if (frame && L.rep.frame) {                                  // (the selection ran ahead of the plan on this stream)
+        const int32_t *best = (const int32_t *)L.rep.hBest.p;
+        for (size_t e = 0; e < rep_slots.size(); ++e) {
+            const int slot = rep_slots[e];
+            if (rep_pending && slot < (int)L.rep.last_best.size() && L.ped_off[e + 1] > L.ped_off[e]) L.rep.last_best[(size_t)slot] = best[slot];
+        }
+    }
     if (records) *records = n_req > 0 ? (const fot_result *)L.hRec.p + rec_first : nullptr;
     return FOT_OK;
 }
@@ -1798,6 +1880,8 @@ int fot_loop_begin(fot_handle *h, int32_t n_episodes, const fot_loop_config *cfg
     h->loop.replay.sum.on = false;                               // ... and the summaries' accumulators with it
     h->loop.replay.smp.on = false;                               // ... and the sampler
     h->loop.replay.sc.on = false;                                // ... and its scores
+    h->loop.rep.mode = FOT_LOOP_PLAN_DISTRIBUTION; h->loop.rep.frame = false;
+    h->loop.rep.last_best.assign(n, -1);
     return FOT_OK;
 }
 
@@ -1856,6 +1940,8 @@ int fot_loop_begin_scenarios(fot_handle *h, int32_t n_episodes, int32_t n_cfg, c
     L.replay.sum.on = false;
     L.replay.smp.on = false;
     L.replay.sc.on = false;
+    L.rep.mode = FOT_LOOP_PLAN_DISTRIBUTION; L.rep.frame = false;
+    L.rep.last_best.assign(n, -1);
     return FOT_OK;
 }
 
@@ -1894,7 +1980,7 @@ int fot_loop_step(fot_handle *h, const fot_loop_frame *frame, const int32_t *epi
     fot_loop_frame fr = *frame;
     fr.ego = W.ego4.data();
     const fot_result *rec = nullptr;
-    { int rc = loop_plan_impl(h, &fr, n, W.req.data(), W.m.data(), &rec, 0, E.scenarios ? ep_scen.data() : nullptr); if (rc != FOT_OK) return rc; }
+    { int rc = loop_plan_impl(h, &fr, n, W.req.data(), W.m.data(), &rec, 0, E.scenarios ? ep_scen.data() : nullptr, episode); if (rc != FOT_OK) return rc; }
     rec = (const fot_result *)L.hRec.p;
     for (int i = 0; i < n; ++i) E.last_clearance[episode[i]] = W.m[i].clearance_ahead;
     step_escalations(E, episode, n, rec, W);
@@ -2082,6 +2168,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     if (E.scenarios) L.frame_scen.resize((size_t)n);
     L.ped_off.assign((size_t)n + 1, 0); L.blk_off.assign((size_t)n + 1, 0); L.t_len.assign((size_t)n, 1);
     L.dist_S = 0;
+    L.rep.frame = false;
     const size_t row_doubles = 2 * (size_t)R.n_cols;
     int rows_run = 0;
     for (int i = 0; i < n; ++i) rows_run += R.ped_off[sel[i] + 1] - R.ped_off[sel[i]];
@@ -2155,7 +2242,15 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         LAUNCH_TRY(h, launch_predict_cv_frame(C.rp.sgan_dt, C.rp.sim_dt, stale, rows, R.n_dense, fd, L.dDyn.as<double>(), st));
     }
     const bool scored = R.sc.on && sampled;                      // the step's distributions are scored where they lie
-    if (scored)                                                  // every episode's representative sample
+    const bool rep_on = L.rep.mode == FOT_LOOP_PLAN_REPRESENTATIVE && sampled;   // ... the requests plan on one sample of each
+    if (rep_on) {
+        // the selection once, into the scores' tables where they are on: a scored and a planning loop read the same choice
+        { int r = rep_ensure(h, n_slots, n_slots, (size_t)R.n_cols, R.n_dense + 1); if (r != FOT_OK) return r; }
+        { int r = rep_enqueue(h, s_slot, fd, n, R.smp.S, R.n_dense, R.sc.on ? R.sc.dDev.as<double>() : L.rep.dDev.as<double>(),
+                              R.sc.on ? R.sc.dBest.as<int32_t>() : L.rep.dBest.as<int32_t>(),
+                              (int32_t *)(R.sc.on ? R.sc.hBest.p : L.rep.hBest.p), st); if (r != FOT_OK) return r; }
+        L.rep.frame = true; L.rep.T = R.n_dense + 1;
+    } else if (scored)                                           // every episode's representative sample
         LAUNCH_TRY(h, launch_loop_best_sample(s_slot, fd, L.dDyn.as<double>(), n, R.smp.S, R.n_dense, R.sc.dDev.as<double>(),
                                               R.sc.dBest.as<int32_t>(), (int32_t *)R.sc.hBest.p, st));
     if (R.sum.on || R.sc.on)                                     // this step's row of every running slot's ring
@@ -2203,6 +2298,13 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
             score_ring_push(Q.fold[(size_t)e], Q.ring.data() + (size_t)e * (size_t)Q.H, Q.H, R.steps[(size_t)e], t);
             if (scored && L.ped_off[(size_t)i + 1] > L.ped_off[(size_t)i]) Q.last_best[(size_t)e] = best[e];
         }
+    }
+    if (L.rep.mode == FOT_LOOP_PLAN_REPRESENTATIVE) {            // the choice the step planned on (fot_loop_last_best_sample)
+        const int32_t *best = (const int32_t *)(R.sc.on ? R.sc.hBest.p : L.rep.hBest.p);
+        std::fill(L.rep.last_best.begin(), L.rep.last_best.end(), -1);
+        for (int i = 0; rep_on && i < n; ++i)
+            if (L.ped_off[(size_t)i + 1] > L.ped_off[(size_t)i]) L.rep.last_best[(size_t)sel[i]] = best[sel[i]];
+        L.rep.run_best.insert(L.rep.run_best.end(), L.rep.last_best.begin(), L.rep.last_best.end());
     }
     for (int i = 0; i < n; ++i) E.last_clearance[sel[i]] = W.m[i].clearance_ahead;
     step_escalations(E, sel.data(), n, dig, W);
@@ -2508,10 +2610,86 @@ int fot_loop_last_best_sample(fot_handle *h, int32_t n_slots, int32_t *out)
 {
     if (!h) return FOT_ERR_INVALID;
     LoopReplay &R = h->loop.replay;
-    if (!R.set || !R.sc.on) return fail(h, FOT_ERR_INVALID, "fot_loop_last_best_sample: scores are not enabled (fot_loop_scores_enable)");
-    if (n_slots != R.cfg.n_slots) return fail(h, FOT_ERR_INVALID, "fot_loop_last_best_sample: n_slots differs from the loop's");
+    const LoopRep &Q = h->loop.rep;
+    const bool scores = R.set && R.sc.on, planned = Q.mode == FOT_LOOP_PLAN_REPRESENTATIVE;
+    if (!scores && !planned)
+        return fail(h, FOT_ERR_INVALID, "fot_loop_last_best_sample: scores are not enabled (fot_loop_scores_enable)");
+    // (a stepwise loop planning on the representative sample: the slots of fot_loop_begin)
+    if (n_slots != (scores ? R.cfg.n_slots : h->loop.ep.n)) return fail(h, FOT_ERR_INVALID, "fot_loop_last_best_sample: n_slots differs from the loop's");
     if (n_slots > 0 && !out) return fail(h, FOT_ERR_INVALID, "fot_loop_last_best_sample: out is NULL");
-    for (int e = 0; e < n_slots; ++e) out[e] = R.sc.last_best[(size_t)e];
+    for (int e = 0; e < n_slots; ++e) out[e] = scores ? R.sc.last_best[(size_t)e] : Q.last_best[(size_t)e];
+    return FOT_OK;
+}
+
+int fot_loop_plan_sample(fot_handle *h, int32_t mode)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopState &L = h->loop;
+    LoopReplay &R = L.replay;
+    if (mode != FOT_LOOP_PLAN_DISTRIBUTION && mode != FOT_LOOP_PLAN_REPRESENTATIVE)
+        return fail(h, FOT_ERR_INVALID, "fot_loop_plan_sample: mode is FOT_LOOP_PLAN_DISTRIBUTION or FOT_LOOP_PLAN_REPRESENTATIVE");
+    if (!(L.ep.cfg.dt > 0.0)) return fail(h, FOT_ERR_INVALID, "fot_loop_plan_sample: fot_loop_begin comes first");
+    if (L.ep.scenarios) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_plan_sample: a scenario loop plans against no distribution");
+    if (R.set) {
+        bool begun = R.clock.frame != R.cfg.warmup_frames;
+        for (int e = 0; e < R.cfg.n_slots; ++e) begun = begun || R.steps[(size_t)e] != 0;
+        if (begun) return fail(h, FOT_ERR_INVALID, "fot_loop_plan_sample: the run has begun (choose between fot_loop_set_replay and the first step)");
+    }
+    if (mode == FOT_LOOP_PLAN_REPRESENTATIVE && R.set) {
+        // a resident run: everything its steps need is allocated here, so that no block grows (and moves) inside the run
+        HIP_TRY(h, hipSetDevice(h->device));
+        int r = rep_ensure(h, R.cfg.n_slots, R.cfg.n_slots, (size_t)R.n_cols, R.n_dense + 1);
+        if (r != FOT_OK) return r;
+    }
+    L.rep.mode = mode;
+    L.rep.frame = false;                                         // (the next frame decides what its requests plan against)
+    L.rep.last_best.assign((size_t)L.ep.n, -1);
+    L.rep.run_best.clear();
+    return FOT_OK;
+}
+
+int fot_loop_run_best_samples(fot_handle *h, int32_t n_steps, int32_t n_slots, int32_t *out)
+{
+    if (!h) return FOT_ERR_INVALID;
+    const LoopState &L = h->loop;
+    if (!L.replay.set || L.rep.mode != FOT_LOOP_PLAN_REPRESENTATIVE)
+        return fail(h, FOT_ERR_INVALID, "fot_loop_run_best_samples: no resident run plans on the representative sample (fot_loop_plan_sample)");
+    if (n_slots != L.replay.cfg.n_slots) return fail(h, FOT_ERR_INVALID, "fot_loop_run_best_samples: n_slots differs from the loop's");
+    if (n_steps < 0 || (size_t)n_steps * (size_t)n_slots != L.rep.run_best.size())
+        return fail(h, FOT_ERR_INVALID, "fot_loop_run_best_samples: n_steps differs from the steps of the most recent fot_loop_run");
+    if (!L.rep.run_best.empty() && !out) return fail(h, FOT_ERR_INVALID, "fot_loop_run_best_samples: out is NULL");
+    if (!L.rep.run_best.empty()) std::memcpy(out, L.rep.run_best.data(), sizeof(int32_t) * L.rep.run_best.size());
+    return FOT_OK;
+}
+
+int fot_debug_loop_block(fot_handle *h, int32_t episode, int32_t cap_points, double *xy, int32_t *P, int32_t *T,
+                         int32_t *prepended)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopState &L = h->loop;
+    if (!L.have_frame) return fail(h, FOT_ERR_INVALID, "fot_debug_loop_block: no frame");
+    const int n_ep = (int)L.ped_off.size() - 1;
+    if (episode < 0 || episode >= n_ep) return fail(h, FOT_ERR_INVALID, "fot_debug_loop_block: episode out of range");
+    if (cap_points < 0 || (cap_points > 0 && !xy)) return fail(h, FOT_ERR_INVALID, "fot_debug_loop_block: cap_points / xy");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t e = (size_t)episode;
+    const int P_e = L.ped_off[e + 1] - L.ped_off[e];
+    int t_len = 0, pre = -1;
+    int64_t first = 0, n_pts = 0;
+    const void *base = nullptr;
+    if (L.rep.frame) {
+        t_len = L.rep.T; first = (int64_t)L.ped_off[e] * t_len; n_pts = (int64_t)P_e * t_len; base = L.rep.dBlk.p;
+        if (P_e > 0) pre = ((const int32_t *)L.rep.hPre.p)[e];
+    } else {
+        t_len = L.t_len[e]; first = L.blk_off[e]; n_pts = (int64_t)std::max(L.dist_S, 1) * P_e * t_len; base = L.dyn_ptr;
+    }
+    if (P) *P = P_e;
+    if (T) *T = t_len;
+    if (prepended) *prepended = pre;
+    if (n_pts > cap_points) return fail(h, FOT_ERR_INVALID, "fot_debug_loop_block: the block holds more than cap_points points");
+    if (n_pts > 0 && base)
+        HIP_TRY(h, hipMemcpy(xy, (const double *)base + 2 * first, sizeof(double) * 2 * (size_t)n_pts, hipMemcpyDefault));
     return FOT_OK;
 }
 
@@ -2822,6 +3000,7 @@ int fot_loop_run(fot_handle *h, int32_t max_steps, fot_loop_run_out *out)
     }
     int done = 0;
     std::vector<int32_t> sel;
+    L.rep.run_best.clear();
     for (; done < max_steps; ++done) {
         sel.clear();
         for (int e = 0; e < n_slots; ++e) if (R.alive[(size_t)e]) sel.push_back(e);

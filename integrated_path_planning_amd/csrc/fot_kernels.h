@@ -7,6 +7,7 @@
 #include "fot_summary.hpp"
 #include "fot_predscore.hpp"
 #include "fot_loopscore.hpp"
+#include "fot_repsample.hpp"
 
 namespace fot {
 
@@ -249,6 +250,12 @@ int launch_loop_pred_error(ReplayView rv, const int32_t *slot_of, FrameDev f, co
 // first minimum, -1 for an episode without pedestrians.  slot_of: pinned host memory.
 int launch_loop_best_sample(const int32_t *slot_of, FrameDev f, const double *dyn, int n_run, int S, int n_dense,
                             double *dev_tab, int32_t *best_tab, int32_t *best_host, hipStream_t st);
+// ---- fot_loop_plan_sample (fot_repsample.hpp): behind launch_loop_best_sample, running episode i's planning block
+// [P_i][n_dense + 1][2] at point f.ped0[i] * (n_dense + 1) of `rep` (HBM) from sample best_tab[slot_of[i]] of its
+// distribution block and the current positions f.pos; pre_dev[i] (HBM) and pre_host[i] (pinned) receive 1 where the
+// current positions lead the block.  Only f.pos, f.ped0 and f.blk are read; an episode without pedestrians writes nothing.
+int launch_loop_rep_block(const int32_t *slot_of, FrameDev f, const double *dyn, const int32_t *best_tab, int n_run, int S,
+                          int n_dense, double *rep, int32_t *pre_dev, int32_t *pre_host, hipStream_t st);
 // The truth k_pred_scores reads for the step's origins, out[n_rows][E][2] (HBM): recording row min(f_cur + stride j,
 // frames - 1), j = 1 .. E, of every row of the frame.
 int launch_loop_score_truth(ReplayView rv, const int32_t *slot_of, FrameDev f, int n_rows, int f_cur, int stride, int E,

@@ -24,6 +24,7 @@
 #include "fot_summary.hpp"
 #include "fot_predscore.hpp"
 #include "fot_loopscore.hpp"
+#include "fot_repsample.hpp"
 
 namespace fot {
 
@@ -2516,6 +2517,51 @@ k_loop_score_truth(ReplayView rv, const int32_t *__restrict__ slot_of, FrameDev 
 }
 
 // ---------------------------------------------------------------------------
+// fot_loop_plan_sample (fot_repsample.hpp): the step's requests plan against every episode's representative sample
+// ---------------------------------------------------------------------------
+
+// One workgroup per running episode, behind k_loop_best_sample: the episode's [P][n_dense + 1][2] planning block from
+// sample best_tab[slot] of its [S][P][n_dense + 1][2] distribution block.  The lanes first AND np.allclose(first dense
+// sample, current position) over the episode's pedestrians (a ballot per wave, the waves' answers side by side in LDS: no
+// atomics, the same answer for any number of lanes), then copy: adjacent lanes take adjacent time entries of a track, one double2 each.  The flag goes to
+// pre_dev[i] (HBM) and pre_host[i] (pinned).  An episode without pedestrians writes nothing.
+constexpr int RB_THREADS = 256;
+
+__global__ void __launch_bounds__(RB_THREADS)
+k_loop_rep_block(const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn,
+                 const int32_t *__restrict__ best_tab, int n_run, int S, int n_dense, double *__restrict__ rep,
+                 int32_t *__restrict__ pre_dev, int32_t *pre_host)
+{
+    __shared__ int s_far[RB_THREADS / WAVE];
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    if (i >= n_run) return;
+    const int p0 = f.ped0[i], P = f.ped0[i + 1] - p0;
+    if (P <= 0) return;                                              // (uniform)
+    const int T = n_dense + 1, n = P * T;
+    const int best = min(max(best_tab[slot_of[i]], 0), S - 1);       // (k_loop_best_sample's choice: always in range)
+    const double2 *src = (const double2 *)dyn + f.blk[i] + (int64_t)best * P * T;
+    const double2 *cur = (const double2 *)f.pos + p0;
+    int close = 1;
+    for (int p = tid; p < P; p += RB_THREADS) {
+        const double2 a = src[(int64_t)p * T + 1], c = cur[p];
+        close &= rs_close_xy(a.x, a.y, c.x, c.y) ? 1 : 0;
+    }
+    // the vote: every wave's ballot into its own slot of LDS (plain stores), every lane reads all of them
+    const unsigned long long far_lanes = __ballot(close == 0);
+    if (lane == 0) s_far[wave] = far_lanes != 0ull ? 1 : 0;
+    __syncthreads();
+    int far = 0;
+    for (int w = 0; w < RB_THREADS / WAVE; ++w) far |= s_far[w];
+    const bool prepend = far != 0;
+    double2 *out = (double2 *)rep + (int64_t)p0 * T;
+    for (int idx = tid; idx < n; idx += RB_THREADS) {
+        const int p = idx / T, t = idx - p * T;
+        out[idx] = prepend && t == 0 ? cur[p] : src[(int64_t)p * T + rs_src(t, T, prepend)];
+    }
+    if (tid == 0) { pre_dev[i] = prepend ? 1 : 0; pre_host[i] = prepend ? 1 : 0; }
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
 
@@ -2773,6 +2819,16 @@ int launch_loop_best_sample(const int32_t *slot_of, FrameDev f, const double *dy
     if (n_run <= 0) return 0;
     if (S < 1 || S > FOT_MAX_SAMPLES || n_dense < 1) return (int)hipErrorInvalidValue;
     k_loop_best_sample<<<n_run, BS_THREADS, 0, st>>>(slot_of, f, dyn, n_run, S, n_dense, dev_tab, best_tab, best_host);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_rep_block(const int32_t *slot_of, FrameDev f, const double *dyn, const int32_t *best_tab, int n_run, int S,
+                          int n_dense, double *rep, int32_t *pre_dev, int32_t *pre_host, hipStream_t st)
+{
+    if (n_run <= 0) return 0;
+    if (S < 1 || S > FOT_MAX_SAMPLES || n_dense < 1) return (int)hipErrorInvalidValue;
+    k_loop_rep_block<<<n_run, RB_THREADS, 0, st>>>(slot_of, f, dyn, best_tab, n_run, S, n_dense, rep, pre_dev, pre_host);
     FOT_LAUNCH_CHECK();
     return 0;
 }

@@ -442,6 +442,7 @@ class BatchPlanner:
         """``fot_loop_begin``: n episode slots (ego5 [n, 5] = x, y, yaw, v, a), every fail-safe machine NORMAL."""
         ego = np.ascontiguousarray(ego5, dtype=np.float64).reshape(-1, 5)
         self._loop_n = len(ego)
+        self._plan_sample_mode = _abi.LOOP_PLAN_DISTRIBUTION          # (fot_loop_begin* resets it)
         _abi.check(self._h, self._lib.fot_loop_begin(self._h, len(ego), C.addressof(config), _addr(ego) if len(ego) else None))
 
     def loop_begin_scenarios(self, configs: Sequence["_abi.LoopConfig"], use_footprint: Sequence[bool],
@@ -456,6 +457,7 @@ class BatchPlanner:
         cfgs = (_abi.LoopConfig * len(configs))(*configs)
         ufp = np.ascontiguousarray([bool(u) for u in use_footprint], dtype=np.int32)
         self._loop_n = len(ego)
+        self._plan_sample_mode = _abi.LOOP_PLAN_DISTRIBUTION          # (fot_loop_begin* resets it)
         _abi.check(self._h, self._lib.fot_loop_begin_scenarios(
             self._h, len(ego), len(configs), C.addressof(cfgs), _addr(ufp), _addr(scen) if len(ego) else None,
             _addr(ego) if len(ego) else None))
@@ -615,10 +617,43 @@ class BatchPlanner:
     def loop_last_best_sample(self) -> np.ndarray:
         """``fot_loop_last_best_sample``: per slot the representative sample the most recent lock step chose (-1: the slot
         did not run, did not predict or has no pedestrians)."""
-        n = int(self._replay_slots)
+        # (planning on the representative sample: the slots of loop_begin, a stepwise loop's too)
+        planned = self._plan_sample_mode == _abi.LOOP_PLAN_REPRESENTATIVE
+        n = int(self._loop_n if planned else getattr(self, "_replay_slots", getattr(self, "_loop_n", 0)))
         out = np.full(max(n, 1), -1, np.int32)
         _abi.check(self._h, self._lib.fot_loop_last_best_sample(self._h, n, _addr(out)))
         return out[:n]
+
+    _plan_sample_mode = _abi.LOOP_PLAN_DISTRIBUTION
+
+    def loop_plan_sample(self, mode: int) -> None:
+        """``fot_loop_plan_sample``: what a step whose frame carries a distribution plans against --
+        ``_abi.LOOP_PLAN_DISTRIBUTION`` (the default: the whole distribution under the chance constraint) or
+        ``_abi.LOOP_PLAN_REPRESENTATIVE`` (every episode's representative sample, chosen and laid out on the device as
+        one fixed-shape [P, n_dense + 1, 2] block).  After ``loop_begin``; with a replay set before the first ``loop_run``.
+        ``loop_last_best_sample`` then answers for stepwise loops too, per slot of ``loop_begin``."""
+        _abi.check(self._h, self._lib.fot_loop_plan_sample(self._h, int(mode)))
+        self._plan_sample_mode = int(mode)
+
+    def loop_run_best_samples(self, n_steps: int) -> np.ndarray:
+        """``fot_loop_run_best_samples``: [n_steps, slots] -- ``loop_last_best_sample`` of every lock step of the most recent
+        ``loop_run`` call (``n_steps``: the steps that call executed), for a resident run that plans on the representative
+        sample."""
+        n, k = int(self._replay_slots), int(n_steps)
+        out = np.full((k, n), -1, np.int32)
+        _abi.check(self._h, self._lib.fot_loop_run_best_samples(self._h, k, n, _addr(out) if out.size else None))
+        return out
+
+    def debug_loop_block(self, episode: int, samples: int = 1, cap_points: int = 1 << 17):
+        """``fot_debug_loop_block`` (tests): (block, prepended) -- the tensor episode ``episode`` of the most recent frame
+        plans against, [samples, P, T, 2] (``samples``: 1, or the frame's dist_S where the loop plans against the whole
+        distribution), and the prepend flag (-1 where there is none)."""
+        xy = np.zeros((max(int(cap_points), 1), 2))
+        P, T, pre = C.c_int32(0), C.c_int32(0), C.c_int32(-1)
+        _abi.check(self._h, self._lib.fot_debug_loop_block(self._h, int(episode), int(cap_points), _addr(xy), C.addressof(P),
+                                                          C.addressof(T), C.addressof(pre)))
+        n = int(samples) * P.value * T.value
+        return xy[:n].reshape(int(samples), P.value, T.value, 2).copy(), pre.value
 
     PRED_SCORE_DT = np.dtype(_abi.PredScore)
     PRED_ORIGIN_DT = np.dtype(_abi.PredOrigin)
