@@ -734,7 +734,8 @@ int fot_sgan_sample(fot_handle *h, int32_t n_scenes, const int32_t *ped_off, con
  *                          r = sqrt(-2 ln u1), outputs r cos(2 pi u2), r sin(2 pi u2), in float64, rounded once to float32
  * A number is a function of (seed, slot, step, p, s, d) alone -- no atomics, nothing of the launch shape or of the other
  * rows -- so a stepwise caller can ask for exactly the noise a resident loop used for any subset of slots at any step.  It
- * is NOT torch.randn's stream: seeds are not comparable with the reference's runs.
+ * is NOT torch.randn's stream: seeds are not comparable with the reference's runs.  (To run a resident loop on the
+ * reference's own samples, record them once and hand the tensor to fot_loop_set_samples, below.)
  * row_slot / row_step / row_index: host [rows]; flags FOT_OUT_DEVICE: out is device memory.  Synchronous, enqueued on
  * `stream` (NULL = the handle's).  No model needs to be loaded.  FOT_ERR_INVALID, nothing changed: an unknown kind or
  * flag, S < 1, rows < 0, noise_dim < 0, a NULL table or `out` that is needed, a negative table entry, row_index > 65535;
@@ -766,8 +767,9 @@ int fot_sgan_noise(fot_handle *h, uint64_t seed, int32_t kind, int32_t S, int32_
                    void *stream);
 int fot_loop_set_sampler(fot_handle *h, int32_t S, uint64_t seed, int32_t kind);
 
-/* ---- prediction scores and episode summaries of a resident sampler loop ------------------------------------------------
- * fot_loop_scores_enable(h, on): between fot_loop_set_sampler and the first step (on = 0 switches it off again).  Every
+/* ---- prediction scores and episode summaries of a resident loop with a sampler or a recording (fot_loop_set_samples) ----
+ * fot_loop_scores_enable(h, on): between fot_loop_set_sampler / fot_loop_set_samples and the first step (on = 0 switches
+ * it off again).  Every
  * sampled lock step then, on the loop's stream behind the resample and ahead of the safety and plan launches and without
  * a synchronisation of its own,
  *   - chooses every running episode's representative sample (predict_single_best, trajectory_predictor.py:346-351): over
@@ -784,8 +786,9 @@ int fot_loop_set_sampler(fot_handle *h, int32_t S, uint64_t seed, int32_t kind);
  * Everything the mode needs is allocated here.  With stride pred_len - 1 >= n_dense no origin ever has a complete horizon
  * and ade .. nll stay NaN / 0 (accepted, as the reference does).  A loop that does not enable the mode launches and
  * allocates nothing of this, and its steps' outputs are the same bytes with the mode on and off.
- * Refusals (FOT_ERR_INVALID, nothing changed): no replay set; no sampler set; after the first step; sgan_dt / sim_dt not
- * an integer.  fot_loop_begin*, fot_loop_set_replay and fot_loop_set_sampler drop the mode, as they drop the sampler.
+ * Refusals (FOT_ERR_INVALID, nothing changed): no replay set; neither a sampler nor a recording set; after the first
+ * step; sgan_dt / sim_dt not an integer.  fot_loop_begin*, fot_loop_set_replay, fot_loop_set_sampler and
+ * fot_loop_set_samples drop the mode, as they drop the sampler or the recording.
  *
  * fot_loop_score_summaries(h, n_slots, out): one fot_loop_summary per slot of the steps run so far; may be called between
  * two fot_loop_run calls, the run goes on.  min_dist .. mean_accel, steps, termination, total_time: as fot_loop_summaries.
@@ -807,7 +810,7 @@ int fot_loop_last_best_sample(fot_handle *h, int32_t n_slots, int32_t *out);
 /* ---- planning on the representative prediction sample (the reference's default: distribution_aware_planning = False,
  *      integrated_simulator.py:447-455, 503-513), the samples never leaving HBM ----
  * fot_loop_plan_sample(h, mode): what the requests of a lock step plan against when its frame carries a distribution
- * (fot_loop_frame.dist_raw; the sampled step of a fot_loop_run with a sampler):
+ * (fot_loop_frame.dist_raw; the sampled step of a fot_loop_run with a sampler or a recording):
  *   FOT_LOOP_PLAN_DISTRIBUTION    the whole distribution under the chance constraint (the default)
  *   FOT_LOOP_PLAN_REPRESENTATIVE  every episode's representative sample (predict_single_best: the sample closest to the
  *                                 sample mean over the episode's own pedestrians, the selection of fot_loop_scores_enable),
@@ -846,6 +849,41 @@ int fot_loop_plan_sample(fot_handle *h, int32_t mode);
 int fot_loop_run_best_samples(fot_handle *h, int32_t n_steps, int32_t n_slots, int32_t *out);
 int fot_debug_loop_block(fot_handle *h, int32_t episode, int32_t cap_points, double *xy, int32_t *P, int32_t *T,
                          int32_t *prepended);
+
+/* ---- a resident loop that predicts from a recorded sample tensor -------------------------------------------------------
+ * With replayed pedestrians the observer's window does not depend on the ego, so neither does the predictor's output: the
+ * samples of a run can be produced once, by anything -- the reference's own generator on PyTorch under torch.manual_seed,
+ * an LSTM, a scripted source -- and stay exact for every planner configuration run over the same recording.  This is
+ * the way to run resident on the reference's own samples; the sampler's seeds above stay incomparable with them.
+ *
+ * fot_loop_set_samples(h, S, n_steps, first_step, samples, dtype, flags): between fot_loop_set_replay and the first step,
+ * where fot_loop_set_sampler would be called.  samples is [n_steps][S][pred_len][n_cols][2], n_cols = ped_off[n_slots] of
+ * the replay (the columns of all slots in the replay's own order), pred_len the replay's, dtype FOT_F32 | FOT_F64.  Row r
+ * belongs to lock step first_step + r, counted since fot_loop_set_replay (fot_loop_run_out.steps of a running slot before
+ * the step); its values are raw predictions on the predictor's own time step anchored at the observer's last sample --
+ * what fot_loop_frame.dist_raw carries for one step.  Without FOT_OUT_DEVICE the tensor is host memory and copied to HBM
+ * once, here; with it, device memory (aligned to one [x, y] element) that is used in place and never written: the caller
+ * has finished writing it before the call and keeps it alive until the next fot_loop_begin*, fot_loop_set_replay or
+ * fot_loop_set_samples on the handle, so one tensor serves a whole sweep of loops without a copy.
+ * A step of fot_loop_run then predicts from the recording where it would have predicted with a sampler (observer ready,
+ * a running slot with pedestrians): behind the frame kernel one gather (k_loop_sample_rows) forms the step's raw tensor
+ * [S][pred_len][rows][2] of the running slots from row step - first_step, in the recording's own element type, and the
+ * ragged resample of the sampler branch lays every episode's [S][P_e][n_dense + 1][2] float64 block out, the current
+ * positions leading every sample.  Level 0, the escalation levels, the resolve and the history follow as behind a sampler;
+ * fot_loop_scores_enable, fot_loop_score_summaries, fot_loop_last_best_sample, fot_loop_plan_sample, fot_loop_run_best_samples
+ * and fot_debug_loop_block work as they do there.  Steps that do not predict read nothing: their rows may hold anything.
+ * A step that would predict but lies outside [first_step, first_step + n_steps) is not run: fot_loop_run stops before it
+ * and returns the steps executed, or FOT_ERR_INVALID (the step is named in fot_last_error) if there were none.
+ * Sampler and recording exclude each other (FOT_ERR_INVALID for the second of the two); fot_loop_summary_enable stays
+ * refused as with a sampler; fot_loop_begin* and fot_loop_set_replay drop the recording.  No model needs to be loaded, and
+ * fot_sgan_load / fot_sgan_unload stay allowed.  Everything the mode needs is allocated here; a loop that never calls the
+ * entry launches and allocates nothing new.
+ * Refusals, a refused call changes nothing.  FOT_ERR_INVALID: no replay set; after the first step; S < 1; n_steps < 1;
+ * first_step < 0; samples NULL (or device memory not aligned to an element); an unknown dtype or flag; a sampler set.
+ * FOT_ERR_UNSUPPORTED: S > FOT_MAX_SAMPLES; a loop begun with fot_loop_begin_scenarios; summaries enabled.
+ * An addition: FOT_ABI_VERSION and the words of fot_abi_info stay as they are; a binding looks the symbol up. */
+int fot_loop_set_samples(fot_handle *h, int32_t S, int32_t n_steps, int32_t first_step, const void *samples, int32_t dtype,
+                         int32_t flags);
 
 /* Host utility (no GPU): the first kmax samples of the 15 path arrays of records[index[i]], i < n, as one dense block
  * out[15][n][kmax] in fot_result array order (t .. c) -- what a history keeps of a step's records. */

@@ -470,7 +470,10 @@ class BatchedClosedLoop:
         ``prediction.SganSampler`` in counter mode built without an engine (``SganSampler(None, weights, S,
         counter_seed=...)``, ``device_samples=True``, ``distribution_aware_planning``): window, noise, samples and the
         planner's tensor are then formed inside the library every step (fot_loop_set_sampler), nothing crosses the
-        bus.  The loop's arrays
+        bus -- or with a ``prediction.RecordedSamples`` (any predictor's samples of the whole run, recorded once with
+        ``prediction.record_samples``; ``device_samples=True``; with ``distribution_aware_planning`` or
+        ``plan_on_representative_sample``): the tensor goes to the library once (fot_loop_set_samples; a CUDA tensor is
+        used in place) and every step gathers its row there.  ``prediction_scores=True`` works with both.  The loop's arrays
         (``ego``, ``sm.state``, ``alive``, ...) are brought up to date after every call; the Python ``observer`` is not
         advanced (the handle owns the clock).
         summaries (resident loops only): the library accumulates every episode's summary metrics on the device while the
@@ -508,20 +511,24 @@ class BatchedClosedLoop:
                                       and getattr(sample_source, "counter_seed", None) is not None
                                       and hasattr(sample_source, "bind") and engine is None
                                       and getattr(sample_source, "engine", None) is None)
-        if self._pred_scores and self._resident and not self._resident_sampler:
+        # ... or recorded samples (prediction.RecordedSamples): the tensor goes to the library once (fot_loop_set_samples)
+        self._resident_recording = bool(self._resident and sample_source is not None and device_samples
+                                        and getattr(sample_source, "recorded", False) and engine is None)
+        self._resident_dist = self._resident_sampler or self._resident_recording
+        if self._pred_scores and self._resident and not self._resident_dist:
             raise ValueError("prediction_scores=True scores the stepwise loop's distributions (resident=False), or those "
                              "of a resident loop's own sampler (a counter-seeded sample_source with device_samples=True)")
         # a resident sampler loop scored inside the library (fot_loop_scores_enable): the summary with it
-        self._resident_scores = bool(self._pred_scores and self._resident_sampler)
+        self._resident_scores = bool(self._pred_scores and self._resident_dist)
         if self._pred_scores and sample_source is None:
             raise ValueError("prediction_scores=True needs a multi-sample predictor (sample_source)")
         if self._pred_scores and engine is not None and not hasattr(engine, "prediction_scores"):
             raise ValueError("prediction_scores=True needs the library's own engine (fot_prediction_scores)")
-        if self._resident and ((sample_source is not None and not self._resident_sampler) or engine is not None
+        if self._resident and ((sample_source is not None and not self._resident_dist) or engine is not None
                                or resampler is not None or fused not in (None, True)):
             raise ValueError("resident=True needs the constant-velocity predictor on the library's own engine "
                              "(no sample_source, engine or resampler; the one-call step)")
-        if self._resident_sampler and self._summaries:
+        if self._resident_dist and self._summaries:
             raise ValueError("summaries=True with a sampler: the resident loop's summaries read the constant-velocity "
                              "prediction (not supported yet)")
         # a sequence of configurations, one per episode: equal ones share a scenario of the ONE handle; more than one
@@ -545,6 +552,9 @@ class BatchedClosedLoop:
         self.ped_radius = getattr(c, "ped_radius", 0.3)
         self.footprint = footprint_from_config(c)
         self.sample_source = sample_source
+        if getattr(sample_source, "recorded", False):                 # a recording: of these tracks, this pred_len?
+            sample_source.attach(np.concatenate([[0], np.cumsum([np.shape(tr)[1] for tr in ped_tracks])]),
+                                 int(c.pred_len), bool(device_samples))
         if sample_source is None and getattr(c, "prediction_method", "sgan") != "cv":
             raise NotImplementedError("the Social-GAN / LSTM networks are not part of this build (SURVEY 8 f1): hand "
                                       "their samples in through sample_source, or use prediction_method='cv'")
@@ -582,7 +592,7 @@ class BatchedClosedLoop:
         if sample_source is not None and engine is None and hasattr(sample_source, "bind") and \
                 getattr(sample_source, "engine", self.engine) is None:
             sample_source.bind(self.engine)                           # (a sampler built without an engine joins this one)
-        if self._resident_sampler and (isinstance(config, (list, tuple)) or self.scenarios is not None):
+        if self._resident_dist and (isinstance(config, (list, tuple)) or self.scenarios is not None):
             raise ValueError("resident=True with a sampler takes one configuration (a scenario loop plans against no "
                              "distribution)")
         self._device_samples = bool(device_samples)
@@ -681,6 +691,8 @@ class BatchedClosedLoop:
                 self.engine.loop_summary_enable(True, int(getattr(c, "num_samples", 1)))
             if self._resident_sampler:
                 self.engine.loop_set_sampler(sample_source.num_samples, sample_source.counter_seed, sample_source.noise_kind)
+            if self._resident_recording:
+                self.engine.loop_set_samples(sample_source.samples, sample_source.first_step)
             if self._resident_scores:
                 self.engine.loop_scores_enable(True)
         if self._plan_rep:
@@ -769,8 +781,9 @@ class BatchedClosedLoop:
         if not getattr(self.sample_source, "needs_history", False):
             return self.sample_source(obs_last, obs_prev)
         window = np.stack([h[rows] for h in self.observer.history], axis=0).astype(np.float32)
-        if getattr(self.sample_source, "counter_seed", None) is not None:
-            # the counter mode: the noise is keyed by every running episode's slot and its own step count
+        if getattr(self.sample_source, "counter_seed", None) is not None or getattr(self.sample_source, "recorded", False):
+            # the counter mode: the noise is keyed by every running episode's slot and its own step count (a recording:
+            # its row by the step count, its columns by the slots)
             sel = np.flatnonzero(self.alive)
             return self.sample_source(window, np.asarray(off, dtype=np.int32), slots=sel, steps=self.step_counts[sel])
         return self.sample_source(window, np.asarray(off, dtype=np.int32))
@@ -1239,7 +1252,7 @@ class BatchedClosedLoop:
                 self.time += self.dt
                 self.ped_time += self.dt
                 self._frame_clock.update(np.array([self.frame + k + 1]), self.ped_time)
-                if self._resident_sampler and self._frame_clock.is_ready:
+                if self._resident_dist and self._frame_clock.is_ready:
                     self._steps[-1].window_frames = [int(f[0]) for f in self._frame_clock.history]
                     self._steps[-1].lock_step = len(self._steps) - 1
                     if best is not None:

@@ -159,6 +159,19 @@ struct LoopSampler {
     void release() { dWin.release(); dNoise.release(); dRaw.release(); hTab.release(); }
 };
 
+// fot_loop_set_samples: the resident loop's recorded predictor (fot_samplerec.hpp) -- the recording in HBM (the library's
+// copy of a host tensor, or the caller's device memory used in place), the raw samples of a step and the row -> column
+// table of the running slots, rebuilt only when a slot drops out
+struct LoopSamples {
+    bool on = false;
+    int S = 0, n_steps = 0, first_step = 0, dtype = FOT_F32;
+    const void *rec = nullptr;                   // [n_steps][S][pred_len][n_cols][2]: dRec, or the caller's tensor
+    DevBuf dRec, dRaw, dCol;                     // the copy | [S][pred_len][rows][2] of `dtype` | int32[rows]
+    PinnedBuf hCol;                              // the table as the host builds it
+    std::vector<int32_t> sel;                    // the running slots dCol stands for (empty: none yet)
+    void release() { dRec.release(); dRaw.release(); dCol.release(); hCol.release(); }
+};
+
 // fot_loop_scores_enable: a resident sampler loop scores its predictor (fot_loopscore.hpp).  The representative sample's
 // error rows go through LoopSummaryAcc's ring (armed, but not `on`: fot_loop_summaries stays refused); the per-origin
 // records of a step land in hRec and wait in each slot's ring of H = stride * pred_len records for their horizon.
@@ -192,10 +205,12 @@ struct LoopReplay {
     int32_t seq = 0;                             // value the completion words are raised to next
     LoopSummaryAcc sum;
     LoopSampler smp;
+    LoopSamples rec;                             // (sampler and recording exclude each other)
     LoopScores sc;
+    int dist_S() const { return smp.on ? smp.S : rec.on ? rec.S : 0; }   // samples of a predicting step's distribution
     void release()
     {
-        sum.release(); smp.release(); sc.release();
+        sum.release(); smp.release(); rec.release(); sc.release();
         dPos.release(); dVel.release(); dTab.release(); dFrame.release(); dRec.release(); dHist.release();
         hStage.release(); hDigest.release(); hHistTab.release(); hWord.release();
     }
@@ -1879,6 +1894,7 @@ int fot_loop_begin(fot_handle *h, int32_t n_episodes, const fot_loop_config *cfg
     h->loop.replay.set = false;                                  // (a new loop: the handle's clock, if it had one, is gone)
     h->loop.replay.sum.on = false;                               // ... and the summaries' accumulators with it
     h->loop.replay.smp.on = false;                               // ... and the sampler
+    h->loop.replay.rec.on = false; h->loop.replay.rec.rec = nullptr;   // ... or the recorded samples
     h->loop.replay.sc.on = false;                                // ... and its scores
     h->loop.rep.mode = FOT_LOOP_PLAN_DISTRIBUTION; h->loop.rep.frame = false;
     h->loop.rep.last_best.assign(n, -1);
@@ -1939,6 +1955,7 @@ int fot_loop_begin_scenarios(fot_handle *h, int32_t n_episodes, int32_t n_cfg, c
     L.replay.set = false;
     L.replay.sum.on = false;
     L.replay.smp.on = false;
+    L.replay.rec.on = false; L.replay.rec.rec = nullptr;
     L.replay.sc.on = false;
     L.rep.mode = FOT_LOOP_PLAN_DISTRIBUTION; L.rep.frame = false;
     L.rep.last_best.assign(n, -1);
@@ -2172,7 +2189,8 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     const size_t row_doubles = 2 * (size_t)R.n_cols;
     int rows_run = 0;
     for (int i = 0; i < n; ++i) rows_run += R.ped_off[sel[i] + 1] - R.ped_off[sel[i]];
-    const bool sampled = R.smp.on && ready && rows_run > 0;      // this step predicts with the sampler
+    const int dist_S = R.dist_S();
+    const bool sampled = dist_S > 0 && ready && rows_run > 0;    // this step predicts with the sampler or the recording
     for (int i = 0; i < n; ++i) {
         const int e = sel[i], c0 = R.ped_off[e], P_e = R.ped_off[e + 1] - c0, nf = R.n_frames[e];
         int pre = 0;
@@ -2185,7 +2203,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         if (sampled) pre = 1;                                    // (the current positions lead EVERY sample, :514-525)
         L.t_len[i] = ready ? R.n_dense + pre : 1;
         L.ped_off[i + 1] = L.ped_off[i] + P_e;
-        L.blk_off[i + 1] = L.blk_off[i] + (int64_t)(sampled ? R.smp.S : 1) * P_e * L.t_len[i];
+        L.blk_off[i + 1] = L.blk_off[i] + (int64_t)(sampled ? dist_S : 1) * P_e * L.t_len[i];
         s_slot[i] = e; s_ped0[i] = L.ped_off[i]; s_blk[i] = L.blk_off[i]; s_pre[i] = pre;
         if (E.scenarios) s_scen[i] = L.frame_scen[(size_t)i] = E.scen[(size_t)e];
         for (int q = 0; q < 4; ++q) s_ego[4 * (size_t)i + q] = W.ego4[4 * (size_t)i + q];
@@ -2205,7 +2223,26 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     L.p_scen = E.scenarios ? fd.scen : nullptr;
     L.ego_radius = C.ego_radius; L.ped_radius = C.ped_radius; L.use_footprint = C.use_footprint;
     L.dyn_ptr = fd.pos;                                          // not ready: the current positions, T = 1
-    if (sampled) {
+    if (sampled && R.rec.on) {
+        // row k - first_step of the recording -> the step's raw samples of the running slots -> every episode's
+        // [S][P_e][n_dense + 1][2] block, all in HBM behind k_loop_frame (fot_loop_run has checked that the row exists)
+        LoopSamples &M = R.rec;
+        if (M.sel != sel) {                                      // a slot dropped out (or the first step): the row -> column table
+            int32_t *col = (int32_t *)M.hCol.p;                  // (no copy of an earlier step still reads it: every step ends
+            sr_fill_columns(n, L.ped_off.data(), sel.data(), R.ped_off.data(), col);    //  with the host waiting for its word)
+            HIP_TRY(h, hipMemcpyAsync(M.dCol.p, col, sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice, st));
+            M.sel = sel;
+        }
+        LoopSampleRows a{};
+        a.d.S = M.S; a.d.pred_len = C.pred_len; a.d.rows = rows; a.d.n_cols = R.n_cols;
+        a.d.rec_row = (int64_t)R.steps[(size_t)sel[0]] - M.first_step;
+        a.rec = M.rec; a.col = M.dCol.as<int32_t>(); a.out = M.dRaw.p; a.dtype = M.dtype;
+        LAUNCH_TRY(h, launch_loop_sample_rows(a, st));
+        L.dyn_ptr = L.dDyn.p;
+        L.dist_S = M.S;
+        LAUNCH_TRY(h, launch_resample(C.rp.sgan_dt, C.rp.sim_dt, stale, M.S, C.pred_len, rows, R.n_dense, 1, 1, 0, M.dRaw.p,
+                                      M.dtype, fd.last, fd.pos, L.dDyn.p, FOT_F64, 0, st, fd.ped_ep, fd.ped0, fd.blk));
+    } else if (sampled) {
         // window -> noise -> samples -> every episode's [S][P_e][n_dense + 1][2] block, all in HBM behind k_loop_frame
         LoopSampler &M = R.smp;
         const fot_sgan_desc &d = h->sgan.desc;
@@ -2246,12 +2283,12 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     if (rep_on) {
         // the selection once, into the scores' tables where they are on: a scored and a planning loop read the same choice
         { int r = rep_ensure(h, n_slots, n_slots, (size_t)R.n_cols, R.n_dense + 1); if (r != FOT_OK) return r; }
-        { int r = rep_enqueue(h, s_slot, fd, n, R.smp.S, R.n_dense, R.sc.on ? R.sc.dDev.as<double>() : L.rep.dDev.as<double>(),
+        { int r = rep_enqueue(h, s_slot, fd, n, dist_S, R.n_dense, R.sc.on ? R.sc.dDev.as<double>() : L.rep.dDev.as<double>(),
                               R.sc.on ? R.sc.dBest.as<int32_t>() : L.rep.dBest.as<int32_t>(),
                               (int32_t *)(R.sc.on ? R.sc.hBest.p : L.rep.hBest.p), st); if (r != FOT_OK) return r; }
         L.rep.frame = true; L.rep.T = R.n_dense + 1;
     } else if (scored)                                           // every episode's representative sample
-        LAUNCH_TRY(h, launch_loop_best_sample(s_slot, fd, L.dDyn.as<double>(), n, R.smp.S, R.n_dense, R.sc.dDev.as<double>(),
+        LAUNCH_TRY(h, launch_loop_best_sample(s_slot, fd, L.dDyn.as<double>(), n, dist_S, R.n_dense, R.sc.dDev.as<double>(),
                                               R.sc.dBest.as<int32_t>(), (int32_t *)R.sc.hBest.p, st));
     if (R.sum.on || R.sc.on)                                     // this step's row of every running slot's ring
         LAUNCH_TRY(h, launch_loop_pred_error(rv, s_slot, fd, L.dDyn.as<double>(), n, ready && rows > 0 ? 1 : 0, f_cur,
@@ -2260,9 +2297,9 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
                                              scored ? R.sc.dBest.as<int32_t>() : nullptr));
     if (scored && R.sc.std_ok) {                                 // one origin per running episode, the truth from the recording
         PredOriginDev *pd = (PredOriginDev *)R.sc.hDesc.p;
-        const double scott = ps_scott(R.smp.S);
+        const double scott = ps_scott(dist_S);
         for (int i = 0; i < n; ++i)
-            pd[i] = PredOriginDev{ L.blk_off[(size_t)i], (int64_t)L.ped_off[(size_t)i], scott, R.smp.S,
+            pd[i] = PredOriginDev{ L.blk_off[(size_t)i], (int64_t)L.ped_off[(size_t)i], scott, dist_S,
                                    L.ped_off[(size_t)i + 1] - L.ped_off[(size_t)i], R.n_dense + 1, 0, 1, 0 };
         LAUNCH_TRY(h, launch_loop_score_truth(rv, s_slot, fd, rows, f_cur, R.sc.stride, C.pred_len, R.sc.dTruth.as<double>(), st));
         LAUNCH_TRY(h, launch_pred_scores(pd, n, L.dDyn.p, FOT_F64, R.sc.stride, C.pred_len, R.sc.dTruth.as<double>(),
@@ -2288,7 +2325,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         std::fill(Q.last_best.begin(), Q.last_best.end(), -1);
         for (int i = 0; i < n; ++i) {
             const int e = sel[i];
-            PredScoreTerms t = ps_zero(R.smp.S);                 // (no prediction, or no horizon that could ever complete)
+            PredScoreTerms t = ps_zero(dist_S);                  // (no prediction, or no horizon that could ever complete)
             if (scored && Q.std_ok) {
                 const fot_pred_score &r = rec[i];
                 t.ade_scene = r.ade_scene; t.fde_scene = r.fde_scene; t.ade_agent_sum = r.ade_agent_sum;
@@ -2407,6 +2444,7 @@ int fot_loop_set_replay(fot_handle *h, const fot_loop_replay *rp)
     R.set = false;
     R.sum.on = false;                                            // (a new recording: summaries are enabled again, if wanted)
     R.smp.on = false;                                            // ... and so is a sampler
+    R.rec.on = false; R.rec.rec = nullptr;                       // ... or recorded samples
     R.sc.on = false;                                             // ... and its scores
     const size_t rec_doubles = (size_t)rp->n_frames_max * cols * 2;
     const int max_lvl = E.max_lvl;
@@ -2460,6 +2498,7 @@ int fot_loop_summary_enable(fot_handle *h, int32_t on, int32_t num_samples)
     LoopSummaryAcc &A = R.sum;
     if (!on) { A.on = false; return FOT_OK; }
     if (R.smp.on) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_summary_enable: a sampler is set (fot_loop_set_sampler): the prediction-error ring reads the constant-velocity tensor");
+    if (R.rec.on) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_summary_enable: recorded samples are set (fot_loop_set_samples): the prediction-error ring reads the constant-velocity tensor");
     if (num_samples < 1) return fail(h, FOT_ERR_INVALID, "fot_loop_summary_enable: num_samples < 1");
     const int stride = summary_stride(R.cfg.rp.sgan_dt, R.cfg.rp.sim_dt);
     if (stride < 1) return fail(h, FOT_ERR_INVALID, "fot_loop_summary_enable: sgan_dt must be a multiple of sim_dt");
@@ -2551,18 +2590,19 @@ int fot_loop_scores_enable(fot_handle *h, int32_t on)
     if (!h) return FOT_ERR_INVALID;
     LoopReplay &R = h->loop.replay;
     if (!R.set) return fail(h, FOT_ERR_INVALID, "fot_loop_scores_enable: fot_loop_set_replay comes first");
-    if (!R.smp.on) return fail(h, FOT_ERR_INVALID, "fot_loop_scores_enable: no sampler is set (fot_loop_set_sampler comes first)");
+    if (!R.smp.on && !R.rec.on)
+        return fail(h, FOT_ERR_INVALID, "fot_loop_scores_enable: no sampler or recording is set (fot_loop_set_sampler / fot_loop_set_samples comes first)");
     const int n = R.cfg.n_slots;
     bool begun = R.clock.frame != R.cfg.warmup_frames;
     for (int e = 0; e < n; ++e) begun = begun || R.steps[(size_t)e] != 0;
-    if (begun) return fail(h, FOT_ERR_INVALID, "fot_loop_scores_enable: the run has begun (enable between fot_loop_set_sampler and the first step)");
+    if (begun) return fail(h, FOT_ERR_INVALID, "fot_loop_scores_enable: the run has begun (enable between fot_loop_set_sampler / fot_loop_set_samples and the first step)");
     LoopScores &Q = R.sc;
     if (!on) { Q.on = false; return FOT_OK; }
     const int stride = summary_stride(R.cfg.rp.sgan_dt, R.cfg.rp.sim_dt);
     if (stride < 1) return fail(h, FOT_ERR_INVALID, "fot_loop_scores_enable: sgan_dt must be a multiple of sim_dt");
     // --- accepted: everything the mode needs is allocated here
     Q.on = false;
-    { int r = summary_arm(h, R.smp.S, stride); if (r != FOT_OK) return r; }
+    { int r = summary_arm(h, R.dist_S(), stride); if (r != FOT_OK) return r; }
     const size_t ns = (size_t)std::max(n, 1), cols = (size_t)std::max(R.n_cols, 1), E = (size_t)R.cfg.pred_len;
     HIP_TRY(h, Q.dBest.ensure(sizeof(int32_t) * ns));
     HIP_TRY(h, Q.dDev.ensure(sizeof(double) * ns * FOT_MAX_SAMPLES));
@@ -2577,7 +2617,7 @@ int fot_loop_scores_enable(fot_handle *h, int32_t on)
     std::memset(Q.hRec.p, 0, sizeof(fot_pred_score) * ns);
     Q.stride = stride; Q.H = stride * R.cfg.pred_len;
     Q.std_ok = ps_horizon_fits(stride, R.cfg.pred_len, R.n_dense + 1, 1);
-    Q.ring.assign(ns * (size_t)Q.H, ps_zero(R.smp.S));
+    Q.ring.assign(ns * (size_t)Q.H, ps_zero(R.dist_S()));
     Q.fold.assign(ns, score_fold_zero());
     Q.last_best.assign(ns, -1);
     Q.on = true;
@@ -2940,6 +2980,7 @@ int fot_loop_set_sampler(fot_handle *h, int32_t S, uint64_t seed, int32_t kind)
     fot_handle::Sgan &G = h->sgan;
     if (!R.set) return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: fot_loop_set_replay comes first");
     if (!G.loaded) return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: no model loaded (fot_sgan_load)");
+    if (R.rec.on) return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: recorded samples are set (fot_loop_set_samples): one predictor per run");
     const int n = R.cfg.n_slots;
     bool begun = R.clock.frame != R.cfg.warmup_frames;
     for (int e = 0; e < n; ++e) begun = begun || R.steps[(size_t)e] != 0;
@@ -2982,6 +3023,56 @@ int fot_loop_set_sampler(fot_handle *h, int32_t S, uint64_t seed, int32_t kind)
     return FOT_OK;
 }
 
+int fot_loop_set_samples(fot_handle *h, int32_t S, int32_t n_steps, int32_t first_step, const void *samples, int32_t dtype,
+                         int32_t flags)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopState &L = h->loop;
+    LoopReplay &R = L.replay;
+    if (!R.set) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: fot_loop_set_replay comes first");
+    if (R.smp.on) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: a sampler is set (fot_loop_set_sampler): one predictor per run");
+    const int n = R.cfg.n_slots;
+    bool begun = R.clock.frame != R.cfg.warmup_frames;
+    for (int e = 0; e < n; ++e) begun = begun || R.steps[(size_t)e] != 0;
+    if (begun) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: the run has begun (set it between fot_loop_set_replay and the first step)");
+    if (S < 1) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: S < 1");
+    if (n_steps < 1 || first_step < 0) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: n_steps < 1 / first_step < 0");
+    if (!samples) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: samples is NULL");
+    if (dtype != FOT_F32 && dtype != FOT_F64) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: dtype is FOT_F32 or FOT_F64");
+    if (flags & ~FOT_OUT_DEVICE) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: flags");
+    const size_t elem = dtype == FOT_F32 ? 2 * sizeof(float) : 2 * sizeof(double);
+    // (the gather moves whole elements of two coordinates; hipMalloc allocations and their slices along any axis
+    //  but the last are aligned to one)
+    if ((flags & FOT_OUT_DEVICE) && (uintptr_t)samples % elem != 0)
+        return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: device samples must be aligned to one [x, y] element");
+    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_samples: S > FOT_MAX_SAMPLES");
+    if (L.ep.scenarios) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_samples: a scenario loop plans against no distribution");
+    if (R.sum.on) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_samples: summaries are enabled (their prediction-error ring reads the constant-velocity tensor)");
+    // --- accepted: everything a step needs is allocated here, so that no block grows (and moves) inside a run
+    LoopSamples &M = R.rec;
+    const size_t N = std::max<size_t>((size_t)R.n_cols, 1), rows = (size_t)S * N;
+    const size_t rec_bytes = (size_t)sr_rec_elems(n_steps, S, R.cfg.pred_len, R.n_cols) * elem;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    M.on = false; M.rec = nullptr;
+    HIP_TRY(h, M.dRaw.ensure(elem * (size_t)S * (size_t)R.cfg.pred_len * N));
+    HIP_TRY(h, M.dCol.ensure(sizeof(int32_t) * N));
+    HIP_TRY(h, M.hCol.ensure(sizeof(int32_t) * N));
+    HIP_TRY(h, L.dDyn.ensure(sizeof(double) * 2 * rows * (size_t)(R.n_dense + 1)));
+    if (flags & FOT_OUT_DEVICE) {
+        M.rec = samples;                                         // used in place, never written
+    } else {
+        HIP_TRY(h, M.dRec.ensure(std::max<size_t>(rec_bytes, elem)));
+        if (rec_bytes) HIP_TRY(h, hipMemcpy(M.dRec.p, samples, rec_bytes, hipMemcpyHostToDevice));
+        M.rec = M.dRec.p;
+    }
+    M.S = S; M.n_steps = n_steps; M.first_step = first_step; M.dtype = dtype;
+    M.sel.clear();
+    M.on = true;
+    R.sc.on = false;                                             // (a new recording: its scores are enabled again, if wanted)
+    return FOT_OK;
+}
+
 int fot_loop_run(fot_handle *h, int32_t max_steps, fot_loop_run_out *out)
 {
     if (!h) return FOT_ERR_INVALID;
@@ -3005,6 +3096,20 @@ int fot_loop_run(fot_handle *h, int32_t max_steps, fot_loop_run_out *out)
         sel.clear();
         for (int e = 0; e < n_slots; ++e) if (R.alive[(size_t)e]) sel.push_back(e);
         if (sel.empty()) break;
+        if (R.rec.on) {
+            // Would this step predict, and is its row recorded?  The clock does not depend on the ego, so the host knows
+            // before anything of the step is enqueued: a step outside the recording is not run.
+            ReplayClock next = R.clock;
+            next.advance();
+            int rows_run = 0;
+            for (int32_t e : sel) rows_run += R.ped_off[(size_t)e + 1] - R.ped_off[(size_t)e];
+            const int step = R.steps[(size_t)sel[0]];
+            if (next.ready() && rows_run > 0 && !sr_covers(R.rec.first_step, R.rec.n_steps, step)) {
+                if (done > 0) break;
+                return fail(h, FOT_ERR_INVALID, "fot_loop_run: lock step " + std::to_string(step) + " predicts, but the recorded samples (fot_loop_set_samples) cover steps " +
+                                                std::to_string(R.rec.first_step) + " .. " + std::to_string((int64_t)R.rec.first_step + R.rec.n_steps - 1));
+            }
+        }
         int rc = loop_run_step(h, sel, done, out, keep_paths ? R.dHist.as<double>() + step_doubles * (size_t)done : nullptr);
         if (rc != FOT_OK) return rc;
     }

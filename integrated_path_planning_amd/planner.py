@@ -517,6 +517,7 @@ class BatchPlanner:
         r.ego_radius, r.ped_radius, r.s_end, r.goal_distance = float(ego_radius), float(ped_radius), float(s_end), float(goal_distance)
         _abi.check(self._h, self._lib.fot_loop_set_replay(self._h, C.addressof(r)))
         self._replay_slots = n
+        self._replay_shape = (int(pred_len), int(off[-1]))           # what a recorded sample tensor must match
 
     def loop_run(self, max_steps: int, keep_paths: bool = True, paths_out: Optional[np.ndarray] = None) -> dict:
         """``fot_loop_run``: up to ``max_steps`` lock steps of every running episode inside the library.  Returns the
@@ -561,6 +562,37 @@ class BatchPlanner:
         """``fot_loop_set_sampler``: the resident loop predicts with the model of ``fot_sgan_load`` and the library's own
         counter-based noise (between ``loop_set_replay`` and the first ``loop_run``)."""
         _abi.check(self._h, self._lib.fot_loop_set_sampler(self._h, int(num_samples), int(seed) & 0xFFFFFFFFFFFFFFFF, int(kind)))
+
+    def loop_set_samples(self, samples, first_step: int = 0) -> None:
+        """``fot_loop_set_samples``: the resident loop predicts from a recorded sample tensor ``[n_steps, S, pred_len,
+        sum P, 2]`` (float32 or float64; row r belongs to lock step ``first_step + r``), between ``loop_set_replay`` and
+        the first ``loop_run``.  A NumPy array is copied to HBM by the call; a contiguous ``torch`` CUDA tensor is used
+        in place and never written -- the engine keeps a reference to it until the next ``loop_begin*`` /
+        ``loop_set_replay`` / ``loop_set_samples``."""
+        on_device = hasattr(samples, "data_ptr")
+        if on_device:
+            import torch
+            if not (samples.is_cuda and samples.is_contiguous() and samples.dtype in (torch.float32, torch.float64)):
+                raise TypeError("loop_set_samples: a contiguous CUDA tensor of float32 or float64")
+            code, ptr = (_abi.F32 if samples.dtype == torch.float32 else _abi.F64), samples.data_ptr()
+            torch.cuda.current_stream(samples.device).synchronize()   # (the library reads it on its own stream)
+        else:
+            samples = np.asarray(samples)
+            if samples.dtype not in (np.float32, np.float64):
+                raise TypeError("loop_set_samples: float32 or float64 samples")
+            samples = np.ascontiguousarray(samples)
+            code, ptr = (_abi.F32 if samples.dtype == np.float32 else _abi.F64), samples.ctypes.data
+        if samples.ndim != 5 or samples.shape[-1] != 2:
+            raise ValueError("loop_set_samples: samples are [n_steps, S, pred_len, sum P, 2]")
+        # (the library takes pred_len and the columns from the replay: a tensor of another shape would be read out of bounds)
+        want = getattr(self, "_replay_shape", None)
+        if want is not None and tuple(int(v) for v in samples.shape[2:4]) != want:
+            raise ValueError(f"loop_set_samples: the replay has pred_len = {want[0]} and {want[1]} pedestrian columns, the "
+                             f"samples are {tuple(samples.shape)}")
+        _abi.check(self._h, self._lib.fot_loop_set_samples(
+            self._h, int(samples.shape[1]), int(samples.shape[0]), int(first_step), C.c_void_p(ptr) if ptr else None, code,
+            _abi.OUT_DEVICE if on_device else 0))
+        self._loop_samples = samples if on_device else None
 
     def sgan_noise(self, seed: int, kind: int, num_samples: int, noise_dim: int, row_slot, row_step, row_index, out=None,
                    stream: Optional[int] = None):

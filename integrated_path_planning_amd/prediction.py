@@ -395,3 +395,184 @@ class SganSampler:
         return out
 
     __call__ = sample
+
+
+class RecordedSamples:
+    """A multi-sample predictor's output for a whole run, recorded once: ``samples`` ``[n_steps, S, pred_len, sum P, 2]``
+    (float32 or float64; a NumPy array or a CUDA ``torch`` tensor), row r the raw samples of lock step ``first_step + r``
+    for the pedestrians of ALL episodes in the loop's order.  With replayed pedestrians the observer's window does not
+    depend on the ego, so a recording stays exact for every planner configuration run over the same tracks -- the
+    reference's own generator under its seed, an LSTM or a scripted source is called once per step of ONE recording run
+    (``record_samples``) and every condition of a sweep replays it.
+
+    A ``sample_source`` of ``BatchedClosedLoop``: with ``resident=True`` (and ``device_samples=True``) the tensor goes to
+    the library once (``fot_loop_set_samples``; a CUDA tensor is used in place) and the whole run stays there; without, the
+    loop calls the object every step with the running episodes' ``slots`` and ``steps`` and gets the step's row cut to
+    their columns -- a device tensor with ``device_samples=True``, a host array otherwise.  Rows of steps at which the
+    observer is not ready are never read."""
+    needs_history = True
+    recorded = True
+
+    def __init__(self, samples, first_step: int = 0):
+        on_device = hasattr(samples, "data_ptr")
+        if on_device:
+            import torch
+            if samples.dtype not in (torch.float32, torch.float64):
+                raise ValueError(f"RecordedSamples: float32 or float64 samples, got {samples.dtype}")
+            if not samples.is_cuda:
+                samples = samples.detach().cpu().numpy()
+                on_device = False
+        if not on_device:
+            samples = np.asarray(samples)
+            if samples.dtype not in (np.float32, np.float64):
+                raise ValueError(f"RecordedSamples: float32 or float64 samples, got {samples.dtype}")
+        if samples.ndim != 5 or samples.shape[-1] != 2:
+            raise ValueError(f"RecordedSamples: samples are [n_steps, S, pred_len, sum P, 2], got {tuple(samples.shape)}")
+        if samples.shape[0] < 1 or not 1 <= samples.shape[1] <= _abi.MAX_SAMPLES:
+            raise ValueError(f"RecordedSamples: n_steps >= 1 and 1 <= S <= {_abi.MAX_SAMPLES}, got {tuple(samples.shape)}")
+        if int(first_step) < 0:
+            raise ValueError("RecordedSamples: first_step >= 0")
+        self.samples = samples.contiguous() if on_device else np.ascontiguousarray(samples)
+        self.first_step = int(first_step)
+        self.n_steps, self.num_samples, self.pred_len, self.n_cols = (int(v) for v in samples.shape[:4])
+        self.ped_off = None                                            # every slot's first column, once a loop is known
+        self.device_out = on_device                                    # what a stepwise call returns (attach decides)
+        self._dev, self._host, self._cols_key, self._cols = None, None, None, None
+
+    def attach(self, ped_off, pred_len: int, device_samples: Optional[bool] = None) -> None:
+        """Join a loop: its episodes' pedestrian offsets and the configuration's ``pred_len`` must be the recording's."""
+        off = np.asarray(ped_off, dtype=np.int64)
+        if int(off[-1]) != self.n_cols:
+            raise ValueError(f"RecordedSamples: the recording has {self.n_cols} pedestrian columns, the tracks {int(off[-1])}")
+        if int(pred_len) != self.pred_len:
+            raise ValueError(f"RecordedSamples: the recording has pred_len = {self.pred_len}, the configuration {int(pred_len)}")
+        self.ped_off = off
+        if device_samples is not None:
+            self.device_out = bool(device_samples)
+
+    def _columns(self, slots) -> Optional[np.ndarray]:
+        """Columns of the episodes ``slots`` (None: all of them, as they lie)."""
+        if self.ped_off is None:
+            raise ValueError("RecordedSamples: not attached to a loop's tracks yet (attach)")
+        slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+        if len(slots) == len(self.ped_off) - 1 and np.array_equal(slots, np.arange(len(slots))):
+            return None
+        key = slots.tobytes()
+        if key != self._cols_key:
+            self._cols_key = key
+            self._cols = (np.concatenate([np.arange(self.ped_off[e], self.ped_off[e + 1]) for e in slots])
+                          if len(slots) else np.zeros(0, np.int64))
+        return self._cols
+
+    def sample(self, obs=None, ped_off=None, slots=None, steps=None):
+        """The raw samples [S, pred_len, rows, 2] of the lock step ``steps`` (one value: the episodes run in lock step) for
+        the pedestrians of the episodes ``slots``; ``obs`` is not looked at, ``ped_off`` (the frame's offsets) only
+        checked."""
+        if slots is None or steps is None:
+            raise ValueError("RecordedSamples: a recording is read by lock step: pass every running episode's slot and "
+                             "step count (slots, steps)")
+        steps = np.asarray(steps, dtype=np.int64).reshape(-1)
+        if len(steps) == 0 or np.any(steps != steps[0]):
+            raise ValueError("RecordedSamples: the running episodes are at one and the same lock step")
+        r = int(steps[0]) - self.first_step
+        if not 0 <= r < self.n_steps:
+            raise IndexError(f"RecordedSamples: lock step {int(steps[0])} predicts, but the recording covers steps "
+                             f"{self.first_step} .. {self.first_step + self.n_steps - 1}")
+        cols = self._columns(slots)
+        n = self.n_cols if cols is None else len(cols)
+        if ped_off is not None and int(np.asarray(ped_off)[-1]) != n:
+            raise ValueError(f"RecordedSamples: the frame has {int(np.asarray(ped_off)[-1])} pedestrians, the slots' columns {n}")
+        stored_on_device = hasattr(self.samples, "data_ptr")
+        if self.device_out:
+            import torch
+            if not stored_on_device and self._dev is None:             # a host recording: uploaded once
+                self._dev = torch.from_numpy(self.samples).cuda()
+            row = (self.samples if stored_on_device else self._dev)[r]
+            if cols is None:
+                return row
+            return row.index_select(2, torch.as_tensor(cols, device=row.device)).contiguous()
+        if stored_on_device and self._host is None:                    # a device recording: fetched once
+            self._host = self.samples.detach().cpu().numpy()
+        row = (self._host if stored_on_device else self.samples)[r]
+        return row if cols is None else np.ascontiguousarray(row[:, :, cols])
+
+    __call__ = sample
+
+
+def record_samples(config, ped_tracks, sample_source, n_steps: int, dtype=np.float32, device=None,
+                   warmup_frames: Optional[int] = None) -> RecordedSamples:
+    """Run the closed loop's observer clock over the replayed tracks -- no ego, no planning -- and record what
+    ``sample_source`` predicts at every lock step: the warm-up of ``int(obs_len * sgan_dt / dt)`` frames, then ``n_steps``
+    steps; at every step where the observer is ready the source is called for the pedestrians of ALL episodes, as a
+    stepwise ``BatchedClosedLoop`` calls it (``(obs_last, obs_prev)``, or the window and the offsets for a
+    ``needs_history`` source; ``slots`` / ``steps`` for a counter-seeded one).  Steps before that stay NaN: they are never
+    read.  dtype: float32 or float64; device: None -- a host array, else the ``torch`` device the recording is kept on;
+    warmup_frames: for a caller of ``fot_loop_set_replay`` with a warm-up of its own (None: the loop's)."""
+    from .closed_loop import Observer, ReplayPedestrians, _Cfg
+    c = _Cfg(config) if isinstance(config, dict) else config
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("record_samples: float32 or float64")
+    sgan_dt, dt = 0.4, float(c.dt)                                    # integrated_simulator.py:323-327
+    peds = [ReplayPedestrians(tr, dt) for tr in ped_tracks]
+    off = np.concatenate([[0], np.cumsum([p.n_peds for p in peds])]).astype(np.int64)
+    t_max = max((p.n_frames for p in peds), default=0)
+    tracks = np.zeros((t_max, int(off[-1]), 2))                       # (a shorter replay holds its last frame)
+    for e, p in enumerate(peds):
+        tracks[: p.n_frames, off[e]:off[e + 1]] = p.trajectories
+        tracks[p.n_frames:, off[e]:off[e + 1]] = p.trajectories[-1]
+    observer = Observer(c.obs_len, dt, sgan_dt)
+    frame, ped_time = 0, 0.0
+
+    def advance():
+        nonlocal frame, ped_time
+        frame += 1
+        ped_time += dt
+        observer.update(tracks[min(frame, t_max - 1)], ped_time)
+
+    for _ in range(int(c.obs_len * sgan_dt / dt) if warmup_frames is None else int(warmup_frames)):   # integrated_simulator.py:406-422
+        advance()
+    n, out = len(peds), None
+    every, off32 = np.arange(n), off.astype(np.int32)
+    keyed = getattr(sample_source, "counter_seed", None) is not None or getattr(sample_source, "recorded", False)
+    for k in range(int(n_steps)):
+        advance()
+        if not observer.is_ready:
+            continue
+        hist = observer.history
+        if getattr(sample_source, "needs_history", False):
+            window = np.stack(list(hist), axis=0).astype(np.float32)
+            kw = dict(slots=every, steps=np.full(n, k, np.int64)) if keyed else {}
+            raw = sample_source(window, off32, **kw)
+        else:                                                         # the observer hands over float32 (observer.py:134)
+            o32 = np.stack([hist[-2], hist[-1]], axis=0).astype(np.float32).astype(np.float64)
+            raw = sample_source(o32[1], o32[0])
+        if hasattr(raw, "detach"):
+            import torch
+            if out is None:
+                out = torch.full((int(n_steps),) + tuple(raw.shape), float("nan"),
+                                 dtype=torch.float32 if dtype == np.float32 else torch.float64,
+                                 device=raw.device if device is None else device)
+            elif not hasattr(out, "detach"):
+                raw = raw.detach().cpu().numpy()
+        if out is None:
+            raw = np.asarray(raw)
+            out = np.full((int(n_steps),) + raw.shape, np.nan, dtype=dtype)
+        if tuple(raw.shape) != tuple(out.shape[1:]):
+            raise ValueError(f"record_samples: the source returned {tuple(raw.shape)} after {tuple(out.shape[1:])}")
+        if hasattr(out, "detach"):
+            import torch
+            t = raw if hasattr(raw, "detach") else torch.from_numpy(np.ascontiguousarray(raw))
+            out[k] = t.to(device=out.device, dtype=out.dtype)
+        else:
+            out[k] = raw
+    if out is None:
+        raise ValueError("record_samples: the observer was never ready in these steps: nothing to record")
+    if hasattr(out, "detach") and device is None:
+        out = out.cpu().numpy()
+    elif not hasattr(out, "detach") and device is not None:
+        import torch
+        out = torch.from_numpy(out).to(device)
+    rec = RecordedSamples(out, first_step=0)
+    rec.attach(off, int(out.shape[2]))
+    return rec
