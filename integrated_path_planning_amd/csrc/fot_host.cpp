@@ -307,6 +307,8 @@ struct fot_handle {
     DevBuf dSplineTab;                       // SplineView[sc.size()]
     int32_t n_shape_entries = 0;             // entries of the concatenated tile table ...
     DevBuf dShapes;                          // ... in HBM: cand0[] | n[] | span[]
+    int head_tmpl_entries = 0;               // entries per variant of the header templates (0: no grouped cut) ...
+    DevBuf dHeadTmpl;                        // ... in HBM: HeadTemplate[HEAD_VARIANTS][head_tmpl_entries]
     Workspace ws[FOT_LANES];
     int lanes_cfg = 1;                       // sub-batches a large batch is split into
     int lanes_used = 0;                      // lanes of the most recent plan call
@@ -462,7 +464,7 @@ int upload_params(fot_handle *h)
 }
 
 // (re)builds the tile tables of all scenarios for the given cut (one cut per handle) and puts their concatenation into
-// HBM: cand0[] | n[] | span[]
+// HBM: cand0[] | n[] | span[]; with them the group-header templates of a grouped cut, which are a function of the table
 int upload_tile_shapes(fot_handle *h, int cut)
 {
     const size_t n_sc = h->sc.size();
@@ -484,6 +486,10 @@ int upload_tile_shapes(fot_handle *h, int cut)
         h->refs[s].shapes = &h->sc[s].shapes; h->refs[s].shape_base = h->sc[s].shape_base;
     }
     h->tile_cut = cut;
+    std::vector<HeadTemplate> tmpl;
+    h->head_tmpl_entries = head_template_entries(h->refs.data(), (int)n_sc);
+    if (h->head_tmpl_entries > 0)
+        build_head_templates(h->refs.data(), (int)n_sc, cand0.data(), nn.data(), h->head_tmpl_entries, tmpl);
     const size_t nt = cand0.size();
     h->n_shape_entries = (int32_t)nt;
     HIP_TRY(h, hipSetDevice(h->device));
@@ -493,6 +499,10 @@ int upload_tile_shapes(fot_handle *h, int cut)
         HIP_TRY(h, hipMemcpy(h->dShapes.p, cand0.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(h->dShapes.as<int32_t>() + nt, nn.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(h->dShapes.as<int32_t>() + 2 * nt, span.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice));
+    }
+    if (!tmpl.empty()) {
+        HIP_TRY(h, h->dHeadTmpl.ensure(sizeof(HeadTemplate) * tmpl.size()));
+        HIP_TRY(h, hipMemcpy(h->dHeadTmpl.p, tmpl.data(), sizeof(HeadTemplate) * tmpl.size(), hipMemcpyHostToDevice));
     }
     h->last_valid = false;
     return FOT_OK;
@@ -642,7 +652,8 @@ int enqueue_lane(fot_handle *h, Workspace &w, const fot_batch &b, const int32_t 
         gh.n_pos = L.max_tiles / GROUP_TILES;
         HIP_TRY(h, w.dHeads.ensure(sizeof(GroupHead) * (size_t)L.n_inst * (size_t)gh.n_pos));
         gh.heads = tt.heads = w.dHeads.as<GroupHead>();
-        gh.tile_cand0 = tt.cand0; gh.tile_n = tt.n;
+        gh.tmpl = h->dHeadTmpl.as<HeadTemplate>(); gh.tmpl_entries = h->head_tmpl_entries;
+        if (gh.tmpl_entries < 1) return fail(h, FOT_ERR_INVALID, "plan: no header templates for this handle's tile table");
     }
     const DevParams *dP = nullptr;
     const PathSet sv = path_set(h, L, &dP);
@@ -941,7 +952,7 @@ void destroy_handle(fot_handle *h)
         return;
     }
     for (Scenario &S : h->sc) S.dSpline.release();
-    DevBuf *bufs[] = { &h->dP, &h->dSplineTab, &h->dShapes, &h->dUserStatic, &h->dUserDyn, &h->dOut, &h->dTmpA, &h->dTmpB, &h->dTmpC, &h->dTmpD
+    DevBuf *bufs[] = { &h->dP, &h->dSplineTab, &h->dShapes, &h->dHeadTmpl, &h->dUserStatic, &h->dUserDyn, &h->dOut, &h->dTmpA, &h->dTmpB, &h->dTmpC, &h->dTmpD
                      };
     for (DevBuf *b : bufs) b->release();
     for (Workspace &w : h->ws) w.release();

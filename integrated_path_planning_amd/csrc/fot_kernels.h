@@ -89,7 +89,8 @@ bool evaluate_in_groups(const TileTable &tiles);
 // The group-header table k_frenet_state fills for the grouped evaluation kernels (heads == nullptr: none wanted)
 struct GroupHeadOut {
     GroupHead *heads = nullptr;         // [n_inst][n_pos]
-    const int32_t *tile_cand0 = nullptr, *tile_n = nullptr;   // the handle's tile table
+    const HeadTemplate *tmpl = nullptr; // the handle's header templates (fot_setup.hpp build_head_templates)
+    int tmpl_entries = 0;               // entries per variant there (head_template_index)
     int n_pos = 0;                      // group positions per instance: max_tiles / GROUP_TILES of the batch
 };
 

@@ -369,22 +369,16 @@ __device__ __forceinline__ void frenet_state_block(const DevParams *__restrict__
             S.n_brake = nb;
             S.n_cand = n_cand;
         }
-        // The group headers of the instance (GroupHead): one lane per (position, profile) -- the first lane of a
-        // position also takes what is one value per group, the first GROUP_TILES lanes a tile each.  Every position of
-        // the batch gets at least its `present` word: the table outlives the call.
+        // The group headers of the instance (GroupHead): one lane per (position, profile).  What the lattice decides comes
+        // out of the handle's template for the instance's shape, with or without the brake ladder (HeadTemplate: the
+        // position's lanes share out the copy); the first lane adds the instance's own fields, and every lane forms the
+        // summary of its profile.  Every position of the batch gets at least its `present` word: the table outlives the call.
         if (gh.heads) {
+            const int variant = nb > 0 ? HEAD_VARIANT_BRAKE : HEAD_VARIANT_GRID;
             for (int t = tid; t < gh.n_pos * GROUP_MAX_PROFILES; t += FRENET_WG) {
                 const int pos = t / GROUP_MAX_PROFILES, p = t - pos * GROUP_MAX_PROFILES;
-                GroupHead &H = gh.heads[(int64_t)inst * gh.n_pos + pos];
-                GroupStage G;
-                const int32_t kind = group_head_stage(P, D, fr, ok ? 1 : 0, n_cand, gh.tile_cand0, gh.tile_n, pos, G);
-                if (kind != GROUP_HEAD_FULL) {
-                    if (p == 0) group_head_none(kind, G, H);
-                    continue;
-                }
-                if (p == 0) group_head_common(P, D, fr, G, H);
-                if (p < GROUP_TILES) group_head_tile(P, D, fr, n_cand, gh.tile_cand0, gh.tile_n, G, p, H);
-                group_head_profile(P, D, fr, G, p, H);
+                group_head_compose(P, D, fr, ok ? 1 : 0, gh.tmpl[head_template_index(D, variant, gh.tmpl_entries, pos)], p,
+                                   gh.heads[(int64_t)inst * gh.n_pos + pos]);
             }
         }
         carry_prev_s = new_prev_s;

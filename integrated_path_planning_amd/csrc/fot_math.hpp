@@ -396,8 +396,29 @@ FOT_HD void lon_sample(const LonInfo &L, int k, double dt, double &s, double &sd
     }
 }
 
+// The jerk sum over a profile's samples and the final speed the cost reads (:703-734), from its coefficients and sample
+// counts.
+FOT_HD void lon_summary(const DevParams &P, LonInfo &L)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)                               // part of the cost: see lateral_jerk_sum
+#endif
+    // sum over the polynomial samples k = 0..n-1 of jerk(t_k)^2 with jerk(t) = 6 a3 + 24 a4 t, t_k = k dt, in closed
+    // form (the jerk is zero on the brake padding): n c0^2 + 2 c0 c1 sum(k) + c1^2 sum(k^2), c1 = 24 a4 dt
+    const double n = (double)L.n_eval, c0 = 6.0 * L.a3, c1 = 24.0 * L.a4 * P.dt;
+    const double sum_k = n * (n - 1.0) * 0.5, sum_k2 = (n - 1.0) * n * (2.0 * n - 1.0) / 6.0;
+    L.Js = n * c0 * c0 + 2.0 * c0 * c1 * sum_k + c1 * c1 * sum_k2;
+    // final speed: the quartic's derivative at the last sample, 0 on a brake profile's padding (lon_sample)
+    if (L.n_t - 1 < L.n_eval) {
+        const double t = (double)(L.n_t - 1) * P.dt, t2 = t * t, t3 = t2 * t;
+        L.sd_last = L.a1 + 2.0 * L.a2 * t + 3.0 * L.a3 * t2 + 4.0 * L.a4 * t3;
+    } else {
+        L.sd_last = 0.0;
+    }
+}
+
 // One longitudinal profile of an instance by its slot (Ti x tv grid entry, then the brake ladder): coefficients and
-// sample counts; with_summary also the jerk sum over the samples and the final speed the cost reads (:703-734).
+// sample counts; with_summary also the jerk sum over the samples and the final speed the cost reads (lon_summary).
 // Cheap and closed-form, so every kernel that needs a profile derives it on the spot -- no table of them in HBM.
 FOT_HD LonInfo profile_info(const DevParams &P, const InstDesc &D, const double *fr, int slot, bool with_summary)
 {
@@ -415,24 +436,21 @@ FOT_HD LonInfo profile_info(const DevParams &P, const InstDesc &D, const double 
         L.n_eval = tb.n_t;
     }
     L.Js = 0.0; L.sd_last = 0.0;
-    if (with_summary) {
-#if defined(__clang__)
-#pragma clang fp contract(off)                           // part of the cost: see lateral_jerk_sum
-#endif
-        // sum over the polynomial samples k = 0..n-1 of jerk(t_k)^2 with jerk(t) = 6 a3 + 24 a4 t, t_k = k dt, in closed
-        // form (the jerk is zero on the brake padding): n c0^2 + 2 c0 c1 sum(k) + c1^2 sum(k^2), c1 = 24 a4 dt
-        const double n = (double)L.n_eval, c0 = 6.0 * L.a3, c1 = 24.0 * L.a4 * P.dt;
-        const double sum_k = n * (n - 1.0) * 0.5, sum_k2 = (n - 1.0) * n * (2.0 * n - 1.0) / 6.0;
-        L.Js = n * c0 * c0 + 2.0 * c0 * c1 * sum_k + c1 * c1 * sum_k2;
-        // final speed: the quartic's derivative at the last sample, 0 on a brake profile's padding (lon_sample)
-        if (L.n_t - 1 < L.n_eval) {
-            const double t = (double)(L.n_t - 1) * P.dt, t2 = t * t, t3 = t2 * t;
-            L.sd_last = L.a1 + 2.0 * L.a2 * t + 3.0 * L.a3 * t2 + 4.0 * L.a4 * t3;
-        } else {
-            L.sd_last = 0.0;
-        }
-    }
+    if (with_summary) lon_summary(P, L);
     return L;
+}
+
+// Where that slot lies in the lattice: horizon ti and terminal-speed index itv, or itv < 0 and ti the brake-ladder entry
+// (what profile_info divides out; the header templates keep it per staged profile).
+struct LonSlot { int ti, itv; };
+
+FOT_HD LonSlot lon_slot(const DevParams &P, const InstDesc &D, int slot)
+{
+    LonSlot s;
+    const int n_grid_lon = P.n_ti * D.n_tv;
+    if (slot < n_grid_lon) { s.ti = slot / D.n_tv; s.itv = slot - s.ti * D.n_tv; }
+    else { s.ti = slot - n_grid_lon; s.itv = -1; }
+    return s;
 }
 
 // ---------------------------------------------------------------------------
@@ -1436,8 +1454,9 @@ FOT_HD CandDecode decode_candidate(const PP &P, const DD &D, const double *fr, i
 
 // ---------------------------------------------------------------------------
 // group headers (GroupHead, fot_types.h): what the grouped evaluation kernels need before their first time step and
-// that no lane decides, derived once per instance.  In parts, so that k_frenet_state can hand them to different lanes;
-// build_group_head is all of them.  tile_cand0 / tile_n: the handle's tile table (TileTable).
+// that no lane decides, one per (instance, group position).  In parts: the host runs stage / common / tile once per handle
+// for the header templates (below), build_group_head is all of them for one instance -- what k_frenet_state's
+// group_head_compose is held against.  tile_cand0 / tile_n: the handle's tile table (TileTable).
 // ---------------------------------------------------------------------------
 static_assert(GROUP_HEAD_TILES == GROUP_TILES && GROUP_HEAD_PROFILES == GROUP_MAX_PROFILES, "GroupHead's array sizes");
 
@@ -1523,6 +1542,76 @@ FOT_HD void group_head_profile(const DevParams &P, const InstDesc &D, const doub
         L.n_t = 0; L.n_eval = 0;
     }
     H.info[p] = L;
+}
+
+// ---------------------------------------------------------------------------
+// header templates (HeadTemplate, fot_types.h): the part of a group header that the lattice alone decides, built once per
+// handle by the parts above on a descriptor that carries only the shape; k_frenet_state composes a header out of its
+// instance's template instead of deriving it.
+// ---------------------------------------------------------------------------
+
+// is 32-bit word w of a GroupHead part of a field that the instance decides?  Those are zero in a template and written by
+// group_head_instance
+FOT_HD bool head_instance_dword(int w)
+{
+    return (w >= (int)offsetof(GroupHead, cand_off) / 4 && w < (int)offsetof(GroupHead, n_grid) / 4) ||
+           (w >= (int)offsetof(GroupHead, ent_off) / 4 && w < (int)offsetof(GroupHead, d_road_w) / 4) ||
+           (w >= (int)offsetof(GroupHead, lim_speed) / 4 && w < (int)offsetof(GroupHead, info) / 4);
+}
+
+// the instance's own fields of a header
+FOT_HD void group_head_instance(const InstDesc &D, const double *fr, GroupHead &H)
+{
+    H.cand_off = D.cand_off; H.tile0 = D.tile0; H.ent_cap = D.ent_cap; H.max_viol = D.max_viol;
+    H.ent_off = D.ent_off;
+    H.lim_speed = D.lim_speed; H.lim_accel = D.lim_accel; H.lim_curv = D.lim_curv; H.lim_lat = D.lim_lat;
+    H.ego_x = D.ego.x; H.ego_y = D.ego.y;
+    for (int i = 0; i < 6; ++i) H.frenet0[i] = fr[i];
+}
+
+// staged profile p of the group out of its template entry: the coefficients and the summary as profile_info(.., true) forms
+// them, without finding the slot's place in the lattice
+FOT_HD void group_head_profile_at(const DevParams &P, const InstDesc &D, const double *fr, const HeadProfile &hp, LonInfo &L)
+{
+    if (hp.n_t > 0) {
+        lon_coeffs(fr, hp.itv >= 0 ? tv_value(P, D, hp.itv) : 0.0, hp.itv >= 0 ? P.ti[hp.ti] : P.brake[hp.ti], L);
+        L.n_t = hp.n_t; L.n_eval = hp.n_eval;
+        lon_summary(P, L);
+    } else {
+        L.a0 = L.a1 = L.a2 = L.a3 = L.a4 = L.Js = L.sd_last = L.T = 0.0;
+        L.n_t = 0; L.n_eval = 0;
+    }
+}
+
+// Lane p (0 .. GROUP_MAX_PROFILES - 1) of a position's share of composing its header from the template T of the instance's
+// lattice shape, variant and position; all lanes together write what build_group_head writes.  c2f_ok == 0: no Frenet
+// state -- a group that exists is EMPTY then.
+FOT_HD void group_head_compose(const DevParams &P, const InstDesc &D, const double *fr, int c2f_ok, const HeadTemplate &T,
+                               int p, GroupHead &H)
+{
+    int32_t kind = (int32_t)T.common[0];
+    if (!c2f_ok && kind == GROUP_HEAD_FULL) kind = GROUP_HEAD_EMPTY;
+    if (kind != GROUP_HEAD_FULL) {
+        if (p == 0) {
+            H.present = kind;
+            if (kind == GROUP_HEAD_EMPTY) H.grp_tile0 = (int32_t)T.common[1];
+        }
+        return;
+    }
+    uint32_t *dst = (uint32_t *)(void *)&H;
+    for (int w = p; w < HEAD_COMMON_DWORDS; w += GROUP_MAX_PROFILES)
+        if (!head_instance_dword(w)) dst[w] = T.common[w];
+    if (p == 0) group_head_instance(D, fr, H);
+    group_head_profile_at(P, D, fr, T.prof[p], H.info[p]);
+}
+
+// Index of the template of position `pos` of an instance in the handle's table: [variant][n_entries], one entry per group of
+// every lattice shape in the order of the tile table (a shape's run there is whole groups under the grouped cut), and
+// one last entry that every position a shape does not have shares (ABSENT).
+FOT_HD int64_t head_template_index(const InstDesc &D, int variant, int n_entries, int pos)
+{
+    const int g = pos < D.n_tiles / GROUP_TILES ? D.shape_off / GROUP_TILES + pos : n_entries - 1;
+    return (int64_t)variant * n_entries + g;
 }
 
 FOT_HD void build_group_head(const DevParams &P, const InstDesc &D, const double *fr, int c2f_ok, int n_cand,

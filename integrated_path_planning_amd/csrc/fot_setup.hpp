@@ -3,7 +3,9 @@
 // Plain C++ (no HIP), shared by libfot.so and the CPU logic tests.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <string>
 #include <cstdlib>
 #include <vector>
@@ -291,6 +293,35 @@ inline void build_tile_shapes(const DevParams &P, TileShapes &T, int cut = TILE_
     build_tile_shapes(&one, 1, &T, cut);
 }
 
+// template of position `pos` of the lattice shape D (shape_desc() with its tile run: n_tiles, shape_off) for n_cand
+// candidates -- D.n_grid (no brake ladder) or D.n_cand_max: the header's parts run on a descriptor that carries only
+// the shape, and what the instance decides is left zero
+inline void build_head_template(const DevParams &P, const InstDesc &D, int n_cand, const int32_t *tile_cand0,
+                                const int32_t *tile_n, int pos, HeadTemplate &T)
+{
+    const double fr[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };     // (nothing that is kept reads the Frenet state)
+    GroupHead H;
+    std::memset((void *)&H, 0, sizeof H);
+    std::memset((void *)&T, 0, sizeof T);
+    GroupStage G = GroupStage();
+    const int32_t kind = group_head_stage(P, D, fr, 1, n_cand, tile_cand0, tile_n, pos, G);
+    if (kind != GROUP_HEAD_FULL) {
+        group_head_none(kind, G, H);
+    } else {
+        group_head_common(P, D, fr, G, H);
+        for (int t = 0; t < GROUP_TILES; ++t) group_head_tile(P, D, fr, n_cand, tile_cand0, tile_n, G, t, H);
+        for (int p = 0; p < G.n_stage; ++p) {
+            const LonSlot s = lon_slot(P, D, G.slot_lo + p);
+            const LonInfo L = profile_info(P, D, fr, G.slot_lo + p, false);
+            HeadProfile &hp = T.prof[p];
+            hp.ti = s.ti; hp.itv = s.itv; hp.n_t = L.n_t; hp.n_eval = L.n_eval; hp.T = L.T;
+        }
+    }
+    uint32_t words[HEAD_COMMON_DWORDS];
+    std::memcpy(words, &H, sizeof words);
+    for (int w = 0; w < HEAD_COMMON_DWORDS; ++w) T.common[w] = head_instance_dword(w) ? 0u : words[w];
+}
+
 struct BatchLayout {
     std::vector<InstDesc> desc;
     int n_inst = 0;
@@ -320,6 +351,40 @@ struct ScenarioRef {
     const TileShapes *shapes = nullptr;
     int32_t shape_base = 0;
 };
+
+// entries per variant of the handle's template table: the groups of the scenarios' tile tables and the shared ABSENT
+// entry (0: not a grouped cut, no templates)
+inline int head_template_entries(const ScenarioRef *sc, int n)
+{
+    int64_t tiles = 0;
+    for (int s = 0; s < n; ++s) {
+        if (!sc[s].shapes->grouped) return 0;
+        tiles += (int64_t)sc[s].shapes->cand0.size();
+    }
+    return (int)(tiles / GROUP_TILES) + 1;
+}
+
+// The header templates of a handle's n scenarios, for the tile tables build_tile_shapes made of them:
+// [variant][n_entries = head_template_entries()], found by head_template_index.
+// tile_cand0 / tile_n: the handle's concatenated table, in which scenario s's run starts at sc[s].shape_base.
+inline void build_head_templates(const ScenarioRef *sc, int n, const int32_t *tile_cand0, const int32_t *tile_n, int n_entries,
+                                 std::vector<HeadTemplate> &out)
+{
+    out.assign((size_t)HEAD_VARIANTS * (size_t)n_entries, HeadTemplate());
+    for (int s = 0; s < n; ++s)
+        for (int n_tv = 1; n_tv <= FOT_MAX_TV; ++n_tv) {
+            const DevParams &P = *sc[s].P;
+            InstDesc D = shape_desc(P, n_tv);
+            D.scen = s;
+            D.shape_off = sc[s].shape_base + sc[s].shapes->off[n_tv];
+            D.n_tiles = sc[s].shapes->tiles_of(n_tv);
+            // (position n_groups: one the shape does not have -- every shape writes the same ABSENT entry)
+            for (int v = 0; v < HEAD_VARIANTS; ++v)
+                for (int pos = 0; pos <= D.n_tiles / GROUP_TILES; ++pos)
+                    build_head_template(P, D, v == HEAD_VARIANT_BRAKE ? D.n_cand_max : D.n_grid, tile_cand0, tile_n, pos,
+                                        out[(size_t)head_template_index(D, v, n_entries, pos)]);
+        }
+}
 
 // scen: [n_inst] scenario of each instance (indices into sc[0, n_scen)), or nullptr = scenario 0 for every instance.
 // Each instance takes its limits, dt, lattice and tile run from its own scenario; the cut and the per-wave row budget

@@ -1,6 +1,7 @@
 // fot_types.h -- plain-old-data shared by the host code and the gfx950 kernels.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/fot.h"
 
@@ -140,5 +141,26 @@ struct alignas(128) GroupHead {
     LonInfo info[GROUP_HEAD_PROFILES];   // profile_info(.., slot_lo + p, true); zero from n_stage on
 };
 static_assert(sizeof(GroupHead) % 128 == 0 && sizeof(GroupHead) == 1536, "whole 128-byte lines");
+
+// What of a GroupHead the lattice alone decides -- the planner constants, the terminal-speed grid size, whether the brake
+// ladder is there, the group position -- built once per handle on the host, next to the tile table and whenever that is
+// rebuilt (fot_setup.hpp build_head_templates).  k_frenet_state copies it and fills in what the instance decides
+// (fot_math.hpp group_head_compose).
+// The handle's table: [variant][group of the tile table | one entry for the positions a shape does not have]
+// (fot_math.hpp head_template_index).
+constexpr int HEAD_COMMON_DWORDS = 344 / 4;                     // GroupHead in front of `info`, as 32-bit words
+enum : int32_t { HEAD_VARIANT_GRID = 0, HEAD_VARIANT_BRAKE = 1, HEAD_VARIANTS = 2 };   // n_cand == n_grid / n_grid + n_brake
+struct HeadProfile {                     // staged profile p of the group; n_t == 0 from n_stage on
+    int32_t ti, itv;                     // horizon and terminal-speed index; itv < 0: entry ti of the brake ladder
+    int32_t n_t, n_eval;                 // LonInfo's
+    double T;
+};
+struct alignas(128) HeadTemplate {
+    uint32_t common[HEAD_COMMON_DWORDS]; // the GroupHead's bytes in front of `info`; the instance's fields are zero
+    uint32_t _pad[2];
+    HeadProfile prof[GROUP_HEAD_PROFILES];
+};
+static_assert(sizeof(HeadTemplate) == 768, "whole 128-byte lines");
+static_assert(offsetof(GroupHead, info) == 4 * HEAD_COMMON_DWORDS, "HeadTemplate::common is the GroupHead in front of info");
 
 }  // namespace fot
