@@ -61,7 +61,7 @@ enum {
 /* fot_result.status */
 enum {
     FOT_PLAN_OK = 0,             /* a path was selected */
-    FOT_PLAN_NO_PATH = 1,        /* plan() would return None after the checks */
+    FOT_PLAN_NO_PATH = 1,        /* plan() would return None after the checks: no 'ok' candidate with a cost below +inf */
     FOT_PLAN_C2F_FAILED = 2      /* plan() would return None at frenet_planner.py:266-268 */
 };
 

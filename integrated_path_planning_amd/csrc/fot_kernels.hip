@@ -802,7 +802,7 @@ __device__ __forceinline__ void tile_results(const DevParams &P, const InstDesc 
         KA.cand_status[slot] = (uint8_t)st_final;
         KA.cand_keep[slot] = (uint16_t)r.keep;
         my_keep = r.keep;
-        if (st_final == FOT_ST_OK) { mine.dist = r.cost; mine.idx = cand0 + lane; }
+        mine = select_entry(st_final, r.cost, cand0 + lane);     // (a cost not below +inf is never selected)
     }
     {
         const ScanBest best = wave_argmin(mine);                 // every lane of the wave is here
@@ -1020,7 +1020,7 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
         KA.cand_status[slot] = (uint8_t)st_final;
         KA.cand_keep[slot] = (uint16_t)r.keep;
         my_keep = r.keep;
-        if (st_final == FOT_ST_OK) { mine.dist = r.cost; mine.idx = cand0 + lane; }
+        mine = select_entry(st_final, r.cost, cand0 + lane);     // (a cost not below +inf is never selected)
     }
     {
         const ScanBest best = wave_argmin(mine);                 // every lane of the wave is here

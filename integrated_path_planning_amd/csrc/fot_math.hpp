@@ -220,6 +220,18 @@ FOT_HD void scan_merge(ScanBest &a, const ScanBest &b)
     if (b.idx >= 0 && (a.idx < 0 || b.dist < a.dist || (b.dist == a.dist && b.idx < a.idx))) a = b;
 }
 
+// What candidate `idx` enters the selection with (frenet_planner.py:1254-1257: `if cost < min_cost`, min_cost starting at
+// +inf, over the 'ok' candidates in generation order): its cost and index if its final status is 'ok' AND its cost lies
+// below +inf; the empty entry otherwise.  An 'ok' candidate whose cost is +inf or NaN keeps its status and is counted,
+// but the reference's loop never picks it -- and scan_merge, which takes any b when a is empty and keeps a NaN once it
+// holds one, must never see it.
+FOT_HD ScanBest select_entry(int st_final, double cost, int idx)
+{
+    ScanBest e = { INFINITY, -1 };
+    if (st_final == FOT_ST_OK && cost < INFINITY) { e.dist = cost; e.idx = idx; }
+    return e;
+}
+
 // distance scan over linspace(s_lo, s_hi, num) restricted to samples lane, lane+nlanes, ...
 // keeps the first strict minimum (:230-237); nan_first reproduces np.argmin (:336)
 FOT_HD ScanBest scan_samples(const SplineView &sp, double x, double y, double s_lo, double s_hi, int num,

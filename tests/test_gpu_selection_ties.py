@@ -1,0 +1,246 @@
+"""The candidate selection at exact cost ties and non-finite costs, on the device.
+
+plan() selects with the reference's `if cost < min_cost` over the 'ok' candidates in generation order: the first minimum
+wins, a cost not below +inf is never picked.  The kernels do it as a parallel arg-min in four places -- within a tile
+(tile_results: wave_argmin + the winner's keep by shuffle), between tiles (tile_done: whichever wave arrives last
+selects), over an instance's tiles (select_instance_wave: lane-strided loop, second wave_argmin, the keep carry) and under
+three evaluation kernels with their own tile order -- and no other test has two 'ok' candidates share the minimum.
+tests/selection_ties_common.py holds the cases (weights that make costs equal bit for bit by construction) and the
+premises that place the winner on chosen lanes, tiles and groups; tests/test_selection_ties_cpu.py asserts the premises
+and runs the merge itself on the CPU.
+
+Per case, under every evaluation path (helpers.EVAL_PATHS) and both forms:
+  A  the record and the candidate tables are the oracle's (status, keep, n_t exactly; cost within oracle.check.TIGHT);
+  B  the tie is real on the device: the library's own cost table holds ONE bit pattern on the oracle's tied set;
+  C  best_index is the lowest index among the library's own 'ok' candidates whose own cost is the library's own minimum
+     below +inf, n_keep that candidate's keep -- independent of the oracle's rounding;
+then D, the tied instance alone, at positions 0, 4 and 8 of nine instances of ragged lattices, and as one of 64 (the
+call then takes k_evaluate_group by itself): byte-identical records, also over three repeats; and E, the device-tensor
+entry, the ego given as a Frenet state, and two scenarios that differ in their weights only.
+
+Measured on an MI355X before select_entry (csrc/fot_math.hpp) went in (profiles/r20_selection_ties.txt): on the classes
+"inf" and "nan" and on the all-+inf instance of "mixed" the device answered PLAN_OK with an 'ok' index and cost inf / NaN
+where the oracle and the emulation say NO_PATH, best_index -1 -- the first 'ok' index with +inf, with NaN index 4 under
+the per-wave cut and 40 under the grouped one; every class of ties matched the oracle from the start under all paths and
+forms.  With k_s_dot ALONE judge B failed -- the oracle's exact 0 on several horizons at once is rounding luck, the device
+had 1.0e-30 on one of them --, so that class carries a small k_t (selection_ties_common.py says why that makes the tie
+one of construction).  Two deliberate breaks in scratch copies fail this file: scan_merge without its index clause
+(78 of 90 tests) and select_instance_wave taking keep_l from lane 0 (48 of 90).
+"""
+import numpy as np
+import pytest
+
+import selection_ties_common as st
+from helpers import EVAL_PATHS, TIGHT, assert_record_matches_oracle, set_eval_path
+from integrated_path_planning_amd import _abi
+from integrated_path_planning_amd.batch import PackedBatch, PlanRequest
+from integrated_path_planning_amd.planner import BatchPlanner
+from oracle import oracle as orc
+from oracle.check import oracle_plan_for_request
+
+pytestmark = pytest.mark.gpu
+
+FORMS = ("auto", "general")
+CAP = 16384
+CASES = st.cases()
+IDS = [f"{c.lattice}-{c.weights}-{k}" for k, c in enumerate(CASES)]
+
+
+@pytest.fixture(scope="module")
+def sel():
+    return st.SelectEmu()                 # (host code only: the tile tables)
+
+
+@pytest.fixture(scope="module")
+def prem(sel):
+    out = {}
+    for c in CASES:
+        out[c.name] = st.premises(c, sel)
+        st.assert_case(c, out[c.name])
+    return out
+
+
+def rec_bytes(rec):
+    return bytes(memoryview(rec).cast("B"))
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+def judge(case, i, p, rec, tables, want, lab):
+    cost, status, keep, nt = tables
+    # A: the oracle's
+    assert_record_matches_oracle(rec, want, label=lab)
+    assert len(cost) == want.n_cand, lab
+    np.testing.assert_array_equal(nt, want.cand_nt, err_msg=lab)
+    np.testing.assert_array_equal(keep, want.cand_keep, err_msg=lab)
+    np.testing.assert_array_equal(status, want.cand_status, err_msg=lab)
+    np.testing.assert_allclose(cost, want.cand_cost, rtol=TIGHT, atol=TIGHT, err_msg=lab)
+    assert rec.n_keep == (want.cand_keep[want.best_index] if want.best_index >= 0 else 0), \
+        f"{lab}: n_keep {rec.n_keep}, the oracle's winner {want.best_index} keeps {want.cand_keep[want.best_index]}"
+    # B: one bit pattern on the oracle's tied set
+    if p["winner"] >= 0:
+        b = bits(cost[p["tied"]])
+        assert np.all(b == b[0]), f"{lab}: the library's costs on the oracle's tied set {p['tied'][:6]}... take " \
+                                  f"{len(set(b.tolist()))} values: {sorted(set(cost[p['tied']].tolist()))[:4]}"
+    # C: the library's own first minimum
+    own, own_cost = st.reference_select(status, cost)
+    assert rec.best_index == own, f"{lab}: best_index {rec.best_index}, the lowest index at the library's own minimum " \
+                                  f"{own_cost!r} is {own} (oracle {want.best_index})"
+    assert rec.n_keep == (keep[own] if own >= 0 else 0), f"{lab}: n_keep {rec.n_keep}, candidate {own} keeps {keep[own]}"
+    assert rec.status == (_abi.PLAN_OK if own >= 0 else _abi.PLAN_NO_PATH), lab
+    if own >= 0:
+        assert bits([rec.cost])[0] == bits([own_cost])[0], lab
+
+
+@pytest.mark.parametrize("path", EVAL_PATHS)
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_selection_at_ties(prem, case, path):
+    with BatchPlanner(waypoints=case.waypoints, **case.kw) as bp:
+        set_eval_path(bp, path)
+        first = None
+        for form in FORMS:
+            bp.set_eval_form(form)
+            res = bp.plan_batch(case.reqs)
+            took = bp.last_eval_form()
+            lean_ok = form == "auto" and case.n_total <= 64
+            assert took == ("lean" if lean_ok else "general"), f"{case.label()} [{path}, {form}]: the launch took the {took} form"
+            for i, (p, want) in enumerate(zip(prem[case.name], case.wants)):
+                lab = f"{case.label(i)} [{path}, {form}] oracle winner {want.best_index} device {res.records[i].best_index}"
+                judge(case, i, p, res.records[i], bp.candidates(i, cap=CAP), want, lab)
+            if first is None:
+                first = [rec_bytes(res.records[i]) for i in range(len(case.reqs))]
+            else:
+                for i in range(len(case.reqs)):
+                    assert rec_bytes(res.records[i]) == first[i], f"{case.label(i)} [{path}]: the forms' records differ"
+
+
+# -- D: arrival order ---------------------------------------------------------------------------------------------------
+def fillers(weights):
+    """Eight instances of the small lattice: ragged terminal-speed grids (n_tv 7 .. 18), one standing ego, some tied some
+    not -- tiles of different instances finish interleaved."""
+    f = [st.off_ego(5.0, 6.0), st.off_ego(3.0, 3.7), st.ego(0.0, 3.0), st.off_ego(7.0, 7.7),
+         st.off_ego(9.0, 6.0, overrides=dict(max_accel=1.75)), st.off_ego(4.0, 4.0, static=st.wall(-1.1)),
+         st.off_ego(6.0, 8.2), st.off_ego(2.0, 6.5, max_stop_distance=6.0)]
+    return f
+
+
+TIED = {"zero": st.off_ego(9.0, 6.0, overrides=dict(max_accel=1.9)),            # winner 587: wave tile 16, group 4
+        "k_t_neg": st.off_ego(5.0, 6.0),                                         # winner 1170: the last horizon
+        "k_d": st.ego(5.0, 6.0)}                                                 # winner 4, tied on every horizon
+
+
+@pytest.mark.parametrize("weights", list(TIED))
+def test_record_does_not_depend_on_position_or_company(sel, weights):
+    kw = dict(st.LATTICES["small"], **st.WEIGHTS[weights])
+    tied = TIED[weights]
+    want = oracle_plan_for_request(orc, orc.make_params(**kw), orc.Spline(*st.STRAIGHT), tied, table=True)
+    assert want.status == _abi.PLAN_OK
+    n_tied = int(np.sum((want.cand_status == _abi.ST_OK) & (bits(want.cand_cost) == bits([want.cost])[0])))
+    assert n_tied >= 8, n_tied
+    with BatchPlanner(waypoints=st.STRAIGHT, **kw) as bp:
+        for path in EVAL_PATHS:
+            set_eval_path(bp, path)
+            alone = rec_bytes(bp.plan_batch([tied]).records[0])
+            assert_record_matches_oracle(bp.plan_batch([tied]).records[0], want, label=f"{weights} alone [{path}]")
+            for pos in (0, 4, 8):
+                reqs = fillers(weights)
+                reqs.insert(pos, tied)
+                runs = [bp.plan_batch(reqs) for _ in range(3)]
+                assert rec_bytes(runs[0].records[pos]) == alone, \
+                    f"{weights} [{path}]: the record at position {pos} of nine differs from the instance planned alone " \
+                    f"(best_index {runs[0].records[pos].best_index} vs {want.best_index})"
+                for r in runs[1:]:
+                    assert bytes(r.records) == bytes(runs[0].records), f"{weights} [{path}] position {pos}: repeats differ"
+        # one of 64: the automatic choice then walks every candidate in one piece under the grouped cut
+        # (csrc/fot_kernels.hip eval_segments_of: more than 2304 tiles; build_tile_shapes: the grouped cut of this lattice)
+        set_eval_path(bp, "auto")
+        f = fillers(weights)
+        reqs = [f[j % len(f)] for j in range(64)]
+        reqs[37] = tied
+        n_tiles = sum(len(sel.tile_tables(kw, st.n_tv_of(kw, r.target_speed), True)[0]) for r in reqs)
+        n_wave = sum(len(sel.tile_tables(kw, n_tv, False)[0]) for n_tv in range(1, 33))
+        n_group = sum(int(np.sum(sel.tile_tables(kw, n_tv, True)[1] > 0)) for n_tv in range(1, 33))
+        assert n_tiles > 2304 and n_group <= 1.15 * n_wave, (n_tiles, n_group, n_wave)
+        runs = [bp.plan_batch(reqs) for _ in range(3)]
+        assert rec_bytes(runs[0].records[37]) == alone, \
+            f"{weights}: the record as one of 64 differs from the instance planned alone (best_index " \
+            f"{runs[0].records[37].best_index} vs {want.best_index})"
+        for r in runs[1:]:
+            assert bytes(r.records) == bytes(runs[0].records), f"{weights}: repeats of the 64-instance call differ"
+
+
+# -- E: other entry forms and scenarios ---------------------------------------------------------------------------------
+def test_device_tensor_entry():
+    """Obstacles and records resident in HBM (no record flags, no pinned staging): the walls case."""
+    import torch
+    case = next(c for c in CASES if c.name.startswith("walls on the right"))
+    with BatchPlanner(waypoints=case.waypoints, **case.kw) as bp:
+        res = bp.plan_batch(case.reqs)
+        for i, want in enumerate(case.wants):
+            assert_record_matches_oracle(res.records[i], want, label=case.label(i))
+        pb = PackedBatch(case.reqs, np.float64)
+        dev = torch.device("cuda", 0)
+        stat = torch.from_numpy(pb.static_xy).to(dev)
+        out = torch.zeros(len(case.reqs) * _abi.RESULT_BYTES, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.Stream(device=dev)
+        torch.cuda.synchronize(dev)
+        bp.plan_packed_device(pb.with_device_obstacles(stat.data_ptr(), None), out.data_ptr(), stream.cuda_stream)
+        stream.synchronize()
+        got = np.frombuffer(out.cpu().numpy().tobytes(), dtype=BatchPlanner.RESULT_DT)
+        for i, want in enumerate(case.wants):
+            assert got[i]["best_index"] == want.best_index and got[i]["n_keep"] == res.records[i].n_keep, case.label(i)
+        assert out.cpu().numpy().tobytes() == bytes(res.records), "the device entry point's records differ"
+
+
+def test_ego_given_as_a_frenet_state():
+    case = next(c for c in CASES if c.name.startswith("short horizons"))
+    with BatchPlanner(waypoints=case.waypoints, **case.kw) as bp:
+        res = bp.plan_batch(case.reqs)
+        given = [PlanRequest(*[float(v) for v in res.records[i].frenet0[:5]], last_kappa=float(res.records[i].frenet0[5]),
+                             is_frenet=True, target_speed=r.target_speed, overrides=r.overrides)
+                 for i, r in enumerate(case.reqs)]
+        for path in EVAL_PATHS:
+            set_eval_path(bp, path)
+            got = bp.plan_batch(given)
+            for i, want in enumerate(case.wants):
+                a, b = got.records[i], res.records[i]
+                lab = f"{case.label(i)} [{path}] given as a Frenet state"
+                assert (a.status, a.best_index, a.n_keep) == (b.status, want.best_index, b.n_keep), \
+                    f"{lab}: {(a.status, a.best_index, a.n_keep)} vs {(b.status, want.best_index, b.n_keep)}"
+                assert list(a.stats) == list(b.stats), lab
+                for f in _abi.PATH_FIELDS:
+                    np.testing.assert_allclose(np.ctypeslib.as_array(getattr(a, f))[: a.n_keep],
+                                               np.ctypeslib.as_array(getattr(b, f))[: b.n_keep], rtol=0, atol=1e-12,
+                                               err_msg=f"{lab} {f}")
+
+
+def test_scenarios_that_differ_in_their_weights_only():
+    """Scenario 0 with all-zero weights, scenario 1 with the default ones, the same egos alternating: each record is its
+    own scenario's oracle's."""
+    lat = st.LATTICES["small"]
+    kws = [dict(lat, **st.WEIGHTS["zero"]), dict(lat, **st.WEIGHTS["default"])]
+    egos = [st.off_ego(9.0, 6.0, overrides=dict(max_accel=1.9)), st.off_ego(5.0, 6.0), st.ego(2.0, 4.0),
+            st.off_ego(9.0, 6.0, overrides=dict(max_accel=1.75), static=st.wall(-0.6))]
+    sp = orc.Spline(*st.STRAIGHT)
+    with BatchPlanner(waypoints=st.STRAIGHT, **kws[0]) as bp:
+        assert bp.add_scenario(waypoints=st.STRAIGHT, **kws[1]) == 1
+        reqs, wants = [], []
+        for j, e in enumerate(egos + egos):
+            scen = (j + j // len(egos)) % 2
+            reqs.append(PlanRequest(**{**e.__dict__, "scenario": scen}))
+            wants.append(oracle_plan_for_request(orc, orc.make_params(**kws[scen]), sp, e, table=True))
+        pairs = [(wants[j].best_index, wants[j + len(egos)].best_index) for j in range(len(egos))]
+        assert sum(a != b for a, b in pairs) >= 3, pairs             # the weights decide the winner
+        for path in EVAL_PATHS:
+            set_eval_path(bp, path)
+            res = bp.plan_batch(reqs)
+            for j, want in enumerate(wants):
+                lab = f"scenario {reqs[j].scenario} inst {j} [{path}]"
+                assert_record_matches_oracle(res.records[j], want, label=lab)
+                cost, status, keep, nt = bp.candidates(j, cap=CAP)
+                np.testing.assert_array_equal(status, want.cand_status, err_msg=lab)
+                np.testing.assert_allclose(cost, want.cand_cost, rtol=TIGHT, atol=TIGHT, err_msg=lab)
+                own, _ = st.reference_select(status, cost)
+                assert res.records[j].best_index == own and res.records[j].n_keep == keep[own], lab
