@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "fot_kernels.h"
+#include "fot_loop_kernels.h"
 #include "fot_math.hpp"
 #include "fot_replay.hpp"
 #include "fot_summary.hpp"
@@ -2087,7 +2088,23 @@ struct FrameLayout {
           off_b(align256(4 * (n + 1))), blk_b(align256(8 * (n + 1))), pre_b(align256(4 * std::max<size_t>(n, 1))),
           ego_b(align256(32 * std::max<size_t>(n, 1))) {}
     size_t dev_bytes() const { return 4 * ped_b + ep_b + off_b + blk_b + pre_b + ego_b + pre_b; }
-    size_t stage_bytes() const { return pre_b + off_b + blk_b + pre_b + ego_b + pre_b; }
+    // the stage block (hStage), which the host fills and k_loop_frame reads (FrameStage): its regions from `base` on and
+    // its size; stage_bytes() is this walk's end
+    struct Stage { int32_t *slot, *ped0; int64_t *blk; int32_t *prepend; double *ego; int32_t *scen; size_t bytes; };
+    Stage stage(void *base) const
+    {
+        uintptr_t p = (uintptr_t)base;
+        Stage s;
+        s.slot = (int32_t *)p; p += pre_b;
+        s.ped0 = (int32_t *)p; p += off_b;
+        s.blk = (int64_t *)p; p += blk_b;
+        s.prepend = (int32_t *)p; p += pre_b;
+        s.ego = (double *)p; p += ego_b;
+        s.scen = (int32_t *)p; p += pre_b;
+        s.bytes = (size_t)(p - (uintptr_t)base);
+        return s;
+    }
+    size_t stage_bytes() const { return stage(nullptr).bytes; }
     FrameDev dev(void *base) const
     {
         char *p = (char *)base;
@@ -2184,12 +2201,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     if (out->staleness) out->staleness[k] = stale;
     // --- 2. the frame of the running episodes: tables on the host, pedestrians on the device
     const FrameLayout FL((size_t)n_slots, (size_t)R.n_cols);
-    char *stg = (char *)R.hStage.p;
-    int32_t *s_slot = (int32_t *)stg, *s_ped0 = (int32_t *)(stg + FL.pre_b);
-    int64_t *s_blk = (int64_t *)(stg + FL.pre_b + FL.off_b);
-    int32_t *s_pre = (int32_t *)(stg + FL.pre_b + FL.off_b + FL.blk_b);
-    double *s_ego = (double *)(stg + 2 * FL.pre_b + FL.off_b + FL.blk_b);
-    int32_t *s_scen = (int32_t *)(stg + 2 * FL.pre_b + FL.off_b + FL.blk_b + FL.ego_b);
+    const FrameLayout::Stage sg = FL.stage(R.hStage.p);
     StepWork W;
     step_level0(E, sel.data(), n, W);
     L.frame_scen.clear();
@@ -2215,19 +2227,19 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         L.t_len[i] = ready ? R.n_dense + pre : 1;
         L.ped_off[i + 1] = L.ped_off[i] + P_e;
         L.blk_off[i + 1] = L.blk_off[i] + (int64_t)(sampled ? dist_S : 1) * P_e * L.t_len[i];
-        s_slot[i] = e; s_ped0[i] = L.ped_off[i]; s_blk[i] = L.blk_off[i]; s_pre[i] = pre;
-        if (E.scenarios) s_scen[i] = L.frame_scen[(size_t)i] = E.scen[(size_t)e];
-        for (int q = 0; q < 4; ++q) s_ego[4 * (size_t)i + q] = W.ego4[4 * (size_t)i + q];
+        sg.slot[i] = e; sg.ped0[i] = L.ped_off[i]; sg.blk[i] = L.blk_off[i]; sg.prepend[i] = pre;
+        if (E.scenarios) sg.scen[i] = L.frame_scen[(size_t)i] = E.scen[(size_t)e];
+        for (int q = 0; q < 4; ++q) sg.ego[4 * (size_t)i + q] = W.ego4[4 * (size_t)i + q];
     }
-    s_ped0[n] = L.ped_off[n]; s_blk[n] = L.blk_off[n];
+    sg.ped0[n] = L.ped_off[n]; sg.blk[n] = L.blk_off[n];
     const int rows = L.ped_off[n];
     ReplayView rv;
     rv.pos = R.dPos.as<double>(); rv.vel = R.dVel.as<double>();
     rv.slot_ped0 = R.dTab.as<int32_t>(); rv.slot_frames = R.dTab.as<int32_t>() + (n_slots + 1);
     rv.n_cols = R.n_cols;
     FrameStage fs;
-    fs.slot = s_slot; fs.ped0 = s_ped0; fs.blk = s_blk; fs.prepend = s_pre; fs.ego = s_ego;
-    fs.scen = E.scenarios ? s_scen : nullptr;
+    fs.slot = sg.slot; fs.ped0 = sg.ped0; fs.blk = sg.blk; fs.prepend = sg.prepend; fs.ego = sg.ego;
+    fs.scen = E.scenarios ? sg.scen : nullptr;
     const FrameDev fd = FL.dev(R.dFrame.p);
     LAUNCH_TRY(h, launch_loop_frame(rv, fs, fd, n, f_cur, ready ? f_last : -1, ready ? f_prev : -1, st));
     L.p_off = fd.ped0; L.p_pos = fd.pos; L.p_vel = fd.vel;
@@ -2261,7 +2273,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         const int nd = d.noise_dim, noise_rows = global_noise ? n : rows;
         SgWindow w{};
         w.pos = rv.pos; w.slot_ped0 = rv.slot_ped0; w.slot_frames = rv.slot_frames;
-        w.ped_ep = fd.ped_ep; w.ep_ped0 = fd.ped0; w.ep_slot = s_slot;
+        w.ped_ep = fd.ped_ep; w.ep_ped0 = fd.ped0; w.ep_slot = sg.slot;
         w.n_cols = R.n_cols; w.rows = rows; w.obs_len = d.obs_len;
         for (int j = 0; j < d.obs_len; ++j) w.frames.f[j] = R.clock.sample_frame[(size_t)j];
         w.out = M.dWin.as<float>();
@@ -2294,15 +2306,15 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     if (rep_on) {
         // the selection once, into the scores' tables where they are on: a scored and a planning loop read the same choice
         { int r = rep_ensure(h, n_slots, n_slots, (size_t)R.n_cols, R.n_dense + 1); if (r != FOT_OK) return r; }
-        { int r = rep_enqueue(h, s_slot, fd, n, dist_S, R.n_dense, R.sc.on ? R.sc.dDev.as<double>() : L.rep.dDev.as<double>(),
+        { int r = rep_enqueue(h, sg.slot, fd, n, dist_S, R.n_dense, R.sc.on ? R.sc.dDev.as<double>() : L.rep.dDev.as<double>(),
                               R.sc.on ? R.sc.dBest.as<int32_t>() : L.rep.dBest.as<int32_t>(),
                               (int32_t *)(R.sc.on ? R.sc.hBest.p : L.rep.hBest.p), st); if (r != FOT_OK) return r; }
         L.rep.frame = true; L.rep.T = R.n_dense + 1;
     } else if (scored)                                           // every episode's representative sample
-        LAUNCH_TRY(h, launch_loop_best_sample(s_slot, fd, L.dDyn.as<double>(), n, dist_S, R.n_dense, R.sc.dDev.as<double>(),
+        LAUNCH_TRY(h, launch_loop_best_sample(sg.slot, fd, L.dDyn.as<double>(), n, dist_S, R.n_dense, R.sc.dDev.as<double>(),
                                               R.sc.dBest.as<int32_t>(), (int32_t *)R.sc.hBest.p, st));
     if (R.sum.on || R.sc.on)                                     // this step's row of every running slot's ring
-        LAUNCH_TRY(h, launch_loop_pred_error(rv, s_slot, fd, L.dDyn.as<double>(), n, ready && rows > 0 ? 1 : 0, f_cur,
+        LAUNCH_TRY(h, launch_loop_pred_error(rv, sg.slot, fd, L.dDyn.as<double>(), n, ready && rows > 0 ? 1 : 0, f_cur,
                                              R.steps[(size_t)sel[0]], R.sum.shape, R.sum.dRing.as<double>(),
                                              R.sum.dRingP.as<int32_t>(), R.sum.dTotals.as<SummaryTotals>(), st,
                                              scored ? R.sc.dBest.as<int32_t>() : nullptr));
@@ -2312,7 +2324,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         for (int i = 0; i < n; ++i)
             pd[i] = PredOriginDev{ L.blk_off[(size_t)i], (int64_t)L.ped_off[(size_t)i], scott, dist_S,
                                    L.ped_off[(size_t)i + 1] - L.ped_off[(size_t)i], R.n_dense + 1, 0, 1, 0 };
-        LAUNCH_TRY(h, launch_loop_score_truth(rv, s_slot, fd, rows, f_cur, R.sc.stride, C.pred_len, R.sc.dTruth.as<double>(), st));
+        LAUNCH_TRY(h, launch_loop_score_truth(rv, sg.slot, fd, rows, f_cur, R.sc.stride, C.pred_len, R.sc.dTruth.as<double>(), st));
         LAUNCH_TRY(h, launch_pred_scores(pd, n, L.dDyn.p, FOT_F64, R.sc.stride, C.pred_len, R.sc.dTruth.as<double>(),
                                          (fot_pred_score *)R.sc.hRec.p, st));
     }

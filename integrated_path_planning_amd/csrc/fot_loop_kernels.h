@@ -1,0 +1,156 @@
+// fot_loop_kernels.h -- host-callable launchers of the prediction and closed-loop kernels (fot_loop_kernels.hip).
+#pragma once
+
+#include <cstddef>
+#include <hip/hip_runtime.h>
+#include "fot_types.h"
+#include "fot_summary.hpp"
+#include "fot_predscore.hpp"
+#include "fot_loopscore.hpp"
+#include "fot_repsample.hpp"
+#include "fot_samplerec.hpp"
+
+namespace fot {
+
+// every launcher returns 0 or the hipError_t of the launch
+int launch_resample(double sgan_dt, double sim_dt, double staleness, int S, int pred_len, int P, int n_dense,
+                    int has_anchor, int prepend, int cv, const void *pred, int pred_dtype, const double *anchor,
+                    const double *current, void *out, int out_dtype, int tmajor, hipStream_t st,
+                    const int32_t *ped_ep = nullptr, const int32_t *ep_ped0 = nullptr, const int64_t *ep_blk = nullptr);
+int launch_sample_dist(int S, int P, int T, int skip, const void *out, int out_dtype, int tmajor, double *dist,
+                       hipStream_t st);
+// ---- fot_prediction_scores (fot_predscore.hpp): one workgroup per prediction origin
+// What the kernel needs of an origin: its block (first point in the tensor), the first row of its pedestrians in `truth`
+// ([rows][E][2]) and Scott's factor S^(-1/6), which the host forms.
+struct PredOriginDev {
+    int64_t offset, truth_row;
+    double scott;
+    int32_t S, P, T, tmajor, skip, _pad;
+};
+// desc / truth / out: HBM or pinned host memory.  The host has checked every origin (1 <= S <= FOT_MAX_SAMPLES, 1 <= E <=
+// FOT_MAX_PRED_LEN, stride E - 1 < T - skip).
+int launch_pred_scores(const PredOriginDev *desc, int n, const void *tensor, int dtype, int stride, int E,
+                       const double *truth, fot_pred_score *out, hipStream_t st);
+// What the safety metrics need of a scenario beyond its DevParams: element s of a table in HBM belongs to scenario s.
+struct SafetyScen {
+    double footprint_radius;
+    int32_t use_fp;                                  // the loop's metrics use this scenario's multi-circle footprint
+    int32_t _pad;
+};
+// ep_scen == nullptr: every ego on scenario P[0] with footprint_radius / use_fp as given.  Otherwise ego e is on scenario
+// ep_scen[e]: its constants are P[ep_scen[e]], its footprint radius and flag scen_tab[ep_scen[e]] (the two arguments are
+// then ignored).
+int launch_safety(const DevParams *P, int n, const double *ego, const int32_t *ped_off, const double *ped_pos,
+                  const double *ped_vel, double ego_radius, double ped_radius, double footprint_radius, int use_fp,
+                  fot_safety *out, hipStream_t st, const int32_t *ep_scen = nullptr, const SafetyScen *scen_tab = nullptr);
+// The static obstacle points of a scenario loop's requests: request j's points are n points from point src of `points`
+// (the scenarios' point sets, each once in HBM), copied to point dst of `out` -- the static_off layout k_cull reads.
+// The table lies in pinned host memory or HBM; the host has checked every range.
+struct StaticGather {
+    int32_t src, dst, n, _pad;
+};
+int launch_static_gather(const StaticGather *tab, int n_req, const double *points, double *out, hipStream_t st);
+// ---- fot_loop_run: the frame of a lock step built from the HBM-resident recording, and what the host reads of a step
+
+// The recording fot_loop_set_replay left in HBM and the per-slot tables beside it.
+struct ReplayView {
+    const double *pos = nullptr, *vel = nullptr;     // [n_frames_max][n_cols][2]
+    const int32_t *slot_ped0 = nullptr;              // [n_slots + 1] first column of each slot
+    const int32_t *slot_frames = nullptr;            // [n_slots] recorded frames (the last one is held afterwards)
+    int n_cols = 0;
+};
+
+// What the host stages for a step's frame in pinned memory (one entry per RUNNING episode, slot order): k_loop_frame
+// moves it into HBM with the pedestrians, so that the step's other kernels read HBM only.
+struct FrameStage {
+    const int32_t *slot = nullptr;                   // [n_run] slot of running episode i
+    const int32_t *ped0 = nullptr;                   // [n_run + 1] first row of episode i in the compacted frame
+    const int64_t *blk = nullptr;                    // [n_run + 1] first point of episode i's block of the prediction tensor
+    const int32_t *prepend = nullptr;                // [n_run] 1: the current positions lead episode i's tracks
+    const double *ego = nullptr;                     // [n_run][4] x, y, yaw, v
+    const int32_t *scen = nullptr;                   // [n_run] scenario of running episode i, or nullptr (all on scenario 0)
+};
+
+// The compacted frame in HBM: rows [ped0[i], ped0[i + 1]) belong to running episode i.
+struct FrameDev {
+    double *pos = nullptr, *vel = nullptr;           // [rows][2] current positions / velocities
+    double *last = nullptr, *prev = nullptr;         // [rows][2] the observer's last two samples, rounded through float32
+    int32_t *ped_ep = nullptr;                       // [rows] running episode of each row
+    int32_t *ped0 = nullptr;                         // [n_run + 1]
+    int64_t *blk = nullptr;                          // [n_run + 1]
+    int32_t *prepend = nullptr;                      // [n_run]
+    double *ego = nullptr;                           // [n_run][4]
+    int32_t *scen = nullptr;                         // [n_run], written when FrameStage::scen is given
+};
+
+// What the host needs of a record to replay the retry loop and move the ego: the record's first 80 bytes as they are
+// (fot_result up to new_prev_s) and sample 1 of x, y, yaw, v, a.  128 bytes = eight 16-byte stores per record.
+struct LoopDigest {
+    int32_t status, best_index, n_cand, n_keep;
+    double cost;
+    int32_t stats[8];
+    int32_t stats_valid, _pad;
+    double new_last_kappa, new_prev_s;
+    double x1, y1, yaw1, v1, a1, _zero;
+};
+static_assert(sizeof(LoopDigest) == 128 && offsetof(LoopDigest, x1) == offsetof(fot_result, frenet0) &&
+              offsetof(LoopDigest, new_prev_s) == offsetof(fot_result, new_prev_s) && sizeof(fot_result) % 16 == 0,
+              "LoopDigest starts with fot_result's header");
+
+// f_cur / f_last / f_prev: replay frames of the current positions and of the observer's last two samples (f_last < 0:
+// the observer still fills, last / prev are not written)
+int launch_loop_frame(ReplayView rv, FrameStage in, FrameDev out, int n_run, int f_cur, int f_last, int f_prev,
+                      hipStream_t st);
+// fot_loop_set_samples: row d.rec_row of the recording rec [n_steps][S][pred_len][n_cols][2] -> the step's raw samples
+// out [S][pred_len][rows][2] of the running slots, both of element type dtype (FOT_F32 | FOT_F64); row q of the frame is
+// column col[q] of the recording (HBM; fot_samplerec.hpp's sr_fill_columns).  rec is only read.
+struct LoopSampleRows {
+    SampleRecDims d;
+    const void *rec;
+    const int32_t *col;                      // [rows]
+    void *out;
+    int32_t dtype, _pad;
+};
+int launch_loop_sample_rows(const LoopSampleRows &a, hipStream_t st);
+// constant-velocity tracks of every row of the frame in ONE launch, episode i's [P_i][n_dense + prepend[i]][2] block at
+// point blk[i] of `out`: k_resample's float32-observation path (cv = 2) with the prepend decided per episode
+int launch_predict_cv_frame(double sgan_dt, double sim_dt, double staleness, int n_rows, int n_dense, FrameDev f,
+                            double *out, hipStream_t st);
+// digests of rec[0 .. n) into pinned memory, then `*done = seq` behind a system-scope release
+int launch_loop_digest(const fot_result *rec, int n, LoopDigest *out, int32_t *done, int32_t seq, hipStream_t st);
+// end of a step: raises `*done = seq` (everything in front of it on the stream is then in host memory) and, with hist,
+// copies the first n_total samples of the 15 path arrays of rec[src[i]] (src[i] < 0: none) into
+// hist[15][n_slots][n_total] at slot[i]; src / slot are pinned host memory
+int launch_loop_history(const fot_result *rec, int n_run, const int32_t *src, const int32_t *slot, double *hist,
+                        int n_slots, int n_total, int32_t *done, int32_t seq, hipStream_t st);
+// ---- fot_loop_summaries (fot_summary.hpp): the prediction error of a resident loop
+// Behind the step's prediction: running episode i (slot slot_of[i], pinned host memory) writes the row of lock step
+// `step` -- sum over its pedestrians of the distance between dense sample k of its block of `dyn` (the prepended column
+// skipped) and recording row min(f_cur + 1 + k, frames - 1) -- into place step % n_dense of its ring and folds the row it
+// replaces into totals[slot].  have_pred == 0 (observer not ready) or no pedestrians: an empty row.  best (HBM, per slot;
+// nullptr: none): episode i's block is a distribution [S][P][T][2] and its row is that of sample best[slot].
+int launch_loop_pred_error(ReplayView rv, const int32_t *slot_of, FrameDev f, const double *dyn, int n_run, int have_pred,
+                           int f_cur, int step, SummaryShape S, double *ring, int32_t *ring_P, SummaryTotals *totals,
+                           hipStream_t st, const int32_t *best = nullptr);
+// ---- fot_loop_scores_enable (fot_loopscore.hpp): a resident sampler loop scores its predictor
+// The representative sample of running episode i's [S][P_i][n_dense + 1][2] block at point f.blk[i] of `dyn`:
+// dev_tab[slot][FOT_MAX_SAMPLES] (HBM) receives the S deviation sums, best_tab[slot] (HBM) and best_host[slot] (pinned) the
+// first minimum, -1 for an episode without pedestrians.  slot_of: pinned host memory.
+int launch_loop_best_sample(const int32_t *slot_of, FrameDev f, const double *dyn, int n_run, int S, int n_dense,
+                            double *dev_tab, int32_t *best_tab, int32_t *best_host, hipStream_t st);
+// ---- fot_loop_plan_sample (fot_repsample.hpp): behind launch_loop_best_sample, running episode i's planning block
+// [P_i][n_dense + 1][2] at point f.ped0[i] * (n_dense + 1) of `rep` (HBM) from sample best_tab[slot_of[i]] of its
+// distribution block and the current positions f.pos; pre_dev[i] (HBM) and pre_host[i] (pinned) receive 1 where the
+// current positions lead the block.  Only f.pos, f.ped0 and f.blk are read; an episode without pedestrians writes nothing.
+int launch_loop_rep_block(const int32_t *slot_of, FrameDev f, const double *dyn, const int32_t *best_tab, int n_run, int S,
+                          int n_dense, double *rep, int32_t *pre_dev, int32_t *pre_host, hipStream_t st);
+// The truth k_pred_scores reads for the step's origins, out[n_rows][E][2] (HBM): recording row min(f_cur + stride j,
+// frames - 1), j = 1 .. E, of every row of the frame.
+int launch_loop_score_truth(ReplayView rv, const int32_t *slot_of, FrameDev f, int n_rows, int f_cur, int stride, int E,
+                            double *out, hipStream_t st);
+// totals + the ring's rows under steps[slot] (pinned) -> the prediction-error keys and counts of out[slot] (pinned); the
+// other fields of the record are the host's.  Changes nothing in HBM.
+int launch_loop_summary(SummaryShape S, const double *ring, const int32_t *ring_P, const SummaryTotals *totals,
+                        const int32_t *steps, int n_slots, int num_samples, fot_loop_summary *out, hipStream_t st);
+
+}  // namespace fot

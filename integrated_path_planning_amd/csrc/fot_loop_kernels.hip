@@ -1,0 +1,816 @@
+// fot_loop_kernels.hip -- gfx950 kernels of the prediction entry points and of the closed loop: everything below the C ABI
+// that is not the plan pipeline (fot_kernels.hip) or the Social-GAN generator (fot_sgan.hip).
+//
+//   k_resample / k_sample_dist   fot_resample_predictions, fot_predict_cv: predictor output -> dense obstacle tensor
+//   k_pred_scores                fot_prediction_scores: best-of-N ADE / FDE and KDE-NLL of a prediction origin
+//   k_safety                     fot_safety_metrics_batch and the loop's per-step metrics
+//   k_loop_* / k_static_gather / k_predict_cv_frame
+//                                the resident loop (fot_loop_run): frame, sample gather, prediction, digests, history,
+//                                prediction-error summaries, predictor scores, representative sample
+// No inline assembly here, so no ISA-guard pass: the evaluation kernels' object file does not depend on this unit.
+#include <hip/hip_runtime.h>
+
+#include "fot_math.hpp"
+#include "fot_loop_kernels.h"
+
+namespace fot {
+
+// ---------------------------------------------------------------------------
+// prediction resampling -> obstacle tensor
+// ---------------------------------------------------------------------------
+
+struct ResampleArgs {
+    double sgan_dt, sim_dt, staleness;
+    int S, pred_len, P, n_dense, T;          // T = n_dense + prepend
+    int has_anchor, prepend, cv;             // cv: sources are (obs_prev, obs_last) -> constant velocity; 2: float32 obs
+    int tmajor;                              // out[k][s][p][axis] (FOT_OUT_TMAJOR) instead of out[s][p][k][axis]
+    // per-episode blocks (the closed loop's distribution frame): pedestrian p belongs to episode ped_ep[p], whose
+    // pedestrians are [ep_ped0[e], ep_ped0[e + 1]) and whose [S][P_e][T][2] block starts at point ep_blk[e]; nullptr: one
+    // [S][P][T][2] tensor
+    const int32_t *ped_ep; const int32_t *ep_ped0; const int64_t *ep_blk;
+};
+
+// one thread per (sample, pedestrian, axis); out[s][p][k][axis]
+template <typename TI, typename TO>
+__global__ void k_resample(ResampleArgs A, const TI *__restrict__ pred, const double *__restrict__ anchor,
+                           const double *__restrict__ current, TO *__restrict__ out)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= A.S * A.P * 2) return;
+    const int ax = idx & 1, sp = idx >> 1, p = sp % A.P, smp = sp / A.P;
+    // element (row k) of this thread's (sample, pedestrian, axis): rows are T apart in the reference's layout and a whole
+    // S x P plane apart in the T-major one (where neighbouring threads then write neighbouring addresses)
+    const int64_t k_stride = A.tmajor ? (int64_t)A.S * A.P * 2 : 2;
+    TO *dst = out + (A.tmajor ? (int64_t)sp * 2 : (int64_t)sp * A.T * 2) + ax;
+    if (A.ped_ep) {
+        const int e = A.ped_ep[p], p0 = A.ep_ped0[e], P_e = A.ep_ped0[e + 1] - p0;
+        dst = out + 2 * (A.ep_blk[e] + ((int64_t)smp * P_e + (p - p0)) * A.T) + ax;
+    }
+    if (A.prepend) dst[0] = (TO)current[2 * p + ax];
+    dst += k_stride * A.prepend;
+    if (A.cv) {                                                     // predict_cv (:188-231)
+        const double cur = anchor[2 * p + ax];                      // obs_last
+        double vel = 0.0;
+        if (pred && A.cv == 2)                                      // float32 observations: float32 velocity (:216)
+            vel = (double)(((float)cur - (float)pred[2 * p + ax]) / (float)A.sgan_dt);
+        else if (pred)
+            vel = (cur - (double)pred[2 * p + ax]) / A.sgan_dt;     // obs_prev
+        for (int i = 0; i < A.n_dense; ++i) {
+            const double t = (A.sim_dt + (double)i * A.sim_dt) + A.staleness;
+            dst[k_stride * i] = (TO)(cur + vel * t);
+        }
+        return;
+    }
+    ResampleAxis R;
+    R.sgan_dt = A.sgan_dt; R.staleness = A.staleness;
+    R.first_k = A.has_anchor ? 0 : 1;
+    int n = 0;
+    if (A.has_anchor) R.co[n++] = anchor[2 * p + ax];
+    for (int k = 0; k < A.pred_len; ++k) R.co[n++] = (double)pred[(((int64_t)smp * A.pred_len + k) * A.P + p) * 2 + ax];
+    R.n_src = n;
+    const bool constant = R.all_close(R.co[0]) || R.all_close(0.0);
+    const double v_tail = R.tail_velocity();
+    for (int i = 0; i < A.n_dense; ++i)
+        dst[k_stride * i] = (TO)R.at(A.sim_dt + (double)i * A.sim_dt, constant, v_tail);
+}
+
+// block = sample: sum over (p, k) of the distance to the sample mean (predict_single_best :346-350)
+template <typename TO>
+__global__ void __launch_bounds__(256)
+k_sample_dist(int S, int P, int T, int skip, int tmajor, const TO *__restrict__ out, double *__restrict__ dist)
+{
+    auto at = [&](int q, int p, int k) {
+        return out + (tmajor ? ((int64_t)k * S + q) * P + p : ((int64_t)q * P + p) * T + k) * 2;
+    };
+    const int smp = blockIdx.x;
+    const int n = P * (T - skip);
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int p = i / (T - skip), k = i - p * (T - skip) + skip;  // the prepended current position is not part of it
+        double mx = 0.0, my = 0.0;
+        for (int q = 0; q < S; ++q) {
+            const TO *e = at(q, p, k);
+            mx += (double)e[0]; my += (double)e[1];
+        }
+        mx /= (double)S; my /= (double)S;
+        const TO *e = at(smp, p, k);
+        const double dx = (double)e[0] - mx, dy = (double)e[1] - my;
+        acc += sqrt(dx * dx + dy * dy);
+    }
+    __shared__ double part[256 / WAVE];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, WAVE);
+    if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int w = 0; w < (int)(blockDim.x / WAVE); ++w) t += part[w];
+        dist[smp] = t;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// fot_prediction_scores (fot_predscore.hpp): one workgroup per prediction origin
+// ---------------------------------------------------------------------------
+// Pedestrians are taken in tiles of PS_TILE_PAIRS / E whose truth points lie in LDS.  Per tile, lanes first run over the
+// pedestrians (sequential over s and j: the row sums d[s][p][.] feed the per-agent minima in registers and, through a
+// butterfly over the wave, the per-sample scene sums in LDS, one slot per (s, wave)), then over the (p, j) pairs (the
+// bandwidths and log p of a pair stay in the lane that owns it).  Lanes past the tile add 0.0.  The partial sums of the
+// lanes meet in a butterfly and the waves' in index order: the order of every sum follows from (S, P, E) alone.
+constexpr int PS_THREADS = 256;
+constexpr int PS_WAVES = PS_THREADS / WAVE;
+constexpr int PS_TILE_PAIRS = 1024;              // truth points of a tile in LDS (16 KB); >= FOT_MAX_PRED_LEN
+static_assert(PS_TILE_PAIRS >= FOT_MAX_PRED_LEN, "a tile holds one pedestrian's evaluation points at least");
+
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, WAVE);
+    return v;
+}
+
+template <typename TO>
+__global__ void __launch_bounds__(PS_THREADS)
+k_pred_scores(const PredOriginDev *__restrict__ desc, const TO *__restrict__ tensor, int stride, int E,
+              const double *__restrict__ truth, fot_pred_score *__restrict__ out)
+{
+    __shared__ double s_g[PS_TILE_PAIRS * 2];
+    __shared__ double s_scene[2][FOT_MAX_SAMPLES][PS_WAVES];
+    __shared__ double s_part[3][PS_WAVES];
+    const PredOriginDev D = desc[blockIdx.x];
+    const int S = D.S, P = D.P, T = D.T, skip = D.skip, tmajor = D.tmajor;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    if (P <= 0) {                                                    // (uniform)
+        if (tid == 0) {
+            fot_pred_score r;
+            r.ade_scene = r.fde_scene = r.ade_agent_sum = r.fde_agent_sum = r.log_lik_sum = 0.0;
+            r.n_peds = 0; r.n_samples = S; r.nll_count = 0; r.flags = 0;
+            out[blockIdx.x] = r;
+        }
+        return;
+    }
+    const TO *base = tensor + 2 * D.offset;
+    auto at = [&](int s, int p, int k) {                             // dense sample k: the prepended entry skipped
+        const int kk = k + skip;
+        return base + (tmajor ? ((int64_t)kk * S + s) * P + p : ((int64_t)s * P + p) * T + kk) * 2;
+    };
+    for (int i = tid; i < 2 * FOT_MAX_SAMPLES * PS_WAVES; i += PS_THREADS) (&s_scene[0][0][0])[i] = 0.0;
+    const int tile_peds = P < PS_TILE_PAIRS / E ? P : PS_TILE_PAIRS / E;
+    double agent_a = 0.0, agent_f = 0.0, ll = 0.0;
+    int varies = 0, nonfinite = 0;
+    for (int p0 = 0; p0 < P; p0 += tile_peds) {
+        const int np = P - p0 < tile_peds ? P - p0 : tile_peds;
+        __syncthreads();                                             // the tile before is done with s_g (first: the zeros)
+        const double *g_src = truth + ((int64_t)D.truth_row + p0) * E * 2;
+        for (int i = tid; i < np * E * 2; i += PS_THREADS) {
+            const double v = g_src[i];
+            nonfinite |= !ps_finite(v);
+            s_g[i] = v;
+        }
+        __syncthreads();
+        // ---- displacement terms: lanes over the tile's pedestrians
+        for (int c = 0; c < np; c += PS_THREADS) {                   // (every lane takes every turn: the butterflies)
+            const int pl = c + tid, p = p0 + pl;
+            const bool active = pl < np;
+            double best_a = 0.0, best_f = 0.0;
+            for (int s = 0; s < S; ++s) {
+                double row = 0.0, last = 0.0;
+                if (active)
+                    for (int j = 0; j < E; ++j) {
+                        const TO *e = at(s, p, stride * (j + 1) - 1);
+                        const double qx = (double)e[0], qy = (double)e[1];
+                        nonfinite |= !ps_finite(qx) || !ps_finite(qy);
+                        last = ps_dist(qx, qy, s_g[(pl * E + j) * 2], s_g[(pl * E + j) * 2 + 1]);
+                        row += last;
+                    }
+                const double a = row / (double)E;
+                best_a = s == 0 ? a : ps_min(best_a, a);
+                best_f = s == 0 ? last : ps_min(best_f, last);
+                const double w_row = wave_sum_f64(row), w_last = wave_sum_f64(last);
+                if (lane == 0) { s_scene[0][s][wave] += w_row; s_scene[1][s][wave] += w_last; }
+            }
+            agent_a += best_a; agent_f += best_f;                    // (a lane past the tile: 0.0)
+        }
+        // ---- KDE terms: lanes over the tile's (p, j) pairs
+        if (S >= 2)
+            for (int i = tid; i < np * E; i += PS_THREADS) {
+                const int pl = i / E, j = i - pl * E, p = p0 + pl, k = stride * (j + 1) - 1;
+                auto qx = [&](int s) { return (double)at(s, p, k)[0]; };
+                auto qy = [&](int s) { return (double)at(s, p, k)[1]; };
+                bool vx, vy;
+                const double bx = ps_bandwidth(S, D.scott, qx, &vx), by = ps_bandwidth(S, D.scott, qy, &vy);
+                varies |= vx || vy;
+                ll += ps_log_p(S, qx, qy, s_g[i * 2], s_g[i * 2 + 1], bx, by);
+            }
+    }
+    const double w_a = wave_sum_f64(agent_a), w_f = wave_sum_f64(agent_f), w_l = wave_sum_f64(ll);
+    if (lane == 0) { s_part[0][wave] = w_a; s_part[1][wave] = w_f; s_part[2][wave] = w_l; }
+    varies = __syncthreads_or(varies);                               // (also orders s_part and s_scene for thread 0)
+    nonfinite = __syncthreads_or(nonfinite);
+    if (tid != 0) return;
+    double tot[3];
+    for (int q = 0; q < 3; ++q) {
+        tot[q] = s_part[q][0];
+        for (int w = 1; w < PS_WAVES; ++w) tot[q] += s_part[q][w];
+    }
+    fot_pred_score r;
+    r.ade_scene = r.fde_scene = 0.0;
+    for (int s = 0; s < S; ++s) {
+        double a = s_scene[0][s][0], f = s_scene[1][s][0];
+        for (int w = 1; w < PS_WAVES; ++w) { a += s_scene[0][s][w]; f += s_scene[1][s][w]; }
+        a /= (double)P * (double)E; f /= (double)P;
+        r.ade_scene = s == 0 ? a : ps_min(r.ade_scene, a);
+        r.fde_scene = s == 0 ? f : ps_min(r.fde_scene, f);
+    }
+    r.ade_agent_sum = tot[0]; r.fde_agent_sum = tot[1];
+    r.log_lik_sum = varies ? tot[2] : 0.0;
+    r.n_peds = P; r.n_samples = S;
+    r.nll_count = varies ? P * E : 0;
+    r.flags = (varies ? PS_FLAG_NLL : 0) | (nonfinite ? PS_FLAG_NONFINITE : 0);
+    out[blockIdx.x] = r;
+}
+
+// ---------------------------------------------------------------------------
+// safety metrics, one wave per ego, lanes over (footprint circle, pedestrian) pairs
+// ---------------------------------------------------------------------------
+
+__device__ __forceinline__ double wave_min_f64(double v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmin(v, __shfl_xor(v, off, WAVE));
+    return v;
+}
+
+__global__ void __launch_bounds__(WAVE)
+k_safety(const DevParams *__restrict__ Pp, int n, const double *__restrict__ ego, const int32_t *__restrict__ ped_off,
+         const double *__restrict__ ped_pos, const double *__restrict__ ped_vel, double ego_radius, double ped_radius,
+         double footprint_radius, int use_fp, fot_safety *__restrict__ out, const int32_t *__restrict__ ep_scen,
+         const SafetyScen *__restrict__ scen_tab)
+{
+    const int e = blockIdx.x;
+    if (e >= n) return;
+    // a scenario loop: the episode's scenario picks the constants, the footprint radius and the flag.  One episode = one
+    // workgroup of one wave, so the id and everything read through it are wave-uniform (scalar loads).
+    if (ep_scen) {
+        const int scen = ep_scen[e];
+        Pp += scen;
+        footprint_radius = scen_tab[scen].footprint_radius;
+        use_fp = scen_tab[scen].use_fp;
+    }
+    const DevParams &P = *Pp;
+    const double x = ego[4 * e], y = ego[4 * e + 1], yaw = ego[4 * e + 2], v = ego[4 * e + 3];
+    const double hx = cos(yaw), hy = sin(yaw);
+    const bool fp = use_fp && P.has_footprint;
+    const int nc = fp ? P.n_circ : 1;
+    const double combined = (fp ? footprint_radius : ego_radius) + ped_radius;
+    const int p0 = ped_off[e], np_ = ped_off[e + 1] - p0;
+    double min_d = INFINITY, ttc = INFINITY, ahead = INFINITY;
+    for (int i = threadIdx.x; i < nc * np_; i += WAVE) {
+        const int c = i / np_, p = i - c * np_;
+        const double off = fp ? P.circ_off[c] : 0.0;
+        const double cx = x + off * hx, cy = y + off * hy;                      // footprint.py:42-45
+        const double px = ped_pos[2 * (p0 + p)], py = ped_pos[2 * (p0 + p) + 1];
+        const double rx = px - cx, ry = py - cy;
+        const double dist = sqrt(rx * rx + ry * ry);
+        min_d = fmin(min_d, dist);
+        const double vx = ped_vel[2 * (p0 + p)] - v * hx, vy = ped_vel[2 * (p0 + p) + 1] - v * hy;
+        const double along = -(rx * vx + ry * vy) / (dist + 1e-8);
+        if (along > 1e-5) {
+            const double t = (dist - combined) / along;
+            if (t >= 0.0) ttc = fmin(ttc, t);
+        }
+        if ((px - x) * hx + (py - y) * hy > 0.0) ahead = fmin(ahead, dist);      // strictly ahead of the vehicle centre
+    }
+    min_d = wave_min_f64(min_d); ttc = wave_min_f64(ttc); ahead = wave_min_f64(ahead);
+    if (threadIdx.x == 0) {
+        fot_safety r;
+        r.min_distance = min_d; r.ttc = ttc; r.clearance = min_d - combined;
+        r.clearance_ahead = isinf(ahead) ? INFINITY : ahead - combined;
+        r.collision = min_d < combined ? 1 : 0; r._pad = 0;
+        out[e] = r;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// fot_loop_run: the step's frame from the resident recording, the records' digests, the history of followed paths
+// ---------------------------------------------------------------------------
+
+// One workgroup per running episode.  Its rows of the recording -- current positions and velocities at frame f_cur, the
+// observer's last two samples at f_last / f_prev, each clamped to the slot's own recording -- go into the compacted
+// frame as 16-byte rows; thread 0 moves the episode's entries of the host's tables into HBM.
+__global__ void __launch_bounds__(WAVE)
+k_loop_frame(ReplayView rv, FrameStage in, FrameDev out, int n_run, int f_cur, int f_last, int f_prev)
+{
+    const int i = blockIdx.x;
+    if (i >= n_run) return;
+    const int slot = in.slot[i], q0 = in.ped0[i], q1 = in.ped0[i + 1];
+    const int c0 = rv.slot_ped0[slot], last_row = rv.slot_frames[slot] - 1;
+    const int64_t cols = rv.n_cols;
+    const double2 *pos = (const double2 *)rv.pos, *vel = (const double2 *)rv.vel;
+    const int64_t r_cur = (int64_t)min(f_cur, last_row) * cols + c0;
+    const int64_t r_last = (int64_t)min(max(f_last, 0), last_row) * cols + c0;
+    const int64_t r_prev = (int64_t)min(max(f_prev, 0), last_row) * cols + c0;
+    for (int p = threadIdx.x; p < q1 - q0; p += WAVE) {
+        const int q = q0 + p;
+        ((double2 *)out.pos)[q] = pos[r_cur + p];
+        ((double2 *)out.vel)[q] = vel[r_cur + p];
+        out.ped_ep[q] = i;
+        if (f_last >= 0) {
+            const double2 l = pos[r_last + p];
+            double2 w; w.x = (double)(float)l.x; w.y = (double)(float)l.y;     // the observer hands over float32 (observer.py:134)
+            ((double2 *)out.last)[q] = w;
+            double2 u = w;                                               // (no second sample: zero velocity)
+            if (f_prev >= 0) { const double2 v = pos[r_prev + p]; u.x = (double)(float)v.x; u.y = (double)(float)v.y; }
+            ((double2 *)out.prev)[q] = u;
+        }
+    }
+    if (threadIdx.x == 0) {
+        out.ped0[i] = q0; out.blk[i] = in.blk[i]; out.prepend[i] = in.prepend[i];
+        if (i == n_run - 1) { out.ped0[n_run] = q1; out.blk[n_run] = in.blk[n_run]; }
+    }
+    if (threadIdx.x < 4) out.ego[4 * i + threadIdx.x] = in.ego[4 * i + threadIdx.x];
+    if (in.scen && threadIdx.x == 0) out.scen[i] = in.scen[i];
+}
+
+namespace {
+
+constexpr int SR_THREADS = 256;
+
+// One thread per (sample s, predictor step j, frame row q) element of two coordinates, rows innermost: a wave reads and
+// writes runs of neighbouring pedestrians, 8 bytes (float32) or 16 bytes (float64) a lane.  The place in the recording
+// is fot_samplerec.hpp's, 64-bit throughout; nothing but the element's own lane index decides what a lane moves.
+template <class V>
+__global__ __launch_bounds__(SR_THREADS) void k_loop_sample_rows(LoopSampleRows a)
+{
+    const int64_t t = (int64_t)blockIdx.x * SR_THREADS + threadIdx.x;
+    if (t >= sr_step_elems(a.d)) return;
+    int32_t s, j, q;
+    sr_split(a.d, t, s, j, q);
+    ((V *)a.out)[t] = ((const V *)a.rec)[sr_src_elem(a.d, s, j, a.col[q])];    // (t = sr_dst_elem(a.d, s, j, q))
+}
+
+}  // namespace
+
+// One workgroup per request of a scenario loop: its scenario's static points, resident once in HBM, into the request's
+// own run of the block k_cull reads (fot_batch::static_off layout).  16-byte rows, coalesced both ways.
+__global__ void __launch_bounds__(256)
+k_static_gather(const StaticGather *__restrict__ tab, int n_req, const double2 *__restrict__ points, double2 *__restrict__ out)
+{
+    const int j = blockIdx.x;
+    if (j >= n_req) return;
+    const int src = tab[j].src, dst = tab[j].dst, n = tab[j].n;
+    for (int p = threadIdx.x; p < n; p += 256) out[dst + p] = points[src + p];
+}
+
+// one thread per (row, axis) of the frame; the arithmetic of k_resample's cv = 2 path, operation for operation
+__global__ void k_predict_cv_frame(double sgan_dt, double sim_dt, double staleness, int n_rows, int n_dense, FrameDev f,
+                                   double *__restrict__ out)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n_rows * 2) return;
+    const int ax = idx & 1, p = idx >> 1;
+    const int e = f.ped_ep[p], p0 = f.ped0[e], pre = f.prepend[e] ? 1 : 0;
+    const int T = n_dense + pre;
+    double *dst = out + 2 * (f.blk[e] + (int64_t)(p - p0) * T) + ax;
+    if (pre) dst[0] = f.pos[2 * p + ax];
+    dst += 2 * pre;
+    const double cur = f.last[2 * p + ax];                          // obs_last
+    const double vel = (double)(((float)cur - (float)f.prev[2 * p + ax]) / (float)sgan_dt);
+    for (int i = 0; i < n_dense; ++i) {
+        const double t = (sim_dt + (double)i * sim_dt) + staleness;
+        dst[2 * i] = (double)(cur + vel * t);
+    }
+}
+
+// One workgroup: eight lanes per record, one 16-byte store each into the pinned digest; every wave releases its stores
+// at system scope before the barrier behind which thread 0 raises the completion word the host polls (the ordering of
+// record_written, for any number of records).
+__global__ void __launch_bounds__(256)
+k_loop_digest(const fot_result *__restrict__ rec, int n, LoopDigest *out, int32_t *done, int32_t seq)
+{
+    for (int c = threadIdx.x; c < 8 * n; c += 256) {
+        const int r = c >> 3, j = c & 7;
+        double2 v;
+        if (j < 5) v = ((const double2 *)(rec + r))[j];                   // the header up to new_prev_s, as it is
+        else if (j == 5) { v.x = rec[r].x[1]; v.y = rec[r].y[1]; }
+        else if (j == 6) { v.x = rec[r].yaw[1]; v.y = rec[r].v[1]; }
+        else { v.x = rec[r].a[1]; v.y = 0.0; }
+        ((double2 *)(out + r))[j] = v;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Workgroup i copies the followed record of running episode i into the step's history block; workgroup 0 first raises
+// the step's completion word: this launch runs behind the step's last kernels on its stream, whose results in pinned
+// memory are complete when it starts.
+__global__ void __launch_bounds__(256)
+k_loop_history(const fot_result *__restrict__ rec, int n_run, const int32_t *__restrict__ src,
+               const int32_t *__restrict__ slot, double *__restrict__ hist, int n_slots, int n_total, int32_t *done,
+               int32_t seq)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    const int i = blockIdx.x;
+    if (!hist || i >= n_run) return;
+    const int r = src[i];
+    if (r < 0) return;
+    const double *from = rec[r].t;                                   // the 15 arrays lie back to back, FOT_MAX_NT apart
+    double *to = hist + (int64_t)slot[i] * n_total;
+    for (int c = threadIdx.x; c < 15 * n_total; c += 256) {
+        const int f = c / n_total, k = c - f * n_total;
+        to[(int64_t)f * n_slots * n_total + k] = from[f * FOT_MAX_NT + k];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// fot_loop_summaries: the prediction error of a resident loop, accumulated while it runs (fot_summary.hpp)
+// ---------------------------------------------------------------------------
+
+// One workgroup per running episode, behind the step's prediction.  Row c[k] = sum_p |pred[p][k] - recording[f_cur + 1 +
+// k][p]| of this step goes into place step % n_dense of the slot's ring; the row it replaces -- the one of step - n_dense,
+// whose horizon is complete now -- is folded into the slot's totals first, by thread 0 from a copy in LDS.
+// Lanes: G = the power of two >= P (at most 64) lanes side by side take the pedestrians of one dense sample, so a
+// recording row's [P][2] run is read as adjacent 16-byte loads; 256 / G samples are in flight per pass.  The sum over the
+// pedestrians is a butterfly over the G lanes: its order depends on P alone, never on the other slots or on timing.
+__global__ void __launch_bounds__(256)
+k_loop_pred_error(ReplayView rv, const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn, int n_run,
+                  int have_pred, int f_cur, int step, SummaryShape S, double *__restrict__ ring,
+                  int32_t *__restrict__ ring_P, SummaryTotals *__restrict__ totals, const int32_t *__restrict__ best)
+{
+    __shared__ double old_row[FOT_MAX_NT];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    if (i >= n_run) return;
+    const int slot = slot_of[i], nd = S.n_dense, r = step % nd;
+    double *row = ring + ((int64_t)slot * nd + r) * nd;
+    int32_t *row_P = ring_P + (int64_t)slot * nd + r;
+    for (int k = tid; k < nd; k += 256) old_row[k] = row[k];
+    __syncthreads();
+    const int p0 = f.ped0[i], P = have_pred ? f.ped0[i + 1] - p0 : 0;
+    if (tid == 0) {
+        const int old_P = *row_P;
+        if (step >= nd && old_P > 0) {
+            SummaryTotals T = totals[slot];
+            summary_fold_row(T, S, old_row, old_P, step - nd, step + 1);
+            totals[slot] = T;
+        }
+        *row_P = P > 0 ? P : 0;
+    }
+    if (P <= 0) {
+        for (int k = tid; k < nd; k += 256) row[k] = 0.0;
+        return;
+    }
+    const int pre = f.prepend[i] ? 1 : 0, T_blk = nd + pre;
+    // [P][T_blk], the prepended column skipped below; of a distribution [S][P][T_blk]: the slot's representative sample
+    const double2 *pred = (const double2 *)dyn + f.blk[i] + (best ? (int64_t)max(best[slot], 0) * P * T_blk : 0);
+    const double2 *rec = (const double2 *)rv.pos + rv.slot_ped0[slot];
+    const int last_row = rv.slot_frames[slot] - 1;
+    const int64_t cols = rv.n_cols;
+    int G = 1;
+    while (G < P && G < WAVE) G <<= 1;
+    const int per_pass = 256 / G, g = tid / G, lane = tid & (G - 1);
+    for (int base = 0; base < nd; base += per_pass) {               // (uniform trip count: every lane takes part in the butterfly)
+        const int k = base + g;
+        double acc = 0.0;
+        if (k < nd) {
+            const int64_t gt_row = (int64_t)min(f_cur + 1 + k, last_row) * cols;
+            for (int p = lane; p < P; p += G) {
+                const double2 q = pred[(int64_t)p * T_blk + pre + k], w = rec[gt_row + p];
+                acc += sqrt(sum_sq_unfused(q.x - w.x, q.y - w.y));
+            }
+        }
+        for (int m = G >> 1; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, WAVE);
+        if (k < nd && lane == 0) row[k] = acc;
+    }
+}
+
+// One workgroup per slot, on request: thread t forms the terms of the ring's t-th oldest row under the slot's current
+// length L (its truncated horizon), thread 0 adds them to a COPY of the totals in step order and writes the
+// prediction-error keys of the slot's record in pinned memory.  Ring and totals are left as they are.
+__global__ void __launch_bounds__(256)
+k_loop_summary(SummaryShape S, const double *__restrict__ ring, const int32_t *__restrict__ ring_P,
+               const SummaryTotals *__restrict__ totals, const int32_t *__restrict__ steps, int n_slots, int num_samples,
+               fot_loop_summary *out)
+{
+    __shared__ SummaryTerms terms[FOT_MAX_NT];
+    const int slot = blockIdx.x, tid = threadIdx.x;
+    if (slot >= n_slots) return;
+    const int L = steps[slot], nd = S.n_dense;
+    const int first = L > nd ? L - nd : 0, n_tail = L - first;
+    for (int t = tid; t < n_tail; t += 256) {
+        const int i = first + t, r = i % nd;
+        terms[t] = summary_row_terms(S, ring + ((int64_t)slot * nd + r) * nd, ring_P[(int64_t)slot * nd + r], i, L);
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    SummaryTotals T = totals[slot];
+    for (int t = 0; t < n_tail; ++t) summary_add_terms(T, terms[t]);
+    double m[4];
+    summary_means(T, m);
+    fot_loop_summary *o = out + slot;
+    o->ade = m[0]; o->fde = m[1]; o->ade_per_agent = m[0]; o->fde_per_agent = m[1];
+    o->planning_ade = m[2]; o->planning_fde = m[3];
+    o->nll = __builtin_nan("");
+    o->pred_samples = T.std_count > 0 ? num_samples : 0;
+    o->ade_eval_count = (int32_t)T.std_count; o->planning_eval_count = (int32_t)T.plan_count;
+    o->nll_eval_count = 0;
+}
+
+// ---------------------------------------------------------------------------
+// fot_loop_scores_enable (fot_loopscore.hpp): a resident sampler loop scores its predictor while it runs
+// ---------------------------------------------------------------------------
+
+// One workgroup per running episode, behind the ragged resample: the representative sample of the episode's
+// [S][P][n_dense + 1][2] block (predict_single_best).  Lanes run over the (p, k) points of the dense tracks, 256 a pass
+// (adjacent lanes: adjacent samples k of a track); a lane forms its point's mean over the samples in index order, then
+// its deviation from every sample; the lanes of a wave meet in a butterfly per sample and pass, the passes add up in a
+// slot of LDS per (sample, wave), the waves in index order: the order of every sum follows from (S, P, n_dense) alone,
+// so an episode chooses the same sample alone and in any batch.  An episode without pedestrians has no distribution: -1.
+constexpr int BS_THREADS = 256;
+constexpr int BS_WAVES = BS_THREADS / WAVE;
+
+__global__ void __launch_bounds__(BS_THREADS)
+k_loop_best_sample(const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn, int n_run, int S,
+                   int n_dense, double *__restrict__ dev_tab, int32_t *__restrict__ best_tab, int32_t *best_host)
+{
+    __shared__ double s_part[FOT_MAX_SAMPLES][BS_WAVES];
+    __shared__ double s_dev[FOT_MAX_SAMPLES];
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    if (i >= n_run) return;
+    const int slot = slot_of[i], p0 = f.ped0[i], P = f.ped0[i + 1] - p0;
+    if (P <= 0) {                                                    // (uniform)
+        if (tid == 0) { best_tab[slot] = -1; best_host[slot] = -1; }
+        return;
+    }
+    const int T = n_dense + 1, n = P * n_dense;
+    const int64_t sample_pts = (int64_t)P * T;
+    const double2 *blk = (const double2 *)dyn + f.blk[i];
+    for (int c = tid; c < FOT_MAX_SAMPLES * BS_WAVES; c += BS_THREADS) (&s_part[0][0])[c] = 0.0;
+    __syncthreads();
+    for (int base = 0; base < n; base += BS_THREADS) {               // (uniform trip count: the butterflies)
+        const int idx = base + tid;
+        const bool active = idx < n;
+        const int p = idx / n_dense, k = idx - p * n_dense;
+        const double2 *e = blk + (int64_t)p * T + 1 + k;             // sample s: e[s * sample_pts]; the prepended entry skipped
+        double mx = 0.0, my = 0.0;
+        if (active) {
+            for (int s = 0; s < S; ++s) {
+                const double2 v = e[s * sample_pts];
+                mx += v.x; my += v.y;
+            }
+            mx /= (double)S; my /= (double)S;
+        }
+        for (int s = 0; s < S; ++s) {
+            double d = 0.0;
+            if (active) {
+                const double2 v = e[s * sample_pts];
+                d = bs_dev(v.x, v.y, mx, my);
+            }
+            d = wave_sum_f64(d);
+            if (lane == 0) s_part[s][wave] += d;                     // (this wave's own column)
+        }
+    }
+    __syncthreads();
+    if (tid < S) {
+        double t = s_part[tid][0];
+        for (int w = 1; w < BS_WAVES; ++w) t += s_part[tid][w];
+        s_dev[tid] = t;
+        dev_tab[(int64_t)slot * FOT_MAX_SAMPLES + tid] = t;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int best = bs_first_min(S, s_dev);
+        best_tab[slot] = best; best_host[slot] = best;
+    }
+}
+
+// One thread per (row of the frame, evaluation step j): the truth of the step's origins, [rows][E][2], from the resident
+// recording -- row min(f_cur + stride (j + 1), frames - 1) of the pedestrian's slot (a shorter recording holds its last frame).
+__global__ void __launch_bounds__(256)
+k_loop_score_truth(ReplayView rv, const int32_t *__restrict__ slot_of, FrameDev f, int n_rows, int f_cur, int stride, int E,
+                   double2 *__restrict__ out)
+{
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n_rows * E) return;
+    const int p = idx / E, j = idx - p * E;
+    const int e = f.ped_ep[p], slot = slot_of[e];
+    const int row = min(f_cur + stride * (j + 1), rv.slot_frames[slot] - 1);
+    out[idx] = ((const double2 *)rv.pos)[(int64_t)row * rv.n_cols + rv.slot_ped0[slot] + (p - f.ped0[e])];
+}
+
+// ---------------------------------------------------------------------------
+// fot_loop_plan_sample (fot_repsample.hpp): the step's requests plan against every episode's representative sample
+// ---------------------------------------------------------------------------
+
+// One workgroup per running episode, behind k_loop_best_sample: the episode's [P][n_dense + 1][2] planning block from
+// sample best_tab[slot] of its [S][P][n_dense + 1][2] distribution block.  The lanes first AND np.allclose(first dense
+// sample, current position) over the episode's pedestrians (a ballot per wave, the waves' answers side by side in LDS: no
+// atomics, the same answer for any number of lanes), then copy: adjacent lanes take adjacent time entries of a track, one double2 each.  The flag goes to
+// pre_dev[i] (HBM) and pre_host[i] (pinned).  An episode without pedestrians writes nothing.
+constexpr int RB_THREADS = 256;
+
+__global__ void __launch_bounds__(RB_THREADS)
+k_loop_rep_block(const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn,
+                 const int32_t *__restrict__ best_tab, int n_run, int S, int n_dense, double *__restrict__ rep,
+                 int32_t *__restrict__ pre_dev, int32_t *pre_host)
+{
+    __shared__ int s_far[RB_THREADS / WAVE];
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    if (i >= n_run) return;
+    const int p0 = f.ped0[i], P = f.ped0[i + 1] - p0;
+    if (P <= 0) return;                                              // (uniform)
+    const int T = n_dense + 1, n = P * T;
+    const int best = min(max(best_tab[slot_of[i]], 0), S - 1);       // (k_loop_best_sample's choice: always in range)
+    const double2 *src = (const double2 *)dyn + f.blk[i] + (int64_t)best * P * T;
+    const double2 *cur = (const double2 *)f.pos + p0;
+    int close = 1;
+    for (int p = tid; p < P; p += RB_THREADS) {
+        const double2 a = src[(int64_t)p * T + 1], c = cur[p];
+        close &= rs_close_xy(a.x, a.y, c.x, c.y) ? 1 : 0;
+    }
+    // the vote: every wave's ballot into its own slot of LDS (plain stores), every lane reads all of them
+    const unsigned long long far_lanes = __ballot(close == 0);
+    if (lane == 0) s_far[wave] = far_lanes != 0ull ? 1 : 0;
+    __syncthreads();
+    int far = 0;
+    for (int w = 0; w < RB_THREADS / WAVE; ++w) far |= s_far[w];
+    const bool prepend = far != 0;
+    double2 *out = (double2 *)rep + (int64_t)p0 * T;
+    for (int idx = tid; idx < n; idx += RB_THREADS) {
+        const int p = idx / T, t = idx - p * T;
+        out[idx] = prepend && t == 0 ? cur[p] : src[(int64_t)p * T + rs_src(t, T, prepend)];
+    }
+    if (tid == 0) { pre_dev[i] = prepend ? 1 : 0; pre_host[i] = prepend ? 1 : 0; }
+}
+
+// ---------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------
+
+#define FOT_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
+
+int launch_resample(double sgan_dt, double sim_dt, double staleness, int S, int pred_len, int P, int n_dense,
+                    int has_anchor, int prepend, int cv, const void *pred, int pred_dtype, const double *anchor,
+                    const double *current, void *out, int out_dtype, int tmajor, hipStream_t st,
+                    const int32_t *ped_ep, const int32_t *ep_ped0, const int64_t *ep_blk)
+{
+    const int total = S * P * 2;
+    if (total <= 0) return 0;
+    ResampleArgs A;
+    A.sgan_dt = sgan_dt; A.sim_dt = sim_dt; A.staleness = staleness;
+    A.S = S; A.pred_len = pred_len; A.P = P; A.n_dense = n_dense; A.T = n_dense + (prepend ? 1 : 0);
+    A.has_anchor = has_anchor; A.prepend = prepend; A.cv = cv; A.tmajor = tmajor;
+    A.ped_ep = ped_ep; A.ep_ped0 = ep_ped0; A.ep_blk = ep_blk;
+    if (ped_ep && tmajor) return (int)hipErrorInvalidValue;
+    const int bs = 128, grid = (total + bs - 1) / bs;
+    if (pred_dtype == FOT_F32 && out_dtype == FOT_F32)
+        k_resample<float, float><<<grid, bs, 0, st>>>(A, (const float *)pred, anchor, current, (float *)out);
+    else if (pred_dtype == FOT_F32)
+        k_resample<float, double><<<grid, bs, 0, st>>>(A, (const float *)pred, anchor, current, (double *)out);
+    else if (out_dtype == FOT_F32)
+        k_resample<double, float><<<grid, bs, 0, st>>>(A, (const double *)pred, anchor, current, (float *)out);
+    else
+        k_resample<double, double><<<grid, bs, 0, st>>>(A, (const double *)pred, anchor, current, (double *)out);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_sample_dist(int S, int P, int T, int skip, const void *out, int out_dtype, int tmajor, double *dist,
+                       hipStream_t st)
+{
+    if (S <= 0) return 0;
+    if (out_dtype == FOT_F32) k_sample_dist<float><<<S, 256, 0, st>>>(S, P, T, skip, tmajor, (const float *)out, dist);
+    else k_sample_dist<double><<<S, 256, 0, st>>>(S, P, T, skip, tmajor, (const double *)out, dist);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_pred_scores(const PredOriginDev *desc, int n, const void *tensor, int dtype, int stride, int E,
+                       const double *truth, fot_pred_score *out, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    if (dtype == FOT_F32) k_pred_scores<float><<<n, PS_THREADS, 0, st>>>(desc, (const float *)tensor, stride, E, truth, out);
+    else k_pred_scores<double><<<n, PS_THREADS, 0, st>>>(desc, (const double *)tensor, stride, E, truth, out);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_safety(const DevParams *P, int n, const double *ego, const int32_t *ped_off, const double *ped_pos,
+                  const double *ped_vel, double ego_radius, double ped_radius, double footprint_radius, int use_fp,
+                  fot_safety *out, hipStream_t st, const int32_t *ep_scen, const SafetyScen *scen_tab)
+{
+    if (n <= 0) return 0;
+    if (!scen_tab) ep_scen = nullptr;
+    k_safety<<<n, WAVE, 0, st>>>(P, n, ego, ped_off, ped_pos, ped_vel, ego_radius, ped_radius, footprint_radius, use_fp, out,
+                                 ep_scen, scen_tab);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_static_gather(const StaticGather *tab, int n_req, const double *points, double *out, hipStream_t st)
+{
+    if (n_req <= 0) return 0;
+    k_static_gather<<<n_req, 256, 0, st>>>(tab, n_req, (const double2 *)points, (double2 *)out);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_frame(ReplayView rv, FrameStage in, FrameDev out, int n_run, int f_cur, int f_last, int f_prev,
+                      hipStream_t st)
+{
+    if (n_run <= 0) return 0;
+    k_loop_frame<<<n_run, WAVE, 0, st>>>(rv, in, out, n_run, f_cur, f_last, f_prev);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_sample_rows(const LoopSampleRows &a, hipStream_t st)
+{
+    const int64_t total = sr_step_elems(a.d);
+    if (total <= 0) return 0;
+    const unsigned grid = (unsigned)((total + SR_THREADS - 1) / SR_THREADS);
+    if (a.dtype == FOT_F32) k_loop_sample_rows<float2><<<grid, SR_THREADS, 0, st>>>(a);
+    else k_loop_sample_rows<double2><<<grid, SR_THREADS, 0, st>>>(a);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_predict_cv_frame(double sgan_dt, double sim_dt, double staleness, int n_rows, int n_dense, FrameDev f,
+                            double *out, hipStream_t st)
+{
+    if (n_rows <= 0) return 0;
+    const int bs = 128, grid = (2 * n_rows + bs - 1) / bs;
+    k_predict_cv_frame<<<grid, bs, 0, st>>>(sgan_dt, sim_dt, staleness, n_rows, n_dense, f, out);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_digest(const fot_result *rec, int n, LoopDigest *out, int32_t *done, int32_t seq, hipStream_t st)
+{
+    k_loop_digest<<<1, 256, 0, st>>>(rec, n > 0 ? n : 0, out, done, seq);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_history(const fot_result *rec, int n_run, const int32_t *src, const int32_t *slot, double *hist,
+                        int n_slots, int n_total, int32_t *done, int32_t seq, hipStream_t st)
+{
+    const int grid = hist && n_run > 0 ? n_run : 1;
+    k_loop_history<<<grid, 256, 0, st>>>(rec, n_run, src, slot, hist, n_slots, n_total, done, seq);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_pred_error(ReplayView rv, const int32_t *slot_of, FrameDev f, const double *dyn, int n_run, int have_pred,
+                           int f_cur, int step, SummaryShape S, double *ring, int32_t *ring_P, SummaryTotals *totals,
+                           hipStream_t st, const int32_t *best)
+{
+    if (n_run <= 0) return 0;
+    if (S.n_dense < 1 || S.n_dense > FOT_MAX_NT || step < 0) return (int)hipErrorInvalidValue;
+    k_loop_pred_error<<<n_run, 256, 0, st>>>(rv, slot_of, f, dyn, n_run, have_pred, f_cur, step, S, ring, ring_P, totals, best);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_best_sample(const int32_t *slot_of, FrameDev f, const double *dyn, int n_run, int S, int n_dense,
+                            double *dev_tab, int32_t *best_tab, int32_t *best_host, hipStream_t st)
+{
+    if (n_run <= 0) return 0;
+    if (S < 1 || S > FOT_MAX_SAMPLES || n_dense < 1) return (int)hipErrorInvalidValue;
+    k_loop_best_sample<<<n_run, BS_THREADS, 0, st>>>(slot_of, f, dyn, n_run, S, n_dense, dev_tab, best_tab, best_host);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_rep_block(const int32_t *slot_of, FrameDev f, const double *dyn, const int32_t *best_tab, int n_run, int S,
+                          int n_dense, double *rep, int32_t *pre_dev, int32_t *pre_host, hipStream_t st)
+{
+    if (n_run <= 0) return 0;
+    if (S < 1 || S > FOT_MAX_SAMPLES || n_dense < 1) return (int)hipErrorInvalidValue;
+    k_loop_rep_block<<<n_run, RB_THREADS, 0, st>>>(slot_of, f, dyn, best_tab, n_run, S, n_dense, rep, pre_dev, pre_host);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_score_truth(ReplayView rv, const int32_t *slot_of, FrameDev f, int n_rows, int f_cur, int stride, int E,
+                            double *out, hipStream_t st)
+{
+    if (n_rows <= 0) return 0;
+    if (stride < 1 || E < 1 || E > FOT_MAX_PRED_LEN) return (int)hipErrorInvalidValue;
+    const int n = n_rows * E;
+    k_loop_score_truth<<<(n + 255) / 256, 256, 0, st>>>(rv, slot_of, f, n_rows, f_cur, stride, E, (double2 *)out);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_summary(SummaryShape S, const double *ring, const int32_t *ring_P, const SummaryTotals *totals,
+                        const int32_t *steps, int n_slots, int num_samples, fot_loop_summary *out, hipStream_t st)
+{
+    if (n_slots <= 0) return 0;
+    if (S.n_dense < 1 || S.n_dense > FOT_MAX_NT) return (int)hipErrorInvalidValue;
+    k_loop_summary<<<n_slots, 256, 0, st>>>(S, ring, ring_P, totals, steps, n_slots, num_samples, out);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace fot

@@ -1,11 +1,10 @@
-// fot_sgan.h -- launchers of the Social-GAN kernels and of the resident loop's sample gathers (fot_sgan.hip) for the host
+// fot_sgan.h -- launchers of the Social-GAN kernels and of the resident loop's observer window (fot_sgan.hip) for the host
 // side (fot_host.cpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "fot_noise.hpp"
-#include "fot_samplerec.hpp"
 #include "fot_sgan.hpp"
 
 namespace fot {
@@ -50,20 +49,8 @@ struct SgWindow {
     float *out;                              // [obs_len][rows][2]
 };
 
-// fot_loop_set_samples: row d.rec_row of the recording rec [n_steps][S][pred_len][n_cols][2] -> the step's raw samples
-// out [S][pred_len][rows][2] of the running slots, both of element type dtype (FOT_F32 | FOT_F64); row q of the frame is
-// column col[q] of the recording (HBM; fot_samplerec.hpp's sr_fill_columns).  rec is only read.
-struct LoopSampleRows {
-    SampleRecDims d;
-    const void *rec;
-    const int32_t *col;                      // [rows]
-    void *out;
-    int32_t dtype, _pad;
-};
-
 int launch_sgan_noise(const SgNoise &a, hipStream_t st);
 int launch_sgan_window(const SgWindow &a, hipStream_t st);
-int launch_loop_sample_rows(const LoopSampleRows &a, hipStream_t st);
 int launch_sgan_encode(const float *img, const SgDevLstm &l, int E, int H, int obs_len, int N, const float *obs, float *henc,
                        hipStream_t st);
 // h [S][N][p.h_dim], pos [S][N][2] -> out [S][N][p.b_pad], which the caller has zeroed

@@ -8,8 +8,6 @@
 //                   every step -- one step per launch, the state in HBM between the launches
 //   k_sgan_noise    fot_sgan_noise: one thread per (sample, row, block of four noise dimensions), fot_noise.hpp's Philox
 //   k_sgan_window   the resident loop's observer window [obs_len][rows][2] float32 out of the recording in HBM
-//   k_loop_sample_rows  its sibling for a loop that predicts from recorded samples (fot_loop_set_samples): a step's raw
-//                   samples [S][pred_len][rows][2] of the running slots out of the recorded tensor in HBM
 // A thread owns an output element and adds its terms in index order; several rows share one read of a weight.  Plain
 // float32 VALU: the f32-input MFMA forms of gfx950 run at the vector rate.
 #include <hip/hip_runtime.h>
@@ -345,19 +343,6 @@ __global__ __launch_bounds__(SG_THREADS) void k_sgan_window(SgWindow a)
     ((float2 *)a.out)[t] = w;
 }
 
-// One thread per (sample s, predictor step j, frame row q) element of two coordinates, rows innermost: a wave reads and
-// writes runs of neighbouring pedestrians, 8 bytes (float32) or 16 bytes (float64) a lane.  The place in the recording
-// is fot_samplerec.hpp's, 64-bit throughout; nothing but the element's own lane index decides what a lane moves.
-template <class V>
-__global__ __launch_bounds__(SG_THREADS) void k_loop_sample_rows(LoopSampleRows a)
-{
-    const int64_t t = (int64_t)blockIdx.x * SG_THREADS + threadIdx.x;
-    if (t >= sr_step_elems(a.d)) return;
-    int32_t s, j, q;
-    sr_split(a.d, t, s, j, q);
-    ((V *)a.out)[t] = ((const V *)a.rec)[sr_src_elem(a.d, s, j, a.col[q])];    // (t = sr_dst_elem(a.d, s, j, q))
-}
-
 }  // namespace
 
 #define FOT_SG_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
@@ -412,17 +397,6 @@ int launch_sgan_window(const SgWindow &a, hipStream_t st)
     const int64_t total = (int64_t)a.obs_len * a.rows;
     if (total <= 0) return 0;
     k_sgan_window<<<(unsigned)((total + SG_THREADS - 1) / SG_THREADS), SG_THREADS, 0, st>>>(a);
-    FOT_SG_LAUNCH_CHECK();
-    return 0;
-}
-
-int launch_loop_sample_rows(const LoopSampleRows &a, hipStream_t st)
-{
-    const int64_t total = sr_step_elems(a.d);
-    if (total <= 0) return 0;
-    const unsigned grid = (unsigned)((total + SG_THREADS - 1) / SG_THREADS);
-    if (a.dtype == FOT_F32) k_loop_sample_rows<float2><<<grid, SG_THREADS, 0, st>>>(a);
-    else k_loop_sample_rows<double2><<<grid, SG_THREADS, 0, st>>>(a);
     FOT_SG_LAUNCH_CHECK();
     return 0;
 }

@@ -2,7 +2,7 @@
 
 ``compute_safety_metrics_static`` has the signature and result dictionary of
 src/core/data_structures.py:301-388; the arithmetic runs in ``k_safety``
-(csrc/fot_kernels.hip), one wavefront per ego, through ``fot_safety_metrics_batch``.
+(csrc/fot_loop_kernels.hip), one wavefront per ego, through ``fot_safety_metrics_batch``.
 ``SafetyMonitor.metrics_batch`` is the many-ego form the reference lacks.
 """
 from __future__ import annotations
