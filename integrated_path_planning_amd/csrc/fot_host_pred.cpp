@@ -1,0 +1,491 @@
+// fot_host_pred.cpp -- the entry points of libfot.so that predict or score without keeping loop state: the resampler and
+// the constant-velocity predictor, the safety metrics, the prediction scores and the Social-GAN sampler.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "fot_host.hpp"
+#include "fot_loop_kernels.h"
+#include "fot_sgan.h"
+
+namespace {
+
+// shared body of fot_resample_predictions (cv = 0) and fot_predict_cv (cv = 1: anchor = obs_last, pred = obs_prev)
+int resample_common(fot_handle *h, const fot_resample_params *rp, int cv, int32_t S, int32_t pred_len, int32_t P,
+                    const void *pred, int32_t pred_dtype, const double *anchor, const double *current,
+                    double staleness, void *out, int32_t out_dtype, int32_t on_device, int32_t *T_out,
+                    double *sample_dist, void *stream)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (!rp || !(rp->sim_dt > 0.0) || !(rp->sgan_dt > 0.0)) return fail(h, FOT_ERR_INVALID, "sgan_dt and sim_dt must be positive");
+    if (S < 0 || P < 0 || pred_len < 1) return fail(h, FOT_ERR_INVALID, "bad S / P / pred_len");
+    if (pred_len > FOT_MAX_PRED_LEN) return fail(h, FOT_ERR_UNSUPPORTED, "pred_len > FOT_MAX_PRED_LEN");
+    if ((pred_dtype != FOT_F32 && pred_dtype != FOT_F64) || (out_dtype != FOT_F32 && out_dtype != FOT_F64))
+        return fail(h, FOT_ERR_INVALID, "dtype");
+    const int n_dense = resample_n_dense(rp->sgan_dt, rp->sim_dt, rp->plan_horizon, pred_len);
+    const int T = n_dense + (current ? 1 : 0);
+    if (T > FOT_MAX_NT) return fail(h, FOT_ERR_UNSUPPORTED, "more than FOT_MAX_NT time steps");
+    if (T_out) *T_out = T;
+    const int tmajor = (on_device & FOT_OUT_TMAJOR) ? 1 : 0;
+    on_device &= FOT_OUT_DEVICE;
+    if (S == 0 || P == 0 || T == 0) return FOT_OK;
+    if (!out || (!cv && !pred) || (cv && !anchor)) return fail(h, FOT_ERR_INVALID, "NULL tensor");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    // small per-pedestrian inputs: anchor | current  (and obs_prev for cv) through the handle's scratch
+    const size_t row = sizeof(double) * 2 * (size_t)P;
+    { int r = order_begin(h, st); if (r != FOT_OK) return r; }  // the scratch below is shared by every entry point
+    {
+        const size_t in_elem_ = pred_dtype == FOT_F32 ? 4 : 8, out_elem_ = out_dtype == FOT_F32 ? 4 : 8;
+        const size_t in_b = cv ? 0 : in_elem_ * 2 * (size_t)P * (size_t)S * pred_len;
+        const size_t out_b = out_elem_ * 2 * (size_t)S * P * T;
+        if (!on_device && 3 * align256(row) + align256(in_b) <= SMALL_CALL_BYTES &&
+            out_b + sizeof(double) * (size_t)S <= SMALL_CALL_BYTES) {
+            // small host call: everything through pinned memory the kernels access directly
+            HIP_TRY(h, h->hSmallIn.ensure(3 * align256(row) + align256(in_b)));
+            HIP_TRY(h, h->hSmallOut.ensure(align256(out_b) + sizeof(double) * (size_t)S));
+            char *p = (char *)h->hSmallIn.p;
+            const double *pa = nullptr, *pc = nullptr;
+            const void *pp = nullptr;
+            if (anchor) { std::memcpy(p, anchor, row); pa = (const double *)p; }
+            if (current) { std::memcpy(p + align256(row), current, row); pc = (const double *)(p + align256(row)); }
+            if (cv) { if (pred) { std::memcpy(p + 2 * align256(row), pred, row); pp = p + 2 * align256(row); } }
+            else { std::memcpy(p + 3 * align256(row), pred, in_b); pp = p + 3 * align256(row); }
+            char *po = (char *)h->hSmallOut.p;
+            LAUNCH_TRY(h, launch_resample(rp->sgan_dt, rp->sim_dt, staleness, S, pred_len, P, n_dense, anchor ? 1 : 0,
+                                          current ? 1 : 0, cv, pp, cv ? FOT_F64 : pred_dtype, pa, pc, po, out_dtype,
+                                          tmajor, st));
+            if (sample_dist)
+                LAUNCH_TRY(h, launch_sample_dist(S, P, T, current ? 1 : 0, po, out_dtype, tmajor,
+                                                 (double *)(po + align256(out_b)), st));
+            { int r = order_end(h, st); if (r != FOT_OK) return r; }
+            HIP_TRY(h, hipStreamSynchronize(st));
+            std::memcpy(out, po, out_b);
+            if (sample_dist) std::memcpy(sample_dist, po + align256(out_b), sizeof(double) * (size_t)S);
+            return FOT_OK;
+        }
+    }
+    HIP_TRY(h, h->dTmpA.ensure(3 * row + 64));
+    char *scr = (char *)h->dTmpA.p;
+    const double *d_anchor = nullptr, *d_current = nullptr;
+    const void *d_pred = pred;
+    if (anchor) { HIP_TRY(h, hipMemcpyAsync(scr, anchor, row, hipMemcpyHostToDevice, st)); d_anchor = (const double *)scr; }
+    if (current) { HIP_TRY(h, hipMemcpyAsync(scr + row, current, row, hipMemcpyHostToDevice, st)); d_current = (const double *)(scr + row); }
+    void *d_out = out;
+    const size_t in_elem = pred_dtype == FOT_F32 ? 4 : 8, out_elem = out_dtype == FOT_F32 ? 4 : 8;
+    const size_t in_bytes = in_elem * 2 * (size_t)P * (cv ? 1 : (size_t)S * pred_len);
+    const size_t out_bytes = out_elem * 2 * (size_t)S * P * T;
+    if (cv) {                                                      // obs_prev is a host array of doubles
+        d_pred = nullptr;
+        if (pred) { HIP_TRY(h, hipMemcpyAsync(scr + 2 * row, pred, row, hipMemcpyHostToDevice, st)); d_pred = scr + 2 * row; }
+    } else if (!on_device) {
+        HIP_TRY(h, h->dTmpB.ensure(in_bytes));
+        HIP_TRY(h, hipMemcpyAsync(h->dTmpB.p, pred, in_bytes, hipMemcpyHostToDevice, st));
+        d_pred = h->dTmpB.p;
+    }
+    if (!on_device) { HIP_TRY(h, h->dTmpC.ensure(out_bytes)); d_out = h->dTmpC.p; }
+    LAUNCH_TRY(h, launch_resample(rp->sgan_dt, rp->sim_dt, staleness, S, pred_len, P, n_dense, anchor ? 1 : 0,
+                                  current ? 1 : 0, cv, d_pred, cv ? FOT_F64 : pred_dtype, d_anchor, d_current, d_out,
+                                  out_dtype, tmajor, st));
+    if (sample_dist) {
+        HIP_TRY(h, h->dTmpD.ensure(sizeof(double) * (size_t)S));
+        LAUNCH_TRY(h, launch_sample_dist(S, P, T, current ? 1 : 0, d_out, out_dtype, tmajor, h->dTmpD.as<double>(), st));
+        HIP_TRY(h, hipMemcpyAsync(sample_dist, h->dTmpD.p, sizeof(double) * (size_t)S, hipMemcpyDeviceToHost, st));
+    }
+    if (!on_device) HIP_TRY(h, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    { int r = order_end(h, st); if (r != FOT_OK) return r; }
+    if (!on_device || sample_dist) HIP_TRY(h, hipStreamSynchronize(st));
+    return FOT_OK;
+}
+
+// Shared body of fot_prediction_scores and fot_loop_prediction_scores: `tensor` is device memory, or host memory of
+// tensor_bytes bytes to be copied first (tensor_bytes > 0).  Checks every origin before anything is enqueued or written.
+int prediction_scores_impl(fot_handle *h, const char *who, int32_t n, const fot_pred_origin *desc, const void *tensor,
+                           size_t tensor_bytes, int32_t dtype, int32_t stride, int32_t E, const double *truth,
+                           fot_pred_score *out, hipStream_t st)
+{
+    const std::string w(who);
+    if (stride < 1 || E < 1) return fail(h, FOT_ERR_INVALID, w + ": stride and E must be positive");
+    if (E > FOT_MAX_PRED_LEN) return fail(h, FOT_ERR_UNSUPPORTED, w + ": E > FOT_MAX_PRED_LEN");
+    size_t rows = 0;
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        const fot_pred_origin &d = desc[i];
+        if (d.S < 1 || d.P < 0 || d.T < 1 || d.offset < 0 || (d.skip != 0 && d.skip != 1) ||
+            (d.layout != 0 && d.layout != FOT_DYN_LAYOUT_TSP))
+            return fail(h, FOT_ERR_INVALID, w + ": an origin's S / P / T / offset / skip / layout");
+        if (!ps_horizon_fits(stride, E, d.T, d.skip))
+            return fail(h, FOT_ERR_INVALID, w + ": stride E - 1 reaches past an origin's dense track (T - skip)");
+        if (d.S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, w + ": S > FOT_MAX_SAMPLES");
+        rows += (size_t)d.P;
+        any |= d.P > 0;
+    }
+    if (!out || (any && (!truth || !tensor))) return fail(h, FOT_ERR_INVALID, w + ": NULL tensor / truth / out");
+    if (!any) {                                                    // nothing for the device to do
+        for (int i = 0; i < n; ++i) {
+            const PredScoreTerms z = ps_zero(desc[i].S);
+            out[i] = fot_pred_score{ 0.0, 0.0, 0.0, 0.0, 0.0, z.n_peds, z.n_samples, z.nll_count, z.flags };
+        }
+        return FOT_OK;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    { int r = order_begin(h, st); if (r != FOT_OK) return r; }
+    const size_t desc_b = align256(sizeof(PredOriginDev) * (size_t)n), truth_b = sizeof(double) * 2 * rows * (size_t)E;
+    HIP_TRY(h, h->hScoreIn.ensure(desc_b + truth_b));
+    HIP_TRY(h, h->hScoreOut.ensure(sizeof(fot_pred_score) * (size_t)n));
+    PredOriginDev *pd = (PredOriginDev *)h->hScoreIn.p;
+    double *pt = (double *)((char *)h->hScoreIn.p + desc_b);
+    size_t row = 0;
+    for (int i = 0; i < n; ++i) {
+        const fot_pred_origin &d = desc[i];
+        pd[i] = PredOriginDev{ d.offset, (int64_t)row, ps_scott(d.S), d.S, d.P, d.T, d.layout == FOT_DYN_LAYOUT_TSP ? 1 : 0,
+                               d.skip, 0 };
+        row += (size_t)d.P;
+    }
+    std::memcpy(pt, truth, truth_b);
+    const void *d_tensor = tensor;
+    if (tensor_bytes > 0) {
+        HIP_TRY(h, h->dScoreT.ensure(tensor_bytes));
+        HIP_TRY(h, hipMemcpyAsync(h->dScoreT.p, tensor, tensor_bytes, hipMemcpyHostToDevice, st));
+        d_tensor = h->dScoreT.p;
+    }
+    LAUNCH_TRY(h, launch_pred_scores(pd, n, d_tensor, dtype, stride, E, pt, (fot_pred_score *)h->hScoreOut.p, st));
+    { int r = order_end(h, st); if (r != FOT_OK) return r; }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    std::memcpy(out, h->hScoreOut.p, sizeof(fot_pred_score) * (size_t)n);
+    return FOT_OK;
+}
+
+}  // namespace
+
+// ---- the helper fot_host.hpp declares for the resident loop's sampler step (fot_host_loop.cpp loop_run_step)
+// The launches of fot_sgan_sample behind its inputs, enqueue only (no copy from host memory, no synchronisation): all S
+// samples of the N > 0 pedestrians of n_scenes scenes.  d_off [n_scenes + 1] and d_scene [N] (the scene of every pedestrian;
+// nullptr unless the noise is per scene) are device memory, as are the tensors.
+int fot::host::sgan_enqueue(fot_handle *h, int n_scenes, int N, int S, const int32_t *d_off, const int32_t *d_scene,
+                            const float *d_obs, const float *d_noise, float *d_out, hipStream_t st)
+{
+    fot_handle::Sgan &G = h->sgan;
+    const fot_sgan_desc &d = G.desc;
+    const int nd = d.noise_dim, noise_rows = d.noise_mix_type == FOT_SGAN_NOISE_GLOBAL ? n_scenes : N;
+    const int E = d.embedding_dim, He = d.encoder_h_dim, Hd = d.decoder_h_dim, T = d.obs_len, L = d.pred_len;
+    const bool pooled = sg_pooled(d), steps = sg_pool_steps(d), context = sg_has_context(d);
+    const int nc = context ? Hd - nd : He;
+    const size_t rows = (size_t)S * N;
+    const float *img = G.dImg.as<float>();
+    // once per pedestrian / scene: encoder, first pooling, context MLP
+    HIP_TRY(h, G.dHenc.ensure(sizeof(float) * (size_t)N * He));
+    LAUNCH_TRY(h, launch_sgan_encode(img, G.dev.enc, E, He, T, N, d_obs, G.dHenc.as<float>(), st));
+    const int bp = pooled ? G.dev.pool.b_pad : 0;
+    if (pooled) {
+        HIP_TRY(h, G.dPool.ensure(sizeof(float) * (steps ? rows : (size_t)N) * bp));
+        HIP_TRY(h, hipMemsetAsync(G.dPool.p, 0, sizeof(float) * (size_t)N * bp, st));
+        LAUNCH_TRY(h, launch_sgan_pool(img, G.dev.pool, n_scenes, 1, N, d_off, G.dHenc.as<float>(),
+                                       d_obs + 2 * (size_t)(T - 1) * N, G.dPool.as<float>(), st));
+    }
+    const float *d_ctx = G.dHenc.as<float>();
+    if (context) {
+        HIP_TRY(h, G.dCtx.ensure(sizeof(float) * (size_t)N * nc));
+        LAUNCH_TRY(h, launch_sgan_mlp(img, G.dev.ctx, G.dHenc.as<float>(), He, G.dPool.as<float>(), pooled ? d.bottleneck_dim : 0, bp,
+                                      N, G.dCtx.as<float>(), nc, st));
+        d_ctx = G.dCtx.as<float>();
+    }
+    // once per sample: the decoder
+    SgDecode a{};
+    a.img = img; a.l = G.dev.dec; a.pos_w = G.dev.pos_w; a.pos_b = G.dev.pos_b;
+    a.E = E; a.H = Hd; a.N = N; a.S = S; a.obs_len = T; a.pred_len = L;
+    a.obs = d_obs; a.ctx = d_ctx; a.noise = d_noise; a.row_scene = d_scene;
+    a.nc = nc; a.nd = nd; a.noise_rows = noise_rows; a.out = d_out;
+    if (!steps) {
+        a.t0 = 0; a.n_steps = L; a.init = 1; a.save = 0;
+        LAUNCH_TRY(h, launch_sgan_decode(a, st));
+    } else {
+        HIP_TRY(h, G.dH.ensure(sizeof(float) * rows * Hd));
+        HIP_TRY(h, G.dC.ensure(sizeof(float) * rows * Hd));
+        HIP_TRY(h, G.dXY.ensure(sizeof(float) * rows * 6));
+        a.h = G.dH.as<float>(); a.c = G.dC.as<float>();
+        a.pos = G.dXY.as<float>(); a.rel = a.pos + rows * 2; a.cum = a.pos + rows * 4;
+        a.n_steps = 1; a.save = 1;
+        for (int t = 0; t < L; ++t) {
+            a.t0 = t; a.init = t == 0;
+            LAUNCH_TRY(h, launch_sgan_decode(a, st));
+            if (t == L - 1) break;                                   // (the last step's pooled state is never read)
+            HIP_TRY(h, hipMemsetAsync(G.dPool.p, 0, sizeof(float) * rows * bp, st));
+            LAUNCH_TRY(h, launch_sgan_pool(img, G.dev.dpool, n_scenes, S, N, d_off, a.h, a.pos, G.dPool.as<float>(), st));
+            LAUNCH_TRY(h, launch_sgan_mlp(img, G.dev.dmlp, a.h, Hd, G.dPool.as<float>(), d.bottleneck_dim, bp, (int64_t)rows, a.h, Hd, st));
+        }
+    }
+    return FOT_OK;
+}
+
+extern "C" {
+
+int fot_resample_n_dense(const fot_resample_params *rp, int32_t pred_len)
+{
+    if (!rp || !(rp->sim_dt > 0.0) || !(rp->sgan_dt > 0.0) || pred_len < 1) return FOT_ERR_INVALID;
+    return resample_n_dense(rp->sgan_dt, rp->sim_dt, rp->plan_horizon, pred_len);
+}
+
+int fot_resample_predictions(fot_handle *h, const fot_resample_params *rp, int32_t S, int32_t pred_len, int32_t P,
+                             const void *pred, int32_t pred_dtype, const double *anchor, const double *current,
+                             double staleness, void *out, int32_t out_dtype, int32_t on_device, int32_t *T_out,
+                             double *sample_dist, void *stream)
+{
+    return resample_common(h, rp, 0, S, pred_len, P, pred, pred_dtype, anchor, current, staleness, out, out_dtype,
+                           on_device, T_out, sample_dist, stream);
+}
+
+int fot_predict_cv(fot_handle *h, const fot_resample_params *rp, int32_t pred_len, int32_t P,
+                   const void *obs_last, const void *obs_prev, int32_t obs_dtype, const double *current,
+                   double staleness, void *out, int32_t out_dtype, int32_t on_device, int32_t *T_out, void *stream)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (obs_dtype == FOT_F64)
+        return resample_common(h, rp, 1, 1, pred_len, P, obs_prev, FOT_F64, (const double *)obs_last, current, staleness,
+                               out, out_dtype, on_device, T_out, nullptr, stream);
+    if (obs_dtype != FOT_F32) return fail(h, FOT_ERR_INVALID, "obs_dtype");
+    // float32 observations travel widened (exact); cv mode 2 forms the velocity in float32
+    const size_t n = 2 * (size_t)(P > 0 ? P : 0);
+    std::vector<double> last(n), prev(n);
+    for (size_t i = 0; i < n && obs_last; ++i) last[i] = (double)((const float *)obs_last)[i];
+    for (size_t i = 0; i < n && obs_prev; ++i) prev[i] = (double)((const float *)obs_prev)[i];
+    return resample_common(h, rp, 2, 1, pred_len, P, obs_prev ? prev.data() : nullptr, FOT_F64,
+                           obs_last ? last.data() : nullptr, current, staleness, out, out_dtype, on_device, T_out,
+                           nullptr, stream);
+}
+
+int fot_safety_metrics_batch(fot_handle *h, int32_t n, const double *ego, const int32_t *ped_off,
+                             const double *ped_pos, const double *ped_vel, double ego_radius, double ped_radius,
+                             int32_t use_footprint, fot_safety *out)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (n <= 0) return n == 0 ? FOT_OK : fail(h, FOT_ERR_INVALID, "n < 0");
+    if (!ego || !ped_off || !out) return fail(h, FOT_ERR_INVALID, "NULL array");
+    for (int i = 0; i < n; ++i)
+        if (ped_off[i + 1] < ped_off[i] || ped_off[0] < 0) return fail(h, FOT_ERR_INVALID, "ped_off must be non-decreasing");
+    const size_t n_ped = (size_t)ped_off[n];
+    if (n_ped > 0 && (!ped_pos || !ped_vel)) return fail(h, FOT_ERR_INVALID, "NULL pedestrian array");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    { int r = order_begin(h, st); if (r != FOT_OK) return r; }
+    const size_t ego_b = sizeof(double) * 4 * (size_t)n, off_b = align256(sizeof(int32_t) * ((size_t)n + 1));
+    const size_t ped_b = sizeof(double) * 2 * std::max<size_t>(n_ped, 1);
+    if (align256(ego_b) + off_b + 2 * align256(ped_b) <= SMALL_CALL_BYTES && sizeof(fot_safety) * (size_t)n <= SMALL_CALL_BYTES) {
+        // small call: the kernel reads its inputs from, and writes its results to, pinned host memory (no copy operations)
+        HIP_TRY(h, h->hSmallIn.ensure(align256(ego_b) + off_b + 2 * align256(ped_b)));
+        HIP_TRY(h, h->hSmallOut.ensure(sizeof(fot_safety) * (size_t)n));
+        char *p = (char *)h->hSmallIn.p;
+        char *p_off = p + align256(ego_b), *p_pos = p_off + off_b, *p_vel = p_pos + align256(ped_b);
+        std::memcpy(p, ego, ego_b);
+        std::memcpy(p_off, ped_off, sizeof(int32_t) * ((size_t)n + 1));
+        if (n_ped) { std::memcpy(p_pos, ped_pos, sizeof(double) * 2 * n_ped); std::memcpy(p_vel, ped_vel, sizeof(double) * 2 * n_ped); }
+        LAUNCH_TRY(h, launch_safety(h->dP.as<DevParams>(), n, (const double *)p, (const int32_t *)p_off, (const double *)p_pos,
+                                    (const double *)p_vel, ego_radius, ped_radius, h->sc[0].params.footprint_radius,
+                                    use_footprint, (fot_safety *)h->hSmallOut.p, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        std::memcpy(out, h->hSmallOut.p, sizeof(fot_safety) * (size_t)n);
+        return FOT_OK;
+    }
+    HIP_TRY(h, h->dTmpA.ensure(align256(ego_b) + off_b));
+    HIP_TRY(h, h->dTmpB.ensure(2 * align256(ped_b)));
+    HIP_TRY(h, h->dTmpC.ensure(sizeof(fot_safety) * (size_t)n));
+    char *a = (char *)h->dTmpA.p, *b = (char *)h->dTmpB.p;
+    HIP_TRY(h, hipMemcpyAsync(a, ego, ego_b, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(a + align256(ego_b), ped_off, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, st));
+    if (n_ped) {
+        HIP_TRY(h, hipMemcpyAsync(b, ped_pos, sizeof(double) * 2 * n_ped, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipMemcpyAsync(b + align256(ped_b), ped_vel, sizeof(double) * 2 * n_ped, hipMemcpyHostToDevice, st));
+    }
+    LAUNCH_TRY(h, launch_safety(h->dP.as<DevParams>(), n, (const double *)a, (const int32_t *)(a + align256(ego_b)),
+                                (const double *)b, (const double *)(b + align256(ped_b)), ego_radius, ped_radius,
+                                h->sc[0].params.footprint_radius, use_footprint, h->dTmpC.as<fot_safety>(), st));
+    HIP_TRY(h, hipMemcpyAsync(out, h->dTmpC.p, sizeof(fot_safety) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return FOT_OK;
+}
+
+int fot_prediction_scores(fot_handle *h, int32_t n_origins, const fot_pred_origin *desc, const void *tensor, int32_t dtype,
+                          int32_t on_device, int32_t stride, int32_t E, const double *truth, fot_pred_score *out,
+                          void *stream)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (n_origins < 0 || (n_origins > 0 && !desc)) return fail(h, FOT_ERR_INVALID, "fot_prediction_scores: n_origins / desc");
+    if (dtype != FOT_F32 && dtype != FOT_F64) return fail(h, FOT_ERR_INVALID, "fot_prediction_scores: dtype");
+    if (n_origins == 0) return FOT_OK;
+    size_t bytes = 0;
+    if (!on_device) {                                              // the host tensor up to the end of the last block
+        int64_t end = 0;
+        for (int i = 0; i < n_origins; ++i)
+            if (desc[i].offset >= 0 && desc[i].S > 0 && desc[i].P > 0 && desc[i].T > 0)
+                end = std::max(end, desc[i].offset + (int64_t)desc[i].S * desc[i].P * desc[i].T);
+        bytes = (dtype == FOT_F32 ? 4 : 8) * 2 * (size_t)end;
+    }
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    return prediction_scores_impl(h, "fot_prediction_scores", n_origins, desc, tensor, bytes, dtype, stride, E, truth, out, st);
+}
+
+int fot_loop_prediction_scores(fot_handle *h, int32_t n_episodes, int32_t stride, int32_t E, const double *truth,
+                               fot_pred_score *out)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopState &L = h->loop;
+    if (L.replay.set) return fail(h, FOT_ERR_INVALID, "fot_loop_prediction_scores: a replay is set (fot_loop_run owns the handle's tensor)");
+    if (!L.have_frame || L.dist_S < 1)
+        return fail(h, FOT_ERR_INVALID, "fot_loop_prediction_scores: the last frame carried no distribution (fot_loop_frame.dist_raw)");
+    if (n_episodes != (int)L.ped_off.size() - 1) return fail(h, FOT_ERR_INVALID, "fot_loop_prediction_scores: n_episodes differs from the frame's");
+    if (n_episodes == 0) return FOT_OK;
+    std::vector<fot_pred_origin> desc((size_t)n_episodes);
+    for (int e = 0; e < n_episodes; ++e)
+        desc[(size_t)e] = fot_pred_origin{ L.blk_off[(size_t)e], L.dist_S, L.ped_off[(size_t)e + 1] - L.ped_off[(size_t)e],
+                                           L.t_len[(size_t)e], 0, 1, 0 };
+    // (a frame without pedestrians left no tensor: every P is 0 and none is read)
+    return prediction_scores_impl(h, "fot_loop_prediction_scores", n_episodes, desc.data(), L.dDyn.p, 0, FOT_F64, stride, E,
+                                  truth, out, h->stream);
+}
+
+// ---- Social-GAN sample generation (include/fot.h; kernels: fot_sgan.hip, arithmetic: fot_sgan.hpp) ------------------------
+int fot_sgan_weight_count(const fot_sgan_desc *desc, int64_t *n)
+{
+    if (!desc || !n) return fail(nullptr, FOT_ERR_INVALID, "fot_sgan_weight_count: desc / n is NULL");
+    std::string why;
+    const int rc = sg_check_desc(*desc, why);
+    if (rc != FOT_OK) return fail(nullptr, rc, why);
+    *n = sg_blob_layout(*desc).total;
+    return FOT_OK;
+}
+
+int fot_sgan_load(fot_handle *h, const fot_sgan_desc *desc, int64_t n, const float *weights)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (!desc || !weights) return fail(h, FOT_ERR_INVALID, "fot_sgan_load: desc / weights is NULL");
+    if (h->loop.replay.set && h->loop.replay.smp.on) return fail(h, FOT_ERR_INVALID, "fot_sgan_load: the resident loop's sampler uses the model (fot_loop_set_sampler)");
+    std::string why;
+    const int rc = sg_check_desc(*desc, why);
+    if (rc != FOT_OK) return fail(h, rc, why);
+    if (n != sg_blob_layout(*desc).total) return fail(h, FOT_ERR_INVALID, "fot_sgan_load: n is not fot_sgan_weight_count of the descriptor");
+    std::vector<float> img;
+    const SgDev dev = sg_dev_image(*desc, weights, img);
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                   // (a sample call of the model before this one is synchronous anyway)
+    fot_handle::Sgan &G = h->sgan;
+    G.loaded = false;
+    HIP_TRY(h, G.dImg.ensure(sizeof(float) * img.size()));
+    HIP_TRY(h, hipMemcpy(G.dImg.p, img.data(), sizeof(float) * img.size(), hipMemcpyHostToDevice));
+    G.desc = *desc;
+    G.dev = dev;
+    G.loaded = true;
+    return FOT_OK;
+}
+
+int fot_sgan_unload(fot_handle *h)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (h->loop.replay.set && h->loop.replay.smp.on) return fail(h, FOT_ERR_INVALID, "fot_sgan_unload: the resident loop's sampler uses the model (fot_loop_set_sampler)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->sgan.loaded = false;
+    h->sgan.release();
+    return FOT_OK;
+}
+
+int fot_sgan_sample(fot_handle *h, int32_t n_scenes, const int32_t *ped_off, const void *obs, int32_t S, const void *noise,
+                    int32_t flags, void *out, void *stream)
+{
+    if (!h) return FOT_ERR_INVALID;
+    fot_handle::Sgan &G = h->sgan;
+    if (!G.loaded) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: no model loaded (fot_sgan_load)");
+    if (n_scenes < 0 || !ped_off) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: n_scenes / ped_off (one offset even for no scene)");
+    if (S < 1) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: S < 1");
+    if (flags & ~(FOT_OUT_DEVICE | FOT_SGAN_OBS_DEVICE | FOT_SGAN_NOISE_DEVICE)) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: flags");
+    if (ped_off[0] != 0) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: ped_off must start at 0 and be non-decreasing");
+    int widest = 0;
+    for (int i = 0; i < n_scenes; ++i) {
+        if (ped_off[i + 1] < ped_off[i]) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: ped_off must start at 0 and be non-decreasing");
+        widest = std::max(widest, ped_off[i + 1] - ped_off[i]);
+    }
+    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, "fot_sgan_sample: S > FOT_MAX_SAMPLES");
+    if (widest > FOT_SGAN_MAX_PEDS) return fail(h, FOT_ERR_UNSUPPORTED, "fot_sgan_sample: a scene of more than FOT_SGAN_MAX_PEDS pedestrians");
+    const fot_sgan_desc &d = G.desc;
+    const int N = ped_off[n_scenes];
+    const bool global_noise = d.noise_mix_type == FOT_SGAN_NOISE_GLOBAL;
+    const int nd = d.noise_dim, noise_rows = global_noise ? n_scenes : N;
+    if (N == 0) return FOT_OK;
+    if (!obs || !out || (nd > 0 && !noise)) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: NULL tensor");
+    const int T = d.obs_len, L = d.pred_len;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    { int r = order_begin(h, st); if (r != FOT_OK) return r; }
+    const size_t obs_bytes = sizeof(float) * 2 * (size_t)T * N, noise_bytes = sizeof(float) * (size_t)S * noise_rows * nd;
+    const size_t out_bytes = sizeof(float) * 2 * (size_t)S * L * N;
+    // the offsets and, for noise per scene, every pedestrian's scene
+    std::vector<int32_t> scene_of;
+    HIP_TRY(h, G.dOff.ensure(sizeof(int32_t) * ((size_t)n_scenes + 1)));
+    HIP_TRY(h, hipMemcpyAsync(G.dOff.p, ped_off, sizeof(int32_t) * ((size_t)n_scenes + 1), hipMemcpyHostToDevice, st));
+    if (global_noise && nd > 0) {
+        scene_of.resize((size_t)N);
+        for (int i = 0; i < n_scenes; ++i) std::fill(scene_of.begin() + ped_off[i], scene_of.begin() + ped_off[i + 1], i);
+        HIP_TRY(h, G.dScene.ensure(sizeof(int32_t) * (size_t)N));
+        HIP_TRY(h, hipMemcpyAsync(G.dScene.p, scene_of.data(), sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, st));
+    }
+    const float *d_obs = (const float *)obs, *d_noise = (const float *)noise;
+    if (!(flags & FOT_SGAN_OBS_DEVICE)) {
+        HIP_TRY(h, G.dObs.ensure(obs_bytes));
+        HIP_TRY(h, hipMemcpyAsync(G.dObs.p, obs, obs_bytes, hipMemcpyHostToDevice, st));
+        d_obs = G.dObs.as<float>();
+    }
+    if (nd > 0 && !(flags & FOT_SGAN_NOISE_DEVICE)) {
+        HIP_TRY(h, G.dNoise.ensure(noise_bytes));
+        HIP_TRY(h, hipMemcpyAsync(G.dNoise.p, noise, noise_bytes, hipMemcpyHostToDevice, st));
+        d_noise = G.dNoise.as<float>();
+    }
+    float *d_out = (float *)out;
+    if (!(flags & FOT_OUT_DEVICE)) { HIP_TRY(h, G.dOut.ensure(out_bytes)); d_out = G.dOut.as<float>(); }
+    { int r = sgan_enqueue(h, n_scenes, N, S, G.dOff.as<int32_t>(), global_noise && nd > 0 ? G.dScene.as<int32_t>() : nullptr, d_obs,
+                           d_noise, d_out, st); if (r != FOT_OK) return r; }
+    if (!(flags & FOT_OUT_DEVICE)) HIP_TRY(h, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    { int r = order_end(h, st); if (r != FOT_OK) return r; }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return FOT_OK;
+}
+
+int fot_sgan_noise(fot_handle *h, uint64_t seed, int32_t kind, int32_t S, int32_t rows, int32_t noise_dim,
+                   const int32_t *row_slot, const int32_t *row_step, const int32_t *row_index, int32_t flags, void *out,
+                   void *stream)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (kind < 0 || kind >= FOT_NOISE_KINDS) return fail(h, FOT_ERR_INVALID, "fot_sgan_noise: kind");
+    if (flags & ~FOT_OUT_DEVICE) return fail(h, FOT_ERR_INVALID, "fot_sgan_noise: flags");
+    if (S < 1 || rows < 0 || noise_dim < 0) return fail(h, FOT_ERR_INVALID, "fot_sgan_noise: S < 1 / rows < 0 / noise_dim < 0");
+    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, "fot_sgan_noise: S > FOT_MAX_SAMPLES");
+    if (rows == 0 || noise_dim == 0) return FOT_OK;
+    if (!row_slot || !row_step || !row_index || !out) return fail(h, FOT_ERR_INVALID, "fot_sgan_noise: NULL table / out");
+    for (int r = 0; r < rows; ++r)
+        if (row_slot[r] < 0 || row_step[r] < 0 || row_index[r] < 0 || row_index[r] > 0xFFFF)
+            return fail(h, FOT_ERR_INVALID, "fot_sgan_noise: a negative table entry, or a row_index above 65535");
+    fot_handle::Sgan &G = h->sgan;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const size_t n_out = (size_t)S * (size_t)rows * (size_t)noise_dim;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                  // (the tables' block: nothing of an earlier call reads it)
+    HIP_TRY(h, G.hTab.ensure(sizeof(int32_t) * 3 * (size_t)rows));
+    uint32_t *d_out = (uint32_t *)out;
+    if (!(flags & FOT_OUT_DEVICE)) { HIP_TRY(h, G.dNoise.ensure(sizeof(uint32_t) * n_out)); d_out = (uint32_t *)G.dNoise.p; }
+    { int r = order_begin(h, st); if (r != FOT_OK) return r; }
+    int32_t *t = (int32_t *)G.hTab.p;
+    std::memcpy(t, row_slot, sizeof(int32_t) * (size_t)rows);
+    std::memcpy(t + rows, row_step, sizeof(int32_t) * (size_t)rows);
+    std::memcpy(t + 2 * (size_t)rows, row_index, sizeof(int32_t) * (size_t)rows);
+    SgNoise a{};
+    a.seed = seed; a.kind = kind; a.S = S; a.rows = rows; a.nd = noise_dim; a.n_blk = (noise_dim + 3) / 4;
+    a.slot = t; a.step = t + rows; a.index = t + 2 * (size_t)rows; a.out = d_out;
+    LAUNCH_TRY(h, launch_sgan_noise(a, st));
+    if (!(flags & FOT_OUT_DEVICE)) HIP_TRY(h, hipMemcpyAsync(out, d_out, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, st));
+    { int r = order_end(h, st); if (r != FOT_OK) return r; }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return FOT_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // fot_replay.hpp -- the host logic of a replayed closed-loop episode that does not touch the GPU: the replay clock, the
 // observer's sampling clock and window, the prepend test and the termination test (fot_loop_set_replay / fot_loop_run).
-// Plain C++, no HIP: fot_host.cpp uses it, tests/emu/fot_replay_emu.cpp exposes it to the CPU tests, which hold it
+// Plain C++, no HIP: fot_host_loop.cpp uses it, tests/emu/fot_replay_emu.cpp exposes it to the CPU tests, which hold it
 // against closed_loop.py's Observer / ReplayPedestrians / BatchedClosedLoop._loop_frame step by step.
 #pragma once
 

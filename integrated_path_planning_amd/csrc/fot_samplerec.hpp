@@ -2,7 +2,7 @@
 // step's raw tensor [S][pred_len][rows][2] -- rows: the pedestrians of the RUNNING episodes, compacted as k_loop_frame
 // leaves them -- to its place in the recording [n_steps][S][pred_len][n_cols][2], whose columns are those of all slots in
 // the replay's own order.  Plain C++ shared by the kernel (k_loop_sample_rows, fot_loop_kernels.hip), the host
-// (fot_host.cpp) and tests/emu/fot_samplerec_emu.cpp.  Every offset into the recording is 64-bit: 256 episodes x 30
+// (fot_host_loop.cpp) and tests/emu/fot_samplerec_emu.cpp.  Every offset into the recording is 64-bit: 256 episodes x 30
 // pedestrians x 20 samples x 12 steps x 274 lock steps are 1.0e9 coordinates, and a longer run or more samples pass 2^31
 // elements.
 #pragma once

@@ -1,5 +1,5 @@
 // fot_sgan.h -- launchers of the Social-GAN kernels and of the resident loop's observer window (fot_sgan.hip) for the host
-// side (fot_host.cpp).
+// side (fot_host_pred.cpp: the sampler; fot_host_loop.cpp: the resident loop's window and noise).
 #pragma once
 
 #include <hip/hip_runtime.h>

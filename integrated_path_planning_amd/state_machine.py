@@ -74,7 +74,7 @@ def constants_of(config) -> Dict[str, float]:
 
 # The transitions and the planner configurations, once: over arrays with one entry per episode (state codes as in
 # STATES; every constant of ``k`` a scalar or an array of the same shape).  They read side by side with sm_update /
-# sm_config of csrc/fot_host.cpp, which fot_loop_step and fot_loop_run run.
+# sm_config of csrc/fot_host_loop.cpp, which fot_loop_step and fot_loop_run run.
 
 def sm_update(state, fails, found, clearance, speed, k):
     """The transition of update() (state_machine.py:116-179) -> new state, new count of consecutive failures."""

@@ -135,7 +135,7 @@ def predict_cv(engine, last, prev, current, staleness, pred_len, sgan_dt, sim_dt
 
 
 def _call_kind(c, b):
-    """small / staged / device, by the library's own rule (fot_host.cpp resample_common: a host call whose inputs and
+    """small / staged / device, by the library's own rule (fot_host_pred.cpp resample_common: a host call whose inputs and
     outputs each fit 1 MiB of pinned memory is a small call)."""
     if c["device"]:
         return "device"
