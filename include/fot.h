@@ -885,6 +885,47 @@ int fot_debug_loop_block(fot_handle *h, int32_t episode, int32_t cap_points, dou
 int fot_loop_set_samples(fot_handle *h, int32_t S, int32_t n_steps, int32_t first_step, const void *samples, int32_t dtype,
                          int32_t flags);
 
+/* ---- sweep loops: every slot on its own scenario AND in its own plan mode over sample distributions ---------------------
+ * A campaign runs one crowd and one predictor output under conditions that differ in the plan mode (the representative
+ * sample against the whole distribution), chance_epsilon and collision_margin_inflation.  One loop runs such a sweep.
+ *
+ * fot_loop_begin_sweep(h, n_episodes, n_cfg, cfg, use_footprint, slot_scenario, slot_plan_mode, ego5):
+ * fot_loop_begin_scenarios -- the same arguments, the same refusals -- plus slot_plan_mode[e], FOT_LOOP_PLAN_DISTRIBUTION
+ * or FOT_LOOP_PLAN_REPRESENTATIVE; NULL: every slot plans against the distribution; any other value: FOT_ERR_INVALID
+ * (nothing changed).  The loop is a scenario loop in every respect, except that a lock step with a distribution is
+ * accepted: fot_loop_step takes a frame with dist_raw, fot_loop_set_sampler and fot_loop_set_samples(_shared) are allowed.
+ * Such a step resamples the frame into every episode's [dist_S][P_e][n_dense + 1][2] block as a one-configuration loop
+ * does; the episodes in representative mode then choose their sample and leave their [P_e][n_dense + 1][2] planning block
+ * (fot_loop_plan_sample above: the same selection, the same prepend rule) BEHIND the step's distribution blocks in the
+ * same tensor, compacted in frame order.  One plan call serves all requests: a request addresses its episode's
+ * distribution block as FOT_DYN_DISTRIBUTION with dist_S samples, or its planning block as FOT_DYN_SINGLE with one, each
+ * on its slot's scenario -- chance_epsilon and collision_margin_inflation are the scenario's, and in representative mode
+ * chance_epsilon plays no part.  The escalation levels plan against the same block in the same mode as their episode's
+ * level 0.  An episode's numbers are the bits it computes in a uniform loop of its own configuration and mode, whatever
+ * its company.  A frame or step without a distribution plans as a scenario loop does (the same bytes).
+ * fot_loop_scores_enable, fot_loop_score_summaries, fot_loop_last_best_sample, fot_loop_run_best_samples work as on a
+ * fot_loop_begin loop; the two best-sample queries answer -1 for a slot in distribution mode unless scores are enabled
+ * (the selection then runs for every running episode).  fot_debug_loop_block answers per episode in that episode's mode.
+ * fot_loop_plan_sample: FOT_ERR_INVALID, the modes were given per slot.  fot_loop_summary_enable: as on any loop, allowed
+ * with constant velocity, refused while a sampler or a recording is set.  fot_loop_begin* ends the sweep loop.
+ * What the sweep needs is allocated by fot_loop_set_sampler / fot_loop_set_samples(_shared) or grows with the frames.
+ *
+ * fot_loop_set_samples_shared(h, S, n_steps, first_step, samples, dtype, flags, n_rec_cols, slot_col0):
+ * fot_loop_set_samples for a recording [n_steps][S][pred_len][n_rec_cols][2] whose columns are not the replay's:
+ * pedestrian p of slot e reads column slot_col0[e] + p, and several slots may name the same columns -- K conditions over
+ * one crowd keep ONE copy of its samples in HBM.  fot_loop_set_samples is this call with n_rec_cols = ped_off[n_slots] and
+ * slot_col0 = ped_off.  When it may be called, the in-place use of a device tensor, the rows that are read and the
+ * refusals are fot_loop_set_samples's (a fot_loop_begin_scenarios loop included); allowed on fot_loop_begin loops and on
+ * sweep loops.  Further FOT_ERR_INVALID (nothing changed): slot_col0 NULL; an entry < 0; slot_col0[e] + P_e > n_rec_cols;
+ * n_rec_cols < 1 with pedestrians in the replay.
+ * Both entries are additions: no structure, capacity or existing entry changes, FOT_ABI_VERSION and the words of
+ * fot_abi_info stay as they are; a loop that never calls them launches and allocates nothing new. */
+int fot_loop_begin_sweep(fot_handle *h, int32_t n_episodes, int32_t n_cfg, const fot_loop_config *cfg,
+                         const int32_t *use_footprint, const int32_t *slot_scenario, const int32_t *slot_plan_mode,
+                         const double *ego5);
+int fot_loop_set_samples_shared(fot_handle *h, int32_t S, int32_t n_steps, int32_t first_step, const void *samples,
+                                int32_t dtype, int32_t flags, int32_t n_rec_cols, const int32_t *slot_col0);
+
 /* Host utility (no GPU): the first kmax samples of the 15 path arrays of records[index[i]], i < n, as one dense block
  * out[15][n][kmax] in fot_result array order (t .. c) -- what a history keeps of a step's records. */
 int fot_gather_paths(const fot_result *records, int32_t n, const int32_t *index, int32_t kmax, double *out);

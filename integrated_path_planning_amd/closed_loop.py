@@ -386,10 +386,11 @@ def loop_config_from(c, k: Dict[str, float], max_replan: int) -> "_abi.LoopConfi
 
 
 # what the episodes of one loop must agree on: one time grid per handle (dt, max_t), and what the frame / the replay
-# carries once per loop (observer and predictor lengths, the metrics' radii), the run length and the predictor
+# carries once per loop (observer and predictor lengths, the metrics' radii), the run length and the predictor.
+# (distribution_aware_planning is an episode's own: configurations that differ only in it share a scenario and differ in
+# the plan mode of their slots, fot_loop_begin_sweep)
 COMMON_FIELDS = (("dt", None), ("max_t", 5.0), ("obs_len", None), ("pred_len", None), ("ego_radius", 1.0),
-                 ("ped_radius", 0.3), ("total_time", 0.0), ("prediction_method", "sgan"),
-                 ("distribution_aware_planning", False))
+                 ("ped_radius", 0.3), ("total_time", 0.0), ("prediction_method", "sgan"))
 
 
 def scenario_key(c) -> tuple:
@@ -496,6 +497,12 @@ class BatchedClosedLoop:
         representative sample on the device, lays it out as one fixed-shape [P, n_dense + 1, 2] block (the conditional
         prepend decided there, ``fot_loop_plan_sample``) and plans against it; a step's ``pred`` in the history is the
         sample the device chose.  Not together with ``distribution_aware_planning``.
+        A list of configurations together with ``sample_source=..., device_samples=True`` is a SWEEP (fot_loop_begin_sweep):
+        every episode on its own scenario and in its own plan mode -- ``distribution_aware_planning`` set: the whole
+        distribution; unset: the representative sample (``plan_on_representative_sample=True`` is then required) -- in one
+        lock step, on the one-call step or ``resident=True`` (a counter-seeded ``SganSampler`` or a ``RecordedSamples``,
+        whose ``slot_col0`` lets the conditions over one crowd share its columns).  A list of one distinct scenario and one
+        mode is today's loop.
         fused: True = the lock step behind one library call (fot_loop_step), False = five separate calls with the
         prediction through the host, None = one call where the engine and the predictor allow it."""
         if fused not in (None, False, True):
@@ -534,12 +541,20 @@ class BatchedClosedLoop:
         # a sequence of configurations, one per episode: equal ones share a scenario of the ONE handle; more than one
         # distinct scenario runs through the one-call step or resident=True only
         self.scenarios, self.slot_scenario, per_episode = None, None, None
+        self._sweep, self._slot_aware, any_aware = False, None, False
         if isinstance(config, (list, tuple)):
             if len(config) != len(ped_tracks):
                 raise ValueError(f"{len(config)} configurations for {len(ped_tracks)} episodes: one configuration per episode")
             distinct, slot, per_episode = merge_configs(config)
+            aware = np.array([bool(getattr(k, "distribution_aware_planning", False)) for k in per_episode])
+            any_aware, mixed = bool(aware.any()), bool(aware.any() and not aware.all())
+            # a sweep: more than one scenario and / or mixed plan modes over a sample source whose samples stay in HBM
+            self._sweep = bool((len(distinct) > 1 or mixed) and sample_source is not None and device_samples
+                               and engine is None and resampler is None and fused in (None, True))
             config = distinct[0]
-            if len(distinct) > 1:
+            if self._sweep:
+                self.scenarios, self.slot_scenario, self._slot_aware = distinct, slot, aware
+            elif len(distinct) > 1 or mixed:
                 if engine is not None or resampler is not None or sample_source is not None or fused not in (None, True):
                     raise ValueError("the five-call step, stand-in engines and sample sources take one configuration: "
                                      "episodes of different configurations run through the one-call step "
@@ -559,6 +574,8 @@ class BatchedClosedLoop:
             raise NotImplementedError("the Social-GAN / LSTM networks are not part of this build (SURVEY 8 f1): hand "
                                       "their samples in through sample_source, or use prediction_method='cv'")
         self.distribution_aware = bool(getattr(c, "distribution_aware_planning", False))
+        if self._sweep:                                               # (per slot: _slot_aware; this one says "all of them")
+            self.distribution_aware = bool(self._slot_aware.all())
         self._plan_rep = bool(plan_on_representative_sample)
         if self._plan_rep and self.distribution_aware:
             raise ValueError("plan_on_representative_sample plans against ONE sample of the distribution: not together "
@@ -566,7 +583,7 @@ class BatchedClosedLoop:
         if self._plan_rep and not device_samples:
             raise ValueError("plan_on_representative_sample needs device_samples=True (a sample source handing its "
                              "samples over on the host plans on the representative sample already)")
-        if self.distribution_aware and sample_source is None:
+        if (self.distribution_aware or any_aware) and sample_source is None:
             raise ValueError("distribution_aware_planning needs a multi-sample predictor (sample_source): the "
                              "constant-velocity predictor yields one sample")
         self.static_obstacle_points = expand_static_obstacles(getattr(c, "static_obstacles", None), step=0.5)
@@ -592,12 +609,12 @@ class BatchedClosedLoop:
         if sample_source is not None and engine is None and hasattr(sample_source, "bind") and \
                 getattr(sample_source, "engine", self.engine) is None:
             sample_source.bind(self.engine)                           # (a sampler built without an engine joins this one)
-        if self._resident_dist and (isinstance(config, (list, tuple)) or self.scenarios is not None):
+        if self._resident_dist and not self._sweep and (isinstance(config, (list, tuple)) or self.scenarios is not None):
             raise ValueError("resident=True with a sampler takes one configuration (a scenario loop plans against no "
                              "distribution)")
         self._device_samples = bool(device_samples)
         if self._device_samples and not (sample_source is not None and (self.distribution_aware or self._plan_rep)
-                                         and engine is None and resampler is None):
+                                         and engine is None and resampler is None):   # (a sweep: some slot plans on its sample)
             raise ValueError("device_samples needs a sample_source, distribution_aware_planning and the library's own engine")
         # the whole step behind ONE call (fot_loop_step: the episodes' state, the fail-safe machine and the retry loop live
         # in the handle, the prediction stays in HBM): the constant-velocity predictor -- or samples in device memory -- on
@@ -674,7 +691,12 @@ class BatchedClosedLoop:
             if self._score_stride < 1 or not np.isclose(ratio, self._score_stride):
                 raise ValueError(f"prediction_scores: the predictor's step {self.sgan_dt} must be a multiple of dt = {self.dt}")
         self._warmup()
-        if self._native and self.scenarios is not None:
+        if self._native and self._sweep:
+            self.engine.loop_begin_sweep(
+                [loop_config_from(k, constants_of(k), self.MAX_REPLAN) for k in self.scenarios],
+                [fp_k is not None for fp_k in self.scenario_footprints], self.slot_scenario,
+                np.where(self._slot_aware, _abi.LOOP_PLAN_DISTRIBUTION, _abi.LOOP_PLAN_REPRESENTATIVE), self.ego)
+        elif self._native and self.scenarios is not None:
             self.engine.loop_begin_scenarios(
                 [loop_config_from(k, constants_of(k), self.MAX_REPLAN) for k in self.scenarios],
                 [fp_k is not None for fp_k in self.scenario_footprints], self.slot_scenario, self.ego)
@@ -691,11 +713,14 @@ class BatchedClosedLoop:
                 self.engine.loop_summary_enable(True, int(getattr(c, "num_samples", 1)))
             if self._resident_sampler:
                 self.engine.loop_set_sampler(sample_source.num_samples, sample_source.counter_seed, sample_source.noise_kind)
-            if self._resident_recording:
+            if self._resident_recording and getattr(sample_source, "slot_col0", None) is not None:
+                self.engine.loop_set_samples(sample_source.samples, sample_source.first_step,
+                                             n_rec_cols=sample_source.n_cols, slot_col0=sample_source.slot_col0)
+            elif self._resident_recording:
                 self.engine.loop_set_samples(sample_source.samples, sample_source.first_step)
             if self._resident_scores:
                 self.engine.loop_scores_enable(True)
-        if self._plan_rep:
+        if self._plan_rep and not self._sweep:                        # (a sweep's modes were given per slot at begin)
             self.engine.loop_plan_sample(_abi.LOOP_PLAN_REPRESENTATIVE)
 
     def close(self) -> None:
@@ -1089,6 +1114,11 @@ class BatchedClosedLoop:
         best = np.argmin(per_ep, axis=0)                                         # [episodes]
         return dist[np.repeat(best, off[1:] - off[:-1]), np.arange(dist.shape[1])]
 
+    def _planned_on(self, best: np.ndarray) -> np.ndarray:
+        """[..., slots] chosen samples -> -1 where a sweep's slot planned on the whole distribution (a scored loop chooses
+        a sample for those too; the history shows the host's ``predict_single_best`` there, as a uniform loop's does)."""
+        return best if not self._sweep else np.where(self._slot_aware, -1, best)
+
     def _materialise_prediction(self, pred_src, off):
         """The prediction a one-call step left in HBM, computed again for whoever reads the step's record (same kernels,
         same numbers): the constant-velocity tracks, or the best sample of the distribution's raw samples."""
@@ -1104,7 +1134,11 @@ class BatchedClosedLoop:
             dist = self.resampler.process_prediction(raw_h, anchor_pos=o32[1].astype(np.float64), staleness=stale)
             if len(pred_src) > 4:                                     # the sample the device chose and planned on, per episode
                 off = np.asarray(off)
-                return dist[np.repeat(np.maximum(pred_src[4], 0), off[1:] - off[:-1]), np.arange(dist.shape[1])]
+                chosen = dist[np.repeat(np.maximum(pred_src[4], 0), off[1:] - off[:-1]), np.arange(dist.shape[1])]
+                whole = np.repeat(pred_src[4] < 0, off[1:] - off[:-1])     # a sweep's slots that planned on the distribution
+                if whole.any() and raw_h.shape[0] > 1:
+                    chosen[whole] = self._best_sample(dist, off)[whole]
+                return chosen
             return dist[0] if raw_h.shape[0] == 1 else self._best_sample(dist, np.asarray(off))
         o32, stale = pred_src
         return self.resampler.predict_cv(o32, staleness=stale, float32_observations=True)
@@ -1164,7 +1198,7 @@ class BatchedClosedLoop:
         o = self.engine.loop_step(frame, sel)
         t_plan = (time.perf_counter() - t0) / n
         if self._plan_rep and pred_src is not None and isinstance(pred_src[0], str):
-            pred_src = pred_src + (self.engine.loop_last_best_sample()[sel].astype(np.int64),)   # what the step planned on
+            pred_src = pred_src + (self._planned_on(self.engine.loop_last_best_sample())[sel].astype(np.int64),)   # what the step planned on
         rec, path_rec, keep = o["records"], o["record"].astype(np.int64), o["keep"].astype(np.int64)
         new_ego = o["ego"]
         self.ego[sel], self.jerk[sel] = new_ego, o["jerk"]
@@ -1246,7 +1280,7 @@ class BatchedClosedLoop:
             if first is None:
                 first = int(ran[0].sum())
             # (planning on the representative sample: what every step of the call chose, for the history)
-            best = self.engine.loop_run_best_samples(done) if self._plan_rep else None
+            best = self._planned_on(self.engine.loop_run_best_samples(done)) if self._plan_rep else None
             for k in range(done):
                 self._steps.append(_ResidentStep(self, o, k, self.time, keep_paths))
                 self.time += self.dt

@@ -19,6 +19,7 @@
 #include "fot_summary.hpp"
 #include "fot_loopscore.hpp"
 #include "fot_sgan.hpp"
+#include "fot_sweep.hpp"
 
 // fot::host: internal to libfot.so -- hidden, so that what is declared here for the other host units is exported nowhere
 namespace fot { namespace host __attribute__((visibility("hidden"))) {
@@ -121,6 +122,9 @@ struct LoopEpisodes {
     std::vector<fot_loop_config> cfgs;
     std::vector<int32_t> use_fp;
     std::vector<int32_t> scen;               // [n] scenario of each slot
+    // fot_loop_begin_sweep: a scenario loop whose lock steps may carry a distribution; plan_mode[e]: FOT_LOOP_PLAN_* of slot e
+    bool sweep = false;
+    std::vector<int32_t> plan_mode;
     int max_lvl = 1;                         // most escalation levels of a configuration in use (sizes the record blocks)
     const fot_loop_config &cfg_of(int e) const { return scenarios ? cfgs[(size_t)scen[(size_t)e]] : cfg; }
     std::vector<double> ego;                 // [n][5] x, y, yaw, v, a
@@ -165,6 +169,8 @@ struct LoopSamples {
     const void *rec = nullptr;                   // [n_steps][S][pred_len][n_cols][2]: dRec, or the caller's tensor
     DevBuf dRec, dRaw, dCol;                     // the copy | [S][pred_len][rows][2] of `dtype` | int32[rows]
     PinnedBuf hCol;                              // the table as the host builds it
+    int n_rec_cols = 0;                          // the recording's columns (fot_loop_set_samples: the replay's n_cols)
+    std::vector<int32_t> slot_col0;              // [slots] first column of each slot (fot_loop_set_samples: the replay's ped_off)
     std::vector<int32_t> sel;                    // the running slots dCol stands for (empty: none yet)
     void release() { dRec.release(); dRaw.release(); dCol.release(); hCol.release(); }
 };
@@ -243,6 +249,12 @@ struct LoopState {
     DevBuf dScenStatic, dGather, dSafScen;   // ... ; SafetyScen[scenarios]
     PinnedBuf hGather;                       // StaticGather[requests] of the plan call being enqueued
     std::vector<int32_t> frame_scen;         // scenario of each episode of the frame (empty: all on scenario 0)
+    // a sweep loop's frame that carried a distribution (fot_sweep.hpp): the planning blocks of its representative-mode
+    // episodes lie in dDyn behind the distribution blocks.  Empty: no such frame.  hSweep: the table where a resident
+    // step's kernels read it.
+    std::vector<SweepEp> sweep_tab;
+    int sweep_T = 0;
+    PinnedBuf hSweep;
     const int32_t *p_scen = nullptr;         // the same where k_safety reads it (beside p_off), or nullptr
     std::vector<int32_t> ped_off;            // of the frame
     std::vector<int64_t> blk_off;            // first point of each episode's block in the tensor
@@ -260,6 +272,7 @@ struct LoopState {
         hFrame.release(); hObserve.release(); hOut.release(); hRec.release();
         dDyn.release(); dStatic.release(); replay.release(); rep.release();
         dScenStatic.release(); dGather.release(); dSafScen.release(); hGather.release();
+        hSweep.release();
     }
 };
 

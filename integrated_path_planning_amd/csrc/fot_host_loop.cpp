@@ -61,6 +61,19 @@ int rep_ensure(fot_handle *h, int n_slots, int n_ep, size_t rows, int T)
     return FOT_OK;
 }
 
+// A resident sweep loop (fot_loop_begin_sweep) that predicts S samples: the selection's tables, the steps' SweepEp rows and
+// a tensor with room for every slot's planning block behind the distribution blocks, so that nothing grows inside a run.
+int sweep_ensure(fot_handle *h, int S)
+{
+    LoopState &L = h->loop;
+    const LoopReplay &R = L.replay;
+    const int n = R.cfg.n_slots, T = R.n_dense + 1;
+    { int r = rep_ensure(h, n, n, 0, T); if (r != FOT_OK) return r; }
+    HIP_TRY(h, L.hSweep.ensure(sizeof(SweepEp) * (size_t)std::max(n, 1)));
+    HIP_TRY(h, L.dDyn.ensure(sizeof(double) * 2 * (size_t)sweep_capacity_points(S, std::max(R.n_cols, 1), T)));
+    return FOT_OK;
+}
+
 // The planning blocks of the frame's n episodes behind their distribution blocks in dDyn (f: pos, ped0, blk): the
 // selection into the given tables (the mode's own, or the scores' where a resident loop scores too), then
 // k_loop_rep_block.  Enqueue only.
@@ -128,6 +141,11 @@ int loop_enqueue_requests(fot_handle *h, int32_t n_req, const fot_loop_request *
             d_off[j] = (int64_t)L.ped_off[e] * L.rep.T;
             dims[4 * j] = P_e > 0 ? FOT_DYN_SINGLE : FOT_DYN_NONE;
             dims[4 * j + 1] = 1; dims[4 * j + 2] = P_e; dims[4 * j + 3] = L.rep.T;
+        } else if (!L.sweep_tab.empty() && sweep_plans_on_block(L.sweep_tab[(size_t)e])) {
+            // a sweep loop's episode in representative mode: its block behind the distribution blocks of the same tensor
+            d_off[j] = L.sweep_tab[(size_t)e].rep_off;
+            dims[4 * j] = P_e > 0 ? FOT_DYN_SINGLE : FOT_DYN_NONE;
+            dims[4 * j + 1] = 1; dims[4 * j + 2] = P_e; dims[4 * j + 3] = L.sweep_T;
         } else {
             d_off[j] = L.blk_off[e];
             dims[4 * j] = P_e > 0 ? (L.dist_S > 0 ? FOT_DYN_DISTRIBUTION : FOT_DYN_SINGLE) : FOT_DYN_NONE;
@@ -201,7 +219,11 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
         const size_t ped_b = align256(sizeof(double) * 2 * std::max<size_t>(n_ped, 1));
         const size_t blk_b = align256(sizeof(int64_t) * ((size_t)n + 1)), pe_b = align256(sizeof(int32_t) * std::max<size_t>(n_ped, 1));
         const bool rep_on = L.rep.mode == FOT_LOOP_PLAN_REPRESENTATIVE && dist;   // (never a scenario loop: the tail is free)
-        HIP_TRY(h, L.hFrame.ensure(ego_b + off_b + 4 * ped_b + blk_b + pe_b + (ep_scen || rep_on ? off_b : 0)));
+        // a sweep loop's frame with a distribution needs both tail tables and, behind them, the episodes' SweepEp rows
+        const bool sweep_on = L.ep.sweep && ep_scen && dist;
+        const size_t tail = ego_b + off_b + 4 * ped_b + blk_b + pe_b;
+        HIP_TRY(h, L.hFrame.ensure(tail + (ep_scen || rep_on ? off_b : 0) +
+                                   (sweep_on ? off_b + align256(sizeof(SweepEp) * (size_t)std::max(n, 1)) : 0)));
         char *p = (char *)L.hFrame.p;
         double *p_ego = (double *)p;
         int32_t *p_off = (int32_t *)(p + ego_b);
@@ -220,6 +242,7 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
         L.t_len.assign((size_t)std::max(n, 1), 1);
         L.dist_S = dist ? frame->dist_S : 0;
         L.rep.frame = false;
+        L.sweep_tab.clear();
         for (int e = 0; e < n; ++e) {
             L.t_len[e] = dist ? n_dense + 1 : ready ? n_dense + (frame->prepend[e] ? 1 : 0) : 1;
             L.blk_off[e + 1] = L.blk_off[e] + (int64_t)(dist ? frame->dist_S : 1) * (L.ped_off[e + 1] - L.ped_off[e]) * L.t_len[e];
@@ -239,11 +262,34 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
             int32_t *p_pe = (int32_t *)((char *)p_blk + blk_b);
             for (int e = 0; e <= n; ++e) p_blk[e] = L.blk_off[e];
             for (int e = 0; e < n; ++e) for (int q = L.ped_off[e]; q < L.ped_off[e + 1]; ++q) p_pe[q] = e;
-            HIP_TRY(h, L.dDyn.ensure(sizeof(double) * 2 * (size_t)L.blk_off[n]));
+            int64_t tensor_pts = L.blk_off[n];
+            int32_t *p_slot = (int32_t *)(p + tail + off_b);     // (a sweep frame: the slots behind the scenarios)
+            SweepEp *p_sweep = (SweepEp *)(p + tail + 2 * off_b);
+            if (sweep_on) {
+                for (int e = 0; e < n; ++e) p_slot[e] = ep_slot ? ep_slot[e] : e;
+                tensor_pts = sweep_layout(n, L.ped_off.data(), p_slot, L.ep.plan_mode.data(), L.blk_off[n], n_dense + 1, false, p_sweep);
+            }
+            HIP_TRY(h, L.dDyn.ensure(sizeof(double) * 2 * (size_t)tensor_pts));
             L.dyn_ptr = L.dDyn.p;
             LAUNCH_TRY(h, launch_resample(frame->rp.sgan_dt, frame->rp.sim_dt, frame->staleness, frame->dist_S, frame->pred_len,
                                           (int)n_ped, n_dense, 1, 1, 0, frame->dist_raw, frame->dist_dtype, p_last, p_pos,
                                           L.dDyn.p, FOT_F64, 0, st, p_pe, p_off, p_blk));
+            if (sweep_on && tensor_pts > L.blk_off[n]) {
+                // the selection and the planning blocks of the episodes in representative mode, behind the resample
+                { int r = rep_ensure(h, std::max(L.ep.n, n), n, 0, n_dense + 1); if (r != FOT_OK) return r; }
+                FrameDev fd;
+                fd.pos = p_pos; fd.ped0 = p_off; fd.blk = p_blk;
+                LAUNCH_TRY(h, launch_loop_best_sample_sweep(p_slot, fd, L.dDyn.as<double>(), p_sweep, n, frame->dist_S, n_dense,
+                                                            L.rep.dDev.as<double>(), L.rep.dBest.as<int32_t>(),
+                                                            (int32_t *)L.rep.hBest.p, st));
+                LAUNCH_TRY(h, launch_loop_rep_block_sweep(p_slot, fd, L.dDyn.as<double>(), p_sweep, L.rep.dBest.as<int32_t>(), n,
+                                                          frame->dist_S, n_dense, L.dDyn.as<double>(), L.rep.dPre.as<int32_t>(),
+                                                          (int32_t *)L.rep.hPre.p, st));
+                L.sweep_tab.assign(p_sweep, p_sweep + n);
+                L.sweep_T = n_dense + 1;
+                rep_pending = true;
+                rep_slots.assign(p_slot, p_slot + n);
+            }
             if (rep_on) {
                 // the selection and every episode's single-sample block behind the resample, on the same stream
                 int32_t *p_slot = (int32_t *)(p + ego_b + off_b + 4 * ped_b + blk_b + pe_b);
@@ -306,12 +352,13 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
         HIP_TRY(h, hipStreamSynchronize(st));
     }
     if (metrics) std::memcpy(safety_out, L.hOut.p, sizeof(fot_safety) * (size_t)n_ep);
-    if (frame && L.rep.mode == FOT_LOOP_PLAN_REPRESENTATIVE)     // (a frame without a distribution chose nothing)
+    if (frame && (L.rep.mode == FOT_LOOP_PLAN_REPRESENTATIVE || L.ep.sweep))   // (a frame without a distribution chose nothing)
         std::fill(L.rep.last_best.begin(), L.rep.last_best.end(), -1);
-    if (frame && L.rep.frame) {                                  // (the selection ran ahead of the plan on this stream)
+    if (frame && (L.rep.frame || !L.sweep_tab.empty())) {        // (the selection ran ahead of the plan on this stream)
         const int32_t *best = (const int32_t *)L.rep.hBest.p;
         for (size_t e = 0; e < rep_slots.size(); ++e) {
             const int slot = rep_slots[e];
+            if (!L.sweep_tab.empty() && !sweep_plans_on_block(L.sweep_tab[e])) continue;   // (a sweep's distribution mode)
             if (rep_pending && slot < (int)L.rep.last_best.size() && L.ped_off[e + 1] > L.ped_off[e]) L.rep.last_best[(size_t)slot] = best[slot];
         }
     }
@@ -630,6 +677,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     L.ped_off.assign((size_t)n + 1, 0); L.blk_off.assign((size_t)n + 1, 0); L.t_len.assign((size_t)n, 1);
     L.dist_S = 0;
     L.rep.frame = false;
+    L.sweep_tab.clear();
     const size_t row_doubles = 2 * (size_t)R.n_cols;
     int rows_run = 0;
     for (int i = 0; i < n; ++i) rows_run += R.ped_off[sel[i] + 1] - R.ped_off[sel[i]];
@@ -673,12 +721,12 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         LoopSamples &M = R.rec;
         if (M.sel != sel) {                                      // a slot dropped out (or the first step): the row -> column table
             int32_t *col = (int32_t *)M.hCol.p;                  // (no copy of an earlier step still reads it: every step ends
-            sr_fill_columns(n, L.ped_off.data(), sel.data(), R.ped_off.data(), col);    //  with the host waiting for its word)
+            sweep_fill_columns(n, L.ped_off.data(), sel.data(), M.slot_col0.data(), col);    //  with the host waiting for its word)
             HIP_TRY(h, hipMemcpyAsync(M.dCol.p, col, sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice, st));
             M.sel = sel;
         }
         LoopSampleRows a{};
-        a.d.S = M.S; a.d.pred_len = C.pred_len; a.d.rows = rows; a.d.n_cols = R.n_cols;
+        a.d.S = M.S; a.d.pred_len = C.pred_len; a.d.rows = rows; a.d.n_cols = M.n_rec_cols;
         a.d.rec_row = (int64_t)R.steps[(size_t)sel[0]] - M.first_step;
         a.rec = M.rec; a.col = M.dCol.as<int32_t>(); a.out = M.dRaw.p; a.dtype = M.dtype;
         LAUNCH_TRY(h, launch_loop_sample_rows(a, st));
@@ -724,7 +772,26 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     }
     const bool scored = R.sc.on && sampled;                      // the step's distributions are scored where they lie
     const bool rep_on = L.rep.mode == FOT_LOOP_PLAN_REPRESENTATIVE && sampled;   // ... the requests plan on one sample of each
-    if (rep_on) {
+    const bool sweep_on = E.sweep && sampled;                    // ... each in its slot's own mode
+    if (sweep_on) {
+        // the selection of the episodes that plan on their sample (of all, where the loop scores), into the scores' tables
+        // where they are on; then the planning blocks, compacted behind the distribution blocks (fot_sweep.hpp)
+        SweepEp *tab = (SweepEp *)L.hSweep.p;
+        const int64_t pts = sweep_layout(n, L.ped_off.data(), sel.data(), E.plan_mode.data(), L.blk_off[n], R.n_dense + 1, R.sc.on, tab);
+        if (sizeof(double) * 2 * (size_t)pts > L.dDyn.cap) return fail(h, FOT_ERR_INVALID, "internal: the sweep's tensor is too small");
+        int32_t *best_tab = R.sc.on ? R.sc.dBest.as<int32_t>() : L.rep.dBest.as<int32_t>();
+        bool any_select = false;                                 // (every running slot in distribution mode, no scores: no launch)
+        for (int i = 0; i < n; ++i) any_select = any_select || tab[i].select != 0;
+        if (any_select)
+            LAUNCH_TRY(h, launch_loop_best_sample_sweep(sg.slot, fd, L.dDyn.as<double>(), tab, n, dist_S, R.n_dense,
+                                                        R.sc.on ? R.sc.dDev.as<double>() : L.rep.dDev.as<double>(), best_tab,
+                                                        (int32_t *)(R.sc.on ? R.sc.hBest.p : L.rep.hBest.p), st));
+        if (pts > L.blk_off[n])                                  // (some running episode has a planning block to write)
+            LAUNCH_TRY(h, launch_loop_rep_block_sweep(sg.slot, fd, L.dDyn.as<double>(), tab, best_tab, n, dist_S, R.n_dense,
+                                                      L.dDyn.as<double>(), L.rep.dPre.as<int32_t>(), (int32_t *)L.rep.hPre.p, st));
+        L.sweep_tab.assign(tab, tab + n);
+        L.sweep_T = R.n_dense + 1;
+    } else if (rep_on) {
         // the selection once, into the scores' tables where they are on: a scored and a planning loop read the same choice
         { int r = rep_ensure(h, n_slots, n_slots, (size_t)R.n_cols, R.n_dense + 1); if (r != FOT_OK) return r; }
         { int r = rep_enqueue(h, sg.slot, fd, n, dist_S, R.n_dense, R.sc.on ? R.sc.dDev.as<double>() : L.rep.dDev.as<double>(),
@@ -780,7 +847,13 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
             if (scored && L.ped_off[(size_t)i + 1] > L.ped_off[(size_t)i]) Q.last_best[(size_t)e] = best[e];
         }
     }
-    if (L.rep.mode == FOT_LOOP_PLAN_REPRESENTATIVE) {            // the choice the step planned on (fot_loop_last_best_sample)
+    if (E.sweep) {                                               // a slot's choice where it planned on it or the loop scores
+        const int32_t *best = (const int32_t *)(R.sc.on ? R.sc.hBest.p : L.rep.hBest.p);
+        std::fill(L.rep.last_best.begin(), L.rep.last_best.end(), -1);
+        for (int i = 0; sweep_on && i < n; ++i)
+            if (L.sweep_tab[(size_t)i].select && L.ped_off[(size_t)i + 1] > L.ped_off[(size_t)i]) L.rep.last_best[(size_t)sel[i]] = best[sel[i]];
+        L.rep.run_best.insert(L.rep.run_best.end(), L.rep.last_best.begin(), L.rep.last_best.end());
+    } else if (L.rep.mode == FOT_LOOP_PLAN_REPRESENTATIVE) {     // the choice the step planned on (fot_loop_last_best_sample)
         const int32_t *best = (const int32_t *)(R.sc.on ? R.sc.hBest.p : L.rep.hBest.p);
         std::fill(L.rep.last_best.begin(), L.rep.last_best.end(), -1);
         for (int i = 0; rep_on && i < n; ++i)
@@ -904,6 +977,67 @@ int summaries_fill(fot_handle *h, int32_t n_slots, fot_loop_summary *out)
     return FOT_OK;
 }
 
+// fot_loop_set_samples / fot_loop_set_samples_shared (who: the entry's name, for the messages); slot_col0 == nullptr: the
+// recording's columns are the replay's own
+int set_samples_impl(fot_handle *h, const std::string &who, int32_t S, int32_t n_steps, int32_t first_step, const void *samples,
+                     int32_t dtype, int32_t flags, bool shared, int32_t n_rec_cols, const int32_t *slot_col0)
+{
+    LoopState &L = h->loop;
+    LoopReplay &R = L.replay;
+    if (!R.set) return fail(h, FOT_ERR_INVALID, who + ": fot_loop_set_replay comes first");
+    if (R.smp.on) return fail(h, FOT_ERR_INVALID, who + ": a sampler is set (fot_loop_set_sampler): one predictor per run");
+    const int n = R.cfg.n_slots;
+    bool begun = R.clock.frame != R.cfg.warmup_frames;
+    for (int e = 0; e < n; ++e) begun = begun || R.steps[(size_t)e] != 0;
+    if (begun) return fail(h, FOT_ERR_INVALID, who + ": the run has begun (set it between fot_loop_set_replay and the first step)");
+    if (S < 1) return fail(h, FOT_ERR_INVALID, who + ": S < 1");
+    if (n_steps < 1 || first_step < 0) return fail(h, FOT_ERR_INVALID, who + ": n_steps < 1 / first_step < 0");
+    if (!samples) return fail(h, FOT_ERR_INVALID, who + ": samples is NULL");
+    if (dtype != FOT_F32 && dtype != FOT_F64) return fail(h, FOT_ERR_INVALID, who + ": dtype is FOT_F32 or FOT_F64");
+    if (flags & ~FOT_OUT_DEVICE) return fail(h, FOT_ERR_INVALID, who + ": flags");
+    const size_t elem = dtype == FOT_F32 ? 2 * sizeof(float) : 2 * sizeof(double);
+    // (the gather moves whole elements of two coordinates; hipMalloc allocations and their slices along any axis
+    //  but the last are aligned to one)
+    if ((flags & FOT_OUT_DEVICE) && (uintptr_t)samples % elem != 0)
+        return fail(h, FOT_ERR_INVALID, who + ": device samples must be aligned to one [x, y] element");
+    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, who + ": S > FOT_MAX_SAMPLES");
+    if (L.ep.scenarios && !L.ep.sweep) return fail(h, FOT_ERR_UNSUPPORTED, who + ": a scenario loop plans against no distribution");
+    if (R.sum.on) return fail(h, FOT_ERR_UNSUPPORTED, who + ": summaries are enabled (their prediction-error ring reads the constant-velocity tensor)");
+    if (shared) {
+        if (!slot_col0) return fail(h, FOT_ERR_INVALID, who + ": slot_col0 is NULL");
+        if (R.n_cols > 0 && n_rec_cols < 1) return fail(h, FOT_ERR_INVALID, who + ": n_rec_cols < 1");
+        if (!sweep_columns_fit(n, R.ped_off.data(), slot_col0, n_rec_cols))
+            return fail(h, FOT_ERR_INVALID, who + ": a slot's columns (slot_col0[e] .. slot_col0[e] + P_e) lie outside the recording's n_rec_cols");
+    } else {
+        n_rec_cols = R.n_cols; slot_col0 = R.ped_off.data();
+    }
+    // --- accepted: everything a step needs is allocated here, so that no block grows (and moves) inside a run
+    LoopSamples &M = R.rec;
+    const size_t N = std::max<size_t>((size_t)R.n_cols, 1), rows = (size_t)S * N;
+    const size_t rec_bytes = (size_t)sr_rec_elems(n_steps, S, R.cfg.pred_len, n_rec_cols) * elem;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    M.on = false; M.rec = nullptr;
+    HIP_TRY(h, M.dRaw.ensure(elem * (size_t)S * (size_t)R.cfg.pred_len * N));
+    HIP_TRY(h, M.dCol.ensure(sizeof(int32_t) * N));
+    HIP_TRY(h, M.hCol.ensure(sizeof(int32_t) * N));
+    HIP_TRY(h, L.dDyn.ensure(sizeof(double) * 2 * rows * (size_t)(R.n_dense + 1)));
+    if (L.ep.sweep) { int r = sweep_ensure(h, S); if (r != FOT_OK) return r; }
+    if (flags & FOT_OUT_DEVICE) {
+        M.rec = samples;                                         // used in place, never written
+    } else {
+        HIP_TRY(h, M.dRec.ensure(std::max<size_t>(rec_bytes, elem)));
+        if (rec_bytes) HIP_TRY(h, hipMemcpy(M.dRec.p, samples, rec_bytes, hipMemcpyHostToDevice));
+        M.rec = M.dRec.p;
+    }
+    M.S = S; M.n_steps = n_steps; M.first_step = first_step; M.dtype = dtype;
+    M.n_rec_cols = n_rec_cols; M.slot_col0.assign(slot_col0, slot_col0 + n);
+    M.sel.clear();
+    M.on = true;
+    R.sc.on = false;                                             // (a new recording: its scores are enabled again, if wanted)
+    return FOT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -975,6 +1109,7 @@ int fot_loop_begin(fot_handle *h, int32_t n_episodes, const fot_loop_config *cfg
     const size_t n = (size_t)n_episodes;
     E.n = n_episodes; E.cfg = *cfg;
     E.scenarios = false; E.cfgs.clear(); E.use_fp.clear(); E.scen.clear();
+    E.sweep = false; E.plan_mode.clear(); h->loop.sweep_tab.clear();
     E.max_lvl = loop_max_levels(*cfg);
     h->loop.frame_scen.clear(); h->loop.p_scen = nullptr;
     E.ego.assign(ego5, ego5 + 5 * n);
@@ -1031,6 +1166,7 @@ int fot_loop_begin_scenarios(fot_handle *h, int32_t n_episodes, int32_t n_cfg, c
     const size_t n = (size_t)n_episodes;
     E.n = n_episodes; E.cfg = cfg[first];
     E.scenarios = true;
+    E.sweep = false; E.plan_mode.clear(); L.sweep_tab.clear();
     E.cfgs.assign(cfg, cfg + n_cfg);
     E.use_fp.assign((size_t)n_cfg, 0);
     for (int s = 0; s < n_cfg; ++s) E.use_fp[(size_t)s] = use_footprint && use_footprint[s] ? 1 : 0;
@@ -1052,6 +1188,24 @@ int fot_loop_begin_scenarios(fot_handle *h, int32_t n_episodes, int32_t n_cfg, c
     return FOT_OK;
 }
 
+int fot_loop_begin_sweep(fot_handle *h, int32_t n_episodes, int32_t n_cfg, const fot_loop_config *cfg,
+                         const int32_t *use_footprint, const int32_t *slot_scenario, const int32_t *slot_plan_mode,
+                         const double *ego5)
+{
+    if (!h) return FOT_ERR_INVALID;
+    for (int e = 0; slot_plan_mode && e < n_episodes; ++e)
+        if (slot_plan_mode[e] != FOT_LOOP_PLAN_DISTRIBUTION && slot_plan_mode[e] != FOT_LOOP_PLAN_REPRESENTATIVE)
+            return fail(h, FOT_ERR_INVALID, "fot_loop_begin_sweep: a slot's plan mode is FOT_LOOP_PLAN_DISTRIBUTION or FOT_LOOP_PLAN_REPRESENTATIVE");
+    // a scenario loop in every respect (the same arguments, the same refusals) ...
+    { int r = fot_loop_begin_scenarios(h, n_episodes, n_cfg, cfg, use_footprint, slot_scenario, ego5); if (r != FOT_OK) return r; }
+    // ... whose lock steps may carry a distribution, planned against in each slot's own mode
+    LoopEpisodes &E = h->loop.ep;
+    E.sweep = true;
+    E.plan_mode.assign((size_t)n_episodes, FOT_LOOP_PLAN_DISTRIBUTION);
+    if (slot_plan_mode) E.plan_mode.assign(slot_plan_mode, slot_plan_mode + n_episodes);
+    return FOT_OK;
+}
+
 int fot_loop_step(fot_handle *h, const fot_loop_frame *frame, const int32_t *episode, fot_loop_step_out *out)
 {
     if (!h) return FOT_ERR_INVALID;
@@ -1070,7 +1224,7 @@ int fot_loop_step(fot_handle *h, const fot_loop_frame *frame, const int32_t *epi
     }
     std::vector<int32_t> ep_scen;
     if (E.scenarios) {
-        if (frame->dist_raw) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_step: a scenario loop takes the constant-velocity predictor only (no dist_raw)");
+        if (frame->dist_raw && !E.sweep) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_step: a scenario loop takes the constant-velocity predictor only (no dist_raw)");
         ep_scen.resize((size_t)n);
         for (int i = 0; i < n; ++i) {
             ep_scen[(size_t)i] = E.scen[(size_t)episode[i]];
@@ -1307,7 +1461,7 @@ int fot_loop_last_best_sample(fot_handle *h, int32_t n_slots, int32_t *out)
     if (!h) return FOT_ERR_INVALID;
     LoopReplay &R = h->loop.replay;
     const LoopRep &Q = h->loop.rep;
-    const bool scores = R.set && R.sc.on, planned = Q.mode == FOT_LOOP_PLAN_REPRESENTATIVE;
+    const bool scores = R.set && R.sc.on, planned = Q.mode == FOT_LOOP_PLAN_REPRESENTATIVE || h->loop.ep.sweep;
     if (!scores && !planned)
         return fail(h, FOT_ERR_INVALID, "fot_loop_last_best_sample: scores are not enabled (fot_loop_scores_enable)");
     // (a stepwise loop planning on the representative sample: the slots of fot_loop_begin)
@@ -1325,6 +1479,7 @@ int fot_loop_plan_sample(fot_handle *h, int32_t mode)
     if (mode != FOT_LOOP_PLAN_DISTRIBUTION && mode != FOT_LOOP_PLAN_REPRESENTATIVE)
         return fail(h, FOT_ERR_INVALID, "fot_loop_plan_sample: mode is FOT_LOOP_PLAN_DISTRIBUTION or FOT_LOOP_PLAN_REPRESENTATIVE");
     if (!(L.ep.cfg.dt > 0.0)) return fail(h, FOT_ERR_INVALID, "fot_loop_plan_sample: fot_loop_begin comes first");
+    if (L.ep.sweep) return fail(h, FOT_ERR_INVALID, "fot_loop_plan_sample: a sweep loop's plan modes were given per slot (fot_loop_begin_sweep)");
     if (L.ep.scenarios) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_plan_sample: a scenario loop plans against no distribution");
     if (R.set) {
         bool begun = R.clock.frame != R.cfg.warmup_frames;
@@ -1348,7 +1503,7 @@ int fot_loop_run_best_samples(fot_handle *h, int32_t n_steps, int32_t n_slots, i
 {
     if (!h) return FOT_ERR_INVALID;
     const LoopState &L = h->loop;
-    if (!L.replay.set || L.rep.mode != FOT_LOOP_PLAN_REPRESENTATIVE)
+    if (!L.replay.set || (L.rep.mode != FOT_LOOP_PLAN_REPRESENTATIVE && !L.ep.sweep))
         return fail(h, FOT_ERR_INVALID, "fot_loop_run_best_samples: no resident run plans on the representative sample (fot_loop_plan_sample)");
     if (n_slots != L.replay.cfg.n_slots) return fail(h, FOT_ERR_INVALID, "fot_loop_run_best_samples: n_slots differs from the loop's");
     if (n_steps < 0 || (size_t)n_steps * (size_t)n_slots != L.rep.run_best.size())
@@ -1376,6 +1531,9 @@ int fot_debug_loop_block(fot_handle *h, int32_t episode, int32_t cap_points, dou
     const void *base = nullptr;
     if (L.rep.frame) {
         t_len = L.rep.T; first = (int64_t)L.ped_off[e] * t_len; n_pts = (int64_t)P_e * t_len; base = L.rep.dBlk.p;
+        if (P_e > 0) pre = ((const int32_t *)L.rep.hPre.p)[e];
+    } else if (!L.sweep_tab.empty() && sweep_plans_on_block(L.sweep_tab[e])) {   // (a sweep's episode in representative mode)
+        t_len = L.sweep_T; first = L.sweep_tab[e].rep_off; n_pts = sweep_block_points(P_e, t_len); base = L.dyn_ptr;
         if (P_e > 0) pre = ((const int32_t *)L.rep.hPre.p)[e];
     } else {
         t_len = L.t_len[e]; first = L.blk_off[e]; n_pts = (int64_t)std::max(L.dist_S, 1) * P_e * t_len; base = L.dyn_ptr;
@@ -1412,7 +1570,7 @@ int fot_loop_set_sampler(fot_handle *h, int32_t S, uint64_t seed, int32_t kind)
     for (int e = 0; e < n; ++e)
         if (R.ped_off[(size_t)e + 1] - R.ped_off[(size_t)e] > FOT_SGAN_MAX_PEDS)
             return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_sampler: a slot of more than FOT_SGAN_MAX_PEDS pedestrians");
-    if (L.ep.scenarios) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_sampler: a scenario loop plans against no distribution");
+    if (L.ep.scenarios && !L.ep.sweep) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_sampler: a scenario loop plans against no distribution");
     if (R.sum.on) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_sampler: summaries are enabled (their prediction-error ring reads the constant-velocity tensor)");
     // --- accepted: everything a step needs is allocated here, so that no block grows (and moves) inside a run
     LoopSampler &M = R.smp;
@@ -1426,6 +1584,7 @@ int fot_loop_set_sampler(fot_handle *h, int32_t S, uint64_t seed, int32_t kind)
     HIP_TRY(h, M.dRaw.ensure(sizeof(float) * 2 * (size_t)S * (size_t)d.pred_len * N));
     HIP_TRY(h, M.hTab.ensure(sizeof(int32_t) * 3 * (N + ns)));
     HIP_TRY(h, L.dDyn.ensure(sizeof(double) * 2 * rows * (size_t)(R.n_dense + 1)));
+    if (L.ep.sweep) { int r = sweep_ensure(h, S); if (r != FOT_OK) return r; }
     HIP_TRY(h, G.dHenc.ensure(sizeof(float) * N * (size_t)d.encoder_h_dim));
     if (bp > 0) HIP_TRY(h, G.dPool.ensure(sizeof(float) * (sg_pool_steps(d) ? rows : N) * (size_t)bp));
     if (sg_has_context(d)) HIP_TRY(h, G.dCtx.ensure(sizeof(float) * N * (size_t)std::max(d.decoder_h_dim - d.noise_dim, 1)));
@@ -1444,50 +1603,14 @@ int fot_loop_set_samples(fot_handle *h, int32_t S, int32_t n_steps, int32_t firs
                          int32_t flags)
 {
     if (!h) return FOT_ERR_INVALID;
-    LoopState &L = h->loop;
-    LoopReplay &R = L.replay;
-    if (!R.set) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: fot_loop_set_replay comes first");
-    if (R.smp.on) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: a sampler is set (fot_loop_set_sampler): one predictor per run");
-    const int n = R.cfg.n_slots;
-    bool begun = R.clock.frame != R.cfg.warmup_frames;
-    for (int e = 0; e < n; ++e) begun = begun || R.steps[(size_t)e] != 0;
-    if (begun) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: the run has begun (set it between fot_loop_set_replay and the first step)");
-    if (S < 1) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: S < 1");
-    if (n_steps < 1 || first_step < 0) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: n_steps < 1 / first_step < 0");
-    if (!samples) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: samples is NULL");
-    if (dtype != FOT_F32 && dtype != FOT_F64) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: dtype is FOT_F32 or FOT_F64");
-    if (flags & ~FOT_OUT_DEVICE) return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: flags");
-    const size_t elem = dtype == FOT_F32 ? 2 * sizeof(float) : 2 * sizeof(double);
-    // (the gather moves whole elements of two coordinates; hipMalloc allocations and their slices along any axis
-    //  but the last are aligned to one)
-    if ((flags & FOT_OUT_DEVICE) && (uintptr_t)samples % elem != 0)
-        return fail(h, FOT_ERR_INVALID, "fot_loop_set_samples: device samples must be aligned to one [x, y] element");
-    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_samples: S > FOT_MAX_SAMPLES");
-    if (L.ep.scenarios) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_samples: a scenario loop plans against no distribution");
-    if (R.sum.on) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_samples: summaries are enabled (their prediction-error ring reads the constant-velocity tensor)");
-    // --- accepted: everything a step needs is allocated here, so that no block grows (and moves) inside a run
-    LoopSamples &M = R.rec;
-    const size_t N = std::max<size_t>((size_t)R.n_cols, 1), rows = (size_t)S * N;
-    const size_t rec_bytes = (size_t)sr_rec_elems(n_steps, S, R.cfg.pred_len, R.n_cols) * elem;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    M.on = false; M.rec = nullptr;
-    HIP_TRY(h, M.dRaw.ensure(elem * (size_t)S * (size_t)R.cfg.pred_len * N));
-    HIP_TRY(h, M.dCol.ensure(sizeof(int32_t) * N));
-    HIP_TRY(h, M.hCol.ensure(sizeof(int32_t) * N));
-    HIP_TRY(h, L.dDyn.ensure(sizeof(double) * 2 * rows * (size_t)(R.n_dense + 1)));
-    if (flags & FOT_OUT_DEVICE) {
-        M.rec = samples;                                         // used in place, never written
-    } else {
-        HIP_TRY(h, M.dRec.ensure(std::max<size_t>(rec_bytes, elem)));
-        if (rec_bytes) HIP_TRY(h, hipMemcpy(M.dRec.p, samples, rec_bytes, hipMemcpyHostToDevice));
-        M.rec = M.dRec.p;
-    }
-    M.S = S; M.n_steps = n_steps; M.first_step = first_step; M.dtype = dtype;
-    M.sel.clear();
-    M.on = true;
-    R.sc.on = false;                                             // (a new recording: its scores are enabled again, if wanted)
-    return FOT_OK;
+    return set_samples_impl(h, "fot_loop_set_samples", S, n_steps, first_step, samples, dtype, flags, false, 0, nullptr);
+}
+
+int fot_loop_set_samples_shared(fot_handle *h, int32_t S, int32_t n_steps, int32_t first_step, const void *samples,
+                                int32_t dtype, int32_t flags, int32_t n_rec_cols, const int32_t *slot_col0)
+{
+    if (!h) return FOT_ERR_INVALID;
+    return set_samples_impl(h, "fot_loop_set_samples_shared", S, n_steps, first_step, samples, dtype, flags, true, n_rec_cols, slot_col0);
 }
 
 int fot_loop_run(fot_handle *h, int32_t max_steps, fot_loop_run_out *out)

@@ -9,6 +9,7 @@
 #include "fot_loopscore.hpp"
 #include "fot_repsample.hpp"
 #include "fot_samplerec.hpp"
+#include "fot_sweep.hpp"
 
 namespace fot {
 
@@ -144,6 +145,15 @@ int launch_loop_best_sample(const int32_t *slot_of, FrameDev f, const double *dy
 // current positions lead the block.  Only f.pos, f.ped0 and f.blk are read; an episode without pedestrians writes nothing.
 int launch_loop_rep_block(const int32_t *slot_of, FrameDev f, const double *dyn, const int32_t *best_tab, int n_run, int S,
                           int n_dense, double *rep, int32_t *pre_dev, int32_t *pre_host, hipStream_t st);
+// ---- fot_loop_begin_sweep (fot_sweep.hpp): the two launches above with a row of tab (pinned host memory) per running
+// episode.  Only episodes with tab[i].select choose a sample (the others' table entries are left alone); only episodes
+// with tab[i].rep_off >= 0 write a planning block, at that point of `tensor` -- the step's own tensor, behind the
+// distribution blocks `dyn` reads.  An episode's numbers are those of the uniform launches, bit for bit.
+int launch_loop_best_sample_sweep(const int32_t *slot_of, FrameDev f, const double *dyn, const SweepEp *tab, int n_run, int S,
+                                  int n_dense, double *dev_tab, int32_t *best_tab, int32_t *best_host, hipStream_t st);
+int launch_loop_rep_block_sweep(const int32_t *slot_of, FrameDev f, const double *dyn, const SweepEp *tab,
+                                const int32_t *best_tab, int n_run, int S, int n_dense, double *tensor, int32_t *pre_dev,
+                                int32_t *pre_host, hipStream_t st);
 // The truth k_pred_scores reads for the step's origins, out[n_rows][E][2] (HBM): recording row min(f_cur + stride j,
 // frames - 1), j = 1 .. E, of every row of the frame.
 int launch_loop_score_truth(ReplayView rv, const int32_t *slot_of, FrameDev f, int n_rows, int f_cur, int stride, int E,

@@ -529,14 +529,14 @@ k_loop_summary(SummaryShape S, const double *__restrict__ ring, const int32_t *_
 constexpr int BS_THREADS = 256;
 constexpr int BS_WAVES = BS_THREADS / WAVE;
 
-__global__ void __launch_bounds__(BS_THREADS)
-k_loop_best_sample(const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn, int n_run, int S,
-                   int n_dense, double *__restrict__ dev_tab, int32_t *__restrict__ best_tab, int32_t *best_host)
+// (the body of both forms: running episode i = blockIdx.x, checked by the caller)
+__device__ __forceinline__ void
+best_sample_episode(const int32_t *__restrict__ slot_of, const FrameDev &f, const double *__restrict__ dyn, int S,
+                    int n_dense, double *__restrict__ dev_tab, int32_t *__restrict__ best_tab, int32_t *best_host)
 {
     __shared__ double s_part[FOT_MAX_SAMPLES][BS_WAVES];
     __shared__ double s_dev[FOT_MAX_SAMPLES];
     const int i = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    if (i >= n_run) return;
     const int slot = slot_of[i], p0 = f.ped0[i], P = f.ped0[i + 1] - p0;
     if (P <= 0) {                                                    // (uniform)
         if (tid == 0) { best_tab[slot] = -1; best_host[slot] = -1; }
@@ -584,6 +584,25 @@ k_loop_best_sample(const int32_t *__restrict__ slot_of, FrameDev f, const double
     }
 }
 
+__global__ void __launch_bounds__(BS_THREADS)
+k_loop_best_sample(const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn, int n_run, int S,
+                   int n_dense, double *__restrict__ dev_tab, int32_t *__restrict__ best_tab, int32_t *best_host)
+{
+    if ((int)blockIdx.x >= n_run) return;
+    best_sample_episode(slot_of, f, dyn, S, n_dense, dev_tab, best_tab, best_host);
+}
+
+// The sweep form (fot_sweep.hpp): only the episodes whose table row asks for it choose; the others leave their slot's
+// entries alone (the host reads them for chosen episodes only).  An episode's sums are the uniform form's, bit for bit.
+__global__ void __launch_bounds__(BS_THREADS)
+k_loop_best_sample_sweep(const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn,
+                         const SweepEp *__restrict__ tab, int n_run, int S, int n_dense, double *__restrict__ dev_tab,
+                         int32_t *__restrict__ best_tab, int32_t *best_host)
+{
+    if ((int)blockIdx.x >= n_run || tab[blockIdx.x].select == 0) return;     // (uniform)
+    best_sample_episode(slot_of, f, dyn, S, n_dense, dev_tab, best_tab, best_host);
+}
+
 // One thread per (row of the frame, evaluation step j): the truth of the step's origins, [rows][E][2], from the resident
 // recording -- row min(f_cur + stride (j + 1), frames - 1) of the pedestrian's slot (a shorter recording holds its last frame).
 __global__ void __launch_bounds__(256)
@@ -609,14 +628,14 @@ k_loop_score_truth(ReplayView rv, const int32_t *__restrict__ slot_of, FrameDev 
 // pre_dev[i] (HBM) and pre_host[i] (pinned).  An episode without pedestrians writes nothing.
 constexpr int RB_THREADS = 256;
 
-__global__ void __launch_bounds__(RB_THREADS)
-k_loop_rep_block(const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn,
-                 const int32_t *__restrict__ best_tab, int n_run, int S, int n_dense, double *__restrict__ rep,
-                 int32_t *__restrict__ pre_dev, int32_t *pre_host)
+// (the body of both forms: running episode i = blockIdx.x, checked by the caller; the block starts at point out_pt of rep)
+__device__ __forceinline__ void
+rep_block_episode(const int32_t *__restrict__ slot_of, const FrameDev &f, const double *__restrict__ dyn,
+                  const int32_t *__restrict__ best_tab, int S, int n_dense, double *__restrict__ rep, int64_t out_pt,
+                  int32_t *__restrict__ pre_dev, int32_t *pre_host)
 {
     __shared__ int s_far[RB_THREADS / WAVE];
     const int i = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    if (i >= n_run) return;
     const int p0 = f.ped0[i], P = f.ped0[i + 1] - p0;
     if (P <= 0) return;                                              // (uniform)
     const int T = n_dense + 1, n = P * T;
@@ -635,12 +654,34 @@ k_loop_rep_block(const int32_t *__restrict__ slot_of, FrameDev f, const double *
     int far = 0;
     for (int w = 0; w < RB_THREADS / WAVE; ++w) far |= s_far[w];
     const bool prepend = far != 0;
-    double2 *out = (double2 *)rep + (int64_t)p0 * T;
+    double2 *out = (double2 *)rep + out_pt;
     for (int idx = tid; idx < n; idx += RB_THREADS) {
         const int p = idx / T, t = idx - p * T;
         out[idx] = prepend && t == 0 ? cur[p] : src[(int64_t)p * T + rs_src(t, T, prepend)];
     }
     if (tid == 0) { pre_dev[i] = prepend ? 1 : 0; pre_host[i] = prepend ? 1 : 0; }
+}
+
+__global__ void __launch_bounds__(RB_THREADS)
+k_loop_rep_block(const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn,
+                 const int32_t *__restrict__ best_tab, int n_run, int S, int n_dense, double *__restrict__ rep,
+                 int32_t *__restrict__ pre_dev, int32_t *pre_host)
+{
+    const int i = blockIdx.x;
+    if (i >= n_run) return;
+    rep_block_episode(slot_of, f, dyn, best_tab, S, n_dense, rep, (int64_t)f.ped0[i] * (n_dense + 1), pre_dev, pre_host);
+}
+
+// The sweep form (fot_sweep.hpp): the episodes in representative mode write their blocks into the step's tensor itself,
+// at the compacted offsets behind the distribution blocks (which are only read: the two regions never overlap).
+__global__ void __launch_bounds__(RB_THREADS)
+k_loop_rep_block_sweep(const int32_t *__restrict__ slot_of, FrameDev f, const double *dyn, const SweepEp *__restrict__ tab,
+                       const int32_t *__restrict__ best_tab, int n_run, int S, int n_dense, double *tensor,
+                       int32_t *__restrict__ pre_dev, int32_t *pre_host)
+{
+    const int i = blockIdx.x;
+    if (i >= n_run || !sweep_plans_on_block(tab[i])) return;             // (uniform)
+    rep_block_episode(slot_of, f, dyn, best_tab, S, n_dense, tensor, tab[i].rep_off, pre_dev, pre_host);
 }
 
 // ---------------------------------------------------------------------------
@@ -778,6 +819,27 @@ int launch_loop_best_sample(const int32_t *slot_of, FrameDev f, const double *dy
     if (n_run <= 0) return 0;
     if (S < 1 || S > FOT_MAX_SAMPLES || n_dense < 1) return (int)hipErrorInvalidValue;
     k_loop_best_sample<<<n_run, BS_THREADS, 0, st>>>(slot_of, f, dyn, n_run, S, n_dense, dev_tab, best_tab, best_host);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_best_sample_sweep(const int32_t *slot_of, FrameDev f, const double *dyn, const SweepEp *tab, int n_run, int S,
+                                  int n_dense, double *dev_tab, int32_t *best_tab, int32_t *best_host, hipStream_t st)
+{
+    if (n_run <= 0) return 0;
+    if (S < 1 || S > FOT_MAX_SAMPLES || n_dense < 1 || !tab) return (int)hipErrorInvalidValue;
+    k_loop_best_sample_sweep<<<n_run, BS_THREADS, 0, st>>>(slot_of, f, dyn, tab, n_run, S, n_dense, dev_tab, best_tab, best_host);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_rep_block_sweep(const int32_t *slot_of, FrameDev f, const double *dyn, const SweepEp *tab,
+                                const int32_t *best_tab, int n_run, int S, int n_dense, double *tensor, int32_t *pre_dev,
+                                int32_t *pre_host, hipStream_t st)
+{
+    if (n_run <= 0) return 0;
+    if (S < 1 || S > FOT_MAX_SAMPLES || n_dense < 1 || !tab) return (int)hipErrorInvalidValue;
+    k_loop_rep_block_sweep<<<n_run, RB_THREADS, 0, st>>>(slot_of, f, dyn, tab, best_tab, n_run, S, n_dense, tensor, pre_dev, pre_host);
     FOT_LAUNCH_CHECK();
     return 0;
 }

@@ -56,7 +56,7 @@ FOT_SR_HD inline int32_t sr_column(int32_t row, const int32_t *ped_ep, const int
 
 // The same for every row of a frame, episode by episode: col [ep_ped0[n_run]].  The set of running slots changes a few
 // times in a run, so the host forms this table when it does and the kernel reads it from HBM -- a lane then touches no
-// table in host memory.
+// table in host memory.  (The host calls fot_sweep.hpp's sweep_fill_columns: this, with first columns the caller may name.)
 inline void sr_fill_columns(int32_t n_run, const int32_t *ep_ped0, const int32_t *ep_slot, const int32_t *slot_ped0,
                             int32_t *col)
 {

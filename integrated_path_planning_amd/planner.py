@@ -442,7 +442,7 @@ class BatchPlanner:
         """``fot_loop_begin``: n episode slots (ego5 [n, 5] = x, y, yaw, v, a), every fail-safe machine NORMAL."""
         ego = np.ascontiguousarray(ego5, dtype=np.float64).reshape(-1, 5)
         self._loop_n = len(ego)
-        self._plan_sample_mode = _abi.LOOP_PLAN_DISTRIBUTION          # (fot_loop_begin* resets it)
+        self._plan_sample_mode, self._loop_sweep = _abi.LOOP_PLAN_DISTRIBUTION, False   # (fot_loop_begin* resets them)
         _abi.check(self._h, self._lib.fot_loop_begin(self._h, len(ego), C.addressof(config), _addr(ego) if len(ego) else None))
 
     def loop_begin_scenarios(self, configs: Sequence["_abi.LoopConfig"], use_footprint: Sequence[bool],
@@ -457,10 +457,32 @@ class BatchPlanner:
         cfgs = (_abi.LoopConfig * len(configs))(*configs)
         ufp = np.ascontiguousarray([bool(u) for u in use_footprint], dtype=np.int32)
         self._loop_n = len(ego)
-        self._plan_sample_mode = _abi.LOOP_PLAN_DISTRIBUTION          # (fot_loop_begin* resets it)
+        self._plan_sample_mode, self._loop_sweep = _abi.LOOP_PLAN_DISTRIBUTION, False   # (fot_loop_begin* resets them)
         _abi.check(self._h, self._lib.fot_loop_begin_scenarios(
             self._h, len(ego), len(configs), C.addressof(cfgs), _addr(ufp), _addr(scen) if len(ego) else None,
             _addr(ego) if len(ego) else None))
+
+    _loop_sweep = False
+
+    def loop_begin_sweep(self, configs: Sequence["_abi.LoopConfig"], use_footprint: Sequence[bool],
+                         slot_scenario: np.ndarray, slot_plan_mode: Optional[np.ndarray], ego5: np.ndarray) -> None:
+        """``fot_loop_begin_sweep``: ``loop_begin_scenarios`` whose lock steps may carry a distribution, planned against in
+        each slot's own mode -- ``slot_plan_mode[e]``: ``_abi.LOOP_PLAN_DISTRIBUTION`` or ``_abi.LOOP_PLAN_REPRESENTATIVE``
+        (None: every slot plans against the whole distribution)."""
+        ego = np.ascontiguousarray(ego5, dtype=np.float64).reshape(-1, 5)
+        scen = np.ascontiguousarray(slot_scenario, dtype=np.int32)
+        if scen.shape != (len(ego),) or len(configs) != len(use_footprint) or not len(configs):
+            raise ValueError("loop_begin_sweep: one scenario id per slot, one footprint flag per configuration")
+        mode = None if slot_plan_mode is None else np.ascontiguousarray(slot_plan_mode, dtype=np.int32)
+        if mode is not None and mode.shape != (len(ego),):
+            raise ValueError("loop_begin_sweep: one plan mode per slot")
+        cfgs = (_abi.LoopConfig * len(configs))(*configs)
+        ufp = np.ascontiguousarray([bool(u) for u in use_footprint], dtype=np.int32)
+        _abi.check(self._h, self._lib.fot_loop_begin_sweep(
+            self._h, len(ego), len(configs), C.addressof(cfgs), _addr(ufp), _addr(scen) if len(ego) else None,
+            _addr(mode) if mode is not None and len(ego) else None, _addr(ego) if len(ego) else None))
+        self._loop_n = len(ego)
+        self._plan_sample_mode, self._loop_sweep = _abi.LOOP_PLAN_DISTRIBUTION, True
 
     def loop_set_scenario_static(self, scenario: int, points: Optional[np.ndarray]) -> None:
         """The static obstacle points the loop's requests on ``scenario`` see (``fot_loop_set_scenario_static``)."""
@@ -563,12 +585,17 @@ class BatchPlanner:
         counter-based noise (between ``loop_set_replay`` and the first ``loop_run``)."""
         _abi.check(self._h, self._lib.fot_loop_set_sampler(self._h, int(num_samples), int(seed) & 0xFFFFFFFFFFFFFFFF, int(kind)))
 
-    def loop_set_samples(self, samples, first_step: int = 0) -> None:
+    def loop_set_samples(self, samples, first_step: int = 0, n_rec_cols: Optional[int] = None, slot_col0=None) -> None:
         """``fot_loop_set_samples``: the resident loop predicts from a recorded sample tensor ``[n_steps, S, pred_len,
         sum P, 2]`` (float32 or float64; row r belongs to lock step ``first_step + r``), between ``loop_set_replay`` and
         the first ``loop_run``.  A NumPy array is copied to HBM by the call; a contiguous ``torch`` CUDA tensor is used
         in place and never written -- the engine keeps a reference to it until the next ``loop_begin*`` /
-        ``loop_set_replay`` / ``loop_set_samples``."""
+        ``loop_set_replay`` / ``loop_set_samples``.
+        slot_col0 (``fot_loop_set_samples_shared``): the tensor is ``[n_steps, S, pred_len, n_rec_cols, 2]`` and pedestrian
+        p of slot e reads column ``slot_col0[e] + p``; several slots may name the same columns.  n_rec_cols: None -- the
+        tensor's own fourth extent."""
+        if slot_col0 is None and n_rec_cols is not None:
+            raise ValueError("loop_set_samples: n_rec_cols goes with slot_col0")
         on_device = hasattr(samples, "data_ptr")
         if on_device:
             import torch
@@ -586,6 +613,20 @@ class BatchPlanner:
             raise ValueError("loop_set_samples: samples are [n_steps, S, pred_len, sum P, 2]")
         # (the library takes pred_len and the columns from the replay: a tensor of another shape would be read out of bounds)
         want = getattr(self, "_replay_shape", None)
+        if slot_col0 is not None:
+            # (the library takes the columns from the call: they must be the tensor's, or it would be read out of bounds)
+            if n_rec_cols is not None and int(n_rec_cols) != int(samples.shape[3]):
+                raise ValueError(f"loop_set_samples: n_rec_cols = {int(n_rec_cols)}, the samples are {tuple(samples.shape)}")
+            if want is not None and int(samples.shape[2]) != want[0]:
+                raise ValueError(f"loop_set_samples: the replay has pred_len = {want[0]}, the samples are {tuple(samples.shape)}")
+            col0 = np.ascontiguousarray(slot_col0, dtype=np.int32).reshape(-1)
+            if len(col0) != int(getattr(self, "_replay_slots", len(col0))):
+                raise ValueError("loop_set_samples: slot_col0 names one first column per slot of the replay")
+            _abi.check(self._h, self._lib.fot_loop_set_samples_shared(
+                self._h, int(samples.shape[1]), int(samples.shape[0]), int(first_step), C.c_void_p(ptr) if ptr else None, code,
+                _abi.OUT_DEVICE if on_device else 0, int(samples.shape[3]), _addr(col0) if len(col0) else None))
+            self._loop_samples = samples if on_device else None
+            return
         if want is not None and tuple(int(v) for v in samples.shape[2:4]) != want:
             raise ValueError(f"loop_set_samples: the replay has pred_len = {want[0]} and {want[1]} pedestrian columns, the "
                              f"samples are {tuple(samples.shape)}")
@@ -650,7 +691,7 @@ class BatchPlanner:
         """``fot_loop_last_best_sample``: per slot the representative sample the most recent lock step chose (-1: the slot
         did not run, did not predict or has no pedestrians)."""
         # (planning on the representative sample: the slots of loop_begin, a stepwise loop's too)
-        planned = self._plan_sample_mode == _abi.LOOP_PLAN_REPRESENTATIVE
+        planned = self._plan_sample_mode == _abi.LOOP_PLAN_REPRESENTATIVE or self._loop_sweep
         n = int(self._loop_n if planned else getattr(self, "_replay_slots", getattr(self, "_loop_n", 0)))
         out = np.full(max(n, 1), -1, np.int32)
         _abi.check(self._h, self._lib.fot_loop_last_best_sample(self._h, n, _addr(out)))

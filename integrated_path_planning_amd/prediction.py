@@ -409,11 +409,15 @@ class RecordedSamples:
     the library once (``fot_loop_set_samples``; a CUDA tensor is used in place) and the whole run stays there; without, the
     loop calls the object every step with the running episodes' ``slots`` and ``steps`` and gets the step's row cut to
     their columns -- a device tensor with ``device_samples=True``, a host array otherwise.  Rows of steps at which the
-    observer is not ready are never read."""
+    observer is not ready are never read.
+
+    slot_col0: the recording's columns are not the loop's -- pedestrian p of slot e reads column ``slot_col0[e] + p``, and
+    several slots may name the same columns: the K conditions of a sweep over one crowd share ONE copy of its samples
+    (``fot_loop_set_samples_shared``).  The stepwise call cuts its rows through the same map."""
     needs_history = True
     recorded = True
 
-    def __init__(self, samples, first_step: int = 0):
+    def __init__(self, samples, first_step: int = 0, slot_col0=None):
         on_device = hasattr(samples, "data_ptr")
         if on_device:
             import torch
@@ -435,14 +439,22 @@ class RecordedSamples:
         self.samples = samples.contiguous() if on_device else np.ascontiguousarray(samples)
         self.first_step = int(first_step)
         self.n_steps, self.num_samples, self.pred_len, self.n_cols = (int(v) for v in samples.shape[:4])
-        self.ped_off = None                                            # every slot's first column, once a loop is known
+        self.ped_off = None                                            # every slot's pedestrian offsets, once a loop is known
+        self.slot_col0 = None if slot_col0 is None else np.asarray(slot_col0, dtype=np.int64).reshape(-1)
         self.device_out = on_device                                    # what a stepwise call returns (attach decides)
         self._dev, self._host, self._cols_key, self._cols = None, None, None, None
 
     def attach(self, ped_off, pred_len: int, device_samples: Optional[bool] = None) -> None:
         """Join a loop: its episodes' pedestrian offsets and the configuration's ``pred_len`` must be the recording's."""
         off = np.asarray(ped_off, dtype=np.int64)
-        if int(off[-1]) != self.n_cols:
+        if self.slot_col0 is not None:                                # every slot's own column range, not the sum
+            if len(self.slot_col0) != len(off) - 1:
+                raise ValueError(f"RecordedSamples: slot_col0 names {len(self.slot_col0)} slots, the loop has {len(off) - 1}")
+            for e, c0 in enumerate(self.slot_col0):
+                if c0 < 0 or c0 + (off[e + 1] - off[e]) > self.n_cols:
+                    raise ValueError(f"RecordedSamples: slot {e} reads columns {int(c0)} .. {int(c0 + off[e + 1] - off[e]) - 1}, "
+                                     f"the recording has {self.n_cols} pedestrian columns")
+        elif int(off[-1]) != self.n_cols:
             raise ValueError(f"RecordedSamples: the recording has {self.n_cols} pedestrian columns, the tracks {int(off[-1])}")
         if int(pred_len) != self.pred_len:
             raise ValueError(f"RecordedSamples: the recording has pred_len = {self.pred_len}, the configuration {int(pred_len)}")
@@ -455,13 +467,14 @@ class RecordedSamples:
         if self.ped_off is None:
             raise ValueError("RecordedSamples: not attached to a loop's tracks yet (attach)")
         slots = np.asarray(slots, dtype=np.int64).reshape(-1)
-        if len(slots) == len(self.ped_off) - 1 and np.array_equal(slots, np.arange(len(slots))):
+        if self.slot_col0 is None and len(slots) == len(self.ped_off) - 1 and np.array_equal(slots, np.arange(len(slots))):
             return None
         key = slots.tobytes()
         if key != self._cols_key:
             self._cols_key = key
-            self._cols = (np.concatenate([np.arange(self.ped_off[e], self.ped_off[e + 1]) for e in slots])
-                          if len(slots) else np.zeros(0, np.int64))
+            col0 = self.ped_off if self.slot_col0 is None else self.slot_col0
+            self._cols = (np.concatenate([col0[e] + np.arange(self.ped_off[e + 1] - self.ped_off[e]) for e in slots])
+                          if len(slots) else np.zeros(0, np.int64)).astype(np.int64)
         return self._cols
 
     def sample(self, obs=None, ped_off=None, slots=None, steps=None):
