@@ -733,7 +733,10 @@ int fot_sgan_sample(fot_handle *h, int32_t n_scenes, const int32_t *ped_off, con
  *   FOT_NOISE_GAUSSIAN     Box-Muller on (x0, x1) and (x2, x3): u1 = ((x >> 8) + 1) 2^-24 in (0, 1], u2 = (x' >> 8) 2^-24,
  *                          r = sqrt(-2 ln u1), outputs r cos(2 pi u2), r sin(2 pi u2), in float64, rounded once to float32
  * A number is a function of (seed, slot, step, p, s, d) alone -- no atomics, nothing of the launch shape or of the other
- * rows -- so a stepwise caller can ask for exactly the noise a resident loop used for any subset of slots at any step.  It
+ * rows -- so a stepwise caller can ask for exactly the noise a resident loop used for any subset of slots at any step.  In
+ * a loop whose slots share their crowds' samples (fot_loop_set_sampler_shared, below) the `slot` word is the CROWD's id:
+ * row_slot = crowd id, row_step and row_index reproduce any step of such a loop, and crowd c draws what slot c of a loop
+ * without crowds draws.  It
  * is NOT torch.randn's stream: seeds are not comparable with the reference's runs.  (To run a resident loop on the
  * reference's own samples, record them once and hand the tensor to fot_loop_set_samples, below.)
  * row_slot / row_step / row_index: host [rows]; flags FOT_OUT_DEVICE: out is device memory.  Synchronous, enqueued on
@@ -919,7 +922,34 @@ int fot_loop_set_samples(fot_handle *h, int32_t S, int32_t n_steps, int32_t firs
  * sweep loops.  Further FOT_ERR_INVALID (nothing changed): slot_col0 NULL; an entry < 0; slot_col0[e] + P_e > n_rec_cols;
  * n_rec_cols < 1 with pedestrians in the replay.
  * Both entries are additions: no structure, capacity or existing entry changes, FOT_ABI_VERSION and the words of
- * fot_abi_info stay as they are; a loop that never calls them launches and allocates nothing new. */
+ * fot_abi_info stay as they are; a loop that never calls them launches and allocates nothing new.
+ *
+ * fot_loop_set_sampler_shared(h, S, seed, kind, n_crowds, slot_crowd): fot_loop_set_sampler for slots that share crowds --
+ * the K conditions of a sweep over one crowd.  slot_crowd[e] in [0, n_crowds) names slot e's crowd; the ids need not be
+ * dense.  With replayed pedestrians the observer's window does not depend on the ego, so every lock step the library
+ * samples each ACTIVE crowd -- one with a running slot that has pedestrians -- ONCE: the active crowds in ascending id are
+ * the generator's scenes, a scene's window is that of the crowd's lowest running slot, and the noise counter's `slot` word
+ * is the crowd's id, its `step` word the slots' step count (all slots of a resident loop start at fot_loop_set_replay, so
+ * the running ones agree).  The crowds' raw samples [S][pred_len][crowd rows][2] are then gathered into the step's raw
+ * tensor of the running episodes, and everything behind it -- resampling, selection, planning blocks, scores, safety, the
+ * plan, each slot in its own mode and on its own scenario -- runs per slot as before.  Every condition of a cell therefore
+ * plans against the SAME samples, crowd c draws exactly what slot c of a loop without crowds draws, and
+ * fot_sgan_noise(seed, ..., row_slot = crowd id, row_step, row_index) reproduces any step.  fot_loop_set_sampler is this
+ * call with slot_crowd[e] = e: the launches and bytes of before.  When it may be called and the refusals are
+ * fot_loop_set_sampler's (fot_loop_begin loops and sweep loops); further FOT_ERR_INVALID, nothing changed: slot_crowd NULL
+ * or n_crowds < 1; an id outside [0, n_crowds); two slots of one crowd that differ in their pedestrian count, in n_frames,
+ * or in any byte of their columns of `pos` over their recorded frames (compared once, on the host, by this call; the
+ * message names both slots).  Everything the mode needs is allocated by the call; fot_loop_begin* and fot_loop_set_replay
+ * drop it with the sampler.  Not supported: one distribution block per crowd (resampling, selection and scores still run
+ * per slot, as for a shared recording), S > FOT_MAX_SAMPLES, crowds whose slots stand at different step counts.
+ *
+ * fot_debug_loop_sampler_shape (tests): the scenes and pedestrian rows the most recent lock step handed to the generator --
+ * 0 / 0 if that step did not sample; FOT_ERR_INVALID without a sampler.  It shows that the work was shared, not only the
+ * numbers.
+ * Both entries are additions as well: FOT_ABI_VERSION stays, a binding that needs them looks the symbols up. */
+int fot_loop_set_sampler_shared(fot_handle *h, int32_t S, uint64_t seed, int32_t kind, int32_t n_crowds,
+                                const int32_t *slot_crowd);
+int fot_debug_loop_sampler_shape(fot_handle *h, int32_t *n_scenes, int32_t *n_rows);
 int fot_loop_begin_sweep(fot_handle *h, int32_t n_episodes, int32_t n_cfg, const fot_loop_config *cfg,
                          const int32_t *use_footprint, const int32_t *slot_scenario, const int32_t *slot_plan_mode,
                          const double *ego5);

@@ -501,8 +501,9 @@ class BatchedClosedLoop:
         every episode on its own scenario and in its own plan mode -- ``distribution_aware_planning`` set: the whole
         distribution; unset: the representative sample (``plan_on_representative_sample=True`` is then required) -- in one
         lock step, on the one-call step or ``resident=True`` (a counter-seeded ``SganSampler`` or a ``RecordedSamples``,
-        whose ``slot_col0`` lets the conditions over one crowd share its columns).  A list of one distinct scenario and one
-        mode is today's loop.
+        whose ``slot_col0`` lets the conditions over one crowd share its columns; a ``SganSampler(..., slot_crowd=...)``
+        samples every crowd once per lock step for all its conditions, fot_loop_set_sampler_shared).  A list of one
+        distinct scenario and one mode is today's loop.
         fused: True = the lock step behind one library call (fot_loop_step), False = five separate calls with the
         prediction through the host, None = one call where the engine and the predictor allow it."""
         if fused not in (None, False, True):
@@ -567,7 +568,10 @@ class BatchedClosedLoop:
         self.ped_radius = getattr(c, "ped_radius", 0.3)
         self.footprint = footprint_from_config(c)
         self.sample_source = sample_source
-        if getattr(sample_source, "recorded", False):                 # a recording: of these tracks, this pred_len?
+        crowd = getattr(sample_source, "slot_crowd", None)            # a sampler whose slots share crowds: one id per episode
+        if crowd is not None and len(crowd) != len(ped_tracks):
+            raise ValueError(f"the sample source's slot_crowd names {len(crowd)} slots, the loop has {len(ped_tracks)} episodes")
+        if getattr(sample_source, "recorded", False):                # a recording: of these tracks, this pred_len?
             sample_source.attach(np.concatenate([[0], np.cumsum([np.shape(tr)[1] for tr in ped_tracks])]),
                                  int(c.pred_len), bool(device_samples))
         if sample_source is None and getattr(c, "prediction_method", "sgan") != "cv":
@@ -712,7 +716,8 @@ class BatchedClosedLoop:
             if self._summaries:
                 self.engine.loop_summary_enable(True, int(getattr(c, "num_samples", 1)))
             if self._resident_sampler:
-                self.engine.loop_set_sampler(sample_source.num_samples, sample_source.counter_seed, sample_source.noise_kind)
+                self.engine.loop_set_sampler(sample_source.num_samples, sample_source.counter_seed, sample_source.noise_kind,
+                                             slot_crowd=getattr(sample_source, "slot_crowd", None))
             if self._resident_recording and getattr(sample_source, "slot_col0", None) is not None:
                 self.engine.loop_set_samples(sample_source.samples, sample_source.first_step,
                                              n_rec_cols=sample_source.n_cols, slot_col0=sample_source.slot_col0)

@@ -157,7 +157,21 @@ struct LoopSampler {
     uint64_t seed = 0;
     DevBuf dWin, dNoise, dRaw;                   // [obs_len][rows][2] | [S][noise rows][nd] | [S][pred_len][rows][2], float32
     PinnedBuf hTab;                              // slot | step | index, n_cols + n_slots entries each
-    void release() { dWin.release(); dNoise.release(); dRaw.release(); hTab.release(); }
+    // fot_loop_set_sampler_shared with a map other than slot e -> crowd e: one sampling per crowd (fot_sweep.hpp).  The
+    // tables are rebuilt only when the set of running slots changes, as LoopSamples::sel.
+    bool crowds = false;
+    std::vector<int32_t> slot_crowd;             // [slots]
+    std::vector<int32_t> sel;                    // the running slots the tables stand for (empty: none yet)
+    std::vector<int32_t> scene_slot, scene_crowd;    // per scene: the representative slot, the crowd's id
+    CrowdShape shape = CrowdShape();
+    DevBuf dCrowdRaw, dCrowdTab;                 // [S][pred_len][crowd_rows][2] float32 | the tables as hCrowdTab holds them
+    PinnedBuf hCrowdTab;                         // scene_off [slots + 1] | scene_slot [slots] | row_scene [cols] | col [cols]
+    int last_scenes = 0, last_rows = 0;          // what the most recent lock step handed to the generator (fot_debug_loop_sampler_shape)
+    void release()
+    {
+        dWin.release(); dNoise.release(); dRaw.release(); hTab.release();
+        dCrowdRaw.release(); dCrowdTab.release(); hCrowdTab.release();
+    }
 };
 
 // fot_loop_set_samples: the resident loop's recorded predictor (fot_samplerec.hpp) -- the recording in HBM (the library's

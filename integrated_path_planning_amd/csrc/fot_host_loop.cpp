@@ -683,6 +683,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     for (int i = 0; i < n; ++i) rows_run += R.ped_off[sel[i] + 1] - R.ped_off[sel[i]];
     const int dist_S = R.dist_S();
     const bool sampled = dist_S > 0 && ready && rows_run > 0;    // this step predicts with the sampler or the recording
+    R.smp.last_scenes = R.smp.last_rows = 0;                     // (fot_debug_loop_sampler_shape: until the sampler branch runs)
     for (int i = 0; i < n; ++i) {
         const int e = sel[i], c0 = R.ped_off[e], P_e = R.ped_off[e + 1] - c0, nf = R.n_frames[e];
         int pre = 0;
@@ -734,9 +735,65 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         L.dist_S = M.S;
         LAUNCH_TRY(h, launch_resample(C.rp.sgan_dt, C.rp.sim_dt, stale, M.S, C.pred_len, rows, R.n_dense, 1, 1, 0, M.dRaw.p,
                                       M.dtype, fd.last, fd.pos, L.dDyn.p, FOT_F64, 0, st, fd.ped_ep, fd.ped0, fd.blk));
+    } else if (sampled && R.smp.crowds) {
+        // One sampling per ACTIVE CROWD (fot_loop_set_sampler_shared): window -> noise keyed by the crowd -> samples of the
+        // crowds' representatives -> gathered into the step's raw tensor of the running episodes -> every episode's block
+        LoopSampler &M = R.smp;
+        const fot_sgan_desc &d = h->sgan.desc;
+        const bool global_noise = d.noise_mix_type == FOT_SGAN_NOISE_GLOBAL;
+        const int nd = d.noise_dim;
+        const size_t ns = (size_t)std::max(n_slots, 1), N = std::max<size_t>((size_t)R.n_cols, 1);
+        int32_t *t_off = (int32_t *)M.hCrowdTab.p, *t_rep = t_off + (ns + 1), *t_scene = t_rep + ns, *t_col = t_scene + N;
+        const int32_t *d_off = M.dCrowdTab.as<int32_t>(), *d_rep = d_off + (ns + 1), *d_scene = d_rep + ns, *d_col = d_scene + N;
+        if (M.sel != sel) {                                      // a slot dropped out (or the first step); no copy of an earlier
+            M.scene_slot.assign((size_t)n, -1);                  // step still reads the tables (as LoopSamples::hCol)
+            M.scene_crowd.assign((size_t)n, -1);
+            M.shape = sweep_crowd_tables(n, L.ped_off.data(), sel.data(), M.slot_crowd.data(), t_off, t_scene, M.scene_slot.data(),
+                                         M.scene_crowd.data(), t_col);
+            for (int c = 0; c < M.shape.n_scenes; ++c) t_rep[c] = M.scene_slot[(size_t)c];
+            HIP_TRY(h, hipMemcpyAsync(M.dCrowdTab.p, M.hCrowdTab.p, sizeof(int32_t) * ((ns + 1) + ns + 2 * N), hipMemcpyHostToDevice, st));
+            M.sel = sel;
+        }
+        const int n_sc = M.shape.n_scenes, c_rows = M.shape.crowd_rows, noise_rows = global_noise ? n_sc : c_rows;
+        if (c_rows > rows || n_sc > n) return fail(h, FOT_ERR_INVALID, "internal: the crowds' tables exceed the frame");
+        float *crowd_raw = M.shape.identity ? M.dRaw.as<float>() : M.dCrowdRaw.as<float>();
+        SgWindow w{};
+        w.pos = rv.pos; w.slot_ped0 = rv.slot_ped0; w.slot_frames = rv.slot_frames;
+        w.ped_ep = d_scene; w.ep_ped0 = d_off; w.ep_slot = d_rep;
+        w.n_cols = R.n_cols; w.rows = c_rows; w.obs_len = d.obs_len;
+        for (int j = 0; j < d.obs_len; ++j) w.frames.f[j] = R.clock.sample_frame[(size_t)j];
+        w.out = M.dWin.as<float>();
+        LAUNCH_TRY(h, launch_sgan_window(w, st));
+        if (nd > 0) {
+            const size_t cap = (size_t)R.n_cols + (size_t)n_slots;
+            int32_t *t_slot = (int32_t *)M.hTab.p, *t_step = t_slot + cap, *t_idx = t_step + cap;
+            int r = 0;
+            for (int c = 0; c < n_sc; ++c) {                     // (the slots of a resident loop run in lock step: the
+                const int e = M.scene_slot[(size_t)c], P_c = t_off[c + 1] - t_off[c];    //  representative's step is its crowd's)
+                for (int p = 0; p < (global_noise ? 1 : P_c); ++p, ++r) { t_slot[r] = M.scene_crowd[(size_t)c]; t_step[r] = R.steps[(size_t)e]; t_idx[r] = p; }
+            }
+            SgNoise a{};
+            a.seed = M.seed; a.kind = M.kind; a.S = M.S; a.rows = noise_rows; a.nd = nd; a.n_blk = (nd + 3) / 4;
+            a.slot = t_slot; a.step = t_step; a.index = t_idx; a.out = (uint32_t *)M.dNoise.p;
+            LAUNCH_TRY(h, launch_sgan_noise(a, st));
+        }
+        { int r = sgan_enqueue(h, n_sc, c_rows, M.S, d_off, global_noise && nd > 0 ? d_scene : nullptr, M.dWin.as<float>(),
+                               M.dNoise.as<float>(), crowd_raw, st); if (r != FOT_OK) return r; }
+        if (!M.shape.identity) {                                 // (one slot per crowd, in the crowds' order: nothing to gather)
+            LoopSampleRows a{};
+            a.d.S = M.S; a.d.pred_len = C.pred_len; a.d.rows = rows; a.d.n_cols = c_rows; a.d.rec_row = 0;
+            a.rec = crowd_raw; a.col = d_col; a.out = M.dRaw.p; a.dtype = FOT_F32;
+            LAUNCH_TRY(h, launch_loop_sample_rows(a, st));
+        }
+        M.last_scenes = n_sc; M.last_rows = c_rows;
+        L.dyn_ptr = L.dDyn.p;
+        L.dist_S = M.S;
+        LAUNCH_TRY(h, launch_resample(C.rp.sgan_dt, C.rp.sim_dt, stale, M.S, C.pred_len, rows, R.n_dense, 1, 1, 0, M.dRaw.p,
+                                      FOT_F32, fd.last, fd.pos, L.dDyn.p, FOT_F64, 0, st, fd.ped_ep, fd.ped0, fd.blk));
     } else if (sampled) {
         // window -> noise -> samples -> every episode's [S][P_e][n_dense + 1][2] block, all in HBM behind k_loop_frame
         LoopSampler &M = R.smp;
+        M.last_scenes = n; M.last_rows = rows;
         const fot_sgan_desc &d = h->sgan.desc;
         const bool global_noise = d.noise_mix_type == FOT_SGAN_NOISE_GLOBAL;
         const int nd = d.noise_dim, noise_rows = global_noise ? n : rows;
@@ -1035,6 +1092,85 @@ int set_samples_impl(fot_handle *h, const std::string &who, int32_t S, int32_t n
     M.sel.clear();
     M.on = true;
     R.sc.on = false;                                             // (a new recording: its scores are enabled again, if wanted)
+    return FOT_OK;
+}
+
+// fot_loop_set_sampler / fot_loop_set_sampler_shared (who: the entry's name, for the messages); slot_crowd == nullptr: slot e
+// is crowd e
+int set_sampler_impl(fot_handle *h, const std::string &who, int32_t S, uint64_t seed, int32_t kind, bool shared, int32_t n_crowds,
+                     const int32_t *slot_crowd)
+{
+    LoopState &L = h->loop;
+    LoopReplay &R = L.replay;
+    fot_handle::Sgan &G = h->sgan;
+    if (!R.set) return fail(h, FOT_ERR_INVALID, who + ": fot_loop_set_replay comes first");
+    if (!G.loaded) return fail(h, FOT_ERR_INVALID, who + ": no model loaded (fot_sgan_load)");
+    if (R.rec.on) return fail(h, FOT_ERR_INVALID, who + ": recorded samples are set (fot_loop_set_samples): one predictor per run");
+    const int n = R.cfg.n_slots;
+    bool begun = R.clock.frame != R.cfg.warmup_frames;
+    for (int e = 0; e < n; ++e) begun = begun || R.steps[(size_t)e] != 0;
+    if (begun) return fail(h, FOT_ERR_INVALID, who + ": the run has begun (set it between fot_loop_set_replay and the first step)");
+    if (S < 1) return fail(h, FOT_ERR_INVALID, who + ": S < 1");
+    if (kind != FOT_NOISE_GAUSSIAN && kind != FOT_NOISE_UNIFORM_SYM)
+        return fail(h, FOT_ERR_INVALID, who + ": kind is FOT_NOISE_GAUSSIAN or FOT_NOISE_UNIFORM_SYM");
+    const fot_sgan_desc &d = G.desc;
+    if (d.obs_len != R.cfg.obs_len || d.pred_len != R.cfg.pred_len)
+        return fail(h, FOT_ERR_INVALID, who + ": the model's obs_len / pred_len differ from the replay's");
+    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, who + ": S > FOT_MAX_SAMPLES");
+    for (int e = 0; e < n; ++e)
+        if (R.ped_off[(size_t)e + 1] - R.ped_off[(size_t)e] > FOT_SGAN_MAX_PEDS)
+            return fail(h, FOT_ERR_UNSUPPORTED, who + ": a slot of more than FOT_SGAN_MAX_PEDS pedestrians");
+    if (L.ep.scenarios && !L.ep.sweep) return fail(h, FOT_ERR_UNSUPPORTED, who + ": a scenario loop plans against no distribution");
+    if (R.sum.on) return fail(h, FOT_ERR_UNSUPPORTED, who + ": summaries are enabled (their prediction-error ring reads the constant-velocity tensor)");
+    bool crowds = false;                                         // some slot is not the crowd of its own number
+    if (shared) {
+        if (!slot_crowd || n_crowds < 1) return fail(h, FOT_ERR_INVALID, who + ": slot_crowd is NULL / n_crowds < 1");
+        for (int e = 0; e < n; ++e) {
+            if (slot_crowd[e] < 0 || slot_crowd[e] >= n_crowds)
+                return fail(h, FOT_ERR_INVALID, who + ": slot_crowd[" + std::to_string(e) + "] lies outside 0 .. n_crowds - 1");
+            crowds = crowds || slot_crowd[e] != e;
+        }
+        // the slots of a crowd replay the same pedestrians: one comparison of their column ranges over the recorded frames
+        int32_t a = 0, b = 0;
+        const int differ = crowds ? sweep_crowds_consistent(n, R.ped_off.data(), R.n_frames.data(), slot_crowd, R.pos.data(), R.n_cols, &a, &b) : 0;
+        if (differ != 0)
+            return fail(h, FOT_ERR_INVALID, who + ": slots " + std::to_string(a) + " and " + std::to_string(b) + " of crowd " +
+                                            std::to_string(slot_crowd[b]) + " differ in " +
+                                            (differ == 1 ? "their pedestrian counts" : differ == 2 ? "n_frames" : "the recorded positions (pos)"));
+    }
+    // --- accepted: everything a step needs is allocated here, so that no block grows (and moves) inside a run
+    LoopSampler &M = R.smp;
+    const size_t N = std::max<size_t>((size_t)R.n_cols, 1), rows = (size_t)S * N, ns = (size_t)std::max(n, 1);
+    const int bp = sg_pooled(d) ? G.dev.pool.b_pad : 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    M.on = false;
+    HIP_TRY(h, M.dWin.ensure(sizeof(float) * 2 * (size_t)d.obs_len * N));
+    HIP_TRY(h, M.dNoise.ensure(sizeof(float) * (size_t)S * std::max(N, ns) * (size_t)std::max(d.noise_dim, 1)));
+    HIP_TRY(h, M.dRaw.ensure(sizeof(float) * 2 * (size_t)S * (size_t)d.pred_len * N));
+    HIP_TRY(h, M.hTab.ensure(sizeof(int32_t) * 3 * (N + ns)));
+    HIP_TRY(h, L.dDyn.ensure(sizeof(double) * 2 * rows * (size_t)(R.n_dense + 1)));
+    if (L.ep.sweep) { int r = sweep_ensure(h, S); if (r != FOT_OK) return r; }
+    HIP_TRY(h, G.dHenc.ensure(sizeof(float) * N * (size_t)d.encoder_h_dim));
+    if (bp > 0) HIP_TRY(h, G.dPool.ensure(sizeof(float) * (sg_pool_steps(d) ? rows : N) * (size_t)bp));
+    if (sg_has_context(d)) HIP_TRY(h, G.dCtx.ensure(sizeof(float) * N * (size_t)std::max(d.decoder_h_dim - d.noise_dim, 1)));
+    if (sg_pool_steps(d)) {
+        HIP_TRY(h, G.dH.ensure(sizeof(float) * rows * (size_t)d.decoder_h_dim));
+        HIP_TRY(h, G.dC.ensure(sizeof(float) * rows * (size_t)d.decoder_h_dim));
+        HIP_TRY(h, G.dXY.ensure(sizeof(float) * rows * 6));
+    }
+    if (crowds) {                                                // (slot e -> crowd e: today's step, nothing new)
+        HIP_TRY(h, M.dCrowdRaw.ensure(sizeof(float) * 2 * (size_t)S * (size_t)d.pred_len * N));
+        HIP_TRY(h, M.dCrowdTab.ensure(sizeof(int32_t) * ((ns + 1) + ns + 2 * N)));
+        HIP_TRY(h, M.hCrowdTab.ensure(sizeof(int32_t) * ((ns + 1) + ns + 2 * N)));
+        M.slot_crowd.assign(slot_crowd, slot_crowd + n);
+    }
+    M.crowds = crowds;
+    M.sel.clear();
+    M.last_scenes = M.last_rows = 0;
+    M.S = S; M.seed = seed; M.kind = kind;
+    M.on = true;
+    R.sc.on = false;                                             // (a new sampler: its scores are enabled again, if wanted)
     return FOT_OK;
 }
 
@@ -1550,52 +1686,22 @@ int fot_debug_loop_block(fot_handle *h, int32_t episode, int32_t cap_points, dou
 int fot_loop_set_sampler(fot_handle *h, int32_t S, uint64_t seed, int32_t kind)
 {
     if (!h) return FOT_ERR_INVALID;
-    LoopState &L = h->loop;
-    LoopReplay &R = L.replay;
-    fot_handle::Sgan &G = h->sgan;
-    if (!R.set) return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: fot_loop_set_replay comes first");
-    if (!G.loaded) return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: no model loaded (fot_sgan_load)");
-    if (R.rec.on) return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: recorded samples are set (fot_loop_set_samples): one predictor per run");
-    const int n = R.cfg.n_slots;
-    bool begun = R.clock.frame != R.cfg.warmup_frames;
-    for (int e = 0; e < n; ++e) begun = begun || R.steps[(size_t)e] != 0;
-    if (begun) return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: the run has begun (set it between fot_loop_set_replay and the first step)");
-    if (S < 1) return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: S < 1");
-    if (kind != FOT_NOISE_GAUSSIAN && kind != FOT_NOISE_UNIFORM_SYM)
-        return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: kind is FOT_NOISE_GAUSSIAN or FOT_NOISE_UNIFORM_SYM");
-    const fot_sgan_desc &d = G.desc;
-    if (d.obs_len != R.cfg.obs_len || d.pred_len != R.cfg.pred_len)
-        return fail(h, FOT_ERR_INVALID, "fot_loop_set_sampler: the model's obs_len / pred_len differ from the replay's");
-    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_sampler: S > FOT_MAX_SAMPLES");
-    for (int e = 0; e < n; ++e)
-        if (R.ped_off[(size_t)e + 1] - R.ped_off[(size_t)e] > FOT_SGAN_MAX_PEDS)
-            return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_sampler: a slot of more than FOT_SGAN_MAX_PEDS pedestrians");
-    if (L.ep.scenarios && !L.ep.sweep) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_sampler: a scenario loop plans against no distribution");
-    if (R.sum.on) return fail(h, FOT_ERR_UNSUPPORTED, "fot_loop_set_sampler: summaries are enabled (their prediction-error ring reads the constant-velocity tensor)");
-    // --- accepted: everything a step needs is allocated here, so that no block grows (and moves) inside a run
-    LoopSampler &M = R.smp;
-    const size_t N = std::max<size_t>((size_t)R.n_cols, 1), rows = (size_t)S * N, ns = (size_t)std::max(n, 1);
-    const int bp = sg_pooled(d) ? G.dev.pool.b_pad : 0;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    M.on = false;
-    HIP_TRY(h, M.dWin.ensure(sizeof(float) * 2 * (size_t)d.obs_len * N));
-    HIP_TRY(h, M.dNoise.ensure(sizeof(float) * (size_t)S * std::max(N, ns) * (size_t)std::max(d.noise_dim, 1)));
-    HIP_TRY(h, M.dRaw.ensure(sizeof(float) * 2 * (size_t)S * (size_t)d.pred_len * N));
-    HIP_TRY(h, M.hTab.ensure(sizeof(int32_t) * 3 * (N + ns)));
-    HIP_TRY(h, L.dDyn.ensure(sizeof(double) * 2 * rows * (size_t)(R.n_dense + 1)));
-    if (L.ep.sweep) { int r = sweep_ensure(h, S); if (r != FOT_OK) return r; }
-    HIP_TRY(h, G.dHenc.ensure(sizeof(float) * N * (size_t)d.encoder_h_dim));
-    if (bp > 0) HIP_TRY(h, G.dPool.ensure(sizeof(float) * (sg_pool_steps(d) ? rows : N) * (size_t)bp));
-    if (sg_has_context(d)) HIP_TRY(h, G.dCtx.ensure(sizeof(float) * N * (size_t)std::max(d.decoder_h_dim - d.noise_dim, 1)));
-    if (sg_pool_steps(d)) {
-        HIP_TRY(h, G.dH.ensure(sizeof(float) * rows * (size_t)d.decoder_h_dim));
-        HIP_TRY(h, G.dC.ensure(sizeof(float) * rows * (size_t)d.decoder_h_dim));
-        HIP_TRY(h, G.dXY.ensure(sizeof(float) * rows * 6));
-    }
-    M.S = S; M.seed = seed; M.kind = kind;
-    M.on = true;
-    R.sc.on = false;                                             // (a new sampler: its scores are enabled again, if wanted)
+    return set_sampler_impl(h, "fot_loop_set_sampler", S, seed, kind, false, 0, nullptr);
+}
+
+int fot_loop_set_sampler_shared(fot_handle *h, int32_t S, uint64_t seed, int32_t kind, int32_t n_crowds, const int32_t *slot_crowd)
+{
+    if (!h) return FOT_ERR_INVALID;
+    return set_sampler_impl(h, "fot_loop_set_sampler_shared", S, seed, kind, true, n_crowds, slot_crowd);
+}
+
+int fot_debug_loop_sampler_shape(fot_handle *h, int32_t *n_scenes, int32_t *n_rows)
+{
+    if (!h) return FOT_ERR_INVALID;
+    const LoopReplay &R = h->loop.replay;
+    if (!R.set || !R.smp.on) return fail(h, FOT_ERR_INVALID, "fot_debug_loop_sampler_shape: no sampler is set (fot_loop_set_sampler)");
+    if (n_scenes) *n_scenes = R.smp.last_scenes;
+    if (n_rows) *n_rows = R.smp.last_rows;
     return FOT_OK;
 }
 

@@ -3,12 +3,16 @@
 // block [S][P_e][T][2] as in any distribution loop; behind them, compacted in frame order, follow the single-sample
 // planning blocks [P_e][T][2] (fot_repsample.hpp) of the episodes in FOT_LOOP_PLAN_REPRESENTATIVE mode.  A request then
 // addresses its episode's distribution block with S samples or its planning block with one, on the same base pointer.
-// Also the row -> column table of a recording whose columns the slots name themselves (fot_loop_set_samples_shared).
+// Also the row -> column table of a recording whose columns the slots name themselves (fot_loop_set_samples_shared), and
+// the tables of a sampler step whose slots share their crowds' samples (fot_loop_set_sampler_shared).
 // Plain C++ shared by the kernels (k_loop_best_sample_sweep, k_loop_rep_block_sweep), the host (fot_host_loop.cpp) and
 // tests/emu/fot_sweep_emu.cpp.  Every offset into the tensor counts points of two coordinates in 64 bits.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
+#include <cstring>
+#include <vector>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define FOT_SW_HD __host__ __device__
@@ -72,6 +76,80 @@ inline bool sweep_columns_fit(int32_t n_slots, const int32_t *slot_ped0, const i
         if (slot_col0[e] < 0 || (int64_t)slot_col0[e] + P > n_rec_cols) return false;
     }
     return true;
+}
+
+// ---- crowds: the slots of a sampler loop that share one sampling (fot_loop_set_sampler_shared) ---------------------------------
+// slot_crowd [n_slots] names every slot's crowd.  A crowd is ACTIVE in a frame when one of its slots runs and has
+// pedestrians; the active crowds, in ascending id, are the sampler's scenes, and a scene's pedestrians are those of the
+// crowd's REPRESENTATIVE, its lowest running slot.
+
+struct CrowdShape {
+    int32_t n_scenes = 0, crowd_rows = 0;    // what the generator is handed: active crowds, the pedestrians of their representatives
+    bool identity = true;                    // col[r] == r for every row and crowd_rows == the frame's rows: nothing to gather
+};
+
+// The tables of a frame of n_run running episodes (ep_ped0 [n_run + 1], ep_slot [n_run] as in sweep_fill_columns):
+//   scene_off   [n_scenes + 1]  first row of each scene in the crowds' tensor
+//   row_scene   [crowd_rows]    scene of each of its rows
+//   scene_slot  [n_scenes]      the representative slot (the window is gathered from its columns of the recording)
+//   scene_crowd [n_scenes]      the crowd's id (the noise counter's `slot` word)
+//   col         [rows]          for every row of the frame its column in the crowds' tensor [S][pred_len][crowd_rows][2]
+// The arrays hold n_run + 1 / rows / n_run / n_run / rows entries.  The slots of a crowd have equal pedestrian counts
+// (sweep_crowds_consistent).  Runs when the set of running slots changes, on the host only.
+inline CrowdShape sweep_crowd_tables(int32_t n_run, const int32_t *ep_ped0, const int32_t *ep_slot, const int32_t *slot_crowd,
+                                     int32_t *scene_off, int32_t *row_scene, int32_t *scene_slot, int32_t *scene_crowd,
+                                     int32_t *col)
+{
+    std::vector<int32_t> order, ep_scene((size_t)(n_run > 0 ? n_run : 0), -1);
+    for (int32_t i = 0; i < n_run; ++i)
+        if (ep_ped0[i + 1] > ep_ped0[i]) order.push_back(i);
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+        const int32_t ca = slot_crowd[ep_slot[a]], cb = slot_crowd[ep_slot[b]];
+        return ca != cb ? ca < cb : ep_slot[a] < ep_slot[b];
+    });
+    CrowdShape sh;
+    scene_off[0] = 0;
+    for (size_t k = 0; k < order.size(); ++k) {
+        const int32_t i = order[k], c = slot_crowd[ep_slot[i]];
+        if (k == 0 || c != slot_crowd[ep_slot[order[k - 1]]]) {   // a new crowd: this episode is its lowest running slot
+            const int32_t P = ep_ped0[i + 1] - ep_ped0[i], sc = sh.n_scenes++;
+            scene_slot[sc] = ep_slot[i]; scene_crowd[sc] = c;
+            for (int32_t p = 0; p < P; ++p) row_scene[sh.crowd_rows + p] = sc;
+            sh.crowd_rows += P;
+            scene_off[sc + 1] = sh.crowd_rows;
+        }
+        ep_scene[(size_t)i] = sh.n_scenes - 1;
+    }
+    for (int32_t i = 0; i < n_run; ++i)
+        for (int32_t row = ep_ped0[i]; row < ep_ped0[i + 1]; ++row) {
+            col[row] = scene_off[ep_scene[(size_t)i]] + (row - ep_ped0[i]);
+            sh.identity = sh.identity && col[row] == row;
+        }
+    sh.identity = sh.identity && sh.crowd_rows == ep_ped0[n_run > 0 ? n_run : 0];
+    return sh;
+}
+
+// Do the slots of every crowd replay the same pedestrians?  slot_ped0 [n_slots + 1], slot_frames [n_slots], pos the
+// recording [n_frames_max][n_cols][2].  Every slot is held against the lowest slot of its crowd: 0 -- they agree; 1 -- the
+// pedestrian counts differ; 2 -- the recorded frames; 3 -- some byte of the positions of a recorded frame.  *slot_a <
+// *slot_b then name the two slots.
+inline int sweep_crowds_consistent(int32_t n_slots, const int32_t *slot_ped0, const int32_t *slot_frames, const int32_t *slot_crowd,
+                                   const double *pos, int32_t n_cols, int32_t *slot_a, int32_t *slot_b)
+{
+    for (int32_t e = 1; e < n_slots; ++e) {
+        int32_t a = 0;
+        while (a < e && slot_crowd[a] != slot_crowd[e]) ++a;
+        if (a == e) continue;                                    // the lowest slot of its crowd
+        *slot_a = a; *slot_b = e;
+        const int32_t P = slot_ped0[e + 1] - slot_ped0[e];
+        if (P != slot_ped0[a + 1] - slot_ped0[a]) return 1;
+        if (slot_frames[a] != slot_frames[e]) return 2;
+        for (int32_t f = 0; P > 0 && f < slot_frames[e]; ++f) {
+            const double *row = pos + (int64_t)f * n_cols * 2;
+            if (std::memcmp(row + 2 * (int64_t)slot_ped0[a], row + 2 * (int64_t)slot_ped0[e], sizeof(double) * 2 * (size_t)P) != 0) return 3;
+        }
+    }
+    return 0;
 }
 
 }  // namespace fot

@@ -580,10 +580,28 @@ class BatchPlanner:
 
     LOOP_SUMMARY_DT = np.dtype(_abi.LoopSummary)
 
-    def loop_set_sampler(self, num_samples: int, seed: int, kind: int = _abi.NOISE_GAUSSIAN) -> None:
+    def loop_set_sampler(self, num_samples: int, seed: int, kind: int = _abi.NOISE_GAUSSIAN, slot_crowd=None) -> None:
         """``fot_loop_set_sampler``: the resident loop predicts with the model of ``fot_sgan_load`` and the library's own
-        counter-based noise (between ``loop_set_replay`` and the first ``loop_run``)."""
-        _abi.check(self._h, self._lib.fot_loop_set_sampler(self._h, int(num_samples), int(seed) & 0xFFFFFFFFFFFFFFFF, int(kind)))
+        counter-based noise (between ``loop_set_replay`` and the first ``loop_run``).
+        slot_crowd (``fot_loop_set_sampler_shared``): one crowd id >= 0 per slot of the replay; the slots of a crowd replay
+        the same pedestrians, the library samples every crowd once per lock step with noise keyed by the crowd's id and
+        all its slots plan against those samples."""
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if slot_crowd is None:
+            _abi.check(self._h, self._lib.fot_loop_set_sampler(self._h, int(num_samples), seed, int(kind)))
+            return
+        crowd = np.ascontiguousarray(slot_crowd, dtype=np.int32).reshape(-1)
+        if len(crowd) != int(getattr(self, "_replay_slots", len(crowd))):
+            raise ValueError("loop_set_sampler: slot_crowd names one crowd per slot of the replay")
+        _abi.check(self._h, self._lib.fot_loop_set_sampler_shared(
+            self._h, int(num_samples), seed, int(kind), int(crowd.max()) + 1 if len(crowd) else 1, _addr(crowd) if len(crowd) else None))
+
+    def debug_loop_sampler_shape(self):
+        """``fot_debug_loop_sampler_shape`` (tests): (scenes, pedestrian rows) the most recent lock step of a resident sampler
+        loop handed to the generator; (0, 0) if that step did not sample."""
+        n_scenes, n_rows = C.c_int32(-1), C.c_int32(-1)
+        _abi.check(self._h, self._lib.fot_debug_loop_sampler_shape(self._h, C.addressof(n_scenes), C.addressof(n_rows)))
+        return n_scenes.value, n_rows.value
 
     def loop_set_samples(self, samples, first_step: int = 0, n_rec_cols: Optional[int] = None, slot_col0=None) -> None:
         """``fot_loop_set_samples``: the resident loop predicts from a recorded sample tensor ``[n_steps, S, pred_len,

@@ -264,6 +264,38 @@ class SganWeights:
         return cls.from_state_dict(args, ckpt["g_state"] if "g_state" in ckpt else ckpt["g_best_state"])
 
 
+def crowd_scenes(slots, counts, steps, slot_crowd):
+    """The sampler's call for running episodes that share crowds (``SganSampler(slot_crowd=...)``,
+    ``fot_loop_set_sampler_shared``; csrc/fot_sweep.hpp's ``sweep_crowd_tables`` restated).  slots / counts / steps: slot,
+    pedestrian count and step count of every running episode, in frame order; slot_crowd: the crowd of every slot of the
+    loop.  A crowd is active when one of its episodes has pedestrians; its representative is its lowest slot among them.
+
+    Returns ``(crowds, rep, noise_slots, cols)``: the active crowds' ids in ascending order; for each the index of its
+    representative in ``slots``; the ``slot`` word of its noise -- the crowd's id; and for every pedestrian row of the
+    frame its column among the representatives' concatenated rows.  ``ValueError`` where two episodes of a crowd disagree
+    in pedestrian count or step count."""
+    slots, counts, steps = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (slots, counts, steps))
+    slot_crowd = np.asarray(slot_crowd, dtype=np.int64).reshape(-1)
+    if not len(slots) == len(counts) == len(steps):
+        raise ValueError("crowd_scenes: one pedestrian count and one step count per slot")
+    if len(slots) and (slots.min() < 0 or slots.max() >= len(slot_crowd)):
+        raise ValueError(f"crowd_scenes: slot_crowd names {len(slot_crowd)} slots, the frame has slot {int(slots.max())}")
+    crowd_of = slot_crowd[slots]
+    rep_of = {}                                                       # crowd -> index of its lowest slot with pedestrians
+    for i in np.argsort(slots, kind="stable"):
+        if counts[i] > 0:
+            j = rep_of.setdefault(int(crowd_of[i]), int(i))
+            if counts[i] != counts[j] or steps[i] != steps[j]:
+                raise ValueError(f"crowd_scenes: slots {int(slots[j])} and {int(slots[i])} of crowd {int(crowd_of[i])} differ in "
+                                 f"their pedestrian counts ({int(counts[j])}, {int(counts[i])}) or step counts "
+                                 f"({int(steps[j])}, {int(steps[i])})")
+    crowds = np.array(sorted(rep_of), dtype=np.int64)
+    rep = np.array([rep_of[int(c)] for c in crowds], dtype=np.int64)
+    first = dict(zip(crowds.tolist(), np.concatenate([[0], np.cumsum(counts[rep])]).tolist()))
+    cols = [first[int(c)] + np.arange(P) for c, P in zip(crowd_of, counts) if P > 0]
+    return crowds, rep, crowds.copy(), (np.concatenate(cols) if cols else np.zeros(0, np.int64)).astype(np.int64)
+
+
 class SganSampler:
     """The multi-sample predictor in front of the planner, in the library: ``sample(obs, ped_off)`` gives the raw samples
     [S, pred_len, sum P, 2] of every scene as a float32 ``torch`` device tensor -- what ``fot_loop_frame.dist_raw`` and
@@ -278,17 +310,27 @@ class SganSampler:
     not depend on which other episodes still run, and ``BatchedClosedLoop(..., resident=True)`` draws the same inside
     the library.  ``sample`` then needs the rows' ``slots`` and ``steps`` (a loop passes them).  The numbers differ from
     ``torch.randn``'s: seeds are not comparable with the reference's runs.
+    slot_crowd (with ``counter_seed``): the loop's slots share crowds -- the K conditions of a sweep over one crowd.  One
+    crowd id >= 0 per slot; the slots of a crowd replay the same pedestrians.  Every crowd with a running slot is sampled
+    ONCE per lock step, its noise keyed by the crowd's id in place of the slot, and all its slots are handed those samples
+    (``fot_loop_set_sampler_shared`` in a resident loop; ``sample`` forms the same bytes for a stepwise one).  Crowd c
+    draws what slot c of a loop without ``slot_crowd`` draws.
     engine None: the sampler joins the engine of the loop it is handed to (``bind``)."""
     needs_history = True
 
     def __init__(self, engine: Optional[BatchPlanner], weights: SganWeights, num_samples: int, seed: Optional[int] = None,
-                 noise_type: Optional[str] = None, counter_seed: Optional[int] = None):
+                 noise_type: Optional[str] = None, counter_seed: Optional[int] = None, slot_crowd=None):
         if noise_type is not None and noise_type not in _NOISE_TYPES:
             raise ValueError(f'Unrecognized noise type "{noise_type}"')
         if not 1 <= int(num_samples) <= _abi.MAX_SAMPLES:
             raise ValueError(f"SganSampler: 1 <= num_samples <= {_abi.MAX_SAMPLES}")
         self.engine, self.weights, self.num_samples, self._noise_type = None, weights, int(num_samples), noise_type
         self.counter_seed = None if counter_seed is None else int(counter_seed) & 0xFFFFFFFFFFFFFFFF
+        if slot_crowd is not None and counter_seed is None:
+            raise ValueError("SganSampler: slot_crowd keys the counter mode's noise by crowd: it needs counter_seed")
+        self.slot_crowd = None if slot_crowd is None else np.asarray(slot_crowd, dtype=np.int64).reshape(-1)
+        if self.slot_crowd is not None and len(self.slot_crowd) and self.slot_crowd.min() < 0:
+            raise ValueError("SganSampler: slot_crowd holds one crowd id >= 0 per slot")
         self._seed = seed
         self._lib = _abi.lib()
         self.device = self.generator = None
@@ -374,6 +416,27 @@ class SganSampler:
             obs_t = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32)).to(self.device)
         if tuple(obs_t.shape) != (d.obs_len, n, 2):
             raise ValueError(f"SganSampler: obs is [obs_len = {d.obs_len}, sum P = {n}, 2], got {tuple(obs_t.shape)}")
+        if noise is None and self.slot_crowd is not None:
+            # one sampling per active crowd: its representative's window under the crowd's noise, then every asked slot's
+            # columns out of the crowds' tensor -- the bytes a resident loop forms (fot_loop_set_sampler_shared)
+            if slots is None or steps is None:
+                raise ValueError("SganSampler: the counter mode needs every scene's slot and step count (slots, steps)")
+            counts = np.diff(off).astype(np.int64)
+            steps = np.asarray(steps, dtype=np.int64).reshape(-1)
+            crowds, rep, noise_slots, cols = crowd_scenes(slots, counts, steps, self.slot_crowd)
+            crowd_of = self.slot_crowd[np.asarray(slots, dtype=np.int64).reshape(-1)]
+            rep_of = dict(zip(crowds.tolist(), rep.tolist()))
+            for i, c in enumerate(crowd_of.tolist()):
+                j = rep_of.get(c, i)
+                if counts[i] > 0 and j != i and not torch.equal(obs_t[:, off[i]:off[i + 1]], obs_t[:, off[j]:off[j + 1]]):
+                    raise ValueError(f"SganSampler: the slots of crowd {c} do not observe the same window (scenes {j} and {i})")
+            if len(rep) == 0:                                         # (no running slot has pedestrians)
+                return torch.empty((self.num_samples, d.pred_len, 0, 2), device=self.device, dtype=torch.float32)
+            rows = np.concatenate([np.arange(off[j], off[j + 1]) for j in rep] + [np.zeros(0, np.int64)]).astype(np.int64)
+            rep_obs = obs_t.index_select(1, torch.as_tensor(rows, device=self.device)).contiguous()
+            rep_off = np.concatenate([[0], np.cumsum(counts[rep])]).astype(np.int32)
+            raw = self._sample_scenes(rep_obs, rep_off, self.counter_noise(noise_slots, steps[rep], counts[rep]))
+            return raw.index_select(2, torch.as_tensor(cols, device=self.device)).contiguous()
         if noise is None and self.counter_seed is not None:
             if slots is None or steps is None:
                 raise ValueError("SganSampler: the counter mode needs every scene's slot and step count (slots, steps)")
@@ -385,6 +448,13 @@ class SganSampler:
             rows = n_scenes if d.noise_mix_type == _abi.SGAN_NOISE_GLOBAL else n
             if tuple(noise_t.shape) != (self.num_samples, rows, d.noise_dim):
                 raise ValueError(f"SganSampler: noise is [S, rows, noise_dim] = {(self.num_samples, rows, d.noise_dim)}")
+        return self._sample_scenes(obs_t, off, noise_t)
+
+    def _sample_scenes(self, obs_t, off, noise_t):
+        """``fot_sgan_sample`` of the scenes ``off`` on device tensors."""
+        import torch
+        d = self.weights.desc
+        n_scenes, n = len(off) - 1, int(off[-1])
         out = torch.empty((self.num_samples, d.pred_len, n, 2), device=self.device, dtype=torch.float32)
         torch.cuda.current_stream(self.device).synchronize()        # (the library reads the tensors on its own stream)
         _abi.check(self.engine._h, self._lib.fot_sgan_sample(
