@@ -953,6 +953,48 @@ int fot_debug_loop_sampler_shape(fot_handle *h, int32_t *n_scenes, int32_t *n_ro
 int fot_loop_begin_sweep(fot_handle *h, int32_t n_episodes, int32_t n_cfg, const fot_loop_config *cfg,
                          const int32_t *use_footprint, const int32_t *slot_scenario, const int32_t *slot_plan_mode,
                          const double *ego5);
+
+/* ---- several Social-GAN models per handle, and a model per slot of a sampler loop --------------------------------------------
+ * A handle holds up to fot_sgan_max_models() (8) loaded models, each with its own device image and work arrays: what model m
+ * computes never depends on what else is loaded or was sampled in between.  fot_sgan_load_model / fot_sgan_unload_model /
+ * fot_sgan_sample_model take the model's id in front of the arguments of fot_sgan_load / fot_sgan_unload / fot_sgan_sample,
+ * which are these entries with model = 0: their behaviour, launches and bytes are as before.  FOT_ERR_INVALID, nothing
+ * changed: a model outside 0 .. fot_sgan_max_models() - 1; sampling or unloading a model that is not loaded; a load or
+ * unload of ANY model while a loop sampler is set.  fot_destroy releases all models.
+ *
+ * fot_loop_set_sampler_models(h, S, seed, n_models, model_kind, n_crowds, slot_crowd, slot_model): fot_loop_set_sampler_shared
+ * for slots that also name their model -- the 'sgan' and 'lstm' conditions of a campaign cell in ONE loop.  slot_model[e] in
+ * [0, n_models) is the id of a loaded model, model_kind[m] (FOT_NOISE_GAUSSIAN | FOT_NOISE_UNIFORM_SYM) the noise kind of
+ * model m, the checkpoint's own noise_type; slot_crowd as in the shared call (its consistency check runs per crowd whatever
+ * the models).  A sampling UNIT is a (crowd, model) pair, active when one of its running slots has pedestrians.  Every lock
+ * step, for each model in ascending id that has an active unit: its active units in ascending crowd id
+ * are the generator's scenes, a scene's window is that of the unit's lowest running slot, the noise counter's `slot` word is
+ * the crowd's id, its `step` word the slots' step count, its kind model_kind[m], the dimensions and the mix type model m's.
+ * A model without an active unit launches nothing that step.  The first active model samples on the loop's stream, every
+ * later one on a side stream of its own, forked from and joined to the loop's stream by events -- their work arrays are
+ * separate and nothing is synchronised with the host (FOT_LOOP_MODEL_STREAMS=0 in the environment of the set call keeps all
+ * of them on the loop's stream: same bytes, for measurements).  The models' raw tensors [S][pred_len][rows_m][2] are gathered
+ * into the step's raw tensor of the running episodes by one launch (k_loop_model_rows) and everything behind it runs per slot
+ * as before: every slot's numbers are the bits of the loop that has only that slot's model loaded, and
+ * fot_sgan_noise(seed, model_kind[m], ..., row_slot = crowd id, ...) fed through fot_sgan_sample_model(m) reproduces any step.
+ * With n_models = 1 the call is fot_loop_set_sampler_shared with kind = model_kind[0]: the launches and bytes of before.
+ * When it may be called and the refusals are fot_loop_set_sampler_shared's; further FOT_ERR_INVALID, nothing changed:
+ * slot_model or model_kind NULL; n_models outside 1 .. fot_sgan_max_models(); a slot naming an id outside [0, n_models) or a
+ * model that is not loaded; an unknown kind; a named model whose obs_len / pred_len differ from the replay's.  Everything is
+ * allocated by the call, sized for every model's worst case; fot_loop_begin* and fot_loop_set_replay drop it.
+ *
+ * fot_debug_loop_sampler_shapes (tests): for model ids 0 .. cap - 1 the scenes and pedestrian rows the most recent lock step
+ * handed to that model -- 0 / 0 for a model that launched nothing; FOT_ERR_INVALID without a sampler.
+ * All entries are additions: no structure, capacity word of fot_abi_info or FOT_ABI_VERSION changes; a binding that needs them
+ * looks the symbols up. */
+int32_t fot_sgan_max_models(void);
+int fot_sgan_load_model(fot_handle *h, int32_t model, const fot_sgan_desc *desc, int64_t n, const float *weights);
+int fot_sgan_unload_model(fot_handle *h, int32_t model);
+int fot_sgan_sample_model(fot_handle *h, int32_t model, int32_t n_scenes, const int32_t *ped_off, const void *obs, int32_t S,
+                          const void *noise, int32_t flags, void *out, void *stream);
+int fot_loop_set_sampler_models(fot_handle *h, int32_t S, uint64_t seed, int32_t n_models, const int32_t *model_kind,
+                                int32_t n_crowds, const int32_t *slot_crowd, const int32_t *slot_model);
+int fot_debug_loop_sampler_shapes(fot_handle *h, int32_t cap, int32_t *n_scenes, int32_t *n_rows);
 int fot_loop_set_samples_shared(fot_handle *h, int32_t S, int32_t n_steps, int32_t first_step, const void *samples,
                                 int32_t dtype, int32_t flags, int32_t n_rec_cols, const int32_t *slot_col0);
 

@@ -181,7 +181,9 @@ SYMBOLS = ["fot_version", "fot_abi_info", "fot_create", "fot_destroy", "fot_live
            "fot_sgan_weight_count", "fot_sgan_load", "fot_sgan_unload", "fot_sgan_sample", "fot_sgan_noise", "fot_loop_set_sampler",
            "fot_loop_scores_enable", "fot_loop_score_summaries", "fot_loop_last_best_sample",
            "fot_loop_plan_sample", "fot_loop_run_best_samples", "fot_debug_loop_block", "fot_loop_set_samples",
-           "fot_loop_begin_sweep", "fot_loop_set_samples_shared", "fot_loop_set_sampler_shared", "fot_debug_loop_sampler_shape"]
+           "fot_loop_begin_sweep", "fot_loop_set_samples_shared", "fot_loop_set_sampler_shared", "fot_debug_loop_sampler_shape",
+           "fot_sgan_max_models", "fot_sgan_load_model", "fot_sgan_unload_model", "fot_sgan_sample_model",
+           "fot_loop_set_sampler_models", "fot_debug_loop_sampler_shapes"]
 LOOP_PLAN_DISTRIBUTION, LOOP_PLAN_REPRESENTATIVE = 0, 1      # FOT_LOOP_PLAN_* (fot_loop_plan_sample)
 PROFILE_KERNELS = 3                      # FOT_PROFILE_KERNELS (include/fot.h)
 ABI_VERSION = 8                          # FOT_ABI_VERSION
@@ -442,7 +444,13 @@ def lib():
                        ("fot_loop_begin_sweep", [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]),
                        ("fot_loop_set_samples_shared", [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp]),
                        ("fot_loop_set_sampler_shared", [vp, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, vp]),
-                       ("fot_debug_loop_sampler_shape", [vp, vp, vp])):
+                       ("fot_debug_loop_sampler_shape", [vp, vp, vp]),
+                       ("fot_sgan_max_models", []),
+                       ("fot_sgan_load_model", [vp, C.c_int32, C.POINTER(SganDesc), C.c_int64, vp]),
+                       ("fot_sgan_unload_model", [vp, C.c_int32]),
+                       ("fot_sgan_sample_model", [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp]),
+                       ("fot_loop_set_sampler_models", [vp, C.c_int32, C.c_uint64, C.c_int32, vp, C.c_int32, vp, vp]),
+                       ("fot_debug_loop_sampler_shapes", [vp, C.c_int32, vp, vp])):
         if hasattr(L, name):
             getattr(L, name).argtypes = args
     L.fot_gather_paths.argtypes = [vp, C.c_int32, vp, C.c_int32, vp]

@@ -502,7 +502,8 @@ class BatchedClosedLoop:
         distribution; unset: the representative sample (``plan_on_representative_sample=True`` is then required) -- in one
         lock step, on the one-call step or ``resident=True`` (a counter-seeded ``SganSampler`` or a ``RecordedSamples``,
         whose ``slot_col0`` lets the conditions over one crowd share its columns; a ``SganSampler(..., slot_crowd=...)``
-        samples every crowd once per lock step for all its conditions, fot_loop_set_sampler_shared).  A list of one
+        samples every crowd once per lock step for all its conditions, fot_loop_set_sampler_shared; built on several
+        ``SganWeights`` with ``slot_model=...`` it gives every slot its own model, fot_loop_set_sampler_models).  A list of one
         distinct scenario and one mode is today's loop.
         fused: True = the lock step behind one library call (fot_loop_step), False = five separate calls with the
         prediction through the host, None = one call where the engine and the predictor allow it."""
@@ -717,7 +718,9 @@ class BatchedClosedLoop:
                 self.engine.loop_summary_enable(True, int(getattr(c, "num_samples", 1)))
             if self._resident_sampler:
                 self.engine.loop_set_sampler(sample_source.num_samples, sample_source.counter_seed, sample_source.noise_kind,
-                                             slot_crowd=getattr(sample_source, "slot_crowd", None))
+                                             slot_crowd=getattr(sample_source, "slot_crowd", None),
+                                             slot_model=getattr(sample_source, "slot_model", None),
+                                             model_kinds=getattr(sample_source, "model_kinds", None))
             if self._resident_recording and getattr(sample_source, "slot_col0", None) is not None:
                 self.engine.loop_set_samples(sample_source.samples, sample_source.first_step,
                                              n_rec_cols=sample_source.n_cols, slot_col0=sample_source.slot_col0)

@@ -149,6 +149,8 @@ struct LoopSummaryAcc {
     void release() { dRing.release(); dRingP.release(); dTotals.release(); hOut.release(); hSteps.release(); }
 };
 
+constexpr int SGAN_MAX_MODELS = 8;           // fot_sgan_max_models(): models a handle holds (fot_sgan_load_model)
+
 // fot_loop_set_sampler: the resident loop's Social-GAN predictor -- the window, the noise and the raw samples of a step in
 // HBM, the noise kernel's row tables in pinned memory
 struct LoopSampler {
@@ -167,10 +169,38 @@ struct LoopSampler {
     DevBuf dCrowdRaw, dCrowdTab;                 // [S][pred_len][crowd_rows][2] float32 | the tables as hCrowdTab holds them
     PinnedBuf hCrowdTab;                         // scene_off [slots + 1] | scene_slot [slots] | row_scene [cols] | col [cols]
     int last_scenes = 0, last_rows = 0;          // what the most recent lock step handed to the generator (fot_debug_loop_sampler_shape)
+    // fot_loop_set_sampler_models with more than one model: one sampling per active (crowd, model) unit (fot_sweep.hpp).
+    // Model m's window, noise, noise tables and raw tensor are the m-th parts of dWin, dNoise, hTab and dCrowdRaw, each
+    // sized for n_cols rows; its scene tables the m-th parts of hCrowdTab / dCrowdTab.  A loop that names one model takes the
+    // step above on the handle's model 0.
+    int n_models = 1;
+    bool models = false;
+    size_t noise_stride = 0;                     // floats of a model's part of dNoise
+    // the second and later active models of a step sample on side streams (side[m]: model m's), forked from and joined to
+    // the loop's stream by events; FOT_LOOP_MODEL_STREAMS=0 at the set call keeps every model on the loop's stream
+    bool side_on = false;
+    hipStream_t side[SGAN_MAX_MODELS] = { nullptr };
+    hipEvent_t fork = nullptr, join[SGAN_MAX_MODELS] = { nullptr };
+    std::vector<int32_t> kinds;                  // [n_models] every model's noise kind
+    std::vector<int32_t> slot_model;             // [slots]
+    std::vector<ModelShape> mshape;              // [n_models] of the tables in force
+    std::vector<int32_t> mscene_crowd;           // [n_models][slots] the crowd of each scene
+    std::vector<int32_t> row_model, row_col;     // [cols] of the tables in force
+    std::vector<int32_t> last_mscenes, last_mrows;   // [n_models] of the most recent lock step (fot_debug_loop_sampler_shapes)
+    DevBuf dModelTab;                            // ModelRow[cols]
+    PinnedBuf hModelTab;                         // ... as the host builds it
     void release()
     {
         dWin.release(); dNoise.release(); dRaw.release(); hTab.release();
         dCrowdRaw.release(); dCrowdTab.release(); hCrowdTab.release();
+        dModelTab.release(); hModelTab.release();
+        for (int m = 0; m < SGAN_MAX_MODELS; ++m) {
+            if (side[m]) (void)hipStreamDestroy(side[m]);
+            if (join[m]) (void)hipEventDestroy(join[m]);
+            side[m] = nullptr; join[m] = nullptr;
+        }
+        if (fork) (void)hipEventDestroy(fork);
+        fork = nullptr;
     }
 };
 
@@ -343,7 +373,8 @@ struct fot_handle {
     DevBuf dScoreT;                          // ... the device copy of a host tensor
     DevBuf dTmpA, dTmpB, dTmpC, dTmpD;
     LoopState loop;
-    // fot_sgan_*: the loaded model (descriptor, device image of the weights) and the work arrays of a sample call
+    // fot_sgan_*: the loaded models (descriptor, device image of the weights), each with the work arrays of its own sample
+    // calls -- what model m computes never depends on what else is loaded or was sampled in between
     struct Sgan {
         bool loaded = false;
         fot_sgan_desc desc{};
@@ -355,7 +386,7 @@ struct fot_handle {
             for (DevBuf *b : { &dImg, &dOff, &dScene, &dObs, &dNoise, &dOut, &dHenc, &dPool, &dCtx, &dH, &dC, &dXY }) b->release();
             hTab.release();
         }
-    } sgan;
+    } sgan[SGAN_MAX_MODELS];
     bool last_valid = false;
     // profiling: event pairs around kernel launches
     bool prof_on = false;
@@ -386,7 +417,7 @@ bool arm_records(fot_handle *h, int n);
 int wait_records(fot_handle *h, int n, hipStream_t st);
 
 // ---- defined in fot_host_pred.cpp
-int sgan_enqueue(fot_handle *h, int n_scenes, int N, int S, const int32_t *d_off, const int32_t *d_scene,
+int sgan_enqueue(fot_handle *h, int model, int n_scenes, int N, int S, const int32_t *d_off, const int32_t *d_scene,
                  const float *d_obs, const float *d_noise, float *d_out, hipStream_t st);
 
 // brackets one launch with events when profiling is on

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -684,6 +685,8 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     const int dist_S = R.dist_S();
     const bool sampled = dist_S > 0 && ready && rows_run > 0;    // this step predicts with the sampler or the recording
     R.smp.last_scenes = R.smp.last_rows = 0;                     // (fot_debug_loop_sampler_shape: until the sampler branch runs)
+    std::fill(R.smp.last_mscenes.begin(), R.smp.last_mscenes.end(), 0);
+    std::fill(R.smp.last_mrows.begin(), R.smp.last_mrows.end(), 0);
     for (int i = 0; i < n; ++i) {
         const int e = sel[i], c0 = R.ped_off[e], P_e = R.ped_off[e + 1] - c0, nf = R.n_frames[e];
         int pre = 0;
@@ -735,11 +738,92 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         L.dist_S = M.S;
         LAUNCH_TRY(h, launch_resample(C.rp.sgan_dt, C.rp.sim_dt, stale, M.S, C.pred_len, rows, R.n_dense, 1, 1, 0, M.dRaw.p,
                                       M.dtype, fd.last, fd.pos, L.dDyn.p, FOT_F64, 0, st, fd.ped_ep, fd.ped0, fd.blk));
+    } else if (sampled && R.smp.models) {
+        // One sampling per ACTIVE (CROWD, MODEL) UNIT (fot_loop_set_sampler_models): for every model with an active unit, in
+        // ascending id, window -> noise keyed by the crowd -> samples of its units' representatives into its
+        // own raw tensor; then ONE gather of all of them into the step's raw tensor of the running episodes -> the blocks
+        LoopSampler &M = R.smp;
+        const size_t ns = (size_t)std::max(n_slots, 1), N = std::max<size_t>((size_t)R.n_cols, 1), nm = (size_t)M.n_models;
+        int32_t *t_off = (int32_t *)M.hCrowdTab.p, *t_rep = t_off + nm * (ns + 1), *t_scene = t_rep + nm * ns;
+        const int32_t *d_off = M.dCrowdTab.as<int32_t>(), *d_rep = d_off + nm * (ns + 1), *d_scene = d_rep + nm * ns;
+        const size_t raw_stride = (size_t)M.S * (size_t)C.pred_len * N;     // elements of two coordinates of a model's raw tensor
+        if (M.sel != sel) {                                      // a slot dropped out (or the first step); no copy of an earlier
+            int64_t base[SGAN_MAX_MODELS];                       // step still reads the tables (as LoopSamples::hCol)
+            for (size_t m = 0; m < nm; ++m) base[m] = (int64_t)(m * raw_stride);
+            sweep_model_tables(n, L.ped_off.data(), sel.data(), M.slot_crowd.data(), M.slot_model.data(), M.n_models, (int32_t)ns,
+                               (int32_t)N, M.mshape.data(), t_off, t_scene, t_rep, M.mscene_crowd.data(), M.row_model.data(),
+                               M.row_col.data());
+            sweep_model_rows(rows, M.row_model.data(), M.row_col.data(), M.mshape.data(), base, (ModelRow *)M.hModelTab.p);
+            HIP_TRY(h, hipMemcpyAsync(M.dCrowdTab.p, M.hCrowdTab.p, sizeof(int32_t) * nm * ((ns + 1) + ns + N), hipMemcpyHostToDevice, st));
+            HIP_TRY(h, hipMemcpyAsync(M.dModelTab.p, M.hModelTab.p, sizeof(ModelRow) * (size_t)rows, hipMemcpyHostToDevice, st));
+            M.sel = sel;
+        }
+        const size_t win_stride = 2 * (size_t)C.obs_len * N, tab_stride = 3 * (N + ns);
+        const size_t noise_stride = M.noise_stride;                         // (sized by the set call for the widest model)
+        int n_active = 0;
+        for (int m = 0; m < M.n_models; ++m) n_active += M.mshape[(size_t)m].n_scenes > 0;
+        // The first active model samples on the loop's stream, every later one on a side stream of its own, forked from the
+        // loop's stream behind the frame and the tables and joined to it in front of the gather by events: their scratch is
+        // separate, nothing waits on the host (profiles/r24_model_sweep.json: 0.69 against 0.75 ms per lock step)
+        const bool side = M.side_on && n_active > 1;
+        if (side) HIP_TRY(h, hipEventRecord(M.fork, st));
+        int i_active = 0;
+        for (int m = 0; m < M.n_models; ++m) {
+            const int n_sc = M.mshape[(size_t)m].n_scenes, m_rows = M.mshape[(size_t)m].rows;
+            if (n_sc == 0) continue;                             // no active unit: nothing is launched for it
+            hipStream_t ms = side && i_active > 0 ? M.side[m] : st;   // the stream model m samples on
+            if (ms != st) HIP_TRY(h, hipStreamWaitEvent(ms, M.fork, 0));
+            ++i_active;
+            if (m_rows > rows || n_sc > n) return fail(h, FOT_ERR_INVALID, "internal: a model's tables exceed the frame");
+            const fot_sgan_desc &d = h->sgan[m].desc;
+            const bool global_noise = d.noise_mix_type == FOT_SGAN_NOISE_GLOBAL;
+            const int nd = d.noise_dim, noise_rows = global_noise ? n_sc : m_rows;
+            const int32_t *m_off = t_off + (size_t)m * (ns + 1), *m_rep = t_rep + (size_t)m * ns, *m_crowd = M.mscene_crowd.data() + (size_t)m * ns;
+            const int32_t *dm_off = d_off + (size_t)m * (ns + 1), *dm_rep = d_rep + (size_t)m * ns, *dm_scene = d_scene + (size_t)m * N;
+            float *win = M.dWin.as<float>() + (size_t)m * win_stride, *noise = M.dNoise.as<float>() + (size_t)m * noise_stride;
+            if ((size_t)M.S * (size_t)noise_rows * (size_t)nd > noise_stride) return fail(h, FOT_ERR_INVALID, "internal: a model's noise exceeds its block");
+            SgWindow w{};
+            w.pos = rv.pos; w.slot_ped0 = rv.slot_ped0; w.slot_frames = rv.slot_frames;
+            w.ped_ep = dm_scene; w.ep_ped0 = dm_off; w.ep_slot = dm_rep;
+            w.n_cols = R.n_cols; w.rows = m_rows; w.obs_len = d.obs_len;
+            for (int j = 0; j < d.obs_len; ++j) w.frames.f[j] = R.clock.sample_frame[(size_t)j];
+            w.out = win;
+            LAUNCH_TRY(h, launch_sgan_window(w, ms));
+            if (nd > 0) {
+                const size_t cap = (size_t)R.n_cols + (size_t)n_slots;
+                int32_t *t_slot = (int32_t *)M.hTab.p + (size_t)m * tab_stride, *t_step = t_slot + cap, *t_idx = t_step + cap;
+                int r = 0;
+                for (int c = 0; c < n_sc; ++c) {                 // (lock step: the representative's step is its unit's)
+                    const int e = m_rep[c], P_c = m_off[c + 1] - m_off[c];
+                    for (int p = 0; p < (global_noise ? 1 : P_c); ++p, ++r) { t_slot[r] = m_crowd[c]; t_step[r] = R.steps[(size_t)e]; t_idx[r] = p; }
+                }
+                SgNoise a{};
+                a.seed = M.seed; a.kind = M.kinds[(size_t)m]; a.S = M.S; a.rows = noise_rows; a.nd = nd; a.n_blk = (nd + 3) / 4;
+                a.slot = t_slot; a.step = t_step; a.index = t_idx; a.out = (uint32_t *)noise;
+                LAUNCH_TRY(h, launch_sgan_noise(a, ms));
+            }
+            { int r = sgan_enqueue(h, m, n_sc, m_rows, M.S, dm_off, global_noise && nd > 0 ? dm_scene : nullptr, win, noise,
+                                   M.dCrowdRaw.as<float>() + 2 * (size_t)m * raw_stride, ms); if (r != FOT_OK) return r; }
+            M.last_mscenes[(size_t)m] = n_sc; M.last_mrows[(size_t)m] = m_rows;
+            M.last_scenes += n_sc; M.last_rows += m_rows;
+            if (ms != st) {
+                HIP_TRY(h, hipEventRecord(M.join[m], ms));
+                HIP_TRY(h, hipStreamWaitEvent(st, M.join[m], 0));
+            }
+        }
+        LoopModelRows g{};
+        g.S = M.S; g.pred_len = C.pred_len; g.rows = rows;
+        g.pool = (const float2 *)M.dCrowdRaw.p; g.tab = M.dModelTab.as<ModelRow>(); g.out = (float2 *)M.dRaw.p;
+        LAUNCH_TRY(h, launch_loop_model_rows(g, st));
+        L.dyn_ptr = L.dDyn.p;
+        L.dist_S = M.S;
+        LAUNCH_TRY(h, launch_resample(C.rp.sgan_dt, C.rp.sim_dt, stale, M.S, C.pred_len, rows, R.n_dense, 1, 1, 0, M.dRaw.p,
+                                      FOT_F32, fd.last, fd.pos, L.dDyn.p, FOT_F64, 0, st, fd.ped_ep, fd.ped0, fd.blk));
     } else if (sampled && R.smp.crowds) {
         // One sampling per ACTIVE CROWD (fot_loop_set_sampler_shared): window -> noise keyed by the crowd -> samples of the
         // crowds' representatives -> gathered into the step's raw tensor of the running episodes -> every episode's block
         LoopSampler &M = R.smp;
-        const fot_sgan_desc &d = h->sgan.desc;
+        const fot_sgan_desc &d = h->sgan[0].desc;
         const bool global_noise = d.noise_mix_type == FOT_SGAN_NOISE_GLOBAL;
         const int nd = d.noise_dim;
         const size_t ns = (size_t)std::max(n_slots, 1), N = std::max<size_t>((size_t)R.n_cols, 1);
@@ -777,7 +861,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
             a.slot = t_slot; a.step = t_step; a.index = t_idx; a.out = (uint32_t *)M.dNoise.p;
             LAUNCH_TRY(h, launch_sgan_noise(a, st));
         }
-        { int r = sgan_enqueue(h, n_sc, c_rows, M.S, d_off, global_noise && nd > 0 ? d_scene : nullptr, M.dWin.as<float>(),
+        { int r = sgan_enqueue(h, 0, n_sc, c_rows, M.S, d_off, global_noise && nd > 0 ? d_scene : nullptr, M.dWin.as<float>(),
                                M.dNoise.as<float>(), crowd_raw, st); if (r != FOT_OK) return r; }
         if (!M.shape.identity) {                                 // (one slot per crowd, in the crowds' order: nothing to gather)
             LoopSampleRows a{};
@@ -794,7 +878,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         // window -> noise -> samples -> every episode's [S][P_e][n_dense + 1][2] block, all in HBM behind k_loop_frame
         LoopSampler &M = R.smp;
         M.last_scenes = n; M.last_rows = rows;
-        const fot_sgan_desc &d = h->sgan.desc;
+        const fot_sgan_desc &d = h->sgan[0].desc;
         const bool global_noise = d.noise_mix_type == FOT_SGAN_NOISE_GLOBAL;
         const int nd = d.noise_dim, noise_rows = global_noise ? n : rows;
         SgWindow w{};
@@ -817,7 +901,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
             a.slot = t_slot; a.step = t_step; a.index = t_idx; a.out = (uint32_t *)M.dNoise.p;
             LAUNCH_TRY(h, launch_sgan_noise(a, st));
         }
-        { int r = sgan_enqueue(h, n, rows, M.S, fd.ped0, global_noise && nd > 0 ? fd.ped_ep : nullptr, M.dWin.as<float>(),
+        { int r = sgan_enqueue(h, 0, n, rows, M.S, fd.ped0, global_noise && nd > 0 ? fd.ped_ep : nullptr, M.dWin.as<float>(),
                                M.dNoise.as<float>(), M.dRaw.as<float>(), st); if (r != FOT_OK) return r; }
         L.dyn_ptr = L.dDyn.p;
         L.dist_S = M.S;
@@ -1095,27 +1179,63 @@ int set_samples_impl(fot_handle *h, const std::string &who, int32_t S, int32_t n
     return FOT_OK;
 }
 
-// fot_loop_set_sampler / fot_loop_set_sampler_shared (who: the entry's name, for the messages); slot_crowd == nullptr: slot e
-// is crowd e
-int set_sampler_impl(fot_handle *h, const std::string &who, int32_t S, uint64_t seed, int32_t kind, bool shared, int32_t n_crowds,
-                     const int32_t *slot_crowd)
+// what a sampler step of the resident loop needs of model `model`'s own work arrays, for S samples of up to N pedestrians
+int sampler_model_scratch(fot_handle *h, int model, size_t S, size_t N)
+{
+    fot_handle::Sgan &G = h->sgan[model];
+    const fot_sgan_desc &d = G.desc;
+    const size_t rows = S * N;
+    const int bp = sg_pooled(d) ? G.dev.pool.b_pad : 0;
+    HIP_TRY(h, G.dHenc.ensure(sizeof(float) * N * (size_t)d.encoder_h_dim));
+    if (bp > 0) HIP_TRY(h, G.dPool.ensure(sizeof(float) * (sg_pool_steps(d) ? rows : N) * (size_t)bp));
+    if (sg_has_context(d)) HIP_TRY(h, G.dCtx.ensure(sizeof(float) * N * (size_t)std::max(d.decoder_h_dim - d.noise_dim, 1)));
+    if (sg_pool_steps(d)) {
+        HIP_TRY(h, G.dH.ensure(sizeof(float) * rows * (size_t)d.decoder_h_dim));
+        HIP_TRY(h, G.dC.ensure(sizeof(float) * rows * (size_t)d.decoder_h_dim));
+        HIP_TRY(h, G.dXY.ensure(sizeof(float) * rows * 6));
+    }
+    return FOT_OK;
+}
+
+// fot_loop_set_sampler / fot_loop_set_sampler_shared / fot_loop_set_sampler_models (who: the entry's name, for the messages).
+// slot_crowd == nullptr: slot e is crowd e.  slot_model == nullptr (the first two entries): one model, the handle's model 0,
+// of kind model_kind[0]; otherwise the third entry, whose slots name their models.
+int set_sampler_impl(fot_handle *h, const std::string &who, int32_t S, uint64_t seed, int32_t n_models, const int32_t *model_kind,
+                     bool shared, int32_t n_crowds, const int32_t *slot_crowd, bool by_model, const int32_t *slot_model)
 {
     LoopState &L = h->loop;
     LoopReplay &R = L.replay;
-    fot_handle::Sgan &G = h->sgan;
     if (!R.set) return fail(h, FOT_ERR_INVALID, who + ": fot_loop_set_replay comes first");
-    if (!G.loaded) return fail(h, FOT_ERR_INVALID, who + ": no model loaded (fot_sgan_load)");
+    bool used[SGAN_MAX_MODELS] = { false };                      // the models some slot names
+    if (by_model) {
+        if (!slot_model || !model_kind) return fail(h, FOT_ERR_INVALID, who + ": slot_model / model_kind is NULL");
+        if (n_models < 1 || n_models > SGAN_MAX_MODELS) return fail(h, FOT_ERR_INVALID, who + ": n_models lies outside 1 .. fot_sgan_max_models()");
+        for (int e = 0; e < R.cfg.n_slots; ++e) {
+            if (slot_model[e] < 0 || slot_model[e] >= n_models)
+                return fail(h, FOT_ERR_INVALID, who + ": slot_model[" + std::to_string(e) + "] lies outside 0 .. n_models - 1");
+            if (!h->sgan[slot_model[e]].loaded)
+                return fail(h, FOT_ERR_INVALID, who + ": slot " + std::to_string(e) + " names model " + std::to_string(slot_model[e]) +
+                                                ", which is not loaded (fot_sgan_load_model)");
+            used[slot_model[e]] = true;
+        }
+        if (n_models == 1 && !h->sgan[0].loaded) return fail(h, FOT_ERR_INVALID, who + ": model 0 is not loaded (fot_sgan_load_model)");
+    } else {
+        if (!h->sgan[0].loaded) return fail(h, FOT_ERR_INVALID, who + ": no model loaded (fot_sgan_load)");
+    }
+    if (n_models == 1) used[0] = true;                           // (a loop that names one model: the shared entry's step)
     if (R.rec.on) return fail(h, FOT_ERR_INVALID, who + ": recorded samples are set (fot_loop_set_samples): one predictor per run");
     const int n = R.cfg.n_slots;
     bool begun = R.clock.frame != R.cfg.warmup_frames;
     for (int e = 0; e < n; ++e) begun = begun || R.steps[(size_t)e] != 0;
     if (begun) return fail(h, FOT_ERR_INVALID, who + ": the run has begun (set it between fot_loop_set_replay and the first step)");
     if (S < 1) return fail(h, FOT_ERR_INVALID, who + ": S < 1");
-    if (kind != FOT_NOISE_GAUSSIAN && kind != FOT_NOISE_UNIFORM_SYM)
-        return fail(h, FOT_ERR_INVALID, who + ": kind is FOT_NOISE_GAUSSIAN or FOT_NOISE_UNIFORM_SYM");
-    const fot_sgan_desc &d = G.desc;
-    if (d.obs_len != R.cfg.obs_len || d.pred_len != R.cfg.pred_len)
-        return fail(h, FOT_ERR_INVALID, who + ": the model's obs_len / pred_len differ from the replay's");
+    for (int m = 0; m < n_models; ++m)
+        if (model_kind[m] != FOT_NOISE_GAUSSIAN && model_kind[m] != FOT_NOISE_UNIFORM_SYM)
+            return fail(h, FOT_ERR_INVALID, who + ": kind is FOT_NOISE_GAUSSIAN or FOT_NOISE_UNIFORM_SYM");
+    for (int m = 0; m < n_models; ++m)
+        if (used[m] && (h->sgan[m].desc.obs_len != R.cfg.obs_len || h->sgan[m].desc.pred_len != R.cfg.pred_len))
+            return fail(h, FOT_ERR_INVALID, who + ": the model's obs_len / pred_len differ from the replay's" +
+                                            (by_model ? " (model " + std::to_string(m) + ")" : ""));
     if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, who + ": S > FOT_MAX_SAMPLES");
     for (int e = 0; e < n; ++e)
         if (R.ped_off[(size_t)e + 1] - R.ped_off[(size_t)e] > FOT_SGAN_MAX_PEDS)
@@ -1141,34 +1261,56 @@ int set_sampler_impl(fot_handle *h, const std::string &who, int32_t S, uint64_t 
     // --- accepted: everything a step needs is allocated here, so that no block grows (and moves) inside a run
     LoopSampler &M = R.smp;
     const size_t N = std::max<size_t>((size_t)R.n_cols, 1), rows = (size_t)S * N, ns = (size_t)std::max(n, 1);
-    const int bp = sg_pooled(d) ? G.dev.pool.b_pad : 0;
+    const bool models = n_models > 1;                            // (one model: the shared entry's step on model 0, nothing new)
+    const size_t nm = (size_t)n_models, obs_len = (size_t)R.cfg.obs_len, pred_len = (size_t)R.cfg.pred_len;
+    int nd_max = 1;
+    for (int m = 0; m < n_models; ++m)
+        if (used[m]) nd_max = std::max(nd_max, h->sgan[m].desc.noise_dim);
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     M.on = false;
-    HIP_TRY(h, M.dWin.ensure(sizeof(float) * 2 * (size_t)d.obs_len * N));
-    HIP_TRY(h, M.dNoise.ensure(sizeof(float) * (size_t)S * std::max(N, ns) * (size_t)std::max(d.noise_dim, 1)));
-    HIP_TRY(h, M.dRaw.ensure(sizeof(float) * 2 * (size_t)S * (size_t)d.pred_len * N));
-    HIP_TRY(h, M.hTab.ensure(sizeof(int32_t) * 3 * (N + ns)));
+    HIP_TRY(h, M.dWin.ensure(sizeof(float) * 2 * obs_len * N * nm));
+    const size_t noise_stride = (size_t)S * std::max(N, ns) * (size_t)nd_max;
+    HIP_TRY(h, M.dNoise.ensure(sizeof(float) * noise_stride * nm));
+    HIP_TRY(h, M.dRaw.ensure(sizeof(float) * 2 * (size_t)S * pred_len * N));
+    HIP_TRY(h, M.hTab.ensure(sizeof(int32_t) * 3 * (N + ns) * nm));
     HIP_TRY(h, L.dDyn.ensure(sizeof(double) * 2 * rows * (size_t)(R.n_dense + 1)));
     if (L.ep.sweep) { int r = sweep_ensure(h, S); if (r != FOT_OK) return r; }
-    HIP_TRY(h, G.dHenc.ensure(sizeof(float) * N * (size_t)d.encoder_h_dim));
-    if (bp > 0) HIP_TRY(h, G.dPool.ensure(sizeof(float) * (sg_pool_steps(d) ? rows : N) * (size_t)bp));
-    if (sg_has_context(d)) HIP_TRY(h, G.dCtx.ensure(sizeof(float) * N * (size_t)std::max(d.decoder_h_dim - d.noise_dim, 1)));
-    if (sg_pool_steps(d)) {
-        HIP_TRY(h, G.dH.ensure(sizeof(float) * rows * (size_t)d.decoder_h_dim));
-        HIP_TRY(h, G.dC.ensure(sizeof(float) * rows * (size_t)d.decoder_h_dim));
-        HIP_TRY(h, G.dXY.ensure(sizeof(float) * rows * 6));
-    }
-    if (crowds) {                                                // (slot e -> crowd e: today's step, nothing new)
-        HIP_TRY(h, M.dCrowdRaw.ensure(sizeof(float) * 2 * (size_t)S * (size_t)d.pred_len * N));
+    for (int m = 0; m < n_models; ++m)
+        if (used[m]) { int r = sampler_model_scratch(h, m, (size_t)S, N); if (r != FOT_OK) return r; }
+    if (models) {                                                // every model's raw tensor, scene tables and the rows' table
+        HIP_TRY(h, M.dCrowdRaw.ensure(sizeof(float) * 2 * (size_t)S * pred_len * N * nm));
+        HIP_TRY(h, M.dCrowdTab.ensure(sizeof(int32_t) * nm * ((ns + 1) + ns + N)));
+        HIP_TRY(h, M.hCrowdTab.ensure(sizeof(int32_t) * nm * ((ns + 1) + ns + N)));
+        HIP_TRY(h, M.dModelTab.ensure(sizeof(ModelRow) * N));
+        HIP_TRY(h, M.hModelTab.ensure(sizeof(ModelRow) * N));
+        M.slot_crowd.assign(slot_crowd, slot_crowd + n);
+        M.slot_model.assign(slot_model, slot_model + n);
+        const char *env = std::getenv("FOT_LOOP_MODEL_STREAMS");    // "0": every model on the loop's stream (measurements)
+        M.side_on = !(env && env[0] == '0');
+        if (M.side_on && !M.fork) HIP_TRY(h, hipEventCreateWithFlags(&M.fork, hipEventDisableTiming));
+        for (int m = 1; M.side_on && m < n_models; ++m) {
+            if (M.side[m]) continue;                             // (kept from an earlier set call of this handle)
+            HIP_TRY(h, hipStreamCreateWithFlags(&M.side[m], hipStreamNonBlocking));
+            HIP_TRY(h, hipEventCreateWithFlags(&M.join[m], hipEventDisableTiming));
+        }
+    } else if (crowds) {                                         // (slot e -> crowd e: today's step, nothing new)
+        HIP_TRY(h, M.dCrowdRaw.ensure(sizeof(float) * 2 * (size_t)S * pred_len * N));
         HIP_TRY(h, M.dCrowdTab.ensure(sizeof(int32_t) * ((ns + 1) + ns + 2 * N)));
         HIP_TRY(h, M.hCrowdTab.ensure(sizeof(int32_t) * ((ns + 1) + ns + 2 * N)));
         M.slot_crowd.assign(slot_crowd, slot_crowd + n);
     }
-    M.crowds = crowds;
+    M.crowds = crowds && !models;
+    M.models = models;
+    M.n_models = n_models; M.noise_stride = noise_stride;
+    M.kinds.assign(model_kind, model_kind + n_models);
+    M.mshape.assign(nm, ModelShape());
+    M.mscene_crowd.assign(nm * ns, -1);
+    M.row_model.assign(N, 0); M.row_col.assign(N, 0);
+    M.last_mscenes.assign(nm, 0); M.last_mrows.assign(nm, 0);
     M.sel.clear();
     M.last_scenes = M.last_rows = 0;
-    M.S = S; M.seed = seed; M.kind = kind;
+    M.S = S; M.seed = seed; M.kind = model_kind[0];
     M.on = true;
     R.sc.on = false;                                             // (a new sampler: its scores are enabled again, if wanted)
     return FOT_OK;
@@ -1686,13 +1828,34 @@ int fot_debug_loop_block(fot_handle *h, int32_t episode, int32_t cap_points, dou
 int fot_loop_set_sampler(fot_handle *h, int32_t S, uint64_t seed, int32_t kind)
 {
     if (!h) return FOT_ERR_INVALID;
-    return set_sampler_impl(h, "fot_loop_set_sampler", S, seed, kind, false, 0, nullptr);
+    return set_sampler_impl(h, "fot_loop_set_sampler", S, seed, 1, &kind, false, 0, nullptr, false, nullptr);
 }
 
 int fot_loop_set_sampler_shared(fot_handle *h, int32_t S, uint64_t seed, int32_t kind, int32_t n_crowds, const int32_t *slot_crowd)
 {
     if (!h) return FOT_ERR_INVALID;
-    return set_sampler_impl(h, "fot_loop_set_sampler_shared", S, seed, kind, true, n_crowds, slot_crowd);
+    return set_sampler_impl(h, "fot_loop_set_sampler_shared", S, seed, 1, &kind, true, n_crowds, slot_crowd, false, nullptr);
+}
+
+int fot_loop_set_sampler_models(fot_handle *h, int32_t S, uint64_t seed, int32_t n_models, const int32_t *model_kind,
+                                int32_t n_crowds, const int32_t *slot_crowd, const int32_t *slot_model)
+{
+    if (!h) return FOT_ERR_INVALID;
+    return set_sampler_impl(h, "fot_loop_set_sampler_models", S, seed, n_models, model_kind, true, n_crowds, slot_crowd, true, slot_model);
+}
+
+int fot_debug_loop_sampler_shapes(fot_handle *h, int32_t cap, int32_t *n_scenes, int32_t *n_rows)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopReplay &R = h->loop.replay;
+    if (!R.set || !R.smp.on) return fail(h, FOT_ERR_INVALID, "fot_debug_loop_sampler_shapes: no sampler is set (fot_loop_set_sampler)");
+    if (cap < 0 || (cap > 0 && (!n_scenes || !n_rows))) return fail(h, FOT_ERR_INVALID, "fot_debug_loop_sampler_shapes: cap / NULL array");
+    for (int m = 0; m < cap; ++m) {                              // (ids the loop does not name: nothing was handed to them)
+        const bool named = m < R.smp.n_models;
+        n_scenes[m] = !named ? 0 : R.smp.models ? R.smp.last_mscenes[(size_t)m] : R.smp.last_scenes;
+        n_rows[m] = !named ? 0 : R.smp.models ? R.smp.last_mrows[(size_t)m] : R.smp.last_rows;
+    }
+    return FOT_OK;
 }
 
 int fot_debug_loop_sampler_shape(fot_handle *h, int32_t *n_scenes, int32_t *n_rows)

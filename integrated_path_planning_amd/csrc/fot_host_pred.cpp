@@ -163,12 +163,12 @@ int prediction_scores_impl(fot_handle *h, const char *who, int32_t n, const fot_
 
 // ---- the helper fot_host.hpp declares for the resident loop's sampler step (fot_host_loop.cpp loop_run_step)
 // The launches of fot_sgan_sample behind its inputs, enqueue only (no copy from host memory, no synchronisation): all S
-// samples of the N > 0 pedestrians of n_scenes scenes.  d_off [n_scenes + 1] and d_scene [N] (the scene of every pedestrian;
+// samples of the N > 0 pedestrians of n_scenes scenes from the loaded model `model`, in its own work arrays.  d_off [n_scenes + 1] and d_scene [N] (the scene of every pedestrian;
 // nullptr unless the noise is per scene) are device memory, as are the tensors.
-int fot::host::sgan_enqueue(fot_handle *h, int n_scenes, int N, int S, const int32_t *d_off, const int32_t *d_scene,
+int fot::host::sgan_enqueue(fot_handle *h, int model, int n_scenes, int N, int S, const int32_t *d_off, const int32_t *d_scene,
                             const float *d_obs, const float *d_noise, float *d_out, hipStream_t st)
 {
-    fot_handle::Sgan &G = h->sgan;
+    fot_handle::Sgan &G = h->sgan[model];
     const fot_sgan_desc &d = G.desc;
     const int nd = d.noise_dim, noise_rows = d.noise_mix_type == FOT_SGAN_NOISE_GLOBAL ? n_scenes : N;
     const int E = d.embedding_dim, He = d.encoder_h_dim, Hd = d.decoder_h_dim, T = d.obs_len, L = d.pred_len;
@@ -357,20 +357,24 @@ int fot_sgan_weight_count(const fot_sgan_desc *desc, int64_t *n)
     return FOT_OK;
 }
 
-int fot_sgan_load(fot_handle *h, const fot_sgan_desc *desc, int64_t n, const float *weights)
+// ---- several models per handle: fot_sgan_load / fot_sgan_unload / fot_sgan_sample are the _model entries with model = 0
+int32_t fot_sgan_max_models(void) { return SGAN_MAX_MODELS; }
+
+static int sgan_load_impl(fot_handle *h, const std::string &who, int32_t model, const fot_sgan_desc *desc, int64_t n, const float *weights)
 {
     if (!h) return FOT_ERR_INVALID;
-    if (!desc || !weights) return fail(h, FOT_ERR_INVALID, "fot_sgan_load: desc / weights is NULL");
-    if (h->loop.replay.set && h->loop.replay.smp.on) return fail(h, FOT_ERR_INVALID, "fot_sgan_load: the resident loop's sampler uses the model (fot_loop_set_sampler)");
+    if (model < 0 || model >= SGAN_MAX_MODELS) return fail(h, FOT_ERR_INVALID, who + ": model lies outside 0 .. fot_sgan_max_models() - 1");
+    if (!desc || !weights) return fail(h, FOT_ERR_INVALID, who + ": desc / weights is NULL");
+    if (h->loop.replay.set && h->loop.replay.smp.on) return fail(h, FOT_ERR_INVALID, who + ": the resident loop's sampler uses the handle's models (fot_loop_set_sampler)");
     std::string why;
     const int rc = sg_check_desc(*desc, why);
     if (rc != FOT_OK) return fail(h, rc, why);
-    if (n != sg_blob_layout(*desc).total) return fail(h, FOT_ERR_INVALID, "fot_sgan_load: n is not fot_sgan_weight_count of the descriptor");
+    if (n != sg_blob_layout(*desc).total) return fail(h, FOT_ERR_INVALID, who + ": n is not fot_sgan_weight_count of the descriptor");
     std::vector<float> img;
     const SgDev dev = sg_dev_image(*desc, weights, img);
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));                   // (a sample call of the model before this one is synchronous anyway)
-    fot_handle::Sgan &G = h->sgan;
+    fot_handle::Sgan &G = h->sgan[model];
     G.loaded = false;
     HIP_TRY(h, G.dImg.ensure(sizeof(float) * img.size()));
     HIP_TRY(h, hipMemcpy(G.dImg.p, img.data(), sizeof(float) * img.size(), hipMemcpyHostToDevice));
@@ -380,40 +384,57 @@ int fot_sgan_load(fot_handle *h, const fot_sgan_desc *desc, int64_t n, const flo
     return FOT_OK;
 }
 
-int fot_sgan_unload(fot_handle *h)
+int fot_sgan_load(fot_handle *h, const fot_sgan_desc *desc, int64_t n, const float *weights)
+{
+    return sgan_load_impl(h, "fot_sgan_load", 0, desc, n, weights);
+}
+
+int fot_sgan_load_model(fot_handle *h, int32_t model, const fot_sgan_desc *desc, int64_t n, const float *weights)
+{
+    return sgan_load_impl(h, "fot_sgan_load_model", model, desc, n, weights);
+}
+
+static int sgan_unload_impl(fot_handle *h, const std::string &who, int32_t model, bool must_be_loaded)
 {
     if (!h) return FOT_ERR_INVALID;
-    if (h->loop.replay.set && h->loop.replay.smp.on) return fail(h, FOT_ERR_INVALID, "fot_sgan_unload: the resident loop's sampler uses the model (fot_loop_set_sampler)");
+    if (model < 0 || model >= SGAN_MAX_MODELS) return fail(h, FOT_ERR_INVALID, who + ": model lies outside 0 .. fot_sgan_max_models() - 1");
+    if (h->loop.replay.set && h->loop.replay.smp.on) return fail(h, FOT_ERR_INVALID, who + ": the resident loop's sampler uses the handle's models (fot_loop_set_sampler)");
+    if (must_be_loaded && !h->sgan[model].loaded) return fail(h, FOT_ERR_INVALID, who + ": the model is not loaded (fot_sgan_load_model)");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->sgan.loaded = false;
-    h->sgan.release();
+    h->sgan[model].loaded = false;
+    h->sgan[model].release();
     return FOT_OK;
 }
 
-int fot_sgan_sample(fot_handle *h, int32_t n_scenes, const int32_t *ped_off, const void *obs, int32_t S, const void *noise,
-                    int32_t flags, void *out, void *stream)
+int fot_sgan_unload(fot_handle *h) { return sgan_unload_impl(h, "fot_sgan_unload", 0, false); }   // (no model: nothing to drop)
+
+int fot_sgan_unload_model(fot_handle *h, int32_t model) { return sgan_unload_impl(h, "fot_sgan_unload_model", model, true); }
+
+static int sgan_sample_impl(fot_handle *h, const std::string &who, int32_t model, int32_t n_scenes, const int32_t *ped_off, const void *obs,
+                            int32_t S, const void *noise, int32_t flags, void *out, void *stream)
 {
     if (!h) return FOT_ERR_INVALID;
-    fot_handle::Sgan &G = h->sgan;
-    if (!G.loaded) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: no model loaded (fot_sgan_load)");
-    if (n_scenes < 0 || !ped_off) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: n_scenes / ped_off (one offset even for no scene)");
-    if (S < 1) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: S < 1");
-    if (flags & ~(FOT_OUT_DEVICE | FOT_SGAN_OBS_DEVICE | FOT_SGAN_NOISE_DEVICE)) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: flags");
-    if (ped_off[0] != 0) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: ped_off must start at 0 and be non-decreasing");
+    if (model < 0 || model >= SGAN_MAX_MODELS) return fail(h, FOT_ERR_INVALID, who + ": model lies outside 0 .. fot_sgan_max_models() - 1");
+    fot_handle::Sgan &G = h->sgan[model];
+    if (!G.loaded) return fail(h, FOT_ERR_INVALID, who + ": no model loaded (fot_sgan_load)");
+    if (n_scenes < 0 || !ped_off) return fail(h, FOT_ERR_INVALID, who + ": n_scenes / ped_off (one offset even for no scene)");
+    if (S < 1) return fail(h, FOT_ERR_INVALID, who + ": S < 1");
+    if (flags & ~(FOT_OUT_DEVICE | FOT_SGAN_OBS_DEVICE | FOT_SGAN_NOISE_DEVICE)) return fail(h, FOT_ERR_INVALID, who + ": flags");
+    if (ped_off[0] != 0) return fail(h, FOT_ERR_INVALID, who + ": ped_off must start at 0 and be non-decreasing");
     int widest = 0;
     for (int i = 0; i < n_scenes; ++i) {
-        if (ped_off[i + 1] < ped_off[i]) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: ped_off must start at 0 and be non-decreasing");
+        if (ped_off[i + 1] < ped_off[i]) return fail(h, FOT_ERR_INVALID, who + ": ped_off must start at 0 and be non-decreasing");
         widest = std::max(widest, ped_off[i + 1] - ped_off[i]);
     }
-    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, "fot_sgan_sample: S > FOT_MAX_SAMPLES");
-    if (widest > FOT_SGAN_MAX_PEDS) return fail(h, FOT_ERR_UNSUPPORTED, "fot_sgan_sample: a scene of more than FOT_SGAN_MAX_PEDS pedestrians");
+    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, who + ": S > FOT_MAX_SAMPLES");
+    if (widest > FOT_SGAN_MAX_PEDS) return fail(h, FOT_ERR_UNSUPPORTED, who + ": a scene of more than FOT_SGAN_MAX_PEDS pedestrians");
     const fot_sgan_desc &d = G.desc;
     const int N = ped_off[n_scenes];
     const bool global_noise = d.noise_mix_type == FOT_SGAN_NOISE_GLOBAL;
     const int nd = d.noise_dim, noise_rows = global_noise ? n_scenes : N;
     if (N == 0) return FOT_OK;
-    if (!obs || !out || (nd > 0 && !noise)) return fail(h, FOT_ERR_INVALID, "fot_sgan_sample: NULL tensor");
+    if (!obs || !out || (nd > 0 && !noise)) return fail(h, FOT_ERR_INVALID, who + ": NULL tensor");
     const int T = d.obs_len, L = d.pred_len;
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
@@ -443,12 +464,24 @@ int fot_sgan_sample(fot_handle *h, int32_t n_scenes, const int32_t *ped_off, con
     }
     float *d_out = (float *)out;
     if (!(flags & FOT_OUT_DEVICE)) { HIP_TRY(h, G.dOut.ensure(out_bytes)); d_out = G.dOut.as<float>(); }
-    { int r = sgan_enqueue(h, n_scenes, N, S, G.dOff.as<int32_t>(), global_noise && nd > 0 ? G.dScene.as<int32_t>() : nullptr, d_obs,
+    { int r = sgan_enqueue(h, model, n_scenes, N, S, G.dOff.as<int32_t>(), global_noise && nd > 0 ? G.dScene.as<int32_t>() : nullptr, d_obs,
                            d_noise, d_out, st); if (r != FOT_OK) return r; }
     if (!(flags & FOT_OUT_DEVICE)) HIP_TRY(h, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     { int r = order_end(h, st); if (r != FOT_OK) return r; }
     HIP_TRY(h, hipStreamSynchronize(st));
     return FOT_OK;
+}
+
+int fot_sgan_sample(fot_handle *h, int32_t n_scenes, const int32_t *ped_off, const void *obs, int32_t S, const void *noise,
+                    int32_t flags, void *out, void *stream)
+{
+    return sgan_sample_impl(h, "fot_sgan_sample", 0, n_scenes, ped_off, obs, S, noise, flags, out, stream);
+}
+
+int fot_sgan_sample_model(fot_handle *h, int32_t model, int32_t n_scenes, const int32_t *ped_off, const void *obs, int32_t S,
+                          const void *noise, int32_t flags, void *out, void *stream)
+{
+    return sgan_sample_impl(h, "fot_sgan_sample_model", model, n_scenes, ped_off, obs, S, noise, flags, out, stream);
 }
 
 int fot_sgan_noise(fot_handle *h, uint64_t seed, int32_t kind, int32_t S, int32_t rows, int32_t noise_dim,
@@ -465,7 +498,7 @@ int fot_sgan_noise(fot_handle *h, uint64_t seed, int32_t kind, int32_t S, int32_
     for (int r = 0; r < rows; ++r)
         if (row_slot[r] < 0 || row_step[r] < 0 || row_index[r] < 0 || row_index[r] > 0xFFFF)
             return fail(h, FOT_ERR_INVALID, "fot_sgan_noise: a negative table entry, or a row_index above 65535");
-    fot_handle::Sgan &G = h->sgan;
+    fot_handle::Sgan &G = h->sgan[0];                              // (its table block and noise scratch: no model is read)
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     const size_t n_out = (size_t)S * (size_t)rows * (size_t)noise_dim;

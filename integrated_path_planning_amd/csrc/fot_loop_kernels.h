@@ -113,6 +113,16 @@ struct LoopSampleRows {
     int32_t dtype, _pad;
 };
 int launch_loop_sample_rows(const LoopSampleRows &a, hipStream_t st);
+// fot_loop_set_sampler_models: the models' raw tensors (float32, [S][pred_len][rows_m][2] each, in one pool) -> the step's
+// raw samples out [S][pred_len][rows][2] of the running slots; tab [rows] names every frame row's tensor, its width and
+// the row's column in it (HBM; fot_sweep.hpp's sweep_model_rows).  pool is only read.
+struct LoopModelRows {
+    int32_t S, pred_len, rows, _pad;
+    const float2 *pool;
+    const ModelRow *tab;                     // [rows]
+    float2 *out;
+};
+int launch_loop_model_rows(const LoopModelRows &a, hipStream_t st);
 // constant-velocity tracks of every row of the frame in ONE launch, episode i's [P_i][n_dense + prepend[i]][2] block at
 // point blk[i] of `out`: k_resample's float32-observation path (cv = 2) with the prepend decided per episode
 int launch_predict_cv_frame(double sgan_dt, double sim_dt, double staleness, int n_rows, int n_dense, FrameDev f,

@@ -349,6 +349,20 @@ __global__ __launch_bounds__(SR_THREADS) void k_loop_sample_rows(LoopSampleRows 
     ((V *)a.out)[t] = ((const V *)a.rec)[sr_src_elem(a.d, s, j, a.col[q])];    // (t = sr_dst_elem(a.d, s, j, q))
 }
 
+// The same lane layout over the raw tensors of several models: row q's 16-byte table entry names its model's tensor, that
+// tensor's width and the row's column (fot_sweep.hpp).  The lanes of a wave load neighbouring entries and, within one
+// episode, read and write runs of neighbouring pedestrians.
+__global__ __launch_bounds__(SR_THREADS) void k_loop_model_rows(LoopModelRows a)
+{
+    SampleRecDims d;
+    d.S = a.S; d.pred_len = a.pred_len; d.rows = a.rows;
+    const int64_t t = (int64_t)blockIdx.x * SR_THREADS + threadIdx.x;
+    if (t >= sr_step_elems(d)) return;
+    int32_t s, j, q;
+    sr_split(d, t, s, j, q);
+    a.out[t] = a.pool[sweep_model_src_elem(a.tab[q], a.pred_len, s, j)];       // (t = sr_dst_elem(d, s, j, q))
+}
+
 }  // namespace
 
 // One workgroup per request of a scenario loop: its scenario's static points, resident once in HBM, into the request's
@@ -772,6 +786,15 @@ int launch_loop_sample_rows(const LoopSampleRows &a, hipStream_t st)
     const unsigned grid = (unsigned)((total + SR_THREADS - 1) / SR_THREADS);
     if (a.dtype == FOT_F32) k_loop_sample_rows<float2><<<grid, SR_THREADS, 0, st>>>(a);
     else k_loop_sample_rows<double2><<<grid, SR_THREADS, 0, st>>>(a);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_model_rows(const LoopModelRows &a, hipStream_t st)
+{
+    const int64_t total = (int64_t)a.S * a.pred_len * a.rows;
+    if (total <= 0) return 0;
+    k_loop_model_rows<<<(unsigned)((total + SR_THREADS - 1) / SR_THREADS), SR_THREADS, 0, st>>>(a);
     FOT_LAUNCH_CHECK();
     return 0;
 }

@@ -4,8 +4,9 @@
 // planning blocks [P_e][T][2] (fot_repsample.hpp) of the episodes in FOT_LOOP_PLAN_REPRESENTATIVE mode.  A request then
 // addresses its episode's distribution block with S samples or its planning block with one, on the same base pointer.
 // Also the row -> column table of a recording whose columns the slots name themselves (fot_loop_set_samples_shared), and
-// the tables of a sampler step whose slots share their crowds' samples (fot_loop_set_sampler_shared).
-// Plain C++ shared by the kernels (k_loop_best_sample_sweep, k_loop_rep_block_sweep), the host (fot_host_loop.cpp) and
+// the tables of a sampler step whose slots share their crowds' samples (fot_loop_set_sampler_shared) and name their
+// models (fot_loop_set_sampler_models).
+// Plain C++ shared by the kernels (k_loop_best_sample_sweep, k_loop_rep_block_sweep, k_loop_model_rows), the host (fot_host_loop.cpp) and
 // tests/emu/fot_sweep_emu.cpp.  Every offset into the tensor counts points of two coordinates in 64 bits.
 #pragma once
 
@@ -127,6 +128,74 @@ inline CrowdShape sweep_crowd_tables(int32_t n_run, const int32_t *ep_ped0, cons
         }
     sh.identity = sh.identity && sh.crowd_rows == ep_ped0[n_run > 0 ? n_run : 0];
     return sh;
+}
+
+// ---- models: the slots of a sampler loop name their Social-GAN model (fot_loop_set_sampler_models) ----------------------------
+// slot_model [n_slots] names every slot's model, in [0, n_models).  A sampling UNIT is a (crowd, model) pair, active when
+// one of its running slots has pedestrians.  Model m's scenes are its active units in ascending crowd id, a scene's
+// pedestrians those of the unit's lowest running slot: sweep_crowd_tables over the running episodes that name m.
+
+struct ModelShape {
+    int32_t n_scenes = 0, rows = 0;          // what model m's generator is handed: its active units, their pedestrians
+};
+
+// One frame row's place among the models' raw tensors, model m's being [S][pred_len][rows_m][2] from element `base` of
+// their common pool: sample s, predictor step j of the row is element base + (s * pred_len + j) * width + col.
+struct ModelRow {
+    int64_t base;                            // first element (of two coordinates) of the row's model's tensor
+    int32_t width, col;                      // rows_m of that model | the row's column in it
+};
+static_assert(sizeof(ModelRow) == 16, "ModelRow is one 16-byte row");
+
+FOT_SW_HD inline int64_t sweep_model_src_elem(const ModelRow &r, int32_t pred_len, int32_t s, int32_t j)
+{
+    return r.base + ((int64_t)s * pred_len + j) * (int64_t)r.width + r.col;
+}
+
+// The tables of a frame of n_run running episodes (ep_ped0, ep_slot, slot_crowd as in sweep_crowd_tables).  Model m's
+// tables are sweep_crowd_tables' of the episodes that name it, at
+//   scene_off + m * (ep_stride + 1), scene_slot + m * ep_stride, scene_crowd + m * ep_stride, row_scene + m * row_stride
+// (ep_stride >= n_run, row_stride >= the frame's rows); shape [n_models].  For every row of the frame: row_model [rows]
+// its model and col [rows] its column in that model's tensor.  A model without an active unit has n_scenes = rows = 0.
+// With n_models = 1 the tables are sweep_crowd_tables' own.  Runs when the set of running slots changes, on the host only.
+inline void sweep_model_tables(int32_t n_run, const int32_t *ep_ped0, const int32_t *ep_slot, const int32_t *slot_crowd,
+                               const int32_t *slot_model, int32_t n_models, int32_t ep_stride, int32_t row_stride,
+                               ModelShape *shape, int32_t *scene_off, int32_t *row_scene, int32_t *scene_slot,
+                               int32_t *scene_crowd, int32_t *row_model, int32_t *col)
+{
+    std::vector<int32_t> sub, sub_ped0, sub_slot, sub_col;
+    for (int32_t m = 0; m < n_models; ++m) {
+        sub.clear(); sub_ped0.assign(1, 0); sub_slot.clear();
+        for (int32_t i = 0; i < n_run; ++i)
+            if (slot_model[ep_slot[i]] == m) {
+                sub.push_back(i);
+                sub_slot.push_back(ep_slot[i]);
+                sub_ped0.push_back(sub_ped0.back() + (ep_ped0[i + 1] - ep_ped0[i]));
+            }
+        sub_col.assign((size_t)sub_ped0.back(), 0);
+        const CrowdShape sh = sweep_crowd_tables((int32_t)sub.size(), sub_ped0.data(), sub_slot.data(), slot_crowd,
+                                                 scene_off + (size_t)m * ((size_t)ep_stride + 1), row_scene + (size_t)m * (size_t)row_stride,
+                                                 scene_slot + (size_t)m * (size_t)ep_stride, scene_crowd + (size_t)m * (size_t)ep_stride,
+                                                 sub_col.data());
+        shape[m].n_scenes = sh.n_scenes; shape[m].rows = sh.crowd_rows;
+        for (size_t k = 0; k < sub.size(); ++k) {
+            const int32_t i = sub[k];
+            for (int32_t row = ep_ped0[i]; row < ep_ped0[i + 1]; ++row) {
+                row_model[row] = m;
+                col[row] = sub_col[(size_t)(sub_ped0[k] + (row - ep_ped0[i]))];
+            }
+        }
+    }
+}
+
+// The gather table of the frame's rows: model m's tensor starts at element model_base[m] of the pool.
+inline void sweep_model_rows(int32_t rows, const int32_t *row_model, const int32_t *col, const ModelShape *shape,
+                             const int64_t *model_base, ModelRow *tab)
+{
+    for (int32_t r = 0; r < rows; ++r) {
+        const int32_t m = row_model[r];
+        tab[r].base = model_base[m]; tab[r].width = shape[m].rows; tab[r].col = col[r];
+    }
 }
 
 // Do the slots of every crowd replay the same pedestrians?  slot_ped0 [n_slots + 1], slot_frames [n_slots], pos the

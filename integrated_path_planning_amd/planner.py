@@ -580,13 +580,27 @@ class BatchPlanner:
 
     LOOP_SUMMARY_DT = np.dtype(_abi.LoopSummary)
 
-    def loop_set_sampler(self, num_samples: int, seed: int, kind: int = _abi.NOISE_GAUSSIAN, slot_crowd=None) -> None:
+    def loop_set_sampler(self, num_samples: int, seed: int, kind: int = _abi.NOISE_GAUSSIAN, slot_crowd=None, slot_model=None,
+                         model_kinds=None) -> None:
         """``fot_loop_set_sampler``: the resident loop predicts with the model of ``fot_sgan_load`` and the library's own
         counter-based noise (between ``loop_set_replay`` and the first ``loop_run``).
         slot_crowd (``fot_loop_set_sampler_shared``): one crowd id >= 0 per slot of the replay; the slots of a crowd replay
         the same pedestrians, the library samples every crowd once per lock step with noise keyed by the crowd's id and
-        all its slots plan against those samples."""
+        all its slots plan against those samples.
+        slot_model, model_kinds (``fot_loop_set_sampler_models``, with slot_crowd): the id of a loaded model
+        (``fot_sgan_load_model``) per slot and the noise kind of every model id 0 .. len(model_kinds) - 1; every active
+        (crowd, model) pair is sampled once per lock step and ``kind`` is not read."""
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if (slot_model is None) != (model_kinds is None) or (slot_model is not None and slot_crowd is None):
+            raise ValueError("loop_set_sampler: slot_model, model_kinds and slot_crowd go together")
+        if slot_model is not None:
+            crowd, model, kinds = (np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (slot_crowd, slot_model, model_kinds))
+            if not len(crowd) == len(model) == int(getattr(self, "_replay_slots", len(crowd))):
+                raise ValueError("loop_set_sampler: slot_crowd and slot_model name one crowd and one model per slot of the replay")
+            _abi.check(self._h, self._lib.fot_loop_set_sampler_models(
+                self._h, int(num_samples), seed, len(kinds), _addr(kinds) if len(kinds) else None,
+                int(crowd.max()) + 1 if len(crowd) else 1, _addr(crowd) if len(crowd) else None, _addr(model) if len(model) else None))
+            return
         if slot_crowd is None:
             _abi.check(self._h, self._lib.fot_loop_set_sampler(self._h, int(num_samples), seed, int(kind)))
             return
@@ -602,6 +616,14 @@ class BatchPlanner:
         n_scenes, n_rows = C.c_int32(-1), C.c_int32(-1)
         _abi.check(self._h, self._lib.fot_debug_loop_sampler_shape(self._h, C.addressof(n_scenes), C.addressof(n_rows)))
         return n_scenes.value, n_rows.value
+
+    def debug_loop_sampler_shapes(self, n_models: Optional[int] = None):
+        """``fot_debug_loop_sampler_shapes`` (tests): per model id 0 .. n_models - 1 (default: every id a handle holds) the
+        (scenes, pedestrian rows) the most recent lock step handed to that model; (0, 0) for one that launched nothing."""
+        cap = int(self._lib.fot_sgan_max_models()) if n_models is None else int(n_models)
+        n_scenes, n_rows = np.full(cap, -1, np.int32), np.full(cap, -1, np.int32)
+        _abi.check(self._h, self._lib.fot_debug_loop_sampler_shapes(self._h, cap, _addr(n_scenes), _addr(n_rows)))
+        return [(int(a), int(b)) for a, b in zip(n_scenes, n_rows)]
 
     def loop_set_samples(self, samples, first_step: int = 0, n_rec_cols: Optional[int] = None, slot_col0=None) -> None:
         """``fot_loop_set_samples``: the resident loop predicts from a recorded sample tensor ``[n_steps, S, pred_len,

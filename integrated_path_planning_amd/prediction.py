@@ -296,6 +296,38 @@ def crowd_scenes(slots, counts, steps, slot_crowd):
     return crowds, rep, crowds.copy(), (np.concatenate(cols) if cols else np.zeros(0, np.int64)).astype(np.int64)
 
 
+def model_scenes(slots, counts, steps, slot_crowd, slot_model):
+    """The sampler's calls for running episodes that share crowds and name their models (``SganSampler`` with several
+    weights, ``fot_loop_set_sampler_models``; csrc/fot_sweep.hpp's ``sweep_model_tables`` restated).  slots / counts / steps
+    as in ``crowd_scenes``; slot_crowd / slot_model: the crowd and the model of every slot of the loop.  A sampling unit is
+    a (crowd, model) pair; model m's scenes are ``crowd_scenes`` of the episodes that name m.
+
+    Returns ``(units, row_model, cols)``: for every model id 0 .. max(slot_model) its ``(crowds, rep, noise_slots)`` --
+    ``rep`` indexes ``slots`` of the whole frame, all three empty for a model without an active unit --; and for every
+    pedestrian row of the frame its model and its column among the rows of that model's representatives."""
+    slots, counts, steps = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (slots, counts, steps))
+    slot_crowd, slot_model = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (slot_crowd, slot_model))
+    if len(slot_crowd) != len(slot_model):
+        raise ValueError("model_scenes: one crowd and one model per slot")
+    if not len(slots) == len(counts) == len(steps):
+        raise ValueError("model_scenes: one pedestrian count and one step count per slot")
+    if len(slots) and (slots.min() < 0 or slots.max() >= len(slot_model)):
+        raise ValueError(f"model_scenes: slot_model names {len(slot_model)} slots, the frame has slot {int(slots.max())}")
+    if len(slot_model) and slot_model.min() < 0:
+        raise ValueError("model_scenes: slot_model holds one model id >= 0 per slot")
+    n_models = int(slot_model.max()) + 1 if len(slot_model) else 0
+    model_of = slot_model[slots]
+    row_model = np.repeat(model_of, counts)
+    cols = np.zeros(int(counts.sum()), np.int64)
+    units = []
+    for m in range(n_models):
+        idx = np.flatnonzero(model_of == m)
+        crowds, rep, noise_slots, sub_cols = crowd_scenes(slots[idx], counts[idx], steps[idx], slot_crowd)
+        units.append((crowds, idx[rep], noise_slots))
+        cols[row_model == m] = sub_cols
+    return units, row_model, cols
+
+
 class SganSampler:
     """The multi-sample predictor in front of the planner, in the library: ``sample(obs, ped_off)`` gives the raw samples
     [S, pred_len, sum P, 2] of every scene as a float32 ``torch`` device tensor -- what ``fot_loop_frame.dist_raw`` and
@@ -315,15 +347,36 @@ class SganSampler:
     ONCE per lock step, its noise keyed by the crowd's id in place of the slot, and all its slots are handed those samples
     (``fot_loop_set_sampler_shared`` in a resident loop; ``sample`` forms the same bytes for a stepwise one).  Crowd c
     draws what slot c of a loop without ``slot_crowd`` draws.
+    weights a sequence ``[w0, w1, ...]`` (with ``counter_seed``, ``slot_crowd`` and ``slot_model``): the handle holds several
+    models (``fot_sgan_load_model``) and slot e predicts with model ``slot_model[e]`` -- the 'sgan' and 'lstm' conditions of a
+    campaign cell in one loop.  Every active (crowd, model) pair is sampled once per lock step, the noise keyed by the
+    crowd's id with the model's own dimensions, mix type and ``noise_type`` (``fot_loop_set_sampler_models``; ``sample``
+    forms the same bytes through ``fot_sgan_sample_model``): a slot's numbers are those of the loop that holds only its model.
     engine None: the sampler joins the engine of the loop it is handed to (``bind``)."""
     needs_history = True
 
     def __init__(self, engine: Optional[BatchPlanner], weights: SganWeights, num_samples: int, seed: Optional[int] = None,
-                 noise_type: Optional[str] = None, counter_seed: Optional[int] = None, slot_crowd=None):
+                 noise_type: Optional[str] = None, counter_seed: Optional[int] = None, slot_crowd=None, slot_model=None):
         if noise_type is not None and noise_type not in _NOISE_TYPES:
             raise ValueError(f'Unrecognized noise type "{noise_type}"')
         if not 1 <= int(num_samples) <= _abi.MAX_SAMPLES:
             raise ValueError(f"SganSampler: 1 <= num_samples <= {_abi.MAX_SAMPLES}")
+        self.models = None if isinstance(weights, SganWeights) else list(weights)
+        if self.models is not None:
+            if not 1 <= len(self.models) <= int(_abi.lib().fot_sgan_max_models()):
+                raise ValueError(f"SganSampler: 1 .. {int(_abi.lib().fot_sgan_max_models())} models")
+            if counter_seed is None or slot_crowd is None or slot_model is None:
+                raise ValueError("SganSampler: several models need counter_seed, slot_crowd and slot_model")
+            if noise_type is not None:
+                raise ValueError("SganSampler: with several models noise_type is each model's own (SganWeights.noise_type)")
+            for w in self.models:
+                if w.noise_type not in _NOISE_TYPES:
+                    raise ValueError(f'Unrecognized noise type "{w.noise_type}"')
+                if (w.desc.obs_len, w.desc.pred_len) != (self.models[0].desc.obs_len, self.models[0].desc.pred_len):
+                    raise ValueError("SganSampler: the models of one loop share obs_len and pred_len")
+            weights = self.models[0]
+        elif slot_model is not None:
+            raise ValueError("SganSampler: slot_model names one of several models: weights is then a sequence")
         self.engine, self.weights, self.num_samples, self._noise_type = None, weights, int(num_samples), noise_type
         self.counter_seed = None if counter_seed is None else int(counter_seed) & 0xFFFFFFFFFFFFFFFF
         if slot_crowd is not None and counter_seed is None:
@@ -331,6 +384,12 @@ class SganSampler:
         self.slot_crowd = None if slot_crowd is None else np.asarray(slot_crowd, dtype=np.int64).reshape(-1)
         if self.slot_crowd is not None and len(self.slot_crowd) and self.slot_crowd.min() < 0:
             raise ValueError("SganSampler: slot_crowd holds one crowd id >= 0 per slot")
+        self.slot_model = None if slot_model is None else np.asarray(slot_model, dtype=np.int64).reshape(-1)
+        if self.slot_model is not None:
+            if len(self.slot_model) != len(self.slot_crowd):
+                raise ValueError("SganSampler: slot_model and slot_crowd hold one entry per slot")
+            if len(self.slot_model) and not 0 <= self.slot_model.min() <= self.slot_model.max() < len(self.models):
+                raise ValueError(f"SganSampler: slot_model holds one model id in 0 .. {len(self.models) - 1} per slot")
         self._seed = seed
         self._lib = _abi.lib()
         self.device = self.generator = None
@@ -348,7 +407,10 @@ class SganSampler:
         if self.engine is engine:
             return
         self.engine = engine
-        self.load(self.weights)
+        if self.models is None:
+            self.load(self.weights)
+        for m, w in enumerate(self.models or ()):
+            _abi.check(engine._h, self._lib.fot_sgan_load_model(engine._h, m, C.byref(w.desc), w.blob.size, w.blob.ctypes.data))
         dev = int(getattr(engine, "device", -1))                    # (fot_create's device < 0: the current one)
         self.device = torch.device("cuda", torch.cuda.current_device() if dev < 0 else dev)
         self.generator = torch.Generator(device=self.device)
@@ -361,6 +423,8 @@ class SganSampler:
 
     def load(self, weights: SganWeights) -> None:
         """Replace the handle's model."""
+        if self.models is not None:
+            raise ValueError("SganSampler: a sampler of several models loads them when it joins its engine")
         if self._noise_type is None and weights.noise_type not in _NOISE_TYPES:
             raise ValueError(f'Unrecognized noise type "{weights.noise_type}"')
         _abi.check(self.engine._h, self._lib.fot_sgan_load(self.engine._h, C.byref(weights.desc), weights.blob.size,
@@ -381,14 +445,27 @@ class SganSampler:
         """The ``fot_sgan_noise`` kind that stands for ``noise_type``."""
         return _abi.NOISE_GAUSSIAN if self.noise_type == "gaussian" else _abi.NOISE_UNIFORM_SYM
 
-    def counter_noise(self, slots, steps, counts, kind: Optional[int] = None):
+    @property
+    def model_kinds(self):
+        """Several models: the ``fot_sgan_noise`` kind of every model's own ``noise_type``; otherwise None."""
+        if self.models is None:
+            return None
+        return [_abi.NOISE_GAUSSIAN if w.noise_type == "gaussian" else _abi.NOISE_UNIFORM_SYM for w in self.models]
+
+    def _desc(self, model):
+        return self.weights.desc if model is None else self.models[model].desc
+
+    def counter_noise(self, slots, steps, counts, kind: Optional[int] = None, model: Optional[int] = None):
         """The counter mode's noise of the scenes ``slots`` (pedestrian counts ``counts``) at their step counts ``steps``,
         from ``fot_sgan_noise`` as a device tensor [S, rows, noise_dim] -- exactly what a resident loop with this seed
-        uses for those slots at those steps, whatever else runs beside them."""
+        uses for those slots at those steps, whatever else runs beside them.  model: of several models, the one whose
+        dimensions, mix type and kind apply (``slots`` are then crowd ids)."""
         import torch
         if self.counter_seed is None:
             raise ValueError("SganSampler: counter_noise needs counter_seed")
-        d = self.weights.desc
+        d = self._desc(model)
+        if kind is None:
+            kind = self.noise_kind if model is None else self.model_kinds[model]
         slots, steps, counts = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (slots, steps, counts))
         if not len(slots) == len(steps) == len(counts):
             raise ValueError("SganSampler: one step and one pedestrian count per slot")
@@ -400,14 +477,19 @@ class SganSampler:
         dtype = torch.int32 if kind == _abi.NOISE_RAW else torch.float32    # (raw words: their bits, as int32)
         out = torch.empty((self.num_samples, len(row_slot), d.noise_dim), device=self.device, dtype=dtype)
         torch.cuda.current_stream(self.device).synchronize()        # (the library writes it on its own stream)
-        return self.engine.sgan_noise(self.counter_seed, self.noise_kind if kind is None else kind, self.num_samples,
+        return self.engine.sgan_noise(self.counter_seed, kind, self.num_samples,
                                       d.noise_dim, row_slot, row_step, row_idx, out=out)
 
-    def sample(self, obs, ped_off, noise=None, slots=None, steps=None):
+    def sample(self, obs, ped_off, noise=None, slots=None, steps=None, model: Optional[int] = None):
         """obs [obs_len, sum P, 2] absolute positions (NumPy, or a float32 torch device tensor); ped_off [n_scenes + 1];
-        slots / steps (counter mode, without ``noise``): the slot and step count of every scene."""
+        slots / steps (counter mode, without ``noise``): the slot and step count of every scene.  model (several models,
+        with ``noise``): the scenes go through that model alone, ``fot_sgan_sample_model``."""
         import torch
-        d = self.weights.desc
+        if self.models is not None and (noise is None) != (model is None):
+            raise ValueError("SganSampler: several models sample by slots and steps, or one `model` under a given `noise`")
+        if self.models is None and model is not None:
+            raise ValueError("SganSampler: `model` names one of several models")
+        d = self._desc(model)
         off = np.ascontiguousarray(ped_off, dtype=np.int32)
         n_scenes, n = len(off) - 1, int(off[-1])
         if hasattr(obs, "data_ptr"):
@@ -416,6 +498,32 @@ class SganSampler:
             obs_t = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32)).to(self.device)
         if tuple(obs_t.shape) != (d.obs_len, n, 2):
             raise ValueError(f"SganSampler: obs is [obs_len = {d.obs_len}, sum P = {n}, 2], got {tuple(obs_t.shape)}")
+        if noise is None and self.models is not None:
+            # one sampling per active (crowd, model) unit, model by model in ascending id, then every asked slot's columns
+            # out of its model's tensor -- the bytes a resident loop forms (fot_loop_set_sampler_models)
+            if slots is None or steps is None:
+                raise ValueError("SganSampler: the counter mode needs every scene's slot and step count (slots, steps)")
+            counts = np.diff(off).astype(np.int64)
+            steps = np.asarray(steps, dtype=np.int64).reshape(-1)
+            slots = np.asarray(slots, dtype=np.int64).reshape(-1)
+            units, row_model, cols = model_scenes(slots, counts, steps, self.slot_crowd, self.slot_model)
+            out = torch.empty((self.num_samples, d.pred_len, n, 2), device=self.device, dtype=torch.float32)
+            for m, (crowds, rep, noise_slots) in enumerate(units):
+                rep_of = dict(zip(crowds.tolist(), rep.tolist()))
+                for i in np.flatnonzero(self.slot_model[slots] == m).tolist():
+                    j = rep_of.get(int(self.slot_crowd[slots[i]]), i)
+                    if counts[i] > 0 and j != i and not torch.equal(obs_t[:, off[i]:off[i + 1]], obs_t[:, off[j]:off[j + 1]]):
+                        raise ValueError(f"SganSampler: the slots of crowd {int(self.slot_crowd[slots[i]])} do not observe the "
+                                         f"same window (scenes {j} and {i})")
+                if len(rep) == 0:                                     # (no active unit: the model is not called)
+                    continue
+                rows = np.concatenate([np.arange(off[j], off[j + 1]) for j in rep]).astype(np.int64)
+                rep_obs = obs_t.index_select(1, torch.as_tensor(rows, device=self.device)).contiguous()
+                rep_off = np.concatenate([[0], np.cumsum(counts[rep])]).astype(np.int32)
+                raw = self._sample_scenes(rep_obs, rep_off, self.counter_noise(noise_slots, steps[rep], counts[rep], model=m), model=m)
+                mine = np.flatnonzero(row_model == m)
+                out[:, :, torch.as_tensor(mine, device=self.device)] = raw.index_select(2, torch.as_tensor(cols[mine], device=self.device))
+            return out
         if noise is None and self.slot_crowd is not None:
             # one sampling per active crowd: its representative's window under the crowd's noise, then every asked slot's
             # columns out of the crowds' tensor -- the bytes a resident loop forms (fot_loop_set_sampler_shared)
@@ -448,19 +556,22 @@ class SganSampler:
             rows = n_scenes if d.noise_mix_type == _abi.SGAN_NOISE_GLOBAL else n
             if tuple(noise_t.shape) != (self.num_samples, rows, d.noise_dim):
                 raise ValueError(f"SganSampler: noise is [S, rows, noise_dim] = {(self.num_samples, rows, d.noise_dim)}")
-        return self._sample_scenes(obs_t, off, noise_t)
+        return self._sample_scenes(obs_t, off, noise_t, model=model)
 
-    def _sample_scenes(self, obs_t, off, noise_t):
-        """``fot_sgan_sample`` of the scenes ``off`` on device tensors."""
+    def _sample_scenes(self, obs_t, off, noise_t, model: Optional[int] = None):
+        """``fot_sgan_sample`` (``fot_sgan_sample_model`` of ``model``) of the scenes ``off`` on device tensors."""
         import torch
-        d = self.weights.desc
+        d = self._desc(model)
         n_scenes, n = len(off) - 1, int(off[-1])
         out = torch.empty((self.num_samples, d.pred_len, n, 2), device=self.device, dtype=torch.float32)
         torch.cuda.current_stream(self.device).synchronize()        # (the library reads the tensors on its own stream)
-        _abi.check(self.engine._h, self._lib.fot_sgan_sample(
-            self.engine._h, n_scenes, off.ctypes.data, C.c_void_p(obs_t.data_ptr()), self.num_samples,
-            C.c_void_p(noise_t.data_ptr()) if noise_t.numel() else None,
-            _abi.OUT_DEVICE | _abi.SGAN_OBS_DEVICE | _abi.SGAN_NOISE_DEVICE, C.c_void_p(out.data_ptr()), None))
+        args = (n_scenes, off.ctypes.data, C.c_void_p(obs_t.data_ptr()), self.num_samples,
+                C.c_void_p(noise_t.data_ptr()) if noise_t.numel() else None,
+                _abi.OUT_DEVICE | _abi.SGAN_OBS_DEVICE | _abi.SGAN_NOISE_DEVICE, C.c_void_p(out.data_ptr()), None)
+        if model is None:
+            _abi.check(self.engine._h, self._lib.fot_sgan_sample(self.engine._h, *args))
+        else:
+            _abi.check(self.engine._h, self._lib.fot_sgan_sample_model(self.engine._h, int(model), *args))
         self.last_noise, self.last_obs, self.last_ped_off = noise_t, obs_t, off
         return out
 
