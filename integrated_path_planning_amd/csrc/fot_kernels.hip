@@ -2,7 +2,8 @@
 //
 // Pipeline of one fot_plan_batch (one launch each over the whole batch; every decision in float64):
 //   k_frenet_state : 4 waves / instance: pulls the instance's descriptor out of the pinned staging block, nearest point
-//                    (sample scan over the workgroup, three refinement rounds per evaluation) + Cartesian->Frenet
+//                    (sample scan over the workgroup, three refinement rounds per evaluation) + Cartesian->Frenet;
+//                    behind the last scan ONE wave goes on (refinement, state, group headers), the other three end
 //   k_cull         : 8 waves / (instance, 8 consecutive time steps): derives and merges the boxes of the instance's
 //                    longitudinal profiles, sorts the obstacles of those time rows that lie inside the grown boxes
 //                    into per-step entry lists (strips, LDS atomics), writes each candidate wave's chunk range
@@ -18,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <cstring>
 
 #include "fot_math.hpp"
 #include "fot_kernels.h"
@@ -248,6 +250,19 @@ __device__ __forceinline__ void scan_nan_tracks(const InstDesc &D, const T *__re
     }
 }
 
+// A condition every lane of the wave holds alike, as a scalar: the branch on it is a jump, not a lane mask (a wave that
+// leaves under it is gone as a whole)
+__device__ __forceinline__ bool wave_uniform(bool c) { return __builtin_amdgcn_readfirstlane((int)c) != 0; }
+
+// The wave ends HERE, inside whatever loop or branch: a `return` out of a loop the compiler holds for divergent only
+// clears the lanes' bits and walks on to the loop's exit.  Kernel-level code only (nothing to unwind on the device).
+__device__ __forceinline__ void end_wave()
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_endpgm();
+#endif
+}
+
 // arg-min of a sample scan over the whole workgroup (lowest index wins ties); every thread gets the result
 __device__ __forceinline__ ScanBest block_argmin(ScanBest b, ScanBest *s_best)
 {
@@ -260,13 +275,18 @@ __device__ __forceinline__ ScanBest block_argmin(ScanBest b, ScanBest *s_best)
     return r;
 }
 
-// One workgroup (4 waves) per instance: the sample scans are spread over all threads, the refinement and the Frenet
-// state are uniform values every wave computes alike.  `block` is the workgroup's role: an instance, or (behind the
-// instances) one part of the NaN scan of an instance's tensor.  `sp`: the reference path, staged by the caller.
+// One workgroup (4 waves) per instance: the sample scans are spread over all threads; the refinement, the Frenet state
+// and the tail are uniform values, which wave 0 ALONE computes for an instance that heads no chain: waves 1 - 3 end
+// behind the last block-wide scan of the search (a terminated wave gives its registers back to the evaluation waves of
+// the calls in flight beside it; the workgroup's LDS, the staged path included, stays until wave 0 ends), and no
+// barrier is reachable for such a block from there on.  The head of a chain keeps its four waves throughout (a barrier
+// and a scan per member), as does every block under all_waves (FOT_FRENET_WAVES=all: tests, A/B runs).  `block` is the
+// workgroup's role: an instance, or (behind the instances) one part of the NaN scan of an instance's tensor.  `sp`: the
+// reference path, staged by the caller.
 __device__ __forceinline__ void frenet_state_block(const DevParams *__restrict__ Pp, const SplineView &sp, const InstDesc *desc,
                                                    InstState *__restrict__ state, int n_inst, const MetaImport &imp,
                                                    const NanScan &scan, int32_t *__restrict__ inst_done, int block,
-                                                   const GroupHeadOut &gh)
+                                                   const GroupHeadOut &gh, int all_waves)
 {
     __shared__ ScanBest s_best[FRENET_WG / WAVE];
     __shared__ InstDesc s_desc;                                   // the descriptor being worked on, read once
@@ -310,7 +330,11 @@ __device__ __forceinline__ void frenet_state_block(const DevParams *__restrict__
     const int n_glob = global_search_count(sp);
     double carry_prev_s = 0.0;                                 // new_prev_s of the previous member of the chain
     bool chained = false;
-    const int n_members = 1 + s_desc.n_chained;
+    const int n_members = 1 + __builtin_amdgcn_readfirstlane(s_desc.n_chained);   // (a scalar: the loop is no lane mask)
+    // one wave behind the search (the wave's number as a scalar: a jump decides who leaves, not a lane mask)
+    const bool solo = n_members == 1 && !all_waves;
+    const bool leaves = solo && __builtin_amdgcn_readfirstlane(tid / WAVE) != 0;
+    const int n_thr = solo ? WAVE : FRENET_WG;                  // threads behind the search (solo: tid < WAVE there)
     for (int m = 0; m < n_members; ++m, ++inst) {
         if (m > 0) {                                           // next member of the chain: its descriptor
             __syncthreads();
@@ -320,13 +344,16 @@ __device__ __forceinline__ void frenet_state_block(const DevParams *__restrict__
         }
         const InstDesc &D = s_desc;
         const double x = D.ego.x, y = D.ego.y;
-        const bool has_prev = chained ? true : D.ego.has_prev_s != 0;
+        // (the branches of the search on scalars: what the waves that leave it jump on must not hang on a lane mask)
+        const int ego_form = __builtin_amdgcn_readfirstlane(D.ego.has_prev_s);
+        const bool has_prev = chained ? true : ego_form != 0;
         const double prev_s = chained ? carry_prev_s : D.ego.prev_s;
 
         double best_s = 0.0;
         bool need_global = true;
-        const bool given = D.ego.has_prev_s == FOT_EGO_IS_FRENET;  // the Frenet state itself: nothing to search
+        const bool given = ego_form == FOT_EGO_IS_FRENET;          // the Frenet state itself: nothing to search
         if (given) need_global = false;
+        if (leaves && given) end_wave();
         if (has_prev && !given) {                              // cached window +-10 m, 100 samples
             const double s_min = fmax(0.0, prev_s - 10.0);
             const double s_max = fmin(s_end, prev_s + 10.0);
@@ -334,10 +361,12 @@ __device__ __forceinline__ void frenet_state_block(const DevParams *__restrict__
             best_s = b.idx >= 0 ? linspace_at(s_min, s_max, 100, b.idx) : 0.0;
             const bool at_lower = fabs(best_s - s_min) < 1e-3 && s_min > 0.0;
             const bool at_upper = fabs(best_s - s_max) < 1e-3 && s_max < s_end;
-            need_global = at_lower || at_upper;
+            need_global = wave_uniform(at_lower || at_upper);
+            if (leaves && !need_global) end_wave();
         }
         if (need_global) {
             ScanBest b = block_argmin(scan_samples(sp, x, y, 0.0, s_end, n_glob, tid, FRENET_WG, true), s_best);
+            if (leaves) end_wave();
             best_s = linspace_at(0.0, s_end, n_glob, b.idx >= 0 ? b.idx : 0);
         }
         if (!given) best_s = refine_nearest_wave(sp, x, y, best_s, lane);
@@ -349,7 +378,10 @@ __device__ __forceinline__ void frenet_state_block(const DevParams *__restrict__
             double px, py;
             spline_xy(sp, best_s, px, py);
             if (isnan(px) || isnan(py)) {                     // coordinate_converter.py:289-295
-                ScanBest b = block_argmin(scan_samples(sp, x, y, 0.0, s_end, n_glob, tid, FRENET_WG, true), s_best);
+                // (solo: the one wave scans alone -- the arg-min takes the lowest index among equal distances, whoever
+                // evaluated which sample, so the entry is the four waves' one)
+                ScanBest b = scan_samples(sp, x, y, 0.0, s_end, n_glob, tid, n_thr, true);
+                b = solo ? wave_argmin(b) : block_argmin(b, s_best);
                 best_s = linspace_at(0.0, s_end, n_glob, b.idx >= 0 ? b.idx : 0);
                 ok = frenet_state_at(sp, D.ego, best_s, fr, ref);
             }
@@ -371,10 +403,27 @@ __device__ __forceinline__ void frenet_state_block(const DevParams *__restrict__
         // summary of its profile.  Every position of the batch gets at least its `present` word: the table outlives the call.
         if (gh.heads) {
             const int variant = nb > 0 ? HEAD_VARIANT_BRAKE : HEAD_VARIANT_GRID;
-            for (int t = tid; t < gh.n_pos * GROUP_MAX_PROFILES; t += FRENET_WG) {
-                const int pos = t / GROUP_MAX_PROFILES, p = t - pos * GROUP_MAX_PROFILES;
-                group_head_compose(P, D, fr, ok ? 1 : 0, gh.tmpl[head_template_index(D, variant, gh.tmpl_entries, pos)], p,
-                                   gh.heads[(int64_t)inst * gh.n_pos + pos]);
+            // Item t of the loop `t = tid; t += n_thr`, HEAD_PASSES of a thread's items at a time: the shares of all of
+            // them are fetched before the first header is written (the one wave has three passes over the bench lattice's
+            // 144 items where four waves have one; a pass's loads would wait behind the stores of the pass before).
+            constexpr int HEAD_PASSES = 3;
+            const int n_items = gh.n_pos * GROUP_MAX_PROFILES;
+            for (int t0 = tid; t0 < n_items; t0 += HEAD_PASSES * n_thr) {
+                HeadShare share[HEAD_PASSES];
+#pragma unroll
+                for (int u = 0; u < HEAD_PASSES; ++u) {
+                    const int t = t0 + u * n_thr;
+                    if (t >= n_items) break;
+                    const int pos = t / GROUP_MAX_PROFILES, p = t - pos * GROUP_MAX_PROFILES;
+                    group_head_fetch(gh.tmpl[head_template_index(D, variant, gh.tmpl_entries, pos)], p, share[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < HEAD_PASSES; ++u) {
+                    const int t = t0 + u * n_thr;
+                    if (t >= n_items) break;
+                    const int pos = t / GROUP_MAX_PROFILES, p = t - pos * GROUP_MAX_PROFILES;
+                    group_head_put(P, D, fr, ok ? 1 : 0, share[u], p, gh.heads[(int64_t)inst * gh.n_pos + pos]);
+                }
             }
         }
         carry_prev_s = new_prev_s;
@@ -385,7 +434,7 @@ __device__ __forceinline__ void frenet_state_block(const DevParams *__restrict__
 __global__ void __launch_bounds__(FRENET_WG)
 k_frenet_state(const DevParams *__restrict__ Pp, SplineView sp_hbm, const SplineView *__restrict__ sp_table, int mixed,
                int lds_knots, const InstDesc *desc, InstState *__restrict__ state, int n_inst, MetaImport imp,
-               NanScan scan, int32_t *__restrict__ inst_done, GroupHeadOut gh)
+               NanScan scan, int32_t *__restrict__ inst_done, GroupHeadOut gh, int all_waves)
 {
     SplineView sp = sp_hbm;
     if ((int)blockIdx.x < n_inst) {                              // (the scan blocks never look at the path)
@@ -396,7 +445,7 @@ k_frenet_state(const DevParams *__restrict__ Pp, SplineView sp_hbm, const Spline
         }
         sp = stage_spline(sp_hbm, lds_knots);
     }
-    frenet_state_block(Pp, sp, desc, state, n_inst, imp, scan, inst_done, (int)blockIdx.x, gh);
+    frenet_state_block(Pp, sp, desc, state, n_inst, imp, scan, inst_done, (int)blockIdx.x, gh, all_waves);
 }
 
 // ---------------------------------------------------------------------------
@@ -1955,8 +2004,10 @@ int launch_frenet_state(const DevParams *P, const PathSet &ps, const InstDesc *d
     const int lds_knots = ps.fit_knots(SPLINE_LDS_KNOTS);
     const int64_t grid = (int64_t)n_inst * (1 + (scan.flag ? scan.blocks_per_inst : 0));
     if (grid > 0x7fffffffLL) return (int)hipErrorInvalidConfiguration;
+    // FOT_FRENET_WAVES=all: every nearest-point block keeps its four waves to its end (tests, A/B runs)
+    static const int all_waves = getenv("FOT_FRENET_WAVES") && !std::strcmp(getenv("FOT_FRENET_WAVES"), "all") ? 1 : 0;
     k_frenet_state<<<(unsigned)grid, FRENET_WG, sizeof(double) * 9 * (size_t)lds_knots, st>>>(
-        P, ps.one, ps.table, ps.mixed, lds_knots, desc, state, n_inst, imp, scan, inst_done, gh);
+        P, ps.one, ps.table, ps.mixed, lds_knots, desc, state, n_inst, imp, scan, inst_done, gh, all_waves);
     FOT_LAUNCH_CHECK();
     return 0;
 }

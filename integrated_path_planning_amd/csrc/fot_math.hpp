@@ -277,6 +277,18 @@ FOT_HD double refine_nearest(const SplineView &sp, double x, double y, double be
     return best_s;
 }
 
+// The arc tangent as a real function on the device, like yaw_step_over_cap (below) and for the same reason: inlined into
+// a loop, its nineteen coefficients are hoisted in front of the loop and live across it.  Two callers: the yaw of the
+// selected path's samples (final_sample: the selection runs behind the evaluation kernels' time-step loop), and the
+// heading of the reference point (frenet_state_at / _given: k_frenet_state's loop over the members of a chain held them
+// across the whole nearest-point search, 207 vector registers instead of 166).
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __attribute__((noinline))
+#else
+inline
+#endif
+double yaw_from_sin_cos(double sn, double cs) { return atan2(sn, cs); }
+
 // reference point at rs + Cartesian->Frenet of the ego
 // (coordinate_converter.py:285-308, :26-88; frenet_planner.py:362-371).  false = the reference raises.
 FOT_HD bool frenet_state_at(const SplineView &sp, const fot_ego &ego, double rs, double *fr, double *ref)
@@ -286,7 +298,7 @@ FOT_HD bool frenet_state_at(const SplineView &sp, const fot_ego &ego, double rs,
     if (isnan(p.x) || isnan(p.y)) return false;
     double cos_r, sin_r, rkappa, rdkappa;
     spline_frame(p, cos_r, sin_r, rkappa, rdkappa);
-    const double rtheta = atan2(p.dy, p.dx);
+    const double rtheta = yaw_from_sin_cos(p.dy, p.dx);
     if (isnan(rtheta) || isnan(rkappa) || isnan(rdkappa)) return false;
     ref[0] = rs; ref[1] = p.x; ref[2] = p.y; ref[3] = rtheta; ref[4] = rkappa; ref[5] = rdkappa;
 
@@ -320,7 +332,7 @@ FOT_HD bool frenet_state_given(const SplineView &sp, const fot_ego &ego, double 
     if (isnan(p.x) || isnan(p.y)) return false;
     double cos_r, sin_r, rkappa, rdkappa;
     spline_frame(p, cos_r, sin_r, rkappa, rdkappa);
-    ref[0] = fr[0]; ref[1] = p.x; ref[2] = p.y; ref[3] = atan2(p.dy, p.dx); ref[4] = rkappa; ref[5] = rdkappa;
+    ref[0] = fr[0]; ref[1] = p.x; ref[2] = p.y; ref[3] = yaw_from_sin_cos(p.dy, p.dx); ref[4] = rkappa; ref[5] = rdkappa;
     return !(isnan(ref[3]) || isnan(rkappa) || isnan(rdkappa));
 }
 
@@ -1598,23 +1610,55 @@ FOT_HD void group_head_profile_at(const DevParams &P, const InstDesc &D, const d
 // Lane p (0 .. GROUP_MAX_PROFILES - 1) of a position's share of composing its header from the template T of the instance's
 // lattice shape, variant and position; all lanes together write what build_group_head writes.  c2f_ok == 0: no Frenet
 // state -- a group that exists is EMPTY then.
-FOT_HD void group_head_compose(const DevParams &P, const InstDesc &D, const double *fr, int c2f_ok, const HeadTemplate &T,
-                               int p, GroupHead &H)
+// In two steps: what lane p reads of the template (HeadShare: all of it loads, none depends on another), and the
+// header written from it -- a caller with several headers per lane (k_frenet_state's one-wave tail) fetches the shares
+// of all of them before it writes the first, so that their loads are in flight together instead of one pass's behind
+// the stores of the pass before.
+constexpr int HEAD_SHARE_WORDS = (HEAD_COMMON_DWORDS + GROUP_MAX_PROFILES - 1) / GROUP_MAX_PROFILES;
+struct HeadShare {
+    int32_t kind, grp_tile0;
+    uint32_t word[HEAD_SHARE_WORDS];         // common[p + i * GROUP_MAX_PROFILES] (0 behind the block's end)
+    HeadProfile prof;
+};
+
+FOT_HD void group_head_fetch(const HeadTemplate &T, int p, HeadShare &S)
 {
-    int32_t kind = (int32_t)T.common[0];
+    S.kind = (int32_t)T.common[0];
+    S.grp_tile0 = (int32_t)T.common[1];
+    for (int i = 0; i < HEAD_SHARE_WORDS; ++i) {
+        const int w = p + i * GROUP_MAX_PROFILES;
+        S.word[i] = w < HEAD_COMMON_DWORDS ? T.common[w] : 0u;
+    }
+    S.prof = T.prof[p];
+}
+
+FOT_HD void group_head_put(const DevParams &P, const InstDesc &D, const double *fr, int c2f_ok, const HeadShare &S, int p,
+                           GroupHead &H)
+{
+    int32_t kind = S.kind;
     if (!c2f_ok && kind == GROUP_HEAD_FULL) kind = GROUP_HEAD_EMPTY;
     if (kind != GROUP_HEAD_FULL) {
         if (p == 0) {
             H.present = kind;
-            if (kind == GROUP_HEAD_EMPTY) H.grp_tile0 = (int32_t)T.common[1];
+            if (kind == GROUP_HEAD_EMPTY) H.grp_tile0 = S.grp_tile0;
         }
         return;
     }
     uint32_t *dst = (uint32_t *)(void *)&H;
-    for (int w = p; w < HEAD_COMMON_DWORDS; w += GROUP_MAX_PROFILES)
-        if (!head_instance_dword(w)) dst[w] = T.common[w];
+    for (int i = 0; i < HEAD_SHARE_WORDS; ++i) {
+        const int w = p + i * GROUP_MAX_PROFILES;
+        if (w < HEAD_COMMON_DWORDS && !head_instance_dword(w)) dst[w] = S.word[i];
+    }
     if (p == 0) group_head_instance(D, fr, H);
-    group_head_profile_at(P, D, fr, T.prof[p], H.info[p]);
+    group_head_profile_at(P, D, fr, S.prof, H.info[p]);
+}
+
+FOT_HD void group_head_compose(const DevParams &P, const InstDesc &D, const double *fr, int c2f_ok, const HeadTemplate &T,
+                               int p, GroupHead &H)
+{
+    HeadShare S;
+    group_head_fetch(T, p, S);
+    group_head_put(P, D, fr, c2f_ok, S, p, H);
 }
 
 // Index of the template of position `pos` of an instance in the handle's table: [variant][n_entries], one entry per group of
@@ -1636,16 +1680,6 @@ FOT_HD void build_group_head(const DevParams &P, const InstDesc &D, const double
     for (int t = 0; t < GROUP_TILES; ++t) group_head_tile(P, D, fr, n_cand, tile_cand0, tile_n, G, t, H);
     for (int p = 0; p < GROUP_MAX_PROFILES; ++p) group_head_profile(P, D, fr, G, p, H);
 }
-
-// yaw of the selected path's samples.  A real function on the device, like yaw_step_over_cap and for the same reason:
-// inlined behind the evaluation kernels' time-step loop (the selection runs there), the arc tangent's constants are
-// hoisted in front of the loop and live across it.
-#if defined(__HIP_DEVICE_COMPILE__)
-__device__ __attribute__((noinline))
-#else
-inline
-#endif
-double yaw_from_sin_cos(double sn, double cs) { return atan2(sn, cs); }
 
 // the 15 FrenetPath values of sample k of one candidate (data_structures.py:164-178 order)
 template <class Tab>

@@ -17,9 +17,16 @@ no such instruction exists:
   * the kernels must not use scratch memory or spill vector registers (a 128-VGPR build that spilled faulted on the
     GPU in round 2: gpurun_out/timeline3.log; whatever the mechanism, a spilling evaluation kernel is not shipped).
 
-Usage: isa_check_async.py <file.s> [--allow-scratch] [--min-kernels N]      exit status 1 = at least one finding
-(or fewer than N evaluation kernels in the file; default 3, csrc/Makefile asks for the 6 the library ships: k_evaluate,
-k_evaluate_split, k_evaluate_group and the lean form of each).
+  * with `--max-vgpr KERNEL=N` (any number of times): kernel KERNEL must be in the file, use at most N vector registers
+    and no scratch memory.  csrc/Makefile asks for k_frenet_state=176: four evaluation waves of 112 registers fill a SIMD's
+    512 but for 64, so a wave of that kernel starts on a SIMD once ONE evaluation wave has left it only up to 176
+    (two up to 288).  With four plan calls in flight the next call's k_frenet_state starts between the evaluation waves
+    of the calls before; at 207 registers it waited for two of them per SIMD and the step was 4 - 5 us longer
+    (profiles/r25_frenet_waves_ab.txt).
+
+Usage: isa_check_async.py <file.s> [--allow-scratch] [--min-kernels N] [--max-vgpr KERNEL=N ...]
+exit status 1 = at least one finding (or fewer than N evaluation kernels in the file; default 3, csrc/Makefile asks for
+the 6 the library ships: k_evaluate, k_evaluate_split, k_evaluate_group and the lean form of each).
 """
 import re
 import sys
@@ -222,6 +229,21 @@ def main(argv):
         if not allow_scratch and (md.get('vspill', 0) or md.get('scratch', 0)):
             print(f"   {m.group(1)} spills vector registers / uses scratch memory: not a build to ship")
             bad_total += 1
+    for k, a in enumerate(argv):                                 # register ceilings of other kernels
+        if a != '--max-vgpr' or k + 1 >= len(argv):
+            continue
+        kernel, _, limit = argv[k + 1].partition('=')
+        found = [f for f in meta if re.match(r'_ZN3fot\d+' + re.escape(kernel) + r'(E|I)', f)]
+        if not found:
+            print(f"{kernel}: not in {path}")
+            bad_total += 1
+        for f in found:
+            md = meta[f]
+            over = md['vgpr'] > int(limit)
+            print(f"{kernel}: vgpr {md['vgpr']} of at most {limit}, vgpr spills {md['vspill']}, scratch {md['scratch']} B"
+                  + (" -- over its register ceiling" if over else ""))
+            if over or md['vspill'] or md['scratch']:
+                bad_total += 1
     if n_kernels < min_kernels:                                  # k_evaluate, _split, _group
         print(f"only {n_kernels} evaluation kernels found in {path}")
         bad_total += 1
