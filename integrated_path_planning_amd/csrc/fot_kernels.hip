@@ -52,6 +52,40 @@ __device__ __forceinline__ float dpp_f32(float v)
 FOT_WAVE_REDUCE_F32(wave_min_f32, fminf)
 FOT_WAVE_REDUCE_F32(wave_max_f32, fmaxf)
 
+// The same reductions for values that are never NaN (k_cull's boxes: finite or +-inf), one instruction a step.  From the
+// source form above the compiler makes four a step: fminf's operands are canonicalised first, which keeps the DPP
+// read out of the min itself.  v_min_f32 / v_max_f32 order -0 below +0 and return an operand unchanged, as fminf and
+// fmaxf compile here, so the results are the same bits.  The statement pads its own hazards (a VALU result read through DPP: two
+// wait states); rows a step masks and lanes without a source are not written, i.e. keep their value, as above.
+#define FOT_WAVE_REDUCE_F32_ASM(NAME, OP)                                                    \
+    __device__ __forceinline__ float NAME(float v)                                           \
+    {                                                                                        \
+        asm("s_nop 1\n\t"                                                                    \
+            OP " %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"   \
+            OP " %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"   \
+            OP " %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"       \
+            OP " %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"            \
+            OP " %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\ts_nop 1\n\t"          \
+            OP " %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\ts_nop 1"              \
+            : "+v"(v));                                                                      \
+        return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));             \
+    }
+FOT_WAVE_REDUCE_F32_ASM(wave_min_nonan_f32, "v_min_f32_dpp")
+FOT_WAVE_REDUCE_F32_ASM(wave_max_nonan_f32, "v_max_f32_dpp")
+
+// inclusive prefix sum over the wave's lanes on the DPP data path: shifts inside the rows of 16, then the last lane of
+// a row to the rows behind it (row_bcast15 -> rows 1 and 3, row_bcast31 -> rows 2 and 3); a lane without a source adds 0
+__device__ __forceinline__ int wave_prefix_sum_i32(int v)
+{
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast15
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast31
+    return v;
+}
+
 // ---------------------------------------------------------------------------
 // ego -> Frenet state
 // ---------------------------------------------------------------------------
@@ -1483,6 +1517,14 @@ cull_group(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, 
     const int n_dyn = dyn_on ? D.S * D.P : 0;
     const int total = D.n_static + n_dyn;
     const bool tmajor = D.dyn_tmajor != 0;                       // [T][S][P][2] instead of the caller's [S][P][T][2]
+    // The instance's prediction tensor is a wave-uniform base plus per-lane byte offsets, and these fit 32 bits unless
+    // the tensor reaches 2 GiB (2^20 obstacles x 128 steps of float64 do): an address is then one 32-bit add and a
+    // load with a scalar base, not 64-bit multiply-adds and selects.  Larger tensors keep the 64-bit forms.
+    const char *dyn_base = (const char *)(dyn_xy + 2 * D.dyn_off);
+    const bool off32 = offsets_fit32((int64_t)n_dyn * D.T * (int64_t)sizeof(Raw));
+    auto dyn_offset = [&](int j, int row) {                      // (off32) byte offset of track j's sample at `row`
+        return (uint32_t)(tmajor ? row * n_dyn + j : j * D.T + row) * (uint32_t)sizeof(Raw);
+    };
 
     // Pass-1 lane roles.  Caller layout: lane = (obstacle slot, step) -- the KG lanes of one obstacle read its KG
     // consecutive samples, a contiguous run of the [S][P][T][2] tensor (32 bytes at KG = 4, float32), so a wave-wide load touches 64 / KG such runs
@@ -1499,7 +1541,8 @@ cull_group(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, 
         const int ic = i < total ? i : total - 1;                 // (total > 0 inside the loop)
         const int j = ic - D.n_static;                            // = s * P + p when dynamic
         const T *ps = static_xy + 2 * ((int64_t)D.static_off + ic);
-        const T *pd = dyn_xy + 2 * (D.dyn_off + (tmajor ? (int64_t)row_l * n_dyn + j : (int64_t)j * D.T + row_l));
+        const T *pd = off32 ? (const T *)(dyn_base + dyn_offset(j, row_l))     // (a static index: not dereferenced)
+                            : dyn_xy + 2 * (D.dyn_off + (tmajor ? (int64_t)row_l * n_dyn + j : (int64_t)j * D.T + row_l));
         const Raw *src = (const Raw *)(ic < D.n_static ? ps : pd);
         o = *src;
     };
@@ -1508,7 +1551,7 @@ cull_group(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, 
     // work instead of waves with a third of their lanes busy --, then wave wv merges the boxes of step k0 + wv.
     if (!(ablate & 8)) {
         for (int i = tid; i < nk * n_ext; i += KG * WAVE) {
-            const int ks = i / n_ext, e = i - ks * n_ext;
+            const int ks = small_quotient(i, n_ext, KG), e = i - ks * n_ext;   // (i < nk * n_ext: no division)
             const bool brake = e >= P.n_ti;
             const int n_eval = brake ? P.brake[e - P.n_ti].n_t : P.ti[e].n_t;
             double *ext = s_ext + (ks * n_ext_cap + e) * 2;
@@ -1516,10 +1559,11 @@ cull_group(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, 
         }
         __syncthreads();
         const int n_tab = n_prof < CULL_PBOX ? n_prof : CULL_PBOX;
+        const float sp_scale = spline_guess_scale(sp);           // (segment lookups start from a guess: fot_math.hpp)
         for (int i = tid; i < nk * n_tab; i += KG * WAVE) {
-            const int ks = i / n_tab, w = i - ks * n_tab;
+            const int ks = small_quotient(i, n_tab, KG), w = i - ks * n_tab;
             const double *ext = s_ext + (ks * n_ext_cap + s_lext[w]) * 2;
-            s_pbox[ks][w] = profile_box_from(s_linfo[w], D, sp, k0 + ks, P.dt, ext[0], ext[1]);   // read again below, per tile
+            s_pbox[ks][w] = profile_box_from_guess(s_linfo[w], D, sp, sp_scale, k0 + ks, P.dt, ext[0], ext[1]);   // read again below, per tile
         }
         __syncthreads();
     }
@@ -1535,8 +1579,8 @@ cull_group(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, 
                 }
             }
         }
-        bw.x0 = wave_min_f32(bw.x0); bw.y0 = wave_min_f32(bw.y0);
-        bw.x1 = wave_max_f32(bw.x1); bw.y1 = wave_max_f32(bw.y1);
+        bw.x0 = wave_min_nonan_f32(bw.x0); bw.y0 = wave_min_nonan_f32(bw.y0);   // (segment_box skips NaN points)
+        bw.x1 = wave_max_nonan_f32(bw.x1); bw.y1 = wave_max_nonan_f32(bw.y1);
         const float mw = cull_margin(sq_max, bw) + slack;
         if (lane == 0) { s_box[wv] = bw; s_margin[wv] = mw; s_bm[wv] = bin_map(bw, mw); s_nin[wv] = 0; }
         if (lane <= CULL_BINS) s_cnt[wv][lane] = 0;
@@ -1555,6 +1599,7 @@ cull_group(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, 
     const Raw *tracks = (const Raw *)(dyn_xy + 2 * D.dyn_off);   // [n_dyn][T] in the caller's layout
     auto track_has_nan = [&](int j) {                            // one lane on its own (the paths that did not fit)
         bool bad = false;
+#pragma clang loop vectorize(disable) unroll(disable)
         for (int t = 0; t < D.T; ++t) { const Raw p = tracks[(int64_t)j * D.T + t]; bad |= (p.x != p.x) | (p.y != p.y); }
         return bad;
     };
@@ -1575,8 +1620,13 @@ cull_group(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, 
             if (lazy) {
                 // remembered, not yet counted: its track is looked through first.  The KG lanes of an obstacle are
                 // neighbours (lane & (KG - 1) = step): the first of them enters the track once for the whole group
-                const uint64_t m = __ballot(in && i >= D.n_static);
-                if ((lane & (KG - 1)) == 0 && ((m >> lane) & ((1ull << KG) - 1ull)) != 0ull) {
+                // (which lanes those are is worked out on the scalar side from the ballot and handed back as a lane
+                // mask: no lane arithmetic per gather)
+                uint64_t m = __builtin_amdgcn_ballot_w64(in && i >= D.n_static);
+#pragma unroll
+                for (int s = 1; s < KG; s <<= 1) m |= m >> s;              // bit l: some lane of l .. l + KG - 1 is in
+                constexpr uint64_t FIRST = ~0ull / ((1ull << KG) - 1ull);  // the first lane of every group of KG
+                if (__builtin_amdgcn_inverse_ballot_w64(m & FIRST)) {
                     const int v = atomicAdd(&s_nver, 1);
                     if (v < CULL_VER) s_ver[v] = (uint32_t)i;
                 }
@@ -1601,6 +1651,24 @@ cull_group(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, 
 #endif
         constexpr int UNROLL = FOT_CULL_UNROLL;                   // gathers in flight per lane
         if (ablate & 64) {                                        // (timing diagnostics: no gathers)
+        } else if (D.n_static == 0 && off32) {
+            // only the prediction tensor (the usual case): a lane's obstacles are a fixed number of bytes apart, so the
+            // offset runs along, one add per gather.  Past the end it is clamped to the tensor's last point (ignored),
+            // which also keeps a wrapped offset inside the tensor: every multiple of the point size below is.
+            const uint32_t step = (uint32_t)(tmajor ? STRIDE : STRIDE * D.T) * (uint32_t)sizeof(Raw);
+            const uint32_t o_last = (uint32_t)((int64_t)n_dyn * D.T * (int64_t)sizeof(Raw)) - (uint32_t)sizeof(Raw);
+            uint32_t off = dyn_offset(i_first, row_l);
+            for (int ib = i_first; ib < total; ib += UNROLL * STRIDE) {
+                Raw o[UNROLL];
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) {
+                    const uint32_t ou = off + (uint32_t)u * step;
+                    o[u] = *(const Raw *)(dyn_base + (ou < o_last ? ou : o_last));
+                }
+                off += (uint32_t)UNROLL * step;
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) classify(ib + u * STRIDE, o[u]);
+            }
         } else if (D.n_static == 0) {
             // only the prediction tensor (the usual case): a lane's obstacles are a fixed number of bytes apart, so the
             // address is a running pointer instead of two 64-bit multiply-adds and a select per gather
@@ -1641,7 +1709,9 @@ cull_group(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, 
 #pragma unroll
             for (int u = 0; u < VU; ++u) {
                 const int v = v0 + u * KG < n_ver ? v0 + u * KG : v0;
-                p[u] = tracks[(int64_t)((int)s_ver[v] - D.n_static) * D.T + (lane < D.T ? lane : D.T - 1)];
+                const int j = (int)s_ver[v] - D.n_static, t = lane < D.T ? lane : D.T - 1;
+                p[u] = off32 ? *(const Raw *)(dyn_base + (uint32_t)(j * D.T + t) * (uint32_t)sizeof(Raw))
+                             : tracks[(int64_t)j * D.T + t];
             }
 #pragma unroll
             for (int u = 0; u < VU; ++u) {
@@ -1677,9 +1747,14 @@ cull_group(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, 
             o.x = (double)static_xy[2 * in]; o.y = (double)static_xy[2 * in + 1];
         } else {
             const int j = i - D.n_static;
-            const int64_t in = D.dyn_off + (tmajor ? (int64_t)row * n_dyn + j : (int64_t)j * D.T + row);
-            o.x = (double)dyn_xy[2 * in]; o.y = (double)dyn_xy[2 * in + 1];
-            sid = j / D.P;
+            if (off32) {
+                const Raw r = *(const Raw *)(dyn_base + dyn_offset(j, row));
+                o.x = (double)r.x; o.y = (double)r.y;
+            } else {
+                const int64_t in = D.dyn_off + (tmajor ? (int64_t)row * n_dyn + j : (int64_t)j * D.T + row);
+                o.x = (double)dyn_xy[2 * in]; o.y = (double)dyn_xy[2 * in + 1];
+            }
+            sid = (int)div_by_magic((uint32_t)j, (uint32_t)D.P, D.p_magic);   // = j / D.P
         }
     };
     if (lazy) {
@@ -1690,6 +1765,8 @@ cull_group(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, 
             for (int j = lane; j < s_nin[kk]; j += WAVE) {
                 const uint32_t e = s_list[kk][j];
                 bool bad = false;
+                // (n_bad is 0 nearly always: as a vectorised loop its set-up alone cost every wave dozens of instructions)
+#pragma clang loop vectorize(disable) unroll(disable)
                 for (int b = 0; b < n_bad; ++b) bad |= s_bad[b] == (e & CULL_IDX_MASK);
                 if (bad) s_list[kk][j] = CULL_DEAD;
                 else atomicAdd(&s_cnt[kk][e >> 20], 1);
@@ -1709,12 +1786,7 @@ cull_group(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, 
     }
     {   // exclusive prefix over the bins (lane = bin; entry CULL_BINS ends with the total); cursors = starts
         const int c = lane < CULL_BINS ? s_cnt[kk][lane] : 0;
-        int incl = c;
-#pragma unroll
-        for (int off = 1; off < WAVE; off <<= 1) {
-            const int t = __shfl_up(incl, off, WAVE);
-            if (lane >= off) incl += t;
-        }
+        const int incl = wave_prefix_sum_i32(c);
         if (lane <= CULL_BINS) { s_start[kk][lane] = incl - c; s_cnt[kk][lane] = incl - c; }
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");       // this wave's LDS writes (other lanes') before the reads below

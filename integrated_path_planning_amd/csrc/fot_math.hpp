@@ -1187,12 +1187,88 @@ FOT_HD Box32 profile_box_from(const LonQuartic &Q, const InstDesc &D, const Spli
     return segment_box(p.x, p.y, p.dx * inv, p.dy * inv, d0, d1, D.ego.x, D.ego.y);
 }
 
+// k_cull's own segment lookup and box (copies: the helpers above are inlined by the evaluation kernels too and stay as
+// they are).  The bisection of spline_index is some ten vector instructions a round; a path sampled at even arc-length
+// steps -- the usual one -- has its segment at (v - s_0) / h, so that guess is tried first and ACCEPTED ONLY IF IT IS
+// v's segment: s[g] <= v < s[g + 1] over non-decreasing knots means exactly g + 1 knots are <= v, which is the index the
+// bisection returns (g <= n - 2, so the clip changes nothing).  Every other case -- uneven knots, v on the last knot --
+// falls back to the bisection: the result is spline_index's for every input, whatever `inv_h` is.
+FOT_HD float spline_guess_scale(const SplineView &sp)
+{
+    const float len = (float)(sp.s[sp.n - 1] - sp.s[0]);
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (float)(sp.n - 1) * __builtin_amdgcn_rcpf(len);          // (a guess's scale: any value will do)
+#else
+    return (float)(sp.n - 1) / len;
+#endif
+}
+
+FOT_HD int spline_index_guess(const SplineView &sp, double v, float inv_h)
+{
+    const float top = (float)(sp.n - 2);
+    float gf = (float)(v - sp.s[0]) * inv_h;
+    gf = gf >= 0.0f ? (gf <= top ? gf : top) : 0.0f;                 // (NaN: 0)
+    const int g = (int)gf;
+    if (sp.s[g] <= v && v < sp.s[g + 1]) return g;
+    return spline_index(sp, v);
+}
+
+FOT_HD Box32 profile_box_from_guess(const LonQuartic &Q, const InstDesc &D, const SplineView &sp, float inv_h, int k,
+                                    double dt, double d0, double d1)
+{
+    if (k >= Q.n_t) return box_empty();
+    LonInfo L;
+    L.a0 = Q.a0; L.a1 = Q.a1; L.a2 = Q.a2; L.a3 = Q.a3; L.a4 = Q.a4; L.n_t = Q.n_t; L.n_eval = Q.n_eval;
+    L.Js = 0.0; L.sd_last = 0.0; L.T = 0.0;
+    double s_, u0, u1, u2;
+    lon_sample(L, k, dt, s_, u0, u1, u2);
+    double px = NAN, py = NAN, pdx = NAN, pdy = NAN;                 // (spline_point's position and tangent, same expressions)
+    if (s_ >= sp.s[0] && s_ <= sp.s[sp.n - 1]) {
+        const int i = spline_index_guess(sp, s_, inv_h);
+        const double h = s_ - sp.s[i], h2 = h * h;
+        const double bx = sp.bx[i], cx = sp.cx[i], dx = sp.dx[i];
+        const double by = sp.by[i], cy = sp.cy[i], dy = sp.dy[i];
+        px = sp.ax[i] + bx * h + cx * h2 + dx * (h2 * h);
+        py = sp.ay[i] + by * h + cy * h2 + dy * (h2 * h);
+        pdx = bx + 2.0 * cx * h + 3.0 * dx * h2;
+        pdy = by + 2.0 * cy * h + 3.0 * dy * h2;
+    }
+    const double inv = fast_rsqrt(pdx * pdx + pdy * pdy);
+    return segment_box(px, py, pdx * inv, pdy * inv, d0, d1, D.ego.x, D.ego.y);
+}
+
 // index of a profile's lateral extent in a per-step table: horizons first, then the brake ladder
 FOT_HD int extent_index(const DevParams &P, const InstDesc &D, int slot)
 {
     const int n_grid_lon = P.n_ti * D.n_tv;
     return slot < n_grid_lon ? slot / D.n_tv : P.n_ti + (slot - n_grid_lon);
 }
+
+// ---- k_cull's index arithmetic.  A division by a run-time value is some twenty vector instructions per lane; the
+// three forms below replace the ones k_cull ran per lane and are EXACT over the ranges given (tests/test_cull_index_cpu.py).
+
+// floor(2^32 / d) for d >= 1 (saturated at d = 1), built once on the host
+FOT_HD uint32_t div_magic(uint32_t d) { return d <= 1u ? 0xffffffffu : (uint32_t)(0x100000000ull / d); }
+
+// n / d from m = div_magic(d), for every 32-bit n and d >= 1.  2^32 / d - m lies in [0, 1), so n * m / 2^32 lies in
+// (n / d - n / 2^32, n / d]: the high word of the product is floor(n / d) or one less, and one remainder test settles it.
+FOT_HD uint32_t div_by_magic(uint32_t n, uint32_t d, uint32_t m)
+{
+    const uint32_t q = (uint32_t)(((uint64_t)n * m) >> 32);
+    return q + (n - q * d >= d ? 1u : 0u);
+}
+
+// i / n for 0 <= i < kg * n and a small kg known at compile time: the multiples of n that i has reached
+FOT_HD int small_quotient(int i, int n, int kg)
+{
+    int q = 0;
+    for (int m = 1; m < kg; ++m) q += i >= m * n ? 1 : 0;
+    return q;
+}
+
+// Whether every byte offset into a tensor of `bytes` bytes fits a 32-bit register (k_cull then addresses the tensor as
+// a wave-uniform base plus a per-lane 32-bit offset; a few strides past the end still do not wrap an unsigned one).
+FOT_HD bool offsets_fit32(int64_t bytes) { return bytes < ((int64_t)1 << 31); }
 
 FOT_HD float box_footprint_slack(const DevParams &P)
 {

@@ -482,6 +482,7 @@ inline int build_batch_layout(const ScenarioRef *sc, int n_scen, const int32_t *
                 if (S > FOT_MAX_SAMPLES) { err = "more prediction samples than FOT_MAX_SAMPLES"; return FOT_ERR_UNSUPPORTED; }
                 if (b.dyn_off[i] < 0) { err = "dyn_off < 0"; return FOT_ERR_INVALID; }
                 D.dyn_mode = mode; D.S = S; D.P = Pn; D.T = T;
+                D.p_magic = div_magic((uint32_t)Pn);
                 if (D.dyn_tmajor) L.any_tmajor = true;
                 D.dyn_off = b.dyn_off[i];
                 const int64_t pts = (int64_t)S * Pn * T;

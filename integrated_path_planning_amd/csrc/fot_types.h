@@ -74,6 +74,8 @@ struct InstDesc {
     int32_t n_cand_max;                  // n_grid + n_brake
     int32_t lon_off;                     // first longitudinal-profile slot
     int32_t n_static;
+    uint32_t p_magic;                    // div_magic(P) (fot_math.hpp): k_cull's sample index j / P without a division
+                                         // (in what was alignment padding: no other member moves)
     int64_t static_off;                  // points into the caller's static_xy
     int32_t dyn_mode, S, P, T;
     int64_t dyn_off;                     // points into the caller's dyn_xy
