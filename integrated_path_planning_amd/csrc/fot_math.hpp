@@ -1406,6 +1406,7 @@ FOT_HD void box_thresholds(const FilterConst &f, const Box32 &b, float m, float 
 }
 
 // exact float64 test of one chunk (the reference's test); updates the per-sample hit state
+// (the count at its sample-count edges, through every device form of it: tests/test_gpu_chance_budget.py)
 FOT_HD void exact_chunk(const d2 *e64, const uint8_t *sid, double px, double py, double sq_static, double sq_dyn,
                         int max_viol, uint64_t &hit_mask, int &viol, bool &collided)
 {

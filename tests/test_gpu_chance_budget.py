@@ -1,0 +1,171 @@
+"""The chance-constraint budget of plan() at its sample-count edges, on the GPU.
+
+A candidate collides when more than max_viol = floor(eps S) distinct samples of a distribution hit it.  Through plan()
+that count is device-only code: k_cull's sample id per list entry (j / P through a host-built reciprocal), the 64-bit
+hit mask and counter of FusedSink<false> on its scalar-load chunk walk, the per-segment masks of k_evaluate_split that
+wave 0 folds as popcount(OR of masks) > max_viol through LDS, the reload of the per-step values past step 64, the
+circle loop of a footprint, and the lean / general choice of a launch from every instance's max_viol.  The instances
+of tests/chance_budget_common.py hit a target candidate in exactly max_viol distinct samples (A: no collision), one
+more (B: collision), or max_viol samples over and over (C: no collision), at sample ids on both ends of the mask and
+both sides of bit 32, for S in 1 .. 64 and eps whose product with S rounds just below or above an integer; D, E, F hold
+the static, NaN and inflation rules next to the count.  tests/test_chance_budget_cpu.py proves on the oracle alone that
+the inputs are what they claim and stay 1e-6 clear of the radius, so every table here must EQUAL the oracle's.
+
+Every distinct (eps, inflation) of a scene is a scenario of one handle and all its instances go out in ONE mixed launch.
+  main leg     every evaluation kernel (EVAL_PATHS) and the per-wave cut in 2 and 3 time segments, float64 [S][P][T][2]:
+               keep / n_t, status (eps_band), cost, record against the oracle; records byte-identical across the paths
+  dtype leg    float32 tensors, the time-major layout, both: the same oracle runs (the inputs are float32-exact);
+               float64 time-major records byte-identical to the plain launch's
+  alone        an A, a B and an eps = 0 instance planned alone: the lean form exactly where the launch is eligible, the
+               general form in company, the record byte-identical either way
+"""
+import numpy as np
+import pytest
+
+import chance_budget_common as cb
+import eps_band
+from helpers import EVAL_PATHS, TIGHT, assert_record_matches_oracle, set_eval_path
+from integrated_path_planning_amd.batch import PackedBatch, PlanRequest
+from integrated_path_planning_amd.planner import BatchPlanner
+
+pytestmark = pytest.mark.gpu
+
+PATHS = EVAL_PATHS + ("wave-2", "wave-3")            # the per-wave cut in 2 and 3 time segments ("split-wave": 4)
+FORMS = ("none", "general", "lean", "both")          # fot_debug_set_eval_form(-1)
+CASES = [(s, g) for s in cb.SCENE_NAMES for g in cb.GROUPS]
+
+
+def set_path(bp, path):
+    if path.startswith("wave-"):
+        bp.set_tile_cut(1)
+        bp.set_eval_segments(int(path[5:]))
+    else:
+        set_eval_path(bp, path)
+
+
+def rec_bytes(rec):
+    return bytes(memoryview(rec).cast("B"))
+
+
+class Handle:
+    """One handle per scene: a scenario per distinct (eps, inflation) of its instances, the requests naming theirs."""
+
+    def __init__(self, name):
+        self.sc, self.insts = cb.scene(name), cb.instances(name)
+        keys = cb.configurations(self.insts)
+        self.bp = BatchPlanner(waypoints=self.sc.waypoints, **self.sc.planner_kw(*keys[0]))
+        for k, key in enumerate(keys[1:], start=1):
+            assert self.bp.add_scenario(waypoints=self.sc.waypoints, **self.sc.planner_kw(*key)) == k
+        self.reqs = [PlanRequest(**{**i.req.__dict__, "scenario": keys.index(i.key)}) for i in self.insts]
+
+    def of_group(self, group):
+        idx = [i for i, inst in enumerate(self.insts) if inst.group == group]
+        assert idx, group
+        return idx
+
+    def check(self, res, i, how, slot=None):
+        """Instance i of the scene, planned as instance `slot` of the last call (its own index in the mixed launch)."""
+        inst, slot = self.insts[i], i if slot is None else slot
+        lab = f"{inst.label()} inst {i} [{how}]"
+        want = inst.want
+        cost, status, keep, nt = self.bp.candidates(slot)
+        assert len(status) == want.n_cand, lab
+        np.testing.assert_array_equal(nt, want.cand_nt, err_msg=lab)
+        np.testing.assert_array_equal(keep, want.cand_keep, err_msg=lab)
+        eps_band.check_status_table(self.bp, slot, status, want.cand_status, lab)
+        np.testing.assert_allclose(cost, want.cand_cost, rtol=TIGHT, atol=TIGHT, err_msg=lab)
+        assert_record_matches_oracle(res.records[slot], want, label=lab)
+
+    def restore(self):
+        set_eval_path(self.bp, "auto")
+        self.bp.set_eval_form("auto")
+
+
+@pytest.fixture(scope="module")
+def handles():
+    made = {}
+
+    def get(name):
+        if name not in made:
+            made[name] = Handle(name)
+        return made[name]
+    yield get
+    for h in made.values():
+        h.restore()
+        h.bp.close()
+
+
+@pytest.mark.parametrize("name,group", CASES, ids=[f"{s}-{g}" for s, g in CASES])
+def test_the_budget_under_every_evaluation_kernel(handles, name, group):
+    h = handles(name)
+    idx = h.of_group(group)
+    first = None
+    try:
+        for path in PATHS:
+            set_path(h.bp, path)
+            res = h.bp.plan_batch(h.reqs)
+            assert FORMS[h.bp.set_eval_form(-1)] == "general", f"{name} [{path}]"
+            for i in idx:
+                h.check(res, i, path)
+            recs = [rec_bytes(res.records[i]) for i in idx]
+            if first is None:
+                first = recs
+            for i, a, b in zip(idx, first, recs):
+                assert a == b, f"{h.insts[i].label()} inst {i}: record under [{path}] differs from [{PATHS[0]}]"
+    finally:
+        h.restore()
+
+
+@pytest.mark.parametrize("name,group", CASES, ids=[f"{s}-{g}" for s, g in CASES])
+def test_the_budget_in_float32_and_time_major_tensors(handles, name, group):
+    h = handles(name)
+    idx = h.of_group(group)
+    try:
+        for path in ("group", "split-wave"):
+            set_eval_path(h.bp, path)
+            plain = h.bp.plan_batch(h.reqs)                                  # (the main leg's launch under this path)
+            plain = [rec_bytes(plain.records[i]) for i in idx]
+            for dtype, tsp in ((np.float64, True), (np.float32, False), (np.float32, True)):
+                how = f"{path}, {np.dtype(dtype).name}{', time-major' if tsp else ''}"
+                res = h.bp.plan_packed(PackedBatch(h.reqs, dtype, dyn_layout_tsp=tsp))
+                for i in idx:
+                    h.check(res, i, how)
+                if dtype is np.float64:
+                    for i, a in zip(idx, plain):
+                        assert rec_bytes(res.records[i]) == a, f"{h.insts[i].label()} inst {i} [{how}]: record differs"
+    finally:
+        h.restore()
+
+
+@pytest.mark.parametrize("name", cb.SCENE_NAMES)
+def test_alone_and_in_company(handles, name):
+    """An A, a B (both with a budget) and an eps = 0 instance with a hit: alone in a launch of its own under "auto" --
+    k_evaluate_split with the library's own segment count, in the lean form where the launch is eligible (at most 64
+    steps, the centre circle alone, max_viol 0 on every instance) -- and among all the others in the general form."""
+    h = handles(name)
+    sc = h.sc
+    pick = {}
+    for i, inst in enumerate(h.insts):
+        if inst.cand != sc.cands[0]:
+            continue
+        if (inst.eps, inst.S) == cb.EXTRA_PAIR and inst.pattern in ("A", "B"):
+            pick.setdefault(inst.pattern, i)
+        if (inst.eps, inst.S) == (0.0, 1) and inst.pattern == "B":
+            pick.setdefault("eps0", i)
+    assert sorted(pick) == ["A", "B", "eps0"]
+    try:
+        h.restore()
+        res = h.bp.plan_batch(h.reqs)
+        assert FORMS[h.bp.set_eval_form(-1)] == "general", f"{name}: the mixed launch"
+        company = {i: rec_bytes(res.records[i]) for i in pick.values()}
+        for what, i in pick.items():
+            inst = h.insts[i]
+            one = h.bp.plan_batch([h.reqs[i]])
+            eligible = sc.n_total <= 64 and sc.footprint is None and cb.max_viol(inst.eps, inst.S) == 0
+            assert eligible == (what == "eps0" and name == "straight")
+            form = FORMS[h.bp.set_eval_form(-1)]
+            assert form == ("lean" if eligible else "general"), f"{inst.label()} alone ran the {form} form"
+            h.check(one, i, "alone", slot=0)
+            assert rec_bytes(one.records[0]) == company[i], f"{inst.label()} inst {i}: alone against in company"
+    finally:
+        h.restore()
