@@ -998,6 +998,70 @@ int fot_debug_loop_sampler_shapes(fot_handle *h, int32_t cap, int32_t *n_scenes,
 int fot_loop_set_samples_shared(fot_handle *h, int32_t S, int32_t n_steps, int32_t first_step, const void *samples,
                                 int32_t dtype, int32_t flags, int32_t n_rec_cols, const int32_t *slot_col0);
 
+/* ---- open-loop prediction evaluation of a whole scene (RQ1a) ------------------------------------------------------------------
+ * The reference's examples/run_openloop_prediction.py (evaluate_window / evaluate_scene) in ONE stateless, synchronous call:
+ * every fixed-population window of obs_len + pred_len frames of a recorded scene is observed for obs_len frames, predicted
+ * (constant velocity, or S samples of a loaded Social-GAN model), resampled through process_prediction at sgan_dt = sim_dt =
+ * dt and plan_horizon = pred_len dt (stride 1, E = pred_len, no prepended entry) and scored at its one origin t = obs_len - 1;
+ * the windows' records are folded count-weighted.  The scene crosses the bus once and the samples never leave HBM.
+ *   scene       [n_frames][n_cols][2] of scene_dtype (FOT_F32 | FOT_F64), host memory or, with FOT_OPENLOOP_SCENE_DEVICE,
+ *               device memory (aligned to one point); only the points the windows name are read (absent ones may be NaN)
+ *   win_frame0  [n_windows] host: first frame of each window
+ *   ped_off     [n_windows + 1] host, non-decreasing from 0;  row_col [ped_off[n_windows]] host: the scene column of every
+ *               row, the pedestrians of a window in the caller's order
+ *   method      FOT_OPENLOOP_CV (S must be 1; the velocity from the last two float32 observations, zero when obs_len == 1),
+ *               or FOT_OPENLOOP_SGAN with `model`, a slot of fot_sgan_load_model whose obs_len / pred_len are the call's
+ *   noise       [S][rows][noise_dim] float32 for the whole call, host memory or (FOT_OPENLOOP_NOISE_DEVICE) device memory,
+ *               rows = ped_off[n_windows] (FOT_SGAN_NOISE_PED) or n_windows (FOT_SGAN_NOISE_GLOBAL); or NULL: the library
+ *               draws fot_sgan_noise's numbers of (seed, noise_kind) with the slot word win_id0 + w, step 0 and the row's
+ *               index within its window -- a window's numbers depend neither on its company nor on how a scene is split
+ *               over calls.  Ignored for CV and for a model with noise_dim 0
+ *   max_rows    rows a chunk of whole windows may hold (0: 8192); the work arrays are sized by it and only grow
+ *   records     host, n_windows fot_pred_score records, or NULL;  raw_out host [S][pred_len][rows][2] float32 or NULL: the
+ *               generator's raw samples of the whole call (tests; not with CV)
+ *   totals      host: sum_ade += ((ade_scene P) / P) P, likewise fde and the per-agent sums (agent_sum / P) P, traj_count
+ *               += P for every window with P > 0 whose ade is not NaN; sum_nll += ((-log_lik_sum) / nll_count) nll_count,
+ *               nll_count += ... for every window with FOT_PRED_NLL -- the reference's operation order, in window order;
+ *               n_windows; flags: the OR of the records' flags.  ade = sum_ade / traj_count ..., nll = sum_nll / nll_count.
+ * Per chunk the gather (k_openloop_rows), the noise, the generator or the constant-velocity predictor, the resampler and the
+ * scorer are enqueued on one stream (NULL = the handle's) with nothing synchronised in between; the call waits once.  A
+ * window's record is byte-identical whatever max_rows, the windows beside it, the placement or the element type of a scene
+ * of the same values.  Non-finite coordinates raise FOT_PRED_NONFINITE as in fot_prediction_scores.
+ * Refusals, a refused call writes nothing.  FOT_ERR_INVALID: a NULL argument that is needed; negative n_frames / n_cols /
+ * n_windows; obs_len, pred_len or S < 1; dt <= 0; offsets not starting at 0 or decreasing; a column outside the scene; a
+ * window starting before frame 0 or reaching past n_frames; max_rows < 0 or below the largest window; an unknown method,
+ * flag, dtype or noise kind (FOT_NOISE_RAW included); S != 1 with CV; no model loaded in the slot, or its obs_len / pred_len
+ * differ; a negative win_id0; a misaligned device scene.  FOT_ERR_UNSUPPORTED: S > FOT_MAX_SAMPLES, pred_len >
+ * FOT_MAX_PRED_LEN, obs_len > FOT_SGAN_MAX_OBS_LEN, a window of more than FOT_SGAN_MAX_PEDS rows.
+ * An addition: no structure, capacity word of fot_abi_info or FOT_ABI_VERSION changes; a binding looks the symbol up. */
+#define FOT_OPENLOOP_CV 0
+#define FOT_OPENLOOP_SGAN 1
+#define FOT_OPENLOOP_SCENE_DEVICE 1
+#define FOT_OPENLOOP_NOISE_DEVICE 2
+typedef struct fot_openloop_params {
+    int32_t n_frames, n_cols, n_windows;
+    int32_t scene_dtype;            /* FOT_F32 | FOT_F64 */
+    int32_t obs_len, pred_len;
+    int32_t method;                 /* FOT_OPENLOOP_CV | FOT_OPENLOOP_SGAN */
+    int32_t model;                  /* slot of fot_sgan_load_model (SGAN) */
+    int32_t S;
+    int32_t noise_kind;             /* FOT_NOISE_GAUSSIAN | FOT_NOISE_UNIFORM | FOT_NOISE_UNIFORM_SYM (noise == NULL) */
+    int32_t win_id0;                /* the noise counter's slot word of window 0 */
+    int32_t max_rows;
+    int32_t flags;                  /* FOT_OPENLOOP_SCENE_DEVICE | FOT_OPENLOOP_NOISE_DEVICE */
+    int32_t _pad;
+    double dt;
+    uint64_t seed;
+} fot_openloop_params;
+typedef struct fot_openloop_totals {
+    double sum_ade, sum_fde, sum_ade_agent, sum_fde_agent, sum_nll;
+    int64_t traj_count, nll_count;
+    int32_t n_windows, flags;
+} fot_openloop_totals;
+int fot_openloop_eval(fot_handle *h, const fot_openloop_params *p, const void *scene, const int32_t *win_frame0,
+                      const int32_t *ped_off, const int32_t *row_col, const void *noise, fot_pred_score *records,
+                      void *raw_out, fot_openloop_totals *totals, void *stream);
+
 /* Host utility (no GPU): the first kmax samples of the 15 path arrays of records[index[i]], i < n, as one dense block
  * out[15][n][kmax] in fot_result array order (t .. c) -- what a history keeps of a step's records. */
 int fot_gather_paths(const fot_result *records, int32_t n, const int32_t *index, int32_t kmax, double *out);

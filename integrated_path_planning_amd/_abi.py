@@ -155,6 +155,24 @@ class SganDesc(C.Structure):                                      # fot_sgan_des
                                          "noise_mix_type")] + [("dropout", C.c_float), ("_pad", C.c_int32)]
 
 
+class OpenLoopParams(C.Structure):                                # fot_openloop_params
+    _fields_ = [(n, C.c_int32) for n in ("n_frames", "n_cols", "n_windows", "scene_dtype", "obs_len", "pred_len", "method",
+                                         "model", "S", "noise_kind", "win_id0", "max_rows", "flags", "_pad")] + \
+               [("dt", C.c_double), ("seed", C.c_uint64)]
+
+
+OPENLOOP_TOTALS_F64 = ("sum_ade", "sum_fde", "sum_ade_agent", "sum_fde_agent", "sum_nll")
+
+
+class OpenLoopTotals(C.Structure):                                # fot_openloop_totals
+    _fields_ = [(n, C.c_double) for n in OPENLOOP_TOTALS_F64] + [("traj_count", C.c_int64), ("nll_count", C.c_int64),
+                                                                 ("n_windows", C.c_int32), ("flags", C.c_int32)]
+
+
+OPENLOOP_CV, OPENLOOP_SGAN = 0, 1        # FOT_OPENLOOP_* methods
+OPENLOOP_SCENE_DEVICE, OPENLOOP_NOISE_DEVICE = 1, 2
+
+
 class Batch(C.Structure):
     _fields_ = [("n_inst", C.c_int32), ("obstacle_dtype", C.c_int32),
                 ("ego", C.POINTER(Ego)), ("target_speed", C.POINTER(C.c_double)),
@@ -183,7 +201,7 @@ SYMBOLS = ["fot_version", "fot_abi_info", "fot_create", "fot_destroy", "fot_live
            "fot_loop_plan_sample", "fot_loop_run_best_samples", "fot_debug_loop_block", "fot_loop_set_samples",
            "fot_loop_begin_sweep", "fot_loop_set_samples_shared", "fot_loop_set_sampler_shared", "fot_debug_loop_sampler_shape",
            "fot_sgan_max_models", "fot_sgan_load_model", "fot_sgan_unload_model", "fot_sgan_sample_model",
-           "fot_loop_set_sampler_models", "fot_debug_loop_sampler_shapes"]
+           "fot_loop_set_sampler_models", "fot_debug_loop_sampler_shapes", "fot_openloop_eval"]
 LOOP_PLAN_DISTRIBUTION, LOOP_PLAN_REPRESENTATIVE = 0, 1      # FOT_LOOP_PLAN_* (fot_loop_plan_sample)
 PROFILE_KERNELS = 3                      # FOT_PROFILE_KERNELS (include/fot.h)
 ABI_VERSION = 8                          # FOT_ABI_VERSION
@@ -450,7 +468,9 @@ def lib():
                        ("fot_sgan_unload_model", [vp, C.c_int32]),
                        ("fot_sgan_sample_model", [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp]),
                        ("fot_loop_set_sampler_models", [vp, C.c_int32, C.c_uint64, C.c_int32, vp, C.c_int32, vp, vp]),
-                       ("fot_debug_loop_sampler_shapes", [vp, C.c_int32, vp, vp])):
+                       ("fot_debug_loop_sampler_shapes", [vp, C.c_int32, vp, vp]),
+                       ("fot_openloop_eval", [vp, C.POINTER(OpenLoopParams), vp, vp, vp, vp, vp, vp, vp,
+                                              C.POINTER(OpenLoopTotals), vp])):
         if hasattr(L, name):
             getattr(L, name).argtypes = args
     L.fot_gather_paths.argtypes = [vp, C.c_int32, vp, C.c_int32, vp]

@@ -80,6 +80,7 @@ void destroy_handle(fot_handle *h)
     h->hSmallIn.release(); h->hSmallOut.release(); h->hRecOut.release(); h->hDone.release();
     h->hScoreIn.release(); h->hScoreOut.release(); h->dScoreT.release();
     for (fot_handle::Sgan &g : h->sgan) g.release();
+    h->ol.release();
     h->loop.release();
     for (hipEvent_t e : h->prof_pool) (void)hipEventDestroy(e);
     if (h->fork) (void)hipEventDestroy(h->fork);

@@ -372,6 +372,18 @@ struct fot_handle {
     PinnedBuf hScoreIn, hScoreOut;           // fot_prediction_scores: PredOriginDev[] | truth; the records the kernel writes
     DevBuf dScoreT;                          // ... the device copy of a host tensor
     DevBuf dTmpA, dTmpB, dTmpC, dTmpD;
+    // fot_openloop_eval: the scene's copy and the call's tables in HBM, the work arrays of a chunk (sized by max_rows,
+    // grow-only), the tables as the host builds them and the records the scorer writes
+    struct OpenLoop {
+        DevBuf dScene, dTab, dNoiseAll;          // a host scene | the call's tables (hTab) | a host noise tensor
+        DevBuf dObs, dAnchor, dTruth, dNoise, dRaw, dDyn;
+        PinnedBuf hTab, hRec;
+        void release()
+        {
+            for (DevBuf *b : { &dScene, &dTab, &dNoiseAll, &dObs, &dAnchor, &dTruth, &dNoise, &dRaw, &dDyn }) b->release();
+            hTab.release(); hRec.release();
+        }
+    } ol;
     LoopState loop;
     // fot_sgan_*: the loaded models (descriptor, device image of the weights), each with the work arrays of its own sample
     // calls -- what model m computes never depends on what else is loaded or was sampled in between

@@ -159,6 +159,26 @@ int prediction_scores_impl(fot_handle *h, const char *who, int32_t n, const fot_
     return FOT_OK;
 }
 
+// The work arrays sgan_enqueue grows on demand, brought to the size of N pedestrians and S samples up front: a call that
+// enqueues several chunks then frees nothing (hipFree waits for the device) between them.
+int sgan_reserve(fot_handle *h, int model, int N, int S)
+{
+    fot_handle::Sgan &G = h->sgan[model];
+    const fot_sgan_desc &d = G.desc;
+    const bool pooled = sg_pooled(d), steps = sg_pool_steps(d), context = sg_has_context(d);
+    const int nc = context ? d.decoder_h_dim - d.noise_dim : d.encoder_h_dim;
+    const size_t rows = (size_t)S * N;
+    HIP_TRY(h, G.dHenc.ensure(sizeof(float) * (size_t)N * d.encoder_h_dim));
+    if (pooled) HIP_TRY(h, G.dPool.ensure(sizeof(float) * (steps ? rows : (size_t)N) * G.dev.pool.b_pad));
+    if (context) HIP_TRY(h, G.dCtx.ensure(sizeof(float) * (size_t)N * nc));
+    if (steps) {
+        HIP_TRY(h, G.dH.ensure(sizeof(float) * rows * d.decoder_h_dim));
+        HIP_TRY(h, G.dC.ensure(sizeof(float) * rows * d.decoder_h_dim));
+        HIP_TRY(h, G.dXY.ensure(sizeof(float) * rows * 6));
+    }
+    return FOT_OK;
+}
+
 }  // namespace
 
 // ---- the helper fot_host.hpp declares for the resident loop's sampler step (fot_host_loop.cpp loop_run_step)
@@ -518,6 +538,184 @@ int fot_sgan_noise(fot_handle *h, uint64_t seed, int32_t kind, int32_t S, int32_
     if (!(flags & FOT_OUT_DEVICE)) HIP_TRY(h, hipMemcpyAsync(out, d_out, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, st));
     { int r = order_end(h, st); if (r != FOT_OK) return r; }
     HIP_TRY(h, hipStreamSynchronize(st));
+    return FOT_OK;
+}
+
+// ---- open-loop prediction evaluation of a scene (include/fot.h; the shared rules: fot_openloop.hpp) -------------------------
+int fot_openloop_eval(fot_handle *h, const fot_openloop_params *p, const void *scene, const int32_t *win_frame0,
+                      const int32_t *ped_off, const int32_t *row_col, const void *noise, fot_pred_score *records,
+                      void *raw_out, fot_openloop_totals *totals, void *stream)
+{
+    static_assert(sizeof(OlTotals) == sizeof(fot_openloop_totals) && offsetof(OlTotals, flags) == offsetof(fot_openloop_totals, flags),
+                  "OlTotals is fot_openloop_totals");
+    if (!h) return FOT_ERR_INVALID;
+    const std::string who = "fot_openloop_eval: ";
+    auto refuse = [&](int bad, const char *why) { return fail(h, bad == OL_BAD_UNSUPPORTED ? FOT_ERR_UNSUPPORTED : FOT_ERR_INVALID, who + why); };
+    if (!p || !totals) return fail(h, FOT_ERR_INVALID, who + "p / totals is NULL");
+    if (p->method != FOT_OPENLOOP_CV && p->method != FOT_OPENLOOP_SGAN) return fail(h, FOT_ERR_INVALID, who + "method");
+    if (p->flags & ~(FOT_OPENLOOP_SCENE_DEVICE | FOT_OPENLOOP_NOISE_DEVICE)) return fail(h, FOT_ERR_INVALID, who + "flags");
+    if (p->scene_dtype != FOT_F32 && p->scene_dtype != FOT_F64) return fail(h, FOT_ERR_INVALID, who + "scene_dtype");
+    if (!(p->dt > 0.0)) return fail(h, FOT_ERR_INVALID, who + "dt must be positive");
+    if (p->max_rows < 0 || p->win_id0 < 0) return fail(h, FOT_ERR_INVALID, who + "max_rows / win_id0 is negative");
+    const bool cv = p->method == FOT_OPENLOOP_CV;
+    const int W = p->n_windows, obs_len = p->obs_len, pred_len = p->pred_len, S = p->S;
+    const char *why = "";
+    { const int bad = ol_check_lengths(p->n_frames, p->n_cols, W, obs_len, pred_len, S, cv, &why); if (bad) return refuse(bad, why); }
+    if (cv && raw_out) return fail(h, FOT_ERR_INVALID, who + "raw_out: the constant-velocity predictor has no raw samples");
+    int nd = 0;
+    bool global_noise = false;
+    if (!cv) {
+        if (p->model < 0 || p->model >= SGAN_MAX_MODELS) return fail(h, FOT_ERR_INVALID, who + "model lies outside 0 .. fot_sgan_max_models() - 1");
+        const fot_handle::Sgan &G = h->sgan[p->model];
+        if (!G.loaded) return fail(h, FOT_ERR_INVALID, who + "no model loaded in the slot (fot_sgan_load_model)");
+        if (G.desc.obs_len != obs_len || G.desc.pred_len != pred_len) return fail(h, FOT_ERR_INVALID, who + "the model's obs_len / pred_len differ from the call's");
+        nd = G.desc.noise_dim;
+        global_noise = G.desc.noise_mix_type == FOT_SGAN_NOISE_GLOBAL;
+        if (nd > 0 && !noise && (p->noise_kind <= FOT_NOISE_RAW || p->noise_kind >= FOT_NOISE_KINDS)) return fail(h, FOT_ERR_INVALID, who + "noise_kind");
+        if ((int64_t)p->win_id0 + W > (int64_t)INT32_MAX) return fail(h, FOT_ERR_INVALID, who + "win_id0 + n_windows exceeds the counter's slot word");
+    }
+    int widest = 0;
+    { const int bad = ol_check_table(p->n_frames, p->n_cols, W, obs_len, pred_len, win_frame0, ped_off, row_col, &widest, &why); if (bad) return refuse(bad, why); }
+    const int max_rows = p->max_rows > 0 ? p->max_rows : OL_DEFAULT_MAX_ROWS;
+    if (widest > max_rows) return fail(h, FOT_ERR_INVALID, who + "max_rows lies below the largest window");
+    const int n_dense = resample_n_dense(p->dt, p->dt, (double)pred_len * p->dt, pred_len);
+    if (!ps_horizon_fits(1, pred_len, n_dense, 0) || n_dense > FOT_MAX_NT) return fail(h, FOT_ERR_INVALID, who + "dt: the dense grid does not hold pred_len steps");
+    const int R_all = ped_off[W];
+    const size_t elem = p->scene_dtype == FOT_F32 ? 4 : 8;
+    if (R_all > 0 && !scene) return fail(h, FOT_ERR_INVALID, who + "scene is NULL");
+    if (R_all > 0 && (p->flags & FOT_OPENLOOP_SCENE_DEVICE) && ((uintptr_t)scene % (2 * elem)) != 0) return fail(h, FOT_ERR_INVALID, who + "a device scene is aligned to one point");
+    OlTotals tot = ol_totals_zero();
+    if (W == 0) { std::memcpy(totals, &tot, sizeof tot); return FOT_OK; }
+    // the chunks: runs of whole windows of at most max_rows rows
+    std::vector<int32_t> chunk_w;                                  // first window of every chunk, then W
+    int cap_rows = 0, cap_win = 0;
+    for (int64_t w0 = 0; w0 < W;) {
+        const int64_t w1 = ol_chunk_end(ped_off, W, w0, max_rows);
+        chunk_w.push_back((int32_t)w0);
+        cap_rows = std::max(cap_rows, ped_off[w1] - ped_off[w0]);
+        cap_win = std::max(cap_win, (int)(w1 - w0));
+        w0 = w1;
+    }
+    const int n_chunks = (int)chunk_w.size();
+    chunk_w.push_back(W);
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    fot_handle::OpenLoop &O = h->ol;
+    // the call's tables, built in pinned memory and copied to HBM once: per row its column, first frame, window within
+    // its chunk, index within its window and noise slot; a run of zeros (the noise's step word, a scene row's index); per
+    // window its noise slot and its origin; per chunk the windows' first rows and first points, relative to the chunk
+    const size_t R_al = align256(sizeof(int32_t) * (size_t)std::max(R_all, 1)), W_al = align256(sizeof(int32_t) * (size_t)W);
+    const size_t zero_al = std::max(R_al, W_al), off_al = align256(sizeof(int32_t) * ((size_t)W + n_chunks));
+    const size_t blk_al = align256(sizeof(int64_t) * ((size_t)W + n_chunks)), desc_al = align256(sizeof(PredOriginDev) * (size_t)W);
+    const size_t tab_bytes = 5 * R_al + zero_al + W_al + off_al + blk_al + desc_al;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                   // (the pinned tables: nothing of an earlier call reads them)
+    HIP_TRY(h, O.hTab.ensure(tab_bytes));
+    HIP_TRY(h, O.dTab.ensure(tab_bytes));
+    HIP_TRY(h, O.hRec.ensure(sizeof(fot_pred_score) * (size_t)W));
+    char *ht = (char *)O.hTab.p;
+    int32_t *t_col = (int32_t *)ht, *t_f0 = (int32_t *)(ht + R_al), *t_win = (int32_t *)(ht + 2 * R_al);
+    int32_t *t_idx = (int32_t *)(ht + 3 * R_al), *t_slot = (int32_t *)(ht + 4 * R_al), *t_zero = (int32_t *)(ht + 5 * R_al);
+    int32_t *t_wslot = (int32_t *)(ht + 5 * R_al + zero_al), *t_off = (int32_t *)(ht + 5 * R_al + zero_al + W_al);
+    int64_t *t_blk = (int64_t *)(ht + 5 * R_al + zero_al + W_al + off_al);
+    PredOriginDev *t_desc = (PredOriginDev *)(ht + 5 * R_al + zero_al + W_al + off_al + blk_al);
+    std::memset(t_zero, 0, zero_al);
+    if (R_all > 0) std::memcpy(t_col, row_col, sizeof(int32_t) * (size_t)R_all);
+    const double scott = ps_scott(S);
+    for (int c = 0; c < n_chunks; ++c) {
+        const int w0 = chunk_w[(size_t)c], w1 = chunk_w[(size_t)c + 1], r0 = ped_off[w0];
+        for (int w = w0; w <= w1; ++w) {                           // (w1: the chunk's end)
+            t_off[w + c] = ped_off[w] - r0;
+            t_blk[w + c] = (int64_t)S * (ped_off[w] - r0) * n_dense;
+        }
+        for (int w = w0; w < w1; ++w) {
+            const int P = ped_off[w + 1] - ped_off[w];
+            t_wslot[w] = p->win_id0 + w;
+            t_desc[w] = PredOriginDev{ t_blk[w + c], (int64_t)(ped_off[w] - r0), scott, S, P, n_dense, 0, 0, 0 };
+            for (int q = 0; q < P; ++q) {
+                const int r = ped_off[w] + q;
+                t_f0[r] = win_frame0[w]; t_win[r] = w - w0; t_idx[r] = q; t_slot[r] = p->win_id0 + w;
+            }
+        }
+    }
+    // the work arrays of the largest chunk
+    HIP_TRY(h, O.dObs.ensure(sizeof(float) * 2 * (size_t)obs_len * std::max(cap_rows, 1)));
+    HIP_TRY(h, O.dAnchor.ensure(sizeof(double) * 2 * (size_t)std::max(cap_rows, 1)));
+    HIP_TRY(h, O.dTruth.ensure(sizeof(double) * 2 * (size_t)std::max(cap_rows, 1) * pred_len));
+    HIP_TRY(h, O.dDyn.ensure(sizeof(double) * 2 * (size_t)S * std::max(cap_rows, 1) * n_dense));
+    const bool with_noise = !cv && nd > 0;
+    if (!cv && cap_rows > 0) {
+        HIP_TRY(h, O.dRaw.ensure(sizeof(float) * 2 * (size_t)S * pred_len * cap_rows));
+        if (with_noise) HIP_TRY(h, O.dNoise.ensure(sizeof(float) * (size_t)S * (global_noise ? cap_win : cap_rows) * nd));
+        { int r = sgan_reserve(h, p->model, cap_rows, S); if (r != FOT_OK) return r; }
+    }
+    const size_t noise_rows_all = global_noise ? (size_t)W : (size_t)R_all;
+    const bool given_noise = with_noise && noise && noise_rows_all > 0;
+    const bool noise_up = given_noise && !(p->flags & FOT_OPENLOOP_NOISE_DEVICE);
+    const size_t scene_bytes = elem * 2 * (size_t)p->n_frames * (size_t)p->n_cols;
+    const bool scene_up = R_all > 0 && !(p->flags & FOT_OPENLOOP_SCENE_DEVICE);
+    if (scene_up) HIP_TRY(h, O.dScene.ensure(scene_bytes));
+    if (noise_up) HIP_TRY(h, O.dNoiseAll.ensure(sizeof(float) * (size_t)S * noise_rows_all * nd));
+    { int r = order_begin(h, st); if (r != FOT_OK) return r; }
+    HIP_TRY(h, hipMemcpyAsync(O.dTab.p, O.hTab.p, tab_bytes, hipMemcpyHostToDevice, st));
+    const void *d_scene = scene;
+    if (scene_up) { HIP_TRY(h, hipMemcpyAsync(O.dScene.p, scene, scene_bytes, hipMemcpyHostToDevice, st)); d_scene = O.dScene.p; }
+    const float *d_noise_all = (const float *)noise;
+    if (noise_up) {
+        HIP_TRY(h, hipMemcpyAsync(O.dNoiseAll.p, noise, sizeof(float) * (size_t)S * noise_rows_all * nd, hipMemcpyHostToDevice, st));
+        d_noise_all = O.dNoiseAll.as<float>();
+    }
+    const char *dt_ = (const char *)O.dTab.p;
+    auto dev = [&](const void *host_ptr) { return dt_ + ((const char *)host_ptr - ht); };
+    const int32_t *d_col = (const int32_t *)dev(t_col), *d_f0 = (const int32_t *)dev(t_f0), *d_win = (const int32_t *)dev(t_win);
+    const int32_t *d_idx = (const int32_t *)dev(t_idx), *d_slot = (const int32_t *)dev(t_slot), *d_zero = (const int32_t *)dev(t_zero);
+    const int32_t *d_wslot = (const int32_t *)dev(t_wslot), *d_off = (const int32_t *)dev(t_off);
+    const int64_t *d_blk = (const int64_t *)dev(t_blk);
+    const PredOriginDev *d_desc = (const PredOriginDev *)dev(t_desc);
+    fot_pred_score *rec = (fot_pred_score *)O.hRec.p;
+    // per chunk: gather -> noise -> generator | constant velocity -> resampler -> scorer, nothing synchronised in between
+    for (int c = 0; c < n_chunks; ++c) {
+        const int w0 = chunk_w[(size_t)c], w1 = chunk_w[(size_t)c + 1], nw = w1 - w0, r0 = ped_off[w0], R = ped_off[w1] - r0;
+        if (R > 0) {
+            OpenLoopRows g{};
+            g.scene = d_scene; g.row_col = d_col + r0; g.row_f0 = d_f0 + r0;
+            g.dtype = p->scene_dtype; g.n_cols = p->n_cols; g.rows = R; g.obs_len = obs_len; g.pred_len = pred_len;
+            g.obs = O.dObs.as<float2>(); g.anchor = O.dAnchor.as<double2>(); g.truth = O.dTruth.as<double2>();
+            LAUNCH_TRY(h, launch_openloop_rows(g, st));
+            if (cv) {
+                // k_resample's float32-observation path (cv = 2): the velocity from the window's last two rows
+                const float *prev = obs_len >= 2 ? O.dObs.as<float>() + 2 * (size_t)(obs_len - 2) * R : nullptr;
+                LAUNCH_TRY(h, launch_resample(p->dt, p->dt, 0.0, 1, pred_len, R, n_dense, 1, 0, 2, prev, FOT_F32, O.dAnchor.as<double>(),
+                                              nullptr, O.dDyn.p, FOT_F64, 0, st, d_win + r0, d_off + w0 + c, d_blk + w0 + c));
+            } else {
+                if (given_noise) {                                 // the chunk's rows of every sample of the call's tensor
+                    const size_t first = global_noise ? (size_t)w0 : (size_t)r0, n = global_noise ? (size_t)nw : (size_t)R;
+                    HIP_TRY(h, hipMemcpy2DAsync(O.dNoise.p, sizeof(float) * n * nd, d_noise_all + first * nd, sizeof(float) * noise_rows_all * nd,
+                                                sizeof(float) * n * nd, (size_t)S, hipMemcpyDeviceToDevice, st));
+                } else if (with_noise) {
+                    SgNoise a{};
+                    a.seed = p->seed; a.kind = p->noise_kind; a.S = S; a.rows = global_noise ? nw : R; a.nd = nd; a.n_blk = (nd + 3) / 4;
+                    a.slot = global_noise ? d_wslot + w0 : d_slot + r0; a.step = d_zero; a.index = global_noise ? d_zero : d_idx + r0;
+                    a.out = (uint32_t *)O.dNoise.p;
+                    LAUNCH_TRY(h, launch_sgan_noise(a, st));
+                }
+                { int r = sgan_enqueue(h, p->model, nw, R, S, d_off + w0 + c, global_noise && nd > 0 ? d_win + r0 : nullptr, O.dObs.as<float>(),
+                                       O.dNoise.as<float>(), O.dRaw.as<float>(), st); if (r != FOT_OK) return r; }
+                if (raw_out)
+                    HIP_TRY(h, hipMemcpy2DAsync((float *)raw_out + 2 * (size_t)r0, sizeof(float) * 2 * (size_t)R_all, O.dRaw.p, sizeof(float) * 2 * (size_t)R,
+                                                sizeof(float) * 2 * (size_t)R, (size_t)S * pred_len, hipMemcpyDeviceToHost, st));
+                LAUNCH_TRY(h, launch_resample(p->dt, p->dt, 0.0, S, pred_len, R, n_dense, 1, 0, 0, O.dRaw.p, FOT_F32, O.dAnchor.as<double>(),
+                                              nullptr, O.dDyn.p, FOT_F64, 0, st, d_win + r0, d_off + w0 + c, d_blk + w0 + c));
+            }
+        }
+        LAUNCH_TRY(h, launch_pred_scores(d_desc + w0, nw, O.dDyn.p, FOT_F64, 1, pred_len, O.dTruth.as<double>(), rec + w0, st));
+    }
+    { int r = order_end(h, st); if (r != FOT_OK) return r; }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    for (int w = 0; w < W; ++w)
+        ol_fold(tot, rec[w].ade_scene, rec[w].fde_scene, rec[w].ade_agent_sum, rec[w].fde_agent_sum, rec[w].log_lik_sum, rec[w].n_peds,
+                rec[w].nll_count, rec[w].flags);
+    if (records) std::memcpy(records, rec, sizeof(fot_pred_score) * (size_t)W);
+    std::memcpy(totals, &tot, sizeof tot);
     return FOT_OK;
 }
 

@@ -10,6 +10,7 @@
 #include "fot_repsample.hpp"
 #include "fot_samplerec.hpp"
 #include "fot_sweep.hpp"
+#include "fot_openloop.hpp"
 
 namespace fot {
 
@@ -172,5 +173,19 @@ int launch_loop_score_truth(ReplayView rv, const int32_t *slot_of, FrameDev f, i
 // other fields of the record are the host's.  Changes nothing in HBM.
 int launch_loop_summary(SummaryShape S, const double *ring, const int32_t *ring_P, const SummaryTotals *totals,
                         const int32_t *steps, int n_slots, int num_samples, fot_loop_summary *out, hipStream_t st);
+// ---- fot_openloop_eval (fot_openloop.hpp): the rows of a chunk of windows gathered from the scene [n_frames][n_cols][2]
+// (HBM, element type dtype: FOT_F32 | FOT_F64).  Row r is column row_col[r] of the window that starts at frame row_f0[r]
+// (HBM tables; the host has checked every row against the scene): its observation window in float32, obs [obs_len][rows]
+// [2]; its anchor, that float32 last observation widened, anchor [rows][2]; its truth, frames obs_len .. obs_len +
+// pred_len - 1 of the window in float64, truth [rows][pred_len][2] -- what sgan_enqueue / launch_resample /
+// launch_pred_scores read.
+struct OpenLoopRows {
+    const void *scene;
+    const int32_t *row_col, *row_f0;         // [rows]
+    int32_t dtype, n_cols, rows, obs_len, pred_len, _pad;
+    float2 *obs;
+    double2 *anchor, *truth;
+};
+int launch_openloop_rows(const OpenLoopRows &a, hipStream_t st);
 
 }  // namespace fot

@@ -699,6 +699,48 @@ k_loop_rep_block_sweep(const int32_t *__restrict__ slot_of, FrameDev f, const do
 }
 
 // ---------------------------------------------------------------------------
+// fot_openloop_eval (fot_openloop.hpp): the rows of a chunk of windows out of the resident scene
+// ---------------------------------------------------------------------------
+// One workgroup per OL_TILE_ROWS rows of the chunk.  Row r reads scene point (row_f0[r] + t, row_col[r]) for t = 0 ..
+// obs_len + pred_len - 1.  A frame's columns are contiguous and the rows of a window are mostly ascending columns, so the
+// lanes run over the ROWS of one frame and the waves over the frames: a wave's loads fall into one or two runs of a
+// frame's columns.  The observation window [obs_len][rows][2] has the rows innermost too: a wave stores 64 adjacent
+// float2.  The truth [rows][pred_len][2] has them outermost -- a tile's block of it is ONE contiguous run, so the loads
+// go through LDS (row-major, as the block lies in HBM) and the block is written out linearly, adjacent lanes adjacent
+// double2.  No atomics; every output element is written once by one thread.
+constexpr int OL_THREADS = 256;
+static_assert(OL_THREADS % OL_TILE_ROWS == 0 && OL_MAX_PRED_LEN == FOT_MAX_PRED_LEN, "tile rows divide the workgroup");
+
+template <typename V2>
+__global__ void __launch_bounds__(OL_THREADS)
+k_openloop_rows(OpenLoopRows A)
+{
+    __shared__ double2 s_truth[OL_TILE_ROWS * FOT_MAX_PRED_LEN];         // 32 KB
+    const V2 *__restrict__ scene = (const V2 *)A.scene;
+    const int row0 = blockIdx.x * OL_TILE_ROWS;
+    const int tile_rows = min(OL_TILE_ROWS, A.rows - row0);               // >= 1: the grid is ceil(rows / tile)
+    const int lr = threadIdx.x % OL_TILE_ROWS, t_first = threadIdx.x / OL_TILE_ROWS;
+    constexpr int T_STEP = OL_THREADS / OL_TILE_ROWS;
+    if (lr < tile_rows) {
+        const int r = row0 + lr;
+        const int32_t f0 = A.row_f0[r], col = A.row_col[r];
+        for (int t = t_first; t < A.obs_len; t += T_STEP) {
+            const V2 v = scene[ol_scene_point(f0, t, A.n_cols, col)];
+            const float2 o = make_float2(ol_observe((double)v.x), ol_observe((double)v.y));
+            A.obs[(int64_t)t * A.rows + r] = o;
+            if (t == A.obs_len - 1) A.anchor[r] = make_double2((double)o.x, (double)o.y);
+        }
+        for (int j = t_first; j < A.pred_len; j += T_STEP) {
+            const V2 v = scene[ol_scene_point(f0, A.obs_len + j, A.n_cols, col)];
+            s_truth[lr * A.pred_len + j] = make_double2((double)v.x, (double)v.y);
+        }
+    }
+    __syncthreads();
+    double2 *__restrict__ dst = A.truth + (int64_t)row0 * A.pred_len;
+    for (int i = threadIdx.x; i < tile_rows * A.pred_len; i += OL_THREADS) dst[i] = s_truth[i];
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
 
@@ -884,6 +926,19 @@ int launch_loop_score_truth(ReplayView rv, const int32_t *slot_of, FrameDev f, i
     if (stride < 1 || E < 1 || E > FOT_MAX_PRED_LEN) return (int)hipErrorInvalidValue;
     const int n = n_rows * E;
     k_loop_score_truth<<<(n + 255) / 256, 256, 0, st>>>(rv, slot_of, f, n_rows, f_cur, stride, E, (double2 *)out);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_openloop_rows(const OpenLoopRows &a, hipStream_t st)
+{
+    if (a.rows <= 0) return 0;
+    if (a.obs_len < 1 || a.pred_len < 1 || a.pred_len > FOT_MAX_PRED_LEN || a.n_cols < 1 || !a.scene || !a.row_col ||
+        !a.row_f0 || !a.obs || !a.anchor || !a.truth)
+        return (int)hipErrorInvalidValue;
+    const unsigned grid = (unsigned)((a.rows + OL_TILE_ROWS - 1) / OL_TILE_ROWS);
+    if (a.dtype == FOT_F32) k_openloop_rows<float2><<<grid, OL_THREADS, 0, st>>>(a);
+    else k_openloop_rows<double2><<<grid, OL_THREADS, 0, st>>>(a);
     FOT_LAUNCH_CHECK();
     return 0;
 }

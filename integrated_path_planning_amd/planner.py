@@ -817,6 +817,63 @@ class BatchPlanner:
                                                                  _addr(truth) if truth.size else None, _addr(out)))
         return out[:int(n_episodes)]
 
+    def openloop_eval(self, scene, win_frame0, ped_off, row_col, obs_len: int, pred_len: int, dt: float, method: int,
+                      model: int = 0, num_samples: int = 1, noise=None, seed: int = 0, noise_kind: int = _abi.NOISE_GAUSSIAN,
+                      win_id0: int = 0, max_rows: int = 0, want_records: bool = True, want_raw: bool = False,
+                      stream: Optional[int] = None):
+        """``fot_openloop_eval``: the open-loop prediction evaluation of the windows (win_frame0, ped_off, row_col) of
+        ``scene`` [n_frames, n_cols, 2] -- a NumPy array or a contiguous ``torch`` CUDA tensor, float32 or float64 -- in one
+        call.  method: ``_abi.OPENLOOP_CV`` or ``_abi.OPENLOOP_SGAN`` with the loaded ``model``; noise: None (the counter
+        noise of ``seed`` / ``noise_kind`` / ``win_id0``), a NumPy array or a CUDA tensor [S, rows, noise_dim] float32.
+        Returns ``(totals, records, raw)``: the ``_abi.OpenLoopTotals``, the windows' ``PRED_SCORE_DT`` records (None
+        without ``want_records``) and, with ``want_raw``, the generator's raw samples [S, pred_len, rows, 2] float32."""
+        f0, off, col = (np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (win_frame0, ped_off, row_col))
+        n_win = len(f0)
+        if len(off) != n_win + 1 or (len(off) and len(col) != max(int(off[-1]), 0)):
+            raise ValueError("openloop_eval: ped_off holds n_windows + 1 offsets and row_col one column per row")
+        flags = 0
+        if hasattr(scene, "data_ptr"):
+            import torch
+            if not (scene.is_cuda and scene.is_contiguous() and scene.dtype in (torch.float32, torch.float64)):
+                raise TypeError("openloop_eval: a contiguous CUDA tensor of float32 or float64")
+            code, shape, s_ptr = (_abi.F32 if scene.dtype == torch.float32 else _abi.F64), tuple(scene.shape), scene.data_ptr()
+            flags |= _abi.OPENLOOP_SCENE_DEVICE
+            if stream is None:
+                torch.cuda.current_stream(scene.device).synchronize()    # (the library reads it on its own stream)
+        else:
+            scene = np.ascontiguousarray(scene, dtype=np.float32 if np.asarray(scene).dtype == np.float32 else np.float64)
+            code, shape, s_ptr = (_abi.F32 if scene.dtype == np.float32 else _abi.F64), scene.shape, scene.ctypes.data
+        if len(shape) != 3 or shape[2] != 2:
+            raise ValueError(f"openloop_eval: a scene is [n_frames, n_cols, 2], got {tuple(shape)}")
+        n_ptr = None
+        if noise is not None:
+            if hasattr(noise, "data_ptr"):
+                import torch
+                if not (noise.is_cuda and noise.is_contiguous() and noise.dtype == torch.float32):
+                    raise TypeError("openloop_eval: noise is a contiguous float32 CUDA tensor or a NumPy array")
+                n_ptr = noise.data_ptr()
+                flags |= _abi.OPENLOOP_NOISE_DEVICE
+                if stream is None:
+                    torch.cuda.current_stream(noise.device).synchronize()
+            else:
+                noise = np.ascontiguousarray(noise, dtype=np.float32)
+                n_ptr = noise.ctypes.data
+            if len(noise.shape) != 3 or noise.shape[0] != int(num_samples):
+                raise ValueError(f"openloop_eval: noise is [S = {int(num_samples)}, rows, noise_dim], got {tuple(noise.shape)}")
+        prm = _abi.OpenLoopParams(int(shape[0]), int(shape[1]), n_win, code, int(obs_len), int(pred_len), int(method), int(model),
+                                  int(num_samples), int(noise_kind), int(win_id0), int(max_rows), flags, 0, float(dt),
+                                  int(seed) & 0xFFFFFFFFFFFFFFFF)
+        rows = int(off[-1]) if len(off) else 0
+        records = np.zeros(max(n_win, 1), dtype=self.PRED_SCORE_DT) if want_records else None
+        raw = np.zeros((int(num_samples), int(pred_len), max(rows, 0), 2), np.float32) if want_raw else None
+        totals = _abi.OpenLoopTotals()
+        _abi.check(self._h, self._lib.fot_openloop_eval(
+            self._h, C.byref(prm), C.c_void_p(s_ptr) if s_ptr else None, _addr(f0) if n_win else None, _addr(off),
+            _addr(col) if len(col) else None, C.c_void_p(n_ptr) if n_ptr else None,
+            _addr(records) if want_records else None, _addr(raw) if want_raw and raw.size else None, C.byref(totals),
+            C.c_void_p(stream) if stream else None))
+        return totals, (records[:n_win] if want_records else None), raw
+
     def _loop_frame(self, frame: dict):
         """fot_loop_frame from the dictionary ``loop_plan`` / ``loop_step`` take (+ the arrays it points into)."""
         f, keep = _abi.LoopFrame(), []

@@ -12,7 +12,7 @@ names; PyTorch-ROCm only draws the noise.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -576,6 +576,134 @@ class SganSampler:
         return out
 
     __call__ = sample
+
+
+# ---- open-loop prediction evaluation of a recorded scene (fot_openloop_eval) ---------------------------------------------------
+class WindowTable(NamedTuple):
+    """The fixed-population windows of a scene as ``fot_openloop_eval`` reads them: window w covers ``seq_len`` frames from
+    ``win_frame0[w]`` on and the scene columns ``row_col[ped_off[w]:ped_off[w + 1]]``."""
+    win_frame0: np.ndarray
+    ped_off: np.ndarray
+    row_col: np.ndarray
+
+    @property
+    def n_windows(self) -> int:
+        return len(self.win_frame0)
+
+    def window(self, scene_xy, w: int, seq_len: int) -> np.ndarray:
+        """Window w as the reference's ``extract_fixed_windows`` returns it: [seq_len, N, 2] float64."""
+        cols = self.row_col[self.ped_off[w]:self.ped_off[w + 1]]
+        f0 = int(self.win_frame0[w])
+        return np.asarray(scene_xy)[f0:f0 + int(seq_len)][:, cols].astype(np.float64)
+
+
+def fixed_windows(scene_xy, seq_len: int, stride: int = 1, min_peds: int = 1, max_windows: Optional[int] = None) -> WindowTable:
+    """``extract_fixed_windows`` (reference src/datasets/eth_ucy_loader.py:154-182) on a dense scene: scene_xy [F, ids, 2]
+    with NaN where a pedestrian is absent, the columns in ascending id order.  Every start 0, stride, .. <= F - seq_len
+    whose window has at least ``min_peds`` pedestrians present in ALL its frames is a window of exactly those pedestrians,
+    in column order; ``max_windows`` keeps the first ones.  Vectorised: one cumulative sum over the frames."""
+    if int(seq_len) <= 0:
+        raise ValueError("seq_len must be positive")
+    if int(stride) <= 0:
+        raise ValueError("stride must be positive")
+    xy = np.asarray(scene_xy)
+    if xy.ndim != 3 or xy.shape[2] != 2:
+        raise ValueError(f"fixed_windows: a scene is [n_frames, n_ids, 2], got {xy.shape}")
+    F, n_ids = xy.shape[0], xy.shape[1]
+    starts = np.arange(0, F - int(seq_len) + 1, int(stride), dtype=np.int64)
+    present = ~np.isnan(xy).any(axis=2)                               # [F, ids]
+    run = np.concatenate([np.zeros((1, n_ids), np.int64), np.cumsum(present, axis=0, dtype=np.int64)])
+    full = (run[starts + int(seq_len)] - run[starts]) == int(seq_len) if len(starts) else np.zeros((0, n_ids), bool)
+    counts = full.sum(axis=1)
+    keep = counts >= int(min_peds)
+    if max_windows is not None:
+        keep &= np.cumsum(keep) <= int(max_windows)
+    w_idx, cols = np.nonzero(full[keep])                              # (row-major: window by window, ascending columns)
+    ped_off = np.concatenate([[0], np.cumsum(counts[keep])]).astype(np.int32)
+    return WindowTable(starts[keep].astype(np.int32), ped_off, cols.astype(np.int32))
+
+
+OPEN_LOOP_CSV_COLUMNS = ("scene", "method", "seed", "num_samples", "n_windows", "n_trajectories", "ade", "fde", "ade_per_agent",
+                         "fde_per_agent", "nll")                     # the reference's header (run_openloop_prediction.py:216-217)
+_OPEN_LOOP_POOLING = {"lstm": _abi.SGAN_POOL_NONE, "sgan": _abi.SGAN_POOL_NET}
+
+
+def open_loop_result(totals) -> dict:
+    """``evaluate_scene``'s result dictionary from the totals of ``fot_openloop_eval`` (run_openloop_prediction.py:143-151):
+    NaN where nothing was counted."""
+    nan = float("nan")
+    n, n_nll = int(totals.traj_count), int(totals.nll_count)
+    return {"n_windows": int(totals.n_windows), "n_trajectories": n,
+            "ade": totals.sum_ade / n if n else nan, "fde": totals.sum_fde / n if n else nan,
+            "ade_per_agent": totals.sum_ade_agent / n if n else nan, "fde_per_agent": totals.sum_fde_agent / n if n else nan,
+            "nll": totals.sum_nll / n_nll if n_nll else nan}
+
+
+def evaluate_open_loop(engine: BatchPlanner, scene_xy, obs_len: int, pred_len: int, dt: float, method: str,
+                       weights_or_model=None, num_samples: int = 20, seed: int = 0, stride: int = 1, min_peds: int = 1,
+                       max_windows: Optional[int] = None, windows: Optional[WindowTable] = None, noise=None,
+                       noise_kind: Optional[int] = None, win_id0: int = 0, max_rows: int = 0, model_slot: int = 0,
+                       records: bool = False, raw: bool = False) -> dict:
+    """The reference's open-loop prediction evaluation of a scene (examples/run_openloop_prediction.py: ``evaluate_scene``
+    over ``extract_fixed_windows``, RQ1a) in one library call, ``fot_openloop_eval``.
+
+    scene_xy [F, ids, 2]: NaN where a pedestrian is absent (a NumPy array; with ``windows`` given also a CUDA tensor, used
+    where it lies).  method 'cv' (one sample, ``num_samples`` ignored as in the reference's script), 'lstm' (a generator
+    without pooling) or 'sgan' (pool net); weights_or_model: ``SganWeights`` -- loaded into ``model_slot`` --, or the slot of
+    a model that is loaded already (``noise_kind`` then says how it draws; default Gaussian).  The no-pooling and the pooled
+    model of a scene live side by side in two slots and evaluate the same ``windows`` in two calls.  noise: None -- the
+    library's counter noise of ``seed`` (``fot_sgan_noise``; window w's slot word is ``win_id0 + w``) --, or the tensor
+    [S, rows, noise_dim].  Returns ``n_windows, n_trajectories, ade, fde, ade_per_agent, fde_per_agent, nll`` as the
+    reference does (NaN where it gives NaN); with ``records`` / ``raw`` also ``records`` (one ``PRED_SCORE_DT`` per window)
+    and ``windows`` / ``raw`` (the generator's raw samples)."""
+    method = str(method).lower()
+    if method not in ("cv", "lstm", "sgan"):
+        raise ValueError(f"Invalid method '{method}'. Must be one of ['cv', 'lstm', 'sgan']")
+    if windows is None:
+        windows = fixed_windows(scene_xy, int(obs_len) + int(pred_len), stride=stride, min_peds=min_peds, max_windows=max_windows)
+    lib = _abi.lib()
+    if method == "cv":
+        code, model, S = _abi.OPENLOOP_CV, 0, 1
+    else:
+        code, S = _abi.OPENLOOP_SGAN, int(num_samples)
+        if isinstance(weights_or_model, SganWeights):
+            w = weights_or_model
+            if w.desc.pooling_type != _OPEN_LOOP_POOLING[method]:     # trajectory_predictor.py:114-121
+                raise ValueError(f"method='{method}' requires a {'no-pooling' if method == 'lstm' else 'pool_net'} generator")
+            if noise is None and noise_kind is None:
+                if w.noise_type not in _NOISE_TYPES:
+                    raise ValueError(f'Unrecognized noise type "{w.noise_type}"')
+                noise_kind = _abi.NOISE_GAUSSIAN if w.noise_type == "gaussian" else _abi.NOISE_UNIFORM_SYM
+            model = int(model_slot)
+            _abi.check(engine._h, lib.fot_sgan_load_model(engine._h, model, C.byref(w.desc), w.blob.size, w.blob.ctypes.data))
+        elif weights_or_model is None:
+            raise ValueError(f"method='{method}' needs SganWeights or the slot of a loaded model")
+        else:
+            model = int(weights_or_model)
+    totals, rec, raw_out = engine.openloop_eval(
+        scene_xy, windows.win_frame0, windows.ped_off, windows.row_col, obs_len, pred_len, dt, code, model=model, num_samples=S,
+        noise=noise, seed=seed, noise_kind=_abi.NOISE_GAUSSIAN if noise_kind is None else int(noise_kind), win_id0=win_id0,
+        max_rows=max_rows, want_records=records, want_raw=raw and method != "cv")
+    out = open_loop_result(totals)
+    if records:
+        out["records"], out["windows"] = rec, windows
+    if raw:
+        out["raw"] = raw_out
+    return out
+
+
+def append_open_loop_csv(path, scene: str, method: str, seed: int, num_samples: int, result: dict) -> None:
+    """Append a result row under the reference's CSV header (run_openloop_prediction.py:213-229): the header goes in when
+    the file is absent or empty."""
+    import os
+    parent = os.path.dirname(os.path.abspath(path))
+    os.makedirs(parent, exist_ok=True)
+    need_header = not os.path.exists(path) or os.path.getsize(path) == 0
+    with open(path, "a") as f:
+        if need_header:
+            f.write(",".join(OPEN_LOOP_CSV_COLUMNS) + "\n")
+        f.write(f"{scene},{method},{seed},{num_samples},{result['n_windows']},{result['n_trajectories']},{result['ade']},"
+                f"{result['fde']},{result['ade_per_agent']},{result['fde_per_agent']},{result['nll']}\n")
 
 
 class RecordedSamples:
