@@ -1062,6 +1062,67 @@ int fot_openloop_eval(fot_handle *h, const fot_openloop_params *p, const void *s
                       const int32_t *ped_off, const int32_t *row_col, const void *noise, fot_pred_score *records,
                       void *raw_out, fot_openloop_totals *totals, void *stream);
 
+/* ---- footprint re-verification of episodes (A-4): centre, circle cover, exact rectangle -----------------------------------------
+ * The reference's examples/recheck_footprint.py (recheck, reconstruct_yaw) and observational_footprint_metrics of
+ * examples/run_footprint_benchmark.py.  Every step of a trajectory -- the ego pose (x, y, yaw) and that step's pedestrians
+ * -- is measured against three geometries that do not depend on what the planner used:
+ *   legacy  the centre distance                  min_p sqrt((px - x)^2 + (py - y)^2)
+ *   multi   the n_circles cover of the rectangle  the same distance to the centres (x + off_k cos yaw, y + off_k sin yaw),
+ *           off_k = -L/2 + seg/2 + seg k, seg = L / n_circles, radius hypot(seg/2, W/2) (EgoFootprint.multi_circle)
+ *   rect    the exact oriented L x W rectangle    min_p hypot(max(|lx| - L/2, 0), max(|ly| - W/2, 0)), (lx, ly) the
+ *           pedestrian in the vehicle frame
+ * A step without pedestrians measures +inf three times.  A trajectory's record holds the minima over its steps and the
+ * steps strictly below each threshold: legacy < legacy_radius (the caller adds ego_radius + ped_radius), multi < radius +
+ * ped_radius, rect < ped_radius; clearance = minimum - threshold; all minima and clearances +inf without any pedestrian.
+ * One record serves both reference forms, which differ in key names only.  float64 throughout, NumPy's operation order
+ * (csrc/fot_footprint_obs.hpp).  Non-finite coordinates: unspecified.
+ *
+ * fot_footprint_recheck: n_traj ragged trajectories in ONE synchronous call (one wait).
+ *   step_off [n_traj + 1] host, from 0: trajectory t owns steps step_off[t] .. step_off[t + 1] - 1 of
+ *   xy [steps][2], yaw [steps] host; yaw == NULL: the heading is reconstructed on the device as reconstruct_yaw does --
+ *            np.gradient of x and y (one-sided at both ends), a step moves when hypot(dx, dy) > 1e-4, its heading is
+ *            atan2(dy, dx); a standing step holds the last moving heading, the steps in front of the first moving one
+ *            take that first heading, a trajectory that never moves is all zeros
+ *   ped_off [steps + 1] host, non-decreasing from 0;  ped_xy [ped_off[steps]][2] host: every step's pedestrians
+ *   series   NULL, or [steps] records of the steps;  yaw_out  NULL, or [steps]: the heading used
+ *   out      [n_traj] records
+ * A trajectory's record and series are byte-identical whatever trajectories share the call.
+ * Refusals (FOT_ERR_INVALID, a refused call changes nothing): geom / out / a table NULL; n_traj < 0; offsets that do not
+ * start at 0 or that decrease; a trajectory of 0 steps, or of 1 step with yaw == NULL (the gradient needs two);
+ * vehicle_length or vehicle_width not positive, a negative radius, n_circles outside 1 .. FOT_MAX_CIRCLES.
+ *
+ * fot_loop_footprint_enable: accepted after fot_loop_begin* and before the loop's first step; geom == NULL switches it off
+ * again.  While on, every lock step of fot_loop_step and fot_loop_run launches the per-step kernel right behind the
+ * k_safety launch of the NEW ego states, on the same poses and the same frame rows (the reference pairs the new ego state
+ * with that step's pedestrians, integrated_simulator.py:707-727); the records land in pinned memory and are folded per
+ * slot at the wait the step already has.  A loop that never enables it launches and allocates nothing for it; the
+ * five-call form (fot_loop_plan / fot_loop_observe_*) names no slots and accumulates nothing.  fot_loop_begin* drops the
+ * accumulators and switches it off.  fot_loop_footprint_obs copies the per-slot records (steps: lock steps folded so far);
+ * it may be called between two fot_loop_run calls and changes nothing.
+ * Refusals (FOT_ERR_INVALID, nothing changed): no loop begun; enabling after the first step; a bad geometry;
+ * fot_loop_footprint_obs: not enabled, n_slots differing from the loop's, out NULL.
+ * Additions: no structure, capacity word of fot_abi_info or FOT_ABI_VERSION changes; a binding looks the symbols up. */
+typedef struct fot_footprint_geom {
+    double vehicle_length, vehicle_width, ped_radius, legacy_radius;
+    int32_t n_circles;              /* 1 .. FOT_MAX_CIRCLES */
+    int32_t _pad;
+} fot_footprint_geom;
+typedef struct fot_footprint_step {
+    double legacy, multi, rect;
+} fot_footprint_step;
+typedef struct fot_footprint_obs {
+    double legacy_min_dist;
+    double multi_min_dist, multi_clearance;
+    double rect_min_surface_dist, rect_clearance;
+    int32_t legacy_collision_steps, multi_violation_steps, rect_violation_steps;
+    int32_t steps, steps_with_peds, _pad;
+} fot_footprint_obs;
+int fot_footprint_recheck(fot_handle *h, const fot_footprint_geom *geom, int32_t n_traj, const int32_t *step_off,
+                          const double *xy, const double *yaw, const int32_t *ped_off, const double *ped_xy,
+                          fot_footprint_step *series, double *yaw_out, fot_footprint_obs *out);
+int fot_loop_footprint_enable(fot_handle *h, const fot_footprint_geom *geom);
+int fot_loop_footprint_obs(fot_handle *h, int32_t n_slots, fot_footprint_obs *out);
+
 /* Host utility (no GPU): the first kmax samples of the 15 path arrays of records[index[i]], i < n, as one dense block
  * out[15][n][kmax] in fot_result array order (t .. c) -- what a history keeps of a step's records. */
 int fot_gather_paths(const fot_result *records, int32_t n, const int32_t *index, int32_t kmax, double *out);

@@ -173,6 +173,23 @@ OPENLOOP_CV, OPENLOOP_SGAN = 0, 1        # FOT_OPENLOOP_* methods
 OPENLOOP_SCENE_DEVICE, OPENLOOP_NOISE_DEVICE = 1, 2
 
 
+class FootprintGeom(C.Structure):                                 # fot_footprint_geom
+    _fields_ = [(n, C.c_double) for n in ("vehicle_length", "vehicle_width", "ped_radius", "legacy_radius")] + \
+               [("n_circles", C.c_int32), ("_pad", C.c_int32)]
+
+
+class FootprintStep(C.Structure):                                 # fot_footprint_step
+    _fields_ = [(n, C.c_double) for n in ("legacy", "multi", "rect")]
+
+
+FOOTPRINT_OBS_F64 = ("legacy_min_dist", "multi_min_dist", "multi_clearance", "rect_min_surface_dist", "rect_clearance")
+FOOTPRINT_OBS_I32 = ("legacy_collision_steps", "multi_violation_steps", "rect_violation_steps", "steps", "steps_with_peds")
+
+
+class FootprintObs(C.Structure):                                  # fot_footprint_obs
+    _fields_ = [(n, C.c_double) for n in FOOTPRINT_OBS_F64] + [(n, C.c_int32) for n in FOOTPRINT_OBS_I32 + ("_pad",)]
+
+
 class Batch(C.Structure):
     _fields_ = [("n_inst", C.c_int32), ("obstacle_dtype", C.c_int32),
                 ("ego", C.POINTER(Ego)), ("target_speed", C.POINTER(C.c_double)),
@@ -201,7 +218,8 @@ SYMBOLS = ["fot_version", "fot_abi_info", "fot_create", "fot_destroy", "fot_live
            "fot_loop_plan_sample", "fot_loop_run_best_samples", "fot_debug_loop_block", "fot_loop_set_samples",
            "fot_loop_begin_sweep", "fot_loop_set_samples_shared", "fot_loop_set_sampler_shared", "fot_debug_loop_sampler_shape",
            "fot_sgan_max_models", "fot_sgan_load_model", "fot_sgan_unload_model", "fot_sgan_sample_model",
-           "fot_loop_set_sampler_models", "fot_debug_loop_sampler_shapes", "fot_openloop_eval"]
+           "fot_loop_set_sampler_models", "fot_debug_loop_sampler_shapes", "fot_openloop_eval",
+           "fot_footprint_recheck", "fot_loop_footprint_enable", "fot_loop_footprint_obs"]
 LOOP_PLAN_DISTRIBUTION, LOOP_PLAN_REPRESENTATIVE = 0, 1      # FOT_LOOP_PLAN_* (fot_loop_plan_sample)
 PROFILE_KERNELS = 3                      # FOT_PROFILE_KERNELS (include/fot.h)
 ABI_VERSION = 8                          # FOT_ABI_VERSION
@@ -470,7 +488,10 @@ def lib():
                        ("fot_loop_set_sampler_models", [vp, C.c_int32, C.c_uint64, C.c_int32, vp, C.c_int32, vp, vp]),
                        ("fot_debug_loop_sampler_shapes", [vp, C.c_int32, vp, vp]),
                        ("fot_openloop_eval", [vp, C.POINTER(OpenLoopParams), vp, vp, vp, vp, vp, vp, vp,
-                                              C.POINTER(OpenLoopTotals), vp])):
+                                              C.POINTER(OpenLoopTotals), vp]),
+                       ("fot_footprint_recheck", [vp, C.POINTER(FootprintGeom), C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]),
+                       ("fot_loop_footprint_enable", [vp, C.POINTER(FootprintGeom)]),
+                       ("fot_loop_footprint_obs", [vp, C.c_int32, vp])):
         if hasattr(L, name):
             getattr(L, name).argtypes = args
     L.fot_gather_paths.argtypes = [vp, C.c_int32, vp, C.c_int32, vp]

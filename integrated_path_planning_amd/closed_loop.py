@@ -453,7 +453,7 @@ class BatchedClosedLoop:
     def __init__(self, config, ped_tracks: Sequence[np.ndarray], ego_initial_states: Optional[Sequence] = None,
                  device: int = -1, engine=None, resampler=None, sample_source=None, fused: Optional[bool] = None,
                  device_samples: bool = False, resident: bool = False, summaries: bool = False,
-                 prediction_scores: bool = False, plan_on_representative_sample: bool = False):
+                 prediction_scores: bool = False, plan_on_representative_sample: bool = False, footprint_obs=None):
         """sample_source: the multi-sample predictor in front of the planner -- a callable
         ``(obs_last [P, 2], obs_prev [P, 2]) -> raw samples [S, pred_len, P, 2]`` at the predictor's own time step
         (a source with the attribute ``needs_history = True``, such as ``prediction.SganSampler``, is called with the
@@ -505,6 +505,13 @@ class BatchedClosedLoop:
         samples every crowd once per lock step for all its conditions, fot_loop_set_sampler_shared; built on several
         ``SganWeights`` with ``slot_model=...`` it gives every slot its own model, fot_loop_set_sampler_models).  A list of one
         distinct scenario and one mode is today's loop.
+        footprint_obs: True, or a dictionary with any of ``vehicle_length``, ``vehicle_width``, ``n_circles``,
+        ``ped_radius`` (the reference's fixed 4.5 / 2.0 / 3 / 0.2 where missing): every lock step also measures the new ego
+        state against that step's pedestrians under three geometries that are the same whatever footprint the planner
+        used -- the centre, the circle cover and the exact rectangle (fot_loop_footprint_enable; the reference's
+        ``observational_footprint_metrics``) -- and ``footprint_metrics()`` returns the episodes' minima and violation
+        steps; ``save_summaries()`` appends them.  Resident loops and the one-call step; the five-call step and stand-in
+        engines raise ValueError.
         fused: True = the lock step behind one library call (fot_loop_step), False = five separate calls with the
         prediction through the host, None = one call where the engine and the predictor allow it."""
         if fused not in (None, False, True):
@@ -634,6 +641,15 @@ class BatchedClosedLoop:
         if self.scenarios is not None and not self._native:
             raise ValueError("episodes of different configurations need the one-call step: more than one configuration "
                              "is not supported by this engine")
+        self._footprint_obs = None
+        if footprint_obs is not None and footprint_obs is not False:
+            if not self._native or not hasattr(self.engine, "loop_footprint_enable"):
+                if self._owns_engine:
+                    self.engine.close()
+                raise ValueError("footprint_obs needs the one-call step or resident=True on the library's own engine (the "
+                                 "five-call step and stand-in engines do not accumulate it)")
+            from .safety import footprint_geometry
+            self._footprint_obs = footprint_geometry(None if footprint_obs is True else dict(footprint_obs))
         if self.scenarios is not None:
             for i, pts in enumerate(self.scenario_static_points):
                 self.engine.loop_set_scenario_static(i, pts)
@@ -707,6 +723,8 @@ class BatchedClosedLoop:
                 [fp_k is not None for fp_k in self.scenario_footprints], self.slot_scenario, self.ego)
         elif self._native:
             self.engine.loop_begin(loop_config_from(c, constants_of(c), self.MAX_REPLAN), self.ego)
+        if self._footprint_obs is not None:
+            self.engine.loop_footprint_enable(self._footprint_obs)
         if self._resident:
             self.engine.loop_set_replay(
                 self.ped_off, self.n_frames, self._ped_all["trajectories"], self._ped_all["velocities"],
@@ -1384,9 +1402,21 @@ class BatchedClosedLoop:
             out.append(d)
         return out
 
+    def footprint_metrics(self) -> List[Dict[str, Any]]:
+        """One dictionary per episode with the keys of the reference's ``observational_footprint_metrics`` over the lock
+        steps run so far: ``legacy_min_dist``, ``multi_clearance``, ``multi_violation_steps``, ``rect_clearance``,
+        ``rect_violation_steps`` (``inf`` where an episode never met a pedestrian).  Accumulated by the library
+        (``footprint_obs=...``); may be called between two ``run()`` calls."""
+        if self._footprint_obs is None:
+            raise ValueError("footprint_metrics() needs BatchedClosedLoop(..., footprint_obs=True | {...})")
+        from .safety import FOOTPRINT_METRIC_KEYS
+        rec = self.engine.loop_footprint_obs(len(self.episodes))
+        return [{k: (int(r[k]) if k.endswith("_steps") else float(r[k])) for k in FOOTPRINT_METRIC_KEYS} for r in rec]
+
     def save_summaries(self, output_path: str) -> str:
         """``metrics_summary.csv`` under output_path: one header, one row per episode, the reference's column names (its
-        wall-clock columns avg_/max_*_time are left out)."""
+        wall-clock columns avg_/max_*_time are left out); with ``footprint_obs`` the five columns of
+        ``footprint_metrics()`` follow."""
         import csv
         rows = self.aggregate_metrics()
         os.makedirs(output_path, exist_ok=True)
@@ -1394,6 +1424,11 @@ class BatchedClosedLoop:
         # the reference's row (integrated_simulator.py:1008-1028): context, the metrics, then the collision flag
         cols = (["episode", "prediction_method", "ego_target_speed", "termination_reason", "total_time", "steps"]
                 + list(self.SUMMARY_KEYS) + ["collision"])
+        if self._footprint_obs is not None:
+            from .safety import FOOTPRINT_METRIC_KEYS
+            fp_rows = self.footprint_metrics()
+            cols += list(FOOTPRINT_METRIC_KEYS)
+            rows = [dict(d, **f) for d, f in zip(rows, fp_rows)]
         with open(f, "w", newline="") as fh:
             w = csv.DictWriter(fh, fieldnames=cols)
             w.writeheader()

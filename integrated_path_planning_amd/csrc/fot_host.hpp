@@ -20,6 +20,7 @@
 #include "fot_loopscore.hpp"
 #include "fot_sgan.hpp"
 #include "fot_sweep.hpp"
+#include "fot_footprint_obs.hpp"
 
 // fot::host: internal to libfot.so -- hidden, so that what is declared here for the other host units is exported nowhere
 namespace fot { namespace host __attribute__((visibility("hidden"))) {
@@ -276,9 +277,23 @@ struct LoopRep {
     void release() { dBlk.release(); dBest.release(); dDev.release(); dPre.release(); hBest.release(); hPre.release(); }
 };
 
+// fot_loop_footprint_enable: the observational footprint metrics of a loop (fot_footprint_obs.hpp).  The geometry where
+// k_footprint_steps reads it, the records of a lock step's new ego states in pinned memory (sized for the loop's slots at
+// the enable call: it never grows inside a run) and the per-slot accumulators the host folds them into
+struct LoopFootprintObs {
+    bool on = false;
+    FpoGeom geom = FpoGeom();
+    PinnedBuf hGeom, hRec;                       // FpoGeom | FpoStep[slots]
+    std::vector<FpoAcc> acc;                     // [slots]
+    std::vector<int32_t> steps;                  // [slots] lock steps folded
+    void release() { hGeom.release(); hRec.release(); }
+};
+
 // fot_loop_*: what one closed-loop step leaves behind for the step's later calls
 struct LoopState {
     LoopEpisodes ep;
+    LoopFootprintObs fpo;
+    bool stepped = false;                    // a lock step has run since fot_loop_begin* (fot_loop_step or fot_loop_run)
     LoopReplay replay;
     LoopRep rep;
     PinnedBuf hFrame, hObserve, hOut, hRec;  // frame inputs | fot_loop_observe's inputs | small outputs | records
@@ -316,7 +331,7 @@ struct LoopState {
         hFrame.release(); hObserve.release(); hOut.release(); hRec.release();
         dDyn.release(); dStatic.release(); replay.release(); rep.release();
         dScenStatic.release(); dGather.release(); dSafScen.release(); hGather.release();
-        hSweep.release();
+        hSweep.release(); fpo.release();
     }
 };
 
@@ -384,6 +399,12 @@ struct fot_handle {
             hTab.release(); hRec.release();
         }
     } ol;
+    // fot_footprint_recheck: the inputs of a large call, the reconstructed headings, the steps' records and the
+    // trajectories' records in HBM (grow-only)
+    struct Footprint {
+        DevBuf dIn, dYaw, dSeries, dOut;
+        void release() { dIn.release(); dYaw.release(); dSeries.release(); dOut.release(); }
+    } fp;
     LoopState loop;
     // fot_sgan_*: the loaded models (descriptor, device image of the weights), each with the work arrays of its own sample
     // calls -- what model m computes never depends on what else is loaded or was sampled in between

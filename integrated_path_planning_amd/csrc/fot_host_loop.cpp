@@ -368,8 +368,9 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
 }
 
 // fot_loop_observe_begin; a scenario loop's frame (LoopState::frame_scen): ego i is measured with, and projected on the
-// path of, the scenario of episode i
-int observe_begin_impl(fot_handle *h, int32_t n, const double *ego5, const double *prev_s)
+// path of, the scenario of episode i.  fpo_slot: the slot of every ego, from the one-call step and the resident step -- with
+// fot_loop_footprint_enable on, the footprint observation of the same poses and frame rows follows k_safety
+int observe_begin_impl(fot_handle *h, int32_t n, const double *ego5, const double *prev_s, const int32_t *fpo_slot = nullptr)
 {
     if (!h) return FOT_ERR_INVALID;
     LoopState &L = h->loop;
@@ -403,6 +404,9 @@ int observe_begin_impl(fot_handle *h, int32_t n, const double *ego5, const doubl
     LAUNCH_TRY(h, launch_safety(h->dP.as<DevParams>(), n, p_ego, L.p_off, L.p_pos, L.p_vel, L.ego_radius, L.ped_radius,
                                 h->sc[0].params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st,
                                 L.p_scen, L.dSafScen.as<SafetyScen>()));
+    if (L.fpo.on && fpo_slot)
+        LAUNCH_TRY(h, launch_footprint_steps((const FpoGeom *)L.fpo.hGeom.p, n, p_ego, 4, p_ego + 2, 4, L.p_off, L.p_pos,
+                                             (FpoStep *)L.fpo.hRec.p, st));
     InstState *p_state = (InstState *)((char *)L.hOut.p + saf_b);
     PathSet ps = PathSet::single(spline_view(h, 0));
     if (by_scen) {                                               // the handle's path table, as a mixed plan batch passes it
@@ -417,6 +421,20 @@ int observe_begin_impl(fot_handle *h, int32_t n, const double *ego5, const doubl
     { int r = order_end(h, st); if (r != FOT_OK) return r; }
     L.observe_n = n;
     return FOT_OK;
+}
+
+// The lock step's footprint records into the slots' accumulators: k_footprint_steps ran behind k_safety on the new ego
+// states, and the caller has waited for the step's observation.  Ego i belongs to slot[i] and met episode i of the frame.
+void fpo_fold_step(LoopState &L, const int32_t *slot, int n)
+{
+    LoopFootprintObs &F = L.fpo;
+    if (!F.on) return;
+    const FpoStep *r = (const FpoStep *)F.hRec.p;
+    for (int i = 0; i < n; ++i) {
+        const size_t e = (size_t)slot[i];
+        fpo_acc_step(F.acc[e], F.geom, r[i].legacy, r[i].multi, r[i].rect, L.ped_off[(size_t)i + 1] > L.ped_off[(size_t)i]);
+        F.steps[e] += 1;
+    }
 }
 
 // ---- the whole lock step of n episodes behind ONE call (SURVEY 8 f2 + f4) -------------------------------------------
@@ -659,6 +677,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     hipStream_t st = h->stream;
     const int n = (int)sel.size(), n_slots = C.n_slots;
     { int r = order_begin(h, st); if (r != FOT_OK) return r; }
+    L.stepped = true;
     // --- 1. pedestrians + observer
     R.clock.advance();
     const bool ready = R.clock.ready();
@@ -1016,7 +1035,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     step_resolve(E, sel.data(), n, dig, W);
     std::vector<double> gps((size_t)n);
     for (int i = 0; i < n; ++i) gps[i] = E.goal_prev_s[sel[i]];
-    { int rc = fot_loop_observe_begin(h, n, W.ego5n.data(), gps.data()); if (rc != FOT_OK) return rc; }
+    { int rc = observe_begin_impl(h, n, W.ego5n.data(), gps.data(), sel.data()); if (rc != FOT_OK) return rc; }
     // the followed paths into the history block, and the word that tells the host the step's results are there
     int32_t *t_src = (int32_t *)R.hHistTab.p, *t_slot = t_src + n_slots;
     for (int i = 0; i < n; ++i) { t_src[i] = W.path_rec[i]; t_slot[i] = sel[i]; }
@@ -1024,6 +1043,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     LAUNCH_TRY(h, launch_loop_history(d_rec, n, t_src, t_slot, d_hist_step, n_slots, h->sc[0].P.n_total, word + 16, seq, st));
     { int rc = wait_word(h, word + 16, seq, st); if (rc != FOT_OK) return rc; }
     L.observe_n = -1;
+    fpo_fold_step(L, sel.data(), n);
     const fot_safety *after = (const fot_safety *)L.hOut.p;
     const InstState *p_state = (const InstState *)((const char *)L.hOut.p + align256(sizeof(fot_safety) * (size_t)n));
     const size_t row = (size_t)k * (size_t)n_slots;
@@ -1401,6 +1421,7 @@ int fot_loop_begin(fot_handle *h, int32_t n_episodes, const fot_loop_config *cfg
     h->loop.replay.sc.on = false;                                // ... and its scores
     h->loop.rep.mode = FOT_LOOP_PLAN_DISTRIBUTION; h->loop.rep.frame = false;
     h->loop.rep.last_best.assign(n, -1);
+    h->loop.fpo.on = false; h->loop.stepped = false;             // ... and the footprint observation's accumulators
     return FOT_OK;
 }
 
@@ -1463,6 +1484,7 @@ int fot_loop_begin_scenarios(fot_handle *h, int32_t n_episodes, int32_t n_cfg, c
     L.replay.sc.on = false;
     L.rep.mode = FOT_LOOP_PLAN_DISTRIBUTION; L.rep.frame = false;
     L.rep.last_best.assign(n, -1);
+    L.fpo.on = false; L.stepped = false;
     return FOT_OK;
 }
 
@@ -1510,6 +1532,7 @@ int fot_loop_step(fot_handle *h, const fot_loop_frame *frame, const int32_t *epi
                 return fail(h, FOT_ERR_NO_PATH_SET, "fot_loop_step: a slot's scenario has no path");
         }
     }
+    L.stepped = true;
     StepWork W;
     step_level0(E, episode, n, W);
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1543,7 +1566,7 @@ int fot_loop_step(fot_handle *h, const fot_loop_frame *frame, const int32_t *epi
     //     outputs filled while they run
     std::vector<double> gps((size_t)n);
     for (int i = 0; i < n; ++i) gps[i] = E.goal_prev_s[episode[i]];
-    { int rc = fot_loop_observe_begin(h, n, W.ego5n.data(), gps.data()); if (rc != FOT_OK) return rc; }
+    { int rc = observe_begin_impl(h, n, W.ego5n.data(), gps.data(), episode); if (rc != FOT_OK) return rc; }
     for (int i = 0; i < n; ++i) {
         const int e = episode[i];
         if (out->state) out->state[i] = E.state[e];
@@ -1552,6 +1575,7 @@ int fot_loop_step(fot_handle *h, const fot_loop_frame *frame, const int32_t *epi
     }
     std::vector<fot_safety> after((size_t)n);
     { int rc = fot_loop_observe_end(h, after.data(), gps.data()); if (rc != FOT_OK) return rc; }
+    fpo_fold_step(L, episode, n);
     for (int i = 0; i < n; ++i) {
         E.goal_prev_s[episode[i]] = gps[i];
         if (out->after) out->after[i] = after[i];
@@ -1932,6 +1956,48 @@ int fot_loop_run(fot_handle *h, int32_t max_steps, fot_loop_run_out *out)
         if (out->termination) out->termination[e] = R.termination[(size_t)e];
     }
     return done;
+}
+
+// ---- the observational footprint metrics of a loop (include/fot.h; fot_footprint_obs.hpp) ---------------------------------
+int fot_loop_footprint_enable(fot_handle *h, const fot_footprint_geom *geom)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopState &L = h->loop;
+    const std::string who = "fot_loop_footprint_enable: ";
+    if (!(L.ep.cfg.dt > 0.0)) return fail(h, FOT_ERR_INVALID, who + "fot_loop_begin* comes first");
+    if (L.stepped) return fail(h, FOT_ERR_INVALID, who + "the loop has stepped (enable between fot_loop_begin* and the first step)");
+    LoopFootprintObs &F = L.fpo;
+    if (!geom) { F.on = false; return FOT_OK; }
+    const char *why = "";
+    if (fpo_check_geom(geom->vehicle_length, geom->vehicle_width, geom->ped_radius, geom->legacy_radius, geom->n_circles, &why))
+        return fail(h, FOT_ERR_INVALID, who + why);
+    const size_t n = (size_t)std::max(L.ep.n, 1);
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                 // nothing may still read the geometry that is replaced
+    HIP_TRY(h, F.hGeom.ensure(sizeof(FpoGeom)));
+    HIP_TRY(h, F.hRec.ensure(sizeof(FpoStep) * n));
+    F.geom = fpo_geom(geom->vehicle_length, geom->vehicle_width, geom->ped_radius, geom->legacy_radius, geom->n_circles);
+    std::memcpy(F.hGeom.p, &F.geom, sizeof F.geom);
+    F.acc.assign(n, fpo_acc_zero());
+    F.steps.assign(n, 0);
+    F.on = true;
+    return FOT_OK;
+}
+
+int fot_loop_footprint_obs(fot_handle *h, int32_t n_slots, fot_footprint_obs *out)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopState &L = h->loop;
+    const std::string who = "fot_loop_footprint_obs: ";
+    if (!(L.ep.cfg.dt > 0.0)) return fail(h, FOT_ERR_INVALID, who + "fot_loop_begin* comes first");
+    if (!L.fpo.on) return fail(h, FOT_ERR_INVALID, who + "not enabled (fot_loop_footprint_enable)");
+    if (n_slots != L.ep.n) return fail(h, FOT_ERR_INVALID, who + "n_slots differs from the loop's");
+    if (n_slots > 0 && !out) return fail(h, FOT_ERR_INVALID, who + "out is NULL");
+    for (int e = 0; e < n_slots; ++e) {
+        const FpoRecord r = fpo_acc_record(L.fpo.acc[(size_t)e], L.fpo.geom, L.fpo.steps[(size_t)e]);
+        std::memcpy(&out[e], &r, sizeof r);
+    }
+    return FOT_OK;
 }
 
 }  // extern "C"

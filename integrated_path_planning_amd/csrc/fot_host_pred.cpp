@@ -719,4 +719,73 @@ int fot_openloop_eval(fot_handle *h, const fot_openloop_params *p, const void *s
     return FOT_OK;
 }
 
+// ---- footprint re-verification of trajectories (include/fot.h; the shared arithmetic and checks: fot_footprint_obs.hpp) ------
+int fot_footprint_recheck(fot_handle *h, const fot_footprint_geom *geom, int32_t n_traj, const int32_t *step_off,
+                          const double *xy, const double *yaw, const int32_t *ped_off, const double *ped_xy,
+                          fot_footprint_step *series, double *yaw_out, fot_footprint_obs *out)
+{
+    static_assert(sizeof(FpoStep) == sizeof(fot_footprint_step) && sizeof(FpoRecord) == sizeof(fot_footprint_obs) &&
+                  offsetof(FpoRecord, steps_with_peds) == offsetof(fot_footprint_obs, steps_with_peds),
+                  "FpoStep / FpoRecord are fot_footprint_step / fot_footprint_obs");
+    if (!h) return FOT_ERR_INVALID;
+    const std::string who = "fot_footprint_recheck: ";
+    if (!geom || !out) return fail(h, FOT_ERR_INVALID, who + "geom / out is NULL");
+    const char *why = "";
+    if (fpo_check_geom(geom->vehicle_length, geom->vehicle_width, geom->ped_radius, geom->legacy_radius, geom->n_circles, &why))
+        return fail(h, FOT_ERR_INVALID, who + why);
+    if (fpo_check_tables(n_traj, step_off, ped_off, yaw != nullptr, &why)) return fail(h, FOT_ERR_INVALID, who + why);
+    if (n_traj == 0) return FOT_OK;
+    const size_t steps = (size_t)step_off[n_traj], n_ped = (size_t)ped_off[steps];
+    if (!xy || (n_ped > 0 && !ped_xy)) return fail(h, FOT_ERR_INVALID, who + "xy / ped_xy is NULL");
+    // the inputs as one block: the geometry | step_off | ped_off | xy | yaw (if given) | ped_xy
+    const size_t geom_b = align256(sizeof(FpoGeom)), soff_b = align256(sizeof(int32_t) * ((size_t)n_traj + 1));
+    const size_t poff_b = align256(sizeof(int32_t) * (steps + 1)), xy_b = align256(sizeof(double) * 2 * steps);
+    const size_t yaw_b = yaw ? align256(sizeof(double) * steps) : 0, ped_b = align256(sizeof(double) * 2 * std::max<size_t>(n_ped, 1));
+    const size_t tab_b = soff_b + poff_b + xy_b + yaw_b + ped_b, out_b = sizeof(FpoRecord) * (size_t)n_traj;
+    const bool small = geom_b + tab_b <= SMALL_CALL_BYTES && out_b <= SMALL_CALL_BYTES;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    fot_handle::Footprint &F = h->fp;
+    // the geometry always goes through the pinned block; a small call's tables too: the kernels read them in place
+    HIP_TRY(h, h->hSmallIn.ensure(geom_b + (small ? tab_b : 0)));
+    if (small) HIP_TRY(h, h->hSmallOut.ensure(out_b));
+    else { HIP_TRY(h, F.dIn.ensure(tab_b)); HIP_TRY(h, F.dOut.ensure(out_b)); }
+    if (!yaw) HIP_TRY(h, F.dYaw.ensure(sizeof(double) * steps));
+    HIP_TRY(h, F.dSeries.ensure(sizeof(FpoStep) * steps));
+    { int r = order_begin(h, st); if (r != FOT_OK) return r; }
+    const FpoGeom G = fpo_geom(geom->vehicle_length, geom->vehicle_width, geom->ped_radius, geom->legacy_radius, geom->n_circles);
+    std::memcpy(h->hSmallIn.p, &G, sizeof G);
+    const FpoGeom *d_geom = (const FpoGeom *)h->hSmallIn.p;
+    char *base = small ? (char *)h->hSmallIn.p + geom_b : (char *)F.dIn.p;
+    char *b_soff = base, *b_poff = b_soff + soff_b, *b_xy = b_poff + poff_b, *b_yaw = b_xy + xy_b, *b_ped = b_yaw + yaw_b;
+    auto put = [&](char *dst, const void *src, size_t bytes) -> hipError_t {
+        if (bytes == 0) return hipSuccess;
+        if (small) { std::memcpy(dst, src, bytes); return hipSuccess; }
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+    };
+    HIP_TRY(h, put(b_soff, step_off, sizeof(int32_t) * ((size_t)n_traj + 1)));
+    HIP_TRY(h, put(b_poff, ped_off, sizeof(int32_t) * (steps + 1)));
+    HIP_TRY(h, put(b_xy, xy, sizeof(double) * 2 * steps));
+    if (yaw) HIP_TRY(h, put(b_yaw, yaw, sizeof(double) * steps));
+    HIP_TRY(h, put(b_ped, ped_xy, sizeof(double) * 2 * n_ped));
+    const double *d_yaw = (const double *)b_yaw;
+    if (!yaw) {
+        LAUNCH_TRY(h, launch_footprint_yaw(n_traj, (const int32_t *)b_soff, (const double *)b_xy, F.dYaw.as<double>(), st));
+        d_yaw = F.dYaw.as<double>();
+    }
+    FpoRecord *d_out = small ? (FpoRecord *)h->hSmallOut.p : F.dOut.as<FpoRecord>();
+    LAUNCH_TRY(h, launch_footprint_steps(d_geom, (int)steps, (const double *)b_xy, 2, d_yaw, 1, (const int32_t *)b_poff,
+                                         (const double *)b_ped, F.dSeries.as<FpoStep>(), st));
+    LAUNCH_TRY(h, launch_footprint_fold(d_geom, n_traj, (const int32_t *)b_soff, (const int32_t *)b_poff, F.dSeries.as<FpoStep>(),
+                                        d_out, st));
+    if (series) HIP_TRY(h, hipMemcpyAsync(series, F.dSeries.p, sizeof(FpoStep) * steps, hipMemcpyDeviceToHost, st));
+    if (yaw_out && !yaw) HIP_TRY(h, hipMemcpyAsync(yaw_out, F.dYaw.p, sizeof(double) * steps, hipMemcpyDeviceToHost, st));
+    if (!small) HIP_TRY(h, hipMemcpyAsync(out, F.dOut.p, out_b, hipMemcpyDeviceToHost, st));
+    { int r = order_end(h, st); if (r != FOT_OK) return r; }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (small) std::memcpy(out, h->hSmallOut.p, out_b);
+    if (yaw_out && yaw && yaw_out != yaw) std::memcpy(yaw_out, yaw, sizeof(double) * steps);
+    return FOT_OK;
+}
+
 }  // extern "C"

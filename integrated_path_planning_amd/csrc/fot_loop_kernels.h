@@ -11,6 +11,7 @@
 #include "fot_samplerec.hpp"
 #include "fot_sweep.hpp"
 #include "fot_openloop.hpp"
+#include "fot_footprint_obs.hpp"
 
 namespace fot {
 
@@ -187,5 +188,17 @@ struct OpenLoopRows {
     double2 *anchor, *truth;
 };
 int launch_openloop_rows(const OpenLoopRows &a, hipStream_t st);
+// ---- fot_footprint_recheck (fot_footprint_obs.hpp).  Pose i is (xy[i xy_stride], xy[i xy_stride + 1]) with the heading
+// yaw[i yaw_stride] -- xy [n][2] and yaw [n] of a recheck, or both inside the loop's [n][4] ego rows -- and its
+// pedestrians are rows ped_off[i] .. ped_off[i + 1] of ped_xy; out[i] is its {legacy, multi, rect} record.  geom: HBM or
+// pinned memory.
+int launch_footprint_steps(const FpoGeom *geom, int n, const double *xy, int xy_stride, const double *yaw, int yaw_stride,
+                           const int32_t *ped_off, const double *ped_xy, FpoStep *out, hipStream_t st);
+// the headings of n_traj trajectories (steps step_off[t] .. step_off[t + 1] of xy [steps][2], each of two steps at
+// least) reconstructed from their positions: yaw_out [steps]
+int launch_footprint_yaw(int n_traj, const int32_t *step_off, const double *xy, double *yaw_out, hipStream_t st);
+// the trajectories' records from their steps' records
+int launch_footprint_fold(const FpoGeom *geom, int n_traj, const int32_t *step_off, const int32_t *ped_off,
+                          const FpoStep *series, FpoRecord *out, hipStream_t st);
 
 }  // namespace fot

@@ -4,6 +4,9 @@
 //   k_resample / k_sample_dist   fot_resample_predictions, fot_predict_cv: predictor output -> dense obstacle tensor
 //   k_pred_scores                fot_prediction_scores: best-of-N ADE / FDE and KDE-NLL of a prediction origin
 //   k_safety                     fot_safety_metrics_batch and the loop's per-step metrics
+//   k_footprint_steps / _yaw / _fold
+//                                fot_footprint_recheck: centre, circle cover and exact rectangle per step, the heading
+//                                reconstruction, the fold of a trajectory
 //   k_loop_* / k_static_gather / k_predict_cv_frame
 //                                the resident loop (fot_loop_run): frame, sample gather, prediction, digests, history,
 //                                prediction-error summaries, predictor scores, representative sample
@@ -741,6 +744,148 @@ k_openloop_rows(OpenLoopRows A)
 }
 
 // ---------------------------------------------------------------------------
+// fot_footprint_recheck (fot_footprint_obs.hpp): centre, circle cover and exact rectangle, observed per step
+// ---------------------------------------------------------------------------
+// One wave per pose, as k_safety.  cos / sin once per wave; lanes over the pedestrians for the centre and the rectangle,
+// over the (circle, pedestrian) pairs for the cover.  A pose without pedestrians writes +inf three times.  No atomics.
+__global__ void __launch_bounds__(WAVE)
+k_footprint_steps(const FpoGeom *__restrict__ geom, int n, const double *__restrict__ xy, int xy_stride,
+                  const double *__restrict__ yaw, int yaw_stride, const int32_t *__restrict__ ped_off,
+                  const double *__restrict__ ped_xy, FpoStep *__restrict__ out)
+{
+    const int i = blockIdx.x;
+    if (i >= n) return;
+    const FpoGeom &G = *geom;
+    const double x = xy[(int64_t)i * xy_stride], y = xy[(int64_t)i * xy_stride + 1];
+    const double a = yaw[(int64_t)i * yaw_stride];
+    const double c = cos(a), s = sin(a);
+    const int p0 = ped_off[i], np_ = ped_off[i + 1] - p0;
+    const double *__restrict__ peds = ped_xy + 2 * (int64_t)p0;  // (8-byte loads: a frame's rows need not be 16-byte aligned)
+    double legacy = INFINITY, multi = INFINITY, rect = INFINITY;
+    for (int p = threadIdx.x; p < np_; p += WAVE) {
+        double2 q;
+        q.x = peds[2 * p]; q.y = peds[2 * p + 1];
+        legacy = fmin(legacy, fpo_legacy(q.x, q.y, x, y));
+        rect = fmin(rect, fpo_rect(q.x, q.y, x, y, c, s, G.half_l, G.half_w));
+    }
+    const int pairs = G.n_circles * np_;
+    for (int j = threadIdx.x; j < pairs; j += WAVE) {
+        const int k = j / np_, p = j - k * np_;
+        double2 q;
+        q.x = peds[2 * p]; q.y = peds[2 * p + 1];
+        const double off = G.off[k];
+        multi = fmin(multi, fpo_multi(q.x, q.y, fpo_centre(x, off, c), fpo_centre(y, off, s)));
+    }
+    legacy = wave_min_f64(legacy); multi = wave_min_f64(multi); rect = wave_min_f64(rect);
+    if (threadIdx.x == 0) {
+        FpoStep r;
+        r.legacy = legacy; r.multi = multi; r.rect = rect;
+        out[i] = r;
+    }
+}
+
+constexpr int FPO_THREADS = 256;
+constexpr int FPO_WAVES = FPO_THREADS / WAVE;
+
+// One workgroup per trajectory: the heading of every step from the central differences of its positions, a standing
+// step holding the heading of the last moving one.  The hold is an inclusive scan of (source step, heading) in chunks of
+// the workgroup's width: a butterfly-free shift scan within a wave, the waves' totals through LDS, the carry of the
+// chunks before in every thread's registers (all threads form the same carry).  The steps in front of the first moving
+// one are written last, once that step is known; a trajectory that never moves is all zeros.  Every element of yaw_out
+// is written once.
+__global__ void __launch_bounds__(FPO_THREADS)
+k_footprint_yaw(const int32_t *__restrict__ step_off, const double *__restrict__ xy, double *__restrict__ yaw_out)
+{
+    __shared__ int32_t s_src[FPO_WAVES];
+    __shared__ double s_yaw[FPO_WAVES];
+    __shared__ int32_t s_first[FPO_WAVES];
+    __shared__ double s_first_yaw;
+    const int i0 = step_off[blockIdx.x], n = step_off[blockIdx.x + 1] - i0;
+    const double *__restrict__ q = xy + 2 * (int64_t)i0;
+    double *__restrict__ out = yaw_out + i0;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    auto X = [&](int i) { return q[2 * i]; };
+    auto Y = [&](int i) { return q[2 * i + 1]; };
+    FpoHold carry;
+    carry.src = -1; carry.yaw = 0.0;
+    int my_first = INT32_MAX;
+    double my_first_yaw = 0.0;
+    for (int c0 = 0; c0 < n; c0 += FPO_THREADS) {
+        const int i = c0 + tid;
+        FpoHold h;
+        h.src = -1; h.yaw = 0.0;
+        if (i < n) {
+            const double dx = fpo_gradient(X, i, n), dy = fpo_gradient(Y, i, n);
+            if (fpo_moving(dx, dy)) {
+                h.src = i; h.yaw = atan2(dy, dx);
+                if (my_first == INT32_MAX) { my_first = i; my_first_yaw = h.yaw; }
+            }
+        }
+#pragma unroll
+        for (int off = 1; off < WAVE; off <<= 1) {
+            FpoHold o;
+            o.src = __shfl_up(h.src, off, WAVE); o.yaw = __shfl_up(h.yaw, off, WAVE);
+            if (lane >= off) h = fpo_hold_join(o, h);
+        }
+        if (lane == WAVE - 1) { s_src[wave] = h.src; s_yaw[wave] = h.yaw; }
+        __syncthreads();
+        FpoHold next = carry;                                        // the carry after this chunk: the same in every thread
+        for (int w = 0; w < FPO_WAVES; ++w) {
+            if (w == wave) h = fpo_hold_join(next, h);               // (next: the carry joined with the waves before this one)
+            FpoHold t;
+            t.src = s_src[w]; t.yaw = s_yaw[w];
+            next = fpo_hold_join(next, t);
+        }
+        if (i < n && h.src >= 0) out[i] = h.yaw;
+        carry = next;
+        __syncthreads();                                             // the next chunk writes s_src / s_yaw again
+    }
+    int first = my_first;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) first = min(first, __shfl_xor(first, off, WAVE));
+    if (lane == 0) s_first[wave] = first;
+    __syncthreads();
+    first = s_first[0];
+    for (int w = 1; w < FPO_WAVES; ++w) first = min(first, s_first[w]);
+    const bool any_moving = first != INT32_MAX;
+    if (any_moving && my_first == first) s_first_yaw = my_first_yaw; // (one thread: the chunk's owner of that step)
+    __syncthreads();
+    FpoHold none;
+    none.src = -1; none.yaw = 0.0;
+    const double lead = fpo_hold_pick(none, any_moving, any_moving ? s_first_yaw : 0.0);
+    const int n_lead = any_moving ? first : n;
+    for (int i = tid; i < n_lead; i += FPO_THREADS) out[i] = lead;
+}
+
+// One workgroup per trajectory: the minima and the counts of its steps' records.  Minima and integer sums: the result
+// does not depend on the order, so lanes stride over the steps, the wave folds with shuffles and the waves meet in LDS.
+__global__ void __launch_bounds__(FPO_THREADS)
+k_footprint_fold(const FpoGeom *__restrict__ geom, const int32_t *__restrict__ step_off, const int32_t *__restrict__ ped_off,
+                 const FpoStep *__restrict__ series, FpoRecord *__restrict__ out)
+{
+    __shared__ FpoAcc s_acc[FPO_WAVES];
+    const FpoGeom &G = *geom;
+    const int i0 = step_off[blockIdx.x], n = step_off[blockIdx.x + 1] - i0;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    FpoAcc a = fpo_acc_zero();
+    for (int i = tid; i < n; i += FPO_THREADS) {
+        const FpoStep r = series[i0 + i];
+        fpo_acc_step(a, G, r.legacy, r.multi, r.rect, ped_off[i0 + i + 1] > ped_off[i0 + i]);
+    }
+    a.legacy = wave_min_f64(a.legacy); a.multi = wave_min_f64(a.multi); a.rect = wave_min_f64(a.rect);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        a.n_legacy += __shfl_xor(a.n_legacy, off, WAVE); a.n_multi += __shfl_xor(a.n_multi, off, WAVE);
+        a.n_rect += __shfl_xor(a.n_rect, off, WAVE); a.with_peds += __shfl_xor(a.with_peds, off, WAVE);
+    }
+    if (lane == 0) s_acc[wave] = a;
+    __syncthreads();
+    if (tid != 0) return;
+    for (int w = 1; w < FPO_WAVES; ++w) fpo_acc_merge(a, s_acc[w]);
+    out[blockIdx.x] = fpo_acc_record(a, G, n);
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
 
@@ -949,6 +1094,35 @@ int launch_loop_summary(SummaryShape S, const double *ring, const int32_t *ring_
     if (n_slots <= 0) return 0;
     if (S.n_dense < 1 || S.n_dense > FOT_MAX_NT) return (int)hipErrorInvalidValue;
     k_loop_summary<<<n_slots, 256, 0, st>>>(S, ring, ring_P, totals, steps, n_slots, num_samples, out);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_footprint_steps(const FpoGeom *geom, int n, const double *xy, int xy_stride, const double *yaw, int yaw_stride,
+                           const int32_t *ped_off, const double *ped_xy, FpoStep *out, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    if (!geom || !xy || !yaw || !ped_off || !out || xy_stride < 2 || yaw_stride < 1) return (int)hipErrorInvalidValue;
+    k_footprint_steps<<<n, WAVE, 0, st>>>(geom, n, xy, xy_stride, yaw, yaw_stride, ped_off, ped_xy, out);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_footprint_yaw(int n_traj, const int32_t *step_off, const double *xy, double *yaw_out, hipStream_t st)
+{
+    if (n_traj <= 0) return 0;
+    if (!step_off || !xy || !yaw_out) return (int)hipErrorInvalidValue;
+    k_footprint_yaw<<<n_traj, FPO_THREADS, 0, st>>>(step_off, xy, yaw_out);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_footprint_fold(const FpoGeom *geom, int n_traj, const int32_t *step_off, const int32_t *ped_off,
+                          const FpoStep *series, FpoRecord *out, hipStream_t st)
+{
+    if (n_traj <= 0) return 0;
+    if (!geom || !step_off || !ped_off || !series || !out) return (int)hipErrorInvalidValue;
+    k_footprint_fold<<<n_traj, FPO_THREADS, 0, st>>>(geom, step_off, ped_off, series, out);
     FOT_LAUNCH_CHECK();
     return 0;
 }

@@ -874,6 +874,49 @@ class BatchPlanner:
             C.c_void_p(stream) if stream else None))
         return totals, (records[:n_win] if want_records else None), raw
 
+    FOOTPRINT_STEP_DT = np.dtype(_abi.FootprintStep)
+    FOOTPRINT_OBS_DT = np.dtype(_abi.FootprintObs)
+
+    def footprint_recheck(self, geom: "_abi.FootprintGeom", step_off, xy, yaw, ped_off, ped_xy, want_series: bool = False,
+                          want_yaw: bool = False):
+        """``fot_footprint_recheck``: the trajectories (step_off [n + 1]) of poses xy [steps, 2] with the headings yaw
+        [steps] (None: reconstructed on the device) and every step's pedestrians (ped_off [steps + 1], ped_xy [rows, 2])
+        measured against the centre, the circle cover and the exact rectangle of ``geom`` in one call.  Returns
+        ``(records, series, yaw_used)``: ``FOOTPRINT_OBS_DT`` per trajectory, ``FOOTPRINT_STEP_DT`` per step (None without
+        ``want_series``) and the headings used (None without ``want_yaw``)."""
+        s_off = np.ascontiguousarray(step_off, dtype=np.int32).reshape(-1)
+        p_off = np.ascontiguousarray(ped_off, dtype=np.int32).reshape(-1)
+        pose = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        peds = np.ascontiguousarray(ped_xy, dtype=np.float64).reshape(-1, 2)
+        n, steps = len(s_off) - 1, pose.shape[0]
+        if n < 0 or len(p_off) != steps + 1:
+            raise ValueError("footprint_recheck: step_off holds n + 1 offsets and ped_off one more than there are steps")
+        head = None if yaw is None else np.ascontiguousarray(yaw, dtype=np.float64).reshape(-1)
+        if head is not None and len(head) != steps:
+            raise ValueError("footprint_recheck: one heading per step")
+        if s_off[-1] != steps or (len(p_off) and max(int(p_off[-1]), 0) != peds.shape[0]):
+            raise ValueError("footprint_recheck: the offsets' last entries are the number of steps and of pedestrian rows")
+        out = np.zeros(max(n, 1), dtype=self.FOOTPRINT_OBS_DT)
+        series = np.zeros(max(steps, 1), dtype=self.FOOTPRINT_STEP_DT) if want_series else None
+        used = np.zeros(max(steps, 1)) if want_yaw else None
+        _abi.check(self._h, self._lib.fot_footprint_recheck(
+            self._h, C.byref(geom), n, _addr(s_off), _addr(pose) if steps else None, _addr(head) if head is not None else None,
+            _addr(p_off), _addr(peds) if peds.size else None, _addr(series) if want_series else None,
+            _addr(used) if want_yaw else None, _addr(out)))
+        return out[:n], (series[:steps] if want_series else None), (used[:steps] if want_yaw else None)
+
+    def loop_footprint_enable(self, geom: Optional["_abi.FootprintGeom"]) -> None:
+        """``fot_loop_footprint_enable``: every lock step of this loop (one-call step or resident) also measures the new ego
+        states against the fixed observational geometries; None switches it off.  Between ``loop_begin*`` and the first step."""
+        _abi.check(self._h, self._lib.fot_loop_footprint_enable(self._h, C.byref(geom) if geom is not None else None))
+
+    def loop_footprint_obs(self, n_slots: int) -> np.ndarray:
+        """``fot_loop_footprint_obs``: one ``FOOTPRINT_OBS_DT`` record per slot over the lock steps run so far."""
+        n = int(n_slots)
+        out = np.zeros(max(n, 1), dtype=self.FOOTPRINT_OBS_DT)
+        _abi.check(self._h, self._lib.fot_loop_footprint_obs(self._h, n, _addr(out)))
+        return out[:n]
+
     def _loop_frame(self, frame: dict):
         """fot_loop_frame from the dictionary ``loop_plan`` / ``loop_step`` take (+ the arrays it points into)."""
         f, keep = _abi.LoopFrame(), []
