@@ -86,6 +86,19 @@ __device__ __forceinline__ int wave_prefix_sum_i32(int v)
     return v;
 }
 
+// minimum over the wave's lanes (every lane active), as a scalar: the shifts and broadcasts of the prefix sum, lane 63
+// ends with the reduction; a lane without a source keeps its own value
+__device__ __forceinline__ int wave_min_i32(int v)
+{
+    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x111, 0xf, 0xf, false));   // row_shr:1
+    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x112, 0xf, 0xf, false));   // row_shr:2
+    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x114, 0xf, 0xf, false));   // row_shr:4
+    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x118, 0xf, 0xf, false));   // row_shr:8
+    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x142, 0xa, 0xf, false));   // row_bcast15
+    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x143, 0xc, 0xf, false));   // row_bcast31
+    return __builtin_amdgcn_readlane(v, 63);
+}
+
 // ---------------------------------------------------------------------------
 // ego -> Frenet state
 // ---------------------------------------------------------------------------
@@ -960,12 +973,20 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
         r[4] = ls.cos_r; r[5] = ls.sin_r; r[6] = ls.kr; r[7] = ls.dkr; r[8] = ls.inv_sd;
     }
     lds_fence();
-    // the time steps this tile needs: the longest of its OWN profiles
+    // the time steps this tile needs: the longest of its OWN profiles -- and the steps before any of them holds (ne_min of
+    // evaluate_segment: the slots between the first and the last candidate's are the ones its lanes read).  SREG: only the
+    // lean split kernel has the scalar registers for that form of the walk (the others would lane-spill them)
+    constexpr bool SREG = LEAN && SPLIT;
+    int ne_min = INT_MAX;
     {
         const int own_lo = decode_candidate(P, D, S.frenet0, cand0).lon_slot - slot_lo;
         const int own_hi = decode_candidate(P, D, S.frenet0, cand0 + n - 1).lon_slot - slot_lo;
-        for (int p = own_lo; p <= own_hi; ++p) { const int nt = s_info[p].n_t; n_loop = nt > n_loop ? nt : n_loop; }
+        for (int p = own_lo; p <= own_hi; ++p) {
+            const int nt = s_info[p].n_t, ne = s_info[p].n_eval;
+            n_loop = nt > n_loop ? nt : n_loop; ne_min = ne < ne_min ? ne : ne_min;
+        }
         n_loop = __builtin_amdgcn_readfirstlane(n_loop);
+        ne_min = __builtin_amdgcn_readfirstlane(ne_min);
     }
     // this wave's time steps
     const int seg_len = (n_loop + n_seg - 1) / n_seg;
@@ -1042,7 +1063,7 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
             lc.n_circ_fp = __builtin_amdgcn_readfirstlane(lc.n_circ_fp);
             asm volatile("" : "+s"(lc.n_circ_fp));
         }
-        evaluate_segment<LEAN>(P, lc, L, tab, q, k0, k1, sink, g);   // (SPLIT: a quarter of the steps -- latency, not issue, bound)
+        evaluate_segment<LEAN, SREG>(P, lc, L, tab, q, k0, k1, sink, g, ne_min);   // (SPLIT: a quarter of the steps -- latency, not issue, bound)
         hit_mask = sink.hit_mask; hit = sink.hit;
 #ifdef FOT_TIMELINE
         tl_rows = tab.t_rows;
@@ -1211,6 +1232,10 @@ __device__ __forceinline__ void evaluate_group_tile(const DevParams *__restrict_
     const int tl_wave = inst_tile0 + tile;
 #endif
     bool hit = false;
+    // the steps before any candidate of the tile holds (ne_min of evaluate_segment; the general form has no scalar registers
+    // to spare for that walk): every lane of the wave is here, the ones that walk the empty path do not count
+    constexpr bool SREG = LEAN;
+    const int ne_min = SREG ? wave_min_i32(has_cand ? L.n_eval : INT_MAX) : 0;
     if (walks) {
         // the walk's wave-uniform state is set up HERE: scalar values do not survive the join of the region above
         FusedSink<LEAN> sink;
@@ -1229,7 +1254,7 @@ __device__ __forceinline__ void evaluate_group_tile(const DevParams *__restrict_
             lc.n_circ_fp = uni(head->n_circ_fp);
             asm volatile("" : "+s"(lc.n_circ_fp));
         }
-        evaluate_segment<LEAN>(P, lc, L, tab, q, 0, n_loop, sink, g);
+        evaluate_segment<LEAN, SREG>(P, lc, L, tab, q, 0, n_loop, sink, g, ne_min);
         hit = sink.hit;
 #ifdef FOT_TIMELINE
         tl_rows = tab.t_rows;

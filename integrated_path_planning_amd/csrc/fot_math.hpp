@@ -694,6 +694,27 @@ bool yaw_step_over_cap(double sn, double cs, double lim_curv, double step2)
     return fabs(atan2(sn, cs)) > fmax(lim_curv * sqrt(step2), 0.1);
 }
 
+// Inside a block behind a wave-uniform condition: the compiler keeps the branch (it cannot run the statement on
+// speculation) instead of turning the block into selects that every step issues.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FOT_KEEP_BRANCH asm volatile("")
+#else
+#define FOT_KEEP_BRANCH ((void)0)
+#endif
+
+// m = max(m, v) for the running largest squared step.  On the device ONE v_max_f64: from `if (v > m) m = v` the compiler
+// makes a compare and two selects, and a source fmax() gets a canonicalising v_max x, x in front.  The same bits as the
+// compare: v is an arithmetic result (never a signalling NaN), a quiet-NaN v leaves m as it is (the instruction returns
+// its other operand), and the values are sums of squares (never -0) over a start value of -inf (m is never NaN).
+FOT_HD void step2_max(double &m, double v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_max_f64 %0, %1, %2" : "=v"(m) : "v"(v), "v"(m));
+#else
+    if (v > m) m = v;
+#endif
+}
+
 // k = index of the sample inside the path; has_geo / has_d: the low-speed rules and the road test
 // only apply when the caller's path carries the arrays they read (:1013-1022, :982).  arc_step() returns
 // |s_k - s_{k-1}|; it is only asked for in the low-speed branch.
@@ -706,7 +727,7 @@ FOT_HD void check_sample(const LoopConst &C, CheckAcc &c, int k, const PathSampl
         const double sx = p.x - c.prev.x, sy = p.y - c.prev.y;                                // :953-956
         const double step2 = sum_sq_unfused(sx, sy);
         check_flag(c, isnan(step2), CK_NANSTEP);
-        if (step2 > c.max_step2) c.max_step2 = step2;
+        step2_max(c.max_step2, step2);
         check_flag(c, p.v > C.lim_speed, CK_SPEED);                                           // :964
         check_flag(c, fabs(p.a) > C.lim_accel, CK_ACCEL);                                     // :966
         if (p.v > 0.5) {                                                                       // LOW_SPEED_CURVATURE_GATE
@@ -859,9 +880,16 @@ FOT_HD void seg_init(SegState &g)
 
 // time steps [k0, k1) of one candidate.  LEAN: the caller vouches for the single centre circle (C.n_circ_fp == 0), so the
 // footprint-circle loop is not instantiated; everything else is the same walk (the sink has a lean form of its own).
-template <bool LEAN = false, class Tab, class Sink>
+// SREG: the walk may spend scalar registers to save vector instructions -- one for ne_min, and a lane mask for "no NaN
+// sample yet" in place of a bit of the per-lane flag word.  The kernels whose scalar file has no room for them (they would
+// be lane-spilled and come back through v_readlane in every step) ask for the walk without; both forms give the same bits.
+// ne_min (SREG): a value every lane of the wave shares, at most the n_eval of every lane that holds a candidate.  In a step
+// below it no lane holds (brake-ladder profiles hold, from their n_eval on): a scalar branch skips what lat_sample
+// spends on the hold -- the compare, the held step and the three zeroed derivatives.  0 (the host): no step skips it;
+// a value that is too small costs time, never a bit.
+template <bool LEAN = false, bool SREG = true, class Tab, class Sink>
 FOT_HD void evaluate_segment(const DevParams &P, const LoopConst &C, const LonInfo &L, const Tab &lon_tab,
-                             const double *q, int k0, int k1, Sink &sink, SegState &g)
+                             const double *q, int k0, int k1, Sink &sink, SegState &g, int ne_min = 0)
 {
     const int n_t = L.n_t;
     CheckAcc &acc = g.acc;
@@ -886,13 +914,26 @@ FOT_HD void evaluate_segment(const DevParams &P, const LoopConst &C, const LonIn
       sink.row_begin(k);
       if (k < n_t) {
         double d, d_d, d_dd, d_ddd;
-        lat_sample(q, k, L.n_eval, C.dt, d, d_d, d_dd, d_ddd);
+        if constexpr (SREG) {
+            // lat_sample with ONE copy of the polynomial: a holding lane evaluates it at its last step and drops the
+            // derivatives; both fix-ups lie behind a scalar branch that the steps below ne_min do not take
+            const bool may_hold = !(k < ne_min);
+            double tk = (double)k;
+            if (may_hold) { FOT_KEEP_BRANCH; tk = (double)(k < L.n_eval ? k : L.n_eval - 1); }
+            lat_eval(q, tk * C.dt, d, d_d, d_dd, d_ddd);
+            if (may_hold) { FOT_KEEP_BRANCH; if (!(k < L.n_eval)) { d_d = 0.0; d_dd = 0.0; d_ddd = 0.0; } }
+        } else {
+            lat_sample(q, k, L.n_eval, C.dt, d, d_d, d_dd, d_ddd);
+        }
         g.d_last = d;
         CartSample c;
         frenet_to_cart(ls, d, d_d, d_dd, c);
         check_flag(acc, isfinite(c.omkd) && c.omkd <= 0.05, CK_SINGULAR);   // SINGULARITY_EPS, any sample
-        if (!(acc.fl & CK_SEEN_NAN) && isnan(c.x)) { acc.fl |= CK_SEEN_NAN; g.first_nan = k; }
-        if (!(acc.fl & CK_SEEN_NAN)) {
+        // SREG: inside a segment "a NaN sample was seen" is first_nan >= 0 (seg_init: -1) -- the walk keys on the index
+        // alone, and CK_SEEN_NAN, which only the code behind the segment reads, is set once behind the loop
+        if constexpr (SREG) { if (g.first_nan < 0 && isnan(c.x)) g.first_nan = k; }
+        else if (!(acc.fl & CK_SEEN_NAN) && isnan(c.x)) { acc.fl |= CK_SEEN_NAN; g.first_nan = k; }
+        if (SREG ? g.first_nan < 0 : !(acc.fl & CK_SEEN_NAN)) {
             PathSample ps;
             ps.x = c.x; ps.y = c.y; ps.cos_t = c.cos_t; ps.sin_t = c.sin_t; ps.kappa = c.kappa;
             ps.v = c.v; ps.a = c.a; ps.d = d;
@@ -911,6 +952,7 @@ FOT_HD void evaluate_segment(const DevParams &P, const LoopConst &C, const LonIn
       }
       sink.row_end(k);
     }
+    if constexpr (SREG) { if (g.first_nan >= 0) acc.fl |= CK_SEEN_NAN; }
 }
 
 // g (segments up to some k) followed by n (the segment that starts there and holds a sample below n_t).  Returns
