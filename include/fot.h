@@ -1123,6 +1123,54 @@ int fot_footprint_recheck(fot_handle *h, const fot_footprint_geom *geom, int32_t
 int fot_loop_footprint_enable(fot_handle *h, const fot_footprint_geom *geom);
 int fot_loop_footprint_obs(fot_handle *h, int32_t n_slots, fot_footprint_obs *out);
 
+/* ---- fidelity statistics of vehicle-pedestrian encounters (RQ2): separation, avoidance onset, roll-out error ---------------------
+ * The reference's min_separation_series and avoidance_onset_distance (src/core/metrics.py) and the measuring half of
+ * fidelity_report / objective_rollout_ade (src/simulation/calibration_harness.py).  An encounter is T steps of an ego
+ * position and of a fixed population of N pedestrians, [T][N][2]; the caller brings the positions from wherever they were
+ * recorded or simulated.  float64 throughout, NumPy's operation order (csrc/fot_fidelity.hpp):
+ *   distance    sqrt(dx dx + dy dy), each product and the sum rounded apart (np.linalg.norm(axis=2))
+ *   gradient    np.gradient(f, dt, axis=0): (f[t+1] - f[t-1]) / (2 dt) inside, (f[1] - f[0]) / dt and (f[T-1] - f[T-2]) / dt
+ *               at the ends.  The velocity is ped_vel, or the gradient of the positions; the acceleration is always the
+ *               gradient of the velocity
+ *   onset       of a pedestrian: the first step t, ascending, with !(dist < 1e-9) && !(dist > max_distance) and
+ *               away > accel_threshold, away = acc_x (rel_x / dist) + acc_y (rel_y / dist), rel = pedestrian - ego;
+ *               onset_dist is that step's distance, the bits of its separation.  A NaN distance is not skipped and a NaN
+ *               away is never an onset; dist == max_distance counts, away == accel_threshold does not; T < 2: no onset
+ *   series      per step the minimum over the pedestrians as np.min forms it (a NaN stays NaN); +inf with N == 0
+ *   error       against truth_xy: err[t][j] = |ped_xy - truth_xy|, step 0 excluded; with interaction_distance not NaN
+ *               only the pedestrians whose truth-side distance to the ego has min_t <= interaction_distance.  err_sum adds
+ *               each kept pedestrian's steps in ascending order, then the pedestrians in ascending order: one fixed order,
+ *               no floating-point atomics
+ * n_enc ragged encounters in ONE synchronous call: everything is enqueued on the handle's stream and waited for once.  All
+ * pointers are host memory.  An encounter's outputs are byte-identical whatever encounters share the call and wherever it
+ * stands in it.  No capacity on T, N or n_enc beyond the int32 offsets.
+ * Refusals (FOT_ERR_INVALID, a refused call changes nothing): p, step_off, n_ped, dt, ego_xy, ped_xy or out NULL;
+ * n_enc < 0; offsets that do not start at 0 or that decrease; an encounter of 0 steps; n_ped[e] < 0; a dt that is not
+ * finite and positive; max_distance or accel_threshold NaN.  n_enc == 0 succeeds and writes nothing.
+ * An addition: no structure, capacity word of fot_abi_info or FOT_ABI_VERSION changes; a binding looks the symbol up. */
+typedef struct fot_fidelity_params {
+    double accel_threshold, max_distance;   /* reference defaults 0.3, 5.0 */
+    double interaction_distance;            /* NaN: keep every pedestrian in the error */
+} fot_fidelity_params;
+typedef struct fot_fidelity_enc {
+    double  closest;                        /* min of the series; +inf if N == 0; NaN propagates */
+    double  err_sum;                        /* 0 without truth */
+    int64_t err_count;                      /* (T - 1) * kept pedestrians; 0 without truth */
+    int32_t n_onset, closest_step;          /* first step holding `closest`; -1 if N == 0 or closest is NaN */
+} fot_fidelity_enc;
+int fot_fidelity_eval(fot_handle *h, const fot_fidelity_params *p, int32_t n_enc,
+                      const int32_t *step_off,  /* [n_enc + 1] from 0 */
+                      const int32_t *n_ped,     /* [n_enc] */
+                      const double  *dt,        /* [n_enc] */
+                      const double  *ego_xy,    /* [steps][2] */
+                      const double  *ped_xy,    /* encounter e: [T_e][N_e][2], encounters back to back */
+                      const double  *ped_vel,   /* same shape, or NULL: finite differences for every encounter */
+                      const double  *truth_xy,  /* same shape, or NULL: no roll-out error */
+                      double *sep_series,       /* NULL or [steps] */
+                      double *onset_dist,       /* NULL or [sum N]: NaN = no onset */
+                      int32_t *onset_step,      /* NULL or [sum N]: -1 = no onset */
+                      fot_fidelity_enc *out);   /* [n_enc] */
+
 /* Host utility (no GPU): the first kmax samples of the 15 path arrays of records[index[i]], i < n, as one dense block
  * out[15][n][kmax] in fot_result array order (t .. c) -- what a history keeps of a step's records. */
 int fot_gather_paths(const fot_result *records, int32_t n, const int32_t *index, int32_t kmax, double *out);

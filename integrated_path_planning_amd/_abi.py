@@ -190,6 +190,15 @@ class FootprintObs(C.Structure):                                  # fot_footprin
     _fields_ = [(n, C.c_double) for n in FOOTPRINT_OBS_F64] + [(n, C.c_int32) for n in FOOTPRINT_OBS_I32 + ("_pad",)]
 
 
+class FidelityParams(C.Structure):                                # fot_fidelity_params
+    _fields_ = [(n, C.c_double) for n in ("accel_threshold", "max_distance", "interaction_distance")]
+
+
+class FidelityEnc(C.Structure):                                   # fot_fidelity_enc
+    _fields_ = [("closest", C.c_double), ("err_sum", C.c_double), ("err_count", C.c_int64), ("n_onset", C.c_int32),
+                ("closest_step", C.c_int32)]
+
+
 class Batch(C.Structure):
     _fields_ = [("n_inst", C.c_int32), ("obstacle_dtype", C.c_int32),
                 ("ego", C.POINTER(Ego)), ("target_speed", C.POINTER(C.c_double)),
@@ -219,7 +228,7 @@ SYMBOLS = ["fot_version", "fot_abi_info", "fot_create", "fot_destroy", "fot_live
            "fot_loop_begin_sweep", "fot_loop_set_samples_shared", "fot_loop_set_sampler_shared", "fot_debug_loop_sampler_shape",
            "fot_sgan_max_models", "fot_sgan_load_model", "fot_sgan_unload_model", "fot_sgan_sample_model",
            "fot_loop_set_sampler_models", "fot_debug_loop_sampler_shapes", "fot_openloop_eval",
-           "fot_footprint_recheck", "fot_loop_footprint_enable", "fot_loop_footprint_obs"]
+           "fot_footprint_recheck", "fot_loop_footprint_enable", "fot_loop_footprint_obs", "fot_fidelity_eval"]
 LOOP_PLAN_DISTRIBUTION, LOOP_PLAN_REPRESENTATIVE = 0, 1      # FOT_LOOP_PLAN_* (fot_loop_plan_sample)
 PROFILE_KERNELS = 3                      # FOT_PROFILE_KERNELS (include/fot.h)
 ABI_VERSION = 8                          # FOT_ABI_VERSION
@@ -491,7 +500,8 @@ def lib():
                                               C.POINTER(OpenLoopTotals), vp]),
                        ("fot_footprint_recheck", [vp, C.POINTER(FootprintGeom), C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]),
                        ("fot_loop_footprint_enable", [vp, C.POINTER(FootprintGeom)]),
-                       ("fot_loop_footprint_obs", [vp, C.c_int32, vp])):
+                       ("fot_loop_footprint_obs", [vp, C.c_int32, vp]),
+                       ("fot_fidelity_eval", [vp, C.POINTER(FidelityParams), C.c_int32] + [vp] * 11)):
         if hasattr(L, name):
             getattr(L, name).argtypes = args
     L.fot_gather_paths.argtypes = [vp, C.c_int32, vp, C.c_int32, vp]

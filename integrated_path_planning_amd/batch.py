@@ -153,6 +153,75 @@ class PackedBatch:
                                  dyn_dev_ptr if self.dyn_xy.size else None)
 
 
+FIDELITY_ENC_DT = np.dtype(_abi.FidelityEnc)
+
+
+class PackedEncounters:
+    """Ragged encounters as ``fot_fidelity_eval`` takes them: the step offsets, the pedestrian counts and the time steps,
+    the ego rows [steps, 2] and every encounter's [T, N, 2] arrays back to back."""
+
+    def __init__(self, ego_xy: Sequence, ped_xy: Sequence, dt: Sequence[float], ped_vel: Optional[Sequence] = None,
+                 truth_xy: Optional[Sequence] = None):
+        egos = [np.asarray(e, dtype=np.float64) for e in ego_xy]
+        peds = [np.asarray(p, dtype=np.float64) for p in ped_xy]
+        for e, p in zip(egos, peds):
+            if p.ndim != 3 or p.shape[2] != 2 or e.ndim != 2 or e.shape[1] != 2:
+                raise ValueError(f"an encounter is ego_xy [T, 2] and ped_xy [T, N, 2], got {e.shape} and {p.shape}")
+            if e.shape[0] != p.shape[0]:
+                raise ValueError(f"ego_xy T={e.shape[0]} != ped_xy T={p.shape[0]}")
+        self.n = len(peds)
+        if len(egos) != self.n or len(dt) != self.n:
+            raise ValueError("one ego_xy, ped_xy and dt per encounter")
+        self.steps = np.array([p.shape[0] for p in peds], dtype=np.int64)
+        self.n_ped = np.array([p.shape[1] for p in peds], dtype=np.int32)
+        if self.steps.sum() > np.iinfo(np.int32).max:
+            raise ValueError("more steps than int32 offsets hold")
+        self.step_off = np.concatenate([[0], np.cumsum(self.steps)]).astype(np.int32)
+        self.ped_base = np.concatenate([[0], np.cumsum(self.n_ped, dtype=np.int64)])
+        self.dt = np.asarray(dt, dtype=np.float64).reshape(self.n)
+        self.ego = self._flat(egos)
+        self.ped = self._flat(peds)
+        self.vel = self._same_shape(ped_vel, peds, "ped_vel")
+        self.truth = self._same_shape(truth_xy, peds, "truth_xy")
+
+    @staticmethod
+    def _flat(arrays) -> np.ndarray:
+        flat = [a.reshape(-1) for a in arrays]
+        out = np.concatenate(flat) if flat else np.zeros(0)
+        return np.ascontiguousarray(out if out.size else np.zeros(2))     # (never a NULL pointer: an empty set is not refused)
+
+    def _same_shape(self, arrays, peds, name):
+        if arrays is None:
+            return None
+        arrays = [np.asarray(a, dtype=np.float64) for a in arrays]
+        if len(arrays) != self.n:
+            raise ValueError(f"one {name} per encounter")
+        for a, p in zip(arrays, peds):
+            if a.shape != p.shape:
+                raise ValueError(f"{name} shape {a.shape} != ped_xy shape {p.shape}")
+        return self._flat(arrays)
+
+
+def fidelity_eval(lib, handle, enc: PackedEncounters, accel_threshold: float = 0.3, max_distance: float = 5.0,
+                  interaction_distance: Optional[float] = None):
+    """``fot_fidelity_eval`` on packed encounters, one call.  Returns ``(records, series, onset_dist, onset_step)``:
+    ``FIDELITY_ENC_DT`` per encounter, the separation per step, and per pedestrian the onset distance (NaN: none) and
+    step (-1: none)."""
+    p = _abi.FidelityParams(float(accel_threshold), float(max_distance),
+                            float("nan") if interaction_distance is None else float(interaction_distance))
+    n, steps, peds = enc.n, int(enc.step_off[-1]), int(enc.ped_base[-1])
+    out = np.zeros(max(n, 1), dtype=FIDELITY_ENC_DT)
+    series = np.zeros(max(steps, 1))
+    dist = np.full(max(peds, 1), np.nan)
+    step = np.full(max(peds, 1), -1, dtype=np.int32)
+    addr = lambda a: None if a is None else a.ctypes.data
+    n_ped, dt = (enc.n_ped, enc.dt) if n else (np.zeros(1, np.int32), np.ones(1))
+    _abi.check(handle, lib.fot_fidelity_eval(handle, C.byref(p), n, addr(enc.step_off), addr(n_ped), addr(dt), addr(enc.ego),
+                                             addr(enc.ped), addr(enc.vel), addr(enc.truth), addr(series), addr(dist),
+                                             addr(step), addr(out)))
+    return out[:n], series[:steps], dist[:peds], step[:peds]
+
+
 def request_from_instance(inst, **kw) -> PlanRequest:
     """plan() arguments of a ``synthetic.Instance`` (the distribution wins over the single sample, as in the
     reference: frenet_planner.py:1043-1047)."""

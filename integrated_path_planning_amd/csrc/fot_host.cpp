@@ -82,6 +82,7 @@ void destroy_handle(fot_handle *h)
     for (fot_handle::Sgan &g : h->sgan) g.release();
     h->ol.release();
     h->fp.release();
+    h->fid.release();
     h->loop.release();
     for (hipEvent_t e : h->prof_pool) (void)hipEventDestroy(e);
     if (h->fork) (void)hipEventDestroy(h->fork);

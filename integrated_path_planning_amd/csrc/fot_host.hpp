@@ -405,6 +405,11 @@ struct fot_handle {
         DevBuf dIn, dYaw, dSeries, dOut;
         void release() { dIn.release(); dYaw.release(); dSeries.release(); dOut.release(); }
     } fp;
+    // fot_fidelity_eval: the tables and the encounters' arrays, and everything the kernels write, in HBM (grow-only)
+    struct Fidelity {
+        DevBuf dIn, dOut;
+        void release() { dIn.release(); dOut.release(); }
+    } fid;
     LoopState loop;
     // fot_sgan_*: the loaded models (descriptor, device image of the weights), each with the work arrays of its own sample
     // calls -- what model m computes never depends on what else is loaded or was sampled in between

@@ -788,4 +788,79 @@ int fot_footprint_recheck(fot_handle *h, const fot_footprint_geom *geom, int32_t
     return FOT_OK;
 }
 
+// ---- fidelity statistics of encounters (include/fot.h; the shared arithmetic and checks: fot_fidelity.hpp) ---------------------
+int fot_fidelity_eval(fot_handle *h, const fot_fidelity_params *p, int32_t n_enc, const int32_t *step_off, const int32_t *n_ped,
+                      const double *dt, const double *ego_xy, const double *ped_xy, const double *ped_vel,
+                      const double *truth_xy, double *sep_series, double *onset_dist, int32_t *onset_step,
+                      fot_fidelity_enc *out)
+{
+    static_assert(sizeof(FidParams) == sizeof(fot_fidelity_params) && sizeof(FidEnc) == sizeof(fot_fidelity_enc) &&
+                  offsetof(FidEnc, closest_step) == offsetof(fot_fidelity_enc, closest_step) &&
+                  offsetof(FidEnc, err_count) == offsetof(fot_fidelity_enc, err_count),
+                  "FidParams / FidEnc are fot_fidelity_params / fot_fidelity_enc");
+    if (!h) return FOT_ERR_INVALID;
+    const std::string who = "fot_fidelity_eval: ";
+    if (!p || !ego_xy || !ped_xy || !out) return fail(h, FOT_ERR_INVALID, who + "p / ego_xy / ped_xy / out is NULL");
+    FidParams P;
+    P.accel_threshold = p->accel_threshold; P.max_distance = p->max_distance; P.interaction_distance = p->interaction_distance;
+    const char *why = "";
+    if (fid_check_params(P, &why) || fid_check_tables(n_enc, step_off, n_ped, dt, &why)) return fail(h, FOT_ERR_INVALID, who + why);
+    if (n_enc == 0) return FOT_OK;
+    // the row and pedestrian offsets, in 64 bits: an encounter's rows are T_e N_e
+    std::vector<int64_t> off64(2 * ((size_t)n_enc + 1));
+    int64_t *row_off = off64.data(), *ped_base = row_off + n_enc + 1;
+    row_off[0] = ped_base[0] = 0;
+    for (int e = 0; e < n_enc; ++e) {
+        row_off[e + 1] = row_off[e] + (int64_t)(step_off[e + 1] - step_off[e]) * n_ped[e];
+        ped_base[e + 1] = ped_base[e] + n_ped[e];
+    }
+    const size_t ne = (size_t)n_enc, steps = (size_t)step_off[n_enc], rows = (size_t)row_off[n_enc], peds = (size_t)ped_base[n_enc];
+    // the inputs as one block: step_off | n_ped | dt | row_off, ped_base | ego | ped_xy | ped_vel | truth
+    const size_t soff_b = align256(sizeof(int32_t) * (ne + 1)), nped_b = align256(sizeof(int32_t) * ne);
+    const size_t dt_b = align256(sizeof(double) * ne), o64_b = align256(sizeof(int64_t) * off64.size());
+    const size_t ego_b = align256(sizeof(double) * 2 * steps), arr_b = align256(sizeof(double) * 2 * std::max<size_t>(rows, 1));
+    const size_t in_b = soff_b + nped_b + dt_b + o64_b + ego_b + arr_b * (1 + (ped_vel ? 1 : 0) + (truth_xy ? 1 : 0));
+    // what the kernels write: series | onset_dist | ped_sum | onset_step | ped_keep | out
+    const size_t ser_b = align256(sizeof(double) * steps), pd_b = align256(sizeof(double) * std::max<size_t>(peds, 1));
+    const size_t pi_b = align256(sizeof(int32_t) * std::max<size_t>(peds, 1)), rec_b = sizeof(FidEnc) * ne;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    fot_handle::Fidelity &F = h->fid;
+    HIP_TRY(h, F.dIn.ensure(in_b));
+    HIP_TRY(h, F.dOut.ensure(ser_b + 2 * pd_b + 2 * pi_b + rec_b));
+    { int r = order_begin(h, st); if (r != FOT_OK) return r; }
+    char *b_soff = (char *)F.dIn.p, *b_nped = b_soff + soff_b, *b_dt = b_nped + nped_b, *b_o64 = b_dt + dt_b;
+    char *b_ego = b_o64 + o64_b, *b_xy = b_ego + ego_b, *b_vel = b_xy + arr_b, *b_truth = b_vel + (ped_vel ? arr_b : 0);
+    auto put = [&](char *dst, const void *src, size_t bytes) -> hipError_t {
+        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+    };
+    HIP_TRY(h, put(b_soff, step_off, sizeof(int32_t) * (ne + 1)));
+    HIP_TRY(h, put(b_nped, n_ped, sizeof(int32_t) * ne));
+    HIP_TRY(h, put(b_dt, dt, sizeof(double) * ne));
+    HIP_TRY(h, put(b_o64, off64.data(), sizeof(int64_t) * off64.size()));
+    HIP_TRY(h, put(b_ego, ego_xy, sizeof(double) * 2 * steps));
+    HIP_TRY(h, put(b_xy, ped_xy, sizeof(double) * 2 * rows));
+    if (ped_vel) HIP_TRY(h, put(b_vel, ped_vel, sizeof(double) * 2 * rows));
+    if (truth_xy) HIP_TRY(h, put(b_truth, truth_xy, sizeof(double) * 2 * rows));
+    char *o_ser = (char *)F.dOut.p, *o_dist = o_ser + ser_b, *o_sum = o_dist + pd_b, *o_step = o_sum + pd_b;
+    char *o_keep = o_step + pi_b, *o_rec = o_keep + pi_b;
+    FidelityArgs A;
+    A.n_enc = n_enc; A.n_steps = (int64_t)steps; A.n_peds = (int64_t)peds;
+    A.step_off = (const int32_t *)b_soff; A.n_ped = (const int32_t *)b_nped; A.dt = (const double *)b_dt;
+    A.row_off = (const int64_t *)b_o64; A.ped_base = A.row_off + n_enc + 1;
+    A.ego = (const double *)b_ego; A.ped_xy = (const double *)b_xy;
+    A.ped_vel = ped_vel ? (const double *)b_vel : nullptr; A.truth = truth_xy ? (const double *)b_truth : nullptr;
+    A.p = P;
+    A.series = (double *)o_ser; A.onset_dist = (double *)o_dist; A.ped_sum = (double *)o_sum;
+    A.onset_step = (int32_t *)o_step; A.ped_keep = (int32_t *)o_keep; A.out = (FidEnc *)o_rec;
+    LAUNCH_TRY(h, launch_fidelity(A, st));
+    if (sep_series) HIP_TRY(h, hipMemcpyAsync(sep_series, o_ser, sizeof(double) * steps, hipMemcpyDeviceToHost, st));
+    if (onset_dist && peds) HIP_TRY(h, hipMemcpyAsync(onset_dist, o_dist, sizeof(double) * peds, hipMemcpyDeviceToHost, st));
+    if (onset_step && peds) HIP_TRY(h, hipMemcpyAsync(onset_step, o_step, sizeof(int32_t) * peds, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(out, o_rec, rec_b, hipMemcpyDeviceToHost, st));
+    { int r = order_end(h, st); if (r != FOT_OK) return r; }
+    HIP_TRY(h, hipStreamSynchronize(st));             // (off64 and the caller's arrays are read until here)
+    return FOT_OK;
+}
+
 }  // extern "C"

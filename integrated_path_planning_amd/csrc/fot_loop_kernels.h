@@ -12,6 +12,7 @@
 #include "fot_sweep.hpp"
 #include "fot_openloop.hpp"
 #include "fot_footprint_obs.hpp"
+#include "fot_fidelity.hpp"
 
 namespace fot {
 
@@ -200,5 +201,24 @@ int launch_footprint_yaw(int n_traj, const int32_t *step_off, const double *xy, 
 // the trajectories' records from their steps' records
 int launch_footprint_fold(const FpoGeom *geom, int n_traj, const int32_t *step_off, const int32_t *ped_off,
                           const FpoStep *series, FpoRecord *out, hipStream_t st);
+
+// ---- fot_fidelity_eval (fot_fidelity.hpp).  Encounter e owns the steps step_off[e] .. step_off[e + 1] - 1 of ego [steps][2]
+// and the rows row_off[e] .. of ped_xy / ped_vel / truth ([T_e][N_e][2] each, back to back; ped_vel and truth may be NULL);
+// its pedestrians are entries ped_base[e] .. ped_base[e + 1] - 1 of the per-pedestrian arrays.  One launch each: lane =
+// pedestrian (onset, error sum, kept), lane = step (separation), wave = encounter (record).
+struct FidelityArgs {
+    int32_t n_enc;
+    int64_t n_steps, n_peds;
+    const int32_t *step_off, *n_ped;             // [n_enc + 1] | [n_enc]
+    const double *dt;                            // [n_enc]
+    const int64_t *row_off, *ped_base;           // [n_enc + 1] each
+    const double *ego, *ped_xy, *ped_vel, *truth;
+    FidParams p;
+    double *series;                              // [steps]
+    double *onset_dist, *ped_sum;                // [sum N]
+    int32_t *onset_step, *ped_keep;              // [sum N]
+    FidEnc *out;                                 // [n_enc]
+};
+int launch_fidelity(const FidelityArgs &a, hipStream_t st);
 
 }  // namespace fot

@@ -7,6 +7,9 @@
 //   k_footprint_steps / _yaw / _fold
 //                                fot_footprint_recheck: centre, circle cover and exact rectangle per step, the heading
 //                                reconstruction, the fold of a trajectory
+//   k_fidelity_peds / _series / _fold
+//                                fot_fidelity_eval: avoidance onset and roll-out error per pedestrian, the separation per
+//                                step, the record of an encounter
 //   k_loop_* / k_static_gather / k_predict_cv_frame
 //                                the resident loop (fot_loop_run): frame, sample gather, prediction, digests, history,
 //                                prediction-error summaries, predictor scores, representative sample
@@ -886,6 +889,104 @@ k_footprint_fold(const FpoGeom *__restrict__ geom, const int32_t *__restrict__ s
 }
 
 // ---------------------------------------------------------------------------
+// fot_fidelity_eval (fot_fidelity.hpp): separation series, avoidance onset and roll-out error of ragged encounters
+// ---------------------------------------------------------------------------
+constexpr int FID_THREADS = 256;
+
+// the encounter that owns entry g of a table of n + 1 non-decreasing offsets from 0: the LAST e with off[e] <= g (an
+// encounter without entries shares its offset with the next one and is never the answer); g < off[n]
+template <typename T>
+__device__ __forceinline__ int fid_owner(const T *__restrict__ off, int n, int64_t g)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if ((int64_t)off[mid] <= g) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Lane = pedestrian, over all encounters' pedestrians back to back, so that waves stay full however small the crowds
+// are: the rows [t][0 .. N) are contiguous over the lanes of an encounter.  Each lane walks its own steps in ascending
+// order with a sliding window of three velocities and leaves the walk at its first onset; the wave leaves when all of
+// its lanes have.  With a truth array a second walk over all steps sums the pedestrian's error.  Nothing is shared
+// between lanes: what a pedestrian gets depends on its encounter alone.
+__global__ void __launch_bounds__(FID_THREADS)
+k_fidelity_peds(FidelityArgs A)
+{
+    const int64_t g = (int64_t)blockIdx.x * FID_THREADS + threadIdx.x;
+    if (g >= A.n_peds) return;
+    const int e = fid_owner(A.ped_base, A.n_enc, g);
+    const int64_t j = g - A.ped_base[e], N = A.n_ped[e];
+    const int s0 = A.step_off[e], T = A.step_off[e + 1] - s0;
+    const double dt = A.dt[e];
+    const double *__restrict__ eg = A.ego + 2 * (int64_t)s0;
+    const int64_t first = 2 * (A.row_off[e] + j), stride = 2 * N;   // (t, c) of this pedestrian: first + t stride + c
+    const double *__restrict__ xy = A.ped_xy + first;
+    auto pos = [&](int t, int c) { return xy[t * stride + c]; };
+    auto ego = [&](int t, int c) { return eg[2 * t + c]; };
+    int32_t step;
+    double dist, away;
+    if (A.ped_vel) {
+        const double *__restrict__ v = A.ped_vel + first;
+        auto vel = [&](int t, int c) { return v[t * stride + c]; };
+        fid_onset(pos, vel, ego, T, dt, A.p, &step, &dist, &away);
+    } else {
+        auto vel = [&](int t, int c) { return fid_gradient([&](int s) { return xy[s * stride + c]; }, t, T, dt); };
+        fid_onset(pos, vel, ego, T, dt, A.p, &step, &dist, &away);
+    }
+    A.onset_step[g] = step;
+    A.onset_dist[g] = dist;
+    if (A.truth) {
+        const double *__restrict__ q = A.truth + first;
+        auto truth = [&](int t, int c) { return q[t * stride + c]; };
+        double sum;
+        int32_t keep;
+        fid_ped_error(pos, truth, ego, T, A.p.interaction_distance, &sum, &keep);
+        A.ped_sum[g] = sum;
+        A.ped_keep[g] = keep;
+    }
+}
+
+// Lane = step, over all encounters' steps back to back: the minimum over the step's pedestrians in ascending order, as
+// np.min forms it (a NaN stays).  A lane reads its row of N positions front to back; neighbouring lanes own
+// neighbouring rows, so every line fetched is used whole.
+__global__ void __launch_bounds__(FID_THREADS)
+k_fidelity_series(FidelityArgs A)
+{
+    const int64_t g = (int64_t)blockIdx.x * FID_THREADS + threadIdx.x;
+    if (g >= A.n_steps) return;
+    const int e = fid_owner(A.step_off, A.n_enc, g);
+    const int t = (int)(g - A.step_off[e]), N = A.n_ped[e];
+    const double *__restrict__ r = A.ped_xy + 2 * (A.row_off[e] + (int64_t)t * N);
+    auto row = [&](int j, int c) { return r[2 * j + c]; };
+    A.series[g] = fid_separation(row, N, A.ego[2 * g], A.ego[2 * g + 1]);
+}
+
+// One wave per encounter: the series' minimum and its first step (lanes stride over the steps, the wave joins with
+// shuffles: the join is exact in any order), then lane 0 adds the kept pedestrians' error sums in ascending order.
+__global__ void __launch_bounds__(WAVE)
+k_fidelity_fold(FidelityArgs A)
+{
+    const int e = blockIdx.x;
+    if (e >= A.n_enc) return;
+    const int s0 = A.step_off[e], T = A.step_off[e + 1] - s0, N = A.n_ped[e];
+    FidMin m = fid_min_zero();
+    for (int t = threadIdx.x; t < T; t += WAVE) m = fid_min_take(m, A.series[s0 + t], t);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        FidMin o;
+        o.v = __shfl_xor(m.v, off, WAVE); o.step = __shfl_xor(m.step, off, WAVE); o.nan = __shfl_xor(m.nan, off, WAVE);
+        m = fid_min_join(m, o);
+    }
+    if (threadIdx.x != 0) return;
+    const int64_t b = A.ped_base[e];
+    const bool have_truth = A.truth != nullptr;
+    A.out[e] = fid_record(m, T, N, have_truth, [&](int j) { return A.ped_sum[b + j]; }, [&](int j) { return A.ped_keep[b + j] != 0; },
+                          [&](int j) { return A.onset_step[b + j]; });
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
 
@@ -1123,6 +1224,26 @@ int launch_footprint_fold(const FpoGeom *geom, int n_traj, const int32_t *step_o
     if (n_traj <= 0) return 0;
     if (!geom || !step_off || !ped_off || !series || !out) return (int)hipErrorInvalidValue;
     k_footprint_fold<<<n_traj, FPO_THREADS, 0, st>>>(geom, step_off, ped_off, series, out);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_fidelity(const FidelityArgs &a, hipStream_t st)
+{
+    if (a.n_enc <= 0) return 0;
+    if (!a.step_off || !a.n_ped || !a.dt || !a.row_off || !a.ped_base || !a.ego || !a.series || !a.out || a.n_steps <= 0 ||
+        a.n_peds < 0) return (int)hipErrorInvalidValue;
+    if (a.n_peds > 0 && (!a.ped_xy || !a.onset_dist || !a.onset_step || (a.truth && (!a.ped_sum || !a.ped_keep))))
+        return (int)hipErrorInvalidValue;
+    const int64_t ped_blocks = (a.n_peds + FID_THREADS - 1) / FID_THREADS, step_blocks = (a.n_steps + FID_THREADS - 1) / FID_THREADS;
+    if (ped_blocks > 0x7fffffffLL || step_blocks > 0x7fffffffLL) return (int)hipErrorInvalidConfiguration;
+    if (ped_blocks > 0) {
+        k_fidelity_peds<<<(unsigned)ped_blocks, FID_THREADS, 0, st>>>(a);
+        FOT_LAUNCH_CHECK();
+    }
+    k_fidelity_series<<<(unsigned)step_blocks, FID_THREADS, 0, st>>>(a);
+    FOT_LAUNCH_CHECK();
+    k_fidelity_fold<<<a.n_enc, WAVE, 0, st>>>(a);
     FOT_LAUNCH_CHECK();
     return 0;
 }

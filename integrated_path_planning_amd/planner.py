@@ -16,6 +16,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _abi
+from . import batch as _batch
 from .batch import PackedBatch, PlanRequest
 from .data_structures import EgoVehicleState, FrenetPath, FrenetState
 from .params import (D_ROAD_W, D_T_S, DT, MAX_ACCEL, MAX_CURVATURE, MAX_ROAD_WIDTH, MAX_SPEED, MAX_T, MIN_T,
@@ -916,6 +917,13 @@ class BatchPlanner:
         out = np.zeros(max(n, 1), dtype=self.FOOTPRINT_OBS_DT)
         _abi.check(self._h, self._lib.fot_loop_footprint_obs(self._h, n, _addr(out)))
         return out[:n]
+
+    def fidelity_eval(self, encounters: "_batch.PackedEncounters", **thresholds):
+        """``fot_fidelity_eval`` (``batch.fidelity_eval``): separation, avoidance onset and roll-out error of packed
+        encounters in one call."""
+        if not hasattr(self._lib, "fot_fidelity_eval"):
+            raise RuntimeError("this libfot.so has no fot_fidelity_eval: rebuild it")
+        return _batch.fidelity_eval(self._lib, self._h, encounters, **thresholds)
 
     def _loop_frame(self, frame: dict):
         """fot_loop_frame from the dictionary ``loop_plan`` / ``loop_step`` take (+ the arrays it points into)."""
