@@ -681,6 +681,9 @@ struct FusedSink {
     // end of the time step, reached by every lane: the warm-up loads have landed, pf may be reused
     __device__ __forceinline__ void row_end(int) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(pf) : : "memory"); }
 
+    // the current time step has chunks to test a point against (wave-uniform; put32 returns at once without)
+    __device__ __forceinline__ bool step_has_points() const { return n_chunks != 0; }
+
     __device__ __forceinline__ void put(int k, int ci, double px, double py, bool alive)
     {
         // (the rows are instance-local: evaluate_tile) -- the point itself is its own exact form
@@ -835,6 +838,13 @@ struct StagedTab {
         double s_, u0, u1, u2;
         lon_sample(*info, k, dt, s_, u0, u1, u2);
         return s_;
+    }
+    // the reference frame of row k alone, through load()'s clamp: for k - 1 the row step k - 1 read (the low-speed rule)
+    __device__ __forceinline__ void frame_at(int k, double &cos_r, double &sin_r) const
+    {
+        const int kk = k < k_max ? k : k_max;
+        const double *r = s_lon + lds_row0 + kk * ROW_FIELDS;
+        cos_r = r[4]; sin_r = r[5];
     }
 };
 

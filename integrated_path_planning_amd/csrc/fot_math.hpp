@@ -550,11 +550,30 @@ struct LonSample {
 
 struct CartSample {
     double x, y, cos_t, sin_t, kappa, v, a, omkd;
+    double cos_d, sin_d;                 // heading relative to the reference frame (cos_t, sin_t: frenet_to_cart<true> only)
 };
+
+// Heading of a sample from its heading relative to the reference frame and the frame's own.  ONE source text for every
+// caller: under -ffp-contract=on each of them forms the same two contractions, so the heading a later step composes
+// again from (cos_d, sin_d) and the row has the bits of the one frenet_to_cart hands out.
+FOT_HD void compose_heading(double cos_d, double sin_d, double cos_r, double sin_r, double &cos_t, double &sin_t)
+{
+    cos_t = cos_d * cos_r - sin_d * sin_r;
+    sin_t = sin_d * cos_r + cos_d * sin_r;
+}
+
+// sin / cos of the yaw step between two headings (the low-speed rule, :1013-1022)
+FOT_HD void yaw_step_sin_cos(double cos_t, double sin_t, double prev_cos_t, double prev_sin_t, double &sn, double &cs)
+{
+    sn = sin_t * prev_cos_t - cos_t * prev_sin_t;
+    cs = cos_t * prev_cos_t + sin_t * prev_sin_t;
+}
 
 // One reciprocal and one reciprocal square root per sample: with h = sqrt(d'^2 + (1-kd)^2) the
 // reference's atan2/cos/tan terms are cos = (1-kd)/h, sin = d'/h, tan = d'/(1-kd), (1-kd)/cos = h and
 // v = sqrt((1-kd)^2 sd^2 + (d' sd)^2) = |sd| h.
+// HEADING = false: cos_t / sin_t are left alone -- the evaluation walk composes them where they are read (check_sample).
+template <bool HEADING = true>
 FOT_HD void frenet_to_cart(const LonSample &L, double d, double d_d, double d_dd, CartSample &o)
 {
     const double dp = d_d * L.inv_sd;
@@ -574,8 +593,8 @@ FOT_HD void frenet_to_cart(const LonSample &L, double d, double d_d, double d_dd
     const double dtp = h * kappa - L.kr;
     o.x = L.rx - L.sin_r * d;
     o.y = L.ry + L.cos_r * d;
-    o.cos_t = cos_d * L.cos_r - sin_d * L.sin_r;
-    o.sin_t = sin_d * L.cos_r + cos_d * L.sin_r;
+    o.cos_d = cos_d; o.sin_d = sin_d;
+    if constexpr (HEADING) compose_heading(cos_d, sin_d, L.cos_r, L.sin_r, o.cos_t, o.sin_t);
     o.kappa = kappa;
     o.v = fabs(L.sd) * h;
     o.a = L.sdd * h + L.sd * L.sd * inv_cos * (dp * dtp - krdp);
@@ -633,6 +652,8 @@ struct CandResult {
 // Running state of the per-candidate checks of _check_paths (frenet_planner.py:932-984) over the
 // kept prefix of a path.  One sample at a time, so the lattice kernel and the external-path entry
 // (fot_check_paths) share the exact same tests.
+// cos_t, sin_t: the heading -- or, where the checks get the reference frames of both samples (FrameHeadings: the lattice
+// walk), the heading RELATIVE to the frame (CartSample::cos_d, sin_d), from which the low-speed rule composes the heading.
 struct PathSample {
     double x, y, cos_t, sin_t, kappa, v, a, d;
 };
@@ -667,6 +688,9 @@ enum : uint32_t {
 struct CheckAcc {
     uint32_t fl;                         // CK_* bits
     double max_step2;                    // largest squared step between consecutive samples
+    // check_sample: the largest v, |a|, v^2 |kappa| and |d| over the checked samples k > 0.  "Some sample exceeds the limit"
+    // is "the maximum exceeds it": check_fold() turns them into CK_SPEED / CK_ACCEL / CK_LAT / CK_ROAD behind the walk
+    double max_v, max_a, max_lat, max_d;
     PathSample prev;
 };
 
@@ -674,6 +698,7 @@ FOT_HD void check_init(CheckAcc &c)
 {
     c.fl = 0;
     c.max_step2 = -INFINITY;
+    c.max_v = c.max_a = c.max_lat = c.max_d = -INFINITY;
     c.prev.x = c.prev.y = c.prev.kappa = c.prev.v = c.prev.a = c.prev.d = 0.0;
     c.prev.cos_t = 1.0; c.prev.sin_t = 0.0;
 }
@@ -715,12 +740,58 @@ FOT_HD void step2_max(double &m, double v)
 #endif
 }
 
-// k = index of the sample inside the path; has_geo / has_d: the low-speed rules and the road test
-// only apply when the caller's path carries the arrays they read (:1013-1022, :982).  arc_step() returns
-// |s_k - s_{k-1}|; it is only asked for in the low-speed branch.
+// m = max(m, |v|), the same way: the source modifier costs nothing, and |v| of an arithmetic result is as little a
+// signalling NaN or (over a start value of -inf, compared with `>` afterwards) a zero whose sign matters.
+FOT_HD void abs_max(double &m, double v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_max_f64 %0, |%1|, %2" : "=v"(m) : "v"(v), "v"(m));
+#else
+    if (fabs(v) > m) m = fabs(v);
+#endif
+}
+
+// What the low-speed rule of check_sample asks of its caller: arc_step() returns |s_k - s_{k-1}|, headings() the
+// (cos, sin) of the heading of sample k and of its predecessor.  Both are asked for in the low-speed branch only.
+// CarriedHeadings: the samples carry their heading (PathSample::cos_t, sin_t).
 template <class ArcStep>
-FOT_HD void check_sample(const LoopConst &C, CheckAcc &c, int k, const PathSample &p, bool has_geo, bool has_d,
-                         const ArcStep &arc_step)
+struct CarriedHeadings {
+    const ArcStep &arc;
+    FOT_HD double arc_step() const { return arc(); }
+    FOT_HD void headings(const PathSample &p, const PathSample &prev, double &ct, double &st, double &pct, double &pst) const
+    {
+        ct = p.cos_t; st = p.sin_t; pct = prev.cos_t; pst = prev.sin_t;
+    }
+};
+// FrameHeadings: the samples carry the heading relative to the reference frame, and the headings are composed HERE,
+// in the branch that reads them, instead of in every step: the previous sample's with the frame of the table's row k - 1
+// -- through the table's own clamp, so a holding brake-ladder lane gets its hold row, the row step k - 1 used.  Sample k's:
+// with (cos_r, sin_r) of row k, handed over by value (HAVE_CUR false); a caller that has formed that heading anyway, for
+// the footprint circles, hands it over in their place (HAVE_CUR true).
+template <class Tab, bool HAVE_CUR>
+struct FrameHeadings {
+    const Tab &tab;
+    int k;
+    double cos_c, sin_c;                 // HAVE_CUR: heading of sample k, else: frame of row k
+    FOT_HD double arc_step() const { return fabs(tab.s_at(k) - tab.s_at(k - 1)); }
+    FOT_HD void headings(const PathSample &p, const PathSample &prev, double &ct, double &st, double &pct, double &pst) const
+    {
+        double pcr, psr;
+        tab.frame_at(k - 1, pcr, psr);
+        if constexpr (HAVE_CUR) { ct = cos_c; st = sin_c; }
+        else compose_heading(p.cos_t, p.sin_t, cos_c, sin_c, ct, st);
+        compose_heading(prev.cos_t, prev.sin_t, pcr, psr, pct, pst);
+    }
+};
+
+// k = index of the sample inside the path; has_geo / has_d: the low-speed rules and the road test
+// only apply when the caller's path carries the arrays they read (:1013-1022, :982).
+// The four limits that are plain thresholds on a value of the sample keep a running maximum here instead of a flag
+// (one v_max_f64 each in place of a compare, a select and an OR): check_fold() sets the flags behind the walk, and
+// check_over_limit() is the same test for whoever needs it in between.  Like the flags, the maxima only see samples k > 0.
+template <class Geo>
+FOT_HD void check_sample_geo(const LoopConst &C, CheckAcc &c, int k, const PathSample &p, bool has_geo, bool has_d,
+                             const Geo &geo)
 {
     check_flag(c, !(isfinite(p.v) && isfinite(p.a) && isfinite(p.kappa)), CK_NONFINITE);     // :944-946
     if (k > 0) {
@@ -728,24 +799,54 @@ FOT_HD void check_sample(const LoopConst &C, CheckAcc &c, int k, const PathSampl
         const double step2 = sum_sq_unfused(sx, sy);
         check_flag(c, isnan(step2), CK_NANSTEP);
         step2_max(c.max_step2, step2);
-        check_flag(c, p.v > C.lim_speed, CK_SPEED);                                           // :964
-        check_flag(c, fabs(p.a) > C.lim_accel, CK_ACCEL);                                     // :966
-        if (p.v > 0.5) {                                                                       // LOW_SPEED_CURVATURE_GATE
-            check_flag(c, fabs(p.kappa) > C.lim_curv, CK_CURV);
-        } else if (has_geo) {
+        step2_max(c.max_v, p.v);                                                              // :964
+        abs_max(c.max_a, p.a);                                                                // :966
+        step2_max(c.max_lat, p.v * p.v * fabs(p.kappa));                                      // :975
+        if (has_d) abs_max(c.max_d, p.d);                                                     // :982
+        // (the fast lanes' rule as a select in front of the branch, which is then the low-speed lanes' alone and the
+        //  last thing of the step: a branch with two sides, or with code behind it, has the compiler merge the sides'
+        //  flag updates as lane masks in scalar registers)
+        const bool fast = p.v > 0.5;                                                           // LOW_SPEED_CURVATURE_GATE
+        check_flag(c, fast && fabs(p.kappa) > C.lim_curv, CK_CURV);
+        if (!fast && has_geo) {
             const double dd = fabs(p.d - c.prev.d);
-            const double d_s = arc_step();
+            const double d_s = geo.arc_step();
             check_flag(c, dd > fmax(1.5 * d_s, 0.02), CK_CURV);                               // lateral slip
-            const double sn = p.sin_t * c.prev.cos_t - p.cos_t * c.prev.sin_t;                // sin/cos of the yaw step
-            const double cs = p.cos_t * c.prev.cos_t + p.sin_t * c.prev.sin_t;
+            // (headings() behind the arc step: asked for first, so that FrameHeadings' table read goes out with the arc
+            //  step's, every leg measured slower -- DESIGN.md section 7 item 0, round 29)
+            double ct, st, pct, pst, sn, cs;
+            geo.headings(p, c.prev, ct, st, pct, pst);
+            yaw_step_sin_cos(ct, st, pct, pst, sn, cs);
             // yaw-step cap: the cap is at least 0.1 rad and |atan2(sn, cs)| <= |sn| / cs for cs > 0, so a step with
             // |sn| <= 0.09 cs can never exceed it -- the arc tangent (and the square root) only for the others
             if (!(cs > 0.0 && fabs(sn) <= 0.09 * cs)) check_flag(c, yaw_step_over_cap(sn, cs, C.lim_curv, step2), CK_CURV);
         }
-        check_flag(c, p.v * p.v * fabs(p.kappa) > C.lim_lat, CK_LAT);                         // :975
-        check_flag(c, has_d && fabs(p.d) > C.road_lim, CK_ROAD);                 // :982
     }
     c.prev = p;
+}
+
+// the form for samples that carry their heading; arc_step() returns |s_k - s_{k-1}|
+template <class ArcStep>
+FOT_HD void check_sample(const LoopConst &C, CheckAcc &c, int k, const PathSample &p, bool has_geo, bool has_d,
+                         const ArcStep &arc_step)
+{
+    check_sample_geo(C, c, k, p, has_geo, has_d, CarriedHeadings<ArcStep>{ arc_step });
+}
+
+// some checked sample so far exceeds one of the four limits check_sample keeps as maxima
+FOT_HD bool check_over_limit(const LoopConst &C, const CheckAcc &c)
+{
+    return c.max_v > C.lim_speed || c.max_a > C.lim_accel || c.max_lat > C.lim_lat || c.max_d > C.road_lim;
+}
+
+// the maxima of check_sample as the flags everything behind a walk reads (seg_merge, check_status); a quiet-NaN value
+// left its maximum alone as its compare left the flag alone, so these are the bits the per-sample compares gave
+FOT_HD void check_fold(const LoopConst &C, CheckAcc &c)
+{
+    check_flag(c, c.max_v > C.lim_speed, CK_SPEED);
+    check_flag(c, c.max_a > C.lim_accel, CK_ACCEL);
+    check_flag(c, c.max_lat > C.lim_lat, CK_LAT);
+    check_flag(c, c.max_d > C.road_lim, CK_ROAD);
 }
 
 // check_sample for an externally constructed path (fot_check_paths), whose arrays may differ in length: the reference
@@ -833,6 +934,9 @@ FOT_HD double lateral_jerk_sum(const double *q, int n_eval, double dt)
 //                                 has already failed a check, i.e. can no longer end as "collision check outstanding"
 // and collided() tells whether the points handed over so far violate the (chance) constraint.
 // Tab::load(k, LonSample&) returns row k of the candidate's longitudinal profile: state and reference frame at s(t_k).
+// Tab::frame_at(k, cos_r, sin_r): the reference frame of that row alone (the low-speed rule, for row k - 1).
+// A sink may say whether the current step has anything to test a point against (step_has_points(), wave-uniform): the
+// walk then leaves out what only put() reads in the steps that have nothing; a sink without it is asked in every step.
 // GlobalTab reads a [field][FOT_MAX_NT] table from memory, ComputeTab evaluates the row on the spot (rows past the
 // profile's n_t are never used and come back unspecified).
 struct GlobalTab {
@@ -840,6 +944,7 @@ struct GlobalTab {
     const double *tab;
     FOT_HD void load(int k, LonSample &L) const { load_lon_sample(tab, k, L); }
     FOT_HD double s_at(int k) const { return tab[k]; }
+    FOT_HD void frame_at(int k, double &cos_r, double &sin_r) const { cos_r = tab[5 * FOT_MAX_NT + k]; sin_r = tab[6 * FOT_MAX_NT + k]; }
 };
 
 struct ComputeTab {
@@ -858,6 +963,12 @@ struct ComputeTab {
         double s_, u0, u1, u2;
         lon_sample(L, k, dt, s_, u0, u1, u2);
         return s_;
+    }
+    FOT_HD void frame_at(int k, double &cos_r, double &sin_r) const
+    {
+        LonSample o;
+        load(k, o);
+        cos_r = o.cos_r; sin_r = o.sin_r;
     }
 };
 
@@ -887,6 +998,11 @@ FOT_HD void seg_init(SegState &g)
 // below it no lane holds (brake-ladder profiles hold, from their n_eval on): a scalar branch skips what lat_sample
 // spends on the hold -- the compare, the held step and the three zeroed derivatives.  0 (the host): no step skips it;
 // a value that is too small costs time, never a bit.
+template <class Sink>
+FOT_HD auto sink_has_points(const Sink &s, int) -> decltype(s.step_has_points()) { return s.step_has_points(); }
+template <class Sink>
+FOT_HD bool sink_has_points(const Sink &, long) { return true; }
+
 template <bool LEAN = false, bool SREG = true, class Tab, class Sink>
 FOT_HD void evaluate_segment(const DevParams &P, const LoopConst &C, const LonInfo &L, const Tab &lon_tab,
                              const double *q, int k0, int k1, Sink &sink, SegState &g, int ne_min = 0)
@@ -899,8 +1015,8 @@ FOT_HD void evaluate_segment(const DevParams &P, const LoopConst &C, const LonIn
         double d, d_d, d_dd, d_ddd;
         lat_sample(q, k0 - 1, L.n_eval, C.dt, d, d_d, d_dd, d_ddd);
         CartSample c;
-        frenet_to_cart(ls, d, d_d, d_dd, c);
-        acc.prev.x = c.x; acc.prev.y = c.y; acc.prev.cos_t = c.cos_t; acc.prev.sin_t = c.sin_t;
+        frenet_to_cart<false>(ls, d, d_d, d_dd, c);
+        acc.prev.x = c.x; acc.prev.y = c.y; acc.prev.cos_t = c.cos_d; acc.prev.sin_t = c.sin_d;   // (relative: FrameHeadings)
         acc.prev.kappa = c.kappa; acc.prev.v = c.v; acc.prev.a = c.a; acc.prev.d = d;
     }
 #if defined(__HIP_DEVICE_COMPILE__) && defined(FOT_EVAL_UNROLL)
@@ -927,7 +1043,7 @@ FOT_HD void evaluate_segment(const DevParams &P, const LoopConst &C, const LonIn
         }
         g.d_last = d;
         CartSample c;
-        frenet_to_cart(ls, d, d_d, d_dd, c);
+        frenet_to_cart<!LEAN>(ls, d, d_d, d_dd, c);                        // (the heading itself: for the footprint circles)
         check_flag(acc, isfinite(c.omkd) && c.omkd <= 0.05, CK_SINGULAR);   // SINGULARITY_EPS, any sample
         // SREG: inside a segment "a NaN sample was seen" is first_nan >= 0 (seg_init: -1) -- the walk keys on the index
         // alone, and CK_SEEN_NAN, which only the code behind the segment reads, is set once behind the loop
@@ -935,17 +1051,25 @@ FOT_HD void evaluate_segment(const DevParams &P, const LoopConst &C, const LonIn
         else if (!(acc.fl & CK_SEEN_NAN) && isnan(c.x)) { acc.fl |= CK_SEEN_NAN; g.first_nan = k; }
         if (SREG ? g.first_nan < 0 : !(acc.fl & CK_SEEN_NAN)) {
             PathSample ps;
-            ps.x = c.x; ps.y = c.y; ps.cos_t = c.cos_t; ps.sin_t = c.sin_t; ps.kappa = c.kappa;
+            ps.x = c.x; ps.y = c.y; ps.cos_t = c.cos_d; ps.sin_t = c.sin_d; ps.kappa = c.kappa;   // (relative: FrameHeadings)
             ps.v = c.v; ps.a = c.a; ps.d = d;
-            check_sample(C, acc, k, ps, true, true, [&] { return fabs(lon_tab.s_at(k) - lon_tab.s_at(k - 1)); });
-            const bool alive = (acc.fl & CK_FAILED) == 0;
-            if constexpr (LEAN) {
-                sink.put(k, 0, c.x, c.y, alive);
-            } else if (C.n_circ_fp > 0) {
-                for (int ci = 0; ci < C.n_circ_fp; ++ci)
-                    sink.put(k, ci, c.x + P.circ_off[ci] * c.cos_t, c.y + P.circ_off[ci] * c.sin_t, alive);
-            } else {
-                sink.put(k, 0, c.x, c.y, alive);
+            if constexpr (LEAN) check_sample_geo(C, acc, k, ps, true, true, FrameHeadings<Tab, false>{ lon_tab, k, ls.cos_r, ls.sin_r });
+            else check_sample_geo(C, acc, k, ps, true, true, FrameHeadings<Tab, true>{ lon_tab, k, c.cos_t, c.sin_t });
+            // alive decides speed, never a record: a hit only turns "collision check outstanding" into "collision"
+            // (finish_candidate), and a candidate over a limit ends with that limit's status, hit or not.  It is formed
+            // where it is read: in a step that has points to test -- the flag word's test and the compares of the four
+            // limits that are maxima -- and a step without points spends nothing on it.
+            if (sink_has_points(sink, 0)) {
+                FOT_KEEP_BRANCH;
+                const bool alive = (acc.fl & CK_FAILED) == 0 && !check_over_limit(C, acc);
+                if constexpr (LEAN) {
+                    sink.put(k, 0, c.x, c.y, alive);
+                } else if (C.n_circ_fp > 0) {
+                    for (int ci = 0; ci < C.n_circ_fp; ++ci)
+                        sink.put(k, ci, c.x + P.circ_off[ci] * c.cos_t, c.y + P.circ_off[ci] * c.sin_t, alive);
+                } else {
+                    sink.put(k, 0, c.x, c.y, alive);
+                }
             }
             g.v_last = c.v; g.k_last = k;
         }
@@ -953,6 +1077,7 @@ FOT_HD void evaluate_segment(const DevParams &P, const LoopConst &C, const LonIn
       sink.row_end(k);
     }
     if constexpr (SREG) { if (g.first_nan >= 0) acc.fl |= CK_SEEN_NAN; }
+    check_fold(C, acc);
 }
 
 // g (segments up to some k) followed by n (the segment that starts there and holds a sample below n_t).  Returns
