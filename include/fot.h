@@ -1171,6 +1171,97 @@ int fot_fidelity_eval(fot_handle *h, const fot_fidelity_params *p, int32_t n_enc
                       int32_t *onset_step,      /* NULL or [sum N]: -1 = no onset */
                       fot_fidelity_enc *out);   /* [n_enc] */
 
+/* ---- vehicle-pedestrian encounters cut out of a recorded clip (RQ2): spans, populations, closest approach, boundary conditions ---
+ * The reference's _ped_velocities and extract_encounters (src/datasets/vci_encounter.py) over every vehicle of a clip
+ * (_split_clip_per_vehicle), and _cruise_speeds, cruise_upper_quantile, cruise_freewalk, _floor and _far_goals
+ * (src/simulation/calibration_harness.py).  The clip is a pedestrian scene ped_xy [T][A][2] (NaN where a pedestrian is
+ * absent), optionally its recorded velocities ped_vel, and K vehicles ALREADY aligned onto the scene's grid: ego_xy
+ * [K][T][2], ego_psi and ego_vel [K][T], NaN outside a vehicle's support (the alignment is sequential host work).  The
+ * scene crosses the bus once per call, or not at all: with FOT_ENC_SCENE_DEVICE ped_xy and ped_vel are device memory,
+ * aligned to one point (16 bytes), never written, and complete before the call (it is read on the handle's stream).  The
+ * ego channels and every output are host memory.  float64
+ * throughout, NumPy's operation order (csrc/fot_encounter.hpp):
+ *   velocity    ped_vel, or with ped_vel NULL the forward difference over the WHOLE grid: vel[t] = (pos[t+1] - pos[t]) / dt,
+ *               vel[T-1] = vel[T-2], all NaN with T < 2 -- a pedestrian's last present frame has a NaN velocity unless it is
+ *               the grid's last frame
+ *   spans       the maximal runs of frames at which x, y, psi and vel of vehicle k are all finite, by vehicle ascending, then
+ *               start ascending; found on the host.  One record each.  A run shorter than min_len: FOT_ENC_SHORT
+ *   population  pedestrian a is present when no position and no velocity component over the span is NaN (isnan: an infinity
+ *               is not absence, and is otherwise unspecified).  None present: FOT_ENC_NO_PEDS.  The kept columns ascend
+ *   closest     min_separation = min over [L][N] of sqrt(dx dx + dy dy) (fot_fidelity_eval's distance), with its first step
+ *               and (compacted) column in row-major order.  min_separation > min_sep_threshold: FOT_ENC_FAR (equality keeps
+ *               the span); everything else: FOT_ENC_KEPT
+ *   rows        the kept spans' pedestrians back to back in span order: span s owns the rows row_base .. row_base + n_ped - 1
+ *               of cols (the scene's column), cruise, goals, onset_dist and onset_step; FAR spans report n_ped but own no rows
+ *   real        with FOT_ENC_MEASURE_REAL every kept span is gathered from the resident scene into fot_fidelity_eval's packed
+ *               layout and measured there from its positions (no velocity, no truth; accel_threshold, max_distance):
+ *               `real` is that call's record, real.closest the bits of min_separation; sep_series holds the kept spans' steps
+ *               back to back
+ *   cruise      per kept pedestrian, speeds[t] = sqrt(vx vx + vy vy) of the span's velocities.  FOT_ENC_CRUISE_MEDIAN: the
+ *               middle order statistic, (s[n/2-1] + s[n/2]) / 2 for even n.  _QUANTILE: np.quantile's linear method at
+ *               cruise_q: v = q (n-1), lo = floor(v), g = v - lo, d = s[lo+1] - s[lo]; s[lo] if d == 0, s[lo] + d g if g < 0.5,
+ *               else s[lo+1] - d (1 - g).  _FREEWALK: that quantile over the steps whose speed is finite and whose distance to
+ *               the ego is > free_distance; without such a step the all-step median.  Every mode ends in the floor: a value
+ *               that is not finite or not > 1e-3 becomes 1e-3.  Order statistics by counting ranks, ties by step
+ *   goals       first position + heading * goal_distance; heading = last - first position, or, if its norm < 1e-3, the first
+ *               velocity if that norm > 1e-3, else (1, 0); divided by the chosen vector's own norm
+ * ONE stateless synchronous call per clip with at most two waits: one for the spans' populations and closest approaches
+ * (which size the rows), one for everything else.  A span's record and rows are byte-identical whatever vehicles share the
+ * call, whether the scene is host or device memory, and whether ped_vel is given or equals the fallback's values.
+ * Refusals, nothing written: FOT_ERR_INVALID for p, n_spans, n_rows, spans or cols NULL; ped_xy or an ego channel NULL where
+ * T, A and K are positive; cruise or goals NULL with a cruise mode; negative T, A, K, max_spans or max_rows; dt not finite
+ * and positive; min_len < 1; a NaN threshold; cruise_q outside [0, 1] (quantile and freewalk modes); an unknown mode or
+ * flag; a misaligned device scene.  FOT_ERR_UNSUPPORTED when the spans exceed max_spans, the rows max_rows or, with
+ * sep_series, the kept spans' steps max_steps, the need named in fot_last_error.  T, A or K of 0 succeed with zero spans.
+ * An addition: no structure, capacity word of fot_abi_info or FOT_ABI_VERSION changes; a binding looks the symbol up. */
+#define FOT_ENC_SHORT 0
+#define FOT_ENC_NO_PEDS 1
+#define FOT_ENC_FAR 2
+#define FOT_ENC_KEPT 3
+#define FOT_ENC_CRUISE_NONE 0
+#define FOT_ENC_CRUISE_MEDIAN 1
+#define FOT_ENC_CRUISE_QUANTILE 2
+#define FOT_ENC_CRUISE_FREEWALK 3
+#define FOT_ENC_SCENE_DEVICE 1
+#define FOT_ENC_MEASURE_REAL 2
+typedef struct fot_encounter_params {
+    double  min_sep_threshold;              /* reference default 8.0 */
+    double  dt;
+    double  accel_threshold, max_distance;  /* the onset's, for `real`: 0.3, 5.0 */
+    double  cruise_q;                       /* 0.85 (cruise_upper_quantile), 0.5 (cruise_freewalk) */
+    double  free_distance, goal_distance;   /* 8.0, 50.0 */
+    int32_t min_len;                        /* 5 */
+    int32_t cruise_mode;                    /* FOT_ENC_CRUISE_* */
+    int32_t flags;                          /* FOT_ENC_SCENE_DEVICE | FOT_ENC_MEASURE_REAL */
+    int32_t _pad;
+} fot_encounter_params;
+typedef struct fot_encounter_span {
+    double  min_separation;                 /* NaN for FOT_ENC_SHORT, +inf for FOT_ENC_NO_PEDS */
+    fot_fidelity_enc real;                  /* KEPT with FOT_ENC_MEASURE_REAL; else closest NaN, closest_step -1, zeros */
+    int64_t row_base;                       /* KEPT: its first row; else -1 */
+    int32_t status, vehicle;                /* FOT_ENC_*; k */
+    int32_t frame0, frame1;                 /* the frames frame0 .. frame1 - 1 */
+    int32_t n_ped;                          /* 0 for SHORT */
+    int32_t min_step, min_col;              /* first (step, compacted column) holding min_separation; -1 without one */
+    int32_t _pad;
+} fot_encounter_span;
+int fot_encounters_extract(fot_handle *h, const fot_encounter_params *p, int32_t T, int32_t A, int32_t K,
+                           const double *ped_xy,   /* [T][A][2] */
+                           const double *ped_vel,  /* [T][A][2], or NULL: the forward-difference fallback */
+                           const double *ego_xy,   /* [K][T][2] */
+                           const double *ego_psi,  /* [K][T] */
+                           const double *ego_vel,  /* [K][T] */
+                           int32_t max_spans, int64_t max_rows,
+                           int32_t *n_spans, int64_t *n_rows,
+                           fot_encounter_span *spans,  /* [max_spans] */
+                           int32_t *cols,          /* [max_rows] */
+                           double *cruise,         /* [max_rows]; NULL allowed with FOT_ENC_CRUISE_NONE */
+                           double *goals,          /* [max_rows][2]; likewise */
+                           double *onset_dist,     /* NULL or [max_rows]: NaN = no onset (FOT_ENC_MEASURE_REAL) */
+                           int32_t *onset_step,    /* NULL or [max_rows]: -1 = no onset */
+                           double *sep_series,     /* NULL or [sum of the kept spans' lengths] */
+                           int64_t max_steps);     /* capacity of sep_series (ignored when it is NULL) */
+
 /* Host utility (no GPU): the first kmax samples of the 15 path arrays of records[index[i]], i < n, as one dense block
  * out[15][n][kmax] in fot_result array order (t .. c) -- what a history keeps of a step's records. */
 int fot_gather_paths(const fot_result *records, int32_t n, const int32_t *index, int32_t kmax, double *out);

@@ -199,6 +199,21 @@ class FidelityEnc(C.Structure):                                   # fot_fidelity
                 ("closest_step", C.c_int32)]
 
 
+class EncounterParams(C.Structure):                               # fot_encounter_params
+    _fields_ = [(n, C.c_double) for n in ("min_sep_threshold", "dt", "accel_threshold", "max_distance", "cruise_q", "free_distance",
+                                          "goal_distance")] + [(n, C.c_int32) for n in ("min_len", "cruise_mode", "flags", "_pad")]
+
+
+class EncounterSpan(C.Structure):                                 # fot_encounter_span
+    _fields_ = [("min_separation", C.c_double), ("real", FidelityEnc), ("row_base", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("status", "vehicle", "frame0", "frame1", "n_ped", "min_step", "min_col", "_pad")]
+
+
+ENC_SHORT, ENC_NO_PEDS, ENC_FAR, ENC_KEPT = range(4)              # FOT_ENC_* statuses
+ENC_CRUISE = {None: 0, "none": 0, "median": 1, "quantile": 2, "freewalk": 3}   # FOT_ENC_CRUISE_*
+ENC_SCENE_DEVICE, ENC_MEASURE_REAL = 1, 2
+
+
 class Batch(C.Structure):
     _fields_ = [("n_inst", C.c_int32), ("obstacle_dtype", C.c_int32),
                 ("ego", C.POINTER(Ego)), ("target_speed", C.POINTER(C.c_double)),
@@ -228,7 +243,8 @@ SYMBOLS = ["fot_version", "fot_abi_info", "fot_create", "fot_destroy", "fot_live
            "fot_loop_begin_sweep", "fot_loop_set_samples_shared", "fot_loop_set_sampler_shared", "fot_debug_loop_sampler_shape",
            "fot_sgan_max_models", "fot_sgan_load_model", "fot_sgan_unload_model", "fot_sgan_sample_model",
            "fot_loop_set_sampler_models", "fot_debug_loop_sampler_shapes", "fot_openloop_eval",
-           "fot_footprint_recheck", "fot_loop_footprint_enable", "fot_loop_footprint_obs", "fot_fidelity_eval"]
+           "fot_footprint_recheck", "fot_loop_footprint_enable", "fot_loop_footprint_obs", "fot_fidelity_eval",
+           "fot_encounters_extract"]
 LOOP_PLAN_DISTRIBUTION, LOOP_PLAN_REPRESENTATIVE = 0, 1      # FOT_LOOP_PLAN_* (fot_loop_plan_sample)
 PROFILE_KERNELS = 3                      # FOT_PROFILE_KERNELS (include/fot.h)
 ABI_VERSION = 8                          # FOT_ABI_VERSION
@@ -501,7 +517,9 @@ def lib():
                        ("fot_footprint_recheck", [vp, C.POINTER(FootprintGeom), C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]),
                        ("fot_loop_footprint_enable", [vp, C.POINTER(FootprintGeom)]),
                        ("fot_loop_footprint_obs", [vp, C.c_int32, vp]),
-                       ("fot_fidelity_eval", [vp, C.POINTER(FidelityParams), C.c_int32] + [vp] * 11)):
+                       ("fot_fidelity_eval", [vp, C.POINTER(FidelityParams), C.c_int32] + [vp] * 11),
+                       ("fot_encounters_extract", [vp, C.POINTER(EncounterParams), C.c_int32, C.c_int32, C.c_int32] + [vp] * 5 +
+                                                  [C.c_int32, C.c_int64] + [vp] * 9 + [C.c_int64])):
         if hasattr(L, name):
             getattr(L, name).argtypes = args
     L.fot_gather_paths.argtypes = [vp, C.c_int32, vp, C.c_int32, vp]

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -220,6 +220,91 @@ def fidelity_eval(lib, handle, enc: PackedEncounters, accel_threshold: float = 0
                                              addr(enc.ped), addr(enc.vel), addr(enc.truth), addr(series), addr(dist),
                                              addr(step), addr(out)))
     return out[:n], series[:steps], dist[:peds], step[:peds]
+
+
+ENCOUNTER_SPAN_DT = np.dtype(_abi.EncounterSpan)
+
+
+def encounter_span_counts(ego_xy: np.ndarray, ego_psi: np.ndarray, ego_vel: np.ndarray, min_len: int) -> Tuple[int, int]:
+    """(candidate spans, those of at least ``min_len`` frames) of aligned ego channels [K, T(, 2)]: the capacities an
+    ``encounters_extract`` call needs, counted as the library finds its spans (maximal runs with all four channels finite)."""
+    here = np.isfinite(ego_xy).all(axis=2) & np.isfinite(ego_psi) & np.isfinite(ego_vel)             # [K, T]
+    edge = np.diff(np.pad(here.astype(np.int8), ((0, 0), (1, 1))), axis=1)
+    starts, stops = np.nonzero(edge == 1), np.nonzero(edge == -1)           # row-major: a row's starts and stops pair up
+    return int(starts[0].size), int(np.count_nonzero(stops[1] - starts[1] >= int(min_len)))
+
+
+def encounters_extract(lib, handle, ped_xy, ped_vel, ego_xy, ego_psi, ego_vel, dt: float, min_sep_threshold: float = 8.0,
+                       min_len: int = 5, accel_threshold: float = 0.3, max_distance: float = 5.0, cruise: Optional[str] = None,
+                       cruise_q: float = 0.85, free_distance: float = 8.0, goal_distance: float = 50.0, measure_real: bool = True,
+                       want_series: bool = False, max_spans: Optional[int] = None, max_rows: Optional[int] = None) -> dict:
+    """``fot_encounters_extract`` on one clip: ``ped_xy`` [T, A, 2] (``ped_vel`` alike, or None: the forward-difference
+    fallback), host arrays or device tensors of float64, and the aligned ego channels ``ego_xy`` [K, T, 2], ``ego_psi``
+    and ``ego_vel`` [K, T].  Returns a dictionary: ``spans`` (``ENCOUNTER_SPAN_DT`` per candidate span), and per row (the
+    kept spans' pedestrians back to back) ``cols``, ``cruise`` and ``goals`` (None without a cruise mode), ``onset_dist``
+    and ``onset_step`` (None without ``measure_real``); ``series`` with ``want_series``.  The capacities default to what
+    the ego channels' runs can need at most."""
+    if cruise not in _abi.ENC_CRUISE:
+        raise ValueError(f"cruise is one of {sorted(k for k in _abi.ENC_CRUISE if k)} or None, got {cruise!r}")
+    ego_xy = np.ascontiguousarray(ego_xy, dtype=np.float64)
+    ego_psi, ego_vel = (np.ascontiguousarray(a, dtype=np.float64) for a in (ego_psi, ego_vel))
+    if ego_xy.ndim != 3 or ego_xy.shape[2] != 2 or ego_psi.shape != ego_xy.shape[:2] or ego_vel.shape != ego_xy.shape[:2]:
+        raise ValueError(f"ego_xy [K, T, 2], ego_psi and ego_vel [K, T], got {ego_xy.shape}, {ego_psi.shape}, {ego_vel.shape}")
+    K, T = ego_xy.shape[:2]
+    on_device = hasattr(ped_xy, "data_ptr")
+    keep = []
+
+    def scene(a, name):
+        if a is None:
+            return None
+        if on_device != hasattr(a, "data_ptr"):
+            raise ValueError("ped_xy and ped_vel lie both on the host or both on the device")
+        if on_device:
+            if str(a.dtype).rsplit(".", 1)[-1] != "float64" or not a.is_contiguous():
+                raise ValueError(f"a device {name} is a contiguous float64 tensor")
+        else:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.ndim != 3 or a.shape[0] != T or a.shape[2] != 2:
+            raise ValueError(f"{name} is [T={T}, A, 2], got {tuple(a.shape)}")
+        keep.append(a)
+        return a
+
+    xy, vel = scene(ped_xy, "ped_xy"), scene(ped_vel, "ped_vel")
+    if vel is not None and tuple(vel.shape) != tuple(xy.shape):
+        raise ValueError(f"ped_vel shape {tuple(vel.shape)} != ped_xy shape {tuple(xy.shape)}")
+    A = int(xy.shape[1])
+    ptr = (lambda a: None if a is None else a.data_ptr()) if on_device else (lambda a: None if a is None else a.ctypes.data)
+    mode = _abi.ENC_CRUISE[cruise]
+    flags = (_abi.ENC_SCENE_DEVICE if on_device else 0) | (_abi.ENC_MEASURE_REAL if measure_real else 0)
+    p = _abi.EncounterParams(float(min_sep_threshold), float(dt), float(accel_threshold), float(max_distance), float(cruise_q),
+                             float(free_distance), float(goal_distance), int(min_len), mode, flags, 0)
+    if max_spans is None or max_rows is None:
+        n_all, n_long = encounter_span_counts(ego_xy, ego_psi, ego_vel, min_len) if K and T else (0, 0)
+        max_spans = n_all if max_spans is None else max_spans
+        max_rows = n_long * A if max_rows is None else max_rows
+    max_spans, max_rows = int(max_spans), int(max_rows)
+    series_on = bool(want_series and measure_real)
+    max_steps = max_spans * T if series_on else 0
+    spans = np.zeros(max(max_spans, 1), dtype=ENCOUNTER_SPAN_DT)
+    cols = np.full(max(max_rows, 1), -1, dtype=np.int32)
+    speed = np.full(max(max_rows, 1), np.nan) if mode else None
+    goals = np.full((max(max_rows, 1), 2), np.nan) if mode else None
+    dist = np.full(max(max_rows, 1), np.nan) if measure_real else None
+    step = np.full(max(max_rows, 1), -1, dtype=np.int32) if measure_real else None
+    series = np.zeros(max(max_steps, 1)) if series_on else None
+    n_spans, n_rows = C.c_int32(0), C.c_int64(0)
+    addr = lambda a: None if a is None else a.ctypes.data
+    _abi.check(handle, lib.fot_encounters_extract(handle, C.byref(p), T, A, K, ptr(xy), ptr(vel), addr(ego_xy), addr(ego_psi),
+                                                  addr(ego_vel), max_spans, max_rows, C.addressof(n_spans), C.addressof(n_rows),
+                                                  addr(spans), addr(cols), addr(speed), addr(goals), addr(dist), addr(step),
+                                                  addr(series), max_steps))
+    ns, nr = n_spans.value, n_rows.value
+    spans = spans[:ns]
+    kept = spans[spans["status"] == _abi.ENC_KEPT]
+    steps = int(np.sum(kept["frame1"] - kept["frame0"]))
+    cut = lambda a: None if a is None else a[:nr]
+    return dict(spans=spans, cols=cols[:nr], cruise=cut(speed), goals=cut(goals), onset_dist=cut(dist), onset_step=cut(step),
+                series=None if series is None else series[:steps])
 
 
 def request_from_instance(inst, **kw) -> PlanRequest:

@@ -83,6 +83,7 @@ void destroy_handle(fot_handle *h)
     h->ol.release();
     h->fp.release();
     h->fid.release();
+    h->enc.release();
     h->loop.release();
     for (hipEvent_t e : h->prof_pool) (void)hipEventDestroy(e);
     if (h->fork) (void)hipEventDestroy(h->fork);

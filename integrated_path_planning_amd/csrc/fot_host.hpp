@@ -410,6 +410,12 @@ struct fot_handle {
         DevBuf dIn, dOut;
         void release() { dIn.release(); dOut.release(); }
     } fid;
+    // fot_encounters_extract: a host clip's copy, the ego rows and the tables, the columns' and spans' work arrays, the
+    // packed encounters with what launch_fidelity writes, the speeds and the per-row outputs, in HBM (grow-only)
+    struct Encounters {
+        DevBuf dScene, dIn, dWork, dTab, dPacked, dSpeeds, dOut;
+        void release() { for (DevBuf *b : { &dScene, &dIn, &dWork, &dTab, &dPacked, &dSpeeds, &dOut }) b->release(); }
+    } enc;
     LoopState loop;
     // fot_sgan_*: the loaded models (descriptor, device image of the weights), each with the work arrays of its own sample
     // calls -- what model m computes never depends on what else is loaded or was sampled in between

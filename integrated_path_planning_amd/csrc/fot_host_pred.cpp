@@ -1,5 +1,6 @@
 // fot_host_pred.cpp -- the entry points of libfot.so that predict or score without keeping loop state: the resampler and
-// the constant-velocity predictor, the safety metrics, the prediction scores and the Social-GAN sampler.
+// the constant-velocity predictor, the safety metrics, the prediction scores, the Social-GAN sampler, the open-loop
+// evaluation, the footprint re-verification, the fidelity statistics and the extraction of encounters.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -861,6 +862,182 @@ int fot_fidelity_eval(fot_handle *h, const fot_fidelity_params *p, int32_t n_enc
     { int r = order_end(h, st); if (r != FOT_OK) return r; }
     HIP_TRY(h, hipStreamSynchronize(st));             // (off64 and the caller's arrays are read until here)
     return FOT_OK;
+}
+
+// ---- encounters cut out of a recorded clip (include/fot.h; the shared arithmetic and checks: fot_encounter.hpp) ---------------
+int fot_encounters_extract(fot_handle *h, const fot_encounter_params *p, int32_t T, int32_t A, int32_t K, const double *ped_xy,
+                           const double *ped_vel, const double *ego_xy, const double *ego_psi, const double *ego_vel,
+                           int32_t max_spans, int64_t max_rows, int32_t *n_spans, int64_t *n_rows, fot_encounter_span *spans,
+                           int32_t *cols, double *cruise, double *goals, double *onset_dist, int32_t *onset_step,
+                           double *sep_series, int64_t max_steps)
+{
+    static_assert(sizeof(EncParams) == sizeof(fot_encounter_params) && sizeof(EncSpan) == sizeof(fot_encounter_span) &&
+                  offsetof(EncParams, min_len) == offsetof(fot_encounter_params, min_len) &&
+                  offsetof(EncSpan, real) == offsetof(fot_encounter_span, real) &&
+                  offsetof(EncSpan, row_base) == offsetof(fot_encounter_span, row_base) &&
+                  offsetof(EncSpan, min_col) == offsetof(fot_encounter_span, min_col),
+                  "EncParams / EncSpan are fot_encounter_params / fot_encounter_span");
+    if (!h) return FOT_ERR_INVALID;
+    const std::string who = "fot_encounters_extract: ";
+    if (!p || !n_spans || !n_rows || !spans || !cols) return fail(h, FOT_ERR_INVALID, who + "p / n_spans / n_rows / spans / cols is NULL");
+    EncParams P;
+    std::memcpy(&P, p, sizeof P);
+    const char *why = "";
+    if (enc_check_params(P, &why)) return fail(h, FOT_ERR_INVALID, who + why);
+    if (T < 0 || A < 0 || K < 0 || max_spans < 0 || max_rows < 0 || (sep_series && max_steps < 0))
+        return fail(h, FOT_ERR_INVALID, who + "a negative size or capacity");
+    const bool cruise_on = P.cruise_mode != ENC_CRUISE_NONE, freewalk = P.cruise_mode == ENC_CRUISE_FREEWALK;
+    const bool measure = (P.flags & ENC_MEASURE_REAL) != 0, on_device = (P.flags & ENC_SCENE_DEVICE) != 0;
+    if (cruise_on && (!cruise || !goals)) return fail(h, FOT_ERR_INVALID, who + "cruise / goals is NULL with a cruise mode");
+    const bool any = T > 0 && A > 0 && K > 0;
+    if (any && (!ped_xy || !ego_xy || !ego_psi || !ego_vel)) return fail(h, FOT_ERR_INVALID, who + "ped_xy / ego_xy / ego_psi / ego_vel is NULL");
+    if (on_device && (((uintptr_t)ped_xy | (uintptr_t)ped_vel) & 15)) return fail(h, FOT_ERR_INVALID, who + "a device scene is not aligned to 16 bytes");
+    if (!any) { *n_spans = 0; *n_rows = 0; return FOT_OK; }
+    // the candidate spans, and which of them go on to the device
+    std::vector<EncSpan> rec;
+    std::vector<int32_t> go_tab, go_rec;                           // [n_go][4]: vehicle, frame0, frame1, 0 | the span's record
+    for (int32_t k = 0; k < K; ++k)
+        enc_find_spans(T, ego_xy + 2 * (size_t)k * T, ego_psi + (size_t)k * T, ego_vel + (size_t)k * T, [&](int32_t f0, int32_t f1) {
+            EncSpan s{};
+            s.min_separation = NAN; s.real.closest = NAN; s.real.closest_step = -1; s.row_base = -1;
+            s.status = ENC_SHORT; s.vehicle = k; s.frame0 = f0; s.frame1 = f1; s.min_step = -1; s.min_col = -1;
+            if (f1 - f0 >= P.min_len) { go_tab.insert(go_tab.end(), { k, f0, f1, 0 }); go_rec.push_back((int32_t)rec.size()); }
+            rec.push_back(s);
+        });
+    if (rec.size() > (size_t)max_spans) return fail(h, FOT_ERR_UNSUPPORTED, who + "needs max_spans >= " + std::to_string(rec.size()));
+    const size_t n_go = go_rec.size();
+    auto deliver = [&](int64_t rows) {
+        if (!rec.empty()) std::memcpy(spans, rec.data(), sizeof(EncSpan) * rec.size());
+        *n_spans = (int32_t)rec.size(); *n_rows = rows;
+        return FOT_OK;
+    };
+    if (n_go == 0) return deliver(0);
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    fot_handle::Encounters &E = h->enc;
+    // the clip in HBM: a host scene is copied once (positions | velocities); the ego rows | the spans' table
+    const size_t scene_b = align256(sizeof(double) * 2 * (size_t)T * A), ego_b = align256(sizeof(double) * 2 * (size_t)K * T);
+    const size_t go_b = align256(sizeof(int32_t) * go_tab.size());
+    const size_t col_b = align256(sizeof(EncCol) * n_go * A), cols_b = align256(sizeof(int32_t) * n_go * A), so_b = sizeof(EncSpanOut) * n_go;
+    if (!on_device) HIP_TRY(h, E.dScene.ensure(scene_b * (ped_vel ? 2 : 1)));
+    HIP_TRY(h, E.dIn.ensure(ego_b + go_b));
+    HIP_TRY(h, E.dWork.ensure(col_b + cols_b + so_b));
+    { int r = order_begin(h, st); if (r != FOT_OK) return r; }
+    EncScene S;
+    S.T = T; S.A = A; S.dt = P.dt; S.ped_xy = ped_xy; S.ped_vel = ped_vel;
+    if (!on_device) {
+        char *d = (char *)E.dScene.p;
+        HIP_TRY(h, hipMemcpyAsync(d, ped_xy, sizeof(double) * 2 * (size_t)T * A, hipMemcpyHostToDevice, st));
+        S.ped_xy = (const double *)d;
+        if (ped_vel) {
+            HIP_TRY(h, hipMemcpyAsync(d + scene_b, ped_vel, sizeof(double) * 2 * (size_t)T * A, hipMemcpyHostToDevice, st));
+            S.ped_vel = (const double *)(d + scene_b);
+        }
+    }
+    char *b_ego = (char *)E.dIn.p, *b_go = b_ego + ego_b;
+    HIP_TRY(h, hipMemcpyAsync(b_ego, ego_xy, sizeof(double) * 2 * (size_t)K * T, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(b_go, go_tab.data(), sizeof(int32_t) * go_tab.size(), hipMemcpyHostToDevice, st));
+    S.ego_xy = (const double *)b_ego;
+    char *w_col = (char *)E.dWork.p, *w_cols = w_col + col_b, *w_out = w_cols + cols_b;
+    EncSpansArgs SA;
+    SA.s = S; SA.n_go = (int32_t)n_go; SA.span = (const int32_t *)b_go;
+    SA.col = (EncCol *)w_col; SA.cols = (int32_t *)w_cols; SA.out = (EncSpanOut *)w_out;
+    LAUNCH_TRY(h, launch_enc_spans(SA, st));
+    std::vector<EncSpanOut> so(n_go);
+    HIP_TRY(h, hipMemcpyAsync(so.data(), w_out, so_b, hipMemcpyDeviceToHost, st));
+    { int r = order_end(h, st); if (r != FOT_OK) return r; }
+    HIP_TRY(h, hipStreamSynchronize(st));             // the first wait: the populations size everything below
+    // the kept spans in fot_fidelity_eval's tables
+    std::vector<int32_t> kept_tab, step_off(1, 0), n_ped;
+    std::vector<int64_t> off64(1, 0), ped_base(1, 0);
+    std::vector<int32_t> kept_rec;
+    for (size_t g = 0; g < n_go; ++g) {
+        EncSpan &s = rec[(size_t)go_rec[g]];
+        const EncMin &m = so[g].m;
+        s.n_ped = so[g].n_ped;
+        s.min_separation = s.n_ped == 0 ? (double)INFINITY : m.nan ? (double)NAN : m.v;
+        if (s.n_ped > 0 && !m.nan) { s.min_step = m.step; s.min_col = m.col; }
+        s.status = enc_status(s.n_ped, s.min_separation, P.min_sep_threshold);
+        if (s.status != ENC_KEPT) continue;
+        const int64_t L = s.frame1 - s.frame0;
+        if ((int64_t)step_off.back() + L > 0x7fffffffLL) return fail(h, FOT_ERR_UNSUPPORTED, who + "more kept steps than int32 offsets hold");
+        s.row_base = ped_base.back();
+        kept_tab.insert(kept_tab.end(), { s.vehicle, s.frame0, (int32_t)g, 0 });
+        kept_rec.push_back(go_rec[g]);
+        step_off.push_back(step_off.back() + (int32_t)L);
+        n_ped.push_back(s.n_ped);
+        off64.push_back(off64.back() + L * s.n_ped);
+        ped_base.push_back(ped_base.back() + s.n_ped);
+    }
+    const size_t ne = kept_rec.size(), steps = (size_t)step_off.back(), cells = (size_t)off64.back(), rows = (size_t)ped_base.back();
+    if ((int64_t)rows > max_rows) return fail(h, FOT_ERR_UNSUPPORTED, who + "needs max_rows >= " + std::to_string(rows));
+    if (sep_series && measure && (int64_t)steps > max_steps) return fail(h, FOT_ERR_UNSUPPORTED, who + "needs max_steps >= " + std::to_string(steps));
+    if (ne == 0) return deliver(0);
+    // the tables as one block: kept | step_off | n_ped | dt | row_off, ped_base | the kept spans' ego rows
+    off64.insert(off64.end(), ped_base.begin(), ped_base.end());
+    std::vector<double> dts(ne, P.dt), ego_rows(2 * steps);
+    for (size_t e = 0; e < ne; ++e) {
+        const EncSpan &s = rec[(size_t)kept_rec[e]];
+        std::memcpy(ego_rows.data() + 2 * (size_t)step_off[e], ego_xy + 2 * ((size_t)s.vehicle * T + s.frame0),
+                    sizeof(double) * 2 * (size_t)(s.frame1 - s.frame0));
+    }
+    const size_t kt_b = align256(sizeof(int32_t) * kept_tab.size()), soff_b = align256(sizeof(int32_t) * (ne + 1));
+    const size_t nped_b = align256(sizeof(int32_t) * ne), dt_b = align256(sizeof(double) * ne), o64_b = align256(sizeof(int64_t) * off64.size());
+    const size_t egor_b = align256(sizeof(double) * 2 * steps);
+    // what the kernels write: col_out | cruise | goals | series | onset_dist | onset_step | records
+    const size_t ci_b = align256(sizeof(int32_t) * rows), rd_b = align256(sizeof(double) * rows), ser_b = align256(sizeof(double) * steps);
+    const size_t frec_b = sizeof(FidEnc) * ne;
+    HIP_TRY(h, E.dTab.ensure(kt_b + soff_b + nped_b + dt_b + o64_b + egor_b));
+    if (measure) HIP_TRY(h, E.dPacked.ensure(sizeof(double) * 2 * cells));
+    if (cruise_on) HIP_TRY(h, E.dSpeeds.ensure(align256(sizeof(double) * cells) * (freewalk ? 2 : 1)));
+    HIP_TRY(h, E.dOut.ensure(ci_b + 3 * rd_b + ser_b + rd_b + ci_b + frec_b));
+    char *t_kept = (char *)E.dTab.p, *t_soff = t_kept + kt_b, *t_nped = t_soff + soff_b, *t_dt = t_nped + nped_b, *t_o64 = t_dt + dt_b;
+    char *t_ego = t_o64 + o64_b;
+    HIP_TRY(h, hipMemcpyAsync(t_kept, kept_tab.data(), sizeof(int32_t) * kept_tab.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(t_soff, step_off.data(), sizeof(int32_t) * (ne + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(t_nped, n_ped.data(), sizeof(int32_t) * ne, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(t_dt, dts.data(), sizeof(double) * ne, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(t_o64, off64.data(), sizeof(int64_t) * off64.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(t_ego, ego_rows.data(), sizeof(double) * 2 * steps, hipMemcpyHostToDevice, st));
+    char *o_col = (char *)E.dOut.p, *o_cruise = o_col + ci_b, *o_goals = o_cruise + rd_b, *o_ser = o_goals + 2 * rd_b;
+    char *o_dist = o_ser + ser_b, *o_step = o_dist + rd_b, *o_rec = o_step + ci_b;
+    EncRowsArgs RA;
+    RA.s = S; RA.p = P; RA.n_kept = (int32_t)ne; RA.n_rows = (int64_t)rows; RA.n_cells = (int64_t)cells;
+    RA.kept = (const int32_t *)t_kept; RA.step_off = (const int32_t *)t_soff; RA.n_ped = (const int32_t *)t_nped;
+    RA.row_off = (const int64_t *)t_o64; RA.ped_base = RA.row_off + ne + 1;
+    RA.cols = (const int32_t *)w_cols;
+    RA.packed_xy = measure ? E.dPacked.as<double>() : nullptr;
+    RA.speeds = cruise_on ? E.dSpeeds.as<double>() : nullptr;
+    RA.free_speeds = freewalk ? (double *)((char *)E.dSpeeds.p + align256(sizeof(double) * cells)) : nullptr;
+    RA.col_out = (int32_t *)o_col; RA.cruise = (double *)o_cruise; RA.goals = (double *)o_goals;
+    LAUNCH_TRY(h, launch_enc_rows(RA, st));
+    std::vector<FidEnc> frec(measure ? ne : 0);
+    if (measure) {
+        FidelityArgs F;
+        F.n_enc = (int32_t)ne; F.n_steps = (int64_t)steps; F.n_peds = (int64_t)rows;
+        F.step_off = RA.step_off; F.n_ped = RA.n_ped; F.dt = (const double *)t_dt; F.row_off = RA.row_off; F.ped_base = RA.ped_base;
+        F.ego = (const double *)t_ego; F.ped_xy = RA.packed_xy; F.ped_vel = nullptr; F.truth = nullptr;
+        F.p.accel_threshold = P.accel_threshold; F.p.max_distance = P.max_distance; F.p.interaction_distance = NAN;
+        F.series = (double *)o_ser; F.onset_dist = (double *)o_dist; F.ped_sum = nullptr; F.onset_step = (int32_t *)o_step;
+        F.ped_keep = nullptr; F.out = (FidEnc *)o_rec;
+        LAUNCH_TRY(h, launch_fidelity(F, st));
+        HIP_TRY(h, hipMemcpyAsync(frec.data(), o_rec, frec_b, hipMemcpyDeviceToHost, st));
+    }
+    // everything below is written only now that the call can no longer be refused
+    HIP_TRY(h, hipMemcpyAsync(cols, o_col, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, st));
+    if (cruise_on) {
+        HIP_TRY(h, hipMemcpyAsync(cruise, o_cruise, sizeof(double) * rows, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipMemcpyAsync(goals, o_goals, sizeof(double) * 2 * rows, hipMemcpyDeviceToHost, st));
+    }
+    if (measure) {
+        if (sep_series) HIP_TRY(h, hipMemcpyAsync(sep_series, o_ser, sizeof(double) * steps, hipMemcpyDeviceToHost, st));
+        if (onset_dist) HIP_TRY(h, hipMemcpyAsync(onset_dist, o_dist, sizeof(double) * rows, hipMemcpyDeviceToHost, st));
+        if (onset_step) HIP_TRY(h, hipMemcpyAsync(onset_step, o_step, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, st));
+    }
+    { int r = order_end(h, st); if (r != FOT_OK) return r; }
+    HIP_TRY(h, hipStreamSynchronize(st));             // the second wait (the tables and ego_rows are read until here)
+    for (size_t e = 0; e < frec.size(); ++e) rec[(size_t)kept_rec[e]].real = frec[e];
+    return deliver((int64_t)rows);
 }
 
 }  // extern "C"

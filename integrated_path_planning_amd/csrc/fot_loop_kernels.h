@@ -13,6 +13,7 @@
 #include "fot_openloop.hpp"
 #include "fot_footprint_obs.hpp"
 #include "fot_fidelity.hpp"
+#include "fot_encounter.hpp"
 
 namespace fot {
 
@@ -220,5 +221,43 @@ struct FidelityArgs {
     FidEnc *out;                                 // [n_enc]
 };
 int launch_fidelity(const FidelityArgs &a, hipStream_t st);
+
+// ---- fot_encounters_extract (fot_encounter.hpp).  The clip as it lies in HBM: ped_xy / ped_vel [T][A][2] (ped_vel NULL: the
+// forward-difference fallback over the whole grid), ego_xy [K][T][2].
+struct EncScene {
+    const double *ped_xy, *ped_vel, *ego_xy;
+    int32_t T, A;
+    double dt;
+};
+struct EncSpanOut { EncMin m; int32_t n_ped, pad_; };            // a span's closest approach and population
+// the spans that are long enough, n_go of them: span [n_go][4] = vehicle, frame0, frame1, 0.  Block = 64 columns x
+// ENC_STEP_WAVES shares of the steps -> col [n_go][A]; then a wave per span compacts the present columns, ascending, into
+// cols [n_go][A] and joins their minima -> out [n_go]
+struct EncSpansArgs {
+    EncScene s;
+    int32_t n_go;
+    const int32_t *span;
+    EncCol *col;
+    int32_t *cols;
+    EncSpanOut *out;
+};
+int launch_enc_spans(const EncSpansArgs &a, hipStream_t st);
+// the kept spans, n_kept of them, in fot_fidelity_eval's tables (step_off, n_ped, row_off, ped_base as in FidelityArgs):
+// kept [n_kept][4] = vehicle, frame0, index among the n_go spans, 0.  Lane = cell (step, pedestrian) of the packed layout:
+// packed_xy [cells][2] (or NULL) and, per pedestrian over its steps, speeds / free_speeds [cells] (or NULL; free_speeds
+// NaN where the step is not free-walking); then a wave per kept pedestrian: col_out, cruise, goals [rows]
+struct EncRowsArgs {
+    EncScene s;
+    EncParams p;
+    int32_t n_kept;
+    int64_t n_rows, n_cells;
+    const int32_t *kept, *step_off, *n_ped;
+    const int64_t *row_off, *ped_base;
+    const int32_t *cols;
+    double *packed_xy, *speeds, *free_speeds;
+    int32_t *col_out;
+    double *cruise, *goals;
+};
+int launch_enc_rows(const EncRowsArgs &a, hipStream_t st);
 
 }  // namespace fot

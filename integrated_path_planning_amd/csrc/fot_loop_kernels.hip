@@ -10,6 +10,9 @@
 //   k_fidelity_peds / _series / _fold
 //                                fot_fidelity_eval: avoidance onset and roll-out error per pedestrian, the separation per
 //                                step, the record of an encounter
+//   k_enc_columns / _compact / _gather / _rows
+//                                fot_encounters_extract: presence and closest approach per column of a span, the kept
+//                                columns and the span's minimum, the packed encounters and speeds, cruise speed and goal
 //   k_loop_* / k_static_gather / k_predict_cv_frame
 //                                the resident loop (fot_loop_run): frame, sample gather, prediction, digests, history,
 //                                prediction-error summaries, predictor scores, representative sample
@@ -987,6 +990,163 @@ k_fidelity_fold(FidelityArgs A)
 }
 
 // ---------------------------------------------------------------------------
+// fot_encounters_extract (fot_encounter.hpp): populations and closest approaches of candidate spans of a resident clip,
+// the kept encounters gathered into fot_fidelity_eval's packed layout, cruise speeds and far goals
+// ---------------------------------------------------------------------------
+// coordinate c of column a at frame f of the clip, and of its velocity (recorded, or the whole-grid fallback)
+__device__ __forceinline__ double enc_pos_at(const EncScene &s, int64_t f, int a, int c) { return s.ped_xy[2 * (f * s.A + a) + c]; }
+__device__ __forceinline__ double enc_vel_at(const EncScene &s, int64_t f, int a, int c)
+{
+    if (s.ped_vel) return s.ped_vel[2 * (f * s.A + a) + c];
+    return enc_fallback_vel([&](int32_t t, int cc) { return enc_pos_at(s, t, a, cc); }, (int32_t)f, s.T, c, s.dt);
+}
+
+// Block = 64 columns of one span (the spans' tiles back to back); lane = column, so that a step's row is read in whole lines; wave w walks the
+// steps w, w + ENC_STEP_WAVES, ...  and wave 0 joins the four shares (the join is exact in any order).
+__global__ void __launch_bounds__(ENC_COL_TILE * ENC_STEP_WAVES)
+k_enc_columns(EncSpansArgs A)
+{
+    __shared__ EncCol s_c[ENC_STEP_WAVES][ENC_COL_TILE];
+    const int tiles = (A.s.A + ENC_COL_TILE - 1) / ENC_COL_TILE;
+    const int lane = threadIdx.x & (ENC_COL_TILE - 1), w = threadIdx.x / ENC_COL_TILE, g = blockIdx.x / tiles;
+    const int a = (blockIdx.x - g * tiles) * ENC_COL_TILE + lane;
+    const int32_t *sp = A.span + 4 * g;
+    const int k = sp[0], f0 = sp[1], L = sp[2] - sp[1];
+    EncCol c; c.m = fid_min_zero(); c.absent = 0;
+    if (a < A.s.A) {
+        const double *__restrict__ eg = A.s.ego_xy + 2 * ((int64_t)k * A.s.T + f0);
+        c = enc_column([&](int32_t t, int cc) { return enc_pos_at(A.s, (int64_t)f0 + t, a, cc); },
+                       [&](int32_t t, int cc) { return enc_vel_at(A.s, (int64_t)f0 + t, a, cc); },
+                       [&](int32_t t, int cc) { return eg[2 * t + cc]; }, w, ENC_STEP_WAVES, L);
+    }
+    s_c[w][lane] = c;
+    __syncthreads();
+    if (w != 0 || a >= A.s.A) return;
+#pragma unroll
+    for (int o = 1; o < ENC_STEP_WAVES; ++o) c = enc_column_join(c, s_c[o][lane]);
+    A.col[(int64_t)g * A.s.A + a] = c;
+}
+
+// One wave per span: the present columns compacted in ascending order (ballot and prefix count, 64 columns a turn), their
+// minima joined with the compacted column as the last key.
+__global__ void __launch_bounds__(WAVE)
+k_enc_compact(EncSpansArgs A)
+{
+    const int g = blockIdx.x, lane = threadIdx.x, n_col = A.s.A;
+    const EncCol *__restrict__ col = A.col + (int64_t)g * n_col;
+    int32_t *__restrict__ cols = A.cols + (int64_t)g * n_col;
+    int count = 0;
+    EncMin m = enc_min_zero();
+    for (int base = 0; base < n_col; base += WAVE) {
+        const int a = base + lane;
+        const bool present = a < n_col && !col[a].absent;
+        const unsigned long long mask = __ballot(present);
+        if (present) {
+            const int idx = count + __popcll(mask & ((1ull << lane) - 1ull));
+            cols[idx] = a;
+            m = enc_min_join(m, enc_min_of_column(col[a].m, idx));
+        }
+        count += __popcll(mask);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        EncMin o;
+        o.v = __shfl_xor(m.v, off, WAVE); o.step = __shfl_xor(m.step, off, WAVE); o.col = __shfl_xor(m.col, off, WAVE);
+        o.nan = __shfl_xor(m.nan, off, WAVE);
+        m = enc_min_join(m, o);
+    }
+    if (lane != 0) return;
+    EncSpanOut r; r.m = m; r.n_ped = count; r.pad_ = 0;
+    A.out[g] = r;
+}
+
+// Lane = cell of the packed layout, over all kept encounters' cells back to back: the position gathered from the clip
+// through the span's column list; with a cruise mode the step's speed, filed per pedestrian over its steps.
+__global__ void __launch_bounds__(FID_THREADS)
+k_enc_gather(EncRowsArgs A)
+{
+    const int64_t r = (int64_t)blockIdx.x * FID_THREADS + threadIdx.x;
+    if (r >= A.n_cells) return;
+    const int e = fid_owner(A.row_off, A.n_kept, r);
+    const int64_t local = r - A.row_off[e];
+    const int N = A.n_ped[e], L = A.step_off[e + 1] - A.step_off[e];
+    const int t = (int)(local / N), n = (int)(local - (int64_t)t * N);
+    const int32_t *kp = A.kept + 4 * e;
+    const int a = A.cols[(int64_t)kp[2] * A.s.A + n];
+    const int64_t f = (int64_t)kp[1] + t;
+    const double px = enc_pos_at(A.s, f, a, 0), py = enc_pos_at(A.s, f, a, 1);
+    if (A.packed_xy) { A.packed_xy[2 * r] = px; A.packed_xy[2 * r + 1] = py; }
+    if (!A.speeds) return;
+    const double s = fid_dist(enc_vel_at(A.s, f, a, 0), enc_vel_at(A.s, f, a, 1));
+    const int64_t at = A.row_off[e] + (int64_t)n * L + t;
+    A.speeds[at] = s;
+    if (!A.free_speeds) return;
+    const double *__restrict__ eg = A.s.ego_xy + 2 * ((int64_t)kp[0] * A.s.T + f);
+    const bool is_free = fid_dist(px - eg[0], py - eg[1]) > A.p.free_distance && s - s == 0.0;
+    A.free_speeds[at] = is_free ? s : (double)NAN;
+}
+
+// the order statistics pick.lo and pick.hi of the non-NaN entries of v[0 .. L): lanes stride over the entries, each ranks
+// its own by counting (ties by index: every rank is taken once), the two hits go through LDS
+__device__ __forceinline__ void enc_select(const double *__restrict__ v, int L, const EncPick &pick, double *s_sel, double *s_lo, double *s_hi)
+{
+    for (int i = threadIdx.x; i < L; i += WAVE) {
+        const double x = v[i];
+        if (x != x) continue;
+        const int32_t r = enc_rank([&](int32_t j) { return v[j]; }, i, L);
+        if (r == pick.lo) s_sel[0] = x;
+        if (r == pick.hi) s_sel[1] = x;
+    }
+    __syncthreads();
+    *s_lo = s_sel[0]; *s_hi = s_sel[1];
+    __syncthreads();
+}
+
+// One wave per kept pedestrian: its column, its cruise speed by the launch's mode, its far goal.
+__global__ void __launch_bounds__(WAVE)
+k_enc_rows(EncRowsArgs A)
+{
+    __shared__ double s_sel[2];
+    const int64_t g = blockIdx.x;
+    const int e = fid_owner(A.ped_base, A.n_kept, g);
+    const int n = (int)(g - A.ped_base[e]), L = A.step_off[e + 1] - A.step_off[e];
+    const int32_t *kp = A.kept + 4 * e;
+    const int a = A.cols[(int64_t)kp[2] * A.s.A + n];
+    if (threadIdx.x == 0) A.col_out[g] = a;
+    if (A.p.cruise_mode == ENC_CRUISE_NONE) return;
+    const double *__restrict__ sp = A.speeds + A.row_off[e] + (int64_t)n * L;
+    double lo, hi, value = 0.0;
+    bool median = A.p.cruise_mode == ENC_CRUISE_MEDIAN;
+    if (A.p.cruise_mode == ENC_CRUISE_FREEWALK) {
+        const double *__restrict__ fs = A.free_speeds + A.row_off[e] + (int64_t)n * L;
+        int n_free = 0;
+        for (int i = threadIdx.x; i < L; i += WAVE) n_free += fs[i] == fs[i] ? 1 : 0;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) n_free += __shfl_xor(n_free, off, WAVE);
+        if (n_free > 0) {
+            const EncPick pick = enc_pick_quantile(n_free, A.p.cruise_q);
+            enc_select(fs, L, pick, s_sel, &lo, &hi);
+            value = enc_quantile_value(lo, hi, pick.g);
+        } else median = true;                                      // never free-walking: the all-step median
+    } else if (!median) {
+        const EncPick pick = enc_pick_quantile(L, A.p.cruise_q);
+        enc_select(sp, L, pick, s_sel, &lo, &hi);
+        value = enc_quantile_value(lo, hi, pick.g);
+    }
+    if (median) {
+        enc_select(sp, L, enc_pick_median(L), s_sel, &lo, &hi);
+        value = enc_median_value(L, lo, hi);
+    }
+    if (threadIdx.x != 0) return;
+    A.cruise[g] = enc_floor(value);
+    const int64_t f0 = kp[1], f1 = f0 + L - 1;
+    double gx, gy;
+    enc_goal(enc_pos_at(A.s, f0, a, 0), enc_pos_at(A.s, f0, a, 1), enc_pos_at(A.s, f1, a, 0), enc_pos_at(A.s, f1, a, 1),
+             enc_vel_at(A.s, f0, a, 0), enc_vel_at(A.s, f0, a, 1), A.p.goal_distance, &gx, &gy);
+    A.goals[2 * g] = gx; A.goals[2 * g + 1] = gy;
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
 
@@ -1244,6 +1404,38 @@ int launch_fidelity(const FidelityArgs &a, hipStream_t st)
     k_fidelity_series<<<(unsigned)step_blocks, FID_THREADS, 0, st>>>(a);
     FOT_LAUNCH_CHECK();
     k_fidelity_fold<<<a.n_enc, WAVE, 0, st>>>(a);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_enc_spans(const EncSpansArgs &a, hipStream_t st)
+{
+    if (a.n_go <= 0) return 0;
+    if (!a.s.ped_xy || !a.s.ego_xy || !a.span || !a.col || !a.cols || !a.out || a.s.T < 1 || a.s.A < 1) return (int)hipErrorInvalidValue;
+    const int64_t blocks = (int64_t)a.n_go * ((a.s.A + ENC_COL_TILE - 1) / ENC_COL_TILE);
+    if (blocks > 0x7fffffffLL) return (int)hipErrorInvalidConfiguration;
+    k_enc_columns<<<(unsigned)blocks, ENC_COL_TILE * ENC_STEP_WAVES, 0, st>>>(a);
+    FOT_LAUNCH_CHECK();
+    k_enc_compact<<<a.n_go, WAVE, 0, st>>>(a);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_enc_rows(const EncRowsArgs &a, hipStream_t st)
+{
+    if (a.n_kept <= 0) return 0;
+    if (!a.s.ped_xy || !a.s.ego_xy || !a.kept || !a.step_off || !a.n_ped || !a.row_off || !a.ped_base || !a.cols || !a.col_out ||
+        a.n_rows < 1 || a.n_cells < 1) return (int)hipErrorInvalidValue;
+    const bool cruise = a.p.cruise_mode != ENC_CRUISE_NONE;
+    if (cruise && (!a.speeds || !a.cruise || !a.goals || (a.p.cruise_mode == ENC_CRUISE_FREEWALK && !a.free_speeds)))
+        return (int)hipErrorInvalidValue;
+    const int64_t cell_blocks = (a.n_cells + FID_THREADS - 1) / FID_THREADS;
+    if (cell_blocks > 0x7fffffffLL || a.n_rows > 0x7fffffffLL) return (int)hipErrorInvalidConfiguration;
+    if (a.packed_xy || a.speeds) {
+        k_enc_gather<<<(unsigned)cell_blocks, FID_THREADS, 0, st>>>(a);
+        FOT_LAUNCH_CHECK();
+    }
+    k_enc_rows<<<(unsigned)a.n_rows, WAVE, 0, st>>>(a);
     FOT_LAUNCH_CHECK();
     return 0;
 }

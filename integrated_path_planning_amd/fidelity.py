@@ -7,15 +7,22 @@ The reference's ``min_separation_series``, ``avoidance_onset_distance``, ``compa
 ``BatchPlanner``) first.  The Social-Force roll-out is not part of this package: the caller brings the simulated positions
 from wherever they were rolled out.  Everything measured on [T, N, 2] arrays -- distances, gradients, the onset search, the
 error sums -- runs on the device in ``fot_fidelity_eval``, any number of ragged encounters per call; the pooling, the
-medians and the KS test stay on the host, in the reference's order."""
+medians and the KS test stay on the host, in the reference's order.
+
+The encounters themselves come out of recorded clips (``extract_encounters``: the reference's
+src/datasets/vci_encounter.py and the roll-out boundary conditions of calibration_harness.py): the vehicles are aligned
+onto the pedestrian grid on the host, and one ``fot_encounters_extract`` call per clip finds the spans, populations and
+closest approaches, measures the recorded side and forms cruise speeds and far goals where the clip lies."""
 from __future__ import annotations
 
 import warnings
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .batch import PackedEncounters
+from . import _abi
+from .batch import FIDELITY_ENC_DT, PackedEncounters
 
 REPORT_KEYS = ("n_encounters", "rollout_ade", "mean_closest_sim", "mean_closest_real", "ks_closest", "p_closest",
                "n_onset_sim", "n_onset_real", "ks_onset", "p_onset", "closest_sim_raw", "closest_real_raw", "onset_sim_raw",
@@ -186,13 +193,29 @@ class _Side:
         return float(np.mean(self.closest)) if self.closest else float("nan")
 
 
+REPORT_ONSET = dict(accel_threshold=0.3, max_distance=5.0)        # the onset parameters a report measures both sides with
+
+
+def _carried_real(encounters: Sequence):
+    """the recorded side as ``extract_encounters`` measured it, in ``fidelity_batch``'s form -- or None unless every
+    encounter carries a ``real`` taken with the report's own onset parameters"""
+    carried = [_get(e, "real") for e in encounters]
+    if not carried or any(r is None or {k: r.get(k) for k in REPORT_ONSET} != REPORT_ONSET for r in carried):
+        return None
+    records = np.array([r["record"] for r in carried], dtype=FIDELITY_ENC_DT)
+    return dict(records=records, onset_dist=[r["onset_dist"] for r in carried], onset_step=[r["onset_step"] for r in carried])
+
+
 def fidelity_report(engine, encounters: Sequence, rollouts: Sequence) -> Dict[str, object]:
     """The reference's ``fidelity_report(encounters, sigma, v0)`` on roll-outs the caller simulated: its dictionary, key for
     key (``REPORT_KEYS``).  Two library calls -- the simulated side with the recording as truth, and the recorded side --
     both measured from positions (no recorded velocity on either side, so that the two accelerations are differentiated
-    alike)."""
+    alike).  Encounters that ``extract_encounters`` cut with ``measure_real`` carry their recorded side already (the same
+    kernels on the same positions): then one call, the simulated side."""
     encounters = list(encounters)
-    sides = {"sim": _Side(fidelity_batch(engine, encounters, rollouts)), "real": _Side(fidelity_batch(engine, encounters))}
+    real = _carried_real(encounters)
+    sides = {"sim": _Side(fidelity_batch(engine, encounters, rollouts)),
+             "real": _Side(fidelity_batch(engine, encounters) if real is None else real)}
     err_sum, err_count = _pooled_error(sides["sim"].records)
     values = {"n_encounters": len(encounters), "rollout_ade": err_sum / err_count if err_count else float("nan")}
     values["ks_closest"], values["p_closest"] = compare_distributions_ks(sides["sim"].closest, sides["real"].closest)
@@ -233,3 +256,144 @@ def calculate_min_separation(engine, history_or_npz) -> Tuple[np.ndarray, float]
     ped_xy = np.concatenate(rows).reshape(len(rows), population, 2) if rows else np.zeros((0, 0, 2))
     series = min_separation_series(engine, ego_xy, ped_xy)
     return series, (float(series.min()) if len(series) else float("inf"))
+
+
+# ---- encounters cut out of recorded clips (the reference's src/datasets/vci_encounter.py and the boundary conditions of
+# src/simulation/calibration_harness.py): alignment on the host, everything on [T, A, 2] arrays in fot_encounters_extract ------
+@dataclass
+class RecordedClip:
+    """One recorded clip as arrays: the pedestrian grid ``times`` [T] with ``ped_xy`` [T, A, 2] (NaN where a pedestrian is
+    absent), ``ped_ids`` [A] and optionally the recorded ``ped_vel`` [T, A, 2]; the vehicles on their own sampling
+    ``veh_times`` [Tv] with ``veh_xy`` [Tv, K, 2], ``veh_ids`` [K] and optionally ``veh_psi`` and ``veh_vel`` [Tv, K]."""
+    name: str
+    times: np.ndarray
+    ped_xy: np.ndarray
+    ped_ids: np.ndarray
+    veh_times: np.ndarray
+    veh_xy: np.ndarray
+    veh_ids: np.ndarray
+    ped_vel: Optional[np.ndarray] = None
+    veh_psi: Optional[np.ndarray] = None
+    veh_vel: Optional[np.ndarray] = None
+
+
+@dataclass
+class Encounter:
+    """A fixed-population interaction window, the reference's fields first.  ``far_goals`` [N, 2] and ``cruise`` [N] are
+    the roll-out's boundary conditions where a cruise mode was asked for; ``real`` is the recorded side of a fidelity
+    report (``record``, ``onset_dist``, ``onset_step`` and the onset parameters they were measured with)."""
+    clip: str
+    times: np.ndarray
+    ego_xy: np.ndarray
+    ego_psi: np.ndarray
+    ego_vel: np.ndarray
+    ped_xy: np.ndarray
+    ped_vel: np.ndarray
+    ped_ids: np.ndarray
+    dt: float
+    min_separation: float
+    goals: Optional[np.ndarray] = None
+    far_goals: Optional[np.ndarray] = None
+    cruise: Optional[np.ndarray] = None
+    real: Optional[dict] = None
+
+
+def _onto_grid(src_t: np.ndarray, src_v: np.ndarray, grid: np.ndarray, angular: bool = False) -> np.ndarray:
+    """One channel of one vehicle interpolated onto the grid; NaN outside its support (1e-9 s of slack) and everywhere
+    with fewer than two usable samples.  A sample is usable when its time and THIS channel's value are finite, so a gap
+    inside the track is bridged.  Headings are unwrapped, interpolated and wrapped again."""
+    usable = np.isfinite(src_t) & np.isfinite(src_v)
+    out = np.full(grid.shape, np.nan)
+    if np.count_nonzero(usable) < 2:
+        return out
+    t, v = src_t[usable], src_v[usable]
+    order = np.argsort(t)                                          # (the reference's call, kind and all: NumPy decides ties)
+    t, v = t[order], v[order]
+    if angular:
+        v = np.unwrap(v)
+    inside = (grid >= t[0] - 1e-9) & (grid <= t[-1] + 1e-9)
+    values = np.interp(grid[inside], t, v)
+    out[inside] = (values + np.pi) % (2 * np.pi) - np.pi if angular else values
+    return out
+
+
+def align_vehicles(clip: RecordedClip) -> Tuple[np.ndarray, np.ndarray, np.ndarray, float]:
+    """Every vehicle of ``clip`` on the pedestrian grid: ``ego_xy`` [K, T, 2], ``ego_psi`` [K, T], ``ego_vel`` [K, T] (NaN
+    outside a vehicle's support) and ``dt``.  Without recorded headings or speeds they come from the gradient of the
+    interpolated path, which leaves NaN at both ends of a vehicle's support."""
+    grid = np.asarray(clip.times, dtype=float)
+    dt = float(grid[1] - grid[0]) if len(grid) >= 2 else 0.4
+    veh_t = np.asarray(clip.veh_times, dtype=float)
+    veh_xy = np.asarray(clip.veh_xy, dtype=float)
+    K, T = veh_xy.shape[1], len(grid)
+    ego_xy, ego_psi, ego_vel = np.full((K, T, 2), np.nan), np.full((K, T), np.nan), np.full((K, T), np.nan)
+    for k in range(K):
+        ego_xy[k] = np.stack([_onto_grid(veh_t, veh_xy[:, k, c], grid) for c in (0, 1)], axis=1)
+        slope = None
+        if clip.veh_psi is None or clip.veh_vel is None:
+            slope = np.gradient(ego_xy[k], dt, axis=0) if T >= 2 else np.full((T, 2), np.nan)
+        ego_psi[k] = (np.arctan2(slope[:, 1], slope[:, 0]) if clip.veh_psi is None
+                      else _onto_grid(veh_t, np.asarray(clip.veh_psi, dtype=float)[:, k], grid, angular=True))
+        ego_vel[k] = (np.linalg.norm(slope, axis=1) if clip.veh_vel is None
+                      else _onto_grid(veh_t, np.asarray(clip.veh_vel, dtype=float)[:, k], grid))
+    return ego_xy, ego_psi, ego_vel, dt
+
+
+def fallback_velocities(ped_xy: np.ndarray, dt: float) -> np.ndarray:
+    """[T, A, 2] forward differences over the whole grid, the last frame repeating the one before; NaN with one frame"""
+    vel = np.full_like(ped_xy, np.nan)
+    if ped_xy.shape[0] >= 2:
+        vel[:-1] = (ped_xy[1:] - ped_xy[:-1]) / dt
+        vel[-1] = vel[-2]
+    return vel
+
+
+def _columns(array: np.ndarray, frames: slice, cols: np.ndarray) -> np.ndarray:
+    """array[frames][:, cols]: a view where the columns are one run, else a copy"""
+    if len(cols) and cols[-1] - cols[0] + 1 == len(cols):
+        return array[frames, int(cols[0]):int(cols[-1]) + 1]
+    return array[frames][:, cols]
+
+
+CRUISE_Q = {"quantile": 0.85, "freewalk": 0.5}                    # cruise_upper_quantile's and cruise_freewalk's defaults
+
+
+def extract_encounters(engine, clips: Sequence[RecordedClip], min_sep_threshold: float = 8.0, min_len: int = 5,
+                       multivehicle: bool = True, cruise: Optional[str] = None, measure_real: bool = True,
+                       cruise_q: Optional[float] = None, free_distance: float = 8.0, goal_distance: float = 50.0) -> List[Encounter]:
+    """The reference's ``encounters_from_clips_multivehicle`` (``multivehicle=False``: ``encounters_from_clips``, which
+    skips clips of several vehicles) with ``engine`` first: one ``fot_encounters_extract`` call per clip, its pedestrian
+    scene sent once whatever the number of vehicles.  ``cruise`` in (None, 'median', 'quantile', 'freewalk') also fills
+    ``Encounter.cruise`` and ``far_goals``; ``measure_real`` fills ``Encounter.real``, which ``fidelity_report`` uses
+    instead of a second library call.  A clip of several vehicles names its encounters ``{name}#v{vehicle id}``."""
+    q = CRUISE_Q.get(cruise, 0.85) if cruise_q is None else float(cruise_q)
+    out: List[Encounter] = []
+    for clip in clips:
+        K = 0 if clip.veh_xy is None else np.shape(clip.veh_xy)[1]
+        if clip.ped_xy is None or K == 0 or (K > 1 and not multivehicle):
+            continue
+        ego_xy, ego_psi, ego_vel, dt = align_vehicles(clip)
+        ped_xy = np.ascontiguousarray(clip.ped_xy, dtype=np.float64)
+        given_vel = None if clip.ped_vel is None else np.ascontiguousarray(clip.ped_vel, dtype=np.float64)
+        got = engine.encounters_extract(ped_xy, given_vel, ego_xy, ego_psi, ego_vel, dt, min_sep_threshold=min_sep_threshold,
+                                        min_len=min_len, cruise=cruise, cruise_q=q, free_distance=free_distance,
+                                        goal_distance=goal_distance, measure_real=measure_real, **REPORT_ONSET)
+        ped_vel = given_vel
+        times, ids = np.asarray(clip.times), np.asarray(clip.ped_ids)
+        for s in got["spans"]:
+            if s["status"] != _abi.ENC_KEPT:
+                continue
+            if ped_vel is None:
+                ped_vel = fallback_velocities(ped_xy, dt)
+            k, frames = int(s["vehicle"]), slice(int(s["frame0"]), int(s["frame1"]))
+            rows = slice(int(s["row_base"]), int(s["row_base"]) + int(s["n_ped"]))
+            cols = got["cols"][rows]
+            real = None
+            if measure_real:
+                real = dict(record=s["real"].copy(), onset_dist=got["onset_dist"][rows], onset_step=got["onset_step"][rows], **REPORT_ONSET)
+            out.append(Encounter(
+                clip=f"{clip.name}#v{int(clip.veh_ids[k])}" if K > 1 else clip.name, times=times[frames], ego_xy=ego_xy[k, frames],
+                ego_psi=ego_psi[k, frames], ego_vel=ego_vel[k, frames], ped_xy=_columns(ped_xy, frames, cols),
+                ped_vel=_columns(ped_vel, frames, cols), ped_ids=ids[cols], dt=dt, min_separation=float(s["min_separation"]),
+                far_goals=None if cruise is None else got["goals"][rows], cruise=None if cruise is None else got["cruise"][rows], real=real))
+    return out

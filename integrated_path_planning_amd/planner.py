@@ -925,6 +925,14 @@ class BatchPlanner:
             raise RuntimeError("this libfot.so has no fot_fidelity_eval: rebuild it")
         return _batch.fidelity_eval(self._lib, self._h, encounters, **thresholds)
 
+    def encounters_extract(self, ped_xy, ped_vel, ego_xy, ego_psi, ego_vel, dt: float, **options):
+        """``fot_encounters_extract`` (``batch.encounters_extract``): the candidate spans of one clip's vehicles, their
+        populations and closest approaches, the kept encounters' recorded-side statistics and roll-out boundary
+        conditions, in one call.  ``ped_xy`` / ``ped_vel`` may be device tensors [T, A, 2] of float64."""
+        if not hasattr(self._lib, "fot_encounters_extract"):
+            raise RuntimeError("this libfot.so has no fot_encounters_extract: rebuild it")
+        return _batch.encounters_extract(self._lib, self._h, ped_xy, ped_vel, ego_xy, ego_psi, ego_vel, dt, **options)
+
     def _loop_frame(self, frame: dict):
         """fot_loop_frame from the dictionary ``loop_plan`` / ``loop_step`` take (+ the arrays it points into)."""
         f, keep = _abi.LoopFrame(), []
