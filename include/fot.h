@@ -289,6 +289,16 @@ int fot_debug_set_tile_cut(fot_handle *h, int32_t cut);
  * or a negative FOT_ERR_*. */
 int fot_debug_set_eval_form(fot_handle *h, int32_t form);
 
+/* Test hook.  The lean evaluation kernels have a flat form for reference paths that are exactly straight: one coordinate
+ * of the path's spline has all first-, second- and third-derivative coefficients exactly zero and the other is finite
+ * and strictly monotonic.  Every row of such a path has curvature and curvature rate +-0, and the flat form leaves out
+ * the arithmetic that exists for them; same decisions, byte-identical records.  The library decides per path where the
+ * path is set, and a lean-eligible launch takes the flat form when every path its instances use is flat.  on = 0 keeps
+ * the handle's later plan calls on the other kernels, 1 restores the choice by eligibility (the default), -1 changes
+ * nothing.  Returns 1 when a launch of the handle's most recent plan call took a flat kernel, 0 when none did, or a
+ * negative FOT_ERR_*.  fot_debug_set_eval_form reports a flat launch as lean. */
+int fot_debug_set_flat(fot_handle *h, int32_t on);
+
 /* FrenetPlanner._build_time_cache (frenet_planner.py:586-617) as the library holds it for a horizon of `time`
  * seconds: the sample count n_t = round(time / dt) + 1 and the closed-form inverses of the quartic / quintic
  * boundary-value matrices (row-major 2x2 and 3x3) that every lattice polynomial is solved with.  Host only. */

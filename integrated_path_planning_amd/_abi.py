@@ -231,7 +231,7 @@ LIB_PATH = os.path.join(_HERE, "libfot.so")
 SYMBOLS = ["fot_version", "fot_abi_info", "fot_create", "fot_destroy", "fot_live_handles", "fot_last_error", "fot_set_path_waypoints",
            "fot_set_path_coeffs", "fot_get_path_coeffs", "fot_spline_eval", "fot_plan_batch",
            "fot_plan_batch_device", "fot_synchronize", "fot_frenet_state_batch", "fot_debug_candidates",
-           "fot_debug_candidate_path", "fot_debug_margins", "fot_debug_set_eval_segments", "fot_debug_set_tile_cut", "fot_debug_set_eval_form", "fot_debug_time_info", "fot_check_collision_paths", "fot_check_paths", "fot_resample_n_dense", "fot_resample_predictions",
+           "fot_debug_candidate_path", "fot_debug_margins", "fot_debug_set_eval_segments", "fot_debug_set_tile_cut", "fot_debug_set_eval_form", "fot_debug_set_flat", "fot_debug_time_info", "fot_check_collision_paths", "fot_check_paths", "fot_resample_n_dense", "fot_resample_predictions",
            "fot_predict_cv", "fot_safety_metrics_batch", "fot_loop_set_static", "fot_loop_plan", "fot_loop_observe", "fot_loop_observe_begin", "fot_loop_observe_end", "fot_loop_begin", "fot_loop_step", "fot_loop_set_replay", "fot_loop_run", "fot_loop_summary_enable", "fot_loop_summaries", "fot_prediction_scores", "fot_loop_prediction_scores", "fot_gather_paths", "fot_wire_n_total", "fot_wire_record_bytes",
            "fot_pack_records_device", "fot_pack_records_host", "fot_unpack_records", "fot_profile_enable", "fot_profile_read", "fot_profile_kernel_name",
            "fot_add_scenario", "fot_set_scenario_path_waypoints", "fot_set_scenario_path_coeffs",
@@ -455,7 +455,8 @@ def lib():
                        ("fot_get_scenario_path_coeffs", [vp, C.c_int32, ip] + [dp] * 9),
                        ("fot_loop_begin_scenarios", [vp, C.c_int32, C.c_int32, vp, vp, vp, vp]),
                        ("fot_loop_set_scenario_static", [vp, C.c_int32, C.c_int32, vp]),
-                       ("fot_debug_set_eval_form", [vp, C.c_int32])):
+                       ("fot_debug_set_eval_form", [vp, C.c_int32]),
+                       ("fot_debug_set_flat", [vp, C.c_int32])):
         if hasattr(L, name):
             getattr(L, name).argtypes = args
     L.fot_synchronize.argtypes = [vp]

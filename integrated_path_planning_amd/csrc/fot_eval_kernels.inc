@@ -1,6 +1,10 @@
-// The three evaluation kernels, included twice by fot_kernels.hip: as k_evaluate / k_evaluate_split / k_evaluate_group
-// (FOT_EVAL_LEAN false: the general form) and as k_evaluate_lean / k_evaluate_split_lean / k_evaluate_group_lean
-// (FOT_EVAL_LEAN true: FusedSink<true>).  Two inclusions rather than a template body behind two wrappers: each kernel
+// The three evaluation kernels, included three times by fot_kernels.hip: as k_evaluate / k_evaluate_split /
+// k_evaluate_group (FOT_EVAL_LEAN false: the general form), as k_evaluate_lean / k_evaluate_split_lean /
+// k_evaluate_group_lean (FOT_EVAL_LEAN true: FusedSink<true>) and as k_evaluate_split_lean_flat /
+// k_evaluate_group_lean_flat (FOT_EVAL_FLAT true on top: the walk of exactly straight reference paths,
+// frenet_to_cart<., true>).  The per-wave kernel has no flat form: it came out with one lane-spilled scalar register
+// more than k_evaluate_lean (10 against 9), and a flat-eligible launch of that shape runs k_evaluate_lean.
+// Inclusions rather than a template body behind wrappers: each kernel
 // then reads its argument struct in place, exactly as the single form did (through a wrapper the struct is copied and
 // every field loaded at entry -- three more lane-spilled SGPRs in the grouped kernel).
 
@@ -9,6 +13,7 @@
 // so their lists sit in its L2 (speed only) -- and an instance's LAST tile comes first (late horizons and the brake
 // ladder run longest), so the long tiles start early and the short ones fill the end of the launch.  The waves of a
 // workgroup share nothing but the staged spline: each has its own slice of LDS.
+#if !FOT_EVAL_FLAT
 __global__ void __launch_bounds__(EVAL_WG) __attribute__((amdgpu_waves_per_eu(3, 3)))
 FOT_EVAL_KERNEL(k_evaluate)(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, const InstState *__restrict__ state,
            const int32_t *__restrict__ tile_cand0, const int32_t *__restrict__ tile_n,
@@ -61,10 +66,11 @@ FOT_EVAL_KERNEL(k_evaluate)(const DevParams *__restrict__ Pp, const InstDesc *__
     if (inst < 0) return;
     const int n_tiles = desc[inst].n_tiles;
     TilePart tp = tile_part_empty();
-    evaluate_tile<TILE_WAVE, FOT_EVAL_LEAN>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, my_rows, inst,
+    evaluate_tile<TILE_WAVE, FOT_EVAL_LEAN, FOT_EVAL_FLAT>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, my_rows, inst,
                          n_tiles - 1 - pos, lane, x, tp);
     tile_done(inst, n_tiles - 1 - pos, lane, tp);
 }
+#endif
 
 // The same for a handful of egos (fewer tiles than the GPU has SIMDs): a tile alone on its SIMD is a chain of
 // ~50 dependent time steps of ~1.1 us, so the workgroup's waves (blockDim.x / 64 <= SEG_MAX) take a time segment
@@ -94,7 +100,7 @@ FOT_EVAL_KERNEL(k_evaluate_split)(const DevParams *__restrict__ Pp, const InstDe
     const SplineView sp_lds = stage_spline(sp_hbm, a.lds_knots, s_part + (SEG_MAX - 1) * SEG_DOUBLES);
     const int tile = n_tiles - 1 - pos;
     TilePart tp = tile_part_empty();
-    evaluate_tile<TILE_SPLIT, FOT_EVAL_LEAN>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, s_lon, inst, tile, lane, x,
+    evaluate_tile<TILE_SPLIT, FOT_EVAL_LEAN, FOT_EVAL_FLAT>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, s_lon, inst, tile, lane, x,
                               tp, seg, n_seg, s_part);
     if (seg == 0) tile_done(inst, tile, lane, tp);               // (the wave that merged the segments and holds the results)
 }
@@ -150,7 +156,7 @@ FOT_EVAL_KERNEL(k_evaluate_group)(const DevParams *__restrict__ Pp, const InstDe
     const int tile0 = __builtin_amdgcn_readfirstlane(s_head->grp_tile0);
     TilePart tp = tile_part_empty();
     // (GROUP_HEAD_EMPTY -- no Frenet state, or the brake ladder of a standing ego: the tiles count as done, nothing found)
-    evaluate_group_tile<FOT_EVAL_LEAN>(Pp, desc, wave_rng, ent32, a, sp_lds, s_lon, inst, tile0 + wv, wv, lane, x, tp,
+    evaluate_group_tile<FOT_EVAL_LEAN, FOT_EVAL_FLAT>(Pp, desc, wave_rng, ent32, a, sp_lds, s_lon, inst, tile0 + wv, wv, lane, x, tp,
                                        present == GROUP_HEAD_FULL);
     tile_done(inst, tile0 + wv, lane, tp);
 }

@@ -118,6 +118,7 @@ int upload_spline(fot_handle *h, int scen = 0)
     HIP_TRY(h, hipMemcpy(S.dSpline.p, flat.data(), flat.size() * sizeof(double), hipMemcpyHostToDevice));
     { int r = upload_spline_table(h); if (r != FOT_OK) return r; }
     S.has_path = true;
+    S.flat_path = spline_is_flat(S.spline);                      // (every fot_set_path_* route ends here)
     h->last_valid = false;
     return FOT_OK;
 }
@@ -274,6 +275,13 @@ int enqueue_lane(fot_handle *h, Workspace &w, const fot_batch &b, const int32_t 
     for (const Scenario &S : h->sc) if (S.P.n_total > WAVE || S.P.has_footprint) tt.lean = 0;
     for (int i = 0; i < L.n_inst && tt.lean; ++i) if (L.desc[(size_t)i].max_viol != 0) tt.lean = 0;
     h->last_eval_forms |= tt.lean ? 2 : 1;
+    // Their flat forms: every path the launch's instances use is exactly straight.  Decided from the paths' coefficients
+    // (Scenario::flat_path) -- the lateral states need no test: frenet_to_cart<., true> keeps the one multiply-add
+    // that poisons a sample whose d is not finite, as the general form's 1 - kr d does.
+    tt.flat = tt.lean && h->flat_mode != 0 ? 1 : 0;
+    if (L.scens.empty()) { if (!h->sc[0].flat_path) tt.flat = 0; }
+    for (int s : L.scens) if (!h->sc[(size_t)s].flat_path) tt.flat = 0;
+    h->last_flat |= evaluate_flat(tt) ? 1 : 0;
     GroupHeadOut gh;                                             // the grouped kernels' headers: k_frenet_state builds them
     if (evaluate_in_groups(tt)) {
         gh.n_pos = L.max_tiles / GROUP_TILES;
@@ -511,6 +519,7 @@ int fot::host::enqueue_plan(fot_handle *h, const fot_batch &b, const int32_t *sc
     { int r = check_scenarios(h, b, scen); if (r != FOT_OK) return r; }
     h->last_valid = false;
     h->last_eval_forms = 0;
+    h->last_flat = 0;
     if (b.n_inst == 0) { h->lanes_used = 0; h->last_valid = true; return FOT_OK; }
     if (!d_out) return fail(h, FOT_ERR_INVALID, "out is NULL");
     if (!b.ego || !b.target_speed) return fail(h, FOT_ERR_INVALID, "ego / target_speed missing");
@@ -1145,6 +1154,15 @@ int fot_debug_set_eval_form(fot_handle *h, int32_t form)
         return fail(h, FOT_ERR_INVALID, "fot_debug_set_eval_form: 0 (by eligibility), 1 (general form), -1 (query only)");
     if (form >= 0) h->eval_form = form;
     return h->last_eval_forms;
+}
+
+int fot_debug_set_flat(fot_handle *h, int32_t on)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (on < -1 || on > 1)
+        return fail(h, FOT_ERR_INVALID, "fot_debug_set_flat: 0 (never), 1 (by eligibility), -1 (query only)");
+    if (on >= 0) h->flat_mode = on;
+    return h->last_flat;
 }
 
 int fot_debug_time_info(const fot_handle *h, double time, int32_t *n_t, double *quartic_inv4, double *quintic_inv9)

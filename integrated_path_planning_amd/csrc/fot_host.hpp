@@ -342,6 +342,7 @@ struct Scenario {
     HostSpline spline;
     DevBuf dSpline;                          // its 9 coefficient arrays (element `id` of the SplineView table)
     bool has_path = false;
+    bool flat_path = false;                  // the path is exactly straight (spline_is_flat): decided where it is set
     TileShapes shapes;                       // its run of the handle's tile table ...
     int32_t shape_base = 0;                  // ... starting at this entry
 };
@@ -370,6 +371,8 @@ struct fot_handle {
     int tile_cut = 0;                    // fot_debug_set_tile_cut (TILE_CUT_*)
     int eval_form = 0;                   // fot_debug_set_eval_form: 0 = by eligibility, 1 = the general form always
     int last_eval_forms = 0;             // forms the launches of the most recent plan call took: 1 general | 2 lean
+    int flat_mode = 1;                   // fot_debug_set_flat: 1 = flat kernels where a launch is eligible, 0 = never
+    int last_flat = 0;                   // 1: a launch of the most recent plan call took a flat kernel
     std::vector<Scenario> sc;                // scenarios; sc[0]: fot_create's params + fot_set_path_*
     std::vector<ScenarioRef> refs;           // what build_batch_layout needs of each (rebuilt with the tile table)
     DevBuf dP;                               // DevParams[sc.size()]

@@ -77,10 +77,14 @@ struct TileTable {
     int eval_segments = 0;              // time segments per tile in k_evaluate: 0 = by batch size, 1..4 forced (tests)
     int lean = 0;                       // the launch may take the lean evaluation kernels: at most 64 samples per candidate,
                                         // the single centre circle, no chance budget on any instance (enqueue_lane)
+    int flat = 0;                       // ... and their flat forms: lean, and every path of the launch is exactly straight
+                                        // (Scenario::flat_path)
     GroupHead *heads = nullptr;         // [n_inst][max_tiles / GROUP_TILES] group headers, where evaluate_in_groups()
 };
 // the evaluation of this batch goes to the grouped kernels (launch_evaluate): k_frenet_state then builds their headers
 bool evaluate_in_groups(const TileTable &tiles);
+// ... and takes a flat kernel (launch_evaluate): tiles.flat and a launch shape that has one (split, grouped)
+bool evaluate_flat(const TileTable &tiles);
 
 // The group-header table k_frenet_state fills for the grouped evaluation kernels (heads == nullptr: none wanted)
 struct GroupHeadOut {

@@ -805,7 +805,9 @@ constexpr int SEG_MAX = 4;
 constexpr int SEG_F64 = 4, SEG_I32 = 4;  // d_last, v_last, max_step2, hit_mask | flags, first_nan, k_last, hit
 constexpr int SEG_DOUBLES = (SEG_F64 + SEG_I32 / 2) * WAVE;
 
-struct StagedTab {
+// FLAT (the walk of an exactly straight path, frenet_to_cart<., true>): the step reads neither kr nor dkr of its row.
+template <bool FLAT = false>
+struct StagedTabT {
     static constexpr bool LOCAL = true;  // rx, ry relative to the ego position (evaluate_tile builds them so)
     int lds_row0;                        // index of this lane's profile row 0 in s_lon
     int k_max;                           // last row of the run (grid: n_t - 1; brake ladder: the hold row n_eval)
@@ -821,11 +823,17 @@ struct StagedTab {
         const int kk = k < k_max ? k : k_max;
         const double *r = s_lon + lds_row0 + kk * ROW_FIELDS;
         L.s = 0.0; L.sd = r[0]; L.sdd = r[1]; L.rx = r[2]; L.ry = r[3];
-        L.cos_r = r[4]; L.sin_r = r[5]; L.kr = r[6]; L.dkr = r[7]; L.inv_sd = r[8];
         // the row is in registers from here on: what follows (the sink's scalar warm-up loads) must not sit
         // between these reads and the wait for them
-        asm volatile("" : "+v"(L.sd), "+v"(L.sdd), "+v"(L.rx), "+v"(L.ry), "+v"(L.cos_r), "+v"(L.sin_r),
-                          "+v"(L.kr), "+v"(L.dkr), "+v"(L.inv_sd));
+        if constexpr (FLAT) {
+            L.cos_r = r[4]; L.sin_r = r[5]; L.kr = 0.0; L.dkr = 0.0; L.inv_sd = r[8];   // (kr, dkr: never read)
+            asm volatile("" : "+v"(L.sd), "+v"(L.sdd), "+v"(L.rx), "+v"(L.ry), "+v"(L.cos_r), "+v"(L.sin_r),
+                              "+v"(L.inv_sd));
+        } else {
+            L.cos_r = r[4]; L.sin_r = r[5]; L.kr = r[6]; L.dkr = r[7]; L.inv_sd = r[8];
+            asm volatile("" : "+v"(L.sd), "+v"(L.sdd), "+v"(L.rx), "+v"(L.ry), "+v"(L.cos_r), "+v"(L.sin_r),
+                              "+v"(L.kr), "+v"(L.dkr), "+v"(L.inv_sd));
+        }
 #ifdef FOT_TIMELINE
         t_rows += __builtin_amdgcn_s_memtime() - t0;
 #endif
@@ -847,6 +855,7 @@ struct StagedTab {
         cos_r = r[4]; sin_r = r[5];
     }
 };
+using StagedTab = StagedTabT<>;
 
 #ifdef FOT_TIMELINE
 // diagnostic build (scripts/timeline.sh): per tile of the last k_evaluate launch -- tile start, start of the sample
@@ -884,7 +893,8 @@ __device__ __forceinline__ void wave_lds_fence()
 // What a tile's wave leaves behind, every lane of it: the candidates' final statuses (stop-distance filter included,
 // frenet_planner.py:307-324) in the candidate arrays and, in tp, what the selection needs of the tile: the histogram of
 // the statuses and the cheapest 'ok' candidate (lowest index among equals)
-__device__ __forceinline__ void tile_results(const DevParams &P, const InstDesc &D, const StagedTab &tab, const LonInfo &L,
+template <class Tab>
+__device__ __forceinline__ void tile_results(const DevParams &P, const InstDesc &D, const Tab &tab, const LonInfo &L,
                                              const double *q, SegState &g, bool hit, bool has_cand, int64_t slot, int cand0,
                                              int lane, TilePart &tp)
 {
@@ -922,7 +932,7 @@ __device__ __forceinline__ void tile_results(const DevParams &P, const InstDesc 
 //               (seg_merge) through `s_part`.
 // (The grouped cut has its own form, evaluate_group_tile below.)
 enum { TILE_WAVE = 0, TILE_SPLIT = 1 };
-template <int MODE, bool LEAN>
+template <int MODE, bool LEAN, bool FLAT = false>
 __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc,
                                               const InstState *__restrict__ state,
                                               const int32_t *__restrict__ tile_cand0, const int32_t *__restrict__ tile_n,
@@ -1024,7 +1034,7 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
     SegState g;
     seg_init(g);
     LonInfo L;
-    StagedTab tab;
+    StagedTabT<FLAT> tab;
     uint64_t hit_mask = 0;
     bool hit = false;
     int64_t slot = 0;
@@ -1073,7 +1083,7 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
             lc.n_circ_fp = __builtin_amdgcn_readfirstlane(lc.n_circ_fp);
             asm volatile("" : "+s"(lc.n_circ_fp));
         }
-        evaluate_segment<LEAN, SREG>(P, lc, L, tab, q, k0, k1, sink, g, ne_min);   // (SPLIT: a quarter of the steps -- latency, not issue, bound)
+        evaluate_segment<LEAN, SREG, FLAT>(P, lc, L, tab, q, k0, k1, sink, g, ne_min);   // (SPLIT: a quarter of the steps -- latency, not issue, bound)
         hit_mask = sink.hit_mask; hit = sink.hit;
 #ifdef FOT_TIMELINE
         tl_rows = tab.t_rows;
@@ -1158,7 +1168,7 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
 // that no lane decides: it comes out of the group's header (GroupHead, built by k_frenet_state), which the caller has put
 // into LDS behind the rows, all waves behind a barrier.  The per-lane set-up is issued BEFORE the rows are built -- it
 // reads none -- so that its loads (the step ranges, the horizon's matrices) and integer divisions run under the build.
-template <bool LEAN>
+template <bool LEAN, bool FLAT = false>
 __device__ __forceinline__ void evaluate_group_tile(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc,
                                                     const TileStep *__restrict__ wave_rng, const f2 *__restrict__ ent32,
                                                     const EvalKernArgs &a, const SplineView &sp_lds, double *my_rows,
@@ -1187,7 +1197,7 @@ __device__ __forceinline__ void evaluate_group_tile(const DevParams *__restrict_
     SegState g;
     seg_init(g);
     LonInfo L;
-    StagedTab tab;
+    StagedTabT<FLAT> tab;
     LoopConst lc;
     int64_t slot = 0;
     double q[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };              // lateral quintic of the lane's candidate
@@ -1264,7 +1274,7 @@ __device__ __forceinline__ void evaluate_group_tile(const DevParams *__restrict_
             lc.n_circ_fp = uni(head->n_circ_fp);
             asm volatile("" : "+s"(lc.n_circ_fp));
         }
-        evaluate_segment<LEAN, SREG>(P, lc, L, tab, q, 0, n_loop, sink, g, ne_min);
+        evaluate_segment<LEAN, SREG, FLAT>(P, lc, L, tab, q, 0, n_loop, sink, g, ne_min);
         hit = sink.hit;
 #ifdef FOT_TIMELINE
         tl_rows = tab.t_rows;
@@ -1455,6 +1465,7 @@ k_select_only(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ des
 }
 
 #define FOT_EVAL_LEAN false
+#define FOT_EVAL_FLAT false
 #define FOT_EVAL_KERNEL(name) name
 #include "fot_eval_kernels.inc"
 #undef FOT_EVAL_LEAN
@@ -1462,7 +1473,14 @@ k_select_only(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ des
 #define FOT_EVAL_LEAN true
 #define FOT_EVAL_KERNEL(name) name##_lean
 #include "fot_eval_kernels.inc"
+#undef FOT_EVAL_FLAT
+#undef FOT_EVAL_KERNEL
+// the flat forms of the lean kernels: every path of the launch is exactly straight (TileTable::flat, enqueue_lane)
+#define FOT_EVAL_FLAT true
+#define FOT_EVAL_KERNEL(name) name##_lean_flat
+#include "fot_eval_kernels.inc"
 #undef FOT_EVAL_LEAN
+#undef FOT_EVAL_FLAT
 #undef FOT_EVAL_KERNEL
 
 // ---------------------------------------------------------------------------
@@ -2157,6 +2175,11 @@ bool evaluate_in_groups(const TileTable &tiles)
     return tiles.n_tiles > 0 && eval_segments_of(tiles) == 1 && tiles.grouped;
 }
 
+bool evaluate_flat(const TileTable &tiles)
+{
+    return tiles.flat && tiles.n_tiles > 0 && (eval_segments_of(tiles) > 1 || tiles.grouped);
+}
+
 int launch_evaluate(const DevParams *P, const PathSet &ps, const InstDesc *desc, const InstState *state, int n_total,
                     int n_inst, TileTable tiles, EntryArrays e, CandArrays c, fot_result *out, int32_t *inst_done,
                     hipStream_t st)
@@ -2168,7 +2191,9 @@ int launch_evaluate(const DevParams *P, const PathSet &ps, const InstDesc *desc,
     //  * a handful of egos: every tile one workgroup, cut into time segments (k_evaluate_split);
     //  * the grouped cut: one workgroup per group of four tiles (k_evaluate_group, four waves per SIMD);
     //  * the per-wave cut: four independent tiles per workgroup (k_evaluate, three waves per SIMD).
-    // Each in its lean form (FusedSink) when the host found the launch eligible (tiles.lean: enqueue_lane).
+    // Each in its lean form (FusedSink) when the host found the launch eligible (tiles.lean: enqueue_lane), and the lean
+    // form in its flat form when every path of the launch is exactly straight (tiles.flat, which implies tiles.lean) --
+    // the split and the grouped shape; the per-wave shape has none (evaluate_flat).
     const int n_seg = eval_segments_of(tiles);
     static const int force_wpw = getenv("FOT_EVAL_WPW") ? atoi(getenv("FOT_EVAL_WPW")) : 0;      // diagnostics
     int wpw = n_seg > 1 ? 1 : tiles.n_tiles >= 1024 ? EVAL_WG / WAVE : 1;
@@ -2191,13 +2216,13 @@ int launch_evaluate(const DevParams *P, const PathSet &ps, const InstDesc *desc,
     if (tiles.n_tiles <= 0) {
         k_select_only<<<(unsigned)n_inst, WAVE, 0, st>>>(P, desc, state, tiles.cand0, tiles.n, e.rng, e.e32, a);
     } else if (n_seg > 1) {
-        (tiles.lean ? k_evaluate_split_lean : k_evaluate_split)<<<(unsigned)n_blocks, n_seg * WAVE, lds, st>>>(
+        (tiles.flat ? k_evaluate_split_lean_flat : tiles.lean ? k_evaluate_split_lean : k_evaluate_split)<<<(unsigned)n_blocks, n_seg * WAVE, lds, st>>>(
             P, desc, state, tiles.cand0, tiles.n, e.rng, e.e32, a);
     } else if (tiles.grouped) {                                            // one workgroup per group of tiles
         if (!tiles.heads) return (int)hipErrorInvalidValue;                // (evaluate_in_groups(): the caller builds them)
         const int per_q = (n_inst + N_XCD - 1) / N_XCD * (tiles.max_tiles / GROUP_TILES);
         const size_t g_lds = sizeof(double) * ((size_t)eval_group_doubles() + 9 * (size_t)lds_knots);
-        (tiles.lean ? k_evaluate_group_lean : k_evaluate_group)<<<(unsigned)(per_q * N_XCD), GROUP_TILES * WAVE, g_lds, st>>>(
+        (tiles.flat ? k_evaluate_group_lean_flat : tiles.lean ? k_evaluate_group_lean : k_evaluate_group)<<<(unsigned)(per_q * N_XCD), GROUP_TILES * WAVE, g_lds, st>>>(
             P, desc, state, tiles.cand0, tiles.n, e.rng, e.e32, a);
     } else {
         (tiles.lean ? k_evaluate_lean : k_evaluate)<<<(unsigned)n_blocks, wpw * WAVE, lds, st>>>(

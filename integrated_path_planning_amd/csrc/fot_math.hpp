@@ -573,11 +573,41 @@ FOT_HD void yaw_step_sin_cos(double cos_t, double sin_t, double prev_cos_t, doub
 // reference's atan2/cos/tan terms are cos = (1-kd)/h, sin = d'/h, tan = d'/(1-kd), (1-kd)/cos = h and
 // v = sqrt((1-kd)^2 sd^2 + (d' sd)^2) = |sd| h.
 // HEADING = false: cos_t / sin_t are left alone -- the evaluation walk composes them where they are read (check_sample).
-template <bool HEADING = true>
+//
+// FLAT: the form for a reference path that is exactly straight (spline_is_flat, fot_setup.hpp): every row has
+// kr = dkr = +-0 bit for bit, so for a finite lateral state 1 - kr d is exactly 1, its reciprocal is 1, krdp is +-0, and
+// every term of the general form that exists for the curvature is a multiplication by one or an addition of zero.  The
+// flat form leaves those out and keeps the general form's roundings: each fused multiply-add stands where the front end
+// contracts the general expression (the left product of a sum), spelled with FOT_FMA.  It reads neither L.kr nor L.dkr.
+// Only the sign of a zero can differ (kappa, a), and no record holds one: the walk hands on flags, maxima of absolute
+// values, first_nan, v_last, d_last and k_last.
+// Non-finite lateral states: the general form's 1 - 0 d is NaN for d = +-inf or NaN and poisons kappa, v and a through
+// hh (CK_NONFINITE).  The flat form keeps exactly that one multiply-add -- `one` is 1, or NaN where d is not finite --
+// and adds it to dp^2 in the place of (1 - kr d)^2, so hh, inv_h and h are NaN in the same samples.  A non-finite d'
+// or d'' with a finite d needs no guard: dp, dpp and everything formed from them are the same expressions in both forms
+// (dp = +-inf: hh = inf, inv_h = 0, h = inf 0 = NaN in both; dp = NaN: hh = NaN in both), and v = |sd| h and a carry h.
+template <bool HEADING = true, bool FLAT = false>
 FOT_HD void frenet_to_cart(const LonSample &L, double d, double d_d, double d_dd, CartSample &o)
 {
     const double dp = d_d * L.inv_sd;
     const double dpp = (d_dd - dp * L.sdd) * (L.inv_sd * L.inv_sd);
+    if constexpr (FLAT) {
+        const double one = FOT_FMA(-0.0, d, 1.0);                // 1 - (+-0) d
+        const double hh = FOT_FMA(dp, dp, one);                  // (one * one is one, or NaN)
+        const double inv_h = fast_rsqrt(hh);
+        const double h = hh * inv_h;
+        const double kappa = dpp * (inv_h * inv_h) * inv_h;
+        const double dtp = h * kappa;
+        o.x = L.rx - L.sin_r * d;
+        o.y = L.ry + L.cos_r * d;
+        o.cos_d = inv_h; o.sin_d = dp * inv_h;
+        if constexpr (HEADING) compose_heading(o.cos_d, o.sin_d, L.cos_r, L.sin_r, o.cos_t, o.sin_t);
+        o.kappa = kappa;
+        o.v = fabs(L.sd) * h;
+        o.a = FOT_FMA(L.sdd, h, L.sd * L.sd * h * (dp * dtp));
+        o.omkd = one;
+        return;
+    }
     const double omkd = 1.0 - L.kr * d;
     const double inv_om = fast_rcp(omkd);
     const double hh = dp * dp + omkd * omkd;
@@ -1003,7 +1033,9 @@ FOT_HD auto sink_has_points(const Sink &s, int) -> decltype(s.step_has_points())
 template <class Sink>
 FOT_HD bool sink_has_points(const Sink &, long) { return true; }
 
-template <bool LEAN = false, bool SREG = true, class Tab, class Sink>
+// FLAT: the reference path is exactly straight (frenet_to_cart<., true>) -- 1 - kr d is one or NaN, never at or below
+// SINGULARITY_EPS, so the walk has no CK_SINGULAR test.
+template <bool LEAN = false, bool SREG = true, bool FLAT = false, class Tab, class Sink>
 FOT_HD void evaluate_segment(const DevParams &P, const LoopConst &C, const LonInfo &L, const Tab &lon_tab,
                              const double *q, int k0, int k1, Sink &sink, SegState &g, int ne_min = 0)
 {
@@ -1015,7 +1047,7 @@ FOT_HD void evaluate_segment(const DevParams &P, const LoopConst &C, const LonIn
         double d, d_d, d_dd, d_ddd;
         lat_sample(q, k0 - 1, L.n_eval, C.dt, d, d_d, d_dd, d_ddd);
         CartSample c;
-        frenet_to_cart<false>(ls, d, d_d, d_dd, c);
+        frenet_to_cart<false, FLAT>(ls, d, d_d, d_dd, c);
         acc.prev.x = c.x; acc.prev.y = c.y; acc.prev.cos_t = c.cos_d; acc.prev.sin_t = c.sin_d;   // (relative: FrameHeadings)
         acc.prev.kappa = c.kappa; acc.prev.v = c.v; acc.prev.a = c.a; acc.prev.d = d;
     }
@@ -1043,8 +1075,8 @@ FOT_HD void evaluate_segment(const DevParams &P, const LoopConst &C, const LonIn
         }
         g.d_last = d;
         CartSample c;
-        frenet_to_cart<!LEAN>(ls, d, d_d, d_dd, c);                        // (the heading itself: for the footprint circles)
-        check_flag(acc, isfinite(c.omkd) && c.omkd <= 0.05, CK_SINGULAR);   // SINGULARITY_EPS, any sample
+        frenet_to_cart<!LEAN, FLAT>(ls, d, d_d, d_dd, c);                  // (the heading itself: for the footprint circles)
+        if constexpr (!FLAT) check_flag(acc, isfinite(c.omkd) && c.omkd <= 0.05, CK_SINGULAR);   // SINGULARITY_EPS, any sample
         // SREG: inside a segment "a NaN sample was seen" is first_nan >= 0 (seg_init: -1) -- the walk keys on the index
         // alone, and CK_SEEN_NAN, which only the code behind the segment reads, is set once behind the loop
         if constexpr (SREG) { if (g.first_nan < 0 && isnan(c.x)) g.first_nan = k; }

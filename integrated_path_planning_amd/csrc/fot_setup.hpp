@@ -165,6 +165,53 @@ inline int build_spline(int n, const double *wx, const double *wy, HostSpline &s
     return FOT_OK;
 }
 
+// A path is FLAT when its spline is exactly straight in the sense the flat evaluation kernels rely on
+// (frenet_to_cart<., true>): one coordinate's first-, second- and third-derivative coefficient arrays (b, c, d) are all
+// exactly zero -- spline_point then returns 0 for that coordinate's three derivatives wherever it returns numbers, and
+// spline_frame_fast forms kappa = (x' 0 - 0 x'') r^3 and kappa' = (x' 0 - 0 x''' - 3 (+-0) c r^2) r^3, both +-0 bit for
+// bit PROVIDED every factor is finite.  That is the second half of the test: the other coordinate's coefficients and the
+// knots are finite and moderate (at most FLAT_COEF_MAX, so that x' x'' and r^2, r^3 neither overflow), and its first
+// derivative -- a quadratic per segment, tested at the segment's ends and at its vertex -- keeps one sign and stays
+// above FLAT_SPEED_MIN in magnitude (r = 1/|x'| stays far below overflow).  A path that fails any of this is not flat
+// and takes the general kernels; so does one with a non-zero coefficient in a single segment.
+constexpr double FLAT_COEF_MAX = 1e30, FLAT_SPEED_MIN = 1e-6;
+
+inline bool spline_is_flat(const HostSpline &sp)
+{
+    const int n = sp.n;
+    if (n < 2) return false;
+    for (const std::vector<double> *v : { &sp.s, &sp.ax, &sp.bx, &sp.cx, &sp.dx, &sp.ay, &sp.by, &sp.cy, &sp.dy })
+        if ((int)v->size() < n) return false;
+    const auto all_zero = [n](const std::vector<double> &b, const std::vector<double> &c, const std::vector<double> &d) {
+        for (int i = 0; i < n; ++i) if (b[i] != 0.0 || c[i] != 0.0 || d[i] != 0.0) return false;
+        return true;
+    };
+    const auto moves = [&](const std::vector<double> &a, const std::vector<double> &b, const std::vector<double> &c,
+                           const std::vector<double> &d) {
+        const auto ok = [](double v) { return std::fabs(v) <= FLAT_COEF_MAX; };     // (false for NaN and inf)
+        for (int i = 0; i < n; ++i) if (!ok(sp.s[i]) || !ok(a[i]) || !ok(b[i]) || !ok(c[i]) || !ok(d[i])) return false;
+        const double sign = b[0] > 0.0 ? 1.0 : -1.0;
+        for (int i = 0; i < n - 1; ++i) {
+            const double h = sp.s[i + 1] - sp.s[i];
+            const auto speed = [&](double t) { return sign * (b[i] + 2.0 * c[i] * t + 3.0 * d[i] * t * t); };
+            if (!(h > 0.0) || !(speed(0.0) >= FLAT_SPEED_MIN) || !(speed(h) >= FLAT_SPEED_MIN)) return false;
+            if (d[i] != 0.0) {
+                const double tv = -c[i] / (3.0 * d[i]);          // vertex of the derivative
+                if (tv > 0.0 && tv < h && !(speed(tv) >= FLAT_SPEED_MIN)) return false;
+            }
+        }
+        return true;
+    };
+    const bool y_still = all_zero(sp.by, sp.cy, sp.dy), x_still = all_zero(sp.bx, sp.cx, sp.dx);
+    const auto offsets_ok = [n](const std::vector<double> &a) {  // the still coordinate's values: finite
+        for (int i = 0; i < n; ++i) if (!(std::fabs(a[i]) <= FLAT_COEF_MAX)) return false;
+        return true;
+    };
+    if (y_still && !x_still) return offsets_ok(sp.ay) && moves(sp.ax, sp.bx, sp.cx, sp.dx);
+    if (x_still && !y_still) return offsets_ok(sp.ax) && moves(sp.ay, sp.by, sp.cy, sp.dy);
+    return false;
+}
+
 // ---------------------------------------------------------------------------
 // batch layout
 // ---------------------------------------------------------------------------

@@ -1069,6 +1069,16 @@ class BatchPlanner:
             _abi.check(self._h, rc)
         return rc
 
+    def set_flat(self, on) -> bool:
+        """Test hook (``fot_debug_set_flat``): 1 / "auto" (the flat form of the lean evaluation kernels where every path
+        of a lean-eligible launch is exactly straight; the default), 0 / "off" (never), -1 / "query".  Returns whether a
+        launch of the most recent plan call took a flat kernel."""
+        on = {"auto": 1, "off": 0, "query": -1}.get(on, on)
+        rc = self._lib.fot_debug_set_flat(self._h, int(on))
+        if rc < 0:
+            _abi.check(self._h, rc)
+        return bool(rc)
+
     def last_eval_form(self) -> str:
         """Which evaluation kernels the most recent plan call ran: "none", "general", "lean" or "both"."""
         return ("none", "general", "lean", "both")[self.set_eval_form(-1)]

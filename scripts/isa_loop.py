@@ -3,6 +3,12 @@
 
     isa_loop.py <file.s> [kernel = k_evaluate_group] [which = 0]
 
+`kernel` is any of the evaluation kernels by its name in the source: k_evaluate, k_evaluate_split, k_evaluate_group, their
+lean forms (`..._lean`) and the lean forms' flat forms (k_evaluate_split_lean_flat, k_evaluate_group_lean_flat: the walk
+of exactly straight reference paths), each a function of its own in the ISA.  `--all` in the place of a kernel name prints
+the `per step` and `min-walk` rows of every evaluation kernel in the file, one block per kernel, so that a form and its
+flat form stand next to each other.
+
 The time-step loop is found through the compiler's own loop annotations ("Loop Header", "in Loop: Header=", "Parent
 Loop", "Child Loop"), not through branch targets: the back edge of a rotated loop does not branch to the header label.
 It is the depth-1 loop whose body holds the hand-issued `s_load_dwordx16` chunk loads (`which`: if there are several).
@@ -129,6 +135,13 @@ def row(label, where, c):
 
 
 def main(argv):
+    if len(argv) > 2 and argv[2] == '--all':
+        names = sorted(set(re.findall(r'\n_ZN3fot\d+(k_evaluate\w*?)E[^\n]*:\s*;', open(argv[1]).read())))
+        rc = 0
+        for name in names:
+            rc |= main([argv[0], argv[1], name])
+            print()
+        return rc if names else 1
     path = argv[1] if len(argv) > 1 else 'integrated_path_planning_amd/csrc/_obj/fot_kernels-hip-amdgcn-amd-amdhsa-gfx950.s'
     kern = argv[2] if len(argv) > 2 else 'k_evaluate_group'
     which = int(argv[3]) if len(argv) > 3 else 0
