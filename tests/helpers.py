@@ -17,14 +17,72 @@ def request_from_golden(g) -> PlanRequest:
 
 
 
-# The evaluation kernels a plan call can take (csrc/fot_kernels.hip launch_evaluate).  Every parity test that asserts a
-# per-candidate table runs under each of them: "auto" is what a caller gets (k_evaluate_split for a handful of egos,
-# k_evaluate_group for batches); "group" / "wave" walk every candidate in one piece under the grouped / per-wave cut
-# (k_evaluate_group / k_evaluate); "split-wave" cuts the per-wave tiles into time segments.
-EVAL_PATHS = ("auto", "group", "wave", "split-wave")
+# The evaluation kernels a plan call can take (csrc/fot_kernels.hip launch_evaluate, csrc/fot_host.cpp enqueue_lane).
+# A name is a launch shape -- (tile cut, time segments) -- and whether the flat form is allowed (set_flat).  The shape
+# picks the kernel family: split (more than one time segment, either cut), grouped (grouped cut, one piece), per-wave
+# (per-wave cut, one piece).  Within a family the launch decides the form:
+#   general   the handle has a scenario of more than 64 samples or with footprint circles, an instance of the launch
+#             has a chance budget (floor(eps * S) > 0 on a prediction distribution), or set_eval_form("general");
+#   flat      otherwise, where set_flat is on, every path the launch's instances use is exactly straight
+#             (spline_is_flat) and the family has a flat kernel (the per-wave family has none);
+#   lean      otherwise.
+#
+#   name           cut, seg, flat   general launch      lean launch, flat path        lean launch, other path
+#   "auto"          0    0    1     what a caller gets: the split family (four segments) up to 2304 tiles in the launch
+#                                   -- a handful of egos -- and beyond that the grouped or the per-wave family, by the cut
+#                                   the handle's lattices choose; each in the form of the columns below
+#   "group"         2    1    1     k_evaluate_group    k_evaluate_group_lean_flat    k_evaluate_group_lean
+#   "wave"          1    1    1     k_evaluate          k_evaluate_lean               k_evaluate_lean
+#   "split-wave"    1    4    1     k_evaluate_split    k_evaluate_split_lean_flat    k_evaluate_split_lean
+#   "group-noflat"  2    1    0     k_evaluate_group    k_evaluate_group_lean         k_evaluate_group_lean
+#   "split-noflat"  1    4    0     k_evaluate_split    k_evaluate_split_lean         k_evaluate_split_lean
+#
+# tests/test_gpu_eval_paths.py holds the library to this table.  Every parity test that asserts a per-candidate table
+# runs under each name.  The two "-noflat" names differ from "group" and "split-wave" only on exactly straight paths:
+# a suite may leave them out only if it ASSERTS that its launches under "group" and "split-wave" took no flat kernel
+# (`not bp.set_flat(-1)` after the plan call, took_flat below) -- on an arc, a road, a random heading.  A suite on
+# synthetic.STRAIGHT_WX / WY or another axis-aligned line runs them.
+EVAL_PATHS = ("auto", "group", "wave", "split-wave", "group-noflat", "split-noflat")
+EVAL_PATH_KNOBS = {"auto": (0, 0, 1), "group": (2, 1, 1), "wave": (1, 1, 1), "split-wave": (1, 4, 1),
+                   "group-noflat": (2, 1, 0), "split-noflat": (1, 4, 0)}      # name -> (tile cut, time segments, flat)
+NOFLAT_PATHS = tuple(p for p in EVAL_PATHS if not EVAL_PATH_KNOBS[p][2])
+FLAT_KERNEL_PATHS = ("group", "split-wave")          # shapes with a flat kernel at any batch size ("auto": by size)
+# for a suite on paths that are never exactly straight: the names that differ there -- with assert_no_flat_launch after
+# every plan call (the rule above)
+EVAL_PATHS_NEVER_FLAT = tuple(p for p in EVAL_PATHS if p not in NOFLAT_PATHS)
 
 
 def set_eval_path(bp, path):
-    cut, seg = {"auto": (0, 0), "group": (2, 1), "wave": (1, 1), "split-wave": (1, 4)}[path]
+    """all three knobs on every call: a loop over the names leaks no state, and "auto" restores a handle's defaults"""
+    cut, seg, flat = EVAL_PATH_KNOBS[path]
     bp.set_tile_cut(cut)
     bp.set_eval_segments(seg)
+    bp.set_flat(flat)
+
+
+def took_flat(bp):
+    """whether a launch of the most recent plan call took a flat kernel (a query: it changes no knob)"""
+    return bp.set_flat(-1)
+
+
+def assert_no_flat_launch(bp, label):
+    """after a plan call of a suite that leaves the "-noflat" names out: its launch took no flat kernel, so "group" and
+    "split-wave" ran the kernels those names would"""
+    assert not took_flat(bp), f"{label}: a flat kernel ran -- this suite must run helpers.NOFLAT_PATHS too"
+
+
+def waypoints_are_flat(wx, wy):
+    """one coordinate of the waypoints exactly constant -- the paths whose natural spline spline_is_flat accepts (the
+    other coordinate moves one way at a finite pace on every path of this suite)"""
+    wx, wy = np.asarray(wx, np.float64), np.asarray(wy, np.float64)
+    return bool(len(wx) >= 2 and ((wx == wx[0]).all() or (wy == wy[0]).all()))
+
+
+def assert_flat_as_named(bp, path, flat_path, label, small_batch=True):
+    """after a lean plan call under `path` on paths that are all exactly straight (`flat_path`) or not: the launch took
+    a flat kernel exactly where helpers' table says so.  small_batch: "auto" cut the launch into time segments (at most
+    2304 tiles); otherwise "auto" is not judged (its cut is the lattice's choice)."""
+    if path == "auto" and not small_batch:
+        return
+    want = bool(flat_path) and EVAL_PATH_KNOBS[path][2] == 1 and path != "wave"
+    assert took_flat(bp) == want, f"{label} [{path}]: flat launch {took_flat(bp)}, expected {want}"

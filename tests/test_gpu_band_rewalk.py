@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 import eps_band
-from helpers import EVAL_PATHS, assert_record_matches_oracle, oracle_plan_for_request, set_eval_path
+from helpers import (EVAL_PATHS_NEVER_FLAT as EVAL_PATHS, assert_no_flat_launch, assert_record_matches_oracle,
+                     oracle_plan_for_request, set_eval_path)
 from oracle import oracle as orc
 from test_gpu_collision_boundary import Scene, Target, rounded32
 
@@ -75,6 +76,8 @@ def test_band_obstacles_among_decoys_match_the_oracle(scene, eps):
         set_eval_path(sc.bp, path)
         for dtype, ws in ((np.float64, wants), (np.float32, wants32)):
             res = sc.bp.plan_batch(reqs, obstacle_dtype=dtype)
+            # (no scene's path is exactly straight: "group" / "split-wave" are the lean kernels, the "-noflat" names add nothing)
+            assert_no_flat_launch(sc.bp, f"{scene} eps {eps} [{path}]")
             for i, want in enumerate(ws):
                 lab = f"{scene} eps {eps} inst {i} [{path}, {np.dtype(dtype).name}] {labels[i]}"
                 _, status, keep, nt = sc.bp.candidates(i)

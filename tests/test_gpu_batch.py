@@ -5,8 +5,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import (EVAL_PATHS, TIGHT, assert_record_matches_oracle, oracle_plan_for_request, request_from_instance,
-                     set_eval_path)
+from helpers import (EVAL_PATHS_NEVER_FLAT, TIGHT, assert_no_flat_launch, assert_record_matches_oracle,
+                     oracle_plan_for_request, request_from_instance, set_eval_path, took_flat)
 from integrated_path_planning_amd import _abi, synthetic as syn
 from integrated_path_planning_amd.batch import PackedBatch, PlanRequest
 from integrated_path_planning_amd.footprint import EgoFootprint
@@ -116,9 +116,13 @@ def test_ragged_batch_vs_oracle():
     ]
     params, sp = _oracle(kw)
     wants = [oracle_plan_for_request(orc, params, sp, rq, table=True) for rq in reqs]
-    for path in EVAL_PATHS:                              # the oracle once, every evaluation kernel against it
+    # the oracle once, every evaluation kernel against it.  eps = 0.1 on distributions of 20 samples: the launch has a
+    # chance budget, runs the general kernels and takes no flat one (asserted) -- helpers' "-noflat" names add nothing
+    for path in EVAL_PATHS_NEVER_FLAT:
         set_eval_path(bp, path)
         res = bp.plan_batch(reqs)
+        assert bp.last_eval_form() == "general", path
+        assert_no_flat_launch(bp, f"ragged batch [{path}]")
         for i, want in enumerate(wants):
             label = f"inst {i} [{path}]"
             assert_record_matches_oracle(res.records[i], want, label=label)
@@ -258,10 +262,12 @@ def test_full_size_sample_vs_oracle(config4):
     assert n_tables >= 8
 
 
-@pytest.mark.parametrize("eval_path", ["wave", "split-wave"])
+@pytest.mark.parametrize("eval_path", ["wave", "split-wave", "group-noflat", "split-noflat"])
 def test_full_size_other_kernels_give_identical_tables(config4, eval_path):
-    """The same 256-instance launch through the per-wave kernel (k_evaluate) and through time segments of per-wave
-    tiles: records byte-identical to the grouped launch, candidate tables of 8 instances equal."""
+    """The same 256-instance launch through the per-wave kernel (k_evaluate_lean), through time segments of per-wave
+    tiles, and -- the path is exactly straight, so what a caller gets is a flat kernel -- through the grouped and the
+    split lean kernel with the flat form off: records byte-identical to the caller's launch, candidate tables of 8
+    instances equal."""
     bp, reqs, pb, res, kw = config4
     set_eval_path(bp, "auto")
     assert bytes(bp.plan_packed(pb).records) == bytes(res.records)
@@ -269,6 +275,7 @@ def test_full_size_other_kernels_give_identical_tables(config4, eval_path):
     set_eval_path(bp, eval_path)
     try:
         other = bp.plan_packed(pb)
+        assert bp.last_eval_form() == "lean" and took_flat(bp) == (eval_path == "split-wave"), eval_path
         assert bytes(other.records) == bytes(res.records)
         for i, (c0, s0, k0, n0) in ref_tables.items():
             c, s_, k, n = bp.candidates(i)

@@ -18,13 +18,18 @@ Every distinct (eps, inflation) of a scene is a scenario of one handle and all i
                float64 time-major records byte-identical to the plain launch's
   alone        an A, a B and an eps = 0 instance planned alone: the lean form exactly where the launch is eligible, the
                general form in company, the record byte-identical either way
+A launch with a budget runs the general kernels, which have no flat form, and the scenes' paths (headings 0.7 and 0.4 rad,
+an arc) are not exactly straight, so the eps = 0 instance planned alone runs k_evaluate_split_lean, never a flat
+kernel: every plan call asserts that no flat kernel ran, and helpers' "-noflat" names, which would repeat "group" and
+"split-wave", are left out (helpers.EVAL_PATHS_NEVER_FLAT).
 """
 import numpy as np
 import pytest
 
 import chance_budget_common as cb
 import eps_band
-from helpers import EVAL_PATHS, TIGHT, assert_record_matches_oracle, set_eval_path
+from helpers import (EVAL_PATHS_NEVER_FLAT as EVAL_PATHS, TIGHT, assert_no_flat_launch, assert_record_matches_oracle,
+                     set_eval_path)
 from integrated_path_planning_amd.batch import PackedBatch, PlanRequest
 from integrated_path_planning_amd.planner import BatchPlanner
 
@@ -105,6 +110,7 @@ def test_the_budget_under_every_evaluation_kernel(handles, name, group):
             set_path(h.bp, path)
             res = h.bp.plan_batch(h.reqs)
             assert FORMS[h.bp.set_eval_form(-1)] == "general", f"{name} [{path}]"
+            assert_no_flat_launch(h.bp, f"{name} [{path}]")
             for i in idx:
                 h.check(res, i, path)
             recs = [rec_bytes(res.records[i]) for i in idx]
@@ -128,6 +134,7 @@ def test_the_budget_in_float32_and_time_major_tensors(handles, name, group):
             for dtype, tsp in ((np.float64, True), (np.float32, False), (np.float32, True)):
                 how = f"{path}, {np.dtype(dtype).name}{', time-major' if tsp else ''}"
                 res = h.bp.plan_packed(PackedBatch(h.reqs, dtype, dyn_layout_tsp=tsp))
+                assert_no_flat_launch(h.bp, f"{name} [{how}]")
                 for i in idx:
                     h.check(res, i, how)
                 if dtype is np.float64:
@@ -165,6 +172,7 @@ def test_alone_and_in_company(handles, name):
             assert eligible == (what == "eps0" and name == "straight")
             form = FORMS[h.bp.set_eval_form(-1)]
             assert form == ("lean" if eligible else "general"), f"{inst.label()} alone ran the {form} form"
+            assert_no_flat_launch(h.bp, f"{inst.label()} alone")
             h.check(one, i, "alone", slot=0)
             assert rec_bytes(one.records[0]) == company[i], f"{inst.label()} inst {i}: alone against in company"
     finally:

@@ -2,14 +2,17 @@
 launch bench.py times: k_evaluate_group at full occupancy, the last-arriver selection under real concurrency), ALL
 records and ALL per-candidate tables -- status, kept length, cost of 573 440 candidates per batch -- against the oracle
 (which runs on a thread pool: the C call releases the GIL).  Default: one batch of fresh seeds, under the grouped and
-the per-wave cut; FOT_FULLSIZE_BATCHES=N sweeps N batches (profiles/r03_*_fullsize_sweep.log)."""
+the per-wave cut; FOT_FULLSIZE_BATCHES=N sweeps N batches (profiles/r03_*_fullsize_sweep.log).  The path is exactly
+straight, so the grouped launch is k_evaluate_group_lean_flat's (asserted); a second test holds k_evaluate_group_lean,
+the kernel a bent road runs at this size, to the same oracle plans with the flat form off ("group-noflat")."""
+import functools
 import os
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
-from helpers import TIGHT, assert_record_matches_oracle, oracle_plan_for_request, request_from_instance, set_eval_path
+from helpers import TIGHT, assert_record_matches_oracle, oracle_plan_for_request, request_from_instance, set_eval_path, took_flat
 from integrated_path_planning_amd import synthetic as syn
 from integrated_path_planning_amd.batch import PackedBatch, PlanRequest
 from integrated_path_planning_amd.planner import BatchPlanner
@@ -29,19 +32,34 @@ def _rounded(r, dt):
                        static=c(r.static), dyn=c(r.dyn), dist=c(r.dist))
 
 
-@pytest.mark.parametrize("batch", range(N_BATCHES))
-def test_every_instance_of_a_full_launch(batch):
-    kw = syn.CONFIG3_PLANNER
-    params, sp = orc.make_params(**kw), orc.Spline(*WP)
-    bp = BatchPlanner(waypoints=WP, **kw)
+@functools.lru_cache(maxsize=None)
+def _batch(batch):
+    """the packed requests of a batch and the oracle's plans of them, computed once"""
+    params, sp = orc.make_params(**syn.CONFIG3_PLANNER), orc.Spline(*WP)
     reqs = [request_from_instance(syn.config3_instance(SEED0 + 256 * batch + s)) for s in range(256)]
-    pb = PackedBatch(reqs, np.float32)
     with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as ex:
         wants = list(ex.map(lambda r: oracle_plan_for_request(orc, params, sp, _rounded(r, np.float32), table=True), reqs))
+    return PackedBatch(reqs, np.float32), wants
+
+
+@pytest.mark.parametrize("batch", range(N_BATCHES))
+def test_every_instance_of_a_full_launch(batch):
+    _full_launch(batch, ("group", "wave"))
+
+
+@pytest.mark.parametrize("batch", range(N_BATCHES))
+def test_every_instance_of_a_full_launch_on_the_lean_grouped_kernel(batch):
+    _full_launch(batch, ("group-noflat",))
+
+
+def _full_launch(batch, paths):
+    pb, wants = _batch(batch)
+    bp = BatchPlanner(waypoints=WP, **syn.CONFIG3_PLANNER)
     n_cand = 0
-    for path in ("group", "wave"):
+    for path in paths:
         set_eval_path(bp, path)
         res = bp.plan_packed(pb)
+        assert bp.last_eval_form() == "lean" and took_flat(bp) == (path == "group"), f"batch {batch} [{path}]"
         for i, want in enumerate(wants):
             label = f"batch {batch} inst {i} [{path}]"
             assert_record_matches_oracle(res.records[i], want, label=label)
@@ -50,6 +68,6 @@ def test_every_instance_of_a_full_launch(batch):
             np.testing.assert_array_equal(keep, want.cand_keep, err_msg=label)
             np.testing.assert_allclose(cost, want.cand_cost, rtol=TIGHT, atol=TIGHT, err_msg=label)
             n_cand += len(status)
-    print(f"batch {batch}: 256 instances x 2 kernels, {n_cand} candidate rows equal to the oracle's; "
+    print(f"batch {batch}: 256 instances x {len(paths)} kernel(s), {n_cand} candidate rows equal to the oracle's; "
           f"{sum(w.status == 0 for w in wants)} instances with a path")
     bp.close()

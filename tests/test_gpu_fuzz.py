@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 
 import eps_band
-from helpers import EVAL_PATHS, NORTH_STAR_TOL, TIGHT, assert_record_matches_oracle, oracle_plan_for_request, set_eval_path
+from helpers import (EVAL_PATH_KNOBS, EVAL_PATHS_NEVER_FLAT, NORTH_STAR_TOL, TIGHT, assert_no_flat_launch,
+                     assert_record_matches_oracle, oracle_plan_for_request, set_eval_path)
 from integrated_path_planning_amd import _abi
 from integrated_path_planning_amd.batch import PackedBatch, PlanRequest
 from integrated_path_planning_amd.footprint import EgoFootprint
@@ -140,13 +141,18 @@ def run_seed(seed, n_inst, dense):
     reqs = [random_request(rng, sp, kw, dense) for _ in range(n_inst)]
     wants = [oracle_plan_for_request(orc, params, sp, rq, table=True) for rq in reqs]
     # the oracle once, the library under every evaluation kernel it ships (FOT_FUZZ_SEGMENTS: that segment count only)
-    paths = tuple(p_ for p_ in os.environ.get("FOT_FUZZ_PATHS", "").split(",") if p_) or EVAL_PATHS   # (sweeps: a subset)
+    # FOT_FUZZ_PATHS: any names of helpers.EVAL_PATHS (sweeps: a subset).  The default leaves "group-noflat" and
+    # "split-noflat" out: a path of random heading is never exactly straight, no launch takes a flat kernel (asserted
+    # below), and the two would repeat "group" and "split-wave".
+    paths = tuple(p_ for p_ in os.environ.get("FOT_FUZZ_PATHS", "").split(",") if p_) or EVAL_PATHS_NEVER_FLAT
+    assert all(p_ in EVAL_PATH_KNOBS for p_ in paths), f"FOT_FUZZ_PATHS: {paths}, known {tuple(EVAL_PATH_KNOBS)}"
     for path in (paths if not FORCE_SEGMENTS else ("forced",)):
         if FORCE_SEGMENTS:
             bp.set_eval_segments(FORCE_SEGMENTS)
         else:
             set_eval_path(bp, path)
         res = bp.plan_batch(reqs)
+        assert_no_flat_launch(bp, f"seed {seed} [{path}]")
         for i, want in enumerate(wants):
             label = f"seed {seed} inst {i} [{path}]"
             cost, status, keep, nt = bp.candidates(i)

@@ -1,8 +1,11 @@
 """The group headers on the GPU: k_frenet_state builds one GroupHead per instance and group position, the grouped
-evaluation kernels (k_evaluate_group / k_evaluate_group_lean) read it instead of deriving its content per workgroup.
+evaluation kernels (k_evaluate_group / k_evaluate_group_lean / k_evaluate_group_lean_flat) read it instead of deriving its
+content per workgroup.
 
-Every case plans the same batch under the grouped cut ("group": the kernels that read the headers) and under the per-wave
-cut ("wave": k_evaluate, which has no header) and asks for byte-identical records, then holds the records to the oracle.
+Every case plans the same batch under the grouped cut -- "group", which on this module's exactly straight path means
+the flat kernel for a lean launch, and "group-noflat", the lean kernel every bent road runs; both are asserted to have
+launched what they name -- and under the per-wave cut ("wave": k_evaluate / k_evaluate_lean, which have no header), asks
+for byte-identical records, then holds the records of both grouped launches to the oracle.
 The cases are the states in which a header differs in kind: group positions a lattice does not have, groups past the
 candidates of a standing ego, no Frenet state at all, chains and Frenet-given egos (whose headers k_frenet_state writes in
 its chain loop), scenarios mixed in one call, both forms of the kernel, a horizon of more than 64 samples, and a handle
@@ -14,7 +17,7 @@ import numpy as np
 import pytest
 
 import eps_band
-from helpers import TIGHT, assert_record_matches_oracle, oracle_plan_for_request, request_from_instance, set_eval_path
+from helpers import TIGHT, assert_record_matches_oracle, oracle_plan_for_request, request_from_instance, set_eval_path, took_flat
 from integrated_path_planning_amd import _abi, synthetic as syn
 from integrated_path_planning_amd.batch import PlanRequest
 from integrated_path_planning_amd.planner import BatchPlanner
@@ -45,37 +48,54 @@ def obstacles(seed):
     return dyn, static
 
 
-def group_and_wave(bp, reqs, label, **kw):
-    """the batch under both cuts: byte-identical records; returns the grouped result"""
-    set_eval_path(bp, "group")
-    grouped = bp.plan_batch(reqs, **kw)
-    blobs = [rec_bytes(grouped.records[i]) for i in range(len(reqs))]
+GROUPED = ("group", "group-noflat")
+
+
+def group_and_wave(bp, reqs, label, flat=True, **kw):
+    """the batch under both cuts: byte-identical records.  flat: the launch under "group" is lean and every path it uses
+    exactly straight, so it takes k_evaluate_group_lean_flat; "group-noflat" never does.  Returns the grouped results by
+    name and the record bytes."""
+    results = {}
+    for path in GROUPED:
+        set_eval_path(bp, path)
+        results[path] = bp.plan_batch(reqs, **kw)
+        want = flat and path == "group"
+        assert took_flat(bp) == want, f"{label} [{path}]: flat launch {took_flat(bp)}, expected {want}"
+        if flat:
+            assert bp.last_eval_form() == "lean", f"{label} [{path}]"
+    blobs = [rec_bytes(results["group"].records[i]) for i in range(len(reqs))]
+    for i in range(len(reqs)):
+        assert blobs[i] == rec_bytes(results["group-noflat"].records[i]), \
+            f"{label} inst {i}: the flat grouped record differs from the lean grouped one"
     set_eval_path(bp, "wave")
     wave = bp.plan_batch(reqs, **kw)
+    assert not took_flat(bp), f"{label} [wave]"
     for i in range(len(reqs)):
         assert blobs[i] == rec_bytes(wave.records[i]), f"{label} inst {i}: the grouped record differs from the per-wave one"
     set_eval_path(bp, "group")
-    return grouped, blobs
+    return results, blobs
 
 
-def against_oracle(res, reqs, kws, wps, label, skip=()):
-    for i, rq in enumerate(reqs):
-        if i in skip:
-            continue
-        want = oracle_plan_for_request(orc, orc.make_params(**kws[rq.scenario]), orc.Spline(*wps[rq.scenario]), rq)
-        assert_record_matches_oracle(res.records[i], want, label=f"{label} inst {i}")
+def against_oracle(results, reqs, kws, wps, label, skip=()):
+    """every result of `results` (by path name) against the oracle's plans, computed once"""
+    wants = {i: oracle_plan_for_request(orc, orc.make_params(**kws[rq.scenario]), orc.Spline(*wps[rq.scenario]), rq)
+             for i, rq in enumerate(reqs) if i not in skip}
+    assert set(results) == set(GROUPED)
+    for path, res in results.items():
+        for i, want in wants.items():
+            assert_record_matches_oracle(res.records[i], want, label=f"{label} [{path}] inst {i}")
 
 
-def check(kw, reqs, label, wp=WP, form=None, **plan_kw):
+def check(kw, reqs, label, wp=WP, form=None, flat=True, **plan_kw):
     bp = BatchPlanner(waypoints=wp, **kw)
     if form:
         bp.set_eval_form(form)
-    res, _ = group_and_wave(bp, reqs, label, **plan_kw)
+    results, _ = group_and_wave(bp, reqs, label, flat=flat, **plan_kw)
     if form:
         assert bp.last_eval_form() == form, label
-    against_oracle(res, reqs, [kw], [wp], label)
+    against_oracle(results, reqs, [kw], [wp], label)
     bp.close()
-    return res
+    return results["group"]
 
 
 def test_one_instance():
@@ -117,9 +137,10 @@ def test_no_frenet_state_between_two_healthy_instances():
     """The middle instance is given as a Frenet state beyond the end of the path: no state, every header says skip."""
     reqs = [c3(0), PlanRequest(500.0, 1.0, 0.0, 0.0, 0.0, is_frenet=True), c3(2)]
     bp = BatchPlanner(waypoints=WP, **syn.CONFIG3_PLANNER)
-    res, _ = group_and_wave(bp, reqs, "failed c2f", obstacle_dtype=np.float32)
-    assert res.records[1].status == _abi.PLAN_C2F_FAILED and res.records[1].n_cand == 0
-    against_oracle(res, reqs, [syn.CONFIG3_PLANNER], [WP], "failed c2f", skip=(1,))
+    results, _ = group_and_wave(bp, reqs, "failed c2f", obstacle_dtype=np.float32)
+    for res in results.values():
+        assert res.records[1].status == _abi.PLAN_C2F_FAILED and res.records[1].n_cand == 0
+    against_oracle(results, reqs, [syn.CONFIG3_PLANNER], [WP], "failed c2f", skip=(1,))
     bp.close()
 
 
@@ -131,15 +152,17 @@ def test_chain_of_three():
         reqs.append(PlanRequest(12.0, 0.3, 0.02, 6.0, 0.2, target_speed=7.0 - 2.5 * j, dyn=dyn, static=static,
                                 chain_prev_s=j > 0, overrides={"max_accel": 1.0 + 0.5 * j} if j else None))
     bp = BatchPlanner(waypoints=WP, **LATTICE)
-    res, _ = group_and_wave(bp, [c3(1)] + reqs + [c3(2)], "chain")
+    results, _ = group_and_wave(bp, [c3(1)] + reqs + [c3(2)], "chain")
     prev_s = None
     for j, rq in enumerate(reqs):                                # the oracle, call by call, as the chain stands for
         one = copy.copy(rq)
         one.chain_prev_s, one.prev_s = False, prev_s
         want = oracle_plan_for_request(orc, orc.make_params(**LATTICE), orc.Spline(*WP), one)
-        assert_record_matches_oracle(res.records[1 + j], want, label=f"chain member {j}")
+        for path, res in results.items():
+            assert_record_matches_oracle(res.records[1 + j], want, label=f"chain member {j} [{path}]")
         prev_s = float(want.new_prev_s)
-    assert len({res.records[1 + j].n_cand for j in range(3)}) == 3
+    for res in results.values():
+        assert len({res.records[1 + j].n_cand for j in range(3)}) == 3
     bp.close()
 
 
@@ -150,12 +173,13 @@ def test_ego_given_as_frenet_state():
     rec0 = bp.plan_batch([ego]).records[0]
     given = PlanRequest(*[float(v) for v in rec0.frenet0[:5]], last_kappa=float(rec0.frenet0[5]), is_frenet=True,
                         target_speed=6.0, dyn=dyn, static=static)
-    res, _ = group_and_wave(bp, [given, ego], "frenet given")
+    results, _ = group_and_wave(bp, [given, ego], "frenet given")
     want = oracle_plan_for_request(orc, orc.make_params(**LATTICE), orc.Spline(*WP), ego)
-    assert_record_matches_oracle(res.records[1], want, label="cartesian ego")
     want_given = copy.copy(want)
     want_given.new_prev_s = float("nan")                        # (no nearest-point search: the record has none)
-    assert_record_matches_oracle(res.records[0], want_given, label="the same ego as a Frenet state")
+    for path, res in results.items():
+        assert_record_matches_oracle(res.records[1], want, label=f"cartesian ego [{path}]")
+        assert_record_matches_oracle(res.records[0], want_given, label=f"the same ego as a Frenet state [{path}]")
     bp.close()
 
 
@@ -166,13 +190,14 @@ def test_three_scenarios_in_one_call():
         assert bp.add_scenario(waypoints=w, **kw) == k
     reqs = [c3(s, scenario=(s * 7 // 5) % 3) for s in range(9)]
     assert {r.scenario for r in reqs} == {0, 1, 2}
-    res, _ = group_and_wave(bp, reqs, "scenarios", obstacle_dtype=np.float32)
-    against_oracle(res, reqs, [kw for _, kw in syn.SCENARIO_PLANNERS], [w for w, _ in syn.SCENARIO_PLANNERS], "scenarios")
+    results, _ = group_and_wave(bp, reqs, "scenarios", flat=False, obstacle_dtype=np.float32)   # (the third path is curved)
+    assert bp.last_eval_form() == "lean"
+    against_oracle(results, reqs, [kw for _, kw in syn.SCENARIO_PLANNERS], [w for w, _ in syn.SCENARIO_PLANNERS], "scenarios")
     bp.close()
 
 
 def test_general_form_forced():
-    check(syn.CONFIG3_PLANNER, [c3(s) for s in range(5)], "general form", form="general", obstacle_dtype=np.float32)
+    check(syn.CONFIG3_PLANNER, [c3(s) for s in range(5)], "general form", form="general", flat=False, obstacle_dtype=np.float32)
 
 
 def test_sixty_five_sample_horizon():
@@ -189,9 +214,9 @@ def test_sixty_five_sample_horizon():
                  + np.cumsum(rng.normal(0, 0.1, (8, 65, 2)), axis=1))
         reqs.append(r)
     bp = BatchPlanner(waypoints=WP, **kw)
-    res, _ = group_and_wave(bp, reqs, "65 samples")
+    results, _ = group_and_wave(bp, reqs, "65 samples", flat=False)
     assert bp.last_eval_form() == "general"
-    against_oracle(res, reqs, [kw], [WP], "65 samples")
+    against_oracle(results, reqs, [kw], [WP], "65 samples")
     bp.close()
 
 
@@ -209,13 +234,15 @@ def test_a_reused_handle_never_reads_an_earlier_batchs_headers():
     bp = BatchPlanner(waypoints=WP, **LATTICE)
     for n, seed in ((9, 1), (1, 2), (9, 3)):
         reqs = batch(n, seed)
-        res, blobs = group_and_wave(bp, reqs, f"reused handle, {n} instances (seed {seed})")
-        against_oracle(res, reqs, [LATTICE], [WP], f"reused handle, {n} instances (seed {seed})")
+        results, blobs = group_and_wave(bp, reqs, f"reused handle, {n} instances (seed {seed})")
+        against_oracle(results, reqs, [LATTICE], [WP], f"reused handle, {n} instances (seed {seed})")
         fresh = BatchPlanner(waypoints=WP, **LATTICE)
-        set_eval_path(fresh, "group")
-        want = fresh.plan_batch(reqs)
-        for i in range(n):
-            assert blobs[i] == rec_bytes(want.records[i]), f"seed {seed} inst {i}: a fresh handle gives another record"
+        for path in GROUPED:
+            set_eval_path(fresh, path)
+            want = fresh.plan_batch(reqs)
+            assert took_flat(fresh) == (path == "group")
+            for i in range(n):
+                assert blobs[i] == rec_bytes(want.records[i]), f"seed {seed} inst {i} [{path}]: a fresh handle gives another record"
         fresh.close()
     bp.close()
 
@@ -230,13 +257,16 @@ def test_candidate_tables_under_the_grouped_cut():
                 setattr(r, f, np.asarray(v, np.float64))
         reqs.append(r)
     bp = BatchPlanner(waypoints=WP, **syn.CONFIG3_PLANNER)
-    set_eval_path(bp, "group")
-    res = bp.plan_batch(reqs)
-    for i, rq in enumerate(reqs):
-        want = oracle_plan_for_request(orc, orc.make_params(**syn.CONFIG3_PLANNER), orc.Spline(*WP), rq, table=True)
-        assert_record_matches_oracle(res.records[i], want, label=f"inst {i}")
-        cost, status, keep, nt = bp.candidates(i)
-        np.testing.assert_array_equal(keep, want.cand_keep, err_msg=f"inst {i}")
-        np.testing.assert_allclose(cost, want.cand_cost, rtol=TIGHT, atol=TIGHT, err_msg=f"inst {i}")
-        eps_band.check_status_table(bp, i, status, want.cand_status, f"inst {i}")
+    wants = [oracle_plan_for_request(orc, orc.make_params(**syn.CONFIG3_PLANNER), orc.Spline(*WP), rq, table=True) for rq in reqs]
+    for path in GROUPED:
+        set_eval_path(bp, path)
+        res = bp.plan_batch(reqs)
+        assert bp.last_eval_form() == "lean" and took_flat(bp) == (path == "group"), path
+        for i, want in enumerate(wants):
+            lab = f"inst {i} [{path}]"
+            assert_record_matches_oracle(res.records[i], want, label=lab)
+            cost, status, keep, nt = bp.candidates(i)
+            np.testing.assert_array_equal(keep, want.cand_keep, err_msg=lab)
+            np.testing.assert_allclose(cost, want.cand_cost, rtol=TIGHT, atol=TIGHT, err_msg=lab)
+            eps_band.check_status_table(bp, i, status, want.cand_status, lab)
     bp.close()

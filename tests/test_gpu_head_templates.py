@@ -6,7 +6,8 @@ ladder), an ego at the 0.1 m/s brake gate and a standing one (the variant withou
 headers only), a chain of two (the head's workgroup writes both members' headers) and an ego given as a Frenet state.
 It runs on a lattice whose one-speed shape is a single tile and on the default lattice; the records must be
 byte-identical between the grouped kernels (which read the headers) and the per-wave kernels (which have none), and
-match the oracle.  Then, on the same handle, whatever rebuilds the tile table must rebuild the templates: a further
+match the oracle -- under "group", which on this module's exactly straight path launches k_evaluate_group_lean_flat, and
+under "group-noflat", which launches k_evaluate_group_lean as any bent road does; both are asserted to.  Then, on the same handle, whatever rebuilds the tile table must rebuild the templates: a further
 scenario with another group count, the tile cut changed and changed back, and one batch over the three scenario planners.
 """
 import copy
@@ -14,7 +15,7 @@ import copy
 import numpy as np
 import pytest
 
-from helpers import assert_record_matches_oracle, oracle_plan_for_request, set_eval_path
+from helpers import assert_record_matches_oracle, oracle_plan_for_request, set_eval_path, took_flat
 from integrated_path_planning_amd import _abi, synthetic as syn
 from integrated_path_planning_amd.batch import PlanRequest
 from integrated_path_planning_amd.planner import BatchPlanner
@@ -63,25 +64,40 @@ def the_batch(bp, scenario=0, seed=1):
 FAILED, CHAIN_HEAD, CHAIN_MEMBER, GIVEN = 3, 4, 5, 6
 
 
-def group_and_wave(bp, reqs, label):
-    """the batch under both cuts (each change of the cut rebuilds the tile table): byte-identical records"""
-    set_eval_path(bp, "group")
-    grouped = bp.plan_batch(reqs)
+GROUPED = ("group", "group-noflat")
+
+
+def group_and_wave(bp, reqs, label, flat=True):
+    """the batch under both cuts (each change of the cut rebuilds the tile table): byte-identical records.  flat: every
+    path the launch uses is exactly straight, so "group" takes the flat kernel; "group-noflat" never does.  Returns the
+    grouped results by name."""
+    results = {}
+    for path in GROUPED:
+        set_eval_path(bp, path)
+        results[path] = bp.plan_batch(reqs)
+        want = flat and path == "group"
+        assert bp.last_eval_form() == "lean", f"{label} [{path}]"
+        assert took_flat(bp) == want, f"{label} [{path}]: flat launch {took_flat(bp)}, expected {want}"
     set_eval_path(bp, "wave")
     wave = bp.plan_batch(reqs)
-    for i in range(len(reqs)):
-        assert rec_bytes(grouped.records[i]) == rec_bytes(wave.records[i]), \
-            f"{label} inst {i}: the grouped record differs from the per-wave one"
+    assert not took_flat(bp), f"{label} [wave]"
+    for path, grouped in results.items():
+        for i in range(len(reqs)):
+            assert rec_bytes(grouped.records[i]) == rec_bytes(wave.records[i]), \
+                f"{label} inst {i}: the grouped record [{path}] differs from the per-wave one"
     set_eval_path(bp, "group")
-    return grouped
+    return results
 
 
-def against_oracle(res, reqs, kws, wps, label):
-    """every record against the oracle; a chain member as the call behind its head, a given state without new_prev_s"""
+def against_oracle(results, reqs, kws, wps, label):
+    """every record of every result (by path name) against the oracle; a chain member as the call behind its head, a
+    given state without new_prev_s"""
+    assert set(results) == set(GROUPED)
     prev_s = None
     for i, rq in enumerate(reqs):
         if rq.is_frenet and rq.x > 400.0:                       # beyond the path: no Frenet state
-            assert res.records[i].status == _abi.PLAN_C2F_FAILED and res.records[i].n_cand == 0, (label, i)
+            for res in results.values():
+                assert res.records[i].status == _abi.PLAN_C2F_FAILED and res.records[i].n_cand == 0, (label, i)
             continue
         one = copy.copy(rq)
         if rq.chain_prev_s:
@@ -94,14 +110,17 @@ def against_oracle(res, reqs, kws, wps, label):
         if given is not None:
             want = copy.copy(want)
             want.new_prev_s = float("nan")
-        assert_record_matches_oracle(res.records[i], want, label=f"{label} inst {i}")
+        for path, res in results.items():
+            assert_record_matches_oracle(res.records[i], want, label=f"{label} [{path}] inst {i}")
 
 
 def check_batch(bp, kws, wps, scenario, label, seed=1):
     reqs = the_batch(bp, scenario, seed)
-    res = group_and_wave(bp, reqs, label)
-    against_oracle(res, reqs, kws, wps, label)
+    results = group_and_wave(bp, reqs, label)
+    against_oracle(results, reqs, kws, wps, label)
+    res = results["group"]
     n = [res.records[i].n_cand for i in range(len(reqs))]
+    assert n == [results["group-noflat"].records[i].n_cand for i in range(len(reqs))]
     assert n[1] > 0 and n[2] > 0 and n[FAILED] == 0 and n[CHAIN_HEAD] != n[CHAIN_MEMBER], (label, n)
     return res, n
 
@@ -137,6 +156,6 @@ def test_default_lattice_then_every_rebuild_of_the_tile_table():
         reqs.append(PlanRequest(*[float(v) for v in r.ego], target_speed=float(r.target_speed),
                                 static=np.asarray(r.static, np.float64), scenario=2 + s % 3))
     reqs[4].v = 0.05                                             # (a standing ego among them)
-    res = group_and_wave(bp, reqs, "scenarios")
-    against_oracle(res, reqs, kws, wps, "scenarios")
+    results = group_and_wave(bp, reqs, "scenarios", flat=False)  # (the third scenario planner's path is curved)
+    against_oracle(results, reqs, kws, wps, "scenarios")
     bp.close()

@@ -24,7 +24,7 @@ import numpy as np
 import pytest
 
 import eps_band
-from helpers import (EVAL_PATHS, TIGHT, PlanRequest, assert_record_matches_oracle, oracle_plan_for_request,
+from helpers import (EVAL_PATHS, TIGHT, PlanRequest, assert_flat_as_named, took_flat, assert_record_matches_oracle, oracle_plan_for_request,
                      request_from_instance, set_eval_path)
 from integrated_path_planning_amd import _abi, synthetic as syn
 from integrated_path_planning_amd.planner import BatchPlanner
@@ -87,6 +87,10 @@ def test_records_tables_and_lateral_columns_under_every_path_and_form(wants):
             res = bp.plan_batch(reqs)
             label = f"[{path}, {form}]"
             assert bp.last_eval_form() == form, f"{label}: ran the {bp.last_eval_form()} form"
+            if form == "lean":                              # (WP is exactly straight: flat kernels, and the lean ones by name)
+                assert_flat_as_named(bp, path, True, label)
+            else:
+                assert not took_flat(bp), label
             got = [rec_bytes(res.records[i]) for i in range(len(reqs))]
             if first is None:
                 first = got

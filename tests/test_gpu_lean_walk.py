@@ -1,23 +1,30 @@
-"""The lean form of the evaluation kernels (k_evaluate_lean / _split_lean / _group_lean) on the GPU.
+"""The lean form of the evaluation kernels (k_evaluate_lean / _split_lean / _group_lean, and the flat forms
+k_evaluate_split_lean_flat / _group_lean_flat of the latter two) on the GPU.
 
 A plan call takes the lean form when every scenario of the handle has at most 64 samples per candidate and the single
 centre circle, and every instance of the launch has no chance budget (max_viol == 0); anything else runs the general
 form.  `BatchPlanner.set_eval_form("general")` forces the general form on an eligible call and `last_eval_form()` tells
-which one the most recent call ran.
+which one the most recent call ran.  On an exactly straight path a lean launch of the split or the grouped shape takes
+the flat form unless `set_flat(0)` holds it back; `set_flat(-1)` tells whether the most recent call did.  Most paths of
+this module are straight, so every comparison names the kernel it wants and asserts that it ran:
 
-  * lean against forced-general: byte-identical records, equal candidate tables -- which also keeps the general form
-    covered on eps = 0 inputs now that "auto" takes the lean one there;
-  * the eligibility edges, each held against per-instance calls and the oracle;
+  * three ways where the path is straight -- flat, lean (`set_flat(0)`: the kernels every bent road runs) and forced
+    general -- and lean against forced-general elsewhere: byte-identical records, equal candidate tables; this also
+    keeps the general form covered on eps = 0 inputs now that "auto" takes the lean one there.  Under the names
+    "group-noflat" / "split-noflat" of helpers.EVAL_PATHS the first leg is itself held back: lean twice, then general;
+  * the eligibility edges, each held against per-instance calls and the oracle, with the flat form and without;
   * band lanes: obstacles one float32 ulp inside / outside the collision radius and at the two float32 thresholds of the
-    sink, on tiles of 1, 63 and 64 candidates, decided by the exact re-check that keeps its state in locals.
+    sink, on tiles of 1, 63 and 64 candidates, decided by the exact re-check that keeps its state in locals -- on their
+    straight scenes under the flat kernels and under the lean ones.
 """
 import numpy as np
 import pytest
 
 import eps_band
 from conftest import Golden
-from helpers import (EVAL_PATHS, TIGHT, assert_record_matches_oracle, oracle_plan_for_request, request_from_golden,
-                     request_from_instance, set_eval_path)
+from helpers import (EVAL_PATH_KNOBS, EVAL_PATHS, NOFLAT_PATHS, TIGHT, assert_flat_as_named, assert_record_matches_oracle,
+                     oracle_plan_for_request, request_from_golden, request_from_instance, set_eval_path, took_flat,
+                     waypoints_are_flat)
 from integrated_path_planning_amd import _abi, synthetic as syn
 from integrated_path_planning_amd.footprint import EgoFootprint
 from integrated_path_planning_amd.planner import BatchPlanner
@@ -43,21 +50,34 @@ def assert_same_tables(a, b, label):
             np.testing.assert_array_equal(x, y, err_msg=f"{label} inst {i}: {name} (lean against general)")
 
 
-def both_forms(bp, reqs, label, **kw):
-    """plan `reqs` in the lean form (what the call takes by itself) and with the general form forced"""
+def both_forms(bp, reqs, label, eval_path, flat_path, **kw):
+    """plan `reqs` under `eval_path` as the call runs by itself -- the flat form where every path is exactly straight
+    (`flat_path`), the name allows it and its shape has a flat kernel, else the lean form --, where that was a flat
+    launch again with the flat form held back (set_flat(0): the lean kernel), and with the general form forced.  Each
+    launch is asserted to have run the kernel it stands for; records byte-identical, tables equal."""
+    set_eval_path(bp, eval_path)
     bp.set_eval_form("auto")
-    lean = bp.plan_batch(reqs, **kw)
+    first = bp.plan_batch(reqs, **kw)
     assert bp.last_eval_form() == "lean", f"{label}: an eligible call ran the {bp.last_eval_form()} form"
-    t_lean = tables(bp, len(reqs))
+    assert_flat_as_named(bp, eval_path, flat_path, label)
+    was_flat = took_flat(bp)
+    legs = [("flat" if was_flat else "lean", first, tables(bp, len(reqs)))]
+    if was_flat:
+        bp.set_flat(0)
+        lean = bp.plan_batch(reqs, **kw)
+        assert bp.last_eval_form() == "lean" and not took_flat(bp), f"{label}: set_flat(0) ran {bp.last_eval_form()}, flat {took_flat(bp)}"
+        legs.append(("lean", lean, tables(bp, len(reqs))))
     bp.set_eval_form("general")
     gen = bp.plan_batch(reqs, **kw)
-    assert bp.last_eval_form() == "general", label
-    t_gen = tables(bp, len(reqs))
+    assert bp.last_eval_form() == "general" and not took_flat(bp), label
+    legs.append(("general", gen, tables(bp, len(reqs))))
     bp.set_eval_form("auto")
-    for i in range(len(reqs)):
-        assert _rec_bytes(lean.records[i]) == _rec_bytes(gen.records[i]), f"{label} inst {i}: records differ"
-    assert_same_tables(t_lean, t_gen, label)
-    return lean
+    set_eval_path(bp, eval_path)
+    for name, res, tabs in legs[1:]:
+        for i in range(len(reqs)):
+            assert _rec_bytes(first.records[i]) == _rec_bytes(res.records[i]), f"{label} inst {i}: {legs[0][0]} and {name} records differ"
+        assert_same_tables(legs[0][2], tabs, f"{label} ({legs[0][0]} against {name})")
+    return first
 
 
 @pytest.mark.parametrize("eval_path", EVAL_PATHS)
@@ -66,7 +86,7 @@ def test_lean_equals_forced_general_on_config3(eval_path):
     bp = BatchPlanner(waypoints=WP, **syn.CONFIG3_PLANNER)
     set_eval_path(bp, eval_path)
     reqs = [request_from_instance(syn.config3_instance(s, S=20, P=30)) for s in range(8)]
-    res = both_forms(bp, reqs, f"config 3 [{eval_path}]", obstacle_dtype=np.float32)
+    res = both_forms(bp, reqs, f"config 3 [{eval_path}]", eval_path, True, obstacle_dtype=np.float32)
     assert res.status(1) == _abi.PLAN_NO_PATH and res.status(0) == _abi.PLAN_OK
     bp.close()
 
@@ -81,11 +101,40 @@ def test_lean_equals_forced_general_on_the_goldens_in_one_call(eval_path):
         r = request_from_golden(g)
         r.scenario = k
         reqs.append(r)
-    both_forms(bp, reqs, f"goldens [{eval_path}]")
+    all_flat = all(waypoints_are_flat(g["wx"], g["wy"]) for g in gs)
+    assert not all_flat and sum(waypoints_are_flat(g["wx"], g["wy"]) for g in gs) == 7     # (arc_singular and the crawls bend)
+    both_forms(bp, reqs, f"goldens [{eval_path}]", eval_path, all_flat)
     bp.plan_batch(reqs)                                      # (lean again: its tables against the reference's)
-    assert bp.last_eval_form() == "lean"
+    assert bp.last_eval_form() == "lean" and not took_flat(bp)
     for i, g in enumerate(gs):
         _check_table(bp, i, g, f"{g.name} lean [{eval_path}]")
+    bp.close()
+
+
+@pytest.mark.parametrize("eval_path", EVAL_PATHS)
+def test_flat_lean_and_general_on_the_straight_goldens_in_one_call(eval_path):
+    """The goldens of the list whose path is exactly straight, alone in a call: such a launch takes the flat form, so the
+    rare branches they reach (truncation at the path's end, NaN pedestrians, creep, standstill, emergency stop) are
+    walked by the flat kernel, by the lean kernel with the flat form held back, and by the general one; the lean
+    kernel's tables are then held to the reference's."""
+    gs = [g for g in (Golden(n) for n in GOLDENS) if waypoints_are_flat(g["wx"], g["wy"])]
+    assert [g.name for g in gs] == ["trunc_end", "trunc_end60", "nan_ped_dist", "nan_ped_single", "creep", "standstill",
+                                    "emergency_stop"]
+    bp = _mixed_handle(gs)
+    reqs = []
+    for k, g in enumerate(gs):
+        r = request_from_golden(g)
+        r.scenario = k
+        reqs.append(r)
+    both_forms(bp, reqs, f"straight goldens [{eval_path}]", eval_path, True)
+    for flat in (1, 0):
+        bp.set_flat(flat and EVAL_PATH_KNOBS[eval_path][2])
+        bp.plan_batch(reqs)
+        assert bp.last_eval_form() == "lean"
+        if not flat:
+            assert not took_flat(bp)
+        for i, g in enumerate(gs):
+            _check_table(bp, i, g, f"{g.name} {'as named' if flat else 'lean, flat form off'} [{eval_path}]")
     bp.close()
 
 
@@ -134,15 +183,20 @@ def plan_and_check(kws, reqs, expect, label):
     for k, kw in enumerate(kws[1:], start=1):
         assert bp.add_scenario(waypoints=WP, **kw) == k
     wants = oracle_plans(reqs, kws)
-    for path in ("auto", "group"):
+    for path in ("auto", "group", "group-noflat", "split-noflat"):       # (WP is straight: flat kernels, then lean ones)
         set_eval_path(bp, path)
         res = bp.plan_batch(reqs)
         assert bp.last_eval_form() == expect, f"{label} [{path}]: ran the {bp.last_eval_form()} form"
+        if expect == "lean":
+            assert_flat_as_named(bp, path, True, label)
+        else:
+            assert not took_flat(bp), f"{label} [{path}]: a general launch took a flat kernel"
         check_against_oracle(bp, res, wants, f"{label} [{path}]")
         singles = []
         for i, rq in enumerate(reqs):
             one = bp.plan_batch([rq])
             singles.append(bp.last_eval_form())
+            assert took_flat(bp) == (singles[-1] == "lean" and path in ("auto", "group")), f"{label} [{path}] inst {i} alone"
             assert _rec_bytes(one.records[0]) == _rec_bytes(res.records[i]), f"{label} [{path}] inst {i}: batch against single call"
     bp.close()
     return singles
@@ -239,7 +293,15 @@ def thresholds32(sq, bound):
     return float(thr), float(sure)
 
 
-@pytest.mark.parametrize("scene,want_tiles,cands", [("lean_64_63", [64, 63], (0, 62, 100, 126)), ("lean_3_1", [3, 1], (2, 3))])
+# The same two lattices on a path along +x (y exactly constant): there "auto" and "group" launch the flat kernels, whose
+# band lanes take the same re-check, and "group-noflat" / "split-noflat" the lean ones.  (The scenes above head 0.7 rad:
+# never flat, asserted.)
+for _name in ("lean_64_63", "lean_3_1"):
+    SCENES.setdefault(_name + "_x", (straight(0.0, 250.0),) + SCENES[_name][1:])
+
+
+@pytest.mark.parametrize("scene,want_tiles,cands", [("lean_64_63", [64, 63], (0, 62, 100, 126)), ("lean_3_1", [3, 1], (2, 3)),
+                                                    ("lean_64_63_x", [64, 63], (0, 62, 100, 126)), ("lean_3_1_x", [3, 1], (2, 3))])
 def test_band_lanes_on_tiles_of_1_63_and_64_candidates(scene, want_tiles, cands):
     """Static obstacles whose float32 distance to a candidate's point falls between the sink's two thresholds, so that
     the lane leaves the min-only walk for the per-chunk walk and the float64 re-check: one float32 ulp of the radius
@@ -272,10 +334,14 @@ def test_band_lanes_on_tiles_of_1_63_and_64_candidates(scene, want_tiles, cands)
     # (half of the placements lie inside the radius of their own candidate's point, half outside; neighbours may be hit)
     n_hit = sum(int(w[c] == _abi.ST_COLLISION) for w, c in zip(want, target))
     assert len(reqs) // 4 <= n_hit <= 3 * len(reqs) // 4, f"{scene}: {n_hit} of {len(reqs)} placements hit their candidate"
-    for path in ("wave", "auto", "group"):
+    flat_path = waypoints_are_flat(*SCENES[scene][0])
+    assert flat_path == scene.endswith("_x")
+    assert len(reqs) * len(want_tiles) <= 2304                   # ("auto": a split launch)
+    for path in ("wave", "auto", "group") + (NOFLAT_PATHS if flat_path else ()):
         set_eval_path(sc.bp, path)
         sc.bp.plan_batch(reqs)
         assert sc.bp.last_eval_form() == "lean", f"{scene} [{path}]"
+        assert_flat_as_named(sc.bp, path, flat_path, scene)
         for i, w in enumerate(want):
             _, status, _, _ = sc.bp.candidates(i)
             bad = np.flatnonzero(status != w)

@@ -39,7 +39,9 @@ import pytest
 
 import eps_band
 import limit_boundaries_common as lb
-from helpers import EVAL_PATHS, assert_record_matches_oracle, set_eval_path
+# (an arc and a line heading 0.4 rad: no path here is exactly straight, so no launch takes a flat kernel -- asserted after
+# each plan call -- and helpers' "-noflat" names would repeat "group" and "split-wave")
+from helpers import EVAL_PATHS_NEVER_FLAT as EVAL_PATHS, assert_no_flat_launch, assert_record_matches_oracle, set_eval_path
 from integrated_path_planning_amd import _abi
 from integrated_path_planning_amd.planner import BatchPlanner
 
@@ -172,6 +174,7 @@ def test_limits_at_the_boundary_match_the_oracle(emu, name):
                 took = h.bp.last_eval_form()
                 lean_ok = form == "auto" and sc.n_total <= 64
                 assert took == ("lean" if lean_ok else "general"), f"{name} [{path}, {form}]: the launch took the {took} form"
+                assert_no_flat_launch(h.bp, f"{name} [{path}, {form}]")
                 judge(sc, h.bp, insts, res, f"{path}, {form}", applied, first)
                 if first is None:
                     first = [rec_bytes(res.records[i]) for i in range(len(insts))]
@@ -196,6 +199,7 @@ def test_brake_ladder_gate(emu):
             for form in FORMS:
                 h.bp.set_eval_form(form)
                 res = h.bp.plan_batch([inst.req for inst in insts])
+                assert_no_flat_launch(h.bp, f"gate [{path}, {form}]")
                 for i, inst in enumerate(insts):
                     label = f"gate inst {i} [{path}, {form}] {inst.label()}"
                     rec = res.records[i]
@@ -240,6 +244,7 @@ def test_mixed_launch_gives_the_per_scene_records(emu):
         for path in EVAL_PATHS:
             set_eval_path(mixed.bp, path)
             res = mixed.bp.plan_batch([inst.req for inst in insts])
+            assert_no_flat_launch(mixed.bp, f"mixed [{path}]")
             for i, (n, j) in enumerate(order):
                 assert rec_bytes(res.records[i]) == want[n][j], \
                     f"mixed inst {i} [{path}] = {n} inst {j} {insts[i].label()}: record differs from the per-scene launch's"

@@ -102,6 +102,28 @@ def test_reference_episode_resident_and_equal_to_stepwise(episodes, name, tmp_pa
         _assert_same_predictions(res, stp)
 
 
+@pytest.mark.parametrize("name", ["fast", "rnd5", "inflate"])
+def test_straight_road_episode_on_the_lean_kernel_and_on_the_flat_one(episodes, name):
+    """Ten of the thirteen reference episodes drive an exactly straight road, where the loop's plan calls -- one
+    episode is a small batch: a split launch -- take k_evaluate_split_lean_flat; k_evaluate_split_lean, which every bent
+    road runs, then meets the reference in closed loop on `turn`, `rnd2` and `rnd4` alone.  Three short straight
+    episodes with the flat form off (set_flat(0) on the loop's handle): the reference's steps and termination, and byte
+    for byte what the same episode leaves at the default, where the flat kernel ran."""
+    cfg = scenario_config(episodes["meta"], name)
+    tracks = [episodes[name + "_ped_traj"]]
+    with BatchedClosedLoop(cfg, tracks, resident=True) as lean, BatchedClosedLoop(cfg, tracks, resident=True) as flat:
+        assert lean._resident and flat._resident
+        lean.engine.set_flat(0)
+        s_lean, s_flat = _spy_s_now(lean), _spy_s_now(flat)
+        hists = lean.run()
+        assert lean.engine.last_eval_form() == "lean" and not lean.engine.set_flat(-1), f"{name}: set_flat(0) before run()"
+        assert_episode_matches(hists[0], lean.episodes[0].termination_reason, episodes, name)
+        flat.run()
+        assert flat.engine.last_eval_form() == "lean" and flat.engine.set_flat(-1), f"{name}: the default took no flat kernel"
+        _assert_same_bytes(lean, flat, s_lean, s_flat, label=name)
+        _assert_same_predictions(lean, flat)
+
+
 def _crowds(episodes):
     """52 episodes on the base scenario: six recorded crowds, each as it is, shifted sideways and along the road,
     cut short (the last frame is then held), thinned out; one episode without pedestrians; standing crowds."""

@@ -7,7 +7,7 @@ import pytest
 
 import eps_band
 from conftest import Golden, golden_names
-from helpers import EVAL_PATHS, TIGHT, request_from_golden, set_eval_path
+from helpers import EVAL_PATHS_NEVER_FLAT as EVAL_PATHS, TIGHT, assert_no_flat_launch, request_from_golden, set_eval_path
 from integrated_path_planning_amd import _abi, synthetic as syn
 from integrated_path_planning_amd.batch import PackedBatch, request_from_instance
 from integrated_path_planning_amd.params import DT, MAX_T, make_params
@@ -84,6 +84,8 @@ def test_every_golden_in_one_call(grid_goldens, single_records, eval_path):
         r.scenario = int(k)
         reqs.append(r)
     res = bp.plan_batch(reqs)
+    # (bent paths among the goldens of the call: no flat kernel, so helpers' "-noflat" names would repeat two of these)
+    assert_no_flat_launch(bp, f"every golden in one call [{eval_path}]")
     for i, k in enumerate(order):
         g = grid_goldens[k]
         assert _rec_bytes(res.records[i]) == single_records[k][0], f"{g.name} [{eval_path}]"

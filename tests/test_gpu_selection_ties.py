@@ -31,7 +31,8 @@ import numpy as np
 import pytest
 
 import selection_ties_common as st
-from helpers import EVAL_PATHS, TIGHT, assert_record_matches_oracle, set_eval_path
+from helpers import (EVAL_PATHS, TIGHT, assert_flat_as_named, assert_record_matches_oracle, set_eval_path, took_flat,
+                     waypoints_are_flat)
 from integrated_path_planning_amd import _abi
 from integrated_path_planning_amd.batch import PackedBatch, PlanRequest
 from integrated_path_planning_amd.planner import BatchPlanner
@@ -106,6 +107,10 @@ def test_selection_at_ties(prem, case, path):
             took = bp.last_eval_form()
             lean_ok = form == "auto" and case.n_total <= 64
             assert took == ("lean" if lean_ok else "general"), f"{case.label()} [{path}, {form}]: the launch took the {took} form"
+            if lean_ok:                                      # flat kernels on the straight cases, the lean ones by name
+                assert_flat_as_named(bp, path, waypoints_are_flat(*case.waypoints), case.label(), small_batch=len(case.reqs) <= 8)
+            else:
+                assert not took_flat(bp), f"{case.label()} [{path}, {form}]"
             for i, (p, want) in enumerate(zip(prem[case.name], case.wants)):
                 lab = f"{case.label(i)} [{path}, {form}] oracle winner {want.best_index} device {res.records[i].best_index}"
                 judge(case, i, p, res.records[i], bp.candidates(i, cap=CAP), want, lab)
