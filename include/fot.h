@@ -41,7 +41,10 @@ extern "C" {
 #define FOT_MAX_TI 64        /* time horizons  int((max_t-min_t)/dt)+1  (min_t = 1 s at max_t = 5 s, dt = 0.1 s: 41) */
 #define FOT_MAX_TV 32        /* terminal speeds per horizon */
 #define FOT_MAX_BRAKE 32     /* brake-ladder entries 0.5 s, 1.0 s, ... < min_t (frenet_planner.py:475): min_t <= 16.4 s */
-#define FOT_MAX_SAMPLES 64   /* prediction samples S of a distribution */
+#define FOT_MAX_SAMPLES 64   /* prediction samples S of a distribution: a fresh handle's capacity, and the capacity of
+                                the prediction, sampler and closed-loop entries whatever the handle's */
+#define FOT_MAX_PLAN_SAMPLES 254  /* ... what fot_set_sample_capacity can raise a handle's plan path to: sample ids travel as
+                                uint8_t with 255 for a static obstacle, and 254 samples are four 64-bit mask words */
 
 /* error codes */
 #define FOT_OK 0
@@ -286,8 +289,24 @@ int fot_debug_set_tile_cut(fot_handle *h, int32_t cut);
  * same decisions, byte-identical records.  form = 1 makes the handle's later plan calls run the general form whatever
  * they are eligible for, 0 restores the choice by eligibility, -1 changes nothing.  Returns (>= 0) the forms the launches
  * of the handle's most recent plan call took -- 0: none yet, 1: general, 2: lean, 3: both (a batch split into lanes) --
- * or a negative FOT_ERR_*. */
+ * or a negative FOT_ERR_*.  A wide launch (fot_set_sample_capacity: an instance of more than FOT_MAX_SAMPLES samples)
+ * adds 4 (the general form with a four-word sample mask) or 8 (the lean form) instead of 1 or 2. */
 int fot_debug_set_eval_form(fot_handle *h, int32_t form);
+
+/* The sample capacity of the handle's plan path: the largest S of a prediction distribution that fot_plan_batch,
+ * fot_plan_batch_device, their _scenarios forms, fot_check_collision_paths and fot_check_paths accept; beyond it they
+ * return FOT_ERR_UNSUPPORTED.  A fresh handle has FOT_MAX_SAMPLES.  fot_set_sample_capacity accepts FOT_MAX_SAMPLES <=
+ * n_samples <= FOT_MAX_PLAN_SAMPLES; anything else is FOT_ERR_INVALID and leaves the handle as it was.  The capacity is
+ * the handle's, for all its scenarios.  A launch with an instance of more than FOT_MAX_SAMPLES samples is WIDE: it runs
+ * evaluation kernels of its own that count distinct samples in four mask words (lean-eligible launches: kernels that
+ * need no sample ids) and has no flat form.  Every other launch runs the kernels it ran before, raised capacity or not.
+ * The fot_debug_* entries work after a wide launch.  The closed-loop, sampler, score and open-loop entries (fot_loop_*,
+ * fot_sgan_*, fot_prediction_scores, fot_openloop_eval) keep FOT_MAX_SAMPLES.
+ * fot_max_plan_samples: the FOT_MAX_PLAN_SAMPLES the library was built with, for a binding to compare with its own.
+ * Additions: no structure, capacity word of fot_abi_info or FOT_ABI_VERSION changes; a binding looks the symbols up. */
+int fot_set_sample_capacity(fot_handle *h, int32_t n_samples);
+int fot_get_sample_capacity(const fot_handle *h, int32_t *out);
+int32_t fot_max_plan_samples(void);
 
 /* Test hook.  The lean evaluation kernels have a flat form for reference paths that are exactly straight: one coordinate
  * of the path's spline has all first-, second- and third-derivative coefficients exactly zero and the other is finite

@@ -14,6 +14,7 @@ MAX_NT = 256
 MAX_CIRCLES = 8
 CHECK_RULE_LENS = 6                      # FOT_CHECK_RULE_LENS: n_geo, len d, v, a, c, s per path of fot_check_paths
 MAX_SAMPLES = 64
+MAX_PLAN_SAMPLES = 254                   # FOT_MAX_PLAN_SAMPLES: what fot_set_sample_capacity can raise a handle to
 
 OK = 0
 ERR_INVALID, ERR_UNSUPPORTED, ERR_HIP, ERR_NO_PATH_SET = -1, -2, -3, -4
@@ -244,7 +245,8 @@ SYMBOLS = ["fot_version", "fot_abi_info", "fot_create", "fot_destroy", "fot_live
            "fot_sgan_max_models", "fot_sgan_load_model", "fot_sgan_unload_model", "fot_sgan_sample_model",
            "fot_loop_set_sampler_models", "fot_debug_loop_sampler_shapes", "fot_openloop_eval",
            "fot_footprint_recheck", "fot_loop_footprint_enable", "fot_loop_footprint_obs", "fot_fidelity_eval",
-           "fot_encounters_extract"]
+           "fot_encounters_extract", "fot_set_sample_capacity", "fot_get_sample_capacity",
+           "fot_max_plan_samples"]
 LOOP_PLAN_DISTRIBUTION, LOOP_PLAN_REPRESENTATIVE = 0, 1      # FOT_LOOP_PLAN_* (fot_loop_plan_sample)
 PROFILE_KERNELS = 3                      # FOT_PROFILE_KERNELS (include/fot.h)
 ABI_VERSION = 8                          # FOT_ABI_VERSION
@@ -303,6 +305,10 @@ def _check_abi(L, path):
     bad = [f"{ABI_WORD_NAMES[i]}: library {got[i]}, binding {want[i]}" for i in range(min(n, len(want))) if got[i] != want[i]]
     if n != len(want):
         bad.append(f"the library reports {n} ABI words, the binding knows {len(want)}")
+    # (FOT_MAX_PLAN_SAMPLES is no word of fot_abi_info: the library reports it through a function of its own; a library
+    #  that predates it loads, as the A side of an A/B against an older build)
+    if hasattr(L, "fot_max_plan_samples") and L.fot_max_plan_samples() != MAX_PLAN_SAMPLES:
+        bad.append(f"FOT_MAX_PLAN_SAMPLES: library {L.fot_max_plan_samples()}, binding {MAX_PLAN_SAMPLES}")
     if bad:
         raise ImportError(f"{path} does not match this binding (include/fot.h changed since it was built?): "
                           + "; ".join(bad))
@@ -456,7 +462,9 @@ def lib():
                        ("fot_loop_begin_scenarios", [vp, C.c_int32, C.c_int32, vp, vp, vp, vp]),
                        ("fot_loop_set_scenario_static", [vp, C.c_int32, C.c_int32, vp]),
                        ("fot_debug_set_eval_form", [vp, C.c_int32]),
-                       ("fot_debug_set_flat", [vp, C.c_int32])):
+                       ("fot_debug_set_flat", [vp, C.c_int32]),
+                       ("fot_set_sample_capacity", [vp, C.c_int32]),
+                       ("fot_get_sample_capacity", [vp, ip])):
         if hasattr(L, name):
             getattr(L, name).argtypes = args
     L.fot_synchronize.argtypes = [vp]

@@ -2,7 +2,9 @@
 // k_evaluate_group (FOT_EVAL_LEAN false: the general form), as k_evaluate_lean / k_evaluate_split_lean /
 // k_evaluate_group_lean (FOT_EVAL_LEAN true: FusedSink<true>) and as k_evaluate_split_lean_flat /
 // k_evaluate_group_lean_flat (FOT_EVAL_FLAT true on top: the walk of exactly straight reference paths,
-// frenet_to_cart<., true>).  The per-wave kernel has no flat form: it came out with one lane-spilled scalar register
+// frenet_to_cart<., true>); and twice more with FOT_EVAL_WORDS = WIDE_MASK_WORDS, as k_evaluate_wide / _split_wide /
+// _group_wide and k_evaluate_lean_wide / _split_lean_wide / _group_lean_wide: the launches with an instance of more than
+// FOT_MAX_SAMPLES prediction samples (FusedSink<., WIDE_MASK_WORDS>).  The per-wave kernel has no flat form: it came out with one lane-spilled scalar register
 // more than k_evaluate_lean (10 against 9), and a flat-eligible launch of that shape runs k_evaluate_lean.
 // Inclusions rather than a template body behind wrappers: each kernel
 // then reads its argument struct in place, exactly as the single form did (through a wrapper the struct is copied and
@@ -66,7 +68,7 @@ FOT_EVAL_KERNEL(k_evaluate)(const DevParams *__restrict__ Pp, const InstDesc *__
     if (inst < 0) return;
     const int n_tiles = desc[inst].n_tiles;
     TilePart tp = tile_part_empty();
-    evaluate_tile<TILE_WAVE, FOT_EVAL_LEAN, FOT_EVAL_FLAT>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, my_rows, inst,
+    evaluate_tile<TILE_WAVE, FOT_EVAL_LEAN, FOT_EVAL_FLAT, FOT_EVAL_WORDS>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, my_rows, inst,
                          n_tiles - 1 - pos, lane, x, tp);
     tile_done(inst, n_tiles - 1 - pos, lane, tp);
 }
@@ -97,10 +99,10 @@ FOT_EVAL_KERNEL(k_evaluate_split)(const DevParams *__restrict__ Pp, const InstDe
     if (pos >= n_tiles) return;
     SplineView sp_hbm = a.sp;
     if (a.mixed) { Pp += desc[inst].scen; sp_hbm = load_const(a.sp_table, desc[inst].scen); }
-    const SplineView sp_lds = stage_spline(sp_hbm, a.lds_knots, s_part + (SEG_MAX - 1) * SEG_DOUBLES);
+    const SplineView sp_lds = stage_spline(sp_hbm, a.lds_knots, s_part + (SEG_MAX - 1) * seg_doubles(FOT_EVAL_LEAN ? 1 : FOT_EVAL_WORDS));
     const int tile = n_tiles - 1 - pos;
     TilePart tp = tile_part_empty();
-    evaluate_tile<TILE_SPLIT, FOT_EVAL_LEAN, FOT_EVAL_FLAT>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, s_lon, inst, tile, lane, x,
+    evaluate_tile<TILE_SPLIT, FOT_EVAL_LEAN, FOT_EVAL_FLAT, FOT_EVAL_WORDS>(Pp, desc, state, tile_cand0, tile_n, wave_rng, ent32, a, sp_lds, s_lon, inst, tile, lane, x,
                               tp, seg, n_seg, s_part);
     if (seg == 0) tile_done(inst, tile, lane, tp);               // (the wave that merged the segments and holds the results)
 }
@@ -111,7 +113,11 @@ FOT_EVAL_KERNEL(k_evaluate_split)(const DevParams *__restrict__ Pp, const InstDe
 #ifndef FOT_GROUP_WAVES
 #define FOT_GROUP_WAVES 4
 #endif
-__global__ void __launch_bounds__(GROUP_TILES * WAVE) __attribute__((amdgpu_waves_per_eu(FOT_GROUP_WAVES, FOT_GROUP_WAVES)))
+// (FOT_EVAL_GROUP_WAVES: FOT_GROUP_WAVES, but for the one inclusion that needs another figure -- see fot_kernels.hip)
+#ifndef FOT_EVAL_GROUP_WAVES
+#define FOT_EVAL_GROUP_WAVES FOT_GROUP_WAVES
+#endif
+__global__ void __launch_bounds__(GROUP_TILES * WAVE) __attribute__((amdgpu_waves_per_eu(FOT_EVAL_GROUP_WAVES, FOT_EVAL_GROUP_WAVES)))
 FOT_EVAL_KERNEL(k_evaluate_group)(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc,
                  const InstState *__restrict__ state, const int32_t *__restrict__ tile_cand0,
                  const int32_t *__restrict__ tile_n, const TileStep *__restrict__ wave_rng,
@@ -156,8 +162,8 @@ FOT_EVAL_KERNEL(k_evaluate_group)(const DevParams *__restrict__ Pp, const InstDe
     const int tile0 = __builtin_amdgcn_readfirstlane(s_head->grp_tile0);
     TilePart tp = tile_part_empty();
     // (GROUP_HEAD_EMPTY -- no Frenet state, or the brake ladder of a standing ego: the tiles count as done, nothing found)
-    evaluate_group_tile<FOT_EVAL_LEAN, FOT_EVAL_FLAT>(Pp, desc, wave_rng, ent32, a, sp_lds, s_lon, inst, tile0 + wv, wv, lane, x, tp,
+    evaluate_group_tile<FOT_EVAL_LEAN, FOT_EVAL_FLAT, FOT_EVAL_WORDS>(Pp, desc, wave_rng, ent32, a, sp_lds, s_lon, inst, tile0 + wv, wv, lane, x, tp,
                                        present == GROUP_HEAD_FULL);
     tile_done(inst, tile0 + wv, lane, tp);
 }
-
+#undef FOT_EVAL_GROUP_WAVES

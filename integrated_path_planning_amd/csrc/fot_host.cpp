@@ -227,7 +227,7 @@ int enqueue_lane(fot_handle *h, Workspace &w, const fot_batch &b, const int32_t 
 {
     BatchLayout &L = w.last;
     std::string err;
-    int rc = build_batch_layout(h->refs.data(), (int)h->refs.size(), scen, b, L, err);
+    int rc = build_batch_layout(h->refs.data(), (int)h->refs.size(), scen, b, L, err, h->sample_cap);
     if (rc != FOT_OK) return fail(h, rc, err);
     if (L.n_inst == 0) return FOT_OK;
 
@@ -274,11 +274,15 @@ int enqueue_lane(fot_handle *h, Workspace &w, const fot_batch &b, const int32_t 
     tt.lean = h->eval_form == 0 ? 1 : 0;
     for (const Scenario &S : h->sc) if (S.P.n_total > WAVE || S.P.has_footprint) tt.lean = 0;
     for (int i = 0; i < L.n_inst && tt.lean; ++i) if (L.desc[(size_t)i].max_viol != 0) tt.lean = 0;
-    h->last_eval_forms |= tt.lean ? 2 : 1;
+    // A wide launch: an instance of more than FOT_MAX_SAMPLES samples (only on a handle whose capacity was raised).  The
+    // same rule picks its form; it has kernels of its own (FusedSink<., WIDE_MASK_WORDS>) and no flat form.  Every other
+    // launch, raised capacity or not, goes where it went before.
+    tt.wide = L.max_S > FOT_MAX_SAMPLES ? 1 : 0;
+    h->last_eval_forms |= tt.wide ? (tt.lean ? 8 : 4) : tt.lean ? 2 : 1;
     // Their flat forms: every path the launch's instances use is exactly straight.  Decided from the paths' coefficients
     // (Scenario::flat_path) -- the lateral states need no test: frenet_to_cart<., true> keeps the one multiply-add
     // that poisons a sample whose d is not finite, as the general form's 1 - kr d does.
-    tt.flat = tt.lean && h->flat_mode != 0 ? 1 : 0;
+    tt.flat = tt.lean && !tt.wide && h->flat_mode != 0 ? 1 : 0;
     if (L.scens.empty()) { if (!h->sc[0].flat_path) tt.flat = 0; }
     for (int s : L.scens) if (!h->sc[(size_t)s].flat_path) tt.flat = 0;
     h->last_flat |= evaluate_flat(tt) ? 1 : 0;
@@ -392,7 +396,7 @@ int check_ext(fot_handle *h, int mode, int32_t n_paths, const int32_t *len, cons
     b.static_xy = static_xy; b.static_off = soff; b.dyn_xy = dyn; b.dyn_off = doff; b.dyn_dims = dims;
     BatchLayout L;
     std::string err;
-    int rc = build_batch_layout(h->sc[0].params, P, h->sc[0].shapes, b, L, err);
+    int rc = build_batch_layout(h->sc[0].params, P, h->sc[0].shapes, b, L, err, h->sample_cap);
     if (rc != FOT_OK) return fail(h, rc, err);
     h->last_valid = false;
 
@@ -443,7 +447,7 @@ int check_ext(fot_handle *h, int mode, int32_t n_paths, const int32_t *len, cons
     HIP_TRY(h, hipMemcpyAsync(h->dTmpC.p, meta.data(), sizeof(int32_t) * meta.size(), hipMemcpyHostToDevice, st));
     LAUNCH_TRY(h, launch_check_ext(h->dP.as<DevParams>(), h->dTmpA.as<InstDesc>(), n_paths, mode, h->dTmpC.as<int32_t>(),
                                    h->dTmpC.as<int32_t>() + np, h->dTmpB.as<double>(), h->dUserStatic.as<double>(),
-                                   h->dUserDyn.as<double>(), h->dTmpD.as<int32_t>(), st));
+                                   h->dUserDyn.as<double>(), h->dTmpD.as<int32_t>(), st, L.max_S > FOT_MAX_SAMPLES ? 1 : 0));
     HIP_TRY(h, hipMemcpyAsync(status_out, h->dTmpD.p, sizeof(int32_t) * np, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     return FOT_OK;
@@ -873,7 +877,7 @@ int fot_plan_batch_scenarios(fot_handle *h, const fot_batch *batch, const int32_
     // extents of the caller's obstacle arrays
     BatchLayout probe;
     std::string err;
-    int rc = build_batch_layout(h->refs.data(), (int)h->refs.size(), scenario, *batch, probe, err);
+    int rc = build_batch_layout(h->refs.data(), (int)h->refs.size(), scenario, *batch, probe, err, h->sample_cap);
     if (rc != FOT_OK) return fail(h, rc, err);
     const size_t elem = batch->obstacle_dtype == FOT_F32 ? sizeof(float) : sizeof(double);
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1154,6 +1158,24 @@ int fot_debug_set_eval_form(fot_handle *h, int32_t form)
         return fail(h, FOT_ERR_INVALID, "fot_debug_set_eval_form: 0 (by eligibility), 1 (general form), -1 (query only)");
     if (form >= 0) h->eval_form = form;
     return h->last_eval_forms;
+}
+
+int fot_set_sample_capacity(fot_handle *h, int32_t n_samples)
+{
+    if (!h) return FOT_ERR_INVALID;
+    if (n_samples < FOT_MAX_SAMPLES || n_samples > FOT_MAX_PLAN_SAMPLES)
+        return fail(h, FOT_ERR_INVALID, "fot_set_sample_capacity: FOT_MAX_SAMPLES (64) .. FOT_MAX_PLAN_SAMPLES (254) samples");
+    h->sample_cap = n_samples;
+    return FOT_OK;
+}
+
+int32_t fot_max_plan_samples(void) { return FOT_MAX_PLAN_SAMPLES; }
+
+int fot_get_sample_capacity(const fot_handle *h, int32_t *out)
+{
+    if (!h || !out) return FOT_ERR_INVALID;
+    *out = h->sample_cap;
+    return FOT_OK;
 }
 
 int fot_debug_set_flat(fot_handle *h, int32_t on)

@@ -371,6 +371,8 @@ struct fot_handle {
     int tile_cut = 0;                    // fot_debug_set_tile_cut (TILE_CUT_*)
     int eval_form = 0;                   // fot_debug_set_eval_form: 0 = by eligibility, 1 = the general form always
     int last_eval_forms = 0;             // forms the launches of the most recent plan call took: 1 general | 2 lean
+                                         // | 4 general, wide | 8 lean, wide
+    int sample_cap = FOT_MAX_SAMPLES;    // fot_set_sample_capacity: most samples of a distribution the plan path accepts
     int flat_mode = 1;                   // fot_debug_set_flat: 1 = flat kernels where a launch is eligible, 0 = never
     int last_flat = 0;                   // 1: a launch of the most recent plan call took a flat kernel
     std::vector<Scenario> sc;                // scenarios; sc[0]: fot_create's params + fot_set_path_*

@@ -79,6 +79,8 @@ struct TileTable {
                                         // the single centre circle, no chance budget on any instance (enqueue_lane)
     int flat = 0;                       // ... and their flat forms: lean, and every path of the launch is exactly straight
                                         // (Scenario::flat_path)
+    int wide = 0;                       // an instance of the launch has more than FOT_MAX_SAMPLES prediction samples (a handle
+                                        // with a raised sample capacity): the *_wide evaluation kernels; never with `flat`
     GroupHead *heads = nullptr;         // [n_inst][max_tiles / GROUP_TILES] group headers, where evaluate_in_groups()
 };
 // the evaluation of this batch goes to the grouped kernels (launch_evaluate): k_frenet_state then builds their headers
@@ -139,6 +141,6 @@ int launch_pack_wire(int n, int n_total, int stride, const fot_result *src, unsi
 int launch_spline_eval(SplineView sp, int n, const double *s, double *out, hipStream_t st);
 int launch_check_ext(const DevParams *P, const InstDesc *desc, int n_paths, int mode, const int32_t *len,
                      const int32_t *rule_len, const double *arrays, const double *static_xy, const double *dyn_xy,
-                     int32_t *status_out, hipStream_t st);
+                     int32_t *status_out, hipStream_t st, int wide = 0);   // wide: desc[0].S > FOT_MAX_SAMPLES
 
 }  // namespace fot

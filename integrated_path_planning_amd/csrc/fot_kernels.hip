@@ -615,8 +615,13 @@ __device__ __forceinline__ const EvalKernArgs &eval_kernargs()
 // register, lane read or branch for it --, hit_mask / viol are never touched (the exact re-check counts on locals: its
 // first violation is a hit), and the per-step values never need a second block of 64 steps.  Same thresholds, same
 // min-only walk, same per-chunk walk of the band lanes, same exact re-check: the decisions are the general form's.
-template <bool LEAN>
+// W: the words of the sample mask.  1 in every launch whose instances have at most FOT_MAX_SAMPLES samples; the WIDE
+// launches (an instance of up to FOT_MAX_PLAN_SAMPLES samples on a handle with a raised capacity) take WIDE_MASK_WORDS: the
+// general form then counts distinct samples in a SampleMask4 (four register pairs, touched by the exact re-check alone,
+// word chosen by a select chain -- no indexed array, no scratch), the lean form re-checks without looking at sample ids.
+template <bool LEAN, int W = 1>
 struct FusedSink {
+    typedef typename SampleMaskOf<LEAN ? 1 : W>::type Mask;
     const DevParams *Pp;
     const InstDesc *Dp;
     // The per-step values of the tile (TileStep) sit in lanes: lane l holds time step step_base + l, 64 steps at a time;
@@ -631,7 +636,7 @@ struct FusedSink {
     float thr, thr_fatal;                // of the current time step (wave-uniform)
     const f2x8 *chunks;                  // float32 entries of this instance, ent_cap / 8 chunks per time step
     int chunks_per_k;                    // ent_cap / 8
-    uint64_t hit_mask;
+    Mask hit_mask;
     int viol;
     bool hit;
     int c_lo, n_chunks;                  // chunk range of the current time step
@@ -767,7 +772,10 @@ struct FusedSink {
             const int hb = 31 - __clz((int)near_bits);             // highest bit = earliest chunk
             near_bits &= ~(1u << hb);
             const int64_t e = base + (int64_t)(c0 + nb - 1 - hb) * ENT_CHUNK;
-            if constexpr (LEAN)
+            if constexpr (LEAN && W != 1)                           // (ids of 64 and more: no one-word mask may see them)
+                exact_chunk_f32first_nobudget(chunks[e / ENT_CHUNK], e64 + e, sid + e, fx, fy, thr, thr_sure, px, py, P.sq_r,
+                                              sq_dyn, hit);
+            else if constexpr (LEAN)
                 exact_chunk_f32first(chunks[e / ENT_CHUNK], e64 + e, sid + e, fx, fy, thr, thr_sure, px, py, P.sq_r, sq_dyn,
                                      0, mask_l, viol_l, hit);
             else
@@ -803,7 +811,8 @@ __host__ __device__ constexpr int eval_group_doubles()
 // A tile cut into time segments (k_evaluate_split): what a later segment hands to the wave of segment 0, per lane
 constexpr int SEG_MAX = 4;
 constexpr int SEG_F64 = 4, SEG_I32 = 4;  // d_last, v_last, max_step2, hit_mask | flags, first_nan, k_last, hit
-constexpr int SEG_DOUBLES = (SEG_F64 + SEG_I32 / 2) * WAVE;
+// (the general form of a wide launch hands over WIDE_MASK_WORDS mask words: slots 3 .. 3 + words - 1, the ints behind them)
+__host__ __device__ constexpr int seg_doubles(int mask_words) { return (SEG_F64 + mask_words - 1 + SEG_I32 / 2) * WAVE; }
 
 // FLAT (the walk of an exactly straight path, frenet_to_cart<., true>): the step reads neither kr nor dkr of its row.
 template <bool FLAT = false>
@@ -932,7 +941,7 @@ __device__ __forceinline__ void tile_results(const DevParams &P, const InstDesc 
 //               (seg_merge) through `s_part`.
 // (The grouped cut has its own form, evaluate_group_tile below.)
 enum { TILE_WAVE = 0, TILE_SPLIT = 1 };
-template <int MODE, bool LEAN, bool FLAT = false>
+template <int MODE, bool LEAN, bool FLAT = false, int W = 1>
 __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc,
                                               const InstState *__restrict__ state,
                                               const int32_t *__restrict__ tile_cand0, const int32_t *__restrict__ tile_n,
@@ -1035,7 +1044,9 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
     seg_init(g);
     LonInfo L;
     StagedTabT<FLAT> tab;
-    uint64_t hit_mask = 0;
+    typedef typename FusedSink<LEAN, W>::Mask Mask;
+    constexpr int MASK_WORDS = LEAN ? 1 : W;                     // words of a segment's hand-over (seg_doubles)
+    Mask hit_mask = Mask();
     bool hit = false;
     int64_t slot = 0;
     double q[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };              // lateral quintic of the lane's candidate
@@ -1058,7 +1069,7 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
         // come back through v_readlane in every time step -- three vector registers are cheaper
         asm volatile("" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]));
 
-        FusedSink<LEAN> sink;
+        FusedSink<LEAN, W> sink;
         sink.Pp = Pp; sink.Dp = &D;
         sink.my_rng = my_rng;
         sink.my_thr = my_step.thr; sink.my_thr_sure = my_step.thr_sure; sink.thr = 0.0f; sink.thr_fatal = -1.0f;
@@ -1066,7 +1077,7 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
         sink.step_base = step_base0; sink.step_row = D.tile0 + tile; sink.lane_id = lane;
         sink.chunks = (const f2x8 *)(ent32 + D.ent_off);
         sink.chunks_per_k = D.ent_cap / ENT_CHUNK;
-        sink.hit_mask = 0; sink.viol = 0; sink.hit = false; sink.n_chunks = 0; sink.c_lo = 0; sink.pf = 0;
+        sink.hit_mask = Mask(); sink.viol = 0; sink.hit = false; sink.n_chunks = 0; sink.c_lo = 0; sink.pf = 0;
         sink.no_warm = (a.ablate & 2) != 0;
         // loop constants as opaque register values: the compiler then keeps them instead of re-fetching each one from
         // the parameter blocks, behind a scalar-memory wait, in every time step
@@ -1094,11 +1105,16 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
 #endif
     if constexpr (SPLIT) {
         // segments 1.. leave their state in LDS, the wave of segment 0 folds them in, in time order
-        double *pf = s_part + (seg - 1) * SEG_DOUBLES;
-        int *pi = (int *)(pf + SEG_F64 * WAVE);
+        double *pf = s_part + (seg - 1) * seg_doubles(MASK_WORDS);
+        int *pi = (int *)(pf + (SEG_F64 + MASK_WORDS - 1) * WAVE);
         if (seg > 0 && has_cand) {
             pf[0 * WAVE + lane] = g.d_last; pf[1 * WAVE + lane] = g.v_last;
-            pf[2 * WAVE + lane] = g.acc.max_step2; ((uint64_t *)pf)[3 * WAVE + lane] = hit_mask;
+            pf[2 * WAVE + lane] = g.acc.max_step2;
+            if constexpr (MASK_WORDS == 1) ((uint64_t *)pf)[3 * WAVE + lane] = hit_mask;
+            else {
+                ((uint64_t *)pf)[3 * WAVE + lane] = hit_mask.w0; ((uint64_t *)pf)[4 * WAVE + lane] = hit_mask.w1;
+                ((uint64_t *)pf)[5 * WAVE + lane] = hit_mask.w2; ((uint64_t *)pf)[6 * WAVE + lane] = hit_mask.w3;
+            }
             pi[0 * WAVE + lane] = (int)g.acc.fl; pi[1 * WAVE + lane] = g.first_nan;
             pi[2 * WAVE + lane] = g.k_last; pi[3 * WAVE + lane] = hit ? 1 : 0;
         }
@@ -1107,19 +1123,25 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
         if (has_cand) {
             for (int sg = 1; sg < n_seg; ++sg) {
                 if (sg * seg_len >= L.n_t) break;                // that segment held no sample of this candidate
-                const double *qf = s_part + (sg - 1) * SEG_DOUBLES;
-                const int *qi = (const int *)(qf + SEG_F64 * WAVE);
+                const double *qf = s_part + (sg - 1) * seg_doubles(MASK_WORDS);
+                const int *qi = (const int *)(qf + (SEG_F64 + MASK_WORDS - 1) * WAVE);
                 SegState nx;
                 nx.d_last = qf[0 * WAVE + lane]; nx.v_last = qf[1 * WAVE + lane];
                 nx.acc.max_step2 = qf[2 * WAVE + lane];
                 nx.acc.fl = (uint32_t)qi[0 * WAVE + lane]; nx.first_nan = qi[1 * WAVE + lane];
                 nx.k_last = qi[2 * WAVE + lane];
                 if (seg_merge(g, nx)) {
-                    hit_mask |= ((const uint64_t *)qf)[3 * WAVE + lane];
+                    if constexpr (MASK_WORDS == 1) hit_mask |= ((const uint64_t *)qf)[3 * WAVE + lane];
+                    else {
+                        const uint64_t *qm = (const uint64_t *)qf;
+                        const SampleMask4 o = { qm[3 * WAVE + lane], qm[4 * WAVE + lane], qm[5 * WAVE + lane], qm[6 * WAVE + lane] };
+                        mask_or(hit_mask, o);
+                    }
                     hit |= qi[3 * WAVE + lane] != 0;
                 }
             }
-            hit |= __popcll(hit_mask) > D.max_viol;
+            if constexpr (MASK_WORDS == 1) hit |= __popcll(hit_mask) > D.max_viol;
+            else hit |= mask_count(hit_mask) > D.max_viol;
         }
     }
     // The candidate's final status (stop-distance filter included, frenet_planner.py:307-324) and, per tile, what the
@@ -1168,7 +1190,7 @@ __device__ __forceinline__ void evaluate_tile(const DevParams *__restrict__ Pp, 
 // that no lane decides: it comes out of the group's header (GroupHead, built by k_frenet_state), which the caller has put
 // into LDS behind the rows, all waves behind a barrier.  The per-lane set-up is issued BEFORE the rows are built -- it
 // reads none -- so that its loads (the step ranges, the horizon's matrices) and integer divisions run under the build.
-template <bool LEAN, bool FLAT = false>
+template <bool LEAN, bool FLAT = false, int W = 1>
 __device__ __forceinline__ void evaluate_group_tile(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc,
                                                     const TileStep *__restrict__ wave_rng, const f2 *__restrict__ ent32,
                                                     const EvalKernArgs &a, const SplineView &sp_lds, double *my_rows,
@@ -1258,7 +1280,7 @@ __device__ __forceinline__ void evaluate_group_tile(const DevParams *__restrict_
     const int ne_min = SREG ? wave_min_i32(has_cand ? L.n_eval : INT_MAX) : 0;
     if (walks) {
         // the walk's wave-uniform state is set up HERE: scalar values do not survive the join of the region above
-        FusedSink<LEAN> sink;
+        FusedSink<LEAN, W> sink;
         sink.Pp = Pp; sink.Dp = &D;
         sink.my_rng = my_rng;
         sink.my_thr = my_step.thr; sink.my_thr_sure = my_step.thr_sure; sink.thr = 0.0f; sink.thr_fatal = -1.0f;
@@ -1267,7 +1289,7 @@ __device__ __forceinline__ void evaluate_group_tile(const DevParams *__restrict_
         const int64_t ent_off = ((int64_t)uni(((const int32_t *)&head->ent_off)[1]) << 32) | (uint32_t)uni(((const int32_t *)&head->ent_off)[0]);
         sink.chunks = (const f2x8 *)(ent32 + ent_off);
         sink.chunks_per_k = ent_cap / ENT_CHUNK;
-        sink.hit_mask = 0; sink.viol = 0; sink.hit = false; sink.n_chunks = 0; sink.c_lo = 0; sink.pf = 0;
+        sink.hit_mask = typename FusedSink<LEAN, W>::Mask(); sink.viol = 0; sink.hit = false; sink.n_chunks = 0; sink.c_lo = 0; sink.pf = 0;
         sink.no_warm = (a.ablate & 2) != 0;
         lc.n_circ_fp = 0;
         if constexpr (!LEAN) {                                   // (LEAN: the single centre circle, never read)
@@ -1464,6 +1486,7 @@ k_select_only(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ des
     }
 }
 
+#define FOT_EVAL_WORDS 1
 #define FOT_EVAL_LEAN false
 #define FOT_EVAL_FLAT false
 #define FOT_EVAL_KERNEL(name) name
@@ -1482,6 +1505,28 @@ k_select_only(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ des
 #undef FOT_EVAL_LEAN
 #undef FOT_EVAL_FLAT
 #undef FOT_EVAL_KERNEL
+#undef FOT_EVAL_WORDS
+// the wide forms (FusedSink<., WIDE_MASK_WORDS>): a launch with an instance of more than FOT_MAX_SAMPLES samples, on a
+// handle whose sample capacity was raised (TileTable::wide, enqueue_lane).  No flat form.
+#define FOT_EVAL_WORDS WIDE_MASK_WORDS
+#define FOT_EVAL_FLAT false
+#define FOT_EVAL_LEAN false
+#define FOT_EVAL_KERNEL(name) name##_wide
+// (the diagnostic -DFOT_TIMELINE build keeps its time stamps in registers beside the four mask words: k_evaluate_group_wide
+//  then does not fit the 128 registers of four waves per SIMD without scratch, and runs three -- that build only)
+#if defined(FOT_TIMELINE) && FOT_GROUP_WAVES > 3
+#define FOT_EVAL_GROUP_WAVES 3
+#endif
+#include "fot_eval_kernels.inc"
+#undef FOT_EVAL_LEAN
+#undef FOT_EVAL_KERNEL
+#define FOT_EVAL_LEAN true
+#define FOT_EVAL_KERNEL(name) name##_lean_wide
+#include "fot_eval_kernels.inc"
+#undef FOT_EVAL_LEAN
+#undef FOT_EVAL_FLAT
+#undef FOT_EVAL_KERNEL
+#undef FOT_EVAL_WORDS
 
 // ---------------------------------------------------------------------------
 // collision broad phase: entry lists
@@ -2116,6 +2161,66 @@ __global__ void k_check_ext(const DevParams *__restrict__ Pp, const InstDesc *__
     status_out[i] = st;
 }
 
+// The same against a distribution of more than FOT_MAX_SAMPLES samples (a handle with a raised sample capacity):
+// collide_candidate counts in a SampleMask4.  A copy of the body above, not a template both kernels share: k_check_ext
+// is then, instruction for instruction, the kernel it was before this one existed (scripts/isa_compare.py).
+__global__ void k_check_ext_wide(const DevParams *__restrict__ Pp, const InstDesc *__restrict__ desc, int n_paths, int mode,
+                                 const int32_t *__restrict__ len, const int32_t *__restrict__ rule_len,
+                                 const double *__restrict__ arrays, const double *__restrict__ static_xy,
+                                 const double *__restrict__ dyn_xy, int32_t *__restrict__ status_out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_paths) return;
+    const DevParams &P = *Pp;
+    const InstDesc &D = desc[0];
+    const int64_t plane = (int64_t)n_paths * FOT_MAX_NT;
+    const double *row = arrays + (int64_t)i * FOT_MAX_NT;
+    const double *ax = row, *ay = row + plane, *ayaw = row + 2 * plane, *av = row + 3 * plane, *aa = row + 4 * plane,
+                 *ac = row + 5 * plane, *ad = row + 6 * plane, *as = row + 7 * plane, *at = row + 8 * plane;
+    const int n = len[i];
+    PathArraySource src;
+    src.x = ax; src.y = ay; src.yaw = ayaw; src.t = at; src.dt = P.dt;
+    src.circ_off = P.circ_off; src.has_footprint = P.has_footprint;
+    ObstacleView obs;
+    obs.stat = static_xy; obs.dyn = dyn_xy; obs.dtype = FOT_F64;
+    // a NaN in any collision point makes the reference's path box NaN, which no obstacle is inside (np.min / np.max
+    // propagate it, frenet_planner.py:1177-1178): such a path collides with nothing, at any of its samples
+    bool nan_point = false;
+    const int n_circ = P.has_footprint ? P.n_circ : 1;
+    for (int k = 0; k < n; ++k)
+        for (int ci = 0; ci < n_circ; ++ci) {
+            double px, py;
+            src.get(k, ci, px, py);
+            nan_point |= isnan(px) || isnan(py);
+        }
+    if (mode == 0) {
+        const bool hit = n > 0 && !nan_point && collide_candidate_wide(P, D, obs, n, src);
+        status_out[i] = hit ? 0 : 1;
+        return;
+    }
+    const int32_t *rl = rule_len + (int64_t)i * FOT_CHECK_RULE_LENS;
+    const int n_geo = rl[0] < n ? rl[0] : n, n_d = rl[1], n_v = rl[2], n_a = rl[3], n_c = rl[4], n_s = rl[5];
+    int n_loop = n;
+    n_loop = n_d > n_loop ? n_d : n_loop; n_loop = n_v > n_loop ? n_v : n_loop;
+    n_loop = n_a > n_loop ? n_a : n_loop; n_loop = n_c > n_loop ? n_c : n_loop;
+    CheckAcc acc;
+    check_init(acc);
+    const LoopConst lc = loop_const(P, D);
+    for (int k = 0; k < n_loop && n > 0; ++k) {
+        const uint32_t has = (k < n ? RL_XY : 0u) | (k < n_v ? RL_V : 0u) | (k < n_a ? RL_A : 0u) | (k < n_c ? RL_C : 0u) |
+                             (k < n_d ? RL_D : 0u) | (k < n_geo ? RL_GEO : 0u);
+        PathSample ps;
+        ps.x = ax[k]; ps.y = ay[k]; ps.cos_t = cos(ayaw[k]); ps.sin_t = sin(ayaw[k]);
+        ps.kappa = ac[k]; ps.v = av[k]; ps.a = aa[k]; ps.d = ad[k];
+        check_sample_ext(lc, acc, k, ps, has, [&] { return fabs(as[k] - as[k - 1]); });
+    }
+    int st = check_status(D, acc, n);
+    if (st == ST_PENDING && n > 0 && !nan_point && collide_candidate_wide(P, D, obs, n, src)) st = FOT_ST_COLLISION;
+    // the stop filter reads the last entries of v and s as the caller gave them (:317-318): no v never stops, no s is no travel
+    if (n > 0) st = final_status(st, n_v > 0 ? av[n_v - 1] : NAN, n_s > 0 ? as[n_s - 1] - as[0] : 0.0, D.max_stop);
+    status_out[i] = st;
+}
+
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
@@ -2201,8 +2306,12 @@ int launch_evaluate(const DevParams *P, const PathSet &ps, const InstDesc *desc,
     const int64_t per_queue = (int64_t)((n_inst + N_XCD - 1) / N_XCD) * tiles.max_tiles;
     const int64_t n_blocks = (per_queue + wpw - 1) / wpw * N_XCD;
     if (n_blocks > 0x7fffffffLL) return (int)hipErrorInvalidConfiguration;
+    // (wide: an instance of more than FOT_MAX_SAMPLES samples -- the *_wide kernels, whose general form hands four mask
+    //  words from segment to segment; no flat form)
+    const int seg_d = seg_doubles(tiles.wide && !tiles.lean ? WIDE_MASK_WORDS : 1);
     const size_t lds = sizeof(double) * ((size_t)eval_wave_doubles(tiles.row_budget) * wpw + 9 * (size_t)lds_knots
-                                         + (n_seg > 1 ? (size_t)(SEG_MAX - 1) * SEG_DOUBLES : 0));
+                                         + (n_seg > 1 ? (size_t)(SEG_MAX - 1) * seg_d : 0));
+    if (tiles.wide && tiles.flat) return (int)hipErrorInvalidValue;
     EvalKernArgs a;
     a.Pp = P; a.sp = ps.one; a.desc = desc; a.state = state;
     a.sp_table = ps.table; a.mixed = ps.mixed;
@@ -2215,6 +2324,20 @@ int launch_evaluate(const DevParams *P, const PathSet &ps, const InstDesc *desc,
     a.heads = tiles.heads;
     if (tiles.n_tiles <= 0) {
         k_select_only<<<(unsigned)n_inst, WAVE, 0, st>>>(P, desc, state, tiles.cand0, tiles.n, e.rng, e.e32, a);
+    } else if (tiles.wide) {
+        if (n_seg > 1) {
+            (tiles.lean ? k_evaluate_split_lean_wide : k_evaluate_split_wide)<<<(unsigned)n_blocks, n_seg * WAVE, lds, st>>>(
+                P, desc, state, tiles.cand0, tiles.n, e.rng, e.e32, a);
+        } else if (tiles.grouped) {
+            if (!tiles.heads) return (int)hipErrorInvalidValue;
+            const int per_q = (n_inst + N_XCD - 1) / N_XCD * (tiles.max_tiles / GROUP_TILES);
+            const size_t g_lds = sizeof(double) * ((size_t)eval_group_doubles() + 9 * (size_t)lds_knots);
+            (tiles.lean ? k_evaluate_group_lean_wide : k_evaluate_group_wide)<<<(unsigned)(per_q * N_XCD), GROUP_TILES * WAVE, g_lds, st>>>(
+                P, desc, state, tiles.cand0, tiles.n, e.rng, e.e32, a);
+        } else {
+            (tiles.lean ? k_evaluate_lean_wide : k_evaluate_wide)<<<(unsigned)n_blocks, wpw * WAVE, lds, st>>>(
+                P, desc, state, tiles.cand0, tiles.n, e.rng, e.e32, a);
+        }
     } else if (n_seg > 1) {
         (tiles.flat ? k_evaluate_split_lean_flat : tiles.lean ? k_evaluate_split_lean : k_evaluate_split)<<<(unsigned)n_blocks, n_seg * WAVE, lds, st>>>(
             P, desc, state, tiles.cand0, tiles.n, e.rng, e.e32, a);
@@ -2267,11 +2390,11 @@ int launch_spline_eval(SplineView sp, int n, const double *s, double *out, hipSt
 
 int launch_check_ext(const DevParams *P, const InstDesc *desc, int n_paths, int mode, const int32_t *len,
                      const int32_t *rule_len, const double *arrays, const double *static_xy, const double *dyn_xy,
-                     int32_t *status_out, hipStream_t st)
+                     int32_t *status_out, hipStream_t st, int wide)
 {
     if (n_paths <= 0) return 0;
-    k_check_ext<<<(n_paths + 63) / 64, 64, 0, st>>>(P, desc, n_paths, mode, len, rule_len, arrays, static_xy, dyn_xy,
-                                                    status_out);
+    (wide ? k_check_ext_wide : k_check_ext)<<<(n_paths + 63) / 64, 64, 0, st>>>(P, desc, n_paths, mode, len, rule_len, arrays,
+                                                                                static_xy, dyn_xy, status_out);
     FOT_LAUNCH_CHECK();
     return 0;
 }

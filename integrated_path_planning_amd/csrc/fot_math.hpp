@@ -1201,6 +1201,40 @@ FOT_HD bool within(const d2 &o, double px, double py, double sq)       // (:1196
     return sum_sq_unfused(px - o.x, py - o.y) <= sq;
 }
 
+// The DISTINCT samples of a prediction distribution that have hit a candidate, one bit each: a 64-bit word up to
+// FOT_MAX_SAMPLES samples (every launch of a fresh handle), SampleMask4 -- four words, sample s is bit s & 63 of word
+// s >> 6 -- for the wide launches of a handle with a raised sample capacity (fot_set_sample_capacity, up to
+// FOT_MAX_PLAN_SAMPLES = 254).  The word index is a run-time value: named words and a select chain, never an indexed
+// array (which the device compiler would put into scratch memory).
+struct SampleMask4 { uint64_t w0, w1, w2, w3; };
+template <int W> struct SampleMaskOf { typedef uint64_t type; };
+template <> struct SampleMaskOf<4> { typedef SampleMask4 type; };
+constexpr int WIDE_MASK_WORDS = 4;
+static_assert(FOT_MAX_SAMPLES == 64 && FOT_MAX_PLAN_SAMPLES <= 64 * WIDE_MASK_WORDS && FOT_MAX_PLAN_SAMPLES < 255,
+              "one word up to FOT_MAX_SAMPLES, four up to FOT_MAX_PLAN_SAMPLES, 255 is SID_STATIC");
+
+FOT_HD bool mask_test(uint64_t m, int s) { return (m >> s) & 1; }
+FOT_HD void mask_set(uint64_t &m, int s) { m |= (uint64_t)1 << s; }
+FOT_HD void mask_or(uint64_t &m, uint64_t o) { m |= o; }
+FOT_HD int mask_count(uint64_t m) { return __builtin_popcountll(m); }
+FOT_HD bool mask_test(const SampleMask4 &m, int s)
+{
+    const int wi = s >> 6;
+    const uint64_t w = wi == 0 ? m.w0 : wi == 1 ? m.w1 : wi == 2 ? m.w2 : m.w3;
+    return (w >> (s & 63)) & 1;
+}
+FOT_HD void mask_set(SampleMask4 &m, int s)
+{
+    const int wi = s >> 6;
+    const uint64_t bit = (uint64_t)1 << (s & 63);
+    m.w0 |= wi == 0 ? bit : 0; m.w1 |= wi == 1 ? bit : 0; m.w2 |= wi == 2 ? bit : 0; m.w3 |= wi == 3 ? bit : 0;
+}
+FOT_HD void mask_or(SampleMask4 &m, const SampleMask4 &o) { m.w0 |= o.w0; m.w1 |= o.w1; m.w2 |= o.w2; m.w3 |= o.w3; }
+FOT_HD int mask_count(const SampleMask4 &m)
+{
+    return __builtin_popcountll(m.w0) + __builtin_popcountll(m.w1) + __builtin_popcountll(m.w2) + __builtin_popcountll(m.w3);
+}
+
 // Exact per-candidate check, straight from the definition.  Source::get(k, circle, x, y) returns the
 // collision points; Source::tindex(k) is round(t_k/dt) (== k for lattice candidates).
 // Returns true when the candidate violates the (chance) constraint.
@@ -1234,6 +1268,47 @@ FOT_HD bool collide_candidate(const DevParams &P, const InstDesc &D, const Obsta
                 }
                 if (hit) {
                     hit_mask |= (uint64_t)1 << s;
+                    if (++viol > D.max_viol) return true;
+                }
+            }
+        }
+    }
+    return false;
+}
+
+// The same for an instance of more than 64 samples (D.S <= FOT_MAX_PLAN_SAMPLES): the distinct samples in a SampleMask4.
+// A copy, not a template parameter of the definition above: the kernels that call that one stay, instruction for
+// instruction, what they were (scripts/isa_compare.py).
+template <class Source>
+FOT_HD bool collide_candidate_wide(const DevParams &P, const InstDesc &D, const ObstacleView &obs, int keep, const Source &src)
+{
+    const int n_circ = P.has_footprint ? P.n_circ : 1;
+    for (int k = 0; k < keep && D.n_static > 0; ++k)
+        for (int ci = 0; ci < n_circ; ++ci) {
+            double px, py;
+            src.get(k, ci, px, py);
+            for (int j = 0; j < D.n_static; ++j)
+                if (within(obs.static_at(j), px, py, P.sq_r)) return true;
+        }
+    if (D.dyn_mode == FOT_DYN_NONE || D.P <= 0 || D.T <= 0) return false;
+    const double sq = D.dyn_mode == FOT_DYN_SINGLE ? P.sq_r_dyn : P.sq_r;
+    SampleMask4 hit_mask = SampleMask4();
+    int viol = 0;
+    for (int k = 0; k < keep; ++k) {
+        int row = src.tindex(k);                                            // clip(round(t/dt), 0, T-1)
+        row = row < 0 ? 0 : (row > D.T - 1 ? D.T - 1 : row);
+        for (int ci = 0; ci < n_circ; ++ci) {
+            double px, py;
+            src.get(k, ci, px, py);
+            for (int s = 0; s < D.S; ++s) {
+                if (mask_test(hit_mask, s)) continue;
+                bool hit = false;
+                for (int p = 0; p < D.P; ++p) {
+                    if (obs.nan_track && obs.nan_track[s * D.P + p]) continue;
+                    if (within(obs.dyn_at(s, p, row, D.P, D.T), px, py, sq)) hit = true;
+                }
+                if (hit) {
+                    mask_set(hit_mask, s);
                     if (++viol > D.max_viol) return true;
                 }
             }
@@ -1606,15 +1681,16 @@ FOT_HD void box_thresholds(const FilterConst &f, const Box32 &b, float m, float 
 
 // exact float64 test of one chunk (the reference's test); updates the per-sample hit state
 // (the count at its sample-count edges, through every device form of it: tests/test_gpu_chance_budget.py)
+template <class Mask>
 FOT_HD void exact_chunk(const d2 *e64, const uint8_t *sid, double px, double py, double sq_static, double sq_dyn,
-                        int max_viol, uint64_t &hit_mask, int &viol, bool &collided)
+                        int max_viol, Mask &hit_mask, int &viol, bool &collided)
 {
     for (int j = 0; j < ENT_CHUNK; ++j) {
         const int s = sid[j];
         if (s == SID_STATIC) {
             if (within(e64[j], px, py, sq_static)) collided = true;         // static obstacles are hard constraints
-        } else if (!((hit_mask >> s) & 1) && within(e64[j], px, py, sq_dyn)) {
-            hit_mask |= (uint64_t)1 << s;
+        } else if (!mask_test(hit_mask, s) && within(e64[j], px, py, sq_dyn)) {
+            mask_set(hit_mask, s);
             if (++viol > max_viol) collided = true;
         }
     }
@@ -1624,9 +1700,10 @@ FOT_HD void exact_chunk(const d2 *e64, const uint8_t *sid, double px, double py,
 // and sample ids of the chunk are fetched in one go (72 contiguous bytes), every entry is classified by its float32
 // squared distance -- above `thr`: miss; at or below `thr_sure` (filter_threshold_sure: within the SMALLER radius for
 // certain): hit of whatever kind; in between: the reference's float64 expression on that one entry.
+template <class Mask>
 FOT_HD void exact_chunk_f32first(const f2x8 &c32, const d2 *e64, const uint8_t *sid, float fx, float fy, float thr,
                                  float thr_sure, double px, double py, double sq_static, double sq_dyn, int max_viol,
-                                 uint64_t &hit_mask, int &viol, bool &collided)
+                                 Mask &hit_mask, int &viol, bool &collided)
 {
     uint8_t s8[ENT_CHUNK];
     for (int j = 0; j < ENT_CHUNK; ++j) s8[j] = sid[j];
@@ -1636,14 +1713,32 @@ FOT_HD void exact_chunk_f32first(const f2x8 &c32, const d2 *e64, const uint8_t *
         if (d32 > thr) continue;                                             // certainly outside either radius
         const int s = s8[j];
         const bool is_static = s == SID_STATIC;
-        if (!is_static && ((hit_mask >> s) & 1)) continue;                   // this sample already counts
+        if (!is_static && mask_test(hit_mask, s)) continue;                  // this sample already counts
         const bool in = d32 <= thr_sure ? true : within(e64[j], px, py, is_static ? sq_static : sq_dyn);
         if (!in) continue;
         if (is_static) collided = true;                                      // static obstacles are hard constraints
         else {
-            hit_mask |= (uint64_t)1 << s;
+            mask_set(hit_mask, s);
             if (++viol > max_viol) collided = true;
         }
+    }
+}
+
+// The same without a chance budget (max_viol == 0), whatever the sample ids: any entry inside its radius settles the
+// candidate, so the id only tells a static entry (its own radius) from a dynamic one.  The exact re-check of the lean
+// form of the wide launches: ids of 64 and more never reach a one-word mask.
+FOT_HD void exact_chunk_f32first_nobudget(const f2x8 &c32, const d2 *e64, const uint8_t *sid, float fx, float fy, float thr,
+                                          float thr_sure, double px, double py, double sq_static, double sq_dyn,
+                                          bool &collided)
+{
+    uint8_t s8[ENT_CHUNK];
+    for (int j = 0; j < ENT_CHUNK; ++j) s8[j] = sid[j];
+    for (int j = 0; j < ENT_CHUNK; ++j) {
+        const float dx = fx - c32.x[j], dy = fy - c32.y[j];
+        const float d32 = fmaf(dy, dy, dx * dx);
+        if (d32 > thr) continue;                                             // certainly outside either radius
+        const bool is_static = s8[j] == SID_STATIC;
+        if (d32 <= thr_sure ? true : within(e64[j], px, py, is_static ? sq_static : sq_dyn)) collided = true;
     }
 }
 
@@ -1653,15 +1748,18 @@ FOT_HD void exact_chunk_f32first(const f2x8 &c32, const d2 *e64, const uint8_t *
 // the chunk walk on scalar loads.
 // LEAN (launches without a chance budget, max_viol == 0): no sample mask and no violation count are carried -- the exact
 // re-check works on locals, because its first violation is a hit.
-template <bool LEAN>
+// W: the words of the sample mask -- 1, or WIDE_MASK_WORDS for an instance of more than 64 samples (the wide launches); the
+// lean form of those re-checks without sample ids (exact_chunk_f32first_nobudget).
+template <bool LEAN, int W = 1>
 struct EntryColliderT {
+    typedef typename SampleMaskOf<LEAN ? 1 : W>::type Mask;
     const uint32_t *rng;                 // [n_total] strip ranges of this candidate's wave, nullptr: no obstacles
     const float *thr_k = nullptr, *thr_sure_k = nullptr;   // [n_total] the tile's thresholds per step (box_thresholds),
                                                            // nullptr: derived from the point itself
     const f2 *e32; const d2 *e64; const uint8_t *sid;                       // of this instance
     int ent_cap, max_viol;
     double ox, oy, sq_static, sq_dyn, sq_max;
-    uint64_t hit_mask;
+    Mask hit_mask;
     int viol;
     bool hit;
     FOT_HD void init(const DevParams &P, const InstDesc &D)
@@ -1671,7 +1769,7 @@ struct EntryColliderT {
         sq_static = P.sq_r;
         sq_dyn = D.dyn_mode == FOT_DYN_SINGLE ? P.sq_r_dyn : P.sq_r;
         sq_max = sq_dyn > P.sq_r ? sq_dyn : P.sq_r;
-        hit_mask = 0; viol = 0; hit = false;
+        hit_mask = Mask(); viol = 0; hit = false;
     }
     FOT_HD void row_begin(int) {}
     FOT_HD void row_end(int) {}
@@ -1695,7 +1793,10 @@ struct EntryColliderT {
             if ((LEAN || max_viol == 0) && m <= thr_sure) { hit = true; break; }   // certain hit: one violation is fatal
             double px, py;
             get_exact(px, py);
-            if constexpr (LEAN) {
+            if constexpr (LEAN && W != 1) {
+                exact_chunk_f32first_nobudget(*(const f2x8 *)(e32 + base + c), e64 + base + c, sid + base + c, fx, fy, thr,
+                                              thr_sure, px, py, sq_static, sq_dyn, hit);
+            } else if constexpr (LEAN) {
                 uint64_t mask_l = 0; int viol_l = 0;
                 exact_chunk_f32first(*(const f2x8 *)(e32 + base + c), e64 + base + c, sid + base + c, fx, fy, thr, thr_sure,
                                      px, py, sq_static, sq_dyn, 0, mask_l, viol_l, hit);
@@ -1705,7 +1806,7 @@ struct EntryColliderT {
             }
         }
     }
-    FOT_HD void restart() { hit_mask = 0; viol = 0; hit = false; }
+    FOT_HD void restart() { hit_mask = Mask(); viol = 0; hit = false; }
     FOT_HD bool collided() const { return hit; }
 };
 using EntryCollider = EntryColliderT<false>;

@@ -387,6 +387,7 @@ struct BatchLayout {
     bool any_obstacles = false;
     bool any_tmajor = false;      // some instance's tensor is time-major (its NaN flags come from k_frenet_state's scan blocks)
     int n_ext = 0;                // most horizons + brake-ladder entries of a scenario of the batch (k_cull's LDS tables)
+    int max_S = 0;                // most prediction samples of an instance (more than FOT_MAX_SAMPLES: a wide launch)
     std::vector<int32_t> scens;   // the scenarios the batch uses, ascending
 };
 
@@ -436,8 +437,9 @@ inline void build_head_templates(const ScenarioRef *sc, int n, const int32_t *ti
 // scen: [n_inst] scenario of each instance (indices into sc[0, n_scen)), or nullptr = scenario 0 for every instance.
 // Each instance takes its limits, dt, lattice and tile run from its own scenario; the cut and the per-wave row budget
 // are the handle's (the largest over its scenarios).
+// sample_cap: the handle's sample capacity (fot_set_sample_capacity), FOT_MAX_SAMPLES .. FOT_MAX_PLAN_SAMPLES
 inline int build_batch_layout(const ScenarioRef *sc, int n_scen, const int32_t *scen, const fot_batch &b,
-                              BatchLayout &L, std::string &err)
+                              BatchLayout &L, std::string &err, int sample_cap = FOT_MAX_SAMPLES)
 {
     L = BatchLayout();
     if (n_scen < 1 || !sc) { err = "no scenario"; return FOT_ERR_INVALID; }
@@ -526,7 +528,13 @@ inline int build_batch_layout(const ScenarioRef *sc, int n_scen, const int32_t *
             }
             if (mode == FOT_DYN_SINGLE) S = 1;
             if (mode != FOT_DYN_NONE && S > 0 && Pn > 0 && T > 0) {
-                if (S > FOT_MAX_SAMPLES) { err = "more prediction samples than FOT_MAX_SAMPLES"; return FOT_ERR_UNSUPPORTED; }
+                if (S > sample_cap) {
+                    err = sample_cap == FOT_MAX_SAMPLES ? "more prediction samples than FOT_MAX_SAMPLES" : "more prediction samples than the handle's raised capacity";
+                    err += " (" + std::to_string(S) + " samples, the handle's sample capacity is " + std::to_string(sample_cap)
+                           + "; fot_set_sample_capacity raises it up to " + std::to_string(FOT_MAX_PLAN_SAMPLES) + ")";
+                    return FOT_ERR_UNSUPPORTED;
+                }
+                if (S > L.max_S) L.max_S = S;
                 if (b.dyn_off[i] < 0) { err = "dyn_off < 0"; return FOT_ERR_INVALID; }
                 D.dyn_mode = mode; D.S = S; D.P = Pn; D.T = T;
                 D.p_magic = div_magic((uint32_t)Pn);
@@ -570,11 +578,11 @@ inline int build_batch_layout(const ScenarioRef *sc, int n_scen, const int32_t *
 
 // the single-scenario form: every instance on the one planner
 inline int build_batch_layout(const fot_params &hp, const DevParams &P, const TileShapes &shapes, const fot_batch &b,
-                              BatchLayout &L, std::string &err)
+                              BatchLayout &L, std::string &err, int sample_cap = FOT_MAX_SAMPLES)
 {
     ScenarioRef one;
     one.hp = &hp; one.P = &P; one.shapes = &shapes; one.shape_base = 0;
-    return build_batch_layout(&one, 1, nullptr, b, L, err);
+    return build_batch_layout(&one, 1, nullptr, b, L, err, sample_cap);
 }
 
 }  // namespace fot

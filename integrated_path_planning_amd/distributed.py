@@ -138,14 +138,17 @@ class ShardedPlanner:
     ``torch`` provides device memory, the stream and the collective; the planning itself is libfot.
     """
 
-    def __init__(self, waypoints, device_index: int, world: int, rank: int, group=None, **planner_kwargs):
+    def __init__(self, waypoints, device_index: int, world: int, rank: int, group=None, sample_capacity=None,
+                 **planner_kwargs):
         import torch
         from .planner import BatchPlanner
 
         self.torch = torch
         self.world, self.rank, self.group = world, rank, group
         self.device = torch.device("cuda", device_index)
-        self.planner = BatchPlanner(waypoints=waypoints, device=device_index, **planner_kwargs)
+        # (sample_capacity: BatchPlanner's -- more than 64 samples of a prediction distribution, up to 254)
+        self.planner = BatchPlanner(waypoints=waypoints, device=device_index, sample_capacity=sample_capacity,
+                                    **planner_kwargs)
         self._keep = None
         self._stream = None
 

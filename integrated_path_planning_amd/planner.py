@@ -158,7 +158,11 @@ class BatchPlanner:
     """One libfot handle: planner parameters + reference path on one GPU (scenario 0), and any further scenarios
     (``add_scenario``) that one plan call may mix."""
 
-    def __init__(self, reference_path=None, waypoints=None, device: int = -1, **planner_kwargs):
+    def __init__(self, reference_path=None, waypoints=None, device: int = -1, sample_capacity: Optional[int] = None,
+                 **planner_kwargs):
+        """``sample_capacity``: the most samples S of a prediction distribution the handle plans and checks against,
+        ``_abi.MAX_SAMPLES`` (64, the default: ``None`` makes no call) to ``_abi.MAX_PLAN_SAMPLES`` (254); see
+        ``set_sample_capacity``."""
         self._lib = _abi.lib()
         self.params = _params_from_kwargs(planner_kwargs)
         self.scenario_params = [self.params]     # [id]: fot_params of scenario id (0: the handle's own)
@@ -166,6 +170,8 @@ class BatchPlanner:
         _abi.check(None, self._lib.fot_create(C.byref(self.params), int(device), C.byref(h)))
         self._h = h
         _abi.register_owner(self)                # closed by _abi's atexit hook if the caller never does
+        if sample_capacity is not None:
+            self.set_sample_capacity(sample_capacity)
         if reference_path is not None:
             self.set_path(reference_path)
         elif waypoints is not None:
@@ -196,6 +202,22 @@ class BatchPlanner:
 
     def __exit__(self, *exc):
         self.close()
+
+    # -- capacities -------------------------------------------------------
+    @property
+    def sample_capacity(self) -> int:
+        """Most samples of a prediction distribution ``plan_batch``, ``paths_collision_free`` and ``check_paths`` accept
+        (``fot_get_sample_capacity``); 64 unless raised."""
+        n = C.c_int32(0)
+        _abi.check(self._h, self._lib.fot_get_sample_capacity(self._h, C.byref(n)))
+        return n.value
+
+    def set_sample_capacity(self, n: int) -> None:
+        """``fot_set_sample_capacity``: ``_abi.MAX_SAMPLES <= n <= _abi.MAX_PLAN_SAMPLES``, for all scenarios of the handle.
+        A plan call with an instance of more than 64 samples runs evaluation kernels of its own ("lean-wide" /
+        "general-wide" in ``last_eval_form``); every other call runs what it ran before.  The closed loop, the samplers
+        and the scores keep 64."""
+        _abi.check(self._h, self._lib.fot_set_sample_capacity(self._h, int(n)))
 
     # -- reference path ---------------------------------------------------
     def set_path(self, path, scenario: int = 0):
@@ -1062,7 +1084,7 @@ class BatchPlanner:
         """Test hook (``fot_debug_set_eval_form``): 0 / "auto" (the lean evaluation kernels where a launch is eligible:
         at most 64 samples, the single centre circle, epsilon = 0 on every instance), 1 / "general" (the general form
         always), -1 / "query".  Returns the forms the most recent plan call's launches took: 0 none yet, 1 general,
-        2 lean, 3 both."""
+        2 lean, 3 both; a wide launch (an instance of more than 64 samples) adds 4 (general) or 8 (lean) instead."""
         form = {"auto": 0, "general": 1, "query": -1}.get(form, form)
         rc = self._lib.fot_debug_set_eval_form(self._h, int(form))
         if rc < 0:
@@ -1080,8 +1102,9 @@ class BatchPlanner:
         return bool(rc)
 
     def last_eval_form(self) -> str:
-        """Which evaluation kernels the most recent plan call ran: "none", "general", "lean" or "both"."""
-        return ("none", "general", "lean", "both")[self.set_eval_form(-1)]
+        """Which evaluation kernels the most recent plan call ran: "none", "general", "lean" or "both"; "general-wide" or
+        "lean-wide" for a call with an instance of more than 64 samples ("both" when its lanes took different forms)."""
+        return {0: "none", 1: "general", 2: "lean", 3: "both", 4: "general-wide", 8: "lean-wide"}.get(self.set_eval_form(-1), "both")
 
     def time_info(self, time: float):
         """(n_t, quartic inverse [2, 2], quintic inverse [3, 3]) the library solves a horizon of ``time`` seconds with
@@ -1258,13 +1281,15 @@ class FrenetPlanner:
         self.last_check_stats = None
         # The reference plans any lattice and its plan() never raises (frenet_planner.py:266-268: a failure is `None`).
         # The library has capacities (include/fot.h FOT_MAX_*: 256 samples per candidate, 64 horizons, 32 terminal speeds,
-        # 32 brake horizons, 8 footprint circles, 64 prediction samples); a configuration or a call beyond them keeps the
-        # reference's contract: a warning once, plan() returns None with last_check_stats None, and `last_error` says why.
+        # 32 brake horizons, 8 footprint circles, 64 prediction samples -- up to 254 with sample_capacity=); a configuration
+        # or a call beyond them keeps the reference's contract: a warning once, plan() returns None with last_check_stats
+        # None, and `last_error` says why.
         self.last_error: Optional[str] = None
         self._warned = False
+        self.sample_capacity = kwargs.get("sample_capacity", None)     # of every engine this planner builds
         try:
             self._engine = BatchPlanner(
-                reference_path=reference_path, device=int(kwargs.get("device", -1)),
+                reference_path=reference_path, device=int(kwargs.get("device", -1)), sample_capacity=self.sample_capacity,
                 max_speed=max_speed, max_accel=max_accel, max_curvature=max_curvature, dt=dt, d_road_w=d_road_w,
                 max_road_width=max_road_width, robot_radius=robot_radius, obstacle_radius=obstacle_radius, min_t=min_t,
                 max_t=max_t, d_t_s=d_t_s, max_lat_accel=self.max_lat_accel, k_j=self.k_j, k_t=self.k_t, k_d=self.k_d,
@@ -1357,7 +1382,7 @@ class FrenetPlanner:
             kw = {name: getattr(p, name) for name, _ in p._fields_
                   if name not in ("_pad", "n_circles", "footprint_radius", "footprint_offsets", "chance_epsilon")}
             cache[float(epsilon)] = BatchPlanner(reference_path=self.csp, chance_epsilon=float(epsilon),
-                                                 footprint=self.footprint, **kw)
+                                                 footprint=self.footprint, sample_capacity=self.sample_capacity, **kw)
         return cache[float(epsilon)]
 
     def _check_collision_distribution(self, fp, static_obstacles, dynamic_distribution, epsilon=None) -> bool:

@@ -24,11 +24,13 @@ no such instruction exists:
     of the calls before; at 207 registers it waited for two of them per SIMD and the step was 4 - 5 us longer
     (profiles/r25_frenet_waves_ab.txt).
 
-Usage: isa_check_async.py <file.s> [--allow-scratch] [--min-kernels N] [--min-flat N] [--max-vgpr KERNEL=N ...]
+Usage: isa_check_async.py <file.s> [--allow-scratch] [--min-kernels N] [--min-flat N] [--min-wide N] [--max-vgpr KERNEL=N ...]
 exit status 1 = at least one finding (or fewer than N evaluation kernels in the file; default 3, csrc/Makefile asks for
 the 6 the library ships: k_evaluate, k_evaluate_split, k_evaluate_group and the lean form of each).  The flat forms of the
 lean kernels (k_evaluate*_lean_flat) get every check of the others and are listed on lines beginning `flat form of`;
-they count towards --min-flat (csrc/Makefile: 2), not towards --min-kernels.
+they count towards --min-flat (csrc/Makefile: 2), not towards --min-kernels.  The same holds for the wide forms
+(k_evaluate*_wide: the launches with more than 64 prediction samples an instance, four-word sample mask): every check,
+lines beginning `wide form of`, counted by --min-wide (csrc/Makefile: 6) alone.
 """
 import re
 import sys
@@ -207,6 +209,7 @@ def main(argv):
     bad_total = 0
     n_kernels = 0
     n_flat = 0
+    n_wide = 0
     for fname, body in funcs.items():
         m = re.match(r'_ZN3fot\d+(k_evaluate\w*?)E', fname)
         if not m:
@@ -215,7 +218,12 @@ def main(argv):
         n_loads, findings = analyse(m.group(1), body, frozenset(callee_regs))
         md = meta.get(fname, {})
         regs = f"(vgpr {md.get('vgpr')}, sgpr spills {md.get('sspill')}, vgpr spills {md.get('vspill')}, scratch {md.get('scratch')} B)"
-        if m.group(1).endswith('_flat'):
+        if m.group(1).endswith('_wide'):
+            # the wide forms (more than 64 prediction samples an instance): lines of a shape of their own as well
+            n_wide += 1
+            print(f"wide form of {m.group(1)[:-len('_wide')]}: {m.group(1)}: {len(findings)} instructions touching a"
+                  f" destination in flight of {n_loads} hand-issued scalar loads {regs}")
+        elif m.group(1).endswith('_flat'):
             # the flat forms of the lean kernels (exactly straight reference paths): lines of a third shape, so that a
             # reader of the lines beginning with `k_evaluate` keeps finding the six kernels of the two forms above
             n_flat += 1
@@ -253,8 +261,11 @@ def main(argv):
                   + (" -- over its register ceiling" if over else ""))
             if over or md['vspill'] or md['scratch']:
                 bad_total += 1
-    if n_kernels - n_flat < min_kernels:                         # k_evaluate, _split, _group (the flat forms do not count)
-        print(f"only {n_kernels - n_flat} evaluation kernels found in {path}")
+    if n_kernels - n_flat - n_wide < min_kernels:                # k_evaluate, _split, _group (the flat and wide forms do not count)
+        print(f"only {n_kernels - n_flat - n_wide} evaluation kernels found in {path}")
+        bad_total += 1
+    if '--min-wide' in argv and n_wide < int(argv[argv.index('--min-wide') + 1]):
+        print(f"only {n_wide} wide evaluation kernels found in {path}")
         bad_total += 1
     if '--min-flat' in argv and n_flat < int(argv[argv.index('--min-flat') + 1]):
         print(f"only {n_flat} flat evaluation kernels found in {path}")

@@ -7,7 +7,8 @@
 lean forms (`..._lean`) and the lean forms' flat forms (k_evaluate_split_lean_flat, k_evaluate_group_lean_flat: the walk
 of exactly straight reference paths), each a function of its own in the ISA.  `--all` in the place of a kernel name prints
 the `per step` and `min-walk` rows of every evaluation kernel in the file, one block per kernel, so that a form and its
-flat form stand next to each other.
+flat form stand next to each other; `--all-wide` does the same for the wide forms (k_evaluate*_wide: launches with more than
+64 prediction samples an instance), which `--all` leaves out and which can be named like any other kernel.
 
 The time-step loop is found through the compiler's own loop annotations ("Loop Header", "in Loop: Header=", "Parent
 Loop", "Child Loop"), not through branch targets: the back edge of a rotated loop does not branch to the header label.
@@ -135,8 +136,9 @@ def row(label, where, c):
 
 
 def main(argv):
-    if len(argv) > 2 and argv[2] == '--all':
+    if len(argv) > 2 and argv[2] in ('--all', '--all-wide'):
         names = sorted(set(re.findall(r'\n_ZN3fot\d+(k_evaluate\w*?)E[^\n]*:\s*;', open(argv[1]).read())))
+        names = [n for n in names if n.endswith('_wide') == (argv[2] == '--all-wide')]
         rc = 0
         for name in names:
             rc |= main([argv[0], argv[1], name])
