@@ -68,7 +68,8 @@ SCENES = {
 class Scene:
     """One reference path and ego, the planner kwargs of one obstacle kind, the obstacle-free lattice of both sides."""
 
-    def __init__(self, name, extra):
+    def __init__(self, name, extra, sample_capacity=None):
+        """sample_capacity: of the scene's handle (None: the default of 64; tests/test_gpu_wide_crowds.py raises it)"""
         (wx, wy), skw, (s0, off, dyaw, v, a), self.target = SCENES[name]
         self.name = name
         self.kw = dict(LENIENT, **skw, **extra)
@@ -85,7 +86,7 @@ class Scene:
         x, y, yaw = (c[0] for c in self.sp.eval([s0])[:3])
         self.ego = PlanRequest(float(x - np.sin(yaw) * off), float(y + np.cos(yaw) * off), float(yaw + dyaw), v, a,
                                target_speed=self.target)
-        self.bp = BatchPlanner(waypoints=(wx, wy), **self.kw)
+        self.bp = BatchPlanner(waypoints=(wx, wy), sample_capacity=sample_capacity, **self.kw)
         self.n_t = int(round(self.kw["max_t"] / self.kw["dt"])) + 1
         free = oracle_plan_for_request(orc, self.params, self.sp, self.request(), table=True)
         self.free = free

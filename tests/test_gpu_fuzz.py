@@ -59,6 +59,14 @@ def random_planner_kwargs(rng):
     return kw
 
 
+def beside_road(rng, kw, ahead, ayaw, idx):
+    """points along both road sides, some reaching into the lattice: beside the points ahead[idx] of the path (headings
+    ayaw[idx]), 0.6 .. 2 times the lattice's reach to either side"""
+    reach = kw["max_road_width"] + kw["robot_radius"] + kw["obstacle_radius"]
+    off = rng.choice([-1.0, 1.0], len(idx)) * rng.uniform(0.6, 2.0, len(idx)) * reach
+    return ahead[idx] + np.stack([-np.sin(ayaw[idx]) * off, np.cos(ayaw[idx]) * off], axis=1)
+
+
 def random_request(rng, sp, kw, dense=False):
     s_end = sp.coeffs()[0][-1]
     s = rng.uniform(0.0, s_end) if rng.random() < 0.9 else rng.uniform(s_end - 3, s_end)
@@ -79,10 +87,8 @@ def random_request(rng, sp, kw, dense=False):
     ax, ay, ayaw = sp.eval(np.clip(s + rng.uniform(0, 45, 64), 0, s_end))[:3]
     ahead = np.stack([ax, ay], axis=1)
 
-    def beside(idx):                                # points along both road sides, some reaching into the lattice
-        reach = kw["max_road_width"] + kw["robot_radius"] + kw["obstacle_radius"]
-        off = rng.choice([-1.0, 1.0], len(idx)) * rng.uniform(0.6, 2.0, len(idx)) * reach
-        return ahead[idx] + np.stack([-np.sin(ayaw[idx]) * off, np.cos(ayaw[idx]) * off], axis=1)
+    def beside(idx):
+        return beside_road(rng, kw, ahead, ayaw, idx)
     mode = rng.integers(0, 4)
     if dense:                                       # crowded scenes: the broad phase's strips, lists and bins fill up
         mode = int(rng.integers(1, 3))

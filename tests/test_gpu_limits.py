@@ -127,19 +127,31 @@ p0[:n_block] = np.column_stack([rng.uniform(22, 26, n_block), np.linspace(-3.2, 
 dist = p0[None, :, None, :] + rng.normal(0, 0.05, (S, P, 1, 2)) * (np.arange(T) * 0.2)[None, None, :, None]
 for j in [s * P + p for s in range(S) for p in range(n_block)]:
     dist[j // P, j % P, rng.integers(0, T), rng.integers(0, 2)] = np.nan
-with BatchPlanner(waypoints=(WX, WY), **kw) as bp:
-    reqs = [PlanRequest(2.0, 0.1, 0.0, 6.0, 0.0, target_speed=7.0, dist=dist),
-            PlanRequest(12.0, -0.3, 0.02, 4.0, 0.3, target_speed=5.0, dist=dist[:, ::2])]
-    dev = torch.device("cuda", 0)
-    h = hashlib.sha256()
-    for dtype in (np.float32, np.float64):
-        pb = PackedBatch(reqs, dtype)
-        dyn = torch.from_numpy(pb.dyn_xy).to(dev)
-        out = torch.zeros(pb.n * _abi.RESULT_BYTES, dtype=torch.uint8, device=dev)
-        bp.plan_packed_device(pb.with_device_obstacles(None, dyn.data_ptr()), out.data_ptr(),
-                              torch.cuda.current_stream(dev).cuda_stream)
-        torch.cuda.synchronize(dev)
-        h.update(out.cpu().numpy().tobytes())
+# a wide case, on a handle of its own with a raised sample capacity: 129 samples of 3 pedestrians, every sample of the two
+# that stand across the lane holds a NaN (258 NaN tracks, sample ids j / P up to 128)
+S2, P2, nb2 = 129, 3, 2
+rng2 = np.random.default_rng(12902)
+q0 = np.column_stack([rng2.uniform(4, 40, P2), rng2.uniform(2.3, 3.0, P2)])
+q0[:nb2] = np.column_stack([rng2.uniform(22, 26, nb2), np.linspace(-3.2, 1.0, nb2)])
+wide = q0[None, :, None, :] + rng2.normal(0, 0.05, (S2, P2, 1, 2)) * (np.arange(T) * 0.2)[None, None, :, None]
+for j in [s * P2 + p for s in range(S2) for p in range(nb2)]:
+    wide[j // P2, j % P2, rng2.integers(0, T), rng2.integers(0, 2)] = np.nan
+h = hashlib.sha256()
+dev = torch.device("cuda", 0)
+cases = [(None, [PlanRequest(2.0, 0.1, 0.0, 6.0, 0.0, target_speed=7.0, dist=dist),
+                 PlanRequest(12.0, -0.3, 0.02, 4.0, 0.3, target_speed=5.0, dist=dist[:, ::2])]),
+         (254, [PlanRequest(2.0, 0.1, 0.0, 6.0, 0.0, target_speed=7.0, dist=wide),
+                PlanRequest(12.0, -0.3, 0.02, 4.0, 0.3, target_speed=5.0, dist=wide[:, ::2])])]
+for capacity, reqs in cases:
+    with BatchPlanner(waypoints=(WX, WY), sample_capacity=capacity, **kw) as bp:
+        for dtype in (np.float32, np.float64):
+            pb = PackedBatch(reqs, dtype)
+            dyn = torch.from_numpy(pb.dyn_xy).to(dev)
+            out = torch.zeros(pb.n * _abi.RESULT_BYTES, dtype=torch.uint8, device=dev)
+            bp.plan_packed_device(pb.with_device_obstacles(None, dyn.data_ptr()), out.data_ptr(),
+                                  torch.cuda.current_stream(dev).cuda_stream)
+            torch.cuda.synchronize(dev)
+            h.update(out.cpu().numpy().tobytes())
 print("RECORDS", h.hexdigest(), flush=True)
 """
 
@@ -147,7 +159,8 @@ print("RECORDS", h.hexdigest(), flush=True)
 def test_scan_blocks_for_every_layout_give_the_same_records():
     """FOT_NAN_SCAN=eager (read once per process): k_frenet_state's scan blocks flag the NaN tracks of [S][P][T] tensors
     too, as before round 4, and k_cull looks nothing up itself -- same records as the default, on HBM-resident tensors
-    with forty NaN tracks across the lane.  Two child processes, one per setting."""
+    with forty NaN tracks across the lane, and on a wide tensor (129 samples, a raised handle) with 258 of them.  Two child
+    processes, one per setting."""
     import os
     import subprocess
     import sys
