@@ -41,9 +41,9 @@ extern "C" {
 #define FOT_MAX_TI 64        /* time horizons  int((max_t-min_t)/dt)+1  (min_t = 1 s at max_t = 5 s, dt = 0.1 s: 41) */
 #define FOT_MAX_TV 32        /* terminal speeds per horizon */
 #define FOT_MAX_BRAKE 32     /* brake-ladder entries 0.5 s, 1.0 s, ... < min_t (frenet_planner.py:475): min_t <= 16.4 s */
-#define FOT_MAX_SAMPLES 64   /* prediction samples S of a distribution: a fresh handle's capacity, and the capacity of
-                                the prediction, sampler and closed-loop entries whatever the handle's */
-#define FOT_MAX_PLAN_SAMPLES 254  /* ... what fot_set_sample_capacity can raise a handle's plan path to: sample ids travel as
+#define FOT_MAX_SAMPLES 64   /* prediction samples S of a distribution: a fresh handle's capacity (and fot_openloop_eval's,
+                                whatever the handle's) */
+#define FOT_MAX_PLAN_SAMPLES 254  /* ... what fot_set_sample_capacity can raise a handle to: sample ids travel as
                                 uint8_t with 255 for a static obstacle, and 254 samples are four 64-bit mask words */
 
 /* error codes */
@@ -293,15 +293,27 @@ int fot_debug_set_tile_cut(fot_handle *h, int32_t cut);
  * adds 4 (the general form with a four-word sample mask) or 8 (the lean form) instead of 1 or 2. */
 int fot_debug_set_eval_form(fot_handle *h, int32_t form);
 
-/* The sample capacity of the handle's plan path: the largest S of a prediction distribution that fot_plan_batch,
- * fot_plan_batch_device, their _scenarios forms, fot_check_collision_paths and fot_check_paths accept; beyond it they
- * return FOT_ERR_UNSUPPORTED.  A fresh handle has FOT_MAX_SAMPLES.  fot_set_sample_capacity accepts FOT_MAX_SAMPLES <=
+/* The sample capacity of the handle: the largest S of a prediction distribution that EVERY entry taking one accepts --
+ * fot_plan_batch, fot_plan_batch_device, their _scenarios forms, fot_check_collision_paths and fot_check_paths; the
+ * frames of fot_loop_plan / fot_loop_step (dist_S); fot_loop_set_samples(_shared); fot_loop_set_sampler(_shared,
+ * _models); fot_sgan_sample(_model) and fot_sgan_noise; fot_prediction_scores and fot_loop_prediction_scores; and with
+ * them fot_loop_scores_enable, fot_loop_plan_sample and the sweep loops, which take the S of the loop's predictor.
+ * Beyond it they return FOT_ERR_UNSUPPORTED with a message that names S and the capacity, and change nothing.  A fresh
+ * handle has FOT_MAX_SAMPLES.  fot_set_sample_capacity accepts FOT_MAX_SAMPLES <=
  * n_samples <= FOT_MAX_PLAN_SAMPLES; anything else is FOT_ERR_INVALID and leaves the handle as it was.  The capacity is
  * the handle's, for all its scenarios.  A launch with an instance of more than FOT_MAX_SAMPLES samples is WIDE: it runs
  * evaluation kernels of its own that count distinct samples in four mask words (lean-eligible launches: kernels that
  * need no sample ids) and has no flat form.  Every other launch runs the kernels it ran before, raised capacity or not.
- * The fot_debug_* entries work after a wide launch.  The closed-loop, sampler, score and open-loop entries (fot_loop_*,
- * fot_sgan_*, fot_prediction_scores, fot_openloop_eval) keep FOT_MAX_SAMPLES.
+ * The fot_debug_* entries work after a wide launch.  The prediction scores and the representative-sample selection of a
+ * distribution of more than FOT_MAX_SAMPLES samples run wide forms of their kernels too (per-sample tables of
+ * FOT_MAX_PLAN_SAMPLES rows); with at most FOT_MAX_SAMPLES samples every entry runs the kernels of a fresh handle and
+ * returns its bytes, raised capacity or not.
+ * A loop that is set up: RAISING the capacity is always accepted (a loop's buffers are sized by its own S, not by the
+ * capacity, so nothing of a begun loop moves).  LOWERING it below the samples of the handle's loop -- the S of a resident
+ * loop's sampler or recording (from the set call until the next fot_loop_begin* / fot_loop_set_replay), or the dist_S of
+ * a stepwise loop's current frame -- is FOT_ERR_INVALID and leaves the capacity as it was.
+ * Out of scope: fot_openloop_eval keeps FOT_MAX_SAMPLES whatever the handle's capacity; the slots of one sweep share one
+ * sample count; summaries together with a sampler or a recording stay refused.
  * fot_max_plan_samples: the FOT_MAX_PLAN_SAMPLES the library was built with, for a binding to compare with its own.
  * Additions: no structure, capacity word of fot_abi_info or FOT_ABI_VERSION changes; a binding looks the symbols up. */
 int fot_set_sample_capacity(fot_handle *h, int32_t n_samples);
@@ -438,7 +450,8 @@ typedef struct fot_loop_frame {
      * device (process_prediction, trajectory_predictor.py:233-313) straight into the handle's tensor, per episode a
      * [dist_S][P_e][n_dense + 1][2] block led by the current positions in EVERY sample, and every request of the step
      * plans against its episode's whole distribution under the handle's chance constraint.  NULL: the constant-velocity
-     * predictor above.  dist_dtype FOT_F32 | FOT_F64; dist_S <= FOT_MAX_SAMPLES. */
+     * predictor above.  dist_dtype FOT_F32 | FOT_F64; dist_S <= the handle's sample capacity
+     * (fot_set_sample_capacity; FOT_ERR_UNSUPPORTED beyond it). */
     const void *dist_raw;
     int32_t dist_S, dist_dtype;
 } fot_loop_frame;
@@ -655,7 +668,7 @@ int fot_loop_summaries(fot_handle *h, int32_t n_slots, fot_loop_summary *out);
  * float64, the origins' pedestrians one after the other; out: host, n_origins records.  stream NULL = the handle's.
  * P = 0 gives a zero record (n_peds 0).  Refusals, a refused call changes nothing: stride < 1, E < 1, S < 1, P < 0,
  * stride E - 1 >= T - skip, skip not 0 / 1, a negative offset, an unknown layout or dtype (FOT_ERR_INVALID); S >
- * FOT_MAX_SAMPLES or E > FOT_MAX_PRED_LEN -- the kernel keeps E truth points per pedestrian of a tile in LDS
+ * the handle's sample capacity or E > FOT_MAX_PRED_LEN -- the kernel keeps E truth points per pedestrian of a tile in LDS
  * (FOT_ERR_UNSUPPORTED).
  * fot_loop_prediction_scores: the same for the distribution blocks the most recent fot_loop_step / fot_loop_plan frame
  * with dist_raw left in the handle's own tensor (float64, [dist_S][P_e][n_dense + 1][2], skip 1): n_episodes == the
@@ -692,7 +705,7 @@ int fot_loop_prediction_scores(fot_handle *h, int32_t n_episodes, int32_t stride
  * pedestrian or per scene; a noise_dim of one entry, 0 included (without noise and pooling and with encoder_h_dim ==
  * decoder_h_dim the context MLP is absent, as in the reference).  BatchNorm is an eval-mode affine map: the caller folds
  * it into the Linear in front of it, the library never sees it.  FOT_ERR_UNSUPPORTED: social pooling (FOT_SGAN_SPOOL),
- * dropout > 0, num_layers > 1, a dimension above its FOT_SGAN_MAX_*, pred_len > FOT_MAX_PRED_LEN, S > FOT_MAX_SAMPLES,
+ * dropout > 0, num_layers > 1, a dimension above its FOT_SGAN_MAX_*, pred_len > FOT_MAX_PRED_LEN, S > the handle's sample capacity,
  * a scene of more than FOT_SGAN_MAX_PEDS pedestrians.
  *
  * Weights: ONE packed float32 blob, every matrix row-major [out][in] as torch stores it, LSTM gates in torch's order
@@ -771,7 +784,7 @@ int fot_sgan_sample(fot_handle *h, int32_t n_scenes, const int32_t *ped_off, con
  * row_slot / row_step / row_index: host [rows]; flags FOT_OUT_DEVICE: out is device memory.  Synchronous, enqueued on
  * `stream` (NULL = the handle's).  No model needs to be loaded.  FOT_ERR_INVALID, nothing changed: an unknown kind or
  * flag, S < 1, rows < 0, noise_dim < 0, a NULL table or `out` that is needed, a negative table entry, row_index > 65535;
- * FOT_ERR_UNSUPPORTED: S > FOT_MAX_SAMPLES.
+ * FOT_ERR_UNSUPPORTED: S > the handle's sample capacity.
  *
  * fot_loop_set_sampler(h, S, seed, kind): between fot_loop_set_replay and the first step.  The resident loop then predicts
  * with the model of fot_sgan_load instead of constant velocity: once the observer is ready, a step gathers the window
@@ -782,7 +795,7 @@ int fot_sgan_sample(fot_handle *h, int32_t n_scenes, const int32_t *ped_off, con
  * the bus in between; level 0, the escalation levels, the resolve and the history run as without a sampler.  seed, slot
  * and fot_loop_run_out.steps reproduce any step's noise through fot_sgan_noise.
  * Refusals, a refused call changes nothing.  FOT_ERR_INVALID: no replay set; no model loaded; after the first step; S < 1;
- * an unknown kind; the model's obs_len / pred_len differ from the replay's.  FOT_ERR_UNSUPPORTED: S > FOT_MAX_SAMPLES; a
+ * an unknown kind; the model's obs_len / pred_len differ from the replay's.  FOT_ERR_UNSUPPORTED: S > the handle's sample capacity; a
  * slot of more than FOT_SGAN_MAX_PEDS pedestrians; a loop begun with fot_loop_begin_scenarios; summaries enabled
  * (fot_loop_summary_enable is refused in turn while a sampler is set: its prediction-error ring reads the
  * constant-velocity tensor's layout).  fot_sgan_load / fot_sgan_unload are refused (FOT_ERR_INVALID) while a sampler is
@@ -912,7 +925,7 @@ int fot_debug_loop_block(fot_handle *h, int32_t episode, int32_t cap_points, dou
  * entry launches and allocates nothing new.
  * Refusals, a refused call changes nothing.  FOT_ERR_INVALID: no replay set; after the first step; S < 1; n_steps < 1;
  * first_step < 0; samples NULL (or device memory not aligned to an element); an unknown dtype or flag; a sampler set.
- * FOT_ERR_UNSUPPORTED: S > FOT_MAX_SAMPLES; a loop begun with fot_loop_begin_scenarios; summaries enabled.
+ * FOT_ERR_UNSUPPORTED: S > the handle's sample capacity; a loop begun with fot_loop_begin_scenarios; summaries enabled.
  * An addition: FOT_ABI_VERSION and the words of fot_abi_info stay as they are; a binding looks the symbol up. */
 int fot_loop_set_samples(fot_handle *h, int32_t S, int32_t n_steps, int32_t first_step, const void *samples, int32_t dtype,
                          int32_t flags);
@@ -970,7 +983,7 @@ int fot_loop_set_samples(fot_handle *h, int32_t S, int32_t n_steps, int32_t firs
  * or in any byte of their columns of `pos` over their recorded frames (compared once, on the host, by this call; the
  * message names both slots).  Everything the mode needs is allocated by the call; fot_loop_begin* and fot_loop_set_replay
  * drop it with the sampler.  Not supported: one distribution block per crowd (resampling, selection and scores still run
- * per slot, as for a shared recording), S > FOT_MAX_SAMPLES, crowds whose slots stand at different step counts.
+ * per slot, as for a shared recording), S > the handle's sample capacity, crowds whose slots stand at different step counts.
  *
  * fot_debug_loop_sampler_shape (tests): the scenes and pedestrian rows the most recent lock step handed to the generator --
  * 0 / 0 if that step did not sample; FOT_ERR_INVALID without a sampler.  It shows that the work was shared, not only the

@@ -453,7 +453,8 @@ class BatchedClosedLoop:
     def __init__(self, config, ped_tracks: Sequence[np.ndarray], ego_initial_states: Optional[Sequence] = None,
                  device: int = -1, engine=None, resampler=None, sample_source=None, fused: Optional[bool] = None,
                  device_samples: bool = False, resident: bool = False, summaries: bool = False,
-                 prediction_scores: bool = False, plan_on_representative_sample: bool = False, footprint_obs=None):
+                 prediction_scores: bool = False, plan_on_representative_sample: bool = False, footprint_obs=None,
+                 sample_capacity: Optional[int] = None):
         """sample_source: the multi-sample predictor in front of the planner -- a callable
         ``(obs_last [P, 2], obs_prev [P, 2]) -> raw samples [S, pred_len, P, 2]`` at the predictor's own time step
         (a source with the attribute ``needs_history = True``, such as ``prediction.SganSampler``, is called with the
@@ -512,6 +513,10 @@ class BatchedClosedLoop:
         ``observational_footprint_metrics``) -- and ``footprint_metrics()`` returns the episodes' minima and violation
         steps; ``save_summaries()`` appends them.  Resident loops and the one-call step; the five-call step and stand-in
         engines raise ValueError.
+        sample_capacity: the most samples of a distribution the loop's engine accepts, 64 (None) to 254: handed to the
+        ``BatchPlanner`` the loop builds (``fot_set_sample_capacity``); with a caller's ``engine`` that engine's own
+        capacity counts.  A sample source that declares more samples than that (``num_samples``: a ``SganSampler``, a
+        ``RecordedSamples``) raises ValueError here, not at the first step.
         fused: True = the lock step behind one library call (fot_loop_step), False = five separate calls with the
         prediction through the host, None = one call where the engine and the predictor allow it."""
         if fused not in (None, False, True):
@@ -576,6 +581,17 @@ class BatchedClosedLoop:
         self.ped_radius = getattr(c, "ped_radius", 0.3)
         self.footprint = footprint_from_config(c)
         self.sample_source = sample_source
+        # the capacity the loop's engine will have: a caller's engine brings its own (a stand-in without one: the keyword)
+        cap = getattr(engine, "sample_capacity", None) if engine is not None else None
+        if cap is None:
+            cap = _abi.MAX_SAMPLES if sample_capacity is None else int(sample_capacity)
+            if not _abi.MAX_SAMPLES <= cap <= _abi.MAX_PLAN_SAMPLES:
+                raise ValueError(f"sample_capacity: {_abi.MAX_SAMPLES} .. {_abi.MAX_PLAN_SAMPLES}, got {sample_capacity}")
+        n_src = getattr(sample_source, "num_samples", None)
+        if n_src is not None and int(n_src) > int(cap):
+            raise ValueError(f"the sample source has {int(n_src)} samples, the loop's engine accepts {int(cap)}: "
+                             + ("raise the engine's own capacity (BatchPlanner(sample_capacity=...))" if engine is not None else
+                                f"pass sample_capacity={int(n_src)} (up to {_abi.MAX_PLAN_SAMPLES}) to BatchedClosedLoop"))
         crowd = getattr(sample_source, "slot_crowd", None)            # a sampler whose slots share crowds: one id per episode
         if crowd is not None and len(crowd) != len(ped_tracks):
             raise ValueError(f"the sample source's slot_crowd names {len(crowd)} slots, the loop has {len(ped_tracks)} episodes")
@@ -604,7 +620,7 @@ class BatchedClosedLoop:
         self._owns_engine = engine is None
         self.engine = engine if engine is not None else BatchPlanner(
             waypoints=(np.asarray(c.reference_waypoints_x, float), np.asarray(c.reference_waypoints_y, float)),
-            device=device, **planner_kwargs_from_config(c, self.footprint))
+            device=device, sample_capacity=sample_capacity, **planner_kwargs_from_config(c, self.footprint))
         self.s_end = float(self.engine.path_coeffs()[0][-1])
         if self.scenarios is not None:
             # scenario 0 is the first configuration; the other distinct ones join the same handle.  Per episode from here

@@ -1165,6 +1165,13 @@ int fot_set_sample_capacity(fot_handle *h, int32_t n_samples)
     if (!h) return FOT_ERR_INVALID;
     if (n_samples < FOT_MAX_SAMPLES || n_samples > FOT_MAX_PLAN_SAMPLES)
         return fail(h, FOT_ERR_INVALID, "fot_set_sample_capacity: FOT_MAX_SAMPLES (64) .. FOT_MAX_PLAN_SAMPLES (254) samples");
+    // a loop that is set up with more samples keeps its capacity: the predictor of a resident loop (sampler or recording),
+    // and the distribution of a stepwise loop's current frame, whose later requests still plan against it
+    const LoopState &L = h->loop;
+    const int loop_S = std::max(L.replay.set ? L.replay.dist_S() : 0, L.have_frame ? L.dist_S : 0);
+    if (n_samples < loop_S)
+        return fail(h, FOT_ERR_INVALID, "fot_set_sample_capacity: the handle's loop is set up with " + std::to_string(loop_S) +
+                                        " samples (a capacity below them: after fot_loop_begin* / fot_loop_set_replay anew)");
     h->sample_cap = n_samples;
     return FOT_OK;
 }

@@ -227,7 +227,7 @@ struct LoopScores {
     bool on = false;
     int stride = 0, H = 0;
     bool std_ok = false;                         // stride * pred_len - 1 < n_dense: the standard metrics apply at all
-    DevBuf dBest, dDev, dTruth;                  // int32[slots] | [slots][FOT_MAX_SAMPLES] deviation sums | [cols][pred_len][2]
+    DevBuf dBest, dDev, dTruth;                  // int32[slots] | [slots][best_dev_stride(S)] deviation sums | [cols][pred_len][2]
     PinnedBuf hBest, hDesc, hRec;                // int32[slots] | PredOriginDev[slots] | fot_pred_score[slots] of the step
     std::vector<PredScoreTerms> ring;            // [slots][H]
     std::vector<ScoreFold> fold;                 // [slots]
@@ -270,7 +270,7 @@ struct LoopRep {
     int mode = 0;                                // FOT_LOOP_PLAN_*
     bool frame = false;                          // the most recent frame left planning blocks in dBlk (it carried a distribution)
     int T = 0;                                   // their time entries: n_dense + 1
-    DevBuf dBlk, dBest, dDev, dPre;              // [rows][T][2] | int32[slots] | [slots][FOT_MAX_SAMPLES] | int32[episodes]
+    DevBuf dBlk, dBest, dDev, dPre;              // [rows][T][2] | int32[slots] | [slots][best_dev_stride(S)] | int32[episodes]
     PinnedBuf hBest, hPre;                       // int32[slots] | int32[episodes of the frame]
     std::vector<int32_t> last_best;              // [slots of fot_loop_begin] of the most recent lock step
     std::vector<int32_t> run_best;               // [steps][slots] of the most recent fot_loop_run call (fot_loop_run_best_samples)
@@ -372,7 +372,7 @@ struct fot_handle {
     int eval_form = 0;                   // fot_debug_set_eval_form: 0 = by eligibility, 1 = the general form always
     int last_eval_forms = 0;             // forms the launches of the most recent plan call took: 1 general | 2 lean
                                          // | 4 general, wide | 8 lean, wide
-    int sample_cap = FOT_MAX_SAMPLES;    // fot_set_sample_capacity: most samples of a distribution the plan path accepts
+    int sample_cap = FOT_MAX_SAMPLES;    // fot_set_sample_capacity: most samples of a distribution any entry accepts
     int flat_mode = 1;                   // fot_debug_set_flat: 1 = flat kernels where a launch is eligible, 0 = never
     int last_flat = 0;                   // 1: a launch of the most recent plan call took a flat kernel
     std::vector<Scenario> sc;                // scenarios; sc[0]: fot_create's params + fot_set_path_*
@@ -491,6 +491,15 @@ struct ProfScope {
 };
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// The refusal of every entry that takes a sample distribution (prediction, samplers, scores, the loop's frames): S lies
+// above the handle's sample capacity.  who: the entry's name with its separator.  Changes nothing but the error text.
+inline int refuse_samples(fot_handle *h, const std::string &who, int S)
+{
+    return fail(h, FOT_ERR_UNSUPPORTED, who + "S > " + (h->sample_cap == FOT_MAX_SAMPLES ? "FOT_MAX_SAMPLES" : "the handle's raised sample capacity") +
+                                        " (" + std::to_string(S) + " samples, the handle's sample capacity is " + std::to_string(h->sample_cap) +
+                                        "; fot_set_sample_capacity raises it up to " + std::to_string(FOT_MAX_PLAN_SAMPLES) + ")");
+}
 
 // Calls whose inputs and outputs stay below this size skip the copy operations: the kernels read / write pinned host
 // memory directly (fot_plan_batch, fot_safety_metrics_batch, fot_frenet_state_batch, the host path of the resampler).

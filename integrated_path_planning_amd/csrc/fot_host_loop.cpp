@@ -48,14 +48,15 @@ int ensure_scen_static(fot_handle *h, int n_req, hipStream_t st)
 }
 
 // FOT_LOOP_PLAN_REPRESENTATIVE: room for a frame of n_ep episodes on slots below n_slots with `rows` pedestrians and T time
-// entries per track.  (A block that grows is freed first, which waits for the device: nothing still reads the old one.)
-int rep_ensure(fot_handle *h, int n_slots, int n_ep, size_t rows, int T)
+// entries per track, each of S samples (the rows of the selection's table are best_dev_stride(S) apart).  (A block that
+// grows is freed first, which waits for the device: nothing still reads the old one.)
+int rep_ensure(fot_handle *h, int n_slots, int n_ep, size_t rows, int T, int S)
 {
     LoopRep &Q = h->loop.rep;
     const size_t ns = (size_t)std::max(n_slots, 1), ne = (size_t)std::max(n_ep, 1);
     HIP_TRY(h, Q.dBlk.ensure(sizeof(double) * 2 * std::max<size_t>(rows, 1) * (size_t)T));
     HIP_TRY(h, Q.dBest.ensure(sizeof(int32_t) * ns));
-    HIP_TRY(h, Q.dDev.ensure(sizeof(double) * ns * FOT_MAX_SAMPLES));
+    HIP_TRY(h, Q.dDev.ensure(sizeof(double) * ns * (size_t)best_dev_stride(S)));
     HIP_TRY(h, Q.dPre.ensure(sizeof(int32_t) * ne));
     HIP_TRY(h, Q.hBest.ensure(sizeof(int32_t) * ns));
     HIP_TRY(h, Q.hPre.ensure(sizeof(int32_t) * ne));
@@ -69,7 +70,7 @@ int sweep_ensure(fot_handle *h, int S)
     LoopState &L = h->loop;
     const LoopReplay &R = L.replay;
     const int n = R.cfg.n_slots, T = R.n_dense + 1;
-    { int r = rep_ensure(h, n, n, 0, T); if (r != FOT_OK) return r; }
+    { int r = rep_ensure(h, n, n, 0, T, S); if (r != FOT_OK) return r; }
     HIP_TRY(h, L.hSweep.ensure(sizeof(SweepEp) * (size_t)std::max(n, 1)));
     HIP_TRY(h, L.dDyn.ensure(sizeof(double) * 2 * (size_t)sweep_capacity_points(S, std::max(R.n_cols, 1), T)));
     return FOT_OK;
@@ -206,8 +207,10 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
         if (n_ped > 0 && (!frame->ped_pos || !frame->ped_vel)) return fail(h, FOT_ERR_INVALID, "frame: NULL pedestrian array");
         const bool ready = frame->obs_last != nullptr;
         const bool dist = ready && frame->dist_raw != nullptr;
-        if (dist && (frame->dist_S < 1 || frame->dist_S > FOT_MAX_SAMPLES || (frame->dist_dtype != FOT_F32 && frame->dist_dtype != FOT_F64)))
-            return fail(h, dist && frame->dist_S > FOT_MAX_SAMPLES ? FOT_ERR_UNSUPPORTED : FOT_ERR_INVALID, "frame: dist_S / dist_dtype");
+        // (the capacity first: more samples than the handle accepts are FOT_ERR_UNSUPPORTED whatever else the frame holds)
+        if (dist && frame->dist_S > h->sample_cap) return refuse_samples(h, "frame: dist_", frame->dist_S);
+        if (dist && (frame->dist_S < 1 || (frame->dist_dtype != FOT_F32 && frame->dist_dtype != FOT_F64)))
+            return fail(h, FOT_ERR_INVALID, "frame: dist_S / dist_dtype");
         if (ready && !dist && n > 0 && !frame->prepend) return fail(h, FOT_ERR_INVALID, "frame: prepend missing");
         if (ready && (!(frame->rp.sim_dt > 0.0) || !(frame->rp.sgan_dt > 0.0) || frame->pred_len < 1 ||
                       frame->pred_len > FOT_MAX_PRED_LEN))
@@ -277,7 +280,7 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
                                           L.dDyn.p, FOT_F64, 0, st, p_pe, p_off, p_blk));
             if (sweep_on && tensor_pts > L.blk_off[n]) {
                 // the selection and the planning blocks of the episodes in representative mode, behind the resample
-                { int r = rep_ensure(h, std::max(L.ep.n, n), n, 0, n_dense + 1); if (r != FOT_OK) return r; }
+                { int r = rep_ensure(h, std::max(L.ep.n, n), n, 0, n_dense + 1, frame->dist_S); if (r != FOT_OK) return r; }
                 FrameDev fd;
                 fd.pos = p_pos; fd.ped0 = p_off; fd.blk = p_blk;
                 LAUNCH_TRY(h, launch_loop_best_sample_sweep(p_slot, fd, L.dDyn.as<double>(), p_sweep, n, frame->dist_S, n_dense,
@@ -296,7 +299,7 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
                 int32_t *p_slot = (int32_t *)(p + ego_b + off_b + 4 * ped_b + blk_b + pe_b);
                 int n_tab = std::max(L.ep.n, n);
                 for (int e = 0; e < n; ++e) p_slot[e] = ep_slot ? ep_slot[e] : e;
-                { int r = rep_ensure(h, n_tab, n, n_ped, n_dense + 1); if (r != FOT_OK) return r; }
+                { int r = rep_ensure(h, n_tab, n, n_ped, n_dense + 1, frame->dist_S); if (r != FOT_OK) return r; }
                 FrameDev fd;
                 fd.pos = p_pos; fd.ped0 = p_off; fd.blk = p_blk;
                 { int r = rep_enqueue(h, p_slot, fd, n, frame->dist_S, n_dense, L.rep.dDev.as<double>(), L.rep.dBest.as<int32_t>(),
@@ -953,7 +956,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         L.sweep_T = R.n_dense + 1;
     } else if (rep_on) {
         // the selection once, into the scores' tables where they are on: a scored and a planning loop read the same choice
-        { int r = rep_ensure(h, n_slots, n_slots, (size_t)R.n_cols, R.n_dense + 1); if (r != FOT_OK) return r; }
+        { int r = rep_ensure(h, n_slots, n_slots, (size_t)R.n_cols, R.n_dense + 1, dist_S); if (r != FOT_OK) return r; }
         { int r = rep_enqueue(h, sg.slot, fd, n, dist_S, R.n_dense, R.sc.on ? R.sc.dDev.as<double>() : L.rep.dDev.as<double>(),
                               R.sc.on ? R.sc.dBest.as<int32_t>() : L.rep.dBest.as<int32_t>(),
                               (int32_t *)(R.sc.on ? R.sc.hBest.p : L.rep.hBest.p), st); if (r != FOT_OK) return r; }
@@ -974,7 +977,7 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
                                    L.ped_off[(size_t)i + 1] - L.ped_off[(size_t)i], R.n_dense + 1, 0, 1, 0 };
         LAUNCH_TRY(h, launch_loop_score_truth(rv, sg.slot, fd, rows, f_cur, R.sc.stride, C.pred_len, R.sc.dTruth.as<double>(), st));
         LAUNCH_TRY(h, launch_pred_scores(pd, n, L.dDyn.p, FOT_F64, R.sc.stride, C.pred_len, R.sc.dTruth.as<double>(),
-                                         (fot_pred_score *)R.sc.hRec.p, st));
+                                         (fot_pred_score *)R.sc.hRec.p, st, dist_S > FOT_MAX_SAMPLES ? 1 : 0));
     }
     LAUNCH_TRY(h, launch_safety(h->dP.as<DevParams>(), n, fd.ego, fd.ped0, fd.pos, fd.vel, L.ego_radius, L.ped_radius,
                                 h->sc[0].params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st,
@@ -1161,7 +1164,7 @@ int set_samples_impl(fot_handle *h, const std::string &who, int32_t S, int32_t n
     //  but the last are aligned to one)
     if ((flags & FOT_OUT_DEVICE) && (uintptr_t)samples % elem != 0)
         return fail(h, FOT_ERR_INVALID, who + ": device samples must be aligned to one [x, y] element");
-    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, who + ": S > FOT_MAX_SAMPLES");
+    if (S > h->sample_cap) return refuse_samples(h, who + ": ", S);
     if (L.ep.scenarios && !L.ep.sweep) return fail(h, FOT_ERR_UNSUPPORTED, who + ": a scenario loop plans against no distribution");
     if (R.sum.on) return fail(h, FOT_ERR_UNSUPPORTED, who + ": summaries are enabled (their prediction-error ring reads the constant-velocity tensor)");
     if (shared) {
@@ -1256,7 +1259,7 @@ int set_sampler_impl(fot_handle *h, const std::string &who, int32_t S, uint64_t 
         if (used[m] && (h->sgan[m].desc.obs_len != R.cfg.obs_len || h->sgan[m].desc.pred_len != R.cfg.pred_len))
             return fail(h, FOT_ERR_INVALID, who + ": the model's obs_len / pred_len differ from the replay's" +
                                             (by_model ? " (model " + std::to_string(m) + ")" : ""));
-    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, who + ": S > FOT_MAX_SAMPLES");
+    if (S > h->sample_cap) return refuse_samples(h, who + ": ", S);
     for (int e = 0; e < n; ++e)
         if (R.ped_off[(size_t)e + 1] - R.ped_off[(size_t)e] > FOT_SGAN_MAX_PEDS)
             return fail(h, FOT_ERR_UNSUPPORTED, who + ": a slot of more than FOT_SGAN_MAX_PEDS pedestrians");
@@ -1717,13 +1720,14 @@ int fot_loop_scores_enable(fot_handle *h, int32_t on)
     { int r = summary_arm(h, R.dist_S(), stride); if (r != FOT_OK) return r; }
     const size_t ns = (size_t)std::max(n, 1), cols = (size_t)std::max(R.n_cols, 1), E = (size_t)R.cfg.pred_len;
     HIP_TRY(h, Q.dBest.ensure(sizeof(int32_t) * ns));
-    HIP_TRY(h, Q.dDev.ensure(sizeof(double) * ns * FOT_MAX_SAMPLES));
+    const size_t dev_stride = (size_t)best_dev_stride(R.dist_S());   // (the table rows of the loop's own S)
+    HIP_TRY(h, Q.dDev.ensure(sizeof(double) * ns * dev_stride));
     HIP_TRY(h, Q.dTruth.ensure(sizeof(double) * 2 * cols * E));
     HIP_TRY(h, Q.hBest.ensure(sizeof(int32_t) * ns));
     HIP_TRY(h, Q.hDesc.ensure(sizeof(PredOriginDev) * ns));
     HIP_TRY(h, Q.hRec.ensure(sizeof(fot_pred_score) * ns));
     HIP_TRY(h, hipMemsetAsync(Q.dBest.p, 0xFF, sizeof(int32_t) * ns, h->stream));
-    HIP_TRY(h, hipMemsetAsync(Q.dDev.p, 0, sizeof(double) * ns * FOT_MAX_SAMPLES, h->stream));
+    HIP_TRY(h, hipMemsetAsync(Q.dDev.p, 0, sizeof(double) * ns * dev_stride, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     std::memset(Q.hBest.p, 0xFF, sizeof(int32_t) * ns);
     std::memset(Q.hRec.p, 0, sizeof(fot_pred_score) * ns);
@@ -1791,7 +1795,7 @@ int fot_loop_plan_sample(fot_handle *h, int32_t mode)
     if (mode == FOT_LOOP_PLAN_REPRESENTATIVE && R.set) {
         // a resident run: everything its steps need is allocated here, so that no block grows (and moves) inside the run
         HIP_TRY(h, hipSetDevice(h->device));
-        int r = rep_ensure(h, R.cfg.n_slots, R.cfg.n_slots, (size_t)R.n_cols, R.n_dense + 1);
+        int r = rep_ensure(h, R.cfg.n_slots, R.cfg.n_slots, (size_t)R.n_cols, R.n_dense + 1, R.dist_S());   // (a predictor set later: grown at its first step)
         if (r != FOT_OK) return r;
     }
     L.rep.mode = mode;

@@ -112,7 +112,7 @@ int prediction_scores_impl(fot_handle *h, const char *who, int32_t n, const fot_
     if (stride < 1 || E < 1) return fail(h, FOT_ERR_INVALID, w + ": stride and E must be positive");
     if (E > FOT_MAX_PRED_LEN) return fail(h, FOT_ERR_UNSUPPORTED, w + ": E > FOT_MAX_PRED_LEN");
     size_t rows = 0;
-    bool any = false;
+    bool any = false, wide = false;                                // wide: an origin of more than FOT_MAX_SAMPLES samples
     for (int i = 0; i < n; ++i) {
         const fot_pred_origin &d = desc[i];
         if (d.S < 1 || d.P < 0 || d.T < 1 || d.offset < 0 || (d.skip != 0 && d.skip != 1) ||
@@ -120,7 +120,8 @@ int prediction_scores_impl(fot_handle *h, const char *who, int32_t n, const fot_
             return fail(h, FOT_ERR_INVALID, w + ": an origin's S / P / T / offset / skip / layout");
         if (!ps_horizon_fits(stride, E, d.T, d.skip))
             return fail(h, FOT_ERR_INVALID, w + ": stride E - 1 reaches past an origin's dense track (T - skip)");
-        if (d.S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, w + ": S > FOT_MAX_SAMPLES");
+        if (d.S > h->sample_cap) return refuse_samples(h, w + ": ", d.S);
+        wide = wide || d.S > FOT_MAX_SAMPLES;
         rows += (size_t)d.P;
         any |= d.P > 0;
     }
@@ -153,7 +154,7 @@ int prediction_scores_impl(fot_handle *h, const char *who, int32_t n, const fot_
         HIP_TRY(h, hipMemcpyAsync(h->dScoreT.p, tensor, tensor_bytes, hipMemcpyHostToDevice, st));
         d_tensor = h->dScoreT.p;
     }
-    LAUNCH_TRY(h, launch_pred_scores(pd, n, d_tensor, dtype, stride, E, pt, (fot_pred_score *)h->hScoreOut.p, st));
+    LAUNCH_TRY(h, launch_pred_scores(pd, n, d_tensor, dtype, stride, E, pt, (fot_pred_score *)h->hScoreOut.p, st, wide ? 1 : 0));
     { int r = order_end(h, st); if (r != FOT_OK) return r; }
     HIP_TRY(h, hipStreamSynchronize(st));
     std::memcpy(out, h->hScoreOut.p, sizeof(fot_pred_score) * (size_t)n);
@@ -448,7 +449,7 @@ static int sgan_sample_impl(fot_handle *h, const std::string &who, int32_t model
         if (ped_off[i + 1] < ped_off[i]) return fail(h, FOT_ERR_INVALID, who + ": ped_off must start at 0 and be non-decreasing");
         widest = std::max(widest, ped_off[i + 1] - ped_off[i]);
     }
-    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, who + ": S > FOT_MAX_SAMPLES");
+    if (S > h->sample_cap) return refuse_samples(h, who + ": ", S);
     if (widest > FOT_SGAN_MAX_PEDS) return fail(h, FOT_ERR_UNSUPPORTED, who + ": a scene of more than FOT_SGAN_MAX_PEDS pedestrians");
     const fot_sgan_desc &d = G.desc;
     const int N = ped_off[n_scenes];
@@ -513,7 +514,7 @@ int fot_sgan_noise(fot_handle *h, uint64_t seed, int32_t kind, int32_t S, int32_
     if (kind < 0 || kind >= FOT_NOISE_KINDS) return fail(h, FOT_ERR_INVALID, "fot_sgan_noise: kind");
     if (flags & ~FOT_OUT_DEVICE) return fail(h, FOT_ERR_INVALID, "fot_sgan_noise: flags");
     if (S < 1 || rows < 0 || noise_dim < 0) return fail(h, FOT_ERR_INVALID, "fot_sgan_noise: S < 1 / rows < 0 / noise_dim < 0");
-    if (S > FOT_MAX_SAMPLES) return fail(h, FOT_ERR_UNSUPPORTED, "fot_sgan_noise: S > FOT_MAX_SAMPLES");
+    if (S > h->sample_cap) return refuse_samples(h, "fot_sgan_noise: ", S);
     if (rows == 0 || noise_dim == 0) return FOT_OK;
     if (!row_slot || !row_step || !row_index || !out) return fail(h, FOT_ERR_INVALID, "fot_sgan_noise: NULL table / out");
     for (int r = 0; r < rows; ++r)

@@ -32,10 +32,11 @@ struct PredOriginDev {
     double scott;
     int32_t S, P, T, tmajor, skip, _pad;
 };
-// desc / truth / out: HBM or pinned host memory.  The host has checked every origin (1 <= S <= FOT_MAX_SAMPLES, 1 <= E <=
-// FOT_MAX_PRED_LEN, stride E - 1 < T - skip).
+// desc / truth / out: HBM or pinned host memory.  The host has checked every origin (1 <= S <= FOT_MAX_SAMPLES -- wide: an
+// origin of the launch has more, up to FOT_MAX_PLAN_SAMPLES, and k_pred_scores_wide runs --, 1 <= E <= FOT_MAX_PRED_LEN,
+// stride E - 1 < T - skip).  An origin's record is the same bits from either kernel.
 int launch_pred_scores(const PredOriginDev *desc, int n, const void *tensor, int dtype, int stride, int E,
-                       const double *truth, fot_pred_score *out, hipStream_t st);
+                       const double *truth, fot_pred_score *out, hipStream_t st, int wide = 0);
 // What the safety metrics need of a scenario beyond its DevParams: element s of a table in HBM belongs to scenario s.
 struct SafetyScen {
     double footprint_radius;
@@ -149,8 +150,11 @@ int launch_loop_pred_error(ReplayView rv, const int32_t *slot_of, FrameDev f, co
                            hipStream_t st, const int32_t *best = nullptr);
 // ---- fot_loop_scores_enable (fot_loopscore.hpp): a resident sampler loop scores its predictor
 // The representative sample of running episode i's [S][P_i][n_dense + 1][2] block at point f.blk[i] of `dyn`:
-// dev_tab[slot][FOT_MAX_SAMPLES] (HBM) receives the S deviation sums, best_tab[slot] (HBM) and best_host[slot] (pinned) the
-// first minimum, -1 for an episode without pedestrians.  slot_of: pinned host memory.
+// dev_tab[slot][best_dev_stride(S)] (HBM) receives the S deviation sums, best_tab[slot] (HBM) and best_host[slot] (pinned)
+// the first minimum, -1 for an episode without pedestrians.  slot_of: pinned host memory.  S <= FOT_MAX_SAMPLES runs
+// k_loop_best_sample (rows FOT_MAX_SAMPLES apart, as ever), more -- up to FOT_MAX_PLAN_SAMPLES -- k_loop_best_sample_wide,
+// which takes the stride as an argument.  Whoever sizes or reads the table uses best_dev_stride of the same S.
+inline int best_dev_stride(int S) { return S > FOT_MAX_SAMPLES ? S : FOT_MAX_SAMPLES; }
 int launch_loop_best_sample(const int32_t *slot_of, FrameDev f, const double *dyn, int n_run, int S, int n_dense,
                             double *dev_tab, int32_t *best_tab, int32_t *best_host, hipStream_t st);
 // ---- fot_loop_plan_sample (fot_repsample.hpp): behind launch_loop_best_sample, running episode i's planning block

@@ -143,100 +143,23 @@ __global__ void __launch_bounds__(PS_THREADS)
 k_pred_scores(const PredOriginDev *__restrict__ desc, const TO *__restrict__ tensor, int stride, int E,
               const double *__restrict__ truth, fot_pred_score *__restrict__ out)
 {
-    __shared__ double s_g[PS_TILE_PAIRS * 2];
-    __shared__ double s_scene[2][FOT_MAX_SAMPLES][PS_WAVES];
-    __shared__ double s_part[3][PS_WAVES];
-    const PredOriginDev D = desc[blockIdx.x];
-    const int S = D.S, P = D.P, T = D.T, skip = D.skip, tmajor = D.tmajor;
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    if (P <= 0) {                                                    // (uniform)
-        if (tid == 0) {
-            fot_pred_score r;
-            r.ade_scene = r.fde_scene = r.ade_agent_sum = r.fde_agent_sum = r.log_lik_sum = 0.0;
-            r.n_peds = 0; r.n_samples = S; r.nll_count = 0; r.flags = 0;
-            out[blockIdx.x] = r;
-        }
-        return;
-    }
-    const TO *base = tensor + 2 * D.offset;
-    auto at = [&](int s, int p, int k) {                             // dense sample k: the prepended entry skipped
-        const int kk = k + skip;
-        return base + (tmajor ? ((int64_t)kk * S + s) * P + p : ((int64_t)s * P + p) * T + kk) * 2;
-    };
-    for (int i = tid; i < 2 * FOT_MAX_SAMPLES * PS_WAVES; i += PS_THREADS) (&s_scene[0][0][0])[i] = 0.0;
-    const int tile_peds = P < PS_TILE_PAIRS / E ? P : PS_TILE_PAIRS / E;
-    double agent_a = 0.0, agent_f = 0.0, ll = 0.0;
-    int varies = 0, nonfinite = 0;
-    for (int p0 = 0; p0 < P; p0 += tile_peds) {
-        const int np = P - p0 < tile_peds ? P - p0 : tile_peds;
-        __syncthreads();                                             // the tile before is done with s_g (first: the zeros)
-        const double *g_src = truth + ((int64_t)D.truth_row + p0) * E * 2;
-        for (int i = tid; i < np * E * 2; i += PS_THREADS) {
-            const double v = g_src[i];
-            nonfinite |= !ps_finite(v);
-            s_g[i] = v;
-        }
-        __syncthreads();
-        // ---- displacement terms: lanes over the tile's pedestrians
-        for (int c = 0; c < np; c += PS_THREADS) {                   // (every lane takes every turn: the butterflies)
-            const int pl = c + tid, p = p0 + pl;
-            const bool active = pl < np;
-            double best_a = 0.0, best_f = 0.0;
-            for (int s = 0; s < S; ++s) {
-                double row = 0.0, last = 0.0;
-                if (active)
-                    for (int j = 0; j < E; ++j) {
-                        const TO *e = at(s, p, stride * (j + 1) - 1);
-                        const double qx = (double)e[0], qy = (double)e[1];
-                        nonfinite |= !ps_finite(qx) || !ps_finite(qy);
-                        last = ps_dist(qx, qy, s_g[(pl * E + j) * 2], s_g[(pl * E + j) * 2 + 1]);
-                        row += last;
-                    }
-                const double a = row / (double)E;
-                best_a = s == 0 ? a : ps_min(best_a, a);
-                best_f = s == 0 ? last : ps_min(best_f, last);
-                const double w_row = wave_sum_f64(row), w_last = wave_sum_f64(last);
-                if (lane == 0) { s_scene[0][s][wave] += w_row; s_scene[1][s][wave] += w_last; }
-            }
-            agent_a += best_a; agent_f += best_f;                    // (a lane past the tile: 0.0)
-        }
-        // ---- KDE terms: lanes over the tile's (p, j) pairs
-        if (S >= 2)
-            for (int i = tid; i < np * E; i += PS_THREADS) {
-                const int pl = i / E, j = i - pl * E, p = p0 + pl, k = stride * (j + 1) - 1;
-                auto qx = [&](int s) { return (double)at(s, p, k)[0]; };
-                auto qy = [&](int s) { return (double)at(s, p, k)[1]; };
-                bool vx, vy;
-                const double bx = ps_bandwidth(S, D.scott, qx, &vx), by = ps_bandwidth(S, D.scott, qy, &vy);
-                varies |= vx || vy;
-                ll += ps_log_p(S, qx, qy, s_g[i * 2], s_g[i * 2 + 1], bx, by);
-            }
-    }
-    const double w_a = wave_sum_f64(agent_a), w_f = wave_sum_f64(agent_f), w_l = wave_sum_f64(ll);
-    if (lane == 0) { s_part[0][wave] = w_a; s_part[1][wave] = w_f; s_part[2][wave] = w_l; }
-    varies = __syncthreads_or(varies);                               // (also orders s_part and s_scene for thread 0)
-    nonfinite = __syncthreads_or(nonfinite);
-    if (tid != 0) return;
-    double tot[3];
-    for (int q = 0; q < 3; ++q) {
-        tot[q] = s_part[q][0];
-        for (int w = 1; w < PS_WAVES; ++w) tot[q] += s_part[q][w];
-    }
-    fot_pred_score r;
-    r.ade_scene = r.fde_scene = 0.0;
-    for (int s = 0; s < S; ++s) {
-        double a = s_scene[0][s][0], f = s_scene[1][s][0];
-        for (int w = 1; w < PS_WAVES; ++w) { a += s_scene[0][s][w]; f += s_scene[1][s][w]; }
-        a /= (double)P * (double)E; f /= (double)P;
-        r.ade_scene = s == 0 ? a : ps_min(r.ade_scene, a);
-        r.fde_scene = s == 0 ? f : ps_min(r.fde_scene, f);
-    }
-    r.ade_agent_sum = tot[0]; r.fde_agent_sum = tot[1];
-    r.log_lik_sum = varies ? tot[2] : 0.0;
-    r.n_peds = P; r.n_samples = S;
-    r.nll_count = varies ? P * E : 0;
-    r.flags = (varies ? PS_FLAG_NLL : 0) | (nonfinite ? PS_FLAG_NONFINITE : 0);
-    out[blockIdx.x] = r;
+#define PS_ROWS FOT_MAX_SAMPLES
+#include "fot_pred_scores_body.inc"
+#undef PS_ROWS
+}
+
+// The wide form: a launch with an origin of more than FOT_MAX_SAMPLES samples (a handle with a raised sample capacity).
+// The same body (fot_pred_scores_body.inc) over tables of FOT_MAX_PLAN_SAMPLES rows (2 x 254 x 4 doubles, 16 KB beside the
+// tile's 16 KB): an origin's sums are taken in the same order in either form, so a narrow origin of a wide launch has the
+// record it has alone.
+template <typename TO>
+__global__ void __launch_bounds__(PS_THREADS)
+k_pred_scores_wide(const PredOriginDev *__restrict__ desc, const TO *__restrict__ tensor, int stride, int E,
+                   const double *__restrict__ truth, fot_pred_score *__restrict__ out)
+{
+#define PS_ROWS FOT_MAX_PLAN_SAMPLES
+#include "fot_pred_scores_body.inc"
+#undef PS_ROWS
 }
 
 // ---------------------------------------------------------------------------
@@ -553,12 +476,17 @@ constexpr int BS_THREADS = 256;
 constexpr int BS_WAVES = BS_THREADS / WAVE;
 
 // (the body of both forms: running episode i = blockIdx.x, checked by the caller)
+// ROWS: the rows of the per-sample tables in LDS (S <= ROWS, checked by the launcher); dev_stride: the row stride of dev_tab
+// (the narrow forms hand in the constant FOT_MAX_SAMPLES, the wide ones their launch argument)
+static_assert(FOT_MAX_PLAN_SAMPLES <= BS_THREADS, "the fold of the waves' columns: one thread per sample (tid < S)");
+template <int ROWS>
 __device__ __forceinline__ void
 best_sample_episode(const int32_t *__restrict__ slot_of, const FrameDev &f, const double *__restrict__ dyn, int S,
-                    int n_dense, double *__restrict__ dev_tab, int32_t *__restrict__ best_tab, int32_t *best_host)
+                    int n_dense, double *__restrict__ dev_tab, int dev_stride, int32_t *__restrict__ best_tab,
+                    int32_t *best_host)
 {
-    __shared__ double s_part[FOT_MAX_SAMPLES][BS_WAVES];
-    __shared__ double s_dev[FOT_MAX_SAMPLES];
+    __shared__ double s_part[ROWS][BS_WAVES];
+    __shared__ double s_dev[ROWS];
     const int i = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
     const int slot = slot_of[i], p0 = f.ped0[i], P = f.ped0[i + 1] - p0;
     if (P <= 0) {                                                    // (uniform)
@@ -568,7 +496,7 @@ best_sample_episode(const int32_t *__restrict__ slot_of, const FrameDev &f, cons
     const int T = n_dense + 1, n = P * n_dense;
     const int64_t sample_pts = (int64_t)P * T;
     const double2 *blk = (const double2 *)dyn + f.blk[i];
-    for (int c = tid; c < FOT_MAX_SAMPLES * BS_WAVES; c += BS_THREADS) (&s_part[0][0])[c] = 0.0;
+    for (int c = tid; c < ROWS * BS_WAVES; c += BS_THREADS) (&s_part[0][0])[c] = 0.0;
     __syncthreads();
     for (int base = 0; base < n; base += BS_THREADS) {               // (uniform trip count: the butterflies)
         const int idx = base + tid;
@@ -598,7 +526,7 @@ best_sample_episode(const int32_t *__restrict__ slot_of, const FrameDev &f, cons
         double t = s_part[tid][0];
         for (int w = 1; w < BS_WAVES; ++w) t += s_part[tid][w];
         s_dev[tid] = t;
-        dev_tab[(int64_t)slot * FOT_MAX_SAMPLES + tid] = t;
+        dev_tab[(int64_t)slot * dev_stride + tid] = t;
     }
     __syncthreads();
     if (tid == 0) {
@@ -612,7 +540,19 @@ k_loop_best_sample(const int32_t *__restrict__ slot_of, FrameDev f, const double
                    int n_dense, double *__restrict__ dev_tab, int32_t *__restrict__ best_tab, int32_t *best_host)
 {
     if ((int)blockIdx.x >= n_run) return;
-    best_sample_episode(slot_of, f, dyn, S, n_dense, dev_tab, best_tab, best_host);
+    best_sample_episode<FOT_MAX_SAMPLES>(slot_of, f, dyn, S, n_dense, dev_tab, FOT_MAX_SAMPLES, best_tab, best_host);
+}
+
+// The wide form: S > FOT_MAX_SAMPLES on a handle with a raised sample capacity.  The same body over tables of
+// FOT_MAX_PLAN_SAMPLES rows (254 x 4 + 254 doubles, 10 KB); dev_tab's rows are dev_stride apart.  The shape of the sums is
+// the narrow form's -- a butterfly per (sample, pass, wave), the passes in order, the waves in index order.
+__global__ void __launch_bounds__(BS_THREADS)
+k_loop_best_sample_wide(const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn, int n_run, int S,
+                        int n_dense, double *__restrict__ dev_tab, int dev_stride, int32_t *__restrict__ best_tab,
+                        int32_t *best_host)
+{
+    if ((int)blockIdx.x >= n_run) return;
+    best_sample_episode<FOT_MAX_PLAN_SAMPLES>(slot_of, f, dyn, S, n_dense, dev_tab, dev_stride, best_tab, best_host);
 }
 
 // The sweep form (fot_sweep.hpp): only the episodes whose table row asks for it choose; the others leave their slot's
@@ -623,7 +563,16 @@ k_loop_best_sample_sweep(const int32_t *__restrict__ slot_of, FrameDev f, const 
                          int32_t *__restrict__ best_tab, int32_t *best_host)
 {
     if ((int)blockIdx.x >= n_run || tab[blockIdx.x].select == 0) return;     // (uniform)
-    best_sample_episode(slot_of, f, dyn, S, n_dense, dev_tab, best_tab, best_host);
+    best_sample_episode<FOT_MAX_SAMPLES>(slot_of, f, dyn, S, n_dense, dev_tab, FOT_MAX_SAMPLES, best_tab, best_host);
+}
+
+__global__ void __launch_bounds__(BS_THREADS)
+k_loop_best_sample_sweep_wide(const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn,
+                              const SweepEp *__restrict__ tab, int n_run, int S, int n_dense, double *__restrict__ dev_tab,
+                              int dev_stride, int32_t *__restrict__ best_tab, int32_t *best_host)
+{
+    if ((int)blockIdx.x >= n_run || tab[blockIdx.x].select == 0) return;     // (uniform)
+    best_sample_episode<FOT_MAX_PLAN_SAMPLES>(slot_of, f, dyn, S, n_dense, dev_tab, dev_stride, best_tab, best_host);
 }
 
 // One thread per (row of the frame, evaluation step j): the truth of the step's origins, [rows][E][2], from the resident
@@ -1189,10 +1138,13 @@ int launch_sample_dist(int S, int P, int T, int skip, const void *out, int out_d
 }
 
 int launch_pred_scores(const PredOriginDev *desc, int n, const void *tensor, int dtype, int stride, int E,
-                       const double *truth, fot_pred_score *out, hipStream_t st)
+                       const double *truth, fot_pred_score *out, hipStream_t st, int wide)
 {
     if (n <= 0) return 0;
-    if (dtype == FOT_F32) k_pred_scores<float><<<n, PS_THREADS, 0, st>>>(desc, (const float *)tensor, stride, E, truth, out);
+    if (wide) {
+        if (dtype == FOT_F32) k_pred_scores_wide<float><<<n, PS_THREADS, 0, st>>>(desc, (const float *)tensor, stride, E, truth, out);
+        else k_pred_scores_wide<double><<<n, PS_THREADS, 0, st>>>(desc, (const double *)tensor, stride, E, truth, out);
+    } else if (dtype == FOT_F32) k_pred_scores<float><<<n, PS_THREADS, 0, st>>>(desc, (const float *)tensor, stride, E, truth, out);
     else k_pred_scores<double><<<n, PS_THREADS, 0, st>>>(desc, (const double *)tensor, stride, E, truth, out);
     FOT_LAUNCH_CHECK();
     return 0;
@@ -1288,8 +1240,12 @@ int launch_loop_best_sample(const int32_t *slot_of, FrameDev f, const double *dy
                             double *dev_tab, int32_t *best_tab, int32_t *best_host, hipStream_t st)
 {
     if (n_run <= 0) return 0;
-    if (S < 1 || S > FOT_MAX_SAMPLES || n_dense < 1) return (int)hipErrorInvalidValue;
-    k_loop_best_sample<<<n_run, BS_THREADS, 0, st>>>(slot_of, f, dyn, n_run, S, n_dense, dev_tab, best_tab, best_host);
+    if (S < 1 || S > FOT_MAX_PLAN_SAMPLES || n_dense < 1) return (int)hipErrorInvalidValue;
+    if (S > FOT_MAX_SAMPLES)
+        k_loop_best_sample_wide<<<n_run, BS_THREADS, 0, st>>>(slot_of, f, dyn, n_run, S, n_dense, dev_tab, best_dev_stride(S),
+                                                              best_tab, best_host);
+    else
+        k_loop_best_sample<<<n_run, BS_THREADS, 0, st>>>(slot_of, f, dyn, n_run, S, n_dense, dev_tab, best_tab, best_host);
     FOT_LAUNCH_CHECK();
     return 0;
 }
@@ -1298,8 +1254,12 @@ int launch_loop_best_sample_sweep(const int32_t *slot_of, FrameDev f, const doub
                                   int n_dense, double *dev_tab, int32_t *best_tab, int32_t *best_host, hipStream_t st)
 {
     if (n_run <= 0) return 0;
-    if (S < 1 || S > FOT_MAX_SAMPLES || n_dense < 1 || !tab) return (int)hipErrorInvalidValue;
-    k_loop_best_sample_sweep<<<n_run, BS_THREADS, 0, st>>>(slot_of, f, dyn, tab, n_run, S, n_dense, dev_tab, best_tab, best_host);
+    if (S < 1 || S > FOT_MAX_PLAN_SAMPLES || n_dense < 1 || !tab) return (int)hipErrorInvalidValue;
+    if (S > FOT_MAX_SAMPLES)
+        k_loop_best_sample_sweep_wide<<<n_run, BS_THREADS, 0, st>>>(slot_of, f, dyn, tab, n_run, S, n_dense, dev_tab,
+                                                                    best_dev_stride(S), best_tab, best_host);
+    else
+        k_loop_best_sample_sweep<<<n_run, BS_THREADS, 0, st>>>(slot_of, f, dyn, tab, n_run, S, n_dense, dev_tab, best_tab, best_host);
     FOT_LAUNCH_CHECK();
     return 0;
 }
@@ -1309,7 +1269,7 @@ int launch_loop_rep_block_sweep(const int32_t *slot_of, FrameDev f, const double
                                 int32_t *pre_host, hipStream_t st)
 {
     if (n_run <= 0) return 0;
-    if (S < 1 || S > FOT_MAX_SAMPLES || n_dense < 1 || !tab) return (int)hipErrorInvalidValue;
+    if (S < 1 || S > FOT_MAX_PLAN_SAMPLES || n_dense < 1 || !tab) return (int)hipErrorInvalidValue;
     k_loop_rep_block_sweep<<<n_run, RB_THREADS, 0, st>>>(slot_of, f, dyn, tab, best_tab, n_run, S, n_dense, tensor, pre_dev, pre_host);
     FOT_LAUNCH_CHECK();
     return 0;
@@ -1319,7 +1279,7 @@ int launch_loop_rep_block(const int32_t *slot_of, FrameDev f, const double *dyn,
                           int n_dense, double *rep, int32_t *pre_dev, int32_t *pre_host, hipStream_t st)
 {
     if (n_run <= 0) return 0;
-    if (S < 1 || S > FOT_MAX_SAMPLES || n_dense < 1) return (int)hipErrorInvalidValue;
+    if (S < 1 || S > FOT_MAX_PLAN_SAMPLES || n_dense < 1) return (int)hipErrorInvalidValue;
     k_loop_rep_block<<<n_run, RB_THREADS, 0, st>>>(slot_of, f, dyn, best_tab, n_run, S, n_dense, rep, pre_dev, pre_host);
     FOT_LAUNCH_CHECK();
     return 0;

@@ -160,7 +160,8 @@ class BatchPlanner:
 
     def __init__(self, reference_path=None, waypoints=None, device: int = -1, sample_capacity: Optional[int] = None,
                  **planner_kwargs):
-        """``sample_capacity``: the most samples S of a prediction distribution the handle plans and checks against,
+        """``sample_capacity``: the most samples S of a prediction distribution the handle accepts -- in plan calls, the
+        closed loop's frames, recordings and samplers, the Social-GAN generator and the prediction scores --,
         ``_abi.MAX_SAMPLES`` (64, the default: ``None`` makes no call) to ``_abi.MAX_PLAN_SAMPLES`` (254); see
         ``set_sample_capacity``."""
         self._lib = _abi.lib()
@@ -206,8 +207,9 @@ class BatchPlanner:
     # -- capacities -------------------------------------------------------
     @property
     def sample_capacity(self) -> int:
-        """Most samples of a prediction distribution ``plan_batch``, ``paths_collision_free`` and ``check_paths`` accept
-        (``fot_get_sample_capacity``); 64 unless raised."""
+        """Most samples of a prediction distribution any entry of the handle accepts -- ``plan_batch``,
+        ``paths_collision_free``, ``check_paths``, the loop's frames, ``loop_set_samples``, ``loop_set_sampler``,
+        ``sgan_noise``, the generator and ``prediction_scores`` (``fot_get_sample_capacity``); 64 unless raised."""
         n = C.c_int32(0)
         _abi.check(self._h, self._lib.fot_get_sample_capacity(self._h, C.byref(n)))
         return n.value
@@ -215,8 +217,11 @@ class BatchPlanner:
     def set_sample_capacity(self, n: int) -> None:
         """``fot_set_sample_capacity``: ``_abi.MAX_SAMPLES <= n <= _abi.MAX_PLAN_SAMPLES``, for all scenarios of the handle.
         A plan call with an instance of more than 64 samples runs evaluation kernels of its own ("lean-wide" /
-        "general-wide" in ``last_eval_form``); every other call runs what it ran before.  The closed loop, the samplers
-        and the scores keep 64."""
+        "general-wide" in ``last_eval_form``); every other call runs what it ran before.  The capacity is that of every
+        entry that takes a sample distribution: the closed loop (five-call, one-call, resident, sweep), recorded samples,
+        the Social-GAN sampler and the prediction scores accept S <= n too, and more than 64 samples run wide forms of
+        the score and selection kernels.  Lowering it below the samples of a loop that is set up raises.  Out of scope:
+        ``openloop_eval`` keeps 64, and the slots of one sweep share one sample count."""
         _abi.check(self._h, self._lib.fot_set_sample_capacity(self._h, int(n)))
 
     # -- reference path ---------------------------------------------------

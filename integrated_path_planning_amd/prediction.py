@@ -171,6 +171,13 @@ def fold_batch_norm(weight, bias, bn_weight, bn_bias, running_mean, running_var,
 _NOISE_TYPES = ("gaussian", "uniform")
 
 
+def _checked_capacity(who: str, n) -> int:
+    """A constructor's ``sample_capacity``: what a handle can be raised to."""
+    if not _abi.MAX_SAMPLES <= int(n) <= _abi.MAX_PLAN_SAMPLES:
+        raise ValueError(f"{who}: {_abi.MAX_SAMPLES} <= sample_capacity <= {_abi.MAX_PLAN_SAMPLES}, got {n}")
+    return int(n)
+
+
 class SganWeights:
     """A Social-GAN generator as ``fot_sgan_load`` takes it: the descriptor and ONE packed float32 blob in the order
     include/fot.h documents, BatchNorm folded into the Linear in front of it."""
@@ -352,15 +359,19 @@ class SganSampler:
     campaign cell in one loop.  Every active (crowd, model) pair is sampled once per lock step, the noise keyed by the
     crowd's id with the model's own dimensions, mix type and ``noise_type`` (``fot_loop_set_sampler_models``; ``sample``
     forms the same bytes through ``fot_sgan_sample_model``): a slot's numbers are those of the loop that holds only its model.
-    engine None: the sampler joins the engine of the loop it is handed to (``bind``)."""
+    engine None: the sampler joins the engine of the loop it is handed to (``bind``).
+    sample_capacity: more than 64 samples, up to ``_abi.MAX_PLAN_SAMPLES`` (254) -- the engine it runs on needs that
+    capacity too (``BatchPlanner(sample_capacity=)``, ``BatchedClosedLoop(sample_capacity=)``)."""
     needs_history = True
 
     def __init__(self, engine: Optional[BatchPlanner], weights: SganWeights, num_samples: int, seed: Optional[int] = None,
-                 noise_type: Optional[str] = None, counter_seed: Optional[int] = None, slot_crowd=None, slot_model=None):
+                 noise_type: Optional[str] = None, counter_seed: Optional[int] = None, slot_crowd=None, slot_model=None,
+                 sample_capacity: int = _abi.MAX_SAMPLES):
         if noise_type is not None and noise_type not in _NOISE_TYPES:
             raise ValueError(f'Unrecognized noise type "{noise_type}"')
-        if not 1 <= int(num_samples) <= _abi.MAX_SAMPLES:
-            raise ValueError(f"SganSampler: 1 <= num_samples <= {_abi.MAX_SAMPLES}")
+        self.sample_capacity = _checked_capacity("SganSampler", sample_capacity)
+        if not 1 <= int(num_samples) <= self.sample_capacity:
+            raise ValueError(f"SganSampler: 1 <= num_samples <= {self.sample_capacity}")
         self.models = None if isinstance(weights, SganWeights) else list(weights)
         if self.models is not None:
             if not 1 <= len(self.models) <= int(_abi.lib().fot_sgan_max_models()):
@@ -722,11 +733,14 @@ class RecordedSamples:
 
     slot_col0: the recording's columns are not the loop's -- pedestrian p of slot e reads column ``slot_col0[e] + p``, and
     several slots may name the same columns: the K conditions of a sweep over one crowd share ONE copy of its samples
-    (``fot_loop_set_samples_shared``).  The stepwise call cuts its rows through the same map."""
+    (``fot_loop_set_samples_shared``).  The stepwise call cuts its rows through the same map.
+    sample_capacity: more than 64 samples per step, up to ``_abi.MAX_PLAN_SAMPLES`` (254); the loop's engine needs that
+    capacity too (``BatchedClosedLoop(sample_capacity=)``)."""
     needs_history = True
     recorded = True
 
-    def __init__(self, samples, first_step: int = 0, slot_col0=None):
+    def __init__(self, samples, first_step: int = 0, slot_col0=None, sample_capacity: int = _abi.MAX_SAMPLES):
+        self.sample_capacity = _checked_capacity("RecordedSamples", sample_capacity)
         on_device = hasattr(samples, "data_ptr")
         if on_device:
             import torch
@@ -741,8 +755,8 @@ class RecordedSamples:
                 raise ValueError(f"RecordedSamples: float32 or float64 samples, got {samples.dtype}")
         if samples.ndim != 5 or samples.shape[-1] != 2:
             raise ValueError(f"RecordedSamples: samples are [n_steps, S, pred_len, sum P, 2], got {tuple(samples.shape)}")
-        if samples.shape[0] < 1 or not 1 <= samples.shape[1] <= _abi.MAX_SAMPLES:
-            raise ValueError(f"RecordedSamples: n_steps >= 1 and 1 <= S <= {_abi.MAX_SAMPLES}, got {tuple(samples.shape)}")
+        if samples.shape[0] < 1 or not 1 <= samples.shape[1] <= self.sample_capacity:
+            raise ValueError(f"RecordedSamples: n_steps >= 1 and 1 <= S <= {self.sample_capacity}, got {tuple(samples.shape)}")
         if int(first_step) < 0:
             raise ValueError("RecordedSamples: first_step >= 0")
         self.samples = samples.contiguous() if on_device else np.ascontiguousarray(samples)
@@ -822,15 +836,21 @@ class RecordedSamples:
 
 
 def record_samples(config, ped_tracks, sample_source, n_steps: int, dtype=np.float32, device=None,
-                   warmup_frames: Optional[int] = None) -> RecordedSamples:
+                   warmup_frames: Optional[int] = None, sample_capacity: Optional[int] = None) -> RecordedSamples:
     """Run the closed loop's observer clock over the replayed tracks -- no ego, no planning -- and record what
     ``sample_source`` predicts at every lock step: the warm-up of ``int(obs_len * sgan_dt / dt)`` frames, then ``n_steps``
     steps; at every step where the observer is ready the source is called for the pedestrians of ALL episodes, as a
     stepwise ``BatchedClosedLoop`` calls it (``(obs_last, obs_prev)``, or the window and the offsets for a
     ``needs_history`` source; ``slots`` / ``steps`` for a counter-seeded one).  Steps before that stay NaN: they are never
     read.  dtype: float32 or float64; device: None -- a host array, else the ``torch`` device the recording is kept on;
-    warmup_frames: for a caller of ``fot_loop_set_replay`` with a warm-up of its own (None: the loop's)."""
+    warmup_frames: for a caller of ``fot_loop_set_replay`` with a warm-up of its own (None: the loop's).
+    sample_capacity: the recording's (``RecordedSamples(sample_capacity=)``); None: the capacity of the source's engine
+    where it has one, else the source's own ``sample_capacity``, else 64."""
     from .closed_loop import Observer, ReplayPedestrians, _Cfg
+    if sample_capacity is None:
+        sample_capacity = getattr(getattr(sample_source, "engine", None), "sample_capacity", None)
+    if sample_capacity is None:
+        sample_capacity = getattr(sample_source, "sample_capacity", _abi.MAX_SAMPLES)
     c = _Cfg(config) if isinstance(config, dict) else config
     dtype = np.dtype(dtype)
     if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
@@ -895,6 +915,6 @@ def record_samples(config, ped_tracks, sample_source, n_steps: int, dtype=np.flo
     elif not hasattr(out, "detach") and device is not None:
         import torch
         out = torch.from_numpy(out).to(device)
-    rec = RecordedSamples(out, first_step=0)
+    rec = RecordedSamples(out, first_step=0, sample_capacity=int(sample_capacity))
     rec.attach(off, int(out.shape[2]))
     return rec
