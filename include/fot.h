@@ -312,8 +312,8 @@ int fot_debug_set_eval_form(fot_handle *h, int32_t form);
  * capacity, so nothing of a begun loop moves).  LOWERING it below the samples of the handle's loop -- the S of a resident
  * loop's sampler or recording (from the set call until the next fot_loop_begin* / fot_loop_set_replay), or the dist_S of
  * a stepwise loop's current frame -- is FOT_ERR_INVALID and leaves the capacity as it was.
- * Out of scope: fot_openloop_eval keeps FOT_MAX_SAMPLES whatever the handle's capacity; the slots of one sweep share one
- * sample count; summaries together with a sampler or a recording stay refused.
+ * Out of scope: fot_openloop_eval keeps FOT_MAX_SAMPLES whatever the handle's capacity; summaries together with a sampler
+ * or a recording stay refused.  (The slots of one sweep may keep sample counts of their own: fot_loop_set_slot_samples.)
  * fot_max_plan_samples: the FOT_MAX_PLAN_SAMPLES the library was built with, for a binding to compare with its own.
  * Additions: no structure, capacity word of fot_abi_info or FOT_ABI_VERSION changes; a binding looks the symbols up. */
 int fot_set_sample_capacity(fot_handle *h, int32_t n_samples);
@@ -1039,6 +1039,43 @@ int fot_loop_set_sampler_models(fot_handle *h, int32_t S, uint64_t seed, int32_t
 int fot_debug_loop_sampler_shapes(fot_handle *h, int32_t cap, int32_t *n_scenes, int32_t *n_rows);
 int fot_loop_set_samples_shared(fot_handle *h, int32_t S, int32_t n_steps, int32_t first_step, const void *samples,
                                 int32_t dtype, int32_t flags, int32_t n_rec_cols, const int32_t *slot_col0);
+
+/* ---- a sample count per slot of a sweep loop -------------------------------------------------------------------------------------
+ * fot_loop_set_slot_samples(h, n_slots, slot_S): slot e of a sweep loop (fot_loop_begin_sweep) uses the FIRST slot_S[e]
+ * samples of what its source provides -- the sample-count ablation (5, 10, 20, 50, 100 samples of one predictor output over
+ * one crowd) as slots of ONE loop, whose crowd is gathered or sampled once per lock step.  Every number of slot e -- records,
+ * chosen samples, planning blocks, scores, summaries -- is the bits of the uniform loop of its configuration run on those
+ * slot_S[e] samples alone: the chance budget floor(eps * slot_S[e]), best-of-N over slot_S[e] samples, the KDE bandwidth of
+ * slot_S[e] samples.  The counter noise is keyed by the sample index and the generator's samples are independent of one
+ * another, so the first k samples of a sampler of S are the samples of a sampler of k.
+ * When: on a sweep loop, after the source is set and before the first step.  A resident loop's source is
+ * fot_loop_set_samples(_shared) or fot_loop_set_sampler(_shared, _models) and 1 <= slot_S[e] <= its S.  A stepwise sweep
+ * (fot_loop_step) takes the call before its first step with 1 <= slot_S[e] <= the handle's sample capacity; the source's
+ * count is then every frame's dist_S, and a frame whose dist_S lies below the count of one of its episodes' slots is
+ * FOT_ERR_INVALID.  fot_loop_begin*, fot_loop_set_replay and a new fot_loop_set_samples* / fot_loop_set_sampler* call drop
+ * the counts with what they drop.  Lowering the handle's sample capacity is judged against the source's S, as before.
+ * A step: running episode i keeps a block [S_i][P_i][T][2] of the step's tensor, the blocks packed by prefix sum and the
+ * planning blocks of the representative-mode episodes behind them (fot_sweep.hpp); the gather of a recording's row and the
+ * sampler move or draw no more than the largest count among the loop's slots; the ragged resample's work follows
+ * sum S_i P_i; selection, planning block, plan request and score origin of an episode take its own S_i; a launch is wide
+ * when one of its running episodes has more than FOT_MAX_SAMPLES samples, so a step whose running counts are all within
+ * FOT_MAX_SAMPLES takes the narrow launches whatever the source's S.  Without the call, and in every step whose running
+ * slots all have slot_S[e] == S, the launches and bytes are those of before.
+ * fot_loop_last_best_sample and fot_loop_run_best_samples answer in [0, slot_S[e]); fot_debug_loop_block answers with the
+ * episode's own count of samples; fot_loop_score_summaries reports pred_samples per slot.
+ * Refused, nothing changed: FOT_ERR_INVALID -- h or slot_S NULL; n_slots not the loop's; an entry outside 1 .. S; a resident
+ * loop without a source; after the first step.  FOT_ERR_UNSUPPORTED -- a loop that is not a sweep loop (fot_loop_begin and
+ * fot_loop_begin_scenarios loops keep one count, and their kernels are untouched).
+ * Not supported: one distribution block per crowd; the cost of a slot of more than FOT_MAX_SAMPLES samples is that of the wide
+ * selection and score kernels' sequential sample walk and of k_cull's NaN scan, as in a uniform loop of that count.
+ *
+ * fot_debug_loop_slot_samples(h, n_slots, out) (tests): out[i] = the sample count of running episode i of the most recent
+ * frame (0: it carried no distribution), -1 behind the frame's episodes; n_slots: the entries of out, at least the frame's
+ * episodes.  It shows that the counts were used, not only that the numbers look right.
+ * Both entries are additions: no structure, capacity word of fot_abi_info or FOT_ABI_VERSION changes; a binding looks the
+ * symbols up. */
+int fot_loop_set_slot_samples(fot_handle *h, int32_t n_slots, const int32_t *slot_S);
+int fot_debug_loop_slot_samples(fot_handle *h, int32_t n_slots, int32_t *out);
 
 /* ---- open-loop prediction evaluation of a whole scene (RQ1a) ------------------------------------------------------------------
  * The reference's examples/run_openloop_prediction.py (evaluate_window / evaluate_scene) in ONE stateless, synchronous call:

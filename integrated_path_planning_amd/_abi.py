@@ -246,7 +246,7 @@ SYMBOLS = ["fot_version", "fot_abi_info", "fot_create", "fot_destroy", "fot_live
            "fot_loop_set_sampler_models", "fot_debug_loop_sampler_shapes", "fot_openloop_eval",
            "fot_footprint_recheck", "fot_loop_footprint_enable", "fot_loop_footprint_obs", "fot_fidelity_eval",
            "fot_encounters_extract", "fot_set_sample_capacity", "fot_get_sample_capacity",
-           "fot_max_plan_samples"]
+           "fot_max_plan_samples", "fot_loop_set_slot_samples", "fot_debug_loop_slot_samples"]
 LOOP_PLAN_DISTRIBUTION, LOOP_PLAN_REPRESENTATIVE = 0, 1      # FOT_LOOP_PLAN_* (fot_loop_plan_sample)
 PROFILE_KERNELS = 3                      # FOT_PROFILE_KERNELS (include/fot.h)
 ABI_VERSION = 8                          # FOT_ABI_VERSION
@@ -528,7 +528,9 @@ def lib():
                        ("fot_loop_footprint_obs", [vp, C.c_int32, vp]),
                        ("fot_fidelity_eval", [vp, C.POINTER(FidelityParams), C.c_int32] + [vp] * 11),
                        ("fot_encounters_extract", [vp, C.POINTER(EncounterParams), C.c_int32, C.c_int32, C.c_int32] + [vp] * 5 +
-                                                  [C.c_int32, C.c_int64] + [vp] * 9 + [C.c_int64])):
+                                                  [C.c_int32, C.c_int64] + [vp] * 9 + [C.c_int64]),
+                       ("fot_loop_set_slot_samples", [vp, C.c_int32, vp]),
+                       ("fot_debug_loop_slot_samples", [vp, C.c_int32, vp])):
         if hasattr(L, name):
             getattr(L, name).argtypes = args
     L.fot_gather_paths.argtypes = [vp, C.c_int32, vp, C.c_int32, vp]

@@ -252,6 +252,8 @@ class _ResidentStep(dict):
                 pred_src = ("sgan", window, sel, np.full(n, self.lock_step, np.int64), o32, float(o["staleness"][k]))
                 if self.best is not None:                             # the sample the device chose and planned on
                     pred_src = pred_src + (self.best[sel].astype(np.int64),)
+                if loop._slot_samples is not None:                    # ... among the episodes' own sample counts
+                    pred_src = pred_src + (() if self.best is not None else (np.full(n, -1, np.int64),)) + (loop._slot_samples[sel],)
         if keep_paths:
             paths = {f: o["paths"][k, j][sel] for j, f in enumerate(_abi.PATH_FIELDS)}
         else:
@@ -506,6 +508,11 @@ class BatchedClosedLoop:
         samples every crowd once per lock step for all its conditions, fot_loop_set_sampler_shared; built on several
         ``SganWeights`` with ``slot_model=...`` it gives every slot its own model, fot_loop_set_sampler_models).  A list of one
         distinct scenario and one mode is today's loop.
+        A source built with ``slot_samples=[...]`` (``RecordedSamples``, ``SganSampler``) gives slot e the first
+        ``slot_samples[e]`` samples of what it provides (fot_loop_set_slot_samples): a sweep as well, also with ONE
+        configuration, which then stands for every slot.  ``pred_samples`` of ``prediction_metrics()``,
+        ``aggregate_metrics()`` and ``save_summaries()`` is the slot's own count.  The five-call step and stand-in
+        engines raise ValueError.
         footprint_obs: True, or a dictionary with any of ``vehicle_length``, ``vehicle_width``, ``n_circles``,
         ``ped_radius`` (the reference's fixed 4.5 / 2.0 / 3 / 0.2 where missing): every lock step also measures the new ego
         state against that step's pedestrians under three geometries that are the same whatever footprint the planner
@@ -556,6 +563,20 @@ class BatchedClosedLoop:
         # distinct scenario runs through the one-call step or resident=True only
         self.scenarios, self.slot_scenario, per_episode = None, None, None
         self._sweep, self._slot_aware, any_aware = False, None, False
+        # a sample count per slot (the source's slot_samples): a sweep loop whose slot e plans against the first
+        # slot_samples[e] samples (fot_loop_set_slot_samples); ONE configuration is then the sweep of it for every slot
+        counts = getattr(sample_source, "slot_samples", None)
+        self._slot_samples = None if counts is None else np.asarray(counts, dtype=np.int64).reshape(-1)
+        if self._slot_samples is not None:
+            if len(self._slot_samples) != len(ped_tracks):
+                raise ValueError(f"the sample source's slot_samples names {len(self._slot_samples)} slots, the loop has "
+                                 f"{len(ped_tracks)} episodes")
+            if not (device_samples and engine is None and resampler is None and fused in (None, True)):
+                raise ValueError("slot_samples needs device_samples=True and the one-call step (fused=None / True) or "
+                                 "resident=True on the library's own engine: the five-call step and stand-in engines plan "
+                                 "against one sample count")
+            if not isinstance(config, (list, tuple)):
+                config = [config] * len(ped_tracks)
         if isinstance(config, (list, tuple)):
             if len(config) != len(ped_tracks):
                 raise ValueError(f"{len(config)} configurations for {len(ped_tracks)} episodes: one configuration per episode")
@@ -563,7 +584,7 @@ class BatchedClosedLoop:
             aware = np.array([bool(getattr(k, "distribution_aware_planning", False)) for k in per_episode])
             any_aware, mixed = bool(aware.any()), bool(aware.any() and not aware.all())
             # a sweep: more than one scenario and / or mixed plan modes over a sample source whose samples stay in HBM
-            self._sweep = bool((len(distinct) > 1 or mixed) and sample_source is not None and device_samples
+            self._sweep = bool((len(distinct) > 1 or mixed or self._slot_samples is not None) and sample_source is not None and device_samples
                                and engine is None and resampler is None and fused in (None, True))
             config = distinct[0]
             if self._sweep:
@@ -733,6 +754,8 @@ class BatchedClosedLoop:
                 [loop_config_from(k, constants_of(k), self.MAX_REPLAN) for k in self.scenarios],
                 [fp_k is not None for fp_k in self.scenario_footprints], self.slot_scenario,
                 np.where(self._slot_aware, _abi.LOOP_PLAN_DISTRIBUTION, _abi.LOOP_PLAN_REPRESENTATIVE), self.ego)
+            if self._slot_samples is not None and not self._resident:    # (a stepwise sweep: every frame brings the source's count)
+                self.engine.loop_set_slot_samples(self._slot_samples)
         elif self._native and self.scenarios is not None:
             self.engine.loop_begin_scenarios(
                 [loop_config_from(k, constants_of(k), self.MAX_REPLAN) for k in self.scenarios],
@@ -760,6 +783,8 @@ class BatchedClosedLoop:
                                              n_rec_cols=sample_source.n_cols, slot_col0=sample_source.slot_col0)
             elif self._resident_recording:
                 self.engine.loop_set_samples(sample_source.samples, sample_source.first_step)
+            if self._slot_samples is not None:                        # (behind the source, whose S bounds the counts)
+                self.engine.loop_set_slot_samples(self._slot_samples)
             if self._resident_scores:
                 self.engine.loop_scores_enable(True)
         if self._plan_rep and not self._sweep:                        # (a sweep's modes were given per slot at begin)
@@ -1142,9 +1167,17 @@ class BatchedClosedLoop:
             pred_src=None, after=after, stats=self.last_stats[sel].copy(), has_path=path_rec >= 0, keep=keep,
             cost=rec["cost"][chosen], paths=paths, t_pred=t_pred, t_plan=t_plan)
 
-    def _best_sample(self, dist: np.ndarray, off: np.ndarray) -> np.ndarray:
+    def _best_sample(self, dist: np.ndarray, off: np.ndarray, counts=None) -> np.ndarray:
         """predict_single_best (trajectory_predictor.py:340-352) per episode: the sample closest to the sample mean over
-        the episode's own pedestrians -> [sum P, T, 2]."""
+        the episode's own pedestrians -> [sum P, T, 2].  counts: episode i chooses among its first counts[i] samples."""
+        if counts is not None:
+            out = np.empty(dist.shape[1:])
+            for i, k in enumerate(counts):
+                lo, hi = int(off[i]), int(off[i + 1])
+                if hi > lo:
+                    out[lo:hi] = dist[0, lo:hi] if k == 1 else self._best_sample(np.ascontiguousarray(dist[:int(k), lo:hi]),
+                                                                                 np.array([0, hi - lo]))
+            return out
         n = len(off) - 1
         dev = np.linalg.norm(dist - dist.mean(axis=0)[None], axis=-1).sum(axis=2)      # [S, sum P]
         # (np.add.reduceat takes no index past the array: episodes without pedestrians at the END of the frame are left out)
@@ -1178,8 +1211,8 @@ class BatchedClosedLoop:
                 off = np.asarray(off)
                 chosen = dist[np.repeat(np.maximum(pred_src[4], 0), off[1:] - off[:-1]), np.arange(dist.shape[1])]
                 whole = np.repeat(pred_src[4] < 0, off[1:] - off[:-1])     # a sweep's slots that planned on the distribution
-                if whole.any() and raw_h.shape[0] > 1:
-                    chosen[whole] = self._best_sample(dist, off)[whole]
+                if whole.any() and raw_h.shape[0] > 1:                # (each among its own sample count, where the slots have one)
+                    chosen[whole] = self._best_sample(dist, off, pred_src[5] if len(pred_src) > 5 else None)[whole]
                 return chosen
             return dist[0] if raw_h.shape[0] == 1 else self._best_sample(dist, np.asarray(off))
         o32, stale = pred_src
@@ -1241,6 +1274,8 @@ class BatchedClosedLoop:
         t_plan = (time.perf_counter() - t0) / n
         if self._plan_rep and pred_src is not None and isinstance(pred_src[0], str):
             pred_src = pred_src + (self._planned_on(self.engine.loop_last_best_sample())[sel].astype(np.int64),)   # what the step planned on
+        if self._slot_samples is not None and pred_src is not None and isinstance(pred_src[0], str):
+            pred_src = pred_src + (() if self._plan_rep else (np.full(n, -1, np.int64),)) + (self._slot_samples[sel],)
         rec, path_rec, keep = o["records"], o["record"].astype(np.int64), o["keep"].astype(np.int64)
         new_ego = o["ego"]
         self.ego[sel], self.jerk[sel] = new_ego, o["jerk"]

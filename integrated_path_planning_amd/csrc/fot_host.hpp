@@ -314,6 +314,12 @@ struct LoopState {
     std::vector<SweepEp> sweep_tab;
     int sweep_T = 0;
     PinnedBuf hSweep;
+    // fot_loop_set_slot_samples: slot e of a sweep loop uses the first slot_S[e] samples of its source (empty: every slot
+    // uses them all).  ep_S: the counts of the episodes of the most recent frame that carried a distribution (empty: it
+    // carried none, or the loop has no counts), hEpS: the same where a resident step's kernels read them.
+    std::vector<int32_t> slot_S, ep_S;
+    PinnedBuf hEpS;
+    int count_of(size_t episode) const { return ep_S.empty() ? dist_S : ep_S[episode]; }   // samples of a frame's episode
     const int32_t *p_scen = nullptr;         // the same where k_safety reads it (beside p_off), or nullptr
     std::vector<int32_t> ped_off;            // of the frame
     std::vector<int64_t> blk_off;            // first point of each episode's block in the tensor
@@ -331,7 +337,7 @@ struct LoopState {
         hFrame.release(); hObserve.release(); hOut.release(); hRec.release();
         dDyn.release(); dStatic.release(); replay.release(); rep.release();
         dScenStatic.release(); dGather.release(); dSafScen.release(); hGather.release();
-        hSweep.release(); fpo.release();
+        hSweep.release(); hEpS.release(); fpo.release();
     }
 };
 

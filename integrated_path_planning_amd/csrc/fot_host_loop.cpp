@@ -151,7 +151,7 @@ int loop_enqueue_requests(fot_handle *h, int32_t n_req, const fot_loop_request *
         } else {
             d_off[j] = L.blk_off[e];
             dims[4 * j] = P_e > 0 ? (L.dist_S > 0 ? FOT_DYN_DISTRIBUTION : FOT_DYN_SINGLE) : FOT_DYN_NONE;
-            dims[4 * j + 1] = L.dist_S > 0 ? L.dist_S : 1; dims[4 * j + 2] = P_e; dims[4 * j + 3] = L.t_len[e];
+            dims[4 * j + 1] = L.dist_S > 0 ? L.count_of((size_t)e) : 1; dims[4 * j + 2] = P_e; dims[4 * j + 3] = L.t_len[e];
         }
         any_dyn = any_dyn || P_e > 0;
     }
@@ -225,9 +225,20 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
         const bool rep_on = L.rep.mode == FOT_LOOP_PLAN_REPRESENTATIVE && dist;   // (never a scenario loop: the tail is free)
         // a sweep loop's frame with a distribution needs both tail tables and, behind them, the episodes' SweepEp rows
         const bool sweep_on = L.ep.sweep && ep_scen && dist;
+        // ... whose slots keep their own sample counts (fot_loop_set_slot_samples): the episodes' counts behind those; a
+        // frame whose episodes all keep the source's count is the frame of before
+        bool ragged = false;
+        for (int e = 0; sweep_on && !L.slot_S.empty() && e < n; ++e) {
+            const int slot = ep_slot ? ep_slot[e] : e;
+            if (slot < 0 || slot >= (int)L.slot_S.size()) return fail(h, FOT_ERR_INVALID, "frame: an episode's slot lies outside the loop's sample counts");
+            if (L.slot_S[(size_t)slot] > frame->dist_S)
+                return fail(h, FOT_ERR_INVALID, "frame: dist_S = " + std::to_string(frame->dist_S) + " is below the sample count of slot " +
+                                                std::to_string(slot) + " (fot_loop_set_slot_samples: " + std::to_string(L.slot_S[(size_t)slot]) + ")");
+            ragged = ragged || L.slot_S[(size_t)slot] != frame->dist_S;
+        }
         const size_t tail = ego_b + off_b + 4 * ped_b + blk_b + pe_b;
-        HIP_TRY(h, L.hFrame.ensure(tail + (ep_scen || rep_on ? off_b : 0) +
-                                   (sweep_on ? off_b + align256(sizeof(SweepEp) * (size_t)std::max(n, 1)) : 0)));
+        const size_t sweep_b = align256(sizeof(SweepEp) * (size_t)std::max(n, 1));
+        HIP_TRY(h, L.hFrame.ensure(tail + (ep_scen || rep_on ? off_b : 0) + (sweep_on ? off_b + sweep_b : 0) + (ragged ? off_b : 0)));
         char *p = (char *)L.hFrame.p;
         double *p_ego = (double *)p;
         int32_t *p_off = (int32_t *)(p + ego_b);
@@ -247,9 +258,16 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
         L.dist_S = dist ? frame->dist_S : 0;
         L.rep.frame = false;
         L.sweep_tab.clear();
+        L.ep_S.clear();
+        int S_run = dist ? frame->dist_S : 0, P_run = 0;             // the largest count / pedestrian count of the frame
+        if (ragged) {
+            L.ep_S.resize((size_t)n);
+            S_run = sweep_slot_counts(n, ep_slot, L.slot_S.data(), L.ep_S.data());
+        }
         for (int e = 0; e < n; ++e) {
             L.t_len[e] = dist ? n_dense + 1 : ready ? n_dense + (frame->prepend[e] ? 1 : 0) : 1;
-            L.blk_off[e + 1] = L.blk_off[e] + (int64_t)(dist ? frame->dist_S : 1) * (L.ped_off[e + 1] - L.ped_off[e]) * L.t_len[e];
+            L.blk_off[e + 1] = L.blk_off[e] + (int64_t)(dist ? L.count_of((size_t)e) : 1) * (L.ped_off[e + 1] - L.ped_off[e]) * L.t_len[e];
+            P_run = std::max(P_run, L.ped_off[e + 1] - L.ped_off[e]);
         }
         L.p_off = p_off; L.p_pos = p_pos; L.p_vel = p_vel;
         L.p_scen = nullptr; L.frame_scen.clear();
@@ -273,22 +291,38 @@ int loop_plan_impl(fot_handle *h, const fot_loop_frame *frame, int32_t n_req, co
                 for (int e = 0; e < n; ++e) p_slot[e] = ep_slot ? ep_slot[e] : e;
                 tensor_pts = sweep_layout(n, L.ped_off.data(), p_slot, L.ep.plan_mode.data(), L.blk_off[n], n_dense + 1, false, p_sweep);
             }
+            int32_t *p_eps = (int32_t *)(p + tail + 2 * off_b + sweep_b);    // (... and the episodes' sample counts behind the rows)
+            if (ragged) std::memcpy(p_eps, L.ep_S.data(), sizeof(int32_t) * (size_t)n);
             HIP_TRY(h, L.dDyn.ensure(sizeof(double) * 2 * (size_t)tensor_pts));
             L.dyn_ptr = L.dDyn.p;
-            LAUNCH_TRY(h, launch_resample(frame->rp.sgan_dt, frame->rp.sim_dt, frame->staleness, frame->dist_S, frame->pred_len,
-                                          (int)n_ped, n_dense, 1, 1, 0, frame->dist_raw, frame->dist_dtype, p_last, p_pos,
-                                          L.dDyn.p, FOT_F64, 0, st, p_pe, p_off, p_blk));
+            if (ragged)
+                LAUNCH_TRY(h, launch_resample_slots(frame->rp.sgan_dt, frame->rp.sim_dt, frame->staleness, S_run, frame->pred_len,
+                                                    (int)n_ped, n_dense, n, P_run, frame->dist_raw, frame->dist_dtype, p_last, p_pos,
+                                                    L.dDyn.as<double>(), p_off, p_blk, p_eps, st));
+            else
+                LAUNCH_TRY(h, launch_resample(frame->rp.sgan_dt, frame->rp.sim_dt, frame->staleness, frame->dist_S, frame->pred_len,
+                                              (int)n_ped, n_dense, 1, 1, 0, frame->dist_raw, frame->dist_dtype, p_last, p_pos,
+                                              L.dDyn.p, FOT_F64, 0, st, p_pe, p_off, p_blk));
             if (sweep_on && tensor_pts > L.blk_off[n]) {
                 // the selection and the planning blocks of the episodes in representative mode, behind the resample
                 { int r = rep_ensure(h, std::max(L.ep.n, n), n, 0, n_dense + 1, frame->dist_S); if (r != FOT_OK) return r; }
                 FrameDev fd;
                 fd.pos = p_pos; fd.ped0 = p_off; fd.blk = p_blk;
+                if (ragged) {
+                    LAUNCH_TRY(h, launch_loop_best_sample_slots(p_slot, fd, L.dDyn.as<double>(), p_sweep, p_eps, n, S_run, n_dense,
+                                                                L.rep.dDev.as<double>(), best_dev_stride(frame->dist_S),
+                                                                L.rep.dBest.as<int32_t>(), (int32_t *)L.rep.hBest.p, st));
+                    LAUNCH_TRY(h, launch_loop_rep_block_slots(p_slot, fd, L.dDyn.as<double>(), p_sweep, p_eps, L.rep.dBest.as<int32_t>(),
+                                                              n, n_dense, L.dDyn.as<double>(), L.rep.dPre.as<int32_t>(),
+                                                              (int32_t *)L.rep.hPre.p, st));
+                } else {
                 LAUNCH_TRY(h, launch_loop_best_sample_sweep(p_slot, fd, L.dDyn.as<double>(), p_sweep, n, frame->dist_S, n_dense,
                                                             L.rep.dDev.as<double>(), L.rep.dBest.as<int32_t>(),
                                                             (int32_t *)L.rep.hBest.p, st));
                 LAUNCH_TRY(h, launch_loop_rep_block_sweep(p_slot, fd, L.dDyn.as<double>(), p_sweep, L.rep.dBest.as<int32_t>(), n,
                                                           frame->dist_S, n_dense, L.dDyn.as<double>(), L.rep.dPre.as<int32_t>(),
                                                           (int32_t *)L.rep.hPre.p, st));
+                }
                 L.sweep_tab.assign(p_sweep, p_sweep + n);
                 L.sweep_T = n_dense + 1;
                 rep_pending = true;
@@ -706,6 +740,22 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     for (int i = 0; i < n; ++i) rows_run += R.ped_off[sel[i] + 1] - R.ped_off[sel[i]];
     const int dist_S = R.dist_S();
     const bool sampled = dist_S > 0 && ready && rows_run > 0;    // this step predicts with the sampler or the recording
+    // fot_loop_set_slot_samples: every running episode on its slot's own count; S_move: what the gather or the sampler
+    // moves or draws (the largest count among the loop's slots), S_run / P_run: the grid of the ragged resample.  A step
+    // whose running slots all keep the source's count is the step of before.
+    L.ep_S.clear();
+    bool ragged = false;
+    int S_move = dist_S, S_run = dist_S, P_run = 0;
+    if (sampled && E.sweep && !L.slot_S.empty()) {
+        S_move = *std::max_element(L.slot_S.begin(), L.slot_S.end());
+        for (int i = 0; i < n; ++i) ragged = ragged || L.slot_S[(size_t)sel[i]] != dist_S;
+        if (ragged) {
+            L.ep_S.resize((size_t)n);
+            S_run = sweep_slot_counts(n, sel.data(), L.slot_S.data(), L.ep_S.data());
+            std::memcpy(L.hEpS.p, L.ep_S.data(), sizeof(int32_t) * (size_t)n);
+        } else S_move = dist_S;
+    }
+    const int32_t *ep_S = (const int32_t *)L.hEpS.p;
     R.smp.last_scenes = R.smp.last_rows = 0;                     // (fot_debug_loop_sampler_shape: until the sampler branch runs)
     std::fill(R.smp.last_mscenes.begin(), R.smp.last_mscenes.end(), 0);
     std::fill(R.smp.last_mrows.begin(), R.smp.last_mrows.end(), 0);
@@ -721,7 +771,8 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         if (sampled) pre = 1;                                    // (the current positions lead EVERY sample, :514-525)
         L.t_len[i] = ready ? R.n_dense + pre : 1;
         L.ped_off[i + 1] = L.ped_off[i] + P_e;
-        L.blk_off[i + 1] = L.blk_off[i] + (int64_t)(sampled ? dist_S : 1) * P_e * L.t_len[i];
+        L.blk_off[i + 1] = L.blk_off[i] + (int64_t)(sampled ? (ragged ? L.ep_S[(size_t)i] : dist_S) : 1) * P_e * L.t_len[i];
+        P_run = std::max(P_run, P_e);
         sg.slot[i] = e; sg.ped0[i] = L.ped_off[i]; sg.blk[i] = L.blk_off[i]; sg.prepend[i] = pre;
         if (E.scenarios) sg.scen[i] = L.frame_scen[(size_t)i] = E.scen[(size_t)e];
         for (int q = 0; q < 4; ++q) sg.ego[4 * (size_t)i + q] = W.ego4[4 * (size_t)i + q];
@@ -755,11 +806,19 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         a.d.S = M.S; a.d.pred_len = C.pred_len; a.d.rows = rows; a.d.n_cols = M.n_rec_cols;
         a.d.rec_row = (int64_t)R.steps[(size_t)sel[0]] - M.first_step;
         a.rec = M.rec; a.col = M.dCol.as<int32_t>(); a.out = M.dRaw.p; a.dtype = M.dtype;
-        LAUNCH_TRY(h, launch_loop_sample_rows(a, st));
+        if (ragged) {                                            // (the largest count's samples only)
+            a.d.S = S_move;
+            LAUNCH_TRY(h, launch_loop_sample_rows_prefix(a, M.S, st));
+        } else
+            LAUNCH_TRY(h, launch_loop_sample_rows(a, st));
         L.dyn_ptr = L.dDyn.p;
         L.dist_S = M.S;
-        LAUNCH_TRY(h, launch_resample(C.rp.sgan_dt, C.rp.sim_dt, stale, M.S, C.pred_len, rows, R.n_dense, 1, 1, 0, M.dRaw.p,
-                                      M.dtype, fd.last, fd.pos, L.dDyn.p, FOT_F64, 0, st, fd.ped_ep, fd.ped0, fd.blk));
+        if (ragged)
+            LAUNCH_TRY(h, launch_resample_slots(C.rp.sgan_dt, C.rp.sim_dt, stale, S_run, C.pred_len, rows, R.n_dense, n, P_run, M.dRaw.p,
+                                                M.dtype, fd.last, fd.pos, L.dDyn.as<double>(), fd.ped0, fd.blk, ep_S, st));
+        else
+            LAUNCH_TRY(h, launch_resample(C.rp.sgan_dt, C.rp.sim_dt, stale, M.S, C.pred_len, rows, R.n_dense, 1, 1, 0, M.dRaw.p,
+                                          M.dtype, fd.last, fd.pos, L.dDyn.p, FOT_F64, 0, st, fd.ped_ep, fd.ped0, fd.blk));
     } else if (sampled && R.smp.models) {
         // One sampling per ACTIVE (CROWD, MODEL) UNIT (fot_loop_set_sampler_models): for every model with an active unit, in
         // ascending id, window -> noise keyed by the crowd -> samples of its units' representatives into its
@@ -820,11 +879,11 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
                     for (int p = 0; p < (global_noise ? 1 : P_c); ++p, ++r) { t_slot[r] = m_crowd[c]; t_step[r] = R.steps[(size_t)e]; t_idx[r] = p; }
                 }
                 SgNoise a{};
-                a.seed = M.seed; a.kind = M.kinds[(size_t)m]; a.S = M.S; a.rows = noise_rows; a.nd = nd; a.n_blk = (nd + 3) / 4;
+                a.seed = M.seed; a.kind = M.kinds[(size_t)m]; a.S = S_move; a.rows = noise_rows; a.nd = nd; a.n_blk = (nd + 3) / 4;
                 a.slot = t_slot; a.step = t_step; a.index = t_idx; a.out = (uint32_t *)noise;
                 LAUNCH_TRY(h, launch_sgan_noise(a, ms));
             }
-            { int r = sgan_enqueue(h, m, n_sc, m_rows, M.S, dm_off, global_noise && nd > 0 ? dm_scene : nullptr, win, noise,
+            { int r = sgan_enqueue(h, m, n_sc, m_rows, S_move, dm_off, global_noise && nd > 0 ? dm_scene : nullptr, win, noise,
                                    M.dCrowdRaw.as<float>() + 2 * (size_t)m * raw_stride, ms); if (r != FOT_OK) return r; }
             M.last_mscenes[(size_t)m] = n_sc; M.last_mrows[(size_t)m] = m_rows;
             M.last_scenes += n_sc; M.last_rows += m_rows;
@@ -834,13 +893,17 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
             }
         }
         LoopModelRows g{};
-        g.S = M.S; g.pred_len = C.pred_len; g.rows = rows;
+        g.S = S_move; g.pred_len = C.pred_len; g.rows = rows;
         g.pool = (const float2 *)M.dCrowdRaw.p; g.tab = M.dModelTab.as<ModelRow>(); g.out = (float2 *)M.dRaw.p;
         LAUNCH_TRY(h, launch_loop_model_rows(g, st));
         L.dyn_ptr = L.dDyn.p;
         L.dist_S = M.S;
-        LAUNCH_TRY(h, launch_resample(C.rp.sgan_dt, C.rp.sim_dt, stale, M.S, C.pred_len, rows, R.n_dense, 1, 1, 0, M.dRaw.p,
-                                      FOT_F32, fd.last, fd.pos, L.dDyn.p, FOT_F64, 0, st, fd.ped_ep, fd.ped0, fd.blk));
+        if (ragged)
+            LAUNCH_TRY(h, launch_resample_slots(C.rp.sgan_dt, C.rp.sim_dt, stale, S_run, C.pred_len, rows, R.n_dense, n, P_run, M.dRaw.p,
+                                                FOT_F32, fd.last, fd.pos, L.dDyn.as<double>(), fd.ped0, fd.blk, ep_S, st));
+        else
+            LAUNCH_TRY(h, launch_resample(C.rp.sgan_dt, C.rp.sim_dt, stale, M.S, C.pred_len, rows, R.n_dense, 1, 1, 0, M.dRaw.p,
+                                          FOT_F32, fd.last, fd.pos, L.dDyn.p, FOT_F64, 0, st, fd.ped_ep, fd.ped0, fd.blk));
     } else if (sampled && R.smp.crowds) {
         // One sampling per ACTIVE CROWD (fot_loop_set_sampler_shared): window -> noise keyed by the crowd -> samples of the
         // crowds' representatives -> gathered into the step's raw tensor of the running episodes -> every episode's block
@@ -879,23 +942,27 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
                 for (int p = 0; p < (global_noise ? 1 : P_c); ++p, ++r) { t_slot[r] = M.scene_crowd[(size_t)c]; t_step[r] = R.steps[(size_t)e]; t_idx[r] = p; }
             }
             SgNoise a{};
-            a.seed = M.seed; a.kind = M.kind; a.S = M.S; a.rows = noise_rows; a.nd = nd; a.n_blk = (nd + 3) / 4;
+            a.seed = M.seed; a.kind = M.kind; a.S = S_move; a.rows = noise_rows; a.nd = nd; a.n_blk = (nd + 3) / 4;
             a.slot = t_slot; a.step = t_step; a.index = t_idx; a.out = (uint32_t *)M.dNoise.p;
             LAUNCH_TRY(h, launch_sgan_noise(a, st));
         }
-        { int r = sgan_enqueue(h, 0, n_sc, c_rows, M.S, d_off, global_noise && nd > 0 ? d_scene : nullptr, M.dWin.as<float>(),
+        { int r = sgan_enqueue(h, 0, n_sc, c_rows, S_move, d_off, global_noise && nd > 0 ? d_scene : nullptr, M.dWin.as<float>(),
                                M.dNoise.as<float>(), crowd_raw, st); if (r != FOT_OK) return r; }
         if (!M.shape.identity) {                                 // (one slot per crowd, in the crowds' order: nothing to gather)
             LoopSampleRows a{};
-            a.d.S = M.S; a.d.pred_len = C.pred_len; a.d.rows = rows; a.d.n_cols = c_rows; a.d.rec_row = 0;
+            a.d.S = S_move; a.d.pred_len = C.pred_len; a.d.rows = rows; a.d.n_cols = c_rows; a.d.rec_row = 0;
             a.rec = crowd_raw; a.col = d_col; a.out = M.dRaw.p; a.dtype = FOT_F32;
             LAUNCH_TRY(h, launch_loop_sample_rows(a, st));
         }
         M.last_scenes = n_sc; M.last_rows = c_rows;
         L.dyn_ptr = L.dDyn.p;
         L.dist_S = M.S;
-        LAUNCH_TRY(h, launch_resample(C.rp.sgan_dt, C.rp.sim_dt, stale, M.S, C.pred_len, rows, R.n_dense, 1, 1, 0, M.dRaw.p,
-                                      FOT_F32, fd.last, fd.pos, L.dDyn.p, FOT_F64, 0, st, fd.ped_ep, fd.ped0, fd.blk));
+        if (ragged)
+            LAUNCH_TRY(h, launch_resample_slots(C.rp.sgan_dt, C.rp.sim_dt, stale, S_run, C.pred_len, rows, R.n_dense, n, P_run, M.dRaw.p,
+                                                FOT_F32, fd.last, fd.pos, L.dDyn.as<double>(), fd.ped0, fd.blk, ep_S, st));
+        else
+            LAUNCH_TRY(h, launch_resample(C.rp.sgan_dt, C.rp.sim_dt, stale, M.S, C.pred_len, rows, R.n_dense, 1, 1, 0, M.dRaw.p,
+                                          FOT_F32, fd.last, fd.pos, L.dDyn.p, FOT_F64, 0, st, fd.ped_ep, fd.ped0, fd.blk));
     } else if (sampled) {
         // window -> noise -> samples -> every episode's [S][P_e][n_dense + 1][2] block, all in HBM behind k_loop_frame
         LoopSampler &M = R.smp;
@@ -919,16 +986,20 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
                 for (int p = 0; p < (global_noise ? 1 : P_e); ++p, ++r) { t_slot[r] = e; t_step[r] = R.steps[(size_t)e]; t_idx[r] = p; }
             }
             SgNoise a{};
-            a.seed = M.seed; a.kind = M.kind; a.S = M.S; a.rows = noise_rows; a.nd = nd; a.n_blk = (nd + 3) / 4;
+            a.seed = M.seed; a.kind = M.kind; a.S = S_move; a.rows = noise_rows; a.nd = nd; a.n_blk = (nd + 3) / 4;
             a.slot = t_slot; a.step = t_step; a.index = t_idx; a.out = (uint32_t *)M.dNoise.p;
             LAUNCH_TRY(h, launch_sgan_noise(a, st));
         }
-        { int r = sgan_enqueue(h, 0, n, rows, M.S, fd.ped0, global_noise && nd > 0 ? fd.ped_ep : nullptr, M.dWin.as<float>(),
+        { int r = sgan_enqueue(h, 0, n, rows, S_move, fd.ped0, global_noise && nd > 0 ? fd.ped_ep : nullptr, M.dWin.as<float>(),
                                M.dNoise.as<float>(), M.dRaw.as<float>(), st); if (r != FOT_OK) return r; }
         L.dyn_ptr = L.dDyn.p;
         L.dist_S = M.S;
-        LAUNCH_TRY(h, launch_resample(C.rp.sgan_dt, C.rp.sim_dt, stale, M.S, C.pred_len, rows, R.n_dense, 1, 1, 0, M.dRaw.p,
-                                      FOT_F32, fd.last, fd.pos, L.dDyn.p, FOT_F64, 0, st, fd.ped_ep, fd.ped0, fd.blk));
+        if (ragged)
+            LAUNCH_TRY(h, launch_resample_slots(C.rp.sgan_dt, C.rp.sim_dt, stale, S_run, C.pred_len, rows, R.n_dense, n, P_run, M.dRaw.p,
+                                                FOT_F32, fd.last, fd.pos, L.dDyn.as<double>(), fd.ped0, fd.blk, ep_S, st));
+        else
+            LAUNCH_TRY(h, launch_resample(C.rp.sgan_dt, C.rp.sim_dt, stale, M.S, C.pred_len, rows, R.n_dense, 1, 1, 0, M.dRaw.p,
+                                          FOT_F32, fd.last, fd.pos, L.dDyn.p, FOT_F64, 0, st, fd.ped_ep, fd.ped0, fd.blk));
     } else if (ready && rows > 0) {
         L.dyn_ptr = L.dDyn.p;
         LAUNCH_TRY(h, launch_predict_cv_frame(C.rp.sgan_dt, C.rp.sim_dt, stale, rows, R.n_dense, fd, L.dDyn.as<double>(), st));
@@ -945,11 +1016,19 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         int32_t *best_tab = R.sc.on ? R.sc.dBest.as<int32_t>() : L.rep.dBest.as<int32_t>();
         bool any_select = false;                                 // (every running slot in distribution mode, no scores: no launch)
         for (int i = 0; i < n; ++i) any_select = any_select || tab[i].select != 0;
-        if (any_select)
+        if (any_select && ragged)                                // (the tables' rows were sized for the source's S)
+            LAUNCH_TRY(h, launch_loop_best_sample_slots(sg.slot, fd, L.dDyn.as<double>(), tab, ep_S, n, S_run, R.n_dense,
+                                                        R.sc.on ? R.sc.dDev.as<double>() : L.rep.dDev.as<double>(),
+                                                        best_dev_stride(dist_S), best_tab,
+                                                        (int32_t *)(R.sc.on ? R.sc.hBest.p : L.rep.hBest.p), st));
+        else if (any_select)
             LAUNCH_TRY(h, launch_loop_best_sample_sweep(sg.slot, fd, L.dDyn.as<double>(), tab, n, dist_S, R.n_dense,
                                                         R.sc.on ? R.sc.dDev.as<double>() : L.rep.dDev.as<double>(), best_tab,
                                                         (int32_t *)(R.sc.on ? R.sc.hBest.p : L.rep.hBest.p), st));
-        if (pts > L.blk_off[n])                                  // (some running episode has a planning block to write)
+        if (pts > L.blk_off[n] && ragged)
+            LAUNCH_TRY(h, launch_loop_rep_block_slots(sg.slot, fd, L.dDyn.as<double>(), tab, ep_S, best_tab, n, R.n_dense,
+                                                      L.dDyn.as<double>(), L.rep.dPre.as<int32_t>(), (int32_t *)L.rep.hPre.p, st));
+        else if (pts > L.blk_off[n])                             // (some running episode has a planning block to write)
             LAUNCH_TRY(h, launch_loop_rep_block_sweep(sg.slot, fd, L.dDyn.as<double>(), tab, best_tab, n, dist_S, R.n_dense,
                                                       L.dDyn.as<double>(), L.rep.dPre.as<int32_t>(), (int32_t *)L.rep.hPre.p, st));
         L.sweep_tab.assign(tab, tab + n);
@@ -972,12 +1051,14 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
     if (scored && R.sc.std_ok) {                                 // one origin per running episode, the truth from the recording
         PredOriginDev *pd = (PredOriginDev *)R.sc.hDesc.p;
         const double scott = ps_scott(dist_S);
-        for (int i = 0; i < n; ++i)
-            pd[i] = PredOriginDev{ L.blk_off[(size_t)i], (int64_t)L.ped_off[(size_t)i], scott, dist_S,
+        for (int i = 0; i < n; ++i) {                            // (a count per slot: the origin's own S and bandwidth factor)
+            const int S_i = L.count_of((size_t)i);
+            pd[i] = PredOriginDev{ L.blk_off[(size_t)i], (int64_t)L.ped_off[(size_t)i], ragged ? ps_scott(S_i) : scott, S_i,
                                    L.ped_off[(size_t)i + 1] - L.ped_off[(size_t)i], R.n_dense + 1, 0, 1, 0 };
+        }
         LAUNCH_TRY(h, launch_loop_score_truth(rv, sg.slot, fd, rows, f_cur, R.sc.stride, C.pred_len, R.sc.dTruth.as<double>(), st));
         LAUNCH_TRY(h, launch_pred_scores(pd, n, L.dDyn.p, FOT_F64, R.sc.stride, C.pred_len, R.sc.dTruth.as<double>(),
-                                         (fot_pred_score *)R.sc.hRec.p, st, dist_S > FOT_MAX_SAMPLES ? 1 : 0));
+                                         (fot_pred_score *)R.sc.hRec.p, st, S_run > FOT_MAX_SAMPLES ? 1 : 0));   // (wide: any running origin is)
     }
     LAUNCH_TRY(h, launch_safety(h->dP.as<DevParams>(), n, fd.ego, fd.ped0, fd.pos, fd.vel, L.ego_radius, L.ped_radius,
                                 h->sc[0].params.footprint_radius, L.use_footprint, (fot_safety *)L.hOut.p, st,
@@ -999,7 +1080,8 @@ int loop_run_step(fot_handle *h, const std::vector<int32_t> &sel, int k, fot_loo
         std::fill(Q.last_best.begin(), Q.last_best.end(), -1);
         for (int i = 0; i < n; ++i) {
             const int e = sel[i];
-            PredScoreTerms t = ps_zero(dist_S);                  // (no prediction, or no horizon that could ever complete)
+            // (no prediction, or no horizon that could ever complete; of the slot's own count)
+            PredScoreTerms t = ps_zero(L.slot_S.empty() ? dist_S : L.slot_S[(size_t)e]);
             if (scored && Q.std_ok) {
                 const fot_pred_score &r = rec[i];
                 t.ade_scene = r.ade_scene; t.fde_scene = r.fde_scene; t.ade_agent_sum = r.ade_agent_sum;
@@ -1199,6 +1281,7 @@ int set_samples_impl(fot_handle *h, const std::string &who, int32_t S, int32_t n
     M.sel.clear();
     M.on = true;
     R.sc.on = false;                                             // (a new recording: its scores are enabled again, if wanted)
+    L.slot_S.clear(); L.ep_S.clear();                            // ... and the slots' sample counts set anew
     return FOT_OK;
 }
 
@@ -1336,6 +1419,7 @@ int set_sampler_impl(fot_handle *h, const std::string &who, int32_t S, uint64_t 
     M.S = S; M.seed = seed; M.kind = model_kind[0];
     M.on = true;
     R.sc.on = false;                                             // (a new sampler: its scores are enabled again, if wanted)
+    L.slot_S.clear(); L.ep_S.clear();                            // ... and the slots' sample counts set anew
     return FOT_OK;
 }
 
@@ -1411,6 +1495,7 @@ int fot_loop_begin(fot_handle *h, int32_t n_episodes, const fot_loop_config *cfg
     E.n = n_episodes; E.cfg = *cfg;
     E.scenarios = false; E.cfgs.clear(); E.use_fp.clear(); E.scen.clear();
     E.sweep = false; E.plan_mode.clear(); h->loop.sweep_tab.clear();
+    h->loop.slot_S.clear(); h->loop.ep_S.clear();            // ... and a sweep's sample counts (fot_loop_set_slot_samples)
     E.max_lvl = loop_max_levels(*cfg);
     h->loop.frame_scen.clear(); h->loop.p_scen = nullptr;
     E.ego.assign(ego5, ego5 + 5 * n);
@@ -1469,6 +1554,7 @@ int fot_loop_begin_scenarios(fot_handle *h, int32_t n_episodes, int32_t n_cfg, c
     E.n = n_episodes; E.cfg = cfg[first];
     E.scenarios = true;
     E.sweep = false; E.plan_mode.clear(); L.sweep_tab.clear();
+    L.slot_S.clear(); L.ep_S.clear();
     E.cfgs.assign(cfg, cfg + n_cfg);
     E.use_fp.assign((size_t)n_cfg, 0);
     for (int s = 0; s < n_cfg; ++s) E.use_fp[(size_t)s] = use_footprint && use_footprint[s] ? 1 : 0;
@@ -1627,6 +1713,7 @@ int fot_loop_set_replay(fot_handle *h, const fot_loop_replay *rp)
     R.smp.on = false;                                            // ... and so is a sampler
     R.rec.on = false; R.rec.rec = nullptr;                       // ... or recorded samples
     R.sc.on = false;                                             // ... and its scores
+    L.slot_S.clear(); L.ep_S.clear();                            // ... and the slots' sample counts, which were the source's
     const size_t rec_doubles = (size_t)rp->n_frames_max * cols * 2;
     const int max_lvl = E.max_lvl;
     const size_t n_rec = (size_t)std::max(n, 1) * (size_t)max_lvl;
@@ -1734,6 +1821,8 @@ int fot_loop_scores_enable(fot_handle *h, int32_t on)
     Q.stride = stride; Q.H = stride * R.cfg.pred_len;
     Q.std_ok = ps_horizon_fits(stride, R.cfg.pred_len, R.n_dense + 1, 1);
     Q.ring.assign(ns * (size_t)Q.H, ps_zero(R.dist_S()));
+    for (size_t e = 0; e < h->loop.slot_S.size(); ++e)           // (a count per slot; no record of the fresh ring is ever folded)
+        std::fill(Q.ring.begin() + (ptrdiff_t)(e * (size_t)Q.H), Q.ring.begin() + (ptrdiff_t)((e + 1) * (size_t)Q.H), ps_zero(h->loop.slot_S[e]));
     Q.fold.assign(ns, score_fold_zero());
     Q.last_best.assign(ns, -1);
     Q.on = true;
@@ -1842,7 +1931,7 @@ int fot_debug_loop_block(fot_handle *h, int32_t episode, int32_t cap_points, dou
         t_len = L.sweep_T; first = L.sweep_tab[e].rep_off; n_pts = sweep_block_points(P_e, t_len); base = L.dyn_ptr;
         if (P_e > 0) pre = ((const int32_t *)L.rep.hPre.p)[e];
     } else {
-        t_len = L.t_len[e]; first = L.blk_off[e]; n_pts = (int64_t)std::max(L.dist_S, 1) * P_e * t_len; base = L.dyn_ptr;
+        t_len = L.t_len[e]; first = L.blk_off[e]; n_pts = (int64_t)std::max(L.count_of(e), 1) * P_e * t_len; base = L.dyn_ptr;
     }
     if (P) *P = P_e;
     if (T) *T = t_len;
@@ -1908,6 +1997,52 @@ int fot_loop_set_samples_shared(fot_handle *h, int32_t S, int32_t n_steps, int32
 {
     if (!h) return FOT_ERR_INVALID;
     return set_samples_impl(h, "fot_loop_set_samples_shared", S, n_steps, first_step, samples, dtype, flags, true, n_rec_cols, slot_col0);
+}
+
+int fot_loop_set_slot_samples(fot_handle *h, int32_t n_slots, const int32_t *slot_S)
+{
+    if (!h) return FOT_ERR_INVALID;
+    LoopState &L = h->loop;
+    LoopReplay &R = L.replay;
+    const std::string who = "fot_loop_set_slot_samples: ";
+    if (!(L.ep.cfg.dt > 0.0)) return fail(h, FOT_ERR_INVALID, who + "fot_loop_begin_sweep comes first");
+    if (!L.ep.sweep) return fail(h, FOT_ERR_UNSUPPORTED, who + "the slots of a sweep loop (fot_loop_begin_sweep) take sample counts of their own; this loop's share one");
+    if (!slot_S) return fail(h, FOT_ERR_INVALID, who + "slot_S is NULL");
+    if (n_slots != L.ep.n) return fail(h, FOT_ERR_INVALID, who + "n_slots differs from the loop's");
+    // the source's count: the recording's or the sampler's of a resident loop; a stepwise loop's frames bring theirs
+    // (fot_loop_frame.dist_S, held against the counts by every fot_loop_step), so the handle's capacity bounds them here
+    int S = h->sample_cap;
+    if (R.set) {
+        if (!R.smp.on && !R.rec.on)
+            return fail(h, FOT_ERR_INVALID, who + "no sampler or recording is set (fot_loop_set_sampler* / fot_loop_set_samples* comes first)");
+        S = R.dist_S();
+    }
+    bool begun = L.stepped || (R.set && R.clock.frame != R.cfg.warmup_frames);
+    for (int e = 0; R.set && e < R.cfg.n_slots; ++e) begun = begun || R.steps[(size_t)e] != 0;
+    if (begun) return fail(h, FOT_ERR_INVALID, who + "the loop has stepped (set the counts between the source and the first step)");
+    for (int e = 0; e < n_slots; ++e)
+        if (slot_S[e] < 1 || slot_S[e] > S)
+            return fail(h, FOT_ERR_INVALID, who + "slot_S[" + std::to_string(e) + "] = " + std::to_string(slot_S[e]) + " lies outside 1 .. " +
+                                            std::to_string(S) + (R.set ? " (the source's samples)" : " (the handle's sample capacity)"));
+    if (R.set && sweep_slot_capacity_points(n_slots, R.ped_off.data(), slot_S, R.n_dense + 1) >
+                     sweep_capacity_points(S, std::max(R.n_cols, 1), R.n_dense + 1))
+        return fail(h, FOT_ERR_INVALID, who + "internal: the counts need more than the sweep's tensor holds");
+    // --- accepted
+    HIP_TRY(h, L.hEpS.ensure(sizeof(int32_t) * (size_t)std::max(n_slots, 1)));
+    L.slot_S.assign(slot_S, slot_S + n_slots);
+    L.ep_S.clear();
+    return FOT_OK;
+}
+
+int fot_debug_loop_slot_samples(fot_handle *h, int32_t n_slots, int32_t *out)
+{
+    if (!h) return FOT_ERR_INVALID;
+    const LoopState &L = h->loop;
+    if (!L.have_frame) return fail(h, FOT_ERR_INVALID, "fot_debug_loop_slot_samples: no frame");
+    const int n_ep = (int)L.ped_off.size() - 1;
+    if (n_slots < n_ep || (n_slots > 0 && !out)) return fail(h, FOT_ERR_INVALID, "fot_debug_loop_slot_samples: room for fewer entries than the frame has episodes / out is NULL");
+    for (int i = 0; i < n_slots; ++i) out[i] = i < n_ep ? L.count_of((size_t)i) : -1;   // (0: the frame carried no distribution)
+    return FOT_OK;
 }
 
 int fot_loop_run(fot_handle *h, int32_t max_steps, fot_loop_run_out *out)

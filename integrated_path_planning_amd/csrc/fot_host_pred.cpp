@@ -361,7 +361,7 @@ int fot_loop_prediction_scores(fot_handle *h, int32_t n_episodes, int32_t stride
     if (n_episodes == 0) return FOT_OK;
     std::vector<fot_pred_origin> desc((size_t)n_episodes);
     for (int e = 0; e < n_episodes; ++e)
-        desc[(size_t)e] = fot_pred_origin{ L.blk_off[(size_t)e], L.dist_S, L.ped_off[(size_t)e + 1] - L.ped_off[(size_t)e],
+        desc[(size_t)e] = fot_pred_origin{ L.blk_off[(size_t)e], L.count_of((size_t)e), L.ped_off[(size_t)e + 1] - L.ped_off[(size_t)e],
                                            L.t_len[(size_t)e], 0, 1, 0 };
     // (a frame without pedestrians left no tensor: every P is 0 and none is read)
     return prediction_scores_impl(h, "fot_loop_prediction_scores", n_episodes, desc.data(), L.dDyn.p, 0, FOT_F64, stride, E,

@@ -172,6 +172,23 @@ int launch_loop_best_sample_sweep(const int32_t *slot_of, FrameDev f, const doub
 int launch_loop_rep_block_sweep(const int32_t *slot_of, FrameDev f, const double *dyn, const SweepEp *tab,
                                 const int32_t *best_tab, int n_run, int S, int n_dense, double *tensor, int32_t *pre_dev,
                                 int32_t *pre_host, hipStream_t st);
+// ---- fot_loop_set_slot_samples (fot_sweep.hpp): a sweep loop's step whose running episode i keeps ep_S[i] samples (pinned
+// host memory, as tab).  launch_resample_slots: the first ep_S[i] samples of the raw tensor pred [S_src][pred_len][rows][2]
+// into episode i's [ep_S[i]][P_i][n_dense + 1][2] block at point ep_blk[i] of `out` -- launch_resample's anchored,
+// prepending float64 path; S_max / P_max: the largest count / pedestrian count among the running episodes (the grid).
+// launch_loop_sample_rows_prefix: launch_loop_sample_rows moving the first a.d.S of the source's S_src samples.  The
+// selection and the planning blocks as in the sweep forms, every episode on its own count; dev_tab's rows are dev_stride
+// apart; a step whose counts are all <= FOT_MAX_SAMPLES (S_max) takes the narrow selection.
+int launch_resample_slots(double sgan_dt, double sim_dt, double staleness, int S_max, int pred_len, int rows, int n_dense,
+                          int n_run, int P_max, const void *pred, int pred_dtype, const double *anchor, const double *current,
+                          double *out, const int32_t *ep_ped0, const int64_t *ep_blk, const int32_t *ep_S, hipStream_t st);
+int launch_loop_sample_rows_prefix(const LoopSampleRows &a, int S_src, hipStream_t st);
+int launch_loop_best_sample_slots(const int32_t *slot_of, FrameDev f, const double *dyn, const SweepEp *tab, const int32_t *ep_S,
+                                  int n_run, int S_max, int n_dense, double *dev_tab, int dev_stride, int32_t *best_tab,
+                                  int32_t *best_host, hipStream_t st);
+int launch_loop_rep_block_slots(const int32_t *slot_of, FrameDev f, const double *dyn, const SweepEp *tab, const int32_t *ep_S,
+                                const int32_t *best_tab, int n_run, int n_dense, double *tensor, int32_t *pre_dev,
+                                int32_t *pre_host, hipStream_t st);
 // The truth k_pred_scores reads for the step's origins, out[n_rows][E][2] (HBM): recording row min(f_cur + stride j,
 // frames - 1), j = 1 .. E, of every row of the frame.
 int launch_loop_score_truth(ReplayView rv, const int32_t *slot_of, FrameDev f, int n_rows, int f_cur, int stride, int E,

@@ -83,6 +83,88 @@ __global__ void k_resample(ResampleArgs A, const TI *__restrict__ pred, const do
         dst[k_stride * i] = (TO)R.at(A.sim_dt + (double)i * A.sim_dt, constant, v_tail);
 }
 
+// The ragged form of a sweep loop with a sample count per slot (fot_loop_set_slot_samples): running episode e keeps the
+// first ep_S[e] samples of the raw tensor [S_src][pred_len][rows][2] in its [ep_S[e]][P_e][n_dense + 1][2] block.  The grid
+// is (episode, sample, chunk of the episode's (pedestrian, axis) pairs): a workgroup whose sample lies beyond its
+// episode's count, or whose chunk lies beyond its pedestrians, leaves on a uniform test before it loads a coordinate, so
+// the work and the stores follow sum S_e * P_e.  The arithmetic of a point is k_resample's anchored, prepending path
+// (has_anchor = prepend = 1, cv = 0, float64 out), operation for operation: a point has the bits it has in any company.
+struct ResampleSlotsArgs {
+    double sgan_dt, sim_dt, staleness;
+    int pred_len, rows, n_dense;             // rows: the frame's pedestrians (the raw tensor's innermost extent)
+    const int32_t *ep_ped0; const int64_t *ep_blk; const int32_t *ep_S;
+};
+constexpr int RSS_THREADS = WAVE;
+
+// ResampleAxis (fot_math.hpp) with the source coordinates of a lane in its own column of LDS instead of a private array
+// (which the run-time index of `at` sends to scratch memory): every method is ResampleAxis's, expression for expression,
+// with co[i] spelled co(i) -- the same operations in the same order, so the same bits.
+struct ResampleAxisLds {
+    const double *col;                       // element i of this lane: col[i * RSS_THREADS]
+    int n_src, first_k;
+    double sgan_dt, staleness;
+    __device__ __forceinline__ double co(int i) const { return col[i * RSS_THREADS]; }
+    __device__ __forceinline__ double ts(int i) const { return (double)(i + first_k) * sgan_dt - staleness; }
+    __device__ __forceinline__ bool all_close(double b) const
+    {
+        bool ok = true;
+        for (int i = 0; i < n_src; ++i) ok = ok && (fabs(co(i) - b) <= 1e-8 + 1e-5 * fabs(b));
+        return ok;
+    }
+    __device__ __forceinline__ double at(double t, bool constant, double v_tail) const
+    {
+        if (constant) return co(n_src - 1);
+        const double t_last = ts(n_src - 1);
+        if (n_src >= 2 && t > t_last) return co(n_src - 1) + v_tail * (t - t_last);
+        if (t > t_last) return co(n_src - 1);
+        if (t < ts(0)) return co(0);
+        int j = 0;
+        for (int i = 1; i < n_src; ++i) j = ts(i) <= t ? i : j;     // last source time <= t
+        if (j == n_src - 1 || ts(j) == t) return co(j);
+        const double slope = (co(j + 1) - co(j)) / (ts(j + 1) - ts(j));
+        return slope * (t - ts(j)) + co(j);
+    }
+    __device__ __forceinline__ double tail_velocity() const
+    {
+        if (n_src < 2) return 0.0;
+        const int lookback = n_src < 3 ? n_src : 3;
+        const double v = (co(n_src - 1) - co(n_src - lookback)) / ((double)(lookback - 1) * sgan_dt);
+        return fmax(fmin(v, 2.5), -2.5);                              // MAX_WALKING_SPEED
+    }
+};
+
+template <typename TI>
+__global__ void __launch_bounds__(RSS_THREADS)
+k_resample_slots(ResampleSlotsArgs A, const TI *__restrict__ pred, const double *__restrict__ anchor,
+                 const double *__restrict__ current, double *__restrict__ out)
+{
+    __shared__ double s_co[FOT_MAX_PRED_LEN + 1][RSS_THREADS];       // 18.5 KB: source i of lane t at [i][t], no bank conflicts
+    const int e = blockIdx.x, smp = blockIdx.y;
+    if (smp >= A.ep_S[e]) return;                                    // (uniform)
+    const int p0 = A.ep_ped0[e], P_e = A.ep_ped0[e + 1] - p0;
+    if ((int)(blockIdx.z * RSS_THREADS) >= 2 * P_e) return;          // (uniform)
+    const int idx = blockIdx.z * RSS_THREADS + threadIdx.x;
+    if (idx >= 2 * P_e) return;
+    const int ax = idx & 1, q = idx >> 1, p = p0 + q, T = A.n_dense + 1;
+    double *dst = out + 2 * (A.ep_blk[e] + ((int64_t)smp * P_e + q) * T) + ax;
+    dst[0] = current[2 * p + ax];
+    dst += 2;
+    double *col = &s_co[0][threadIdx.x];                             // (a lane reads only what it wrote: no barrier)
+    ResampleAxisLds R;
+    R.col = col;
+    R.sgan_dt = A.sgan_dt; R.staleness = A.staleness;
+    R.first_k = 0;
+    int n = 0;
+    col[RSS_THREADS * n++] = anchor[2 * p + ax];
+    for (int k = 0; k < A.pred_len; ++k)
+        col[RSS_THREADS * n++] = (double)pred[(((int64_t)smp * A.pred_len + k) * A.rows + p) * 2 + ax];
+    R.n_src = n;
+    const bool constant = R.all_close(R.co(0)) || R.all_close(0.0);
+    const double v_tail = R.tail_velocity();
+    for (int i = 0; i < A.n_dense; ++i)
+        dst[2 * i] = R.at(A.sim_dt + (double)i * A.sim_dt, constant, v_tail);
+}
+
 // block = sample: sum over (p, k) of the distance to the sample mean (predict_single_best :346-350)
 template <typename TO>
 __global__ void __launch_bounds__(256)
@@ -293,6 +375,20 @@ __global__ __launch_bounds__(SR_THREADS) void k_loop_model_rows(LoopModelRows a)
     int32_t s, j, q;
     sr_split(d, t, s, j, q);
     a.out[t] = a.pool[sweep_model_src_elem(a.tab[q], a.pred_len, s, j)];       // (t = sr_dst_elem(d, s, j, q))
+}
+
+// k_loop_sample_rows for a loop with a sample count per slot: the step's raw tensor holds the first a.d.S samples only
+// (the largest count among the loop's slots), read out of a source of S_src >= a.d.S samples a row.
+template <class V>
+__global__ __launch_bounds__(SR_THREADS) void k_loop_sample_rows_prefix(LoopSampleRows a, int32_t S_src)
+{
+    const int64_t t = (int64_t)blockIdx.x * SR_THREADS + threadIdx.x;
+    if (t >= sr_step_elems(a.d)) return;
+    int32_t s, j, q;
+    sr_split(a.d, t, s, j, q);
+    SampleRecDims src = a.d;
+    src.S = S_src;
+    ((V *)a.out)[t] = ((const V *)a.rec)[sr_src_elem(src, s, j, a.col[q])];
 }
 
 }  // namespace
@@ -575,6 +671,29 @@ k_loop_best_sample_sweep_wide(const int32_t *__restrict__ slot_of, FrameDev f, c
     best_sample_episode<FOT_MAX_PLAN_SAMPLES>(slot_of, f, dyn, S, n_dense, dev_tab, dev_stride, best_tab, best_host);
 }
 
+// The sweep forms with a sample count per slot (fot_loop_set_slot_samples): episode i chooses among its own ep_S[i]
+// samples -- one scalar load, uniform for the workgroup.  The shape of the sums is unchanged (lanes over (p, k), a butterfly
+// per (sample, pass, wave), the passes in order, the waves in index order), so a slot chooses what the uniform loop of its
+// count chooses.  The narrow form serves a step whose running counts are all <= FOT_MAX_SAMPLES; dev_tab's rows are
+// dev_stride apart in both.
+__global__ void __launch_bounds__(BS_THREADS)
+k_loop_best_sample_slots(const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn,
+                         const SweepEp *__restrict__ tab, const int32_t *__restrict__ ep_S, int n_run, int n_dense,
+                         double *__restrict__ dev_tab, int dev_stride, int32_t *__restrict__ best_tab, int32_t *best_host)
+{
+    if ((int)blockIdx.x >= n_run || tab[blockIdx.x].select == 0) return;     // (uniform)
+    best_sample_episode<FOT_MAX_SAMPLES>(slot_of, f, dyn, ep_S[blockIdx.x], n_dense, dev_tab, dev_stride, best_tab, best_host);
+}
+
+__global__ void __launch_bounds__(BS_THREADS)
+k_loop_best_sample_slots_wide(const int32_t *__restrict__ slot_of, FrameDev f, const double *__restrict__ dyn,
+                              const SweepEp *__restrict__ tab, const int32_t *__restrict__ ep_S, int n_run, int n_dense,
+                              double *__restrict__ dev_tab, int dev_stride, int32_t *__restrict__ best_tab, int32_t *best_host)
+{
+    if ((int)blockIdx.x >= n_run || tab[blockIdx.x].select == 0) return;     // (uniform)
+    best_sample_episode<FOT_MAX_PLAN_SAMPLES>(slot_of, f, dyn, ep_S[blockIdx.x], n_dense, dev_tab, dev_stride, best_tab, best_host);
+}
+
 // One thread per (row of the frame, evaluation step j): the truth of the step's origins, [rows][E][2], from the resident
 // recording -- row min(f_cur + stride (j + 1), frames - 1) of the pedestrian's slot (a shorter recording holds its last frame).
 __global__ void __launch_bounds__(256)
@@ -654,6 +773,17 @@ k_loop_rep_block_sweep(const int32_t *__restrict__ slot_of, FrameDev f, const do
     const int i = blockIdx.x;
     if (i >= n_run || !sweep_plans_on_block(tab[i])) return;             // (uniform)
     rep_block_episode(slot_of, f, dyn, best_tab, S, n_dense, tensor, tab[i].rep_off, pre_dev, pre_host);
+}
+
+// ... with a sample count per slot: the clamp of the choice and the source's sample stride are the episode's own.
+__global__ void __launch_bounds__(RB_THREADS)
+k_loop_rep_block_slots(const int32_t *__restrict__ slot_of, FrameDev f, const double *dyn, const SweepEp *__restrict__ tab,
+                       const int32_t *__restrict__ ep_S, const int32_t *__restrict__ best_tab, int n_run, int n_dense,
+                       double *tensor, int32_t *__restrict__ pre_dev, int32_t *pre_host)
+{
+    const int i = blockIdx.x;
+    if (i >= n_run || !sweep_plans_on_block(tab[i])) return;             // (uniform)
+    rep_block_episode(slot_of, f, dyn, best_tab, ep_S[i], n_dense, tensor, tab[i].rep_off, pre_dev, pre_host);
 }
 
 // ---------------------------------------------------------------------------
@@ -1127,6 +1257,24 @@ int launch_resample(double sgan_dt, double sim_dt, double staleness, int S, int 
     return 0;
 }
 
+int launch_resample_slots(double sgan_dt, double sim_dt, double staleness, int S_max, int pred_len, int rows, int n_dense,
+                          int n_run, int P_max, const void *pred, int pred_dtype, const double *anchor, const double *current,
+                          double *out, const int32_t *ep_ped0, const int64_t *ep_blk, const int32_t *ep_S, hipStream_t st)
+{
+    if (n_run <= 0 || S_max <= 0 || P_max <= 0 || rows <= 0) return 0;
+    if (S_max > FOT_MAX_PLAN_SAMPLES || pred_len < 1 || pred_len > FOT_MAX_PRED_LEN || n_dense < 1 || !ep_ped0 || !ep_blk || !ep_S)
+        return (int)hipErrorInvalidValue;
+    ResampleSlotsArgs A;
+    A.sgan_dt = sgan_dt; A.sim_dt = sim_dt; A.staleness = staleness;
+    A.pred_len = pred_len; A.rows = rows; A.n_dense = n_dense;
+    A.ep_ped0 = ep_ped0; A.ep_blk = ep_blk; A.ep_S = ep_S;
+    const dim3 grid((unsigned)n_run, (unsigned)S_max, (unsigned)((2 * P_max + RSS_THREADS - 1) / RSS_THREADS));
+    if (pred_dtype == FOT_F32) k_resample_slots<float><<<grid, RSS_THREADS, 0, st>>>(A, (const float *)pred, anchor, current, out);
+    else k_resample_slots<double><<<grid, RSS_THREADS, 0, st>>>(A, (const double *)pred, anchor, current, out);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
 int launch_sample_dist(int S, int P, int T, int skip, const void *out, int out_dtype, int tmajor, double *dist,
                        hipStream_t st)
 {
@@ -1186,6 +1334,18 @@ int launch_loop_sample_rows(const LoopSampleRows &a, hipStream_t st)
     const unsigned grid = (unsigned)((total + SR_THREADS - 1) / SR_THREADS);
     if (a.dtype == FOT_F32) k_loop_sample_rows<float2><<<grid, SR_THREADS, 0, st>>>(a);
     else k_loop_sample_rows<double2><<<grid, SR_THREADS, 0, st>>>(a);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_sample_rows_prefix(const LoopSampleRows &a, int S_src, hipStream_t st)
+{
+    const int64_t total = sr_step_elems(a.d);
+    if (total <= 0) return 0;
+    if (a.d.S > S_src) return (int)hipErrorInvalidValue;             // (the step moves a prefix of the source's samples)
+    const unsigned grid = (unsigned)((total + SR_THREADS - 1) / SR_THREADS);
+    if (a.dtype == FOT_F32) k_loop_sample_rows_prefix<float2><<<grid, SR_THREADS, 0, st>>>(a, S_src);
+    else k_loop_sample_rows_prefix<double2><<<grid, SR_THREADS, 0, st>>>(a, S_src);
     FOT_LAUNCH_CHECK();
     return 0;
 }
@@ -1271,6 +1431,33 @@ int launch_loop_rep_block_sweep(const int32_t *slot_of, FrameDev f, const double
     if (n_run <= 0) return 0;
     if (S < 1 || S > FOT_MAX_PLAN_SAMPLES || n_dense < 1 || !tab) return (int)hipErrorInvalidValue;
     k_loop_rep_block_sweep<<<n_run, RB_THREADS, 0, st>>>(slot_of, f, dyn, tab, best_tab, n_run, S, n_dense, tensor, pre_dev, pre_host);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_best_sample_slots(const int32_t *slot_of, FrameDev f, const double *dyn, const SweepEp *tab, const int32_t *ep_S,
+                                  int n_run, int S_max, int n_dense, double *dev_tab, int dev_stride, int32_t *best_tab,
+                                  int32_t *best_host, hipStream_t st)
+{
+    if (n_run <= 0) return 0;
+    if (S_max < 1 || S_max > FOT_MAX_PLAN_SAMPLES || dev_stride < S_max || n_dense < 1 || !tab || !ep_S) return (int)hipErrorInvalidValue;
+    if (S_max > FOT_MAX_SAMPLES)
+        k_loop_best_sample_slots_wide<<<n_run, BS_THREADS, 0, st>>>(slot_of, f, dyn, tab, ep_S, n_run, n_dense, dev_tab, dev_stride,
+                                                                    best_tab, best_host);
+    else
+        k_loop_best_sample_slots<<<n_run, BS_THREADS, 0, st>>>(slot_of, f, dyn, tab, ep_S, n_run, n_dense, dev_tab, dev_stride,
+                                                               best_tab, best_host);
+    FOT_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_loop_rep_block_slots(const int32_t *slot_of, FrameDev f, const double *dyn, const SweepEp *tab, const int32_t *ep_S,
+                                const int32_t *best_tab, int n_run, int n_dense, double *tensor, int32_t *pre_dev,
+                                int32_t *pre_host, hipStream_t st)
+{
+    if (n_run <= 0) return 0;
+    if (n_dense < 1 || !tab || !ep_S) return (int)hipErrorInvalidValue;
+    k_loop_rep_block_slots<<<n_run, RB_THREADS, 0, st>>>(slot_of, f, dyn, tab, ep_S, best_tab, n_run, n_dense, tensor, pre_dev, pre_host);
     FOT_LAUNCH_CHECK();
     return 0;
 }

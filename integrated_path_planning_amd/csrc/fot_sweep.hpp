@@ -5,9 +5,10 @@
 // addresses its episode's distribution block with S samples or its planning block with one, on the same base pointer.
 // Also the row -> column table of a recording whose columns the slots name themselves (fot_loop_set_samples_shared), and
 // the tables of a sampler step whose slots share their crowds' samples (fot_loop_set_sampler_shared) and name their
-// models (fot_loop_set_sampler_models).
+// models (fot_loop_set_sampler_models), and the ragged layout of a sweep whose slots keep sample counts of their own
+// (fot_loop_set_slot_samples).
 // Plain C++ shared by the kernels (k_loop_best_sample_sweep, k_loop_rep_block_sweep, k_loop_model_rows), the host (fot_host_loop.cpp) and
-// tests/emu/fot_sweep_emu.cpp.  Every offset into the tensor counts points of two coordinates in 64 bits.
+// tests/emu/fot_sweep_emu.cpp, tests/emu/fot_slot_samples_emu.cpp.  Every offset into the tensor counts points of two coordinates in 64 bits.
 #pragma once
 
 #include <algorithm>
@@ -58,6 +59,46 @@ inline int64_t sweep_layout(int32_t n_run, const int32_t *ep_ped0, const int32_t
 
 // The most points a step of a resident sweep loop can need: every slot running, S samples, n_cols pedestrians in all.
 FOT_SW_HD inline int64_t sweep_capacity_points(int32_t S, int64_t n_cols, int32_t T) { return ((int64_t)S + 1) * n_cols * T; }
+
+// ---- a sample count per slot (fot_loop_set_slot_samples) -------------------------------------------------------------------------
+// Slot e plans against the first slot_S[e] samples of what the loop's source provides.  Running episode i then keeps a
+// block [S_i][P_i][T][2], the blocks packed by prefix sum; the planning blocks follow behind them as sweep_layout places
+// them (dist_end = what sweep_slot_blocks returns).  The counts live in a table of their own, [n_run], beside the SweepEp
+// rows: SweepEp stays as it is.
+
+// ep_S [n_run]: the count of every running episode of the frame (ep_slot == nullptr: episode i is slot i).  Returns the
+// largest of them (0 for no episode).
+inline int32_t sweep_slot_counts(int32_t n_run, const int32_t *ep_slot, const int32_t *slot_S, int32_t *ep_S)
+{
+    int32_t most = 0;
+    for (int32_t i = 0; i < n_run; ++i) {
+        ep_S[i] = slot_S[ep_slot ? ep_slot[i] : i];
+        most = std::max(most, ep_S[i]);
+    }
+    return most;
+}
+
+// points of the distribution block of an episode of S samples, P pedestrians and T time entries
+FOT_SW_HD inline int64_t sweep_slot_block_points(int32_t S, int32_t P, int32_t T) { return (int64_t)S * P * T; }
+
+// blk [n_run + 1]: first point of every running episode's distribution block, blk[n_run] (returned) the points of them all.
+// With every count equal to S this is the uniform frame's table (LoopState::blk_off).
+inline int64_t sweep_slot_blocks(int32_t n_run, const int32_t *ep_ped0, const int32_t *ep_S, int32_t T, int64_t *blk)
+{
+    blk[0] = 0;
+    for (int32_t i = 0; i < n_run; ++i) blk[i + 1] = blk[i] + sweep_slot_block_points(ep_S[i], ep_ped0[i + 1] - ep_ped0[i], T);
+    return blk[n_run > 0 ? n_run : 0];
+}
+
+// The most points a step of a resident sweep loop with slot counts can need: every slot running, its distribution block
+// and a planning block each.  slot_ped0 [n_slots + 1]: the replay's.  Never more than sweep_capacity_points of the
+// source's S, which is what the loop's tensor was sized with.
+inline int64_t sweep_slot_capacity_points(int32_t n_slots, const int32_t *slot_ped0, const int32_t *slot_S, int32_t T)
+{
+    int64_t pts = 0;
+    for (int32_t e = 0; e < n_slots; ++e) pts += ((int64_t)slot_S[e] + 1) * (slot_ped0[e + 1] - slot_ped0[e]) * T;
+    return pts;
+}
 
 // Frame row -> column of a recording whose slots name their first column themselves: row r of running episode i is
 // column slot_col0[ep_slot[i]] + (r - ep_ped0[i]).  Slots may share, overlap or reverse their columns.

@@ -703,6 +703,20 @@ class BatchPlanner:
             _abi.OUT_DEVICE if on_device else 0))
         self._loop_samples = samples if on_device else None
 
+    def loop_set_slot_samples(self, slot_samples) -> None:
+        """``fot_loop_set_slot_samples``: slot e of a sweep loop uses the first ``slot_samples[e]`` samples of what its
+        source provides (after ``loop_set_samples`` / ``loop_set_sampler`` of a resident loop, before the first step; a
+        stepwise sweep: before its first ``loop_step``, whose frames then carry the source's count)."""
+        counts = np.ascontiguousarray(slot_samples, dtype=np.int32).reshape(-1)
+        _abi.check(self._h, self._lib.fot_loop_set_slot_samples(self._h, len(counts), _addr(counts) if len(counts) else None))
+
+    def debug_loop_slot_samples(self) -> np.ndarray:
+        """``fot_debug_loop_slot_samples`` (tests): the sample count of every running episode of the most recent frame (0:
+        it carried no distribution)."""
+        out = np.full(max(int(self._loop_n), 1), -1, np.int32)
+        _abi.check(self._h, self._lib.fot_debug_loop_slot_samples(self._h, len(out), _addr(out)))
+        return out[out >= 0]
+
     def sgan_noise(self, seed: int, kind: int, num_samples: int, noise_dim: int, row_slot, row_step, row_index, out=None,
                    stream: Optional[int] = None):
         """``fot_sgan_noise``: the counter-based noise [S, rows, noise_dim] of the rows (slot, that slot's step count, index

@@ -335,6 +335,19 @@ def model_scenes(slots, counts, steps, slot_crowd, slot_model):
     return units, row_model, cols
 
 
+def _checked_slot_samples(who: str, slot_samples, num_samples: int):
+    """``slot_samples`` of a sample source as an int64 array (None stays None): one count in 1 .. num_samples per slot."""
+    if slot_samples is None:
+        return None
+    counts = np.asarray(slot_samples)
+    if counts.ndim != 1 or not np.issubdtype(counts.dtype, np.integer):
+        raise ValueError(f"{who}: slot_samples holds one integer sample count per slot")
+    counts = counts.astype(np.int64)
+    if len(counts) and not 1 <= counts.min() <= counts.max() <= int(num_samples):
+        raise ValueError(f"{who}: slot_samples holds one count in 1 .. {int(num_samples)} (num_samples) per slot")
+    return counts
+
+
 class SganSampler:
     """The multi-sample predictor in front of the planner, in the library: ``sample(obs, ped_off)`` gives the raw samples
     [S, pred_len, sum P, 2] of every scene as a float32 ``torch`` device tensor -- what ``fot_loop_frame.dist_raw`` and
@@ -361,12 +374,16 @@ class SganSampler:
     forms the same bytes through ``fot_sgan_sample_model``): a slot's numbers are those of the loop that holds only its model.
     engine None: the sampler joins the engine of the loop it is handed to (``bind``).
     sample_capacity: more than 64 samples, up to ``_abi.MAX_PLAN_SAMPLES`` (254) -- the engine it runs on needs that
-    capacity too (``BatchPlanner(sample_capacity=)``, ``BatchedClosedLoop(sample_capacity=)``)."""
+    capacity too (``BatchPlanner(sample_capacity=)``, ``BatchedClosedLoop(sample_capacity=)``).
+    slot_samples (with ``counter_seed``): one count in 1 .. ``num_samples`` per slot of a sweep loop -- slot e plans against,
+    and is scored on, the FIRST ``slot_samples[e]`` samples of its crowd's draw (``fot_loop_set_slot_samples``): the
+    sample-count ablation as slots of one loop.  ``sample`` still hands over all ``num_samples`` samples; the library takes
+    each slot's prefix."""
     needs_history = True
 
     def __init__(self, engine: Optional[BatchPlanner], weights: SganWeights, num_samples: int, seed: Optional[int] = None,
                  noise_type: Optional[str] = None, counter_seed: Optional[int] = None, slot_crowd=None, slot_model=None,
-                 sample_capacity: int = _abi.MAX_SAMPLES):
+                 sample_capacity: int = _abi.MAX_SAMPLES, slot_samples=None):
         if noise_type is not None and noise_type not in _NOISE_TYPES:
             raise ValueError(f'Unrecognized noise type "{noise_type}"')
         self.sample_capacity = _checked_capacity("SganSampler", sample_capacity)
@@ -401,6 +418,12 @@ class SganSampler:
                 raise ValueError("SganSampler: slot_model and slot_crowd hold one entry per slot")
             if len(self.slot_model) and not 0 <= self.slot_model.min() <= self.slot_model.max() < len(self.models):
                 raise ValueError(f"SganSampler: slot_model holds one model id in 0 .. {len(self.models) - 1} per slot")
+        self.slot_samples = _checked_slot_samples("SganSampler", slot_samples, self.num_samples)
+        if self.slot_samples is not None and self.counter_seed is None:
+            raise ValueError("SganSampler: slot_samples takes every slot's first samples of one draw: it needs counter_seed "
+                             "(the counter noise is keyed by the sample index)")
+        if self.slot_samples is not None and self.slot_crowd is not None and len(self.slot_samples) != len(self.slot_crowd):
+            raise ValueError("SganSampler: slot_samples and slot_crowd hold one entry per slot")
         self._seed = seed
         self._lib = _abi.lib()
         self.device = self.generator = None
@@ -735,11 +758,14 @@ class RecordedSamples:
     several slots may name the same columns: the K conditions of a sweep over one crowd share ONE copy of its samples
     (``fot_loop_set_samples_shared``).  The stepwise call cuts its rows through the same map.
     sample_capacity: more than 64 samples per step, up to ``_abi.MAX_PLAN_SAMPLES`` (254); the loop's engine needs that
-    capacity too (``BatchedClosedLoop(sample_capacity=)``)."""
+    capacity too (``BatchedClosedLoop(sample_capacity=)``).
+    slot_samples: one count in 1 .. S per slot of a sweep loop -- slot e plans against, and is scored on, the FIRST
+    ``slot_samples[e]`` samples of its columns (``fot_loop_set_slot_samples``): the sample-count ablation over ONE recording.
+    The stepwise call still hands over all S samples; the library takes each slot's prefix."""
     needs_history = True
     recorded = True
 
-    def __init__(self, samples, first_step: int = 0, slot_col0=None, sample_capacity: int = _abi.MAX_SAMPLES):
+    def __init__(self, samples, first_step: int = 0, slot_col0=None, sample_capacity: int = _abi.MAX_SAMPLES, slot_samples=None):
         self.sample_capacity = _checked_capacity("RecordedSamples", sample_capacity)
         on_device = hasattr(samples, "data_ptr")
         if on_device:
@@ -764,12 +790,15 @@ class RecordedSamples:
         self.n_steps, self.num_samples, self.pred_len, self.n_cols = (int(v) for v in samples.shape[:4])
         self.ped_off = None                                            # every slot's pedestrian offsets, once a loop is known
         self.slot_col0 = None if slot_col0 is None else np.asarray(slot_col0, dtype=np.int64).reshape(-1)
+        self.slot_samples = _checked_slot_samples("RecordedSamples", slot_samples, self.num_samples)
         self.device_out = on_device                                    # what a stepwise call returns (attach decides)
         self._dev, self._host, self._cols_key, self._cols = None, None, None, None
 
     def attach(self, ped_off, pred_len: int, device_samples: Optional[bool] = None) -> None:
         """Join a loop: its episodes' pedestrian offsets and the configuration's ``pred_len`` must be the recording's."""
         off = np.asarray(ped_off, dtype=np.int64)
+        if self.slot_samples is not None and len(self.slot_samples) != len(off) - 1:
+            raise ValueError(f"RecordedSamples: slot_samples names {len(self.slot_samples)} slots, the loop has {len(off) - 1}")
         if self.slot_col0 is not None:                                # every slot's own column range, not the sum
             if len(self.slot_col0) != len(off) - 1:
                 raise ValueError(f"RecordedSamples: slot_col0 names {len(self.slot_col0)} slots, the loop has {len(off) - 1}")
